@@ -23,6 +23,10 @@ Extra objects on the JSON line:
                the kernel is limited by; `k_shade` carries the same for the one kernel that really is traffic bound.
   cpu_baseline the CPU oracle (a port; the reference cannot be built here) path tracing a centred crop of the same
                frame on the host cores; the crop also yields rmse_vs_oracle
+
+`--dump-outputs DIR` writes what the last timed step computed, the frame a caller receives (rank 0's assembled `Light` image,
+linear radiance, (H, W, 4) float32), as DIR/light.npy.  The inputs are seeded: the same arguments give the same frame, so two
+builds can be compared output for output.  Above 64 MB a fixed seeded sample of pixels is written instead (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -37,8 +41,34 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
 DEFAULT_SAH_TOP = 1  # the library's RT3_OPT_SAH_TOP default (the oracle of the parity leg is built the same way)
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs writes at most this many bytes of .npy files in all
+DUMP_SEED = 0x5EED
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
+
+
+def dump_outputs(out_dir, arrays: dict, cap: int = DUMP_CAP_BYTES) -> list:
+    """Write every (H, W, ...) float32 / float64 array of `arrays` as out_dir/<name>.npy.  When they would take more than `cap`
+    bytes together, the same fixed seeded sample of pixels is written from each one, (n, ...) in ascending pixel order, and
+    beside them pixel_index.npy: the row-major pixel index y * W + x of every sampled row (float64).  Returns the file names."""
+    import numpy as np
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n_px = math.prod(next(iter(arrays.values())).shape[:2])
+    total = sum(a.nbytes for a in arrays.values())
+    header = 128 * (len(arrays) + 1)  # an .npy header is 128 bytes for these shapes
+    if total + header > cap:
+        per_px = total // n_px + 8  # + the float64 index
+        keep = np.random.default_rng(DUMP_SEED).choice(n_px, (cap - header) // per_px, replace=False)
+        keep.sort()
+        arrays = {k: a.reshape(n_px, *a.shape[2:])[keep] for k, a in arrays.items()}
+        arrays["pixel_index"] = keep.astype(np.float64)
+    else:
+        (out / "pixel_index.npy").unlink(missing_ok=True)  # of an earlier, sampled dump into the same directory
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", np.ascontiguousarray(a))
+    return [f"{k}.npy" for k in arrays]
 
 
 def usable_cpus() -> int:
@@ -190,9 +220,12 @@ def main():
     ap.add_argument("--flags", type=int, default=-1, help="GConst.pad[0] feature flags (-1 = the full estimator); experiments only")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-crop", type=str, default="1280x720")  # ~14 s of oracle time on the GPU box's 16 host cores
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame as DIR/light.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
     default_workload = ((args.width, args.height, args.spp, args.bounces, args.detail) == (1920, 1080, 64, 4, 1.0)
@@ -330,6 +363,10 @@ def main():
     dt = time.perf_counter() - t0
     st = pt.ctx.stats()
     pt.ctx.set_option(L.OPT_PROFILE, 0)
+    if args.dump_outputs and rank == 0:
+        # now, before the counting frame below renders into the same `Light` image: on rank 0 it holds the last step's whole frame
+        names = dump_outputs(args.dump_outputs, {"light": pt.light()})
+        print(f"bench.py: --dump-outputs: frame {args.warmup + args.steps - 1} -> {', '.join(names)} in {args.dump_outputs}", file=sys.stderr, flush=True)
 
     rays_local = st.extension_rays + st.shadow_rays
     by_rank = None

@@ -7,7 +7,9 @@ with the tests, 5.17 without -- the iteration is a dependent fetch first and ~23
 tests out of the loop and running them in iterations of their own (3.5 more wave-iterations per 64 rays against 19.8 / 0.9 = 22 now) cannot pay.
 Test infrastructure (uses the oracle): lives under tests/.   RT3_LIBRARY=<variant .so> python tests/experiments/exp_skip_tris.py"""
 import sys, math, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent.parent
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
 import orc
 from raytracer3_amd import scenes, assets
 from raytracer3_amd.render_graph import Context

@@ -1014,6 +1014,38 @@ def test_bench_default_command_prints_the_contract_line():
     assert abs(sum(ms.values()) - d["ms_per_step"]) < 0.05 * d["ms_per_step"]
 
 
+def test_bench_dump_outputs_is_the_last_timed_frame(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the frame its last timed step rendered (frame index warmup + steps - 1): the same bits on
+    two runs with the same arguments, and the same bits as a PathTracer rendering that frame directly."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from raytracer3_amd.renderer import DEFAULT_FLAGS
+
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RT3_DIST_BACKEND", "RT3_SKY_W")}
+    W, H, spp, steps, warmup = 200, 150, 2, 3, 1
+    for d in ("a", "b"):
+        cmd = [sys.executable, str(root / "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu", "--width", str(W), "--height", str(H),
+               "--spp", str(spp), "--detail", "0.3", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=500)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["steps"] == steps
+    a, b = np.load(tmp_path / "a" / "light.npy"), np.load(tmp_path / "b" / "light.npy")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["light.npy"]
+    assert a.dtype == np.float32 and a.shape == (H, W, 4) and a[..., :3].mean() > 0
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    pt = PathTracer((W, H))
+    pt.set_scene(scenes.atrium(0.3), scenes.sky(2048, 1024), assets.load_bluenoise())
+    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    pt.render(pt.make_gconst(cam, spp, 4, frame=warmup + steps - 1, flags=DEFAULT_FLAGS))
+    want = pt.light()
+    pt.close()
+    assert np.array_equal(a.view(np.uint32), want.view(np.uint32))
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """The same command on the real backend (RCCL cannot put two ranks on one GPU): with fewer than N visible devices it must exit
     non-zero with a message, never report a 1-GPU number as the N-GPU point."""

@@ -266,3 +266,42 @@ def test_bench_self_launch_refuses_without_devices():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0 and "no GPU visible" in r.stderr
     assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
+def test_bench_refuses_zero_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: a run with none is refused before any device work."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0", "--no-cpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
+def test_bench_dump_outputs_writes_whole_arrays_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: below the cap every array is written whole; above it, the same seeded pixels of every array (the
+    same ones on every run) and their row-major indices, within the cap."""
+    import bench
+
+    rng = np.random.default_rng(3)
+    light = rng.random((90, 160, 4), dtype=np.float32)
+    depth = rng.random((90, 160), dtype=np.float32)
+    assert bench.dump_outputs(tmp_path / "whole", {"light": light}) == ["light.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "light.npy"), light)
+
+    cap = 40_000
+    for d in ("a", "b"):
+        names = bench.dump_outputs(tmp_path / d, {"light": light, "depth": depth}, cap=cap)
+        assert names == ["light.npy", "depth.npy", "pixel_index.npy"]
+        assert sum((tmp_path / d / n).stat().st_size for n in names) <= cap
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) > 1000 and np.all(np.diff(idx) > 0)
+    i = idx.astype(np.int64)
+    sl, sd = np.load(tmp_path / "a" / "light.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert sl.dtype == sd.dtype == np.float32 and sl.shape == (len(i), 4) and sd.shape == (len(i),)
+    assert np.array_equal(sl, light.reshape(-1, 4)[i]) and np.array_equal(sd, depth.reshape(-1)[i])
+    for n in ("light.npy", "depth.npy", "pixel_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    # a whole dump into a directory that held a sampled one leaves no stale index beside it
+    bench.dump_outputs(tmp_path / "a", {"light": light})
+    assert not (tmp_path / "a" / "pixel_index.npy").exists()
