@@ -123,7 +123,7 @@ typedef struct rt3_stats {
     uint64_t shadow_nodes_visited_lds; /* requested from the vector-memory path (counting mode; default node layout only) */
     double accel_build_ms;       /* host wall clock of the last rt3_accel_build, stream synchronised on both sides */
     uint64_t accel_bulk_copies;  /* host <-> device copies of array size (> 64 KiB) made by rt3_accel_build calls since rt3_stats_reset:
-                                    0 on the default path (the build stays on the GPU; a few KiB of per-geometry tables go up) */
+                                    the build stays on the GPU, so only geometry tables over 64 KiB (many placements) count */
 } rt3_stats;
 
 typedef struct rt3_ctx rt3_ctx;
@@ -150,7 +150,7 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
 #define RT3_OPT_SAH_TOP 11       /* T > 0 (default 1 = binned SAH down to single triangles; collapse 0 / 1 use max(T, leaf size)): the tree above Karras subtrees of at most T triangles is re-linked by binned SAH
                                      (the reference asks its driver for PREFER_FAST_TRACE builds, raytracing.rs:103,131); 0 = plain LBVH */
 #define RT3_OPT_TRACE_BLOCKS 12   /* traversal tuning: persistent workgroups (256 threads) per traversal launch (default 2048 = 8 per CU) */
-#define RT3_OPT_SAH_TOP_DEVICE 13  /* 1 (default): the SAH top is built on the GPU, no bulk copies; 0: on the host (same tree, bit for bit) */
+/* 13: retired (was RT3_OPT_SAH_TOP_DEVICE, the host build of the SAH top); not reused */
 int rt3_set_option(rt3_ctx *ctx, int option, int64_t value);
 
 /* ---- scene upload: DynamicBuffer::push (vulkan/buffer.rs:406-420) into the world buffers of

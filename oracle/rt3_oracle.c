@@ -786,7 +786,7 @@ static int delta_fn(const uint64_t *codes, int n, int i, int j) {
  * "cluster roots" (maximal subtrees of at most T triangles: contiguous Morton ranges); the C - 1 nodes above the C cluster roots
  * are re-linked into a tree built top-down by binned SAH (16 bins on the cluster centroids, cost = half area x triangle count)
  * over the cluster boxes.  Node indices are reused (the top of a binary tree with C leaves has C - 1 nodes), the root stays
- * node 0.  fp32 in a fixed order; the product's host code (rt3_lbvh.hip, sah_top_relink) runs the same algorithm. */
+ * node 0.  fp32 in a fixed order; the product (rt3_sah_top.hip, on the GPU) runs the same algorithm, bit for bit. */
 typedef struct { uint32_t ref, cnt; float mn[3], mx[3]; } sah_cluster;
 static inline float half_area3(const float mn[3], const float mx[3]) {
     float ex = mx[0] - mn[0], ey = mx[1] - mn[1], ez = mx[2] - mn[2];

@@ -120,7 +120,7 @@ struct rt3_ctx {
     int64_t opt_batch_spp = 0;
     bool opt_profile = false, opt_count = false;
     int opt_variant = 0;  // RT3_OPT_EXTEND_VARIANT: reserved for traversal experiments
-    uint32_t opt_leaf_size = 2, opt_node_width = 4, opt_node_quant = 1, opt_collapse = 2, opt_sah_top = 1, opt_sah_device = 1;
+    uint32_t opt_leaf_size = 2, opt_node_width = 4, opt_node_quant = 1, opt_collapse = 2, opt_sah_top = 1;
     int opt_fused_trace = 0;  // 1: k_trace (extension + shadow queue in one launch per bounce)
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
@@ -755,11 +755,6 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             c->opt_sah_top = (uint32_t)value;
             c->accel_built = false;
             return RT3_OK;
-        case RT3_OPT_SAH_TOP_DEVICE:
-            if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "SAH-top device must be 0 (host) or 1 (GPU)");
-            c->opt_sah_device = (uint32_t)value;
-            c->accel_built = false;
-            return RT3_OK;
         case RT3_OPT_FUSED_TRACE:
             if (value < 0 || value > 1) return fail(c, RT3_E_INVALID, "fused trace must be 0 or 1");
             c->opt_fused_trace = (int)value;
@@ -1111,15 +1106,17 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     if (int r = validate_geometry(c, c->h_geoms.data(), c->h_prim_counts.data(), (uint32_t)c->h_geoms.size())) return r;
     HIPC(c, hipStreamSynchronize(c->stream));
     const auto t_build0 = std::chrono::steady_clock::now();
+    // until the rebuild has succeeded: a failed one (the geometry tables reallocated by flatten_world included) must leave
+    // RT3_E_STATE behind, not an empty tree or one that points at freed tables
+    c->accel_built = false;
     if (int r = flatten_world(c)) return r;
-    c->accel_built = false;  // until the rebuild has succeeded: a failed one must leave RT3_E_STATE behind, not an empty tree
     dev_free(c->bvh.nodes);
     dev_free(c->bvh.tris);
     dev_free(c->bvh.tri_shade);
     dev_free(c->bvh.tri_uv);
     dev_free(c->bvh.top);
     hipError_t e = lbvh_build(c->stream, c->d_verts, c->d_indices, c->d_geoms, c->d_prim_geom, c->d_first_prim, c->n_flat_prims, c->opt_leaf_size,
-                              c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->opt_sah_device, c->build_arena, &c->bvh);
+                              c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena, &c->bvh);
     if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
     // worst-case stack use of the near-first walk: (children per node - 1) entries per level above the leaves
@@ -1135,7 +1132,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     }
     HIPC(c, hipStreamSynchronize(c->stream));
     c->stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-    c->stats.accel_bulk_copies += c->bulk_copies + c->bvh.bulk_copies;
+    c->stats.accel_bulk_copies += c->bulk_copies;
     c->bulk_copies = 0;
     c->accel_built = true;
     if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;

@@ -64,6 +64,12 @@ RT3_DEV int wrap_index(int x, int W) {
 }
 RT3_DEV float fmin_sel(float a, float b) { return a < b ? a : b; }
 RT3_DEV float fmax_sel(float a, float b) { return a > b ? a : b; }
+// fp32 <-> uint32 with the same order (so that atomicMin / atomicMax on the uint compute the float min / max): LBVH build, SAH top
+RT3_DEV uint32_t float_to_ordered(float f) {
+    uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+RT3_DEV float ordered_to_float(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 
 // ------------------------------------------------------------------------------------------------ RNG
 // random.slang:5-15

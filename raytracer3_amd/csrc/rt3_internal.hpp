@@ -129,11 +129,15 @@ struct LbvhResult {
     float4* top = nullptr;     // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
-    uint32_t bulk_copies = 0;  // array-sized host <-> device copies this build made (0 on the default path)
 };
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, uint32_t sah_device, BuildArena& arena, LbvhResult* out);
+                      uint32_t sah_top, BuildArena& arena, LbvhResult* out);
+// Binned-SAH top (rt3_sah_top.hip): re-links, in place, the nodes of the Karras tree (left / right / rcnt / pint / pleaf, boxes in nbox)
+// above its subtrees of at most T triangles, and writes the boxes of the re-linked nodes.  *relinked = false (and nothing written) when
+// there are fewer than three such subtrees.  Its scratch comes out of `arena`, after what the caller has taken.
+hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t n, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
+                              const float* lmin, const float* lmax, float* nbox, uint32_t T, BuildArena& arena, bool* relinked);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, float4** top, uint32_t* n_top);
 

@@ -157,24 +157,21 @@ def test_lbvh_sah_top_bit_identical(small, T):
 
 
 @pytest.mark.parametrize("T", [2, 5, 200])
-def test_sah_top_device_and_host_builds_are_identical(small, T):
-    """RT3_OPT_SAH_TOP_DEVICE: the binned-SAH top built on the GPU (default; level-synchronous for big segments, one thread per
-    small one) against the same algorithm on the host, and both against the oracle: every reduction in it is a min, a max or an
-    integer sum and the partitions are stable, so the trees are the same arrays bit for bit."""
+def test_sah_top_device_bit_identical_collapse1(small, T):
+    """The binned-SAH top built on the GPU (level-synchronous for big segments, one thread per small one) under the surface-area
+    collapse, against the oracle's: every reduction in it is a min, a max or an integer sum and the partitions are stable, so the
+    trees are the same arrays bit for bit."""
     mesh, sky, bn, _ = small
-    osc = orc.Scene(mesh, sah_top=T, collapse=1)  # (the host SAH top exists for the surface-area collapse; the cost-driven default always builds on the device)
-    out = []
-    for dev in (1, 0):
-        ctx = Context(0)
-        ctx.set_option(L.OPT_SAH_TOP, T)
-        ctx.set_option(L.OPT_WIDE_COLLAPSE, 1)
-        ctx.set_option(L.OPT_SAH_TOP_DEVICE, dev)
-        ctx.upload_mesh(mesh)
-        ctx.build_accel()
-        out.append((ctx.accel_info(), *ctx.accel_download()))
-        ctx.close()
-    assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
-    assert np.array_equal(out[0][1], osc.nodes()) and np.array_equal(out[0][2], osc.tris())
+    osc = orc.Scene(mesh, sah_top=T, collapse=1)
+    ctx = Context(0)
+    ctx.set_option(L.OPT_SAH_TOP, T)
+    ctx.set_option(L.OPT_WIDE_COLLAPSE, 1)
+    ctx.upload_mesh(mesh)
+    ctx.build_accel()
+    assert ctx.accel_info()[:3] == (osc.n_nodes, osc.n_tris, osc.max_depth)
+    nodes, tris = ctx.accel_download()
+    ctx.close()
+    assert np.array_equal(nodes, osc.nodes()) and np.array_equal(tris, osc.tris())
 
 
 def test_one_context_rebuilds_scenes_of_different_sizes(small, cornell):
@@ -193,11 +190,12 @@ def test_one_context_rebuilds_scenes_of_different_sizes(small, cornell):
     ctx.close()
 
 
-def test_accel_build_stays_on_the_gpu():
+def test_accel_build_makes_no_bulk_copies():
     """the default build (LBVH + device SAH top + four-wide emit) of the 260 k-triangle bench scene moves
     no array between host and device -- counted by the library itself (rt3_stats.accel_bulk_copies), not inferred from a wall clock that
-    a busy box would stretch; the host SAH top (RT3_OPT_SAH_TOP_DEVICE = 0) is the path that does, and the counter sees it.  The build
-    time is reported (5 - 6 ms on an idle box for the cost-driven default, 3 - 4 ms for collapse 1), not asserted."""
+    a busy box would stretch -- and neither does collapse 1 with T = 2.  The counter does see the geometry tables of a world with many
+    placements (over 64 KiB).  The build time is reported (5 - 6 ms on an idle box for the cost-driven default, 3 - 4 ms for collapse 1),
+    not asserted."""
     mesh = scenes.atrium(1.0)
     ctx = Context(0)
     ctx.upload_mesh(mesh)
@@ -209,12 +207,19 @@ def test_accel_build_stays_on_the_gpu():
     assert st.accel_bulk_copies == 0
     assert 0.0 < st.accel_build_ms < 10_000.0
     print(f"rt3_accel_build, {mesh.n_triangles} triangles, warm context: {st.accel_build_ms:.2f} ms")
-    ctx.set_option(L.OPT_SAH_TOP_DEVICE, 0)
-    ctx.set_option(L.OPT_WIDE_COLLAPSE, 1)  # (the cost-driven default always builds on the device; the host SAH top belongs to collapse 1)
+    ctx.set_option(L.OPT_WIDE_COLLAPSE, 1)
     ctx.set_option(L.OPT_SAH_TOP, 2)
     ctx.stats_reset()
     ctx.build_accel()
-    assert ctx.stats().accel_bulk_copies >= 8
+    assert ctx.stats().accel_bulk_copies == 0
+    ctx.close()
+    # positive control: one cornell geometry placed 600 times flattens to 600 x 128 B of geometry tables, more than 64 KiB
+    ctx = Context(0)
+    ctx.upload_mesh(scenes.cornell())
+    ctx.set_instances([(0, 1, _trs((0.0, 0.0, 0.01 * k))) for k in range(600)])
+    ctx.stats_reset()
+    ctx.build_accel()
+    assert ctx.stats().accel_bulk_copies >= 3
     ctx.close()
 
 
@@ -731,6 +736,8 @@ def test_error_behaviour(small):
     assert lib.rt3_image_create(ctx.h, 64, 64, 12345, C.byref(img)) == L.E_INVALID
     assert lib.rt3_image_create(ctx.h, 64, 64, L.FORMAT_R32_SFLOAT, C.byref(img)) == 0
     assert img.value >> 30 == L.TAG_IMAGE
+    # option 13 (the retired host SAH top) is unknown
+    assert lib.rt3_set_option(ctx.h, 13, 0) == L.E_INVALID and lib.rt3_set_option(ctx.h, 13, 1) == L.E_INVALID
     # sky radiance must be finite and non-negative (a NaN would poison every CDF entry after it); the oracle applies the same contract
     for bad_value in (np.nan, np.inf, -1.0):
         bad_sky = np.ones((4, 8, 3), np.float32)
@@ -1170,13 +1177,18 @@ def test_rccl_rendezvous_of_two_processes(tmp_path):
     assert any("uplicate GPU" in o for o in outs), outs[0][-1500:]
 
 
-def test_lbvh_large_scene_bit_identical():
+@pytest.mark.parametrize("collapse,quant,leaf,T", [(2, 1, 2, 1), (2, 2, 8, 1)], ids=["default", "compact_leaf8"])
+def test_lbvh_large_scene_bit_identical(collapse, quant, leaf, T):
     """0.9 M triangles (atrium at 3x tessellation): GPU build (Morton sort, Karras hierarchy, cluster boxes, device SAH top with its
-    tiled levels, collapse, quantisation) against the oracle's arrays, and 100 k rays with their visit counts."""
+    tiled levels, collapse, quantisation) against the oracle's arrays, and 100 k rays with their visit counts.  The default options,
+    and the configuration that takes the most builder scratch (cost-driven collapse, compact 48 B nodes, T = 1): its bound in
+    lbvh_build must hold."""
     mesh = scenes.atrium(3.0)
     assert mesh.n_triangles > 900_000
-    osc = orc.Scene(mesh)
+    osc = orc.Scene(mesh, leaf_size=leaf, quantized=quant, collapse=collapse, sah_top=T)
     ctx = Context(0)
+    for opt, value in ((L.OPT_WIDE_COLLAPSE, collapse), (L.OPT_NODE_QUANT, quant), (L.OPT_LEAF_SIZE, leaf), (L.OPT_SAH_TOP, T)):
+        ctx.set_option(opt, value)
     ctx.upload_mesh(mesh)
     ctx.build_accel()
     assert ctx.accel_info()[:3] == (osc.n_nodes, osc.n_tris, osc.max_depth)
