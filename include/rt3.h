@@ -151,6 +151,8 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
                                      (the reference asks its driver for PREFER_FAST_TRACE builds, raytracing.rs:103,131); 0 = plain LBVH */
 #define RT3_OPT_TRACE_BLOCKS 12   /* traversal tuning: persistent workgroups (256 threads) per traversal launch (default 2048 = 8 per CU) */
 /* 13: retired (was RT3_OPT_SAH_TOP_DEVICE, the host build of the SAH top); not reused */
+#define RT3_OPT_INSTANCE_MODE 14  /* how rt3_accel_build treats instances: 0 = flatten (default), 1 = two-level (shared bottom trees under a top tree; default node
+                                     layout only).  See the instances block below; next rt3_accel_build */
 int rt3_set_option(rt3_ctx *ctx, int option, int64_t value);
 
 /* ---- scene upload: DynamicBuffer::push (vulkan/buffer.rs:406-420) into the world buffers of
@@ -170,12 +172,19 @@ int rt3_scene_set_texture(rt3_ctx *ctx, uint32_t index, const uint8_t *rgba_srgb
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info
  *      turns the shading normal by the instance matrix (hit_logic.slang:23).  Here: n = 0 (the default) places every geometry once
  *      under the identity.  Otherwise instance i places geometries [first, first + count) under its matrix; the same geometry may be
- *      placed many times.  There is no separate top level: rt3_accel_build FLATTENS the instances into world-space triangles
- *      (p' = ((x_axis x + y_axis y) + z_axis z) + w_axis in fp32, glam's transform_point3; identity matrices leave positions
- *      untouched) and builds one tree over them -- the build takes ~3 ms for 260 k triangles and stays on the GPU, so re-building
- *      after an instance moved IS the TLAS update (rt3_stats.accel_build_ms).  Primitive ids reported by hits (gbuffer, rt3_trace_rays)
- *      count through the placed geometries in instance order.  Normals: normalize(M3 * normalize(interpolated)), M3 = upper 3 x 3,
- *      as hit_logic.slang:22-23 writes it (no inverse transpose).  Call before rt3_accel_build; borrowed for the call. ---- */
+ *      placed many times.  Both instance modes (RT3_OPT_INSTANCE_MODE) give the same hits, bit for bit:
+ *       - 0, flatten (default): rt3_accel_build FLATTENS the instances into world-space triangles (p' = ((x_axis x + y_axis y) + z_axis z)
+ *         + w_axis in fp32, glam's transform_point3; identity matrices leave positions untouched) and builds one tree over them -- ~3 ms
+ *         for 260 k triangles on the GPU, so re-building after an instance moved IS the TLAS update (rt3_stats.accel_build_ms);
+ *       - 1, two-level: one bottom tree per distinct run (first, count), built in object space and shared by its placements, under a
+ *         top tree over the instances' world boxes.  Triangles are still tested in world space, transformed by the same expression,
+ *         so t, u, v and primitive ids equal mode 0's; only the box tests see an object-space ray (with conservatively widened boxes).
+ *         A rebuild after only matrices changed rebuilds the instance records and the top tree, not the meshes (rt3_accel_levels).
+ *         Needs the default node layout (else RT3_E_UNSUPPORTED at build) and an invertible, not too badly conditioned upper 3 x 3
+ *         (else RT3_E_UNSUPPORTED at build); rt3_accel_download / rt3_accel_import are RT3_E_UNSUPPORTED.
+ *      Primitive ids reported by hits (gbuffer, rt3_trace_rays) count through the placed geometries in instance order.  Normals:
+ *      normalize(M3 * normalize(interpolated)), M3 = upper 3 x 3, as hit_logic.slang:22-23 writes it (no inverse transpose).  Call
+ *      before rt3_accel_build; borrowed for the call. ---- */
 int rt3_scene_set_instances(rt3_ctx *ctx, const rt3_instance *instances, uint32_t n);
 
 /* ---- acceleration structure: create_acceleration_structure (vulkan/raytracing.rs:88-148) -> GPU LBVH.
@@ -184,6 +193,11 @@ int rt3_accel_build(rt3_ctx *ctx, uint32_t *out_handle);
 /* introspection for parity tests: copy the BVH to the host (nodes: n_nodes x node_bytes (64 | 128), tris: n_tris x 48 B) */
 int rt3_accel_info(rt3_ctx *ctx, uint32_t *n_nodes, uint32_t *n_tris, uint32_t *max_depth, uint32_t *node_bytes);
 int rt3_accel_download(rt3_ctx *ctx, void *nodes, size_t nodes_bytes, void *tris, size_t tris_bytes);
+/* the levels of the last rt3_accel_build (any pointer may be NULL): distinct bottom trees, how many of them that build (re)built (the rest
+ * were reused), nodes of the top tree, and the device bytes the traversal kernels read (nodes, triangle records, top tree, instance
+ * records; not the shading tables).  Instance mode 0 reports 0, 0, 0 and the flattened tree's bytes.  In mode 1 rt3_accel_info gives the
+ * summed node and triangle counts of both levels and the combined depth. */
+int rt3_accel_levels(rt3_ctx *ctx, uint32_t *n_meshes, uint32_t *n_meshes_built, uint32_t *n_top_nodes, uint64_t *accel_bytes);
 /* the way back: install a tree built elsewhere over the same (flattened) triangles -- a better offline builder, a cache of an earlier run
  * (what vkCmdCopyMemoryToAccelerationStructureKHR is to the reference's driver).  Default layout only (64-byte nodes, 48-byte triangle
  * records, rt3_accel_download's format); call rt3_accel_build first (it makes the shading records).  Every reference is validated on

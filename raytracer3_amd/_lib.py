@@ -19,12 +19,13 @@ FORMAT_R32_SFLOAT, FORMAT_R32G32B32A32_SFLOAT, FORMAT_R32G32B32A32_UINT, FORMAT_
 F_NEE_SKY, F_BLUENOISE, F_SPECULAR, F_FACEFORWARD, F_PROBE_RADIANCE = 1, 2, 4, 8, 16
 OPT_BATCH_SPP, OPT_PROFILE, OPT_COUNT_TRAVERSAL, OPT_EXTEND_VARIANT, OPT_LEAF_SIZE, OPT_NODE_WIDTH, OPT_NODE_QUANT = 1, 2, 3, 4, 5, 6, 7
 OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_FUSED_TRACE, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 10, 11, 12
+OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_instances",
-    "rt3_accel_build", "rt3_accel_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
+    "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
@@ -112,6 +113,7 @@ def load():
         "rt3_scene_set_instances": (i32, [vp, vp, u32]),
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),
+        "rt3_accel_levels": (i32, [vp, pu32, pu32, pu32, C.POINTER(C.c_uint64)]),
         "rt3_accel_download": (i32, [vp, vp, sz, vp, sz]),
         "rt3_accel_import": (i32, [vp, vp, sz, vp, sz]),
         "rt3_sky_download": (i32, [vp, vp, vp, vp, vp]),

@@ -58,6 +58,28 @@ struct CounterBlock {  // device counters of one refrence_mode launch, harvested
     uint32_t first, n_pairs;  // n_pairs x {extension-queue size, shadow-queue size}: one 8-byte pair per bounce (k_shade bumps both with ONE 64-bit atomic)
 };
 
+// RT3_OPT_INSTANCE_MODE 1: what a build keeps for the next one.  The bottom trees live in the combined arrays
+// (rt3_tlas.hip's layout); `meshes` says where, and they are reused while `gen` equals the context's scene generation.
+struct TlMesh {
+    uint32_t first, count;              // the geometry run
+    uint32_t node_off, tri_off;         // in the combined arrays
+    uint32_t n_nodes, n_tris, depth;
+    double box[6];                      // the root's (quantised, conservative) object-space box
+};
+struct TwoLevelState {
+    bool valid = false;                 // c->bvh holds a two-level structure whose bottom trees match `meshes`
+    uint64_t gen = 0;
+    uint32_t head = 0;                  // nodes before the first bottom tree: top capacity + 2 per instance
+    uint32_t n_alloc_nodes = 0;         // nodes of the combined array
+    std::vector<TlMesh> meshes;
+    std::vector<uint32_t> shade_key;    // (first, count) of every instance the shading records were made for
+    uint64_t shade_gen = 0;
+    bool shade_valid = false;
+    uint32_t n_meshes = 0, n_built = 0, n_top = 0;
+    char* scratch = nullptr;            // top build inputs: boxes, degenerate triangles, identity table
+    size_t scratch_cap = 0;
+};
+
 }  // namespace
 
 struct rt3_ctx {
@@ -122,6 +144,9 @@ struct rt3_ctx {
     int opt_variant = 0;  // RT3_OPT_EXTEND_VARIANT: reserved for traversal experiments
     uint32_t opt_leaf_size = 2, opt_node_width = 4, opt_node_quant = 1, opt_collapse = 2, opt_sah_top = 1;
     int opt_fused_trace = 0;  // 1: k_trace (extension + shadow queue in one launch per bounce)
+    int opt_instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
+    uint64_t scene_gen = 1;     // bumped by everything a bottom tree depends on (vertices, indices, geometry, leaf size, collapse, SAH top)
+    TwoLevelState tl;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
     std::vector<Timed> pending_events;
@@ -703,6 +728,7 @@ void rt3_destroy(rt3_ctx* c) {
     dev_free(c->d_tex_pixels); dev_free(c->d_tex_table); dev_free(c->d_srgb_lut);
     dev_free(c->d_sky); dev_free(c->d_sky_alias); dev_free(c->d_cdf_marg); dev_free(c->d_bn);
     dev_free(c->bvh.nodes); dev_free(c->bvh.tris); dev_free(c->bvh.tri_shade); dev_free(c->bvh.tri_uv); dev_free(c->bvh.top); dev_free(c->d_guide_marg);
+    dev_free(c->tl.scratch);
     c->build_arena.release();
     for (auto& r : c->resources)
         if (r.owned && r.ptr) (void)hipFree(r.ptr);
@@ -744,16 +770,19 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             if (value < 1 || value > 8) return fail(c, RT3_E_INVALID, "leaf size must be 1..8");
             c->opt_leaf_size = (uint32_t)value;
             c->accel_built = false;
+            c->scene_gen++;
             return RT3_OK;
         case RT3_OPT_NODE_QUANT:
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "node quantisation must be 0 (fp32), 1 (64 B) or 2 (compact 48 B)");
             c->opt_node_quant = (uint32_t)value;
             c->accel_built = false;
+            c->scene_gen++;
             return RT3_OK;
         case RT3_OPT_SAH_TOP:
             if (value < 0 || value > 65536) return fail(c, RT3_E_INVALID, "SAH-top cluster size must be 0 (off) .. 65536");
             c->opt_sah_top = (uint32_t)value;
             c->accel_built = false;
+            c->scene_gen++;
             return RT3_OK;
         case RT3_OPT_FUSED_TRACE:
             if (value < 0 || value > 1) return fail(c, RT3_E_INVALID, "fused trace must be 0 or 1");
@@ -772,10 +801,17 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "wide collapse must be 0 (even depth), 1 (surface area) or 2 (cost-driven)");
             c->opt_collapse = (uint32_t)value;
             c->accel_built = false;
+            c->scene_gen++;
             return RT3_OK;
         case RT3_OPT_NODE_WIDTH:
             if (value != 2 && value != 4) return fail(c, RT3_E_INVALID, "node width must be 2 or 4");
             c->opt_node_width = (uint32_t)value;
+            c->accel_built = false;
+            c->scene_gen++;
+            return RT3_OK;
+        case RT3_OPT_INSTANCE_MODE:
+            if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "instance mode must be 0 (flatten) or 1 (two-level)");
+            c->opt_instance_mode = (int)value;
             c->accel_built = false;
             return RT3_OK;
         default: return fail(c, RT3_E_INVALID, "unknown option");
@@ -795,6 +831,7 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (n) HIPC(c, hipMemcpy(c->d_verts, v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->n_verts = n;
     c->accel_built = false;
+    c->scene_gen++;
     return RT3_OK;
 }
 int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
@@ -805,6 +842,7 @@ int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
     c->n_indices = n;
     c->h_indices.assign(idx, idx + n);
     c->accel_built = false;
+    c->scene_gen++;
     return RT3_OK;
 }
 // bounds of every geometry's index / vertex range against the world buffers as they are NOW: the kernels index them without
@@ -842,6 +880,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->max_tex_index = max_tex;
     c->n_prims = (uint32_t)total;
     c->accel_built = false;
+    c->scene_gen++;
     return RT3_OK;
 }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
@@ -1097,6 +1136,394 @@ static int flatten_world(rt3_ctx* c) {
     return RT3_OK;
 }
 
+// ---- two-level structure (RT3_OPT_INSTANCE_MODE 1): shared bottom trees under a top tree over instance records
+// Conservativeness of the two-level boxes: every box is grown by kTlPad times a bound on the magnitudes involved,
+// three orders above the rounding it must cover; matrices with ||M3|| ||M3^-1|| above kTlMaxCondition are refused
+constexpr double kTlPad = 1.0 / 4096.0;
+constexpr double kTlMaxCondition = 1048576.0;
+static void tl_reset(rt3_ctx* c) {
+    c->tl.valid = false;
+    c->tl.shade_valid = false;
+    c->tl.meshes.clear();
+    c->tl.n_meshes = c->tl.n_built = c->tl.n_top = 0;
+    c->tl.n_alloc_nodes = 0;
+}
+static void free_accel(rt3_ctx* c) {
+    dev_free(c->bvh.nodes);
+    dev_free(c->bvh.tris);
+    dev_free(c->bvh.tri_shade);
+    dev_free(c->bvh.tri_uv);
+    dev_free(c->bvh.top);
+    c->bvh = LbvhResult{};
+    tl_reset(c);
+}
+static void free_result(LbvhResult& r) {
+    dev_free(r.nodes);
+    dev_free(r.tris);
+    dev_free(r.tri_shade);
+    dev_free(r.tri_uv);
+    dev_free(r.top);
+}
+// the union of the child boxes of a quantised 64-byte node, decoded as the traversal decodes them (origin + q * step), in double
+static void quantised_node_box(const uint32_t* w, double box[6]) {
+    float org[3], step[3];
+    memcpy(org, w, 12);
+    memcpy(&step[0], &w[3], 4);
+    memcpy(&step[1], &w[14], 4);
+    memcpy(&step[2], &w[15], 4);
+    for (int a = 0; a < 3; a++) {
+        box[a] = INFINITY;
+        box[3 + a] = -INFINITY;
+    }
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(w + 4);
+    for (int k = 0; k < 4; k++) {
+        if (w[10 + k] == 0xFFFFFFFFu) continue;
+        for (int a = 0; a < 3; a++) {
+            const double lo = (double)org[a] + (double)bytes[6 * k + a] * (double)step[a], hi = (double)org[a] + (double)bytes[6 * k + 3 + a] * (double)step[a];
+            box[a] = lo < box[a] ? lo : box[a];
+            box[3 + a] = hi > box[3 + a] ? hi : box[3 + a];
+        }
+    }
+}
+// one bottom tree: the geometries [first, first + count) as uploaded (identity table, local primitive ids)
+static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
+    std::vector<FlatGeomDev> tbl(m.count);
+    std::vector<uint32_t> fp(m.count);
+    uint32_t tot = 0;
+    for (uint32_t k = 0; k < m.count; k++) {
+        FlatGeomDev& f = tbl[k];
+        memset(&f, 0, sizeof(f));
+        memcpy(&f.g, &c->h_geoms[m.first + k], sizeof(f.g));
+        f.m[0] = f.m[4] = f.m[8] = 1.0f;
+        f.identity = 1u;
+        f.geom = m.first + k;
+        fp[k] = tot;
+        tot += c->h_prim_counts[m.first + k];
+    }
+    FlatGeomDev* d_tbl = nullptr;
+    uint32_t *d_fp = nullptr, *d_pg = nullptr;
+    hipError_t e = hipMalloc(&d_tbl, tbl.size() * sizeof(FlatGeomDev));
+    if (e == hipSuccess) e = hipMalloc(&d_fp, fp.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_pg, (size_t)m.n_tris * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tbl, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_fp, fp.data(), fp.size() * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_prim_geom(c->stream, d_fp, m.count, m.n_tris, d_pg);
+        e = lbvh_build(c->stream, c->d_verts, c->d_indices, d_tbl, d_pg, d_fp, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse, c->opt_sah_top,
+                       c->build_arena, res);
+    }
+    uint32_t root[16];
+    if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes, 64, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_tbl);
+    (void)hipFree(d_fp);
+    (void)hipFree(d_pg);
+    if (e != hipSuccess) {
+        free_result(*res);
+        return fail(c, RT3_E_HIP, std::string("two-level: bottom tree: ") + hipGetErrorString(e));
+    }
+    m.n_nodes = res->n_nodes;
+    m.depth = res->max_depth;
+    quantised_node_box(root, m.box);
+    return RT3_OK;
+}
+static float round_down(double x) {
+    float f = (float)x;
+    return (double)f > x ? std::nextafter(f, -INFINITY) : f;
+}
+static float round_up(double x) {
+    float f = (float)x;
+    return (double)f < x ? std::nextafter(f, INFINITY) : f;
+}
+
+static int build_two_level(rt3_ctx* c) {
+    if (c->opt_node_width != 4 || c->opt_node_quant != 1)
+        return fail(c, RT3_E_UNSUPPORTED, "instance mode 1 (two-level) needs the default node layout: RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1");
+    TwoLevelState& tl = c->tl;
+    if (!tl.valid) free_accel(c);  // what c->bvh holds is a flattened tree (or nothing)
+    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    rt3_instance whole;
+    whole.geometry_first = 0;
+    whole.geometry_count = c->n_geoms;
+    memcpy(whole.transform, kIdentity, sizeof(kIdentity));
+    const rt3_instance* inst = c->h_instances.empty() ? &whole : c->h_instances.data();
+    const size_t n_inst = c->h_instances.empty() ? 1 : c->h_instances.size();
+
+    // ---- matrices: the inverse (double, then fp32) and its conditioning; meshes = distinct geometry runs that hold triangles
+    struct InstInfo {
+        double A[3][3], b[3];
+        uint32_t mesh, prim_base;
+        bool identity;
+    };
+    std::vector<InstInfo> ii(n_inst);
+    std::vector<TlMesh> meshes;
+    uint32_t total = 0;
+    for (size_t i = 0; i < n_inst; i++) {
+        const float* m = inst[i].transform;
+        double M[3][3];
+        for (int r = 0; r < 3; r++)
+            for (int k = 0; k < 3; k++) M[r][k] = m[4 * k + r];
+        const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+                           M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+        InstInfo& in = ii[i];
+        in.identity = memcmp(m, kIdentity, sizeof(kIdentity)) == 0;
+        if (!(std::fabs(det) > 0.0) || !std::isfinite(1.0 / det))
+            return fail(c, RT3_E_UNSUPPORTED, "instance " + std::to_string(i) + ": the upper 3 x 3 of the transform is singular (instance mode 1 needs its inverse)");
+        const double id = 1.0 / det;
+        in.A[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) * id;
+        in.A[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) * id;
+        in.A[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) * id;
+        in.A[1][0] = (M[1][2] * M[2][0] - M[1][0] * M[2][2]) * id;
+        in.A[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) * id;
+        in.A[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) * id;
+        in.A[2][0] = (M[1][0] * M[2][1] - M[1][1] * M[2][0]) * id;
+        in.A[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) * id;
+        in.A[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) * id;
+        for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) in.A[r][k] = (double)(float)in.A[r][k];  // what the record holds
+            in.b[r] = (double)(float)-(in.A[r][0] * m[12] + in.A[r][1] * m[13] + in.A[r][2] * m[14]);
+        }
+        double nA = 0.0, nM = 0.0;
+        for (int r = 0; r < 3; r++) {
+            nA = std::fmax(nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
+            nM = std::fmax(nM, std::fabs(M[r][0]) + std::fabs(M[r][1]) + std::fabs(M[r][2]));
+        }
+        if (!std::isfinite(nA) || nA * nM > kTlMaxCondition)
+            return fail(c, RT3_E_UNSUPPORTED, "instance " + std::to_string(i) + ": the transform is too badly conditioned for instance mode 1 (||M|| ||M^-1|| > 2^20)");
+        in.prim_base = total;
+        uint32_t cnt = 0;
+        for (uint32_t k = 0; k < inst[i].geometry_count; k++) cnt += c->h_prim_counts[inst[i].geometry_first + k];
+        total += cnt;
+        in.mesh = ~0u;
+        if (cnt == 0) continue;
+        for (size_t q = 0; q < meshes.size(); q++)
+            if (meshes[q].first == inst[i].geometry_first && meshes[q].count == inst[i].geometry_count) in.mesh = (uint32_t)q;
+        if (in.mesh == ~0u) {
+            TlMesh nm;
+            memset(&nm, 0, sizeof(nm));
+            nm.first = inst[i].geometry_first;
+            nm.count = inst[i].geometry_count;
+            nm.n_tris = cnt;
+            in.mesh = (uint32_t)meshes.size();
+            meshes.push_back(nm);
+        }
+    }
+    uint32_t n_ne = 0;  // instances that place triangles: they get records and top-tree leaves, the others are left out
+    for (auto& in : ii) n_ne += in.mesh != ~0u ? 1u : 0u;
+    if (n_ne >= (1u << 26)) return fail(c, RT3_E_UNSUPPORTED, "instance mode 1: too many instances");
+    const uint32_t top_cap = n_ne ? n_ne : 1u;  // a four-wide tree over n leaves has at most max(1, n - 1) nodes
+    const uint32_t head = top_cap + 2u * n_ne;
+
+    // ---- bottom trees: kept while the meshes, the generation and the head are what the last build had
+    bool same = tl.valid && tl.gen == c->scene_gen && tl.head == head && tl.meshes.size() == meshes.size();
+    for (size_t q = 0; same && q < meshes.size(); q++) same = tl.meshes[q].first == meshes[q].first && tl.meshes[q].count == meshes[q].count;
+    tl.n_built = 0;
+    if (same) {
+        meshes = tl.meshes;
+    } else {
+        const bool reuse = tl.valid && tl.gen == c->scene_gen;
+        std::vector<LbvhResult> built(meshes.size());
+        std::vector<int> from(meshes.size(), -1);
+        int rc = RT3_OK;
+        for (size_t q = 0; q < meshes.size() && rc == RT3_OK; q++) {
+            for (size_t o = 0; reuse && o < tl.meshes.size(); o++)
+                if (tl.meshes[o].first == meshes[q].first && tl.meshes[o].count == meshes[q].count) from[q] = (int)o;
+            if (from[q] >= 0) {
+                const TlMesh& om = tl.meshes[from[q]];
+                meshes[q].n_nodes = om.n_nodes;
+                meshes[q].depth = om.depth;
+                memcpy(meshes[q].box, om.box, sizeof(om.box));
+            } else {
+                rc = tl_build_mesh(c, meshes[q], &built[q]);
+                tl.n_built++;
+            }
+        }
+        uint64_t nodes_total = head, tris_total = 0;
+        for (auto& m : meshes) {
+            m.node_off = (uint32_t)nodes_total;
+            m.tri_off = (uint32_t)tris_total;
+            nodes_total += m.n_nodes;
+            tris_total += m.n_tris;
+        }
+        if (rc == RT3_OK && (nodes_total >= (1ull << 29) || tris_total > (1ull << 28)))
+            rc = fail(c, RT3_E_UNSUPPORTED, "instance mode 1: the bottom trees exceed the 28-bit references");
+        float4 *nodes = nullptr, *tris = nullptr;
+        hipError_t e = hipSuccess;
+        if (rc == RT3_OK) {
+            e = hipMalloc(&nodes, (size_t)nodes_total * 64);
+            if (e == hipSuccess) e = hipMalloc(&tris, (size_t)tris_total * 48 + 128);  // + the traversal's over-read slack
+            if (e == hipSuccess) e = hipMemsetAsync((char*)tris + (size_t)tris_total * 48, 0, 128, c->stream);
+            for (size_t q = 0; e == hipSuccess && q < meshes.size(); q++) {
+                const TlMesh& m = meshes[q];
+                if (from[q] >= 0) {
+                    const TlMesh& om = tl.meshes[from[q]];
+                    tlas_rebase_nodes(c->stream, c->bvh.nodes + 4 * (size_t)om.node_off, nodes + 4 * (size_t)m.node_off, m.n_nodes, om.node_off, m.node_off,
+                                      om.tri_off, m.tri_off);
+                    e = hipMemcpyAsync(tris + 3 * (size_t)m.tri_off, c->bvh.tris + 3 * (size_t)om.tri_off, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
+                } else {
+                    tlas_rebase_nodes(c->stream, built[q].nodes, nodes + 4 * (size_t)m.node_off, m.n_nodes, 0u, m.node_off, 0u, m.tri_off);
+                    e = hipMemcpyAsync(tris + 3 * (size_t)m.tri_off, built[q].tris, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
+                }
+            }
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) rc = fail(c, RT3_E_HIP, std::string("two-level: bottom trees: ") + hipGetErrorString(e));
+        }
+        for (auto& r : built) free_result(r);
+        if (rc != RT3_OK) {
+            if (nodes) (void)hipFree(nodes);
+            if (tris) (void)hipFree(tris);
+            free_accel(c);
+            return rc;
+        }
+        dev_free(c->bvh.nodes);
+        dev_free(c->bvh.tris);
+        c->bvh.nodes = nodes;
+        c->bvh.tris = tris;
+        tl.meshes = meshes;
+        tl.head = head;
+        tl.gen = c->scene_gen;
+        tl.n_alloc_nodes = (uint32_t)nodes_total;
+        tl.valid = true;
+    }
+
+    // ---- shading records, per placed triangle in flattened order: they do not depend on the matrices
+    std::vector<uint32_t> key(2 * n_inst);
+    for (size_t i = 0; i < n_inst; i++) {
+        key[2 * i] = inst[i].geometry_first;
+        key[2 * i + 1] = inst[i].geometry_count;
+    }
+    if (!(tl.shade_valid && tl.shade_gen == c->scene_gen && tl.shade_key == key)) {
+        tl.shade_valid = false;
+        if (int r = dev_alloc(c, &c->bvh.tri_shade, (size_t)c->n_flat_prims)) return r;
+        if (int r = dev_alloc(c, &c->bvh.tri_uv, 3 * (size_t)c->n_flat_prims)) return r;
+        launch_tri_shade(c->stream, c->d_verts, c->d_indices, c->d_geoms, c->d_prim_geom, c->d_first_prim, c->n_flat_prims, c->bvh.tri_shade, c->bvh.tri_uv);
+        HIPC(c, hipGetLastError());
+        tl.shade_key = key;
+        tl.shade_gen = c->scene_gen;
+        tl.shade_valid = true;
+    }
+
+    // ---- instance records and world boxes (host, a few KiB), then the top tree (GPU)
+    std::vector<uint32_t> rec((size_t)32 * n_ne);
+    std::vector<float> boxes((size_t)6 * n_ne);
+    uint32_t slot = 0, max_bottom = 0;
+    for (size_t i = 0; i < n_inst; i++) {
+        const InstInfo& in = ii[i];
+        if (in.mesh == ~0u) continue;
+        const TlMesh& ms = meshes[in.mesh];
+        max_bottom = ms.depth > max_bottom ? ms.depth : max_bottom;
+        const float* m = inst[i].transform;
+        double nA = 0.0, nM = 0.0, tM = 0.0, Bobj = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int r = 0; r < 3; r++) {
+            nA = std::fmax(nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
+            nM = std::fmax(nM, std::fabs((double)m[r]) + std::fabs((double)m[4 + r]) + std::fabs((double)m[8 + r]));
+            tM = std::fmax(tM, std::fabs((double)m[12 + r]));
+        }
+        for (int k = 0; k < 6; k++) Bobj = std::fmax(Bobj, std::fabs(ms.box[k]));
+        for (int corner = 0; corner < 8; corner++) {
+            const double p[3] = {ms.box[(corner & 1) ? 3 : 0], ms.box[(corner & 2) ? 4 : 1], ms.box[(corner & 4) ? 5 : 2]};
+            for (int r = 0; r < 3; r++) {
+                const double w = (double)m[r] * p[0] + (double)m[4 + r] * p[1] + (double)m[8 + r] * p[2] + (double)m[12 + r];
+                lo[r] = std::fmin(lo[r], w);
+                hi[r] = std::fmax(hi[r], w);
+            }
+        }
+        double Bw = 0.0;
+        for (int r = 0; r < 3; r++) Bw = std::fmax(Bw, std::fmax(std::fabs(lo[r]), std::fabs(hi[r])));
+        const double widen = kTlPad * (Bw + nM * Bobj + tM);
+        for (int r = 0; r < 3; r++) {
+            boxes[6 * slot + r] = round_down(lo[r] - widen);
+            boxes[6 * slot + 3 + r] = round_up(hi[r] + widen);
+        }
+        uint32_t* a = &rec[32 * (size_t)slot];
+        float fa[12], ff[12];
+        for (int k = 0; k < 3; k++)
+            for (int r = 0; r < 3; r++) fa[3 * k + r] = (float)in.A[r][k];
+        for (int r = 0; r < 3; r++) fa[9 + r] = (float)in.b[r];
+        for (int k = 0; k < 4; k++)
+            for (int r = 0; r < 3; r++) ff[3 * k + r] = m[4 * k + r];
+        memcpy(a, fa, 48);
+        a[12] = ms.node_off;
+        a[13] = (ii[i].prim_base + 0u) | (in.identity ? 0x80000000u : 0u);
+        const float pad_abs = round_up(kTlPad * (nA * (2.0 * Bw + nM * Bobj + tM) + Bobj)), pad_rel = round_up(kTlPad * (2.0 * nA + 1.0));
+        memcpy(&a[14], &pad_abs, 4);
+        memcpy(&a[15], &pad_rel, 4);
+        memcpy(a + 16, ff, 48);
+        slot++;
+    }
+    if (n_ne == 0) {  // nothing placed: every ray misses (the kernels' empty-scene path)
+        dev_free(c->bvh.nodes);
+        dev_free(c->bvh.tris);
+        dev_free(c->bvh.top);
+        tl.valid = false;
+        tl.n_meshes = 0;
+        tl.n_top = 0;
+        c->bvh.n_nodes = c->bvh.n_tris = c->bvh.n_top = 0;
+        c->bvh.max_depth = 0;
+        c->bvh.node_bytes = 64;
+        c->bvh.layout = kLayoutTwoLevel;
+        return RT3_OK;
+    }
+    const size_t rec_bytes = rec.size() * 4;
+    HIPC(c, hipMemcpyAsync(c->bvh.nodes + 4 * (size_t)top_cap, rec.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
+    if (rec_bytes > (64u << 10)) c->bulk_copies += 1;
+    // the top build's inputs: boxes, degenerate triangles, a one-entry identity table, first_prim / prim_geom = 0
+    const size_t off_boxes = 0, off_verts = (n_ne * 24 + 255) & ~(size_t)255, off_idx = off_verts + (((size_t)n_ne * 96 + 255) & ~(size_t)255),
+                 off_tbl = off_idx + (((size_t)n_ne * 12 + 255) & ~(size_t)255), off_pg = off_tbl + 256, need = off_pg + (size_t)n_ne * 4 + 256;
+    if (tl.scratch_cap < need) {
+        dev_free(tl.scratch);
+        tl.scratch_cap = 0;
+        HIPC(c, hipMalloc((void**)&tl.scratch, need));
+        tl.scratch_cap = need;
+    }
+    FlatGeomDev tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.m[0] = tg.m[4] = tg.m[8] = 1.0f;
+    tg.identity = 1u;
+    HIPC(c, hipMemcpyAsync(tl.scratch + off_boxes, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (boxes.size() * 4 > (64u << 10)) c->bulk_copies += 1;
+    HIPC(c, hipMemcpyAsync(tl.scratch + off_tbl, &tg, sizeof(tg), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(tl.scratch + off_pg, 0, (size_t)n_ne * 4 + 4, c->stream));
+    tlas_box_tris(c->stream, (const float*)(tl.scratch + off_boxes), n_ne, (float*)(tl.scratch + off_verts), (uint32_t*)(tl.scratch + off_idx));
+    LbvhResult top;
+    hipError_t e = lbvh_build(c->stream, (const float*)(tl.scratch + off_verts), (const uint32_t*)(tl.scratch + off_idx), (const FlatGeomDev*)(tl.scratch + off_tbl),
+                              (const uint32_t*)(tl.scratch + off_pg), (const uint32_t*)(tl.scratch + off_pg + (size_t)n_ne * 4), n_ne, 1u, 4u, 1u, c->opt_collapse, 1u,
+                              c->build_arena, &top);
+    if (e == hipSuccess && top.n_nodes > top_cap) e = hipErrorInvalidValue;  // cannot happen (see top_cap); never write past the top's region
+    if (e == hipSuccess) {
+        tlas_emit_top(c->stream, top.nodes, top.n_nodes, top.tris, top_cap, c->bvh.nodes);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = lbvh_make_top(c->stream, c->bvh.nodes, tl.n_alloc_nodes, &c->bvh.top, &c->bvh.n_top);
+    const uint32_t top_nodes = top.n_nodes, top_depth = top.max_depth;
+    free_result(top);
+    if (e != hipSuccess) {
+        free_accel(c);
+        return fail(c, RT3_E_HIP, std::string("two-level: top tree: ") + hipGetErrorString(e));
+    }
+    // stack bound: the top walk's entries below the instance leaf, then the bottom walk's (the hand-over pushes nothing)
+    const uint32_t stack_need = (top_depth > 1 ? 3 * (top_depth - 1) : 0) + (max_bottom > 1 ? 3 * (max_bottom - 1) : 0);
+    if (stack_need > kMaxStack) {
+        free_accel(c);
+        return fail(c, RT3_E_DEPTH, "two-level structure needs " + std::to_string(stack_need) + " stack entries (top " + std::to_string(top_depth) +
+                                        " levels + bottom " + std::to_string(max_bottom) + "), the traversal kernels hold " + std::to_string(kMaxStack));
+    }
+    uint32_t bottom_nodes = 0, bottom_tris = 0;
+    for (auto& m : meshes) {
+        bottom_nodes += m.n_nodes;
+        bottom_tris += m.n_tris;
+    }
+    tl.n_meshes = (uint32_t)meshes.size();
+    tl.n_top = top_nodes;
+    c->bvh.n_nodes = top_nodes + bottom_nodes;
+    c->bvh.n_tris = bottom_tris;
+    c->bvh.max_depth = top_depth + max_bottom;
+    c->bvh.node_bytes = 64;
+    c->bvh.layout = kLayoutTwoLevel;
+    return RT3_OK;
+}
+
 // ---- acceleration structure
 int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     if (!c) return RT3_E_INVALID;
@@ -1110,6 +1537,17 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     // RT3_E_STATE behind, not an empty tree or one that points at freed tables
     c->accel_built = false;
     if (int r = flatten_world(c)) return r;
+    if (c->opt_instance_mode == 1) {
+        if (int r = build_two_level(c)) return r;
+        HIPC(c, hipStreamSynchronize(c->stream));
+        c->stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+        c->stats.accel_bulk_copies += c->bulk_copies;
+        c->bulk_copies = 0;
+        c->accel_built = true;
+        if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
+        return RT3_OK;
+    }
+    tl_reset(c);  // (a two-level structure's arrays are c->bvh's: freed just below)
     dev_free(c->bvh.nodes);
     dev_free(c->bvh.tris);
     dev_free(c->bvh.tri_shade);
@@ -1146,8 +1584,21 @@ int rt3_accel_info(rt3_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* ma
     if (node_bytes) *node_bytes = c->bvh.node_bytes;
     return RT3_OK;
 }
+int rt3_accel_levels(rt3_ctx* c, uint32_t* n_meshes, uint32_t* n_meshes_built, uint32_t* n_top_nodes, uint64_t* accel_bytes) {
+    if (!c || !c->accel_built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    const bool two = c->bvh.layout == kLayoutTwoLevel;
+    if (n_meshes) *n_meshes = two ? c->tl.n_meshes : 0u;
+    if (n_meshes_built) *n_meshes_built = two ? c->tl.n_built : 0u;
+    if (n_top_nodes) *n_top_nodes = two ? c->tl.n_top : 0u;
+    if (accel_bytes) {  // what the traversal kernels read: node array (two-level: top tree, instance records, bottom trees), triangle records, LDS top copy
+        const uint64_t nodes = c->bvh.nodes == nullptr ? 0u : (two ? (uint64_t)c->tl.n_alloc_nodes * 64u : (uint64_t)c->bvh.n_nodes * c->bvh.node_bytes);
+        *accel_bytes = nodes + (c->bvh.tris == nullptr ? 0u : (uint64_t)c->bvh.n_tris * 48u) + (uint64_t)c->bvh.n_top * 64u;
+    }
+    return RT3_OK;
+}
 int rt3_accel_download(rt3_ctx* c, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes) {
     if (!c || !c->accel_built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_download: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (nodes) {
         if (nodes_bytes != (size_t)c->bvh.n_nodes * c->bvh.node_bytes) return fail(c, RT3_E_INVALID, "nodes_bytes mismatch");
         if (nodes_bytes) HIPC(c, hipMemcpy(nodes, c->bvh.nodes, nodes_bytes, hipMemcpyDeviceToHost));
@@ -1165,6 +1616,7 @@ int rt3_accel_download(rt3_ctx* c, void* nodes, size_t nodes_bytes, void* tris, 
 int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const void* tris, size_t tris_bytes) {
     if (!c || !nodes || !tris) return fail(c, RT3_E_INVALID, "accel_import: NULL argument");
     if (!c->accel_built) return fail(c, RT3_E_STATE, "accel_import: build the scene's own structure first (rt3_accel_build makes the shading records)");
+    if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (c->bvh.layout != kLayoutWide64Q) return fail(c, RT3_E_UNSUPPORTED, "accel_import: default node layout only");
     if (nodes_bytes == 0 || nodes_bytes % 64 || tris_bytes % 48 || nodes_bytes / 64 > 0x3FFFFFFFull) return fail(c, RT3_E_INVALID, "accel_import: sizes must be multiples of 64 / 48 bytes");
     const uint32_t nn = (uint32_t)(nodes_bytes / 64), nt = (uint32_t)(tris_bytes / 48);

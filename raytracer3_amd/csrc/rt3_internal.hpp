@@ -22,6 +22,7 @@ constexpr int kLayoutWide128 = 1;    // 128 B: four {fp32 min, max, ref, pad} sl
 constexpr int kLayoutWide48Q = 3;    // 48 B: as kLayoutWide64Q, references implied (node_base / tri_base + a nibble per child): 3 loads per node
 constexpr int kC48Stride = 3;        // float4s per compact node
 constexpr int kLayoutWide64Q = 2;    // 64 B: origin + power-of-two steps + four 8-bit boxes + four references
+constexpr int kLayoutTwoLevel = 4;   // RT3_OPT_INSTANCE_MODE 1: kLayoutWide64Q nodes of a top tree over instance records and shared bottom trees (rt3_tlas.hip)
 constexpr uint32_t kMaxStack = 64;         // traversal stack entries: LDS short stack (12) + private spill (52)
 constexpr uint32_t kTopCacheNodes = 128;   // top-of-tree nodes the traversal kernels hold in LDS (8 KiB)
 
@@ -138,6 +139,21 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
 // there are fewer than three such subtrees.  Its scratch comes out of `arena`, after what the caller has taken.
 hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t n, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
                               const float* lmin, const float* lmax, float* nbox, uint32_t T, BuildArena& arena, bool* relinked);
+
+// shading records (tri_shade, tri_uv) of n flattened primitives alone, without a tree (two-level builds: they do not depend on the matrices)
+void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                      const uint32_t* first_prim, uint32_t n, uint4* tri_shade, float2* tri_uv);
+
+// Two-level structure (rt3_tlas.hip).  One node array: [top tree | two 64-byte records per instance | bottom trees], one triangle array of
+// the bottom trees' object-space records (local primitive ids).
+// dst[k] = src[k] with internal references moved from node_from to node_to and leaf references from tri_from to tri_to
+void tlas_rebase_nodes(hipStream_t st, const float4* src, float4* dst, uint32_t n, uint32_t node_from, uint32_t node_to, uint32_t tri_from, uint32_t tri_to);
+// n boxes {lo.xyz, hi.xyz} -> the degenerate triangles (lo, hi, lo) whose bounds they are (8-float vertices, indices 0..3n-1): the top tree is
+// built by lbvh_build over them
+void tlas_box_tris(hipStream_t st, const float* boxes, uint32_t n, float* verts, uint32_t* indices);
+// copy the top tree built over those triangles to dst, its leaf references (one triangle each) now naming instance records:
+// 0x80000000 | (rec_base + 2 * instance slot)
+void tlas_emit_top(hipStream_t st, const float4* top_nodes, uint32_t n_nodes, const float4* top_tris, uint32_t rec_base, float4* dst);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, float4** top, uint32_t* n_top);
 

@@ -31,6 +31,9 @@ constexpr int kSpill = 64 - kLdsStack;  // kLdsStack + kSpill >= kMaxBvhDepth (c
 constexpr uint32_t kMaxSteps = 1u << 20;  // safety bound on traversal steps per ray (a corrupt tree must not hang the GPU)
 
 constexpr uint32_t kEmptySlot = 0xFFFFFFFFu;
+// two-level walk: the boxes of the top tree are widened by kTopPadRel max|o| (the rounding of the slab test itself, which grows with the
+// distance of the origin; the instance boxes carry the rest of the bound)
+constexpr float kTopPadRel = 2.44140625e-4f;  // 2^-12
 
 struct Cand {  // a child slot that the ray enters: entry distance + reference
     float tn;
@@ -115,6 +118,17 @@ __device__ __forceinline__ bool slab_test_sorted(uint32_t p, uint32_t q, V3 A, V
     return tn <= tf;
 }
 
+// the same test on a box widened by pad.{x,y,z} (= P |inv|: a box grown by P on every side) -- the two-level walk's conservative boxes
+__device__ __forceinline__ bool slab_test_sorted_pad(uint32_t p, uint32_t q, V3 A, V3 B, V3 pad, float tmin, float tbest, float& tn_out) {
+    const float nx = __builtin_fmaf((float)(p & 0xFFu), A.x, B.x) - pad.x, ny = __builtin_fmaf((float)((p >> 8) & 0xFFu), A.y, B.y) - pad.y,
+                nz = __builtin_fmaf((float)((p >> 16) & 0xFFu), A.z, B.z) - pad.z, fx = __builtin_fmaf((float)(p >> 24), A.x, B.x) + pad.x,
+                fy = __builtin_fmaf((float)(q & 0xFFu), A.y, B.y) + pad.y, fz = __builtin_fmaf((float)((q >> 8) & 0xFFu), A.z, B.z) + pad.z;
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(nx, ny), __builtin_fmaxf(nz, tmin));
+    const float tf = __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, tbest));
+    tn_out = tn;
+    return tn <= tf;
+}
+
 struct LaneRay {  // traversal state of the ray a lane currently owns
     V3 o, d, inv;
     float tmin, inv_dd;  // inv_dd = 1 / d.d (the triangle test makes no unit-length assumption)
@@ -129,7 +143,12 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // MODE 0: closest hit over one queue; 1: any hit over one queue; 2: both queues in one walk -- the lanes of a wave take
 // extension rays (closest hit) until that pool is dry and shadow rays (any hit) from then on, so the two kinds share a
 // wave for a while and no lane waits for the wave's last extension ray before it starts on shadow rays.
-template <int MODE, bool COUNT, int LAYOUT, typename Finish>
+// TWO: the two-level structure (kLayoutTwoLevel) over the quantised 64-byte node format: node 0 is the root of the top
+// tree, whose leaf references name instance records (0x80000000 | record node, count field 0: in the top tree every leaf is an instance).  A
+// lane that reaches one fetches the record, moves its ray into object space for the box tests of the bottom tree, marks its stack and walks
+// that tree; its triangles are transformed to world space with flattening's own expression and tested against the world ray.  Once the
+// bottom walk has popped down to the mark the lane goes back to the world ray and the top tree's entries.
+template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              const float* __restrict__ rays_a, size_t stride, uint32_t n_a, uint32_t* __restrict__ work_counter_a,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false,
@@ -177,6 +196,27 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
     r.pay0 = r.pay1 = r.pay2 = r.pay3 = 0.0f;
     r.sel_p0 = r.sel_q0 = r.sel_p1 = r.sel_q1 = 0u;
     bool busy = false;
+    // two-level state (TWO only): the origin the box tests use (object space in a bottom tree), the slab widening P |inv| of the
+    // current level, the stack mark of the instance being walked, its record's node and its primitive base | identity << 31
+    V3 tl_o = v3(0.0f, 0.0f, 0.0f), tl_pad = v3(0.0f, 0.0f, 0.0f);
+    uint32_t tl_mark = 0u, tl_rec = 0u, tl_base = 0u;
+    bool tl_bottom = false;
+    // the world level: the ray's own inverses, selectors and widening (ray start, and back from a bottom tree)
+    auto tl_world = [&]() {
+        r.inv = v3(guarded_inverse(r.d.x), guarded_inverse(r.d.y), guarded_inverse(r.d.z));
+        tl_o = r.o;
+        const float pw = kTopPadRel * __builtin_fmaxf(__builtin_fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z));
+        tl_pad = v3(pw * fabsf(r.inv.x), pw * fabsf(r.inv.y), pw * fabsf(r.inv.z));
+        tl_bottom = false;
+    };
+    auto tl_sels = [&]() {  // as at ray start: v_perm_b32 selectors that put a child's near planes first, for the current r.inv
+        const uint32_t sx = r.inv.x < 0.0f ? 1u : 0u, sy = r.inv.y < 0.0f ? 1u : 0u, sz = r.inv.z < 0.0f ? 1u : 0u;
+        const uint32_t nx = 3u * sx, ny = 1u + 3u * sy, nz = 2u + 3u * sz, fx = 3u - 3u * sx, fy = 4u - 3u * sy, fz = 5u - 3u * sz;
+        r.sel_p0 = nx | (ny << 8) | (nz << 16) | (fx << 24);
+        r.sel_q0 = fy | (fz << 8);
+        r.sel_p1 = r.sel_p0 + 0x02020202u;
+        r.sel_q1 = r.sel_q0 + 0x00000202u;
+    };
     for (;;) {
         // ---- refill idle lanes from the pool
         const unsigned long long m_idle = __ballot(!busy);
@@ -237,6 +277,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                     r.sel_q1 = r.sel_q0 + 0x00000202u;
                 }
                 r.cur = (LAYOUT == kLayoutWide64Q && use_top) ? kTopFlag : 0u;  // the root: slot 0 of the LDS copy, or node 0
+                if (TWO) tl_world();
                 r.leaf_k = 0u;
                 r.sp = 0;
                 r.index = idx;
@@ -265,7 +306,10 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
         const bool is_leaf = (r.cur & 0x80000000u) != 0u;
         const uint32_t first = r.cur & 0x0FFFFFFFu, cnt = ((r.cur >> 28) & 7u) + 1u;
         const bool cached = LAYOUT == kLayoutWide64Q && !is_leaf && (r.cur & kTopFlag) != 0u;  // a top-of-tree node held in LDS
-        const float4* p = is_leaf ? tris + 3 * (size_t)(first + r.leaf_k) : nodes + (WIDE ? 8 : (C48 ? kC48Stride : 4)) * (size_t)(cached ? 0u : r.cur);
+        const bool is_inst = TWO && is_leaf && !tl_bottom;  // a leaf of the top tree: the instance record at node `first`
+        const bool is_tri = is_leaf && !is_inst;
+        const float4* p = is_tri ? tris + 3 * (size_t)(first + r.leaf_k)
+                                 : nodes + (WIDE ? 8 : (C48 ? kC48Stride : 4)) * (size_t)(cached ? 0u : (is_inst ? first : r.cur));
         // one batch of loads (the triangle array carries 128 B of slack so that over-reading a leaf is in bounds)
         float4 q0, q1, q2, q3, q4, q5, q6, q7;
         if (LAYOUT == kLayoutWide64Q && cached) {
@@ -286,6 +330,13 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
             q6 = p[6];
             q7 = p[7];
         }
+        if (TWO && is_tri) {  // the instance's forward matrix (the record's second node), in the same batch as the triangle
+            const float4* pm = nodes + 4 * (size_t)(tl_rec + 1u);
+            q4 = pm[0];
+            q5 = pm[1];
+            q6 = pm[2];
+            pin(q4); pin(q5); pin(q6);
+        }
         // pin the fetched registers: without this LLVM sinks the loads only one branch needs into that branch, which
         // turns one memory round trip per step into two
         pin(q0); pin(q1); pin(q2);
@@ -294,9 +345,42 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
         bool pop = false, done = false;
         const V3 o = r.o, d = r.d, inv = r.inv;
         const float tmin = r.tmin;
-        if (is_leaf) {
+        if (TWO && is_inst) {
+            // hand-over: record = {inverse 3 x 4 (words 0..11, FlatGeomDev order), bottom root, prim base | identity << 31, pad_abs, pad_rel}.
+            // The object-space ray (direction not normalised: t keeps its meaning) only steers the bottom tree's box tests.
+            if (COUNT) r.cn++;
+            const float mi[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+            const V3 oo = transform_point(mi, o), dd = transform_vector(mi, d);
+            r.inv = v3(guarded_inverse(dd.x), guarded_inverse(dd.y), guarded_inverse(dd.z));
+            tl_sels();
+            const float om = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(fabsf(o.x), fabsf(o.y)), __builtin_fmaxf(fabsf(o.z), fabsf(oo.x))),
+                                             __builtin_fmaxf(fabsf(oo.y), fabsf(oo.z)));
+            const float pb = __builtin_fmaf(q3.w, om, q3.z);  // P = pad_abs + pad_rel max(|o|, |o'|)
+            tl_pad = v3(pb * fabsf(r.inv.x), pb * fabsf(r.inv.y), pb * fabsf(r.inv.z));
+            tl_o = oo;
+            tl_mark = (uint32_t)r.sp;
+            tl_rec = first;
+            tl_base = __float_as_uint(q3.y);
+            tl_bottom = true;
+            r.cur = __float_as_uint(q3.x);
+        } else if (is_leaf) {
             if (COUNT) r.ct++;
-            tri_test_nb(q0, q1, q2, o, d, r.inv_dd, tmin, r.best);
+            if (TWO) {
+                // world-space triangle: the object-space vertices under the instance's matrix, fetch_triangle's expression (an identity
+                // instance keeps the uploaded bits), and the global primitive id -- the flattened build's record, bit for bit
+                const float fm[12] = {q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, q6.x, q6.y, q6.z, q6.w};
+                V3 a = v3(q0.x, q0.y, q0.z), b = v3(q0.w, q1.x, q1.y), c = v3(q1.z, q1.w, q2.x);
+                if ((tl_base >> 31) == 0u) {
+                    a = transform_point(fm, a);
+                    b = transform_point(fm, b);
+                    c = transform_point(fm, c);
+                }
+                const uint32_t gp = __float_as_uint(q2.y) + (tl_base & 0x7FFFFFFFu);
+                tri_test_nb(make_float4(a.x, a.y, a.z, b.x), make_float4(b.y, b.z, c.x, c.y), make_float4(c.z, __uint_as_float(gp), 0.0f, 0.0f), o, d,
+                            r.inv_dd, tmin, r.best);
+            } else {
+                tri_test_nb(q0, q1, q2, o, d, r.inv_dd, tmin, r.best);
+            }
             r.leaf_k++;
             if (WIDE) {  // the 128 B fetch holds a second triangle
                 if (r.leaf_k < cnt && !(ANY && r.best.prim != kMiss)) {
@@ -329,7 +413,8 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                     const V3 A = C48 ? v3(__uint_as_float((ex & 0xFFu) << 23) * inv.x, __uint_as_float(((ex >> 8) & 0xFFu) << 23) * inv.y,
                                           __uint_as_float(((ex >> 16) & 0xFFu) << 23) * inv.z)
                                      : v3(q0.w * inv.x, q3.z * inv.y, q3.w * inv.z);
-                    const V3 B = v3((q0.x - o.x) * inv.x, (q0.y - o.y) * inv.y, (q0.z - o.z) * inv.z);
+                    const V3 ob = TWO ? tl_o : o;  // two-level: the object-space origin inside a bottom tree
+                    const V3 B = v3((q0.x - ob.x) * inv.x, (q0.y - ob.y) * inv.y, (q0.z - ob.z) * inv.z);
                     const uint32_t w0 = __float_as_uint(q1.x), w1 = __float_as_uint(q1.y), w2 = __float_as_uint(q1.z), w3 = __float_as_uint(q1.w),
                                    w4 = __float_as_uint(q2.x), w5 = __float_as_uint(q2.y);
                     if (C48) {
@@ -361,7 +446,8 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 __builtin_fmaf(lz, A.z, B.z), __builtin_fmaf(hz, A.z, B.z), tmin, r.best.t, tn)
                     if (LAYOUT == kLayoutWide64Q) {
 #define RT3_SLABS(wlo, whi, selp, selq, tn)                                                                                                    \
-    slab_test_sorted(__builtin_amdgcn_perm(whi, wlo, selp), __builtin_amdgcn_perm(whi, wlo, selq), A, B, tmin, r.best.t, tn)
+    (TWO ? slab_test_sorted_pad(__builtin_amdgcn_perm(whi, wlo, selp), __builtin_amdgcn_perm(whi, wlo, selq), A, B, tl_pad, tmin, r.best.t, tn) \
+         : slab_test_sorted(__builtin_amdgcn_perm(whi, wlo, selp), __builtin_amdgcn_perm(whi, wlo, selq), A, B, tmin, r.best.t, tn))
                         h0 = RT3_SLABS(w0, w1, r.sel_p0, r.sel_q0, t0) & (r0 != kEmptySlot);
                         h1 = RT3_SLABS(w1, w2, r.sel_p1, r.sel_q1, t1) & (r1 != kEmptySlot);
                         h2 = RT3_SLABS(w3, w4, r.sel_p0, r.sel_q0, t2) & (r2 != kEmptySlot);
@@ -432,6 +518,10 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
             }
         }
         if (pop && !done) {
+            if (TWO && tl_bottom && (uint32_t)r.sp == tl_mark) {  // the bottom tree is done: back to the world ray and the top tree's entries
+                tl_world();
+                tl_sels();
+            }
             if (r.sp == 0) {
                 done = true;
             } else {
@@ -481,7 +571,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
             tot_l += cl;
         }
     };
-    trace_stream<0, COUNT, LAYOUT>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, nullptr, 0, nullptr, payload != 0, s_top, use_top);
+    trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, nullptr, 0, nullptr, payload != 0, s_top, use_top);
     if (COUNT && totals) {
         atomicAdd(&totals[0], tot_n);
         atomicAdd(&totals[1], tot_t);
@@ -505,7 +595,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
-    trace_stream<1, COUNT, LAYOUT>(
+    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(
         nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, bool, float c_r, float c_g, float c_b, float c_pid) {
             if (occluded_out) {
@@ -549,7 +639,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_trace(const float4* __restrict
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n_ext = *ext_count, n_sh = *sh_count;
     unsigned long long en = 0, et = 0, sn = 0, stt = 0, el = 0, sl = 0;
-    trace_stream<2, COUNT, LAYOUT>(
+    trace_stream<2, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(
         nodes, tris, ext_rays, stride, n_ext, work_ext, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, bool any, float c_r, float c_g, float c_b, float c_pid) {
             if (!any) {
@@ -1116,12 +1206,14 @@ void launch_extend(hipStream_t st, bool count, int layout, const float4* nodes, 
     hipLaunchKernelGGL((k_extend<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr, count_imm, hits, cn, ct, totals, \
                        work_counter, payload ? 1 : 0, totals ? totals + 10 : nullptr /* the context's totals block: [10] = LDS-served visits, closest hit */)
     if (count) {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(true, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_EXTEND(true, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(true, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_EXTEND(true, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_EXTEND(true, kLayoutWide128);
         else RT3_LAUNCH_EXTEND(true, kLayoutBinary64);
     } else {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(false, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_EXTEND(false, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(false, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_EXTEND(false, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_EXTEND(false, kLayoutWide128);
         else RT3_LAUNCH_EXTEND(false, kLayoutBinary64);
@@ -1136,12 +1228,14 @@ void launch_shadow(hipStream_t st, bool count, int layout, const float4* nodes, 
     hipLaunchKernelGGL((k_shadow<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, \
                        lstride, occluded_out, cn, ct, totals, work_counter, totals ? totals + 9 : nullptr /* totals = block + 2 here: block[11] = LDS-served visits, any hit */)
     if (count) {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(true, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_SHADOW(true, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(true, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_SHADOW(true, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_SHADOW(true, kLayoutWide128);
         else RT3_LAUNCH_SHADOW(true, kLayoutBinary64);
     } else {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(false, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_SHADOW(false, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(false, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_SHADOW(false, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_SHADOW(false, kLayoutWide128);
         else RT3_LAUNCH_SHADOW(false, kLayoutBinary64);
@@ -1156,12 +1250,14 @@ void launch_trace(hipStream_t st, bool count, int layout, const float4* nodes, c
     hipLaunchKernelGGL((k_trace<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, ext_rays, sh_rays, stride, ext_count, sh_count, hits, \
                        contrib, lacc, totals, work_ext, work_sh)
     if (count) {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(true, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_TRACE(true, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(true, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_TRACE(true, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_TRACE(true, kLayoutWide128);
         else RT3_LAUNCH_TRACE(true, kLayoutBinary64);
     } else {
-        if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(false, kLayoutWide48Q);
+        if (layout == kLayoutTwoLevel) RT3_LAUNCH_TRACE(false, kLayoutTwoLevel);
+        else if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(false, kLayoutWide48Q);
         else if (layout == kLayoutWide64Q) RT3_LAUNCH_TRACE(false, kLayoutWide64Q);
         else if (layout == kLayoutWide128) RT3_LAUNCH_TRACE(false, kLayoutWide128);
         else RT3_LAUNCH_TRACE(false, kLayoutBinary64);

@@ -133,6 +133,13 @@ __global__ void k_tri_shade(const float* verts, const uint32_t* indices, const F
     }
 }
 
+void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                      const uint32_t* first_prim, uint32_t n, uint4* tri_shade, float2* tri_uv) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + 255) / 256);
+    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, tri_shade, tri_uv);
+}
+
 __device__ __forceinline__ uint64_t expand21(uint32_t v) {
     uint64_t x = v & 0x1FFFFFu;
     x = (x | (x << 32)) & 0x001F00000000FFFFull;

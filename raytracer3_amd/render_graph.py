@@ -208,6 +208,12 @@ class Context:
         self.check(self.lib.rt3_accel_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
+    def accel_levels(self):
+        """(n_meshes, n_meshes_built, n_top_nodes, accel_bytes) of the last build: rt3_accel_levels (instance mode 0: 0, 0, 0, bytes)"""
+        a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self.check(self.lib.rt3_accel_levels(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
     def accel_download(self):
         nn, nt, _, nb = self.accel_info()
         nodes = np.empty((nn, nb // 4), np.uint32)
