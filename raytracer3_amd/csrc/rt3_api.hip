@@ -29,15 +29,15 @@ thread_local std::string g_create_error;
 
 struct Resource {
     uint32_t tag = 0;
-    void* ptr = nullptr;
+    void* ptr = nullptr;    // mem.get(), or the caller's memory for rt3_image_import (never freed here)
+    DevBuf<char> mem;
     size_t bytes = 0;
     uint32_t w = 0, h = 0, format = 0;
-    bool owned = true;
 };
 struct PixelList {
     uint32_t w, h, rank, n_ranks, count;
-    uint32_t* dev;
-    uint2* dev_bn = nullptr;      // {x | y << 16, blue-noise word of that pixel}: one load instead of two dependent ones in k_shade
+    DevBuf<uint32_t> dev;
+    DevBuf<uint2> dev_bn;         // {x | y << 16, blue-noise word of that pixel}: one load instead of two dependent ones in k_shade
     uint64_t bn_stamp = ~0ull;    // which blue-noise upload dev_bn was built from
 };
 // Frame-end gather (north_star: "a single RCCL gather over xGMI at frame end").  The root receives every other rank's tiles
@@ -47,7 +47,7 @@ struct PixelList {
 struct GatherLayout {
     uint32_t w, h, root, n_ranks;
     std::vector<uint64_t> off;  // n_ranks + 1 entries, in pixels
-    uint32_t* dev = nullptr;    // off[n_ranks] pixel words (x | y << 16)
+    DevBuf<uint32_t> dev;       // off[n_ranks] pixel words (x | y << 16)
 };
 enum Cat { CAT_EXTEND = 0, CAT_SHADOW = 1, CAT_SHADE = 2, CAT_OTHER = 3, CAT_TRACE = 4, CAT_GATHER = 5 };
 struct Timed {
@@ -76,7 +76,7 @@ struct TwoLevelState {
     uint64_t shade_gen = 0;
     bool shade_valid = false;
     uint32_t n_meshes = 0, n_built = 0, n_top = 0;
-    char* scratch = nullptr;            // top build inputs: boxes, degenerate triangles, identity table
+    DevBuf<char> scratch;               // top build inputs: boxes, degenerate triangles, identity table
     size_t scratch_cap = 0;
 };
 
@@ -88,30 +88,30 @@ struct rt3_ctx {
     std::string err;
     char name[256] = {0};
     // scene
-    float* d_verts = nullptr;
+    DevBuf<float> d_verts;
     uint32_t n_verts = 0;
-    uint32_t* d_indices = nullptr;
+    DevBuf<uint32_t> d_indices;
     uint32_t n_indices = 0;
-    FlatGeomDev* d_geoms = nullptr;          // one entry per (instance, geometry): built by rt3_accel_build (flatten_world)
-    ShadeGeomDev* d_shade_geoms = nullptr;   // the same table as hit_info reads it
+    DevBuf<FlatGeomDev> d_geoms;             // one entry per (instance, geometry): built by rt3_accel_build (flatten_world)
+    DevBuf<ShadeGeomDev> d_shade_geoms;      // the same table as hit_info reads it
     uint32_t n_geoms = 0, n_prims = 0;       // uploaded geometries / their primitives (one instance of each)
     uint32_t n_flat_geoms = 0, n_flat_prims = 0;  // after flattening: what the acceleration structure and the shading records cover
-    uint32_t *d_prim_geom = nullptr, *d_first_prim = nullptr;
+    DevBuf<uint32_t> d_prim_geom, d_first_prim;
     std::vector<rt3_instance> h_instances;   // empty = one identity instance of every geometry
     uint64_t bulk_copies = 0;                // host <-> device copies of more than 64 KiB made by rt3_accel_build (rt3_stats.accel_bulk_copies)
-    uint2* d_sky = nullptr;  // 8-byte texels {RGB9E5, pdf_uv} in 4 x 4 tiles
-    float* d_cdf_marg = nullptr;
-    uint32_t *d_sky_alias = nullptr, *d_guide_marg = nullptr;
+    DevBuf<uint2> d_sky;  // 8-byte texels {RGB9E5, pdf_uv} in 4 x 4 tiles
+    DevBuf<float> d_cdf_marg;
+    DevBuf<uint32_t> d_sky_alias, d_guide_marg;
     uint32_t sky_w = 0, sky_h = 0, sky_wt = 0;
-    uint8_t* d_bn = nullptr;
+    DevBuf<uint8_t> d_bn;
     uint32_t bn_w = 0, bn_h = 0;
     uint64_t bn_stamp = 0;  // bumped by every rt3_scene_set_bluenoise
     // base-colour textures: host staging (RGBA8) + device atlas rebuilt lazily
     std::vector<std::vector<uint8_t>> h_tex;
     std::vector<uint32_t> tex_w, tex_h;
-    uint8_t* d_tex_pixels = nullptr;
-    uint4* d_tex_table = nullptr;
-    float* d_srgb_lut = nullptr;
+    DevBuf<uint8_t> d_tex_pixels;
+    DevBuf<uint4> d_tex_table;
+    DevBuf<float> d_srgb_lut;
     bool tex_dirty = false;
     LbvhResult bvh;
     BuildArena build_arena;
@@ -120,7 +120,7 @@ struct rt3_ctx {
     std::vector<rt3_geometry_info> h_geoms;
     std::vector<uint32_t> h_prim_counts;
     int64_t max_tex_index = -1;
-    // resources
+    // resources.  A Resource* / PixelList* holds until the next push_back; the device memory they own never moves
     std::vector<Resource> resources;
     std::vector<PixelList> pixlists;
     std::vector<GatherLayout> gather_layouts;
@@ -128,15 +128,15 @@ struct rt3_ctx {
     // communicator of the frame-end gather (RCCL): one rank per context / GPU / process
     ncclComm_t comm = nullptr;
     uint32_t comm_rank = 0, comm_size = 0;
-    void* gather_buf = nullptr;  // non-root: this rank's packed tiles; root: the receive buffer of all other ranks' tiles
+    DevBuf<char> gather_buf;  // non-root: this rank's packed tiles; root: the receive buffer of all other ranks' tiles
     size_t gather_buf_bytes = 0;
     // work queues (capacity in paths)
     size_t cap = 0, cap_pix = 0;
-    float *rays[2] = {nullptr, nullptr}, *hits = nullptr, *T[2] = {nullptr, nullptr};
-    float *sh_rays = nullptr, *sh_contrib = nullptr, *lacc = nullptr, *radsum = nullptr;
-    uint32_t* d_counters = nullptr;
+    DevBuf<float> rays[2], hits, T[2];
+    DevBuf<float> sh_rays, sh_contrib, lacc, radsum;
+    DevBuf<uint32_t> d_counters;
     uint32_t counters_cap = 1 << 16, counters_next = 0;
-    unsigned long long* d_totals = nullptr;
+    DevBuf<unsigned long long> d_totals;
     std::vector<CounterBlock> pending_counters;
     // options / stats
     int64_t opt_batch_spp = 0;
@@ -167,18 +167,9 @@ int fail(rt3_ctx* c, int code, const std::string& msg) {
     } while (0)
 
 template <typename T>
-int dev_alloc(rt3_ctx* c, T** p, size_t count) {
-    if (*p) {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
-    HIPC(c, hipMalloc((void**)p, (count ? count : 1) * sizeof(T)));
+int dev_alloc(rt3_ctx* c, DevBuf<T>& b, size_t count) {
+    HIPC(c, b.alloc_bytes((count ? count : 1) * sizeof(T)));
     return RT3_OK;
-}
-template <typename T>
-void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
 }
 
 uint32_t spread1by1(uint32_t x) {  // math.slang:105-112 integer_explode
@@ -223,10 +214,10 @@ int get_pixlist(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ra
     std::vector<uint32_t> px;
     tile_pixels(w, h, rank, n_ranks, px);
     PixelList pl;
-    pl.w = w; pl.h = h; pl.rank = rank; pl.n_ranks = n_ranks; pl.count = (uint32_t)px.size(); pl.dev = nullptr;
-    HIPC(c, hipMalloc((void**)&pl.dev, (px.size() ? px.size() : 1) * 4));
-    if (!px.empty()) HIPC(c, hipMemcpy(pl.dev, px.data(), px.size() * 4, hipMemcpyHostToDevice));
-    c->pixlists.push_back(pl);
+    pl.w = w; pl.h = h; pl.rank = rank; pl.n_ranks = n_ranks; pl.count = (uint32_t)px.size();
+    HIPC(c, pl.dev.alloc_bytes((px.size() ? px.size() : 1) * 4));
+    if (!px.empty()) HIPC(c, hipMemcpy(pl.dev.get(), px.data(), px.size() * 4, hipMemcpyHostToDevice));
+    c->pixlists.push_back(std::move(pl));
     *out = &c->pixlists.back();
     return RT3_OK;
 }
@@ -250,28 +241,28 @@ size_t format_bytes(uint32_t f) {
 
 SceneDev scene_dev(const rt3_ctx* c) {
     SceneDev s;
-    s.verts = c->d_verts;
-    s.indices = c->d_indices;
-    s.geoms = c->d_geoms;
-    s.shade_geoms = c->d_shade_geoms;
+    s.verts = c->d_verts.get();
+    s.indices = c->d_indices.get();
+    s.geoms = c->d_geoms.get();
+    s.shade_geoms = c->d_shade_geoms.get();
     s.n_geoms = c->n_flat_geoms;
-    s.prim_geom = c->d_prim_geom;
-    s.first_prim = c->d_first_prim;
-    s.tri_shade = c->bvh.tri_shade;
-    s.tri_uv = c->bvh.tri_uv;
-    s.guide_marg = c->d_guide_marg;
-    s.sky = c->d_sky;
-    s.sky_alias = c->d_sky_alias;
-    s.cdf_marg = c->d_cdf_marg;
+    s.prim_geom = c->d_prim_geom.get();
+    s.first_prim = c->d_first_prim.get();
+    s.tri_shade = c->bvh.tri_shade.get();
+    s.tri_uv = c->bvh.tri_uv.get();
+    s.guide_marg = c->d_guide_marg.get();
+    s.sky = c->d_sky.get();
+    s.sky_alias = c->d_sky_alias.get();
+    s.cdf_marg = c->d_cdf_marg.get();
     s.sky_w = c->sky_w;
     s.sky_h = c->sky_h;
     s.sky_wt = c->sky_wt;
-    s.bluenoise = c->d_bn;
+    s.bluenoise = c->d_bn.get();
     s.bn_w = c->bn_w;
     s.bn_h = c->bn_h;
-    s.tex_pixels = c->d_tex_pixels;
-    s.tex_table = c->d_tex_table;
-    s.srgb_lut = c->d_srgb_lut;
+    s.tex_pixels = c->d_tex_pixels.get();
+    s.tex_table = c->d_tex_table.get();
+    s.srgb_lut = c->d_srgb_lut.get();
     s.n_tex = c->d_tex_pixels ? (uint32_t)c->h_tex.size() : 0u;
     return s;
 }
@@ -289,18 +280,18 @@ int sync_textures(rt3_ctx* c) {
     if (total > 0xFFFFFFF0ull) return fail(c, RT3_E_INVALID, "textures exceed 4 GiB");
     std::vector<uint8_t> all(total);
     for (size_t i = 0; i < c->h_tex.size(); i++) memcpy(all.data() + table[i].x, c->h_tex[i].data(), c->h_tex[i].size());
-    if (int r = dev_alloc(c, &c->d_tex_pixels, total)) return r;
-    if (int r = dev_alloc(c, &c->d_tex_table, table.size())) return r;
-    HIPC(c, hipMemcpy(c->d_tex_pixels, all.data(), total, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_tex_table, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    if (int r = dev_alloc(c, c->d_tex_pixels, total)) return r;
+    if (int r = dev_alloc(c, c->d_tex_table, table.size())) return r;
+    HIPC(c, hipMemcpy(c->d_tex_pixels.get(), all.data(), total, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->d_tex_table.get(), table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
     if (!c->d_srgb_lut) {
         float lut[256];
         for (int i = 0; i < 256; i++) {  // sRGB EOTF (IEC 61966-2-1), evaluated in double
             double v = i / 255.0;
             lut[i] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
         }
-        if (int r = dev_alloc(c, &c->d_srgb_lut, (size_t)256)) return r;
-        HIPC(c, hipMemcpy(c->d_srgb_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+        if (int r = dev_alloc(c, c->d_srgb_lut, (size_t)256)) return r;
+        HIPC(c, hipMemcpy(c->d_srgb_lut.get(), lut, sizeof(lut), hipMemcpyHostToDevice));
     }
     c->tex_dirty = false;
     return RT3_OK;
@@ -309,8 +300,8 @@ int sync_textures(rt3_ctx* c) {
 // Failure-atomic: if any allocation fails the whole queue set is released and the capacities drop to 0, so the next pass
 // re-allocates (or reports the error again) instead of launching kernels on a half-resized set.
 void free_work(rt3_ctx* c) {
-    for (int k = 0; k < 2; k++) { dev_free(c->rays[k]); dev_free(c->T[k]); }
-    dev_free(c->hits); dev_free(c->sh_rays); dev_free(c->sh_contrib); dev_free(c->lacc); dev_free(c->radsum);
+    for (int k = 0; k < 2; k++) { c->rays[k].reset(); c->T[k].reset(); }
+    c->hits.reset(); c->sh_rays.reset(); c->sh_contrib.reset(); c->lacc.reset(); c->radsum.reset();
     c->cap = 0;
     c->cap_pix = 0;
 }
@@ -320,18 +311,18 @@ int ensure_work(rt3_ctx* c, size_t paths, size_t npix) {
         size_t P = (paths + 255) & ~(size_t)255;
         c->cap = 0;
         for (int k = 0; k < 2 && !r; k++) {
-            if (!r) r = dev_alloc(c, &c->rays[k], 8 * P);
-            if (!r) r = dev_alloc(c, &c->T[k], 3 * P);  // throughput planes (the path's pdf and id ride in the ray records)
+            if (!r) r = dev_alloc(c, c->rays[k], 8 * P);
+            if (!r) r = dev_alloc(c, c->T[k], 3 * P);  // throughput planes (the path's pdf and id ride in the ray records)
         }
-        if (!r) r = dev_alloc(c, &c->hits, 4 * P);
-        if (!r) r = dev_alloc(c, &c->sh_rays, 8 * P);
-        if (!r) r = dev_alloc(c, &c->sh_contrib, 2 * P);  // {blue contribution, path id} records (red / green ride with the ray)
-        if (!r) r = dev_alloc(c, &c->lacc, 4 * P);        // float4 per path
+        if (!r) r = dev_alloc(c, c->hits, 4 * P);
+        if (!r) r = dev_alloc(c, c->sh_rays, 8 * P);
+        if (!r) r = dev_alloc(c, c->sh_contrib, 2 * P);  // {blue contribution, path id} records (red / green ride with the ray)
+        if (!r) r = dev_alloc(c, c->lacc, 4 * P);        // float4 per path
         if (!r) c->cap = P;
     }
     if (!r && npix > c->cap_pix) {
         c->cap_pix = 0;
-        r = dev_alloc(c, &c->radsum, 3 * npix);
+        r = dev_alloc(c, c->radsum, 3 * npix);
         if (!r) c->cap_pix = npix;
     }
     if (r) free_work(c);
@@ -341,7 +332,7 @@ int ensure_work(rt3_ctx* c, size_t paths, size_t npix) {
 int harvest(rt3_ctx* c) {  // stream must be idle
     if (!c->pending_counters.empty()) {
         std::vector<uint32_t> h(c->counters_next);
-        HIPC(c, hipMemcpy(h.data(), c->d_counters, (size_t)c->counters_next * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(h.data(), c->d_counters.get(), (size_t)c->counters_next * 4, hipMemcpyDeviceToHost));
         for (auto& b : c->pending_counters) {
             for (uint32_t k = 0; k < b.n_pairs; k++) {
                 c->stats.extension_rays += h[b.first + 2 * k];
@@ -355,7 +346,7 @@ int harvest(rt3_ctx* c) {  // stream must be idle
     c->primary_rays_pending = 0;
     if (c->opt_count) {
         unsigned long long t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [0..3] k_extend / k_shadow, [4..9] k_trace {rays, nodes, tris} x 2, [10..11] node visits served by the LDS top-of-tree copy {closest, any}
-        HIPC(c, hipMemcpy(t, c->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(t, c->d_totals.get(), sizeof(t), hipMemcpyDeviceToHost));
         c->stats.nodes_visited += t[0] + t[5];
         c->stats.tris_tested += t[1] + t[6];
         c->stats.shadow_nodes_visited += t[2] + t[8];
@@ -368,7 +359,7 @@ int harvest(rt3_ctx* c) {  // stream must be idle
         c->stats.trace_tris[1] += t[9];
         c->stats.nodes_visited_lds += t[10];
         c->stats.shadow_nodes_visited_lds += t[11];
-        HIPC(c, hipMemset(c->d_totals, 0, sizeof(t)));
+        HIPC(c, hipMemset(c->d_totals.get(), 0, sizeof(t)));
     }
     for (auto& t : c->pending_events) {
         float ms = 0.0f;
@@ -418,7 +409,7 @@ int reserve_counters(rt3_ctx* c, uint32_t n, uint32_t* first) {
     if (n > c->counters_cap) return fail(c, RT3_E_INVALID, "too many bounces x batches for the counter block");
     *first = c->counters_next;
     c->counters_next += n;
-    HIPC(c, hipMemsetAsync(c->d_counters + *first, 0, (size_t)n * 4, c->stream));
+    HIPC(c, hipMemsetAsync(c->d_counters.get() + *first, 0, (size_t)n * 4, c->stream));
     return RT3_OK;
 }
 
@@ -458,19 +449,19 @@ int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const 
     size_t S = c->cap;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_raygen(c->stream, gd, pl->dev, pl->count, c->rays[0], S);
+        launch_raygen(c->stream, gd, pl->dev.get(), pl->count, c->rays[0].get(), S);
     }
     uint32_t wc_slot;
     if (int r = reserve_counters(c, 1, &wc_slot)) return r;  // ray-pool cursor of the launch
     {
         ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, c->rays[0], S, nullptr, pl->count, pl->count, c->hits, nullptr, nullptr,
-                      c->opt_count ? c->d_totals : nullptr, c->d_counters + wc_slot);
+        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[0].get(), S, nullptr, pl->count,
+                      pl->count, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
     }
     c->primary_rays_pending += pl->count;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_gbuffer(c->stream, scene_dev(c), pl->dev, pl->count, W, c->hits, S, gb->ptr, (float*)dp->ptr);
+        launch_gbuffer(c->stream, scene_dev(c), pl->dev.get(), pl->count, W, c->hits.get(), S, gb->ptr, (float*)dp->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -495,8 +486,8 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
     const uint32_t npix = pl->count;
     if (npix == 0) return RT3_OK;
     if (pl->bn_stamp != c->bn_stamp || !pl->dev_bn) {  // (re)build the {pixel, blue-noise word} list of this window / rank
-        if (!pl->dev_bn) HIPC(c, hipMalloc((void**)&pl->dev_bn, (size_t)npix * 8));
-        launch_pixbn(c->stream, pl->dev, npix, c->d_bn, c->bn_w, c->bn_h, pl->dev_bn);
+        if (!pl->dev_bn) HIPC(c, pl->dev_bn.alloc_bytes((size_t)npix * 8));
+        launch_pixbn(c->stream, pl->dev.get(), npix, c->d_bn.get(), c->bn_w, c->bn_h, pl->dev_bn.get());
         pl->bn_stamp = c->bn_stamp;
     }
     // paths per wavefront batch: 160 B of queue state each, so 2^28 paths = 43 GB of the 288 GB; the C3 frame (132.7 M paths)
@@ -518,21 +509,21 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
         if (int r = reserve_counters(c, 4 * B + 1, &first)) return r;
         first += first & 1u;  // 8-byte aligned pairs
         // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
-        uint32_t* pairs = c->d_counters + first;
-        uint32_t* pool_cur = c->d_counters + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
+        uint32_t* pairs = c->d_counters.get() + first;
+        uint32_t* pool_cur = c->d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
         c->pending_counters.push_back(CounterBlock{first, B});
         auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
         auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
         int cur = 0;
         for (uint32_t bn = 0; bn < B; bn++) {
             ShadeLaunch L;
-            L.g = gd; L.sc = sc; L.pixels = pl->dev; L.pixbn = pl->dev_bn; L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
+            L.g = gd; L.sc = sc; L.pixels = pl->dev.get(); L.pixbn = pl->dev_bn.get(); L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
             L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr;
-            L.in_rays = c->rays[cur]; L.in_hits = c->hits; L.in_T = c->T[cur];
+            L.in_rays = c->rays[cur].get(); L.in_hits = c->hits.get(); L.in_T = c->T[cur].get();
             L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
-            L.out_rays = c->rays[cur ^ 1]; L.out_T = c->T[cur ^ 1]; L.out_count = ext_cnt_at(bn);
-            L.sh_rays = c->sh_rays; L.sh_contrib = c->sh_contrib; L.sh_count = sh_cnt_at(bn);
-            L.lacc = c->lacc; L.stride = S; L.max_n = n_first;
+            L.out_rays = c->rays[cur ^ 1].get(); L.out_T = c->T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
+            L.sh_rays = c->sh_rays.get(); L.sh_contrib = c->sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
+            L.lacc = c->lacc.get(); L.stride = S; L.max_n = n_first;
             {
                 ScopedTimer t(c, CAT_SHADE);
                 launch_shade(c->stream, bn == 0, L);
@@ -545,24 +536,26 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
             const bool fuse = c->opt_fused_trace == 1;
             if (nee && bn != B - 1 && fuse) {
                 ScopedTimer t(c, CAT_TRACE);
-                launch_trace(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, c->rays[cur], c->sh_rays, S, ext_cnt_at(bn), sh_cnt_at(bn), n_first,
-                             c->hits, c->sh_contrib, c->lacc, c->opt_count ? c->d_totals + 4 : nullptr, pool_cur + bn, pool_cur + B + bn);
+                launch_trace(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), c->sh_rays.get(), S,
+                             ext_cnt_at(bn), sh_cnt_at(bn), n_first, c->hits.get(), c->sh_contrib.get(), c->lacc.get(), c->opt_count ? c->d_totals.get() + 4 : nullptr,
+                             pool_cur + bn, pool_cur + B + bn);
             } else {
                 if (nee) {
                     ScopedTimer t(c, CAT_SHADOW);
-                    launch_shadow(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, c->sh_rays, S, sh_cnt_at(bn), 0, n_first, c->sh_contrib, nullptr,
-                                  c->lacc, S, nullptr, nullptr, nullptr, c->opt_count ? c->d_totals + 2 : nullptr, pool_cur + B + bn);
+                    launch_shadow(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->sh_rays.get(), S, sh_cnt_at(bn), 0,
+                                  n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S, nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() + 2 : nullptr,
+                                  pool_cur + B + bn);
                 }
                 if (bn != B - 1) {
                     ScopedTimer t(c, CAT_EXTEND);
-                    launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, c->rays[cur], S, ext_cnt_at(bn), 0, n_first, c->hits, nullptr, nullptr,
-                                  c->opt_count ? c->d_totals : nullptr, pool_cur + bn, true);
+                    launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), S, ext_cnt_at(bn), 0,
+                                  n_first, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
                 }
             }
         }
         {
             ScopedTimer t(c, CAT_OTHER);
-            launch_accumulate(c->stream, gd, pl->dev, npix, W, (const float*)dp->ptr, c->lacc, S, nsb, s0 == 0, s0 + nsb >= Sspp, c->radsum, li->ptr,
+            launch_accumulate(c->stream, gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->lacc.get(), S, nsb, s0 == 0, s0 + nsb >= Sspp, c->radsum.get(), li->ptr,
                               pv->ptr);
         }
     }
@@ -587,7 +580,7 @@ int pass_postprocess(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, ui
     GConstDev gd;
     memcpy(&gd, g, sizeof(gd));
     ScopedTimer t(c, CAT_OTHER);
-    launch_postprocess(c->stream, gd, scene_dev(c), pl->dev, pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
+    launch_postprocess(c->stream, gd, scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -638,19 +631,19 @@ int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, c
     const size_t S = c->cap;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_probe_raygen(c->stream, gd, W, x / 8, y / 8, (const float*)dp->ptr, dir->ptr, at->ptr, c->rays[0], S, c->T[0]);
+        launch_probe_raygen(c->stream, gd, W, x / 8, y / 8, (const float*)dp->ptr, dir->ptr, at->ptr, c->rays[0].get(), S, c->T[0].get());
     }
     uint32_t wc_slot;
     if (int r = reserve_counters(c, 1, &wc_slot)) return r;
     {
         ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, c->rays[0], S, nullptr, n, n, c->hits, nullptr, nullptr,
-                      c->opt_count ? c->d_totals : nullptr, c->d_counters + wc_slot);
+        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[0].get(), S, nullptr, n, n, c->hits.get(),
+                      nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
     }
     c->primary_rays_pending += n;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, x / 8, y / 8, c->hits, c->T[0], pv->ptr, at->ptr);
+        launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, x / 8, y / 8, c->hits.get(), c->T[0].get(), pv->ptr, at->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -711,9 +704,9 @@ int rt3_create(int device, rt3_ctx** out) {
     c->device = device;
     snprintf(c->name, sizeof(c->name), "%s (%s)", prop.name, prop.gcnArchName);
     memset(&c->stats, 0, sizeof(c->stats));
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&c->d_counters, (size_t)c->counters_cap * 4) != hipSuccess ||
-        hipMalloc((void**)&c->d_totals, 96) != hipSuccess || hipMemset(c->d_totals, 0, 96) != hipSuccess) {
-        delete c;
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || c->d_counters.alloc_bytes((size_t)c->counters_cap * 4) != hipSuccess ||
+        c->d_totals.alloc_bytes(96) != hipSuccess || hipMemset(c->d_totals.get(), 0, 96) != hipSuccess) {
+        rt3_destroy(c);  // the stream too
         return fail(nullptr, RT3_E_HIP, "stream / counter allocation failed");
     }
     *out = c;
@@ -723,28 +716,13 @@ int rt3_create(int device, rt3_ctx** out) {
 void rt3_destroy(rt3_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    dev_free(c->d_verts); dev_free(c->d_indices); dev_free(c->d_geoms); dev_free(c->d_shade_geoms); dev_free(c->d_prim_geom); dev_free(c->d_first_prim);
-    dev_free(c->d_tex_pixels); dev_free(c->d_tex_table); dev_free(c->d_srgb_lut);
-    dev_free(c->d_sky); dev_free(c->d_sky_alias); dev_free(c->d_cdf_marg); dev_free(c->d_bn);
-    dev_free(c->bvh.nodes); dev_free(c->bvh.tris); dev_free(c->bvh.tri_shade); dev_free(c->bvh.tri_uv); dev_free(c->bvh.top); dev_free(c->d_guide_marg);
-    dev_free(c->tl.scratch);
-    c->build_arena.release();
-    for (auto& r : c->resources)
-        if (r.owned && r.ptr) (void)hipFree(r.ptr);
-    for (auto& p : c->pixlists) {
-        (void)hipFree(p.dev);
-        (void)hipFree(p.dev_bn);
-    }
-    free_work(c);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);  // no device memory is freed before the stream is idle
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    dev_free(c->gather_buf);
-    for (auto& gl : c->gather_layouts) (void)hipFree(gl.dev);
-    dev_free(c->d_counters); dev_free(c->d_totals);
     for (auto& t : c->pending_events) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     for (auto& t : c->free_events) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    hipStream_t stream = c->stream;
+    delete c;  // releases every device buffer the context owns
+    if (stream) (void)hipStreamDestroy(stream);  // the stream goes last
 }
 
 const char* rt3_last_error(rt3_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -827,8 +805,8 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
         for (int k = 0; k < 3; k++)
             if (!(std::fabs(v[8 * i + k]) <= 1.0e18f)) return fail(c, RT3_E_INVALID, "vertex " + std::to_string(i) + ": position is not finite (or beyond 1e18)");
     HIPC(c, hipSetDevice(c->device));
-    if (int r = dev_alloc(c, &c->d_verts, (size_t)n * 8)) return r;
-    if (n) HIPC(c, hipMemcpy(c->d_verts, v, (size_t)n * 32, hipMemcpyHostToDevice));
+    if (int r = dev_alloc(c, c->d_verts, (size_t)n * 8)) return r;
+    if (n) HIPC(c, hipMemcpy(c->d_verts.get(), v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->n_verts = n;
     c->accel_built = false;
     c->scene_gen++;
@@ -837,8 +815,8 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
 int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
     if (!c || (!idx && n)) return fail(c, RT3_E_INVALID, "indices NULL");
     HIPC(c, hipSetDevice(c->device));
-    if (int r = dev_alloc(c, &c->d_indices, (size_t)n)) return r;
-    if (n) HIPC(c, hipMemcpy(c->d_indices, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (int r = dev_alloc(c, c->d_indices, (size_t)n)) return r;
+    if (n) HIPC(c, hipMemcpy(c->d_indices.get(), idx, (size_t)n * 4, hipMemcpyHostToDevice));
     c->n_indices = n;
     c->h_indices.assign(idx, idx + n);
     c->accel_built = false;
@@ -1004,14 +982,14 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
             memcpy(&pb, &pdf[(size_t)y * w + x], 4);
             tiled[((size_t)(y >> 2) * wt + (x >> 2)) * 16 + (((y & 3u) << 2) | (x & 3u))] = make_uint2(texq[(size_t)y * w + x], pb);
         }
-    if (int r = dev_alloc(c, &c->d_guide_marg, gmarg.size())) return r;
-    if (int r = dev_alloc(c, &c->d_sky_alias, alias.size())) return r;
-    if (int r = dev_alloc(c, &c->d_sky, tiled.size())) return r;
-    if (int r = dev_alloc(c, &c->d_cdf_marg, margp.size())) return r;
-    HIPC(c, hipMemcpy(c->d_guide_marg, gmarg.data(), gmarg.size() * 4, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_sky_alias, alias.data(), alias.size() * 4, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_sky, tiled.data(), tiled.size() * 8, hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_cdf_marg, margp.data(), margp.size() * 4, hipMemcpyHostToDevice));
+    if (int r = dev_alloc(c, c->d_guide_marg, gmarg.size())) return r;
+    if (int r = dev_alloc(c, c->d_sky_alias, alias.size())) return r;
+    if (int r = dev_alloc(c, c->d_sky, tiled.size())) return r;
+    if (int r = dev_alloc(c, c->d_cdf_marg, margp.size())) return r;
+    HIPC(c, hipMemcpy(c->d_guide_marg.get(), gmarg.data(), gmarg.size() * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->d_sky_alias.get(), alias.data(), alias.size() * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->d_sky.get(), tiled.data(), tiled.size() * 8, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->d_cdf_marg.get(), margp.data(), margp.size() * 4, hipMemcpyHostToDevice));
     c->sky_w = w;
     c->sky_h = h;
     c->sky_wt = wt;
@@ -1020,8 +998,8 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
 int rt3_scene_set_bluenoise(rt3_ctx* c, const uint8_t* rgba, uint32_t w, uint32_t h) {
     if (!c || !rgba || !w || !h) return fail(c, RT3_E_INVALID, "bluenoise NULL / empty");
     HIPC(c, hipSetDevice(c->device));
-    if (int r = dev_alloc(c, &c->d_bn, (size_t)w * h * 4)) return r;
-    HIPC(c, hipMemcpy(c->d_bn, rgba, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    if (int r = dev_alloc(c, c->d_bn, (size_t)w * h * 4)) return r;
+    HIPC(c, hipMemcpy(c->d_bn.get(), rgba, (size_t)w * h * 4, hipMemcpyHostToDevice));
     c->bn_w = w;
     c->bn_h = h;
     c->bn_stamp++;
@@ -1044,11 +1022,11 @@ int rt3_scene_set_texture(rt3_ctx* c, uint32_t index, const uint8_t* rgba, uint3
 int rt3_sky_download(rt3_ctx* c, uint32_t* alias, uint32_t* texels, float* marg, float* pdf) {
     if (!c || !c->d_sky) return fail(c, RT3_E_STATE, "no sky set");
     const uint32_t w = c->sky_w, h = c->sky_h, wt = c->sky_wt, ht = (h + 3) / 4;
-    if (alias) HIPC(c, hipMemcpy(alias, c->d_sky_alias, (size_t)w * h * 4, hipMemcpyDeviceToHost));
-    if (marg) HIPC(c, hipMemcpy(marg, c->d_cdf_marg + 1, (size_t)h * 4, hipMemcpyDeviceToHost));  // strip the padding
+    if (alias) HIPC(c, hipMemcpy(alias, c->d_sky_alias.get(), (size_t)w * h * 4, hipMemcpyDeviceToHost));
+    if (marg) HIPC(c, hipMemcpy(marg, c->d_cdf_marg.get() + 1, (size_t)h * 4, hipMemcpyDeviceToHost));  // strip the padding
     if (texels || pdf) {  // un-tile
         std::vector<uint2> tiled((size_t)wt * ht * 16);
-        HIPC(c, hipMemcpy(tiled.data(), c->d_sky, tiled.size() * 8, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(tiled.data(), c->d_sky.get(), tiled.size() * 8, hipMemcpyDeviceToHost));
         for (uint32_t y = 0; y < h; y++)
             for (uint32_t x = 0; x < w; x++) {
                 const uint2 t = tiled[((size_t)(y >> 2) * wt + (x >> 2)) * 16 + (((y & 3u) << 2) | (x & 3u))];
@@ -1119,16 +1097,16 @@ static int flatten_world(rt3_ctx* c) {
         }
     }
     const size_t nf = flat.size();
-    if (int r = dev_alloc(c, &c->d_geoms, nf)) return r;
-    if (int r = dev_alloc(c, &c->d_shade_geoms, nf)) return r;
-    if (int r = dev_alloc(c, &c->d_first_prim, nf)) return r;
-    if (int r = dev_alloc(c, &c->d_prim_geom, (size_t)total)) return r;
+    if (int r = dev_alloc(c, c->d_geoms, nf)) return r;
+    if (int r = dev_alloc(c, c->d_shade_geoms, nf)) return r;
+    if (int r = dev_alloc(c, c->d_first_prim, nf)) return r;
+    if (int r = dev_alloc(c, c->d_prim_geom, (size_t)total)) return r;
     if (nf) {
-        HIPC(c, hipMemcpy(c->d_geoms, flat.data(), nf * sizeof(FlatGeomDev), hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(c->d_shade_geoms, shade.data(), nf * sizeof(ShadeGeomDev), hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(c->d_first_prim, first.data(), nf * 4, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->d_geoms.get(), flat.data(), nf * sizeof(FlatGeomDev), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->d_shade_geoms.get(), shade.data(), nf * sizeof(ShadeGeomDev), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->d_first_prim.get(), first.data(), nf * 4, hipMemcpyHostToDevice));
         if (nf * sizeof(FlatGeomDev) > (64u << 10)) c->bulk_copies += 3;
-        launch_prim_geom(c->stream, c->d_first_prim, (uint32_t)nf, (uint32_t)total, c->d_prim_geom);
+        launch_prim_geom(c->stream, c->d_first_prim.get(), (uint32_t)nf, (uint32_t)total, c->d_prim_geom.get());
         HIPC(c, hipGetLastError());
     }
     c->n_flat_geoms = (uint32_t)nf;
@@ -1149,20 +1127,8 @@ static void tl_reset(rt3_ctx* c) {
     c->tl.n_alloc_nodes = 0;
 }
 static void free_accel(rt3_ctx* c) {
-    dev_free(c->bvh.nodes);
-    dev_free(c->bvh.tris);
-    dev_free(c->bvh.tri_shade);
-    dev_free(c->bvh.tri_uv);
-    dev_free(c->bvh.top);
     c->bvh = LbvhResult{};
     tl_reset(c);
-}
-static void free_result(LbvhResult& r) {
-    dev_free(r.nodes);
-    dev_free(r.tris);
-    dev_free(r.tri_shade);
-    dev_free(r.tri_uv);
-    dev_free(r.top);
 }
 // the union of the child boxes of a quantised 64-byte node, decoded as the traversal decodes them (origin + q * step), in double
 static void quantised_node_box(const uint32_t* w, double box[6]) {
@@ -1200,28 +1166,22 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
         fp[k] = tot;
         tot += c->h_prim_counts[m.first + k];
     }
-    FlatGeomDev* d_tbl = nullptr;
-    uint32_t *d_fp = nullptr, *d_pg = nullptr;
-    hipError_t e = hipMalloc(&d_tbl, tbl.size() * sizeof(FlatGeomDev));
-    if (e == hipSuccess) e = hipMalloc(&d_fp, fp.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_pg, (size_t)m.n_tris * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tbl, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_fp, fp.data(), fp.size() * 4, hipMemcpyHostToDevice, c->stream);
+    DevBuf<FlatGeomDev> d_tbl;
+    DevBuf<uint32_t> d_fp, d_pg;
+    hipError_t e = d_tbl.alloc_bytes(tbl.size() * sizeof(FlatGeomDev));
+    if (e == hipSuccess) e = d_fp.alloc_bytes(fp.size() * 4);
+    if (e == hipSuccess) e = d_pg.alloc_bytes((size_t)m.n_tris * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tbl.get(), tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_fp.get(), fp.data(), fp.size() * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_prim_geom(c->stream, d_fp, m.count, m.n_tris, d_pg);
-        e = lbvh_build(c->stream, c->d_verts, c->d_indices, d_tbl, d_pg, d_fp, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse, c->opt_sah_top,
-                       c->build_arena, res);
+        launch_prim_geom(c->stream, d_fp.get(), m.count, m.n_tris, d_pg.get());
+        e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), d_tbl.get(), d_pg.get(), d_fp.get(), m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
+                       c->opt_sah_top, c->build_arena, res);
     }
     uint32_t root[16];
-    if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes, 64, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_tbl);
-    (void)hipFree(d_fp);
-    (void)hipFree(d_pg);
-    if (e != hipSuccess) {
-        free_result(*res);
-        return fail(c, RT3_E_HIP, std::string("two-level: bottom tree: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("two-level: bottom tree: ") + hipGetErrorString(e));
     m.n_nodes = res->n_nodes;
     m.depth = res->max_depth;
     quantised_node_box(root, m.box);
@@ -1347,39 +1307,35 @@ static int build_two_level(rt3_ctx* c) {
         }
         if (rc == RT3_OK && (nodes_total >= (1ull << 29) || tris_total > (1ull << 28)))
             rc = fail(c, RT3_E_UNSUPPORTED, "instance mode 1: the bottom trees exceed the 28-bit references");
-        float4 *nodes = nullptr, *tris = nullptr;
+        DevBuf<float4> nodes, tris;
         hipError_t e = hipSuccess;
         if (rc == RT3_OK) {
-            e = hipMalloc(&nodes, (size_t)nodes_total * 64);
-            if (e == hipSuccess) e = hipMalloc(&tris, (size_t)tris_total * 48 + 128);  // + the traversal's over-read slack
-            if (e == hipSuccess) e = hipMemsetAsync((char*)tris + (size_t)tris_total * 48, 0, 128, c->stream);
+            e = nodes.alloc_bytes((size_t)nodes_total * 64);
+            if (e == hipSuccess) e = tris.alloc_bytes((size_t)tris_total * 48 + 128);  // + the traversal's over-read slack
+            if (e == hipSuccess) e = hipMemsetAsync((char*)tris.get() + (size_t)tris_total * 48, 0, 128, c->stream);
             for (size_t q = 0; e == hipSuccess && q < meshes.size(); q++) {
                 const TlMesh& m = meshes[q];
                 if (from[q] >= 0) {
                     const TlMesh& om = tl.meshes[from[q]];
-                    tlas_rebase_nodes(c->stream, c->bvh.nodes + 4 * (size_t)om.node_off, nodes + 4 * (size_t)m.node_off, m.n_nodes, om.node_off, m.node_off,
-                                      om.tri_off, m.tri_off);
-                    e = hipMemcpyAsync(tris + 3 * (size_t)m.tri_off, c->bvh.tris + 3 * (size_t)om.tri_off, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
+                    tlas_rebase_nodes(c->stream, c->bvh.nodes.get() + 4 * (size_t)om.node_off, nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, om.node_off,
+                                      m.node_off, om.tri_off, m.tri_off);
+                    e = hipMemcpyAsync(tris.get() + 3 * (size_t)m.tri_off, c->bvh.tris.get() + 3 * (size_t)om.tri_off, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice,
+                                       c->stream);
                 } else {
-                    tlas_rebase_nodes(c->stream, built[q].nodes, nodes + 4 * (size_t)m.node_off, m.n_nodes, 0u, m.node_off, 0u, m.tri_off);
-                    e = hipMemcpyAsync(tris + 3 * (size_t)m.tri_off, built[q].tris, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
+                    tlas_rebase_nodes(c->stream, built[q].nodes.get(), nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, 0u, m.node_off, 0u, m.tri_off);
+                    e = hipMemcpyAsync(tris.get() + 3 * (size_t)m.tri_off, built[q].tris.get(), (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
                 }
             }
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) rc = fail(c, RT3_E_HIP, std::string("two-level: bottom trees: ") + hipGetErrorString(e));
         }
-        for (auto& r : built) free_result(r);
         if (rc != RT3_OK) {
-            if (nodes) (void)hipFree(nodes);
-            if (tris) (void)hipFree(tris);
             free_accel(c);
             return rc;
         }
-        dev_free(c->bvh.nodes);
-        dev_free(c->bvh.tris);
-        c->bvh.nodes = nodes;
-        c->bvh.tris = tris;
+        c->bvh.nodes = std::move(nodes);
+        c->bvh.tris = std::move(tris);
         tl.meshes = meshes;
         tl.head = head;
         tl.gen = c->scene_gen;
@@ -1395,9 +1351,10 @@ static int build_two_level(rt3_ctx* c) {
     }
     if (!(tl.shade_valid && tl.shade_gen == c->scene_gen && tl.shade_key == key)) {
         tl.shade_valid = false;
-        if (int r = dev_alloc(c, &c->bvh.tri_shade, (size_t)c->n_flat_prims)) return r;
-        if (int r = dev_alloc(c, &c->bvh.tri_uv, 3 * (size_t)c->n_flat_prims)) return r;
-        launch_tri_shade(c->stream, c->d_verts, c->d_indices, c->d_geoms, c->d_prim_geom, c->d_first_prim, c->n_flat_prims, c->bvh.tri_shade, c->bvh.tri_uv);
+        if (int r = dev_alloc(c, c->bvh.tri_shade, (size_t)c->n_flat_prims)) return r;
+        if (int r = dev_alloc(c, c->bvh.tri_uv, 3 * (size_t)c->n_flat_prims)) return r;
+        launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
+                         c->bvh.tri_shade.get(), c->bvh.tri_uv.get());
         HIPC(c, hipGetLastError());
         tl.shade_key = key;
         tl.shade_gen = c->scene_gen;
@@ -1453,9 +1410,9 @@ static int build_two_level(rt3_ctx* c) {
         slot++;
     }
     if (n_ne == 0) {  // nothing placed: every ray misses (the kernels' empty-scene path)
-        dev_free(c->bvh.nodes);
-        dev_free(c->bvh.tris);
-        dev_free(c->bvh.top);
+        c->bvh.nodes.reset();
+        c->bvh.tris.reset();
+        c->bvh.top.reset();
         tl.valid = false;
         tl.n_meshes = 0;
         tl.n_top = 0;
@@ -1466,38 +1423,37 @@ static int build_two_level(rt3_ctx* c) {
         return RT3_OK;
     }
     const size_t rec_bytes = rec.size() * 4;
-    HIPC(c, hipMemcpyAsync(c->bvh.nodes + 4 * (size_t)top_cap, rec.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->bvh.nodes.get() + 4 * (size_t)top_cap, rec.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
     if (rec_bytes > (64u << 10)) c->bulk_copies += 1;
     // the top build's inputs: boxes, degenerate triangles, a one-entry identity table, first_prim / prim_geom = 0
     const size_t off_boxes = 0, off_verts = (n_ne * 24 + 255) & ~(size_t)255, off_idx = off_verts + (((size_t)n_ne * 96 + 255) & ~(size_t)255),
                  off_tbl = off_idx + (((size_t)n_ne * 12 + 255) & ~(size_t)255), off_pg = off_tbl + 256, need = off_pg + (size_t)n_ne * 4 + 256;
     if (tl.scratch_cap < need) {
-        dev_free(tl.scratch);
         tl.scratch_cap = 0;
-        HIPC(c, hipMalloc((void**)&tl.scratch, need));
+        HIPC(c, tl.scratch.alloc_bytes(need));
         tl.scratch_cap = need;
     }
+    char* const scr = tl.scratch.get();
     FlatGeomDev tg;
     memset(&tg, 0, sizeof(tg));
     tg.m[0] = tg.m[4] = tg.m[8] = 1.0f;
     tg.identity = 1u;
-    HIPC(c, hipMemcpyAsync(tl.scratch + off_boxes, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(scr + off_boxes, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (boxes.size() * 4 > (64u << 10)) c->bulk_copies += 1;
-    HIPC(c, hipMemcpyAsync(tl.scratch + off_tbl, &tg, sizeof(tg), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(tl.scratch + off_pg, 0, (size_t)n_ne * 4 + 4, c->stream));
-    tlas_box_tris(c->stream, (const float*)(tl.scratch + off_boxes), n_ne, (float*)(tl.scratch + off_verts), (uint32_t*)(tl.scratch + off_idx));
+    HIPC(c, hipMemcpyAsync(scr + off_tbl, &tg, sizeof(tg), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(scr + off_pg, 0, (size_t)n_ne * 4 + 4, c->stream));
+    tlas_box_tris(c->stream, (const float*)(scr + off_boxes), n_ne, (float*)(scr + off_verts), (uint32_t*)(scr + off_idx));
     LbvhResult top;
-    hipError_t e = lbvh_build(c->stream, (const float*)(tl.scratch + off_verts), (const uint32_t*)(tl.scratch + off_idx), (const FlatGeomDev*)(tl.scratch + off_tbl),
-                              (const uint32_t*)(tl.scratch + off_pg), (const uint32_t*)(tl.scratch + off_pg + (size_t)n_ne * 4), n_ne, 1u, 4u, 1u, c->opt_collapse, 1u,
+    hipError_t e = lbvh_build(c->stream, (const float*)(scr + off_verts), (const uint32_t*)(scr + off_idx), (const FlatGeomDev*)(scr + off_tbl),
+                              (const uint32_t*)(scr + off_pg), (const uint32_t*)(scr + off_pg + (size_t)n_ne * 4), n_ne, 1u, 4u, 1u, c->opt_collapse, 1u,
                               c->build_arena, &top);
     if (e == hipSuccess && top.n_nodes > top_cap) e = hipErrorInvalidValue;  // cannot happen (see top_cap); never write past the top's region
     if (e == hipSuccess) {
-        tlas_emit_top(c->stream, top.nodes, top.n_nodes, top.tris, top_cap, c->bvh.nodes);
+        tlas_emit_top(c->stream, top.nodes.get(), top.n_nodes, top.tris.get(), top_cap, c->bvh.nodes.get());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = lbvh_make_top(c->stream, c->bvh.nodes, tl.n_alloc_nodes, &c->bvh.top, &c->bvh.n_top);
+    if (e == hipSuccess) e = lbvh_make_top(c->stream, c->bvh.nodes.get(), tl.n_alloc_nodes, c->bvh.top, &c->bvh.n_top);
     const uint32_t top_nodes = top.n_nodes, top_depth = top.max_depth;
-    free_result(top);
     if (e != hipSuccess) {
         free_accel(c);
         return fail(c, RT3_E_HIP, std::string("two-level: top tree: ") + hipGetErrorString(e));
@@ -1547,26 +1503,21 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
         if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
         return RT3_OK;
     }
-    tl_reset(c);  // (a two-level structure's arrays are c->bvh's: freed just below)
-    dev_free(c->bvh.nodes);
-    dev_free(c->bvh.tris);
-    dev_free(c->bvh.tri_shade);
-    dev_free(c->bvh.tri_uv);
-    dev_free(c->bvh.top);
-    hipError_t e = lbvh_build(c->stream, c->d_verts, c->d_indices, c->d_geoms, c->d_prim_geom, c->d_first_prim, c->n_flat_prims, c->opt_leaf_size,
-                              c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena, &c->bvh);
+    free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
+    hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
+                              c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena, &c->bvh);
     if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
-    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
+    if (e != hipSuccess) {
+        free_accel(c);  // (what the failed build allocated)
+        return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
+    }
     // worst-case stack use of the near-first walk: (children per node - 1) entries per level above the leaves
     const uint32_t stack_need = c->bvh.max_depth > 1 ? (c->opt_node_width - 1) * (c->bvh.max_depth - 1) : 0;
     if (stack_need > kMaxStack) {
-        dev_free(c->bvh.nodes);
-        dev_free(c->bvh.tris);
-        dev_free(c->bvh.tri_shade);
-        dev_free(c->bvh.tri_uv);
-        dev_free(c->bvh.top);
-        return fail(c, RT3_E_DEPTH, "LBVH with " + std::to_string(c->bvh.max_depth) + " levels needs " + std::to_string(stack_need) +
-                                        " stack entries, the traversal kernels hold " + std::to_string(kMaxStack));
+        const int rc = fail(c, RT3_E_DEPTH, "LBVH with " + std::to_string(c->bvh.max_depth) + " levels needs " + std::to_string(stack_need) +
+                                                " stack entries, the traversal kernels hold " + std::to_string(kMaxStack));
+        free_accel(c);  // (after the message: it clears max_depth)
+        return rc;
     }
     HIPC(c, hipStreamSynchronize(c->stream));
     c->stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
@@ -1591,8 +1542,8 @@ int rt3_accel_levels(rt3_ctx* c, uint32_t* n_meshes, uint32_t* n_meshes_built, u
     if (n_meshes_built) *n_meshes_built = two ? c->tl.n_built : 0u;
     if (n_top_nodes) *n_top_nodes = two ? c->tl.n_top : 0u;
     if (accel_bytes) {  // what the traversal kernels read: node array (two-level: top tree, instance records, bottom trees), triangle records, LDS top copy
-        const uint64_t nodes = c->bvh.nodes == nullptr ? 0u : (two ? (uint64_t)c->tl.n_alloc_nodes * 64u : (uint64_t)c->bvh.n_nodes * c->bvh.node_bytes);
-        *accel_bytes = nodes + (c->bvh.tris == nullptr ? 0u : (uint64_t)c->bvh.n_tris * 48u) + (uint64_t)c->bvh.n_top * 64u;
+        const uint64_t nodes = !c->bvh.nodes ? 0u : (two ? (uint64_t)c->tl.n_alloc_nodes * 64u : (uint64_t)c->bvh.n_nodes * c->bvh.node_bytes);
+        *accel_bytes = nodes + (!c->bvh.tris ? 0u : (uint64_t)c->bvh.n_tris * 48u) + (uint64_t)c->bvh.n_top * 64u;
     }
     return RT3_OK;
 }
@@ -1601,11 +1552,11 @@ int rt3_accel_download(rt3_ctx* c, void* nodes, size_t nodes_bytes, void* tris, 
     if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_download: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (nodes) {
         if (nodes_bytes != (size_t)c->bvh.n_nodes * c->bvh.node_bytes) return fail(c, RT3_E_INVALID, "nodes_bytes mismatch");
-        if (nodes_bytes) HIPC(c, hipMemcpy(nodes, c->bvh.nodes, nodes_bytes, hipMemcpyDeviceToHost));
+        if (nodes_bytes) HIPC(c, hipMemcpy(nodes, c->bvh.nodes.get(), nodes_bytes, hipMemcpyDeviceToHost));
     }
     if (tris) {
         if (tris_bytes != (size_t)c->bvh.n_tris * 48) return fail(c, RT3_E_INVALID, "tris_bytes mismatch");
-        if (tris_bytes) HIPC(c, hipMemcpy(tris, c->bvh.tris, tris_bytes, hipMemcpyDeviceToHost));
+        if (tris_bytes) HIPC(c, hipMemcpy(tris, c->bvh.tris.get(), tris_bytes, hipMemcpyDeviceToHost));
     }
     return RT3_OK;
 }
@@ -1650,25 +1601,19 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     if (3u * (depth - 1) > kMaxStack) return fail(c, RT3_E_DEPTH, "accel_import: the tree is deeper than the traversal stack supports");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    float4 *d_nodes = nullptr, *d_tris = nullptr;
-    HIPC(c, hipMalloc(&d_nodes, nodes_bytes));
-    hipError_t e = hipMalloc(&d_tris, tris_bytes + 128);  // (the walk over-reads a leaf's last record by up to 128 bytes)
-    if (e == hipSuccess) e = hipMemset(d_tris, 0, tris_bytes + 128);
-    if (e == hipSuccess) e = hipMemcpy(d_nodes, nodes, nodes_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && tris_bytes) e = hipMemcpy(d_tris, tris, tris_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_tris);
-        return fail(c, RT3_E_HIP, std::string("accel_import: ") + hipGetErrorString(e));
-    }
-    dev_free(c->bvh.nodes);
-    dev_free(c->bvh.tris);
-    c->bvh.nodes = d_nodes;
-    c->bvh.tris = d_tris;
+    DevBuf<float4> d_nodes, d_tris;
+    HIPC(c, d_nodes.alloc_bytes(nodes_bytes));
+    hipError_t e = d_tris.alloc_bytes(tris_bytes + 128);  // (the walk over-reads a leaf's last record by up to 128 bytes)
+    if (e == hipSuccess) e = hipMemset(d_tris.get(), 0, tris_bytes + 128);
+    if (e == hipSuccess) e = hipMemcpy(d_nodes.get(), nodes, nodes_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tris_bytes) e = hipMemcpy(d_tris.get(), tris, tris_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_import: ") + hipGetErrorString(e));
+    c->bvh.nodes = std::move(d_nodes);
+    c->bvh.tris = std::move(d_tris);
     c->bvh.n_nodes = nn;
     c->bvh.n_tris = nt;
     c->bvh.max_depth = depth;
-    e = lbvh_make_top(c->stream, c->bvh.nodes, nn, &c->bvh.top, &c->bvh.n_top);
+    e = lbvh_make_top(c->stream, c->bvh.nodes.get(), nn, c->bvh.top, &c->bvh.n_top);
     if (e != hipSuccess) {
         c->accel_built = false;
         return fail(c, RT3_E_HIP, std::string("accel_import: top-of-tree copy: ") + hipGetErrorString(e));
@@ -1683,9 +1628,10 @@ int rt3_buffer_create(rt3_ctx* c, size_t bytes, uint32_t* out) {
     Resource r;
     r.tag = RT3_TAG_BUFFER;
     r.bytes = bytes;
-    HIPC(c, hipMalloc(&r.ptr, bytes));
+    HIPC(c, r.mem.alloc_bytes(bytes));
+    r.ptr = r.mem.get();
     HIPC(c, hipMemset(r.ptr, 0, bytes));
-    c->resources.push_back(r);
+    c->resources.push_back(std::move(r));
     *out = (RT3_TAG_BUFFER << 30) | (uint32_t)(c->resources.size() - 1);
     return RT3_OK;
 }
@@ -1697,9 +1643,10 @@ int rt3_image_create(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t format, uint32
     r.tag = RT3_TAG_IMAGE;
     r.w = w; r.h = h; r.format = format;
     r.bytes = (size_t)w * h * px;
-    HIPC(c, hipMalloc(&r.ptr, r.bytes));
+    HIPC(c, r.mem.alloc_bytes(r.bytes));
+    r.ptr = r.mem.get();
     HIPC(c, hipMemset(r.ptr, 0, r.bytes));
-    c->resources.push_back(r);
+    c->resources.push_back(std::move(r));
     *out = (RT3_TAG_IMAGE << 30) | (uint32_t)(c->resources.size() - 1);
     return RT3_OK;
 }
@@ -1710,9 +1657,8 @@ int rt3_image_import(rt3_ctx* c, void* device_ptr, uint32_t w, uint32_t h, uint3
     r.tag = RT3_TAG_IMAGE;
     r.w = w; r.h = h; r.format = format;
     r.bytes = (size_t)w * h * px;
-    r.ptr = device_ptr;
-    r.owned = false;
-    c->resources.push_back(r);
+    r.ptr = device_ptr;  // borrowed: r.mem stays empty
+    c->resources.push_back(std::move(r));
     *out = (RT3_TAG_IMAGE << 30) | (uint32_t)(c->resources.size() - 1);
     return RT3_OK;
 }
@@ -1773,7 +1719,7 @@ int rt3_image_pack_tiles(rt3_ctx* c, uint32_t image, uint32_t rank, uint32_t n_r
     HIPC(c, hipSetDevice(c->device));
     PixelList* pl;
     if (int e = get_pixlist(c, r->w, r->h, rank, n_ranks, &pl)) return e;
-    if (pl->count) launch_pack_tiles(c->stream, pl->dev, pl->count, r->w, r->ptr, dst);
+    if (pl->count) launch_pack_tiles(c->stream, pl->dev.get(), pl->count, r->w, r->ptr, dst);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -1784,7 +1730,7 @@ int rt3_image_unpack_tiles(rt3_ctx* c, uint32_t image, uint32_t rank, uint32_t n
     HIPC(c, hipSetDevice(c->device));
     PixelList* pl;
     if (int e = get_pixlist(c, r->w, r->h, rank, n_ranks, &pl)) return e;
-    if (pl->count) launch_unpack_tiles(c->stream, pl->dev, pl->count, r->w, src, r->ptr);
+    if (pl->count) launch_unpack_tiles(c->stream, pl->dev.get(), pl->count, r->w, src, r->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -1827,24 +1773,20 @@ static int get_gather_layout(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t root, 
         all.insert(all.end(), px.begin(), px.end());
     }
     gl.off[n_ranks] = all.size();
-    HIPC(c, hipMalloc((void**)&gl.dev, (all.size() ? all.size() : 1) * 4));
+    HIPC(c, gl.dev.alloc_bytes((all.size() ? all.size() : 1) * 4));
     if (!all.empty()) {
-        hipError_t e = hipMemcpy(gl.dev, all.data(), all.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(gl.dev);  // not yet owned by the context's layout cache
-            return fail(c, RT3_E_HIP, std::string("gather layout upload: ") + hipGetErrorString(e));
-        }
+        hipError_t e = hipMemcpy(gl.dev.get(), all.data(), all.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("gather layout upload: ") + hipGetErrorString(e));
     }
-    c->gather_layouts.push_back(gl);
+    c->gather_layouts.push_back(std::move(gl));
     *out = &c->gather_layouts.back();
     return RT3_OK;
 }
 static int ensure_gather_buf(rt3_ctx* c, size_t bytes) {
     if (bytes <= c->gather_buf_bytes) return RT3_OK;
-    HIPC(c, hipStreamSynchronize(c->stream));  // an earlier gather may still be reading the old buffer
-    dev_free(c->gather_buf);
+    HIPC(c, hipStreamSynchronize(c->stream));  // an earlier gather may still be reading the old buffer: idle before it is dropped
     c->gather_buf_bytes = 0;
-    HIPC(c, hipMalloc(&c->gather_buf, bytes));
+    HIPC(c, c->gather_buf.alloc_bytes(bytes));
     c->gather_buf_bytes = bytes;
     return RT3_OK;
 }
@@ -1904,7 +1846,7 @@ int rt3_gather_unpack(rt3_ctx* c, uint32_t image, uint32_t root, uint32_t n_rank
     GatherLayout* gl;
     if (int e = get_gather_layout(c, r->w, r->h, root, n_ranks, &gl)) return e;
     const uint64_t total = gl->off[n_ranks];
-    if (total) launch_unpack_tiles(c->stream, gl->dev, (uint32_t)total, r->w, recv_device, r->ptr);  // ONE launch for all ranks
+    if (total) launch_unpack_tiles(c->stream, gl->dev.get(), (uint32_t)total, r->w, recv_device, r->ptr);  // ONE launch for all ranks
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -1926,11 +1868,11 @@ int rt3_gather_tiles(rt3_ctx* c, uint32_t image, uint32_t root) {
         if (int e = ensure_gather_buf(c, (size_t)pl->count * 16)) return e;
         {
             ScopedTimer t(c, CAT_OTHER);
-            launch_pack_tiles(c->stream, pl->dev, pl->count, r->w, r->ptr, c->gather_buf);
+            launch_pack_tiles(c->stream, pl->dev.get(), pl->count, r->w, r->ptr, c->gather_buf.get());
         }
         HIPC(c, hipGetLastError());
         ScopedTimer t(c, CAT_GATHER);
-        ncclResult_t se = ncclSend(c->gather_buf, (size_t)pl->count * 4, ncclFloat, (int)root, c->comm, c->stream);
+        ncclResult_t se = ncclSend(c->gather_buf.get(), (size_t)pl->count * 4, ncclFloat, (int)root, c->comm, c->stream);
         if (se != ncclSuccess) return comm_abort(c, std::string("ncclSend: ") + ncclGetErrorString(se));
         return RT3_OK;
     }
@@ -1947,14 +1889,14 @@ int rt3_gather_tiles(rt3_ctx* c, uint32_t image, uint32_t root) {
         for (uint32_t p = 0; p < n; p++) {
             const uint64_t cnt = gl->off[p + 1] - gl->off[p];
             if (p == root || cnt == 0) continue;
-            ncclResult_t e = ncclRecv((char*)c->gather_buf + gl->off[p] * 16, (size_t)cnt * 4, ncclFloat, (int)p, c->comm, c->stream);
+            ncclResult_t e = ncclRecv((char*)c->gather_buf.get() + gl->off[p] * 16, (size_t)cnt * 4, ncclFloat, (int)p, c->comm, c->stream);
             if (e != ncclSuccess) return comm_abort(c, std::string("ncclRecv: ") + ncclGetErrorString(e));
         }
         ncclResult_t ge = ncclGroupEnd();
         if (ge != ncclSuccess) return comm_abort(c, std::string("ncclGroupEnd: ") + ncclGetErrorString(ge));
     }
     ScopedTimer t(c, CAT_OTHER);
-    launch_unpack_tiles(c->stream, gl->dev, (uint32_t)total, r->w, c->gather_buf, r->ptr);  // stream-ordered behind the receives
+    launch_unpack_tiles(c->stream, gl->dev.get(), (uint32_t)total, r->w, c->gather_buf.get(), r->ptr);  // stream-ordered behind the receives
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -1999,32 +1941,23 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
     if (!c->accel_built) return fail(c, RT3_E_STATE, "rt3_accel_build has not been called for the current scene");
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
-    float *d_rays = nullptr, *d_hits = nullptr;
-    uint32_t *d_cn = nullptr, *d_ct = nullptr, *d_occ = nullptr, *d_cur = nullptr;
+    DevBuf<float> d_rays, d_hits;
+    DevBuf<uint32_t> d_cn, d_ct, d_occ, d_cur;
     const bool count = n_nodes || n_tris;
-    int rc = RT3_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_rays); (void)hipFree(d_hits); (void)hipFree(d_cn); (void)hipFree(d_ct); (void)hipFree(d_occ); (void)hipFree(d_cur);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-#define TR(call)                                                                            \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            rc = fail(c, RT3_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));     \
-            cleanup();                                                                      \
-            return rc;                                                                      \
-        }                                                                                   \
-    } while (0)
-    TR(hipMalloc((void**)&d_rays, (size_t)n * 32));
-    TR(hipMalloc((void**)&d_hits, (size_t)n * 16));
-    TR(hipMalloc((void**)&d_occ, (size_t)n * 4));
-    TR(hipMalloc((void**)&d_cur, 4));
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    HIPC(c, d_rays.alloc_bytes((size_t)n * 32));
+    HIPC(c, d_hits.alloc_bytes((size_t)n * 16));
+    HIPC(c, d_occ.alloc_bytes((size_t)n * 4));
+    HIPC(c, d_cur.alloc_bytes(4));
     if (count) {
-        TR(hipMalloc((void**)&d_cn, (size_t)n * 4));
-        TR(hipMalloc((void**)&d_ct, (size_t)n * 4));
+        HIPC(c, d_cn.alloc_bytes((size_t)n * 4));
+        HIPC(c, d_ct.alloc_bytes((size_t)n * 4));
     }
     {  // host SoA (ox..tmax) -> device records {o.xyz, tmin} x n, {d.xyz, tmax} x n
         std::vector<float> rec((size_t)n * 8);
@@ -2034,32 +1967,34 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
             a[0] = rays[i]; a[1] = rays[(size_t)n + i]; a[2] = rays[2 * (size_t)n + i]; a[3] = rays[6 * (size_t)n + i];
             b[0] = rays[3 * (size_t)n + i]; b[1] = rays[4 * (size_t)n + i]; b[2] = rays[5 * (size_t)n + i]; b[3] = rays[7 * (size_t)n + i];
         }
-        TR(hipMemcpy(d_rays, rec.data(), (size_t)n * 32, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(d_rays.get(), rec.data(), (size_t)n * 32, hipMemcpyHostToDevice));
     }
-    TR(hipEventCreate(&e0));
-    TR(hipEventCreate(&e1));
+    HIPC(c, hipEventCreate(&ev.e0));
+    HIPC(c, hipEventCreate(&ev.e1));
     if (repeat < 1) repeat = 1;
     auto launch = [&]() {
-        (void)hipMemsetAsync(d_cur, 0, 4, c->stream);  // ray-pool cursor
+        (void)hipMemsetAsync(d_cur.get(), 0, 4, c->stream);  // ray-pool cursor
         if (any_hit)
-            launch_shadow(c->stream, count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, d_rays, n, nullptr, n, n, nullptr, nullptr, nullptr, 0, d_occ, d_cn, d_ct, nullptr, d_cur);
+            launch_shadow(c->stream, count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, d_rays.get(), n, nullptr, n, n,
+                          nullptr, nullptr, nullptr, 0, d_occ.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
         else
-            launch_extend(c->stream, count, c->bvh.layout, c->bvh.nodes, c->bvh.tris, c->bvh.top, c->bvh.n_top, d_rays, n, nullptr, n, n, d_hits, d_cn, d_ct, nullptr, d_cur);
+            launch_extend(c->stream, count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, d_rays.get(), n, nullptr, n, n,
+                          d_hits.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
     };
     launch();  // warm-up (also the result-producing launch)
-    TR(hipEventRecord(e0, c->stream));
+    HIPC(c, hipEventRecord(ev.e0, c->stream));
     for (int k = 0; k < repeat; k++) launch();
-    TR(hipEventRecord(e1, c->stream));
-    TR(hipGetLastError());
-    TR(hipStreamSynchronize(c->stream));
+    HIPC(c, hipEventRecord(ev.e1, c->stream));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    TR(hipEventElapsedTime(&ms, e0, e1));
+    HIPC(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     if (kernel_ms) *kernel_ms = (double)ms / repeat;
     if (any_hit) {
-        TR(hipMemcpy(prim, d_occ, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(prim, d_occ.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     } else {
         std::vector<float> rec((size_t)n * 4);  // device hits are {t, u, v, prim} records
-        TR(hipMemcpy(rec.data(), d_hits, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(rec.data(), d_hits.get(), (size_t)n * 16, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; i++) {
             t[i] = rec[4 * (size_t)i];
             u[i] = rec[4 * (size_t)i + 1];
@@ -2067,10 +2002,8 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
             memcpy(&prim[i], &rec[4 * (size_t)i + 3], 4);
         }
     }
-    if (n_nodes) TR(hipMemcpy(n_nodes, d_cn, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (n_tris) TR(hipMemcpy(n_tris, d_ct, (size_t)n * 4, hipMemcpyDeviceToHost));
-#undef TR
-    cleanup();
+    if (n_nodes) HIPC(c, hipMemcpy(n_nodes, d_cn.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (n_tris) HIPC(c, hipMemcpy(n_tris, d_ct.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RT3_OK;
 }
 
@@ -2079,20 +2012,15 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
-    uint32_t *d_in = nullptr, *d_out = nullptr;
-    HIPC(c, hipMalloc((void**)&d_in, (size_t)n * iw * 4));
-    if (hipMalloc((void**)&d_out, (size_t)n * ow * 4) != hipSuccess) {
-        (void)hipFree(d_in);
-        return fail(c, RT3_E_HIP, "selftest: hipMalloc failed");
-    }
-    hipError_t e = hipMemcpy(d_in, in, (size_t)n * iw * 4, hipMemcpyHostToDevice);
+    DevBuf<uint32_t> d_in, d_out;
+    HIPC(c, d_in.alloc_bytes((size_t)n * iw * 4));
+    HIPC(c, d_out.alloc_bytes((size_t)n * ow * 4));
+    hipError_t e = hipMemcpy(d_in.get(), in, (size_t)n * iw * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_selftest(c->stream, op, d_in, n, d_out);
+        launch_selftest(c->stream, op, d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * ow * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), (size_t)n * ow * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("selftest: ") + hipGetErrorString(e));
     return RT3_OK;
 }

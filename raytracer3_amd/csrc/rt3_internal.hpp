@@ -89,20 +89,54 @@ void set_trace_blocks(uint32_t v);
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w);
 void launch_selftest(hipStream_t st, int op, const uint32_t* in, uint32_t n, uint32_t* out);
 
+// Owner of at most one hipMalloc allocation, freed when the owner goes.  The only place the host layer frees device memory.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    // frees the old allocation BEFORE allocating, so the two never coexist (peak memory); empty on failure
+    hipError_t alloc_bytes(size_t bytes) {
+        reset();
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) p_ = static_cast<T*>(p);
+        return e;
+    }
+
+private:
+    T* p_ = nullptr;
+};
+
 // LBVH build (rt3_lbvh.hip).  All pointers are device memory owned by the caller except the scratch the builder
 // allocates and frees itself.  Returns hipSuccess or the failing HIP error; *max_depth is read back to the host.
 // Scratch memory of the builder: ONE device allocation, handed out by a bump pointer and kept by the context from build to build
 // (a build made ~50 hipMalloc / hipFree pairs before, a third of its wall time on a 260 k-triangle scene).
 struct BuildArena {
-    char* base = nullptr;
+    DevBuf<char> base;
     size_t cap = 0, used = 0;
     hipError_t reserve(size_t bytes) {  // a fresh build: everything handed out before is void
         used = 0;
         if (bytes <= cap) return hipSuccess;
-        if (base) (void)hipFree(base);
-        base = nullptr;
         cap = 0;
-        hipError_t e = hipMalloc((void**)&base, bytes);
+        hipError_t e = base.alloc_bytes(bytes);
         if (e == hipSuccess) cap = bytes;
         return e;
     }
@@ -110,27 +144,27 @@ struct BuildArena {
     hipError_t take(T** p, size_t bytes) {
         const size_t at = (used + 255) & ~(size_t)255;
         if (at + bytes > cap) return hipErrorOutOfMemory;  // the builder's bound on its own scratch was wrong: fail, never overrun
-        *p = reinterpret_cast<T*>(base + at);
+        *p = reinterpret_cast<T*>(base.get() + at);
         used = at + bytes;
         return hipSuccess;
     }
     void release() {
-        if (base) (void)hipFree(base);
-        base = nullptr;
+        base.reset();
         cap = used = 0;
     }
 };
 struct LbvhResult {
-    float4* nodes = nullptr;   // n_nodes x node_bytes: 64 B {box0, box1, ref0, ref1, pad} or 128 B 4 x {min, max, ref, pad}
+    DevBuf<float4> nodes;      // n_nodes x node_bytes: 64 B {box0, box1, ref0, ref1, pad} or 128 B 4 x {min, max, ref, pad}
     uint32_t node_bytes = 128;
     int layout = kLayoutWide128;
-    float4* tris = nullptr;    // n_tris x 3 float4 (48 B), Morton order
-    uint4* tri_shade = nullptr;   // n_tris x 16 B, flattened primitive order: three octahedral vertex normals + flattened geometry index
-    float2* tri_uv = nullptr;     // n_tris x 3 float2: vertex uvs
-    float4* top = nullptr;     // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
+    DevBuf<float4> tris;       // n_tris x 3 float4 (48 B), Morton order
+    DevBuf<uint4> tri_shade;   // n_tris x 16 B, flattened primitive order: three octahedral vertex normals + flattened geometry index
+    DevBuf<float2> tri_uv;     // n_tris x 3 float2: vertex uvs
+    DevBuf<float4> top;        // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
 };
+// On failure *out may hold some of its arrays: they go with it.
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
                       uint32_t sah_top, BuildArena& arena, LbvhResult* out);
@@ -155,6 +189,6 @@ void tlas_box_tris(hipStream_t st, const float* boxes, uint32_t n, float* verts,
 // 0x80000000 | (rec_base + 2 * instance slot)
 void tlas_emit_top(hipStream_t st, const float4* top_nodes, uint32_t n_nodes, const float4* top_tris, uint32_t rec_base, float4* dst);
 
-hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, float4** top, uint32_t* n_top);
+hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 
 }  // namespace rt3

@@ -760,19 +760,18 @@ __global__ void k_top_cache(const float4* __restrict__ nodes, uint32_t n_nodes, 
 }
 
 // (re)make the LDS top-of-tree copy for a node array in the quantised 64-byte layout (rt3_accel_import)
-hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, float4** top, uint32_t* n_top) {
+hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top) {
     *n_top = 0;
-    if (!*top) {
-        hipError_t e = hipMalloc(top, (size_t)kTopCacheNodes * 64);
+    if (!top) {
+        hipError_t e = top.alloc_bytes((size_t)kTopCacheNodes * 64);
         if (e != hipSuccess) return e;
     }
-    uint32_t* d_ntop = nullptr;
-    hipError_t e = hipMalloc(&d_ntop, 4);
+    DevBuf<uint32_t> d_ntop;
+    hipError_t e = d_ntop.alloc_bytes(4);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, nodes, n_nodes, (uint32_t*)*top, d_ntop);
-    e = hipMemcpyAsync(n_top, d_ntop, 4, hipMemcpyDeviceToHost, st);
+    hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, nodes, n_nodes, (uint32_t*)top.get(), d_ntop.get());
+    e = hipMemcpyAsync(n_top, d_ntop.get(), 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_ntop);
     return e;
 }
 
@@ -804,19 +803,15 @@ __global__ void k_single(const float* lmin, const float* lmax, int wide, int qua
     }
 }
 
-#define LB_CHECK(x)                  \
-    do {                             \
-        hipError_t e_ = (x);         \
-        if (e_ != hipSuccess) {      \
-            err = e_;                \
-            goto done;               \
-        }                            \
+#define LB_CHECK(x)                      \
+    do {                                 \
+        hipError_t e_ = (x);             \
+        if (e_ != hipSuccess) return e_; \
     } while (0)
 
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
                       uint32_t sah_top, BuildArena& arena, LbvhResult* out) {
-    hipError_t err = hipSuccess;
     *out = LbvhResult{};
     out->n_tris = n;
     const int wide = node_width == 4, quant = wide ? (node_quant > 2 ? 2 : (int)node_quant) : 0, collapse = wide ? (collapse_mode > 2 ? 2 : (int)collapse_mode) : 0;
@@ -886,10 +881,10 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
         LB_CHECK(arena.take(&lmax2, (size_t)n * 12));
         LB_CHECK(arena.take(&tris_dp, (size_t)n * 48));
     }
-    LB_CHECK(hipMalloc(&out->tris, (size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
-    LB_CHECK(hipMemsetAsync((char*)out->tris + (size_t)n * 48, 0, 128, st));
-    LB_CHECK(hipMalloc(&out->tri_shade, (size_t)n * 16));
-    LB_CHECK(hipMalloc(&out->tri_uv, (size_t)n * 24));
+    LB_CHECK(out->tris.alloc_bytes((size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
+    LB_CHECK(hipMemsetAsync((char*)out->tris.get() + (size_t)n * 48, 0, 128, st));
+    LB_CHECK(out->tri_shade.alloc_bytes((size_t)n * 16));
+    LB_CHECK(out->tri_uv.alloc_bytes((size_t)n * 24));
     if (quant == 2 && n > 1) {
         LB_CHECK(arena.take(&tris_morton, (size_t)n * 48));
         LB_CHECK(arena.take(&n_int, (size_t)nn * 4));
@@ -901,16 +896,16 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     LB_CHECK(hipMemsetAsync(arrive, 0, (size_t)nn * 4, st));
     LB_CHECK(hipMemsetAsync(levels, 0, 4, st));
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, bmin, bmax, bounds);
-    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, out->tri_shade, out->tri_uv);
+    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, out->tri_shade.get(), out->tri_uv.get());
     hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, bmin, bmax, bounds, n, keys_in, vals_in);
     LB_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
     LB_CHECK(arena.take(&temp, temp_bytes ? temp_bytes : 16));
     LB_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
     hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, vals_out, bmin, bmax, bounds, n,
-                       tris_dp ? tris_dp : (tris_morton ? tris_morton : out->tris), lmin, lmax);
+                       tris_dp ? tris_dp : (tris_morton ? tris_morton : out->tris.get()), lmin, lmax);
     if (n == 1) {
-        LB_CHECK(hipMalloc(&out->nodes, out->node_bytes));
-        hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, lmin, lmax, wide, quant, out->nodes);
+        LB_CHECK(out->nodes.alloc_bytes(out->node_bytes));
+        hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, lmin, lmax, wide, quant, out->nodes.get());
         out->n_nodes = 1;
         out->max_depth = 2;
         LB_CHECK(hipGetLastError());
@@ -944,7 +939,7 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
             hipLaunchKernelGGL(k_dp_up, dim3(grid), dim3(256), 0, st, left, right, pint, pleaf, lmin, lmax, nbox, n, leaf_max, rcnt, dc, dk, live, arrive);
             const unsigned g3 = (unsigned)(((uint64_t)n + nn + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + nn + 255) / 256);
             hipLaunchKernelGGL(k_tree_order, dim3(g3), dim3(256), 0, st, left, right, pint, pleaf, rcnt, n, nn, newpos, rlo);
-            float4* tris_to = quant == 2 ? tris_morton : out->tris;  // (the compact layout moves them once more, into leaf order, when it emits)
+            float4* tris_to = quant == 2 ? tris_morton : out->tris.get();  // (the compact layout moves them once more, into leaf order, when it emits)
             hipLaunchKernelGGL(k_tree_reorder, dim3(g3), dim3(256), 0, st, newpos, n, nn, tris_dp, tris_to, lmin, lmax, lmin2, lmax2, left, right);
             lmin = lmin2;
             lmax = lmax2;
@@ -995,7 +990,7 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
         LB_CHECK(hipMemcpyAsync(&out->max_depth, levels, 4, hipMemcpyDeviceToHost, st));
         LB_CHECK(hipStreamSynchronize(st));
         out->n_nodes = tail[0] + tail[1];
-        LB_CHECK(hipMalloc(&out->nodes, (size_t)out->n_nodes * out->node_bytes));
+        LB_CHECK(out->nodes.alloc_bytes((size_t)out->n_nodes * out->node_bytes));
         if (quant == 2) {
             hipLaunchKernelGGL(k_child_counts, dim3(grid), dim3(256), 0, st, left, right, rcnt, nbox, keep, nn, live, dk, collapse, n_int, n_ltri);
             LB_CHECK(hipcub::DeviceScan::ExclusiveSum(temp2, temp2_bytes, n_int, cbase, (int)nn, st));
@@ -1003,12 +998,12 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
             hipLaunchKernelGGL(k_assign_index, dim3(grid), dim3(256), 0, st, left, right, live, nbox, keep, nn, dk, collapse, cbase, newidx);
         }
         hipLaunchKernelGGL(k_emit_nodes, dim3(grid), dim3(256), 0, st, left, right, rlo, rcnt, keep, newidx, lmin, lmax, nbox, nn, live, dk, wide,
-                           quant, collapse, out->nodes, cbase, tbase, tris_morton, out->tris);
+                           quant, collapse, out->nodes.get(), cbase, tbase, tris_morton, out->tris.get());
         if (wide && quant == 1) {  // top-of-tree copy the traversal kernels keep in LDS
             uint32_t* d_ntop = nullptr;
-            LB_CHECK(hipMalloc(&out->top, (size_t)kTopCacheNodes * 64));
+            LB_CHECK(out->top.alloc_bytes((size_t)kTopCacheNodes * 64));
             LB_CHECK(arena.take(&d_ntop, 4));
-            hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, out->nodes, out->n_nodes, (uint32_t*)out->top, d_ntop);
+            hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, out->nodes.get(), out->n_nodes, (uint32_t*)out->top.get(), d_ntop);
             hipError_t e3 = hipMemcpyAsync(&out->n_top, d_ntop, 4, hipMemcpyDeviceToHost, st);
             if (e3 == hipSuccess) e3 = hipStreamSynchronize(st);
             LB_CHECK(e3);
@@ -1018,21 +1013,7 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
         if (getenv("RT3_TRACE_BUILD"))
             fprintf(stderr, "rt3 build: collapse + emit %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
     }
-done:
-    if (err != hipSuccess) {
-        (void)hipFree(out->nodes);
-        (void)hipFree(out->tris);
-        (void)hipFree(out->tri_shade);
-        (void)hipFree(out->tri_uv);
-        (void)hipFree(out->top);
-        out->top = nullptr;
-        out->n_top = 0;
-        out->nodes = nullptr;
-        out->tris = nullptr;
-        out->tri_shade = nullptr;
-        out->tri_uv = nullptr;
-    }
-    return err;
+    return hipSuccess;
 }
 
 }  // namespace rt3

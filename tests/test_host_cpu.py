@@ -305,3 +305,21 @@ def test_bench_dump_outputs_writes_whole_arrays_or_a_fixed_sample(tmp_path):
     # a whole dump into a directory that held a sampled one leaves no stale index beside it
     bench.dump_outputs(tmp_path / "a", {"light": light})
     assert not (tmp_path / "a" / "pixel_index.npy").exists()
+
+
+def test_device_memory_is_freed_only_by_devbuf():
+    """The host layer owns device memory through DevBuf (rt3_internal.hpp) alone: a hipFree( anywhere else in the native sources is
+    hand-written ownership coming back."""
+    csrc = ROOT / "raytracer3_amd" / "csrc"
+    header = (csrc / "rt3_internal.hpp").read_text()
+    start = header.index("class DevBuf {")
+    end = header.index("\n};", start)
+    assert "hipFree(" in header[start:end]
+    stray = []
+    for path in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.hpp")):
+        text = path.read_text()
+        for m in re.finditer(r"\bhipFree\s*\(", text):
+            if path.name == "rt3_internal.hpp" and start <= m.start() < end:
+                continue
+            stray.append(f"{path.name}:{text.count(chr(10), 0, m.start()) + 1}")
+    assert not stray, f"hipFree outside DevBuf: {stray}"
