@@ -1031,9 +1031,12 @@ int orc_accel_build(orc_scene *s) {
             smin[k] = fminx(smin[k], lo); smax[k] = fmaxx(smax[k], hi);
         }
     }
-    /* conservative leaf padding so that the slab test never culls a triangle the fp32 triangle test accepts */
+    /* conservative leaf padding so that the slab test never culls a triangle the fp32 triangle test accepts: a share of the
+     * scene's extent, and at least 2^-20 of its largest coordinate magnitude so that bmin - pad / bmax + pad still move the
+     * planes by several ulps far from the origin ("Leaf padding") */
     float ext = fmaxx(smax[0] - smin[0], fmaxx(smax[1] - smin[1], smax[2] - smin[2]));
-    float pad = ext * 1.0e-5f;
+    float mag = fmaxx(fmaxx(fabsf(smin[0]), fabsf(smax[0])), fmaxx(fmaxx(fabsf(smin[1]), fabsf(smax[1])), fmaxx(fabsf(smin[2]), fabsf(smax[2]))));
+    float pad = fmaxx(ext * 1.0e-5f, mag * 0x1p-20f);
     code_prim *cp = (code_prim *)malloc((size_t)n * sizeof(code_prim));
     for (uint32_t i = 0; i < n; i++) {
         uint32_t q[3];

@@ -176,7 +176,11 @@ __global__ void k_leaves(const float* verts, const uint32_t* indices, const Flat
     float ex = ordered_to_float(bounds[3]) - ordered_to_float(bounds[0]);
     float ey = ordered_to_float(bounds[4]) - ordered_to_float(bounds[1]);
     float ez = ordered_to_float(bounds[5]) - ordered_to_float(bounds[2]);
-    float pad = fmax_sel(ex, fmax_sel(ey, ez)) * 1.0e-5f;  // conservative leaf padding
+    float mag = fmax_sel(fmax_sel(fabsf(ordered_to_float(bounds[0])), fabsf(ordered_to_float(bounds[3]))),
+                         fmax_sel(fmax_sel(fabsf(ordered_to_float(bounds[1])), fabsf(ordered_to_float(bounds[4]))),
+                                  fmax_sel(fabsf(ordered_to_float(bounds[2])), fabsf(ordered_to_float(bounds[5])))));
+    // conservative leaf padding: a share of the extent, and at least 2^-20 of the largest coordinate magnitude ("Leaf padding")
+    float pad = fmax_sel(fmax_sel(ex, fmax_sel(ey, ez)) * 1.0e-5f, mag * 0x1p-20f);
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         uint32_t p = sorted_prim[k];
         V3 a, b, c;
