@@ -111,11 +111,10 @@ typedef struct rt3_stats {
     double shadow_ms;
     double shade_ms;
     double other_ms;
-    /* k_trace = one launch per bounce that drains the extension queue and then the shadow queue (the frame's dominant
-     * kernel); its rays are ALSO included in extension_rays / shadow_rays and its visits in the four totals above */
+    /* always 0 since the fused traversal launch (k_trace, option 10) was retired; kept so that the layout stays put */
     uint64_t trace_launches;
     double trace_ms;
-    uint64_t trace_rays[2];  /* counting mode: [0] closest-hit, [1] any-hit rays traced by k_trace launches */
+    uint64_t trace_rays[2];
     uint64_t trace_nodes[2];
     uint64_t trace_tris[2];
     double gather_ms; /* RCCL send / grouped receives of rt3_gather_tiles (the pack / untile kernels are in other_ms) */
@@ -146,7 +145,7 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
                                      programme also decides which subtrees become multi-triangle leaves; triangle records in tree order), 1 = greedy by surface
                                      area, 0 = even binary depth */
 #define RT3_OPT_POOL_CHUNK 9      /* traversal tuning: rays a wave takes from the launch's ray pool per grab (default 256) */
-#define RT3_OPT_FUSED_TRACE 10    /* 1: one k_trace launch per bounce walks the extension queue and then the shadow queue; 0 (default): separate k_shadow and k_extend launches */
+/* 10: retired (was RT3_OPT_FUSED_TRACE, one k_trace launch per bounce for both ray queues; measured slower); not reused */
 #define RT3_OPT_SAH_TOP 11       /* T > 0 (default 1 = binned SAH down to single triangles; collapse 0 / 1 use max(T, leaf size)): the tree above Karras subtrees of at most T triangles is re-linked by binned SAH
                                      (the reference asks its driver for PREFER_FAST_TRACE builds, raytracing.rs:103,131); 0 = plain LBVH */
 #define RT3_OPT_TRACE_BLOCKS 12   /* traversal tuning: persistent workgroups (256 threads) per traversal launch (default 2048 = 8 per CU) */

@@ -49,7 +49,7 @@ struct GatherLayout {
     std::vector<uint64_t> off;  // n_ranks + 1 entries, in pixels
     DevBuf<uint32_t> dev;       // off[n_ranks] pixel words (x | y << 16)
 };
-enum Cat { CAT_EXTEND = 0, CAT_SHADOW = 1, CAT_SHADE = 2, CAT_OTHER = 3, CAT_TRACE = 4, CAT_GATHER = 5 };
+enum Cat { CAT_EXTEND = 0, CAT_SHADOW = 1, CAT_SHADE = 2, CAT_OTHER = 3, CAT_GATHER = 4 };
 struct Timed {
     hipEvent_t a, b;
     int cat;
@@ -136,14 +136,13 @@ struct rt3_ctx {
     DevBuf<float> sh_rays, sh_contrib, lacc, radsum;
     DevBuf<uint32_t> d_counters;
     uint32_t counters_cap = 1 << 16, counters_next = 0;
-    DevBuf<unsigned long long> d_totals;
+    DevBuf<unsigned long long> d_totals;  // counting mode: kTotWords words (TotalsWord)
     std::vector<CounterBlock> pending_counters;
     // options / stats
     int64_t opt_batch_spp = 0;
     bool opt_profile = false, opt_count = false;
     int opt_variant = 0;  // RT3_OPT_EXTEND_VARIANT: reserved for traversal experiments
     uint32_t opt_leaf_size = 2, opt_node_width = 4, opt_node_quant = 1, opt_collapse = 2, opt_sah_top = 1;
-    int opt_fused_trace = 0;  // 1: k_trace (extension + shadow queue in one launch per bounce)
     int opt_instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
     uint64_t scene_gen = 1;     // bumped by everything a bottom tree depends on (vertices, indices, geometry, leaf size, collapse, SAH top)
     TwoLevelState tl;
@@ -345,20 +344,14 @@ int harvest(rt3_ctx* c) {  // stream must be idle
     c->stats.extension_rays += c->primary_rays_pending;
     c->primary_rays_pending = 0;
     if (c->opt_count) {
-        unsigned long long t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [0..3] k_extend / k_shadow, [4..9] k_trace {rays, nodes, tris} x 2, [10..11] node visits served by the LDS top-of-tree copy {closest, any}
+        unsigned long long t[kTotWords] = {};
         HIPC(c, hipMemcpy(t, c->d_totals.get(), sizeof(t), hipMemcpyDeviceToHost));
-        c->stats.nodes_visited += t[0] + t[5];
-        c->stats.tris_tested += t[1] + t[6];
-        c->stats.shadow_nodes_visited += t[2] + t[8];
-        c->stats.shadow_tris_tested += t[3] + t[9];
-        c->stats.trace_rays[0] += t[4];
-        c->stats.trace_nodes[0] += t[5];
-        c->stats.trace_tris[0] += t[6];
-        c->stats.trace_rays[1] += t[7];
-        c->stats.trace_nodes[1] += t[8];
-        c->stats.trace_tris[1] += t[9];
-        c->stats.nodes_visited_lds += t[10];
-        c->stats.shadow_nodes_visited_lds += t[11];
+        c->stats.nodes_visited += t[kTotExtendNodes];
+        c->stats.tris_tested += t[kTotExtendTris];
+        c->stats.shadow_nodes_visited += t[kTotShadowNodes];
+        c->stats.shadow_tris_tested += t[kTotShadowTris];
+        c->stats.nodes_visited_lds += t[kTotExtendLds];
+        c->stats.shadow_nodes_visited_lds += t[kTotShadowLds];
         HIPC(c, hipMemset(c->d_totals.get(), 0, sizeof(t)));
     }
     for (auto& t : c->pending_events) {
@@ -368,7 +361,6 @@ int harvest(rt3_ctx* c) {  // stream must be idle
             case CAT_EXTEND: c->stats.extend_ms += ms; c->stats.extend_launches++; break;
             case CAT_SHADOW: c->stats.shadow_ms += ms; c->stats.shadow_launches++; break;
             case CAT_SHADE: c->stats.shade_ms += ms; break;
-            case CAT_TRACE: c->stats.trace_ms += ms; c->stats.trace_launches++; break;
             case CAT_GATHER: c->stats.gather_ms += ms; break;
             default: c->stats.other_ms += ms; break;
         }
@@ -529,28 +521,16 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
                 launch_shade(c->stream, bn == 0, L);
             }
             cur ^= 1;
-            // both queues in one launch (k_trace, RT3_OPT_FUSED_TRACE = 1): one end-of-launch drain less per bounce (the waves of a
-            // persistent walk finish spread over the time their longest last ray takes, ~0.15 ms), against the cost of mixing the
-            // two ray kinds in a wave.  Which side wins moved with every change of the shadow walk (+3 % at N = 8 before the SAH top,
-            // -3 % after it), so the default is the simple one: separate launches.
-            const bool fuse = c->opt_fused_trace == 1;
-            if (nee && bn != B - 1 && fuse) {
-                ScopedTimer t(c, CAT_TRACE);
-                launch_trace(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), c->sh_rays.get(), S,
-                             ext_cnt_at(bn), sh_cnt_at(bn), n_first, c->hits.get(), c->sh_contrib.get(), c->lacc.get(), c->opt_count ? c->d_totals.get() + 4 : nullptr,
-                             pool_cur + bn, pool_cur + B + bn);
-            } else {
-                if (nee) {
-                    ScopedTimer t(c, CAT_SHADOW);
-                    launch_shadow(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->sh_rays.get(), S, sh_cnt_at(bn), 0,
-                                  n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S, nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() + 2 : nullptr,
-                                  pool_cur + B + bn);
-                }
-                if (bn != B - 1) {
-                    ScopedTimer t(c, CAT_EXTEND);
-                    launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), S, ext_cnt_at(bn), 0,
-                                  n_first, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
-                }
+            if (nee) {
+                ScopedTimer t(c, CAT_SHADOW);
+                launch_shadow(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->sh_rays.get(), S, sh_cnt_at(bn), 0,
+                              n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S, nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr,
+                              pool_cur + B + bn);
+            }
+            if (bn != B - 1) {
+                ScopedTimer t(c, CAT_EXTEND);
+                launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), S, ext_cnt_at(bn), 0,
+                              n_first, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
             }
         }
         {
@@ -705,7 +685,7 @@ int rt3_create(int device, rt3_ctx** out) {
     snprintf(c->name, sizeof(c->name), "%s (%s)", prop.name, prop.gcnArchName);
     memset(&c->stats, 0, sizeof(c->stats));
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || c->d_counters.alloc_bytes((size_t)c->counters_cap * 4) != hipSuccess ||
-        c->d_totals.alloc_bytes(96) != hipSuccess || hipMemset(c->d_totals.get(), 0, 96) != hipSuccess) {
+        c->d_totals.alloc_bytes(kTotWords * 8) != hipSuccess || hipMemset(c->d_totals.get(), 0, kTotWords * 8) != hipSuccess) {
         rt3_destroy(c);  // the stream too
         return fail(nullptr, RT3_E_HIP, "stream / counter allocation failed");
     }
@@ -761,10 +741,6 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             c->opt_sah_top = (uint32_t)value;
             c->accel_built = false;
             c->scene_gen++;
-            return RT3_OK;
-        case RT3_OPT_FUSED_TRACE:
-            if (value < 0 || value > 1) return fail(c, RT3_E_INVALID, "fused trace must be 0 or 1");
-            c->opt_fused_trace = (int)value;
             return RT3_OK;
         case RT3_OPT_POOL_CHUNK:
             if (value < 64 || value > 65536 || (value & 63)) return fail(c, RT3_E_INVALID, "pool chunk must be a multiple of 64 in [64, 65536]");

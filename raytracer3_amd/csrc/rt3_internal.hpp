@@ -25,6 +25,18 @@ constexpr int kLayoutWide64Q = 2;    // 64 B: origin + power-of-two steps + four
 constexpr int kLayoutTwoLevel = 4;   // RT3_OPT_INSTANCE_MODE 1: kLayoutWide64Q nodes of a top tree over instance records and shared bottom trees (rt3_tlas.hip)
 constexpr uint32_t kMaxStack = 64;         // traversal stack entries: LDS short stack (12) + private spill (52)
 constexpr uint32_t kTopCacheNodes = 128;   // top-of-tree nodes the traversal kernels hold in LDS (8 KiB)
+// counting mode (RT3_OPT_COUNT_TRAVERSAL): the words of the context's block of 64-bit traversal totals.  launch_extend / launch_shadow
+// take the block's base; each kernel adds its {nodes, tris} at the word it is handed (so a kind's two words are adjacent) and its
+// LDS-served node visits at a second pointer.
+enum TotalsWord : int {
+    kTotExtendNodes = 0,
+    kTotExtendTris = 1,
+    kTotShadowNodes = 2,
+    kTotShadowTris = 3,
+    kTotExtendLds = 4,  // node visits served by the LDS top-of-tree copy
+    kTotShadowLds = 5,
+    kTotWords = 6
+};
 
 struct ShadeLaunch {
     GConstDev g;
@@ -57,9 +69,6 @@ void launch_extend(hipStream_t st, bool count, int layout, const float4* nodes, 
 void launch_shadow(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
                    const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc,
                    size_t lstride, uint32_t* occluded_out, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter);
-void launch_trace(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* ext_rays, const float* sh_rays,
-                  size_t stride, const uint32_t* ext_count, const uint32_t* sh_count, uint32_t max_n, float* hits, const float* contrib, float* lacc,
-                  unsigned long long* totals, uint32_t* work_ext, uint32_t* work_sh);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
 void launch_shade(hipStream_t st, bool first, const ShadeLaunch& L);

@@ -2,7 +2,7 @@
 //
 // Pipeline (replaces shaders/old/{gbuffer,refrence_mode,postprocess}.slang + the driver's ray traversal):
 //   k_raygen -> k_extend -> k_gbuffer                                   ("gbuffer" pass)
-//   k_shade<first> -> [k_shadow] -> k_extend -> k_shade -> ... -> k_accumulate   ("refrence_mode" pass; k_trace = k_shadow + k_extend in one launch)
+//   k_shade<first> -> [k_shadow] -> k_extend -> k_shade -> ... -> k_accumulate   ("refrence_mode" pass)
 //   k_postprocess                                                        ("postprocess" pass)
 // All queues are structure-of-arrays of 16-byte records (ray = {o, tmin} + {d, tmax}, state = {T, pdf}, hit = {t, u, v, prim};
 // shadow ray = {o, contribution.r} + {d, contribution.g} + 8 bytes {contribution.b, path id}): lane i touches record i of each
@@ -10,6 +10,8 @@
 // 64-bit atomic per workgroup for both output queues.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "rt3_device.hpp"
 #include "rt3_internal.hpp"
@@ -140,9 +142,7 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
     uint32_t sel_p0, sel_q0, sel_p1, sel_q1;  // default layout: v_perm_b32 selectors that put a child's NEAR planes first (see the box block)
 };
 
-// MODE 0: closest hit over one queue; 1: any hit over one queue; 2: both queues in one walk -- the lanes of a wave take
-// extension rays (closest hit) until that pool is dry and shadow rays (any hit) from then on, so the two kinds share a
-// wave for a while and no lane waits for the wave's last extension ray before it starts on shadow rays.
+// MODE 0: closest hit over one queue; 1: any hit over one queue.
 // TWO: the two-level structure (kLayoutTwoLevel) over the quantised 64-byte node format: node 0 is the root of the top
 // tree, whose leaf references name instance records (0x80000000 | record node, count field 0: in the top tree every leaf is an instance).  A
 // lane that reaches one fetches the record, moves its ray into object space for the box tests of the bottom tree, marks its stack and walks
@@ -150,19 +150,13 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // bottom walk has popped down to the mark the lane goes back to the world ray and the top tree's entries.
 template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, const float4* __restrict__ tris,
-                                             const float* __restrict__ rays_a, size_t stride, uint32_t n_a, uint32_t* __restrict__ work_counter_a,
-                                             uint32_t* __restrict__ lds, Finish finish, bool any_payload = false,
-                                             const float* __restrict__ rays_b = nullptr, uint32_t n_b = 0, uint32_t* __restrict__ work_counter_b = nullptr,
-                                             bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
+                                             const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
+                                             uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
                                              const float2* __restrict__ any_contrib = nullptr) {
     // any_payload: the any-hit rays come from k_shade's shadow queue, where every ray has the range (kRayTMin, kBackgroundDepth):
     // the two .w slots of its record carry payload (two contribution channels) instead of tmin / tmax -- 16 bytes less per ray.
     // ext_payload: likewise for the extension rays of the path tracer's own queue (.w = the path's pdf and id, read by k_shade)
-    const float* __restrict__ rays = rays_a;
-    uint32_t n = n_a;
-    uint32_t* __restrict__ work_counter = work_counter_a;
-    bool second_pool = false;  // MODE 2: wave-uniform, true once this wave has moved on to the shadow queue
-    bool lane_any = MODE == 1;
+    constexpr bool ANY = MODE == 1;
     constexpr bool WIDE = LAYOUT == kLayoutWide128;   // 8 x 16 B per fetch
     constexpr bool WIDEQ = LAYOUT == kLayoutWide64Q || LAYOUT == kLayoutWide48Q;  // quantised boxes
     constexpr bool C48 = LAYOUT == kLayoutWide48Q;  // 3 x 16 B per fetch: node and triangle records are both 48 B
@@ -178,7 +172,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
     // a launch whose queue is mostly covered by the waves' static first chunks (a 1-spp frame: 2 M rays over 8192 waves) balances
     // better with chunks of half the size: 0.79 -> 0.72 ms per frame at 1080p, 1 spp, one bounce; long queues keep the full chunk
     const uint32_t kRefillLanes = g_refill_lanes,
-                   kPoolChunk = (n_a < 2u * n_waves * g_pool_chunk && g_pool_chunk >= 128u) ? ((g_pool_chunk >> 1) & ~63u) : g_pool_chunk;
+                   kPoolChunk = (n < 2u * n_waves * g_pool_chunk && g_pool_chunk >= 128u) ? ((g_pool_chunk >> 1) & ~63u) : g_pool_chunk;
     // the first chunk of every wave is static (chunk number = global wave number): no atomic storm at launch, when all the
     // waves of the grid would hit the cursor at once (8192 returning atomics on one word ~ 0.1 ms); the cursor counts the
     // chunks handed out after those
@@ -234,16 +228,6 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
             queue_empty = base >= n;
             pool_next = base < n ? base : n;
             pool_end = (n - pool_next) > kPoolChunk ? pool_next + kPoolChunk : n;
-            if (MODE == 2 && queue_empty && !second_pool) {  // extension queue dry: this wave's idle lanes go on with shadow rays
-                second_pool = true;
-                rays = rays_b;
-                n = n_b;
-                work_counter = work_counter_b;
-                first_chunk = true;
-                queue_empty = false;
-                pool_next = pool_end = 0;
-                continue;
-            }
         }
         if (m_idle != 0ull && pool_next < pool_end && ((uint32_t)__popcll(m_idle) >= kRefillLanes || m_idle == ~0ull)) {
             const uint32_t idx = pool_next + (uint32_t)__popcll(m_idle & lanes_below);
@@ -251,12 +235,12 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 const float4 ro = reinterpret_cast<const float4*>(rays)[idx], rd = reinterpret_cast<const float4*>(rays)[stride + idx];
                 r.o = v3(ro.x, ro.y, ro.z);
                 r.d = v3(rd.x, rd.y, rd.z);
-                const bool payload = (any_payload && (MODE == 1 || (MODE == 2 && second_pool))) || (ext_payload && (MODE == 0 || (MODE == 2 && !second_pool)));
+                const bool payload = ANY ? any_payload : ext_payload;
                 r.tmin = payload ? kRayTMin : ro.w;
                 r.best = Hit{payload ? kBackgroundDepth : rd.w, 0.0f, 0.0f, kMiss};
                 r.pay0 = ro.w;
                 r.pay1 = rd.w;
-                if (any_contrib != nullptr && (MODE == 1 || (MODE == 2 && second_pool))) {
+                if (ANY && any_contrib != nullptr) {
                     const float2 c2 = any_contrib[idx];
                     r.pay2 = c2.x;
                     r.pay3 = c2.y;
@@ -284,14 +268,13 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 r.steps = 0u;
                 r.cn = r.ct = r.cl = 0u;
                 busy = true;
-                if (MODE == 2) lane_any = second_pool;
                 // a ray with a non-finite origin or direction (NaN camera, a zero-length shading normal upstream) misses: with NaNs every
                 // slab test of the min/max form passes and the ray would walk the whole tree
                 const float kMaxF = 3.4028234663852886e38f;
                 const bool finite_ray = fabsf(r.o.x) <= kMaxF && fabsf(r.o.y) <= kMaxF && fabsf(r.o.z) <= kMaxF && fabsf(r.d.x) <= kMaxF &&
                                         fabsf(r.d.y) <= kMaxF && fabsf(r.d.z) <= kMaxF;
                 if (nodes == nullptr || !finite_ray) {  // empty scene: everything misses
-                    finish(r.index, r.best, 0u, 0u, 0u, MODE == 2 ? lane_any : MODE == 1, r.pay0, r.pay1, r.pay2, r.pay3);
+                    finish(r.index, r.best, 0u, 0u, 0u, r.pay0, r.pay1, r.pay2, r.pay3);
                     busy = false;
                 }
             }
@@ -302,7 +285,6 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
         // ---- one traversal step.  (One region under `if (busy)` and a single way back to the loop header: with `continue`s in front of it
         // the compiler copied the eight registers of the walk's state aside at the top of every step and back at its end.)
         if (busy) {
-        const bool ANY = MODE == 2 ? lane_any : MODE == 1;  // compile-time constant for MODE 0 / 1, per lane for MODE 2
         const bool is_leaf = (r.cur & 0x80000000u) != 0u;
         const uint32_t first = r.cur & 0x0FFFFFFFu, cnt = ((r.cur >> 28) & 7u) + 1u;
         const bool cached = LAYOUT == kLayoutWide64Q && !is_leaf && (r.cur & kTopFlag) != 0u;  // a top-of-tree node held in LDS
@@ -538,7 +520,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
         // kMaxSteps bounds the walk so that a corrupt tree can never hang the GPU (a valid tree visits < 2 n nodes)
         if (++r.steps >= kMaxSteps) done = true;
         if (done) {
-            finish(r.index, r.best, r.cn, r.ct, r.cl, MODE == 2 ? lane_any : MODE == 1, r.pay0, r.pay1, r.pay2, r.pay3);
+            finish(r.index, r.best, r.cn, r.ct, r.cl, r.pay0, r.pay1, r.pay2, r.pay3);
             busy = false;
         }
         }  // if (busy)
@@ -559,7 +541,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
-    auto finish = [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, bool, float, float, float, float) {
+    auto finish = [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float, float, float, float) {
         // one 16-byte record per ray: with persistent waves rays finish out of order, four SoA streams would be four
         // scattered partial-line writes
         reinterpret_cast<float4*>(hits)[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
@@ -571,7 +553,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
             tot_l += cl;
         }
     };
-    trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, nullptr, 0, nullptr, payload != 0, s_top, use_top);
+    trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top);
     if (COUNT && totals) {
         atomicAdd(&totals[0], tot_n);
         atomicAdd(&totals[1], tot_t);
@@ -597,7 +579,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
     trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(
         nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
-        [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, bool, float c_r, float c_g, float c_b, float c_pid) {
+        [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
             if (occluded_out) {
                 occluded_out[i] = h.prim != kMiss ? 1u : 0u;
             } else if (h.prim == kMiss) {
@@ -615,61 +597,11 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
                 tot_l += cl;
             }
         },
-        occluded_out == nullptr, nullptr, 0, nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr);
+        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr);
     if (COUNT && totals) {
         atomicAdd(&totals[0], tot_n);
         atomicAdd(&totals[1], tot_t);
         if (lds_total) atomicAdd(lds_total, tot_l);
-    }
-}
-
-// One launch per bounce for BOTH ray kinds: the lanes of every wave take extension rays (closest hit) until that queue is dry and
-// shadow rays (any hit) from then on -- no grid-wide barrier and no per-wave drain in between -- a launch boundary idles the machine while the last
-// waves finish (each k_extend / k_shadow pair cost one such drain more), which matters most when the frame is split
-// over several GPUs and every launch is 1/N as long.  totals (counting mode): {rays, nodes, tris} x {closest, any}.
-template <bool COUNT, int LAYOUT>
-__global__ __launch_bounds__(kExtendBlock) void k_trace(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
-                                                        const float* __restrict__ ext_rays, const float* __restrict__ sh_rays, size_t stride,
-                                                        const uint32_t* __restrict__ ext_count, const uint32_t* __restrict__ sh_count,
-                                                        float* __restrict__ hits, const float* __restrict__ contrib, float* __restrict__ lacc,
-                                                        unsigned long long* __restrict__ totals, uint32_t* __restrict__ work_ext,
-                                                        uint32_t* __restrict__ work_sh) {
-    __shared__ uint32_t stack[kLdsStack * kExtendBlock];
-    __shared__ float4 s_top[4 * kTopNodes];
-    const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
-    const uint32_t n_ext = *ext_count, n_sh = *sh_count;
-    unsigned long long en = 0, et = 0, sn = 0, stt = 0, el = 0, sl = 0;
-    trace_stream<2, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(
-        nodes, tris, ext_rays, stride, n_ext, work_ext, stack + threadIdx.x,
-        [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, bool any, float c_r, float c_g, float c_b, float c_pid) {
-            if (!any) {
-                reinterpret_cast<float4*>(hits)[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
-            } else if (h.prim == kMiss) {
-                float4* L = reinterpret_cast<float4*>(lacc) + __float_as_uint(c_pid);  // {blue, path id} came with the ray
-                float4 v = *L;
-                *L = make_float4(v.x + c_r, v.y + c_g, v.z + c_b, 0.0f);
-            }
-            if (COUNT) {
-                en += any ? 0u : cn;
-                et += any ? 0u : ct;
-                sn += any ? cn : 0u;
-                stt += any ? ct : 0u;
-                el += any ? 0u : cl;
-                sl += any ? cl : 0u;
-            }
-        },
-        true, sh_rays, n_sh, work_sh, true, s_top, use_top, reinterpret_cast<const float2*>(contrib));
-    if (COUNT && totals) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            atomicAdd(&totals[0], (unsigned long long)n_ext);
-            atomicAdd(&totals[3], (unsigned long long)n_sh);
-        }
-        atomicAdd(&totals[1], en);
-        atomicAdd(&totals[2], et);
-        atomicAdd(&totals[4], sn);
-        atomicAdd(&totals[5], stt);
-        atomicAdd(&totals[6], el);  // (= d_totals[10], [11]: node visits served by the LDS copy, closest / any)
-        atomicAdd(&totals[7], sl);
     }
 }
 
@@ -1198,71 +1130,42 @@ static inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks)
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride) {
     hipLaunchKernelGGL(k_raygen, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, g, pixels, npix, rays, stride);
 }
+// The k_extend / k_shadow instance of (count, layout): `launch` is called with std::integral_constant<bool, COUNT> and
+// std::integral_constant<int, LAYOUT>.  A layout that is none of the named ones runs as kLayoutBinary64.
+template <typename Launch>
+static void dispatch_traversal(bool count, int layout, Launch launch) {
+    auto by_layout = [&](auto c) {
+        if (layout == kLayoutTwoLevel) launch(c, std::integral_constant<int, kLayoutTwoLevel>{});
+        else if (layout == kLayoutWide48Q) launch(c, std::integral_constant<int, kLayoutWide48Q>{});
+        else if (layout == kLayoutWide64Q) launch(c, std::integral_constant<int, kLayoutWide64Q>{});
+        else if (layout == kLayoutWide128) launch(c, std::integral_constant<int, kLayoutWide128>{});
+        else launch(c, std::integral_constant<int, kLayoutBinary64>{});
+    };
+    if (count) by_layout(std::true_type{});
+    else by_layout(std::false_type{});
+}
+// totals: the base of the context's counter block (TotalsWord) or nullptr
 void launch_extend(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
                    const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct,
                    unsigned long long* totals, uint32_t* work_counter, bool payload) {
-    unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
-#define RT3_LAUNCH_EXTEND(C, L)                                                                                                                  \
-    hipLaunchKernelGGL((k_extend<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr, count_imm, hits, cn, ct, totals, \
-                       work_counter, payload ? 1 : 0, totals ? totals + 10 : nullptr /* the context's totals block: [10] = LDS-served visits, closest hit */)
-    if (count) {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_EXTEND(true, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(true, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_EXTEND(true, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_EXTEND(true, kLayoutWide128);
-        else RT3_LAUNCH_EXTEND(true, kLayoutBinary64);
-    } else {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_EXTEND(false, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_EXTEND(false, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_EXTEND(false, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_EXTEND(false, kLayoutWide128);
-        else RT3_LAUNCH_EXTEND(false, kLayoutBinary64);
-    }
-#undef RT3_LAUNCH_EXTEND
+    const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
+    unsigned long long* const tot = totals ? totals + kTotExtendNodes : nullptr;
+    unsigned long long* const lds_tot = totals ? totals + kTotExtendLds : nullptr;
+    dispatch_traversal(count, layout, [&](auto c, auto l) {
+        hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr,
+                           count_imm, hits, cn, ct, tot, work_counter, payload ? 1 : 0, lds_tot);
+    });
 }
 void launch_shadow(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
                    const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc,
                    size_t lstride, uint32_t* occluded_out, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter) {
-    unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
-#define RT3_LAUNCH_SHADOW(C, L)                                                                                                                \
-    hipLaunchKernelGGL((k_shadow<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, \
-                       lstride, occluded_out, cn, ct, totals, work_counter, totals ? totals + 9 : nullptr /* totals = block + 2 here: block[11] = LDS-served visits, any hit */)
-    if (count) {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_SHADOW(true, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(true, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_SHADOW(true, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_SHADOW(true, kLayoutWide128);
-        else RT3_LAUNCH_SHADOW(true, kLayoutBinary64);
-    } else {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_SHADOW(false, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_SHADOW(false, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_SHADOW(false, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_SHADOW(false, kLayoutWide128);
-        else RT3_LAUNCH_SHADOW(false, kLayoutBinary64);
-    }
-#undef RT3_LAUNCH_SHADOW
-}
-void launch_trace(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* ext_rays, const float* sh_rays,
-                  size_t stride, const uint32_t* ext_count, const uint32_t* sh_count, uint32_t max_n, float* hits, const float* contrib, float* lacc,
-                  unsigned long long* totals, uint32_t* work_ext, uint32_t* work_sh) {
-    unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
-#define RT3_LAUNCH_TRACE(C, L)                                                                                                                  \
-    hipLaunchKernelGGL((k_trace<C, L>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, ext_rays, sh_rays, stride, ext_count, sh_count, hits, \
-                       contrib, lacc, totals, work_ext, work_sh)
-    if (count) {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_TRACE(true, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(true, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_TRACE(true, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_TRACE(true, kLayoutWide128);
-        else RT3_LAUNCH_TRACE(true, kLayoutBinary64);
-    } else {
-        if (layout == kLayoutTwoLevel) RT3_LAUNCH_TRACE(false, kLayoutTwoLevel);
-        else if (layout == kLayoutWide48Q) RT3_LAUNCH_TRACE(false, kLayoutWide48Q);
-        else if (layout == kLayoutWide64Q) RT3_LAUNCH_TRACE(false, kLayoutWide64Q);
-        else if (layout == kLayoutWide128) RT3_LAUNCH_TRACE(false, kLayoutWide128);
-        else RT3_LAUNCH_TRACE(false, kLayoutBinary64);
-    }
-#undef RT3_LAUNCH_TRACE
+    const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
+    unsigned long long* const tot = totals ? totals + kTotShadowNodes : nullptr;
+    unsigned long long* const lds_tot = totals ? totals + kTotShadowLds : nullptr;
+    dispatch_traversal(count, layout, [&](auto c, auto l) {
+        hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr,
+                           count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot);
+    });
 }
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth) {

@@ -736,8 +736,9 @@ def test_error_behaviour(small):
     assert lib.rt3_image_create(ctx.h, 64, 64, 12345, C.byref(img)) == L.E_INVALID
     assert lib.rt3_image_create(ctx.h, 64, 64, L.FORMAT_R32_SFLOAT, C.byref(img)) == 0
     assert img.value >> 30 == L.TAG_IMAGE
-    # option 13 (the retired host SAH top) is unknown
+    # options 13 (the retired host SAH top) and 10 (the retired fused traversal launch) are unknown
     assert lib.rt3_set_option(ctx.h, 13, 0) == L.E_INVALID and lib.rt3_set_option(ctx.h, 13, 1) == L.E_INVALID
+    assert lib.rt3_set_option(ctx.h, 10, 0) == L.E_INVALID and lib.rt3_set_option(ctx.h, 10, 1) == L.E_INVALID
     # sky radiance must be finite and non-negative (a NaN would poison every CDF entry after it); the oracle applies the same contract
     for bad_value in (np.nan, np.inf, -1.0):
         bad_sky = np.ones((4, 8, 3), np.float32)
@@ -906,30 +907,35 @@ def test_full_size_frame_properties():
     assert np.array_equal(olight[y0:y0 + 64, x0:x0 + 64].view(np.uint32), a[y0:y0 + 64, x0:x0 + 64].view(np.uint32))
 
 
-def test_fused_and_separate_traversal_launches_agree(small):
-    """RT3_OPT_FUSED_TRACE: one k_trace launch per bounce (extension queue, then shadow queue) vs k_shadow + k_extend: same
-    image, same ray counts, same traversal counters; k_trace's own counters cover exactly its launches."""
+def test_traversal_counting_keeps_the_frame(small):
+    """RT3_OPT_COUNT_TRAVERSAL 0 vs 1: the same image bit for bit and the same ray counts; the counting run fills every traversal
+    total (the LDS-served visits are a part of their kind's node visits); k_shadow (NEE on) and k_extend are launched exactly as
+    pass_reference_mode issues them, and the stats of the retired fused launch stay 0."""
     mesh, sky, bn, osc = small
-    W, H = 128, 72
+    W, H, B = 128, 72, 4
+    assert SPEC & L.F_NEE_SKY
     out = {}
-    for fused in (0, 1):
+    for count in (0, 1):
         pt = PathTracer((W, H))
-        pt.ctx.set_option(L.OPT_FUSED_TRACE, fused)
-        pt.ctx.set_option(L.OPT_COUNT_TRAVERSAL, 1)
+        pt.ctx.set_option(L.OPT_COUNT_TRAVERSAL, count)
         pt.set_scene(mesh, sky, bn)
         cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(65.0), W / H)
-        g = pt.make_gconst(cam, 4, 4, frame=2, flags=SPEC)
+        g = pt.make_gconst(cam, 4, B, frame=2, flags=SPEC)
         pt.ctx.set_option(L.OPT_PROFILE, 1)
         pt.render(g)
-        out[fused] = (pt.light(), pt.ctx.stats())
+        out[count] = (pt.light(), pt.ctx.stats())
         pt.close()
     (la, sa), (lb, sb) = out[0], out[1]
     assert np.array_equal(la.view(np.uint32), lb.view(np.uint32))
+    assert sa.extension_rays == sb.extension_rays and sa.shadow_rays == sb.shadow_rays
     for f in ("extension_rays", "shadow_rays", "nodes_visited", "tris_tested", "shadow_nodes_visited", "shadow_tris_tested"):
-        assert getattr(sa, f) == getattr(sb, f) > 0, f
-    assert sa.trace_launches == 0 and sb.trace_launches == 3 and sb.extend_launches == 1 and sb.shadow_launches == 1
-    assert sb.trace_rays[0] == sb.extension_rays - W * H  # every bounce ray, not the primary rays of the gbuffer pass
-    assert 0 < sb.trace_rays[1] < sb.shadow_rays and 0 < sb.trace_nodes[0] < sb.nodes_visited and 0 < sb.trace_nodes[1] < sb.shadow_nodes_visited
+        assert getattr(sb, f) > 0, f
+    assert 0 < sb.nodes_visited_lds < sb.nodes_visited and 0 < sb.shadow_nodes_visited_lds < sb.shadow_nodes_visited
+    for s in (sa, sb):
+        # the gbuffer pass's extend, one extend per bounce but the last, one shadow per bounce
+        assert s.extend_launches == 1 + (B - 1) and s.shadow_launches == B
+        assert s.trace_launches == 0 and s.trace_ms == 0.0
+        assert list(s.trace_rays) == list(s.trace_nodes) == list(s.trace_tris) == [0, 0]
 
 
 def test_multi_rank_gather_rehearsal(tmp_path):

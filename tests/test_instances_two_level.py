@@ -181,13 +181,12 @@ def test_two_level_hits_bit_for_bit():
     ctx0.close()
 
 
-def render(mesh, inst, mode, sky, bn, g, fused, probes=None):
+def render(mesh, inst, mode, sky, bn, g, probes=None):
     W, H = int(g.window_size[0]), int(g.window_size[1])
     pt = PathTracer((W, H))
     pt.set_scene(mesh, sky, bn)
     pt.ctx.set_instances(inst)
     pt.ctx.set_option(L.OPT_INSTANCE_MODE, mode)
-    pt.ctx.set_option(L.OPT_FUSED_TRACE, fused)
     pt.ctx.build_accel()
     pt.render(g)
     out = [pt.light(), *pt.gbuffer()]
@@ -215,13 +214,12 @@ def test_two_level_frame_bit_identical():
     og = as_orc(g)
     ogb, odepth = osc.gbuffer(og)
     olight, _ = osc.reference_mode(og, ogb, odepth)
-    for fused in (0, 1):
-        light, gb, depth, atlas, plight = render(room, inst, 1, sky, bn, g, fused, probes=gp)
-        assert np.array_equal(bits(depth), bits(odepth)) and np.array_equal(gb, ogb)
-        assert np.array_equal(bits(light), bits(olight))
-        light0, gb0, depth0, atlas0, plight0 = render(room, inst, 0, sky, bn, g, fused, probes=gp)
-        assert np.array_equal(bits(light), bits(light0)) and np.array_equal(gb, gb0) and np.array_equal(bits(depth), bits(depth0))
-        assert np.array_equal(bits(atlas), bits(atlas0)) and np.array_equal(bits(plight), bits(plight0))
+    light, gb, depth, atlas, plight = render(room, inst, 1, sky, bn, g, probes=gp)
+    assert np.array_equal(bits(depth), bits(odepth)) and np.array_equal(gb, ogb)
+    assert np.array_equal(bits(light), bits(olight))
+    light0, gb0, depth0, atlas0, plight0 = render(room, inst, 0, sky, bn, g, probes=gp)
+    assert np.array_equal(bits(light), bits(light0)) and np.array_equal(gb, gb0) and np.array_equal(bits(depth), bits(depth0))
+    assert np.array_equal(bits(atlas), bits(atlas0)) and np.array_equal(bits(plight), bits(plight0))
     assert olight[..., :3].mean() > 0
 
 

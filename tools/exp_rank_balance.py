@@ -21,7 +21,6 @@ cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"]
 import os
 from raytracer3_amd import _lib as L
 
-FUSED = int(os.environ.get("RT3_EXP_FUSED", "-1"))  # -1: library default
 CHUNK = int(os.environ.get("RT3_EXP_CHUNK", "0"))
 BLOCKS = int(os.environ.get("RT3_EXP_BLOCKS", "0"))
 NS = [int(x) for x in os.environ.get("RT3_EXP_N", "2,4,8").split(",")]
@@ -29,8 +28,6 @@ NS = [int(x) for x in os.environ.get("RT3_EXP_N", "2,4,8").split(",")]
 
 def timed(rank, n):
     pt = PathTracer((W, H), device=0, rank=rank, n_ranks=n)
-    if FUSED >= 0:
-        pt.ctx.set_option(L.OPT_FUSED_TRACE, FUSED)
     if CHUNK:
         pt.ctx.set_option(L.OPT_POOL_CHUNK, CHUNK)
     if BLOCKS:
