@@ -203,6 +203,21 @@ int rt3_accel_levels(rt3_ctx *ctx, uint32_t *n_meshes, uint32_t *n_meshes_built,
  * the host (range, no node reachable twice, depth) before a kernel may follow it.  Triangle records may repeat a primitive (spatial
  * splits): the closest hit is decided by (t, prim), not by the record.  Used by tests/experiments/tree_quality_gpu.py. */
 int rt3_accel_import(rt3_ctx *ctx, const void *nodes, size_t nodes_bytes, const void *tris, size_t tris_bytes);
+/* ---- update after the vertices moved (what VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR is to the reference's driver, raytracing.rs:88-148):
+ *      skinning, cloth, morph targets, an editor dragging vertices.  DESIGN.md section 4c. ---- */
+/* overwrite vertices [first, first + n) in place (same 32-byte Vertex layout as rt3_scene_set_vertices); the index buffer, geometry and
+ * instances are untouched.  Marks an existing acceleration structure stale: rt3_pass_launch / rt3_trace_rays / rt3_accel_download return
+ * RT3_E_STATE until rt3_accel_refit or rt3_accel_build.  A range past the vertex buffer, or a position that is not finite (or beyond 1e18),
+ * is RT3_E_INVALID and changes nothing; n = 0 is a no-op. */
+int rt3_scene_update_vertices(rt3_ctx *ctx, const float *interleaved_p_n_t, uint32_t first, uint32_t n);
+/* update of the last build: same nodes, same references, same triangle-record order; every box, every triangle record, the shading records
+ * and the LDS top-of-tree copy recomputed from the current vertices (leaf pad and all from the new bounds).  Hits equal those of a fresh
+ * build over the same vertices bit for bit (closest hits are decided by (t, prim), not by the tree); only traversal visits differ.
+ * RT3_E_STATE without a structure, or when anything but vertex contents changed since rt3_accel_build (vertex count, indices, geometry,
+ * instances, a tree option); RT3_E_UNSUPPORTED for any node layout but the default.  Works after rt3_accel_import and in both instance
+ * modes (mode 1: every bottom tree, then the instance records and the top tree; rt3_accel_levels then reports 0 meshes built).  Does not
+ * change rt3_stats.accel_build_ms. */
+int rt3_accel_refit(rt3_ctx *ctx, uint32_t *out_handle);
 /* sky tables for parity tests (any pointer may be NULL): per-row alias words q16 | alias << 16 (w*h), RGB9E5 texels (w*h),
  * marginal CDF (h), realised (u,v) density (w*h) */
 int rt3_sky_download(rt3_ctx *ctx, uint32_t *alias, uint32_t *texels_rgb9e5, float *cdf_marg, float *pdf_uv);

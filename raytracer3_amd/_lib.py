@@ -27,6 +27,7 @@ EXPORTS = [
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
+    "rt3_scene_update_vertices", "rt3_accel_refit",
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
@@ -118,6 +119,8 @@ def load():
         "rt3_accel_download": (i32, [vp, vp, sz, vp, sz]),
         "rt3_accel_import": (i32, [vp, vp, sz, vp, sz]),
         "rt3_sky_download": (i32, [vp, vp, vp, vp, vp]),
+        "rt3_scene_update_vertices": (i32, [vp, vp, u32, u32]),
+        "rt3_accel_refit": (i32, [vp, pu32]),
         "rt3_buffer_create": (i32, [vp, sz, pu32]),
         "rt3_image_create": (i32, [vp, u32, u32, u32, pu32]),
         "rt3_image_import": (i32, [vp, vp, u32, u32, u32, pu32]),

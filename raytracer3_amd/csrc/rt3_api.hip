@@ -66,12 +66,19 @@ struct TlMesh {
     uint32_t n_nodes, n_tris, depth;
     double box[6];                      // the root's (quantised, conservative) object-space box
 };
+struct TlInstance {                     // one placement: the inverse of its matrix as the record holds it (fp32 values, in double)
+    double A[3][3], b[3];
+    float m[16];                        // object -> world, column-major (rt3_instance::transform)
+    uint32_t mesh, prim_base;           // mesh = ~0u: the instance places no triangles
+    bool identity;
+};
 struct TwoLevelState {
     bool valid = false;                 // c->bvh holds a two-level structure whose bottom trees match `meshes`
     uint64_t gen = 0;
     uint32_t head = 0;                  // nodes before the first bottom tree: top capacity + 2 per instance
     uint32_t n_alloc_nodes = 0;         // nodes of the combined array
     std::vector<TlMesh> meshes;
+    std::vector<TlInstance> inst;       // the instances of that build (a refit redoes their records and the top tree)
     std::vector<uint32_t> shade_key;    // (first, count) of every instance the shading records were made for
     uint64_t shade_gen = 0;
     bool shade_valid = false;
@@ -144,7 +151,19 @@ struct rt3_ctx {
     int opt_variant = 0;  // RT3_OPT_EXTEND_VARIANT: reserved for traversal experiments
     uint32_t opt_leaf_size = 2, opt_node_width = 4, opt_node_quant = 1, opt_collapse = 2, opt_sah_top = 1;
     int opt_instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
-    uint64_t scene_gen = 1;     // bumped by everything a bottom tree depends on (vertices, indices, geometry, leaf size, collapse, SAH top)
+    // generations: topo_gen is bumped by everything a tree's shape depends on (vertex count, indices, geometry, leaf size, layout, collapse,
+    // SAH top); content_gen by all of that and by rt3_scene_update_vertices too.  A refit needs the topology of the build it updates; the
+    // two-level structure keeps its bottom trees while the content is what they were built (or refitted) for
+    uint64_t topo_gen = 1, content_gen = 1;
+    uint64_t accel_topo_gen = 0;  // topo_gen of the last successful rt3_accel_build
+    bool accel_stale = false;     // vertices updated since the structure was built or refitted: nothing traces it until a refit or build
+    // refit plans (rt3_refit.hip), made on the first refit after a build or import: one per tree (instance mode 1: one per bottom tree)
+    bool refit_planned = false;
+    std::vector<RefitTree> refit_trees;
+    std::vector<DevBuf<char>> refit_tables;  // instance mode 1: each bottom tree's identity table, first_prim, prim_geom (tl_build_mesh's)
+    DevBuf<float> refit_box;                 // scratch: 6 floats per node, then 6 per triangle record
+    size_t refit_box_cap = 0;
+    DevBuf<uint32_t> refit_bounds;
     TwoLevelState tl;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
@@ -728,19 +747,22 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             if (value < 1 || value > 8) return fail(c, RT3_E_INVALID, "leaf size must be 1..8");
             c->opt_leaf_size = (uint32_t)value;
             c->accel_built = false;
-            c->scene_gen++;
+            c->topo_gen++;
+            c->content_gen++;
             return RT3_OK;
         case RT3_OPT_NODE_QUANT:
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "node quantisation must be 0 (fp32), 1 (64 B) or 2 (compact 48 B)");
             c->opt_node_quant = (uint32_t)value;
             c->accel_built = false;
-            c->scene_gen++;
+            c->topo_gen++;
+            c->content_gen++;
             return RT3_OK;
         case RT3_OPT_SAH_TOP:
             if (value < 0 || value > 65536) return fail(c, RT3_E_INVALID, "SAH-top cluster size must be 0 (off) .. 65536");
             c->opt_sah_top = (uint32_t)value;
             c->accel_built = false;
-            c->scene_gen++;
+            c->topo_gen++;
+            c->content_gen++;
             return RT3_OK;
         case RT3_OPT_POOL_CHUNK:
             if (value < 64 || value > 65536 || (value & 63)) return fail(c, RT3_E_INVALID, "pool chunk must be a multiple of 64 in [64, 65536]");
@@ -755,13 +777,15 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "wide collapse must be 0 (even depth), 1 (surface area) or 2 (cost-driven)");
             c->opt_collapse = (uint32_t)value;
             c->accel_built = false;
-            c->scene_gen++;
+            c->topo_gen++;
+            c->content_gen++;
             return RT3_OK;
         case RT3_OPT_NODE_WIDTH:
             if (value != 2 && value != 4) return fail(c, RT3_E_INVALID, "node width must be 2 or 4");
             c->opt_node_width = (uint32_t)value;
             c->accel_built = false;
-            c->scene_gen++;
+            c->topo_gen++;
+            c->content_gen++;
             return RT3_OK;
         case RT3_OPT_INSTANCE_MODE:
             if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "instance mode must be 0 (flatten) or 1 (two-level)");
@@ -785,7 +809,23 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (n) HIPC(c, hipMemcpy(c->d_verts.get(), v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->n_verts = n;
     c->accel_built = false;
-    c->scene_gen++;
+    c->topo_gen++;
+    c->content_gen++;
+    return RT3_OK;
+}
+// vertices [first, first + n) in place; the shape of every tree stays, so a structure built before is stale, not gone (rt3_accel_refit)
+int rt3_scene_update_vertices(rt3_ctx* c, const float* v, uint32_t first, uint32_t n) {
+    if (!c || (!v && n)) return fail(c, RT3_E_INVALID, "vertices NULL");
+    if ((uint64_t)first + n > c->n_verts) return fail(c, RT3_E_INVALID, "update_vertices: [first, first + n) exceeds the vertex buffer (rt3_scene_set_vertices)");
+    for (size_t i = 0; i < (size_t)n; i++)  // rt3_scene_set_vertices' check
+        for (int k = 0; k < 3; k++)
+            if (!(std::fabs(v[8 * i + k]) <= 1.0e18f)) return fail(c, RT3_E_INVALID, "vertex " + std::to_string(first + i) + ": position is not finite (or beyond 1e18)");
+    if (n == 0) return RT3_OK;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));  // work in flight may still read the old vertices
+    c->content_gen++;
+    if (c->accel_built) c->accel_stale = true;
+    HIPC(c, hipMemcpy(c->d_verts.get() + 8 * (size_t)first, v, (size_t)n * 32, hipMemcpyHostToDevice));
     return RT3_OK;
 }
 int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
@@ -796,7 +836,8 @@ int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
     c->n_indices = n;
     c->h_indices.assign(idx, idx + n);
     c->accel_built = false;
-    c->scene_gen++;
+    c->topo_gen++;
+    c->content_gen++;
     return RT3_OK;
 }
 // bounds of every geometry's index / vertex range against the world buffers as they are NOW: the kernels index them without
@@ -834,7 +875,8 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->max_tex_index = max_tex;
     c->n_prims = (uint32_t)total;
     c->accel_built = false;
-    c->scene_gen++;
+    c->topo_gen++;
+    c->content_gen++;
     return RT3_OK;
 }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
@@ -1172,6 +1214,7 @@ static float round_up(double x) {
     return (double)f < x ? std::nextafter(f, INFINITY) : f;
 }
 
+static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, const std::vector<TlMesh>& meshes);
 static int build_two_level(rt3_ctx* c) {
     if (c->opt_node_width != 4 || c->opt_node_quant != 1)
         return fail(c, RT3_E_UNSUPPORTED, "instance mode 1 (two-level) needs the default node layout: RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1");
@@ -1186,12 +1229,7 @@ static int build_two_level(rt3_ctx* c) {
     const size_t n_inst = c->h_instances.empty() ? 1 : c->h_instances.size();
 
     // ---- matrices: the inverse (double, then fp32) and its conditioning; meshes = distinct geometry runs that hold triangles
-    struct InstInfo {
-        double A[3][3], b[3];
-        uint32_t mesh, prim_base;
-        bool identity;
-    };
-    std::vector<InstInfo> ii(n_inst);
+    std::vector<TlInstance> ii(n_inst);
     std::vector<TlMesh> meshes;
     uint32_t total = 0;
     for (size_t i = 0; i < n_inst; i++) {
@@ -1201,7 +1239,8 @@ static int build_two_level(rt3_ctx* c) {
             for (int k = 0; k < 3; k++) M[r][k] = m[4 * k + r];
         const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
                            M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-        InstInfo& in = ii[i];
+        TlInstance& in = ii[i];
+        memcpy(in.m, m, sizeof(in.m));
         in.identity = memcmp(m, kIdentity, sizeof(kIdentity)) == 0;
         if (!(std::fabs(det) > 0.0) || !std::isfinite(1.0 / det))
             return fail(c, RT3_E_UNSUPPORTED, "instance " + std::to_string(i) + ": the upper 3 x 3 of the transform is singular (instance mode 1 needs its inverse)");
@@ -1251,13 +1290,13 @@ static int build_two_level(rt3_ctx* c) {
     const uint32_t head = top_cap + 2u * n_ne;
 
     // ---- bottom trees: kept while the meshes, the generation and the head are what the last build had
-    bool same = tl.valid && tl.gen == c->scene_gen && tl.head == head && tl.meshes.size() == meshes.size();
+    bool same = tl.valid && tl.gen == c->content_gen && tl.head == head && tl.meshes.size() == meshes.size();
     for (size_t q = 0; same && q < meshes.size(); q++) same = tl.meshes[q].first == meshes[q].first && tl.meshes[q].count == meshes[q].count;
     tl.n_built = 0;
     if (same) {
         meshes = tl.meshes;
     } else {
-        const bool reuse = tl.valid && tl.gen == c->scene_gen;
+        const bool reuse = tl.valid && tl.gen == c->content_gen;
         std::vector<LbvhResult> built(meshes.size());
         std::vector<int> from(meshes.size(), -1);
         int rc = RT3_OK;
@@ -1314,7 +1353,7 @@ static int build_two_level(rt3_ctx* c) {
         c->bvh.tris = std::move(tris);
         tl.meshes = meshes;
         tl.head = head;
-        tl.gen = c->scene_gen;
+        tl.gen = c->content_gen;
         tl.n_alloc_nodes = (uint32_t)nodes_total;
         tl.valid = true;
     }
@@ -1325,7 +1364,7 @@ static int build_two_level(rt3_ctx* c) {
         key[2 * i] = inst[i].geometry_first;
         key[2 * i + 1] = inst[i].geometry_count;
     }
-    if (!(tl.shade_valid && tl.shade_gen == c->scene_gen && tl.shade_key == key)) {
+    if (!(tl.shade_valid && tl.shade_gen == c->content_gen && tl.shade_key == key)) {
         tl.shade_valid = false;
         if (int r = dev_alloc(c, c->bvh.tri_shade, (size_t)c->n_flat_prims)) return r;
         if (int r = dev_alloc(c, c->bvh.tri_uv, 3 * (size_t)c->n_flat_prims)) return r;
@@ -1333,20 +1372,31 @@ static int build_two_level(rt3_ctx* c) {
                          c->bvh.tri_shade.get(), c->bvh.tri_uv.get());
         HIPC(c, hipGetLastError());
         tl.shade_key = key;
-        tl.shade_gen = c->scene_gen;
+        tl.shade_gen = c->content_gen;
         tl.shade_valid = true;
     }
 
-    // ---- instance records and world boxes (host, a few KiB), then the top tree (GPU)
+    tl.inst = ii;
+    return tl_records_and_top(c, tl.inst, meshes);
+}
+
+// The instance records and world boxes (host, a few KiB), then the top tree (GPU), over bottom trees that are in place: the tail of a
+// two-level build, and what a refit redoes after the bottom trees' boxes moved.
+static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, const std::vector<TlMesh>& meshes) {
+    TwoLevelState& tl = c->tl;
+    const size_t n_inst = ii.size();
+    uint32_t n_ne = 0;
+    for (auto& in : ii) n_ne += in.mesh != ~0u ? 1u : 0u;
+    const uint32_t top_cap = n_ne ? n_ne : 1u;
     std::vector<uint32_t> rec((size_t)32 * n_ne);
     std::vector<float> boxes((size_t)6 * n_ne);
     uint32_t slot = 0, max_bottom = 0;
     for (size_t i = 0; i < n_inst; i++) {
-        const InstInfo& in = ii[i];
+        const TlInstance& in = ii[i];
         if (in.mesh == ~0u) continue;
         const TlMesh& ms = meshes[in.mesh];
         max_bottom = ms.depth > max_bottom ? ms.depth : max_bottom;
-        const float* m = inst[i].transform;
+        const float* m = in.m;
         double nA = 0.0, nM = 0.0, tM = 0.0, Bobj = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
         for (int r = 0; r < 3; r++) {
             nA = std::fmax(nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
@@ -1468,6 +1518,8 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     // until the rebuild has succeeded: a failed one (the geometry tables reallocated by flatten_world included) must leave
     // RT3_E_STATE behind, not an empty tree or one that points at freed tables
     c->accel_built = false;
+    c->accel_stale = false;
+    c->refit_planned = false;
     if (int r = flatten_world(c)) return r;
     if (c->opt_instance_mode == 1) {
         if (int r = build_two_level(c)) return r;
@@ -1476,6 +1528,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
         c->stats.accel_bulk_copies += c->bulk_copies;
         c->bulk_copies = 0;
         c->accel_built = true;
+        c->accel_topo_gen = c->topo_gen;
         if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
         return RT3_OK;
     }
@@ -1500,6 +1553,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     c->stats.accel_bulk_copies += c->bulk_copies;
     c->bulk_copies = 0;
     c->accel_built = true;
+    c->accel_topo_gen = c->topo_gen;
     if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
     return RT3_OK;
 }
@@ -1525,6 +1579,7 @@ int rt3_accel_levels(rt3_ctx* c, uint32_t* n_meshes, uint32_t* n_meshes_built, u
 }
 int rt3_accel_download(rt3_ctx* c, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes) {
     if (!c || !c->accel_built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
     if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_download: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (nodes) {
         if (nodes_bytes != (size_t)c->bvh.n_nodes * c->bvh.node_bytes) return fail(c, RT3_E_INVALID, "nodes_bytes mismatch");
@@ -1589,11 +1644,142 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     c->bvh.n_nodes = nn;
     c->bvh.n_tris = nt;
     c->bvh.max_depth = depth;
+    c->refit_planned = false;
     e = lbvh_make_top(c->stream, c->bvh.nodes.get(), nn, c->bvh.top, &c->bvh.n_top);
     if (e != hipSuccess) {
         c->accel_built = false;
         return fail(c, RT3_E_HIP, std::string("accel_import: top-of-tree copy: ") + hipGetErrorString(e));
     }
+    return RT3_OK;
+}
+
+// ---- refit (rt3_refit.hip): the last build's trees, their boxes and triangle records recomputed from the current vertices
+static int refit_scratch(rt3_ctx* c, size_t n_nodes, size_t n_tris) {
+    const size_t need = 24 * (n_nodes + n_tris);
+    if (!c->refit_bounds) HIPC(c, c->refit_bounds.alloc_bytes(32));
+    if (need > c->refit_box_cap) {
+        c->refit_box_cap = 0;
+        HIPC(c, c->refit_box.alloc_bytes(need));
+        c->refit_box_cap = need;
+    }
+    return RT3_OK;
+}
+static int refit_flat(rt3_ctx* c) {
+    LbvhResult& b = c->bvh;
+    if (b.n_nodes) {
+        if (!c->refit_planned) {
+            c->refit_trees.clear();
+            c->refit_trees.resize(1);
+            const hipError_t e = refit_plan(c->stream, b.nodes.get(), 0u, b.n_nodes, b.max_depth, &c->refit_trees[0]);
+            if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
+            c->refit_planned = true;
+        }
+        if (int r = refit_scratch(c, b.n_nodes, b.n_tris)) return r;
+        float* nbox = c->refit_box.get();
+        hipError_t e = refit_tree(c->stream, c->refit_trees[0], c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
+                                  c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)b.n_nodes);
+        if (e == hipSuccess) e = lbvh_make_top(c->stream, b.nodes.get(), b.n_nodes, b.top, &b.n_top);
+        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: ") + hipGetErrorString(e));
+    }
+    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
+                     b.tri_shade.get(), b.tri_uv.get());
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+// instance mode 1: every bottom tree in the combined arrays (object space, its own bounds and pad, as tl_build_mesh builds it), then the
+// instance records and the top tree over the bottom trees' new root boxes
+static int refit_two_level(rt3_ctx* c) {
+    TwoLevelState& tl = c->tl;
+    if (tl.valid) {
+        const std::vector<TlMesh>& meshes = tl.meshes;
+        const size_t nm = meshes.size();
+        // per bottom tree: [identity table | first_prim | prim_geom], each at a 256-byte boundary
+        auto tables = [&](size_t q, size_t* off_fp, size_t* off_pg) {
+            *off_fp = ((size_t)meshes[q].count * sizeof(FlatGeomDev) + 255) & ~(size_t)255;
+            *off_pg = *off_fp + (((size_t)meshes[q].count * 4 + 255) & ~(size_t)255);
+            return *off_pg + (size_t)meshes[q].n_tris * 4;
+        };
+        if (!c->refit_planned) {
+            c->refit_trees.clear();
+            c->refit_trees.resize(nm);
+            c->refit_tables.clear();
+            c->refit_tables.resize(nm);
+            for (size_t q = 0; q < nm; q++) {
+                const TlMesh& m = meshes[q];
+                std::vector<FlatGeomDev> tbl(m.count);
+                std::vector<uint32_t> fp(m.count);
+                uint32_t tot = 0;
+                for (uint32_t k = 0; k < m.count; k++) {
+                    FlatGeomDev& f = tbl[k];
+                    memset(&f, 0, sizeof(f));
+                    memcpy(&f.g, &c->h_geoms[m.first + k], sizeof(f.g));
+                    f.m[0] = f.m[4] = f.m[8] = 1.0f;
+                    f.identity = 1u;
+                    f.geom = m.first + k;
+                    fp[k] = tot;
+                    tot += c->h_prim_counts[m.first + k];
+                }
+                size_t off_fp, off_pg;
+                const size_t bytes = tables(q, &off_fp, &off_pg);
+                char* base = nullptr;
+                HIPC(c, c->refit_tables[q].alloc_bytes(bytes));
+                base = c->refit_tables[q].get();
+                HIPC(c, hipMemcpy(base, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice));
+                HIPC(c, hipMemcpy(base + off_fp, fp.data(), fp.size() * 4, hipMemcpyHostToDevice));
+                if (tbl.size() * sizeof(FlatGeomDev) > (64u << 10)) c->bulk_copies += 1;
+                launch_prim_geom(c->stream, (const uint32_t*)(base + off_fp), m.count, m.n_tris, (uint32_t*)(base + off_pg));
+                const hipError_t e = refit_plan(c->stream, c->bvh.nodes.get(), m.node_off, m.n_nodes, m.depth, &c->refit_trees[q]);
+                if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
+            }
+            c->refit_planned = true;
+        }
+        if (int r = refit_scratch(c, tl.n_alloc_nodes, c->bvh.n_tris)) return r;
+        float* nbox = c->refit_box.get();
+        std::vector<uint32_t> roots(16 * nm);
+        hipError_t e = hipSuccess;
+        for (size_t q = 0; e == hipSuccess && q < nm; q++) {
+            const TlMesh& m = meshes[q];
+            size_t off_fp, off_pg;
+            (void)tables(q, &off_fp, &off_pg);
+            const char* base = c->refit_tables[q].get();
+            e = refit_tree(c->stream, c->refit_trees[q], c->d_verts.get(), c->d_indices.get(), (const FlatGeomDev*)base, (const uint32_t*)(base + off_pg),
+                           (const uint32_t*)(base + off_fp), m.n_tris, m.tri_off, m.n_tris, c->bvh.nodes.get(), c->bvh.tris.get(), c->refit_bounds.get(), nbox,
+                           nbox + 6 * (size_t)tl.n_alloc_nodes);
+            if (e == hipSuccess) e = hipMemcpyAsync(&roots[16 * q], c->bvh.nodes.get() + 4 * (size_t)m.node_off, 64, hipMemcpyDeviceToHost, c->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: bottom trees: ") + hipGetErrorString(e));
+        for (size_t q = 0; q < nm; q++) quantised_node_box(&roots[16 * q], tl.meshes[q].box);
+        tl.gen = c->content_gen;  // the bottom trees now match the vertices: a later build that only moved instances keeps them
+    }
+    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
+                     c->bvh.tri_shade.get(), c->bvh.tri_uv.get());
+    HIPC(c, hipGetLastError());
+    tl.shade_gen = c->content_gen;
+    tl.n_built = 0;
+    if (!tl.valid) return RT3_OK;  // nothing placed: no trees
+    const std::vector<TlInstance> inst = tl.inst;
+    const std::vector<TlMesh> meshes = tl.meshes;
+    return tl_records_and_top(c, inst, meshes);
+}
+int rt3_accel_refit(rt3_ctx* c, uint32_t* out_handle) {
+    if (!c) return RT3_E_INVALID;
+    if (c->opt_node_width != 4 || c->opt_node_quant != 1)
+        return fail(c, RT3_E_UNSUPPORTED, "accel_refit: default node layout only (RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1)");
+    if (!c->accel_built || c->accel_topo_gen != c->topo_gen)
+        return fail(c, RT3_E_STATE, "accel_refit: no acceleration structure for the current scene (only rt3_scene_update_vertices may come between rt3_accel_build and a refit)");
+    const bool two = c->bvh.layout == kLayoutTwoLevel;
+    if (!two && c->bvh.layout != kLayoutWide64Q) return fail(c, RT3_E_UNSUPPORTED, "accel_refit: default node layout only");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->accel_built = false;  // until the refit has succeeded: a failed one leaves boxes of neither the old nor the new vertices
+    if (int r = two ? refit_two_level(c) : refit_flat(c)) return r;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->stats.accel_bulk_copies += c->bulk_copies;
+    c->bulk_copies = 0;
+    c->accel_built = true;
+    c->accel_stale = false;
+    if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
     return RT3_OK;
 }
 
@@ -1885,6 +2071,7 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
     if (!constants || constants_size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "constants must be the 304-byte GConst block");
     if (!bindings && n_bindings) return fail(c, RT3_E_INVALID, "bindings NULL");
     if (!c->accel_built) return fail(c, RT3_E_STATE, "rt3_accel_build has not been called for the current scene");
+    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
     HIPC(c, hipSetDevice(c->device));
     if (int r = sync_textures(c)) return r;
     if (c->max_tex_index >= (int64_t)c->h_tex.size())
@@ -1915,6 +2102,7 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
                    uint32_t* n_tris, int repeat, double* kernel_ms) {
     if (!c || !rays || !prim || (!any_hit && (!t || !u || !v))) return fail(c, RT3_E_INVALID, "trace_rays: NULL argument");
     if (!c->accel_built) return fail(c, RT3_E_STATE, "rt3_accel_build has not been called for the current scene");
+    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
     DevBuf<float> d_rays, d_hits;

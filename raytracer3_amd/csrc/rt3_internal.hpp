@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "rt3_device.hpp"
 
 #define RT3_FLAG_NEE_SKY 1u
@@ -197,6 +199,21 @@ void tlas_box_tris(hipStream_t st, const float* boxes, uint32_t n, float* verts,
 // copy the top tree built over those triangles to dst, its leaf references (one triangle each) now naming instance records:
 // 0x80000000 | (rec_base + 2 * instance slot)
 void tlas_emit_top(hipStream_t st, const float4* top_nodes, uint32_t n_nodes, const float4* top_tris, uint32_t rec_base, float4* dst);
+
+// Refit (rt3_refit.hip) of a quantised 64-byte four-wide tree in place, after its vertices moved (rt3_accel_refit).  The plan comes from the
+// node array alone: the internal nodes reachable from `root`, level by level (order[] holds level 0, then level 1, ...).
+struct RefitTree {
+    DevBuf<uint32_t> order;
+    std::vector<uint32_t> level_count;
+};
+// max_depth: the tree's levels down to the leaf slots (LbvhResult::max_depth); hipErrorInvalidValue if the node array disagrees with it
+hipError_t refit_plan(hipStream_t st, const float4* nodes, uint32_t root, uint32_t n_nodes, uint32_t max_depth, RefitTree* plan);
+// Rewrites the triangle records [tri_first, tri_first + n_tris) from their primitives (fetched through geoms / prim_geom / first_prim; the
+// leaf pad from the bounds of primitives 0 .. n_prims-1) and then every node of the plan.  Scratch: bounds (6 words), nbox (6 floats per
+// node of `nodes`), tbox (6 floats per record of `tris`).
+hipError_t refit_tree(hipStream_t st, const RefitTree& plan, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                      const uint32_t* first_prim, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes, float4* tris, uint32_t* bounds,
+                      float* nbox, float* tbox);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

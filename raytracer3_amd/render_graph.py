@@ -196,6 +196,18 @@ class Context:
         self.check(self.lib.rt3_accel_build(self.h, C.byref(out)))
         return out.value
 
+    def update_vertices(self, vertices, first=0):
+        """overwrite vertices [first, first + len(vertices)) in place (rt3_scene_update_vertices; rows of the 8-float Vertex).  A built
+        structure is stale until refit_accel() or build_accel()."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 8)
+        self.check(self.lib.rt3_scene_update_vertices(self.h, v.ctypes.data, int(first), len(v)))
+
+    def refit_accel(self) -> int:
+        """recompute the boxes of the last build from the current vertices, same topology (rt3_accel_refit)"""
+        out = C.c_uint32()
+        self.check(self.lib.rt3_accel_refit(self.h, C.byref(out)))
+        return out.value
+
     def accel_import(self, nodes, tris):
         """install a tree built elsewhere over the same triangles (rt3_accel_download's format)"""
         n = np.ascontiguousarray(nodes)

@@ -70,6 +70,11 @@ class PathTracer:
             self.ctx.set_bluenoise(bluenoise)
         self._accel = self.ctx.build_accel()
 
+    def update_vertices(self, vertices, first=0):
+        """deformed vertices (same topology): upload them and refit the acceleration structure"""
+        self.ctx.update_vertices(vertices, first)
+        self._accel = self.ctx.refit_accel()
+
     def make_gconst(self, camera: Camera, samples, bounces=4, frame=0, blendfactor=1.0, flags=DEFAULT_FLAGS) -> L.GConst:
         g = camera.gconst(self.window)
         g.frame, g.samples, g.bounces, g.blendfactor = frame, samples, bounces, blendfactor

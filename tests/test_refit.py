@@ -1,0 +1,433 @@
+"""Refit after vertex updates (rt3_scene_update_vertices + rt3_accel_refit) on the GPU.
+
+Closest hits are decided by (t, prim) and any hits by "some triangle within (tmin, tmax]", neither by the tree, so a refitted tree must
+give the same t, u, v, prim and the same any-hit answers, bit for bit, as a fresh build over the same vertices and as the oracle's own
+tree; only visit counts may differ.  Covered: four deformations (a smooth wave, one geometry moved out of its boxes, a scale that must
+grow the leaf pad, a geometry collapsed to a point) of two scenes at the origin and at 1e4, whole and partial updates; the refitted
+structure itself (references, triangle records, conservative boxes); a path-traced frame; 30 chained refits; instance mode 1; an
+imported tree; the error codes; and the cost against a build."""
+import statistics
+import time
+import zlib
+
+import numpy as np
+import pytest
+
+import orc
+from raytracer3_amd import _lib as L
+from raytracer3_amd import assets, scenes
+from raytracer3_amd.render_graph import Context
+from raytracer3_amd.renderer import Camera, PathTracer
+from test_instances_two_level import as_orc, check_hits, cornell_world, make_rays
+from test_traversal_exactness_cpu import DISPUTED_MAX, brute, check_against_brute, interval_rays, placed, ray_families
+
+pytestmark = pytest.mark.gpu
+
+FAR = (1e4, 1e4, 1e4)
+DEFORMS = ("wave", "move", "scale", "collapse")
+MOVED = {"cornell": "tall", "atrium": "col0_3"}
+FLAGS = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD | L.F_SPECULAR
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def scene(name, offset):
+    return placed(scenes.cornell() if name == "cornell" else scenes.atrium(0.2), 1.0, offset)
+
+
+def with_vertices(mesh, v):
+    return assets.Mesh(np.ascontiguousarray(v, np.float32), mesh.indices, mesh.geometries, mesh.prim_counts, list(mesh.names), list(mesh.textures))
+
+
+def geometry_vertices(mesh, gname):
+    """the contiguous vertex range [lo, hi) the triangles of geometry `gname` use"""
+    g = mesh.geometries[mesh.names.index(gname)]
+    cnt = int(mesh.prim_counts[mesh.names.index(gname)])
+    idx = mesh.indices[int(g["index_offset"]):int(g["index_offset"]) + 3 * cnt].astype(np.int64) + int(g["vertex_offset"])
+    return int(idx.min()), int(idx.max()) + 1
+
+
+def wave(mesh, amplitude, phase=0.0):
+    """every position displaced by a smooth wave of `amplitude` x the scene extent"""
+    v = mesh.vertices.copy()
+    p = v[:, :3].astype(np.float64)
+    lo, hi = p.min(0), p.max(0)
+    ext = float((hi - lo).max())
+    s = (p - lo) / ext
+    d = np.stack([np.sin(2 * np.pi * (s[:, 1] + s[:, 2]) + phase), np.sin(2 * np.pi * (s[:, 0] - s[:, 2]) + 1.3 * phase),
+                  np.cos(2 * np.pi * (s[:, 0] + s[:, 1]) + 0.7 * phase)], 1)
+    v[:, :3] = (p + amplitude * ext * d).astype(np.float32)
+    return v
+
+
+def deform(mesh, kind, gname):
+    """(deformed vertices, the vertex range an update has to send)"""
+    v = mesh.vertices.copy()
+    if kind == "wave":
+        return wave(mesh, 0.01), (0, len(v))
+    if kind == "scale":
+        v[:, :3] = (v[:, :3].astype(np.float64) * 1000.0 + 1e4).astype(np.float32)
+        return v, (0, len(v))
+    lo, hi = geometry_vertices(mesh, gname)
+    if kind == "move":  # 1 m up and sideways: out of its old boxes and out of the top-of-tree copy's
+        v[lo:hi, :3] = (v[lo:hi, :3].astype(np.float64) + [0.7, 1.0, -0.4]).astype(np.float32)
+    else:  # collapse: every vertex of the geometry onto its first one -- degenerate triangles
+        v[lo:hi, :3] = v[lo, :3]
+    return v, (lo, hi)
+
+
+def upload(ctx, v, rng, partial):
+    """send v[lo:hi] in one call, or split into a few calls"""
+    lo, hi = partial
+    if hi - lo < 8:
+        ctx.update_vertices(v[lo:hi], lo)
+        return
+    cuts = sorted(set([lo, hi] + [int(x) for x in rng.integers(lo + 1, hi, 3)]))
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        ctx.update_vertices(v[a:b], a)
+
+
+def built(mesh, **opts):
+    ctx = Context(0)
+    for k, val in opts.items():
+        ctx.set_option(k, val)
+    ctx.upload_mesh(mesh)
+    ctx.build_accel()
+    return ctx
+
+
+def leaf_pad(tri):
+    """the fp32 leaf pad of k_leaves / k_refit_tris from the scene bounds"""
+    p = tri.reshape(-1, 3)
+    lo, hi = p.min(0), p.max(0)
+    ext = np.float32(max(hi - lo))
+    mag = np.float32(max(np.abs(lo).max(), np.abs(hi).max()))
+    return max(np.float32(ext * np.float32(1e-5)), np.float32(mag * np.float32(2.0 ** -20)))
+
+
+def check_containment(nodes, tris):
+    """every child slot box of every node, decoded as the traversal decodes it (fp32 origin + q * step), contains in double the padded
+    boxes of all triangles below it"""
+    tv = tris[:, :9].copy().view(np.float32).reshape(-1, 3, 3)
+    pad = leaf_pad(tv)
+    tlo, thi = (tv.min(1) - pad).astype(np.float64), (tv.max(1) + pad).astype(np.float64)
+    order, stack = [], [0]
+    while stack:  # parents before children
+        n = stack.pop()
+        order.append(n)
+        stack += [int(r) for r in nodes[n, 10:14] if r != 0xFFFFFFFF and not r & 0x80000000]
+    need = {}
+    for n in reversed(order):
+        w = nodes[n]
+        org = w[0:3].view(np.float32)
+        step = np.array([w[3], w[14], w[15]], np.uint32).view(np.float32)
+        q = w[4:10].view(np.uint8)
+        lo_all, hi_all = np.full(3, np.inf), np.full(3, -np.inf)
+        for k in range(4):
+            r = int(w[10 + k])
+            if r == 0xFFFFFFFF:
+                continue
+            if r & 0x80000000:
+                first, cnt = r & 0x0FFFFFFF, ((r >> 28) & 7) + 1
+                lo, hi = tlo[first:first + cnt].min(0), thi[first:first + cnt].max(0)
+            else:
+                lo, hi = need[r]
+            dlo = (org + q[6 * k:6 * k + 3].astype(np.float32) * step).astype(np.float64)
+            dhi = (org + q[6 * k + 3:6 * k + 6].astype(np.float32) * step).astype(np.float64)
+            assert (dlo <= lo).all() and (dhi >= hi).all(), (n, k)
+            lo_all, hi_all = np.minimum(lo_all, lo), np.maximum(hi_all, hi)
+        need[n] = (lo_all, hi_all)
+
+
+def check_rays(tag, ctx, osc, mesh, seed, other=None, dmax=DISPUTED_MAX):
+    """closest / any hit = the oracle's tree bit for bit, the brute-force criterion, and (if given) = another context bit for bit"""
+    fams = ray_families(mesh, n=1000, seed=seed)
+    fams["interval"] = interval_rays(osc, np.concatenate([fams["random"], fams["vertex"]], 1))
+    for fam, rays in fams.items():
+        t, u, v, p, _ = ctx.trace_rays(rays)
+        ot, ou, ov, op = osc.trace_closest(rays)
+        assert np.array_equal(p, op) and np.array_equal(bits(t), bits(ot)) and np.array_equal(bits(u), bits(ou)) and np.array_equal(bits(v), bits(ov)), (tag, fam)
+        occ = ctx.trace_rays(rays, any_hit=True)[3]
+        assert np.array_equal(occ != 0, osc.trace_any(rays) != 0), (tag, fam)
+        ref, dp = brute(osc, rays)
+        check_against_brute(f"{tag} {fam}", (t, u, v, p), occ, ref, dp, dmax[fam])
+        if other is not None:
+            t2, u2, v2, p2, _ = other.trace_rays(rays)
+            assert np.array_equal(p2, p) and np.array_equal(bits(t2), bits(t)) and np.array_equal(bits(u2), bits(u)) and np.array_equal(bits(v2), bits(v)), (tag, fam)
+            assert np.array_equal(other.trace_rays(rays, any_hit=True)[3] != 0, occ != 0), (tag, fam)
+
+
+@pytest.mark.parametrize("kind", DEFORMS)
+@pytest.mark.parametrize("offset", [(0.0, 0.0, 0.0), FAR], ids=["origin", "far"])
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_refit_equals_oracle_and_rebuild(name, offset, kind):
+    mesh = scene(name, offset)
+    v, rng_partial = deform(mesh, kind, MOVED[name])
+    deformed = with_vertices(mesh, v)
+    ctx = built(mesh)
+    fresh = None
+    try:
+        info = ctx.accel_info()
+        nodes0, tris0 = ctx.accel_download()
+        upload(ctx, v, np.random.default_rng(1), rng_partial)
+        ctx.refit_accel()
+        assert ctx.accel_info() == info
+        nodes1, tris1 = ctx.accel_download()
+        # same references, same records in the same slots; the records' vertices are the rebuild's for the same primitive
+        assert np.array_equal(nodes1[:, 10:14], nodes0[:, 10:14])
+        assert np.array_equal(tris1[:, 9], tris0[:, 9]) and not tris1[:, 10:].any()
+        fresh = built(deformed)
+        _, tris_f = fresh.accel_download()
+        by_prim = np.empty_like(tris_f)
+        by_prim[tris_f[:, 9]] = tris_f
+        assert np.array_equal(tris1, by_prim[tris1[:, 9]])
+        check_containment(nodes1, tris1)
+        # the wave bends every shared edge of the Cornell room's large flat triangles into a crease, and a ray aimed at a crease meets both
+        # triangles at nearly the same t: there the fp32 and fp64 brute force part more often than DISPUTED_MAX["edge"] was measured for
+        # on flat tessellations (about 0.63 of the edge family at the origin).  Criteria 1 and 2 and the bit-exact equalities still hold.
+        dmax = dict(DISPUTED_MAX, edge=0.75) if (name, kind) == ("cornell", "wave") else DISPUTED_MAX
+        check_rays(f"{name} {offset} {kind}", ctx, orc.Scene(deformed), deformed, seed=zlib.crc32(f"{name} {kind}".encode()) & 0xFFFF, other=fresh, dmax=dmax)
+    finally:
+        ctx.close()
+        if fresh is not None:
+            fresh.close()
+
+
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_refit_of_unchanged_vertices_gives_back_the_build(name):
+    """min / max are exact and the refit writes nodes with the build's encoder: nothing moved, nothing changes"""
+    ctx = built(scene(name, FAR))
+    try:
+        nodes0, tris0 = ctx.accel_download()
+        ctx.refit_accel()
+        nodes1, tris1 = ctx.accel_download()
+        assert np.array_equal(nodes1, nodes0) and np.array_equal(tris1, tris0)
+    finally:
+        ctx.close()
+
+
+def test_frame_parity_after_refit():
+    """a deformed atrium, refitted: G-buffer, depth and radiance equal the oracle's bit for bit (k_extend, k_shadow, shading records)"""
+    mesh = scenes.atrium(0.3)
+    deformed = with_vertices(mesh, wave(mesh, 0.01, phase=0.4))
+    sky, bn = scenes.sky(512, 256), assets.load_bluenoise()
+    osc = orc.Scene(deformed, sky, bn)
+    W, H = 128, 72
+    pt = PathTracer((W, H))
+    try:
+        pt.set_scene(mesh, sky, bn)
+        pt.update_vertices(deformed.vertices)
+        cam = scenes.ATRIUM_CAMERA
+        g = pt.make_gconst(Camera(cam["position"], cam["direction"], np.radians(cam["fov_deg"]), W / H), 4, 4, frame=2, flags=FLAGS)
+        pt.render(g, postprocess=True)
+        light = pt.light()
+        gb, depth = pt.gbuffer()
+    finally:
+        pt.close()
+    og = as_orc(g)
+    ogb, odepth = osc.gbuffer(og)
+    assert np.array_equal(bits(depth), bits(odepth))
+    hit = depth != L.BACKGROUND_DEPTH
+    assert hit.mean() > 0.5
+    assert np.array_equal(gb[hit], ogb[hit])
+    olight, _ = osc.reference_mode(og, ogb, odepth)
+    assert np.array_equal(bits(light), bits(olight))
+
+
+def test_animation_chained_refits():
+    """30 wave frames, each refitted on the previous refit; no refit copies anything big between host and device"""
+    mesh = scenes.cornell()
+    ctx = built(mesh)
+    try:
+        ctx.stats_reset()
+        for f in range(30):
+            deformed = with_vertices(mesh, wave(mesh, 0.02, phase=0.35 * f))
+            ctx.update_vertices(deformed.vertices)
+            ctx.refit_accel()
+            osc = orc.Scene(deformed)
+            rays = ray_families(deformed, n=600, seed=f)["random"]
+            t, u, v, p, _ = ctx.trace_rays(rays)
+            ot, ou, ov, op = osc.trace_closest(rays)
+            assert np.array_equal(p, op) and np.array_equal(bits(t), bits(ot)) and np.array_equal(bits(u), bits(ou)) and np.array_equal(bits(v), bits(ov)), f
+            assert np.array_equal(ctx.trace_rays(rays, any_hit=True)[3] != 0, osc.trace_any(rays) != 0), f
+        assert ctx.stats().accel_bulk_copies == 0
+    finally:
+        ctx.close()
+
+
+def test_two_level_refit():
+    """instance mode 1: every bottom tree refitted in place, then the instance records and the top tree; no bottom tree rebuilt"""
+    room, inst, _ = cornell_world()
+    lo, hi = geometry_vertices(room, "tall")
+    v = room.vertices.copy()
+    v[lo:hi] = wave(room, 0.03)[lo:hi]
+    deformed = with_vertices(room, v)
+    ctxs = []
+    try:
+        c1 = Context(0)
+        ctxs.append(c1)
+        c1.upload_mesh(room)
+        c1.set_instances(inst)
+        c1.set_option(L.OPT_INSTANCE_MODE, 1)
+        c1.build_accel()
+        n_meshes = c1.accel_levels()[0]
+        c1.update_vertices(v[lo:hi], lo)
+        c1.refit_accel()
+        assert c1.accel_levels()[1] == 0
+        c0 = Context(0)
+        ctxs.append(c0)
+        c0.upload_mesh(deformed)
+        c0.set_instances(inst)
+        c0.build_accel()
+        osc = orc.Scene(deformed, instances=inst)
+        assert check_hits(c1, c0, osc, make_rays(osc, 4000, seed=3)) > 0.5
+        # an instance move after the refit: the top tree is rebuilt, the refitted bottom trees are kept
+        moved = [(f, n, m.copy()) for f, n, m in inst]
+        for _, _, m in moved[1:]:
+            m[:3, 3] += np.float32(0.05)
+        c1.set_instances(moved)
+        c1.build_accel()
+        assert c1.accel_levels()[1] == 0
+        c0.set_instances(moved)
+        c0.build_accel()
+        osc = orc.Scene(deformed, instances=moved)
+        check_hits(c1, c0, osc, make_rays(osc, 4000, seed=4))
+        # an update followed by a build (no refit) rebuilds every bottom tree
+        c1.update_vertices(room.vertices[lo:hi], lo)
+        c1.build_accel()
+        assert c1.accel_levels()[1] == n_meshes
+        c0.upload_mesh(room)
+        c0.set_instances(moved)
+        c0.build_accel()
+        osc = orc.Scene(room, instances=moved)
+        check_hits(c1, c0, osc, make_rays(osc, 4000, seed=5))
+    finally:
+        for c in ctxs:
+            c.close()
+
+
+def test_refit_after_import():
+    mesh = scene("atrium", FAR)
+    v, _ = deform(mesh, "move", MOVED["atrium"])
+    deformed = with_vertices(mesh, v)
+    ctx = built(mesh)
+    try:
+        nodes, tris = ctx.accel_download()
+        ctx.accel_import(nodes, tris)
+        ctx.update_vertices(v)
+        ctx.refit_accel()
+        check_rays("import", ctx, orc.Scene(deformed), deformed, seed=77)
+    finally:
+        ctx.close()
+
+
+def test_refit_errors():
+    mesh = scenes.cornell()
+    v = wave(mesh, 0.01)
+    rays = ray_families(mesh, n=200, seed=1)["random"]
+    ctx = Context(0)
+    try:
+        ctx.upload_mesh(mesh)
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.refit_accel()
+        assert e.value.code == L.E_STATE  # before a build
+        ctx.update_vertices(v)  # without a structure: only the vertices change
+        ctx.build_accel()
+        ref = ctx.trace_rays(rays)[:4]
+        n = len(mesh.vertices)
+        for first, cnt in ((n, 1), (n - 2, 3), (0xFFFFFFFF, 2)):
+            with pytest.raises(L.Rt3Error) as e:
+                ctx.update_vertices(np.zeros((cnt, 8), np.float32), first)
+            assert e.value.code == L.E_INVALID
+        bad = v[:4].copy()
+        bad[2, 1] = np.nan
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.update_vertices(bad, 10)
+        assert e.value.code == L.E_INVALID
+        bad[2, 1] = 2e18
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.update_vertices(bad, 10)
+        assert e.value.code == L.E_INVALID
+        ctx.update_vertices(v[:0], 5)  # n = 0: a no-op
+        out = ctx.trace_rays(rays)[:4]  # refused calls and the no-op left the structure usable
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(out, ref))
+        ctx.update_vertices(v[:4], 0)  # now stale
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.trace_rays(rays)
+        assert e.value.code == L.E_STATE
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.accel_download()
+        assert e.value.code == L.E_STATE
+        pt = PathTracer((32, 16))
+        try:
+            pt.set_scene(mesh)
+            pt.ctx.update_vertices(v[:4], 0)
+            cam = scenes.CORNELL_CAMERA if hasattr(scenes, "CORNELL_CAMERA") else dict(position=(0.0, 1.0, 3.0), direction=(0.0, 0.0, -1.0))
+            g = pt.make_gconst(Camera(cam["position"], cam["direction"], 1.0, 2.0), 1, 1)
+            with pytest.raises(L.Rt3Error) as e:
+                pt.render(g)
+            assert e.value.code == L.E_STATE
+            pt.ctx.refit_accel()
+            pt.render(g)
+        finally:
+            pt.close()
+        ctx.refit_accel()
+        ctx.trace_rays(rays)
+        # anything but vertex contents changed since the build: no refit
+        for change in (lambda: ctx.upload_mesh(mesh), lambda: ctx.set_instances([]), lambda: ctx.set_option(L.OPT_LEAF_SIZE, 2)):
+            ctx.build_accel()
+            change()
+            with pytest.raises(L.Rt3Error) as e:
+                ctx.refit_accel()
+            assert e.value.code == L.E_STATE
+        ctx.build_accel()
+        ctx.check(ctx.lib.rt3_scene_set_indices(ctx.h, mesh.indices.ctypes.data, len(mesh.indices)))
+        with pytest.raises(L.Rt3Error) as e:
+            ctx.refit_accel()
+        assert e.value.code == L.E_STATE
+    finally:
+        ctx.close()
+    for opt, val, mode in ((L.OPT_NODE_WIDTH, 2, 0), (L.OPT_NODE_QUANT, 0, 0), (L.OPT_NODE_QUANT, 2, 0), (L.OPT_NODE_WIDTH, 2, 1), (L.OPT_NODE_QUANT, 2, 1)):
+        c = Context(0)
+        try:
+            c.upload_mesh(mesh)
+            c.set_option(L.OPT_INSTANCE_MODE, mode)
+            c.set_option(opt, val)
+            if mode == 0:
+                c.build_accel()
+            with pytest.raises(L.Rt3Error) as e:
+                c.refit_accel()
+            assert e.value.code == L.E_UNSUPPORTED, (opt, val, mode)
+            if mode == 0:
+                c.trace_rays(rays)  # still usable
+        finally:
+            c.close()
+
+
+def test_refit_cost():
+    """on ~260 k triangles a refit costs at most a quarter of a build (median of 7 each, host clock around synchronised calls)"""
+    mesh = scenes.atrium(1.0)
+    deformed = wave(mesh, 0.005)
+    ctx = built(mesh)
+    try:
+        ctx.update_vertices(deformed)
+        ctx.refit_accel()
+        ctx.build_accel()
+
+        def clock(fn):
+            ctx.wait()
+            t0 = time.perf_counter()
+            fn()
+            ctx.wait()
+            return time.perf_counter() - t0
+
+        builds = [clock(ctx.build_accel) for _ in range(7)]
+        ctx.update_vertices(deformed)
+        refits = [clock(ctx.refit_accel) for _ in range(7)]
+        b, r = statistics.median(builds), statistics.median(refits)
+        print(f"atrium(1.0): build {b * 1e3:.2f} ms, refit {r * 1e3:.2f} ms")
+        assert r <= 0.25 * b, (r, b)
+    finally:
+        ctx.close()
