@@ -68,6 +68,7 @@ struct TlMesh {
 };
 struct TlInstance {                     // one placement: the inverse of its matrix as the record holds it (fp32 values, in double)
     double A[3][3], b[3];
+    double nA, nM;                      // row-sum norms of A and of the matrix's upper 3 x 3
     float m[16];                        // object -> world, column-major (rt3_instance::transform)
     uint32_t mesh, prim_base;           // mesh = ~0u: the instance places no triangles
     bool identity;
@@ -79,12 +80,26 @@ struct TwoLevelState {
     uint32_t n_alloc_nodes = 0;         // nodes of the combined array
     std::vector<TlMesh> meshes;
     std::vector<TlInstance> inst;       // the instances of that build (a refit redoes their records and the top tree)
-    std::vector<uint32_t> shade_key;    // (first, count) of every instance the shading records were made for
-    uint64_t shade_gen = 0;
-    bool shade_valid = false;
+    uint32_t n_placed = 0, top_cap = 0; // of `inst`: those that place triangles (records, top-tree leaves); top-tree node capacity
     uint32_t n_meshes = 0, n_built = 0, n_top = 0;
     DevBuf<char> scratch;               // top build inputs: boxes, degenerate triangles, identity table
     size_t scratch_cap = 0;
+};
+// A bottom tree's geometry tables: the identity table of its geometries as uploaded, first_prim and prim_geom (local primitive ids), in one
+// device allocation
+struct MeshTables {
+    DevBuf<char> mem;
+    FlatGeomDev* geoms = nullptr;
+    uint32_t *first_prim = nullptr, *prim_geom = nullptr;
+};
+// Shading records (k_tri_shade), per placed triangle in flattened order.  They depend on the flattening, the vertices and the indices, never
+// on a tree or a matrix.  `key` = what they were made for: content_gen, then (geometry_first, geometry_count) of every placement; empty
+// = nothing valid.
+struct ShadeRecords {
+    DevBuf<uint4> rec;
+    DevBuf<float2> uv;
+    uint32_t n = 0;  // records the buffers hold
+    std::vector<uint64_t> key;
 };
 
 }  // namespace
@@ -121,6 +136,7 @@ struct rt3_ctx {
     DevBuf<float> d_srgb_lut;
     bool tex_dirty = false;
     LbvhResult bvh;
+    ShadeRecords shade;
     BuildArena build_arena;
     bool accel_built = false;
     std::vector<uint32_t> h_indices;  // host copies, only for range validation (rt3_scene_set_geometry, again in rt3_accel_build)
@@ -160,7 +176,7 @@ struct rt3_ctx {
     // refit plans (rt3_refit.hip), made on the first refit after a build or import: one per tree (instance mode 1: one per bottom tree)
     bool refit_planned = false;
     std::vector<RefitTree> refit_trees;
-    std::vector<DevBuf<char>> refit_tables;  // instance mode 1: each bottom tree's identity table, first_prim, prim_geom (tl_build_mesh's)
+    std::vector<MeshTables> refit_tables;    // instance mode 1: each bottom tree's (tl_build_mesh's)
     DevBuf<float> refit_box;                 // scratch: 6 floats per node, then 6 per triangle record
     size_t refit_box_cap = 0;
     DevBuf<uint32_t> refit_bounds;
@@ -266,8 +282,8 @@ SceneDev scene_dev(const rt3_ctx* c) {
     s.n_geoms = c->n_flat_geoms;
     s.prim_geom = c->d_prim_geom.get();
     s.first_prim = c->d_first_prim.get();
-    s.tri_shade = c->bvh.tri_shade.get();
-    s.tri_uv = c->bvh.tri_uv.get();
+    s.tri_shade = c->shade.rec.get();
+    s.tri_uv = c->shade.uv.get();
     s.guide_marg = c->d_guide_marg.get();
     s.sky = c->d_sky.get();
     s.sky_alias = c->d_sky_alias.get();
@@ -283,6 +299,19 @@ SceneDev scene_dev(const rt3_ctx* c) {
     s.srgb_lut = c->d_srgb_lut.get();
     s.n_tex = c->d_tex_pixels ? (uint32_t)c->h_tex.size() : 0u;
     return s;
+}
+
+// a change every tree's shape depends on: the structure goes, and a refit cannot bring it back
+void invalidate_topology(rt3_ctx* c) {
+    c->accel_built = false;
+    c->topo_gen++;
+    c->content_gen++;
+}
+// RT3_OK when the structure may be traced: built, and no vertex updated since
+int check_accel_current(rt3_ctx* c, const char* unbuilt = "rt3_accel_build has not been called for the current scene") {
+    if (!c || !c->accel_built) return fail(c, RT3_E_STATE, unbuilt);
+    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
+    return RT3_OK;
 }
 
 // (re)build the device texture atlas after rt3_scene_set_texture calls
@@ -466,8 +495,8 @@ int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const 
     if (int r = reserve_counters(c, 1, &wc_slot)) return r;  // ray-pool cursor of the launch
     {
         ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[0].get(), S, nullptr, pl->count,
-                      pl->count, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
+        launch_extend(c->stream, c->opt_count, c->bvh, c->rays[0].get(), S, nullptr, pl->count, pl->count, c->hits.get(), nullptr, nullptr,
+                      c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
     }
     c->primary_rays_pending += pl->count;
     {
@@ -542,14 +571,13 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
             cur ^= 1;
             if (nee) {
                 ScopedTimer t(c, CAT_SHADOW);
-                launch_shadow(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->sh_rays.get(), S, sh_cnt_at(bn), 0,
-                              n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S, nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr,
-                              pool_cur + B + bn);
+                launch_shadow(c->stream, c->opt_count, c->bvh, c->sh_rays.get(), S, sh_cnt_at(bn), 0, n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S,
+                              nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + B + bn);
             }
             if (bn != B - 1) {
                 ScopedTimer t(c, CAT_EXTEND);
-                launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[cur].get(), S, ext_cnt_at(bn), 0,
-                              n_first, c->hits.get(), nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
+                launch_extend(c->stream, c->opt_count, c->bvh, c->rays[cur].get(), S, ext_cnt_at(bn), 0, n_first, c->hits.get(), nullptr, nullptr,
+                              c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
             }
         }
         {
@@ -636,8 +664,8 @@ int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, c
     if (int r = reserve_counters(c, 1, &wc_slot)) return r;
     {
         ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, c->rays[0].get(), S, nullptr, n, n, c->hits.get(),
-                      nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
+        launch_extend(c->stream, c->opt_count, c->bvh, c->rays[0].get(), S, nullptr, n, n, c->hits.get(), nullptr, nullptr,
+                      c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
     }
     c->primary_rays_pending += n;
     {
@@ -746,23 +774,17 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
         case RT3_OPT_LEAF_SIZE:
             if (value < 1 || value > 8) return fail(c, RT3_E_INVALID, "leaf size must be 1..8");
             c->opt_leaf_size = (uint32_t)value;
-            c->accel_built = false;
-            c->topo_gen++;
-            c->content_gen++;
+            invalidate_topology(c);
             return RT3_OK;
         case RT3_OPT_NODE_QUANT:
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "node quantisation must be 0 (fp32), 1 (64 B) or 2 (compact 48 B)");
             c->opt_node_quant = (uint32_t)value;
-            c->accel_built = false;
-            c->topo_gen++;
-            c->content_gen++;
+            invalidate_topology(c);
             return RT3_OK;
         case RT3_OPT_SAH_TOP:
             if (value < 0 || value > 65536) return fail(c, RT3_E_INVALID, "SAH-top cluster size must be 0 (off) .. 65536");
             c->opt_sah_top = (uint32_t)value;
-            c->accel_built = false;
-            c->topo_gen++;
-            c->content_gen++;
+            invalidate_topology(c);
             return RT3_OK;
         case RT3_OPT_POOL_CHUNK:
             if (value < 64 || value > 65536 || (value & 63)) return fail(c, RT3_E_INVALID, "pool chunk must be a multiple of 64 in [64, 65536]");
@@ -776,16 +798,12 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
         case RT3_OPT_WIDE_COLLAPSE:
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "wide collapse must be 0 (even depth), 1 (surface area) or 2 (cost-driven)");
             c->opt_collapse = (uint32_t)value;
-            c->accel_built = false;
-            c->topo_gen++;
-            c->content_gen++;
+            invalidate_topology(c);
             return RT3_OK;
         case RT3_OPT_NODE_WIDTH:
             if (value != 2 && value != 4) return fail(c, RT3_E_INVALID, "node width must be 2 or 4");
             c->opt_node_width = (uint32_t)value;
-            c->accel_built = false;
-            c->topo_gen++;
-            c->content_gen++;
+            invalidate_topology(c);
             return RT3_OK;
         case RT3_OPT_INSTANCE_MODE:
             if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "instance mode must be 0 (flatten) or 1 (two-level)");
@@ -808,9 +826,7 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (int r = dev_alloc(c, c->d_verts, (size_t)n * 8)) return r;
     if (n) HIPC(c, hipMemcpy(c->d_verts.get(), v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->n_verts = n;
-    c->accel_built = false;
-    c->topo_gen++;
-    c->content_gen++;
+    invalidate_topology(c);
     return RT3_OK;
 }
 // vertices [first, first + n) in place; the shape of every tree stays, so a structure built before is stale, not gone (rt3_accel_refit)
@@ -835,9 +851,7 @@ int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
     if (n) HIPC(c, hipMemcpy(c->d_indices.get(), idx, (size_t)n * 4, hipMemcpyHostToDevice));
     c->n_indices = n;
     c->h_indices.assign(idx, idx + n);
-    c->accel_built = false;
-    c->topo_gen++;
-    c->content_gen++;
+    invalidate_topology(c);
     return RT3_OK;
 }
 // bounds of every geometry's index / vertex range against the world buffers as they are NOW: the kernels index them without
@@ -874,9 +888,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->n_geoms = n;
     c->max_tex_index = max_tex;
     c->n_prims = (uint32_t)total;
-    c->accel_built = false;
-    c->topo_gen++;
-    c->content_gen++;
+    invalidate_topology(c);
     return RT3_OK;
 }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
@@ -1069,16 +1081,20 @@ int rt3_scene_set_instances(rt3_ctx* c, const rt3_instance* inst, uint32_t n) {
     c->accel_built = false;
     return RT3_OK;
 }
-// One (instance, geometry) pair per entry, instance-major; no instances = one identity instance of everything.  A few KiB of tables
-// go up; primitive -> entry is filled in on the device (k_prim_geom), so a rebuild after a moved instance copies nothing big.
-static int flatten_world(rt3_ctx* c) {
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    rt3_instance whole;
+static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+// The placements a build covers: the instances set, or (none) one identity instance of every geometry, which `whole` then holds
+static std::pair<const rt3_instance*, size_t> placements(const rt3_ctx* c, rt3_instance& whole) {
+    if (!c->h_instances.empty()) return {c->h_instances.data(), c->h_instances.size()};
     whole.geometry_first = 0;
     whole.geometry_count = c->n_geoms;
     memcpy(whole.transform, kIdentity, sizeof(kIdentity));
-    const rt3_instance* inst = c->h_instances.empty() ? &whole : c->h_instances.data();
-    const size_t n_inst = c->h_instances.empty() ? 1 : c->h_instances.size();
+    return {&whole, 1};
+}
+// One (instance, geometry) pair per entry, instance-major.  A few KiB of tables go up; primitive -> entry is filled in on the device
+// (k_prim_geom), so a rebuild after a moved instance copies nothing big.
+static int flatten_world(rt3_ctx* c) {
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
     std::vector<FlatGeomDev> flat;
     std::vector<ShadeGeomDev> shade;
     std::vector<uint32_t> first;
@@ -1131,6 +1147,31 @@ static int flatten_world(rt3_ctx* c) {
     c->n_flat_prims = (uint32_t)total;
     return RT3_OK;
 }
+// the shading records of the flattened world, remade only when what they depend on has changed since they were made
+static int make_shade_records(rt3_ctx* c) {
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
+    std::vector<uint64_t> key{c->content_gen};
+    for (size_t i = 0; i < n_inst; i++) {
+        key.push_back(inst[i].geometry_first);
+        key.push_back(inst[i].geometry_count);
+    }
+    ShadeRecords& s = c->shade;
+    if (key == s.key) return RT3_OK;
+    s.key.clear();  // until the new records are in place
+    if (!s.rec || !s.uv || s.n != c->n_flat_prims) {  // (a refit rewrites them in place)
+        if (int r = dev_alloc(c, s.rec, (size_t)c->n_flat_prims)) return r;
+        if (int r = dev_alloc(c, s.uv, 3 * (size_t)c->n_flat_prims)) return r;
+        s.n = c->n_flat_prims;
+    }
+    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
+                     s.rec.get(), s.uv.get());
+    HIPC(c, hipGetLastError());
+    s.key = std::move(key);
+    return RT3_OK;
+}
+// worst-case stack use of the near-first walk over a tree of `depth` levels: (children per node - 1) entries per level above the leaves
+static uint32_t stack_entries(uint32_t width, uint32_t depth) { return depth > 1 ? (width - 1) * (depth - 1) : 0; }
 
 // ---- two-level structure (RT3_OPT_INSTANCE_MODE 1): shared bottom trees under a top tree over instance records
 // Conservativeness of the two-level boxes: every box is grown by kTlPad times a bound on the magnitudes involved,
@@ -1139,7 +1180,6 @@ constexpr double kTlPad = 1.0 / 4096.0;
 constexpr double kTlMaxCondition = 1048576.0;
 static void tl_reset(rt3_ctx* c) {
     c->tl.valid = false;
-    c->tl.shade_valid = false;
     c->tl.meshes.clear();
     c->tl.n_meshes = c->tl.n_built = c->tl.n_top = 0;
     c->tl.n_alloc_nodes = 0;
@@ -1169,8 +1209,8 @@ static void quantised_node_box(const uint32_t* w, double box[6]) {
         }
     }
 }
-// one bottom tree: the geometries [first, first + count) as uploaded (identity table, local primitive ids)
-static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
+// the tables of a bottom tree over the geometries [first, first + count) as uploaded: identity matrices, local primitive ids
+static hipError_t make_mesh_tables(rt3_ctx* c, const TlMesh& m, MeshTables* t) {
     std::vector<FlatGeomDev> tbl(m.count);
     std::vector<uint32_t> fp(m.count);
     uint32_t tot = 0;
@@ -1184,18 +1224,25 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
         fp[k] = tot;
         tot += c->h_prim_counts[m.first + k];
     }
-    DevBuf<FlatGeomDev> d_tbl;
-    DevBuf<uint32_t> d_fp, d_pg;
-    hipError_t e = d_tbl.alloc_bytes(tbl.size() * sizeof(FlatGeomDev));
-    if (e == hipSuccess) e = d_fp.alloc_bytes(fp.size() * 4);
-    if (e == hipSuccess) e = d_pg.alloc_bytes((size_t)m.n_tris * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tbl.get(), tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_fp.get(), fp.data(), fp.size() * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_prim_geom(c->stream, d_fp.get(), m.count, m.n_tris, d_pg.get());
-        e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), d_tbl.get(), d_pg.get(), d_fp.get(), m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
+    // [identity table | first_prim | prim_geom], each at a 256-byte boundary
+    const size_t off_fp = (tbl.size() * sizeof(FlatGeomDev) + 255) & ~(size_t)255, off_pg = off_fp + ((fp.size() * 4 + 255) & ~(size_t)255);
+    hipError_t e = t->mem.alloc_bytes(off_pg + (size_t)m.n_tris * 4);
+    if (e != hipSuccess) return e;
+    t->geoms = reinterpret_cast<FlatGeomDev*>(t->mem.get());
+    t->first_prim = reinterpret_cast<uint32_t*>(t->mem.get() + off_fp);
+    t->prim_geom = reinterpret_cast<uint32_t*>(t->mem.get() + off_pg);
+    e = hipMemcpy(t->geoms, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->first_prim, fp.data(), fp.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) launch_prim_geom(c->stream, t->first_prim, m.count, m.n_tris, t->prim_geom);
+    return e;
+}
+// one bottom tree: the geometries [first, first + count) as uploaded
+static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
+    MeshTables t;
+    hipError_t e = make_mesh_tables(c, m, &t);
+    if (e == hipSuccess)
+        e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
                        c->opt_sah_top, c->build_arena, res);
-    }
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1214,19 +1261,14 @@ static float round_up(double x) {
     return (double)f < x ? std::nextafter(f, INFINITY) : f;
 }
 
-static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, const std::vector<TlMesh>& meshes);
+static int tl_records_and_top(rt3_ctx* c);
 static int build_two_level(rt3_ctx* c) {
     if (c->opt_node_width != 4 || c->opt_node_quant != 1)
         return fail(c, RT3_E_UNSUPPORTED, "instance mode 1 (two-level) needs the default node layout: RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1");
     TwoLevelState& tl = c->tl;
     if (!tl.valid) free_accel(c);  // what c->bvh holds is a flattened tree (or nothing)
-    static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     rt3_instance whole;
-    whole.geometry_first = 0;
-    whole.geometry_count = c->n_geoms;
-    memcpy(whole.transform, kIdentity, sizeof(kIdentity));
-    const rt3_instance* inst = c->h_instances.empty() ? &whole : c->h_instances.data();
-    const size_t n_inst = c->h_instances.empty() ? 1 : c->h_instances.size();
+    const auto [inst, n_inst] = placements(c, whole);
 
     // ---- matrices: the inverse (double, then fp32) and its conditioning; meshes = distinct geometry runs that hold triangles
     std::vector<TlInstance> ii(n_inst);
@@ -1258,12 +1300,12 @@ static int build_two_level(rt3_ctx* c) {
             for (int k = 0; k < 3; k++) in.A[r][k] = (double)(float)in.A[r][k];  // what the record holds
             in.b[r] = (double)(float)-(in.A[r][0] * m[12] + in.A[r][1] * m[13] + in.A[r][2] * m[14]);
         }
-        double nA = 0.0, nM = 0.0;
+        in.nA = in.nM = 0.0;
         for (int r = 0; r < 3; r++) {
-            nA = std::fmax(nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
-            nM = std::fmax(nM, std::fabs(M[r][0]) + std::fabs(M[r][1]) + std::fabs(M[r][2]));
+            in.nA = std::fmax(in.nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
+            in.nM = std::fmax(in.nM, std::fabs(M[r][0]) + std::fabs(M[r][1]) + std::fabs(M[r][2]));
         }
-        if (!std::isfinite(nA) || nA * nM > kTlMaxCondition)
+        if (!std::isfinite(in.nA) || in.nA * in.nM > kTlMaxCondition)
             return fail(c, RT3_E_UNSUPPORTED, "instance " + std::to_string(i) + ": the transform is too badly conditioned for instance mode 1 (||M|| ||M^-1|| > 2^20)");
         in.prim_base = total;
         uint32_t cnt = 0;
@@ -1357,37 +1399,20 @@ static int build_two_level(rt3_ctx* c) {
         tl.n_alloc_nodes = (uint32_t)nodes_total;
         tl.valid = true;
     }
-
-    // ---- shading records, per placed triangle in flattened order: they do not depend on the matrices
-    std::vector<uint32_t> key(2 * n_inst);
-    for (size_t i = 0; i < n_inst; i++) {
-        key[2 * i] = inst[i].geometry_first;
-        key[2 * i + 1] = inst[i].geometry_count;
-    }
-    if (!(tl.shade_valid && tl.shade_gen == c->content_gen && tl.shade_key == key)) {
-        tl.shade_valid = false;
-        if (int r = dev_alloc(c, c->bvh.tri_shade, (size_t)c->n_flat_prims)) return r;
-        if (int r = dev_alloc(c, c->bvh.tri_uv, 3 * (size_t)c->n_flat_prims)) return r;
-        launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
-                         c->bvh.tri_shade.get(), c->bvh.tri_uv.get());
-        HIPC(c, hipGetLastError());
-        tl.shade_key = key;
-        tl.shade_gen = c->content_gen;
-        tl.shade_valid = true;
-    }
-
-    tl.inst = ii;
-    return tl_records_and_top(c, tl.inst, meshes);
+    tl.inst = std::move(ii);
+    tl.n_placed = n_ne;
+    tl.top_cap = top_cap;
+    return tl_records_and_top(c);
 }
 
 // The instance records and world boxes (host, a few KiB), then the top tree (GPU), over bottom trees that are in place: the tail of a
 // two-level build, and what a refit redoes after the bottom trees' boxes moved.
-static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, const std::vector<TlMesh>& meshes) {
+static int tl_records_and_top(rt3_ctx* c) {
     TwoLevelState& tl = c->tl;
+    const std::vector<TlInstance>& ii = tl.inst;
+    const std::vector<TlMesh>& meshes = tl.meshes;  // (free_accel clears it: nothing reads it after that)
     const size_t n_inst = ii.size();
-    uint32_t n_ne = 0;
-    for (auto& in : ii) n_ne += in.mesh != ~0u ? 1u : 0u;
-    const uint32_t top_cap = n_ne ? n_ne : 1u;
+    const uint32_t n_ne = tl.n_placed, top_cap = tl.top_cap;
     std::vector<uint32_t> rec((size_t)32 * n_ne);
     std::vector<float> boxes((size_t)6 * n_ne);
     uint32_t slot = 0, max_bottom = 0;
@@ -1397,12 +1422,9 @@ static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, con
         const TlMesh& ms = meshes[in.mesh];
         max_bottom = ms.depth > max_bottom ? ms.depth : max_bottom;
         const float* m = in.m;
-        double nA = 0.0, nM = 0.0, tM = 0.0, Bobj = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int r = 0; r < 3; r++) {
-            nA = std::fmax(nA, std::fabs(in.A[r][0]) + std::fabs(in.A[r][1]) + std::fabs(in.A[r][2]));
-            nM = std::fmax(nM, std::fabs((double)m[r]) + std::fabs((double)m[4 + r]) + std::fabs((double)m[8 + r]));
-            tM = std::fmax(tM, std::fabs((double)m[12 + r]));
-        }
+        const double nA = in.nA, nM = in.nM;
+        double tM = 0.0, Bobj = 0.0, lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int r = 0; r < 3; r++) tM = std::fmax(tM, std::fabs((double)m[12 + r]));
         for (int k = 0; k < 6; k++) Bobj = std::fmax(Bobj, std::fabs(ms.box[k]));
         for (int corner = 0; corner < 8; corner++) {
             const double p[3] = {ms.box[(corner & 1) ? 3 : 0], ms.box[(corner & 2) ? 4 : 1], ms.box[(corner & 4) ? 5 : 2]};
@@ -1485,7 +1507,7 @@ static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, con
         return fail(c, RT3_E_HIP, std::string("two-level: top tree: ") + hipGetErrorString(e));
     }
     // stack bound: the top walk's entries below the instance leaf, then the bottom walk's (the hand-over pushes nothing)
-    const uint32_t stack_need = (top_depth > 1 ? 3 * (top_depth - 1) : 0) + (max_bottom > 1 ? 3 * (max_bottom - 1) : 0);
+    const uint32_t stack_need = stack_entries(4, top_depth) + stack_entries(4, max_bottom);
     if (stack_need > kMaxStack) {
         free_accel(c);
         return fail(c, RT3_E_DEPTH, "two-level structure needs " + std::to_string(stack_need) + " stack entries (top " + std::to_string(top_depth) +
@@ -1507,6 +1529,18 @@ static int tl_records_and_top(rt3_ctx* c, const std::vector<TlInstance>& ii, con
 }
 
 // ---- acceleration structure
+// the end of a successful build or refit: the shading records, then the structure goes live
+static int accel_finish(rt3_ctx* c, uint32_t* out_handle) {
+    if (int r = make_shade_records(c)) return r;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->stats.accel_bulk_copies += c->bulk_copies;
+    c->bulk_copies = 0;
+    c->accel_built = true;
+    c->accel_stale = false;
+    c->accel_topo_gen = c->topo_gen;  // (unchanged by a refit, which needs the build's)
+    if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
+    return RT3_OK;
+}
 int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     if (!c) return RT3_E_INVALID;
     HIPC(c, hipSetDevice(c->device));
@@ -1523,38 +1557,26 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     if (int r = flatten_world(c)) return r;
     if (c->opt_instance_mode == 1) {
         if (int r = build_two_level(c)) return r;
-        HIPC(c, hipStreamSynchronize(c->stream));
-        c->stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-        c->stats.accel_bulk_copies += c->bulk_copies;
-        c->bulk_copies = 0;
-        c->accel_built = true;
-        c->accel_topo_gen = c->topo_gen;
-        if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
-        return RT3_OK;
+    } else {
+        free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
+        hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
+                                  c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena,
+                                  &c->bvh);
+        if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
+        if (e != hipSuccess) {
+            free_accel(c);  // (what the failed build allocated)
+            return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
+        }
+        const uint32_t stack_need = stack_entries(c->opt_node_width, c->bvh.max_depth);
+        if (stack_need > kMaxStack) {
+            const int rc = fail(c, RT3_E_DEPTH, "LBVH with " + std::to_string(c->bvh.max_depth) + " levels needs " + std::to_string(stack_need) +
+                                                    " stack entries, the traversal kernels hold " + std::to_string(kMaxStack));
+            free_accel(c);  // (after the message: it clears max_depth)
+            return rc;
+        }
     }
-    free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
-    hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
-                              c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena, &c->bvh);
-    if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
-    if (e != hipSuccess) {
-        free_accel(c);  // (what the failed build allocated)
-        return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
-    }
-    // worst-case stack use of the near-first walk: (children per node - 1) entries per level above the leaves
-    const uint32_t stack_need = c->bvh.max_depth > 1 ? (c->opt_node_width - 1) * (c->bvh.max_depth - 1) : 0;
-    if (stack_need > kMaxStack) {
-        const int rc = fail(c, RT3_E_DEPTH, "LBVH with " + std::to_string(c->bvh.max_depth) + " levels needs " + std::to_string(stack_need) +
-                                                " stack entries, the traversal kernels hold " + std::to_string(kMaxStack));
-        free_accel(c);  // (after the message: it clears max_depth)
-        return rc;
-    }
-    HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = accel_finish(c, out_handle)) return r;
     c->stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-    c->stats.accel_bulk_copies += c->bulk_copies;
-    c->bulk_copies = 0;
-    c->accel_built = true;
-    c->accel_topo_gen = c->topo_gen;
-    if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
     return RT3_OK;
 }
 int rt3_accel_info(rt3_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* max_depth, uint32_t* node_bytes) {
@@ -1578,8 +1600,7 @@ int rt3_accel_levels(rt3_ctx* c, uint32_t* n_meshes, uint32_t* n_meshes_built, u
     return RT3_OK;
 }
 int rt3_accel_download(rt3_ctx* c, void* nodes, size_t nodes_bytes, void* tris, size_t tris_bytes) {
-    if (!c || !c->accel_built) return fail(c, RT3_E_STATE, "no acceleration structure built");
-    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
+    if (int r = check_accel_current(c, "no acceleration structure built")) return r;
     if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_download: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (nodes) {
         if (nodes_bytes != (size_t)c->bvh.n_nodes * c->bvh.node_bytes) return fail(c, RT3_E_INVALID, "nodes_bytes mismatch");
@@ -1629,7 +1650,7 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
         }
     }
     const uint32_t depth = max_level + 1;  // levels from the root to the leaf slots, as lbvh_build counts them
-    if (3u * (depth - 1) > kMaxStack) return fail(c, RT3_E_DEPTH, "accel_import: the tree is deeper than the traversal stack supports");
+    if (stack_entries(4, depth) > kMaxStack) return fail(c, RT3_E_DEPTH, "accel_import: the tree is deeper than the traversal stack supports");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     DevBuf<float4> d_nodes, d_tris;
@@ -1666,101 +1687,60 @@ static int refit_scratch(rt3_ctx* c, size_t n_nodes, size_t n_tris) {
 }
 static int refit_flat(rt3_ctx* c) {
     LbvhResult& b = c->bvh;
-    if (b.n_nodes) {
-        if (!c->refit_planned) {
-            c->refit_trees.clear();
-            c->refit_trees.resize(1);
-            const hipError_t e = refit_plan(c->stream, b.nodes.get(), 0u, b.n_nodes, b.max_depth, &c->refit_trees[0]);
-            if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
-            c->refit_planned = true;
-        }
-        if (int r = refit_scratch(c, b.n_nodes, b.n_tris)) return r;
-        float* nbox = c->refit_box.get();
-        hipError_t e = refit_tree(c->stream, c->refit_trees[0], c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                                  c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)b.n_nodes);
-        if (e == hipSuccess) e = lbvh_make_top(c->stream, b.nodes.get(), b.n_nodes, b.top, &b.n_top);
-        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: ") + hipGetErrorString(e));
+    if (!b.n_nodes) return RT3_OK;
+    if (!c->refit_planned) {
+        c->refit_trees.clear();
+        c->refit_trees.resize(1);
+        const hipError_t e = refit_plan(c->stream, b.nodes.get(), 0u, b.n_nodes, b.max_depth, &c->refit_trees[0]);
+        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
+        c->refit_planned = true;
     }
-    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
-                     b.tri_shade.get(), b.tri_uv.get());
-    HIPC(c, hipGetLastError());
+    if (int r = refit_scratch(c, b.n_nodes, b.n_tris)) return r;
+    float* nbox = c->refit_box.get();
+    hipError_t e = refit_tree(c->stream, c->refit_trees[0], c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
+                              c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)b.n_nodes);
+    if (e == hipSuccess) e = lbvh_make_top(c->stream, b.nodes.get(), b.n_nodes, b.top, &b.n_top);
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: ") + hipGetErrorString(e));
     return RT3_OK;
 }
 // instance mode 1: every bottom tree in the combined arrays (object space, its own bounds and pad, as tl_build_mesh builds it), then the
 // instance records and the top tree over the bottom trees' new root boxes
 static int refit_two_level(rt3_ctx* c) {
     TwoLevelState& tl = c->tl;
-    if (tl.valid) {
-        const std::vector<TlMesh>& meshes = tl.meshes;
-        const size_t nm = meshes.size();
-        // per bottom tree: [identity table | first_prim | prim_geom], each at a 256-byte boundary
-        auto tables = [&](size_t q, size_t* off_fp, size_t* off_pg) {
-            *off_fp = ((size_t)meshes[q].count * sizeof(FlatGeomDev) + 255) & ~(size_t)255;
-            *off_pg = *off_fp + (((size_t)meshes[q].count * 4 + 255) & ~(size_t)255);
-            return *off_pg + (size_t)meshes[q].n_tris * 4;
-        };
-        if (!c->refit_planned) {
-            c->refit_trees.clear();
-            c->refit_trees.resize(nm);
-            c->refit_tables.clear();
-            c->refit_tables.resize(nm);
-            for (size_t q = 0; q < nm; q++) {
-                const TlMesh& m = meshes[q];
-                std::vector<FlatGeomDev> tbl(m.count);
-                std::vector<uint32_t> fp(m.count);
-                uint32_t tot = 0;
-                for (uint32_t k = 0; k < m.count; k++) {
-                    FlatGeomDev& f = tbl[k];
-                    memset(&f, 0, sizeof(f));
-                    memcpy(&f.g, &c->h_geoms[m.first + k], sizeof(f.g));
-                    f.m[0] = f.m[4] = f.m[8] = 1.0f;
-                    f.identity = 1u;
-                    f.geom = m.first + k;
-                    fp[k] = tot;
-                    tot += c->h_prim_counts[m.first + k];
-                }
-                size_t off_fp, off_pg;
-                const size_t bytes = tables(q, &off_fp, &off_pg);
-                char* base = nullptr;
-                HIPC(c, c->refit_tables[q].alloc_bytes(bytes));
-                base = c->refit_tables[q].get();
-                HIPC(c, hipMemcpy(base, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(base + off_fp, fp.data(), fp.size() * 4, hipMemcpyHostToDevice));
-                if (tbl.size() * sizeof(FlatGeomDev) > (64u << 10)) c->bulk_copies += 1;
-                launch_prim_geom(c->stream, (const uint32_t*)(base + off_fp), m.count, m.n_tris, (uint32_t*)(base + off_pg));
-                const hipError_t e = refit_plan(c->stream, c->bvh.nodes.get(), m.node_off, m.n_nodes, m.depth, &c->refit_trees[q]);
-                if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
-            }
-            c->refit_planned = true;
-        }
-        if (int r = refit_scratch(c, tl.n_alloc_nodes, c->bvh.n_tris)) return r;
-        float* nbox = c->refit_box.get();
-        std::vector<uint32_t> roots(16 * nm);
-        hipError_t e = hipSuccess;
-        for (size_t q = 0; e == hipSuccess && q < nm; q++) {
-            const TlMesh& m = meshes[q];
-            size_t off_fp, off_pg;
-            (void)tables(q, &off_fp, &off_pg);
-            const char* base = c->refit_tables[q].get();
-            e = refit_tree(c->stream, c->refit_trees[q], c->d_verts.get(), c->d_indices.get(), (const FlatGeomDev*)base, (const uint32_t*)(base + off_pg),
-                           (const uint32_t*)(base + off_fp), m.n_tris, m.tri_off, m.n_tris, c->bvh.nodes.get(), c->bvh.tris.get(), c->refit_bounds.get(), nbox,
-                           nbox + 6 * (size_t)tl.n_alloc_nodes);
-            if (e == hipSuccess) e = hipMemcpyAsync(&roots[16 * q], c->bvh.nodes.get() + 4 * (size_t)m.node_off, 64, hipMemcpyDeviceToHost, c->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: bottom trees: ") + hipGetErrorString(e));
-        for (size_t q = 0; q < nm; q++) quantised_node_box(&roots[16 * q], tl.meshes[q].box);
-        tl.gen = c->content_gen;  // the bottom trees now match the vertices: a later build that only moved instances keeps them
-    }
-    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
-                     c->bvh.tri_shade.get(), c->bvh.tri_uv.get());
-    HIPC(c, hipGetLastError());
-    tl.shade_gen = c->content_gen;
     tl.n_built = 0;
     if (!tl.valid) return RT3_OK;  // nothing placed: no trees
-    const std::vector<TlInstance> inst = tl.inst;
-    const std::vector<TlMesh> meshes = tl.meshes;
-    return tl_records_and_top(c, inst, meshes);
+    const std::vector<TlMesh>& meshes = tl.meshes;
+    const size_t nm = meshes.size();
+    if (!c->refit_planned) {
+        c->refit_trees.clear();
+        c->refit_trees.resize(nm);
+        c->refit_tables.clear();
+        c->refit_tables.resize(nm);
+        for (size_t q = 0; q < nm; q++) {
+            const TlMesh& m = meshes[q];
+            hipError_t e = make_mesh_tables(c, m, &c->refit_tables[q]);
+            if (e == hipSuccess && m.count * sizeof(FlatGeomDev) > (64u << 10)) c->bulk_copies += 1;
+            if (e == hipSuccess) e = refit_plan(c->stream, c->bvh.nodes.get(), m.node_off, m.n_nodes, m.depth, &c->refit_trees[q]);
+            if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
+        }
+        c->refit_planned = true;
+    }
+    if (int r = refit_scratch(c, tl.n_alloc_nodes, c->bvh.n_tris)) return r;
+    float* nbox = c->refit_box.get();
+    std::vector<uint32_t> roots(16 * nm);
+    hipError_t e = hipSuccess;
+    for (size_t q = 0; e == hipSuccess && q < nm; q++) {
+        const TlMesh& m = meshes[q];
+        const MeshTables& t = c->refit_tables[q];
+        e = refit_tree(c->stream, c->refit_trees[q], c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, m.tri_off, m.n_tris,
+                       c->bvh.nodes.get(), c->bvh.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)tl.n_alloc_nodes);
+        if (e == hipSuccess) e = hipMemcpyAsync(&roots[16 * q], c->bvh.nodes.get() + 4 * (size_t)m.node_off, 64, hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: bottom trees: ") + hipGetErrorString(e));
+    for (size_t q = 0; q < nm; q++) quantised_node_box(&roots[16 * q], tl.meshes[q].box);
+    tl.gen = c->content_gen;  // the bottom trees now match the vertices: a later build that only moved instances keeps them
+    return tl_records_and_top(c);
 }
 int rt3_accel_refit(rt3_ctx* c, uint32_t* out_handle) {
     if (!c) return RT3_E_INVALID;
@@ -1774,13 +1754,7 @@ int rt3_accel_refit(rt3_ctx* c, uint32_t* out_handle) {
     HIPC(c, hipStreamSynchronize(c->stream));
     c->accel_built = false;  // until the refit has succeeded: a failed one leaves boxes of neither the old nor the new vertices
     if (int r = two ? refit_two_level(c) : refit_flat(c)) return r;
-    HIPC(c, hipStreamSynchronize(c->stream));
-    c->stats.accel_bulk_copies += c->bulk_copies;
-    c->bulk_copies = 0;
-    c->accel_built = true;
-    c->accel_stale = false;
-    if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
-    return RT3_OK;
+    return accel_finish(c, out_handle);
 }
 
 // ---- resources
@@ -2070,8 +2044,7 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
     if (entry && strcmp(entry, "main") != 0) return fail(c, RT3_E_INVALID, std::string("unknown entry point '") + entry + "' (the reference passes use \"main\")");
     if (!constants || constants_size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "constants must be the 304-byte GConst block");
     if (!bindings && n_bindings) return fail(c, RT3_E_INVALID, "bindings NULL");
-    if (!c->accel_built) return fail(c, RT3_E_STATE, "rt3_accel_build has not been called for the current scene");
-    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
+    if (int r = check_accel_current(c)) return r;
     HIPC(c, hipSetDevice(c->device));
     if (int r = sync_textures(c)) return r;
     if (c->max_tex_index >= (int64_t)c->h_tex.size())
@@ -2101,8 +2074,7 @@ int rt3_frame_wait(rt3_ctx* c) {
 int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float* t, float* u, float* v, uint32_t* prim, uint32_t* n_nodes,
                    uint32_t* n_tris, int repeat, double* kernel_ms) {
     if (!c || !rays || !prim || (!any_hit && (!t || !u || !v))) return fail(c, RT3_E_INVALID, "trace_rays: NULL argument");
-    if (!c->accel_built) return fail(c, RT3_E_STATE, "rt3_accel_build has not been called for the current scene");
-    if (c->accel_stale) return fail(c, RT3_E_STATE, "vertices were updated since the acceleration structure was built: rt3_accel_refit or rt3_accel_build first");
+    if (int r = check_accel_current(c)) return r;
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
     DevBuf<float> d_rays, d_hits;
@@ -2139,11 +2111,10 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
     auto launch = [&]() {
         (void)hipMemsetAsync(d_cur.get(), 0, 4, c->stream);  // ray-pool cursor
         if (any_hit)
-            launch_shadow(c->stream, count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, d_rays.get(), n, nullptr, n, n,
-                          nullptr, nullptr, nullptr, 0, d_occ.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
+            launch_shadow(c->stream, count, c->bvh, d_rays.get(), n, nullptr, n, n, nullptr, nullptr, nullptr, 0, d_occ.get(), d_cn.get(), d_ct.get(), nullptr,
+                          d_cur.get());
         else
-            launch_extend(c->stream, count, c->bvh.layout, c->bvh.nodes.get(), c->bvh.tris.get(), c->bvh.top.get(), c->bvh.n_top, d_rays.get(), n, nullptr, n, n,
-                          d_hits.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
+            launch_extend(c->stream, count, c->bvh, d_rays.get(), n, nullptr, n, n, d_hits.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
     };
     launch();  // warm-up (also the result-producing launch)
     HIPC(c, hipEventRecord(ev.e0, c->stream));

@@ -65,12 +65,6 @@ struct ShadeLaunch {
 };
 
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
-void launch_extend(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
-                   const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct,
-                   unsigned long long* totals, uint32_t* work_counter, bool payload = false);
-void launch_shadow(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
-                   const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc,
-                   size_t lstride, uint32_t* occluded_out, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
 void launch_shade(hipStream_t st, bool first, const ShadeLaunch& L);
@@ -169,12 +163,16 @@ struct LbvhResult {
     uint32_t node_bytes = 128;
     int layout = kLayoutWide128;
     DevBuf<float4> tris;       // n_tris x 3 float4 (48 B), Morton order
-    DevBuf<uint4> tri_shade;   // n_tris x 16 B, flattened primitive order: three octahedral vertex normals + flattened geometry index
-    DevBuf<float2> tri_uv;     // n_tris x 3 float2: vertex uvs
     DevBuf<float4> top;        // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
 };
+// traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
+void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
+                   uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, bool payload = false);
+void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
+                   uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
+                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter);
 // On failure *out may hold some of its arrays: they go with it.
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
@@ -185,7 +183,7 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
 hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t n, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
                               const float* lmin, const float* lmax, float* nbox, uint32_t T, BuildArena& arena, bool* relinked);
 
-// shading records (tri_shade, tri_uv) of n flattened primitives alone, without a tree (two-level builds: they do not depend on the matrices)
+// shading records (SceneDev::tri_shade, tri_uv) of n flattened primitives: they depend on no tree and no matrix
 void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n, uint4* tri_shade, float2* tri_uv);
 

@@ -1145,26 +1145,25 @@ static void dispatch_traversal(bool count, int layout, Launch launch) {
     else by_layout(std::false_type{});
 }
 // totals: the base of the context's counter block (TotalsWord) or nullptr
-void launch_extend(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
-                   const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct,
-                   unsigned long long* totals, uint32_t* work_counter, bool payload) {
+void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
+                   uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, bool payload) {
     const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
     unsigned long long* const tot = totals ? totals + kTotExtendNodes : nullptr;
     unsigned long long* const lds_tot = totals ? totals + kTotExtendLds : nullptr;
-    dispatch_traversal(count, layout, [&](auto c, auto l) {
-        hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr,
-                           count_imm, hits, cn, ct, tot, work_counter, payload ? 1 : 0, lds_tot);
+    dispatch_traversal(count, bvh.layout, [&](auto c, auto l) {
+        hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
+                           bvh.n_top, rays, stride, count_ptr, count_imm, hits, cn, ct, tot, work_counter, payload ? 1 : 0, lds_tot);
     });
 }
-void launch_shadow(hipStream_t st, bool count, int layout, const float4* nodes, const float4* tris, const float4* top, uint32_t n_top, const float* rays, size_t stride,
-                   const uint32_t* count_ptr, uint32_t count_imm, uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc,
-                   size_t lstride, uint32_t* occluded_out, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter) {
+void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
+                   uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
+                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter) {
     const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
     unsigned long long* const tot = totals ? totals + kTotShadowNodes : nullptr;
     unsigned long long* const lds_tot = totals ? totals + kTotShadowLds : nullptr;
-    dispatch_traversal(count, layout, [&](auto c, auto l) {
-        hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, nodes, tris, top, n_top, rays, stride, count_ptr,
-                           count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot);
+    dispatch_traversal(count, bvh.layout, [&](auto c, auto l) {
+        hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
+                           bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot);
     });
 }
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,

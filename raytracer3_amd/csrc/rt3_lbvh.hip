@@ -801,8 +801,6 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     }
     LB_CHECK(out->tris.alloc_bytes((size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
     LB_CHECK(hipMemsetAsync((char*)out->tris.get() + (size_t)n * 48, 0, 128, st));
-    LB_CHECK(out->tri_shade.alloc_bytes((size_t)n * 16));
-    LB_CHECK(out->tri_uv.alloc_bytes((size_t)n * 24));
     if (quant == 2 && n > 1) {
         LB_CHECK(arena.take(&tris_morton, (size_t)n * 48));
         LB_CHECK(arena.take(&n_int, (size_t)nn * 4));
@@ -814,7 +812,6 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     LB_CHECK(hipMemsetAsync(arrive, 0, (size_t)nn * 4, st));
     LB_CHECK(hipMemsetAsync(levels, 0, 4, st));
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, bmin, bmax, bounds);
-    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, out->tri_shade.get(), out->tri_uv.get());
     hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, bmin, bmax, bounds, n, keys_in, vals_in);
     LB_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
     LB_CHECK(arena.take(&temp, temp_bytes ? temp_bytes : 16));

@@ -50,7 +50,7 @@ __global__ void k_tlas_box_tris(const float* __restrict__ boxes, uint32_t n, flo
             o[1] = c[1];
             o[2] = c[2];
             for (int k = 3; k < 8; k++) o[k] = 0.0f;
-            o[3 + 2] = 1.0f;  // a unit normal: the shading record lbvh_build makes of it is discarded, but stays finite
+            o[3 + 2] = 1.0f;  // a unit normal: nothing reads it, but the vertex stays well formed
             indices[3 * (size_t)i + v] = 3u * i + (uint32_t)v;
         }
     }
