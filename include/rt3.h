@@ -57,6 +57,13 @@ extern "C" {
 #define RT3_F_SPECULAR 4u    /* layered BSDF: DiffuseBrdf under the GGX SpecularBrdf of brdf.slang:141-311 */
 #define RT3_F_FACEFORWARD 8u /* flip the shading normal towards the incoming ray */
 #define RT3_F_PROBE_RADIANCE 16u /* trace_probes: store lerp(prev, radiance, blendfactor) per ray, the store its line 74 keeps in a comment */
+/* next-event estimation + MIS to emissive triangles.  The same integral as the frame without the flag: at every vertex
+ * b <= B-2 one emitter is picked with probability p_sel ~ area x luminance(12 emission) (an integer CDF on the 2^-23 grid of the RNG: RNG dims
+ * 5, 6, 7, no blue-noise shift), a point on it uniformly; its emission (two-sided) is added with the balance weight p_solid / (p_solid + p_bsdf)
+ * behind a shadow ray that ends just short of the point.  A BSDF-sampled ray that hits an emitter at a vertex >= 1 adds its emission with
+ * weight p_bsdf / (p_bsdf + p_solid).  No emitter NEE at the last vertex, so with B = 1 (or a scene without emission) nothing changes.  Only
+ * refrence_mode reads the bit; the emitter table follows every rt3_accel_build / refit / import (rt3_light_info). */
+#define RT3_F_NEE_EMISSIVE 32u
 
 /* src/renderer/mod.rs:47-63 == shaders/include/datatypes.slang:28-43.  304 bytes, 16-byte aligned, column-major
  * matrices.  Offsets 0,64,128,192,256,264,268,272,276,280,284,288,296. */
@@ -218,6 +225,13 @@ int rt3_scene_update_vertices(rt3_ctx *ctx, const float *interleaved_p_n_t, uint
  * modes (mode 1: every bottom tree, then the instance records and the top tree; rt3_accel_levels then reports 0 meshes built).  Does not
  * change rt3_stats.accel_build_ms. */
 int rt3_accel_refit(rt3_ctx *ctx, uint32_t *out_handle);
+/* the emitter table of RT3_F_NEE_EMISSIVE for the current structure, built on the GPU on first use after rt3_accel_build / refit / import:
+ * every flattened primitive of a geometry with non-zero emission, in primitive order.  *cdf_total = 2^23 (the selection grid), or 0 when no
+ * emitter has power (the flag then changes nothing).  rt3_light_download (any pointer may be NULL; n_emitters entries each): primitive ids,
+ * world-space areas, selection masses in CDF units (p_sel = mass / cdf_total; mass 0 = never sampled).  Both RT3_E_STATE before a build and
+ * while vertices are stale. */
+int rt3_light_info(rt3_ctx *ctx, uint32_t *n_emitters, uint64_t *cdf_total);
+int rt3_light_download(rt3_ctx *ctx, uint32_t *prim, float *area, uint32_t *mass /* CDF units */);
 /* sky tables for parity tests (any pointer may be NULL): per-row alias words q16 | alias << 16 (w*h), RGB9E5 texels (w*h),
  * marginal CDF (h), realised (u,v) density (w*h) */
 int rt3_sky_download(rt3_ctx *ctx, uint32_t *alias, uint32_t *texels_rgb9e5, float *cdf_marg, float *pdf_uv);

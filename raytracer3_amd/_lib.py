@@ -17,6 +17,7 @@ MISS = 0xFFFFFFFF
 BACKGROUND_DEPTH = 100000.0
 FORMAT_R32_SFLOAT, FORMAT_R32G32B32A32_SFLOAT, FORMAT_R32G32B32A32_UINT, FORMAT_R8G8B8A8_UNORM, FORMAT_R16_UINT = 100, 109, 107, 37, 74
 F_NEE_SKY, F_BLUENOISE, F_SPECULAR, F_FACEFORWARD, F_PROBE_RADIANCE = 1, 2, 4, 8, 16
+F_NEE_EMISSIVE = 32  # next-event estimation + MIS to emissive triangles; off by default
 OPT_BATCH_SPP, OPT_PROFILE, OPT_COUNT_TRAVERSAL, OPT_EXTEND_VARIANT, OPT_LEAF_SIZE, OPT_NODE_WIDTH, OPT_NODE_QUANT = 1, 2, 3, 4, 5, 6, 7
 OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
@@ -27,7 +28,7 @@ EXPORTS = [
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
-    "rt3_scene_update_vertices", "rt3_accel_refit",
+    "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
@@ -121,6 +122,8 @@ def load():
         "rt3_sky_download": (i32, [vp, vp, vp, vp, vp]),
         "rt3_scene_update_vertices": (i32, [vp, vp, u32, u32]),
         "rt3_accel_refit": (i32, [vp, pu32]),
+        "rt3_light_info": (i32, [vp, pu32, C.POINTER(C.c_uint64)]),
+        "rt3_light_download": (i32, [vp, vp, vp, vp]),
         "rt3_buffer_create": (i32, [vp, sz, pu32]),
         "rt3_image_create": (i32, [vp, u32, u32, u32, pu32]),
         "rt3_image_import": (i32, [vp, vp, u32, u32, u32, pu32]),

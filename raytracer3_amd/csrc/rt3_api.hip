@@ -21,7 +21,7 @@ using namespace rt3;
 
 static_assert(sizeof(rt3_gconst) == 304 && sizeof(GConstDev) == 304, "GConst is 304 bytes (renderer/mod.rs:47-63)");
 static_assert(sizeof(rt3_geometry_info) == 64, "geometry info is 64 bytes");
-static_assert(RT3_F_NEE_SKY == RT3_FLAG_NEE_SKY && RT3_F_BLUENOISE == RT3_FLAG_BLUENOISE && RT3_F_FACEFORWARD == RT3_FLAG_FACEFORWARD && RT3_F_SPECULAR == RT3_FLAG_SPECULAR && RT3_F_PROBE_RADIANCE == RT3_FLAG_PROBE_RADIANCE, "flags");
+static_assert(RT3_F_NEE_SKY == RT3_FLAG_NEE_SKY && RT3_F_BLUENOISE == RT3_FLAG_BLUENOISE && RT3_F_FACEFORWARD == RT3_FLAG_FACEFORWARD && RT3_F_SPECULAR == RT3_FLAG_SPECULAR && RT3_F_PROBE_RADIANCE == RT3_FLAG_PROBE_RADIANCE && RT3_F_NEE_EMISSIVE == RT3_FLAG_NEE_EMISSIVE, "flags");
 
 namespace {
 
@@ -56,6 +56,7 @@ struct Timed {
 };
 struct CounterBlock {  // device counters of one refrence_mode launch, harvested lazily
     uint32_t first, n_pairs;  // n_pairs x {extension-queue size, shadow-queue size}: one 8-byte pair per bounce (k_shade bumps both with ONE 64-bit atomic)
+    uint32_t emit_first = 0, n_emit = 0;  // RT3_F_NEE_EMISSIVE: n_emit emitter-shadow-queue sizes from emit_first (one per bounce)
 };
 
 // RT3_OPT_INSTANCE_MODE 1: what a build keeps for the next one.  The bottom trees live in the combined arrays
@@ -157,6 +158,8 @@ struct rt3_ctx {
     size_t cap = 0, cap_pix = 0;
     DevBuf<float> rays[2], hits, T[2];
     DevBuf<float> sh_rays, sh_contrib, lacc, radsum;
+    DevBuf<float> sh2_rays, sh2_contrib, sh2_tmax;  // RT3_F_NEE_EMISSIVE: the emitter shadow queue, allocated when the flag is first used
+    size_t cap_emit = 0;
     DevBuf<uint32_t> d_counters;
     uint32_t counters_cap = 1 << 16, counters_next = 0;
     DevBuf<unsigned long long> d_totals;  // counting mode: kTotWords words (TotalsWord)
@@ -173,6 +176,8 @@ struct rt3_ctx {
     uint64_t topo_gen = 1, content_gen = 1;
     uint64_t accel_topo_gen = 0;  // topo_gen of the last successful rt3_accel_build
     bool accel_stale = false;     // vertices updated since the structure was built or refitted: nothing traces it until a refit or build
+    uint64_t accel_stamp = 0;     // bumped by every successful rt3_accel_build / rt3_accel_refit / rt3_accel_import
+    LightTable lights;            // RT3_F_NEE_EMISSIVE: built lazily for accel_stamp (ensure_lights)
     // refit plans (rt3_refit.hip), made on the first refit after a build or import: one per tree (instance mode 1: one per bottom tree)
     bool refit_planned = false;
     std::vector<RefitTree> refit_trees;
@@ -186,6 +191,8 @@ struct rt3_ctx {
     std::vector<Timed> pending_events;
     std::vector<Timed> free_events;
 };
+
+static int ensure_lights(rt3_ctx* c);
 
 namespace {
 
@@ -349,6 +356,8 @@ int sync_textures(rt3_ctx* c) {
 void free_work(rt3_ctx* c) {
     for (int k = 0; k < 2; k++) { c->rays[k].reset(); c->T[k].reset(); }
     c->hits.reset(); c->sh_rays.reset(); c->sh_contrib.reset(); c->lacc.reset(); c->radsum.reset();
+    c->sh2_rays.reset(); c->sh2_contrib.reset(); c->sh2_tmax.reset();
+    c->cap_emit = 0;
     c->cap = 0;
     c->cap_pix = 0;
 }
@@ -375,6 +384,17 @@ int ensure_work(rt3_ctx* c, size_t paths, size_t npix) {
     if (r) free_work(c);
     return r;
 }
+// the emitter shadow queue, as large as the other queues (after ensure_work)
+int ensure_emit_queue(rt3_ctx* c) {
+    if (c->cap_emit >= c->cap) return RT3_OK;
+    c->cap_emit = 0;
+    int r = dev_alloc(c, c->sh2_rays, 8 * c->cap);
+    if (!r) r = dev_alloc(c, c->sh2_contrib, 2 * c->cap);
+    if (!r) r = dev_alloc(c, c->sh2_tmax, c->cap);
+    if (!r) c->cap_emit = c->cap;
+    else free_work(c);
+    return r;
+}
 
 int harvest(rt3_ctx* c) {  // stream must be idle
     if (!c->pending_counters.empty()) {
@@ -385,6 +405,7 @@ int harvest(rt3_ctx* c) {  // stream must be idle
                 c->stats.extension_rays += h[b.first + 2 * k];
                 c->stats.shadow_rays += h[b.first + 2 * k + 1];
             }
+            for (uint32_t k = 0; k < b.n_emit; k++) c->stats.shadow_rays += h[b.emit_first + k];
         }
         c->pending_counters.clear();
     }
@@ -541,17 +562,29 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
     GConstDev gd;
     memcpy(&gd, g, sizeof(gd));
     const bool nee = (g->pad[0] & RT3_F_NEE_SKY) && c->d_sky;
+    // RT3_F_NEE_EMISSIVE: only with something to sample; otherwise the frame is the flag-less one, same kernels
+    // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
+    LightsDev lights{};
+    if ((g->pad[0] & RT3_F_NEE_EMISSIVE) && B > 1) {
+        if (int r = ensure_lights(c)) return r;
+        lights = c->lights.dev();
+        if (lights.n)
+            if (int r = ensure_emit_queue(c)) return r;
+    }
+    const bool nee_e = lights.n != 0u;
     SceneDev sc = scene_dev(c);
     for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
         const uint32_t nsb = std::min(sb, Sspp - s0);
         const uint32_t n_first = nsb * npix;
         uint32_t first;
-        if (int r = reserve_counters(c, 4 * B + 1, &first)) return r;
+        if (int r = reserve_counters(c, (nee_e ? 6 : 4) * B + 1, &first)) return r;
         first += first & 1u;  // 8-byte aligned pairs
         // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
         uint32_t* pairs = c->d_counters.get() + first;
         uint32_t* pool_cur = c->d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
-        c->pending_counters.push_back(CounterBlock{first, B});
+        // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
+        uint32_t* emit_cnt = c->d_counters.get() + first + 4 * B;
+        c->pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
         auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
         auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
         int cur = 0;
@@ -564,6 +597,8 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
             L.out_rays = c->rays[cur ^ 1].get(); L.out_T = c->T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
             L.sh_rays = c->sh_rays.get(); L.sh_contrib = c->sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
             L.lacc = c->lacc.get(); L.stride = S; L.max_n = n_first;
+            L.lights = lights;
+            L.sh2_rays = c->sh2_rays.get(); L.sh2_contrib = c->sh2_contrib.get(); L.sh2_tmax = c->sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
             {
                 ScopedTimer t(c, CAT_SHADE);
                 launch_shade(c->stream, bn == 0, L);
@@ -573,6 +608,11 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
                 ScopedTimer t(c, CAT_SHADOW);
                 launch_shadow(c->stream, c->opt_count, c->bvh, c->sh_rays.get(), S, sh_cnt_at(bn), 0, n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S,
                               nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + B + bn);
+            }
+            if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
+                ScopedTimer t(c, CAT_SHADOW);
+                launch_shadow(c->stream, c->opt_count, c->bvh, c->sh2_rays.get(), S, emit_cnt + bn, 0, n_first, c->sh2_contrib.get(), nullptr, c->lacc.get(), S,
+                              nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, emit_cnt + B + bn, c->sh2_tmax.get());
             }
             if (bn != B - 1) {
                 ScopedTimer t(c, CAT_EXTEND);
@@ -1170,6 +1210,36 @@ static int make_shade_records(rt3_ctx* c) {
     s.key = std::move(key);
     return RT3_OK;
 }
+// The emitter table (RT3_F_NEE_EMISSIVE, rt3_lights.hip) of the current structure, remade when a build, refit or import has happened since.  The
+// host walks only the flattened geometries (as flatten_world does) to find the emissive ones; the table itself is made on the GPU.
+static int ensure_lights(rt3_ctx* c) {
+    if (int r = check_accel_current(c)) return r;
+    if (c->lights.stamp == c->accel_stamp) return RT3_OK;
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
+    std::vector<uint32_t> geom_base, eg_geom, eg_first;
+    uint64_t n = 0;
+    for (size_t i = 0; i < n_inst; i++)
+        for (uint32_t k = 0; k < inst[i].geometry_count; k++) {
+            const uint32_t g = inst[i].geometry_first + k;
+            const float* em = c->h_geoms[g].emission;
+            const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && c->h_prim_counts[g] > 0;
+            geom_base.push_back(emissive ? (uint32_t)n : kMiss);
+            if (emissive) {
+                eg_geom.push_back((uint32_t)(geom_base.size() - 1));
+                eg_first.push_back((uint32_t)n);
+                n += c->h_prim_counts[g];
+            }
+        }
+    if (geom_base.size() != c->n_flat_geoms) return fail(c, RT3_E_STATE, "emitter table: the placements changed since rt3_accel_build");
+    HIPC(c, hipSetDevice(c->device));
+    const hipError_t e = lights_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
+                                      geom_base, eg_geom, eg_first, (uint32_t)n, &c->lights);
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("emitter table: ") + hipGetErrorString(e));
+    c->lights.stamp = c->accel_stamp;
+    return RT3_OK;
+}
+
 // worst-case stack use of the near-first walk over a tree of `depth` levels: (children per node - 1) entries per level above the leaves
 static uint32_t stack_entries(uint32_t width, uint32_t depth) { return depth > 1 ? (width - 1) * (depth - 1) : 0; }
 
@@ -1537,6 +1607,7 @@ static int accel_finish(rt3_ctx* c, uint32_t* out_handle) {
     c->bulk_copies = 0;
     c->accel_built = true;
     c->accel_stale = false;
+    c->accel_stamp++;                 // the emitter table follows (ensure_lights)
     c->accel_topo_gen = c->topo_gen;  // (unchanged by a refit, which needs the build's)
     if (out_handle) *out_handle = (RT3_TAG_ACCEL << 30) | 0u;
     return RT3_OK;
@@ -1666,6 +1737,7 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     c->bvh.n_tris = nt;
     c->bvh.max_depth = depth;
     c->refit_planned = false;
+    c->accel_stamp++;
     e = lbvh_make_top(c->stream, c->bvh.nodes.get(), nn, c->bvh.top, &c->bvh.n_top);
     if (e != hipSuccess) {
         c->accel_built = false;
@@ -2157,6 +2229,28 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), (size_t)n * ow * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("selftest: ") + hipGetErrorString(e));
+    return RT3_OK;
+}
+
+// ---- emitter table of RT3_F_NEE_EMISSIVE
+int rt3_light_info(rt3_ctx* c, uint32_t* n_emitters, uint64_t* cdf_total) {
+    if (!c) return RT3_E_INVALID;
+    if (int r = ensure_lights(c)) return r;
+    if (n_emitters) *n_emitters = c->lights.n;
+    if (cdf_total) *cdf_total = c->lights.total;
+    return RT3_OK;
+}
+int rt3_light_download(rt3_ctx* c, uint32_t* prim, float* area, uint32_t* mass) {
+    if (!c) return RT3_E_INVALID;
+    if (int r = ensure_lights(c)) return r;
+    const LightTable& t = c->lights;
+    if (!t.n) return RT3_OK;
+    if (prim) HIPC(c, hipMemcpy(prim, t.prim.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    if (area) HIPC(c, hipMemcpy(area, t.area.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    if (mass) {
+        HIPC(c, hipMemcpy(mass, t.cdf.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+        for (uint32_t k = t.n - 1; k > 0; k--) mass[k] -= mass[k - 1];  // inclusive CDF -> masses
+    }
     return RT3_OK;
 }
 

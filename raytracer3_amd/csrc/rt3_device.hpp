@@ -644,6 +644,30 @@ RT3_DEV void sky_sample(const SceneDev& sc, float u0, float u1, V3& dir, V3& rad
     sky_sample_radiance(sc, p, rad, pdf);
 }
 
+// ------------------------------------------------------------------------------------------------ emitters (RT3_F_NEE_EMISSIVE)
+// The emitter table (rt3_lights.hip).  Record e, 64 bytes = 4 float4:
+//   {A.xyz, p_sel / area}  {E1.xyz, Le.r}  {E2.xyz, Le.g}  {unit geometric normal, Le.b}
+// A, A + E1, A + E2: the world-space triangle as flattening makes it; Le = 12 emission (hit_finish's value); p_sel = mass / 2^23, exact.
+// cdf: inclusive integer CDF (cdf[n - 1] = 2^23); guide: 2^23 >> guide_shift cells + 1, cell c holds the first e with cdf[e] > c << shift.
+struct LightsDev {
+    const float4* rec;
+    const uint32_t* cdf;
+    const uint32_t* guide;
+    const uint32_t* geom_base;  // per flattened geometry: its first emitter, or kMiss for a geometry without emission
+    uint32_t n, guide_shift;    // n = 0: nothing to sample
+};
+// the emitter that owns k in [0, 2^23): the first e with cdf[e] > k (emitters of zero mass are never returned)
+RT3_DEV uint32_t light_find(const LightsDev& lt, uint32_t k) {
+    const uint32_t c = k >> lt.guide_shift;
+    uint32_t lo = lt.guide[c], hi = lt.guide[c + 1];
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (lt.cdf[mid] > k) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 // ------------------------------------------------------------------------------------------------ intersection (north_star)
 struct Hit {
     float t, u, v;

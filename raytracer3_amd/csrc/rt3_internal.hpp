@@ -13,6 +13,7 @@
 #define RT3_FLAG_SPECULAR 4u
 #define RT3_FLAG_FACEFORWARD 8u
 #define RT3_FLAG_PROBE_RADIANCE 16u
+#define RT3_FLAG_NEE_EMISSIVE 32u
 
 namespace rt3 {
 
@@ -62,6 +63,12 @@ struct ShadeLaunch {
     float* lacc;
     size_t stride;
     uint32_t max_n;  // upper bound of live paths (grid sizing)
+    // RT3_F_NEE_EMISSIVE: the emitter table and the second shadow queue; lights.n == 0 = the flag is off
+    LightsDev lights;
+    float* sh2_rays;
+    float* sh2_contrib;
+    float* sh2_tmax;
+    uint32_t* sh2_count;
 };
 
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
@@ -170,9 +177,10 @@ struct LbvhResult {
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
 void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
                    uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, bool payload = false);
+// tmax != nullptr: every ray has its own range (kRayTMin, tmax[i]) -- the emitter shadow queue of RT3_F_NEE_EMISSIVE
 void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
                    uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
-                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter);
+                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, const float* tmax = nullptr);
 // On failure *out may hold some of its arrays: they go with it.
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
@@ -212,6 +220,29 @@ hipError_t refit_plan(hipStream_t st, const float4* nodes, uint32_t root, uint32
 hipError_t refit_tree(hipStream_t st, const RefitTree& plan, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes, float4* tris, uint32_t* bounds,
                       float* nbox, float* tbox);
+
+// Emitter table of RT3_F_NEE_EMISSIVE (rt3_lights.hip): every flattened primitive of a geometry with non-zero emission,
+// in flattened order.  Selection by an integer CDF on the 2^-23 grid of uniform_float; records as LightsDev describes.
+struct LightTable {
+    DevBuf<float4> rec;                       // 4 per emitter
+    DevBuf<uint32_t> cdf, guide, prim, geom_base;
+    DevBuf<float> area;
+    DevBuf<char> scratch;                     // power, quantised power and its scan, the scan's temporary storage
+    size_t scratch_cap = 0;
+    uint32_t n = 0, n_guide = 0, guide_shift = 0, total = 0;  // total: cdf[n - 1] (2^23, or 0 when no emitter has power)
+    uint64_t stamp = 0;                       // the acceleration-structure stamp the table was built for (0 = none)
+    LightsDev dev() const {
+        LightsDev d;
+        d.rec = rec.get(); d.cdf = cdf.get(); d.guide = guide.get(); d.geom_base = geom_base.get();
+        d.n = total ? n : 0u; d.guide_shift = guide_shift;
+        return d;
+    }
+};
+// geom_base: per flattened geometry its first emitter or kMiss (host table, n_flat_geoms entries); eg_geom / eg_first: the emissive flattened
+// geometries and their first emitter (n_eg entries); n: emitters.  Reads back nothing but the CDF's last word (into *total).
+hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                        const uint32_t* first_prim, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
+                        const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

@@ -148,11 +148,12 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // lane that reaches one fetches the record, moves its ray into object space for the box tests of the bottom tree, marks its stack and walks
 // that tree; its triangles are transformed to world space with flattening's own expression and tested against the world ray.  Once the
 // bottom walk has popped down to the mark the lane goes back to the world ray and the top tree's entries.
-template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, typename Finish>
+// RANGE (any hit only): ray i ends at any_tmax[i] instead of kBackgroundDepth -- the emitter shadow queue of RT3_F_NEE_EMISSIVE.
+template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
-                                             const float2* __restrict__ any_contrib = nullptr) {
+                                             const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr) {
     // any_payload: the any-hit rays come from k_shade's shadow queue, where every ray has the range (kRayTMin, kBackgroundDepth):
     // the two .w slots of its record carry payload (two contribution channels) instead of tmin / tmax -- 16 bytes less per ray.
     // ext_payload: likewise for the extension rays of the path tracer's own queue (.w = the path's pdf and id, read by k_shade)
@@ -238,6 +239,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 const bool payload = ANY ? any_payload : ext_payload;
                 r.tmin = payload ? kRayTMin : ro.w;
                 r.best = Hit{payload ? kBackgroundDepth : rd.w, 0.0f, 0.0f, kMiss};
+                if (RANGE) r.best.t = any_tmax[idx];
                 r.pay0 = ro.w;
                 r.pay1 = rd.w;
                 if (ANY && any_contrib != nullptr) {
@@ -563,7 +565,8 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
 
 // any-hit over the shadow queue; unoccluded rays add their contribution to the path's radiance slot.
 // If `occluded_out` != nullptr the kernel only reports occlusion (rt3_trace_rays).
-template <bool COUNT, int LAYOUT>
+// RANGE: the emitter shadow queue, whose rays end short of their sampled emitter point (range (kRayTMin, tmax[i]))
+template <bool COUNT, int LAYOUT, bool RANGE = false>
 __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
                                                          const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
@@ -571,13 +574,14 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
                                                          float* __restrict__ lacc, size_t lstride,
                                                          uint32_t* __restrict__ occluded_out, uint32_t* __restrict__ cnt_nodes,
                                                          uint32_t* __restrict__ cnt_tris, unsigned long long* __restrict__ totals,
-                                                         uint32_t* __restrict__ work_counter, unsigned long long* __restrict__ lds_total) {
+                                                         uint32_t* __restrict__ work_counter, unsigned long long* __restrict__ lds_total,
+                                                         const float* __restrict__ tmax) {
     __shared__ uint32_t stack[kLdsStack * kExtendBlock];
     __shared__ float4 s_top[4 * kTopNodes];
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
-    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(
+    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE>(
         nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
             if (occluded_out) {
@@ -597,7 +601,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
                 tot_l += cl;
             }
         },
-        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr);
+        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr, tmax);
     if (COUNT && totals) {
         atomicAdd(&totals[0], tot_n);
         atomicAdd(&totals[1], tot_t);
@@ -677,6 +681,50 @@ __device__ __forceinline__ BlockAppend block_append2(bool want_ext, bool want_sh
     r.sh = lds[2 * kWaves + 1] + lds[kWaves + 1 + wave] + (uint32_t)__popcll(m_sh & below);
     return r;  // no third barrier: the caller alternates between two lds buffers from one loop iteration to the next
 }
+// block_append2 plus the emitter shadow queue of RT3_F_NEE_EMISSIVE (k_shade<.., .., true> only): the pair moves with its one 64-bit atomic
+// as before, the third count with one 32-bit atomic of its own
+struct BlockAppend3 {
+    uint32_t ext, sh, sh2;
+};
+__device__ __forceinline__ BlockAppend3 block_append3(bool want_ext, bool want_sh, bool want_sh2, unsigned long long* pair, uint32_t* count2,
+                                                      uint32_t* lds /* 3 * (waves + 1) words */) {
+    constexpr int kWaves = kShadeBlock / 64, kW1 = kWaves + 1;
+    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+    const unsigned long long m_ext = __ballot(want_ext), m_sh = __ballot(want_sh), m_sh2 = __ballot(want_sh2);
+    if (lane == 0) {
+        lds[wave] = (uint32_t)__popcll(m_ext);
+        lds[kW1 + wave] = (uint32_t)__popcll(m_sh);
+        lds[2 * kW1 + wave] = (uint32_t)__popcll(m_sh2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t te = 0, ts = 0, t2 = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) {
+            const uint32_t ce = lds[w], cs = lds[kW1 + w], c2 = lds[2 * kW1 + w];
+            lds[w] = te;
+            lds[kW1 + w] = ts;
+            lds[2 * kW1 + w] = t2;
+            te += ce;
+            ts += cs;
+            t2 += c2;
+        }
+        unsigned long long old = 0ull;
+        if (te | ts) old = atomicAdd(pair, (unsigned long long)te | ((unsigned long long)ts << 32));
+        lds[kWaves] = (uint32_t)old;
+        lds[kW1 + kWaves] = (uint32_t)(old >> 32);
+        lds[2 * kW1 + kWaves] = t2 ? atomicAdd(count2, t2) : 0u;
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    BlockAppend3 r;
+    r.ext = lds[kWaves] + lds[wave] + (uint32_t)__popcll(m_ext & below);
+    r.sh = lds[kW1 + kWaves] + lds[kW1 + wave] + (uint32_t)__popcll(m_sh & below);
+    r.sh2 = lds[2 * kW1 + kWaves] + lds[2 * kW1 + wave] + (uint32_t)__popcll(m_sh2 & below);
+    return r;
+}
+// the emitter shadow ray ends this far along its way to the sampled point: the emitter never occludes itself, another one in front does
+constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
 
 struct ShadeArgs {
     GConstDev g;
@@ -705,16 +753,23 @@ struct ShadeArgs {
     uint32_t* sh_count;
     float* lacc;             // float4 {r, g, b, -} per path id
     size_t stride;
+    // EMIT (RT3_F_NEE_EMISSIVE): the emitter table and the emitter shadow queue {o, c.r} {d, c.g} {c.b, path id} + range end, and its count
+    LightsDev lights;
+    float* sh2_rays;
+    float* sh2_contrib;
+    float* sh2_tmax;
+    uint32_t* sh2_count;
 };
 
 // refrence_mode.slang:28-57 for one bounce of every live path
 // GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
 // normal matrix cost an LDS read behind the shading record instead of a second dependent global gather
-template <bool FIRST, bool GLDS>
+// EMIT: next-event estimation to emissive triangles with MIS; launched only with RT3_F_NEE_EMISSIVE and a non-empty table
+template <bool FIRST, bool GLDS, bool EMIT = false>
 // 6 waves per SIMD (80 VGPRs, 32 bytes of scratch): the kernel lives off memory-level parallelism -- 28.8 -> 27.7 ms against the
 // compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks)
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_shade(ShadeArgs a) {
-    __shared__ uint32_t append_lds[2][2 * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
+    __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
     __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
     if (GLDS) {
         const uint32_t words = (a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds) * (uint32_t)(sizeof(ShadeGeomDev) / 4);
@@ -814,6 +869,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
         bool emit_shadow = false, emit_ext = false;
         V3 wl = v3(0, 1, 0), contrib = v3(0, 0, 0), nd = v3(0, 0, 1), Tn = T;
         float pdf_n = 0.0f;
+        bool emit_shadow_e = false;  // EMIT: the emitter shadow ray
+        V3 wle = v3(0, 1, 0), contrib_e = v3(0, 0, 0);
+        float tmax_e = 0.0f;
         if (active) {
             uint32_t seed = rng_seed(px, py, g.frame);  // :25
             uint32_t sm = a.s0 + sample_in_batch;
@@ -839,6 +897,21 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
                     ul1 = bluenoise_shift(ul1, (bn >> 24) & 0xFFu);
                 }
                 pick = sky_sample_direction(a.sc, cdf_marg, guide_marg, ul0, ul1, wl);
+            }
+            // EMIT: an emitter and a point on it for vertices 0 .. B-2 (the emission vertex b + 1 would collect); dims 5, 6, 7, no blue-noise
+            // shift.  The chain guide -> CDF -> record is issued here, beside the sky's, and used once the surface is known.
+            const bool nee_e = EMIT && b + 1u < B;
+            float4 er0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), er1 = er0, er2 = er0, er3 = er0;
+            float eu6 = 0.0f, eu7 = 0.0f;
+            if (nee_e) {
+                const uint32_t ke = (uint32_t)(uniform_float(seed, base + 5) * 8388608.0f);  // exact: the 23-bit integer uniform_float was made of
+                eu6 = uniform_float(seed, base + 6);
+                eu7 = uniform_float(seed, base + 7);
+                const float4* R = a.lights.rec + 4 * (size_t)light_find(a.lights, ke);
+                er0 = R[0];
+                er1 = R[1];
+                er2 = R[2];
+                er3 = R[3];
             }
             if (!FIRST) {  // :55, second half (two calls, not a selected pointer: a select would turn the LDS reads into flat loads)
                 if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
@@ -873,9 +946,49 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
             if (FIRST) {  // L starts at 0 and T = 1: 0 + 1 * e == e
                 reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(T.x * surf.emissive.x, T.y * surf.emissive.y, T.z * surf.emissive.z, 0.0f);
             } else if (surf.emissive.x != 0.0f || surf.emissive.y != 0.0f || surf.emissive.z != 0.0f) {
+                V3 le = surf.emissive;
+                if (EMIT) {  // a BSDF-sampled ray found an emitter the previous vertex also sampled directly: balance weight pdf_b / (pdf_b + p_solid)
+                    const uint32_t eb = a.lights.geom_base[hrecord.rec.w];
+                    if (eb != kMiss) {
+                        const float4* R = a.lights.rec + 4 * (size_t)(eb + (hrecord.prim - a.sc.first_prim[hrecord.rec.w]));
+                        const float pa = R[0].w;  // p_sel / area, the value the sampler divides by
+                        const float4 rn = R[3];
+                        const float dl = sqrtf(dot(d, d)), cle = fabsf(rn.x * d.x + rn.y * d.y + rn.z * d.z) / dl, dist = t * dl;
+                        if (pa > 0.0f && cle > 0.0f) {
+                            const float ps = pa * (dist * dist) / cle;
+                            le = le * (pdf_b / (pdf_b + ps));
+                        }
+                    }
+                }
                 float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
                 float4 lv = *Lp;
-                *Lp = make_float4(lv.x + T.x * surf.emissive.x, lv.y + T.y * surf.emissive.y, lv.z + T.z * surf.emissive.z, 0.0f);
+                *Lp = make_float4(lv.x + T.x * le.x, lv.y + T.y * le.y, lv.z + T.z * le.z, 0.0f);
+            }
+            if (nee_e && er0.w > 0.0f) {  // the emitter sample: p = A + b1 E1 + b2 E2 with b0 = 1 - sqrt(u6), b1 = u7 sqrt(u6)
+                const float su = sqrtf(eu6), lb1 = eu7 * su, lb2 = su - lb1;
+                const V3 pe = v3(er0.x + er1.x * lb1 + er2.x * lb2, er0.y + er1.y * lb1 + er2.y * lb2, er0.z + er1.z * lb1 + er2.z * lb2);
+                const V3 wv = pe - o;
+                const float dist2 = dot(wv, wv), dist = sqrtf(dist2);
+                if (dist2 > 0.0f) {
+                    wle = wv * (1.0f / dist);
+                    const float cs = dot(N, wle), cle = fabsf(er3.x * wle.x + er3.y * wle.y + er3.z * wle.z);  // emission is two-sided
+                    if (cs > 0.0f && cle > 0.0f) {
+                        const float ps = er0.w * dist2 / cle;  // p_sel / area * dist^2 / |cos_l|: solid-angle density of the sample
+                        V3 fv;
+                        float scale;
+                        if (spec) {  // f cos Le / (p_solid + p_bsdf) == f cos Le w / p_solid, balance heuristic
+                            float pproj;
+                            bsdf_eval(bs, wo, v3(dot(wle, b1), dot(wle, b2), cs), fv, pproj);
+                            scale = cs / (ps + pproj * cs);
+                        } else {
+                            fv = surf.albedo;
+                            scale = (cs * kInvPi) / (ps + cs * kInvPi);
+                        }
+                        contrib_e = v3((T.x * fv.x) * (er1.w * scale), (T.y * fv.y) * (er2.w * scale), (T.z * fv.z) * (er3.w * scale));
+                        tmax_e = dist * kEmitShadowEnd;
+                        emit_shadow_e = contrib_e.x > 0.0f || contrib_e.y > 0.0f || contrib_e.z > 0.0f;
+                    }
+                }
             }
             if (nee) {
                 if (cosl > 0.0f && pl > 0.0f) {
@@ -902,8 +1015,23 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
                 emit_ext = true;                  // :53
             }
         }
-        const BlockAppend slot = block_append2(emit_ext, emit_shadow, reinterpret_cast<unsigned long long*>(a.out_count), append_lds[parity]);  // out_count, sh_count: one pair
+        BlockAppend slot;
+        uint32_t slot_e = 0;
+        if (EMIT) {
+            const BlockAppend3 s3 = block_append3(emit_ext, emit_shadow, emit_shadow_e, reinterpret_cast<unsigned long long*>(a.out_count), a.sh2_count, append_lds[parity]);
+            slot.ext = s3.ext;
+            slot.sh = s3.sh;
+            slot_e = s3.sh2;
+        } else {
+            slot = block_append2(emit_ext, emit_shadow, reinterpret_cast<unsigned long long*>(a.out_count), append_lds[parity]);  // out_count, sh_count: one pair
+        }
         parity ^= 1u;
+        if (EMIT && emit_shadow_e) {  // 44 bytes: the 40-byte shadow record plus the ray's own range end
+            reinterpret_cast<float4*>(a.sh2_rays)[slot_e] = make_float4(o.x, o.y, o.z, contrib_e.x);
+            reinterpret_cast<float4*>(a.sh2_rays)[S + slot_e] = make_float4(wle.x, wle.y, wle.z, contrib_e.y);
+            reinterpret_cast<float2*>(a.sh2_contrib)[slot_e] = make_float2(contrib_e.z, __uint_as_float(pid));
+            a.sh2_tmax[slot_e] = tmax_e;
+        }
         if (emit_shadow) {
             const uint32_t j = slot.sh;
             // 40 bytes per shadow ray: its range is always (kRayTMin, kBackgroundDepth), so the .w of the two ray records carry the
@@ -1157,13 +1285,17 @@ void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const floa
 }
 void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
                    uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
-                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter) {
+                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, const float* tmax) {
     const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
     unsigned long long* const tot = totals ? totals + kTotShadowNodes : nullptr;
     unsigned long long* const lds_tot = totals ? totals + kTotShadowLds : nullptr;
     dispatch_traversal(count, bvh.layout, [&](auto c, auto l) {
-        hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
-                           bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot);
+        if (tmax)
+            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, true>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(),
+                               bvh.top.get(), bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot, tmax);
+        else
+            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
+                               bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot, nullptr);
     });
 }
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
@@ -1192,9 +1324,15 @@ void launch_shade(hipStream_t st, bool first, const ShadeLaunch& L) {
     a.out_rays = L.out_rays; a.out_T = L.out_T; a.out_count = L.out_count;
     a.sh_rays = L.sh_rays; a.sh_contrib = L.sh_contrib; a.sh_count = L.sh_count;
     a.lacc = L.lacc; a.stride = L.stride;
+    a.lights = L.lights; a.sh2_rays = L.sh2_rays; a.sh2_contrib = L.sh2_contrib; a.sh2_tmax = L.sh2_tmax; a.sh2_count = L.sh2_count;
     unsigned grid = grid_for(L.max_n, kShadeBlock, 8192);
-    if (first) hipLaunchKernelGGL((k_shade<true, false>), dim3(grid), dim3(kShadeBlock), 0, st, a);  // the first vertex comes from the G-buffer
-    else if (a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds) hipLaunchKernelGGL((k_shade<false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+    const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
+    if (a.lights.n != 0u) {  // RT3_F_NEE_EMISSIVE with something to sample
+        if (first) hipLaunchKernelGGL((k_shade<true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else if (glds) hipLaunchKernelGGL((k_shade<false, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else hipLaunchKernelGGL((k_shade<false, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+    } else if (first) hipLaunchKernelGGL((k_shade<true, false>), dim3(grid), dim3(kShadeBlock), 0, st, a);  // the first vertex comes from the G-buffer
+    else if (glds) hipLaunchKernelGGL((k_shade<false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
     else hipLaunchKernelGGL((k_shade<false, false>), dim3(grid), dim3(kShadeBlock), 0, st, a);
 }
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,

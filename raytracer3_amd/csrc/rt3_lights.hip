@@ -1,0 +1,168 @@
+// rt3_lights.hip -- the emitter table of RT3_F_NEE_EMISSIVE, built on the GPU from the flattened geometry tables.
+//
+//   k_emit_prims : emitter e -> its primitive, world triangle (fetch_triangle: flattening's own expression), area, normal, radiance, power
+//   k_emit_max   : the largest power (ordered-uint atomicMax: the same answer whatever the order)
+//   k_emit_quant : power -> 64-bit integer weight on a 2^24 grid relative to the largest
+//   hipcub inclusive scan of the weights (integer: associative, so the same bits on every run, in both instance modes)
+//   k_emit_cdf   : cdf[e] = floor(prefix[e] / total * 2^23), exact in fp64 (prefix < 2^53); p_sel / area into the record
+//   k_emit_guide : guide cells for a constant-time start of the lookup
+// Selection then happens on the 2^-23 grid uniform_float produces: emitter e is picked for exactly (cdf[e] - cdf[e-1]) of its 2^23 values,
+// so the probability the estimator divides by is the one realised.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "rt3_bvh_device.hpp"
+#include "rt3_device.hpp"
+#include "rt3_internal.hpp"
+
+namespace rt3 {
+
+constexpr uint32_t kCdfTotal = 1u << 23;
+constexpr uint32_t kMaxGuideCells = 1u << 20;
+
+static unsigned grid_of(uint64_t n) { return (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256 ? (n + 255) / 256 : 1); }
+
+__global__ void k_emit_prims(const float* __restrict__ verts, const uint32_t* __restrict__ indices, const FlatGeomDev* __restrict__ geoms,
+                             const uint32_t* __restrict__ prim_geom, const uint32_t* __restrict__ first_prim, const uint32_t* __restrict__ eg_geom,
+                             const uint32_t* __restrict__ eg_first, uint32_t n_eg, uint32_t n, float4* __restrict__ rec, uint32_t* __restrict__ prim_out,
+                             float* __restrict__ area_out, float* __restrict__ power, uint32_t* __restrict__ max_power) {
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = n_eg - 1;  // the last emissive geometry whose first emitter is <= e
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (eg_first[mid] <= e) lo = mid;
+            else hi = mid - 1;
+        }
+        const uint32_t g = eg_geom[lo];
+        const uint32_t prim = first_prim[g] + (e - eg_first[lo]);
+        V3 a, b, c;
+        fetch_triangle(verts, indices, geoms, prim_geom, first_prim, prim, a, b, c);
+        const V3 e1 = b - a, e2 = c - a, cr = cross(e1, e2);
+        const float len = sqrtf(dot(cr, cr));
+        const float area = 0.5f * len;
+        const V3 nl = len > 0.0f ? cr * (1.0f / len) : v3(0.0f, 0.0f, 1.0f);
+        const float* em = geoms[g].g.emission;
+        const V3 le = v3(em[0] * 12.0f, em[1] * 12.0f, em[2] * 12.0f);  // hit_finish's radiance, same fp32 products
+        float p = area * luminance(le);
+        p = (p > 0.0f && p <= 3.4028234663852886e38f) ? p : 0.0f;  // no power: never sampled
+        rec[4 * (size_t)e] = make_float4(a.x, a.y, a.z, 0.0f);
+        rec[4 * (size_t)e + 1] = make_float4(e1.x, e1.y, e1.z, le.x);
+        rec[4 * (size_t)e + 2] = make_float4(e2.x, e2.y, e2.z, le.y);
+        rec[4 * (size_t)e + 3] = make_float4(nl.x, nl.y, nl.z, le.z);
+        prim_out[e] = prim;
+        area_out[e] = area;
+        power[e] = p;
+        atomicMax(max_power, __float_as_uint(p));  // non-negative floats order like their bits
+    }
+}
+
+__global__ void k_emit_quant(const float* __restrict__ power, const uint32_t* __restrict__ max_power, uint32_t n, unsigned long long* __restrict__ q) {
+    const double pm = (double)__uint_as_float(*max_power);
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x)
+        q[e] = pm > 0.0 ? (unsigned long long)floor((double)power[e] / pm * 16777216.0 + 0.5) : 0ull;  // <= 2^24 each, < 2^52 in all
+}
+
+__global__ void k_emit_cdf(const unsigned long long* __restrict__ prefix, const float* __restrict__ area, uint32_t n, uint32_t* __restrict__ cdf,
+                           float4* __restrict__ rec) {
+    const unsigned long long Q = prefix[n - 1];
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+        auto at = [&](uint32_t k) { return Q ? (uint32_t)floor((double)prefix[k] / (double)Q * (double)kCdfTotal) : 0u; };  // at(n - 1) = 2^23
+        const uint32_t hi = at(e), lo = e ? at(e - 1) : 0u, mass = hi - lo;
+        cdf[e] = hi;
+        const float p_sel = (float)mass * (1.0f / (float)kCdfTotal);  // exact
+        rec[4 * (size_t)e].w = (mass && area[e] > 0.0f) ? p_sel / area[e] : 0.0f;
+    }
+}
+
+__global__ void k_emit_guide(const uint32_t* __restrict__ cdf, uint32_t n, uint32_t cells, uint32_t shift, uint32_t* __restrict__ guide) {
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c <= cells; c += gridDim.x * blockDim.x) {
+        if (c == cells) {
+            guide[c] = n - 1;
+            continue;
+        }
+        const uint32_t k = c << shift;
+        uint32_t lo = 0, hi = n - 1;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (cdf[mid] > k) hi = mid;
+            else lo = mid + 1;
+        }
+        guide[c] = lo;
+    }
+}
+
+#define LT_CHECK(x)                            \
+    do {                                       \
+        hipError_t e_ = (x);                   \
+        if (e_ != hipSuccess) return e_;       \
+    } while (0)
+
+template <typename T>
+static hipError_t alloc_n(DevBuf<T>& b, size_t n) {
+    return b.alloc_bytes((n ? n : 1) * sizeof(T));
+}
+
+hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                        const uint32_t* first_prim, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
+                        const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out) {
+    out->stamp = 0;
+    out->n = out->total = 0;
+    const size_t ng = geom_base.size(), neg = eg_geom.size();
+    // per flattened geometry its first emitter, then the emissive geometries' {flattened index, first emitter}: a few KiB at most
+    std::vector<uint32_t> small(ng + 2 * neg);
+    std::copy(geom_base.begin(), geom_base.end(), small.begin());
+    std::copy(eg_geom.begin(), eg_geom.end(), small.begin() + ng);
+    std::copy(eg_first.begin(), eg_first.end(), small.begin() + ng + neg);
+    LT_CHECK(alloc_n(out->geom_base, small.size()));
+    if (!small.empty()) LT_CHECK(hipMemcpyAsync(out->geom_base.get(), small.data(), small.size() * 4, hipMemcpyHostToDevice, st));
+    if (n == 0 || neg == 0) {
+        LT_CHECK(hipStreamSynchronize(st));  // (the host vector goes out of scope)
+        return hipSuccess;
+    }
+    uint32_t cells = 1, shift = 23;
+    while (cells < n && cells < kMaxGuideCells) {
+        cells <<= 1;
+        shift--;
+    }
+    LT_CHECK(alloc_n(out->rec, 4 * (size_t)n));
+    LT_CHECK(alloc_n(out->cdf, n));
+    LT_CHECK(alloc_n(out->prim, n));
+    LT_CHECK(alloc_n(out->area, n));
+    LT_CHECK(alloc_n(out->guide, (size_t)cells + 1));
+    // scratch: power (4 n), max word, weights (8 n), prefix (8 n), scan storage
+    unsigned long long *q = nullptr, *prefix = nullptr;
+    size_t scan_bytes = 0;
+    LT_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, q, prefix, (int)n, st));
+    const size_t off_max = ((size_t)n * 4 + 255) & ~(size_t)255, off_q = off_max + 256, off_p = off_q + (((size_t)n * 8 + 255) & ~(size_t)255),
+                 off_s = off_p + (((size_t)n * 8 + 255) & ~(size_t)255), need = off_s + scan_bytes + 256;
+    if (need > out->scratch_cap) {
+        out->scratch_cap = 0;
+        LT_CHECK(out->scratch.alloc_bytes(need));
+        out->scratch_cap = need;
+    }
+    char* s = out->scratch.get();
+    float* power = reinterpret_cast<float*>(s);
+    uint32_t* max_power = reinterpret_cast<uint32_t*>(s + off_max);
+    q = reinterpret_cast<unsigned long long*>(s + off_q);
+    prefix = reinterpret_cast<unsigned long long*>(s + off_p);
+    const uint32_t* d_eg_geom = out->geom_base.get() + ng;
+    const uint32_t* d_eg_first = d_eg_geom + neg;
+    LT_CHECK(hipMemsetAsync(max_power, 0, 4, st));
+    hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n)), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, d_eg_geom, d_eg_first, (uint32_t)neg, n,
+                       out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
+    hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, power, max_power, n, q);
+    LT_CHECK(hipcub::DeviceScan::InclusiveSum(s + off_s, scan_bytes, q, prefix, (int)n, st));
+    hipLaunchKernelGGL(k_emit_cdf, dim3(grid_of(n)), dim3(256), 0, st, prefix, out->area.get(), n, out->cdf.get(), out->rec.get());
+    hipLaunchKernelGGL(k_emit_guide, dim3(grid_of((uint64_t)cells + 1)), dim3(256), 0, st, out->cdf.get(), n, cells, shift, out->guide.get());
+    LT_CHECK(hipGetLastError());
+    uint32_t total = 0;
+    LT_CHECK(hipMemcpyAsync(&total, out->cdf.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    LT_CHECK(hipStreamSynchronize(st));
+    out->n = n;
+    out->n_guide = cells;
+    out->guide_shift = shift;
+    out->total = total;
+    return hipSuccess;
+}
+
+}  // namespace rt3

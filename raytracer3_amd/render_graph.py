@@ -208,6 +208,19 @@ class Context:
         self.check(self.lib.rt3_accel_refit(self.h, C.byref(out)))
         return out.value
 
+    def light_info(self):
+        """(n_emitters, cdf_total) of the RT3_F_NEE_EMISSIVE emitter table (rt3_light_info)"""
+        n, t = C.c_uint32(), C.c_uint64()
+        self.check(self.lib.rt3_light_info(self.h, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def light_download(self):
+        """(primitive ids uint32, areas float32, masses uint32 in CDF units) of the emitter table (rt3_light_download)"""
+        n, _ = self.light_info()
+        prim, area, mass = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+        self.check(self.lib.rt3_light_download(self.h, prim.ctypes.data, area.ctypes.data, mass.ctypes.data))
+        return prim, area, mass
+
     def accel_import(self, nodes, tris):
         """install a tree built elsewhere over the same triangles (rt3_accel_download's format)"""
         n = np.ascontiguousarray(nodes)
