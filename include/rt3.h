@@ -309,7 +309,14 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      9 sincos_2pi (u -> sin,cos) 10 atan2 (y,x) 11 rng_seed(px,py,frame)
  *      12 division-free integer helpers (n,d -> n/d, n%d, wrap(int(n), (d & 0xFFFF)+1))
  *      13 octa_decode (fx,fy -> n) 14 sh3Evaluate (dir -> 9 coefficients) 15 64-lane bitonic sort (64 keys -> 64 keys, 64 lane ids)
- *      16 64-lane sum (64 floats -> 1) 17 octa_encode16 (n -> the 2 x 16-bit word of a shading-record normal) 18 octa_decode16 (word -> n).
+ *      16 64-lane sum (64 floats -> 1) 17 octa_encode16 (n -> the 2 x 16-bit word of a shading-record normal) 18 octa_decode16 (word -> n)
+ *      layered BSDF, material = albedo rgb, roughness, metalness; directions in the tangent frame (z = shading normal):
+ *      19 bsdf_setup + bsdf_eval (material, wo, wi -> value rgb, pdf in projected solid angle)
+ *      20 bsdf_setup + bsdf_sample (material, wo, u0, u1, u2 -> valid, wi, value / pdf, pdf in solid angle; zeros if not valid)
+ *      21 sample_vndf (alpha, wo, u0, u1 -> half vector) 22 direction_to_equirect_uv (dir -> u, v)
+ *      23 float3_to_rgb9e5 (rgb -> word) 24 rgb9e5_to_float3 (word -> rgb)
+ *      sky of the context (RT3_E_STATE without one): 25 light sample (u0, u1 -> dir, radiance, pdf in solid angle, texel x, texel y)
+ *      26 sky_eval_and_pdf (u, v -> bilinear radiance, pdf in solid angle).
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

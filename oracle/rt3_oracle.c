@@ -1677,7 +1677,7 @@ static uint32_t cdf_find(const float *cdf, uint32_t n, float u) { /* first index
     }
     return lo;
 }
-static void sky_sample(const orc_scene *s, float u0, float u1, float dir[3], float rad[3], float *pdf) {
+static void sky_sample(const orc_scene *s, float u0, float u1, float dir[3], float rad[3], float *pdf, uint32_t texel[2]) {
     uint32_t W = s->sky_w, H = s->sky_h;
     uint32_t y = cdf_find(s->cdf_marg, H, u0);
     float lo = y > 0 ? s->cdf_marg[y - 1] : 0.0f, hi = s->cdf_marg[y];
@@ -1702,6 +1702,7 @@ static void sky_sample(const orc_scene *s, float u0, float u1, float dir[3], flo
     dir[0] = (-c2) * st; dir[1] = ct; dir[2] = (-s2) * st;
     sky_eval(s, u, v, rad);
     *pdf = st > 0.0f ? s->pdf_uv[(size_t)y * W + x] / (2.0f * F_PI * F_PI * st) : 0.0f;
+    if (texel) { texel[0] = x; texel[1] = y; }
 }
 /* [north_star] Cranley-Patterson shift by a blue-noise channel: frac(u + c/256) */
 static inline float bn_shift(float u, uint32_t c) {
@@ -1797,6 +1798,55 @@ static int bsdf_sample(const bsdf_t *b, const float wo[3], float u0, float u1, f
     for (int k = 0; k < 3; k++) vop[k] = value[k] / pdf;
     *pdf_solid = pdf * wi[2];
     return 1;
+}
+
+/* ---- exported batch wrappers over the static shading functions above, for tests that check the math against
+ * independent references.  Rows of 32-bit words, the layouts of rt3_selftest_eval's ops 19-21, 25, 26 (include/rt3.h). */
+static void bsdf_from_row(const float *p, bsdf_t *b) {
+    float surf[11] = {p[0], p[1], p[2], 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, p[3], p[4]};
+    bsdf_setup(surf, b);
+}
+void orc_bsdf_eval(const float *in, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float *p = in + 11 * (size_t)i;
+        bsdf_t b;
+        bsdf_from_row(p, &b);
+        bsdf_eval(&b, p + 5, p + 8, out + 4 * (size_t)i, out + 4 * (size_t)i + 3);
+    }
+}
+void orc_bsdf_sample(const float *in, uint32_t n, uint32_t *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float *p = in + 11 * (size_t)i;
+        uint32_t *o = out + 8 * (size_t)i;
+        bsdf_t b;
+        bsdf_from_row(p, &b);
+        float wi[3] = {0.0f, 0.0f, 0.0f}, vop[3] = {0.0f, 0.0f, 0.0f}, pdf = 0.0f;
+        o[0] = (uint32_t)bsdf_sample(&b, p + 5, p[8], p[9], p[10], wi, vop, &pdf);
+        if (!o[0]) wi[0] = wi[1] = wi[2] = 0.0f;
+        for (int k = 0; k < 3; k++) { o[1 + k] = f2u(wi[k]); o[4 + k] = f2u(vop[k]); }
+        o[7] = f2u(pdf);
+    }
+}
+void orc_sample_vndf(const float *in, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float *p = in + 6 * (size_t)i;
+        sample_vndf(p[0], p + 1, p[4], p[5], out + 3 * (size_t)i);
+    }
+}
+void orc_scene_sky_sample(const orc_scene *s, const float *u, uint32_t n, uint32_t *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t *o = out + 9 * (size_t)i;
+        float dir[3], rad[3], pdf;
+        sky_sample(s, u[2 * (size_t)i], u[2 * (size_t)i + 1], dir, rad, &pdf, o + 7);
+        for (int k = 0; k < 3; k++) { o[k] = f2u(dir[k]); o[3 + k] = f2u(rad[k]); }
+        o[6] = f2u(pdf);
+    }
+}
+void orc_scene_sky_eval_pdf(const orc_scene *s, const float *uv, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) {
+        sky_eval(s, uv[2 * (size_t)i], uv[2 * (size_t)i + 1], out + 4 * (size_t)i);
+        out[4 * (size_t)i + 3] = sky_pdf(s, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]);
+    }
 }
 
 /* ------------------------------------------------------------------------------------------------ passes */
@@ -1905,7 +1955,7 @@ static void refmode_body(void *c, uint32_t bgn, uint32_t end, int tid) {
                     float ul0 = orc_uniform_float(seed, base + 3), ul1 = orc_uniform_float(seed, base + 4);
                     if (bnz) { ul0 = bn_shift(ul0, bn[2]); ul1 = bn_shift(ul1, bn[3]); }
                     float wl[3], rad[3], pl;
-                    sky_sample(s, ul0, ul1, wl, rad, &pl);
+                    sky_sample(s, ul0, ul1, wl, rad, &pl, NULL);
                     float cosl = dot3(N, wl);
                     if (cosl > 0.0f && pl > 0.0f) {
                         float fv[3], scale;

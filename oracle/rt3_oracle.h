@@ -157,6 +157,19 @@ void orc_trace_brute(const orc_scene *s, const float *rays, uint32_t n, float *t
 /* hit_logic.slang:5-40 : out = albedo emissive normal roughness metalness (11 floats) */
 void orc_hit_info(const orc_scene *s, uint32_t prim, float bu, float bv, float surf[11]);
 
+/* ---- the layered BSDF and the sky sampler one function at a time, for tests (n rows of 32-bit words each; same layouts as
+ * rt3_selftest_eval ops 19, 20, 21, 25, 26 in include/rt3.h).  Material rows: albedo rgb, roughness, metalness. ----
+ * orc_bsdf_eval:   {material, wo, wi} (11)       -> {value rgb, pdf (projected solid angle)} (4)
+ * orc_bsdf_sample: {material, wo, u0, u1, u2} (11) -> {valid, wi, value / pdf, pdf (solid angle)} (8; wi, vop, pdf zero if invalid)
+ * orc_sample_vndf: {alpha, wo, u0, u1} (6)       -> half vector (3)
+ * orc_scene_sky_sample:   {u0, u1} (2) -> {dir, radiance, pdf (solid angle), texel x, texel y} (9)
+ * orc_scene_sky_eval_pdf: {u, v} (2)   -> {bilinear radiance, pdf of the sky sampler (solid angle)} (4) */
+void orc_bsdf_eval(const float *in, uint32_t n, float *out);
+void orc_bsdf_sample(const float *in, uint32_t n, uint32_t *out);
+void orc_sample_vndf(const float *in, uint32_t n, float *out);
+void orc_scene_sky_sample(const orc_scene *s, const float *u, uint32_t n, uint32_t *out);
+void orc_scene_sky_eval_pdf(const orc_scene *s, const float *uv, uint32_t n, float *out);
+
 /* ---- passes over a pixel rectangle [x0,x1) x [y0,y1) of the window in g->window_size.
  * All images are full-window row-major arrays. ---- */
 /* gbuffer.slang:8-21 */

@@ -2217,6 +2217,7 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
+    if ((op == 25 || op == 26) && !c->d_sky) return fail(c, RT3_E_STATE, "selftest: the sky ops need a sky (rt3_scene_set_sky)");
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
     DevBuf<uint32_t> d_in, d_out;
@@ -2224,7 +2225,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     HIPC(c, d_out.alloc_bytes((size_t)n * ow * 4));
     hipError_t e = hipMemcpy(d_in.get(), in, (size_t)n * iw * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_selftest(c->stream, op, d_in.get(), n, d_out.get());
+        launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), (size_t)n * ow * 4, hipMemcpyDeviceToHost);

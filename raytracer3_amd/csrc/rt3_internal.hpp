@@ -99,7 +99,7 @@ void set_refill_lanes(uint32_t v);
 void set_pool_chunk(uint32_t v);
 void set_trace_blocks(uint32_t v);
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w);
-void launch_selftest(hipStream_t st, int op, const uint32_t* in, uint32_t n, uint32_t* out);
+void launch_selftest(hipStream_t st, int op, const SceneDev& sc, const uint32_t* in, uint32_t n, uint32_t* out);
 
 // Owner of at most one hipMalloc allocation, freed when the owner goes.  The only place the host layer frees device memory.
 template <typename T>

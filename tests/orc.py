@@ -78,6 +78,10 @@ def lib():
         L.orc_bounce1_rays.restype = u32; L.orc_bounce1_rays.argtypes = [vp, vp, vp, vp, vp, u32]
         L.orc_tile_pixels.restype = u32; L.orc_tile_pixels.argtypes = [u32, u32, u32, u32, vp]
         L.orc_octa_decode.argtypes = [f32, f32, vp]
+        for n in ("orc_bsdf_eval", "orc_bsdf_sample", "orc_sample_vndf"):
+            getattr(L, n).argtypes = [vp, u32, vp]
+        for n in ("orc_scene_sky_sample", "orc_scene_sky_eval_pdf"):
+            getattr(L, n).argtypes = [vp, vp, u32, vp]
         L.orc_sh3_evaluate.argtypes = [vp, vp]
         L.orc_wave_sort64.argtypes = [vp, vp]
         L.orc_wave_sum64.restype = f32; L.orc_wave_sum64.argtypes = [vp]
@@ -188,6 +192,20 @@ class Scene:
         pu = np.ctypeslib.as_array(C.cast(L.orc_sky_pdf_uv(self.h), C.POINTER(C.c_float)), (h, w)).copy()
         return al, tx, cm, pu
 
+    def sky_sample(self, u):
+        """the sky light sample for rows {u0, u1}: (n, 9) words {dir, radiance, pdf (f32 bits), texel x, texel y}"""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        out = np.zeros((len(u), 9), np.uint32)
+        lib().orc_scene_sky_sample(self.h, ptr(u), len(u), ptr(out))
+        return out
+
+    def sky_eval_pdf(self, uv):
+        """bilinear radiance and the sampler's solid-angle pdf at rows {u, v}: (n, 4) float32"""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 4), np.float32)
+        lib().orc_scene_sky_eval_pdf(self.h, ptr(uv), len(uv), ptr(out))
+        return out
+
     def trace_closest(self, rays, threads=8, counts=False):
         """rays: (8, n) float32 SoA ox,oy,oz,dx,dy,dz,tmin,tmax"""
         rays = np.ascontiguousarray(rays, np.float32); n = rays.shape[1]
@@ -241,6 +259,28 @@ class Scene:
 
 
 # ---- probe-GI passes (oracle/rt3_oracle_probes.c)
+def _rows(fn, rows, in_w, out_w, dtype):
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, in_w)
+    out = np.zeros((len(rows), out_w), dtype)
+    getattr(lib(), fn)(ptr(rows), len(rows), ptr(out))
+    return out
+
+
+def bsdf_eval(rows):
+    """rows {albedo rgb, roughness, metalness, wo, wi} -> (n, 4) float32 {value rgb, pdf in projected solid angle}"""
+    return _rows("orc_bsdf_eval", rows, 11, 4, np.float32)
+
+
+def bsdf_sample(rows):
+    """rows {albedo rgb, roughness, metalness, wo, u0, u1, u2} -> (n, 8) words {valid, wi, value / pdf, pdf in solid angle}"""
+    return _rows("orc_bsdf_sample", rows, 11, 8, np.uint32)
+
+
+def sample_vndf(rows):
+    """rows {alpha, wo, u0, u1} -> (n, 3) float32 half vectors"""
+    return _rows("orc_sample_vndf", rows, 6, 3, np.float32)
+
+
 def sh_buffer_floats(probes_x, probes_y):
     """floats in a float3x3 buffer indexed by zcurve(3 * gx + c, gy) (12 floats per element)"""
     return 12 * (lib().orc_zcurve(probes_x * 3 - 1, probes_y - 1) + 1)

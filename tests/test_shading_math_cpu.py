@@ -1,0 +1,521 @@
+"""The layered BSDF and the sky sampler against float64 restatements of their definitions (tests/ref_shading.py).  The GPU
+suite pins the device to the oracle bit for bit; these checks pin the shared formulas themselves: a wrong pdf, Jacobian or
+sampling frame present on both sides fails here.  The checks take a backend (the oracle here; the device, checked against the
+oracle first, in test_shading_math.py)."""
+import numpy as np
+import pytest
+from scipy import stats
+
+import orc
+import ref_shading as R
+from raytracer3_amd import scenes
+
+F32 = np.float32
+ONE_MINUS = float(np.nextafter(F32(1.0), F32(0.0)))  # 0.99999994, the largest u below 1
+
+# ------------------------------------------------------------------------------------------------ backends
+class Oracle:
+    name = "oracle"
+
+    def bsdf_eval(self, rows):
+        return orc.bsdf_eval(rows)
+
+    def bsdf_sample(self, rows):
+        return orc.bsdf_sample(rows)
+
+    def sample_vndf(self, rows):
+        return orc.sample_vndf(rows)
+
+    def equirect_uv(self, d):
+        L = orc.lib()
+        d = np.ascontiguousarray(d, F32)
+        out = np.zeros((len(d), 2), F32)
+        for i in range(len(d)):
+            L.orc_dir_to_equirect_uv(orc.ptr(d[i]), orc.ptr(out[i]))
+        return out
+
+    def rgb9e5(self, c):
+        L = orc.lib()
+        c = np.ascontiguousarray(c, F32)
+        return np.array([L.orc_float3_to_rgb9e5(orc.ptr(c[i])) for i in range(len(c))], np.uint32)
+
+    def sky(self, rgb):
+        return OracleSky(rgb)
+
+
+class OracleSky:
+    def __init__(self, rgb):
+        self.shape = rgb.shape[:2]
+        self.s = orc.Scene(scenes.cornell(), rgb, build=False)
+
+    def tables(self):
+        """(alias words, RGB9E5 texels, marginal CDF, pdf_uv)"""
+        return self.s.sky_tables(self.shape[1], self.shape[0])
+
+    def sample(self, u):
+        return self.s.sky_sample(u)
+
+    def eval_pdf(self, uv):
+        return self.s.sky_eval_pdf(uv)
+
+
+@pytest.fixture(scope="module")
+def backend():
+    return Oracle()
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+MATERIALS = [(a, r, m) for r in (0.0, 0.0499, 0.05, 0.3, 1.0) for m in (0.0, 0.5, 1.0)
+             for a in ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (0.9, 0.6, 0.3))]
+WO_Z = [-0.3, 0.0, 1e-5, float(np.nextafter(F32(1e-5), F32(1.0))), 1e-4, 0.01, 0.5, 1.0]
+
+
+def unit32(v):
+    v = np.asarray(v, np.float64)
+    return (v / np.linalg.norm(v)).astype(F32)
+
+
+def wo_from_z(z, phi=0.7):
+    """a view direction with the given fp32 cosine (exactly) and a generic azimuth"""
+    z = F32(z)
+    s = np.sqrt(max(0.0, 1.0 - float(z) ** 2))
+    return np.array([s * np.cos(phi), s * np.sin(phi), z], F32)
+
+
+def eval_grid():
+    """(material index, rows of 11 words) over MATERIALS x WO_Z x {mirror, grazing wi.z = 1e-7, below the horizon, two generic}"""
+    rows, mats = [], []
+    for mi, (a, r, m) in enumerate(MATERIALS):
+        for z in WO_Z:
+            wo = wo_from_z(z)
+            mirror = np.array([-wo[0], -wo[1], wo[2]], F32) if wo[2] > 0 else unit32([-wo[0], -wo[1], 0.3])
+            wis = [mirror, unit32([0.6, -0.8, 1e-7]), unit32([0.3, 0.1, -0.2]), unit32([0.2, 0.5, 0.8]), unit32([-0.9, 0.1, 0.3])]
+            wis[1][2] = F32(1e-7)
+            for wi in wis:
+                rows.append(np.concatenate([np.asarray(a, F32), [r, m], wo, wi]).astype(F32))
+                mats.append(mi)
+    return np.array(mats), np.array(rows, F32)
+
+
+def material_of(row):
+    return R.Material(row[0:3], row[3], row[4])
+
+
+# ------------------------------------------------------------------------------------------------ checks (shared with the GPU suite)
+def check_bsdf_eval(backend):
+    """value and pdf against float64 over the grid; the bound is R.bsdf_eval_rtol (64 fp32 roundings, plus the condition of D
+    at the specular peak and of the Fresnel power), i.e. 3.8e-6 away from the peak and ~1e-4 on the mirror direction at alpha 0.05"""
+    mats, rows = eval_grid()
+    out = backend.bsdf_eval(rows).astype(np.float64)
+    worst = 0.0
+    for i, row in enumerate(rows.astype(np.float64)):
+        mat = material_of(rows[i])
+        wo, wi = row[5:8], row[8:11]
+        v, p = R.bsdf_eval(mat, wo[None], wi[None])
+        tol = float(R.bsdf_eval_rtol(mat, wo, wi)) if wo[2] > R.COS_MIN and wi[2] > 0 else 4 * R.EPS32
+        got = np.concatenate([out[i, :3], out[i, 3:]])
+        want = np.concatenate([v[0], p])
+        if not wi[2] > 0:
+            assert (got == 0).all(), (i, got)
+            continue
+        err = np.abs(got - want) / np.maximum(np.abs(want), 1e-30)
+        err[want == 0] = np.abs(got[want == 0])
+        assert (err <= tol).all(), (i, rows[i].tolist(), got, want, err, tol)
+        worst = max(worst, float((err / tol).max()))
+    assert worst > 0.0  # the comparison saw rounding, i.e. both sides really computed
+
+
+def check_bsdf_reciprocity(backend):
+    """f(wo, wi) = f(wi, wo) where both cosines exceed the grazing threshold"""
+    mats, rows = eval_grid()
+    ok = (rows[:, 7] > F32(1e-5)) & (rows[:, 10] > F32(1e-5))
+    fwd = rows[ok]
+    rev = fwd.copy()
+    rev[:, 5:8], rev[:, 8:11] = fwd[:, 8:11], fwd[:, 5:8]
+    a, b = backend.bsdf_eval(fwd)[:, :3].astype(np.float64), backend.bsdf_eval(rev)[:, :3].astype(np.float64)
+    tol = np.array([R.bsdf_eval_rtol(material_of(r), r[5:8], r[8:11]) for r in fwd.astype(np.float64)])
+    assert (np.abs(a - b) <= 2 * tol[:, None] * np.maximum(np.abs(a), np.abs(b))).all()
+
+
+def sample_rows(material, wo, u):
+    a, r, m = material
+    n = len(u)
+    return np.concatenate([np.tile(np.array([*a, r, m], F32), (n, 1)), np.tile(np.asarray(wo, F32), (n, 1)), np.asarray(u, F32)], 1)
+
+
+def check_bsdf_sample_consistency(backend):
+    """A sample's weight is exactly value / pdf of the evaluation at its own direction, its solid-angle pdf is exactly
+    pdf_proj wi.z, wi is unit length, and value / pdf agrees with float64 -- at the edges of u and of the lobe choice."""
+    edge = [0.0, 0.5, 0.25, ONE_MINUS, 1e-7]
+    for a, r, m in [((0.9, 0.6, 0.3), 0.05, 0.0), ((0.9, 0.6, 0.3), 0.3, 0.5), ((1.0, 1.0, 1.0), 1.0, 1.0), ((0.0, 0.0, 0.0), 0.05, 0.0)]:
+        mat = R.Material(a, r, m)
+        p_spec = float(np.float32(_p_spec32(a, r, m)))
+        u2s = [0.0, p_spec, float(np.nextafter(F32(p_spec), F32(0))), ONE_MINUS, 0.5]
+        for wo in [np.array([0, 0, 1], F32), wo_from_z(0.5), wo_from_z(0.01), wo_from_z(0.97)]:
+            u = np.array([[u0, u1, u2] for u0 in edge for u1 in edge for u2 in u2s], F32)
+            rows = sample_rows((a, r, m), wo, u)
+            out = backend.bsdf_sample(rows)
+            valid = out[:, 0] == 1
+            assert valid.mean() > 0.5
+            wi, vop, pdf_s = out[:, 1:4].view(F32), out[:, 4:7].view(F32), out[:, 7].view(F32)
+            assert (wi[~valid] == 0).all() and (pdf_s[~valid] == 0).all()
+            wi, vop, pdf_s = wi[valid], vop[valid], pdf_s[valid]
+            assert np.abs(np.linalg.norm(wi.astype(np.float64), axis=1) - 1.0).max() < 4e-6
+            ev = backend.bsdf_eval(np.concatenate([rows[valid, :8], wi], 1))
+            value, pdf = ev[:, :3], ev[:, 3]
+            assert np.array_equal(vop, value / pdf[:, None])         # fp32 division, as the sampler does it
+            assert np.array_equal(pdf_s, pdf * wi[:, 2])
+            v64, p64 = R.bsdf_eval(mat, np.broadcast_to(wo.astype(np.float64), wi.shape), wi.astype(np.float64))
+            tol = R.bsdf_eval_rtol(mat, np.broadcast_to(wo.astype(np.float64), wi.shape), wi.astype(np.float64))
+            ref = v64 / p64[:, None]
+            assert (np.abs(vop - ref) <= 2 * tol[:, None] * np.abs(ref) + 1e-30).all()
+            # u2 exactly p_spec picks the diffuse lobe (u2 < p_spec is the specular test): cosine-distributed wi, mixture weight
+            if p_spec < 1:
+                d = (rows[valid, 10] == F32(p_spec)) & (rows[valid, 9] == 0.0)
+                assert d.any() and np.allclose(wi[d], [0.0, 0.0, 1.0], atol=1e-6)
+
+
+def _p_spec32(a, r, m):
+    """bsdf_setup's p_spec in fp32 (the u2 threshold of the lobe choice)"""
+    a = np.asarray(a, F32)
+    m = F32(m)
+    f0 = F32(0.04) + (a - F32(0.04)) * m
+    da = a * (F32(1.0) - m)
+    lum = lambda c: c[0] * F32(0.299) + c[1] * F32(0.587) + c[2] * F32(0.114)  # noqa: E731
+    ls, ld = lum(f0), lum(da)
+    p = ls / (ls + ld) if ls + ld > 0 else F32(1.0)
+    return min(max(p, F32(0.1)), F32(0.9)) if ld > 0 else F32(1.0)
+
+
+UNBIASED_CASES = [  # (albedo, roughness, metalness), wo.z -- all outside the VNDF frame band
+    (((0.9, 0.6, 0.3), 0.05, 0.0), 1.0), (((0.9, 0.6, 0.3), 0.05, 0.0), 0.5), (((0.9, 0.6, 0.3), 0.05, 0.0), 0.05),
+    (((0.9, 0.6, 0.3), 0.3, 0.5), 0.8), (((0.9, 0.6, 0.3), 0.3, 0.5), 0.2), (((0.9, 0.6, 0.3), 1.0, 0.0), 0.6),
+    (((1.0, 1.0, 1.0), 0.05, 1.0), 0.7), (((1.0, 1.0, 1.0), 0.3, 1.0), 0.3), (((0.95, 0.64, 0.54), 1.0, 1.0), 0.9),
+    (((0.0, 0.0, 0.0), 0.05, 0.0), 0.6), (((0.0, 0.0, 0.0), 0.5, 0.0), 0.1), (((0.5, 0.5, 0.5), 0.0, 0.0), 0.0),
+    (((0.2, 0.8, 0.4), 0.6, 0.3), float(np.nextafter(F32(1e-5), F32(1.0)))),
+]
+
+
+def stratified_u(log2n, seed):
+    """n = 2^log2n points: (u0, u1) jittered on a 2^(k) x 2^(log2n - k) grid, u2 an independent stratified permutation"""
+    n = 1 << log2n
+    k = log2n // 2
+    nx, ny = 1 << k, n >> k
+    rng = np.random.default_rng(seed)
+    i = np.arange(n)
+    u0 = ((i % nx) + rng.random(n)) / nx
+    u1 = ((i // nx) + rng.random(n)) / ny
+    u2 = (rng.permutation(n) + rng.random(n)) / n
+    return np.minimum(np.stack([u0, u1, u2], 1), ONE_MINUS).astype(F32)
+
+
+def check_unbiased(backend, log2n, z_max=5.0):
+    """E[value / pdf] = directional albedo: the sample mean over stratified samples (invalid samples count 0) agrees with the
+    float64 quadrature within z_max standard errors (the iid error, an upper bound for stratified samples)"""
+    for idx, (material, z) in enumerate(UNBIASED_CASES):
+        wo = wo_from_z(z, phi=0.3 + idx)
+        out = backend.bsdf_sample(sample_rows(material, wo, stratified_u(log2n, 100 + idx)))
+        vop = np.where(out[:, :1] == 1, out[:, 4:7].view(F32).astype(np.float64), 0.0)
+        mean, se = vop.mean(0), vop.std(0) / np.sqrt(len(vop))
+        want = R.directional_albedo(R.Material(*material), wo.astype(np.float64))
+        zs = np.abs(mean - want) / np.maximum(se, 1e-12)
+        assert (zs < z_max).all() or np.abs(mean - want).max() < 1e-6, (idx, material, z, mean, want, se, zs)
+
+
+def vndf_rows(alpha, wo, u):
+    n = len(u)
+    return np.concatenate([np.full((n, 1), alpha, F32), np.tile(np.asarray(wo, F32), (n, 1)), np.asarray(u[:, :2], F32)], 1)
+
+
+def view(theta_deg):
+    t = np.radians(theta_deg)
+    return np.array([np.sin(t), 0.0, np.cos(t)], F32)
+
+
+def vndf_sample_error(alpha, wo, u, h):
+    """|h - float64 sampler(u)| per sample, and its bound: 2e-6 plus four times the change of the float64 sample under input
+    perturbations of a few fp32 ulps (the fp32 evaluation is backward stable; near the rim of the projected disk, where
+    sqrt(1 - t1^2 - t2^2) -> 0, the map itself amplifies them)"""
+    wo = wo.astype(np.float64)
+    u0, u1 = u[:, 0].astype(np.float64), u[:, 1].astype(np.float64)
+    model = R.sample_vndf_as_written(alpha, wo, u0, u1)[0]
+    sens = np.zeros(len(u))
+    for d0, d1 in [(1, 0), (-1, 0), (0, 1), (0, -1)]:
+        m = R.sample_vndf_as_written(alpha, wo, u0 * (1 + d0 * 2.0**-21), u1 + d1 * 2.0**-22)[0]
+        sens = np.maximum(sens, np.abs(m - model).max(1))
+    return np.abs(h - model).max(1), 2e-6 + 4 * sens
+
+
+def check_vndf_outside_band(backend, log2n):
+    """Outside the band the half vectors follow the ideal visible-normal density: chi^2 over 16 x 16 bins of GGX-CDF
+    coordinates, and the first two moments within 5 standard errors; each sample is the float64 sampler's within fp32 error."""
+    for alpha, theta in [(0.05, 17.0), (0.05, 60.0), (0.3, 10.0), (0.3, 85.0), (1.0, 45.0)]:
+        wo = view(theta)
+        u = stratified_u(log2n, int(theta * 7 + alpha * 100))
+        h = backend.sample_vndf(vndf_rows(alpha, wo, u)).astype(np.float64)
+        err, tol = vndf_sample_error(alpha, wo, u, h)
+        assert (err <= tol).all(), (alpha, theta, err.max())
+        m1, m2, tot = R.vndf_moments(alpha, wo.astype(np.float64))
+        assert abs(tot - 1) < 1e-6
+        n = len(h)
+        for got, want, sd in [(h.mean(0), m1, h.std(0)), ((h * h).mean(0), m2, (h * h).std(0))]:
+            assert (np.abs(got - want) <= 5 * sd / np.sqrt(n) + 1e-9).all(), (alpha, theta, got, want, sd / np.sqrt(n))
+        probs = R.vndf_bin_probs(alpha, wo.astype(np.float64), 16, 16).ravel()
+        assert abs(probs.sum() - 1) < 1e-3  # 8 x 8 Gauss points per bin: the horizon bins converge slowly, far below the noise
+        probs /= probs.sum()
+        counts = np.bincount(R.h_to_bins(alpha, h, 16, 16), minlength=256)
+        keep = probs * n >= 5
+        exp = probs[keep] * n
+        chi2 = float((((counts[keep] - exp) ** 2) / exp).sum() + (counts[~keep].sum() - probs[~keep].sum() * n) ** 2 / max(probs[~keep].sum() * n, 1))
+        assert stats.chi2.sf(chi2, keep.sum()) > 1e-6, (alpha, theta, chi2, keep.sum())
+
+
+VNDF_BAND_GAP = -0.0014414  # E[h.x] as written - ideal at alpha = 0.05, view 15 degrees (float64 quadrature)
+
+
+def check_vndf_band(backend, log2n):
+    """Inside Vh.z >= 0.9999 (view angles below ~15.8 degrees at alpha = 0.05) each sample is the as-written float64 sampler
+    (T1 = (1, 0, 0)), and the mean h.x sits the pinned distance away from the ideal VNDF's: if the gap grows or vanishes the
+    sampling frame changed."""
+    alpha, wo = 0.05, view(15.0)
+    u = stratified_u(log2n, 15)
+    h = backend.sample_vndf(vndf_rows(alpha, wo, u)).astype(np.float64)
+    err, tol = vndf_sample_error(alpha, wo, u, h)
+    assert (err <= tol).all(), err.max()
+    # the as-written mean by float64 quadrature over (u0, u1), and the ideal one
+    xq, wq = np.polynomial.legendre.leggauss(400)
+    q = 0.5 * (xq + 1)
+    U0, U1 = np.meshgrid(1 - q * q, q, indexing="ij")  # u0 = 1 - q^2: the rim of the disk (nz -> 0) becomes smooth
+    W = np.outer(wq * q, 0.5 * wq).ravel()
+    asw = W @ R.sample_vndf_as_written(alpha, wo.astype(np.float64), U0.ravel(), U1.ravel())[0]
+    ideal = R.vndf_moments(alpha, wo.astype(np.float64))[0]
+    assert abs((asw[0] - ideal[0]) - VNDF_BAND_GAP) < 2e-6, asw[0] - ideal[0]
+    se = h[:, 0].std() / np.sqrt(len(h))
+    assert abs(h[:, 0].mean() - asw[0]) < 5 * se, (h[:, 0].mean(), asw[0], se)
+    assert abs(h[:, 0].mean() - ideal[0]) > 8 * se  # still resolvable at this sample count
+    return h[:, 0].mean(), asw[0], ideal[0], se
+
+
+# ---- sky
+def sky_gradient_sun(w, h, sun=40.0):
+    v = (np.arange(h) + 0.5) / h
+    col = np.clip(np.cos(np.pi * v), 0, 1)[:, None, None] * np.array([1.0, 0.9, 0.7]) + 0.05
+    sky = np.broadcast_to(col, (h, w, 3)).copy()
+    sky[h // 5:h // 5 + 2, w // 3:w // 3 + 3] += sun
+    return sky.astype(F32)
+
+
+def sky_cases():
+    rng = np.random.default_rng(5)
+    dark = np.full((64, 48, 3), 1e-7, F32)
+    dark[40:42, 20:22] = 1e4  # rows after the sun add less than an ulp of 1: tied CDF values
+    return {
+        "37x19": (sky_gradient_sun(37, 19) * rng.uniform(0.5, 1.5, (19, 37, 1))).astype(F32),
+        "5x3": rng.uniform(0.0, 3.0, (3, 5, 3)).astype(F32),
+        "256x128": scenes.sky(256, 128),
+        "sun1e4": dark,
+    }
+
+
+def guide_widths(cdf):
+    """hi - lo of every guide cell of the device's marginal search (rt3_scene_set_sky builds the cells this way)"""
+    h = len(cdf)
+    g, i = [], 0
+    for k in range(h + 1):
+        thr = F32(k) / F32(h)
+        while i < h - 1 and not (cdf[i] > thr):
+            i += 1
+        g.append(i)
+    return np.array([min(g[k + 1], h - 1) - g[max(k - 1, 0)] for k in range(h)])
+
+
+def sky_u_edges(cdf, n_random, seed):
+    """u0 on every marginal CDF value and its float neighbours (and 0, 1-), u1 random; plus n_random uniform pairs"""
+    c = np.unique(np.concatenate([[0.0], cdf.astype(F32)]))
+    u0 = np.concatenate([c, np.nextafter(c, F32(0)), np.nextafter(c, F32(1)), [0.0, ONE_MINUS]]).astype(F32)
+    u0 = u0[(u0 >= 0) & (u0 < 1)]
+    rng = np.random.default_rng(seed)
+    u = np.stack([u0, rng.random(len(u0))], 1)
+    return np.concatenate([u, rng.random((n_random, 2))]).clip(0, ONE_MINUS).astype(F32), len(u0)
+
+
+def check_sky(sk, n_random, seed):
+    """dir, texel, pdf and radiance of the sky sampler against float64 inversion of its tables; texel counts by chi^2"""
+    al, tx, cm, pu = sk.tables()
+    H, W = al.shape
+    rgb = R.rgb9e5_decode(tx)
+    u, n_edge = sky_u_edges(cm, n_random, seed)
+    out = sk.sample(u)
+    d, rad, pdf = out[:, 0:3].view(F32).astype(np.float64), out[:, 3:6].view(F32).astype(np.float64), out[:, 6].view(F32).astype(np.float64)
+    x, y = out[:, 7].astype(np.int64), out[:, 8].astype(np.int64)
+    # zero-width rows (tied CDF values) are never returned
+    lo = np.where(y > 0, cm[np.maximum(y - 1, 0)], F32(0))
+    assert (cm[y] > lo).all()
+    rx, ry, ru, rv = R.sky_invert(cm, al, u[:, 0], u[:, 1])
+    assert np.array_equal(y, ry) and np.array_equal(x, rx)
+    assert np.abs(np.linalg.norm(d, axis=1) - 1).max() < 4e-6
+    assert np.abs(d - R.equirect_dir(ru, rv)).max() < 4e-6
+    du, dv = R.dir_to_equirect(d)
+    st = np.sin(np.pi * rv)  # an error e in dir moves u by e / (2 pi sin(theta)) and v by e / (pi sin(theta)), or sqrt(2 e) / pi at a pole
+    assert (np.abs(np.mod(du - ru + 0.5, 1.0) - 0.5) * st < 4e-6).all()
+    assert (np.abs(dv - rv) < 4e-6 / (np.pi * st) + np.sqrt(8e-6) / np.pi).all()
+    # pdf = pdf_uv[texel] / (2 pi^2 sin(theta)); fp32 v carries ~6e-8 absolute error, amplified by cot near the poles
+    want = pu[y, x] / R.equirect_jacobian(rv)
+    tol = 1e-6 + 2e-7 * np.pi * np.abs(1.0 / np.tan(np.pi * rv))
+    assert (np.abs(pdf / want - 1) <= tol).all(), np.abs(pdf / want - 1).max()
+    # bilinear radiance at the sampled point
+    ref = R.sky_bilinear(rgb, ru, rv)
+    # fp32 bilinear weights: a few roundings of the largest corner; fp32 (u, v) vs float64: ~1e-7 times the texel-to-texel slope
+    assert (np.abs(rad - ref) <= 8 * R.EPS32 * rgb.max() + 2e-7 * _lipschitz(rgb)).all(), np.abs(rad - ref).max()
+    # texel counts of the random part: chi^2 against pdf_uv / (w h)
+    xy = y[n_edge:] * W + x[n_edge:]
+    n = len(xy)
+    p = pu.astype(np.float64).ravel() / (W * H)
+    counts = np.bincount(xy, minlength=W * H)
+    keep = p * n >= 5
+    exp = p[keep] * n
+    rest_e = max(n - exp.sum(), 1e-9)
+    chi2 = float(((counts[keep] - exp) ** 2 / exp).sum() + (counts[~keep].sum() - rest_e) ** 2 / rest_e)
+    assert stats.chi2.sf(chi2, keep.sum()) > 1e-6, (chi2, keep.sum())
+    return d, pdf, x, y, n_edge
+
+
+def _lipschitz(rgb):
+    """largest radiance step between neighbouring texels, times the texel count (bounds d radiance / d u, d v)"""
+    H, W = rgb.shape[:2]
+    return max(np.abs(np.diff(rgb, axis=0)).max() * H if H > 1 else 0, np.abs(np.diff(rgb, axis=1)).max() * W)
+
+
+def check_sky_eval_roundtrip(backend, sk, d, pdf, x, y, n_edge):
+    """sky_eval_and_pdf at direction_to_equirect_uv(dir) returns the sampler's pdf, unless the recomputed texel differs -- rare
+    among random samples, and then the float64 coordinate lies within 2e-6 (the polynomial atan2's error) of a texel edge.  The
+    first n_edge samples start ON row edges (u0 = a CDF value); the poles (sin(theta) < 1e-4, pdf -> 0 or huge) are left out."""
+    al, tx, cm, pu = sk.tables()
+    H, W = al.shape
+    keep = np.abs(d[:, 1].astype(F32)) < 1
+    d, pdf, x, y, n_edge = d[keep], pdf[keep], x[keep], y[keep], int(keep[:n_edge].sum())
+    uv = backend.equirect_uv(d.astype(F32))
+    ev = sk.eval_pdf(uv)
+    ix = np.clip((uv[:, 0] * F32(W)).astype(np.int64), 0, W - 1)
+    iy = np.clip((uv[:, 1] * F32(H)).astype(np.int64), 0, H - 1)
+    same = (ix == x) & (iy == y)
+    # the same texel density over sin(theta) of the recomputed v: the polynomial atan2 moves v by up to ~2e-6, and the fp32
+    # direction by 1e-7 / (pi sin(theta)) more towards the poles; relative pdf error = pi |cot(pi v)| dv
+    dv = coord_error(d)
+    tol = 4e-6 + np.pi / np.abs(np.tan(np.pi * uv[same, 1].astype(np.float64))) * dv[same]
+    assert (np.abs(ev[same, 3] / pdf[same] - 1) <= tol).all(), np.abs(ev[same, 3] / pdf[same] - 1).max()
+    assert (~same[n_edge:]).mean() < 2e-3, (~same[n_edge:]).mean()
+    u64, v64 = R.dir_to_equirect(d[~same])
+    edge = np.minimum(np.abs(u64 * W - np.round(u64 * W)) / W, np.abs(v64 * H - np.round(v64 * H)) / H)
+    assert (edge < dv[~same]).all(), (edge / dv[~same]).max()
+
+
+def coord_error(d):
+    """error bound of direction_to_equirect_uv's (u, v) for fp32 directions: the polynomial atan2 (~1e-6 rad, / pi) plus one
+    fp32 rounding of the direction, which moves the angles by 1.2e-7 / sin(theta)"""
+    st = np.sqrt(np.maximum(1.0 - d[:, 1].astype(np.float64) ** 2, 1e-30))
+    return 2e-6 + 1.2e-7 / (np.pi * st)
+
+
+def check_sky_seams(sk):
+    """bilinear radiance and pdf at u in {0, 1-}, v in {0, 1-} and inside, against float64 (wrap u, clamp v)"""
+    al, tx, cm, pu = sk.tables()
+    H, W = al.shape
+    rgb = R.rgb9e5_decode(tx)
+    vals = np.array([0.0, ONE_MINUS, 0.5 / W, 1.0 - 0.5 / W, 0.37, 1e-7], F32)
+    vv = np.array([0.0, ONE_MINUS, 0.5 / H, 1.0 - 0.5 / H, 0.61, 1e-7], F32)
+    uv = np.array([[a, b] for a in vals for b in vv], F32)
+    ev = sk.eval_pdf(uv).astype(np.float64)
+    ref = R.sky_bilinear(rgb, uv[:, 0].astype(np.float64), uv[:, 1].astype(np.float64))
+    scale = rgb.max()
+    assert np.abs(ev[:, :3] - ref).max() <= 8 * R.EPS32 * scale + _lipschitz(rgb) * 2 * R.EPS32, np.abs(ev[:, :3] - ref).max()
+    ix = np.clip((uv[:, 0] * F32(W)).astype(np.int64), 0, W - 1)
+    iy = np.clip((uv[:, 1] * F32(H)).astype(np.int64), 0, H - 1)
+    jac = R.equirect_jacobian(uv[:, 1].astype(np.float64))
+    pos = jac > 0
+    want = pu[iy, ix] / jac
+    assert (np.abs(ev[pos, 3] / want[pos] - 1) < 1e-5).all()
+    assert (ev[~pos, 3] == 0).all()  # v = 0: the pole, sin(theta) = 0
+
+
+RGB9E5_MAX = 511.0 / 512.0 * 65536.0
+
+
+def rgb9e5_inputs():
+    e = []
+    for base in [0.0, 1e-45, 1e-40, 2.0**-126 * 0.75, 2.0**-16, 2.0**-16 * 1.5, 2.0**-17, 2.0**-24, 1.0, 0.5, 3.14159, 1000.0,
+                 RGB9E5_MAX, float(np.nextafter(F32(RGB9E5_MAX), F32(1e9))), 65536.0, 1e9, 3.4e38, -1.0, -0.0, -1e-40]:
+        e.append([base, base * 0.5, base * 0.01])
+    for k in range(-16, 16):  # the mantissa carry: max rounds up to 512 -> next exponent
+        s = 2.0 ** (k - 8)
+        e += [[511.5 * s, 3.0 * s, 0.0], [511.49 * s, 0.25 * s, 1.0 * s], [511.51 * s, 511.51 * s, 255.5 * s], [255.75 * s, 0.0, 0.0]]
+    rng = np.random.default_rng(9)
+    e += list(np.exp(rng.uniform(-14, 11, (300, 3))) * rng.uniform(0, 1, (300, 1)) ** 2)
+    return np.array(e, F32)
+
+
+def check_rgb9e5(words, c, allow_ambiguous=True):
+    """packer words against the float64 definition; decoded values within half a mantissa step of the clamped input"""
+    want, amb = R.rgb9e5_encode(c.astype(np.float64))
+    bad = words != want
+    if allow_ambiguous:
+        assert not (bad & ~amb).any(), (c[bad & ~amb], words[bad & ~amb], want[bad & ~amb])
+    else:
+        assert not bad.any()
+    cc = np.clip(c.astype(np.float64), 0, RGB9E5_MAX)
+    step = np.exp2((words & 31).astype(np.float64) - 24)
+    assert (np.abs(R.rgb9e5_decode(words) - cc) <= 0.5 * step[:, None] * (1 + 1e-6) + 2.0**-25).all()
+
+
+# ------------------------------------------------------------------------------------------------ the oracle
+def test_bsdf_eval_matches_float64(backend):
+    check_bsdf_eval(backend)
+
+
+def test_bsdf_is_reciprocal(backend):
+    check_bsdf_reciprocity(backend)
+
+
+def test_bsdf_sample_is_its_own_evaluation(backend):
+    check_bsdf_sample_consistency(backend)
+
+
+def test_bsdf_sampling_is_unbiased(backend):
+    check_unbiased(backend, 16)
+
+
+def test_vndf_outside_the_frame_band_is_ideal(backend):
+    check_vndf_outside_band(backend, 18)
+
+
+def test_vndf_inside_the_frame_band_is_pinned(backend):
+    check_vndf_band(backend, 20)
+
+
+@pytest.mark.parametrize("name", ["37x19", "5x3", "256x128", "sun1e4"])
+def test_sky_sampler_matches_float64(backend, name):
+    rgb = sky_cases()[name]
+    sk = backend.sky(rgb)
+    d, pdf, x, y, n_edge = check_sky(sk, 1 << 17, 11)
+    m = n_edge + 8192
+    check_sky_eval_roundtrip(backend, sk, d[:m], pdf[:m], x[:m], y[:m], n_edge)
+    check_sky_seams(sk)
+
+
+def test_sky_cases_reach_the_search_edges():
+    """the skies above cover tied CDF values and guide cells of every width the guided search distinguishes (<= 2, 3, > 3)"""
+    widths, ties = set(), 0
+    for name, rgb in sky_cases().items():
+        cm = OracleSky(rgb).tables()[2]
+        widths |= set(np.minimum(guide_widths(cm), 4).tolist())
+        ties += int((np.diff(cm) == 0).sum())
+    assert {0, 1, 2, 3, 4} <= widths and ties > 0, (widths, ties)
+
+
+def test_rgb9e5_matches_float64(backend):
+    c = rgb9e5_inputs()
+    check_rgb9e5(backend.rgb9e5(c), c)
+    # the sky's texels are packed by the same definition (finite, non-negative radiance only)
+    pos = c[(c >= 0).all(1) & (c <= 3.0e38).all(1)]
+    sk = backend.sky(pos.reshape(1, -1, 3))
+    check_rgb9e5(sk.tables()[1].ravel(), pos)
