@@ -473,6 +473,25 @@ int reserve_counters(rt3_ctx* c, uint32_t n, uint32_t* first) {
     HIPC(c, hipMemsetAsync(c->d_counters.get() + *first, 0, (size_t)n * 4, c->stream));
     return RT3_OK;
 }
+// a traversal launch over the context's queues (`stride` records), counting into its totals when RT3_OPT_COUNT_TRAVERSAL is on
+TraceLaunch ctx_trace(rt3_ctx* c) {
+    TraceLaunch L;
+    L.stride = c->cap;
+    L.count = c->opt_count;
+    L.totals = c->opt_count ? c->d_totals.get() : nullptr;
+    return L;
+}
+// closest hits of the n primary rays in c->rays[0], into c->hits
+int trace_primary(rt3_ctx* c, uint32_t n) {
+    uint32_t wc_slot;
+    if (int r = reserve_counters(c, 1, &wc_slot)) return r;  // ray-pool cursor of the launch
+    TraceLaunch L = ctx_trace(c);
+    L.rays = c->rays[0].get(); L.n = n; L.work_counter = c->d_counters.get() + wc_slot; L.hits = c->hits.get();
+    c->primary_rays_pending += n;
+    ScopedTimer t(c, CAT_EXTEND);
+    launch_extend(c->stream, c->bvh, L);
+    return RT3_OK;
+}
 
 // ---------------------------------------------------------------------------------------------- passes
 int check_window(rt3_ctx* c, const rt3_gconst* g, uint32_t* W, uint32_t* H) {
@@ -512,14 +531,7 @@ int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const 
         ScopedTimer t(c, CAT_OTHER);
         launch_raygen(c->stream, gd, pl->dev.get(), pl->count, c->rays[0].get(), S);
     }
-    uint32_t wc_slot;
-    if (int r = reserve_counters(c, 1, &wc_slot)) return r;  // ray-pool cursor of the launch
-    {
-        ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh, c->rays[0].get(), S, nullptr, pl->count, pl->count, c->hits.get(), nullptr, nullptr,
-                      c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
-    }
-    c->primary_rays_pending += pl->count;
+    if (int r = trace_primary(c, pl->count)) return r;
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_gbuffer(c->stream, scene_dev(c), pl->dev.get(), pl->count, W, c->hits.get(), S, gb->ptr, (float*)dp->ptr);
@@ -605,19 +617,25 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
             }
             cur ^= 1;
             if (nee) {
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
+                tr.contrib = c->sh_contrib.get(); tr.lacc = c->lacc.get();
                 ScopedTimer t(c, CAT_SHADOW);
-                launch_shadow(c->stream, c->opt_count, c->bvh, c->sh_rays.get(), S, sh_cnt_at(bn), 0, n_first, c->sh_contrib.get(), nullptr, c->lacc.get(), S,
-                              nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, pool_cur + B + bn);
+                launch_shadow(c->stream, c->bvh, tr);
             }
             if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
+                tr.contrib = c->sh2_contrib.get(); tr.lacc = c->lacc.get(); tr.tmax = c->sh2_tmax.get();
                 ScopedTimer t(c, CAT_SHADOW);
-                launch_shadow(c->stream, c->opt_count, c->bvh, c->sh2_rays.get(), S, emit_cnt + bn, 0, n_first, c->sh2_contrib.get(), nullptr, c->lacc.get(), S,
-                              nullptr, nullptr, nullptr, c->opt_count ? c->d_totals.get() : nullptr, emit_cnt + B + bn, c->sh2_tmax.get());
+                launch_shadow(c->stream, c->bvh, tr);
             }
             if (bn != B - 1) {
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->rays[cur].get(); tr.count_ptr = ext_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + bn;
+                tr.hits = c->hits.get(); tr.payload = true;
                 ScopedTimer t(c, CAT_EXTEND);
-                launch_extend(c->stream, c->opt_count, c->bvh, c->rays[cur].get(), S, ext_cnt_at(bn), 0, n_first, c->hits.get(), nullptr, nullptr,
-                              c->opt_count ? c->d_totals.get() : nullptr, pool_cur + bn, true);
+                launch_extend(c->stream, c->bvh, tr);
             }
         }
         {
@@ -700,14 +718,7 @@ int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, c
         ScopedTimer t(c, CAT_OTHER);
         launch_probe_raygen(c->stream, gd, W, x / 8, y / 8, (const float*)dp->ptr, dir->ptr, at->ptr, c->rays[0].get(), S, c->T[0].get());
     }
-    uint32_t wc_slot;
-    if (int r = reserve_counters(c, 1, &wc_slot)) return r;
-    {
-        ScopedTimer t(c, CAT_EXTEND);
-        launch_extend(c->stream, c->opt_count, c->bvh, c->rays[0].get(), S, nullptr, n, n, c->hits.get(), nullptr, nullptr,
-                      c->opt_count ? c->d_totals.get() : nullptr, c->d_counters.get() + wc_slot);
-    }
-    c->primary_rays_pending += n;
+    if (int r = trace_primary(c, n)) return r;
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, x / 8, y / 8, c->hits.get(), c->T[0].get(), pv->ptr, at->ptr);
@@ -2180,13 +2191,14 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
     HIPC(c, hipEventCreate(&ev.e0));
     HIPC(c, hipEventCreate(&ev.e1));
     if (repeat < 1) repeat = 1;
+    TraceLaunch L;
+    L.rays = d_rays.get(); L.stride = n; L.n = n; L.work_counter = d_cur.get();
+    L.hits = d_hits.get(); L.occluded = d_occ.get();  // the launch below writes one of the two
+    L.count = count; L.cnt_nodes = d_cn.get(); L.cnt_tris = d_ct.get();
     auto launch = [&]() {
         (void)hipMemsetAsync(d_cur.get(), 0, 4, c->stream);  // ray-pool cursor
-        if (any_hit)
-            launch_shadow(c->stream, count, c->bvh, d_rays.get(), n, nullptr, n, n, nullptr, nullptr, nullptr, 0, d_occ.get(), d_cn.get(), d_ct.get(), nullptr,
-                          d_cur.get());
-        else
-            launch_extend(c->stream, count, c->bvh, d_rays.get(), n, nullptr, n, n, d_hits.get(), d_cn.get(), d_ct.get(), nullptr, d_cur.get());
+        if (any_hit) launch_shadow(c->stream, c->bvh, L);
+        else launch_extend(c->stream, c->bvh, L);
     };
     launch();  // warm-up (also the result-producing launch)
     HIPC(c, hipEventRecord(ev.e0, c->stream));

@@ -28,8 +28,8 @@ constexpr int kLayoutWide64Q = 2;    // 64 B: origin + power-of-two steps + four
 constexpr int kLayoutTwoLevel = 4;   // RT3_OPT_INSTANCE_MODE 1: kLayoutWide64Q nodes of a top tree over instance records and shared bottom trees (rt3_tlas.hip)
 constexpr uint32_t kMaxStack = 64;         // traversal stack entries: LDS short stack (12) + private spill (52)
 constexpr uint32_t kTopCacheNodes = 128;   // top-of-tree nodes the traversal kernels hold in LDS (8 KiB)
-// counting mode (RT3_OPT_COUNT_TRAVERSAL): the words of the context's block of 64-bit traversal totals.  launch_extend / launch_shadow
-// take the block's base; each kernel adds its {nodes, tris} at the word it is handed (so a kind's two words are adjacent) and its
+// counting mode (RT3_OPT_COUNT_TRAVERSAL): the words of the context's block of 64-bit traversal totals.  TraceLaunch::totals is the
+// block's base; each kernel adds its {nodes, tris} at the word it is handed (so a kind's two words are adjacent) and its
 // LDS-served node visits at a second pointer.
 enum TotalsWord : int {
     kTotExtendNodes = 0,
@@ -174,13 +174,26 @@ struct LbvhResult {
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
 };
+// One traversal launch over a ray queue: closest hit (launch_extend) or any hit (launch_shadow).  Each reads only its own outputs.
+struct TraceLaunch {
+    const float* rays = nullptr;          // two float4 streams of `stride` records, {o.xyz, tmin} then {d.xyz, tmax}
+    size_t stride = 0;
+    const uint32_t* count_ptr = nullptr;  // the queue's length on the device, or null
+    uint32_t n = 0;                       // the queue's length without count_ptr; with it, the upper bound that sizes the grid
+    uint32_t* work_counter = nullptr;     // the launch's ray-pool cursor, zero before it
+    float* hits = nullptr;                // closest hit: one float4 {t, u, v, prim} per ray
+    bool payload = false;                 // the .w of the ray records carry the path's pdf and id (the path tracer's own queue)
+    const float* contrib = nullptr;       // any hit: an unoccluded ray adds its contribution to its path's radiance slot in lacc
+    float* lacc = nullptr;
+    const float* tmax = nullptr;          // every ray has its own range (kRayTMin, tmax[i]): the emitter queue of RT3_F_NEE_EMISSIVE
+    uint32_t* occluded = nullptr;         // set: the launch only reports occlusion (rt3_trace_rays)
+    bool count = false;                   // counting: per-ray node visits / triangle tests (either may be null) and the totals (TotalsWord)
+    uint32_t *cnt_nodes = nullptr, *cnt_tris = nullptr;
+    unsigned long long* totals = nullptr;
+};
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
-void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
-                   uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, bool payload = false);
-// tmax != nullptr: every ray has its own range (kRayTMin, tmax[i]) -- the emitter shadow queue of RT3_F_NEE_EMISSIVE
-void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
-                   uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
-                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, const float* tmax = nullptr);
+void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
+void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
 // On failure *out may hold some of its arrays: they go with it.
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,

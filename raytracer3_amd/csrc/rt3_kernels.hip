@@ -529,6 +529,28 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
     }
 }
 
+// counting mode: the per-ray counts a traversal kernel stores (cnt_nodes / cnt_tris, either may be null) and the sums each thread adds,
+// once, at its end to totals[0..1] and lds_total
+template <bool COUNT>
+struct TraceCounts {
+    uint32_t *cnt_nodes, *cnt_tris;
+    unsigned long long nodes = 0, tris = 0, lds = 0;
+    __device__ __forceinline__ void ray(uint32_t i, uint32_t cn, uint32_t ct, uint32_t cl) {
+        if (!COUNT) return;
+        if (cnt_nodes) cnt_nodes[i] = cn;
+        if (cnt_tris) cnt_tris[i] = ct;
+        nodes += cn;
+        tris += ct;
+        lds += cl;
+    }
+    __device__ __forceinline__ void add_totals(unsigned long long* totals, unsigned long long* lds_total) {
+        if (!COUNT || !totals) return;
+        atomicAdd(&totals[0], nodes);
+        atomicAdd(&totals[1], tris);
+        if (lds_total) atomicAdd(lds_total, lds);
+    }
+};
+
 // closest-hit over a ray queue.  rays: two float4 streams of `stride` records, {o.xyz, tmin} then {d.xyz, tmax};
 // hits: one float4 {t, u, v, prim} per ray.  16-byte records are the widest coalesced access (1 KiB per wave instruction).
 template <bool COUNT, int LAYOUT>
@@ -542,25 +564,15 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
     __shared__ float4 s_top[4 * kTopNodes];
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
-    unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
+    TraceCounts<COUNT> counts{cnt_nodes, cnt_tris};
     auto finish = [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float, float, float, float) {
         // one 16-byte record per ray: with persistent waves rays finish out of order, four SoA streams would be four
         // scattered partial-line writes
         reinterpret_cast<float4*>(hits)[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
-        if (COUNT) {
-            if (cnt_nodes) cnt_nodes[i] = cn;
-            if (cnt_tris) cnt_tris[i] = ct;
-            tot_n += cn;
-            tot_t += ct;
-            tot_l += cl;
-        }
+        counts.ray(i, cn, ct, cl);
     };
     trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top);
-    if (COUNT && totals) {
-        atomicAdd(&totals[0], tot_n);
-        atomicAdd(&totals[1], tot_t);
-        if (lds_total) atomicAdd(lds_total, tot_l);
-    }
+    counts.add_totals(totals, lds_total);
 }
 
 // any-hit over the shadow queue; unoccluded rays add their contribution to the path's radiance slot.
@@ -570,8 +582,7 @@ template <bool COUNT, int LAYOUT, bool RANGE = false>
 __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
                                                          const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
-                                                         const float* __restrict__ contrib, const uint32_t* __restrict__ pid,
-                                                         float* __restrict__ lacc, size_t lstride,
+                                                         const float* __restrict__ contrib, float* __restrict__ lacc,
                                                          uint32_t* __restrict__ occluded_out, uint32_t* __restrict__ cnt_nodes,
                                                          uint32_t* __restrict__ cnt_tris, unsigned long long* __restrict__ totals,
                                                          uint32_t* __restrict__ work_counter, unsigned long long* __restrict__ lds_total,
@@ -580,7 +591,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     __shared__ float4 s_top[4 * kTopNodes];
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
-    unsigned long long tot_n = 0, tot_t = 0, tot_l = 0;
+    TraceCounts<COUNT> counts{cnt_nodes, cnt_tris};
     trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE>(
         nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
@@ -593,20 +604,10 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
                 float4 v = *L;
                 *L = make_float4(v.x + c_r, v.y + c_g, v.z + c_b, 0.0f);
             }
-            if (COUNT) {
-                if (cnt_nodes) cnt_nodes[i] = cn;
-                if (cnt_tris) cnt_tris[i] = ct;
-                tot_n += cn;
-                tot_t += ct;
-                tot_l += cl;
-            }
+            counts.ray(i, cn, ct, cl);
         },
         occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr, tmax);
-    if (COUNT && totals) {
-        atomicAdd(&totals[0], tot_n);
-        atomicAdd(&totals[1], tot_t);
-        if (lds_total) atomicAdd(lds_total, tot_l);
-    }
+    counts.add_totals(totals, lds_total);
 }
 
 // ------------------------------------------------------------------------------------------------ gbuffer pass
@@ -1330,30 +1331,27 @@ static void dispatch_traversal(bool count, int layout, Launch launch) {
     if (count) by_layout(std::true_type{});
     else by_layout(std::false_type{});
 }
-// totals: the base of the context's counter block (TotalsWord) or nullptr
-void launch_extend(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
-                   uint32_t max_n, float* hits, uint32_t* cn, uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, bool payload) {
-    const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
-    unsigned long long* const tot = totals ? totals + kTotExtendNodes : nullptr;
-    unsigned long long* const lds_tot = totals ? totals + kTotExtendLds : nullptr;
-    dispatch_traversal(count, bvh.layout, [&](auto c, auto l) {
+void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
+    const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
+    unsigned long long* const tot = L.totals ? L.totals + kTotExtendNodes : nullptr;
+    unsigned long long* const lds_tot = L.totals ? L.totals + kTotExtendLds : nullptr;
+    dispatch_traversal(L.count, bvh.layout, [&](auto c, auto l) {
         hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
-                           bvh.n_top, rays, stride, count_ptr, count_imm, hits, cn, ct, tot, work_counter, payload ? 1 : 0, lds_tot);
+                           bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.hits, L.cnt_nodes, L.cnt_tris, tot, L.work_counter, L.payload ? 1 : 0, lds_tot);
     });
 }
-void launch_shadow(hipStream_t st, bool count, const LbvhResult& bvh, const float* rays, size_t stride, const uint32_t* count_ptr, uint32_t count_imm,
-                   uint32_t max_n, const float* contrib, const uint32_t* pid, float* lacc, size_t lstride, uint32_t* occluded_out, uint32_t* cn,
-                   uint32_t* ct, unsigned long long* totals, uint32_t* work_counter, const float* tmax) {
-    const unsigned grid = grid_for(max_n, kExtendBlock, g_trace_max_blocks);
-    unsigned long long* const tot = totals ? totals + kTotShadowNodes : nullptr;
-    unsigned long long* const lds_tot = totals ? totals + kTotShadowLds : nullptr;
-    dispatch_traversal(count, bvh.layout, [&](auto c, auto l) {
-        if (tmax)
-            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, true>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(),
-                               bvh.top.get(), bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot, tmax);
-        else
-            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
-                               bvh.n_top, rays, stride, count_ptr, count_imm, contrib, pid, lacc, lstride, occluded_out, cn, ct, tot, work_counter, lds_tot, nullptr);
+void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
+    const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
+    unsigned long long* const tot = L.totals ? L.totals + kTotShadowNodes : nullptr;
+    unsigned long long* const lds_tot = L.totals ? L.totals + kTotShadowLds : nullptr;
+    dispatch_traversal(L.count, bvh.layout, [&](auto c, auto l) {
+        auto launch = [&](auto range) {
+            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, decltype(range)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(),
+                               bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.contrib, L.lacc, L.occluded, L.cnt_nodes,
+                               L.cnt_tris, tot, L.work_counter, lds_tot, L.tmax);
+        };
+        if (L.tmax) launch(std::true_type{});
+        else launch(std::false_type{});
     });
 }
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
