@@ -173,6 +173,21 @@ int rt3_scene_set_bluenoise(rt3_ctx *ctx, const uint8_t *rgba, uint32_t width, u
 /* base-colour texture `index` (dense indices 0..n-1): RGBA8 with sRGB-encoded colour, sampled bilinearly with repeat
  * addressing at mip 0 like Textures[i].SampleLevel(uvs, 0.0) (hit_logic.slang:31-33; bindless set 2, bindless/mod.rs:38-77) */
 int rt3_scene_set_texture(rt3_ctx *ctx, uint32_t index, const uint8_t *rgba_srgb, uint32_t width, uint32_t height);
+/* ---- alpha-masked cutout geometry: glTF alphaMode MASK (foliage, chains, fences).  No reference counterpart: the reference builds its
+ *      acceleration structures opaque (hit_logic.slang).  DESIGN.md section 4e.  One cutoff c per geometry of the last
+ *      rt3_scene_set_geometry (n = that count), or n = 0: all opaque.  c = 0 (the default, and what rt3_scene_set_geometry resets every
+ *      geometry to) is opaque, today's behaviour; 0 < c <= 1 masks the geometry: one of its ray-triangle intersections counts only if
+ *      alpha >= c, alpha = base_color[3] * tex_alpha(u, v) in fp32, where tex_alpha is the bilinear alpha of the base-colour texture at mip 0
+ *      with repeat addressing (texture_sample's texel coordinates and weights; the byte times 1 / 255, linear) and 1 without a texture, at
+ *      the uv that hit_finish interpolates with the candidate's barycentrics.  Hits are defined as sets: the closest hit is the minimum over
+ *      (t, prim) of the intersections in (tmin, tmax) that count, an any hit "some intersection counts" -- for every ray the library traces
+ *      (passes, rt3_trace_rays, both instance modes).  Shading is unchanged.  Masked geometries are left out of the emitter table of
+ *      RT3_F_NEE_EMISSIVE (their emission still counts, with weight 1, where a BSDF-sampled ray hits them).
+ *      A value that is not finite or not in [0, 1], or a wrong n, is RT3_E_INVALID and changes nothing.  The cutoffs take effect at the next
+ *      rt3_accel_build; setting them leaves an existing structure unusable like a geometry change (rt3_pass_launch, rt3_trace_rays and
+ *      rt3_accel_download return RT3_E_STATE, rt3_accel_refit RT3_E_STATE) until rt3_accel_build.  A masked geometry needs the default node
+ *      layout (else RT3_E_UNSUPPORTED at build); rt3_accel_import is RT3_E_UNSUPPORTED while any cutoff is > 0.  Borrowed for the call. ---- */
+int rt3_scene_set_alpha_cutoffs(rt3_ctx *ctx, const float *cutoffs, uint32_t n);
 
 /* ---- instances: the reference's world is a list of placed meshes (add_instance / loaded_assets, world/mod.rs:50-101) under a
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info
@@ -317,6 +332,8 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      23 float3_to_rgb9e5 (rgb -> word) 24 rgb9e5_to_float3 (word -> rgb)
  *      sky of the context (RT3_E_STATE without one): 25 light sample (u0, u1 -> dir, radiance, pdf in solid angle, texel x, texel y)
  *      26 sky_eval_and_pdf (u, v -> bilinear radiance, pdf in solid angle).
+ *      textures of the context: 27 tex_alpha (base-colour texture index as int32, u, v -> alpha in [0, 1]; 1 for an index without a texture),
+ *      the alpha-mask lookup of the traversal kernels (rt3_scene_set_alpha_cutoffs).
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

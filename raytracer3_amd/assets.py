@@ -43,6 +43,8 @@ class Material:
     roughness_factor: float = 1.0
     emission: tuple = (0.0, 0.0, 0.0)
     texture_offset: int = -1
+    alpha_cutoff: float = 0.0  # glTF alphaMode MASK: alphaCutoff (0 = opaque)
+    alpha: float = 1.0  # baseColorFactor[3] -> GeometryInfo.base_color[3]
 
 
 @dataclass
@@ -55,6 +57,12 @@ class Mesh:
     prim_counts: np.ndarray  # (g,) uint32
     names: list = field(default_factory=list)
     textures: list = field(default_factory=list)  # base-colour textures: (h, w, 4) uint8, sRGB-encoded colour
+    alpha_cutoffs: np.ndarray = None  # (g,) float32 alpha cutoff per geometry (rt3_scene_set_alpha_cutoffs); None -> zeros (all opaque)
+
+    def __post_init__(self):
+        if self.alpha_cutoffs is None:
+            self.alpha_cutoffs = np.zeros(len(self.geometries), np.float32)
+        self.alpha_cutoffs = np.ascontiguousarray(self.alpha_cutoffs, np.float32).reshape(len(self.geometries))
 
     @property
     def n_triangles(self) -> int:
@@ -74,7 +82,7 @@ class MeshBuilder:
     """Accumulates (positions, normals, uvs, triangles, material) parts into a `Mesh`."""
 
     def __init__(self):
-        self.v, self.i, self.g, self.c, self.names = [], [], [], [], []
+        self.v, self.i, self.g, self.c, self.names, self.cut = [], [], [], [], [], []
         self.nv = 0
         self.ni = 0
 
@@ -89,7 +97,7 @@ class MeshBuilder:
         tris = np.asarray(tris, np.uint32).reshape(-1, 3)
         assert tris.size == 0 or int(tris.max()) < len(pos)
         g = np.zeros((), GEOMETRY_DTYPE)
-        g["base_color"] = (*mat.color, 1.0)
+        g["base_color"] = (*mat.color, mat.alpha)
         g["base_color_texture_index"] = mat.texture_offset
         g["metallic_factor"] = mat.metalic_factor
         g["roughness"] = mat.roughness_factor
@@ -100,6 +108,7 @@ class MeshBuilder:
         self.i.append(tris.reshape(-1))
         self.g.append(g)
         self.c.append(len(tris))
+        self.cut.append(mat.alpha_cutoff)
         self.names.append(name)
         self.nv += len(pos)
         self.ni += tris.size
@@ -111,6 +120,7 @@ class MeshBuilder:
             np.array(self.g, GEOMETRY_DTYPE),
             np.array(self.c, np.uint32),
             list(self.names),
+            alpha_cutoffs=np.array(self.cut, np.float32),
         )
 
 
@@ -160,7 +170,10 @@ def write_glb(path, mesh: Mesh) -> None:
         }
         if int(g["base_color_texture_index"]) > -1:
             pbr["baseColorTexture"] = {"index": int(g["base_color_texture_index"])}
-        materials.append({"name": f"mat{gi}", "pbrMetallicRoughness": pbr, "emissiveFactor": [float(x) for x in g["emission"][:3]]})
+        mtl = {"name": f"mat{gi}", "pbrMetallicRoughness": pbr, "emissiveFactor": [float(x) for x in g["emission"][:3]]}
+        if float(mesh.alpha_cutoffs[gi]) > 0.0:  # masked; opaque is glTF's default and stays implicit
+            mtl["alphaMode"], mtl["alphaCutoff"] = "MASK", float(mesh.alpha_cutoffs[gi])
+        materials.append(mtl)
         meshes.append({"name": mesh.names[gi] if gi < len(mesh.names) else f"g{gi}",
                        "primitives": [{"attributes": {"POSITION": acc[0], "NORMAL": acc[1], "TEXCOORD_0": acc[2]}, "indices": ia, "material": gi}]})
         nodes.append({"mesh": gi})
@@ -294,7 +307,10 @@ class GltfMeshLoader:
                         em = np.array(gmtl.get("emissiveFactor", [0, 0, 0]), np.float64)
                         em = em * gmtl.get("extensions", {}).get("KHR_materials_emissive_strength", {}).get("emissiveStrength", 1.0)
                         tex = pbr.get("baseColorTexture", {}).get("index", -1)
-                        mat = Material(tuple(bc[:3]), pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), tuple(em), tex)
+                        # alphaMode MASK: alphaCutoff (default 0.5); OPAQUE and BLEND (not supported: drawn opaque) -> 0
+                        cut = float(gmtl.get("alphaCutoff", 0.5)) if gmtl.get("alphaMode", "OPAQUE") == "MASK" else 0.0
+                        mat = Material(tuple(bc[:3]), pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), tuple(em), tex, cut,
+                                       float(bc[3]) if len(bc) > 3 else 1.0)
                     mb.add(f"{gm.get('name', 'mesh')}.{pi}", pos, nrm, uv, tris, mat, normalize=not keep)
             for c in node.get("children", []):
                 visit(c, m)
@@ -317,6 +333,13 @@ class GltfMeshLoader:
 
             mesh.textures.append(np.ascontiguousarray(np.array(Image.open(io.BytesIO(raw)).convert("RGBA"), np.uint8)))
         return mesh
+
+
+def load(path) -> Mesh:
+    """A scene file -> `Mesh` by its extension (GltfMeshLoader.extensions: binary glTF)."""
+    if Path(path).suffix.lower().lstrip(".") in GltfMeshLoader.extensions:
+        return GltfMeshLoader.load(path)
+    raise ValueError(f"{path}: unsupported scene format (expected one of {GltfMeshLoader.extensions})")
 
 
 # ----------------------------------------------------------------------------------------------- EXR (scanline, no compression)

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -144,6 +145,11 @@ struct rt3_ctx {
     std::vector<rt3_geometry_info> h_geoms;
     std::vector<uint32_t> h_prim_counts;
     int64_t max_tex_index = -1;
+    // alpha masks: cutoff per uploaded geometry (empty = all 0, opaque); the tables of the last rt3_accel_build:
+    // d_geom_mask per uploaded geometry {cutoff bits, slot}, d_alpha per masked geometry {texture index, base_color[3] bits}
+    std::vector<float> h_cutoffs;
+    DevBuf<uint2> d_geom_mask, d_alpha;
+    bool accel_masked = false;  // the structure holds masked triangles: traversal launches run the MASK kernels
     // resources.  A Resource* / PixelList* holds until the next push_back; the device memory they own never moves
     std::vector<Resource> resources;
     std::vector<PixelList> pixlists;
@@ -473,12 +479,25 @@ int reserve_counters(rt3_ctx* c, uint32_t n, uint32_t* first) {
     HIPC(c, hipMemsetAsync(c->d_counters.get() + *first, 0, (size_t)n * 4, c->stream));
     return RT3_OK;
 }
+// the alpha-mask tables of a traversal launch over the current structure: empty (table null) without masked triangles.  The texture atlas
+// must be synchronised (sync_textures) first.
+AlphaDev alpha_dev(const rt3_ctx* c) {
+    AlphaDev a = {};
+    if (!c->accel_masked) return a;
+    a.table = c->d_alpha.get();
+    a.tri_uv = c->shade.uv.get();
+    a.tex_table = c->d_tex_table.get();
+    a.tex_pixels = c->d_tex_pixels.get();
+    a.n_tex = c->d_tex_pixels ? (uint32_t)c->h_tex.size() : 0u;
+    return a;
+}
 // a traversal launch over the context's queues (`stride` records), counting into its totals when RT3_OPT_COUNT_TRAVERSAL is on
 TraceLaunch ctx_trace(rt3_ctx* c) {
     TraceLaunch L;
     L.stride = c->cap;
     L.count = c->opt_count;
     L.totals = c->opt_count ? c->d_totals.get() : nullptr;
+    L.alpha = alpha_dev(c);
     return L;
 }
 // closest hits of the n primary rays in c->rays[0], into c->hits
@@ -936,12 +955,26 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     // (the device tables -- one entry per (instance, geometry) -- are made by rt3_accel_build, which knows the instances)
     c->h_geoms.assign(g, g + n);
     c->h_prim_counts.assign(prim_counts, prim_counts + n);
+    c->h_cutoffs.clear();  // every geometry opaque again
     c->n_geoms = n;
     c->max_tex_index = max_tex;
     c->n_prims = (uint32_t)total;
     invalidate_topology(c);
     return RT3_OK;
 }
+// alpha cutoffs of the geometries of the last rt3_scene_set_geometry; n = 0: all opaque
+int rt3_scene_set_alpha_cutoffs(rt3_ctx* c, const float* cutoffs, uint32_t n) {
+    if (!c || (!cutoffs && n)) return fail(c, RT3_E_INVALID, "alpha cutoffs NULL");
+    if (n != 0 && n != c->n_geoms)
+        return fail(c, RT3_E_INVALID, "alpha cutoffs: n must be 0 or the geometry count of rt3_scene_set_geometry (" + std::to_string(c->n_geoms) + ")");
+    for (uint32_t i = 0; i < n; i++)
+        if (!(cutoffs[i] >= 0.0f && cutoffs[i] <= 1.0f)) return fail(c, RT3_E_INVALID, "alpha cutoff " + std::to_string(i) + " is not in [0, 1]");
+    c->h_cutoffs.clear();
+    if (std::any_of(cutoffs, cutoffs + n, [](float v) { return v > 0.0f; })) c->h_cutoffs.assign(cutoffs, cutoffs + n);  // (kept only when some geometry is masked)
+    invalidate_topology(c);  // the triangle records carry the masks: a new build, not a refit
+    return RT3_OK;
+}
+static bool any_cutoff(const rt3_ctx* c) { return !c->h_cutoffs.empty(); }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
 // arithmetic, in double, in the same order): radiance stored as RGB9E5 (packing.slang:99-162), marginal CDF over rows, one alias
 // table per row with 16-bit keep-thresholds, pdf_uv = the density the quantised tables really realise.
@@ -1234,7 +1267,8 @@ static int ensure_lights(rt3_ctx* c) {
         for (uint32_t k = 0; k < inst[i].geometry_count; k++) {
             const uint32_t g = inst[i].geometry_first + k;
             const float* em = c->h_geoms[g].emission;
-            const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && c->h_prim_counts[g] > 0;
+            const bool masked = any_cutoff(c) && c->h_cutoffs[g] > 0.0f;  // left out: its points may be cut away
+            const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && c->h_prim_counts[g] > 0 && !masked;
             geom_base.push_back(emissive ? (uint32_t)n : kMiss);
             if (emissive) {
                 eg_geom.push_back((uint32_t)(geom_base.size() - 1));
@@ -1323,7 +1357,7 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
     hipError_t e = make_mesh_tables(c, m, &t);
     if (e == hipSuccess)
         e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
-                       c->opt_sah_top, c->build_arena, res);
+                       c->opt_sah_top, c->build_arena, res, c->accel_masked ? c->d_geom_mask.get() : nullptr);
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1610,6 +1644,35 @@ static int tl_records_and_top(rt3_ctx* c) {
 }
 
 // ---- acceleration structure
+// The alpha-mask tables of a build: per uploaded geometry the triangle records' last two words {cutoff bits, slot} and
+// per masked geometry (slot) {texture index, base_color[3] bits}.  c->accel_masked: some placed geometry with triangles is masked.
+static int make_alpha_tables(rt3_ctx* c) {
+    c->accel_masked = false;
+    if (!any_cutoff(c)) return RT3_OK;
+    if (c->opt_node_width != 4 || c->opt_node_quant != 1)
+        return fail(c, RT3_E_UNSUPPORTED, "alpha-masked geometry needs the default node layout (RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1)");
+    std::vector<uint2> mask(c->n_geoms, make_uint2(0u, 0u)), table;
+    for (uint32_t g = 0; g < c->n_geoms; g++) {
+        if (!(c->h_cutoffs[g] > 0.0f)) continue;
+        uint32_t cb, ab;
+        memcpy(&cb, &c->h_cutoffs[g], 4);
+        memcpy(&ab, &c->h_geoms[g].base_color[3], 4);
+        mask[g] = make_uint2(cb, (uint32_t)table.size());
+        table.push_back(make_uint2((uint32_t)c->h_geoms[g].base_color_texture_index, ab));
+    }
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
+    for (size_t i = 0; i < n_inst && !c->accel_masked; i++)
+        for (uint32_t k = 0; k < inst[i].geometry_count; k++) {
+            const uint32_t g = inst[i].geometry_first + k;
+            if (mask[g].x != 0u && c->h_prim_counts[g] > 0) c->accel_masked = true;
+        }
+    if (int r = dev_alloc(c, c->d_geom_mask, mask.size())) return r;
+    if (int r = dev_alloc(c, c->d_alpha, table.size())) return r;
+    HIPC(c, hipMemcpy(c->d_geom_mask.get(), mask.data(), mask.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->d_alpha.get(), table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    return RT3_OK;
+}
 // the end of a successful build or refit: the shading records, then the structure goes live
 static int accel_finish(rt3_ctx* c, uint32_t* out_handle) {
     if (int r = make_shade_records(c)) return r;
@@ -1637,13 +1700,14 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     c->accel_stale = false;
     c->refit_planned = false;
     if (int r = flatten_world(c)) return r;
+    if (int r = make_alpha_tables(c)) return r;
     if (c->opt_instance_mode == 1) {
         if (int r = build_two_level(c)) return r;
     } else {
         free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
         hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
                                   c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena,
-                                  &c->bvh);
+                                  &c->bvh, c->accel_masked ? c->d_geom_mask.get() : nullptr);
         if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
             free_accel(c);  // (what the failed build allocated)
@@ -1703,6 +1767,7 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     if (!c->accel_built) return fail(c, RT3_E_STATE, "accel_import: build the scene's own structure first (rt3_accel_build makes the shading records)");
     if (c->bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (c->bvh.layout != kLayoutWide64Q) return fail(c, RT3_E_UNSUPPORTED, "accel_import: default node layout only");
+    if (any_cutoff(c)) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for a scene with alpha-masked geometry (rt3_scene_set_alpha_cutoffs)");
     if (nodes_bytes == 0 || nodes_bytes % 64 || tris_bytes % 48 || nodes_bytes / 64 > 0x3FFFFFFFull) return fail(c, RT3_E_INVALID, "accel_import: sizes must be multiples of 64 / 48 bytes");
     const uint32_t nn = (uint32_t)(nodes_bytes / 64), nt = (uint32_t)(tris_bytes / 48);
     const uint32_t* w = static_cast<const uint32_t*>(nodes);
@@ -2195,6 +2260,10 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
     L.rays = d_rays.get(); L.stride = n; L.n = n; L.work_counter = d_cur.get();
     L.hits = d_hits.get(); L.occluded = d_occ.get();  // the launch below writes one of the two
     L.count = count; L.cnt_nodes = d_cn.get(); L.cnt_tris = d_ct.get();
+    if (c->accel_masked) {
+        if (int r = sync_textures(c)) return r;
+        L.alpha = alpha_dev(c);
+    }
     auto launch = [&]() {
         (void)hipMemsetAsync(d_cur.get(), 0, 4, c->stream);  // ray-pool cursor
         if (any_hit) launch_shadow(c->stream, c->bvh, L);
@@ -2232,6 +2301,8 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     if ((op == 25 || op == 26) && !c->d_sky) return fail(c, RT3_E_STATE, "selftest: the sky ops need a sky (rt3_scene_set_sky)");
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
+    if (op == 27)
+        if (int r = sync_textures(c)) return r;
     DevBuf<uint32_t> d_in, d_out;
     HIPC(c, d_in.alloc_bytes((size_t)n * iw * 4));
     HIPC(c, d_out.alloc_bytes((size_t)n * ow * 4));

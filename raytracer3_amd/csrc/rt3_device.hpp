@@ -454,6 +454,44 @@ RT3_DEV V3 texture_sample(const SceneDev& sc, uint32_t index, float u, float v) 
     }
     return v3(o[0], o[1], o[2]);
 }
+// Alpha-masked geometry (glTF alphaMode MASK).  tex_alpha: the bilinear alpha of base-colour texture `index` at mip 0,
+// texture_sample's texel coordinates, weights and association on the alpha byte (linear: byte * (1 / 255), no sRGB decode); 1 without a
+// texture (index -1 or out of range)
+RT3_DEV float tex_alpha(const uint4* tex_table, const uint8_t* tex_pixels, uint32_t n_tex, int32_t index, float u, float v) {
+    if (index < 0 || (uint32_t)index >= n_tex) return 1.0f;
+    const uint4 t = tex_table[index];
+    const int W = (int)t.y, H = (int)t.z;
+    const uint8_t* px = tex_pixels + t.x;
+    float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
+    float xf = floorf(x), yf = floorf(y), fx = x - xf, fy = y - yf;
+    int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
+    x0 = wrap_index(x0, W);
+    x1 = wrap_index(x1, W);
+    y0 = wrap_index(y0, H);
+    y1 = wrap_index(y1, H);
+    const float a00 = (float)px[4 * ((size_t)y0 * W + x0) + 3] * (1.0f / 255.0f), a10 = (float)px[4 * ((size_t)y0 * W + x1) + 3] * (1.0f / 255.0f);
+    const float a01 = (float)px[4 * ((size_t)y1 * W + x0) + 3] * (1.0f / 255.0f), a11 = (float)px[4 * ((size_t)y1 * W + x1) + 3] * (1.0f / 255.0f);
+    const float top = a00 * (1.0f - fx) + a10 * fx, bot = a01 * (1.0f - fx) + a11 * fx;
+    return top * (1.0f - fy) + bot * fy;
+}
+// What the masked traversal kernels read besides the tree.  A masked triangle record carries {v2.z, prim, cutoff, slot} (unmasked: cutoff
+// 0.0f and slot 0): table[slot] = {base-colour texture index (int32), base_color[3] bits} of its geometry.
+struct AlphaDev {
+    const uint2* table;
+    const float2* tri_uv;  // SceneDev::tri_uv
+    const uint4* tex_table;
+    const uint8_t* tex_pixels;
+    uint32_t n_tex;
+};
+// does the intersection (prim, bu, bv) of a masked triangle count?  alpha = base_color[3] * tex_alpha at the uv hit_finish interpolates
+RT3_DEV bool alpha_counts(const AlphaDev& a, uint32_t slot, float cutoff, uint32_t prim, float bu, float bv) {
+    const uint2 e = a.table[slot];
+    const float2 t0 = a.tri_uv[3 * (size_t)prim], t1 = a.tri_uv[3 * (size_t)prim + 1], t2 = a.tri_uv[3 * (size_t)prim + 2];
+    const float b0 = 1.0f - bu - bv;
+    const float uu = t0.x * b0 + t1.x * bu + t2.x * bv, vv = t0.y * b0 + t1.y * bu + t2.y * bv;
+    const float alpha = __uint_as_float(e.y) * tex_alpha(a.tex_table, a.tex_pixels, a.n_tex, (int32_t)e.x, uu, vv);
+    return alpha >= cutoff;
+}
 // packing.slang:64-86: the reference's octahedral map.  Vertex normals live in the shading records through it, 16 bits per
 // coordinate (the oracle's tri_shade defines the same representation: a normal IS octa_decode16(octa_encode16(n)) on both sides).
 RT3_DEV V3 octa_decode(float fx, float fy) {  // :77-86
@@ -673,7 +711,7 @@ struct Hit {
     float t, u, v;
     uint32_t prim;
 };
-// Triangle records: 3 x float4 {v0.xyz,v1.x} {v1.yz,v2.xy} {v2.z,prim,-,-}; the watertight two-sided test is tri_test_nb
+// Triangle records: 3 x float4 {v0.xyz,v1.x} {v1.yz,v2.xy} {v2.z,prim,cutoff,slot} (alpha mask, 0 0 = opaque: AlphaDev); the watertight two-sided test is tri_test_nb
 // (rt3_kernels.hip).  Order-independent acceptance: t > tmin && (t < best.t || (t == best.t && prim < best.prim)).
 // Dot products use explicit fused multiply-adds in a fixed order (the oracle mirrors them with fmaf).
 RT3_DEV float dot_fma(V3 a, V3 b) { return __builtin_fmaf(a.x, b.x, __builtin_fmaf(a.y, b.y, a.z * b.z)); }

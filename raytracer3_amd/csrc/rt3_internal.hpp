@@ -190,14 +190,16 @@ struct TraceLaunch {
     bool count = false;                   // counting: per-ray node visits / triangle tests (either may be null) and the totals (TotalsWord)
     uint32_t *cnt_nodes = nullptr, *cnt_tris = nullptr;
     unsigned long long* totals = nullptr;
+    AlphaDev alpha = {};                  // alpha.table set: the structure holds masked triangles, the launch runs the MASK instance
 };
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
 void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
-// On failure *out may hold some of its arrays: they go with it.
+// On failure *out may hold some of its arrays: they go with it.  geom_mask: the alpha-mask words of the triangle records per uploaded geometry
+// (DESIGN.md section 4e), or null (every record {v2.z, prim, 0, 0}).
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, BuildArena& arena, LbvhResult* out);
+                      uint32_t sah_top, BuildArena& arena, LbvhResult* out, const uint2* geom_mask = nullptr);
 // Binned-SAH top (rt3_sah_top.hip): re-links, in place, the nodes of the Karras tree (left / right / rcnt / pint / pleaf, boxes in nbox)
 // above its subtrees of at most T triangles, and writes the boxes of the re-linked nodes.  *relinked = false (and nothing written) when
 // there are fewer than three such subtrees.  Its scratch comes out of `arena`, after what the caller has taken.

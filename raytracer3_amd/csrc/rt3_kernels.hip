@@ -59,7 +59,10 @@ __device__ __forceinline__ void pin(float4& q) { asm volatile("" : "+v"(q.x), "+
 // the same number for it up to sign and no ray passes between them.  No early-outs: the three loads of a triangle are issued
 // together instead of being sunk behind branches.  Record: {v0.xyz, v1.x} {v1.yz, v2.xy} {v2.z, prim, -, -}.
 __device__ __forceinline__ V3 cross_exact(V3 a, V3 b) { return V3{(a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)}; }
-__device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 o, V3 d, float inv_dd, float tmin, Hit& best) {
+// MASK: a candidate that would be accepted is, if its record is masked (q2.z = cutoff > 0, q2.w = slot), kept only when its alpha passes
+// (alpha_counts): a masked triangle that fails is not there for this ray.
+template <bool MASK = false>
+__device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 o, V3 d, float inv_dd, float tmin, Hit& best, const AlphaDev& alpha = AlphaDev{}) {
     const V3 A = v3(q0.x, q0.y, q0.z) - o, B = v3(q0.w, q1.x, q1.y) - o, C = v3(q1.z, q1.w, q2.x) - o;
     const float U = dot_fma(d, cross_exact(B, C)), V = dot_fma(d, cross_exact(C, A)), W = dot_fma(d, cross_exact(A, B));
     const float det = U + (V + W);  // the association of T below: equal vertex distances give t exactly
@@ -72,7 +75,8 @@ __device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 
     // and edges of separate meshes that merely coincide, which no watertight test covers
     constexpr float kEdgeEps = 9.5367431640625e-07f;
     const bool inside = (w >= -kEdgeEps) & (u >= -kEdgeEps) & (v >= -kEdgeEps);
-    const bool ok = (det != 0.0f) & inside & (t > tmin) & ((t < best.t) | ((t == best.t) & (prim < best.prim)));
+    bool ok = (det != 0.0f) & inside & (t > tmin) & ((t < best.t) | ((t == best.t) & (prim < best.prim)));
+    if (MASK && ok && q2.z != 0.0f) ok = alpha_counts(alpha, __float_as_uint(q2.w), q2.z, prim, u, v);
     best.t = ok ? t : best.t;
     best.u = ok ? u : best.u;
     best.v = ok ? v : best.v;
@@ -149,11 +153,15 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // that tree; its triangles are transformed to world space with flattening's own expression and tested against the world ray.  Once the
 // bottom walk has popped down to the mark the lane goes back to the world ray and the top tree's entries.
 // RANGE (any hit only): ray i ends at any_tmax[i] instead of kBackgroundDepth -- the emitter shadow queue of RT3_F_NEE_EMISSIVE.
-template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, typename Finish>
+// MASK: the structure holds alpha-masked triangles: a candidate that would be accepted (inside, t in range, better than
+// best) is alpha-tested inline in its leaf step -- the extra gathers (table, 3 uvs, texture entry, 4 texels) stay out of every other step.
+// best is only updated, and an any-hit lane only finishes, on an intersection that counts.
+template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
-                                             const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr) {
+                                             const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr,
+                                             const AlphaDev& alpha = AlphaDev{}) {
     // any_payload: the any-hit rays come from k_shade's shadow queue, where every ray has the range (kRayTMin, kBackgroundDepth):
     // the two .w slots of its record carry payload (two contribution channels) instead of tmin / tmax -- 16 bytes less per ray.
     // ext_payload: likewise for the extension rays of the path tracer's own queue (.w = the path's pdf and id, read by k_shade)
@@ -360,10 +368,10 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                     c = transform_point(fm, c);
                 }
                 const uint32_t gp = __float_as_uint(q2.y) + (tl_base & 0x7FFFFFFFu);
-                tri_test_nb(make_float4(a.x, a.y, a.z, b.x), make_float4(b.y, b.z, c.x, c.y), make_float4(c.z, __uint_as_float(gp), 0.0f, 0.0f), o, d,
-                            r.inv_dd, tmin, r.best);
+                tri_test_nb<MASK>(make_float4(a.x, a.y, a.z, b.x), make_float4(b.y, b.z, c.x, c.y),
+                                  make_float4(c.z, __uint_as_float(gp), MASK ? q2.z : 0.0f, MASK ? q2.w : 0.0f), o, d, r.inv_dd, tmin, r.best, alpha);
             } else {
-                tri_test_nb(q0, q1, q2, o, d, r.inv_dd, tmin, r.best);
+                tri_test_nb<MASK>(q0, q1, q2, o, d, r.inv_dd, tmin, r.best, alpha);
             }
             r.leaf_k++;
             if (WIDE) {  // the 128 B fetch holds a second triangle
@@ -551,15 +559,28 @@ struct TraceCounts {
     }
 };
 
+// the alpha-mask kernel argument: AlphaDev for the MASK instances; for the others an empty struct, placed in the padding after a 32-bit
+// argument, so that their argument layout -- and their machine code -- stays what it is without masks
+template <bool MASK>
+struct AlphaArg {
+    AlphaDev a;
+    __device__ __forceinline__ AlphaDev get() const { return a; }
+};
+template <>
+struct AlphaArg<false> {
+    __device__ __forceinline__ AlphaDev get() const { return AlphaDev{}; }
+};
+
 // closest-hit over a ray queue.  rays: two float4 streams of `stride` records, {o.xyz, tmin} then {d.xyz, tmax};
 // hits: one float4 {t, u, v, prim} per ray.  16-byte records are the widest coalesced access (1 KiB per wave instruction).
-template <bool COUNT, int LAYOUT>
+template <bool COUNT, int LAYOUT, bool MASK = false>
 __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
                                                          const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
                                                          float* __restrict__ hits, uint32_t* __restrict__ cnt_nodes,
                                                          uint32_t* __restrict__ cnt_tris, unsigned long long* __restrict__ totals,
-                                                         uint32_t* __restrict__ work_counter, int payload, unsigned long long* __restrict__ lds_total) {
+                                                         uint32_t* __restrict__ work_counter, int payload, AlphaArg<MASK> alpha,
+                                                         unsigned long long* __restrict__ lds_total) {
     __shared__ uint32_t stack[kLdsStack * kExtendBlock];
     __shared__ float4 s_top[4 * kTopNodes];
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
@@ -571,17 +592,18 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
         reinterpret_cast<float4*>(hits)[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
         counts.ray(i, cn, ct, cl);
     };
-    trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel>(nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top);
+    trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, false, MASK>(
+        nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top, nullptr, nullptr, alpha.get());
     counts.add_totals(totals, lds_total);
 }
 
 // any-hit over the shadow queue; unoccluded rays add their contribution to the path's radiance slot.
 // If `occluded_out` != nullptr the kernel only reports occlusion (rt3_trace_rays).
 // RANGE: the emitter shadow queue, whose rays end short of their sampled emitter point (range (kRayTMin, tmax[i]))
-template <bool COUNT, int LAYOUT, bool RANGE = false>
+template <bool COUNT, int LAYOUT, bool RANGE = false, bool MASK = false>
 __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
-                                                         const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
+                                                         const uint32_t* __restrict__ count_ptr, uint32_t count_imm, AlphaArg<MASK> alpha,
                                                          const float* __restrict__ contrib, float* __restrict__ lacc,
                                                          uint32_t* __restrict__ occluded_out, uint32_t* __restrict__ cnt_nodes,
                                                          uint32_t* __restrict__ cnt_tris, unsigned long long* __restrict__ totals,
@@ -592,7 +614,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     const bool use_top = load_top(s_top, top, n_top);  // (the LDS array itself is passed on, never a selected pointer: a select would turn its reads into flat loads)
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     TraceCounts<COUNT> counts{cnt_nodes, cnt_tris};
-    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE>(
+    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE, MASK>(
         nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
             if (occluded_out) {
@@ -606,7 +628,8 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
             }
             counts.ray(i, cn, ct, cl);
         },
-        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr, tmax);
+        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr, tmax,
+        alpha.get());
     counts.add_totals(totals, lds_total);
 }
 
@@ -1290,14 +1313,17 @@ __global__ void k_selftest(int op, const SceneDev sc, const uint32_t* __restrict
             out[4 * i] = U(rad.x); out[4 * i + 1] = U(rad.y); out[4 * i + 2] = U(rad.z); out[4 * i + 3] = U(pdf);
             break;
         }
+        case 27:  // alpha mask: {texture index (int32), u, v} -> tex_alpha, the traversal's function
+            out[i] = U(tex_alpha(sc.tex_table, sc.tex_pixels, sc.n_tex, (int32_t)in[3 * i], F(in[3 * i + 1]), F(in[3 * i + 2])));
+            break;
         default: break;
     }
 }
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
-    static const uint32_t w[27][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
+    static const uint32_t w[28][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
-                                      {2, 9}, {2, 4}};
-    if (op < 0 || op > 26) return false;
+                                      {2, 9}, {2, 4}, {3, 1}};
+    if (op < 0 || op > 27) return false;
     *in_w = w[op][0];
     *out_w = w[op][1];
     return true;
@@ -1317,38 +1343,49 @@ static inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks)
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride) {
     hipLaunchKernelGGL(k_raygen, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, g, pixels, npix, rays, stride);
 }
-// The k_extend / k_shadow instance of (count, layout): `launch` is called with std::integral_constant<bool, COUNT> and
-// std::integral_constant<int, LAYOUT>.  A layout that is none of the named ones runs as kLayoutBinary64.
+// The k_extend / k_shadow instance of (count, layout, mask): `launch` is called with std::integral_constant<bool, COUNT>,
+// std::integral_constant<int, LAYOUT> and std::integral_constant<bool, MASK>.  A layout that is none of the named ones runs as kLayoutBinary64.
+// MASK instances exist for the default layout and the two-level one only (rt3_accel_build refuses masks with the others).
 template <typename Launch>
-static void dispatch_traversal(bool count, int layout, Launch launch) {
+static void dispatch_traversal(bool count, int layout, bool masked, Launch launch) {
+    auto by_mask = [&](auto c, auto l) {
+        if (masked) launch(c, l, std::true_type{});
+        else launch(c, l, std::false_type{});
+    };
     auto by_layout = [&](auto c) {
-        if (layout == kLayoutTwoLevel) launch(c, std::integral_constant<int, kLayoutTwoLevel>{});
-        else if (layout == kLayoutWide48Q) launch(c, std::integral_constant<int, kLayoutWide48Q>{});
-        else if (layout == kLayoutWide64Q) launch(c, std::integral_constant<int, kLayoutWide64Q>{});
-        else if (layout == kLayoutWide128) launch(c, std::integral_constant<int, kLayoutWide128>{});
-        else launch(c, std::integral_constant<int, kLayoutBinary64>{});
+        if (layout == kLayoutTwoLevel) by_mask(c, std::integral_constant<int, kLayoutTwoLevel>{});
+        else if (layout == kLayoutWide48Q) launch(c, std::integral_constant<int, kLayoutWide48Q>{}, std::false_type{});
+        else if (layout == kLayoutWide64Q) by_mask(c, std::integral_constant<int, kLayoutWide64Q>{});
+        else if (layout == kLayoutWide128) launch(c, std::integral_constant<int, kLayoutWide128>{}, std::false_type{});
+        else launch(c, std::integral_constant<int, kLayoutBinary64>{}, std::false_type{});
     };
     if (count) by_layout(std::true_type{});
     else by_layout(std::false_type{});
+}
+template <bool MASK>
+static AlphaArg<MASK> alpha_arg(const TraceLaunch& L) {
+    if constexpr (MASK) return AlphaArg<true>{L.alpha};
+    else return AlphaArg<false>{};
 }
 void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
     const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
     unsigned long long* const tot = L.totals ? L.totals + kTotExtendNodes : nullptr;
     unsigned long long* const lds_tot = L.totals ? L.totals + kTotExtendLds : nullptr;
-    dispatch_traversal(L.count, bvh.layout, [&](auto c, auto l) {
-        hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(),
-                           bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.hits, L.cnt_nodes, L.cnt_tris, tot, L.work_counter, L.payload ? 1 : 0, lds_tot);
+    dispatch_traversal(L.count, bvh.layout, L.alpha.table != nullptr, [&](auto c, auto l, auto m) {
+        hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value, decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(),
+                           bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.hits, L.cnt_nodes, L.cnt_tris, tot, L.work_counter,
+                           L.payload ? 1 : 0, alpha_arg<decltype(m)::value>(L), lds_tot);
     });
 }
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
     const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
     unsigned long long* const tot = L.totals ? L.totals + kTotShadowNodes : nullptr;
     unsigned long long* const lds_tot = L.totals ? L.totals + kTotShadowLds : nullptr;
-    dispatch_traversal(L.count, bvh.layout, [&](auto c, auto l) {
+    dispatch_traversal(L.count, bvh.layout, L.alpha.table != nullptr, [&](auto c, auto l, auto m) {
         auto launch = [&](auto range) {
-            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, decltype(range)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(),
-                               bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.contrib, L.lacc, L.occluded, L.cnt_nodes,
-                               L.cnt_tris, tot, L.work_counter, lds_tot, L.tmax);
+            hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, decltype(range)::value, decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0,
+                               st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n,
+                               alpha_arg<decltype(m)::value>(L), L.contrib, L.lacc, L.occluded, L.cnt_nodes, L.cnt_tris, tot, L.work_counter, lds_tot, L.tmax);
         };
         if (L.tmax) launch(std::true_type{});
         else launch(std::false_type{});

@@ -152,9 +152,11 @@ __global__ void k_morton(const float* bmin, const float* bmax, const uint32_t* b
     }
 }
 
+// geom_mask (may be null: no masks): per uploaded geometry (FlatGeomDev::geom) the record's last two words {cutoff bits, alpha slot}, {0, 0} =
+// opaque
 __global__ void k_leaves(const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                          const uint32_t* first_prim, const uint32_t* sorted_prim, const float* bmin, const float* bmax,
-                         const uint32_t* bounds, uint32_t n, float4* tris, float* lmin, float* lmax) {
+                         const uint32_t* bounds, uint32_t n, float4* tris, float* lmin, float* lmax, const uint2* geom_mask) {
     const float pad = leaf_pad(bounds);
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         uint32_t p = sorted_prim[k];
@@ -164,7 +166,8 @@ __global__ void k_leaves(const float* verts, const uint32_t* indices, const Flat
         // for the watertight edge functions of the triangle test
         tris[3 * (size_t)k + 0] = make_float4(a.x, a.y, a.z, b.x);
         tris[3 * (size_t)k + 1] = make_float4(b.y, b.z, c.x, c.y);
-        tris[3 * (size_t)k + 2] = make_float4(c.z, __uint_as_float(p), 0.0f, 0.0f);
+        const uint2 mk = geom_mask ? geom_mask[geoms[prim_geom[p]].geom] : make_uint2(0u, 0u);
+        tris[3 * (size_t)k + 2] = make_float4(c.z, __uint_as_float(p), __uint_as_float(mk.x), __uint_as_float(mk.y));
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             lmin[3 * (size_t)k + j] = bmin[3 * (size_t)p + j] - pad;
@@ -729,7 +732,7 @@ __global__ void k_single(const float* lmin, const float* lmax, int wide, int qua
 
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, BuildArena& arena, LbvhResult* out) {
+                      uint32_t sah_top, BuildArena& arena, LbvhResult* out, const uint2* geom_mask) {
     *out = LbvhResult{};
     out->n_tris = n;
     const int wide = node_width == 4, quant = wide ? (node_quant > 2 ? 2 : (int)node_quant) : 0, collapse = wide ? (collapse_mode > 2 ? 2 : (int)collapse_mode) : 0;
@@ -817,7 +820,7 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     LB_CHECK(arena.take(&temp, temp_bytes ? temp_bytes : 16));
     LB_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
     hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, vals_out, bmin, bmax, bounds, n,
-                       tris_dp ? tris_dp : (tris_morton ? tris_morton : out->tris.get()), lmin, lmax);
+                       tris_dp ? tris_dp : (tris_morton ? tris_morton : out->tris.get()), lmin, lmax, geom_mask);
     if (n == 1) {
         LB_CHECK(out->nodes.alloc_bytes(out->node_bytes));
         hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, lmin, lmax, wide, quant, out->nodes.get());

@@ -80,7 +80,7 @@ __global__ void k_refit_bounds(const float* verts, const uint32_t* indices, cons
     }
 }
 
-// records [first, first + n): each keeps its slot and its primitive (word 9); tbox gets its padded box (6 floats per record)
+// records [first, first + n): each keeps its slot, its primitive (word 9) and its alpha-mask words (10, 11); tbox gets its padded box (6 floats per record)
 __global__ void k_refit_tris(const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom, const uint32_t* first_prim,
                              const uint32_t* bounds, uint32_t first, uint32_t n, float4* tris, float* tbox) {
     const float pad = leaf_pad(bounds);
@@ -91,7 +91,7 @@ __global__ void k_refit_tris(const float* verts, const uint32_t* indices, const 
         fetch_triangle(verts, indices, geoms, prim_geom, first_prim, p, a, b, c);
         tris[3 * k + 0] = make_float4(a.x, a.y, a.z, b.x);
         tris[3 * k + 1] = make_float4(b.y, b.z, c.x, c.y);
-        tris[3 * k + 2] = make_float4(c.z, __uint_as_float(p), 0.0f, 0.0f);
+        tris[3 * k + 2] = make_float4(c.z, __uint_as_float(p), tris[3 * k + 2].z, tris[3 * k + 2].w);  // (the alpha-mask words stay)
         tbox[6 * k + 0] = fmin_sel(a.x, fmin_sel(b.x, c.x)) - pad;
         tbox[6 * k + 1] = fmin_sel(a.y, fmin_sel(b.y, c.y)) - pad;
         tbox[6 * k + 2] = fmin_sel(a.z, fmin_sel(b.z, c.z)) - pad;

@@ -735,6 +735,8 @@ struct Material {  // assets/mod.rs:52-59 (+ emission, datatypes.slang:17)
     float metalic_factor = 0.0f, roughness_factor = 1.0f;
     float emission[3] = {0.0f, 0.0f, 0.0f};
     int32_t texture_offset = -1;
+    float alpha_cutoff = 0.0f;  // glTF alphaMode MASK: alphaCutoff (0 = opaque)
+    float alpha = 1.0f;         // baseColorFactor[3] -> rt3_geometry_info::base_color[3]
 };
 struct Mesh {
     std::vector<float> vertices;                // n x 8: position, normal, uv (Vertex, assets/mod.rs:127-133)
@@ -743,6 +745,7 @@ struct Mesh {
     std::vector<uint32_t> prim_counts;
     std::vector<std::string> names;
     std::vector<Image> textures;
+    std::vector<float> alpha_cutoffs;           // one per geometry (rt3_scene_set_alpha_cutoffs), 0 = opaque
     size_t n_vertices() const { return vertices.size() / 8; }
     size_t n_triangles() const {
         size_t t = 0;
@@ -1001,13 +1004,19 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                             if (const Json* s = es->find("emissiveStrength")) strength = s->number(1.0);
                     for (int k = 0; k < 3; k++) mat.emission[k] = gmtl.has("emissiveFactor") ? (float)(gmtl.at("emissiveFactor").at((size_t)k).number(0.0) * strength) : 0.0f;
                     if (const Json* bt = pbr.find("baseColorTexture")) mat.texture_offset = (int32_t)bt->at("index").integer(-1);
+                    if (const Json* bc = pbr.find("baseColorFactor"))
+                        if (bc->kind == Json::Arr && bc->arr.size() > 3) mat.alpha = (float)bc->arr[3].number(1.0);
+                    // alphaMode MASK: alphaCutoff (default 0.5); OPAQUE and BLEND (not supported: drawn opaque) -> 0
+                    const Json* mode = gmtl.find("alphaMode");
+                    if (mode && mode->kind == Json::Str && mode->str == "MASK")
+                        mat.alpha_cutoff = gmtl.has("alphaCutoff") ? (float)gmtl.at("alphaCutoff").number(0.5) : 0.5f;
                 }
                 rt3_geometry_info g{};
                 for (int k = 0; k < 3; k++) {
                     g.base_color[k] = mat.color[k];
                     g.emission[k] = mat.emission[k];
                 }
-                g.base_color[3] = 1.0f;
+                g.base_color[3] = mat.alpha;
                 g.emission[3] = 0.0f;
                 g.base_color_texture_index = mat.texture_offset;
                 g.metallic_factor = mat.metalic_factor;
@@ -1021,6 +1030,7 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                 mesh_.indices.insert(mesh_.indices.end(), idx.begin(), idx.end());
                 mesh_.geometries.push_back(g);
                 mesh_.prim_counts.push_back((uint32_t)(idx.size() / 3));
+                mesh_.alpha_cutoffs.push_back(mat.alpha_cutoff);
                 mesh_.names.push_back((gm.has("name") ? gm.at("name").str : std::string("mesh")) + "." + std::to_string(this_pi));
             }
         }
@@ -1470,6 +1480,10 @@ inline uint32_t upload(rt3_ctx* ctx, const Mesh& m) {
     check(ctx, rt3_scene_set_vertices(ctx, m.vertices.data(), (uint32_t)m.n_vertices()), "rt3_scene_set_vertices");
     check(ctx, rt3_scene_set_indices(ctx, m.indices.data(), (uint32_t)m.indices.size()), "rt3_scene_set_indices");
     check(ctx, rt3_scene_set_geometry(ctx, m.geometries.data(), m.prim_counts.data(), (uint32_t)m.geometries.size()), "rt3_scene_set_geometry");
+    bool masked = false;
+    for (float c : m.alpha_cutoffs) masked = masked || c != 0.0f;
+    if (masked)  // alpha-masked geometry; an opaque scene makes no call
+        check(ctx, rt3_scene_set_alpha_cutoffs(ctx, m.alpha_cutoffs.data(), (uint32_t)m.alpha_cutoffs.size()), "rt3_scene_set_alpha_cutoffs");
     for (size_t i = 0; i < m.textures.size(); i++)
         check(ctx, rt3_scene_set_texture(ctx, (uint32_t)i, m.textures[i].rgba.data(), m.textures[i].w, m.textures[i].h), "rt3_scene_set_texture");
     uint32_t handle = 0;

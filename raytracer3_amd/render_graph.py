@@ -170,9 +170,17 @@ class Context:
         self.check(self.lib.rt3_scene_set_vertices(self.h, v.ctypes.data, len(v)))
         self.check(self.lib.rt3_scene_set_indices(self.h, i.ctypes.data, len(i)))
         self.check(self.lib.rt3_scene_set_geometry(self.h, g.ctypes.data, pc.ctypes.data, len(g)))
+        cut = getattr(mesh, "alpha_cutoffs", None)
+        if cut is not None and np.any(np.asarray(cut) != 0):  # alpha-masked geometry; opaque scenes make no call
+            self.set_alpha_cutoffs(cut)
         for i, t in enumerate(getattr(mesh, "textures", None) or []):  # base-colour textures, RGBA8 sRGB
             t = np.ascontiguousarray(t, np.uint8)
             self.check(self.lib.rt3_scene_set_texture(self.h, i, t.ctypes.data, t.shape[1], t.shape[0]))
+
+    def set_alpha_cutoffs(self, cutoffs):
+        """per-geometry alpha cutoffs (glTF alphaMode MASK; 0 = opaque, [] = all opaque); rt3_scene_set_alpha_cutoffs, next build_accel()"""
+        c = np.ascontiguousarray(cutoffs, np.float32).reshape(-1)
+        self.check(self.lib.rt3_scene_set_alpha_cutoffs(self.h, c.ctypes.data, len(c)))
 
     def set_instances(self, instances):
         """instances: [(geometry_first, geometry_count, 4x4 matrix as numpy, object -> world)] -- Instance + Transform of

@@ -337,6 +337,37 @@ def textured_cornell() -> Mesh:
     return mesh
 
 
+def cutout_cornell() -> Mesh:
+    """The Cornell box with alpha-masked cutout geometry (glTF alphaMode MASK): a tilted lattice panel (hard 0 / 255
+    alpha, cutoff 0.5) and overlapping leaf quads at different depths whose alpha is a smooth gradient (cutoffs 0.3, 0.5, 0.7, uv repeated),
+    one more quad masked by base_color[3] alone (no texture).  Opaque emitter and walls."""
+    mesh = cornell()
+    yy, xx = np.mgrid[0:64, 0:64]
+    bars = ((xx % 16) < 5) | ((yy % 16) < 5)  # lattice: bars opaque, cells cut away
+    lattice = np.stack([np.full(xx.shape, 150, np.uint8), np.full(xx.shape, 110, np.uint8), np.full(xx.shape, 60, np.uint8),
+                        np.where(bars, 255, 0).astype(np.uint8)], -1)
+    r = np.hypot((xx + 0.5) / 64.0 - 0.5, (yy + 0.5) / 64.0 - 0.5) * 2.0  # leaf: alpha falls off from the centre, a hard notch on one side
+    a = np.clip(255.0 * (1.0 - r), 0.0, 255.0)
+    a = np.where((xx > 44) & (np.abs(yy - 32) < 4), 0.0, a)
+    leaf = np.stack([(60 + xx).astype(np.uint8), (140 + yy).astype(np.uint8), np.full(xx.shape, 50, np.uint8), np.round(a).astype(np.uint8)], -1)
+    mb = MeshBuilder()
+    mb.add("lattice", *_grid([-0.8, 0.2, -0.2], [1.3, 0.0, 0.5], [0.2, 1.4, -0.3], 3, 3), Material((1.0, 1.0, 1.0), texture_offset=0, alpha_cutoff=0.5))
+    for k, (z, cut) in enumerate(((0.4, 0.3), (0.7, 0.5), (1.0, 0.7))):
+        p, n, uv, t = _grid([-0.5 + 0.25 * k, 0.3 + 0.2 * k, z], [0.8, 0.0, 0.1], [0.0, 0.8, 0.05], 2, 2)
+        mb.add(f"leaf{k}", p, n, uv * (1.0 + k), t, Material((1.0, 1.0, 1.0), texture_offset=1, alpha_cutoff=cut))
+    mb.add("veil", *_grid([0.2, 0.9, 0.3], [0.6, 0.0, 0.0], [0.0, 0.6, 0.2], 1, 1), Material((0.9, 0.6, 0.6), alpha_cutoff=0.5, alpha=0.6))
+    cut = mb.build()
+    n_geo, n_idx, n_vtx = len(mesh.geometries), len(mesh.indices), len(mesh.vertices)
+    g = cut.geometries.copy()
+    g["index_offset"] += n_idx
+    g["vertex_offset"] += n_vtx
+    return Mesh(np.ascontiguousarray(np.concatenate([mesh.vertices, cut.vertices]), np.float32),
+                np.ascontiguousarray(np.concatenate([mesh.indices, cut.indices]), np.uint32), np.concatenate([mesh.geometries, g]),
+                np.concatenate([mesh.prim_counts, cut.prim_counts]).astype(np.uint32), mesh.names + cut.names,
+                [np.ascontiguousarray(lattice), np.ascontiguousarray(leaf)],
+                np.concatenate([mesh.alpha_cutoffs, cut.alpha_cutoffs]).astype(np.float32))
+
+
 def sky(width: int = 2048, height: int = 1024, seed: int = SKY_SEED) -> np.ndarray:
     """Equirect RGB32F sky: horizon-to-zenith gradient, ground bounce, soft cloud noise, 0.5 degree sun (5e4)."""
     rng = np.random.default_rng(seed)

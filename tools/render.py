@@ -24,7 +24,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -51,6 +51,8 @@ def main():
         mesh, cam_kw = assets.GltfMeshLoader.load(args.glb), scenes.ATRIUM_CAMERA
     elif args.scene == "cornell":
         mesh, cam_kw = scenes.cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "cutout_cornell":  # alpha-masked cutout geometry
+        mesh, cam_kw = scenes.cutout_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "cornell_ref":
         mesh, cam_kw = scenes.cornell_ref(), scenes.CORNELL_REF_CAMERA
     else:
