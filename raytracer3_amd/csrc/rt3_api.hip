@@ -84,8 +84,7 @@ struct TwoLevelState {
     std::vector<TlInstance> inst;       // the instances of that build (a refit redoes their records and the top tree)
     uint32_t n_placed = 0, top_cap = 0; // of `inst`: those that place triangles (records, top-tree leaves); top-tree node capacity
     uint32_t n_meshes = 0, n_built = 0, n_top = 0;
-    DevBuf<char> scratch;               // top build inputs: boxes, degenerate triangles, identity table
-    size_t scratch_cap = 0;
+    DevBuf<char> scratch;               // grow-only: the top build's inputs (tl_records_and_top)
 };
 // A bottom tree's geometry tables: the identity table of its geometries as uploaded, first_prim and prim_geom (local primitive ids), in one
 // device allocation
@@ -139,7 +138,7 @@ struct rt3_ctx {
     bool tex_dirty = false;
     LbvhResult bvh;
     ShadeRecords shade;
-    BuildArena build_arena;
+    DevBuf<char> build_scratch;  // grow-only: lbvh_build's scratch, kept from build to build
     bool accel_built = false;
     std::vector<uint32_t> h_indices;  // host copies, only for range validation (rt3_scene_set_geometry, again in rt3_accel_build)
     std::vector<rt3_geometry_info> h_geoms;
@@ -158,8 +157,7 @@ struct rt3_ctx {
     // communicator of the frame-end gather (RCCL): one rank per context / GPU / process
     ncclComm_t comm = nullptr;
     uint32_t comm_rank = 0, comm_size = 0;
-    DevBuf<char> gather_buf;  // non-root: this rank's packed tiles; root: the receive buffer of all other ranks' tiles
-    size_t gather_buf_bytes = 0;
+    DevBuf<char> gather_buf;  // grow-only; non-root: this rank's packed tiles; root: the receive buffer of all other ranks' tiles
     // work queues (capacity in paths)
     size_t cap = 0, cap_pix = 0;
     DevBuf<float> rays[2], hits, T[2];
@@ -188,9 +186,7 @@ struct rt3_ctx {
     bool refit_planned = false;
     std::vector<RefitTree> refit_trees;
     std::vector<MeshTables> refit_tables;    // instance mode 1: each bottom tree's (tl_build_mesh's)
-    DevBuf<float> refit_box;                 // scratch: 6 floats per node, then 6 per triangle record
-    size_t refit_box_cap = 0;
-    DevBuf<uint32_t> refit_bounds;
+    DevBuf<char> refit_scratch;              // grow-only: refit_tree's bounds, node boxes and record boxes
     TwoLevelState tl;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
@@ -1339,14 +1335,11 @@ static hipError_t make_mesh_tables(rt3_ctx* c, const TlMesh& m, MeshTables* t) {
         fp[k] = tot;
         tot += c->h_prim_counts[m.first + k];
     }
-    // [identity table | first_prim | prim_geom], each at a 256-byte boundary
-    const size_t off_fp = (tbl.size() * sizeof(FlatGeomDev) + 255) & ~(size_t)255, off_pg = off_fp + ((fp.size() * 4 + 255) & ~(size_t)255);
-    hipError_t e = t->mem.alloc_bytes(off_pg + (size_t)m.n_tris * 4);
-    if (e != hipSuccess) return e;
-    t->geoms = reinterpret_cast<FlatGeomDev*>(t->mem.get());
-    t->first_prim = reinterpret_cast<uint32_t*>(t->mem.get() + off_fp);
-    t->prim_geom = reinterpret_cast<uint32_t*>(t->mem.get() + off_pg);
-    e = hipMemcpy(t->geoms, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice);
+    BufLayout plan;
+    plan.add(&t->geoms, tbl.size()).add(&t->first_prim, fp.size()).add(&t->prim_geom, m.n_tris);
+    RT3_TRY(t->mem.alloc_bytes(plan.bytes()));
+    RT3_TRY(plan.carve(t->mem));
+    hipError_t e = hipMemcpy(t->geoms, tbl.data(), tbl.size() * sizeof(FlatGeomDev), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t->first_prim, fp.data(), fp.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) launch_prim_geom(c->stream, t->first_prim, m.count, m.n_tris, t->prim_geom);
     return e;
@@ -1357,7 +1350,7 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
     hipError_t e = make_mesh_tables(c, m, &t);
     if (e == hipSuccess)
         e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
-                       c->opt_sah_top, c->build_arena, res, c->accel_masked ? c->d_geom_mask.get() : nullptr);
+                       c->opt_sah_top, c->build_scratch, res, c->accel_masked ? c->d_geom_mask.get() : nullptr);
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1588,28 +1581,25 @@ static int tl_records_and_top(rt3_ctx* c) {
     const size_t rec_bytes = rec.size() * 4;
     HIPC(c, hipMemcpyAsync(c->bvh.nodes.get() + 4 * (size_t)top_cap, rec.data(), rec_bytes, hipMemcpyHostToDevice, c->stream));
     if (rec_bytes > (64u << 10)) c->bulk_copies += 1;
-    // the top build's inputs: boxes, degenerate triangles, a one-entry identity table, first_prim / prim_geom = 0
-    const size_t off_boxes = 0, off_verts = (n_ne * 24 + 255) & ~(size_t)255, off_idx = off_verts + (((size_t)n_ne * 96 + 255) & ~(size_t)255),
-                 off_tbl = off_idx + (((size_t)n_ne * 12 + 255) & ~(size_t)255), off_pg = off_tbl + 256, need = off_pg + (size_t)n_ne * 4 + 256;
-    if (tl.scratch_cap < need) {
-        tl.scratch_cap = 0;
-        HIPC(c, tl.scratch.alloc_bytes(need));
-        tl.scratch_cap = need;
-    }
-    char* const scr = tl.scratch.get();
+    // the top build's inputs: boxes, degenerate triangles, a one-entry identity table, prim_geom = 0 and then first_prim = 0
+    float *boxes_d = nullptr, *verts = nullptr;
+    uint32_t *idx = nullptr, *zeros = nullptr;
+    FlatGeomDev* tbl = nullptr;
+    BufLayout plan;
+    plan.add(&boxes_d, boxes.size()).add(&verts, (size_t)n_ne * 24).add(&idx, (size_t)n_ne * 3).add(&tbl, 1).add(&zeros, (size_t)n_ne + 1);
+    HIPC(c, tl.scratch.grow_bytes(plan.bytes()));
+    HIPC(c, plan.carve(tl.scratch));
     FlatGeomDev tg;
     memset(&tg, 0, sizeof(tg));
     tg.m[0] = tg.m[4] = tg.m[8] = 1.0f;
     tg.identity = 1u;
-    HIPC(c, hipMemcpyAsync(scr + off_boxes, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(boxes_d, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (boxes.size() * 4 > (64u << 10)) c->bulk_copies += 1;
-    HIPC(c, hipMemcpyAsync(scr + off_tbl, &tg, sizeof(tg), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(scr + off_pg, 0, (size_t)n_ne * 4 + 4, c->stream));
-    tlas_box_tris(c->stream, (const float*)(scr + off_boxes), n_ne, (float*)(scr + off_verts), (uint32_t*)(scr + off_idx));
+    HIPC(c, hipMemcpyAsync(tbl, &tg, sizeof(tg), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(zeros, 0, ((size_t)n_ne + 1) * 4, c->stream));
+    tlas_box_tris(c->stream, boxes_d, n_ne, verts, idx);
     LbvhResult top;
-    hipError_t e = lbvh_build(c->stream, (const float*)(scr + off_verts), (const uint32_t*)(scr + off_idx), (const FlatGeomDev*)(scr + off_tbl),
-                              (const uint32_t*)(scr + off_pg), (const uint32_t*)(scr + off_pg + (size_t)n_ne * 4), n_ne, 1u, 4u, 1u, c->opt_collapse, 1u,
-                              c->build_arena, &top);
+    hipError_t e = lbvh_build(c->stream, verts, idx, tbl, zeros, zeros + n_ne, n_ne, 1u, 4u, 1u, c->opt_collapse, 1u, c->build_scratch, &top);
     if (e == hipSuccess && top.n_nodes > top_cap) e = hipErrorInvalidValue;  // cannot happen (see top_cap); never write past the top's region
     if (e == hipSuccess) {
         tlas_emit_top(c->stream, top.nodes.get(), top.n_nodes, top.tris.get(), top_cap, c->bvh.nodes.get());
@@ -1706,9 +1696,9 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     } else {
         free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
         hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                                  c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_arena,
+                                  c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_scratch,
                                   &c->bvh, c->accel_masked ? c->d_geom_mask.get() : nullptr);
-        if (c->build_arena.cap > ((size_t)1 << 30)) c->build_arena.release();  // a big scene's scratch is not worth keeping resident
+        if (c->build_scratch.capacity_bytes() > ((size_t)1 << 30)) c->build_scratch.reset();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
             free_accel(c);  // (what the failed build allocated)
             return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
@@ -1823,14 +1813,15 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
 }
 
 // ---- refit (rt3_refit.hip): the last build's trees, their boxes and triangle records recomputed from the current vertices
-static int refit_scratch(rt3_ctx* c, size_t n_nodes, size_t n_tris) {
-    const size_t need = 24 * (n_nodes + n_tris);
-    if (!c->refit_bounds) HIPC(c, c->refit_bounds.alloc_bytes(32));
-    if (need > c->refit_box_cap) {
-        c->refit_box_cap = 0;
-        HIPC(c, c->refit_box.alloc_bytes(need));
-        c->refit_box_cap = need;
-    }
+struct RefitScratch {
+    uint32_t* bounds;
+    float *nbox, *tbox;
+};
+static int refit_scratch(rt3_ctx* c, size_t n_nodes, size_t n_tris, RefitScratch* s) {
+    BufLayout plan;
+    plan.add(&s->bounds, 6).add(&s->nbox, 6 * n_nodes).add(&s->tbox, 6 * n_tris);
+    HIPC(c, c->refit_scratch.grow_bytes(plan.bytes()));
+    HIPC(c, plan.carve(c->refit_scratch));
     return RT3_OK;
 }
 static int refit_flat(rt3_ctx* c) {
@@ -1843,10 +1834,10 @@ static int refit_flat(rt3_ctx* c) {
         if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: plan: ") + hipGetErrorString(e));
         c->refit_planned = true;
     }
-    if (int r = refit_scratch(c, b.n_nodes, b.n_tris)) return r;
-    float* nbox = c->refit_box.get();
+    RefitScratch s;
+    if (int r = refit_scratch(c, b.n_nodes, b.n_tris, &s)) return r;
     hipError_t e = refit_tree(c->stream, c->refit_trees[0], c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                              c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)b.n_nodes);
+                              c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), s.bounds, s.nbox, s.tbox);
     if (e == hipSuccess) e = lbvh_make_top(c->stream, b.nodes.get(), b.n_nodes, b.top, &b.n_top);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: ") + hipGetErrorString(e));
     return RT3_OK;
@@ -1873,15 +1864,15 @@ static int refit_two_level(rt3_ctx* c) {
         }
         c->refit_planned = true;
     }
-    if (int r = refit_scratch(c, tl.n_alloc_nodes, c->bvh.n_tris)) return r;
-    float* nbox = c->refit_box.get();
+    RefitScratch s;
+    if (int r = refit_scratch(c, tl.n_alloc_nodes, c->bvh.n_tris, &s)) return r;
     std::vector<uint32_t> roots(16 * nm);
     hipError_t e = hipSuccess;
     for (size_t q = 0; e == hipSuccess && q < nm; q++) {
         const TlMesh& m = meshes[q];
         const MeshTables& t = c->refit_tables[q];
         e = refit_tree(c->stream, c->refit_trees[q], c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, m.tri_off, m.n_tris,
-                       c->bvh.nodes.get(), c->bvh.tris.get(), c->refit_bounds.get(), nbox, nbox + 6 * (size_t)tl.n_alloc_nodes);
+                       c->bvh.nodes.get(), c->bvh.tris.get(), s.bounds, s.nbox, s.tbox);
         if (e == hipSuccess) e = hipMemcpyAsync(&roots[16 * q], c->bvh.nodes.get() + 4 * (size_t)m.node_off, 64, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -2067,11 +2058,9 @@ static int get_gather_layout(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t root, 
     return RT3_OK;
 }
 static int ensure_gather_buf(rt3_ctx* c, size_t bytes) {
-    if (bytes <= c->gather_buf_bytes) return RT3_OK;
+    if (bytes <= c->gather_buf.capacity_bytes()) return RT3_OK;
     HIPC(c, hipStreamSynchronize(c->stream));  // an earlier gather may still be reading the old buffer: idle before it is dropped
-    c->gather_buf_bytes = 0;
     HIPC(c, c->gather_buf.alloc_bytes(bytes));
-    c->gather_buf_bytes = bytes;
     return RT3_OK;
 }
 

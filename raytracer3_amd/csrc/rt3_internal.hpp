@@ -101,6 +101,13 @@ void set_trace_blocks(uint32_t v);
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w);
 void launch_selftest(hipStream_t st, int op, const SceneDev& sc, const uint32_t* in, uint32_t n, uint32_t* out);
 
+// early return from host code that returns hipError_t
+#define RT3_TRY(x)                           \
+    do {                                     \
+        const hipError_t e_ = (x);           \
+        if (e_ != hipSuccess) return e_;     \
+    } while (0)
+
 // Owner of at most one hipMalloc allocation, freed when the owner goes.  The only place the host layer frees device memory.
 template <typename T>
 class DevBuf {
@@ -108,63 +115,79 @@ public:
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) {
+        o.p_ = nullptr;
+        o.cap_ = 0;
+    }
     DevBuf& operator=(DevBuf&& o) noexcept {
         if (this != &o) {
             reset();
             p_ = o.p_;
+            cap_ = o.cap_;
             o.p_ = nullptr;
+            o.cap_ = 0;
         }
         return *this;
     }
     ~DevBuf() { reset(); }
     T* get() const { return p_; }
+    size_t capacity_bytes() const { return cap_; }
     explicit operator bool() const { return p_ != nullptr; }
     void reset() {
         if (p_) (void)hipFree(p_);
         p_ = nullptr;
+        cap_ = 0;
     }
     // frees the old allocation BEFORE allocating, so the two never coexist (peak memory); empty on failure
     hipError_t alloc_bytes(size_t bytes) {
         reset();
         void* p = nullptr;
         const hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) p_ = static_cast<T*>(p);
+        if (e == hipSuccess) {
+            p_ = static_cast<T*>(p);
+            cap_ = bytes;
+        }
         return e;
     }
+    // grow-only: keeps the allocation when it holds `bytes` already, otherwise alloc_bytes
+    hipError_t grow_bytes(size_t bytes) { return bytes <= cap_ ? hipSuccess : alloc_bytes(bytes); }
 
 private:
     T* p_ = nullptr;
+    size_t cap_ = 0;
 };
 
-// LBVH build (rt3_lbvh.hip).  All pointers are device memory owned by the caller except the scratch the builder
-// allocates and frees itself.  Returns hipSuccess or the failing HIP error; *max_depth is read back to the host.
-// Scratch memory of the builder: ONE device allocation, handed out by a bump pointer and kept by the context from build to build
-// (a build made ~50 hipMalloc / hipFree pairs before, a third of its wall time on a 260 k-triangle scene).
-struct BuildArena {
-    DevBuf<char> base;
-    size_t cap = 0, used = 0;
-    hipError_t reserve(size_t bytes) {  // a fresh build: everything handed out before is void
-        used = 0;
-        if (bytes <= cap) return hipSuccess;
-        cap = 0;
-        hipError_t e = base.alloc_bytes(bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
+// Several arrays in one device allocation.  add() records a typed piece (where its pointer goes, how many elements) at the next 256-byte
+// boundary; bytes() is the size of all of them; carve() points every recorded pointer into a buffer of at least that size, and refuses a
+// smaller one.
+class BufLayout {
+public:
     template <typename T>
-    hipError_t take(T** p, size_t bytes) {
-        const size_t at = (used + 255) & ~(size_t)255;
-        if (at + bytes > cap) return hipErrorOutOfMemory;  // the builder's bound on its own scratch was wrong: fail, never overrun
-        *p = reinterpret_cast<T*>(base.get() + at);
-        used = at + bytes;
+    BufLayout& add(T** dst, size_t count) {
+        const size_t at = (end_ + 255) & ~(size_t)255;
+        pieces_.push_back({dst, at, &set_ptr<T>});
+        end_ = at + count * sizeof(T);
+        return *this;
+    }
+    size_t bytes() const { return end_; }
+    hipError_t carve(const DevBuf<char>& buf) const {
+        if (buf.capacity_bytes() < end_) return hipErrorOutOfMemory;
+        for (const Piece& p : pieces_) p.set(p.dst, buf.get() + p.at);
         return hipSuccess;
     }
-    void release() {
-        base.reset();
-        cap = used = 0;
-    }
+
+private:
+    struct Piece {
+        void* dst;
+        size_t at;
+        void (*set)(void* dst, char* p);
+    };
+    template <typename T>
+    static void set_ptr(void* dst, char* p) { *static_cast<T**>(dst) = reinterpret_cast<T*>(p); }
+    std::vector<Piece> pieces_;
+    size_t end_ = 0;
 };
+
 struct LbvhResult {
     DevBuf<float4> nodes;      // n_nodes x node_bytes: 64 B {box0, box1, ref0, ref1, pad} or 128 B 4 x {min, max, ref, pad}
     uint32_t node_bytes = 128;
@@ -195,16 +218,27 @@ struct TraceLaunch {
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
 void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
-// On failure *out may hold some of its arrays: they go with it.  geom_mask: the alpha-mask words of the triangle records per uploaded geometry
-// (DESIGN.md section 4e), or null (every record {v2.z, prim, 0, 0}).
+// LBVH build (rt3_lbvh.hip).  All pointers are device memory owned by the caller.  The build's scratch is carved from `scratch`, which grows
+// to what this configuration and size need and is kept for the next build.  On failure *out may hold some of its arrays: they go with it.
+// geom_mask: the alpha-mask words of the triangle records per uploaded geometry, or null (every record {v2.z, prim, 0, 0}).
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, BuildArena& arena, LbvhResult* out, const uint2* geom_mask = nullptr);
-// Binned-SAH top (rt3_sah_top.hip): re-links, in place, the nodes of the Karras tree (left / right / rcnt / pint / pleaf, boxes in nbox)
-// above its subtrees of at most T triangles, and writes the boxes of the re-linked nodes.  *relinked = false (and nothing written) when
-// there are fewer than three such subtrees.  Its scratch comes out of `arena`, after what the caller has taken.
-hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t n, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
-                              const float* lmin, const float* lmax, float* nbox, uint32_t T, BuildArena& arena, bool* relinked);
+                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask = nullptr);
+// Scratch of the binned-SAH top (rt3_sah_top.hip), part of the builder's: sah_top_plan adds it to `plan` for a tree over n triangles (at
+// most n clusters under n - 1 top nodes).  The segment and tile records are of types private to rt3_sah_top.hip.
+struct SahTopScratch {
+    uint32_t *top, *ncl, *pool_pos, *cl_pos, *pool, *cl_ref, *cl_cnt, *idx, *tmp, *counters, *tile_left, *tile_woff, *tile_roff;
+    float *cl_mn, *cl_mx;
+    char *seg_a, *seg_b, *seg_small, *huge, *tiles;
+    char* scan_tmp;
+    size_t scan_bytes;
+};
+hipError_t sah_top_plan(hipStream_t st, uint32_t n, BufLayout& plan, SahTopScratch* s);
+// Binned-SAH top: re-links, in place, the nodes of the Karras tree (left / right / rcnt / pint / pleaf, boxes in nbox) above its subtrees
+// of at most T triangles, and writes the boxes of the re-linked nodes.  *relinked = false (and nothing written) when there are fewer than
+// three such subtrees.
+hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
+                              const float* lmin, const float* lmax, float* nbox, uint32_t T, const SahTopScratch& s, bool* relinked);
 
 // shading records (SceneDev::tri_shade, tri_uv) of n flattened primitives: they depend on no tree and no matrix
 void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
@@ -242,8 +276,7 @@ struct LightTable {
     DevBuf<float4> rec;                       // 4 per emitter
     DevBuf<uint32_t> cdf, guide, prim, geom_base;
     DevBuf<float> area;
-    DevBuf<char> scratch;                     // power, quantised power and its scan, the scan's temporary storage
-    size_t scratch_cap = 0;
+    DevBuf<char> scratch;                     // grow-only: power, quantised power and its scan, the scan's temporary storage
     uint32_t n = 0, n_guide = 0, guide_shift = 0, total = 0;  // total: cdf[n - 1] (2^23, or 0 when no emitter has power)
     uint64_t stamp = 0;                       // the acceleration-structure stamp the table was built for (0 = none)
     LightsDev dev() const {

@@ -724,15 +724,52 @@ __global__ void k_single(const float* lmin, const float* lmax, int wide, int qua
     }
 }
 
-#define LB_CHECK(x)                      \
-    do {                                 \
-        hipError_t e_ = (x);             \
-        if (e_ != hipSuccess) return e_; \
-    } while (0)
+namespace {
+// The scratch of one build: the arrays its configuration uses (plan_scratch), carved from one allocation; the others stay null.
+struct LbvhScratch {
+    float *bmin, *bmax, *lmin, *lmax, *nbox;
+    uint32_t *bounds, *vals_in, *vals_out, *left, *right, *pint, *pleaf, *arrive, *rlo, *rcnt, *keep, *newidx, *levels, *live;
+    uint64_t *keys_in, *keys_out;
+    char *sort_tmp, *scan_tmp;  // hipcub's temporary storage
+    size_t sort_bytes, scan_bytes;
+    // cost-driven collapse: choices, costs, tree-order positions and boxes; Morton-ordered triangle records before they move into tree order
+    uint32_t *dk, *newpos;
+    float *dc, *lmin2, *lmax2;
+    float4* tris_dp;
+    // compact layout: Morton-ordered triangle records before they move into leaf order; child counts and their bases
+    float4* tris_morton;
+    uint32_t *n_int, *n_ltri, *cbase, *tbase;
+    SahTopScratch sah;
+    uint32_t *fr_a, *fr_b, *fr_n;  // four-wide collapse: the frontiers and their sizes
+    uint32_t* n_top;               // the top-of-tree copy's node count
+};
+hipError_t plan_scratch(hipStream_t st, uint32_t n, int quant, int collapse, bool sah_top, bool top_cache, BufLayout& plan, LbvhScratch* s) {
+    const size_t nn = n > 1 ? n - 1 : 1;
+    plan.add(&s->bmin, 3 * (size_t)n).add(&s->bmax, 3 * (size_t)n).add(&s->lmin, 3 * (size_t)n).add(&s->lmax, 3 * (size_t)n).add(&s->nbox, 6 * nn);
+    plan.add(&s->bounds, 12).add(&s->keys_in, n).add(&s->keys_out, n).add(&s->vals_in, n).add(&s->vals_out, n);
+    plan.add(&s->left, nn).add(&s->right, nn).add(&s->pint, nn).add(&s->pleaf, n).add(&s->arrive, nn).add(&s->rlo, nn).add(&s->rcnt, nn);
+    plan.add(&s->keep, nn).add(&s->newidx, nn).add(&s->levels, 1).add(&s->live, nn);
+    if (collapse == 2 && n > 1) {
+        plan.add(&s->dk, nn).add(&s->dc, 3 * nn).add(&s->newpos, n).add(&s->lmin2, 3 * (size_t)n).add(&s->lmax2, 3 * (size_t)n);
+        plan.add(&s->tris_dp, 3 * (size_t)n);
+    }
+    if (quant == 2 && n > 1)
+        plan.add(&s->tris_morton, 3 * (size_t)n).add(&s->n_int, nn).add(&s->n_ltri, nn).add(&s->cbase, nn).add(&s->tbase, nn);
+    RT3_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, s->sort_bytes, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)n, 0, 63, st));
+    plan.add(&s->sort_tmp, s->sort_bytes);
+    if (n == 1) return hipSuccess;
+    if (sah_top) RT3_TRY(sah_top_plan(st, n, plan, &s->sah));
+    if (collapse) plan.add(&s->fr_a, nn).add(&s->fr_b, nn).add(&s->fr_n, nn + 18);  // a level per node at most, plus one burst
+    RT3_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, s->scan_bytes, s->keep, s->newidx, (int)nn, st));
+    plan.add(&s->scan_tmp, s->scan_bytes);
+    if (top_cache) plan.add(&s->n_top, 1);
+    return hipSuccess;
+}
+}  // namespace
 
 hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                       const uint32_t* first_prim, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, BuildArena& arena, LbvhResult* out, const uint2* geom_mask) {
+                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask) {
     *out = LbvhResult{};
     out->n_tris = n;
     const int wide = node_width == 4, quant = wide ? (node_quant > 2 ? 2 : (int)node_quant) : 0, collapse = wide ? (collapse_mode > 2 ? 2 : (int)collapse_mode) : 0;
@@ -741,17 +778,15 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     out->layout = !wide ? kLayoutBinary64 : (quant == 2 ? kLayoutWide48Q : (quant ? kLayoutWide64Q : kLayoutWide128));
     if (n == 0) return hipSuccess;
     const uint32_t nn = n > 1 ? n - 1 : 1;
-    float *bmin = nullptr, *bmax = nullptr, *lmin = nullptr, *lmax = nullptr, *nbox = nullptr;
-    uint32_t *live = nullptr, *dk = nullptr, *newpos = nullptr;
-    float *dc = nullptr, *lmin2 = nullptr, *lmax2 = nullptr;
-    float4* tris_dp = nullptr;  // cost-driven collapse: Morton-ordered triangle records before they move into tree order
-    uint32_t *bounds = nullptr, *vals_in = nullptr, *vals_out = nullptr, *left = nullptr, *right = nullptr, *pint = nullptr, *pleaf = nullptr,
-             *arrive = nullptr, *levels = nullptr, *rlo = nullptr, *rcnt = nullptr, *keep = nullptr, *newidx = nullptr, *n_int = nullptr,
-             *n_ltri = nullptr, *cbase = nullptr, *tbase = nullptr;
-    float4* tris_morton = nullptr;  // compact layout: Morton-ordered triangle records before they move into leaf order
-    uint64_t *keys_in = nullptr, *keys_out = nullptr;
-    void *temp = nullptr, *temp2 = nullptr;
-    size_t temp_bytes = 0, temp2_bytes = 0;
+    LbvhScratch s = {};
+    {
+        BufLayout plan;
+        RT3_TRY(plan_scratch(st, n, quant, collapse, sah_top != 0, wide && quant == 1, plan, &s));
+        RT3_TRY(scratch.grow_bytes(plan.bytes()));
+        RT3_TRY(plan.carve(scratch));
+        if (getenv("RT3_TRACE_BUILD"))
+            fprintf(stderr, "rt3 build: %u triangles, scratch %zu bytes (radix sort %zu, scan %zu)\n", n, plan.bytes(), s.sort_bytes, s.scan_bytes);
+    }
     const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + 255) / 256);
     uint32_t init_bounds[12];
     uint32_t tail[2] = {0, 0};
@@ -761,91 +796,41 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
         init_bounds[6 + k] = 0xFFFFFFFFu;
         init_bounds[9 + k] = 0u;
     }
-    {
-        // everything below comes out of one block.  Per triangle, in the largest configuration (cost-driven collapse, compact 48 B
-        // layout, SAH top with T = 1, where every triangle is a cluster): 4 x 12 (boxes) + 24 (node boxes) + 24 (sort keys / values)
-        // + 10 x 4 (links, ranges, flags) + 92 (cost-driven collapse: costs, choices, tree-order copies of boxes and triangles) + 64
-        // (compact layout) + 12 (collapse frontiers) + 16 + 44 + 12 (SAH top: marks, clusters, segment queues) = 376 bytes, and < 1
-        // for the SAH top's tiled-segment records; 448 leaves room above that.  Plus the library scans' / sort's own scratch and the
-        // alignment of ~70 pieces
-        size_t sort_bytes = 0, scan_bytes = 0;
-        LB_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
-        LB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep, newidx, (int)nn, st));
-        LB_CHECK(arena.reserve((size_t)n * 448 + sort_bytes + 2 * scan_bytes + ((size_t)1 << 20)));
-    }
-    LB_CHECK(arena.take(&bmin, (size_t)n * 12));
-    LB_CHECK(arena.take(&bmax, (size_t)n * 12));
-    LB_CHECK(arena.take(&lmin, (size_t)n * 12));
-    LB_CHECK(arena.take(&lmax, (size_t)n * 12));
-    LB_CHECK(arena.take(&nbox, (size_t)nn * 24));
-    LB_CHECK(arena.take(&bounds, 64));
-    LB_CHECK(arena.take(&keys_in, (size_t)n * 8));
-    LB_CHECK(arena.take(&keys_out, (size_t)n * 8));
-    LB_CHECK(arena.take(&vals_in, (size_t)n * 4));
-    LB_CHECK(arena.take(&vals_out, (size_t)n * 4));
-    LB_CHECK(arena.take(&left, (size_t)nn * 4));
-    LB_CHECK(arena.take(&right, (size_t)nn * 4));
-    LB_CHECK(arena.take(&pint, (size_t)nn * 4));
-    LB_CHECK(arena.take(&pleaf, (size_t)n * 4));
-    LB_CHECK(arena.take(&arrive, (size_t)nn * 4));
-    LB_CHECK(arena.take(&rlo, (size_t)nn * 4));
-    LB_CHECK(arena.take(&rcnt, (size_t)nn * 4));
-    LB_CHECK(arena.take(&keep, (size_t)nn * 4));
-    LB_CHECK(arena.take(&newidx, (size_t)nn * 4));
-    LB_CHECK(arena.take(&levels, 4));
-    LB_CHECK(arena.take(&live, (size_t)nn * 4));
-    if (dp && n > 1) {
-        LB_CHECK(arena.take(&dk, (size_t)nn * 4));
-        LB_CHECK(arena.take(&dc, (size_t)nn * 12));
-        LB_CHECK(arena.take(&newpos, (size_t)n * 4));
-        LB_CHECK(arena.take(&lmin2, (size_t)n * 12));
-        LB_CHECK(arena.take(&lmax2, (size_t)n * 12));
-        LB_CHECK(arena.take(&tris_dp, (size_t)n * 48));
-    }
-    LB_CHECK(out->tris.alloc_bytes((size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
-    LB_CHECK(hipMemsetAsync((char*)out->tris.get() + (size_t)n * 48, 0, 128, st));
-    if (quant == 2 && n > 1) {
-        LB_CHECK(arena.take(&tris_morton, (size_t)n * 48));
-        LB_CHECK(arena.take(&n_int, (size_t)nn * 4));
-        LB_CHECK(arena.take(&n_ltri, (size_t)nn * 4));
-        LB_CHECK(arena.take(&cbase, (size_t)nn * 4));
-        LB_CHECK(arena.take(&tbase, (size_t)nn * 4));
-    }
-    LB_CHECK(hipMemcpyAsync(bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
-    LB_CHECK(hipMemsetAsync(arrive, 0, (size_t)nn * 4, st));
-    LB_CHECK(hipMemsetAsync(levels, 0, 4, st));
-    hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, bmin, bmax, bounds);
-    hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, bmin, bmax, bounds, n, keys_in, vals_in);
-    LB_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
-    LB_CHECK(arena.take(&temp, temp_bytes ? temp_bytes : 16));
-    LB_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 63, st));
-    hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, vals_out, bmin, bmax, bounds, n,
-                       tris_dp ? tris_dp : (tris_morton ? tris_morton : out->tris.get()), lmin, lmax, geom_mask);
+    RT3_TRY(out->tris.alloc_bytes((size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
+    RT3_TRY(hipMemsetAsync((char*)out->tris.get() + (size_t)n * 48, 0, 128, st));
+    RT3_TRY(hipMemcpyAsync(s.bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
+    RT3_TRY(hipMemsetAsync(s.arrive, 0, (size_t)nn * 4, st));
+    RT3_TRY(hipMemsetAsync(s.levels, 0, 4, st));
+    hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, s.bmin, s.bmax, s.bounds);
+    hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, s.bmin, s.bmax, s.bounds, n, s.keys_in, s.vals_in);
+    RT3_TRY(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, s.sort_bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)n, 0, 63, st));
+    hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, s.vals_out, s.bmin, s.bmax, s.bounds, n,
+                       s.tris_dp ? s.tris_dp : (s.tris_morton ? s.tris_morton : out->tris.get()), s.lmin, s.lmax, geom_mask);
     if (n == 1) {
-        LB_CHECK(out->nodes.alloc_bytes(out->node_bytes));
-        hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, lmin, lmax, wide, quant, out->nodes.get());
+        RT3_TRY(out->nodes.alloc_bytes(out->node_bytes));
+        hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, s.lmin, s.lmax, wide, quant, out->nodes.get());
         out->n_nodes = 1;
         out->max_depth = 2;
-        LB_CHECK(hipGetLastError());
-        LB_CHECK(hipStreamSynchronize(st));
+        RT3_TRY(hipGetLastError());
+        RT3_TRY(hipStreamSynchronize(st));
     } else {
-        hipLaunchKernelGGL(k_hierarchy, dim3(grid), dim3(256), 0, st, keys_out, (int)n, left, right, pint, pleaf, rlo, rcnt);
+        hipLaunchKernelGGL(k_hierarchy, dim3(grid), dim3(256), 0, st, s.keys_out, (int)n, s.left, s.right, s.pint, s.pleaf, s.rlo, s.rcnt);
         // clusters of the SAH top: Karras subtrees of at most T triangles.  Without tree order a multi-triangle leaf must be a Morton range,
         // so T >= leaf_max; with it (cost-driven collapse) T goes down to single triangles
         const uint32_t T_sah = dp ? sah_top : (sah_top > leaf_max ? sah_top : leaf_max);
         const bool lite = sah_top && T_sah <= 64;  // the SAH top only reads the cluster boxes and writes every box above them itself
-        if (lite) hipLaunchKernelGGL(k_refit_clusters, dim3(grid), dim3(256), 0, st, rlo, rcnt, lmin, lmax, nn, T_sah, nbox);
-        else hipLaunchKernelGGL(k_refit, dim3(grid), dim3(256), 0, st, left, right, pint, pleaf, lmin, lmax, n, nbox, arrive);
+        if (lite) hipLaunchKernelGGL(k_refit_clusters, dim3(grid), dim3(256), 0, st, s.rlo, s.rcnt, s.lmin, s.lmax, nn, T_sah, s.nbox);
+        else hipLaunchKernelGGL(k_refit, dim3(grid), dim3(256), 0, st, s.left, s.right, s.pint, s.pleaf, s.lmin, s.lmax, n, s.nbox, s.arrive);
         if (sah_top) {  // re-link the upper tree by binned SAH
             bool relinked = false;
             const auto t0 = std::chrono::steady_clock::now();
-            LB_CHECK(sah_top_relink_gpu(st, n, nn, left, right, rcnt, pint, pleaf, lmin, lmax, nbox, T_sah, arena, &relinked));
+            RT3_TRY(sah_top_relink_gpu(st, nn, s.left, s.right, s.rcnt, s.pint, s.pleaf, s.lmin, s.lmax, s.nbox, T_sah, s.sah, &relinked));
             if (!relinked && lite) {  // fewer than three clusters: the Karras tree stands, and its upper boxes are still to come
-                LB_CHECK(hipMemsetAsync(arrive, 0, (size_t)nn * 4, st));
-                hipLaunchKernelGGL(k_refit, dim3(grid), dim3(256), 0, st, left, right, pint, pleaf, lmin, lmax, n, nbox, arrive);
+                RT3_TRY(hipMemsetAsync(s.arrive, 0, (size_t)nn * 4, st));
+                hipLaunchKernelGGL(k_refit, dim3(grid), dim3(256), 0, st, s.left, s.right, s.pint, s.pleaf, s.lmin, s.lmax, n, s.nbox, s.arrive);
             }
             if (getenv("RT3_TRACE_BUILD")) {
-                LB_CHECK(hipStreamSynchronize(st));
+                RT3_TRY(hipStreamSynchronize(st));
                 fprintf(stderr, "rt3 build: device SAH top (incl. GPU LBVH drain) %.2f ms\n",
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             }
@@ -853,81 +838,71 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
         const auto t3 = std::chrono::steady_clock::now();
         if (dp) {
             // bottom-up: true triangle counts, the collapse costs and choices; then every triangle's / node's place in tree order, and the move
-            LB_CHECK(hipMemsetAsync(arrive, 0, (size_t)nn * 4, st));
-            hipLaunchKernelGGL(k_dp_up, dim3(grid), dim3(256), 0, st, left, right, pint, pleaf, lmin, lmax, nbox, n, leaf_max, rcnt, dc, dk, live, arrive);
+            RT3_TRY(hipMemsetAsync(s.arrive, 0, (size_t)nn * 4, st));
+            hipLaunchKernelGGL(k_dp_up, dim3(grid), dim3(256), 0, st, s.left, s.right, s.pint, s.pleaf, s.lmin, s.lmax, s.nbox, n, leaf_max, s.rcnt, s.dc, s.dk,
+                               s.live, s.arrive);
             const unsigned g3 = (unsigned)(((uint64_t)n + nn + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + nn + 255) / 256);
-            hipLaunchKernelGGL(k_tree_order, dim3(g3), dim3(256), 0, st, left, right, pint, pleaf, rcnt, n, nn, newpos, rlo);
-            float4* tris_to = quant == 2 ? tris_morton : out->tris.get();  // (the compact layout moves them once more, into leaf order, when it emits)
-            hipLaunchKernelGGL(k_tree_reorder, dim3(g3), dim3(256), 0, st, newpos, n, nn, tris_dp, tris_to, lmin, lmax, lmin2, lmax2, left, right);
-            lmin = lmin2;
-            lmax = lmax2;
+            hipLaunchKernelGGL(k_tree_order, dim3(g3), dim3(256), 0, st, s.left, s.right, s.pint, s.pleaf, s.rcnt, n, nn, s.newpos, s.rlo);
+            float4* tris_to = quant == 2 ? s.tris_morton : out->tris.get();  // (the compact layout moves them once more, into leaf order, when it emits)
+            hipLaunchKernelGGL(k_tree_reorder, dim3(g3), dim3(256), 0, st, s.newpos, n, nn, s.tris_dp, tris_to, s.lmin, s.lmax, s.lmin2, s.lmax2, s.left, s.right);
+            s.lmin = s.lmin2;
+            s.lmax = s.lmax2;
         } else {
-            hipLaunchKernelGGL(k_live_flags, dim3(grid), dim3(256), 0, st, rcnt, nn, leaf_max, live);
+            hipLaunchKernelGGL(k_live_flags, dim3(grid), dim3(256), 0, st, s.rcnt, nn, leaf_max, s.live);
         }
         if (collapse) {
             // top-down, one four-wide level per launch (the frontier of level l+1 is produced by level l); ~log4(n) launches, sixteen at a
             // time between looks at the frontier counters (fr_n[l] = size of level l's frontier)
-            uint32_t *fr_a = nullptr, *fr_b = nullptr, *fr_n = nullptr, wide_levels = 0;
             const uint32_t root = 0, one = 1;
-            const size_t n_cnt = (size_t)nn + 18;  // a level per node at most, plus one burst
-            hipError_t e2 = arena.take(&fr_a, (size_t)nn * 4);
-            if (e2 == hipSuccess) e2 = arena.take(&fr_b, (size_t)nn * 4);
-            if (e2 == hipSuccess) e2 = arena.take(&fr_n, n_cnt * 4);
-            if (e2 == hipSuccess) e2 = hipMemsetAsync(keep, 0, (size_t)nn * 4, st);
-            if (e2 == hipSuccess) e2 = hipMemsetAsync(fr_n, 0, n_cnt * 4, st);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(fr_a, &root, 4, hipMemcpyHostToDevice, st);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(fr_n, &one, 4, hipMemcpyHostToDevice, st);
+            const size_t n_cnt = (size_t)nn + 18;
+            RT3_TRY(hipMemsetAsync(s.keep, 0, (size_t)nn * 4, st));
+            RT3_TRY(hipMemsetAsync(s.fr_n, 0, n_cnt * 4, st));
+            RT3_TRY(hipMemcpyAsync(s.fr_a, &root, 4, hipMemcpyHostToDevice, st));
+            RT3_TRY(hipMemcpyAsync(s.fr_n, &one, 4, hipMemcpyHostToDevice, st));
             const unsigned g2 = (unsigned)((nn + 255) / 256 > 1024 ? 1024 : (nn + 255) / 256);
-            uint32_t level = 0, last = 1;
-            while (e2 == hipSuccess && last > 0 && level + 16 < n_cnt) {
+            uint32_t level = 0, last = 1, wide_levels = 0;
+            while (last > 0 && level + 16 < n_cnt) {
                 for (int burst = 0; burst < 16; burst++, level++) {
-                    hipLaunchKernelGGL(k_wide_level, dim3(g2), dim3(256), 0, st, left, right, live, nbox, dk, collapse, fr_a, fr_n + level, keep, fr_b, fr_n + level + 1);
-                    std::swap(fr_a, fr_b);
+                    hipLaunchKernelGGL(k_wide_level, dim3(g2), dim3(256), 0, st, s.left, s.right, s.live, s.nbox, s.dk, collapse, s.fr_a, s.fr_n + level, s.keep,
+                                       s.fr_b, s.fr_n + level + 1);
+                    std::swap(s.fr_a, s.fr_b);
                 }
-                e2 = hipMemcpyAsync(&last, fr_n + level, 4, hipMemcpyDeviceToHost, st);
-                if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+                RT3_TRY(hipMemcpyAsync(&last, s.fr_n + level, 4, hipMemcpyDeviceToHost, st));
+                RT3_TRY(hipStreamSynchronize(st));
             }
-            if (e2 == hipSuccess) {  // the number of non-empty frontiers
-                std::vector<uint32_t> h_cnt(level + 1);
-                e2 = hipMemcpyAsync(h_cnt.data(), fr_n, (size_t)(level + 1) * 4, hipMemcpyDeviceToHost, st);
-                if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-                while (wide_levels <= level && h_cnt[wide_levels] > 0) wide_levels++;
-            }
-            LB_CHECK(e2);
+            std::vector<uint32_t> h_cnt(level + 1);  // the number of non-empty frontiers
+            RT3_TRY(hipMemcpyAsync(h_cnt.data(), s.fr_n, (size_t)(level + 1) * 4, hipMemcpyDeviceToHost, st));
+            RT3_TRY(hipStreamSynchronize(st));
+            while (wide_levels <= level && h_cnt[wide_levels] > 0) wide_levels++;
             const uint32_t lv = wide_levels + 1;  // levels from the root down to the deepest node's leaf slots
-            LB_CHECK(hipMemcpyAsync(levels, &lv, 4, hipMemcpyHostToDevice, st));
-            LB_CHECK(hipStreamSynchronize(st));
+            RT3_TRY(hipMemcpyAsync(s.levels, &lv, 4, hipMemcpyHostToDevice, st));
+            RT3_TRY(hipStreamSynchronize(st));
         } else {
-            hipLaunchKernelGGL(k_keep_flags, dim3(grid), dim3(256), 0, st, pint, live, nn, wide, keep, levels);
+            hipLaunchKernelGGL(k_keep_flags, dim3(grid), dim3(256), 0, st, s.pint, s.live, nn, wide, s.keep, s.levels);
         }
-        LB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, temp2_bytes, keep, newidx, (int)nn, st));
-        LB_CHECK(arena.take(&temp2, temp2_bytes ? temp2_bytes : 16));
-        LB_CHECK(hipcub::DeviceScan::ExclusiveSum(temp2, temp2_bytes, keep, newidx, (int)nn, st));
-        LB_CHECK(hipMemcpyAsync(&tail[0], newidx + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-        LB_CHECK(hipMemcpyAsync(&tail[1], keep + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-        LB_CHECK(hipMemcpyAsync(&out->max_depth, levels, 4, hipMemcpyDeviceToHost, st));
-        LB_CHECK(hipStreamSynchronize(st));
+        RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, s.scan_bytes, s.keep, s.newidx, (int)nn, st));
+        RT3_TRY(hipMemcpyAsync(&tail[0], s.newidx + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+        RT3_TRY(hipMemcpyAsync(&tail[1], s.keep + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+        RT3_TRY(hipMemcpyAsync(&out->max_depth, s.levels, 4, hipMemcpyDeviceToHost, st));
+        RT3_TRY(hipStreamSynchronize(st));
         out->n_nodes = tail[0] + tail[1];
-        LB_CHECK(out->nodes.alloc_bytes((size_t)out->n_nodes * out->node_bytes));
+        RT3_TRY(out->nodes.alloc_bytes((size_t)out->n_nodes * out->node_bytes));
         if (quant == 2) {
-            hipLaunchKernelGGL(k_child_counts, dim3(grid), dim3(256), 0, st, left, right, rcnt, nbox, keep, nn, live, dk, collapse, n_int, n_ltri);
-            LB_CHECK(hipcub::DeviceScan::ExclusiveSum(temp2, temp2_bytes, n_int, cbase, (int)nn, st));
-            LB_CHECK(hipcub::DeviceScan::ExclusiveSum(temp2, temp2_bytes, n_ltri, tbase, (int)nn, st));
-            hipLaunchKernelGGL(k_assign_index, dim3(grid), dim3(256), 0, st, left, right, live, nbox, keep, nn, dk, collapse, cbase, newidx);
+            hipLaunchKernelGGL(k_child_counts, dim3(grid), dim3(256), 0, st, s.left, s.right, s.rcnt, s.nbox, s.keep, nn, s.live, s.dk, collapse, s.n_int, s.n_ltri);
+            RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, s.scan_bytes, s.n_int, s.cbase, (int)nn, st));
+            RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, s.scan_bytes, s.n_ltri, s.tbase, (int)nn, st));
+            hipLaunchKernelGGL(k_assign_index, dim3(grid), dim3(256), 0, st, s.left, s.right, s.live, s.nbox, s.keep, nn, s.dk, collapse, s.cbase, s.newidx);
         }
-        hipLaunchKernelGGL(k_emit_nodes, dim3(grid), dim3(256), 0, st, left, right, rlo, rcnt, keep, newidx, lmin, lmax, nbox, nn, live, dk, wide,
-                           quant, collapse, out->nodes.get(), cbase, tbase, tris_morton, out->tris.get());
+        hipLaunchKernelGGL(k_emit_nodes, dim3(grid), dim3(256), 0, st, s.left, s.right, s.rlo, s.rcnt, s.keep, s.newidx, s.lmin, s.lmax, s.nbox, nn, s.live, s.dk,
+                           wide, quant, collapse, out->nodes.get(), s.cbase, s.tbase, s.tris_morton, out->tris.get());
         if (wide && quant == 1) {  // top-of-tree copy the traversal kernels keep in LDS
-            uint32_t* d_ntop = nullptr;
-            LB_CHECK(out->top.alloc_bytes((size_t)kTopCacheNodes * 64));
-            LB_CHECK(arena.take(&d_ntop, 4));
-            hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, out->nodes.get(), out->n_nodes, (uint32_t*)out->top.get(), d_ntop);
-            hipError_t e3 = hipMemcpyAsync(&out->n_top, d_ntop, 4, hipMemcpyDeviceToHost, st);
-            if (e3 == hipSuccess) e3 = hipStreamSynchronize(st);
-            LB_CHECK(e3);
+            RT3_TRY(out->top.alloc_bytes((size_t)kTopCacheNodes * 64));
+            hipLaunchKernelGGL(k_top_cache, dim3(1), dim3(1), 0, st, out->nodes.get(), out->n_nodes, (uint32_t*)out->top.get(), s.n_top);
+            RT3_TRY(hipMemcpyAsync(&out->n_top, s.n_top, 4, hipMemcpyDeviceToHost, st));
+            RT3_TRY(hipStreamSynchronize(st));
         }
-        LB_CHECK(hipGetLastError());
-        LB_CHECK(hipStreamSynchronize(st));
+        RT3_TRY(hipGetLastError());
+        RT3_TRY(hipStreamSynchronize(st));
         if (getenv("RT3_TRACE_BUILD"))
             fprintf(stderr, "rt3 build: collapse + emit %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
     }

@@ -91,12 +91,6 @@ __global__ void k_emit_guide(const uint32_t* __restrict__ cdf, uint32_t n, uint3
     }
 }
 
-#define LT_CHECK(x)                            \
-    do {                                       \
-        hipError_t e_ = (x);                   \
-        if (e_ != hipSuccess) return e_;       \
-    } while (0)
-
 template <typename T>
 static hipError_t alloc_n(DevBuf<T>& b, size_t n) {
     return b.alloc_bytes((n ? n : 1) * sizeof(T));
@@ -113,10 +107,10 @@ hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indi
     std::copy(geom_base.begin(), geom_base.end(), small.begin());
     std::copy(eg_geom.begin(), eg_geom.end(), small.begin() + ng);
     std::copy(eg_first.begin(), eg_first.end(), small.begin() + ng + neg);
-    LT_CHECK(alloc_n(out->geom_base, small.size()));
-    if (!small.empty()) LT_CHECK(hipMemcpyAsync(out->geom_base.get(), small.data(), small.size() * 4, hipMemcpyHostToDevice, st));
+    RT3_TRY(alloc_n(out->geom_base, small.size()));
+    if (!small.empty()) RT3_TRY(hipMemcpyAsync(out->geom_base.get(), small.data(), small.size() * 4, hipMemcpyHostToDevice, st));
     if (n == 0 || neg == 0) {
-        LT_CHECK(hipStreamSynchronize(st));  // (the host vector goes out of scope)
+        RT3_TRY(hipStreamSynchronize(st));  // (the host vector goes out of scope)
         return hipSuccess;
     }
     uint32_t cells = 1, shift = 23;
@@ -124,40 +118,35 @@ hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indi
         cells <<= 1;
         shift--;
     }
-    LT_CHECK(alloc_n(out->rec, 4 * (size_t)n));
-    LT_CHECK(alloc_n(out->cdf, n));
-    LT_CHECK(alloc_n(out->prim, n));
-    LT_CHECK(alloc_n(out->area, n));
-    LT_CHECK(alloc_n(out->guide, (size_t)cells + 1));
-    // scratch: power (4 n), max word, weights (8 n), prefix (8 n), scan storage
+    RT3_TRY(alloc_n(out->rec, 4 * (size_t)n));
+    RT3_TRY(alloc_n(out->cdf, n));
+    RT3_TRY(alloc_n(out->prim, n));
+    RT3_TRY(alloc_n(out->area, n));
+    RT3_TRY(alloc_n(out->guide, (size_t)cells + 1));
+    // scratch: power, max word, weights, prefix, scan storage
+    float* power = nullptr;
+    uint32_t* max_power = nullptr;
     unsigned long long *q = nullptr, *prefix = nullptr;
+    char* scan_tmp = nullptr;
     size_t scan_bytes = 0;
-    LT_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, q, prefix, (int)n, st));
-    const size_t off_max = ((size_t)n * 4 + 255) & ~(size_t)255, off_q = off_max + 256, off_p = off_q + (((size_t)n * 8 + 255) & ~(size_t)255),
-                 off_s = off_p + (((size_t)n * 8 + 255) & ~(size_t)255), need = off_s + scan_bytes + 256;
-    if (need > out->scratch_cap) {
-        out->scratch_cap = 0;
-        LT_CHECK(out->scratch.alloc_bytes(need));
-        out->scratch_cap = need;
-    }
-    char* s = out->scratch.get();
-    float* power = reinterpret_cast<float*>(s);
-    uint32_t* max_power = reinterpret_cast<uint32_t*>(s + off_max);
-    q = reinterpret_cast<unsigned long long*>(s + off_q);
-    prefix = reinterpret_cast<unsigned long long*>(s + off_p);
+    RT3_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, q, prefix, (int)n, st));
+    BufLayout plan;
+    plan.add(&power, n).add(&max_power, 1).add(&q, n).add(&prefix, n).add(&scan_tmp, scan_bytes);
+    RT3_TRY(out->scratch.grow_bytes(plan.bytes()));
+    RT3_TRY(plan.carve(out->scratch));
     const uint32_t* d_eg_geom = out->geom_base.get() + ng;
     const uint32_t* d_eg_first = d_eg_geom + neg;
-    LT_CHECK(hipMemsetAsync(max_power, 0, 4, st));
+    RT3_TRY(hipMemsetAsync(max_power, 0, 4, st));
     hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n)), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, d_eg_geom, d_eg_first, (uint32_t)neg, n,
                        out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
     hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, power, max_power, n, q);
-    LT_CHECK(hipcub::DeviceScan::InclusiveSum(s + off_s, scan_bytes, q, prefix, (int)n, st));
+    RT3_TRY(hipcub::DeviceScan::InclusiveSum(scan_tmp, scan_bytes, q, prefix, (int)n, st));
     hipLaunchKernelGGL(k_emit_cdf, dim3(grid_of(n)), dim3(256), 0, st, prefix, out->area.get(), n, out->cdf.get(), out->rec.get());
     hipLaunchKernelGGL(k_emit_guide, dim3(grid_of((uint64_t)cells + 1)), dim3(256), 0, st, out->cdf.get(), n, cells, shift, out->guide.get());
-    LT_CHECK(hipGetLastError());
+    RT3_TRY(hipGetLastError());
     uint32_t total = 0;
-    LT_CHECK(hipMemcpyAsync(&total, out->cdf.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    LT_CHECK(hipStreamSynchronize(st));
+    RT3_TRY(hipMemcpyAsync(&total, out->cdf.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipStreamSynchronize(st));
     out->n = n;
     out->n_guide = cells;
     out->guide_shift = shift;

@@ -894,132 +894,107 @@ __global__ __launch_bounds__(256) void k_sah_small(SahArrays A, const SahSeg* se
 }
 }  // namespace
 
+hipError_t sah_top_plan(hipStream_t st, uint32_t n, BufLayout& plan, SahTopScratch* s) {
+    const size_t nn = n - 1, nc = n;  // top nodes, clusters: at most
+    plan.add(&s->top, nn).add(&s->ncl, nn).add(&s->pool_pos, nn).add(&s->cl_pos, nn);
+    RT3_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, s->scan_bytes, s->top, s->pool_pos, (int)nn, st));
+    plan.add(&s->scan_tmp, s->scan_bytes);
+    plan.add(&s->pool, nn).add(&s->cl_ref, nc).add(&s->cl_cnt, nc).add(&s->cl_mn, 3 * nc).add(&s->cl_mx, 3 * nc).add(&s->idx, nc).add(&s->tmp, nc);
+    plan.add(&s->seg_a, 2 * (nc / kSahSmall + 2) * sizeof(SahSeg));  // [huge | big] of the current level
+    plan.add(&s->seg_b, 2 * (nc / kSahSmall + 2) * sizeof(SahSeg));  // ... of the next one
+    plan.add(&s->seg_small, (nc / 2 + 2) * sizeof(SahSeg));
+    plan.add(&s->counters, 16);
+    const size_t mh = nc / kSahHuge + 1, mt = nc / kSahTile + mh + 1;
+    plan.add(&s->huge, mh * sizeof(SahHuge)).add(&s->tiles, mt * sizeof(SahTile)).add(&s->tile_left, mt).add(&s->tile_woff, mt).add(&s->tile_roff, mt);
+    return hipSuccess;
+}
+
 // returns hipSuccess and *relinked = false when the tree has fewer than three clusters (nothing to do, like the oracle)
-hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t n, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
-                              const float* lmin, const float* lmax, float* nbox, uint32_t T, BuildArena& arena, bool* relinked) {
+hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t nn, uint32_t* left, uint32_t* right, uint32_t* rcnt, uint32_t* pint, uint32_t* pleaf,
+                              const float* lmin, const float* lmax, float* nbox, uint32_t T, const SahTopScratch& s, bool* relinked) {
     *relinked = false;
-    hipError_t err = hipSuccess;
-    uint32_t *top = nullptr, *ncl = nullptr, *pool_pos = nullptr, *cl_pos = nullptr, *pool = nullptr, *cl_ref = nullptr, *cl_cnt = nullptr, *idx = nullptr, *tmp = nullptr,
-             *counters = nullptr;
-    float *cl_mn = nullptr, *cl_mx = nullptr;
-    SahSeg *seg_a = nullptr, *seg_b = nullptr, *seg_small = nullptr;
-    SahHuge* hs = nullptr;
-    SahTile* tiles = nullptr;
-    uint32_t *tile_left = nullptr, *tile_woff = nullptr, *tile_roff = nullptr;
-    void* scan_tmp = nullptr;
-    size_t scan_bytes = 0;
-    uint32_t tails[4] = {0, 0, 0, 0}, npool = 0, nc = 0;
+    uint32_t tails[4] = {0, 0, 0, 0};
     const unsigned grid = (unsigned)(((uint64_t)nn + 255) / 256 > 4096 ? 4096 : ((uint64_t)nn + 255) / 256);
-#define SAH_CHECK(x)            \
-    do {                        \
-        err = (x);              \
-        if (err != hipSuccess) goto sah_done; \
-    } while (0)
-    SAH_CHECK(arena.take(&top, (size_t)nn * 4));
-    SAH_CHECK(arena.take(&ncl, (size_t)nn * 4));
-    SAH_CHECK(arena.take(&pool_pos, (size_t)nn * 4));
-    SAH_CHECK(arena.take(&cl_pos, (size_t)nn * 4));
-    hipLaunchKernelGGL(k_sah_mark, dim3(grid), dim3(256), 0, st, left, right, rcnt, nn, T, top, ncl);
-    SAH_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, top, pool_pos, (int)nn, st));
-    SAH_CHECK(arena.take(&scan_tmp, scan_bytes ? scan_bytes : 16));
-    SAH_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, top, pool_pos, (int)nn, st));
-    SAH_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ncl, cl_pos, (int)nn, st));
-    SAH_CHECK(hipMemcpyAsync(&tails[0], pool_pos + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-    SAH_CHECK(hipMemcpyAsync(&tails[1], top + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-    SAH_CHECK(hipMemcpyAsync(&tails[2], cl_pos + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-    SAH_CHECK(hipMemcpyAsync(&tails[3], ncl + (nn - 1), 4, hipMemcpyDeviceToHost, st));
-    SAH_CHECK(hipStreamSynchronize(st));
-    npool = tails[0] + tails[1];
-    nc = tails[2] + tails[3];
-    if (nc < 3 || npool != nc - 1) goto sah_done;  // (the oracle's early return)
-    (void)n;
-    SAH_CHECK(arena.take(&pool, (size_t)npool * 4));
-    SAH_CHECK(arena.take(&cl_ref, (size_t)nc * 4));
-    SAH_CHECK(arena.take(&cl_cnt, (size_t)nc * 4));
-    SAH_CHECK(arena.take(&cl_mn, (size_t)nc * 12));
-    SAH_CHECK(arena.take(&cl_mx, (size_t)nc * 12));
-    SAH_CHECK(arena.take(&idx, (size_t)nc * 4));
-    SAH_CHECK(arena.take(&tmp, (size_t)nc * 4));
-    SAH_CHECK(arena.take(&seg_a, 2 * ((size_t)nc / kSahSmall + 2) * sizeof(SahSeg)));  // [huge | big] of the current level
-    SAH_CHECK(arena.take(&seg_b, 2 * ((size_t)nc / kSahSmall + 2) * sizeof(SahSeg)));  // ... of the next one
-    SAH_CHECK(arena.take(&seg_small, ((size_t)nc / 2 + 2) * sizeof(SahSeg)));
-    SAH_CHECK(arena.take(&counters, 64));
-    SAH_CHECK(hipMemsetAsync(counters, 0, 64, st));
-    {
-        const size_t mh = (size_t)nc / kSahHuge + 1, mt = (size_t)nc / kSahTile + mh + 1;
-        SAH_CHECK(arena.take(&hs, mh * sizeof(SahHuge)));
-        SAH_CHECK(arena.take(&tiles, mt * sizeof(SahTile)));
-        SAH_CHECK(arena.take(&tile_left, mt * 4));
-        SAH_CHECK(arena.take(&tile_woff, mt * 4));
-        SAH_CHECK(arena.take(&tile_roff, mt * 4));
-    }
-    hipLaunchKernelGGL(k_sah_gather, dim3(grid), dim3(256), 0, st, left, right, rcnt, nn, T, top, pool_pos, cl_pos, lmin, lmax, nbox, pool, cl_ref, cl_cnt, cl_mn, cl_mx, idx);
-    {
-        SahArrays A{left, right, rcnt, pint, pleaf, cl_ref, cl_cnt, cl_mn, cl_mx, pool, idx, tmp, T, nbox};
-        const size_t half = (size_t)nc / kSahSmall + 2;
-        const SahSeg root{0, nc, 0, 0xFFFFFFFFu};
-        // counters: [0..2] huge / big segment counts of the level being processed + spare, [4..6] of the next level, [8] small segments
-        uint32_t cnt[3] = {0, 0, 0};
-        cnt[nc > kSahHuge ? 0 : (nc > kSahSmall ? 1 : 2)] = 1;
-        SAH_CHECK(hipMemcpyAsync(nc > kSahHuge ? seg_a : (nc > kSahSmall ? seg_a + half : seg_small), &root, sizeof(root), hipMemcpyHostToDevice, st));
-        SAH_CHECK(hipMemcpyAsync(counters, cnt, 8, hipMemcpyHostToDevice, st));
-        SAH_CHECK(hipMemcpyAsync(counters + 8, &cnt[2], 4, hipMemcpyHostToDevice, st));
-        const bool trace = getenv("RT3_TRACE_BUILD") != nullptr;
-        auto tnow = [] { return std::chrono::steady_clock::now(); };
-        auto tl = tnow();
-        // Levels are launched back to back with grids sized for the most segments a level can hold (workgroups beyond the level's
-        // count return at once); the host looks at the counters only every 24 levels.  A level's segments have more than kSahSmall
-        // (kSahHuge) clusters each, so there are at most nc / kSahSmall (nc / kSahHuge) of them.
-        const uint32_t max_huge = nc / kSahHuge + 1, max_big = nc / kSahSmall + 1, max_tiles = nc / kSahTile + max_huge + 1;
-        bool huge_possible = nc > kSahHuge;  // (checked again with the counters after every burst of levels)
-        int level = 0, cur = 0;
-        for (;;) {
-            for (int burst = 0; burst < (huge_possible ? 8 : 24); burst++, level++, cur ^= 1) {
-                uint32_t* c_cur = counters + 4 * cur;
-                uint32_t* c_next = counters + 4 * (cur ^ 1);
-                SAH_CHECK(hipMemsetAsync(c_next, 0, 8, st));
-                const SahQueues Q{seg_b, seg_b + half, seg_small, c_next, counters + 8};
-                if (huge_possible) {  // segments of more than kSahHuge clusters, tiled over several workgroups: one launch per phase
-                    uint32_t* n_tiles = counters + 12;
-                    SAH_CHECK(hipMemsetAsync(n_tiles, 0, 4, st));
-                    hipLaunchKernelGGL(k_sahh_tiles, dim3(max_huge), dim3(64), 0, st, seg_a, c_cur, hs, tiles, n_tiles);
-                    hipLaunchKernelGGL(k_sahh_bounds, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
-                    hipLaunchKernelGGL(k_sahh_bins, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
-                    hipLaunchKernelGGL(k_sahh_pick, dim3(max_huge), dim3(64), 0, st, seg_a, c_cur, hs);
-                    hipLaunchKernelGGL(k_sahh_count, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles, tile_left);
-                    hipLaunchKernelGGL(k_sahh_scan, dim3((max_huge + 63) / 64), dim3(64), 0, st, seg_a, c_cur, hs, tile_left, tile_woff, tile_roff);
-                    hipLaunchKernelGGL(k_sahh_scatter, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles, tile_woff, tile_roff);
-                    hipLaunchKernelGGL(k_sahh_copy, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
-                    hipLaunchKernelGGL(k_sahh_emit, dim3((max_huge + 63) / 64), dim3(64), 0, st, A, seg_a, c_cur, hs, Q);
-                }
-                hipLaunchKernelGGL(k_sah_block<256>, dim3(max_big), dim3(256), 0, st, A, seg_a + half, c_cur + 1, Q);
-                std::swap(seg_a, seg_b);
+    size_t scan_bytes = s.scan_bytes;
+    hipLaunchKernelGGL(k_sah_mark, dim3(grid), dim3(256), 0, st, left, right, rcnt, nn, T, s.top, s.ncl);
+    RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, scan_bytes, s.top, s.pool_pos, (int)nn, st));
+    RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, scan_bytes, s.ncl, s.cl_pos, (int)nn, st));
+    RT3_TRY(hipMemcpyAsync(&tails[0], s.pool_pos + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipMemcpyAsync(&tails[1], s.top + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipMemcpyAsync(&tails[2], s.cl_pos + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipMemcpyAsync(&tails[3], s.ncl + (nn - 1), 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipStreamSynchronize(st));
+    const uint32_t npool = tails[0] + tails[1], nc = tails[2] + tails[3];
+    if (nc < 3 || npool != nc - 1) return hipSuccess;  // (the oracle's early return)
+    SahSeg *seg_a = reinterpret_cast<SahSeg*>(s.seg_a), *seg_b = reinterpret_cast<SahSeg*>(s.seg_b), *seg_small = reinterpret_cast<SahSeg*>(s.seg_small);
+    SahHuge* hs = reinterpret_cast<SahHuge*>(s.huge);
+    SahTile* tiles = reinterpret_cast<SahTile*>(s.tiles);
+    uint32_t* counters = s.counters;
+    RT3_TRY(hipMemsetAsync(counters, 0, 64, st));
+    hipLaunchKernelGGL(k_sah_gather, dim3(grid), dim3(256), 0, st, left, right, rcnt, nn, T, s.top, s.pool_pos, s.cl_pos, lmin, lmax, nbox, s.pool, s.cl_ref,
+                       s.cl_cnt, s.cl_mn, s.cl_mx, s.idx);
+    SahArrays A{left, right, rcnt, pint, pleaf, s.cl_ref, s.cl_cnt, s.cl_mn, s.cl_mx, s.pool, s.idx, s.tmp, T, nbox};
+    const size_t half = (size_t)nc / kSahSmall + 2;
+    const SahSeg root{0, nc, 0, 0xFFFFFFFFu};
+    // counters: [0..2] huge / big segment counts of the level being processed + spare, [4..6] of the next level, [8] small segments
+    uint32_t cnt[3] = {0, 0, 0};
+    cnt[nc > kSahHuge ? 0 : (nc > kSahSmall ? 1 : 2)] = 1;
+    RT3_TRY(hipMemcpyAsync(nc > kSahHuge ? seg_a : (nc > kSahSmall ? seg_a + half : seg_small), &root, sizeof(root), hipMemcpyHostToDevice, st));
+    RT3_TRY(hipMemcpyAsync(counters, cnt, 8, hipMemcpyHostToDevice, st));
+    RT3_TRY(hipMemcpyAsync(counters + 8, &cnt[2], 4, hipMemcpyHostToDevice, st));
+    const bool trace = getenv("RT3_TRACE_BUILD") != nullptr;
+    auto tnow = [] { return std::chrono::steady_clock::now(); };
+    auto tl = tnow();
+    // Levels are launched back to back with grids sized for the most segments a level can hold (workgroups beyond the level's
+    // count return at once); the host looks at the counters only every 24 levels.  A level's segments have more than kSahSmall
+    // (kSahHuge) clusters each, so there are at most nc / kSahSmall (nc / kSahHuge) of them.
+    const uint32_t max_huge = nc / kSahHuge + 1, max_big = nc / kSahSmall + 1, max_tiles = nc / kSahTile + max_huge + 1;
+    bool huge_possible = nc > kSahHuge;  // (checked again with the counters after every burst of levels)
+    int level = 0, cur = 0;
+    for (;;) {
+        for (int burst = 0; burst < (huge_possible ? 8 : 24); burst++, level++, cur ^= 1) {
+            uint32_t* c_cur = counters + 4 * cur;
+            uint32_t* c_next = counters + 4 * (cur ^ 1);
+            RT3_TRY(hipMemsetAsync(c_next, 0, 8, st));
+            const SahQueues Q{seg_b, seg_b + half, seg_small, c_next, counters + 8};
+            if (huge_possible) {  // segments of more than kSahHuge clusters, tiled over several workgroups: one launch per phase
+                uint32_t* n_tiles = counters + 12;
+                RT3_TRY(hipMemsetAsync(n_tiles, 0, 4, st));
+                hipLaunchKernelGGL(k_sahh_tiles, dim3(max_huge), dim3(64), 0, st, seg_a, c_cur, hs, tiles, n_tiles);
+                hipLaunchKernelGGL(k_sahh_bounds, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
+                hipLaunchKernelGGL(k_sahh_bins, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
+                hipLaunchKernelGGL(k_sahh_pick, dim3(max_huge), dim3(64), 0, st, seg_a, c_cur, hs);
+                hipLaunchKernelGGL(k_sahh_count, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles, s.tile_left);
+                hipLaunchKernelGGL(k_sahh_scan, dim3((max_huge + 63) / 64), dim3(64), 0, st, seg_a, c_cur, hs, s.tile_left, s.tile_woff, s.tile_roff);
+                hipLaunchKernelGGL(k_sahh_scatter, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles, s.tile_woff, s.tile_roff);
+                hipLaunchKernelGGL(k_sahh_copy, dim3(max_tiles), dim3(256), 0, st, A, seg_a, hs, tiles, n_tiles);
+                hipLaunchKernelGGL(k_sahh_emit, dim3((max_huge + 63) / 64), dim3(64), 0, st, A, seg_a, c_cur, hs, Q);
             }
-            SAH_CHECK(hipMemcpyAsync(cnt, counters + 4 * cur, 8, hipMemcpyDeviceToHost, st));
-            SAH_CHECK(hipStreamSynchronize(st));
-            if (cnt[0] + cnt[1] == 0) break;
-            huge_possible = cnt[0] > 0;
+            hipLaunchKernelGGL(k_sah_block<256>, dim3(max_big), dim3(256), 0, st, A, seg_a + half, c_cur + 1, Q);
+            std::swap(seg_a, seg_b);
         }
-        if (trace) {
-            fprintf(stderr, "rt3 build:   SAH block levels (%d launched): %.3f ms\n", level, std::chrono::duration<double, std::milli>(tnow() - tl).count());
-            tl = tnow();
-        }
-        SAH_CHECK(hipMemcpyAsync(&cnt[2], counters + 8, 4, hipMemcpyDeviceToHost, st));
-        SAH_CHECK(hipStreamSynchronize(st));
-        if (cnt[2]) hipLaunchKernelGGL(k_sah_small, dim3((cnt[2] + 15) / 16), dim3(256), 0, st, A, seg_small, cnt[2]);
-        if (trace) {
-            SAH_CHECK(hipStreamSynchronize(st));
-            fprintf(stderr, "rt3 build:   SAH small: %u segments, %.3f ms (%u clusters)\n", cnt[2], std::chrono::duration<double, std::milli>(tnow() - tl).count(), nc);
-        }
-        const uint32_t no_parent = 0xFFFFFFFFu;
-        SAH_CHECK(hipMemcpyAsync(pint, &no_parent, 4, hipMemcpyHostToDevice, st));
-        SAH_CHECK(hipGetLastError());
-        SAH_CHECK(hipStreamSynchronize(st));  // (no_parent / root live on this frame's stack)
-        *relinked = true;
+        RT3_TRY(hipMemcpyAsync(cnt, counters + 4 * cur, 8, hipMemcpyDeviceToHost, st));
+        RT3_TRY(hipStreamSynchronize(st));
+        if (cnt[0] + cnt[1] == 0) break;
+        huge_possible = cnt[0] > 0;
     }
-sah_done:
-#undef SAH_CHECK
-    return err;
+    if (trace) {
+        fprintf(stderr, "rt3 build:   SAH block levels (%d launched): %.3f ms\n", level, std::chrono::duration<double, std::milli>(tnow() - tl).count());
+        tl = tnow();
+    }
+    RT3_TRY(hipMemcpyAsync(&cnt[2], counters + 8, 4, hipMemcpyDeviceToHost, st));
+    RT3_TRY(hipStreamSynchronize(st));
+    if (cnt[2]) hipLaunchKernelGGL(k_sah_small, dim3((cnt[2] + 15) / 16), dim3(256), 0, st, A, seg_small, cnt[2]);
+    if (trace) {
+        RT3_TRY(hipStreamSynchronize(st));
+        fprintf(stderr, "rt3 build:   SAH small: %u segments, %.3f ms (%u clusters)\n", cnt[2], std::chrono::duration<double, std::milli>(tnow() - tl).count(), nc);
+    }
+    const uint32_t no_parent = 0xFFFFFFFFu;
+    RT3_TRY(hipMemcpyAsync(pint, &no_parent, 4, hipMemcpyHostToDevice, st));
+    RT3_TRY(hipGetLastError());
+    RT3_TRY(hipStreamSynchronize(st));  // (no_parent / root live on this frame's stack)
+    *relinked = true;
+    return hipSuccess;
 }
 
 }  // namespace rt3
