@@ -297,6 +297,8 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *        "gbuffer"       (x,y)=window   bindings {gbuffer RGBA32UI, gbuffer_depth R32F}                (gbuffer.slang:5-6)
  *        "refrence_mode" (x,y)=window   bindings {gbuffer, gbuffer_depth, Light, PrevLight}            (refrence_mode.slang:8-11)
  *        "postprocess"   (x,y,z)=groups of 8x8  bindings {Depth, Out RGBA32F, In RGBA32F}             (postprocess.slang:5-7)
+ *        "denoise"       (x,y,z)=groups of 8x8 over the window  bindings {gbuffer, gbuffer_depth, In RGBA32F, Out RGBA32F}
+ *                        (no reference counterpart: the edge-avoiding filter described at rt3_denoise_set_params below)
  *      and the probe-GI passes (restated as written, debug stores included; rules for what the text leaves open are listed in
  *      DESIGN.md section 11).  A probe owns 16x16 pixels and an 8x8-texel cell of the atlas images; bindings are ordered by
  *      (descriptor set, binding) as the shaders declare them:
@@ -307,6 +309,30 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *      Work is enqueued on the context's stream and returns immediately. ---- */
 int rt3_pass_launch(rt3_ctx *ctx, const char *pass_name, const char *entry, uint32_t x, uint32_t y, uint32_t z,
                     const void *constants, size_t constants_size, const uint32_t *bindings, uint32_t n_bindings);
+/* ---- "denoise": a G-buffer-guided, edge-avoiding a-trous wavelet filter (the spatial half of SVGF) for low-sample frames.  No reference
+ *      counterpart; DESIGN.md section 4f.  Out = filtered In (linear radiance, e.g. the Light of refrence_mode) for foreground pixels; background
+ *      pixels (gbuffer_depth == RT3_BACKGROUND_DEPTH) and every alpha are copied from In bit for bit, and background pixels never contribute.
+ *      In is demodulated by the first-hit albedo and emission of the G-buffer (c = (In - emission) / max(albedo, 1/256)), filtered, and
+ *      modulated again, so base-colour textures are preserved.  Stages: a 7 x 7 spatial variance estimate of luminance(c), then `iterations`
+ *      passes of 5 x 5 B3-spline taps at step 2^i, each tap weighted by max(0, n_p . n_q)^(2^normal_squarings) (shading normals),
+ *      exp(-sin(angle by which the tap leaves p's tangent plane) / sigma_z) (world positions from gbuffer_depth and GConst's camera) and
+ *      exp(-|l_q - l_p| / (sigma_l * sqrt(3 x 3 blurred variance) + 1e-6)).  fp32, equal to tests/ref_denoise.py bit for bit.
+ *      In and Out must be different images (RT3_E_INVALID); formats and sizes are checked like every pass.  iterations = 0 copies In to Out.
+ *      A tap needs pixels that other ranks own: under a tile partition with more than one rank the pass returns RT3_E_STATE (filter the
+ *      gathered image on the gather root with the partition switched off).  The scratch images (64 bytes per pixel) belong to the context,
+ *      are reserved on first use and kept across frames.
+ *      rt3_denoise_set_params: NULL restores the defaults {5, 7, 0.05, 4.0, 0}.  RT3_E_INVALID (nothing changed) for iterations > 8,
+ *      normal_squarings > 16, a sigma that is not finite or not positive, or an unknown flag. ---- */
+#define RT3_DENOISE_NO_DEMODULATION 1u /* In is not what refrence_mode wrote (the probe-GI Light, for one): filter it as it is */
+typedef struct rt3_denoise_params {
+    uint32_t iterations;       /* a-trous passes, step 1, 2, 4, ...: 0..8 */
+    uint32_t normal_squarings; /* k: the normal weight's exponent is 2^k */
+    float sigma_z;
+    float sigma_l;
+    uint32_t flags; /* RT3_DENOISE_* */
+} rt3_denoise_params;
+int rt3_denoise_set_params(rt3_ctx *ctx, const rt3_denoise_params *params);
+
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);
 
@@ -334,6 +360,7 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      26 sky_eval_and_pdf (u, v -> bilinear radiance, pdf in solid angle).
  *      textures of the context: 27 tex_alpha (base-colour texture index as int32, u, v -> alpha in [0, 1]; 1 for an index without a texture),
  *      the alpha-mask lookup of the traversal kernels (rt3_scene_set_alpha_cutoffs).
+ *      28 expn (x >= 0 -> e^-x, the polynomial of the denoise pass's edge weights).
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

@@ -22,6 +22,8 @@ OPT_BATCH_SPP, OPT_PROFILE, OPT_COUNT_TRAVERSAL, OPT_EXTEND_VARIANT, OPT_LEAF_SI
 OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
 OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
+DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
+SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
@@ -33,7 +35,7 @@ EXPORTS = [
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
-    "rt3_pass_launch", "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
+    "rt3_pass_launch", "rt3_denoise_set_params", "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
 
 
@@ -58,6 +60,15 @@ class Instance(C.Structure):
     """rt3_instance: Instance{model} + Transform{Mat4} (src/renderer/world/mod.rs:34-60); transform column-major like glam's Mat4."""
 
     _fields_ = [("geometry_first", C.c_uint32), ("geometry_count", C.c_uint32), ("transform", C.c_float * 16)]
+
+
+class DenoiseParams(C.Structure):
+    """rt3_denoise_params: the "denoise" pass.  The defaults are the library's."""
+
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("flags", C.c_uint32)]
+
+    def __init__(self, iterations=5, normal_squarings=7, sigma_z=0.05, sigma_l=4.0, flags=0):
+        super().__init__(iterations, normal_squarings, sigma_z, sigma_l, flags)
 
 
 assert C.sizeof(GConst) == 304
@@ -144,6 +155,7 @@ def load():
         "rt3_gather_layout": (i32, [vp, u32, u32, u32, C.POINTER(C.c_uint64)]),
         "rt3_gather_unpack": (i32, [vp, u32, u32, u32, vp]),
         "rt3_pass_launch": (i32, [vp, C.c_char_p, C.c_char_p, u32, u32, u32, vp, sz, pu32, u32]),
+        "rt3_denoise_set_params": (i32, [vp, C.POINTER(DenoiseParams)]),
         "rt3_frame_wait": (i32, [vp]),
         "rt3_trace_rays": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double)]),
         "rt3_selftest_eval": (i32, [vp, i32, vp, u32, vp]),

@@ -27,6 +27,7 @@ static_assert(RT3_F_NEE_SKY == RT3_FLAG_NEE_SKY && RT3_F_BLUENOISE == RT3_FLAG_B
 namespace {
 
 thread_local std::string g_create_error;
+static const rt3_denoise_params kDenoiseDefaults = {5u, 7u, 0.05f, 4.0f, 0u};
 
 struct Resource {
     uint32_t tag = 0;
@@ -188,6 +189,9 @@ struct rt3_ctx {
     std::vector<MeshTables> refit_tables;    // instance mode 1: each bottom tree's (tl_build_mesh's)
     DevBuf<char> refit_scratch;              // grow-only: refit_tree's bounds, node boxes and record boxes
     TwoLevelState tl;
+    // "denoise" pass: parameters (rt3_denoise_set_params) and the grow-only scratch its records are carved from
+    rt3_denoise_params dn_params = kDenoiseDefaults;
+    DevBuf<char> dn_scratch;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
     std::vector<Timed> pending_events;
@@ -774,6 +778,58 @@ int pass_interpolate_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_
     memcpy(&gd, g, sizeof(gd));
     ScopedTimer t(c, CAT_OTHER);
     launch_interpolate(c->stream, gd, W, H, gb->ptr, (const float*)dp->ptr, sh->ptr, li->ptr);
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "denoise": edge-avoiding a-trous filter over the whole window (no reference counterpart)
+int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
+    uint32_t W, H;
+    if (int r = check_window(c, g, &W, &H)) return r;
+    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1) return fail(c, RT3_E_INVALID, "denoise: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups");
+    if (nb != 4) return fail(c, RT3_E_INVALID, "denoise expects 4 bindings {gbuffer, gbuffer_depth, In, Out}");
+    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
+    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
+    Resource* in = image_checked(c, b[2], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "In");
+    Resource* out = image_checked(c, b[3], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Out");
+    if (!gb || !dp || !in || !out) return RT3_E_INVALID;
+    if (in == out || in->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: 'In' and 'Out' must be different images (a tap reads In while other pixels are written)");
+    if (c->n_ranks > 1)
+        return fail(c, RT3_E_STATE, "denoise: a tap needs pixels that other ranks own; run it on the gathered image with the tile partition switched off "
+                                    "(rt3_set_tile_partition(w, h, 0, 1))");
+    const rt3_denoise_params& p = c->dn_params;
+    if (p.iterations == 0) {
+        ScopedTimer t(c, CAT_OTHER);
+        HIPC(c, hipMemcpyAsync(out->ptr, in->ptr, (size_t)W * H * 16, hipMemcpyDeviceToDevice, c->stream));
+        return RT3_OK;
+    }
+    DenoiseLaunch L;
+    memcpy(&L.g, g, sizeof(L.g));
+    L.W = W; L.H = H; L.squarings = p.normal_squarings; L.flags = p.flags; L.sigma_z = p.sigma_z; L.sigma_l = p.sigma_l;
+    L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr; L.in = in->ptr; L.out = out->ptr;
+    BufLayout plan;
+    denoise_plan(W, H, plan, &L.s);
+    if (c->dn_scratch.capacity_bytes() < plan.bytes()) {  // the stream may still read the old allocation
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, c->dn_scratch.grow_bytes(plan.bytes()));
+    }
+    HIPC(c, plan.carve(c->dn_scratch));
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_prepare(c->stream, L);
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_variance(c->stream, L);
+    }
+    for (uint32_t i = 0; i < p.iterations; i++) {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_atrous(c->stream, L, i);
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_finish(c->stream, L, p.iterations);
+    }
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -2196,9 +2252,24 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
     if (!strcmp(pass_name, "trace_probes")) return pass_trace_probes(c, &g, x, y, bindings, n_bindings);
     if (!strcmp(pass_name, "spherical_harmonic_conversion")) return pass_sh_conversion(c, x, y, z, bindings, n_bindings);
     if (!strcmp(pass_name, "interpolate_probes")) return pass_interpolate_probes(c, &g, x, y, z, bindings, n_bindings);
+    if (!strcmp(pass_name, "denoise")) return pass_denoise(c, &g, x, y, z, bindings, n_bindings);
     return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name +
                                       "' (known: gbuffer, refrence_mode, postprocess, structured_importance_sampling, trace_probes, "
-                                      "spherical_harmonic_conversion, interpolate_probes)");
+                                      "spherical_harmonic_conversion, interpolate_probes, denoise)");
+}
+int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->dn_params = kDenoiseDefaults;
+        return RT3_OK;
+    }
+    if (p->iterations > 8) return fail(c, RT3_E_INVALID, "denoise params: iterations must be 0..8 (step 2^i: 8 iterations reach 512 pixels)");
+    if (p->normal_squarings > 16) return fail(c, RT3_E_INVALID, "denoise params: normal_squarings must be 0..16 (the exponent is 2^k)");
+    if (!(std::isfinite(p->sigma_z) && p->sigma_z > 0.0f) || !(std::isfinite(p->sigma_l) && p->sigma_l > 0.0f))
+        return fail(c, RT3_E_INVALID, "denoise params: sigma_z and sigma_l must be finite and positive");
+    if (p->flags & ~RT3_DENOISE_NO_DEMODULATION) return fail(c, RT3_E_INVALID, "denoise params: unknown flag bits");
+    c->dn_params = *p;
+    return RT3_OK;
 }
 int rt3_frame_wait(rt3_ctx* c) {
     if (!c) return RT3_E_INVALID;

@@ -201,6 +201,27 @@ RT3_DEV void sincos_2pi(float u, float& s_out, float& c_out) {
     s_out = q == 0 ? ss : (q == 1 ? cc : (q == 2 ? -ss : -cc));
     c_out = q == 0 ? cc : (q == 1 ? -ss : (q == 2 ? -cc : ss));
 }
+// e^-x for x >= 0 (the denoise pass's edge weights): t = x log2(e) rounded once, i = int(t + 1/2), f = t - i exact with |f| <= 1/2; 2^-f by
+// the degree-7 Taylor polynomial of exp(-f ln 2); scaled by 2^-i in two exact power-of-two factors, so that a result below 2^-126 is
+// rounded once, as a denormal; 0 from t >= 150 on (2^-150 ties to 0), which +inf and NaN reach too.  tests/ref_denoise.py restates it.
+RT3_DEV float expn(float x) {
+    const float t = x * 1.442695022e+00f;
+    const bool live = t < 150.0f;
+    const float tc = live ? t : 0.0f;
+    const int i = (int)(tc + 0.5f);
+    const float f = tc - (float)i;
+    float p = -1.525273365e-05f;
+    p = p * f + 1.540352969e-04f;
+    p = p * f + -1.333355787e-03f;
+    p = p * f + 9.618128650e-03f;
+    p = p * f + -5.550410971e-02f;
+    p = p * f + 2.402265072e-01f;
+    p = p * f + -6.931471825e-01f;
+    p = p * f + 1.0f;
+    const int i0 = i >> 1;
+    const float r = (p * exp2_int(-i0)) * exp2_int(i0 - i);
+    return live ? r : 0.0f;
+}
 RT3_DEV float atan2_poly(float y, float x) {
     float ax = x < 0.0f ? -x : x, ay = y < 0.0f ? -y : y;
     float mx = fmax_sel(ax, ay), mn = fmin_sel(ax, ay);

@@ -292,6 +292,29 @@ hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indi
                         const uint32_t* first_prim, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
                         const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out);
 
+// "denoise" pass (rt3_denoise.hip).  Scratch: two guide records and two signal images of W x H float4, carved from the
+// context's grow-only denoise buffer.  Stages in stream order: prepare, variance, `iterations` x atrous (iteration 0, 1, ...), finish.
+struct DenoiseScratch {
+    float4 *gP, *gN;  // {P.xyz, 1 = foreground} and {n.xyz, 0}; a background record is all zero
+    float4* sig[2];   // {c.rgb, variance}, ping-pong
+};
+struct DenoiseLaunch {
+    GConstDev g;
+    uint32_t W, H, squarings, flags;
+    float sigma_z, sigma_l;
+    const void* gbuffer;
+    const float* depth;
+    const void* in;
+    void* out;
+    DenoiseScratch s;
+};
+void denoise_plan(uint32_t W, uint32_t H, BufLayout& plan, DenoiseScratch* s);
+void launch_denoise_prepare(hipStream_t st, const DenoiseLaunch& L);
+void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L);
+void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iteration);
+void launch_denoise_finish(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
+void launch_selftest_denoise(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);  // selftest op 28: expn
+
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 
 }  // namespace rt3

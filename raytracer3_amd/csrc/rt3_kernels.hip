@@ -1320,16 +1320,17 @@ __global__ void k_selftest(int op, const SceneDev sc, const uint32_t* __restrict
     }
 }
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
-    static const uint32_t w[28][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
+    static const uint32_t w[29][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
-                                      {2, 9}, {2, 4}, {3, 1}};
-    if (op < 0 || op > 27) return false;
+                                      {2, 9}, {2, 4}, {3, 1}, {1, 1}};
+    if (op < 0 || op > 28) return false;
     *in_w = w[op][0];
     *out_w = w[op][1];
     return true;
 }
 void launch_selftest(hipStream_t st, int op, const SceneDev& sc, const uint32_t* in, uint32_t n, uint32_t* out) {
     if (op >= 13 && op <= 16) return launch_selftest_probes(st, op, in, n, out);
+    if (op == 28) return launch_selftest_denoise(st, in, n, out);
     hipLaunchKernelGGL(k_selftest, dim3((n + 255) / 256), dim3(256), 0, st, op, sc, in, n, out);
 }
 

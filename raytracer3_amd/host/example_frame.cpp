@@ -2,10 +2,12 @@
 // It is the analogue of `renderer::commands` (src/renderer/mod.rs:65-106) for the three path-tracing passes:
 // reads a scene dump, describes one frame with the builder chain, runs it and writes Light (RGBA32F) + colour.
 //
-//   example_frame scene.bin W H spp bounces flags frame out.bin [probes]
+//   example_frame scene.bin W H spp bounces flags frame out.bin [probes | denoise]
 // With the trailing word `probes` the frame is the probe-GI chain of the old shaders instead (gbuffer ->
 // structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes) and
 // out.bin holds Light followed by the probe atlas.
+// With the trailing word `denoise` (single process only) the node ComputePass "denoise" (the library's a-trous filter)
+// sits between refrence_mode and postprocess, which then tone-maps the filtered image; out.bin holds Light, colour, then the filtered image.
 // Multi-GPU (one process per GPU, like `bench.py --gpus N`): with RT3_RANKS = n > 0 in the environment this process is rank RT3_RANK of n on
 // device RT3_DEVICE (default: the rank), renders its 64x64 tiles and joins the frame's ONE collective, rt3_gather_tiles; rank 0 creates the
 // RCCL id and hands it to the others through the file RT3_UID_FILE (the C ABI opens no channel of its own) and writes out.bin.
@@ -29,8 +31,9 @@ static std::vector<T> read_vec(FILE* f, size_t n) {
 
 int main(int argc, char** argv) {
     const bool probes = argc == 10 && std::string(argv[9]) == "probes";
-    if (argc != 9 && !probes) {
-        fprintf(stderr, "usage: %s scene.bin W H spp bounces flags frame out.bin [probes]\n", argv[0]);
+    const bool denoise = argc == 10 && std::string(argv[9]) == "denoise";
+    if (argc != 9 && !probes && !denoise) {
+        fprintf(stderr, "usage: %s scene.bin W H spp bounces flags frame out.bin [probes | denoise]\n", argv[0]);
         return 2;
     }
     try {
@@ -156,8 +159,16 @@ int main(int argc, char** argv) {
                       .write(rt3::IMPORTED, gbuffer).write(rt3::IMPORTED, depth).launch(rt3::WorkSize2D::FullScreen());
         auto pt = rt3::RayTracingPass::New(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
                       .read(gb, gbuffer).read(gb, depth).write(rt3::IMPORTED, light).read(rt3::IMPORTED, prev).launch(rt3::WorkSize2D::FullScreen());
+        auto lit_node = pt;
+        auto lit = light;
+        if (denoise) {
+            if (n_ranks) throw std::runtime_error("denoise: a tap needs pixels other ranks own; filter the gathered frame on one rank");
+            lit = rg.image(rt3::ImageSize::FullScreen(), RT3_FORMAT_R32G32B32A32_SFLOAT, "denoised");
+            lit_node = rt3::ComputePass::New(rg, "denoise").shader("denoise").constants(gconst)
+                           .read(gb, gbuffer).read(gb, depth).read(pt, light).write(rt3::IMPORTED, lit).dispatch(rt3::DispatchSize::FullScreen());
+        }
         rt3::ComputePass::New(rg, "postprocess").shader("postprocess").constants(gconst)
-            .read(gb, depth).write(rt3::IMPORTED, color).read(pt, light).dispatch(rt3::DispatchSize::FullScreen());
+            .read(gb, depth).write(rt3::IMPORTED, color).read(lit_node, lit).dispatch(rt3::DispatchSize::FullScreen());
         rg.draw_frame(color);
         if (n_ranks) {  // the frame's collective(s): enqueued behind the passes on the context's stream, no host synchronisation
             ctx.check(rt3_gather_tiles(ctx.raw(), light, 0), "gather Light");
@@ -175,6 +186,10 @@ int main(int argc, char** argv) {
         FILE* o = fopen(argv[8], "wb");
         fwrite(out.data(), 4, out.size(), o);
         fwrite(col.data(), 4, col.size(), o);
+        if (denoise) {
+            ctx.check(rt3_resource_download(ctx.raw(), lit, col.data(), col.size() * 4), "download");
+            fwrite(col.data(), 4, col.size(), o);
+        }
         fclose(o);
         rt3_stats st;
         ctx.check(rt3_stats_get(ctx.raw(), &st), "stats");

@@ -91,6 +91,8 @@ class Context {
     void check(int rc, const char* what) const {
         if (rc) throw std::runtime_error(std::string(what) + ": " + rt3_last_error(ctx_) + " (" + std::to_string(rc) + ")");
     }
+    // parameters of ComputePass "denoise" (rt3_denoise_set_params; no reference counterpart); nullptr = the defaults
+    void set_denoise_params(const rt3_denoise_params* p) const { check(rt3_denoise_set_params(ctx_, p), "rt3_denoise_set_params"); }
 
    private:
     rt3_ctx* ctx_ = nullptr;

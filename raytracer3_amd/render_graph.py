@@ -282,6 +282,12 @@ class Context:
         self.check(self.lib.rt3_selftest_eval(self.h, op, inp.ctypes.data, n, out.ctypes.data))
         return out
 
+    def set_denoise_params(self, params=None, **kw):
+        """parameters of the "denoise" pass (rt3_denoise_set_params): an L.DenoiseParams, or its fields as keywords; nothing = the defaults"""
+        if params is None and kw:
+            params = L.DenoiseParams(**kw)
+        self.check(self.lib.rt3_denoise_set_params(self.h, C.byref(params) if params is not None else None))
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

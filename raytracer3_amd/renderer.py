@@ -5,6 +5,7 @@ Per frame, three passes exactly as the old shaders were wired:
   RayTracingPass("gbuffer")        -> packed G-buffer + depth                 shaders/old/gbuffer.slang
   RayTracingPass("refrence_mode")  -> Light (RGBA32F linear radiance)          shaders/old/refrence_mode.slang
   ComputePass("postprocess")       -> display image (AgX)                      shaders/old/postprocess.slang
+with, on request, ComputePass("denoise") between the last two (no reference counterpart: the a-trous filter of DESIGN.md section 4f),
 and, as a second frame description, the probe-GI chain of the old shaders (`probe_commands`):
   gbuffer -> structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes
 """
@@ -45,6 +46,37 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
+def frame_nodes(rg, gconst, postprocess=True, denoise=False):
+    """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
+    `denoise`, the "denoise" node filters `Light` into `denoised` and postprocess reads that instead."""
+    gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
+    depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
+    light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
+    prev = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "PrevLight")
+    out = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "color")
+    handles = dict(gbuffer=gbuffer, depth=depth, light=light, prev=prev, color=out)
+    gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
+          .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
+    pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
+          .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
+    src, lit = pt, light
+    if denoise:
+        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, pt, light)
+        handles["denoised"] = lit
+    if postprocess:
+        (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
+         .read(gb, depth).write(IMPORTED, out).read(src, lit).dispatch(DispatchSize.FullScreen))
+    return handles
+
+
+def denoise_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
+    """ComputePass("denoise"): {gbuffer, gbuffer_depth, In = `light`, Out = the image `denoised`}.  Returns (node, denoised)."""
+    denoised = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "denoised")
+    dn = (ComputePass.new(rg, "denoise").shader("denoise").constants(gconst)
+          .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light).write(IMPORTED, denoised).dispatch(DispatchSize.FullScreen))
+    return dn, denoised
+
+
 class PathTracer:
     """One GPU's share of the frame.  `rank` / `n_ranks` select the interleaved 64x64 tiles this process renders."""
 
@@ -81,23 +113,36 @@ class PathTracer:
         g.pad[0] = flags
         return g
 
-    def commands(self, gconst: L.GConst, postprocess=True):
-        """Build this frame's nodes (the analogue of renderer::commands, renderer/mod.rs:65-106)."""
+    def commands(self, gconst: L.GConst, postprocess=True, denoise=False):
+        """Build this frame's nodes (frame_nodes).  `denoise` needs the whole window on this rank: with several ranks use denoise()."""
+        self.rg.begin_frame()
+        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise)
+        return self.handles
+
+    def denoise(self, gconst, wait=True):
+        """Filter the `Light` of the last render() into `denoised` with the "denoise" pass (parameters: ctx.set_denoise_params).  A tap
+        reads pixels of other tiles, so with several ranks this runs on the rank that holds the assembled frame -- after
+        gather_light(..., download=False) on its root -- with the partition switched off around it, like render_probes: the G-buffer is
+        rendered again for the whole window (primary rays only), then the gathered `Light` is filtered.  Returns the handles."""
         rg = self.rg
         rg.begin_frame()
         gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
         depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
         light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
-        prev = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "PrevLight")
-        out = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "color")
-        gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
-              .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
-        pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
-              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
-        if postprocess:
-            (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
-             .read(gb, depth).write(IMPORTED, out).read(pt, light).dispatch(DispatchSize.FullScreen))
-        self.handles = dict(gbuffer=gbuffer, depth=depth, light=light, prev=prev, color=out)
+        gb = IMPORTED
+        if self.n_ranks > 1:
+            gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
+                  .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
+        _, denoised = denoise_node(rg, gconst, gb, gbuffer, depth, IMPORTED, light)
+        self.handles = dict(getattr(self, "handles", {}), gbuffer=gbuffer, depth=depth, light=light, denoised=denoised)
+        W, H = self.window
+        if self.n_ranks > 1:
+            self.ctx.set_tile_partition(W, H, 0, 1)
+        try:
+            rg.draw_frame(denoised, wait=wait)
+        finally:
+            if self.n_ranks > 1:  # launches read the partition when they are enqueued: safe to restore behind them
+                self.ctx.set_tile_partition(W, H, self.rank, self.n_ranks)
         return self.handles
 
     def probe_commands(self, gconst: L.GConst):
@@ -151,9 +196,9 @@ class PathTracer:
         W, H = self.window
         self.rg.upload(self.handles["prev_atlas"], self.rg.download(self.handles["atlas"], (H // 16 * 8, W // 16 * 8, 4), np.float32))
 
-    def render(self, gconst, postprocess=False, wait=True):
-        h = self.commands(gconst, postprocess)
-        self.rg.draw_frame(h["color"] if postprocess else h["light"], wait=wait)
+    def render(self, gconst, postprocess=False, wait=True, denoise=False):
+        h = self.commands(gconst, postprocess, denoise)
+        self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else h["light"]), wait=wait)
         return h
 
     # ---- results
@@ -164,6 +209,10 @@ class PathTracer:
     def color(self):
         W, H = self.window
         return self.rg.download(self.handles["color"], (H, W, 4), np.float32)
+
+    def denoised(self):
+        W, H = self.window
+        return self.rg.download(self.handles["denoised"], (H, W, 4), np.float32)
 
     def gbuffer(self):
         W, H = self.window

@@ -7,6 +7,8 @@
                          --compare resources/refrence_480x270.png --side-by-side profiles/r02_cornell_ref_side_by_side.png
                           (informational only: a 480x270 copy of the reference tree's resources/refrence.png, a Blender-Cycles render of
                           the box scenes.cornell_ref() rebuilds from the reference's processed asset; Cycles is not this estimator)
+  python tools/render.py --scene atrium --size 1920x1080 --spp 1 --denoise --out atrium_1spp_denoised.png
+                         (the a-trous filter of DESIGN.md section 4f between refrence_mode and postprocess; for low sample counts)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -33,6 +35,8 @@ def main():
     ap.add_argument("--passes", type=int, default=1)
     ap.add_argument("--bounces", type=int, default=4)
     ap.add_argument("--flags", type=int, default=-1)
+    ap.add_argument("--denoise", action="store_true", help="filter Light with the 'denoise' pass before the tone map (last pass only)")
+    ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous iterations of --denoise (0..8)")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
@@ -63,11 +67,14 @@ def main():
     flags = args.flags if args.flags >= 0 else (DEFAULT_FLAGS if sky is not None else L.F_FACEFORWARD | L.F_SPECULAR)
     pt = PathTracer((W, H))
     pt.set_scene(mesh, sky, assets.load_bluenoise())
+    if args.denoise:
+        pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
     cam = Camera(cam_kw["position"], cam_kw["direction"], math.radians(cam_kw["fov_deg"]), W / H)
     history, t0 = [], time.perf_counter()
     for p in range(args.passes):
         g = pt.make_gconst(cam, args.spp, args.bounces, frame=p, blendfactor=1.0 / (p + 1), flags=flags)
-        pt.render(g, postprocess=(p == args.passes - 1))
+        last = p == args.passes - 1
+        pt.render(g, postprocess=last, denoise=args.denoise and last)
         if args.curve:
             history.append(pt.light()[..., :3].copy())
         if p != args.passes - 1:
