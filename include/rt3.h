@@ -299,6 +299,9 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *        "postprocess"   (x,y,z)=groups of 8x8  bindings {Depth, Out RGBA32F, In RGBA32F}             (postprocess.slang:5-7)
  *        "denoise"       (x,y,z)=groups of 8x8 over the window  bindings {gbuffer, gbuffer_depth, In RGBA32F, Out RGBA32F}
  *                        (no reference counterpart: the edge-avoiding filter described at rt3_denoise_set_params below)
+ *        "temporal"      (x,y,z)=groups of 8x8 over the window  bindings {gbuffer, gbuffer_depth, In RGBA32F, PrevGbuffer RGBA32UI,
+ *                        PrevDepth R32F, PrevHistory RGBA32F, PrevMoments RGBA32F, Out RGBA32F, History RGBA32F, Moments RGBA32F}
+ *                        (no reference counterpart: the reprojected accumulation described at rt3_temporal_set_params below)
  *      and the probe-GI passes (restated as written, debug stores included; rules for what the text leaves open are listed in
  *      DESIGN.md section 11).  A probe owns 16x16 pixels and an 8x8-texel cell of the atlas images; bindings are ordered by
  *      (descriptor set, binding) as the shaders declare them:
@@ -332,6 +335,43 @@ typedef struct rt3_denoise_params {
     uint32_t flags; /* RT3_DENOISE_* */
 } rt3_denoise_params;
 int rt3_denoise_set_params(rt3_ctx *ctx, const rt3_denoise_params *params);
+/* The temporal variance for "denoise": with `moments_image` set to the Moments image {mu1, mu2, variance, N} that "temporal" wrote for the
+ * same frame, the result of the 7 x 7 stage is replaced per foreground pixel by Moments.z where Moments.w >= 4 (SVGF's rule: a history of
+ * at least four frames); elsewhere the spatial estimate stands.  0 (the default) = none: "denoise" computes what it always did.  The image
+ * is checked when "denoise" is launched: a live RGBA32F image of the window's size that is not Out, else RT3_E_INVALID. */
+int rt3_denoise_set_variance_input(rt3_ctx *ctx, uint32_t moments_image);
+
+/* ---- "temporal": reprojected accumulation under a moving camera (the temporal half of SVGF).  No reference counterpart; DESIGN.md section
+ *      4g.  Per foreground pixel: the surface record of "denoise" (world position P from gbuffer_depth and GConst's camera, 11:10:11 normal n,
+ *      c = (In - emission) / max(albedo, 1/256), l = luminance(c)); q = prev.proj * prev.view * (P, 1) gives the position (sx, sy) in the
+ *      previous frame, sx = (q.x / q.w * 0.5 + 0.5) * W - 0.5, sy = (-q.y / q.w * 0.5 + 0.5) * H - 0.5.  Its four bilinear taps count when they
+ *      lie inside the window, are foreground in PrevDepth, have PrevHistory.w > 0, n . n_q >= normal_cos and
+ *      |n . (P_q - P)| <= plane_tolerance * |P - eye| (P_q from PrevDepth and the previous camera).  With h, k the weight-normalised taps of
+ *      PrevHistory and PrevMoments: N = min(h.w + 1, max_history), a = max(alpha, 1 / N), c_acc = h + a (c - h), likewise mu1, mu2 of l and
+ *      l * l with alpha_moments; variance = max(0, mu2 - mu1^2).  Without a counted tap (or q.w <= 0, or (sx, sy) outside (-1, W) x (-1, H)):
+ *      N = 1, c_acc = c, mu1 = l, mu2 = l * l.  History = {c_acc, N}, Moments = {mu1, mu2, variance, N}, Out = {emission + c_acc * albedo,
+ *      In.a}: displayable, and a valid In for "denoise".  Background pixels: Out = In bit for bit, History = Moments = 0.
+ *      PrevHistory.w > 0 is the reset rule: zeroed previous images mean "no history" (first frame, resize, new scene).  fp32, equal to
+ *      tests/ref_temporal.py bit for bit.  The scene is taken as static between the two frames: there are no motion vectors, and geometry
+ *      moved by rt3_scene_update_vertices is caught only as far as the plane test catches it.
+ *      The three written images must differ from each other and from every image read (RT3_E_INVALID).  Under a tile partition with more
+ *      than one rank the pass returns RT3_E_STATE, like "denoise".  A launch with no previous view set returns RT3_E_STATE; a previous
+ *      window_size that differs from the launch's is RT3_E_INVALID.
+ *      rt3_temporal_set_prev_view: the previous frame's 304-byte GConst, captured by value at each launch; only proj, view, proj_inverse,
+ *      view_inverse and window_size are read.  size must be 304; (NULL, 0) forgets the view.
+ *      rt3_temporal_set_params: NULL restores the defaults {0.2, 0.2, 32, 0.9, 0.01, 0}.  RT3_E_INVALID (nothing changed) for a value outside
+ *      the ranges below, NaN included, or an unknown flag. ---- */
+#define RT3_TEMPORAL_NO_DEMODULATION 1u /* same meaning as RT3_DENOISE_NO_DEMODULATION */
+typedef struct rt3_temporal_params {
+    float alpha;           /* floor of the colour blend weight, 0..1; 0 = plain running mean */
+    float alpha_moments;   /* the same for the moments */
+    uint32_t max_history;  /* N is clamped to this, 1..65535 */
+    float normal_cos;      /* a tap is rejected when n_p . n_q < normal_cos; -1..1 */
+    float plane_tolerance; /* ... or when |n_p . (P_q - P_p)| > plane_tolerance * |P_p - eye|; finite, > 0 */
+    uint32_t flags;        /* RT3_TEMPORAL_* */
+} rt3_temporal_params;
+int rt3_temporal_set_prev_view(rt3_ctx *ctx, const void *prev_gconst, size_t size);
+int rt3_temporal_set_params(rt3_ctx *ctx, const rt3_temporal_params *params);
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);

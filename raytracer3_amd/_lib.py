@@ -23,6 +23,7 @@ OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
 OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
 DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
+TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
 
 EXPORTS = [
@@ -35,7 +36,8 @@ EXPORTS = [
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
-    "rt3_pass_launch", "rt3_denoise_set_params", "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
+    "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
+    "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
 
 
@@ -69,6 +71,16 @@ class DenoiseParams(C.Structure):
 
     def __init__(self, iterations=5, normal_squarings=7, sigma_z=0.05, sigma_l=4.0, flags=0):
         super().__init__(iterations, normal_squarings, sigma_z, sigma_l, flags)
+
+
+class TemporalParams(C.Structure):
+    """rt3_temporal_params: the "temporal" pass.  The defaults are the library's."""
+
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_uint32), ("normal_cos", C.c_float),
+                ("plane_tolerance", C.c_float), ("flags", C.c_uint32)]
+
+    def __init__(self, alpha=0.2, alpha_moments=0.2, max_history=32, normal_cos=0.9, plane_tolerance=0.01, flags=0):
+        super().__init__(alpha, alpha_moments, max_history, normal_cos, plane_tolerance, flags)
 
 
 assert C.sizeof(GConst) == 304
@@ -156,6 +168,9 @@ def load():
         "rt3_gather_unpack": (i32, [vp, u32, u32, u32, vp]),
         "rt3_pass_launch": (i32, [vp, C.c_char_p, C.c_char_p, u32, u32, u32, vp, sz, pu32, u32]),
         "rt3_denoise_set_params": (i32, [vp, C.POINTER(DenoiseParams)]),
+        "rt3_denoise_set_variance_input": (i32, [vp, u32]),
+        "rt3_temporal_set_prev_view": (i32, [vp, vp, sz]),
+        "rt3_temporal_set_params": (i32, [vp, C.POINTER(TemporalParams)]),
         "rt3_frame_wait": (i32, [vp]),
         "rt3_trace_rays": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double)]),
         "rt3_selftest_eval": (i32, [vp, i32, vp, u32, vp]),

@@ -28,6 +28,7 @@ namespace {
 
 thread_local std::string g_create_error;
 static const rt3_denoise_params kDenoiseDefaults = {5u, 7u, 0.05f, 4.0f, 0u};
+static const rt3_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32u, 0.9f, 0.01f, 0u};
 
 struct Resource {
     uint32_t tag = 0;
@@ -192,6 +193,11 @@ struct rt3_ctx {
     // "denoise" pass: parameters (rt3_denoise_set_params) and the grow-only scratch its records are carved from
     rt3_denoise_params dn_params = kDenoiseDefaults;
     DevBuf<char> dn_scratch;
+    uint32_t dn_variance_image = 0;  // rt3_denoise_set_variance_input: the "temporal" pass's Moments image, 0 = none
+    // "temporal" pass: parameters (rt3_temporal_set_params) and the previous frame's GConst (rt3_temporal_set_prev_view)
+    rt3_temporal_params tp_params = kTemporalDefaults;
+    rt3_gconst tp_prev;
+    bool tp_has_prev = false;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
     std::vector<Timed> pending_events;
@@ -797,6 +803,12 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32
     if (c->n_ranks > 1)
         return fail(c, RT3_E_STATE, "denoise: a tap needs pixels that other ranks own; run it on the gathered image with the tile partition switched off "
                                     "(rt3_set_tile_partition(w, h, 0, 1))");
+    Resource* mo = nullptr;
+    if (c->dn_variance_image) {
+        mo = image_checked(c, c->dn_variance_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "variance input");
+        if (!mo) return RT3_E_INVALID;
+        if (mo == out || mo->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: the variance input (rt3_denoise_set_variance_input) must not be 'Out'");
+    }
     const rt3_denoise_params& p = c->dn_params;
     if (p.iterations == 0) {
         ScopedTimer t(c, CAT_OTHER);
@@ -807,6 +819,7 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32
     memcpy(&L.g, g, sizeof(L.g));
     L.W = W; L.H = H; L.squarings = p.normal_squarings; L.flags = p.flags; L.sigma_z = p.sigma_z; L.sigma_l = p.sigma_l;
     L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr; L.in = in->ptr; L.out = out->ptr;
+    L.moments = mo ? mo->ptr : nullptr;
     BufLayout plan;
     denoise_plan(W, H, plan, &L.s);
     if (c->dn_scratch.capacity_bytes() < plan.bytes()) {  // the stream may still read the old allocation
@@ -829,6 +842,51 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_denoise_finish(c->stream, L, p.iterations);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "temporal": reprojected accumulation of the previous frame's history (no reference counterpart)
+int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
+    uint32_t W, H;
+    if (int r = check_window(c, g, &W, &H)) return r;
+    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1) return fail(c, RT3_E_INVALID, "temporal: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups");
+    if (nb != 10)
+        return fail(c, RT3_E_INVALID, "temporal expects 10 bindings {gbuffer, gbuffer_depth, In, PrevGbuffer, PrevDepth, PrevHistory, PrevMoments, Out, "
+                                      "History, Moments}");
+    static const struct { uint32_t format; const char* name; } kB[10] = {
+        {RT3_FORMAT_R32G32B32A32_UINT, "gbuffer"},       {RT3_FORMAT_R32_SFLOAT, "gbuffer_depth"},        {RT3_FORMAT_R32G32B32A32_SFLOAT, "In"},
+        {RT3_FORMAT_R32G32B32A32_UINT, "PrevGbuffer"},   {RT3_FORMAT_R32_SFLOAT, "PrevDepth"},            {RT3_FORMAT_R32G32B32A32_SFLOAT, "PrevHistory"},
+        {RT3_FORMAT_R32G32B32A32_SFLOAT, "PrevMoments"}, {RT3_FORMAT_R32G32B32A32_SFLOAT, "Out"},         {RT3_FORMAT_R32G32B32A32_SFLOAT, "History"},
+        {RT3_FORMAT_R32G32B32A32_SFLOAT, "Moments"}};
+    Resource* r[10];
+    for (int i = 0; i < 10; i++)
+        if (!(r[i] = image_checked(c, b[i], W, H, kB[i].format, kB[i].name))) return RT3_E_INVALID;
+    for (int i = 7; i < 10; i++)
+        for (int j = 0; j < i; j++)
+            if (r[i] == r[j] || r[i]->ptr == r[j]->ptr)
+                return fail(c, RT3_E_INVALID, std::string("temporal: '") + kB[i].name + "' and '" + kB[j].name +
+                                                  "' must be different images (taps read the previous images while other pixels are written)");
+    if (c->n_ranks > 1)
+        return fail(c, RT3_E_STATE, "temporal: a reprojected tap may belong to pixels that other ranks own; run it on the gathered image with the tile "
+                                    "partition switched off (rt3_set_tile_partition(w, h, 0, 1))");
+    if (!c->tp_has_prev) return fail(c, RT3_E_STATE, "temporal: no previous view (rt3_temporal_set_prev_view)");
+    if (c->tp_prev.window_size[0] != g->window_size[0] || c->tp_prev.window_size[1] != g->window_size[1])
+        return fail(c, RT3_E_INVALID, "temporal: the previous view's window_size differs from this frame's (after a resize, start over from zeroed history)");
+    const rt3_temporal_params& p = c->tp_params;
+    TemporalLaunch L;
+    memcpy(&L.g, g, sizeof(L.g));
+    memcpy(&L.prev, &c->tp_prev, sizeof(L.prev));
+    L.W = W; L.H = H; L.flags = p.flags;
+    L.alpha = p.alpha; L.alpha_moments = p.alpha_moments; L.max_history = (float)p.max_history; L.normal_cos = p.normal_cos;
+    L.plane_tolerance = p.plane_tolerance;
+    L.gbuffer = r[0]->ptr; L.depth = (const float*)r[1]->ptr; L.in = r[2]->ptr;
+    L.prev_gbuffer = r[3]->ptr; L.prev_depth = (const float*)r[4]->ptr; L.prev_history = r[5]->ptr; L.prev_moments = r[6]->ptr;
+    L.out = r[7]->ptr; L.history = r[8]->ptr; L.moments = r[9]->ptr;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_temporal(c->stream, L);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -2253,9 +2311,10 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
     if (!strcmp(pass_name, "spherical_harmonic_conversion")) return pass_sh_conversion(c, x, y, z, bindings, n_bindings);
     if (!strcmp(pass_name, "interpolate_probes")) return pass_interpolate_probes(c, &g, x, y, z, bindings, n_bindings);
     if (!strcmp(pass_name, "denoise")) return pass_denoise(c, &g, x, y, z, bindings, n_bindings);
+    if (!strcmp(pass_name, "temporal")) return pass_temporal(c, &g, x, y, z, bindings, n_bindings);
     return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name +
                                       "' (known: gbuffer, refrence_mode, postprocess, structured_importance_sampling, trace_probes, "
-                                      "spherical_harmonic_conversion, interpolate_probes, denoise)");
+                                      "spherical_harmonic_conversion, interpolate_probes, denoise, temporal)");
 }
 int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
     if (!c) return RT3_E_INVALID;
@@ -2269,6 +2328,37 @@ int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
         return fail(c, RT3_E_INVALID, "denoise params: sigma_z and sigma_l must be finite and positive");
     if (p->flags & ~RT3_DENOISE_NO_DEMODULATION) return fail(c, RT3_E_INVALID, "denoise params: unknown flag bits");
     c->dn_params = *p;
+    return RT3_OK;
+}
+int rt3_denoise_set_variance_input(rt3_ctx* c, uint32_t moments_image) {
+    if (!c) return RT3_E_INVALID;
+    c->dn_variance_image = moments_image;  // checked when "denoise" is launched: the image may be created, resized or destroyed in between
+    return RT3_OK;
+}
+int rt3_temporal_set_prev_view(rt3_ctx* c, const void* prev_gconst, size_t size) {
+    if (!c) return RT3_E_INVALID;
+    if (!prev_gconst && size == 0) {
+        c->tp_has_prev = false;
+        return RT3_OK;
+    }
+    if (!prev_gconst || size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "temporal prev view: must be the 304-byte GConst block of the previous frame, or (NULL, 0)");
+    memcpy(&c->tp_prev, prev_gconst, sizeof(rt3_gconst));
+    c->tp_has_prev = true;
+    return RT3_OK;
+}
+int rt3_temporal_set_params(rt3_ctx* c, const rt3_temporal_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->tp_params = kTemporalDefaults;
+        return RT3_OK;
+    }
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
+        return fail(c, RT3_E_INVALID, "temporal params: alpha and alpha_moments must lie in [0, 1]");
+    if (p->max_history < 1 || p->max_history > 65535) return fail(c, RT3_E_INVALID, "temporal params: max_history must be 1..65535");
+    if (!(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f)) return fail(c, RT3_E_INVALID, "temporal params: normal_cos must lie in [-1, 1]");
+    if (!(std::isfinite(p->plane_tolerance) && p->plane_tolerance > 0.0f)) return fail(c, RT3_E_INVALID, "temporal params: plane_tolerance must be finite and positive");
+    if (p->flags & ~RT3_TEMPORAL_NO_DEMODULATION) return fail(c, RT3_E_INVALID, "temporal params: unknown flag bits");
+    c->tp_params = *p;
     return RT3_OK;
 }
 int rt3_frame_wait(rt3_ctx* c) {

@@ -2,7 +2,8 @@
 // low-sample radiance image.  No reference counterpart (the reference has no spatial filter); DESIGN.md section 4f.
 //
 //   k_dn_prepare  -> per-pixel records: guide {P.xyz, foreground}, {n.xyz, 0} and signal {c.rgb, 0}, c = (In - emission) / max(albedo, 1/256)
-//   k_dn_variance -> signal.w = spatial variance of luminance(c) over 7 x 7, weighted by w_n * w_z
+//   k_dn_variance -> signal.w = spatial variance of luminance(c) over 7 x 7, weighted by w_n * w_z (or the temporal variance of the
+//                    "temporal" pass where its history is at least 4 frames long: rt3_denoise_set_variance_input)
 //   k_dn_atrous   -> one iteration at step 2^i: 5 x 5 B3-spline taps weighted by h * w_n * expn(x_z + x_l); ping-pong between two signal images
 //   k_dn_finish   -> Out = emission + c * albedo (alpha and background pixels: In, bit for bit)
 //
@@ -17,17 +18,14 @@
 // it loses (197 us: the border is 3.5 x the tile), so steps >= 4 read through the caches.
 #include <hip/hip_runtime.h>
 
-#include "rt3_device.hpp"
+#include "rt3_filter_device.hpp"
 #include "rt3_internal.hpp"
 
 namespace rt3 {
 
 namespace {
 
-constexpr int kDnTileX = 32, kDnTileY = 8;  // one 256-thread workgroup; a wave covers two 32-pixel rows (512 B per record stream and row)
-constexpr float kDnTinyR = 1e-20f, kDnTinyL = 1e-6f, kDnAlbedoFloor = 1.0f / 256.0f;
-
-RT3_DEV float dn_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+constexpr float kDnTinyR = 1e-20f, kDnTinyL = 1e-6f;  // the tile, the modulation and the luminance: rt3_filter_device.hpp
 
 struct DnCentre {
     V3 P, n;
@@ -58,18 +56,14 @@ __global__ __launch_bounds__(256) void k_dn_prepare(GConstDev g, uint32_t W, uin
     }
     const uint4 w = gbuffer[pi];
     const float4 L = in[pi];
-    V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
-    if (!(flags & 1u)) {
-        const V3 a = unpack_color_888(w.x);
-        m = v3(a.x > kDnAlbedoFloor ? a.x : kDnAlbedoFloor, a.y > kDnAlbedoFloor ? a.y : kDnAlbedoFloor, a.z > kDnAlbedoFloor ? a.z : kDnAlbedoFloor);
-        e = rgb9e5_to_float3(w.w);
-    }
+    V3 m, e;
+    dn_modulation(flags, w, m, e);
     const V3 n = unpack_normal_11_10_11(w.y);
-    V3 o, d;
-    primary_ray(g, px, py, o, d);
-    gP[pi] = make_float4(o.x + d.x * t, o.y + d.y * t, o.z + d.z * t, 1.0f);
+    const V3 P = dn_position(g, px, py, t);
+    const V3 s = dn_demodulate(L, e, m);
+    gP[pi] = make_float4(P.x, P.y, P.z, 1.0f);
     gN[pi] = make_float4(n.x, n.y, n.z, 0.0f);
-    sig[pi] = make_float4((L.x - e.x) / m.x, (L.y - e.y) / m.y, (L.z - e.z) / m.z, 0.0f);
+    sig[pi] = make_float4(s.x, s.y, s.z, 0.0f);
 }
 
 // The tile of a workgroup and a HALO-wide border of the three record images, staged in LDS (HALO > 0), or the images themselves (HALO = 0:
@@ -109,8 +103,11 @@ struct DnTile {
     DnTile<HALO> tile = {lds_p, lds_n, lds_s, gP, gN, sin, (int)(blockIdx.x * kDnTileX) - HALO, (int)(blockIdx.y * kDnTileY) - HALO, W}; \
     tile.stage(H)
 
+// TEMPORAL: the "temporal" pass's Moments image {mu1, mu2, variance, N} overrides the spatial estimate where N >= 4 (SVGF's rule)
+template <bool TEMPORAL>
 __global__ __launch_bounds__(256) void k_dn_variance(uint32_t W, uint32_t H, uint32_t squarings, float inv_sigma_z, const float4* __restrict__ gP,
-                                                     const float4* __restrict__ gN, const float4* __restrict__ sin, float4* __restrict__ sout) {
+                                                     const float4* __restrict__ gN, const float4* __restrict__ sin, float4* __restrict__ sout,
+                                                     const float4* __restrict__ moments) {
     RT3_DN_TILE(3);
     const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
     if (px >= W || py >= H) return;
@@ -144,6 +141,10 @@ __global__ __launch_bounds__(256) void k_dn_variance(uint32_t W, uint32_t H, uin
     const float mu1 = s1 / s0;
     const float d = s2 / s0 - mu1 * mu1;
     c.w = d > 0.0f ? d : 0.0f;
+    if constexpr (TEMPORAL) {
+        const float4 mo = moments[pi];
+        if (mo.w >= 4.0f) c.w = mo.z;
+    }
     sout[pi] = c;
 }
 
@@ -215,16 +216,12 @@ __global__ __launch_bounds__(256) void k_dn_finish(uint32_t W, uint32_t H, uint3
     float4 L = in[pi];
     if (depth[pi] != kBackgroundDepth) {
         const float4 c = sig[pi];
-        V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
-        if (!(flags & 1u)) {
-            const uint4 w = gbuffer[pi];
-            const V3 a = unpack_color_888(w.x);
-            m = v3(a.x > kDnAlbedoFloor ? a.x : kDnAlbedoFloor, a.y > kDnAlbedoFloor ? a.y : kDnAlbedoFloor, a.z > kDnAlbedoFloor ? a.z : kDnAlbedoFloor);
-            e = rgb9e5_to_float3(w.w);
-        }
-        L.x = e.x + c.x * m.x;
-        L.y = e.y + c.y * m.y;
-        L.z = e.z + c.z * m.z;
+        V3 m, e;
+        dn_modulation(flags, gbuffer[pi], m, e);
+        const V3 r = dn_modulate(v3(c.x, c.y, c.z), e, m);
+        L.x = r.x;
+        L.y = r.y;
+        L.z = r.z;
     }
     out[pi] = L;
 }
@@ -233,8 +230,6 @@ __global__ void k_selftest_expn(const uint32_t* __restrict__ in, uint32_t n, uin
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = __float_as_uint(expn(__uint_as_float(in[i])));
 }
-
-dim3 dn_grid(uint32_t W, uint32_t H) { return dim3((W + kDnTileX - 1) / kDnTileX, (H + kDnTileY - 1) / kDnTileY); }
 
 }  // namespace
 
@@ -248,8 +243,9 @@ void launch_denoise_prepare(hipStream_t st, const DenoiseLaunch& L) {
                        (const float4*)L.in, L.s.gP, L.s.gN, L.s.sig[0]);
 }
 void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L) {
-    hipLaunchKernelGGL(k_dn_variance, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.squarings, 1.0f / L.sigma_z, L.s.gP, L.s.gN,
-                       L.s.sig[0], L.s.sig[1]);
+    auto k = L.moments ? k_dn_variance<true> : k_dn_variance<false>;
+    hipLaunchKernelGGL(k, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.squarings, 1.0f / L.sigma_z, L.s.gP, L.s.gN, L.s.sig[0],
+                       L.s.sig[1], (const float4*)L.moments);
 }
 void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iteration) {
     const uint32_t step = 1u << iteration;

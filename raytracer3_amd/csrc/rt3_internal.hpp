@@ -306,6 +306,7 @@ struct DenoiseLaunch {
     const float* depth;
     const void* in;
     void* out;
+    const void* moments = nullptr;  // rt3_denoise_set_variance_input: the "temporal" pass's Moments image, or none
     DenoiseScratch s;
 };
 void denoise_plan(uint32_t W, uint32_t H, BufLayout& plan, DenoiseScratch* s);
@@ -314,6 +315,18 @@ void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L);
 void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iteration);
 void launch_denoise_finish(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
 void launch_selftest_denoise(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);  // selftest op 28: expn
+
+// "temporal" pass (rt3_temporal.hip): one kernel, one thread per pixel, no scratch.  `prev` is the previous frame's
+// GConst (rt3_temporal_set_prev_view), captured by value like `g`.
+struct TemporalLaunch {
+    GConstDev g, prev;
+    uint32_t W, H, flags;
+    float alpha, alpha_moments, max_history, normal_cos, plane_tolerance;
+    const void *gbuffer, *in, *prev_gbuffer, *prev_history, *prev_moments;
+    const float *depth, *prev_depth;
+    void *out, *history, *moments;
+};
+void launch_temporal(hipStream_t st, const TemporalLaunch& L);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

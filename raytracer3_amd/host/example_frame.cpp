@@ -2,12 +2,16 @@
 // It is the analogue of `renderer::commands` (src/renderer/mod.rs:65-106) for the three path-tracing passes:
 // reads a scene dump, describes one frame with the builder chain, runs it and writes Light (RGBA32F) + colour.
 //
-//   example_frame scene.bin W H spp bounces flags frame out.bin [probes | denoise]
+//   example_frame scene.bin W H spp bounces flags frame out.bin [probes | denoise | temporal]
 // With the trailing word `probes` the frame is the probe-GI chain of the old shaders instead (gbuffer ->
 // structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes) and
 // out.bin holds Light followed by the probe atlas.
 // With the trailing word `denoise` (single process only) the node ComputePass "denoise" (the library's a-trous filter)
 // sits between refrence_mode and postprocess, which then tone-maps the filtered image; out.bin holds Light, colour, then the filtered image.
+// With the trailing word `temporal` (single process only) two frames are rendered through gbuffer -> refrence_mode -> ComputePass "temporal"
+// (the library's reprojected accumulation) -> postprocess: frame `frame` from the camera of the scene file, which
+// starts from zeroed history, and frame `frame` + 1 with the camera moved by position + (0.02, 0, 0.01), direction + (0, 0, 0.012), which
+// reprojects the first.  out.bin holds the second frame's Light, colour and accumulated image, then the first frame's Light.
 // Multi-GPU (one process per GPU, like `bench.py --gpus N`): with RT3_RANKS = n > 0 in the environment this process is rank RT3_RANK of n on
 // device RT3_DEVICE (default: the rank), renders its 64x64 tiles and joins the frame's ONE collective, rt3_gather_tiles; rank 0 creates the
 // RCCL id and hands it to the others through the file RT3_UID_FILE (the C ABI opens no channel of its own) and writes out.bin.
@@ -32,8 +36,9 @@ static std::vector<T> read_vec(FILE* f, size_t n) {
 int main(int argc, char** argv) {
     const bool probes = argc == 10 && std::string(argv[9]) == "probes";
     const bool denoise = argc == 10 && std::string(argv[9]) == "denoise";
-    if (argc != 9 && !probes && !denoise) {
-        fprintf(stderr, "usage: %s scene.bin W H spp bounces flags frame out.bin [probes | denoise]\n", argv[0]);
+    const bool temporal = argc == 10 && std::string(argv[9]) == "temporal";
+    if (argc != 9 && !probes && !denoise && !temporal) {
+        fprintf(stderr, "usage: %s scene.bin W H spp bounces flags frame out.bin [probes | denoise | temporal]\n", argv[0]);
         return 2;
     }
     try {
@@ -148,6 +153,65 @@ int main(int argc, char** argv) {
             fwrite(at.data(), 4, at.size(), o);
             fclose(o);
             printf("example_frame: probe-GI frame %ux%u, %ux%u probes\n", W, H, px, py);
+            return 0;
+        }
+        if (temporal) {
+            if (n_ranks) throw std::runtime_error("temporal: a reprojected tap may belong to another rank; accumulate the gathered frame on one rank");
+            const auto full = rt3::ImageSize::FullScreen();
+            const uint32_t f4 = RT3_FORMAT_R32G32B32A32_SFLOAT;
+            const char* swaps[4][2] = {{"gbuffer", "PrevGbuffer"}, {"gbuffer_depth", "PrevDepth"}, {"History", "PrevHistory"}, {"Moments", "PrevMoments"}};
+            std::vector<float> first((size_t)W * H * 4), zero((size_t)W * H * 4, 0.0f);
+            rt3_gconst prev_view = gconst;
+            rt3::ResourceHandle light = 0, color = 0, acc = 0;
+            for (int k = 0; k < 2; k++) {
+                if (k) {  // the second frame: the camera moves, and what the first wrote becomes Prev*
+                    rt3::Camera moved = camera;
+                    moved.position[0] += 0.02f; moved.position[2] += 0.01f; moved.direction[2] += 0.012f;
+                    const rt3_gconst first_view = gconst;
+                    gconst = moved.gconst(W, H);
+                    gconst.samples = first_view.samples; gconst.bounces = first_view.bounces; gconst.pad[0] = first_view.pad[0];
+                    gconst.frame = first_view.frame + 1; gconst.blendfactor = 1.0f;
+                    prev_view = first_view;
+                    for (auto& s : swaps) rg.swap_names(s[0], s[1]);
+                    ctx.check(rt3_resource_download(ctx.raw(), light, first.data(), first.size() * 4), "download");
+                }
+                rg.begin_frame();
+                auto gbuffer = rg.image(full, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
+                auto depth = rg.image(full, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
+                auto pgb = rg.image(full, RT3_FORMAT_R32G32B32A32_UINT, "PrevGbuffer");
+                auto pdepth = rg.image(full, RT3_FORMAT_R32_SFLOAT, "PrevDepth");
+                auto phist = rg.image(full, f4, "PrevHistory"), pmom = rg.image(full, f4, "PrevMoments");
+                auto hist = rg.image(full, f4, "History"), mom = rg.image(full, f4, "Moments");
+                light = rg.image(full, f4, "Light");
+                auto prev = rg.image(full, f4, "PrevLight");
+                color = rg.image(full, f4, "color");
+                acc = rg.image(full, f4, "accumulated");
+                if (!k) {  // the reset rule: zeroed previous images mean "no history"
+                    ctx.check(rt3_resource_upload(ctx.raw(), phist, zero.data(), zero.size() * 4), "upload");
+                    ctx.check(rt3_resource_upload(ctx.raw(), pmom, zero.data(), zero.size() * 4), "upload");
+                }
+                ctx.set_prev_view(&prev_view);
+                auto gb = rt3::RayTracingPass::New(rg, "gbuffer").shader("gbuffer").constants(gconst)
+                              .write(rt3::IMPORTED, gbuffer).write(rt3::IMPORTED, depth).launch(rt3::WorkSize2D::FullScreen());
+                auto pt = rt3::RayTracingPass::New(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
+                              .read(gb, gbuffer).read(gb, depth).write(rt3::IMPORTED, light).read(rt3::IMPORTED, prev).launch(rt3::WorkSize2D::FullScreen());
+                auto tp = rt3::ComputePass::New(rg, "temporal").shader("temporal").constants(gconst)
+                              .read(gb, gbuffer).read(gb, depth).read(pt, light).read(rt3::IMPORTED, pgb).read(rt3::IMPORTED, pdepth)
+                              .read(rt3::IMPORTED, phist).read(rt3::IMPORTED, pmom).write(rt3::IMPORTED, acc).write(rt3::IMPORTED, hist)
+                              .write(rt3::IMPORTED, mom).dispatch(rt3::DispatchSize::FullScreen());
+                rt3::ComputePass::New(rg, "postprocess").shader("postprocess").constants(gconst)
+                    .read(gb, depth).write(rt3::IMPORTED, color).read(tp, acc).dispatch(rt3::DispatchSize::FullScreen());
+                rg.draw_frame(color);
+            }
+            std::vector<float> img((size_t)W * H * 4);
+            FILE* o = fopen(argv[8], "wb");
+            for (auto h : {light, color, acc}) {
+                ctx.check(rt3_resource_download(ctx.raw(), h, img.data(), img.size() * 4), "download");
+                fwrite(img.data(), 4, img.size(), o);
+            }
+            fwrite(first.data(), 4, first.size(), o);
+            fclose(o);
+            printf("example_frame: two temporal frames %ux%u, %llu frames drawn\n", W, H, (unsigned long long)rg.frame_number);
             return 0;
         }
         auto gbuffer = rg.image(rt3::ImageSize::FullScreen(), RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");

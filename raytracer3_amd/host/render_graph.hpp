@@ -93,6 +93,11 @@ class Context {
     }
     // parameters of ComputePass "denoise" (rt3_denoise_set_params; no reference counterpart); nullptr = the defaults
     void set_denoise_params(const rt3_denoise_params* p) const { check(rt3_denoise_set_params(ctx_, p), "rt3_denoise_set_params"); }
+    // ComputePass "temporal" (no reference counterpart): its parameters (nullptr = the defaults), the previous frame's GConst (nullptr forgets
+    // it), and the Moments image whose variance "denoise" starts from (0 = none)
+    void set_temporal_params(const rt3_temporal_params* p) const { check(rt3_temporal_set_params(ctx_, p), "rt3_temporal_set_params"); }
+    void set_prev_view(const rt3_gconst* prev) const { check(rt3_temporal_set_prev_view(ctx_, prev, prev ? sizeof(*prev) : 0), "rt3_temporal_set_prev_view"); }
+    void set_denoise_variance_input(uint32_t moments_image) const { check(rt3_denoise_set_variance_input(ctx_, moments_image), "rt3_denoise_set_variance_input"); }
 
    private:
     rt3_ctx* ctx_ = nullptr;
@@ -135,6 +140,8 @@ class RenderGraph {
         return named_[name] = h;
     }
     void begin_frame() { nodes.clear(); }  // mod.rs:656-686
+    // two resources trade names: what one frame wrote as `a` the next one reads as `b` (history images of ComputePass "temporal")
+    void swap_names(const std::string& a, const std::string& b) { std::swap(named_.at(a), named_.at(b)); }
 
     std::vector<NodeHandle> bake(NodeHandle root) const {  // bake.rs:29-49
         std::vector<NodeHandle> order, out;

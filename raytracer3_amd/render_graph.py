@@ -288,6 +288,23 @@ class Context:
             params = L.DenoiseParams(**kw)
         self.check(self.lib.rt3_denoise_set_params(self.h, C.byref(params) if params is not None else None))
 
+    def set_denoise_variance_input(self, moments_image=0):
+        """the "temporal" pass's Moments image whose variance "denoise" starts from (rt3_denoise_set_variance_input); 0 = none"""
+        self.check(self.lib.rt3_denoise_set_variance_input(self.h, int(moments_image)))
+
+    def set_temporal_params(self, params=None, **kw):
+        """parameters of the "temporal" pass (rt3_temporal_set_params): an L.TemporalParams, or its fields as keywords; nothing = the defaults"""
+        if params is None and kw:
+            params = L.TemporalParams(**kw)
+        self.check(self.lib.rt3_temporal_set_params(self.h, C.byref(params) if params is not None else None))
+
+    def set_prev_view(self, gconst=None):
+        """the previous frame's GConst for the "temporal" pass (rt3_temporal_set_prev_view); None forgets it"""
+        if gconst is None:
+            self.check(self.lib.rt3_temporal_set_prev_view(self.h, None, 0))
+        else:
+            self.check(self.lib.rt3_temporal_set_prev_view(self.h, C.byref(gconst), C.sizeof(gconst)))
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

@@ -5,7 +5,8 @@ Per frame, three passes exactly as the old shaders were wired:
   RayTracingPass("gbuffer")        -> packed G-buffer + depth                 shaders/old/gbuffer.slang
   RayTracingPass("refrence_mode")  -> Light (RGBA32F linear radiance)          shaders/old/refrence_mode.slang
   ComputePass("postprocess")       -> display image (AgX)                      shaders/old/postprocess.slang
-with, on request, ComputePass("denoise") between the last two (no reference counterpart: the a-trous filter of DESIGN.md section 4f),
+with, on request, ComputePass("temporal") and / or ComputePass("denoise") between the last two (no reference counterpart: the reprojected
+accumulation of DESIGN.md section 4g and the a-trous filter of section 4f),
 and, as a second frame description, the probe-GI chain of the old shaders (`probe_commands`):
   gbuffer -> structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes
 """
@@ -46,9 +47,10 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
-def frame_nodes(rg, gconst, postprocess=True, denoise=False):
+def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
-    `denoise`, the "denoise" node filters `Light` into `denoised` and postprocess reads that instead."""
+    `temporal`, the "temporal" node accumulates `Light` with the reprojected history into `accumulated`; with `denoise`, the "denoise"
+    node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them."""
     gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
     depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
     light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
@@ -60,8 +62,12 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False):
     pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
           .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
     src, lit = pt, light
+    if temporal:
+        src, th = temporal_node(rg, gconst, gb, gbuffer, depth, pt, light)
+        handles.update(th)
+        lit = th["accumulated"]
     if denoise:
-        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, pt, light)
+        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit)
         handles["denoised"] = lit
     if postprocess:
         (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
@@ -77,6 +83,28 @@ def denoise_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
     return dn, denoised
 
 
+TEMPORAL_SWAPS = (("History", "PrevHistory"), ("Moments", "PrevMoments"))
+
+
+def temporal_images(rg):
+    """the images of the "temporal" pass besides this frame's: the previous frame's G-buffer, depth, History, Moments and the three written"""
+    f4, full = L.FORMAT_R32G32B32A32_SFLOAT, ImageSize.FullScreen
+    return dict(prev_gbuffer=rg.image(full, L.FORMAT_R32G32B32A32_UINT, "PrevGbuffer"), prev_depth=rg.image(full, L.FORMAT_R32_SFLOAT, "PrevDepth"),
+                prev_history=rg.image(full, f4, "PrevHistory"), prev_moments=rg.image(full, f4, "PrevMoments"),
+                accumulated=rg.image(full, f4, "accumulated"), history=rg.image(full, f4, "History"), moments=rg.image(full, f4, "Moments"))
+
+
+def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
+    """ComputePass("temporal"): {gbuffer, gbuffer_depth, In = `light`, PrevGbuffer, PrevDepth, PrevHistory, PrevMoments, Out = `accumulated`,
+    History, Moments}.  The previous view is context state (ctx.set_prev_view).  Returns (node, the handles of temporal_images)."""
+    t = temporal_images(rg)
+    tn = (ComputePass.new(rg, "temporal").shader("temporal").constants(gconst)
+          .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light)
+          .read(IMPORTED, t["prev_gbuffer"]).read(IMPORTED, t["prev_depth"]).read(IMPORTED, t["prev_history"]).read(IMPORTED, t["prev_moments"])
+          .write(IMPORTED, t["accumulated"]).write(IMPORTED, t["history"]).write(IMPORTED, t["moments"]).dispatch(DispatchSize.FullScreen))
+    return tn, t
+
+
 class PathTracer:
     """One GPU's share of the frame.  `rank` / `n_ranks` select the interleaved 64x64 tiles this process renders."""
 
@@ -90,6 +118,7 @@ class PathTracer:
         self.comm_ready = False  # True once init_comm() has joined librt3's RCCL communicator
         self._stage = None       # rehearsal path only: staging buffer of the host-moved gather
         self.host_group = None   # process group of the host-moved gather (None = the default group)
+        self._prev_gconst = None  # "temporal": the view of the frame whose G-buffer / History / Moments the images hold; None = no history
 
     def close(self):
         self.ctx.close()
@@ -101,6 +130,38 @@ class PathTracer:
         if bluenoise is not None:
             self.ctx.set_bluenoise(bluenoise)
         self._accel = self.ctx.build_accel()
+        self.reset_history()
+
+    def reset_history(self):
+        """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
+        self._prev_gconst = None
+
+    def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth")):
+        """Before a temporal frame's nodes are built: what the last temporal frame wrote, and the G-buffer it read (the images named
+        `gbuffer_names`), become `Prev*` (the images trade names, like swap_light_prev), or, with no history, zeros are uploaded; the
+        previous view and the variance input of "denoise" are set.  A frame rendered without `temporal` in between overwrites the kept
+        G-buffer: call reset_history() after one."""
+        rg = self.rg
+        temporal_images(rg)
+        for name, fmt in zip(gbuffer_names, (L.FORMAT_R32G32B32A32_UINT, L.FORMAT_R32_SFLOAT)):
+            rg.image(ImageSize.FullScreen, fmt, name)
+        if self._prev_gconst is not None:
+            n = rg.named
+            for a, b in TEMPORAL_SWAPS + ((gbuffer_names[0], "PrevGbuffer"), (gbuffer_names[1], "PrevDepth")):
+                n[a], n[b] = n[b], n[a]
+        t = temporal_images(rg)
+        if self._prev_gconst is None:
+            W, H = self.window
+            zero = np.zeros((H, W, 4), np.float32)
+            rg.upload(t["prev_history"], zero)
+            rg.upload(t["prev_moments"], zero)
+        self.ctx.set_prev_view(self._prev_gconst if self._prev_gconst is not None else gconst)
+        self.ctx.set_denoise_variance_input(t["moments"] if denoise else 0)
+
+    def _end_temporal(self, gconst):
+        keep = L.GConst()
+        C.memmove(C.byref(keep), C.byref(gconst), C.sizeof(keep))
+        self._prev_gconst = keep
 
     def update_vertices(self, vertices, first=0):
         """deformed vertices (same topology): upload them and refit the acceleration structure"""
@@ -113,28 +174,44 @@ class PathTracer:
         g.pad[0] = flags
         return g
 
-    def commands(self, gconst: L.GConst, postprocess=True, denoise=False):
-        """Build this frame's nodes (frame_nodes).  `denoise` needs the whole window on this rank: with several ranks use denoise()."""
+    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False):
+        """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
+        denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""
         self.rg.begin_frame()
-        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise)
+        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal)
         return self.handles
 
-    def denoise(self, gconst, wait=True):
+    def denoise(self, gconst, wait=True, temporal=False, denoise=True):
         """Filter the `Light` of the last render() into `denoised` with the "denoise" pass (parameters: ctx.set_denoise_params).  A tap
         reads pixels of other tiles, so with several ranks this runs on the rank that holds the assembled frame -- after
         gather_light(..., download=False) on its root -- with the partition switched off around it, like render_probes: the G-buffer is
-        rendered again for the whole window (primary rays only), then the gathered `Light` is filtered.  Returns the handles."""
+        rendered again for the whole window (primary rays only), then the gathered `Light` is filtered.  Returns the handles.
+        With `temporal` the "temporal" pass runs first on the same footing (history as in render(temporal=True); call it once per
+        frame; the whole-window G-buffer is rendered into images of its own, which render() does not touch, on one rank too) and
+        "denoise" -- unless `denoise` is False -- filters its `accumulated` image with the temporal variance."""
         rg = self.rg
+        names = ("TemporalGbuffer", "TemporalDepth") if temporal else ("gbuffer", "gbuffer_depth")  # render() must not overwrite the kept one
+        if temporal:
+            self._begin_temporal(gconst, denoise, names)
+        elif denoise:
+            self.ctx.set_denoise_variance_input(0)
         rg.begin_frame()
-        gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
-        depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
+        gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, names[0])
+        depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, names[1])
         light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
         gb = IMPORTED
-        if self.n_ranks > 1:
+        if self.n_ranks > 1 or temporal:
             gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
                   .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
-        _, denoised = denoise_node(rg, gconst, gb, gbuffer, depth, IMPORTED, light)
-        self.handles = dict(getattr(self, "handles", {}), gbuffer=gbuffer, depth=depth, light=light, denoised=denoised)
+        src, lit, extra = IMPORTED, light, {}
+        if temporal:
+            src, extra = temporal_node(rg, gconst, gb, gbuffer, depth, IMPORTED, light)
+            lit = extra["accumulated"]
+        denoised = lit
+        if denoise:
+            _, denoised = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit)
+            extra = dict(extra, denoised=denoised)
+        self.handles = dict(getattr(self, "handles", {}), gbuffer=gbuffer, depth=depth, light=light, **extra)
         W, H = self.window
         if self.n_ranks > 1:
             self.ctx.set_tile_partition(W, H, 0, 1)
@@ -143,6 +220,8 @@ class PathTracer:
         finally:
             if self.n_ranks > 1:  # launches read the partition when they are enqueued: safe to restore behind them
                 self.ctx.set_tile_partition(W, H, self.rank, self.n_ranks)
+        if temporal:
+            self._end_temporal(gconst)
         return self.handles
 
     def probe_commands(self, gconst: L.GConst):
@@ -196,9 +275,18 @@ class PathTracer:
         W, H = self.window
         self.rg.upload(self.handles["prev_atlas"], self.rg.download(self.handles["atlas"], (H // 16 * 8, W // 16 * 8, 4), np.float32))
 
-    def render(self, gconst, postprocess=False, wait=True, denoise=False):
-        h = self.commands(gconst, postprocess, denoise)
-        self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else h["light"]), wait=wait)
+    def render(self, gconst, postprocess=False, wait=True, denoise=False, temporal=False):
+        """One frame.  `temporal` accumulates it with the reprojected history of the previous temporal frame (this object keeps two sets
+        of history images, the previous G-buffer, depth and GConst, and starts from zeros after set_scene / reset_history); with
+        `denoise` too, the filter reads the accumulated image and its temporal variance.  One rank only: see denoise()."""
+        if temporal:
+            self._begin_temporal(gconst, denoise)
+        elif denoise:
+            self.ctx.set_denoise_variance_input(0)
+        h = self.commands(gconst, postprocess, denoise, temporal)
+        self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
+        if temporal:
+            self._end_temporal(gconst)
         return h
 
     # ---- results
@@ -213,6 +301,16 @@ class PathTracer:
     def denoised(self):
         W, H = self.window
         return self.rg.download(self.handles["denoised"], (H, W, 4), np.float32)
+
+    def accumulated(self):
+        """Out of the "temporal" pass"""
+        W, H = self.window
+        return self.rg.download(self.handles["accumulated"], (H, W, 4), np.float32)
+
+    def history(self):
+        """(History, Moments) of the "temporal" pass"""
+        W, H = self.window
+        return self.rg.download(self.handles["history"], (H, W, 4), np.float32), self.rg.download(self.handles["moments"], (H, W, 4), np.float32)
 
     def gbuffer(self):
         W, H = self.window

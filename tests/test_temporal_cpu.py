@@ -1,0 +1,382 @@
+"""The "temporal" pass, CPU half: tests/ref_temporal.py -- the numpy float32 restatement the GPU pass must equal
+bit for bit (tests/test_temporal.py) -- is pinned here by what reprojected accumulation owes its user, on oracle frames: without history it
+is the identity; under a static camera it accumulates K samples; under a moving camera it beats both one sample and the PrevLight blend
+it replaces; it never mixes surfaces that the normal or the plane test tells apart; its moments are the running mean and mean square; the
+a-trous filter starts from its variance; and the Python frame graph places the node where the header says."""
+import ctypes as C
+import math
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import orc
+import ref_denoise as rd
+import ref_temporal as rt
+from raytracer3_amd import _lib as L
+from raytracer3_amd import assets, scenes
+from raytracer3_amd.assets import Material, MeshBuilder
+from raytracer3_amd.render_graph import RenderGraph
+
+U = 2.0 ** -24  # unit roundoff of float32
+BG = np.float32(orc.BACKGROUND_DEPTH)
+F = np.float32
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def gamma(n):
+    """Higham's gamma_n = n u / (1 - n u): the relative error bound of n chained float32 roundings"""
+    return n * U / (1 - n * U)
+
+
+def rmse_fg(a, ref, fg):
+    return float(np.sqrt((((a[..., :3].astype(np.float64) - ref[..., :3].astype(np.float64))[fg]) ** 2).mean()))
+
+
+def zeros(H, W):
+    return np.zeros((H, W, 4), F)
+
+
+# ------------------------------------------------------------------------------------------------ the two oracle cases
+class Case:
+    def __init__(self, name):
+        self.name = name
+        if name == "cornell":
+            self.W, self.H, self.cam, self.ref_spp = 128, 128, scenes.CORNELL_CAMERA, 2048
+            self.flags = L.F_FACEFORWARD
+            self.osc = orc.Scene(scenes.cornell())
+            self.move = ((0.01, 0.0, 0.0), (0.0105, 0.0, 0.0))  # per frame: position, direction (about 2 pixels)
+        else:
+            self.W, self.H, self.cam, self.ref_spp = 192, 108, scenes.ATRIUM_CAMERA, 1024
+            self.flags = L.F_NEE_SKY | L.F_BLUENOISE | L.F_SPECULAR | L.F_FACEFORWARD  # 15
+            self.osc = orc.Scene(scenes.atrium(0.25), scenes.sky(512, 256), assets.load_bluenoise())
+            self.move = ((0.02, 0.0, 0.01), (0.0, 0.0, 0.012))
+
+    def gconst(self, step=0, spp=1, frame=1, blendfactor=1.0):
+        pos = np.asarray(self.cam["position"], np.float64) + step * np.asarray(self.move[0])
+        dirn = np.asarray(self.cam["direction"], np.float64) + step * np.asarray(self.move[1])
+        g = orc.camera_gconst(position=pos, direction=dirn, fov_deg=self.cam["fov_deg"], width=self.W, height=self.H)
+        g.bounces, g.samples, g.frame, g.blendfactor = 4, spp, frame, blendfactor
+        g.pad[0] = self.flags
+        return g
+
+    def frame(self, g, prev=None):
+        gb, depth = self.osc.gbuffer(g, threads=16)
+        return gb, depth, self.osc.reference_mode(g, gb, depth, prev=prev, threads=16)[0]
+
+
+def run_sequence(case, steps, **params):
+    """feed K frames of 1 spp (frame = 1..K) through the reference pass; camera step `steps[k]` for frame k"""
+    H, W = case.H, case.W
+    prev = None
+    for k, step in enumerate(steps):
+        g = case.gconst(step, 1, k + 1)
+        gb, depth, light = case.frame(g)
+        if prev is None:
+            prev = (g, gb, depth, zeros(H, W), zeros(H, W))
+        out, hist, mom = rt.temporal(g, gb, depth, light, *prev, **params)
+        prev = (g, gb, depth, hist, mom)
+    return g, gb, depth, light, out, hist, mom
+
+
+# ------------------------------------------------------------------------------------------------ 1. no history is the identity
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_no_history_is_identity(name):
+    case = Case(name)
+    g = case.gconst(0, 1, 3)
+    gb, depth, light = case.frame(g)
+    fg = depth != BG
+    light = light.copy()
+    light[..., 3] = np.random.default_rng(1).random(depth.shape, dtype=F)  # any alpha passes through
+    if (~fg).any():
+        junk = np.array([np.nan, np.inf, -np.inf, -0.0], F)
+        light[~fg] = junk[np.random.default_rng(2).integers(0, 4, ((~fg).sum(), 4))]
+    stages = {}
+    out, hist, mom = rt.temporal(g, gb, depth, light, g, gb, depth, zeros(*depth.shape), zeros(*depth.shape), stages=stages)
+    assert out.dtype == hist.dtype == mom.dtype == F
+    assert np.all(hist[fg][:, 3] == 1) and np.all(mom[fg][:, 3] == 1)
+    assert np.array_equal(bits(hist[..., :3][fg]), bits(stages["c"][fg]))
+    assert np.array_equal(bits(mom[..., 0][fg]), bits(stages["l"][fg])) and np.all(mom[..., 2][fg] == 0)
+    assert np.array_equal(bits(out[..., 3]), bits(light[..., 3]))
+    assert np.array_equal(bits(out[~fg]), bits(light[~fg])) and not hist[~fg].any() and not mom[~fg].any()
+    # Out = e + ((In - e) / m) * m: the subtraction is undone by the addition up to their two roundings, and divide-then-multiply adds two more
+    # relative to |In - e| <= |In| + e: |Out - In| <= gamma_4 (|In| + 2 e)
+    pr = rd.prepare(g, gb, depth, light)
+    bound = gamma(4) * (np.abs(light[..., :3].astype(np.float64)) + 2 * pr["e"])
+    with np.errstate(invalid="ignore"):  # the background holds inf and NaN on purpose
+        err = np.abs(out[..., :3].astype(np.float64) - light[..., :3])
+    print(f"{name}: max |Out - In| / bound = {np.max(err[fg] / np.maximum(bound[fg], 1e-300)):.3f}")
+    assert np.all(err[fg] <= bound[fg])
+
+
+# ------------------------------------------------------------------------------------------------ 2. a static camera accumulates
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_static_camera_accumulates(name):
+    """K = 16 frames of 1 spp, plain running mean.  Foreground RMSE against a converged oracle frame (another seed) must not exceed that of
+    the oracle's own K/2-spp frame; N == K on at least 95 % of the foreground.  Measured: cornell 0.3336 against
+    0.469 allowed (oracle 16 spp: 0.333), N == K on 100 %; atrium 0.0882 against 0.124 (oracle 16 spp: 0.0884), N == K on 98.8 %."""
+    case, K = Case(name), 16
+    g, gb, depth, light, out, hist, mom = run_sequence(case, [0] * K, alpha=0.0, alpha_moments=0.0, max_history=K)
+    fg = depth != BG
+    ref = case.frame(case.gconst(0, case.ref_spp, 1000))[2]
+    half = case.frame(case.gconst(0, K // 2, 7))[2]
+    full = case.frame(case.gconst(0, K, 7))[2]
+    e, e_half, e_full, e_1 = rmse_fg(out, ref, fg), rmse_fg(half, ref, fg), rmse_fg(full, ref, fg), rmse_fg(light, ref, fg)
+    n_full = float((hist[..., 3][fg] == K).mean())
+    print(f"{name} static K={K}: 1 spp {e_1:.4f}, temporal {e:.4f}, oracle {K // 2} spp {e_half:.4f}, oracle {K} spp {e_full:.4f}, N == K on {100 * n_full:.1f} %")
+    assert e <= e_half
+    assert n_full >= 0.95
+    assert np.array_equal(bits(hist[..., 3]), bits(mom[..., 3]))
+
+
+# ------------------------------------------------------------------------------------------------ 3. a moving camera
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_moving_camera_beats_one_sample_and_the_prevlight_blend(name):
+    """K = 8 frames, about 2 pixels of motion per frame, default parameters.  Measured: cornell 0.422 against 1.314
+    (1 spp) and 1.186 (PrevLight blend 0.2), N >= K/2 on 93.1 %; atrium 0.113 against 0.387 and 0.214, N >= K/2 on 95.6 %."""
+    case, K = Case(name), 8
+    g, gb, depth, light, out, hist, mom = run_sequence(case, list(range(K)))
+    fg = depth != BG
+    ref = case.frame(case.gconst(K - 1, case.ref_spp, 1000))[2]
+    # the mechanism this pass replaces: refrence_mode's lerp(PrevLight, radiance, 0.2) of pixel (x, y) with pixel (x, y)
+    blend = None
+    for k in range(K):
+        blend = case.frame(case.gconst(k, 1, k + 1, blendfactor=1.0 if k == 0 else 0.2), prev=blend)[2]
+    e, e_1, e_blend = rmse_fg(out, ref, fg), rmse_fg(light, ref, fg), rmse_fg(blend, ref, fg)
+    N = hist[..., 3]
+    aged = float((N[fg] >= K / 2).mean())
+    print(f"{name} moving K={K}: 1 spp {e_1:.4f}, PrevLight blend {e_blend:.4f}, temporal {e:.4f}, N >= K/2 on {100 * aged:.1f} %, "
+          f"N == K on {100 * float((N[fg] == K).mean()):.1f} %")
+    assert e < e_1 and e < e_blend
+    assert aged >= 0.75
+    # pixels whose reprojection falls outside the previous window start over
+    valid, sx, sy = rt.reproject(g, case.gconst(K - 2), rt.positions(g, depth))
+    outside = fg & ~valid
+    assert outside.any() and np.all(N[outside] == 1)
+
+
+# ------------------------------------------------------------------------------------------------ 4. no bleeding, from geometry alone
+def quad(mb, name, origin, du, dv, color):
+    o, du, dv = (np.asarray(a, np.float64) for a in (origin, du, dv))
+    pos = np.array([o, o + du, o + du + dv, o + dv])
+    n = np.cross(du, dv)
+    mb.add(name, pos, np.tile(n / np.linalg.norm(n), (4, 1)), np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float64), [[0, 1, 2], [0, 2, 3]],
+           Material(color))
+
+
+def synthetic(kind, step, W=96, H=80):
+    """G-buffer and depth (the oracle's gbuffer pass) of two quads under the camera of frame `step`, and the surface id per pixel
+    (0 = background, 1, 2).  The camera slides sideways, which uncovers part of the surface behind the nearer one."""
+    mb = MeshBuilder()
+    if kind == "corner":  # a floor meeting a wall at a right angle: told apart by the normal test
+        quad(mb, "floor", [-1.6, 0, 2], [3.0, 0, 0], [0, 0, -4], (0.8, 0.2, 0.2))
+        quad(mb, "wall", [-1.6, 0, -2], [3.0, 0, 0], [0, 1.8, 0], (0.2, 0.8, 0.2))
+        cam = dict(position=(0.3 + 0.05 * step, 1.2 + 0.04 * step, 3.0), direction=(-0.05, -0.25, -1.0), fov_deg=50.0)
+    else:  # two parallel quads at different depths, the near one covering part of the far one: told apart by the plane test
+        quad(mb, "far", [-4, -2, -2], [8, 0, 0], [0, 5, 0], (0.8, 0.2, 0.2))
+        quad(mb, "near", [-0.6, 0.5, 0], [1.3, 0, 0], [0, 1.1, 0], (0.2, 0.8, 0.2))
+        cam = dict(position=(0.1 + 0.25 * step, 1.0, 3.0), direction=(0.02, 0.01, -1.0), fov_deg=50.0)
+    g = orc.camera_gconst(width=W, height=H, **cam)
+    g.pad[0] = L.F_FACEFORWARD
+    gb, depth = orc.Scene(mb.build()).gbuffer(g)
+    words = np.sort(np.unique(gb[depth != BG][:, 0]))
+    assert len(words) == 2  # two albedo words = two surfaces
+    ident = np.where(depth == BG, 0, np.where(gb[..., 0] == words[0], 1, 2))
+    return g, gb, depth, ident
+
+
+# One launch computes h = (sum_k w_k v_k) / (sum_k w_k) over at most four taps with non-negative weights -- a product and at most three
+# additions per term of the numerator (gamma_4), three additions in the denominator (gamma_3), one division: gamma_8 -- and then
+# h + a (c - h): three more roundings.  With every v_k within d of the constant A and c = A exactly, |c_acc - A| <= d + gamma_11 (|A| + d).
+STEP_ROUNDING = gamma(11)
+
+
+def constant_bound(A, launches):
+    d = 0.0
+    for _ in range(launches):
+        d = d + STEP_ROUNDING * (A + d)
+    return d
+
+
+@pytest.mark.parametrize("kind", ["corner", "parallel"])
+def test_no_bleeding_across_surfaces(kind):
+    const = {0: 0.0, 1: 0.25, 2: 37.0}
+    prev, n_frames = None, 4
+    for step in range(n_frames):
+        g, gb, depth, ident = synthetic(kind, step)
+        H, W = depth.shape
+        light = np.zeros((H, W, 4), F)
+        for s in (1, 2):
+            light[ident == s, :3] = const[s]
+        light[..., 3] = 1.0
+        if prev is None:
+            prev = (g, gb, depth, zeros(H, W), zeros(H, W), ident)
+        stages = {}
+        out, hist, mom = rt.temporal(g, gb, depth, light, *prev[:5], flags=rt.NO_DEMODULATION, stages=stages)
+        if step:
+            # newly uncovered: none of the four taps of the reprojected position lay on this surface in the previous frame
+            pid = np.pad(prev[5], 1)  # index + 1; the border is "outside"
+            x0 = np.where(stages["valid"], np.floor(stages["sx"]), -1).astype(int)
+            y0 = np.where(stages["valid"], np.floor(stages["sy"]), -1).astype(int)
+            same = np.zeros((H, W), bool)
+            for j in (0, 1):
+                for i in (0, 1):
+                    same |= stages["valid"] & (pid[y0 + j + 1, x0 + i + 1] == ident)
+            fresh = (ident != 0) & ~same
+            assert np.all(hist[..., 3][fresh] == 1)
+            behind = fresh & stages["valid"]
+            print(f"{kind} frame {step}: {int(fresh.sum())} fresh pixels, {int(behind.sum())} of them uncovered inside the window")
+            assert behind.any() or kind == "corner"
+        prev = (g, gb, depth, hist, mom, ident)
+    N = hist[..., 3]
+    for s in (1, 2):
+        sel = ident == s
+        err = np.abs(hist[..., :3][sel].astype(np.float64) - const[s]).max()
+        bound = constant_bound(const[s], n_frames)
+        print(f"{kind} surface {s}: max |c_acc - A| = {err:.3e}, bound {bound:.3e}; N up to {N[sel].max():.2f}, N > 1 on {100 * (N[sel] > 1).mean():.1f} %")
+        assert err <= bound
+        assert (N[sel] > 1).mean() > 0.5  # ... and not by throwing the history away
+        assert np.abs(out[..., :3][sel].astype(np.float64) - const[s]).max() <= bound
+    assert not hist[ident == 0].any()
+
+
+# ------------------------------------------------------------------------------------------------ 5. moments, and the filter's variance input
+def test_moments_are_the_running_mean_and_mean_square():
+    """every pixel of a static frame is fed the luminances l_1..l_K (alpha_moments = 0): taps mix equal values, so each pixel is `one pixel`.
+    A launch is a convex combination plus STEP_ROUNDING relative to the largest value, so K launches stay within K STEP_ROUNDING max|v|."""
+    K = 12
+    g, gb, depth, ident = synthetic("corner", 0)
+    H, W = depth.shape
+    fg = depth != BG
+    vals = (np.random.default_rng(5).random(K) * 3 + 0.1).astype(F)
+    prev = (g, gb, depth, zeros(H, W), zeros(H, W))
+    ls = []
+    for v in vals:
+        light = np.full((H, W, 4), v, F)
+        stages = {}
+        out, hist, mom = rt.temporal(g, gb, depth, light, *prev, alpha=0.0, alpha_moments=0.0, max_history=64, flags=rt.NO_DEMODULATION, stages=stages)
+        ls.append(float(stages["l"][fg][0]))
+        assert np.all(stages["l"][fg] == stages["l"][fg][0])
+        prev = (g, gb, depth, hist, mom)
+    ls = np.array(ls, np.float64)
+    interior = fg & (hist[..., 3] == K)
+    assert interior.mean() > 0.5
+    m1, m2 = ls.mean(), (ls ** 2).mean()
+    b1, b2 = K * STEP_ROUNDING * ls.max(), K * STEP_ROUNDING * (ls ** 2).max() * (1 + 2 * U)  # l * l is rounded before it is fed
+    e1, e2 = np.abs(mom[..., 0][interior] - m1).max(), np.abs(mom[..., 1][interior] - m2).max()
+    # variance = max(0, mu2 - mu1 mu1): the errors of mu2 and of mu1 mu1 (2 |mu1| b1 + b1^2 and one rounding) and one more rounding
+    bv = b2 + 2 * ls.max() * b1 + b1 ** 2 + 3 * U * (ls ** 2).max()
+    ev = np.abs(mom[..., 2][interior] - (m2 - m1 * m1)).max()
+    print(f"moments after {K} frames: |mu1 - mean| {e1:.3e} (bound {b1:.3e}), |mu2 - mean sq| {e2:.3e} (bound {b2:.3e}), |var - pop var| {ev:.3e} (bound {bv:.3e})")
+    assert e1 <= b1 and e2 <= b2 and ev <= bv
+    assert np.abs(hist[..., 0][interior] - m1).max() <= b1  # the colour runs the same mean (NO_DEMODULATION: c = In, l ~ In)
+
+
+def test_denoise_starts_from_the_temporal_variance():
+    case, K = Case("cornell"), 6
+    g, gb, depth, light, out, hist, mom = run_sequence(case, list(range(K)))
+    fg = depth != BG
+    old, young = fg & (mom[..., 3] >= 4), fg & (mom[..., 3] < 4)
+    assert old.any() and young.any()
+    plain_stages, st = {}, {}
+    plain = rd.denoise(g, gb, depth, out, stages=plain_stages)  # today's filter
+    with_var = rt.denoise(g, gb, depth, out, moments=mom, stages=st)
+    assert np.array_equal(bits(st["var0"][old]), bits(mom[..., 2][old]))
+    assert np.array_equal(bits(st["var0"][~old]), bits(plain_stages["var0"][~old]))
+    assert np.array_equal(bits(st["var_spatial"]), bits(plain_stages["var0"]))
+    assert not np.array_equal(bits(with_var), bits(plain))
+    # unset, or with a history younger than four frames everywhere, the filter is the one it was: ref_denoise.denoise, bit for bit
+    young_everywhere = mom.copy()
+    young_everywhere[..., 3] = np.minimum(mom[..., 3], 3.5)
+    assert np.array_equal(bits(rt.denoise(g, gb, depth, out, moments=young_everywhere)), bits(plain))
+    assert np.array_equal(bits(rt.denoise(g, gb, depth, out, moments=None)), bits(plain))
+    for kw in (dict(iterations=3, normal_squarings=5, sigma_z=0.1, sigma_l=2.0), dict(iterations=0), dict(flags=rd.NO_DEMODULATION)):
+        assert np.array_equal(bits(rt.denoise(g, gb, depth, out, **kw)), bits(rd.denoise(g, gb, depth, out, **kw)))
+    ref = case.frame(case.gconst(K - 1, case.ref_spp, 1000))[2]
+    print(f"cornell moving K={K}: temporal {rmse_fg(out, ref, fg):.4f}, + denoise (spatial variance) {rmse_fg(plain, ref, fg):.4f}, "
+          f"+ denoise (temporal variance) {rmse_fg(with_var, ref, fg):.4f}")
+
+
+# ------------------------------------------------------------------------------------------------ 6. the Python surface
+class RecordingCtx:
+    """stands in for render_graph.Context: records rt3_pass_launch instead of running it"""
+
+    def __init__(self):
+        self.calls, self.n = [], 0
+        self.lib, self.h = self, None
+
+    def check(self, rc):
+        assert rc == 0
+
+    def rt3_image_create(self, h, w, hh, fmt, out):
+        self.n += 1
+        out._obj.value = (L.TAG_IMAGE << 30) | self.n
+        return 0
+
+    def rt3_pass_launch(self, h, path, entry, x, y, z, cst, size, b, nb):
+        self.calls.append((path.decode(), (x, y, z), [b[i] for i in range(nb)]))
+        return 0
+
+    def wait(self):
+        pass
+
+
+def test_frame_graph_places_the_temporal_node():
+    from raytracer3_amd.renderer import frame_nodes
+
+    W, H = 250, 187
+    ctx = RecordingCtx()
+    rg = RenderGraph(ctx, (W, H))
+    rg.begin_frame()
+    h = frame_nodes(rg, L.GConst(), postprocess=True, temporal=True)
+    rg.draw_frame(h["color"])
+    assert [c[0] for c in ctx.calls] == ["gbuffer", "refrence_mode", "temporal", "postprocess"]
+    tp, pp = ctx.calls[2], ctx.calls[3]
+    assert tp[1] == (math.ceil(W / 8), math.ceil(H / 8), 1) == (32, 24, 1)
+    assert tp[2] == [h["gbuffer"], h["depth"], h["light"], h["prev_gbuffer"], h["prev_depth"], h["prev_history"], h["prev_moments"],
+                     h["accumulated"], h["history"], h["moments"]]
+    assert len(set(tp[2])) == 10 and pp[2] == [h["depth"], h["color"], h["accumulated"]]
+    # temporal + denoise: the filter, then the tone map, read the accumulated image
+    ctx.calls.clear()
+    rg.begin_frame()
+    h = frame_nodes(rg, L.GConst(), postprocess=True, denoise=True, temporal=True)
+    rg.draw_frame(h["color"])
+    assert [c[0] for c in ctx.calls] == ["gbuffer", "refrence_mode", "temporal", "denoise", "postprocess"]
+    assert ctx.calls[3][2] == [h["gbuffer"], h["depth"], h["accumulated"], h["denoised"]]
+    assert ctx.calls[4][2] == [h["depth"], h["color"], h["denoised"]]
+    ctx.calls.clear()
+    rg.begin_frame()
+    h = frame_nodes(rg, L.GConst(), postprocess=False, temporal=True)
+    rg.draw_frame(h["accumulated"])
+    assert [c[0] for c in ctx.calls] == ["gbuffer", "refrence_mode", "temporal"]
+    # default: today's graph, node for node
+    ctx.calls.clear()
+    rg.begin_frame()
+    h = frame_nodes(rg, L.GConst())
+    assert sorted(h) == ["color", "depth", "gbuffer", "light", "prev"]
+    rg.draw_frame(h["color"])
+    assert [c[0] for c in ctx.calls] == ["gbuffer", "refrence_mode", "postprocess"]
+    assert ctx.calls[0][2] == [h["gbuffer"], h["depth"]] and ctx.calls[1][2] == [h["gbuffer"], h["depth"], h["light"], h["prev"]]
+    assert ctx.calls[2][2] == [h["depth"], h["color"], h["light"]] and ctx.calls[2][1] == (32, 24, 1)
+
+
+def test_params_struct_and_exports_match_the_header():
+    p = L.TemporalParams()
+    assert C.sizeof(p) == 24
+    assert (p.max_history, p.flags) == (32, 0)
+    assert (p.alpha, p.alpha_moments, p.normal_cos, p.plane_tolerance) == (F(0.2), F(0.2), F(0.9), F(0.01))
+    assert rt.DEFAULTS == dict(alpha=0.2, alpha_moments=0.2, max_history=32, normal_cos=0.9, plane_tolerance=0.01, flags=0)
+    assert L.TEMPORAL_NO_DEMODULATION == rt.NO_DEMODULATION == 1
+    header = (Path(__file__).resolve().parent.parent / "include" / "rt3.h").read_text()
+    for name in ("rt3_temporal_set_prev_view", "rt3_temporal_set_params", "rt3_denoise_set_variance_input"):
+        assert name in L.EXPORTS and re.search(r"\bint " + name + r"\(", header)
+    body = re.search(r"typedef struct rt3_temporal_params \{(.*?)\} rt3_temporal_params;", header, re.S).group(1)
+    fields = re.findall(r"^\s*(float|uint32_t) (\w+);", body, re.M)
+    assert [f[1] for f in fields] == [f[0] for f in L.TemporalParams._fields_]
+    assert [f[0] for f in fields] == ["float", "float", "uint32_t", "float", "float", "uint32_t"]
+    assert "{0.2, 0.2, 32, 0.9, 0.01, 0}" in header and "#define RT3_TEMPORAL_NO_DEMODULATION 1u" in header
+    assert '"temporal"' in header

@@ -9,6 +9,9 @@
                           the box scenes.cornell_ref() rebuilds from the reference's processed asset; Cycles is not this estimator)
   python tools/render.py --scene atrium --size 1920x1080 --spp 1 --denoise --out atrium_1spp_denoised.png
                          (the a-trous filter of DESIGN.md section 4f between refrence_mode and postprocess; for low sample counts)
+  python tools/render.py --scene atrium --size 1920x1080 --spp 1 --temporal 16 --denoise --out atrium_1spp_temporal.png
+                         (16 frames of 1 spp along a small camera move through the "temporal" pass of DESIGN.md section 4g -- reprojected
+                         accumulation -- and, with --denoise, the a-trous filter fed with its variance; the last frame is written)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--flags", type=int, default=-1)
     ap.add_argument("--denoise", action="store_true", help="filter Light with the 'denoise' pass before the tone map (last pass only)")
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous iterations of --denoise (0..8)")
+    ap.add_argument("--temporal", type=int, default=0, metavar="N",
+                    help="render N frames of --spp along a small camera move through the 'temporal' pass and write the last one (replaces --passes)")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
@@ -71,7 +76,13 @@ def main():
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
     cam = Camera(cam_kw["position"], cam_kw["direction"], math.radians(cam_kw["fov_deg"]), W / H)
     history, t0 = [], time.perf_counter()
-    for p in range(args.passes):
+    for k in range(args.temporal):  # the camera slides and turns by a few pixels per frame; every frame reprojects the one before
+        step = np.float32(k) * np.array([0.02, 0.0, 0.01], np.float32)
+        moved = Camera(cam.position + step, cam.direction + np.float32(k) * np.array([0.0, 0.0, 0.012], np.float32), cam.fov, W / H)
+        g = pt.make_gconst(moved, args.spp, args.bounces, frame=k + 1, flags=flags)
+        last = k == args.temporal - 1
+        pt.render(g, postprocess=last, denoise=args.denoise and last, temporal=True)
+    for p in range(args.passes if not args.temporal else 0):
         g = pt.make_gconst(cam, args.spp, args.bounces, frame=p, blendfactor=1.0 / (p + 1), flags=flags)
         last = p == args.passes - 1
         pt.render(g, postprocess=last, denoise=args.denoise and last)
@@ -87,7 +98,7 @@ def main():
     img8 = (np.clip(color[..., :3], 0, 1) * 255 + 0.5).astype(np.uint8)
     Image.fromarray(img8).save(args.out)
     rays = st.extension_rays + st.shadow_rays
-    print(f"{args.out}: {W}x{H} {args.passes} x {args.spp} spp, {rays / 1e6:.0f} Mrays in {dt:.2f} s ({rays / dt / 1e6:.0f} Mrays/s incl. host), mean radiance {light[..., :3].mean():.4f}")
+    print(f"{args.out}: {W}x{H} {args.temporal or args.passes} x {args.spp} spp, {rays / 1e6:.0f} Mrays in {dt:.2f} s ({rays / dt / 1e6:.0f} Mrays/s incl. host), mean radiance {light[..., :3].mean():.4f}")
     if args.curve:
         ref = history[-1].astype(np.float64)
         curve = [{"spp": (i + 1) * args.spp, "rmse_vs_final": float(np.sqrt(np.mean((h - ref) ** 2)))} for i, h in enumerate(history[:-1])]
