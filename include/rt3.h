@@ -207,6 +207,13 @@ int rt3_scene_set_alpha_cutoffs(rt3_ctx *ctx, const float *cutoffs, uint32_t n);
  *      normalize(M3 * normalize(interpolated)), M3 = upper 3 x 3, as hit_logic.slang:22-23 writes it (no inverse transpose).  Call
  *      before rt3_accel_build; borrowed for the call. ---- */
 int rt3_scene_set_instances(rt3_ctx *ctx, const rt3_instance *instances, uint32_t n);
+/* The previous frame's object -> world matrices (n x 16 floats, column-major), one per instance of the current rt3_scene_set_instances
+ * list, in its order: what the "motion" pass (below) compares the built structure's matrices with.  Validated like an instance's matrix
+ * (finite, last row (0, 0, 0, 1)); a bad matrix returns RT3_E_INVALID and changes nothing.  (NULL, 0) forgets them: every instance counts
+ * as unmoved.  The acceleration structure does not become stale and no build reads the matrices.  n is checked when "motion" is launched:
+ * it must be the instance count of the built structure (1 when no instances were set) or 0, else RT3_E_STATE.  Borrowed for the call; the
+ * device table (64 B per instance) is uploaded when the matrices or the structure changed. */
+int rt3_scene_set_prev_transforms(rt3_ctx *ctx, const float *transforms /* n x 16, column-major */, uint32_t n);
 
 /* ---- acceleration structure: create_acceleration_structure (vulkan/raytracing.rs:88-148) -> GPU LBVH.
  *      Returns the handle (tag 3) in *out_handle, like the TLAS registered at bindless/mod.rs:314-337 ---- */
@@ -302,6 +309,8 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *        "temporal"      (x,y,z)=groups of 8x8 over the window  bindings {gbuffer, gbuffer_depth, In RGBA32F, PrevGbuffer RGBA32UI,
  *                        PrevDepth R32F, PrevHistory RGBA32F, PrevMoments RGBA32F, Out RGBA32F, History RGBA32F, Moments RGBA32F}
  *                        (no reference counterpart: the reprojected accumulation described at rt3_temporal_set_params below)
+ *        "motion"        (x,y)=window   bindings {Motion RGBA32F}
+ *                        (no reference counterpart: where each surface point was one frame ago, rt3_temporal_set_motion_input below)
  *      and the probe-GI passes (restated as written, debug stores included; rules for what the text leaves open are listed in
  *      DESIGN.md section 11).  A probe owns 16x16 pixels and an 8x8-texel cell of the atlas images; bindings are ordered by
  *      (descriptor set, binding) as the shaders declare them:
@@ -352,8 +361,9 @@ int rt3_denoise_set_variance_input(rt3_ctx *ctx, uint32_t moments_image);
  *      N = 1, c_acc = c, mu1 = l, mu2 = l * l.  History = {c_acc, N}, Moments = {mu1, mu2, variance, N}, Out = {emission + c_acc * albedo,
  *      In.a}: displayable, and a valid In for "denoise".  Background pixels: Out = In bit for bit, History = Moments = 0.
  *      PrevHistory.w > 0 is the reset rule: zeroed previous images mean "no history" (first frame, resize, new scene).  fp32, equal to
- *      tests/ref_temporal.py bit for bit.  The scene is taken as static between the two frames: there are no motion vectors, and geometry
- *      moved by rt3_scene_update_vertices is caught only as far as the plane test catches it.
+ *      tests/ref_temporal.py bit for bit.  Without a motion input (rt3_temporal_set_motion_input, below) the scene is taken as static between
+ *      the two frames; with one, instances whose matrices changed keep their history.  Geometry moved by rt3_scene_update_vertices has
+ *      no previous vertices and is caught only as far as the plane test catches it.
  *      The three written images must differ from each other and from every image read (RT3_E_INVALID).  Under a tile partition with more
  *      than one rank the pass returns RT3_E_STATE, like "denoise".  A launch with no previous view set returns RT3_E_STATE; a previous
  *      window_size that differs from the launch's is RT3_E_INVALID.
@@ -372,6 +382,27 @@ typedef struct rt3_temporal_params {
 } rt3_temporal_params;
 int rt3_temporal_set_prev_view(rt3_ctx *ctx, const void *prev_gconst, size_t size);
 int rt3_temporal_set_params(rt3_ctx *ctx, const rt3_temporal_params *params);
+/* ---- "motion": temporal history that follows moved instances.  No reference counterpart; DESIGN.md section 4h.  The pass traces the
+ *      primary rays of GConst's camera (the launches of "gbuffer", so the hits are the G-buffer's) and writes one texel per pixel this rank
+ *      owns; with i the instance of the hit geometry:
+ *        miss                                                                       -> {0, 0, 0, 0}
+ *        no previous transforms, or instance i's 3 x 4 matrix equals its previous
+ *        one word for word (as uint32: -0 is not +0)                                -> {P, 1}, P = o + d t: the bits "denoise" and
+ *                                                                                      "temporal" compute from gbuffer_depth
+ *        otherwise                                                                  -> {P', 2}, P' = prev_i * p, p = (a w + b u) + c v with
+ *                                                                                      w = (1 - u) - v and a, b, c the triangle's vertices
+ *                                                                                      in object space (P' = p when prev_i is the identity)
+ *      fp32, singly rounded, equal to tests/ref_motion.py bit for bit.  RT3_E_STATE without a structure, while vertices are stale, or when
+ *      the number of previous transforms is neither 0 nor the structure's instance count.  Works under a tile partition like "gbuffer".
+ *      rt3_temporal_set_motion_input: the Motion image "temporal" reads; 0 (the default) = none, and every bit "temporal" writes is what it
+ *      was.  With one, a foreground pixel whose texel has w < 1 gets no history (N = 1); otherwise the texel's xyz takes P's place in the
+ *      reprojection and in P_q - P of the plane test, while the tolerance |P - eye|, the normal and the surface record stay this frame's.
+ *      Checked when "temporal" is launched: a live RGBA32F image of the window's size that is none of Out, History, Moments, else
+ *      RT3_E_INVALID.
+ *      Limits: the normal test compares this frame's normal with the previous G-buffer's, so an instance that turns by more than
+ *      acos(normal_cos) in one frame loses its history; light that moves (a moved object's shadow, a moved emitter) still lags on unmoved
+ *      surfaces. ---- */
+int rt3_temporal_set_motion_input(rt3_ctx *ctx, uint32_t motion_image);
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);

@@ -37,6 +37,7 @@ EXPORTS = [
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
+    "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
 
@@ -171,6 +172,8 @@ def load():
         "rt3_denoise_set_variance_input": (i32, [vp, u32]),
         "rt3_temporal_set_prev_view": (i32, [vp, vp, sz]),
         "rt3_temporal_set_params": (i32, [vp, C.POINTER(TemporalParams)]),
+        "rt3_scene_set_prev_transforms": (i32, [vp, vp, u32]),
+        "rt3_temporal_set_motion_input": (i32, [vp, u32]),
         "rt3_frame_wait": (i32, [vp]),
         "rt3_trace_rays": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double)]),
         "rt3_selftest_eval": (i32, [vp, i32, vp, u32, vp]),

@@ -198,6 +198,14 @@ struct rt3_ctx {
     rt3_temporal_params tp_params = kTemporalDefaults;
     rt3_gconst tp_prev;
     bool tp_has_prev = false;
+    uint32_t tp_motion_image = 0;  // rt3_temporal_set_motion_input: the "motion" pass's image, 0 = none
+    // "motion" pass: the previous frame's instance matrices (rt3_scene_set_prev_transforms; empty = every instance unmoved) and the device
+    // tables made from them for the structure of accel_stamp mo_stamp (motion_tables)
+    std::vector<float> mo_prev;  // n x 16, column-major
+    bool mo_dirty = false, mo_any_moved = false;
+    uint64_t mo_stamp = 0;
+    DevBuf<MotionPrevDev> d_mo_prev;
+    DevBuf<uint32_t> d_mo_slot;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
     std::vector<Timed> pending_events;
@@ -205,6 +213,7 @@ struct rt3_ctx {
 };
 
 static int ensure_lights(rt3_ctx* c);
+static int motion_tables(rt3_ctx* c);
 
 namespace {
 
@@ -884,9 +893,51 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint3
     L.gbuffer = r[0]->ptr; L.depth = (const float*)r[1]->ptr; L.in = r[2]->ptr;
     L.prev_gbuffer = r[3]->ptr; L.prev_depth = (const float*)r[4]->ptr; L.prev_history = r[5]->ptr; L.prev_moments = r[6]->ptr;
     L.out = r[7]->ptr; L.history = r[8]->ptr; L.moments = r[9]->ptr;
+    if (c->tp_motion_image) {
+        Resource* mv = image_checked(c, c->tp_motion_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "motion input");
+        if (!mv) return RT3_E_INVALID;
+        for (int i = 7; i < 10; i++)
+            if (mv == r[i] || mv->ptr == r[i]->ptr)
+                return fail(c, RT3_E_INVALID, std::string("temporal: the motion input (rt3_temporal_set_motion_input) must not be '") + kB[i].name + "'");
+        L.motion = mv->ptr;
+    }
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_temporal(c->stream, L);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "motion": where each pixel's surface point was one frame ago (no reference counterpart).  The primary trace is
+// pass_gbuffer's, launch for launch, so the hits are the G-buffer's.
+int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const uint32_t* b, uint32_t nb) {
+    uint32_t W, H;
+    if (int r = check_window(c, g, &W, &H)) return r;
+    if (x != W || y != H) return fail(c, RT3_E_INVALID, "motion: launch size must be the window size (WorkSize2D::FullScreen, like gbuffer)");
+    if (nb != 1) return fail(c, RT3_E_INVALID, "motion expects 1 binding {Motion}");
+    Resource* mv = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Motion");
+    if (!mv) return RT3_E_INVALID;
+    if (int r = motion_tables(c)) return r;
+    PixelList* pl;
+    if (int r = get_pixlist(c, W, H, c->rank, c->n_ranks, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    if (int r = ensure_work(c, pl->count, pl->count)) return r;
+    MotionLaunch L;
+    memcpy(&L.g, g, sizeof(L.g));
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_raygen(c->stream, L.g, pl->dev.get(), pl->count, c->rays[0].get(), c->cap);
+    }
+    if (int r = trace_primary(c, pl->count)) return r;
+    L.m.verts = c->d_verts.get(); L.m.indices = c->d_indices.get(); L.m.geoms = c->d_geoms.get();
+    L.m.prim_geom = c->d_prim_geom.get(); L.m.first_prim = c->d_first_prim.get();
+    L.m.geom_slot = c->mo_any_moved ? c->d_mo_slot.get() : nullptr;
+    L.m.prev = c->d_mo_prev.get();
+    L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->hits.get(); L.out = mv->ptr;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_motion(c->stream, L);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -1275,6 +1326,20 @@ int rt3_scene_set_instances(rt3_ctx* c, const rt3_instance* inst, uint32_t n) {
     c->accel_built = false;
     return RT3_OK;
 }
+// The previous frame's matrices of the same instances, for the "motion" pass only: no build reads them and the structure stays as it is
+int rt3_scene_set_prev_transforms(rt3_ctx* c, const float* transforms, uint32_t n) {
+    if (!c || (!transforms && n)) return fail(c, RT3_E_INVALID, "previous transforms NULL");
+    for (uint32_t i = 0; i < n; i++) {
+        const float* m = transforms + 16 * (size_t)i;
+        for (int k = 0; k < 16; k++)
+            if (!(std::fabs(m[k]) <= 1.0e18f)) return fail(c, RT3_E_INVALID, "previous transform " + std::to_string(i) + " is not finite (or beyond 1e18)");
+        if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f)
+            return fail(c, RT3_E_INVALID, "previous transform " + std::to_string(i) + ": the last row must be (0, 0, 0, 1), as for an instance's matrix");
+    }
+    c->mo_prev.assign(transforms, transforms + 16 * (size_t)n);
+    c->mo_dirty = true;
+    return RT3_OK;
+}
 static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 // The placements a build covers: the instances set, or (none) one identity instance of every geometry, which `whole` then holds
 static std::pair<const rt3_instance*, size_t> placements(const rt3_ctx* c, rt3_instance& whole) {
@@ -1339,6 +1404,46 @@ static int flatten_world(rt3_ctx* c) {
     }
     c->n_flat_geoms = (uint32_t)nf;
     c->n_flat_prims = (uint32_t)total;
+    return RT3_OK;
+}
+// The device tables of the "motion" pass for the built structure: per instance its previous matrix, per flattened geometry its instance's
+// index if that instance moved -- the 12 stored floats of the two matrices differ in some word -- else kMotionUnmoved.  Remade when the
+// previous transforms or the structure changed; the count is checked at every launch.
+static int motion_tables(rt3_ctx* c) {
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
+    const size_t n = c->mo_prev.size() / 16;
+    if (n != 0 && n != n_inst)
+        return fail(c, RT3_E_STATE, "motion: " + std::to_string(n) + " previous transforms (rt3_scene_set_prev_transforms) for a structure of " +
+                                        std::to_string(n_inst) + " instance(s)");
+    if (!c->mo_dirty && c->mo_stamp == c->accel_stamp) return RT3_OK;
+    std::vector<MotionPrevDev> rec(n);
+    std::vector<uint32_t> slot;
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        const float *pm = &c->mo_prev[16 * i], *cm = inst[i].transform;
+        float cur[12];
+        memset(&rec[i], 0, sizeof(rec[i]));
+        for (int col = 0; col < 4; col++)
+            for (int row = 0; row < 3; row++) {
+                rec[i].m[3 * col + row] = pm[4 * col + row];
+                cur[3 * col + row] = cm[4 * col + row];
+            }
+        rec[i].identity = memcmp(pm, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u;
+        const bool moved = memcmp(rec[i].m, cur, sizeof(cur)) != 0;  // word for word: -0 is not +0
+        slot.insert(slot.end(), inst[i].geometry_count, moved ? (uint32_t)i : kMotionUnmoved);
+        any = any || (moved && inst[i].geometry_count);
+    }
+    if (any) {
+        HIPC(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the old tables
+        if (int r = dev_alloc(c, c->d_mo_prev, rec.size())) return r;
+        if (int r = dev_alloc(c, c->d_mo_slot, slot.size())) return r;
+        HIPC(c, hipMemcpy(c->d_mo_prev.get(), rec.data(), rec.size() * sizeof(MotionPrevDev), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->d_mo_slot.get(), slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
+    }
+    c->mo_any_moved = any;
+    c->mo_dirty = false;
+    c->mo_stamp = c->accel_stamp;
     return RT3_OK;
 }
 // the shading records of the flattened world, remade only when what they depend on has changed since they were made
@@ -2312,9 +2417,10 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
     if (!strcmp(pass_name, "interpolate_probes")) return pass_interpolate_probes(c, &g, x, y, z, bindings, n_bindings);
     if (!strcmp(pass_name, "denoise")) return pass_denoise(c, &g, x, y, z, bindings, n_bindings);
     if (!strcmp(pass_name, "temporal")) return pass_temporal(c, &g, x, y, z, bindings, n_bindings);
+    if (!strcmp(pass_name, "motion")) return pass_motion(c, &g, x, y, bindings, n_bindings);
     return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name +
                                       "' (known: gbuffer, refrence_mode, postprocess, structured_importance_sampling, trace_probes, "
-                                      "spherical_harmonic_conversion, interpolate_probes, denoise, temporal)");
+                                      "spherical_harmonic_conversion, interpolate_probes, denoise, temporal, motion)");
 }
 int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
     if (!c) return RT3_E_INVALID;
@@ -2344,6 +2450,11 @@ int rt3_temporal_set_prev_view(rt3_ctx* c, const void* prev_gconst, size_t size)
     if (!prev_gconst || size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "temporal prev view: must be the 304-byte GConst block of the previous frame, or (NULL, 0)");
     memcpy(&c->tp_prev, prev_gconst, sizeof(rt3_gconst));
     c->tp_has_prev = true;
+    return RT3_OK;
+}
+int rt3_temporal_set_motion_input(rt3_ctx* c, uint32_t motion_image) {
+    if (!c) return RT3_E_INVALID;
+    c->tp_motion_image = motion_image;  // checked when "temporal" is launched, like the variance input of "denoise"
     return RT3_OK;
 }
 int rt3_temporal_set_params(rt3_ctx* c, const rt3_temporal_params* p) {

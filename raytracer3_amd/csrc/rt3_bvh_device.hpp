@@ -27,6 +27,20 @@ __device__ __forceinline__ void fetch_triangle(const float* verts, const uint32_
         c = transform_point(fg.m, c);
     }
 }
+// The same triangle in object space: fetch_triangle's index arithmetic without the matrix (the "motion" pass puts the previous frame's
+// matrix on the interpolated point instead, rt3_motion.hip)
+__device__ __forceinline__ void fetch_triangle_object(const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                                                      const uint32_t* first_prim, uint32_t prim, V3& a, V3& b, V3& c) {
+    uint32_t g = prim_geom[prim];
+    const FlatGeomDev& fg = geoms[g];
+    uint32_t io = fg.g.index_offset + 3u * (prim - first_prim[g]);
+    const float* v0 = verts + 8 * (size_t)(fg.g.vertex_offset + indices[io]);
+    const float* v1 = verts + 8 * (size_t)(fg.g.vertex_offset + indices[io + 1]);
+    const float* v2 = verts + 8 * (size_t)(fg.g.vertex_offset + indices[io + 2]);
+    a = v3(v0[0], v0[1], v0[2]);
+    b = v3(v1[0], v1[1], v1[2]);
+    c = v3(v2[0], v2[1], v2[2]);
+}
 // conservative leaf padding from the scene bounds (ordered-uint encoded min.xyz, max.xyz): a share of the extent, and at least 2^-20
 // of the largest coordinate magnitude ("Leaf padding")
 __device__ __forceinline__ float leaf_pad(const uint32_t* bounds) {

@@ -325,8 +325,35 @@ struct TemporalLaunch {
     const void *gbuffer, *in, *prev_gbuffer, *prev_history, *prev_moments;
     const float *depth, *prev_depth;
     void *out, *history, *moments;
+    const void* motion = nullptr;  // rt3_temporal_set_motion_input: the "motion" pass's image, or none
 };
 void launch_temporal(hipStream_t st, const TemporalLaunch& L);
+
+// "motion" pass (rt3_motion.hip): one kernel behind the primary trace, one thread per listed pixel, no scratch.
+// `prev` holds one record per instance; the host's "moved" flag travels as `geom_slot`: per flattened geometry its instance's index when that
+// instance moved, else kMotionUnmoved.  geom_slot = nullptr: no instance moved, nothing but `hits` and the camera is read.
+constexpr uint32_t kMotionUnmoved = 0xFFFFFFFFu;
+struct MotionPrevDev {
+    float m[12];        // the previous object -> world matrix, stored like FlatGeomDev::m
+    uint32_t identity;  // 1: it is exactly the identity -- the object-space point is used as it is (the flattening's rule)
+    uint32_t pad[3];
+};
+static_assert(sizeof(MotionPrevDev) == 64, "MotionPrev layout");
+struct MotionDev {
+    const float* verts;
+    const uint32_t *indices, *prim_geom, *first_prim, *geom_slot;
+    const FlatGeomDev* geoms;
+    const MotionPrevDev* prev;
+};
+struct MotionLaunch {
+    GConstDev g;
+    MotionDev m;
+    const uint32_t* pixels;  // the rank's pixel list, c->hits in its order
+    uint32_t npix, width;
+    const float* hits;
+    void* out;
+};
+void launch_motion(hipStream_t st, const MotionLaunch& L);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

@@ -5,6 +5,8 @@
 //   k_temporal -> per pixel: the surface record of the denoise pass (rt3_filter_device.hpp), its world position projected into the previous
 //                 view, four bilinear taps of the previous History / Moments that pass a normal and a plane test, and the blend
 //                 History = {c_acc.rgb, N}, Moments = {mu1, mu2, variance, N}, Out = {emission + c_acc * albedo, In.a}
+//                 <true>: with the "motion" pass's image (rt3_motion.hip) the projected point is where the surface
+//                 point was one frame ago; <false> (no input set) projects P itself
 //
 // Arithmetic contract: tests/ref_temporal.py restates every operation below in numpy float32, in this order (matrix rows summed left to
 // right like primary_ray, taps rows outer, columns inner); the pass equals it bit for bit.  A tap that does not count is skipped: the
@@ -35,11 +37,15 @@ struct TemporalArgs {  // everything but the two cameras
     const float* prev_depth;
     const float4 *prev_history, *prev_moments;
     float4 *out, *history, *moments;
+    const float4* motion;  // MOTION only: the "motion" pass's image {P', kind}
 };
 
 // row r of (column-major m) * (v, w), summed left to right like primary_ray
 RT3_DEV float mat_row(const float* m, int r, float x, float y, float z, float w) { return m[r] * x + m[4 + r] * y + m[8 + r] * z + m[12 + r] * w; }
 
+// MOTION: the point that is looked up in the previous frame is the Motion texel's (where this surface point was one frame ago) instead of
+// P, and a texel of kind < 1 on a foreground pixel means "no history".  Everything else stays on the current frame.
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, TemporalArgs a) {
     const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
     const uint32_t W = a.W, H = a.H;
@@ -61,12 +67,19 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
     const V3 c = dn_demodulate(L, e, m);
     const float l = dn_lum(c.x, c.y, c.z);
 
-    // reproject P into the previous view
-    const float vx = mat_row(prev.view, 0, P.x, P.y, P.z, 1.0f), vy = mat_row(prev.view, 1, P.x, P.y, P.z, 1.0f);
-    const float vz = mat_row(prev.view, 2, P.x, P.y, P.z, 1.0f), vw = mat_row(prev.view, 3, P.x, P.y, P.z, 1.0f);
+    V3 R = P;  // the point whose place in the previous frame is looked up
+    bool known = true;
+    if (MOTION) {
+        const float4 M = a.motion[pi];
+        R = v3(M.x, M.y, M.z);
+        known = !(M.w < 1.0f);
+    }
+    // reproject R into the previous view
+    const float vx = mat_row(prev.view, 0, R.x, R.y, R.z, 1.0f), vy = mat_row(prev.view, 1, R.x, R.y, R.z, 1.0f);
+    const float vz = mat_row(prev.view, 2, R.x, R.y, R.z, 1.0f), vw = mat_row(prev.view, 3, R.x, R.y, R.z, 1.0f);
     const float qx = mat_row(prev.proj, 0, vx, vy, vz, vw), qy = mat_row(prev.proj, 1, vx, vy, vz, vw), qw = mat_row(prev.proj, 3, vx, vy, vz, vw);
     float ws = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, k1 = 0.0f, k2 = 0.0f;
-    if (qw > 0.0f) {
+    if (known && qw > 0.0f) {
         const float Wf = g.window_size[0], Hf = g.window_size[1];
         const float ndx = qx / qw, ndy = qy / qw;
         const float sx = (ndx * 0.5f + 0.5f) * Wf - 0.5f, sy = (-ndy * 0.5f + 0.5f) * Hf - 0.5f;
@@ -92,7 +105,7 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
                     if (!(ph.w > 0.0f)) continue;
                     const V3 nq = unpack_normal_11_10_11(a.prev_gbuffer[qi * 4 + 1]);
                     if (!(dot(n, nq) >= a.normal_cos)) continue;
-                    const V3 dP = dn_position(prev, (uint32_t)tx, (uint32_t)ty, td) - P;
+                    const V3 dP = dn_position(prev, (uint32_t)tx, (uint32_t)ty, td) - R;
                     if (!(fabsf(dot(n, dP)) <= tol)) continue;
                     const float4 pm = a.prev_moments[qi];
                     const float wt = (i ? fx : 1.0f - fx) * wy;
@@ -137,8 +150,9 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
 void launch_temporal(hipStream_t st, const TemporalLaunch& L) {
     const TemporalArgs a = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance, (const uint4*)L.gbuffer,
                             L.depth, (const float4*)L.in, (const uint32_t*)L.prev_gbuffer, L.prev_depth, (const float4*)L.prev_history,
-                            (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments};
-    hipLaunchKernelGGL(k_temporal, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a);
+                            (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments, (const float4*)L.motion};
+    if (L.motion) hipLaunchKernelGGL(k_temporal<true>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a);
+    else hipLaunchKernelGGL(k_temporal<false>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a);
 }
 
 }  // namespace rt3

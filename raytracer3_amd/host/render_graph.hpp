@@ -97,6 +97,10 @@ class Context {
     // it), and the Moments image whose variance "denoise" starts from (0 = none)
     void set_temporal_params(const rt3_temporal_params* p) const { check(rt3_temporal_set_params(ctx_, p), "rt3_temporal_set_params"); }
     void set_prev_view(const rt3_gconst* prev) const { check(rt3_temporal_set_prev_view(ctx_, prev, prev ? sizeof(*prev) : 0), "rt3_temporal_set_prev_view"); }
+    // RayTracingPass "motion" (no reference counterpart): the previous frame's instance matrices (n x 16, column-major; nullptr forgets them)
+    // and the Motion image that "temporal" follows moved instances with (0 = none)
+    void set_prev_transforms(const float* m, uint32_t n) const { check(rt3_scene_set_prev_transforms(ctx_, m, n), "rt3_scene_set_prev_transforms"); }
+    void set_temporal_motion_input(uint32_t motion_image) const { check(rt3_temporal_set_motion_input(ctx_, motion_image), "rt3_temporal_set_motion_input"); }
     void set_denoise_variance_input(uint32_t moments_image) const { check(rt3_denoise_set_variance_input(ctx_, moments_image), "rt3_denoise_set_variance_input"); }
 
    private:

@@ -191,6 +191,13 @@ class Context:
             arr[k].transform[:] = [float(x) for x in np.asarray(m, np.float32).T.ravel()]  # column-major, like glam's Mat4
         self.check(self.lib.rt3_scene_set_instances(self.h, C.byref(arr), len(instances)))
 
+    def set_prev_transforms(self, transforms=None):
+        """the previous frame's 4x4 object -> world matrices, one per instance of the set_instances list, for the "motion" pass
+        (rt3_scene_set_prev_transforms); None or [] forgets them: every instance counts as unmoved.  No rebuild is needed."""
+        n = 0 if transforms is None else len(transforms)
+        arr = np.ascontiguousarray([np.asarray(m, np.float32).T.ravel() for m in transforms], np.float32).reshape(n, 16) if n else None
+        self.check(self.lib.rt3_scene_set_prev_transforms(self.h, arr.ctypes.data if n else None, n))
+
     def set_sky(self, rgb):
         s = np.ascontiguousarray(rgb, np.float32)
         self.check(self.lib.rt3_scene_set_sky(self.h, s.ctypes.data, s.shape[1], s.shape[0]))
@@ -304,6 +311,10 @@ class Context:
             self.check(self.lib.rt3_temporal_set_prev_view(self.h, None, 0))
         else:
             self.check(self.lib.rt3_temporal_set_prev_view(self.h, C.byref(gconst), C.sizeof(gconst)))
+
+    def set_temporal_motion_input(self, motion_image=0):
+        """the "motion" pass's image that "temporal" follows moved instances with (rt3_temporal_set_motion_input); 0 = none"""
+        self.check(self.lib.rt3_temporal_set_motion_input(self.h, int(motion_image)))
 
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))

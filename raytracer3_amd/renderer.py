@@ -6,7 +6,8 @@ Per frame, three passes exactly as the old shaders were wired:
   RayTracingPass("refrence_mode")  -> Light (RGBA32F linear radiance)          shaders/old/refrence_mode.slang
   ComputePass("postprocess")       -> display image (AgX)                      shaders/old/postprocess.slang
 with, on request, ComputePass("temporal") and / or ComputePass("denoise") between the last two (no reference counterpart: the reprojected
-accumulation of DESIGN.md section 4g and the a-trous filter of section 4f),
+accumulation of DESIGN.md section 4g and the a-trous filter of section 4f), and RayTracingPass("motion") in front of "temporal" in a frame
+whose instances moved (section 4h),
 and, as a second frame description, the probe-GI chain of the old shaders (`probe_commands`):
   gbuffer -> structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes
 """
@@ -47,10 +48,11 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
-def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False):
+def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
     `temporal`, the "temporal" node accumulates `Light` with the reprojected history into `accumulated`; with `denoise`, the "denoise"
-    node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them."""
+    node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them.  With `motion`, the "motion" node is
+    in the list too (handle `motion`); "temporal" reads its image as context state, so it is a root of its own, drawn first."""
     gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
     depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
     light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
@@ -62,6 +64,8 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False):
     pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
           .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
     src, lit = pt, light
+    if motion:
+        handles["motion"] = motion_node(rg, gconst)[1]
     if temporal:
         src, th = temporal_node(rg, gconst, gb, gbuffer, depth, pt, light)
         handles.update(th)
@@ -105,6 +109,21 @@ def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
     return tn, t
 
 
+def motion_node(rg, gconst):
+    """RayTracingPass("motion"): {Motion}, where each pixel's surface point was one frame ago under the previous instance matrices
+    (ctx.set_prev_transforms).  "temporal" reads the image as context state (ctx.set_temporal_motion_input), not through an edge: draw this
+    node (rg.draw_frame(motion)) before the frame.  Returns (node, motion)."""
+    motion = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion")
+    mn = RayTracingPass.new(rg, "motion").shader("motion").constants(gconst).write(IMPORTED, motion).launch(WorkSize2D.FullScreen)
+    return mn, motion
+
+
+def _instance_key(instances):
+    """(the geometry runs, the matrices' float32 words) of an instance list"""
+    return ([(int(f), int(n)) for f, n, _ in instances],
+            [np.ascontiguousarray(np.asarray(m, np.float32)).view(np.uint32).tolist() for _, _, m in instances])
+
+
 class PathTracer:
     """One GPU's share of the frame.  `rank` / `n_ranks` select the interleaved 64x64 tiles this process renders."""
 
@@ -119,6 +138,8 @@ class PathTracer:
         self._stage = None       # rehearsal path only: staging buffer of the host-moved gather
         self.host_group = None   # process group of the host-moved gather (None = the default group)
         self._prev_gconst = None  # "temporal": the view of the frame whose G-buffer / History / Moments the images hold; None = no history
+        self._instances = None    # set_instances: the list the structure was built for; None = never called
+        self._prev_instances = None  # ... and the one the last temporal frame was rendered with
 
     def close(self):
         self.ctx.close()
@@ -131,6 +152,17 @@ class PathTracer:
             self.ctx.set_bluenoise(bluenoise)
         self._accel = self.ctx.build_accel()
         self.reset_history()
+
+    def set_instances(self, instances):
+        """Place the scene's geometries: upload the list (ctx.set_instances) and rebuild.  The next temporal frame compares it with the
+        list of the last one and, where matrices differ, runs the "motion" pass so that moved instances keep their history.  A list with
+        other geometry runs (another count included), and the first list set, start the history over."""
+        instances = [(int(f), int(n), np.array(m, np.float32)) for f, n, m in instances]
+        self.ctx.set_instances(instances)
+        self._accel = self.ctx.build_accel()
+        if self._instances is None or _instance_key(instances)[0] != _instance_key(self._instances)[0]:
+            self.reset_history()
+        self._instances = instances
 
     def reset_history(self):
         """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
@@ -157,11 +189,18 @@ class PathTracer:
             rg.upload(t["prev_moments"], zero)
         self.ctx.set_prev_view(self._prev_gconst if self._prev_gconst is not None else gconst)
         self.ctx.set_denoise_variance_input(t["moments"] if denoise else 0)
+        # instances that moved since the last temporal frame: hand over its matrices and let "temporal" read the "motion" pass's image
+        moved = (self._prev_gconst is not None and self._instances is not None and self._prev_instances is not None
+                 and _instance_key(self._instances) != _instance_key(self._prev_instances))
+        self.ctx.set_prev_transforms([m for _, _, m in self._prev_instances] if moved else None)
+        self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved else 0)
+        return moved
 
     def _end_temporal(self, gconst):
         keep = L.GConst()
         C.memmove(C.byref(keep), C.byref(gconst), C.sizeof(keep))
         self._prev_gconst = keep
+        self._prev_instances = self._instances
 
     def update_vertices(self, vertices, first=0):
         """deformed vertices (same topology): upload them and refit the acceleration structure"""
@@ -174,11 +213,11 @@ class PathTracer:
         g.pad[0] = flags
         return g
 
-    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False):
+    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False):
         """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
         denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""
         self.rg.begin_frame()
-        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal)
+        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion)
         return self.handles
 
     def denoise(self, gconst, wait=True, temporal=False, denoise=True):
@@ -191,9 +230,8 @@ class PathTracer:
         "denoise" -- unless `denoise` is False -- filters its `accumulated` image with the temporal variance."""
         rg = self.rg
         names = ("TemporalGbuffer", "TemporalDepth") if temporal else ("gbuffer", "gbuffer_depth")  # render() must not overwrite the kept one
-        if temporal:
-            self._begin_temporal(gconst, denoise, names)
-        elif denoise:
+        moved = temporal and self._begin_temporal(gconst, denoise, names)
+        if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
         rg.begin_frame()
         gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, names[0])
@@ -207,15 +245,21 @@ class PathTracer:
         if temporal:
             src, extra = temporal_node(rg, gconst, gb, gbuffer, depth, IMPORTED, light)
             lit = extra["accumulated"]
+        if moved:
+            extra = dict(extra, motion=motion_node(rg, gconst)[1])
         denoised = lit
         if denoise:
             _, denoised = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit)
             extra = dict(extra, denoised=denoised)
         self.handles = dict(getattr(self, "handles", {}), gbuffer=gbuffer, depth=depth, light=light, **extra)
+        if not moved:
+            self.handles.pop("motion", None)
         W, H = self.window
         if self.n_ranks > 1:
             self.ctx.set_tile_partition(W, H, 0, 1)
         try:
+            if moved:  # on the whole window, like the G-buffer above
+                rg.draw_frame(extra["motion"])
             rg.draw_frame(denoised, wait=wait)
         finally:
             if self.n_ranks > 1:  # launches read the partition when they are enqueued: safe to restore behind them
@@ -278,12 +322,16 @@ class PathTracer:
     def render(self, gconst, postprocess=False, wait=True, denoise=False, temporal=False):
         """One frame.  `temporal` accumulates it with the reprojected history of the previous temporal frame (this object keeps two sets
         of history images, the previous G-buffer, depth and GConst, and starts from zeros after set_scene / reset_history); with
-        `denoise` too, the filter reads the accumulated image and its temporal variance.  One rank only: see denoise()."""
+        `denoise` too, the filter reads the accumulated image and its temporal variance.  One rank only: see denoise().  After
+        set_instances() moved something, the frame has the "motion" node as well (handle `motion`) and "temporal" follows the instances."""
+        motion = False
         if temporal:
-            self._begin_temporal(gconst, denoise)
+            motion = self._begin_temporal(gconst, denoise)
         elif denoise:
             self.ctx.set_denoise_variance_input(0)
-        h = self.commands(gconst, postprocess, denoise, temporal)
+        h = self.commands(gconst, postprocess, denoise, temporal, motion)
+        if motion:
+            self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
         if temporal:
             self._end_temporal(gconst)
@@ -311,6 +359,11 @@ class PathTracer:
         """(History, Moments) of the "temporal" pass"""
         W, H = self.window
         return self.rg.download(self.handles["history"], (H, W, 4), np.float32), self.rg.download(self.handles["moments"], (H, W, 4), np.float32)
+
+    def motion(self):
+        """the "motion" pass's image of the last frame that had one"""
+        W, H = self.window
+        return self.rg.download(self.handles["motion"], (H, W, 4), np.float32)
 
     def gbuffer(self):
         W, H = self.window
