@@ -329,6 +329,11 @@ SceneDev scene_dev(const rt3_ctx* c) {
     return s;
 }
 
+// the geometry tables of the flattened world ...
+GeomTables world_tables(const rt3_ctx* c) { return {c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get()}; }
+// ... and of a bottom tree: the world's vertices and indices, read through the tree's own tables
+GeomTables mesh_tables(const rt3_ctx* c, const MeshTables& t) { return {c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim}; }
+
 // a change every tree's shape depends on: the structure goes, and a refit cannot bring it back
 void invalidate_topology(rt3_ctx* c) {
     c->accel_built = false;
@@ -528,6 +533,14 @@ int trace_primary(rt3_ctx* c, uint32_t n) {
 }
 
 // ---------------------------------------------------------------------------------------------- passes
+// A pass is one entry of kPasses (below): launch_pass checks the launch against the entry and hands the pass function (pass_*) the window
+// and the resolved bindings, in the entry's order.  What a pass function still checks is its own: context state, the least size of a
+// buffer, the optional context-state inputs.
+GConstDev gconst_dev(const rt3_gconst* g) {
+    GConstDev gd;
+    memcpy(&gd, g, sizeof(gd));
+    return gd;
+}
 int check_window(rt3_ctx* c, const rt3_gconst* g, uint32_t* W, uint32_t* H) {
     float fw = g->window_size[0], fh = g->window_size[1];
     if (!(fw >= 1.0f && fh >= 1.0f && fw <= 65535.0f && fh <= 65535.0f) || fw != std::floor(fw) || fh != std::floor(fh))
@@ -544,47 +557,40 @@ Resource* image_checked(rt3_ctx* c, uint32_t handle, uint32_t W, uint32_t H, uin
     }
     return r;
 }
-
-// gbuffer.slang:8-21
-int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != W || y != H) return fail(c, RT3_E_INVALID, "gbuffer: launch size must be the window size (WorkSize2D::FullScreen, executions.rs:73)");
-    if (nb != 2) return fail(c, RT3_E_INVALID, "gbuffer expects 2 bindings {gbuffer, gbuffer_depth}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    if (!gb || !dp) return RT3_E_INVALID;
-    PixelList* pl;
-    if (int r = get_pixlist(c, W, H, c->rank, c->n_ranks, &pl)) return r;
+int buffer_at_least(rt3_ctx* c, const Resource* r, size_t need, const char* what) {
+    if (r->bytes >= need) return RT3_OK;
+    return fail(c, RT3_E_INVALID, std::string("binding '") + what + "' must be a buffer of at least " + std::to_string(need) + " bytes");
+}
+// The primary rays of this rank's pixels of the W x H window (*out: the list) into c->rays[0], their closest hits into c->hits, in the
+// list's order.  An empty list: nothing is allocated, nothing enqueued.
+int primary_hits(rt3_ctx* c, const GConstDev& gd, uint32_t W, uint32_t H, PixelList** out) {
+    if (int r = get_pixlist(c, W, H, c->rank, c->n_ranks, out)) return r;
+    const PixelList* pl = *out;
     if (pl->count == 0) return RT3_OK;
     if (int r = ensure_work(c, pl->count, pl->count)) return r;
-    GConstDev gd;
-    memcpy(&gd, g, sizeof(gd));
-    size_t S = c->cap;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_raygen(c->stream, gd, pl->dev.get(), pl->count, c->rays[0].get(), S);
+        launch_raygen(c->stream, gd, pl->dev.get(), pl->count, c->rays[0].get(), c->cap);
     }
-    if (int r = trace_primary(c, pl->count)) return r;
+    return trace_primary(c, pl->count);
+}
+
+// gbuffer.slang:8-21
+int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    PixelList* pl;
+    if (int r = primary_hits(c, gconst_dev(g), W, H, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_gbuffer(c->stream, scene_dev(c), pl->dev.get(), pl->count, W, c->hits.get(), S, gb->ptr, (float*)dp->ptr);
+        launch_gbuffer(c->stream, scene_dev(c), pl->dev.get(), pl->count, W, c->hits.get(), c->cap, res[0]->ptr, (float*)res[1]->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 
 // refrence_mode.slang:14-66 as a wavefront loop
-int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != W || y != H) return fail(c, RT3_E_INVALID, "refrence_mode: launch size must be the window size");
-    if (nb != 4) return fail(c, RT3_E_INVALID, "refrence_mode expects 4 bindings {gbuffer, gbuffer_depth, Light, PrevLight}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    Resource* li = image_checked(c, b[2], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Light");
-    Resource* pv = image_checked(c, b[3], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "PrevLight");
-    if (!gb || !dp || !li || !pv) return RT3_E_INVALID;
+int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *li = res[2], *pv = res[3];
     const uint32_t Sspp = g->samples, B = g->bounces;
     if (Sspp == 0 || B == 0) return RT3_OK;  // GConst::default() leaves samples = bounces = 0 (renderer/mod.rs:47-63): nothing to trace
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
@@ -605,8 +611,7 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
     if ((uint64_t)sb * npix > 0xFFFFFF00ull) return fail(c, RT3_E_INVALID, "batch too large");
     if (int r = ensure_work(c, (size_t)sb * npix, npix)) return r;
     const size_t S = c->cap;
-    GConstDev gd;
-    memcpy(&gd, g, sizeof(gd));
+    const GConstDev gd = gconst_dev(g);
     const bool nee = (g->pad[0] & RT3_F_NEE_SKY) && c->d_sky;
     // RT3_F_NEE_EMISSIVE: only with something to sample; otherwise the frame is the flag-less one, same kernels
     // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
@@ -637,12 +642,12 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
         for (uint32_t bn = 0; bn < B; bn++) {
             ShadeLaunch L;
             L.g = gd; L.sc = sc; L.pixels = pl->dev.get(); L.pixbn = pl->dev_bn.get(); L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
-            L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr;
+            L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
             L.in_rays = c->rays[cur].get(); L.in_hits = c->hits.get(); L.in_T = c->T[cur].get();
             L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
             L.out_rays = c->rays[cur ^ 1].get(); L.out_T = c->T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
             L.sh_rays = c->sh_rays.get(); L.sh_contrib = c->sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
-            L.lacc = c->lacc.get(); L.stride = S; L.max_n = n_first;
+            L.lacc = c->lacc.get(); L.stride = S;
             L.lights = lights;
             L.sh2_rays = c->sh2_rays.get(); L.sh2_contrib = c->sh2_contrib.get(); L.sh2_tmax = c->sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
             {
@@ -683,140 +688,75 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y,
 }
 
 // postprocess.slang:90-112
-int pass_postprocess(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1)
-        return fail(c, RT3_E_INVALID, "postprocess: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups (DispatchSize::FullScreen, build.rs:254-258)");
-    if (nb != 3) return fail(c, RT3_E_INVALID, "postprocess expects 3 bindings {Depth, Out, In}");
-    Resource* dp = image_checked(c, b[0], W, H, RT3_FORMAT_R32_SFLOAT, "Depth");
-    Resource* out = image_checked(c, b[1], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Out");
-    Resource* in = image_checked(c, b[2], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "In");
-    if (!dp || !out || !in) return RT3_E_INVALID;
+int pass_postprocess(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *dp = res[0], *out = res[1], *in = res[2];
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->rank, c->n_ranks, &pl)) return r;
     if (pl->count == 0) return RT3_OK;
-    GConstDev gd;
-    memcpy(&gd, g, sizeof(gd));
     ScopedTimer t(c, CAT_OTHER);
-    launch_postprocess(c->stream, gd, scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
+    launch_postprocess(c->stream, gconst_dev(g), scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 
 // ---- probe-GI passes.  A probe owns a 16x16 pixel block and an 8x8-texel cell of the probe atlas; the passes
-//      run on the whole window on every rank (they are not part of the tile-partitioned path).
-int probe_grid(rt3_ctx* c, const char* pass, uint32_t W, uint32_t H, uint32_t px, uint32_t py) {
-    if (px == 0 || py == 0 || px > W / 16 || py > H / 16)
-        return fail(c, RT3_E_INVALID, std::string(pass) + ": the probe grid must be between 1x1 and floor(W/16) x floor(H/16) probes");
-    return RT3_OK;
-}
+//      run on the whole window on every rank (they are not part of the tile-partitioned path).  The probe grid is the atlas binding's
+//      size over 8.
 // structured_importance_sampling.slang:7-11 : set 1 {gbuffer, gbuffer_depth, out, debug}, set 2 {probe_atlas}
-int pass_sis(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (z != 1) return fail(c, RT3_E_INVALID, "structured_importance_sampling: dispatch is probes_x x probes_y x 1 groups of 8x8 threads");
-    if (int r = probe_grid(c, "structured_importance_sampling", W, H, x, y)) return r;
-    if (nb != 5) return fail(c, RT3_E_INVALID, "structured_importance_sampling expects 5 bindings {gbuffer, gbuffer_depth, out, debug, probe_atlas}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    Resource* out = image_checked(c, b[2], x * 8, y * 8, RT3_FORMAT_R16_UINT, "out");
-    Resource* dbg = image_checked(c, b[3], x * 8, y * 8, RT3_FORMAT_R32_SFLOAT, "debug");
-    Resource* at = image_checked(c, b[4], x * 8, y * 8, RT3_FORMAT_R32G32B32A32_SFLOAT, "probe_atlas");
-    if (!gb || !dp || !out || !dbg || !at) return RT3_E_INVALID;
+int pass_sis(rt3_ctx* c, const rt3_gconst*, uint32_t W, uint32_t, Resource* const* res) {
     ScopedTimer t(c, CAT_OTHER);
-    launch_sis(c->stream, W, x, y, gb->ptr, out->ptr, (float*)dbg->ptr);
+    launch_sis(c->stream, W, res[4]->w / 8, res[4]->h / 8, res[0]->ptr, res[2]->ptr, (float*)res[3]->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 // trace_probes.slang:8-12 : set 1 {gbuffer, gbuffer_depth, directions}, set 2 {probe_atlas}, set 3 {prev_probe_atlas}
-int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x % 8 || y % 8) return fail(c, RT3_E_INVALID, "trace_probes: launch size is the probe atlas, 8 x 8 texels per probe");
-    if (int r = probe_grid(c, "trace_probes", W, H, x / 8, y / 8)) return r;
-    if (nb != 5) return fail(c, RT3_E_INVALID, "trace_probes expects 5 bindings {gbuffer, gbuffer_depth, directions, probe_atlas, prev_probe_atlas}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    Resource* dir = image_checked(c, b[2], x, y, RT3_FORMAT_R16_UINT, "directions");
-    Resource* at = image_checked(c, b[3], x, y, RT3_FORMAT_R32G32B32A32_SFLOAT, "probe_atlas");
-    Resource* pv = image_checked(c, b[4], x, y, RT3_FORMAT_R32G32B32A32_SFLOAT, "prev_probe_atlas");
-    if (!gb || !dp || !dir || !at || !pv) return RT3_E_INVALID;
-    if (at->ptr == pv->ptr) return fail(c, RT3_E_INVALID, "trace_probes: probe_atlas and prev_probe_atlas must be different images");
-    const uint32_t n = x * y;
+int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t, Resource* const* res) {
+    const Resource *dp = res[1], *dir = res[2], *at = res[3], *pv = res[4];
+    const uint32_t px = at->w / 8, py = at->h / 8, n = at->w * at->h;
     if (int r = ensure_work(c, n, 0)) return r;
-    GConstDev gd;
-    memcpy(&gd, g, sizeof(gd));
     const size_t S = c->cap;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_probe_raygen(c->stream, gd, W, x / 8, y / 8, (const float*)dp->ptr, dir->ptr, at->ptr, c->rays[0].get(), S, c->T[0].get());
+        launch_probe_raygen(c->stream, gconst_dev(g), W, px, py, (const float*)dp->ptr, dir->ptr, at->ptr, c->rays[0].get(), S, c->T[0].get());
     }
     if (int r = trace_primary(c, n)) return r;
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, x / 8, y / 8, c->hits.get(), c->T[0].get(), pv->ptr, at->ptr);
+        launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, px, py, c->hits.get(), c->T[0].get(), pv->ptr, at->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 // spherical_harmonic_conversion.slang:6-7 : set 0 {out}, set 1 {probe_atlas}
-int pass_sh_conversion(rt3_ctx* c, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    if (z != 1 || x == 0 || y == 0 || x > 8191 || y > 8191)
-        return fail(c, RT3_E_INVALID, "spherical_harmonic_conversion: dispatch is probes_x x probes_y x 1 groups of 8x8 threads");
-    if (nb != 2) return fail(c, RT3_E_INVALID, "spherical_harmonic_conversion expects 2 bindings {out, probe_atlas}");
-    Resource* out = get_res(c, b[0], RT3_TAG_BUFFER);
-    Resource* at = image_checked(c, b[1], x * 8, y * 8, RT3_FORMAT_R32G32B32A32_SFLOAT, "probe_atlas");
-    if (!at) return RT3_E_INVALID;
-    const size_t need = ((size_t)zcurve_host(x * 3 - 1, y - 1) + 1) * 48;  // float3x3 elements at Z-curve indices (:30-32)
-    if (!out || out->bytes < need) return fail(c, RT3_E_INVALID, "spherical_harmonic_conversion: 'out' must be a buffer of at least " + std::to_string(need) + " bytes");
+int pass_sh_conversion(rt3_ctx* c, const rt3_gconst*, uint32_t, uint32_t, Resource* const* res) {
+    const Resource *out = res[0], *at = res[1];
+    const uint32_t px = at->w / 8, py = at->h / 8;
+    // float3x3 elements at Z-curve indices (:30-32)
+    if (int r = buffer_at_least(c, out, ((size_t)zcurve_host(px * 3 - 1, py - 1) + 1) * 48, "out")) return r;
     ScopedTimer t(c, CAT_OTHER);
-    launch_sh_conversion(c->stream, x, y, at->ptr, out->ptr);
+    launch_sh_conversion(c->stream, px, py, at->ptr, out->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 // interpolate_probes.slang:6-9 : set 1 {gbuffer, gbuffer_depth, sh_coeficents}, set 2 {Light}
-int pass_interpolate_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1) return fail(c, RT3_E_INVALID, "interpolate_probes: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups");
-    if (nb != 4) return fail(c, RT3_E_INVALID, "interpolate_probes expects 4 bindings {gbuffer, gbuffer_depth, sh_coeficents, Light}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    Resource* sh = get_res(c, b[2], RT3_TAG_BUFFER);
-    Resource* li = image_checked(c, b[3], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Light");
-    if (!gb || !dp || !li) return RT3_E_INVALID;
+int pass_interpolate_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *sh = res[2], *li = res[3];
     const uint32_t npx = W / 16, npy = H / 16;
-    const size_t need = npx && npy ? ((size_t)zcurve_host(npx * 3 - 1, npy - 1) + 1) * 48 : 0;
-    if (!sh || sh->bytes < need) return fail(c, RT3_E_INVALID, "interpolate_probes: 'sh_coeficents' must be a buffer of at least " + std::to_string(need) + " bytes");
-    GConstDev gd;
-    memcpy(&gd, g, sizeof(gd));
+    if (int r = buffer_at_least(c, sh, npx && npy ? ((size_t)zcurve_host(npx * 3 - 1, npy - 1) + 1) * 48 : 0, "sh_coeficents")) return r;
     ScopedTimer t(c, CAT_OTHER);
-    launch_interpolate(c->stream, gd, W, H, gb->ptr, (const float*)dp->ptr, sh->ptr, li->ptr);
+    launch_interpolate(c->stream, gconst_dev(g), W, H, gb->ptr, (const float*)dp->ptr, sh->ptr, li->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
 
 // "denoise": edge-avoiding a-trous filter over the whole window (no reference counterpart)
-int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1) return fail(c, RT3_E_INVALID, "denoise: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups");
-    if (nb != 4) return fail(c, RT3_E_INVALID, "denoise expects 4 bindings {gbuffer, gbuffer_depth, In, Out}");
-    Resource* gb = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
-    Resource* dp = image_checked(c, b[1], W, H, RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
-    Resource* in = image_checked(c, b[2], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "In");
-    Resource* out = image_checked(c, b[3], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Out");
-    if (!gb || !dp || !in || !out) return RT3_E_INVALID;
-    if (in == out || in->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: 'In' and 'Out' must be different images (a tap reads In while other pixels are written)");
-    if (c->n_ranks > 1)
-        return fail(c, RT3_E_STATE, "denoise: a tap needs pixels that other ranks own; run it on the gathered image with the tile partition switched off "
-                                    "(rt3_set_tile_partition(w, h, 0, 1))");
-    Resource* mo = nullptr;
+int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *in = res[2], *out = res[3];
+    const Resource* mo = nullptr;
     if (c->dn_variance_image) {
         mo = image_checked(c, c->dn_variance_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "variance input");
         if (!mo) return RT3_E_INVALID;
-        if (mo == out || mo->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: the variance input (rt3_denoise_set_variance_input) must not be 'Out'");
+        if (mo->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: the variance input (rt3_denoise_set_variance_input) must not be 'Out'");
     }
     const rt3_denoise_params& p = c->dn_params;
     if (p.iterations == 0) {
@@ -825,7 +765,7 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32
         return RT3_OK;
     }
     DenoiseLaunch L;
-    memcpy(&L.g, g, sizeof(L.g));
+    L.g = gconst_dev(g);
     L.W = W; L.H = H; L.squarings = p.normal_squarings; L.flags = p.flags; L.sigma_z = p.sigma_z; L.sigma_l = p.sigma_l;
     L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr; L.in = in->ptr; L.out = out->ptr;
     L.moments = mo ? mo->ptr : nullptr;
@@ -857,36 +797,14 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32
 }
 
 // "temporal": reprojected accumulation of the previous frame's history (no reference counterpart)
-int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1) return fail(c, RT3_E_INVALID, "temporal: dispatch must be ceil(W/8) x ceil(H/8) x 1 groups");
-    if (nb != 10)
-        return fail(c, RT3_E_INVALID, "temporal expects 10 bindings {gbuffer, gbuffer_depth, In, PrevGbuffer, PrevDepth, PrevHistory, PrevMoments, Out, "
-                                      "History, Moments}");
-    static const struct { uint32_t format; const char* name; } kB[10] = {
-        {RT3_FORMAT_R32G32B32A32_UINT, "gbuffer"},       {RT3_FORMAT_R32_SFLOAT, "gbuffer_depth"},        {RT3_FORMAT_R32G32B32A32_SFLOAT, "In"},
-        {RT3_FORMAT_R32G32B32A32_UINT, "PrevGbuffer"},   {RT3_FORMAT_R32_SFLOAT, "PrevDepth"},            {RT3_FORMAT_R32G32B32A32_SFLOAT, "PrevHistory"},
-        {RT3_FORMAT_R32G32B32A32_SFLOAT, "PrevMoments"}, {RT3_FORMAT_R32G32B32A32_SFLOAT, "Out"},         {RT3_FORMAT_R32G32B32A32_SFLOAT, "History"},
-        {RT3_FORMAT_R32G32B32A32_SFLOAT, "Moments"}};
-    Resource* r[10];
-    for (int i = 0; i < 10; i++)
-        if (!(r[i] = image_checked(c, b[i], W, H, kB[i].format, kB[i].name))) return RT3_E_INVALID;
-    for (int i = 7; i < 10; i++)
-        for (int j = 0; j < i; j++)
-            if (r[i] == r[j] || r[i]->ptr == r[j]->ptr)
-                return fail(c, RT3_E_INVALID, std::string("temporal: '") + kB[i].name + "' and '" + kB[j].name +
-                                                  "' must be different images (taps read the previous images while other pixels are written)");
-    if (c->n_ranks > 1)
-        return fail(c, RT3_E_STATE, "temporal: a reprojected tap may belong to pixels that other ranks own; run it on the gathered image with the tile "
-                                    "partition switched off (rt3_set_tile_partition(w, h, 0, 1))");
+int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* r) {
     if (!c->tp_has_prev) return fail(c, RT3_E_STATE, "temporal: no previous view (rt3_temporal_set_prev_view)");
     if (c->tp_prev.window_size[0] != g->window_size[0] || c->tp_prev.window_size[1] != g->window_size[1])
         return fail(c, RT3_E_INVALID, "temporal: the previous view's window_size differs from this frame's (after a resize, start over from zeroed history)");
     const rt3_temporal_params& p = c->tp_params;
     TemporalLaunch L;
-    memcpy(&L.g, g, sizeof(L.g));
-    memcpy(&L.prev, &c->tp_prev, sizeof(L.prev));
+    L.g = gconst_dev(g);
+    L.prev = gconst_dev(&c->tp_prev);
     L.W = W; L.H = H; L.flags = p.flags;
     L.alpha = p.alpha; L.alpha_moments = p.alpha_moments; L.max_history = (float)p.max_history; L.normal_cos = p.normal_cos;
     L.plane_tolerance = p.plane_tolerance;
@@ -894,11 +812,10 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint3
     L.prev_gbuffer = r[3]->ptr; L.prev_depth = (const float*)r[4]->ptr; L.prev_history = r[5]->ptr; L.prev_moments = r[6]->ptr;
     L.out = r[7]->ptr; L.history = r[8]->ptr; L.moments = r[9]->ptr;
     if (c->tp_motion_image) {
-        Resource* mv = image_checked(c, c->tp_motion_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "motion input");
+        const Resource* mv = image_checked(c, c->tp_motion_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "motion input");
         if (!mv) return RT3_E_INVALID;
-        for (int i = 7; i < 10; i++)
-            if (mv == r[i] || mv->ptr == r[i]->ptr)
-                return fail(c, RT3_E_INVALID, std::string("temporal: the motion input (rt3_temporal_set_motion_input) must not be '") + kB[i].name + "'");
+        if (mv->ptr == r[7]->ptr || mv->ptr == r[8]->ptr || mv->ptr == r[9]->ptr)
+            return fail(c, RT3_E_INVALID, "temporal: the motion input (rt3_temporal_set_motion_input) must not be 'Out', 'History' or 'Moments'");
         L.motion = mv->ptr;
     }
     {
@@ -910,37 +827,125 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, uint3
 }
 
 // "motion": where each pixel's surface point was one frame ago (no reference counterpart).  The primary trace is
-// pass_gbuffer's, launch for launch, so the hits are the G-buffer's.
-int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t x, uint32_t y, const uint32_t* b, uint32_t nb) {
-    uint32_t W, H;
-    if (int r = check_window(c, g, &W, &H)) return r;
-    if (x != W || y != H) return fail(c, RT3_E_INVALID, "motion: launch size must be the window size (WorkSize2D::FullScreen, like gbuffer)");
-    if (nb != 1) return fail(c, RT3_E_INVALID, "motion expects 1 binding {Motion}");
-    Resource* mv = image_checked(c, b[0], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "Motion");
-    if (!mv) return RT3_E_INVALID;
+// pass_gbuffer's (primary_hits), so the hits are the G-buffer's.
+int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
     if (int r = motion_tables(c)) return r;
-    PixelList* pl;
-    if (int r = get_pixlist(c, W, H, c->rank, c->n_ranks, &pl)) return r;
-    if (pl->count == 0) return RT3_OK;
-    if (int r = ensure_work(c, pl->count, pl->count)) return r;
     MotionLaunch L;
-    memcpy(&L.g, g, sizeof(L.g));
-    {
-        ScopedTimer t(c, CAT_OTHER);
-        launch_raygen(c->stream, L.g, pl->dev.get(), pl->count, c->rays[0].get(), c->cap);
-    }
-    if (int r = trace_primary(c, pl->count)) return r;
-    L.m.verts = c->d_verts.get(); L.m.indices = c->d_indices.get(); L.m.geoms = c->d_geoms.get();
-    L.m.prim_geom = c->d_prim_geom.get(); L.m.first_prim = c->d_first_prim.get();
+    L.g = gconst_dev(g);
+    PixelList* pl;
+    if (int r = primary_hits(c, L.g, W, H, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    const GeomTables t = world_tables(c);
+    L.m.verts = t.verts; L.m.indices = t.indices; L.m.geoms = t.geoms; L.m.prim_geom = t.prim_geom; L.m.first_prim = t.first_prim;
     L.m.geom_slot = c->mo_any_moved ? c->d_mo_slot.get() : nullptr;
     L.m.prev = c->d_mo_prev.get();
-    L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->hits.get(); L.out = mv->ptr;
+    L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->hits.get(); L.out = res[0]->ptr;
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_motion(c->stream, L);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
+}
+
+// ---- the pass table: everything rt3_pass_launch checks before a pass function runs, and the texts of its errors.  include/rt3.h describes
+//      the same passes for callers.
+enum Shape {
+    kWindow,      // (x, y) = the window exactly (WorkSize2D::FullScreen, executions.rs:73); z is ignored, here and by the next
+    kProbeAtlas,  // (x, y) = the probe atlas, 8 x 8 texels for each of 1x1 .. floor(W/16) x floor(H/16) probes
+    kGroups,      // ceil(W/8) x ceil(H/8) x 1 groups of 8x8 threads (DispatchSize::FullScreen, build.rs:254-258)
+    kProbeGrid    // probes_x x probes_y x 1 groups, one per probe: at most floor(W/16) x floor(H/16), or 8191 x 8191 without a window
+};
+constexpr uint32_t kBuffer = 0;  // a binding that is a buffer, not an image of a format; the pass function checks its size
+constexpr uint32_t kU4 = RT3_FORMAT_R32G32B32A32_UINT, kF4 = RT3_FORMAT_R32G32B32A32_SFLOAT, kF1 = RT3_FORMAT_R32_SFLOAT, kU16 = RT3_FORMAT_R16_UINT;
+constexpr uint32_t kMaxBindings = 10;
+struct Binding {
+    const char* name;       // null: the end of the list
+    uint32_t format;
+    bool atlas = false;     // the image is as large as the probe atlas, not the window
+    uint32_t distinct = 0;  // bit j: the image may not be the one bound at (the earlier) position j
+};
+struct PassDesc {
+    const char* name;
+    Shape shape;
+    bool window;    // reads GConst.window_size
+    bool one_rank;  // reads pixels around its own: refused under a tile partition of several ranks
+    int (*run)(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res);
+    Binding b[kMaxBindings];
+};
+const PassDesc kPasses[] = {
+    {"gbuffer", kWindow, true, false, pass_gbuffer, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}}},
+    {"refrence_mode", kWindow, true, false, pass_reference_mode, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"Light", kF4}, {"PrevLight", kF4}}},
+    {"postprocess", kGroups, true, false, pass_postprocess, {{"Depth", kF1}, {"Out", kF4}, {"In", kF4}}},
+    {"structured_importance_sampling", kProbeGrid, true, false, pass_sis,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"out", kU16, true}, {"debug", kF1, true}, {"probe_atlas", kF4, true}}},
+    {"trace_probes", kProbeAtlas, true, false, pass_trace_probes,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"directions", kU16, true}, {"probe_atlas", kF4, true}, {"prev_probe_atlas", kF4, true, 1u << 3}}},
+    {"spherical_harmonic_conversion", kProbeGrid, false, false, pass_sh_conversion, {{"out", kBuffer}, {"probe_atlas", kF4, true}}},
+    {"interpolate_probes", kGroups, true, false, pass_interpolate_probes,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"sh_coeficents", kBuffer}, {"Light", kF4}}},
+    {"denoise", kGroups, true, true, pass_denoise, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"In", kF4}, {"Out", kF4, false, 1u << 2}}},
+    {"temporal", kGroups, true, true, pass_temporal,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"In", kF4}, {"PrevGbuffer", kU4}, {"PrevDepth", kF1}, {"PrevHistory", kF4}, {"PrevMoments", kF4},
+      {"Out", kF4, false, 0x7Fu}, {"History", kF4, false, 0xFFu}, {"Moments", kF4, false, 0x1FFu}}},
+    {"motion", kWindow, true, false, pass_motion, {{"Motion", kF4}}},
+};
+// a, b, ... : the names of a table's entries
+template <typename T, size_t N>
+std::string names_of(const T (&list)[N]) {
+    std::string s;
+    for (size_t i = 0; i < N && list[i].name; i++) s += (i ? ", " : "") + std::string(list[i].name);
+    return s;
+}
+
+// Checks in this order: window, launch shape, binding count, the bindings in their order, aliasing, tile partition; then the pass function
+int launch_pass(rt3_ctx* c, const PassDesc& p, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
+    const std::string name = p.name;
+    uint32_t W = 0, H = 0, ax = 0, ay = 0;  // the window; the probe atlas
+    if (p.window)
+        if (int r = check_window(c, g, &W, &H)) return r;
+    const uint32_t max_px = p.window ? W / 16 : 8191u, max_py = p.window ? H / 16 : 8191u;
+    switch (p.shape) {
+        case kWindow:
+            if (x != W || y != H) return fail(c, RT3_E_INVALID, name + ": launch size must be the window size (WorkSize2D::FullScreen, executions.rs:73)");
+            break;
+        case kProbeAtlas:
+            if (x % 8 || y % 8 || x == 0 || y == 0 || x / 8 > max_px || y / 8 > max_py)
+                return fail(c, RT3_E_INVALID, name + ": launch size is the probe atlas, 8 x 8 texels per probe, of 1x1 to floor(W/16) x floor(H/16) probes");
+            ax = x, ay = y;
+            break;
+        case kGroups:
+            if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1)
+                return fail(c, RT3_E_INVALID, name + ": dispatch must be ceil(W/8) x ceil(H/8) x 1 groups (DispatchSize::FullScreen, build.rs:254-258)");
+            break;
+        case kProbeGrid:
+            if (z != 1 || x == 0 || y == 0 || x > max_px || y > max_py)
+                return fail(c, RT3_E_INVALID, name + ": dispatch is probes_x x probes_y x 1 groups of 8x8 threads, 1x1 to floor(W/16) x floor(H/16) probes");
+            ax = 8 * x, ay = 8 * y;
+            break;
+    }
+    uint32_t n = 0;
+    while (n < kMaxBindings && p.b[n].name) n++;
+    if (nb != n)
+        return fail(c, RT3_E_INVALID, name + " expects " + std::to_string(n) + (n == 1 ? " binding {" : " bindings {") + names_of(p.b) + "}");
+    Resource* res[kMaxBindings];
+    for (uint32_t i = 0; i < n; i++) {
+        const Binding& bd = p.b[i];
+        if (bd.format == kBuffer) {
+            if (!(res[i] = get_res(c, b[i], RT3_TAG_BUFFER))) return fail(c, RT3_E_INVALID, name + ": binding '" + bd.name + "' is not a buffer");
+        } else if (!(res[i] = image_checked(c, b[i], bd.atlas ? ax : W, bd.atlas ? ay : H, bd.format, bd.name))) {
+            return RT3_E_INVALID;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = 0; j < i; j++)
+            if ((p.b[i].distinct >> j & 1u) && res[i]->ptr == res[j]->ptr)
+                return fail(c, RT3_E_INVALID, name + ": '" + p.b[i].name + "' and '" + p.b[j].name +
+                                                  "' must be different images (one is read while pixels of the other are written)");
+    if (p.one_rank && c->n_ranks > 1)
+        return fail(c, RT3_E_STATE, name + ": a tap may need pixels that other ranks own; run it on the gathered image with the tile partition "
+                                           "switched off (rt3_set_tile_partition(w, h, 0, 1))");
+    return p.run(c, g, W, H, res);
 }
 
 }  // namespace
@@ -1463,8 +1468,7 @@ static int make_shade_records(rt3_ctx* c) {
         if (int r = dev_alloc(c, s.uv, 3 * (size_t)c->n_flat_prims)) return r;
         s.n = c->n_flat_prims;
     }
-    launch_tri_shade(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(), c->n_flat_prims,
-                     s.rec.get(), s.uv.get());
+    launch_tri_shade(c->stream, world_tables(c), c->n_flat_prims, s.rec.get(), s.uv.get());
     HIPC(c, hipGetLastError());
     s.key = std::move(key);
     return RT3_OK;
@@ -1493,8 +1497,7 @@ static int ensure_lights(rt3_ctx* c) {
         }
     if (geom_base.size() != c->n_flat_geoms) return fail(c, RT3_E_STATE, "emitter table: the placements changed since rt3_accel_build");
     HIPC(c, hipSetDevice(c->device));
-    const hipError_t e = lights_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                                      geom_base, eg_geom, eg_first, (uint32_t)n, &c->lights);
+    const hipError_t e = lights_build(c->stream, world_tables(c), geom_base, eg_geom, eg_first, (uint32_t)n, &c->lights);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("emitter table: ") + hipGetErrorString(e));
     c->lights.stamp = c->accel_stamp;
     return RT3_OK;
@@ -1568,8 +1571,8 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
     MeshTables t;
     hipError_t e = make_mesh_tables(c, m, &t);
     if (e == hipSuccess)
-        e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse,
-                       c->opt_sah_top, c->build_scratch, res, c->accel_masked ? c->d_geom_mask.get() : nullptr);
+        e = lbvh_build(c->stream, mesh_tables(c, t), m.n_tris, c->opt_leaf_size, 4, 1, c->opt_collapse, c->opt_sah_top, c->build_scratch, res,
+                       c->accel_masked ? c->d_geom_mask.get() : nullptr);
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1818,7 +1821,7 @@ static int tl_records_and_top(rt3_ctx* c) {
     HIPC(c, hipMemsetAsync(zeros, 0, ((size_t)n_ne + 1) * 4, c->stream));
     tlas_box_tris(c->stream, boxes_d, n_ne, verts, idx);
     LbvhResult top;
-    hipError_t e = lbvh_build(c->stream, verts, idx, tbl, zeros, zeros + n_ne, n_ne, 1u, 4u, 1u, c->opt_collapse, 1u, c->build_scratch, &top);
+    hipError_t e = lbvh_build(c->stream, GeomTables{verts, idx, tbl, zeros, zeros + n_ne}, n_ne, 1u, 4u, 1u, c->opt_collapse, 1u, c->build_scratch, &top);
     if (e == hipSuccess && top.n_nodes > top_cap) e = hipErrorInvalidValue;  // cannot happen (see top_cap); never write past the top's region
     if (e == hipSuccess) {
         tlas_emit_top(c->stream, top.nodes.get(), top.n_nodes, top.tris.get(), top_cap, c->bvh.nodes.get());
@@ -1914,9 +1917,8 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
         if (int r = build_two_level(c)) return r;
     } else {
         free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
-        hipError_t e = lbvh_build(c->stream, c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                                  c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse, c->opt_sah_top, c->build_scratch,
-                                  &c->bvh, c->accel_masked ? c->d_geom_mask.get() : nullptr);
+        hipError_t e = lbvh_build(c->stream, world_tables(c), c->n_flat_prims, c->opt_leaf_size, c->opt_node_width, c->opt_node_quant, c->opt_collapse,
+                                  c->opt_sah_top, c->build_scratch, &c->bvh, c->accel_masked ? c->d_geom_mask.get() : nullptr);
         if (c->build_scratch.capacity_bytes() > ((size_t)1 << 30)) c->build_scratch.reset();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
             free_accel(c);  // (what the failed build allocated)
@@ -2055,8 +2057,8 @@ static int refit_flat(rt3_ctx* c) {
     }
     RefitScratch s;
     if (int r = refit_scratch(c, b.n_nodes, b.n_tris, &s)) return r;
-    hipError_t e = refit_tree(c->stream, c->refit_trees[0], c->d_verts.get(), c->d_indices.get(), c->d_geoms.get(), c->d_prim_geom.get(), c->d_first_prim.get(),
-                              c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), s.bounds, s.nbox, s.tbox);
+    hipError_t e = refit_tree(c->stream, c->refit_trees[0], world_tables(c), c->n_flat_prims, 0u, b.n_tris, b.nodes.get(), b.tris.get(), s.bounds, s.nbox,
+                              s.tbox);
     if (e == hipSuccess) e = lbvh_make_top(c->stream, b.nodes.get(), b.n_nodes, b.top, &b.n_top);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_refit: ") + hipGetErrorString(e));
     return RT3_OK;
@@ -2089,9 +2091,8 @@ static int refit_two_level(rt3_ctx* c) {
     hipError_t e = hipSuccess;
     for (size_t q = 0; e == hipSuccess && q < nm; q++) {
         const TlMesh& m = meshes[q];
-        const MeshTables& t = c->refit_tables[q];
-        e = refit_tree(c->stream, c->refit_trees[q], c->d_verts.get(), c->d_indices.get(), t.geoms, t.prim_geom, t.first_prim, m.n_tris, m.tri_off, m.n_tris,
-                       c->bvh.nodes.get(), c->bvh.tris.get(), s.bounds, s.nbox, s.tbox);
+        e = refit_tree(c->stream, c->refit_trees[q], mesh_tables(c, c->refit_tables[q]), m.n_tris, m.tri_off, m.n_tris, c->bvh.nodes.get(), c->bvh.tris.get(),
+                       s.bounds, s.nbox, s.tbox);
         if (e == hipSuccess) e = hipMemcpyAsync(&roots[16 * q], c->bvh.nodes.get() + 4 * (size_t)m.node_off, 64, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -2408,19 +2409,9 @@ int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32
                                         std::to_string(c->h_tex.size()) + " texture(s) were set (rt3_scene_set_texture)");
     rt3_gconst g;
     memcpy(&g, constants, sizeof(g));
-    if (!strcmp(pass_name, "gbuffer")) return pass_gbuffer(c, &g, x, y, bindings, n_bindings);
-    if (!strcmp(pass_name, "refrence_mode")) return pass_reference_mode(c, &g, x, y, bindings, n_bindings);
-    if (!strcmp(pass_name, "postprocess")) return pass_postprocess(c, &g, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "structured_importance_sampling")) return pass_sis(c, &g, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "trace_probes")) return pass_trace_probes(c, &g, x, y, bindings, n_bindings);
-    if (!strcmp(pass_name, "spherical_harmonic_conversion")) return pass_sh_conversion(c, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "interpolate_probes")) return pass_interpolate_probes(c, &g, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "denoise")) return pass_denoise(c, &g, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "temporal")) return pass_temporal(c, &g, x, y, z, bindings, n_bindings);
-    if (!strcmp(pass_name, "motion")) return pass_motion(c, &g, x, y, bindings, n_bindings);
-    return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name +
-                                      "' (known: gbuffer, refrence_mode, postprocess, structured_importance_sampling, trace_probes, "
-                                      "spherical_harmonic_conversion, interpolate_probes, denoise, temporal, motion)");
+    for (const PassDesc& p : kPasses)
+        if (!strcmp(pass_name, p.name)) return launch_pass(c, p, &g, x, y, z, bindings, n_bindings);
+    return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name + "' (known: " + names_of(kPasses) + ")");
 }
 int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
     if (!c) return RT3_E_INVALID;

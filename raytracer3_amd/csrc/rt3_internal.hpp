@@ -41,40 +41,57 @@ enum TotalsWord : int {
     kTotWords = 6
 };
 
+// One k_shade launch (refrence_mode.slang:28-57 for one bounce of every live path): the kernel's argument, filled by the host.  launch_shade
+// sets npix_div, sizes the grid from n_first and picks the instance.
 struct ShadeLaunch {
     GConstDev g;
     SceneDev sc;
-    const uint32_t* pixels;
-    const uint2* pixbn;
-    uint32_t npix, width, s0, bounce;
-    const void* gbuffer;
+    const uint32_t* pixels;  // x | y << 16, this rank's pixels in render order
+    const uint2* pixbn;      // the same list with each pixel's blue-noise word beside it
+    uint32_t npix, width;
+    FastDiv npix_div;        // path id = sample_in_batch * npix + pixel_index
+    uint32_t s0;             // first sample index of this batch
+    uint32_t bounce;         // b
+    // FIRST: gbuffer images
+    const uint4* gbuffer;
     const float* depth;
+    // !FIRST: input queue
     const float* in_rays;
     const float* in_hits;
-    const float* in_T;
+    const float* in_T;       // throughput: three planes of `stride` floats (the path's pdf and id ride in the .w of its two ray records)
     const uint32_t* in_count;
-    uint32_t n_first;
+    uint32_t n_first;        // npix * samples_in_batch: the paths of bounce 0, an upper bound of the live paths after it
+    // outputs
     float* out_rays;
     float* out_T;
     uint32_t* out_count;
     float* sh_rays;
     float* sh_contrib;
     uint32_t* sh_count;
-    float* lacc;
+    float* lacc;             // float4 {r, g, b, -} per path id
     size_t stride;
-    uint32_t max_n;  // upper bound of live paths (grid sizing)
-    // RT3_F_NEE_EMISSIVE: the emitter table and the second shadow queue; lights.n == 0 = the flag is off
+    // EMIT (RT3_F_NEE_EMISSIVE): the emitter table and the emitter shadow queue {o, c.r} {d, c.g} {c.b, path id} + range
+    // end, and its count; lights.n == 0 = the flag is off
     LightsDev lights;
     float* sh2_rays;
     float* sh2_contrib;
     float* sh2_tmax;
     uint32_t* sh2_count;
 };
+// The geometry tables a builder reads triangles through: primitive p belongs to geoms[prim_geom[p]] and is that geometry's triangle
+// p - first_prim[prim_geom[p]], its corners found through the geometry's offsets into indices and verts.  The five go together: the
+// flattened world's, or the world's verts and indices with a bottom tree's tables (local primitive ids).
+struct GeomTables {
+    const float* verts;
+    const uint32_t* indices;
+    const FlatGeomDev* geoms;
+    const uint32_t *prim_geom, *first_prim;
+};
 
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
-void launch_shade(hipStream_t st, bool first, const ShadeLaunch& L);
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,
@@ -221,8 +238,7 @@ void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
 // LBVH build (rt3_lbvh.hip).  All pointers are device memory owned by the caller.  The build's scratch is carved from `scratch`, which grows
 // to what this configuration and size need and is kept for the next build.  On failure *out may hold some of its arrays: they go with it.
 // geom_mask: the alpha-mask words of the triangle records per uploaded geometry, or null (every record {v2.z, prim, 0, 0}).
-hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
+hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
                       uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask = nullptr);
 // Scratch of the binned-SAH top (rt3_sah_top.hip), part of the builder's: sah_top_plan adds it to `plan` for a tree over n triangles (at
 // most n clusters under n - 1 top nodes).  The segment and tile records are of types private to rt3_sah_top.hip.
@@ -241,8 +257,7 @@ hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t nn, uint32_t* left, uint3
                               const float* lmin, const float* lmax, float* nbox, uint32_t T, const SahTopScratch& s, bool* relinked);
 
 // shading records (SceneDev::tri_shade, tri_uv) of n flattened primitives: they depend on no tree and no matrix
-void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n, uint4* tri_shade, float2* tri_uv);
+void launch_tri_shade(hipStream_t st, GeomTables t, uint32_t n, uint4* tri_shade, float2* tri_uv);
 
 // Two-level structure (rt3_tlas.hip).  One node array: [top tree | two 64-byte records per instance | bottom trees], one triangle array of
 // the bottom trees' object-space records (local primitive ids).
@@ -263,12 +278,11 @@ struct RefitTree {
 };
 // max_depth: the tree's levels down to the leaf slots (LbvhResult::max_depth); hipErrorInvalidValue if the node array disagrees with it
 hipError_t refit_plan(hipStream_t st, const float4* nodes, uint32_t root, uint32_t n_nodes, uint32_t max_depth, RefitTree* plan);
-// Rewrites the triangle records [tri_first, tri_first + n_tris) from their primitives (fetched through geoms / prim_geom / first_prim; the
-// leaf pad from the bounds of primitives 0 .. n_prims-1) and then every node of the plan.  Scratch: bounds (6 words), nbox (6 floats per
-// node of `nodes`), tbox (6 floats per record of `tris`).
-hipError_t refit_tree(hipStream_t st, const RefitTree& plan, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes, float4* tris, uint32_t* bounds,
-                      float* nbox, float* tbox);
+// Rewrites the triangle records [tri_first, tri_first + n_tris) from their primitives (fetched through `t`; the leaf pad from the bounds of
+// primitives 0 .. n_prims-1) and then every node of the plan.  Scratch: bounds (6 words), nbox (6 floats per node of `nodes`), tbox (6
+// floats per record of `tris`).
+hipError_t refit_tree(hipStream_t st, const RefitTree& plan, GeomTables t, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes,
+                      float4* tris, uint32_t* bounds, float* nbox, float* tbox);
 
 // Emitter table of RT3_F_NEE_EMISSIVE (rt3_lights.hip): every flattened primitive of a geometry with non-zero emission,
 // in flattened order.  Selection by an integer CDF on the 2^-23 grid of uniform_float; records as LightsDev describes.
@@ -288,8 +302,7 @@ struct LightTable {
 };
 // geom_base: per flattened geometry its first emitter or kMiss (host table, n_flat_geoms entries); eg_geom / eg_first: the emissive flattened
 // geometries and their first emitter (n_eg entries); n: emitters.  Reads back nothing but the CDF's last word (into *total).
-hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                        const uint32_t* first_prim, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
+hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
                         const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out);
 
 // "denoise" pass (rt3_denoise.hip).  Scratch: two guide records and two signal images of W x H float4, carved from the

@@ -750,41 +750,6 @@ __device__ __forceinline__ BlockAppend3 block_append3(bool want_ext, bool want_s
 // the emitter shadow ray ends this far along its way to the sampled point: the emitter never occludes itself, another one in front does
 constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
 
-struct ShadeArgs {
-    GConstDev g;
-    SceneDev sc;
-    const uint32_t* pixels;  // x | y << 16, this rank's pixels in render order
-    const uint2* pixbn;      // the same list with each pixel's blue-noise word beside it
-    uint32_t npix, width;
-    FastDiv npix_div;        // path id = sample_in_batch * npix + pixel_index
-    uint32_t s0;             // first sample index of this batch
-    uint32_t bounce;         // b
-    // FIRST: gbuffer images
-    const uint4* gbuffer;
-    const float* depth;
-    // !FIRST: input queue
-    const float* in_rays;
-    const float* in_hits;
-    const float* in_T;       // throughput: three planes of `stride` floats (the path's pdf and id ride in the .w of its two ray records)
-    const uint32_t* in_count;
-    uint32_t n_first;        // FIRST: npix * samples_in_batch
-    // outputs
-    float* out_rays;
-    float* out_T;
-    uint32_t* out_count;
-    float* sh_rays;
-    float* sh_contrib;
-    uint32_t* sh_count;
-    float* lacc;             // float4 {r, g, b, -} per path id
-    size_t stride;
-    // EMIT (RT3_F_NEE_EMISSIVE): the emitter table and the emitter shadow queue {o, c.r} {d, c.g} {c.b, path id} + range end, and its count
-    LightsDev lights;
-    float* sh2_rays;
-    float* sh2_contrib;
-    float* sh2_tmax;
-    uint32_t* sh2_count;
-};
-
 // refrence_mode.slang:28-57 for one bounce of every live path
 // GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
 // normal matrix cost an LDS read behind the shading record instead of a second dependent global gather
@@ -792,7 +757,7 @@ struct ShadeArgs {
 template <bool FIRST, bool GLDS, bool EMIT = false>
 // 6 waves per SIMD (80 VGPRs, 32 bytes of scratch): the kernel lives off memory-level parallelism -- 28.8 -> 27.7 ms against the
 // compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks)
-__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_shade(ShadeArgs a) {
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_shade(ShadeLaunch a) {
     __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
     __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
     if (GLDS) {
@@ -1408,18 +1373,9 @@ __global__ void k_pixbn(const uint32_t* __restrict__ pixels, uint32_t npix, cons
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out) {
     hipLaunchKernelGGL(k_pixbn, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, pixels, npix, bluenoise, bn_w, bn_h, out);
 }
-void launch_shade(hipStream_t st, bool first, const ShadeLaunch& L) {
-    ShadeArgs a;
-    a.g = L.g; a.sc = L.sc; a.pixels = L.pixels; a.npix = L.npix; a.width = L.width; a.s0 = L.s0; a.bounce = L.bounce;
-    a.npix_div = make_fastdiv(L.npix);
-    a.pixbn = L.pixbn;
-    a.gbuffer = (const uint4*)L.gbuffer; a.depth = L.depth;
-    a.in_rays = L.in_rays; a.in_hits = L.in_hits; a.in_T = L.in_T; a.in_count = L.in_count; a.n_first = L.n_first;
-    a.out_rays = L.out_rays; a.out_T = L.out_T; a.out_count = L.out_count;
-    a.sh_rays = L.sh_rays; a.sh_contrib = L.sh_contrib; a.sh_count = L.sh_count;
-    a.lacc = L.lacc; a.stride = L.stride;
-    a.lights = L.lights; a.sh2_rays = L.sh2_rays; a.sh2_contrib = L.sh2_contrib; a.sh2_tmax = L.sh2_tmax; a.sh2_count = L.sh2_count;
-    unsigned grid = grid_for(L.max_n, kShadeBlock, 8192);
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a) {
+    a.npix_div = make_fastdiv(a.npix);
+    unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
     if (a.lights.n != 0u) {  // RT3_F_NEE_EMISSIVE with something to sample
         if (first) hipLaunchKernelGGL((k_shade<true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);

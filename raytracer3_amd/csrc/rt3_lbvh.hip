@@ -115,11 +115,10 @@ __global__ void k_tri_shade(const float* verts, const uint32_t* indices, const F
     }
 }
 
-void launch_tri_shade(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n, uint4* tri_shade, float2* tri_uv) {
+void launch_tri_shade(hipStream_t st, GeomTables t, uint32_t n, uint4* tri_shade, float2* tri_uv) {
     if (n == 0) return;
     const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + 255) / 256);
-    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, tri_shade, tri_uv);
+    hipLaunchKernelGGL(k_tri_shade, dim3(grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n, tri_shade, tri_uv);
 }
 
 __device__ __forceinline__ uint64_t expand21(uint32_t v) {
@@ -767,8 +766,7 @@ hipError_t plan_scratch(hipStream_t st, uint32_t n, int quant, int collapse, boo
 }
 }  // namespace
 
-hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
+hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
                       uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask) {
     *out = LbvhResult{};
     out->n_tris = n;
@@ -801,10 +799,10 @@ hipError_t lbvh_build(hipStream_t st, const float* verts, const uint32_t* indice
     RT3_TRY(hipMemcpyAsync(s.bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
     RT3_TRY(hipMemsetAsync(s.arrive, 0, (size_t)nn * 4, st));
     RT3_TRY(hipMemsetAsync(s.levels, 0, 4, st));
-    hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n, s.bmin, s.bmax, s.bounds);
+    hipLaunchKernelGGL(k_prim_bounds, dim3(grid > 512 ? 512 : grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n, s.bmin, s.bmax, s.bounds);
     hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, s.bmin, s.bmax, s.bounds, n, s.keys_in, s.vals_in);
     RT3_TRY(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, s.sort_bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)n, 0, 63, st));
-    hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, s.vals_out, s.bmin, s.bmax, s.bounds, n,
+    hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, s.vals_out, s.bmin, s.bmax, s.bounds, n,
                        s.tris_dp ? s.tris_dp : (s.tris_morton ? s.tris_morton : out->tris.get()), s.lmin, s.lmax, geom_mask);
     if (n == 1) {
         RT3_TRY(out->nodes.alloc_bytes(out->node_bytes));

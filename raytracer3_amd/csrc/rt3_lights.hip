@@ -96,8 +96,7 @@ static hipError_t alloc_n(DevBuf<T>& b, size_t n) {
     return b.alloc_bytes((n ? n : 1) * sizeof(T));
 }
 
-hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                        const uint32_t* first_prim, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
+hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
                         const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out) {
     out->stamp = 0;
     out->n = out->total = 0;
@@ -137,7 +136,7 @@ hipError_t lights_build(hipStream_t st, const float* verts, const uint32_t* indi
     const uint32_t* d_eg_geom = out->geom_base.get() + ng;
     const uint32_t* d_eg_first = d_eg_geom + neg;
     RT3_TRY(hipMemsetAsync(max_power, 0, 4, st));
-    hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n)), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, d_eg_geom, d_eg_first, (uint32_t)neg, n,
+    hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, d_eg_geom, d_eg_first, (uint32_t)neg, n,
                        out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
     hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, power, max_power, n, q);
     RT3_TRY(hipcub::DeviceScan::InclusiveSum(scan_tmp, scan_bytes, q, prefix, (int)n, st));

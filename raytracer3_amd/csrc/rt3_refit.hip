@@ -182,15 +182,14 @@ hipError_t refit_plan(hipStream_t st, const float4* nodes, uint32_t root, uint32
     return hipSuccess;
 }
 
-hipError_t refit_tree(hipStream_t st, const RefitTree& plan, const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                      const uint32_t* first_prim, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes, float4* tris, uint32_t* bounds,
-                      float* nbox, float* tbox) {
+hipError_t refit_tree(hipStream_t st, const RefitTree& plan, GeomTables t, uint32_t n_prims, uint32_t tri_first, uint32_t n_tris, float4* nodes,
+                      float4* tris, uint32_t* bounds, float* nbox, float* tbox) {
     hipError_t e = hipMemsetAsync(bounds, 0xFF, 12, st);  // min: ordered +inf and beyond; max: 0 = below every ordered float
     if (e == hipSuccess) e = hipMemsetAsync(bounds + 3, 0, 12, st);
     if (e != hipSuccess) return e;
-    if (n_prims) hipLaunchKernelGGL(k_refit_bounds, dim3(grid_for(n_prims, 512)), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, n_prims, bounds);
+    if (n_prims) hipLaunchKernelGGL(k_refit_bounds, dim3(grid_for(n_prims, 512)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n_prims, bounds);
     if (n_tris)
-        hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n_tris, 4096)), dim3(256), 0, st, verts, indices, geoms, prim_geom, first_prim, bounds, tri_first, n_tris,
+        hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n_tris, 4096)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, bounds, tri_first, n_tris,
                            tris, tbox);
     uint32_t start = 0;
     for (uint32_t c : plan.level_count) start += c;
