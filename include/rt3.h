@@ -214,6 +214,24 @@ int rt3_scene_set_instances(rt3_ctx *ctx, const rt3_instance *instances, uint32_
  * it must be the instance count of the built structure (1 when no instances were set) or 0, else RT3_E_STATE.  Borrowed for the call; the
  * device table (64 B per instance) is uploaded when the matrices or the structure changed. */
 int rt3_scene_set_prev_transforms(rt3_ctx *ctx, const float *transforms /* n x 16, column-major */, uint32_t n);
+/* ---- previous vertex positions: what lets the "motion" pass (below) follow a mesh that rt3_scene_update_vertices deforms (skinning, cloth,
+ *      morph targets).  DESIGN.md section 4i.
+ *      rt3_scene_snapshot_vertices: the positions the vertex buffer holds now become "the previous frame's".  A device-side copy on the
+ *      context's stream into a buffer of the context, one 16-byte record {x, y, z, 0} per vertex; the first snapshot copies every vertex, a
+ *      later one only the ranges rt3_scene_update_vertices touched since the snapshot before it.  Call it before the frame's updates.
+ *      RT3_E_STATE before rt3_scene_set_vertices.  The acceleration structure does not become stale; no build or refit reads the snapshot.
+ *      rt3_scene_forget_prev_vertices: no previous positions; "motion" is what it is without them.  rt3_scene_set_vertices,
+ *      rt3_scene_set_indices and rt3_scene_set_geometry forget them too (with another topology the previous hit point means nothing).
+ *      Which geometries are deformed is defined by the data, not by the calls made: geometry g is deformed when some vertex of its span
+ *      [vertex_offset + least index, vertex_offset + largest index] (over its triangles) differs from the snapshot in one of its three
+ *      position words, compared as uint32 (-0 is not +0, as for matrices).  Normal and uv words do not count, so neither does sending the
+ *      same positions again.  A vertex inside the span that no triangle of the geometry indexes still counts.  The flags are computed on
+ *      the device when "motion" is launched (or here) after a snapshot, an update or a forget, over the updated ranges only.
+ *      rt3_scene_deformed_geometries: introspection for tests, one byte (0 / 1) per geometry of rt3_scene_set_geometry.  RT3_E_STATE without
+ *      a snapshot, RT3_E_INVALID when n is not the geometry count. ---- */
+int rt3_scene_snapshot_vertices(rt3_ctx *ctx);
+int rt3_scene_forget_prev_vertices(rt3_ctx *ctx);
+int rt3_scene_deformed_geometries(rt3_ctx *ctx, uint8_t *flags, uint32_t n);
 
 /* ---- acceleration structure: create_acceleration_structure (vulkan/raytracing.rs:88-148) -> GPU LBVH.
  *      Returns the handle (tag 3) in *out_handle, like the TLAS registered at bindless/mod.rs:314-337 ---- */
@@ -364,8 +382,9 @@ int rt3_denoise_set_variance_input(rt3_ctx *ctx, uint32_t moments_image);
  *      In.a}: displayable, and a valid In for "denoise".  Background pixels: Out = In bit for bit, History = Moments = 0.
  *      PrevHistory.w > 0 is the reset rule: zeroed previous images mean "no history" (first frame, resize, new scene).  fp32, equal to
  *      tests/ref_temporal.py bit for bit.  Without a motion input (rt3_temporal_set_motion_input, below) the scene is taken as static between
- *      the two frames; with one, instances whose matrices changed keep their history.  Geometry moved by rt3_scene_update_vertices has
- *      no previous vertices and is caught only as far as the plane test catches it.
+ *      the two frames; with one, instances whose matrices changed keep their history, and so do meshes deformed by
+ *      rt3_scene_update_vertices after a rt3_scene_snapshot_vertices; without a snapshot such a mesh has no previous vertices and is caught
+ *      only as far as the plane test catches it.
  *      The three written images must differ from each other and from every image read (RT3_E_INVALID).  Under a tile partition with more
  *      than one rank the pass returns RT3_E_STATE, like "denoise".  A launch with no previous view set returns RT3_E_STATE; a previous
  *      window_size that differs from the launch's is RT3_E_INVALID.
@@ -394,7 +413,12 @@ int rt3_temporal_set_params(rt3_ctx *ctx, const rt3_temporal_params *params);
  *        otherwise                                                                  -> {P', 2}, P' = prev_i * p, p = (a w + b u) + c v with
  *                                                                                      w = (1 - u) - v and a, b, c the triangle's vertices
  *                                                                                      in object space (P' = p when prev_i is the identity)
- *      fp32, singly rounded, equal to tests/ref_motion.py bit for bit.  RT3_E_STATE without a structure, while vertices are stale, or when
+ *        the hit geometry is deformed (rt3_scene_snapshot_vertices, above), whether or
+ *        not instance i moved                                                       -> {P'', 3}, P'' = M * p'', p'' the same expression over
+ *                                                                                      the triangle's three snapshot positions; M = prev_i, or
+ *                                                                                      instance i's current matrix without previous
+ *                                                                                      transforms (P'' = p'' when M is the identity)
+ *      fp32, singly rounded, equal to tests/ref_motion.py and tests/ref_deform.py bit for bit.  RT3_E_STATE without a structure, while vertices are stale, or when
  *      the number of previous transforms is neither 0 nor the structure's instance count.  Works under a tile partition like "gbuffer".
  *      rt3_temporal_set_motion_input: the Motion image "temporal" reads; 0 (the default) = none, and every bit "temporal" writes is what it
  *      was.  With one, a foreground pixel whose texel has w < 1 gets no history (N = 1); otherwise the texel's xyz takes P's place in the
@@ -403,7 +427,8 @@ int rt3_temporal_set_params(rt3_ctx *ctx, const rt3_temporal_params *params);
  *      RT3_E_INVALID.
  *      Limits: the normal test compares this frame's normal with the previous G-buffer's, so an instance that turns by more than
  *      acos(normal_cos) in one frame loses its history; light that moves (a moved object's shadow, a moved emitter) still lags on unmoved
- *      surfaces. ---- */
+ *      surfaces; "deformed" is per geometry, so the still part of a deformed mesh pays for the gather (its texel is its own point);
+ *      there are no previous normals: a surface that bends by more than acos(normal_cos) in one frame loses its history. ---- */
 int rt3_temporal_set_motion_input(rt3_ctx *ctx, uint32_t motion_image);
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */

@@ -38,6 +38,7 @@ EXPORTS = [
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
+    "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
 
@@ -174,6 +175,9 @@ def load():
         "rt3_temporal_set_params": (i32, [vp, C.POINTER(TemporalParams)]),
         "rt3_scene_set_prev_transforms": (i32, [vp, vp, u32]),
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
+        "rt3_scene_snapshot_vertices": (i32, [vp]),
+        "rt3_scene_forget_prev_vertices": (i32, [vp]),
+        "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),
         "rt3_frame_wait": (i32, [vp]),
         "rt3_trace_rays": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double)]),
         "rt3_selftest_eval": (i32, [vp, i32, vp, u32, vp]),

@@ -206,6 +206,17 @@ struct rt3_ctx {
     uint64_t mo_stamp = 0;
     DevBuf<MotionPrevDev> d_mo_prev;
     DevBuf<uint32_t> d_mo_slot;
+    bool mo_any_deformed = false;
+    // deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex ranges
+    // rt3_scene_update_vertices touched since it, sorted and merged; per uploaded geometry its vertex span [lo, hi] (lo > hi: no triangle)
+    // and, once deform_flags has run, whether some position word inside the span differs from the snapshot
+    DevBuf<float4> d_prev_pos;
+    bool df_snapshot = false, df_dirty = false;
+    std::vector<std::pair<uint32_t, uint32_t>> df_ranges;  // [first, end)
+    std::vector<std::pair<uint32_t, uint32_t>> h_geom_span;
+    std::vector<uint32_t> h_deformed;
+    DevBuf<uint32_t> d_deformed;
+    DevBuf<uint4> d_df_chunks;
     rt3_stats stats;
     uint64_t primary_rays_pending = 0;
     std::vector<Timed> pending_events;
@@ -214,6 +225,7 @@ struct rt3_ctx {
 
 static int ensure_lights(rt3_ctx* c);
 static int motion_tables(rt3_ctx* c);
+static int deform_flags(rt3_ctx* c);
 
 namespace {
 
@@ -840,6 +852,7 @@ int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resourc
     L.m.geom_slot = c->mo_any_moved ? c->d_mo_slot.get() : nullptr;
     L.m.prev = c->d_mo_prev.get();
     L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->hits.get(); L.out = res[0]->ptr;
+    L.prev_pos = c->mo_any_deformed ? c->d_prev_pos.get() : nullptr;
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_motion(c->stream, L);
@@ -1051,6 +1064,67 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
 }
 
 // ---- scene
+// [first, end) joins the sorted list of disjoint ranges; ranges that touch merge.  A list that grows long collapses into its hull.
+static void add_dirty_range(std::vector<std::pair<uint32_t, uint32_t>>& ranges, uint32_t first, uint32_t end) {
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    bool placed = false;
+    for (const auto& r : ranges) {
+        if (r.second < first) out.push_back(r);
+        else if (end < r.first) {
+            if (!placed) out.push_back({first, end});
+            placed = true;
+            out.push_back(r);
+        } else {
+            first = std::min(first, r.first);
+            end = std::max(end, r.second);
+        }
+    }
+    if (!placed) out.push_back({first, end});
+    if (out.size() > 64) out.assign(1, {out.front().first, out.back().second});
+    ranges.swap(out);
+}
+// no previous positions: "motion" is what it is without them
+static void forget_snapshot(rt3_ctx* c) {
+    c->df_snapshot = false;
+    c->df_ranges.clear();
+    c->df_dirty = true;
+}
+// Which geometries are deformed: geometry g is when some vertex of its span differs from the snapshot in a position
+// word.  Only vertices updated since the snapshot can differ, so the compare kernel runs over the spans' intersections with the dirty
+// ranges, in chunks of at most kDeformChunk vertices; with none no kernel runs.  Leaves the flags in h_deformed and marks the motion
+// tables for a rebuild.
+static int deform_flags(rt3_ctx* c) {
+    if (!c->df_dirty) return RT3_OK;
+    c->h_deformed.assign(c->n_geoms, 0u);
+    std::vector<uint4> chunks;
+    if (c->df_snapshot)
+        for (uint32_t g = 0; g < c->n_geoms && g < c->h_geom_span.size(); g++) {
+            const auto [lo, hi] = c->h_geom_span[g];
+            if (lo > hi) continue;
+            for (const auto& r : c->df_ranges) {  // (every range lies inside the vertex buffer and the snapshot: rt3_scene_update_vertices)
+                const uint32_t a = std::max(lo, r.first), b = std::min(hi + 1u, r.second);
+                for (uint32_t at = a; at < b; at += kDeformChunk) chunks.push_back(make_uint4(g, at, std::min(b, at + kDeformChunk), 0u));
+            }
+        }
+    if (!chunks.empty()) {
+        HIPC(c, hipSetDevice(c->device));
+        HIPC(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the chunk table
+        HIPC(c, c->d_df_chunks.grow_bytes(chunks.size() * sizeof(uint4)));
+        HIPC(c, c->d_deformed.grow_bytes((size_t)c->n_geoms * 4));
+        HIPC(c, hipMemcpy(c->d_df_chunks.get(), chunks.data(), chunks.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        HIPC(c, hipMemsetAsync(c->d_deformed.get(), 0, (size_t)c->n_geoms * 4, c->stream));
+        {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_compare_positions(c->stream, c->d_verts.get(), c->d_prev_pos.get(), c->d_df_chunks.get(), (uint32_t)chunks.size(), c->d_deformed.get());
+        }
+        HIPC(c, hipGetLastError());
+        HIPC(c, hipMemcpyAsync(c->h_deformed.data(), c->d_deformed.get(), (size_t)c->n_geoms * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+    }
+    c->df_dirty = false;
+    c->mo_dirty = true;
+    return RT3_OK;
+}
 int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (!c || (!v && n)) return fail(c, RT3_E_INVALID, "vertices NULL");
     // a NaN / infinite position would poison the scene bounds, the Morton codes and every box above it: reject it here
@@ -1063,6 +1137,7 @@ int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (n) HIPC(c, hipMemcpy(c->d_verts.get(), v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->n_verts = n;
     invalidate_topology(c);
+    forget_snapshot(c);
     return RT3_OK;
 }
 // vertices [first, first + n) in place; the shape of every tree stays, so a structure built before is stale, not gone (rt3_accel_refit)
@@ -1078,6 +1153,45 @@ int rt3_scene_update_vertices(rt3_ctx* c, const float* v, uint32_t first, uint32
     c->content_gen++;
     if (c->accel_built) c->accel_stale = true;
     HIPC(c, hipMemcpy(c->d_verts.get() + 8 * (size_t)first, v, (size_t)n * 32, hipMemcpyHostToDevice));
+    if (c->df_snapshot) {
+        add_dirty_range(c->df_ranges, first, first + n);
+        c->df_dirty = true;
+    }
+    return RT3_OK;
+}
+// "the positions the vertex buffer holds now are the previous frame's" (DESIGN.md section 4i): a device-side copy of the ranges updated since
+// the last snapshot (the first one: of every vertex) on the context's stream.  Nothing a build or refit reads changes.
+int rt3_scene_snapshot_vertices(rt3_ctx* c) {
+    if (!c) return fail(c, RT3_E_INVALID, "context NULL");
+    if (!c->d_verts || c->n_verts == 0) return fail(c, RT3_E_STATE, "snapshot_vertices: no vertices (rt3_scene_set_vertices)");
+    HIPC(c, hipSetDevice(c->device));
+    if (!c->df_snapshot) {
+        HIPC(c, hipStreamSynchronize(c->stream));  // an earlier "motion" launch may still read the old records
+        HIPC(c, c->d_prev_pos.grow_bytes((size_t)c->n_verts * sizeof(float4)));
+        c->df_ranges.assign(1, {0u, c->n_verts});
+    }
+    for (const auto& r : c->df_ranges) {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_snapshot_positions(c->stream, c->d_verts.get(), r.first, r.second - r.first, c->d_prev_pos.get());
+    }
+    HIPC(c, hipGetLastError());
+    c->df_ranges.clear();
+    c->df_snapshot = true;
+    c->df_dirty = true;
+    return RT3_OK;
+}
+int rt3_scene_forget_prev_vertices(rt3_ctx* c) {
+    if (!c) return fail(c, RT3_E_INVALID, "context NULL");
+    forget_snapshot(c);
+    return RT3_OK;
+}
+// The flags of deform_flags, one byte per uploaded geometry
+int rt3_scene_deformed_geometries(rt3_ctx* c, uint8_t* flags, uint32_t n) {
+    if (!c || (!flags && n)) return fail(c, RT3_E_INVALID, "deformed_geometries: NULL");
+    if (!c->df_snapshot) return fail(c, RT3_E_STATE, "deformed_geometries: no snapshot (rt3_scene_snapshot_vertices)");
+    if (n != c->n_geoms) return fail(c, RT3_E_INVALID, "deformed_geometries: n must be the geometry count of rt3_scene_set_geometry (" + std::to_string(c->n_geoms) + ")");
+    if (int r = deform_flags(c)) return r;
+    for (uint32_t i = 0; i < n; i++) flags[i] = c->h_deformed[i] ? 1 : 0;
     return RT3_OK;
 }
 int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
@@ -1088,29 +1202,36 @@ int rt3_scene_set_indices(rt3_ctx* c, const uint32_t* idx, uint32_t n) {
     c->n_indices = n;
     c->h_indices.assign(idx, idx + n);
     invalidate_topology(c);
+    forget_snapshot(c);
     return RT3_OK;
 }
 // bounds of every geometry's index / vertex range against the world buffers as they are NOW: the kernels index them without
 // checks (a GPU fault would take the node down).  Run by rt3_scene_set_geometry and again by rt3_accel_build, because the vertex
 // and index buffers may be replaced (by smaller ones) after the geometry was set.
-static int validate_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_t* prim_counts, uint32_t n) {
+// spans: per geometry the vertices [vertex_offset + least index, vertex_offset + largest index] its triangles lie in ({1, 0}: none)
+static int validate_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_t* prim_counts, uint32_t n,
+                             std::vector<std::pair<uint32_t, uint32_t>>* spans = nullptr) {
     for (uint32_t i = 0; i < n; i++) {
         if ((uint64_t)g[i].index_offset + 3ull * prim_counts[i] > c->n_indices)
             return fail(c, RT3_E_INVALID, "geometry " + std::to_string(i) + ": index range exceeds the index buffer");
-        uint32_t mx = 0;
+        uint32_t mx = 0, mn = 0xFFFFFFFFu;
         for (uint64_t k = 0; k < 3ull * prim_counts[i]; k++) {
             uint32_t v = c->h_indices[g[i].index_offset + k];
             mx = v > mx ? v : mx;
+            mn = v < mn ? v : mn;
         }
         if (prim_counts[i] && (uint64_t)g[i].vertex_offset + mx >= (uint64_t)c->n_verts)
             return fail(c, RT3_E_INVALID, "geometry " + std::to_string(i) + ": vertex range exceeds the vertex buffer (set vertices and indices before geometry)");
+        if (spans) spans->push_back(prim_counts[i] ? std::make_pair(g[i].vertex_offset + mn, g[i].vertex_offset + mx) : std::make_pair(1u, 0u));
     }
     return RT3_OK;
 }
 int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_t* prim_counts, uint32_t n) {
     if (!c || ((!g || !prim_counts) && n)) return fail(c, RT3_E_INVALID, "geometry NULL");
     HIPC(c, hipSetDevice(c->device));
-    if (int r = validate_geometry(c, g, prim_counts, n)) return r;
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    if (int r = validate_geometry(c, g, prim_counts, n, &spans)) return r;
+    c->h_geom_span.swap(spans);
     uint64_t total = 0;
     int64_t max_tex = -1;
     for (uint32_t i = 0; i < n; i++) {
@@ -1126,6 +1247,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->max_tex_index = max_tex;
     c->n_prims = (uint32_t)total;
     invalidate_topology(c);
+    forget_snapshot(c);
     return RT3_OK;
 }
 // alpha cutoffs of the geometries of the last rt3_scene_set_geometry; n = 0: all opaque
@@ -1411,9 +1533,11 @@ static int flatten_world(rt3_ctx* c) {
     c->n_flat_prims = (uint32_t)total;
     return RT3_OK;
 }
-// The device tables of the "motion" pass for the built structure: per instance its previous matrix, per flattened geometry its instance's
-// index if that instance moved -- the 12 stored floats of the two matrices differ in some word -- else kMotionUnmoved.  Remade when the
-// previous transforms or the structure changed; the count is checked at every launch.
+// The device tables of the "motion" pass for the built structure: per instance its previous matrix, per flattened geometry its slot --
+// kMotionUnmoved, or its instance's index if that instance moved (the 12 stored floats of the two matrices differ in some word), or that
+// index | kMotionDeformed if the geometry is deformed (deform_flags).  Without previous transforms a deformed geometry's record holds its
+// instance's current matrix.  Remade when the previous transforms, the snapshot, the vertices or the structure changed; the count is
+// checked at every launch.
 static int motion_tables(rt3_ctx* c) {
     rt3_instance whole;
     const auto [inst, n_inst] = placements(c, whole);
@@ -1421,12 +1545,14 @@ static int motion_tables(rt3_ctx* c) {
     if (n != 0 && n != n_inst)
         return fail(c, RT3_E_STATE, "motion: " + std::to_string(n) + " previous transforms (rt3_scene_set_prev_transforms) for a structure of " +
                                         std::to_string(n_inst) + " instance(s)");
+    if (int r = deform_flags(c)) return r;
     if (!c->mo_dirty && c->mo_stamp == c->accel_stamp) return RT3_OK;
-    std::vector<MotionPrevDev> rec(n);
+    const bool deformed_any = std::any_of(c->h_deformed.begin(), c->h_deformed.end(), [](uint32_t f) { return f != 0; });
+    std::vector<MotionPrevDev> rec(n || deformed_any ? n_inst : 0);
     std::vector<uint32_t> slot;
-    bool any = false;
-    for (size_t i = 0; i < n; i++) {
-        const float *pm = &c->mo_prev[16 * i], *cm = inst[i].transform;
+    bool any = false, any_deformed = false;
+    for (size_t i = 0; i < rec.size(); i++) {
+        const float *cm = inst[i].transform, *pm = n ? &c->mo_prev[16 * i] : cm;
         float cur[12];
         memset(&rec[i], 0, sizeof(rec[i]));
         for (int col = 0; col < 4; col++)
@@ -1436,8 +1562,13 @@ static int motion_tables(rt3_ctx* c) {
             }
         rec[i].identity = memcmp(pm, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u;
         const bool moved = memcmp(rec[i].m, cur, sizeof(cur)) != 0;  // word for word: -0 is not +0
-        slot.insert(slot.end(), inst[i].geometry_count, moved ? (uint32_t)i : kMotionUnmoved);
-        any = any || (moved && inst[i].geometry_count);
+        for (uint32_t k = 0; k < inst[i].geometry_count; k++) {
+            const uint32_t g = inst[i].geometry_first + k;
+            const bool deformed = g < c->h_deformed.size() && c->h_deformed[g];
+            slot.push_back(deformed ? ((uint32_t)i | kMotionDeformed) : (moved ? (uint32_t)i : kMotionUnmoved));
+            any = any || moved || deformed;
+            any_deformed = any_deformed || deformed;
+        }
     }
     if (any) {
         HIPC(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the old tables
@@ -1447,6 +1578,7 @@ static int motion_tables(rt3_ctx* c) {
         HIPC(c, hipMemcpy(c->d_mo_slot.get(), slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
     }
     c->mo_any_moved = any;
+    c->mo_any_deformed = any_deformed;
     c->mo_dirty = false;
     c->mo_stamp = c->accel_stamp;
     return RT3_OK;
@@ -1903,7 +2035,9 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     HIPC(c, hipSetDevice(c->device));
     if (c->n_prims && (!c->d_verts || !c->d_indices)) return fail(c, RT3_E_STATE, "set vertices, indices and geometry before rt3_accel_build");
     // the vertex / index buffers may have been replaced since rt3_scene_set_geometry checked its ranges against them
-    if (int r = validate_geometry(c, c->h_geoms.data(), c->h_prim_counts.data(), (uint32_t)c->h_geoms.size())) return r;
+    std::vector<std::pair<uint32_t, uint32_t>> spans;  // (the indices may have been replaced since rt3_scene_set_geometry)
+    if (int r = validate_geometry(c, c->h_geoms.data(), c->h_prim_counts.data(), (uint32_t)c->h_geoms.size(), &spans)) return r;
+    c->h_geom_span.swap(spans);
     HIPC(c, hipStreamSynchronize(c->stream));
     const auto t_build0 = std::chrono::steady_clock::now();
     // until the rebuild has succeeded: a failed one (the geometry tables reallocated by flatten_world included) must leave

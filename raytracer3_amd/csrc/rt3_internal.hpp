@@ -342,10 +342,12 @@ struct TemporalLaunch {
 };
 void launch_temporal(hipStream_t st, const TemporalLaunch& L);
 
-// "motion" pass (rt3_motion.hip): one kernel behind the primary trace, one thread per listed pixel, no scratch.
-// `prev` holds one record per instance; the host's "moved" flag travels as `geom_slot`: per flattened geometry its instance's index when that
-// instance moved, else kMotionUnmoved.  geom_slot = nullptr: no instance moved, nothing but `hits` and the camera is read.
+// "motion" pass (rt3_motion.hip, DESIGN.md sections 4h and 4i): one kernel behind the primary trace, one thread per listed pixel, no scratch.
+// `prev` holds one record per instance; the host's "moved" and "deformed" flags travel as `geom_slot`: per flattened geometry
+// kMotionUnmoved, or its instance's index when that instance moved, or that index | kMotionDeformed when the geometry's vertices differ
+// from the snapshot (rt3_scene_snapshot_vertices).  geom_slot = nullptr: nothing moved, nothing but `hits` and the camera is read.
 constexpr uint32_t kMotionUnmoved = 0xFFFFFFFFu;
+constexpr uint32_t kMotionDeformed = 0x80000000u;
 struct MotionPrevDev {
     float m[12];        // the previous object -> world matrix, stored like FlatGeomDev::m
     uint32_t identity;  // 1: it is exactly the identity -- the object-space point is used as it is (the flattening's rule)
@@ -365,8 +367,15 @@ struct MotionLaunch {
     uint32_t npix, width;
     const float* hits;
     void* out;
+    const float4* prev_pos = nullptr;  // some geometry is deformed: the snapshot, one {x, y, z, 0} per vertex; selects k_motion<true>
 };
 void launch_motion(hipStream_t st, const MotionLaunch& L);
+// The snapshot of rt3_scene_snapshot_vertices: prev_pos[v] = {verts[8 v], verts[8 v + 1], verts[8 v + 2], 0} for v in [first, first + n)
+void launch_snapshot_positions(hipStream_t st, const float* verts, uint32_t first, uint32_t n, float4* prev_pos);
+// Which geometries are deformed: chunk {geometry, lo, hi, -} sets flags[geometry] = 1 when a vertex v in [lo, hi) has a position word that
+// differs from prev_pos[v]'s (as uint32).  One 256-thread group per chunk; flags are zeroed by the caller.
+constexpr uint32_t kDeformChunk = 1024;  // vertices per chunk, at most
+void launch_compare_positions(hipStream_t st, const float* verts, const float4* prev_pos, const uint4* chunks, uint32_t n_chunks, uint32_t* flags);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

@@ -101,6 +101,10 @@ class Context {
     // and the Motion image that "temporal" follows moved instances with (0 = none)
     void set_prev_transforms(const float* m, uint32_t n) const { check(rt3_scene_set_prev_transforms(ctx_, m, n), "rt3_scene_set_prev_transforms"); }
     void set_temporal_motion_input(uint32_t motion_image) const { check(rt3_temporal_set_motion_input(ctx_, motion_image), "rt3_temporal_set_motion_input"); }
+    // previous vertex positions: "motion" follows meshes that update_vertices deforms after a snapshot
+    void snapshot_vertices() const { check(rt3_scene_snapshot_vertices(ctx_), "rt3_scene_snapshot_vertices"); }
+    void forget_prev_vertices() const { check(rt3_scene_forget_prev_vertices(ctx_), "rt3_scene_forget_prev_vertices"); }
+    void deformed_geometries(uint8_t* flags, uint32_t n) const { check(rt3_scene_deformed_geometries(ctx_, flags, n), "rt3_scene_deformed_geometries"); }
     void set_denoise_variance_input(uint32_t moments_image) const { check(rt3_denoise_set_variance_input(ctx_, moments_image), "rt3_denoise_set_variance_input"); }
 
    private:

@@ -198,6 +198,22 @@ class Context:
         arr = np.ascontiguousarray([np.asarray(m, np.float32).T.ravel() for m in transforms], np.float32).reshape(n, 16) if n else None
         self.check(self.lib.rt3_scene_set_prev_transforms(self.h, arr.ctypes.data if n else None, n))
 
+    def snapshot_vertices(self):
+        """the positions the vertex buffer holds now become the previous frame's (rt3_scene_snapshot_vertices): the "motion" pass follows
+        geometries that update_vertices() deforms afterwards.  A device-side copy of the ranges updated since the last snapshot."""
+        self.check(self.lib.rt3_scene_snapshot_vertices(self.h))
+
+    def forget_prev_vertices(self):
+        """no previous positions (rt3_scene_forget_prev_vertices): "motion" sees no deformed geometry"""
+        self.check(self.lib.rt3_scene_forget_prev_vertices(self.h))
+
+    def deformed_geometries(self, n):
+        """one bool per geometry of the uploaded mesh (`n` of them): does a position word inside its vertex span differ from the snapshot?
+        (rt3_scene_deformed_geometries)"""
+        flags = np.zeros(int(n), np.uint8)
+        self.check(self.lib.rt3_scene_deformed_geometries(self.h, flags.ctypes.data, len(flags)))
+        return flags.astype(bool)
+
     def set_sky(self, rgb):
         s = np.ascontiguousarray(rgb, np.float32)
         self.check(self.lib.rt3_scene_set_sky(self.h, s.ctypes.data, s.shape[1], s.shape[0]))

@@ -7,7 +7,7 @@ Per frame, three passes exactly as the old shaders were wired:
   ComputePass("postprocess")       -> display image (AgX)                      shaders/old/postprocess.slang
 with, on request, ComputePass("temporal") and / or ComputePass("denoise") between the last two (no reference counterpart: the reprojected
 accumulation of DESIGN.md section 4g and the a-trous filter of section 4f), and RayTracingPass("motion") in front of "temporal" in a frame
-whose instances moved (section 4h),
+whose instances moved (section 4h) or whose vertices were updated (section 4i),
 and, as a second frame description, the probe-GI chain of the old shaders (`probe_commands`):
   gbuffer -> structured_importance_sampling -> trace_probes -> spherical_harmonic_conversion -> interpolate_probes
 """
@@ -140,12 +140,15 @@ class PathTracer:
         self._prev_gconst = None  # "temporal": the view of the frame whose G-buffer / History / Moments the images hold; None = no history
         self._instances = None    # set_instances: the list the structure was built for; None = never called
         self._prev_instances = None  # ... and the one the last temporal frame was rendered with
+        self._snapshot = False        # the context holds a snapshot of the vertex positions (ctx.snapshot_vertices)
+        self._verts_updated = False   # update_vertices() since the last temporal frame (it took the snapshot before its first upload)
 
     def close(self):
         self.ctx.close()
 
     def set_scene(self, mesh, sky=None, bluenoise=None):
         self.ctx.upload_mesh(mesh)
+        self._snapshot = False  # (new vertices: the context forgot it)
         if sky is not None:
             self.ctx.set_sky(sky)
         if bluenoise is not None:
@@ -167,6 +170,10 @@ class PathTracer:
     def reset_history(self):
         """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
         self._prev_gconst = None
+        self._verts_updated = False
+        if self._snapshot:
+            self.ctx.forget_prev_vertices()
+            self._snapshot = False
 
     def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth")):
         """Before a temporal frame's nodes are built: what the last temporal frame wrote, and the G-buffer it read (the images named
@@ -193,6 +200,12 @@ class PathTracer:
         moved = (self._prev_gconst is not None and self._instances is not None and self._prev_instances is not None
                  and _instance_key(self._instances) != _instance_key(self._prev_instances))
         self.ctx.set_prev_transforms([m for _, _, m in self._prev_instances] if moved else None)
+        # vertices updated since the last temporal frame: update_vertices() took the snapshot, "motion" follows the deformed geometries.  No
+        # update since: the snapshot is brought up to the current positions (a copy of the ranges last updated), so nothing is deformed
+        deformed = self._prev_gconst is not None and self._verts_updated and self._snapshot
+        if self._snapshot and not deformed:
+            self.ctx.snapshot_vertices()
+        moved = moved or deformed
         self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved else 0)
         return moved
 
@@ -201,9 +214,16 @@ class PathTracer:
         C.memmove(C.byref(keep), C.byref(gconst), C.sizeof(keep))
         self._prev_gconst = keep
         self._prev_instances = self._instances
+        self._verts_updated = False
 
     def update_vertices(self, vertices, first=0):
-        """deformed vertices (same topology): upload them and refit the acceleration structure"""
+        """deformed vertices (same topology): upload them and refit the acceleration structure.  Between temporal frames the positions as
+        they were at the last one are kept first (ctx.snapshot_vertices, once per frame interval, before its first upload), and the next
+        temporal frame runs the "motion" pass so that the deformed geometries keep their history."""
+        if self._prev_gconst is not None and not self._verts_updated:
+            self.ctx.snapshot_vertices()
+            self._snapshot = True
+        self._verts_updated = True
         self.ctx.update_vertices(vertices, first)
         self._accel = self.ctx.refit_accel()
 
@@ -323,7 +343,8 @@ class PathTracer:
         """One frame.  `temporal` accumulates it with the reprojected history of the previous temporal frame (this object keeps two sets
         of history images, the previous G-buffer, depth and GConst, and starts from zeros after set_scene / reset_history); with
         `denoise` too, the filter reads the accumulated image and its temporal variance.  One rank only: see denoise().  After
-        set_instances() moved something, the frame has the "motion" node as well (handle `motion`) and "temporal" follows the instances."""
+        set_instances() moved something or update_vertices() deformed something, the frame has the "motion" node as well (handle `motion`)
+        and "temporal" follows the instances and the deformed geometries."""
         motion = False
         if temporal:
             motion = self._begin_temporal(gconst, denoise)

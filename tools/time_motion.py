@@ -11,6 +11,10 @@ Beside the times the bytes each variant moves per pixel: the kernels of "motion"
 16-byte hit record and write the 32-byte ray and the 16-byte texel (a moved pixel gathers up to 4 + 4 + 4 + 8 + 12 + 96 + 64 more from
 small tables that its neighbours share); "temporal" reads 16 more with the input.
 
+With --deform, after those rows (which stay as they are): the placed column's own mesh is bent through rt3_scene_update_vertices behind a
+snapshot and four more rows are timed the same way -- the snapshot's full copy, its copy of the updated range, the
+compare kernel over that range, and "motion" with the deformed mesh in view (both placements of the column follow).
+
   python tools/time_motion.py --size 1920x1080 --out time_motion.json
 """
 import argparse
@@ -32,6 +36,41 @@ TEMPORAL_BYTES = 36 + 48 + 52       # tools/time_temporal.py: this frame, the th
 COLUMN = "col0_0"
 
 
+def time_deform(args, ctx, pt, mesh, ci, passes, h, W, H):
+    """the rows of --deform; leaves the column bent and the structure refitted"""
+    first = int(mesh.geometries["vertex_offset"][ci])
+    end = int(mesh.geometries["vertex_offset"][ci + 1]) if ci + 1 < len(mesh.geometries) else len(mesh.vertices)
+    rest = np.ascontiguousarray(mesh.vertices[first:end], np.float32)
+    bent = rest.copy()
+    y = bent[:, 1] - bent[:, 1].min()
+    bent[:, 0] += np.float32(0.02) * y * y  # 2 cm at one metre, growing with the height
+
+    def timed(prepare, call):
+        rows = []
+        for k in range(args.warmup + args.repeats):
+            prepare()
+            ctx.stats_reset()
+            call()
+            rows.append(ctx.stats().other_ms)  # synchronises
+        rows = rows[args.warmup:]
+        return {"ms": round(statistics.median(rows), 4), "ms_min": round(min(rows), 4), "ms_max": round(max(rows), 4)}
+
+    out = {"vertices": len(mesh.vertices), "updated_vertices": end - first}
+    ctx.set_prev_transforms(None)
+    out["snapshot_full"] = timed(ctx.forget_prev_vertices, ctx.snapshot_vertices)
+    out["snapshot_dirty_range"] = timed(lambda: ctx.update_vertices(bent, first), ctx.snapshot_vertices)
+    ctx.update_vertices(rest, first)
+    ctx.snapshot_vertices()
+    out["compare"] = timed(lambda: ctx.update_vertices(bent, first), lambda: ctx.deformed_geometries(len(mesh.geometries)))
+    ctx.refit_accel()
+    flags = ctx.deformed_geometries(len(mesh.geometries))
+    assert flags.tolist() == [i == ci for i in range(len(flags))]
+    out["motion_deformed"] = passes("motion", W, H, 1, [h["motion"]])
+    M = pt.rg.download(h["motion"], (H, W, 4), np.float32)
+    out["deformed_pixels"] = int((M[..., 3] == 3).sum())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
@@ -40,6 +79,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=31)
     ap.add_argument("--instance-mode", type=int, default=0)
+    ap.add_argument("--deform", action="store_true", help="also time the snapshot, the compare kernel and \"motion\" on a deformed mesh")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -111,6 +151,9 @@ def main():
     out["temporal_with_motion_input"] = passes("temporal", X, Y, 1, tb)
     ctx.set_temporal_motion_input(0)
     out["temporal_without"] = passes("temporal", X, Y, 1, tb)
+    deform = None
+    if args.deform:
+        deform = time_deform(args, ctx, pt, mesh, ci, passes, h, W, H)
     ctx.set_option(L.OPT_PROFILE, 0)
     npx = W * H
     for k, per_px in (("motion", MOTION_BYTES), ("motion_nothing_moved", MOTION_BYTES)):
@@ -122,6 +165,8 @@ def main():
     result = {"scene": "atrium + one moved column", "detail": args.detail, "size": [W, H], "instance_mode": args.instance_mode,
               "foreground_pixels": fg, "moved_pixels": moved, "moved_gather_bytes": MOVED_GATHER_BYTES, "mean_history_on_moved_pixels": round(n_moved, 3),
               "pass": out}
+    if deform:
+        result["deform"] = deform
     pt.close()
     line = json.dumps(result)
     print(line)
