@@ -337,7 +337,7 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *        "spherical_harmonic_conversion"  (x,y,1)=probes  {out buffer of float3x3 (48 B, rows padded to float4), probe_atlas}
  *        "interpolate_probes"             (x,y,1)=groups of 8x8 over the window  {gbuffer, gbuffer_depth, sh_coeficents buffer, Light}
  *      The checked form of this list (launch shape, bindings, formats, the images that may not alias) is the table kPasses in
- *      raytracer3_amd/csrc/rt3_api.hip: where the two differ, the table is what the library does.
+ *      raytracer3_amd/csrc/rt3_passes.hip: where the two differ, the table is what the library does.
  *      Work is enqueued on the context's stream and returns immediately. ---- */
 int rt3_pass_launch(rt3_ctx *ctx, const char *pass_name, const char *entry, uint32_t x, uint32_t y, uint32_t z,
                     const void *constants, size_t constants_size, const uint32_t *bindings, uint32_t n_bindings);

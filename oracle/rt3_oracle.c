@@ -576,7 +576,7 @@ int orc_scene_set_indices(orc_scene *s, const uint32_t *idx, uint32_t n) {
     return 0;
 }
 /* One (instance, geometry) pair per flattened geometry, instance-major; no instances = one identity instance of everything.
- * The product's flatten_world (rt3_api.hip) makes the same tables. */
+ * The product's flatten_world (rt3_accel.hip) makes the same tables. */
 static const float k_identity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 static int flatten_world(orc_scene *s) {
     free(s->first_prim); free(s->prim_geom); free(s->flat_geom); free(s->flat_inst); free(s->flat_identity);

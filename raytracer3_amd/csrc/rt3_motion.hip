@@ -11,7 +11,7 @@
 //
 // Arithmetic contract: tests/ref_motion.py and tests/ref_deform.py restate every operation in numpy float32; the pass equals them bit for
 // bit.  Which instances moved is decided on the host, word for word, and which geometries are deformed by k_compare_positions below, word
-// for word too (rt3_api.hip: motion_tables); the kernel only follows the table.
+// for word too (rt3_passes.hip: motion_tables); the kernel only follows the table.
 //
 // One thread per listed pixel, like k_gbuffer: the 16-byte hit record is read and the 16-byte texel stored in list order.  With nothing moved
 // or deformed the table is absent and a hit lane only computes primary_ray.  Otherwise every hit lane reads prim_geom[prim] and its

@@ -1,0 +1,648 @@
+// rt3_passes.hip -- host layer, the passes: the wavefront work queues and counter reservation, the primary trace, every pass function,
+// the pass table kPasses and its validator, rt3_pass_launch, and the state of the "denoise", "temporal" and "motion" passes
+// (include/rt3.h: rt3_pass_launch, rt3_denoise_*, rt3_temporal_*).  Owns rt3_ctx::work, ::denoise, ::temporal and ::motion.
+// rt3_pass_launch() is the drop-in for executing one pass node of the reference's frame graph (render_graph/mod.rs:80-107): the pass
+// name selects a HIP kernel sequence instead of a SPIR-V pipeline.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "rt3_ctx.hpp"
+
+using namespace rt3;
+
+namespace rt3 {
+
+void motion_tables_stale(rt3_ctx* c) { c->motion.dirty = true; }
+
+}  // namespace rt3
+
+namespace {
+
+uint32_t spread1by1(uint32_t x) {  // math.slang:105-112 integer_explode
+    x = (x | (x << 8)) & 0x00FF00FFu;
+    x = (x | (x << 4)) & 0x0F0F0F0Fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+uint32_t zcurve_host(uint32_t x, uint32_t y) { return spread1by1(x) | (spread1by1(y) << 1); }  // math.slang:114-117
+
+// Failure-atomic: if any allocation fails the whole queue set is released and the capacities drop to 0, so the next pass
+// re-allocates (or reports the error again) instead of launching kernels on a half-resized set.
+void free_work(rt3_ctx* c) {
+    for (int k = 0; k < 2; k++) { c->work.rays[k].reset(); c->work.T[k].reset(); }
+    c->work.hits.reset(); c->work.sh_rays.reset(); c->work.sh_contrib.reset(); c->work.lacc.reset(); c->work.radsum.reset();
+    c->work.sh2_rays.reset(); c->work.sh2_contrib.reset(); c->work.sh2_tmax.reset();
+    c->work.cap_emit = 0;
+    c->work.cap = 0;
+    c->work.cap_pix = 0;
+}
+int ensure_work(rt3_ctx* c, size_t paths, size_t npix) {
+    int r = RT3_OK;
+    if (paths > c->work.cap) {
+        size_t P = (paths + 255) & ~(size_t)255;
+        c->work.cap = 0;
+        for (int k = 0; k < 2 && !r; k++) {
+            if (!r) r = dev_alloc(c, c->work.rays[k], 8 * P);
+            if (!r) r = dev_alloc(c, c->work.T[k], 3 * P);  // throughput planes (the path's pdf and id ride in the ray records)
+        }
+        if (!r) r = dev_alloc(c, c->work.hits, 4 * P);
+        if (!r) r = dev_alloc(c, c->work.sh_rays, 8 * P);
+        if (!r) r = dev_alloc(c, c->work.sh_contrib, 2 * P);  // {blue contribution, path id} records (red / green ride with the ray)
+        if (!r) r = dev_alloc(c, c->work.lacc, 4 * P);        // float4 per path
+        if (!r) c->work.cap = P;
+    }
+    if (!r && npix > c->work.cap_pix) {
+        c->work.cap_pix = 0;
+        r = dev_alloc(c, c->work.radsum, 3 * npix);
+        if (!r) c->work.cap_pix = npix;
+    }
+    if (r) free_work(c);
+    return r;
+}
+// the emitter shadow queue, as large as the other queues (after ensure_work)
+int ensure_emit_queue(rt3_ctx* c) {
+    if (c->work.cap_emit >= c->work.cap) return RT3_OK;
+    c->work.cap_emit = 0;
+    int r = dev_alloc(c, c->work.sh2_rays, 8 * c->work.cap);
+    if (!r) r = dev_alloc(c, c->work.sh2_contrib, 2 * c->work.cap);
+    if (!r) r = dev_alloc(c, c->work.sh2_tmax, c->work.cap);
+    if (!r) c->work.cap_emit = c->work.cap;
+    else free_work(c);
+    return r;
+}
+
+int reserve_counters(rt3_ctx* c, uint32_t n, uint32_t* first) {
+    if (c->work.counters_next + n > c->work.counters_cap) {
+        HIPC(c, hipStreamSynchronize(c->stream));
+        if (int r = harvest(c)) return r;
+    }
+    if (n > c->work.counters_cap) return fail(c, RT3_E_INVALID, "too many bounces x batches for the counter block");
+    *first = c->work.counters_next;
+    c->work.counters_next += n;
+    HIPC(c, hipMemsetAsync(c->work.d_counters.get() + *first, 0, (size_t)n * 4, c->stream));
+    return RT3_OK;
+}
+// a traversal launch over the context's queues (`stride` records), counting into its totals when RT3_OPT_COUNT_TRAVERSAL is on
+TraceLaunch ctx_trace(rt3_ctx* c) {
+    TraceLaunch L;
+    L.stride = c->work.cap;
+    L.count = c->opt.count;
+    L.totals = c->opt.count ? c->work.d_totals.get() : nullptr;
+    L.alpha = alpha_dev(c);
+    return L;
+}
+// closest hits of the n primary rays in c->work.rays[0], into c->work.hits
+int trace_primary(rt3_ctx* c, uint32_t n) {
+    uint32_t wc_slot;
+    if (int r = reserve_counters(c, 1, &wc_slot)) return r;  // ray-pool cursor of the launch
+    TraceLaunch L = ctx_trace(c);
+    L.rays = c->work.rays[0].get(); L.n = n; L.work_counter = c->work.d_counters.get() + wc_slot; L.hits = c->work.hits.get();
+    c->work.primary_rays_pending += n;
+    ScopedTimer t(c, CAT_EXTEND);
+    launch_extend(c->stream, c->accel.bvh, L);
+    return RT3_OK;
+}
+
+// The device tables of the "motion" pass for the built structure: per instance its previous matrix, per flattened geometry its slot --
+// kMotionUnmoved, or its instance's index if that instance moved (the 12 stored floats of the two matrices differ in some word), or that
+// index | kMotionDeformed if the geometry is deformed (deform_flags).  Without previous transforms a deformed geometry's record holds its
+// instance's current matrix.  Remade when the previous transforms, the snapshot, the vertices or the structure changed; the count is
+// checked at every launch.
+int motion_tables(rt3_ctx* c) {
+    rt3_instance whole;
+    const auto [inst, n_inst] = placements(c, whole);
+    const size_t n = c->scene.prev_transforms.size() / 16;
+    if (n != 0 && n != n_inst)
+        return fail(c, RT3_E_STATE, "motion: " + std::to_string(n) + " previous transforms (rt3_scene_set_prev_transforms) for a structure of " +
+                                        std::to_string(n_inst) + " instance(s)");
+    if (int r = deform_flags(c)) return r;
+    if (!c->motion.dirty && c->motion.stamp == c->accel.stamp) return RT3_OK;
+    const bool deformed_any = std::any_of(c->deform.h_deformed.begin(), c->deform.h_deformed.end(), [](uint32_t f) { return f != 0; });
+    std::vector<MotionPrevDev> rec(n || deformed_any ? n_inst : 0);
+    std::vector<uint8_t> moved(rec.size());
+    std::vector<uint32_t> slot;
+    bool any = false, any_deformed = false;
+    for (size_t i = 0; i < rec.size(); i++) {
+        const float *cm = inst[i].transform, *pm = n ? &c->scene.prev_transforms[16 * i] : cm;
+        float cur[12];
+        memset(&rec[i], 0, sizeof(rec[i]));
+        pack3x4(pm, rec[i].m);
+        pack3x4(cm, cur);
+        rec[i].identity = memcmp(pm, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u;
+        moved[i] = memcmp(rec[i].m, cur, sizeof(cur)) != 0;  // word for word: -0 is not +0
+    }
+    if (!rec.empty())
+        for (const Placed& p : c->accel.placed) {  // one slot per flattened geometry
+            const bool deformed = p.geom < c->deform.h_deformed.size() && c->deform.h_deformed[p.geom];
+            slot.push_back(deformed ? (p.instance | kMotionDeformed) : (moved[p.instance] ? p.instance : kMotionUnmoved));
+            any = any || moved[p.instance] || deformed;
+            any_deformed = any_deformed || deformed;
+        }
+    if (any) {
+        HIPC(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the old tables
+        if (int r = dev_alloc(c, c->motion.d_prev, rec.size())) return r;
+        if (int r = dev_alloc(c, c->motion.d_slot, slot.size())) return r;
+        HIPC(c, hipMemcpy(c->motion.d_prev.get(), rec.data(), rec.size() * sizeof(MotionPrevDev), hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->motion.d_slot.get(), slot.data(), slot.size() * 4, hipMemcpyHostToDevice));
+    }
+    c->motion.any_moved = any;
+    c->motion.any_deformed = any_deformed;
+    c->motion.dirty = false;
+    c->motion.stamp = c->accel.stamp;
+    return RT3_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- passes
+// A pass is one entry of kPasses (below): launch_pass checks the launch against the entry and hands the pass function (pass_*) the window
+// and the resolved bindings, in the entry's order.  What a pass function still checks is its own: context state, the least size of a
+// buffer, the optional context-state inputs.
+GConstDev gconst_dev(const rt3_gconst* g) {
+    GConstDev gd;
+    memcpy(&gd, g, sizeof(gd));
+    return gd;
+}
+int check_window(rt3_ctx* c, const rt3_gconst* g, uint32_t* W, uint32_t* H) {
+    float fw = g->window_size[0], fh = g->window_size[1];
+    if (!(fw >= 1.0f && fh >= 1.0f && fw <= 65535.0f && fh <= 65535.0f) || fw != std::floor(fw) || fh != std::floor(fh))
+        return fail(c, RT3_E_INVALID, "GConst.window_size must hold integral pixel counts in [1, 65535]");
+    *W = (uint32_t)fw;
+    *H = (uint32_t)fh;
+    return RT3_OK;
+}
+Resource* image_checked(rt3_ctx* c, uint32_t handle, uint32_t W, uint32_t H, uint32_t format, const char* what) {
+    Resource* r = get_res(c, handle, RT3_TAG_IMAGE);
+    if (!r || r->w != W || r->h != H || r->format != format) {
+        c->err = std::string("binding '") + what + "' is not a " + std::to_string(W) + "x" + std::to_string(H) + " image of the expected format";
+        return nullptr;
+    }
+    return r;
+}
+int buffer_at_least(rt3_ctx* c, const Resource* r, size_t need, const char* what) {
+    if (r->bytes >= need) return RT3_OK;
+    return fail(c, RT3_E_INVALID, std::string("binding '") + what + "' must be a buffer of at least " + std::to_string(need) + " bytes");
+}
+// The primary rays of this rank's pixels of the W x H window (*out: the list) into c->work.rays[0], their closest hits into c->work.hits, in the
+// list's order.  An empty list: nothing is allocated, nothing enqueued.
+int primary_hits(rt3_ctx* c, const GConstDev& gd, uint32_t W, uint32_t H, PixelList** out) {
+    if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, out)) return r;
+    const PixelList* pl = *out;
+    if (pl->count == 0) return RT3_OK;
+    if (int r = ensure_work(c, pl->count, pl->count)) return r;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_raygen(c->stream, gd, pl->dev.get(), pl->count, c->work.rays[0].get(), c->work.cap);
+    }
+    return trace_primary(c, pl->count);
+}
+
+// gbuffer.slang:8-21
+int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    PixelList* pl;
+    if (int r = primary_hits(c, gconst_dev(g), W, H, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_gbuffer(c->stream, scene_dev(c), pl->dev.get(), pl->count, W, c->work.hits.get(), c->work.cap, res[0]->ptr, (float*)res[1]->ptr);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// refrence_mode.slang:14-66 as a wavefront loop
+int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *li = res[2], *pv = res[3];
+    const uint32_t Sspp = g->samples, B = g->bounces;
+    if (Sspp == 0 || B == 0) return RT3_OK;  // GConst::default() leaves samples = bounces = 0 (renderer/mod.rs:47-63): nothing to trace
+    if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
+    PixelList* pl;
+    if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
+    const uint32_t npix = pl->count;
+    if (npix == 0) return RT3_OK;
+    if (int r = pixlist_bluenoise(c, pl)) return r;
+    // paths per wavefront batch: 160 B of queue state each, so 2^28 paths = 43 GB of the 288 GB; the C3 frame (132.7 M paths)
+    // is ONE batch.  Larger launches amortise the ramp / tail of the persistent traversal kernels: 16 -> 64 spp per batch = -6.5 % frame time.
+    uint64_t max_paths = 1ull << 28;
+    uint32_t sb = c->opt.batch_spp > 0 ? (uint32_t)c->opt.batch_spp : (uint32_t)std::max<uint64_t>(1, max_paths / npix);
+    if (sb > Sspp) sb = Sspp;
+    if ((uint64_t)sb * npix > 0xFFFFFF00ull) return fail(c, RT3_E_INVALID, "batch too large");
+    if (int r = ensure_work(c, (size_t)sb * npix, npix)) return r;
+    const size_t S = c->work.cap;
+    const GConstDev gd = gconst_dev(g);
+    const bool nee = (g->pad[0] & RT3_F_NEE_SKY) && c->scene.d_sky;
+    // RT3_F_NEE_EMISSIVE: only with something to sample; otherwise the frame is the flag-less one, same kernels
+    // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
+    LightsDev lights{};
+    if ((g->pad[0] & RT3_F_NEE_EMISSIVE) && B > 1) {
+        if (int r = ensure_lights(c)) return r;
+        lights = c->accel.lights.dev();
+        if (lights.n)
+            if (int r = ensure_emit_queue(c)) return r;
+    }
+    const bool nee_e = lights.n != 0u;
+    SceneDev sc = scene_dev(c);
+    for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
+        const uint32_t nsb = std::min(sb, Sspp - s0);
+        const uint32_t n_first = nsb * npix;
+        uint32_t first;
+        if (int r = reserve_counters(c, (nee_e ? 6 : 4) * B + 1, &first)) return r;
+        first += first & 1u;  // 8-byte aligned pairs
+        // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
+        uint32_t* pairs = c->work.d_counters.get() + first;
+        uint32_t* pool_cur = c->work.d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
+        // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
+        uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
+        c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
+        auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
+        auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
+        int cur = 0;
+        for (uint32_t bn = 0; bn < B; bn++) {
+            ShadeLaunch L;
+            L.g = gd; L.sc = sc; L.pixels = pl->dev.get(); L.pixbn = pl->dev_bn.get(); L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
+            L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
+            L.in_rays = c->work.rays[cur].get(); L.in_hits = c->work.hits.get(); L.in_T = c->work.T[cur].get();
+            L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
+            L.out_rays = c->work.rays[cur ^ 1].get(); L.out_T = c->work.T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
+            L.sh_rays = c->work.sh_rays.get(); L.sh_contrib = c->work.sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
+            L.lacc = c->work.lacc.get(); L.stride = S;
+            L.lights = lights;
+            L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
+            {
+                ScopedTimer t(c, CAT_SHADE);
+                launch_shade(c->stream, bn == 0, L);
+            }
+            cur ^= 1;
+            if (nee) {
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
+                tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
+                ScopedTimer t(c, CAT_SHADOW);
+                launch_shadow(c->stream, c->accel.bvh, tr);
+            }
+            if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->work.sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
+                tr.contrib = c->work.sh2_contrib.get(); tr.lacc = c->work.lacc.get(); tr.tmax = c->work.sh2_tmax.get();
+                ScopedTimer t(c, CAT_SHADOW);
+                launch_shadow(c->stream, c->accel.bvh, tr);
+            }
+            if (bn != B - 1) {
+                TraceLaunch tr = ctx_trace(c);
+                tr.rays = c->work.rays[cur].get(); tr.count_ptr = ext_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + bn;
+                tr.hits = c->work.hits.get(); tr.payload = true;
+                ScopedTimer t(c, CAT_EXTEND);
+                launch_extend(c->stream, c->accel.bvh, tr);
+            }
+        }
+        {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_accumulate(c->stream, gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->work.lacc.get(), S, nsb, s0 == 0, s0 + nsb >= Sspp, c->work.radsum.get(), li->ptr,
+                              pv->ptr);
+        }
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// postprocess.slang:90-112
+int pass_postprocess(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *dp = res[0], *out = res[1], *in = res[2];
+    PixelList* pl;
+    if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    ScopedTimer t(c, CAT_OTHER);
+    launch_postprocess(c->stream, gconst_dev(g), scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// ---- probe-GI passes.  A probe owns a 16x16 pixel block and an 8x8-texel cell of the probe atlas; the passes
+//      run on the whole window on every rank (they are not part of the tile-partitioned path).  The probe grid is the atlas binding's
+//      size over 8.
+// structured_importance_sampling.slang:7-11 : set 1 {gbuffer, gbuffer_depth, out, debug}, set 2 {probe_atlas}
+int pass_sis(rt3_ctx* c, const rt3_gconst*, uint32_t W, uint32_t, Resource* const* res) {
+    ScopedTimer t(c, CAT_OTHER);
+    launch_sis(c->stream, W, res[4]->w / 8, res[4]->h / 8, res[0]->ptr, res[2]->ptr, (float*)res[3]->ptr);
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+// trace_probes.slang:8-12 : set 1 {gbuffer, gbuffer_depth, directions}, set 2 {probe_atlas}, set 3 {prev_probe_atlas}
+int pass_trace_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t, Resource* const* res) {
+    const Resource *dp = res[1], *dir = res[2], *at = res[3], *pv = res[4];
+    const uint32_t px = at->w / 8, py = at->h / 8, n = at->w * at->h;
+    if (int r = ensure_work(c, n, 0)) return r;
+    const size_t S = c->work.cap;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_probe_raygen(c->stream, gconst_dev(g), W, px, py, (const float*)dp->ptr, dir->ptr, at->ptr, c->work.rays[0].get(), S, c->work.T[0].get());
+    }
+    if (int r = trace_primary(c, n)) return r;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_probe_store(c->stream, scene_dev(c), g->pad[0], g->blendfactor, px, py, c->work.hits.get(), c->work.T[0].get(), pv->ptr, at->ptr);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+// spherical_harmonic_conversion.slang:6-7 : set 0 {out}, set 1 {probe_atlas}
+int pass_sh_conversion(rt3_ctx* c, const rt3_gconst*, uint32_t, uint32_t, Resource* const* res) {
+    const Resource *out = res[0], *at = res[1];
+    const uint32_t px = at->w / 8, py = at->h / 8;
+    // float3x3 elements at Z-curve indices (:30-32)
+    if (int r = buffer_at_least(c, out, ((size_t)zcurve_host(px * 3 - 1, py - 1) + 1) * 48, "out")) return r;
+    ScopedTimer t(c, CAT_OTHER);
+    launch_sh_conversion(c->stream, px, py, at->ptr, out->ptr);
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+// interpolate_probes.slang:6-9 : set 1 {gbuffer, gbuffer_depth, sh_coeficents}, set 2 {Light}
+int pass_interpolate_probes(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *sh = res[2], *li = res[3];
+    const uint32_t npx = W / 16, npy = H / 16;
+    if (int r = buffer_at_least(c, sh, npx && npy ? ((size_t)zcurve_host(npx * 3 - 1, npy - 1) + 1) * 48 : 0, "sh_coeficents")) return r;
+    ScopedTimer t(c, CAT_OTHER);
+    launch_interpolate(c->stream, gconst_dev(g), W, H, gb->ptr, (const float*)dp->ptr, sh->ptr, li->ptr);
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "denoise": edge-avoiding a-trous filter over the whole window (no reference counterpart)
+int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *in = res[2], *out = res[3];
+    const Resource* mo = nullptr;
+    if (c->denoise.variance_image) {
+        mo = image_checked(c, c->denoise.variance_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "variance input");
+        if (!mo) return RT3_E_INVALID;
+        if (mo->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: the variance input (rt3_denoise_set_variance_input) must not be 'Out'");
+    }
+    const rt3_denoise_params& p = c->denoise.params;
+    if (p.iterations == 0) {
+        ScopedTimer t(c, CAT_OTHER);
+        HIPC(c, hipMemcpyAsync(out->ptr, in->ptr, (size_t)W * H * 16, hipMemcpyDeviceToDevice, c->stream));
+        return RT3_OK;
+    }
+    DenoiseLaunch L;
+    L.g = gconst_dev(g);
+    L.W = W; L.H = H; L.squarings = p.normal_squarings; L.flags = p.flags; L.sigma_z = p.sigma_z; L.sigma_l = p.sigma_l;
+    L.gbuffer = gb->ptr; L.depth = (const float*)dp->ptr; L.in = in->ptr; L.out = out->ptr;
+    L.moments = mo ? mo->ptr : nullptr;
+    BufLayout plan;
+    denoise_plan(W, H, plan, &L.s);
+    if (c->denoise.scratch.capacity_bytes() < plan.bytes()) {  // the stream may still read the old allocation
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, c->denoise.scratch.grow_bytes(plan.bytes()));
+    }
+    HIPC(c, plan.carve(c->denoise.scratch));
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_prepare(c->stream, L);
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_variance(c->stream, L);
+    }
+    for (uint32_t i = 0; i < p.iterations; i++) {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_atrous(c->stream, L, i);
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_denoise_finish(c->stream, L, p.iterations);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "temporal": reprojected accumulation of the previous frame's history (no reference counterpart)
+int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* r) {
+    if (!c->temporal.has_prev) return fail(c, RT3_E_STATE, "temporal: no previous view (rt3_temporal_set_prev_view)");
+    if (c->temporal.prev.window_size[0] != g->window_size[0] || c->temporal.prev.window_size[1] != g->window_size[1])
+        return fail(c, RT3_E_INVALID, "temporal: the previous view's window_size differs from this frame's (after a resize, start over from zeroed history)");
+    const rt3_temporal_params& p = c->temporal.params;
+    TemporalLaunch L;
+    L.g = gconst_dev(g);
+    L.prev = gconst_dev(&c->temporal.prev);
+    L.W = W; L.H = H; L.flags = p.flags;
+    L.alpha = p.alpha; L.alpha_moments = p.alpha_moments; L.max_history = (float)p.max_history; L.normal_cos = p.normal_cos;
+    L.plane_tolerance = p.plane_tolerance;
+    L.gbuffer = r[0]->ptr; L.depth = (const float*)r[1]->ptr; L.in = r[2]->ptr;
+    L.prev_gbuffer = r[3]->ptr; L.prev_depth = (const float*)r[4]->ptr; L.prev_history = r[5]->ptr; L.prev_moments = r[6]->ptr;
+    L.out = r[7]->ptr; L.history = r[8]->ptr; L.moments = r[9]->ptr;
+    if (c->temporal.motion_image) {
+        const Resource* mv = image_checked(c, c->temporal.motion_image, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "motion input");
+        if (!mv) return RT3_E_INVALID;
+        if (mv->ptr == r[7]->ptr || mv->ptr == r[8]->ptr || mv->ptr == r[9]->ptr)
+            return fail(c, RT3_E_INVALID, "temporal: the motion input (rt3_temporal_set_motion_input) must not be 'Out', 'History' or 'Moments'");
+        L.motion = mv->ptr;
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_temporal(c->stream, L);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "motion": where each pixel's surface point was one frame ago (no reference counterpart).  The primary trace is
+// pass_gbuffer's (primary_hits), so the hits are the G-buffer's.
+int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    if (int r = motion_tables(c)) return r;
+    MotionLaunch L;
+    L.g = gconst_dev(g);
+    PixelList* pl;
+    if (int r = primary_hits(c, L.g, W, H, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    const GeomTables t = world_tables(c);
+    L.m.verts = t.verts; L.m.indices = t.indices; L.m.geoms = t.geoms; L.m.prim_geom = t.prim_geom; L.m.first_prim = t.first_prim;
+    L.m.geom_slot = c->motion.any_moved ? c->motion.d_slot.get() : nullptr;
+    L.m.prev = c->motion.d_prev.get();
+    L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->work.hits.get(); L.out = res[0]->ptr;
+    L.prev_pos = c->motion.any_deformed ? c->deform.d_prev_pos.get() : nullptr;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_motion(c->stream, L);
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// ---- the pass table: everything rt3_pass_launch checks before a pass function runs, and the texts of its errors.  include/rt3.h describes
+//      the same passes for callers.
+enum Shape {
+    kWindow,      // (x, y) = the window exactly (WorkSize2D::FullScreen, executions.rs:73); z is ignored, here and by the next
+    kProbeAtlas,  // (x, y) = the probe atlas, 8 x 8 texels for each of 1x1 .. floor(W/16) x floor(H/16) probes
+    kGroups,      // ceil(W/8) x ceil(H/8) x 1 groups of 8x8 threads (DispatchSize::FullScreen, build.rs:254-258)
+    kProbeGrid    // probes_x x probes_y x 1 groups, one per probe: at most floor(W/16) x floor(H/16), or 8191 x 8191 without a window
+};
+constexpr uint32_t kBuffer = 0;  // a binding that is a buffer, not an image of a format; the pass function checks its size
+constexpr uint32_t kU4 = RT3_FORMAT_R32G32B32A32_UINT, kF4 = RT3_FORMAT_R32G32B32A32_SFLOAT, kF1 = RT3_FORMAT_R32_SFLOAT, kU16 = RT3_FORMAT_R16_UINT;
+constexpr uint32_t kMaxBindings = 10;
+struct Binding {
+    const char* name;       // null: the end of the list
+    uint32_t format;
+    bool atlas = false;     // the image is as large as the probe atlas, not the window
+    uint32_t distinct = 0;  // bit j: the image may not be the one bound at (the earlier) position j
+};
+struct PassDesc {
+    const char* name;
+    Shape shape;
+    bool window;    // reads GConst.window_size
+    bool one_rank;  // reads pixels around its own: refused under a tile partition of several ranks
+    int (*run)(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res);
+    Binding b[kMaxBindings];
+};
+const PassDesc kPasses[] = {
+    {"gbuffer", kWindow, true, false, pass_gbuffer, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}}},
+    {"refrence_mode", kWindow, true, false, pass_reference_mode, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"Light", kF4}, {"PrevLight", kF4}}},
+    {"postprocess", kGroups, true, false, pass_postprocess, {{"Depth", kF1}, {"Out", kF4}, {"In", kF4}}},
+    {"structured_importance_sampling", kProbeGrid, true, false, pass_sis,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"out", kU16, true}, {"debug", kF1, true}, {"probe_atlas", kF4, true}}},
+    {"trace_probes", kProbeAtlas, true, false, pass_trace_probes,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"directions", kU16, true}, {"probe_atlas", kF4, true}, {"prev_probe_atlas", kF4, true, 1u << 3}}},
+    {"spherical_harmonic_conversion", kProbeGrid, false, false, pass_sh_conversion, {{"out", kBuffer}, {"probe_atlas", kF4, true}}},
+    {"interpolate_probes", kGroups, true, false, pass_interpolate_probes,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"sh_coeficents", kBuffer}, {"Light", kF4}}},
+    {"denoise", kGroups, true, true, pass_denoise, {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"In", kF4}, {"Out", kF4, false, 1u << 2}}},
+    {"temporal", kGroups, true, true, pass_temporal,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"In", kF4}, {"PrevGbuffer", kU4}, {"PrevDepth", kF1}, {"PrevHistory", kF4}, {"PrevMoments", kF4},
+      {"Out", kF4, false, 0x7Fu}, {"History", kF4, false, 0xFFu}, {"Moments", kF4, false, 0x1FFu}}},
+    {"motion", kWindow, true, false, pass_motion, {{"Motion", kF4}}},
+};
+// a, b, ... : the names of a table's entries
+template <typename T, size_t N>
+std::string names_of(const T (&list)[N]) {
+    std::string s;
+    for (size_t i = 0; i < N && list[i].name; i++) s += (i ? ", " : "") + std::string(list[i].name);
+    return s;
+}
+
+// Checks in this order: window, launch shape, binding count, the bindings in their order, aliasing, tile partition; then the pass function
+int launch_pass(rt3_ctx* c, const PassDesc& p, const rt3_gconst* g, uint32_t x, uint32_t y, uint32_t z, const uint32_t* b, uint32_t nb) {
+    const std::string name = p.name;
+    uint32_t W = 0, H = 0, ax = 0, ay = 0;  // the window; the probe atlas
+    if (p.window)
+        if (int r = check_window(c, g, &W, &H)) return r;
+    const uint32_t max_px = p.window ? W / 16 : 8191u, max_py = p.window ? H / 16 : 8191u;
+    switch (p.shape) {
+        case kWindow:
+            if (x != W || y != H) return fail(c, RT3_E_INVALID, name + ": launch size must be the window size (WorkSize2D::FullScreen, executions.rs:73)");
+            break;
+        case kProbeAtlas:
+            if (x % 8 || y % 8 || x == 0 || y == 0 || x / 8 > max_px || y / 8 > max_py)
+                return fail(c, RT3_E_INVALID, name + ": launch size is the probe atlas, 8 x 8 texels per probe, of 1x1 to floor(W/16) x floor(H/16) probes");
+            ax = x, ay = y;
+            break;
+        case kGroups:
+            if (x != (W + 7) / 8 || y != (H + 7) / 8 || z != 1)
+                return fail(c, RT3_E_INVALID, name + ": dispatch must be ceil(W/8) x ceil(H/8) x 1 groups (DispatchSize::FullScreen, build.rs:254-258)");
+            break;
+        case kProbeGrid:
+            if (z != 1 || x == 0 || y == 0 || x > max_px || y > max_py)
+                return fail(c, RT3_E_INVALID, name + ": dispatch is probes_x x probes_y x 1 groups of 8x8 threads, 1x1 to floor(W/16) x floor(H/16) probes");
+            ax = 8 * x, ay = 8 * y;
+            break;
+    }
+    uint32_t n = 0;
+    while (n < kMaxBindings && p.b[n].name) n++;
+    if (nb != n)
+        return fail(c, RT3_E_INVALID, name + " expects " + std::to_string(n) + (n == 1 ? " binding {" : " bindings {") + names_of(p.b) + "}");
+    Resource* res[kMaxBindings];
+    for (uint32_t i = 0; i < n; i++) {
+        const Binding& bd = p.b[i];
+        if (bd.format == kBuffer) {
+            if (!(res[i] = get_res(c, b[i], RT3_TAG_BUFFER))) return fail(c, RT3_E_INVALID, name + ": binding '" + bd.name + "' is not a buffer");
+        } else if (!(res[i] = image_checked(c, b[i], bd.atlas ? ax : W, bd.atlas ? ay : H, bd.format, bd.name))) {
+            return RT3_E_INVALID;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = 0; j < i; j++)
+            if ((p.b[i].distinct >> j & 1u) && res[i]->ptr == res[j]->ptr)
+                return fail(c, RT3_E_INVALID, name + ": '" + p.b[i].name + "' and '" + p.b[j].name +
+                                                  "' must be different images (one is read while pixels of the other are written)");
+    if (p.one_rank && c->tiles.n_ranks > 1)
+        return fail(c, RT3_E_STATE, name + ": a tap may need pixels that other ranks own; run it on the gathered image with the tile partition "
+                                           "switched off (rt3_set_tile_partition(w, h, 0, 1))");
+    return p.run(c, g, W, H, res);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- pass launch
+int rt3_pass_launch(rt3_ctx* c, const char* pass_name, const char* entry, uint32_t x, uint32_t y, uint32_t z, const void* constants,
+                    size_t constants_size, const uint32_t* bindings, uint32_t n_bindings) {
+    if (!c || !pass_name) return fail(c, RT3_E_INVALID, "pass_name NULL");
+    if (entry && strcmp(entry, "main") != 0) return fail(c, RT3_E_INVALID, std::string("unknown entry point '") + entry + "' (the reference passes use \"main\")");
+    if (!constants || constants_size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "constants must be the 304-byte GConst block");
+    if (!bindings && n_bindings) return fail(c, RT3_E_INVALID, "bindings NULL");
+    if (int r = check_accel_current(c)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    if (int r = sync_textures(c)) return r;
+    if (c->scene.max_tex_index >= (int64_t)c->scene.h_tex.size())
+        return fail(c, RT3_E_STATE, "a geometry references base-colour texture " + std::to_string(c->scene.max_tex_index) + " but only " +
+                                        std::to_string(c->scene.h_tex.size()) + " texture(s) were set (rt3_scene_set_texture)");
+    rt3_gconst g;
+    memcpy(&g, constants, sizeof(g));
+    for (const PassDesc& p : kPasses)
+        if (!strcmp(pass_name, p.name)) return launch_pass(c, p, &g, x, y, z, bindings, n_bindings);
+    return fail(c, RT3_E_INVALID, std::string("unknown pass '") + pass_name + "' (known: " + names_of(kPasses) + ")");
+}
+int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->denoise.params = kDenoiseDefaults;
+        return RT3_OK;
+    }
+    if (p->iterations > 8) return fail(c, RT3_E_INVALID, "denoise params: iterations must be 0..8 (step 2^i: 8 iterations reach 512 pixels)");
+    if (p->normal_squarings > 16) return fail(c, RT3_E_INVALID, "denoise params: normal_squarings must be 0..16 (the exponent is 2^k)");
+    if (!(std::isfinite(p->sigma_z) && p->sigma_z > 0.0f) || !(std::isfinite(p->sigma_l) && p->sigma_l > 0.0f))
+        return fail(c, RT3_E_INVALID, "denoise params: sigma_z and sigma_l must be finite and positive");
+    if (p->flags & ~RT3_DENOISE_NO_DEMODULATION) return fail(c, RT3_E_INVALID, "denoise params: unknown flag bits");
+    c->denoise.params = *p;
+    return RT3_OK;
+}
+int rt3_denoise_set_variance_input(rt3_ctx* c, uint32_t moments_image) {
+    if (!c) return RT3_E_INVALID;
+    c->denoise.variance_image = moments_image;  // checked when "denoise" is launched: the image may be created, resized or destroyed in between
+    return RT3_OK;
+}
+int rt3_temporal_set_prev_view(rt3_ctx* c, const void* prev_gconst, size_t size) {
+    if (!c) return RT3_E_INVALID;
+    if (!prev_gconst && size == 0) {
+        c->temporal.has_prev = false;
+        return RT3_OK;
+    }
+    if (!prev_gconst || size != sizeof(rt3_gconst)) return fail(c, RT3_E_INVALID, "temporal prev view: must be the 304-byte GConst block of the previous frame, or (NULL, 0)");
+    memcpy(&c->temporal.prev, prev_gconst, sizeof(rt3_gconst));
+    c->temporal.has_prev = true;
+    return RT3_OK;
+}
+int rt3_temporal_set_motion_input(rt3_ctx* c, uint32_t motion_image) {
+    if (!c) return RT3_E_INVALID;
+    c->temporal.motion_image = motion_image;  // checked when "temporal" is launched, like the variance input of "denoise"
+    return RT3_OK;
+}
+int rt3_temporal_set_params(rt3_ctx* c, const rt3_temporal_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->temporal.params = kTemporalDefaults;
+        return RT3_OK;
+    }
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
+        return fail(c, RT3_E_INVALID, "temporal params: alpha and alpha_moments must lie in [0, 1]");
+    if (p->max_history < 1 || p->max_history > 65535) return fail(c, RT3_E_INVALID, "temporal params: max_history must be 1..65535");
+    if (!(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f)) return fail(c, RT3_E_INVALID, "temporal params: normal_cos must lie in [-1, 1]");
+    if (!(std::isfinite(p->plane_tolerance) && p->plane_tolerance > 0.0f)) return fail(c, RT3_E_INVALID, "temporal params: plane_tolerance must be finite and positive");
+    if (p->flags & ~RT3_TEMPORAL_NO_DEMODULATION) return fail(c, RT3_E_INVALID, "temporal params: unknown flag bits");
+    c->temporal.params = *p;
+    return RT3_OK;
+}
+
+}  // extern "C"
