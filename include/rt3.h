@@ -459,6 +459,10 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      textures of the context: 27 tex_alpha (base-colour texture index as int32, u, v -> alpha in [0, 1]; 1 for an index without a texture),
  *      the alpha-mask lookup of the traversal kernels (rt3_scene_set_alpha_cutoffs).
  *      28 expn (x >= 0 -> e^-x, the polynomial of the denoise pass's edge weights).
+ *      29 hit_info, the surface stage (flattened primitive id as u32, bu, bv -> Surface in op 5's 11 words: albedo, emissive, normal,
+ *      roughness, metalness), read from the shading tables of the current acceleration structure in either instance mode: RT3_E_STATE
+ *      without a built, current structure; RT3_E_INVALID, before anything is launched, if a row's primitive id is not below the number
+ *      of flattened primitives.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

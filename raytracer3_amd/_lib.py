@@ -25,6 +25,7 @@ OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: sh
 DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
 TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
+SELFTEST_HIT_INFO = 29  # rt3_selftest_eval op: {flattened primitive (u32), bu, bv} -> Surface (11 words), hit_info of the built world
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",

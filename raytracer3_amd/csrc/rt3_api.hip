@@ -353,9 +353,16 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     uint32_t iw, ow;
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
     if ((op == 25 || op == 26) && !c->scene.d_sky) return fail(c, RT3_E_STATE, "selftest: the sky ops need a sky (rt3_scene_set_sky)");
+    if (op == 29) {  // hit_info indexes the flattened world's tables: nothing is launched that would read outside them
+        if (int r = check_accel_current(c)) return r;
+        const uint32_t* rows = static_cast<const uint32_t*>(in);
+        for (uint32_t i = 0; i < n; i++)
+            if (rows[3 * (size_t)i] >= c->accel.n_flat_prims)
+                return fail(c, RT3_E_INVALID, "selftest: hit_info row " + std::to_string(i) + " names a primitive the flattened world does not have");
+    }
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
-    if (op == 27)
+    if (op == 27 || op == 29)
         if (int r = sync_textures(c)) return r;
     DevBuf<uint32_t> d_in, d_out;
     HIPC(c, d_in.alloc_bytes((size_t)n * iw * 4));

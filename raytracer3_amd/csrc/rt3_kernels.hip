@@ -1148,7 +1148,8 @@ __global__ void k_unpack_tiles(const uint32_t* __restrict__ pixels, uint32_t npi
 // ------------------------------------------------------------------------------------------------ self-test
 // Evaluates one device function per element so that tests can pin the device arithmetic against known answers
 // (rt3_selftest_eval).  in / out are dense arrays of `in_w` / `out_w` 32-bit words per element.
-// Ops 25 and 26 read the context's sky through `sc` (rt3_selftest_eval refuses them without one).
+// Ops 25 and 26 read the context's sky through `sc` (rt3_selftest_eval refuses them without one); op 29 reads the flattened world's
+// shading tables (refused without a current acceleration structure, and for a primitive the world does not have).
 __global__ void k_selftest(int op, const SceneDev sc, const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1281,14 +1282,23 @@ __global__ void k_selftest(int op, const SceneDev sc, const uint32_t* __restrict
         case 27:  // alpha mask: {texture index (int32), u, v} -> tex_alpha, the traversal's function
             out[i] = U(tex_alpha(sc.tex_table, sc.tex_pixels, sc.n_tex, (int32_t)in[3 * i], F(in[3 * i + 1]), F(in[3 * i + 2])));
             break;
+        case 29: {  // surface stage: {prim, bu, bv} -> Surface in op 5's order (rt3_selftest_eval checks prim against the flattened world)
+            const Surface s = hit_info(sc, in[3 * i], F(in[3 * i + 1]), F(in[3 * i + 2]));
+            uint32_t* o = out + 11 * i;
+            o[0] = U(s.albedo.x); o[1] = U(s.albedo.y); o[2] = U(s.albedo.z);
+            o[3] = U(s.emissive.x); o[4] = U(s.emissive.y); o[5] = U(s.emissive.z);
+            o[6] = U(s.normal.x); o[7] = U(s.normal.y); o[8] = U(s.normal.z);
+            o[9] = U(s.roughness); o[10] = U(s.metalness);
+            break;
+        }
         default: break;
     }
 }
 bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
-    static const uint32_t w[29][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
+    static const uint32_t w[30][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
-                                      {2, 9}, {2, 4}, {3, 1}, {1, 1}};
-    if (op < 0 || op > 28) return false;
+                                      {2, 9}, {2, 4}, {3, 1}, {1, 1}, {3, 11}};
+    if (op < 0 || op > 29) return false;
     *in_w = w[op][0];
     *out_w = w[op][1];
     return true;

@@ -227,6 +227,16 @@ class Scene:
         lib().orc_trace_brute(self.h, ptr(rays), n, ptr(t), ptr(u), ptr(v), ptr(p), mode, threads)
         return t, u, v, p
 
+    def hit_info(self, prim, bu, bv):
+        """the surfaces of hits (flattened primitive ids, barycentrics): (n, 11) float32 {albedo, emissive, normal, roughness, metalness}.
+        Reads the flattened world, not the tree: no orc_accel_build needed."""
+        prim = np.ascontiguousarray(prim, np.uint32); bu = np.ascontiguousarray(bu, np.float32); bv = np.ascontiguousarray(bv, np.float32)
+        out = np.zeros((len(prim), 11), np.float32)
+        fn = lib().orc_hit_info
+        for i in range(len(prim)):
+            fn(self.h, int(prim[i]), float(bu[i]), float(bv[i]), out[i].ctypes.data)
+        return out
+
     def gbuffer(self, g, rect=None, threads=8):
         W, H = int(g.window_size[0]), int(g.window_size[1])
         x0, y0, x1, y1 = rect or (0, 0, W, H)

@@ -314,6 +314,9 @@ def sky_cases():
         "5x3": rng.uniform(0.0, 3.0, (3, 5, 3)).astype(F32),
         "256x128": scenes.sky(256, 128),
         "sun1e4": dark,
+        # the heights on both sides of k_shade's switch between marginal tables staged in LDS (<= 2048 rows) and read from global memory
+        "8x2048": (sky_gradient_sun(8, 2048) * rng.uniform(0.5, 1.5, (2048, 8, 1))).astype(F32),
+        "8x2049": (sky_gradient_sun(8, 2049) * rng.uniform(0.5, 1.5, (2049, 8, 1))).astype(F32),
     }
 
 
@@ -492,7 +495,7 @@ def test_vndf_inside_the_frame_band_is_pinned(backend):
     check_vndf_band(backend, 20)
 
 
-@pytest.mark.parametrize("name", ["37x19", "5x3", "256x128", "sun1e4"])
+@pytest.mark.parametrize("name", ["37x19", "5x3", "256x128", "sun1e4", "8x2048", "8x2049"])
 def test_sky_sampler_matches_float64(backend, name):
     rgb = sky_cases()[name]
     sk = backend.sky(rgb)
