@@ -188,6 +188,37 @@ int rt3_scene_set_texture(rt3_ctx *ctx, uint32_t index, const uint8_t *rgba_srgb
  *      rt3_accel_download return RT3_E_STATE, rt3_accel_refit RT3_E_STATE) until rt3_accel_build.  A masked geometry needs the default node
  *      layout (else RT3_E_UNSUPPORTED at build); rt3_accel_import is RT3_E_UNSUPPORTED while any cutoff is > 0.  Borrowed for the call. ---- */
 int rt3_scene_set_alpha_cutoffs(rt3_ctx *ctx, const float *cutoffs, uint32_t n);
+/* ---- material textures: glTF pbrMetallicRoughness.metallicRoughnessTexture, normalTexture and emissiveTexture.  No reference counterpart
+ *      (hit_logic.slang:31-33 samples base colour only).  DESIGN.md section 4j.  One entry per geometry of the last rt3_scene_set_geometry
+ *      (n = that count), or n = 0: none, which is also what rt3_scene_set_geometry resets every geometry to.  The indices name textures of
+ *      the one pool of rt3_scene_set_texture (RGBA8); the slot that names a texture decides how its bytes are decoded.  -1, or an index at or
+ *      above the number of uploaded textures, is "no texture" (as for base_color_texture_index).  All three lookups happen at the uv that
+ *      hit_finish interpolates, with texture_sample's texel coordinates, repeat addressing and weights (fx, fy) at mip 0, and blend as
+ *      lerp(a, b, f) = a + (b - a) * f, along x first, then along y -- so a constant texture returns its value exactly:
+ *       - roughness = roughness_factor * G, metalness = metallic_factor * B, a byte decoded as (float)byte * (1.0f / 255.0f) (linear);
+ *       - emissive = (emission * 12) * rgb, rgb decoded by the sRGB table of the base-colour lookup.  A geometry that names an emissive
+ *         texture (index >= 0) is left out of the emitter table of RT3_F_NEE_EMISSIVE like a masked one: its emission counts with weight 1
+ *         where a BSDF-sampled ray hits it;
+ *       - normal map: every flattened primitive gets a tangent at build and at refit, from its object-space positions p and uvs:
+ *         e1 = p1 - p0, e2 = p2 - p0, det = du1 dv2 - du2 dv1, T = normalise(e1 dv2 - e2 dv1) * sign(det), handedness
+ *         h = sign(det) * sign(dot(cross(e1, e2), n0 + n1 + n2)) (a zero dot counts as positive); det == 0 or a T that is not finite: the
+ *         primitive has no tangent.  T is stored octahedrally, 2 x 15 bits.  At a hit, with n the normalised blend of the vertex normals in
+ *         object space: t = normalise(T - n dot(n, T)), b = h cross(n, t), c = 2 lerp(byte / 255) - 1 per channel,
+ *         n' = normalise((s c.x) t + (s c.y) b + c.z n), s = normal_scale; n' replaces n ahead of the instance matrix.  n stays when the
+ *         primitive has no tangent or when T - n dot(n, T) or the combined vector is zero or not finite.  Per-triangle tangents (no TANGENT
+ *         accessor, no MikkTSpace) are the documented deviation; a mapped normal that faces away from the ray is treated as an interpolated
+ *         one is.
+ *      G-buffer packing, face-forward, the BSDF, the alpha test and the motion, temporal and denoise passes are unchanged.  Works in both
+ *      instance modes and after rt3_accel_import.  A normal_scale that is not finite, an index below -1 or a wrong n is RT3_E_INVALID and
+ *      changes nothing.  Takes effect at the next rt3_accel_build; until then an existing structure is unusable, as after
+ *      rt3_scene_set_alpha_cutoffs.  Borrowed for the call. ---- */
+typedef struct rt3_material_textures {
+    int32_t metallic_roughness_texture; /* -1 = none; glTF channels: G = roughness, B = metalness, linear */
+    int32_t normal_texture;             /* -1 = none; tangent-space normal map, linear */
+    int32_t emissive_texture;           /* -1 = none; sRGB-encoded colour */
+    float   normal_scale;               /* glTF normalTexture.scale */
+} rt3_material_textures;                /* 16 bytes */
+int rt3_scene_set_material_textures(rt3_ctx *ctx, const rt3_material_textures *m, uint32_t n);
 
 /* ---- instances: the reference's world is a list of placed meshes (add_instance / loaded_assets, world/mod.rs:50-101) under a
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info

@@ -31,6 +31,7 @@ EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_alpha_cutoffs",
+    "rt3_scene_set_material_textures",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
@@ -141,6 +142,7 @@ def load():
         "rt3_scene_set_bluenoise": (i32, [vp, vp, u32, u32]),
         "rt3_scene_set_texture": (i32, [vp, u32, vp, u32, u32]),
         "rt3_scene_set_alpha_cutoffs": (i32, [vp, vp, u32]),
+        "rt3_scene_set_material_textures": (i32, [vp, vp, u32]),
         "rt3_scene_set_instances": (i32, [vp, vp, u32]),
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),

@@ -32,6 +32,19 @@ GEOMETRY_DTYPE = np.dtype(
     ]
 )
 assert GEOMETRY_DTYPE.itemsize == 64
+# rt3_material_textures (include/rt3.h): texture indices into Mesh.textures, -1 = none
+MATERIAL_TEXTURES_DTYPE = np.dtype(
+    [("metallic_roughness_texture", "<i4"), ("normal_texture", "<i4"), ("emissive_texture", "<i4"), ("normal_scale", "<f4")]
+)
+assert MATERIAL_TEXTURES_DTYPE.itemsize == 16
+
+
+def no_material_textures(n: int) -> np.ndarray:
+    """n entries of MATERIAL_TEXTURES_DTYPE that name no texture (normal_scale 1)"""
+    t = np.zeros(n, MATERIAL_TEXTURES_DTYPE)
+    t["metallic_roughness_texture"] = t["normal_texture"] = t["emissive_texture"] = -1
+    t["normal_scale"] = 1.0
+    return t
 
 
 @dataclass
@@ -45,6 +58,11 @@ class Material:
     texture_offset: int = -1
     alpha_cutoff: float = 0.0  # glTF alphaMode MASK: alphaCutoff (0 = opaque)
     alpha: float = 1.0  # baseColorFactor[3] -> GeometryInfo.base_color[3]
+    # material textures: indices into Mesh.textures, -1 = none
+    metallic_roughness_texture: int = -1  # G = roughness, B = metalness, linear
+    normal_texture: int = -1  # tangent-space normal map, linear
+    emissive_texture: int = -1  # sRGB-encoded colour
+    normal_scale: float = 1.0  # glTF normalTexture.scale
 
 
 @dataclass
@@ -58,8 +76,12 @@ class Mesh:
     names: list = field(default_factory=list)
     textures: list = field(default_factory=list)  # base-colour textures: (h, w, 4) uint8, sRGB-encoded colour
     alpha_cutoffs: np.ndarray = None  # (g,) float32 alpha cutoff per geometry (rt3_scene_set_alpha_cutoffs); None -> zeros (all opaque)
+    material_textures: np.ndarray = None  # (g,) MATERIAL_TEXTURES_DTYPE (rt3_scene_set_material_textures); None -> no texture anywhere
 
     def __post_init__(self):
+        if self.material_textures is None:
+            self.material_textures = no_material_textures(len(self.geometries))
+        self.material_textures = np.ascontiguousarray(self.material_textures, MATERIAL_TEXTURES_DTYPE).reshape(len(self.geometries))
         if self.alpha_cutoffs is None:
             self.alpha_cutoffs = np.zeros(len(self.geometries), np.float32)
         self.alpha_cutoffs = np.ascontiguousarray(self.alpha_cutoffs, np.float32).reshape(len(self.geometries))
@@ -82,7 +104,7 @@ class MeshBuilder:
     """Accumulates (positions, normals, uvs, triangles, material) parts into a `Mesh`."""
 
     def __init__(self):
-        self.v, self.i, self.g, self.c, self.names, self.cut = [], [], [], [], [], []
+        self.v, self.i, self.g, self.c, self.names, self.cut, self.mt = [], [], [], [], [], [], []
         self.nv = 0
         self.ni = 0
 
@@ -109,6 +131,7 @@ class MeshBuilder:
         self.g.append(g)
         self.c.append(len(tris))
         self.cut.append(mat.alpha_cutoff)
+        self.mt.append((mat.metallic_roughness_texture, mat.normal_texture, mat.emissive_texture, mat.normal_scale))
         self.names.append(name)
         self.nv += len(pos)
         self.ni += tris.size
@@ -121,6 +144,7 @@ class MeshBuilder:
             np.array(self.c, np.uint32),
             list(self.names),
             alpha_cutoffs=np.array(self.cut, np.float32),
+            material_textures=np.array(self.mt, MATERIAL_TEXTURES_DTYPE),
         )
 
 
@@ -171,6 +195,13 @@ def write_glb(path, mesh: Mesh) -> None:
         if int(g["base_color_texture_index"]) > -1:
             pbr["baseColorTexture"] = {"index": int(g["base_color_texture_index"])}
         mtl = {"name": f"mat{gi}", "pbrMetallicRoughness": pbr, "emissiveFactor": [float(x) for x in g["emission"][:3]]}
+        mt = mesh.material_textures[gi]
+        if int(mt["metallic_roughness_texture"]) > -1:
+            pbr["metallicRoughnessTexture"] = {"index": int(mt["metallic_roughness_texture"])}
+        if int(mt["normal_texture"]) > -1:
+            mtl["normalTexture"] = {"index": int(mt["normal_texture"]), "scale": float(mt["normal_scale"])}
+        if int(mt["emissive_texture"]) > -1:
+            mtl["emissiveTexture"] = {"index": int(mt["emissive_texture"])}
         if float(mesh.alpha_cutoffs[gi]) > 0.0:  # masked; opaque is glTF's default and stays implicit
             mtl["alphaMode"], mtl["alphaCutoff"] = "MASK", float(mesh.alpha_cutoffs[gi])
         materials.append(mtl)
@@ -309,8 +340,14 @@ class GltfMeshLoader:
                         tex = pbr.get("baseColorTexture", {}).get("index", -1)
                         # alphaMode MASK: alphaCutoff (default 0.5); OPAQUE and BLEND (not supported: drawn opaque) -> 0
                         cut = float(gmtl.get("alphaCutoff", 0.5)) if gmtl.get("alphaMode", "OPAQUE") == "MASK" else 0.0
+
+                        def tex_index(info):  # a texture reference; one through another uv set than TEXCOORD_0 counts as absent
+                            return int(info.get("index", -1)) if info and info.get("texCoord", 0) == 0 else -1
+
+                        nt = gmtl.get("normalTexture")
                         mat = Material(tuple(bc[:3]), pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), tuple(em), tex, cut,
-                                       float(bc[3]) if len(bc) > 3 else 1.0)
+                                       float(bc[3]) if len(bc) > 3 else 1.0, tex_index(pbr.get("metallicRoughnessTexture")), tex_index(nt),
+                                       tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0)
                     mb.add(f"{gm.get('name', 'mesh')}.{pi}", pos, nrm, uv, tris, mat, normalize=not keep)
             for c in node.get("children", []):
                 visit(c, m)

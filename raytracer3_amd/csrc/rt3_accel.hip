@@ -58,6 +58,8 @@ SceneDev scene_dev(const rt3_ctx* c) {
     s.tex_table = c->scene.d_tex_table.get();
     s.srgb_lut = c->scene.d_srgb_lut.get();
     s.n_tex = c->scene.d_tex_pixels ? (uint32_t)c->scene.h_tex.size() : 0u;
+    s.mat_tex = c->accel.has_mat_tex ? c->accel.d_mat_tex.get() : nullptr;
+    s.tri_tan = c->accel.has_mat_tex && c->accel.shade.has_tan ? c->accel.shade.tan.get() : nullptr;
     return s;
 }
 
@@ -84,6 +86,7 @@ static int flatten_world(rt3_ctx* c) {
     const auto [inst, n_inst] = placements(c, whole);
     std::vector<FlatGeomDev> flat;
     std::vector<ShadeGeomDev> shade;
+    std::vector<MatTexDev> mats;
     std::vector<uint32_t> first;
     std::vector<Placed> placed;
     uint64_t total = 0;
@@ -112,6 +115,12 @@ static int flatten_world(rt3_ctx* c) {
             memcpy(sg.m, f.m, 9 * sizeof(float));
             flat.push_back(f);
             shade.push_back(sg);
+            if (any_mat_tex(c)) {
+                static_assert(sizeof(rt3_material_textures) == sizeof(MatTexDev), "material texture layouts");
+                MatTexDev mt;
+                memcpy(&mt, &c->scene.h_mat_tex[g], sizeof(mt));
+                mats.push_back(mt);
+            }
             first.push_back((uint32_t)total);
             placed.push_back({(uint32_t)i, g, (uint32_t)total, c->scene.h_prim_counts[g], identity});
             total += c->scene.h_prim_counts[g];
@@ -131,6 +140,13 @@ static int flatten_world(rt3_ctx* c) {
         launch_prim_geom(c->stream, c->accel.d_first_prim.get(), (uint32_t)nf, (uint32_t)total, c->accel.d_prim_geom.get());
         HIPC(c, hipGetLastError());
     }
+    c->accel.has_mat_tex = c->accel.has_normal_tex = false;
+    if (!mats.empty()) {
+        if (int r = dev_alloc(c, c->accel.d_mat_tex, nf)) return r;
+        HIPC(c, hipMemcpy(c->accel.d_mat_tex.get(), mats.data(), nf * sizeof(MatTexDev), hipMemcpyHostToDevice));
+        c->accel.has_mat_tex = true;
+        for (const MatTexDev& mt : mats) c->accel.has_normal_tex = c->accel.has_normal_tex || mt.normal_tex >= 0;
+    }
     c->accel.n_flat_geoms = (uint32_t)nf;
     c->accel.n_flat_prims = (uint32_t)total;
     c->accel.placed.swap(placed);
@@ -141,8 +157,9 @@ static int make_shade_records(rt3_ctx* c) {
     std::vector<uint64_t> key{c->scene.content_gen};
     for (const Placed& p : c->accel.placed) key.push_back(p.geom);
     ShadeRecords& s = c->accel.shade;
-    if (key == s.key) return RT3_OK;
+    if (key == s.key && s.has_tan == c->accel.has_normal_tex) return RT3_OK;
     s.key.clear();  // until the new records are in place
+    s.has_tan = false;
     if (!s.rec || !s.uv || s.n != c->accel.n_flat_prims) {  // (a refit rewrites them in place)
         if (int r = dev_alloc(c, s.rec, (size_t)c->accel.n_flat_prims)) return r;
         if (int r = dev_alloc(c, s.uv, 3 * (size_t)c->accel.n_flat_prims)) return r;
@@ -150,6 +167,15 @@ static int make_shade_records(rt3_ctx* c) {
     }
     launch_tri_shade(c->stream, world_tables(c), c->accel.n_flat_prims, s.rec.get(), s.uv.get());
     HIPC(c, hipGetLastError());
+    if (c->accel.has_normal_tex) {  // the tangent records go with the shading records: remade by the same builds and refits
+        if (s.tan.capacity_bytes() < (size_t)c->accel.n_flat_prims * sizeof(uint32_t))  // (a refit rewrites them in place)
+            if (int r = dev_alloc(c, s.tan, (size_t)c->accel.n_flat_prims)) return r;
+        launch_tri_tangent(c->stream, world_tables(c), c->accel.n_flat_prims, s.tan.get());
+        HIPC(c, hipGetLastError());
+        s.has_tan = true;
+    } else {
+        s.tan.reset();
+    }
     s.key = std::move(key);
     return RT3_OK;
 }
@@ -166,7 +192,9 @@ int ensure_lights(rt3_ctx* c) {
     for (const Placed& p : c->accel.placed) {
         const float* em = c->scene.h_geoms[p.geom].emission;
         const bool masked = any_cutoff(c) && c->scene.h_cutoffs[p.geom] > 0.0f;  // left out: its points may be cut away
-        const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked;
+        // an emissive texture scales the radiance point by point: left out like a masked geometry
+        const bool textured = any_mat_tex(c) && c->scene.h_mat_tex[p.geom].emissive_texture >= 0;
+        const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked && !textured;
         geom_base.push_back(emissive ? (uint32_t)n : kMiss);
         if (emissive) {
             eg_geom.push_back((uint32_t)(geom_base.size() - 1));

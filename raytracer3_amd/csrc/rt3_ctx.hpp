@@ -98,6 +98,8 @@ struct MeshTables {
 struct ShadeRecords {
     DevBuf<uint4> rec;
     DevBuf<float2> uv;
+    DevBuf<uint32_t> tan;  // tangent words (k_tri_tangent): held only while some geometry names a normal texture; has_tan says whether valid
+    bool has_tan = false;
     uint32_t n = 0;  // records the buffers hold
     std::vector<uint64_t> key;
 };
@@ -134,6 +136,8 @@ struct rt3_ctx {
         int64_t max_tex_index = -1;
         // alpha masks: cutoff per uploaded geometry (empty = all 0, opaque)
         std::vector<float> h_cutoffs;
+        // material textures per uploaded geometry (empty = none anywhere)
+        std::vector<rt3_material_textures> h_mat_tex;
         std::vector<rt3_instance> h_instances;   // empty = one identity instance of every geometry
         // the previous frame's instance matrices, n x 16 column-major (rt3_scene_set_prev_transforms; empty = every instance unmoved)
         std::vector<float> prev_transforms;
@@ -161,6 +165,8 @@ struct rt3_ctx {
     struct Accel {
         rt3::DevBuf<rt3::FlatGeomDev> d_geoms;             // one entry per (instance, geometry): built by rt3_accel_build (flatten_world)
         rt3::DevBuf<rt3::ShadeGeomDev> d_shade_geoms;      // the same table as hit_info reads it
+        rt3::DevBuf<rt3::MatTexDev> d_mat_tex;             // per flattened geometry; has_mat_tex: the built scene names a material texture
+        bool has_mat_tex = false, has_normal_tex = false;
         rt3::DevBuf<uint32_t> d_prim_geom, d_first_prim;
         uint32_t n_flat_geoms = 0, n_flat_prims = 0;  // after flattening: what the acceleration structure and the shading records cover
         std::vector<rt3::Placed> placed;              // the same, on the host: n_flat_geoms entries
@@ -310,6 +316,7 @@ int sync_textures(rt3_ctx* c);
 int revalidate_geometry(rt3_ctx* c);
 int deform_flags(rt3_ctx* c);
 inline bool any_cutoff(const rt3_ctx* c) { return !c->scene.h_cutoffs.empty(); }
+inline bool any_mat_tex(const rt3_ctx* c) { return !c->scene.h_mat_tex.empty(); }
 
 // ---- rt3_accel.hip
 void invalidate_accel(rt3_ctx* c);  // the structure is not for the current scene any more: accel.built goes

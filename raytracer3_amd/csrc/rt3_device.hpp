@@ -426,6 +426,13 @@ RT3_DEV V3 transform_vector(const float* m9, V3 v) {  // mul(transform, float4(v
     return v3(m9[6] * v.z + (m9[3] * v.y + m9[0] * v.x), m9[7] * v.z + (m9[4] * v.y + m9[1] * v.x), m9[8] * v.z + (m9[5] * v.y + m9[2] * v.x));
 }
 
+// == rt3_material_textures, per flattened geometry (the side table of hit_finish<true>)
+struct MatTexDev {
+    int32_t mr_tex, normal_tex, emissive_tex;
+    float normal_scale;
+};
+static_assert(sizeof(MatTexDev) == 16, "MatTex layout");
+
 struct SceneDev {
     const float* verts;          // interleaved p n t (8 floats)
     const uint32_t* indices;
@@ -448,6 +455,9 @@ struct SceneDev {
     uint32_t sky_w, sky_h, sky_wt;  // sky_wt = tiles per tile row = ceil(sky_w / 4)
     const uint8_t* bluenoise;
     uint32_t bn_w, bn_h;
+    // material textures: null unless the built scene names one
+    const MatTexDev* mat_tex;    // per flattened geometry, 16 B
+    const uint32_t* tri_tan;     // per global primitive: the tangent word (tan_encode); null unless some geometry names a normal texture
 };
 
 // hit_logic.slang:5-40 (transform = identity, vertex colour = 1).  The three index + three vertex gathers of
@@ -542,6 +552,95 @@ RT3_DEV uint32_t octa_encode16(V3 n) {  // :64-75, then 16-bit unorm per coordin
 }
 RT3_DEV V3 octa_decode16(uint32_t w) { return octa_decode((float)(w & 0xFFFFu) * (1.0f / 65535.0f), (float)(w >> 16) * (1.0f / 65535.0f)); }
 
+// ------------------------------------------------------------------------------------------------ material textures
+// Tangent word of a primitive: the unit tangent T through the octahedral map at 15 bits per coordinate (bits 0-14 x, 15-29 y), bit 30 = the
+// handedness h is -1, bit 31 = the primitive has a tangent.  0 = no tangent.
+constexpr uint32_t kTanValid = 0x80000000u, kTanFlip = 0x40000000u;
+RT3_DEV bool finite_pos(float x) { return x > 0.0f && x <= 3.4028234663852886e38f; }
+RT3_DEV uint32_t tan_encode(V3 T, bool flip) {  // octa_encode16's steps on a 15-bit grid
+    const float s = fabsf(T.x) + fabsf(T.y) + fabsf(T.z);
+    if (!finite_pos(s)) return 0u;
+    float x = T.x / s, y = T.y / s;
+    const float z = T.z / s;
+    if (z < 0.0f) {  // octa_wrap
+        const float wx = (1.0f - fabsf(y)) * ((x >= 0.0f ? 1.0f : 0.0f) * 2.0f - 1.0f);
+        const float wy = (1.0f - fabsf(x)) * ((y >= 0.0f ? 1.0f : 0.0f) * 2.0f - 1.0f);
+        x = wx;
+        y = wy;
+    }
+    x = x * 0.5f + 0.5f;
+    y = y * 0.5f + 0.5f;
+    const uint32_t qx = (uint32_t)(fmin_sel(fmax_sel(x, 0.0f), 1.0f) * 32767.0f + 0.5f), qy = (uint32_t)(fmin_sel(fmax_sel(y, 0.0f), 1.0f) * 32767.0f + 0.5f);
+    return qx | (qy << 15) | (flip ? kTanFlip : 0u) | kTanValid;
+}
+RT3_DEV V3 tan_decode(uint32_t w) { return octa_decode((float)(w & 0x7FFFu) * (1.0f / 32767.0f), (float)((w >> 15) & 0x7FFFu) * (1.0f / 32767.0f)); }
+// The tangent word of a triangle from its object-space positions, uvs and vertex normals (k_tri_tangent; rt3.h has the rule)
+RT3_DEV uint32_t tangent_word(V3 p0, V3 p1, V3 p2, float2 t0, float2 t1, float2 t2, V3 nsum) {
+    const V3 e1 = p1 - p0, e2 = p2 - p0;
+    const float du1 = t1.x - t0.x, dv1 = t1.y - t0.y, du2 = t2.x - t0.x, dv2 = t2.y - t0.y;
+    const float det = du1 * dv2 - du2 * dv1;
+    if (!(det != 0.0f)) return 0u;  // (a NaN determinant too)
+    const V3 r = e1 * dv2 - e2 * dv1;
+    const float l2 = dot(r, r);
+    if (!finite_pos(l2)) return 0u;
+    V3 T = r * (1.0f / sqrtf(l2));
+    if (det < 0.0f) T = neg(T);
+    const bool flip = (det < 0.0f) != (dot(cross(e1, e2), nsum) < 0.0f);
+    return tan_encode(T, flip);
+}
+// the four texels of texture_sample's bilinear footprint and its weights
+struct TexQuad {
+    uint32_t p00, p10, p01, p11;
+    float fx, fy;
+};
+RT3_DEV TexQuad tex_quad(const SceneDev& sc, uint32_t index, float u, float v) {
+    const uint4 t = sc.tex_table[index];
+    const int W = (int)t.y, H = (int)t.z;
+    const uint8_t* px = sc.tex_pixels + t.x;
+    float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
+    float xf = floorf(x), yf = floorf(y);
+    int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
+    x0 = wrap_index(x0, W);
+    x1 = wrap_index(x1, W);
+    y0 = wrap_index(y0, H);
+    y1 = wrap_index(y1, H);
+    TexQuad q;
+    q.fx = x - xf;
+    q.fy = y - yf;
+    q.p00 = *reinterpret_cast<const uint32_t*>(px + 4 * ((size_t)y0 * W + x0));
+    q.p10 = *reinterpret_cast<const uint32_t*>(px + 4 * ((size_t)y0 * W + x1));
+    q.p01 = *reinterpret_cast<const uint32_t*>(px + 4 * ((size_t)y1 * W + x0));
+    q.p11 = *reinterpret_cast<const uint32_t*>(px + 4 * ((size_t)y1 * W + x1));
+    return q;
+}
+RT3_DEV float lerp_ab(float a, float b, float f) { return a + (b - a) * f; }
+// channel k of the footprint, bytes decoded linearly; x first, then y
+RT3_DEV float quad_linear(const TexQuad& q, int k) {
+    const float a = (float)((q.p00 >> (8 * k)) & 0xFFu) * (1.0f / 255.0f), b = (float)((q.p10 >> (8 * k)) & 0xFFu) * (1.0f / 255.0f);
+    const float c = (float)((q.p01 >> (8 * k)) & 0xFFu) * (1.0f / 255.0f), d = (float)((q.p11 >> (8 * k)) & 0xFFu) * (1.0f / 255.0f);
+    return lerp_ab(lerp_ab(a, b, q.fx), lerp_ab(c, d, q.fx), q.fy);
+}
+RT3_DEV float quad_srgb(const SceneDev& sc, const TexQuad& q, int k) {
+    const float a = sc.srgb_lut[(q.p00 >> (8 * k)) & 0xFFu], b = sc.srgb_lut[(q.p10 >> (8 * k)) & 0xFFu];
+    const float c = sc.srgb_lut[(q.p01 >> (8 * k)) & 0xFFu], d = sc.srgb_lut[(q.p11 >> (8 * k)) & 0xFFu];
+    return lerp_ab(lerp_ab(a, b, q.fx), lerp_ab(c, d, q.fx), q.fy);
+}
+// n (unit, object space) tilted by the normal-map texel c = 2 lerp - 1 in the frame of tangent word `tanw`; n itself where the rule says so
+RT3_DEV V3 normal_map_apply(V3 n, uint32_t tanw, float cx, float cy, float cz, float s) {
+    if (!(tanw & kTanValid)) return n;
+    const V3 T = tan_decode(tanw);
+    const V3 tp = T - n * dot(n, T);
+    const float l2 = dot(tp, tp);
+    if (!finite_pos(l2)) return n;
+    const V3 t = tp * (1.0f / sqrtf(l2));
+    V3 b = cross(n, t);
+    if (tanw & kTanFlip) b = neg(b);
+    const V3 m = t * (s * cx) + b * (s * cy) + n * cz;
+    const float m2 = dot(m, m);
+    if (!finite_pos(m2)) return n;
+    return m * (1.0f / sqrtf(m2));
+}
+
 // In two steps so that a caller can put independent work (the light sample's table gathers) between the issue of the
 // shading-record load and its use.  The record is 16 bytes {n0, n1, n2, geometry}: a quarter of round 2's 64-byte record, i.e.
 // a 4 MB table for 260 k triangles instead of 16.6 MB (an L2 miss costs a 128-byte line whatever the record's size).
@@ -550,18 +649,51 @@ struct HitRecord {
     uint32_t prim;
 };
 RT3_DEV HitRecord hit_fetch(const SceneDev& sc, uint32_t prim) { return HitRecord{sc.tri_shade[prim], prim}; }
-// `geoms`: the ShadeGeomDev table -- sc.shade_geoms, or the caller's LDS copy of it
-RT3_DEV Surface hit_finish(const SceneDev& sc, const ShadeGeomDev* geoms, const HitRecord& h, float bu, float bv) {
+// the tangent word of a hit: issued beside hit_fetch's record (it depends on the primitive alone), used by hit_finish<true>
+RT3_DEV uint32_t tan_fetch(const SceneDev& sc, uint32_t prim) { return sc.tri_tan ? sc.tri_tan[prim] : 0u; }
+// `geoms`: the ShadeGeomDev table -- sc.shade_geoms, or the caller's LDS copy of it.  MAT: the material textures of DESIGN.md section 4j;
+// `mats` is sc.mat_tex or the caller's LDS copy of it, `tanw` the hit's tan_fetch
+template <bool MAT = false>
+RT3_DEV Surface hit_finish(const SceneDev& sc, const ShadeGeomDev* geoms, const HitRecord& h, float bu, float bv, const MatTexDev* mats = nullptr,
+                           uint32_t tanw = 0u) {
     const ShadeGeomDev& gi = geoms[h.rec.w];
     const V3 n0 = octa_decode16(h.rec.x), n1 = octa_decode16(h.rec.y), n2 = octa_decode16(h.rec.z);
     float b0 = 1.0f - bu - bv;
     V3 n = v3(n0.x * b0 + n1.x * bu + n2.x * bv, n0.y * b0 + n1.y * bu + n2.y * bv, n0.z * b0 + n1.z * bu + n2.z * bv);
     n = normalize(n);                                   // :22
+    V3 tex_albedo = v3(1.0f, 1.0f, 1.0f), tex_emissive = v3(1.0f, 1.0f, 1.0f);
+    float tex_rough = 1.0f, tex_metal = 1.0f;
+    bool has_base = false, has_mr = false, has_e = false;
+    if constexpr (MAT) {
+        const MatTexDev mt = mats[h.rec.w];
+        has_base = gi.tex > -1 && (uint32_t)gi.tex < sc.n_tex;
+        has_mr = mt.mr_tex > -1 && (uint32_t)mt.mr_tex < sc.n_tex;
+        has_e = mt.emissive_tex > -1 && (uint32_t)mt.emissive_tex < sc.n_tex;
+        const bool has_n = mt.normal_tex > -1 && (uint32_t)mt.normal_tex < sc.n_tex;
+        if (has_base || has_mr || has_n || has_e) {
+            const float2 t0 = sc.tri_uv[3 * (size_t)h.prim], t1 = sc.tri_uv[3 * (size_t)h.prim + 1], t2 = sc.tri_uv[3 * (size_t)h.prim + 2];
+            const float uu = t0.x * b0 + t1.x * bu + t2.x * bv, vv = t0.y * b0 + t1.y * bu + t2.y * bv;
+            // the footprints first (up to sixteen independent texel loads in flight), their arithmetic after
+            TexQuad qn = {}, qm = {}, qe = {};
+            if (has_n) qn = tex_quad(sc, (uint32_t)mt.normal_tex, uu, vv);
+            if (has_mr) qm = tex_quad(sc, (uint32_t)mt.mr_tex, uu, vv);
+            if (has_e) qe = tex_quad(sc, (uint32_t)mt.emissive_tex, uu, vv);
+            if (has_base) tex_albedo = texture_sample(sc, (uint32_t)gi.tex, uu, vv);
+            if (has_n) n = normal_map_apply(n, tanw, 2.0f * quad_linear(qn, 0) - 1.0f, 2.0f * quad_linear(qn, 1) - 1.0f, 2.0f * quad_linear(qn, 2) - 1.0f, mt.normal_scale);
+            if (has_mr) {
+                tex_rough = quad_linear(qm, 1);
+                tex_metal = quad_linear(qm, 2);
+            }
+            if (has_e) tex_emissive = v3(quad_srgb(sc, qe, 0), quad_srgb(sc, qe, 1), quad_srgb(sc, qe, 2));
+        }
+    }
     if (!gi.identity) n = transform_vector(gi.m, n);    // :23 mul(geometryInfo.transform, float4(normal, 0.0)).xyz
     n = normalize(n);                                   // :23
     Surface s;
     s.albedo = v3(gi.base_color[0], gi.base_color[1], gi.base_color[2]);
-    if (gi.tex > -1 && (uint32_t)gi.tex < sc.n_tex) {  // :27,31-33
+    if constexpr (MAT) {
+        if (has_base) s.albedo = s.albedo * tex_albedo;
+    } else if (gi.tex > -1 && (uint32_t)gi.tex < sc.n_tex) {  // :27,31-33
         const float2 t0 = sc.tri_uv[3 * (size_t)h.prim], t1 = sc.tri_uv[3 * (size_t)h.prim + 1], t2 = sc.tri_uv[3 * (size_t)h.prim + 2];
         float uu = t0.x * b0 + t1.x * bu + t2.x * bv, vv = t0.y * b0 + t1.y * bu + t2.y * bv;
         s.albedo = s.albedo * texture_sample(sc, (uint32_t)gi.tex, uu, vv);
@@ -570,9 +702,20 @@ RT3_DEV Surface hit_finish(const SceneDev& sc, const ShadeGeomDev* geoms, const 
     s.normal = n;
     s.roughness = gi.roughness;
     s.metalness = gi.metallic;
+    if constexpr (MAT) {
+        if (has_e) s.emissive = s.emissive * tex_emissive;
+        if (has_mr) {
+            s.roughness = gi.roughness * tex_rough;
+            s.metalness = gi.metallic * tex_metal;
+        }
+    }
     return s;
 }
-RT3_DEV Surface hit_info(const SceneDev& sc, uint32_t prim, float bu, float bv) { return hit_finish(sc, sc.shade_geoms, hit_fetch(sc, prim), bu, bv); }
+// (a uniform branch: kernels off the hot path -- k_gbuffer, the probes, selftest op 29 -- take whichever the built scene needs)
+RT3_DEV Surface hit_info(const SceneDev& sc, uint32_t prim, float bu, float bv) {
+    if (sc.mat_tex) return hit_finish<true>(sc, sc.shade_geoms, hit_fetch(sc, prim), bu, bv, sc.mat_tex, tan_fetch(sc, prim));
+    return hit_finish(sc, sc.shade_geoms, hit_fetch(sc, prim), bu, bv);
+}
 
 // ------------------------------------------------------------------------------------------------ sky (north_star)
 // Texels are 8 bytes {RGB9E5 radiance, pdf_uv as f32}: the importance-sampling density of a texel travels with its colour (the

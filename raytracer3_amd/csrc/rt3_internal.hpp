@@ -258,6 +258,8 @@ hipError_t sah_top_relink_gpu(hipStream_t st, uint32_t nn, uint32_t* left, uint3
 
 // shading records (SceneDev::tri_shade, tri_uv) of n flattened primitives: they depend on no tree and no matrix
 void launch_tri_shade(hipStream_t st, GeomTables t, uint32_t n, uint4* tri_shade, float2* tri_uv);
+// tangent words (SceneDev::tri_tan) of the same primitives, for scenes with a normal texture
+void launch_tri_tangent(hipStream_t st, GeomTables t, uint32_t n, uint32_t* tri_tan);
 
 // Two-level structure (rt3_tlas.hip).  One node array: [top tree | two 64-byte records per instance | bottom trees], one triangle array of
 // the bottom trees' object-space records (local primitive ids).

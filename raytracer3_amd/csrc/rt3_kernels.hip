@@ -754,15 +754,26 @@ constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
 // GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
 // normal matrix cost an LDS read behind the shading record instead of a second dependent global gather
 // EMIT: next-event estimation to emissive triangles with MIS; launched only with RT3_F_NEE_EMISSIVE and a non-empty table
-template <bool FIRST, bool GLDS, bool EMIT = false>
-// 6 waves per SIMD (80 VGPRs, 32 bytes of scratch): the kernel lives off memory-level parallelism -- 28.8 -> 27.7 ms against the
-// compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks)
-__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_shade(ShadeLaunch a) {
+// MAT: material textures (hit_finish<true>); launched only when the built scene has the side table (sc.mat_tex), and
+// never for the first vertex, which comes from the G-buffer.  With GLDS the 16-byte side table sits in LDS beside the geometry table, so
+// only the tangent word -- fetched by primitive, beside the shading record -- and the texels themselves are global gathers.
+// Waves per SIMD: 6 (80 VGPRs, 32 bytes of scratch) without MAT: the kernel lives off memory-level parallelism -- 28.8 -> 27.7 ms against
+// the compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks).  MAT holds up to twelve more texels and three footprints' weights
+// across the light sample: the compiler's own allocation is 94 VGPRs (116 with EMIT), above the 80 that 6 waves leave, and a 512-thread
+// block is 2 waves per SIMD, so the next step down from 6 is 4 = 128 VGPRs, which holds both without scratch.
+constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
+template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
+    static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
     __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
     __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
+    __shared__ MatTexDev s_mats[GLDS && MAT ? kShadeGeomsLds : 1];
     if (GLDS) {
-        const uint32_t words = (a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds) * (uint32_t)(sizeof(ShadeGeomDev) / 4);
+        const uint32_t ng = a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds;
+        const uint32_t words = ng * (uint32_t)(sizeof(ShadeGeomDev) / 4);
         for (uint32_t k = threadIdx.x; k < words; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_geoms)[k] = reinterpret_cast<const uint32_t*>(a.sc.shade_geoms)[k];
+        if constexpr (MAT)
+            for (uint32_t k = threadIdx.x; k < ng * 4u; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_mats)[k] = reinterpret_cast<const uint32_t*>(a.sc.mat_tex)[k];
         __syncthreads();
     }
     uint32_t parity = 0;
@@ -803,6 +814,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
         hrecord.rec = make_uint4(0u, 0u, 0u, 0u);
         hrecord.prim = 0u;
         float hbu = 0.0f, hbv = 0.0f;
+        uint32_t htan = 0u;
         float4 ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
         if (!FIRST && active) {  // ray records {o, pdf} + {d, path id}
             ro = reinterpret_cast<const float4*>(a.in_rays)[i];
@@ -853,6 +865,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
                 hbu = hrec.y;
                 hbv = hrec.z;
                 hrecord = hit_fetch(a.sc, prim);  // :55, first half: the loads are issued here, used after the light-sample gathers
+                if constexpr (MAT) htan = tan_fetch(a.sc, prim);
             }
         }
         bool emit_shadow = false, emit_ext = false;
@@ -903,7 +916,10 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(6, 
                 er3 = R[3];
             }
             if (!FIRST) {  // :55, second half (two calls, not a selected pointer: a select would turn the LDS reads into flat loads)
-                if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
+                if constexpr (MAT) {
+                    if (GLDS) surf = hit_finish<true>(a.sc, s_geoms, hrecord, hbu, hbv, s_mats, htan);
+                    else surf = hit_finish<true>(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv, a.sc.mat_tex, htan);
+                } else if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
                 else surf = hit_finish(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv);
             }
             V3 N = surf.normal;
@@ -1387,6 +1403,14 @@ void launch_shade(hipStream_t st, bool first, ShadeLaunch a) {
     a.npix_div = make_fastdiv(a.npix);
     unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
+    if (!first && a.sc.mat_tex != nullptr) {  // the built scene has material textures: the MAT instances, GLDS x EMIT
+        const bool emit = a.lights.n != 0u;
+        if (glds && emit) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else if (glds) hipLaunchKernelGGL((k_shade<false, true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else if (emit) hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else hipLaunchKernelGGL((k_shade<false, false, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        return;
+    }
     if (a.lights.n != 0u) {  // RT3_F_NEE_EMISSIVE with something to sample
         if (first) hipLaunchKernelGGL((k_shade<true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
         else if (glds) hipLaunchKernelGGL((k_shade<false, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);

@@ -115,6 +115,28 @@ __global__ void k_tri_shade(const float* verts, const uint32_t* indices, const F
     }
 }
 
+// tangent word of every flattened primitive (SceneDev::tri_tan), from object-space positions, uvs and vertex normals as
+// uploaded: like the shading records it depends on no tree and no matrix
+__global__ void k_tri_tangent(const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                              const uint32_t* first_prim, uint32_t n, uint32_t* tan) {
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        uint32_t g = prim_geom[p];
+        const GeometryInfoDev& gi = geoms[g].g;
+        uint32_t io = gi.index_offset + 3u * (p - first_prim[g]);
+        const float* v0 = verts + 8 * (size_t)(gi.vertex_offset + indices[io]);
+        const float* v1 = verts + 8 * (size_t)(gi.vertex_offset + indices[io + 1]);
+        const float* v2 = verts + 8 * (size_t)(gi.vertex_offset + indices[io + 2]);
+        const V3 nsum = v3(v0[3], v0[4], v0[5]) + v3(v1[3], v1[4], v1[5]) + v3(v2[3], v2[4], v2[5]);
+        tan[p] = tangent_word(v3(v0[0], v0[1], v0[2]), v3(v1[0], v1[1], v1[2]), v3(v2[0], v2[1], v2[2]), make_float2(v0[6], v0[7]), make_float2(v1[6], v1[7]),
+                              make_float2(v2[6], v2[7]), nsum);
+    }
+}
+void launch_tri_tangent(hipStream_t st, GeomTables t, uint32_t n, uint32_t* tri_tan) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + 255) / 256);
+    hipLaunchKernelGGL(k_tri_tangent, dim3(grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n, tri_tan);
+}
+
 void launch_tri_shade(hipStream_t st, GeomTables t, uint32_t n, uint4* tri_shade, float2* tri_uv) {
     if (n == 0) return;
     const unsigned grid = (unsigned)(((uint64_t)n + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + 255) / 256);

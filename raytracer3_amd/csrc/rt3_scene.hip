@@ -246,6 +246,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->scene.h_geoms.assign(g, g + n);
     c->scene.h_prim_counts.assign(prim_counts, prim_counts + n);
     c->scene.h_cutoffs.clear();  // every geometry opaque again
+    c->scene.h_mat_tex.clear();  // and without material textures
     c->scene.n_geoms = n;
     c->scene.max_tex_index = max_tex;
     c->scene.n_prims = (uint32_t)total;
@@ -263,6 +264,22 @@ int rt3_scene_set_alpha_cutoffs(rt3_ctx* c, const float* cutoffs, uint32_t n) {
     c->scene.h_cutoffs.clear();
     if (std::any_of(cutoffs, cutoffs + n, [](float v) { return v > 0.0f; })) c->scene.h_cutoffs.assign(cutoffs, cutoffs + n);  // (kept only when some geometry is masked)
     invalidate_topology(c);  // the triangle records carry the masks: a new build, not a refit
+    return RT3_OK;
+}
+// material textures of the geometries of the last rt3_scene_set_geometry; n = 0: none
+int rt3_scene_set_material_textures(rt3_ctx* c, const rt3_material_textures* m, uint32_t n) {
+    if (!c || (!m && n)) return fail(c, RT3_E_INVALID, "material textures NULL");
+    if (n != 0 && n != c->scene.n_geoms)
+        return fail(c, RT3_E_INVALID, "material textures: n must be 0 or the geometry count of rt3_scene_set_geometry (" + std::to_string(c->scene.n_geoms) + ")");
+    for (uint32_t i = 0; i < n; i++) {
+        if (m[i].metallic_roughness_texture < -1 || m[i].normal_texture < -1 || m[i].emissive_texture < -1)
+            return fail(c, RT3_E_INVALID, "material textures: entry " + std::to_string(i) + " has a texture index below -1");
+        if (!(std::fabs(m[i].normal_scale) <= 3.4028234663852886e38f)) return fail(c, RT3_E_INVALID, "material textures: normal_scale " + std::to_string(i) + " is not finite");
+    }
+    c->scene.h_mat_tex.clear();
+    if (std::any_of(m, m + n, [](const rt3_material_textures& e) { return e.metallic_roughness_texture >= 0 || e.normal_texture >= 0 || e.emissive_texture >= 0; }))
+        c->scene.h_mat_tex.assign(m, m + n);  // (kept only when some geometry names a texture)
+    invalidate_topology(c);  // the side table and the tangent records are made by a build
     return RT3_OK;
 }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same

@@ -737,6 +737,8 @@ struct Material {  // assets/mod.rs:52-59 (+ emission, datatypes.slang:17)
     int32_t texture_offset = -1;
     float alpha_cutoff = 0.0f;  // glTF alphaMode MASK: alphaCutoff (0 = opaque)
     float alpha = 1.0f;         // baseColorFactor[3] -> rt3_geometry_info::base_color[3]
+    // material textures: indices into Mesh::textures, -1 = none; glTF normalTexture.scale
+    rt3_material_textures textures = {-1, -1, -1, 1.0f};
 };
 struct Mesh {
     std::vector<float> vertices;                // n x 8: position, normal, uv (Vertex, assets/mod.rs:127-133)
@@ -746,6 +748,7 @@ struct Mesh {
     std::vector<std::string> names;
     std::vector<Image> textures;
     std::vector<float> alpha_cutoffs;           // one per geometry (rt3_scene_set_alpha_cutoffs), 0 = opaque
+    std::vector<rt3_material_textures> material_textures;  // one per geometry (rt3_scene_set_material_textures)
     size_t n_vertices() const { return vertices.size() / 8; }
     size_t n_triangles() const {
         size_t t = 0;
@@ -1010,6 +1013,18 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                     const Json* mode = gmtl.find("alphaMode");
                     if (mode && mode->kind == Json::Str && mode->str == "MASK")
                         mat.alpha_cutoff = gmtl.has("alphaCutoff") ? (float)gmtl.at("alphaCutoff").number(0.5) : 0.5f;
+                    // a texture reference; one through another uv set than TEXCOORD_0 counts as absent
+                    auto tex_index = [](const Json* info) -> int32_t {
+                        if (!info || !info->has("index")) return -1;
+                        if (const Json* tc = info->find("texCoord"))
+                            if (tc->integer(0) != 0) return -1;
+                        return (int32_t)info->at("index").integer(-1);
+                    };
+                    mat.textures.metallic_roughness_texture = tex_index(pbr.find("metallicRoughnessTexture"));
+                    mat.textures.normal_texture = tex_index(gmtl.find("normalTexture"));
+                    mat.textures.emissive_texture = tex_index(gmtl.find("emissiveTexture"));
+                    if (const Json* nt = gmtl.find("normalTexture"))
+                        if (const Json* sc = nt->find("scale")) mat.textures.normal_scale = (float)sc->number(1.0);
                 }
                 rt3_geometry_info g{};
                 for (int k = 0; k < 3; k++) {
@@ -1031,6 +1046,7 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                 mesh_.geometries.push_back(g);
                 mesh_.prim_counts.push_back((uint32_t)(idx.size() / 3));
                 mesh_.alpha_cutoffs.push_back(mat.alpha_cutoff);
+                mesh_.material_textures.push_back(mat.textures);
                 mesh_.names.push_back((gm.has("name") ? gm.at("name").str : std::string("mesh")) + "." + std::to_string(this_pi));
             }
         }
@@ -1484,6 +1500,10 @@ inline uint32_t upload(rt3_ctx* ctx, const Mesh& m) {
     for (float c : m.alpha_cutoffs) masked = masked || c != 0.0f;
     if (masked)  // alpha-masked geometry; an opaque scene makes no call
         check(ctx, rt3_scene_set_alpha_cutoffs(ctx, m.alpha_cutoffs.data(), (uint32_t)m.alpha_cutoffs.size()), "rt3_scene_set_alpha_cutoffs");
+    bool mapped = false;
+    for (const rt3_material_textures& t : m.material_textures) mapped = mapped || t.metallic_roughness_texture >= 0 || t.normal_texture >= 0 || t.emissive_texture >= 0;
+    if (mapped)  // material textures; a scene without them makes no call
+        check(ctx, rt3_scene_set_material_textures(ctx, m.material_textures.data(), (uint32_t)m.material_textures.size()), "rt3_scene_set_material_textures");
     for (size_t i = 0; i < m.textures.size(); i++)
         check(ctx, rt3_scene_set_texture(ctx, (uint32_t)i, m.textures[i].rgba.data(), m.textures[i].w, m.textures[i].h), "rt3_scene_set_texture");
     uint32_t handle = 0;

@@ -173,6 +173,9 @@ class Context:
         cut = getattr(mesh, "alpha_cutoffs", None)
         if cut is not None and np.any(np.asarray(cut) != 0):  # alpha-masked geometry; opaque scenes make no call
             self.set_alpha_cutoffs(cut)
+        mt = getattr(mesh, "material_textures", None)
+        if mt is not None and len(mt) and any(np.any(mt[k] >= 0) for k in ("metallic_roughness_texture", "normal_texture", "emissive_texture")):
+            self.set_material_textures(mt)  # material textures; scenes without them make no call
         for i, t in enumerate(getattr(mesh, "textures", None) or []):  # base-colour textures, RGBA8 sRGB
             t = np.ascontiguousarray(t, np.uint8)
             self.check(self.lib.rt3_scene_set_texture(self.h, i, t.ctypes.data, t.shape[1], t.shape[0]))
@@ -181,6 +184,14 @@ class Context:
         """per-geometry alpha cutoffs (glTF alphaMode MASK; 0 = opaque, [] = all opaque); rt3_scene_set_alpha_cutoffs, next build_accel()"""
         c = np.ascontiguousarray(cutoffs, np.float32).reshape(-1)
         self.check(self.lib.rt3_scene_set_alpha_cutoffs(self.h, c.ctypes.data, len(c)))
+
+    def set_material_textures(self, table):
+        """per-geometry metallic-roughness / normal / emissive texture indices and normal scale (assets.MATERIAL_TEXTURES_DTYPE; [] = none);
+        rt3_scene_set_material_textures, next build_accel()"""
+        from .assets import MATERIAL_TEXTURES_DTYPE
+
+        t = np.ascontiguousarray(table, MATERIAL_TEXTURES_DTYPE).reshape(-1)
+        self.check(self.lib.rt3_scene_set_material_textures(self.h, t.ctypes.data if len(t) else None, len(t)))
 
     def set_instances(self, instances):
         """instances: [(geometry_first, geometry_count, 4x4 matrix as numpy, object -> world)] -- Instance + Transform of

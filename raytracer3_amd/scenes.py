@@ -368,6 +368,51 @@ def cutout_cornell() -> Mesh:
                 np.concatenate([mesh.alpha_cutoffs, cut.alpha_cutoffs]).astype(np.float32))
 
 
+MATERIAL_SEED = 20240607
+
+
+def material_cornell(seed: int = MATERIAL_SEED) -> Mesh:
+    """The Cornell box with material textures: the floor's roughness, metalness and normals come from maps (a
+    brushed, tiled metal: factors 1, everything in the textures, as exporters write it) and the ceiling panel's emission from an emissive
+    map (a grid of lamps).  The textures are generated from `seed`."""
+    rng = np.random.default_rng(seed)
+    mesh = cornell()
+    n = 64
+    yy, xx = np.mgrid[0:n, 0:n]
+    tile = ((xx // 16) + (yy // 16)) % 2
+    noise = rng.integers(0, 40, (n, n))
+    rough = np.where(tile == 0, 60, 170) + noise  # G: polished and dull tiles
+    metal = np.where(tile == 0, 255, 30)  # B
+    mr = np.stack([np.zeros_like(rough), rough, metal, np.full_like(rough, 255)], -1).astype(np.uint8)
+    # normal map of a height field: tile bevels plus seeded ripples; c = (-dh/dx, -dh/dy, 1) normalised, stored as (c + 1) / 2
+    fx, fy = (xx % 16) / 16.0, (yy % 16) / 16.0
+    height = 0.6 * np.minimum(np.minimum(fx, 1 - fx), np.minimum(fy, 1 - fy)).clip(0, 0.15)
+    for _ in range(4):
+        kx, ky, ph = rng.integers(1, 5), rng.integers(1, 5), rng.uniform(0, 2 * np.pi)
+        height = height + 0.01 * np.sin(2 * np.pi * (kx * xx + ky * yy) / n + ph)
+    dx = (np.roll(height, -1, 1) - np.roll(height, 1, 1)) * (n / 2.0) * 0.25
+    dy = (np.roll(height, -1, 0) - np.roll(height, 1, 0)) * (n / 2.0) * 0.25
+    c = np.stack([-dx, -dy, np.ones_like(dx)], -1)
+    c /= np.linalg.norm(c, axis=-1, keepdims=True)
+    nm = np.concatenate([np.round((c * 0.5 + 0.5) * 255.0), np.full((n, n, 1), 255.0)], -1).astype(np.uint8)
+    lamps = (((xx % 16) - 8) ** 2 + ((yy % 16) - 8) ** 2 < 30).astype(np.uint8)
+    em = np.stack([lamps * 255, lamps * 240, lamps * 200, np.full_like(lamps, 255)], -1).astype(np.uint8)
+    mesh.textures = [np.ascontiguousarray(t) for t in (mr, nm, em)]
+    light = int(np.flatnonzero((mesh.geometries["emission"][:, :3] != 0).any(1))[0])
+    for g, name in enumerate(mesh.names):
+        if name.startswith("floor"):
+            mesh.geometries["base_color"][g] = (0.9, 0.85, 0.8, 1.0)
+            mesh.geometries["metallic_factor"][g] = mesh.geometries["roughness"][g] = 1.0
+            mesh.material_textures["metallic_roughness_texture"][g], mesh.material_textures["normal_texture"][g] = 0, 1
+            mesh.material_textures["normal_scale"][g] = 1.5
+            vo = int(mesh.geometries["vertex_offset"][g])
+            later = [int(x) for x in mesh.geometries["vertex_offset"] if int(x) > vo]
+            mesh.vertices[vo : (min(later) if later else len(mesh.vertices)), 6:8] *= 2.0
+    mesh.material_textures["emissive_texture"][light] = 2
+    mesh.geometries["emission"][light, :3] *= 3.0  # the lamps cover about a third of the panel
+    return mesh
+
+
 def sky(width: int = 2048, height: int = 1024, seed: int = SKY_SEED) -> np.ndarray:
     """Equirect RGB32F sky: horizon-to-zenith gradient, ground bounce, soft cloud noise, 0.5 degree sun (5e4)."""
     rng = np.random.default_rng(seed)
