@@ -4,7 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rt3_device.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 

@@ -18,8 +18,10 @@
 // it loses (197 us: the border is 3.5 x the tile), so steps >= 4 read through the caches.
 #include <hip/hip_runtime.h>
 
+#include "rt3_camera.hpp"
 #include "rt3_filter_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
 
 namespace rt3 {
 

@@ -3,7 +3,11 @@
 // G-buffer, the demodulated signal and its luminance) and the 32 x 8 launch tile.  One definition, so that both passes round alike: the
 // numpy restatements (tests/ref_denoise.py prepare(), tests/ref_temporal.py) state each expression once as well.
 #pragma once
-#include "rt3_device.hpp"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt3_camera.hpp"
+#include "rt3_math.hpp"
 
 namespace rt3 {
 

@@ -6,7 +6,9 @@
 
 #include <vector>
 
-#include "rt3_device.hpp"
+#include "rt3_camera.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 #define RT3_FLAG_NEE_SKY 1u
 #define RT3_FLAG_BLUENOISE 2u
@@ -87,6 +89,13 @@ struct GeomTables {
     const FlatGeomDev* geoms;
     const uint32_t *prim_geom, *first_prim;
 };
+
+// blocks of `block` threads that cover n elements: at least one, at most max_blocks (grid-stride beyond that)
+inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks) {
+    uint64_t b = (n + block - 1) / block;
+    if (b < 1) b = 1;
+    return (unsigned)(b > max_blocks ? max_blocks : b);
+}
 
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,

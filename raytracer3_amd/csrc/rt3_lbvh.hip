@@ -22,9 +22,10 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rt3_device.hpp"
-#include "rt3_internal.hpp"
 #include "rt3_bvh_device.hpp"
+#include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 
@@ -97,7 +98,7 @@ __global__ void k_prim_bounds(const float* verts, const uint32_t* indices, const
     }
 }
 
-// shading record of hit_logic.slang:10-27: the three vertex normals (octahedral, 2 x 16 bit: rt3_device.hpp) + the flattened geometry
+// shading record of hit_logic.slang:10-27: the three vertex normals (octahedral, 2 x 16 bit: rt3_math.hpp) + the flattened geometry
 // index, 16 B; the three uv pairs go to their own stream, which only textured geometries read
 __global__ void k_tri_shade(const float* verts, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
                             const uint32_t* first_prim, uint32_t n, uint4* rec, float2* uv) {

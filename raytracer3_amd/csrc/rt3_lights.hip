@@ -12,8 +12,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rt3_bvh_device.hpp"
-#include "rt3_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 
@@ -44,7 +45,7 @@ __global__ void k_emit_prims(const float* __restrict__ verts, const uint32_t* __
         const float* em = geoms[g].g.emission;
         const V3 le = v3(em[0] * 12.0f, em[1] * 12.0f, em[2] * 12.0f);  // hit_finish's radiance, same fp32 products
         float p = area * luminance(le);
-        p = (p > 0.0f && p <= 3.4028234663852886e38f) ? p : 0.0f;  // no power: never sampled
+        p = (p > 0.0f && p <= kFloatMax) ? p : 0.0f;  // no power: never sampled
         rec[4 * (size_t)e] = make_float4(a.x, a.y, a.z, 0.0f);
         rec[4 * (size_t)e + 1] = make_float4(e1.x, e1.y, e1.z, le.x);
         rec[4 * (size_t)e + 2] = make_float4(e2.x, e2.y, e2.z, le.y);

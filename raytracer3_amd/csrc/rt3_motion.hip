@@ -25,8 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include "rt3_bvh_device.hpp"
+#include "rt3_camera.hpp"
 #include "rt3_filter_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 

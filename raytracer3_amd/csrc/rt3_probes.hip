@@ -7,14 +7,18 @@
 // probe; on CDNA4 that is exactly one wavefront, so its groupshared sort (math.slang:140-160) and WaveActiveSum become
 // cross-lane exchanges with no barriers and no LDS round trips.  The shaders are restated as written (debug stores included);
 // oracle/rt3_oracle_probes.c lists the [rule]s chosen where the text leaves a result open.
+#include "rt3_camera.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_rng.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 namespace {
 
 constexpr float kShPi = 3.1415926536f;  // spherical_harmonics.slang:4
 
-// octa_decode (packing.slang:77-86): rt3_device.hpp
+// octa_decode (packing.slang:77-86): rt3_math.hpp
 // spherical_harmonics.slang:30-44 ; sh[r * 3 + c] = result[r][c]
 RT3_DEV void sh3_evaluate(V3 d, float sh[9]) {
     sh[0] = 0.28209479177387814347403972578039f;

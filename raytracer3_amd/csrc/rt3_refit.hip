@@ -14,6 +14,8 @@
 
 #include "rt3_bvh_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 

@@ -13,8 +13,8 @@
 #include <cstdlib>
 #include <utility>
 
-#include "rt3_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
 
 namespace rt3 {
 

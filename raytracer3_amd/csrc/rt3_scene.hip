@@ -274,7 +274,7 @@ int rt3_scene_set_material_textures(rt3_ctx* c, const rt3_material_textures* m, 
     for (uint32_t i = 0; i < n; i++) {
         if (m[i].metallic_roughness_texture < -1 || m[i].normal_texture < -1 || m[i].emissive_texture < -1)
             return fail(c, RT3_E_INVALID, "material textures: entry " + std::to_string(i) + " has a texture index below -1");
-        if (!(std::fabs(m[i].normal_scale) <= 3.4028234663852886e38f)) return fail(c, RT3_E_INVALID, "material textures: normal_scale " + std::to_string(i) + " is not finite");
+        if (!(std::fabs(m[i].normal_scale) <= kFloatMax)) return fail(c, RT3_E_INVALID, "material textures: normal_scale " + std::to_string(i) + " is not finite");
     }
     c->scene.h_mat_tex.clear();
     if (std::any_of(m, m + n, [](const rt3_material_textures& e) { return e.metallic_roughness_texture >= 0 || e.normal_texture >= 0 || e.emissive_texture >= 0; }))
@@ -285,7 +285,7 @@ int rt3_scene_set_material_textures(rt3_ctx* c, const rt3_material_textures* m, 
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
 // arithmetic, in double, in the same order): radiance stored as RGB9E5 (packing.slang:99-162), marginal CDF over rows, one alias
 // table per row with 16-bit keep-thresholds, pdf_uv = the density the quantised tables really realise.
-static uint32_t host_rgb9e5(const float* c) {  // packing.slang:99-144 == rt3_device.hpp float3_to_rgb9e5
+static uint32_t host_rgb9e5(const float* c) {  // packing.slang:99-144 == rt3_math.hpp float3_to_rgb9e5
     auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
     auto from_bits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
     const float mx = (511.0f / 512.0f) * 65536.0f;
@@ -317,7 +317,7 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
     HIPC(c, hipSetDevice(c->device));
     const size_t n = (size_t)w * h;
     for (size_t i = 0; i < 3 * n; i++)  // a NaN or negative texel would poison the sampling tables
-        if (!(rgb[i] >= 0.0f && rgb[i] <= 3.4028234663852886e38f))
+        if (!(rgb[i] >= 0.0f && rgb[i] <= kFloatMax))
             return fail(c, RT3_E_INVALID, "sky texel " + std::to_string(i / 3) + " is negative or not finite (clamp the image before uploading it)");
     std::vector<uint32_t> texq(n), alias(n);
     std::vector<float> pdf(n), marg(h);

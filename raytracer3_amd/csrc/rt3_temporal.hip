@@ -20,8 +20,10 @@
 // case that lost in DESIGN.md section 7's denoise measurements).
 #include <hip/hip_runtime.h>
 
+#include "rt3_camera.hpp"
 #include "rt3_filter_device.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
 
 namespace rt3 {
 

@@ -9,7 +9,6 @@
 // degenerate triangle per instance whose bounds are the instance's world box (its leaves are then re-pointed at the records).
 #include <hip/hip_runtime.h>
 
-#include "rt3_device.hpp"
 #include "rt3_internal.hpp"
 
 namespace rt3 {

@@ -1,20 +1,13 @@
-// rt3_kernels.hip -- gfx950 wavefront path-tracing kernels (hand-written HIP, wave64).
-//
-// Pipeline (replaces shaders/old/{gbuffer,refrence_mode,postprocess}.slang + the driver's ray traversal):
-//   k_raygen -> k_extend -> k_gbuffer                                   ("gbuffer" pass)
-//   k_shade<first> -> [k_shadow] -> k_extend -> k_shade -> ... -> k_accumulate   ("refrence_mode" pass)
-//   k_postprocess                                                        ("postprocess" pass)
-// All queues are structure-of-arrays of 16-byte records (ray = {o, tmin} + {d, tmax}, state = {T, pdf}, hit = {t, u, v, prim};
-// shadow ray = {o, contribution.r} + {d, contribution.g} + 8 bytes {contribution.b, path id}): lane i touches record i of each
-// stream, 1 KiB per wave instruction, the widest coalesced access; live rays are compacted with __ballot / popcount, one
-// 64-bit atomic per workgroup for both output queues.
+// rt3_trace.hip -- the persistent-wave BVH traversal (trace_stream) and its two kernels: k_extend (closest hit) and k_shadow (any hit).
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "rt3_device.hpp"
+#include "rt3_hit.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_math.hpp"
+#include "rt3_surface.hpp"
 
 namespace rt3 {
 
@@ -280,9 +273,8 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 busy = true;
                 // a ray with a non-finite origin or direction (NaN camera, a zero-length shading normal upstream) misses: with NaNs every
                 // slab test of the min/max form passes and the ray would walk the whole tree
-                const float kMaxF = 3.4028234663852886e38f;
-                const bool finite_ray = fabsf(r.o.x) <= kMaxF && fabsf(r.o.y) <= kMaxF && fabsf(r.o.z) <= kMaxF && fabsf(r.d.x) <= kMaxF &&
-                                        fabsf(r.d.y) <= kMaxF && fabsf(r.d.z) <= kMaxF;
+                const bool finite_ray = fabsf(r.o.x) <= kFloatMax && fabsf(r.o.y) <= kFloatMax && fabsf(r.o.z) <= kFloatMax && fabsf(r.d.x) <= kFloatMax &&
+                                        fabsf(r.d.y) <= kFloatMax && fabsf(r.d.z) <= kFloatMax;
                 if (nodes == nullptr || !finite_ray) {  // empty scene: everything misses
                     finish(r.index, r.best, 0u, 0u, 0u, r.pay0, r.pay1, r.pay2, r.pay3);
                     busy = false;
@@ -633,708 +625,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     counts.add_totals(totals, lds_total);
 }
 
-// ------------------------------------------------------------------------------------------------ gbuffer pass
-// gbuffer.slang:8-12 : primary rays for the pixels this rank owns (pixel list is in tile / Z-curve order)
-__global__ void k_raygen(GConstDev g, const uint32_t* __restrict__ pixels, uint32_t npix, float* __restrict__ rays, size_t stride) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i];
-        V3 o, d;
-        primary_ray(g, xy & 0xFFFFu, xy >> 16, o, d);
-        reinterpret_cast<float4*>(rays)[i] = make_float4(o.x, o.y, o.z, 0.0f);                         // TMin, gbuffer_helpers.slang:100
-        reinterpret_cast<float4*>(rays)[stride + i] = make_float4(d.x, d.y, d.z, kBackgroundDepth);    // TMax, :101
-    }
-}
-// gbuffer.slang:15-20
-__global__ void k_gbuffer(SceneDev sc, const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width,
-                          const float* __restrict__ hits, size_t stride, uint4* __restrict__ gbuffer, float* __restrict__ depth) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i];
-        size_t pi = (size_t)(xy >> 16) * width + (xy & 0xFFFFu);
-        const float4 hrec = reinterpret_cast<const float4*>(hits)[i];
-        uint32_t prim = __float_as_uint(hrec.w);
-        if (prim == kMiss) {
-            depth[pi] = kBackgroundDepth;
-        } else {
-            Surface s = hit_info(sc, prim, hrec.y, hrec.z);
-            gbuffer[pi] = gbuffer_pack(s);
-            depth[pi] = hrec.x;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ shading
-// Queue append for a whole workgroup: every wave ballots its lanes, the wave totals meet in LDS and ONE returning
-// atomic per workgroup and queue reserves the range (a single counter word sustains only ~88 returning atomics per
-// microsecond chip-wide, so one atomic per wave made k_shade atomic-bound: 1 M atomics per launch ~ 10 ms).
-// Order is preserved inside the workgroup.  Must be reached by all threads of the block.
-constexpr int kShadeBlock = 512;
-struct BlockAppend {
-    uint32_t ext, sh;
-};
-__device__ __forceinline__ BlockAppend block_append2(bool want_ext, bool want_sh, unsigned long long* pair /* {ext count, shadow count} */,
-                                                     uint32_t* lds /* 2 * (waves + 1) words */) {
-    constexpr int kWaves = kShadeBlock / 64;
-    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    const unsigned long long m_ext = __ballot(want_ext), m_sh = __ballot(want_sh);
-    if (lane == 0) {
-        lds[wave] = (uint32_t)__popcll(m_ext);
-        lds[kWaves + 1 + wave] = (uint32_t)__popcll(m_sh);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t te = 0, ts = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            uint32_t ce = lds[w], cs = lds[kWaves + 1 + w];
-            lds[w] = te;
-            lds[kWaves + 1 + w] = ts;
-            te += ce;
-            ts += cs;
-        }
-        // both queue sizes live in one 8-byte word and move with ONE returning atomic (they used to be two atomics on the same
-        // cache line, i.e. on the same L2 atomic unit: the unit's throughput is what a 256-thread block size ran into)
-        unsigned long long old = 0ull;
-        if (te | ts) old = atomicAdd(pair, (unsigned long long)te | ((unsigned long long)ts << 32));
-        lds[kWaves] = (uint32_t)old;
-        lds[2 * kWaves + 1] = (uint32_t)(old >> 32);
-    }
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    BlockAppend r;
-    r.ext = lds[kWaves] + lds[wave] + (uint32_t)__popcll(m_ext & below);
-    r.sh = lds[2 * kWaves + 1] + lds[kWaves + 1 + wave] + (uint32_t)__popcll(m_sh & below);
-    return r;  // no third barrier: the caller alternates between two lds buffers from one loop iteration to the next
-}
-// block_append2 plus the emitter shadow queue of RT3_F_NEE_EMISSIVE (k_shade<.., .., true> only): the pair moves with its one 64-bit atomic
-// as before, the third count with one 32-bit atomic of its own
-struct BlockAppend3 {
-    uint32_t ext, sh, sh2;
-};
-__device__ __forceinline__ BlockAppend3 block_append3(bool want_ext, bool want_sh, bool want_sh2, unsigned long long* pair, uint32_t* count2,
-                                                      uint32_t* lds /* 3 * (waves + 1) words */) {
-    constexpr int kWaves = kShadeBlock / 64, kW1 = kWaves + 1;
-    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    const unsigned long long m_ext = __ballot(want_ext), m_sh = __ballot(want_sh), m_sh2 = __ballot(want_sh2);
-    if (lane == 0) {
-        lds[wave] = (uint32_t)__popcll(m_ext);
-        lds[kW1 + wave] = (uint32_t)__popcll(m_sh);
-        lds[2 * kW1 + wave] = (uint32_t)__popcll(m_sh2);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t te = 0, ts = 0, t2 = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t ce = lds[w], cs = lds[kW1 + w], c2 = lds[2 * kW1 + w];
-            lds[w] = te;
-            lds[kW1 + w] = ts;
-            lds[2 * kW1 + w] = t2;
-            te += ce;
-            ts += cs;
-            t2 += c2;
-        }
-        unsigned long long old = 0ull;
-        if (te | ts) old = atomicAdd(pair, (unsigned long long)te | ((unsigned long long)ts << 32));
-        lds[kWaves] = (uint32_t)old;
-        lds[kW1 + kWaves] = (uint32_t)(old >> 32);
-        lds[2 * kW1 + kWaves] = t2 ? atomicAdd(count2, t2) : 0u;
-    }
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    BlockAppend3 r;
-    r.ext = lds[kWaves] + lds[wave] + (uint32_t)__popcll(m_ext & below);
-    r.sh = lds[kW1 + kWaves] + lds[kW1 + wave] + (uint32_t)__popcll(m_sh & below);
-    r.sh2 = lds[2 * kW1 + kWaves] + lds[2 * kW1 + wave] + (uint32_t)__popcll(m_sh2 & below);
-    return r;
-}
-// the emitter shadow ray ends this far along its way to the sampled point: the emitter never occludes itself, another one in front does
-constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
-
-// refrence_mode.slang:28-57 for one bounce of every live path
-// GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
-// normal matrix cost an LDS read behind the shading record instead of a second dependent global gather
-// EMIT: next-event estimation to emissive triangles with MIS; launched only with RT3_F_NEE_EMISSIVE and a non-empty table
-// MAT: material textures (hit_finish<true>); launched only when the built scene has the side table (sc.mat_tex), and
-// never for the first vertex, which comes from the G-buffer.  With GLDS the 16-byte side table sits in LDS beside the geometry table, so
-// only the tangent word -- fetched by primitive, beside the shading record -- and the texels themselves are global gathers.
-// Waves per SIMD: 6 (80 VGPRs, 32 bytes of scratch) without MAT: the kernel lives off memory-level parallelism -- 28.8 -> 27.7 ms against
-// the compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks).  MAT holds up to twelve more texels and three footprints' weights
-// across the light sample: the compiler's own allocation is 94 VGPRs (116 with EMIT), above the 80 that 6 waves leave, and a 512-thread
-// block is 2 waves per SIMD, so the next step down from 6 is 4 = 128 VGPRs, which holds both without scratch.
-constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
-template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
-__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
-    static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
-    __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
-    __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
-    __shared__ MatTexDev s_mats[GLDS && MAT ? kShadeGeomsLds : 1];
-    if (GLDS) {
-        const uint32_t ng = a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds;
-        const uint32_t words = ng * (uint32_t)(sizeof(ShadeGeomDev) / 4);
-        for (uint32_t k = threadIdx.x; k < words; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_geoms)[k] = reinterpret_cast<const uint32_t*>(a.sc.shade_geoms)[k];
-        if constexpr (MAT)
-            for (uint32_t k = threadIdx.x; k < ng * 4u; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_mats)[k] = reinterpret_cast<const uint32_t*>(a.sc.mat_tex)[k];
-        __syncthreads();
-    }
-    uint32_t parity = 0;
-    // the marginal sky tables (one guide word + one CDF value per row) are the first two links of every light sample's chain of
-    // dependent lookups: staged in LDS they cost ~100 cycles each instead of an L1/L2 round trip
-    constexpr uint32_t kMargRows = 2048;
-    __shared__ uint32_t s_guide_marg[kMargRows];
-    __shared__ float s_cdf_marg[kMargRows + 4];
-    const bool marg_in_lds = (a.g.pad[0] & RT3_FLAG_NEE_SKY) && a.sc.sky != nullptr && a.sc.sky_h <= kMargRows;
-    if (marg_in_lds) {
-        for (uint32_t k = threadIdx.x; k < a.sc.sky_h; k += kShadeBlock) s_guide_marg[k] = a.sc.guide_marg[k];
-        for (uint32_t k = threadIdx.x; k < a.sc.sky_h + 4u; k += kShadeBlock) s_cdf_marg[k] = a.sc.cdf_marg[k];
-        __syncthreads();
-    }
-    const float* cdf_marg = marg_in_lds ? s_cdf_marg : a.sc.cdf_marg;
-    const uint32_t* guide_marg = marg_in_lds ? s_guide_marg : a.sc.guide_marg;
-    const GConstDev& g = a.g;
-    const uint32_t flags = g.pad[0], B = g.bounces, b = a.bounce;
-    const uint32_t dims = flags ? 8u : 2u;
-    const bool nee = (flags & RT3_FLAG_NEE_SKY) && a.sc.sky != nullptr;
-    const bool bnz = (flags & RT3_FLAG_BLUENOISE) && a.sc.bluenoise != nullptr;
-    const bool spec = (flags & RT3_FLAG_SPECULAR) != 0u;
-    const size_t S = a.stride;
-    const uint32_t n = FIRST ? a.n_first : *a.in_count;
-    const uint32_t n_round = (n + (kShadeBlock - 1)) & ~(uint32_t)(kShadeBlock - 1);  // whole workgroups iterate: barriers inside
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += gridDim.x * blockDim.x) {
-        bool active = i < n;
-        uint32_t pid = 0;
-        V3 o = v3(0, 0, 0), d = v3(0, 0, 1), T = v3(1, 1, 1);
-        float t = 0.0f, pdf_b = 0.0f;
-        Surface surf;
-        surf.albedo = surf.emissive = v3(0, 0, 0);
-        surf.normal = v3(0, 0, 1);
-        surf.roughness = 1.0f;
-        surf.metalness = 0.0f;
-        uint32_t px = 0, py = 0, sample_in_batch = 0, bn = 0;
-        HitRecord hrecord;
-        hrecord.rec = make_uint4(0u, 0u, 0u, 0u);
-        hrecord.prim = 0u;
-        float hbu = 0.0f, hbv = 0.0f;
-        uint32_t htan = 0u;
-        float4 ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-        if (!FIRST && active) {  // ray records {o, pdf} + {d, path id}
-            ro = reinterpret_cast<const float4*>(a.in_rays)[i];
-            rd = reinterpret_cast<const float4*>(a.in_rays)[S + i];
-        }
-        if (active) {
-            pid = FIRST ? i : __float_as_uint(rd.w);
-            sample_in_batch = fast_div(a.npix_div, pid);
-            const uint2 pb = a.pixbn[pid - sample_in_batch * a.npix];  // pixel and its blue-noise word in one load
-            px = pb.x & 0xFFFFu;
-            py = pb.x >> 16;
-            bn = pb.y;
-        }
-        if (FIRST) {
-            if (active) {
-                size_t pi = (size_t)py * a.width + px;
-                float d0 = a.depth[pi];
-                if (d0 == kBackgroundDepth) {  // :18-21
-                    reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                    active = false;
-                } else {
-                    surf = gbuffer_unpack(a.gbuffer[pi]);  // :23
-                    primary_ray(g, px, py, o, d);          // :30
-                    t = d0;                                // :33
-                }
-            }
-        } else if (active) {
-            o = v3(ro.x, ro.y, ro.z);
-            d = v3(rd.x, rd.y, rd.z);
-            T = v3(a.in_T[i], a.in_T[S + i], a.in_T[2 * S + i]);
-            pdf_b = ro.w;
-            const float4 hrec = reinterpret_cast<const float4*>(a.in_hits)[i];
-            uint32_t prim = __float_as_uint(hrec.w);
-            if (prim == kMiss) {  // :37-40 ; sky through MIS (north_star)
-                if (nee && pdf_b > 0.0f) {
-                    float su, sv;
-                    direction_to_equirect_uv(d, su, sv);
-                    float pl;
-                    V3 rad = sky_eval_and_pdf(a.sc, su, sv, pl);
-                    float w = pdf_b / (pdf_b + pl);
-                    float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
-                    float4 lv = *Lp;
-                    *Lp = make_float4(lv.x + T.x * (rad.x * w), lv.y + T.y * (rad.y * w), lv.z + T.z * (rad.z * w), 0.0f);
-                }
-                active = false;
-            } else {
-                t = hrec.x;
-                hbu = hrec.y;
-                hbv = hrec.z;
-                hrecord = hit_fetch(a.sc, prim);  // :55, first half: the loads are issued here, used after the light-sample gathers
-                if constexpr (MAT) htan = tan_fetch(a.sc, prim);
-            }
-        }
-        bool emit_shadow = false, emit_ext = false;
-        V3 wl = v3(0, 1, 0), contrib = v3(0, 0, 0), nd = v3(0, 0, 1), Tn = T;
-        float pdf_n = 0.0f;
-        bool emit_shadow_e = false;  // EMIT: the emitter shadow ray
-        V3 wle = v3(0, 1, 0), contrib_e = v3(0, 0, 0);
-        float tmax_e = 0.0f;
-        if (active) {
-            uint32_t seed = rng_seed(px, py, g.frame);  // :25
-            uint32_t sm = a.s0 + sample_in_batch;
-            uint32_t base = (sm * B + b) * dims;
-            float u0 = uniform_float(seed, base), u1 = uniform_float(seed, base + 1);  // :43
-            if (bnz) {  // bn = bluenoise[(py % bn_h), (px % bn_w)], gathered once per pixel list (k_pixbn)
-                u0 = bluenoise_shift(u0, bn & 0xFFu);
-                u1 = bluenoise_shift(u1, (bn >> 8) & 0xFFu);
-            }
-            // the light sample first: its chain of dependent table gathers (guide -> CDF -> guide -> CDF -> texels) is then in
-            // flight while the shading record arrives and the BSDF is set up and sampled below.  Samples below the horizon
-            // of the surface (cos <= 0) are dropped before the radiance texels are fetched: those two cache lines are the
-            // expensive part of a light sample.
-            V3 rad = v3(0.0f, 0.0f, 0.0f);
-            float pl = 0.0f, cosl = 0.0f;
-            SkyPick pick;
-            pick.u = pick.v = pick.sin_theta = 0.0f;
-            pick.x = pick.y = 0;
-            if (nee) {
-                float ul0 = uniform_float(seed, base + 3), ul1 = uniform_float(seed, base + 4);
-                if (bnz) {
-                    ul0 = bluenoise_shift(ul0, (bn >> 16) & 0xFFu);
-                    ul1 = bluenoise_shift(ul1, (bn >> 24) & 0xFFu);
-                }
-                pick = sky_sample_direction(a.sc, cdf_marg, guide_marg, ul0, ul1, wl);
-            }
-            // EMIT: an emitter and a point on it for vertices 0 .. B-2 (the emission vertex b + 1 would collect); dims 5, 6, 7, no blue-noise
-            // shift.  The chain guide -> CDF -> record is issued here, beside the sky's, and used once the surface is known.
-            const bool nee_e = EMIT && b + 1u < B;
-            float4 er0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), er1 = er0, er2 = er0, er3 = er0;
-            float eu6 = 0.0f, eu7 = 0.0f;
-            if (nee_e) {
-                const uint32_t ke = (uint32_t)(uniform_float(seed, base + 5) * 8388608.0f);  // exact: the 23-bit integer uniform_float was made of
-                eu6 = uniform_float(seed, base + 6);
-                eu7 = uniform_float(seed, base + 7);
-                const float4* R = a.lights.rec + 4 * (size_t)light_find(a.lights, ke);
-                er0 = R[0];
-                er1 = R[1];
-                er2 = R[2];
-                er3 = R[3];
-            }
-            if (!FIRST) {  // :55, second half (two calls, not a selected pointer: a select would turn the LDS reads into flat loads)
-                if constexpr (MAT) {
-                    if (GLDS) surf = hit_finish<true>(a.sc, s_geoms, hrecord, hbu, hbv, s_mats, htan);
-                    else surf = hit_finish<true>(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv, a.sc.mat_tex, htan);
-                } else if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
-                else surf = hit_finish(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv);
-            }
-            V3 N = surf.normal;
-            if ((flags & RT3_FLAG_FACEFORWARD) && dot(N, d) > 0.0f) N = neg(N);
-            if (nee) {
-                cosl = dot(N, wl);
-                if (cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
-            }
-            V3 b1, b2;
-            build_orthonormal_basis(N, b1, b2);  // :44
-            V3 wi = v3(0.0f, 0.0f, 1.0f), vop = surf.albedo, wo = v3(0.0f, 0.0f, 1.0f);
-            float pdf_s = 0.0f;
-            bool valid = true;
-            Bsdf bs;
-            const bool last = b == B - 1;  // the last vertex of a path emits no extension ray (:53): its BSDF sample is never used
-            if (spec) {  // layered diffuse + GGX (brdf.slang:141-311)
-                bs = bsdf_setup(surf.albedo, surf.roughness, surf.metalness);
-                wo = v3(-(d.x * b1.x + d.y * b1.y + d.z * b1.z), -(d.x * b2.x + d.y * b2.y + d.z * b2.z), -(d.x * N.x + d.y * N.y + d.z * N.z));
-                if (!last) {
-                    float u2 = uniform_float(seed, base + 2);
-                    valid = bsdf_sample(bs, wo, u0, u1, u2, wi, vop, pdf_s);
-                }
-            } else if (!last) {
-                wi = diffuse_sample(u0, u1);  // :45
-                pdf_s = wi.z * kInvPi;
-            }
-            o = v3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);  // :47
-            // :50 radiance += ray_color * emissive.  x + (+0) == x exactly, so non-emitters skip the read-modify-write.
-            if (FIRST) {  // L starts at 0 and T = 1: 0 + 1 * e == e
-                reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(T.x * surf.emissive.x, T.y * surf.emissive.y, T.z * surf.emissive.z, 0.0f);
-            } else if (surf.emissive.x != 0.0f || surf.emissive.y != 0.0f || surf.emissive.z != 0.0f) {
-                V3 le = surf.emissive;
-                if (EMIT) {  // a BSDF-sampled ray found an emitter the previous vertex also sampled directly: balance weight pdf_b / (pdf_b + p_solid)
-                    const uint32_t eb = a.lights.geom_base[hrecord.rec.w];
-                    if (eb != kMiss) {
-                        const float4* R = a.lights.rec + 4 * (size_t)(eb + (hrecord.prim - a.sc.first_prim[hrecord.rec.w]));
-                        const float pa = R[0].w;  // p_sel / area, the value the sampler divides by
-                        const float4 rn = R[3];
-                        const float dl = sqrtf(dot(d, d)), cle = fabsf(rn.x * d.x + rn.y * d.y + rn.z * d.z) / dl, dist = t * dl;
-                        if (pa > 0.0f && cle > 0.0f) {
-                            const float ps = pa * (dist * dist) / cle;
-                            le = le * (pdf_b / (pdf_b + ps));
-                        }
-                    }
-                }
-                float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
-                float4 lv = *Lp;
-                *Lp = make_float4(lv.x + T.x * le.x, lv.y + T.y * le.y, lv.z + T.z * le.z, 0.0f);
-            }
-            if (nee_e && er0.w > 0.0f) {  // the emitter sample: p = A + b1 E1 + b2 E2 with b0 = 1 - sqrt(u6), b1 = u7 sqrt(u6)
-                const float su = sqrtf(eu6), lb1 = eu7 * su, lb2 = su - lb1;
-                const V3 pe = v3(er0.x + er1.x * lb1 + er2.x * lb2, er0.y + er1.y * lb1 + er2.y * lb2, er0.z + er1.z * lb1 + er2.z * lb2);
-                const V3 wv = pe - o;
-                const float dist2 = dot(wv, wv), dist = sqrtf(dist2);
-                if (dist2 > 0.0f) {
-                    wle = wv * (1.0f / dist);
-                    const float cs = dot(N, wle), cle = fabsf(er3.x * wle.x + er3.y * wle.y + er3.z * wle.z);  // emission is two-sided
-                    if (cs > 0.0f && cle > 0.0f) {
-                        const float ps = er0.w * dist2 / cle;  // p_sel / area * dist^2 / |cos_l|: solid-angle density of the sample
-                        V3 fv;
-                        float scale;
-                        if (spec) {  // f cos Le / (p_solid + p_bsdf) == f cos Le w / p_solid, balance heuristic
-                            float pproj;
-                            bsdf_eval(bs, wo, v3(dot(wle, b1), dot(wle, b2), cs), fv, pproj);
-                            scale = cs / (ps + pproj * cs);
-                        } else {
-                            fv = surf.albedo;
-                            scale = (cs * kInvPi) / (ps + cs * kInvPi);
-                        }
-                        contrib_e = v3((T.x * fv.x) * (er1.w * scale), (T.y * fv.y) * (er2.w * scale), (T.z * fv.z) * (er3.w * scale));
-                        tmax_e = dist * kEmitShadowEnd;
-                        emit_shadow_e = contrib_e.x > 0.0f || contrib_e.y > 0.0f || contrib_e.z > 0.0f;
-                    }
-                }
-            }
-            if (nee) {
-                if (cosl > 0.0f && pl > 0.0f) {
-                    V3 fv;
-                    float scale;
-                    if (spec) {  // evaluate the layered BSDF towards the light; f cos / (p_light + p_bsdf)
-                        float pproj;
-                        bsdf_eval(bs, wo, v3(dot(wl, b1), dot(wl, b2), cosl), fv, pproj);
-                        float pb = pproj * cosl;
-                        scale = (b == B - 1) ? cosl / pl : cosl / (pl + pb);
-                    } else {  // diffuse: f = albedo / pi folded into the scale
-                        float pb = cosl * kInvPi;
-                        fv = surf.albedo;
-                        scale = (b == B - 1) ? (cosl * kInvPi) / pl : (cosl * kInvPi) / (pl + pb);
-                    }
-                    contrib = v3((T.x * fv.x) * (rad.x * scale), (T.y * fv.y) * (rad.y * scale), (T.z * fv.z) * (rad.z * scale));
-                    emit_shadow = true;
-                }
-            }
-            if (valid && !last) {  // an invalid specular sample (brdf.slang:227-229) ends the path
-                nd = basis_apply(b1, b2, N, wi);  // :48
-                pdf_n = pdf_s;
-                Tn = T * vop;                     // :51 value_over_pdf (= albedo for the diffuse BRDF)
-                emit_ext = true;                  // :53
-            }
-        }
-        BlockAppend slot;
-        uint32_t slot_e = 0;
-        if (EMIT) {
-            const BlockAppend3 s3 = block_append3(emit_ext, emit_shadow, emit_shadow_e, reinterpret_cast<unsigned long long*>(a.out_count), a.sh2_count, append_lds[parity]);
-            slot.ext = s3.ext;
-            slot.sh = s3.sh;
-            slot_e = s3.sh2;
-        } else {
-            slot = block_append2(emit_ext, emit_shadow, reinterpret_cast<unsigned long long*>(a.out_count), append_lds[parity]);  // out_count, sh_count: one pair
-        }
-        parity ^= 1u;
-        if (EMIT && emit_shadow_e) {  // 44 bytes: the 40-byte shadow record plus the ray's own range end
-            reinterpret_cast<float4*>(a.sh2_rays)[slot_e] = make_float4(o.x, o.y, o.z, contrib_e.x);
-            reinterpret_cast<float4*>(a.sh2_rays)[S + slot_e] = make_float4(wle.x, wle.y, wle.z, contrib_e.y);
-            reinterpret_cast<float2*>(a.sh2_contrib)[slot_e] = make_float2(contrib_e.z, __uint_as_float(pid));
-            a.sh2_tmax[slot_e] = tmax_e;
-        }
-        if (emit_shadow) {
-            const uint32_t j = slot.sh;
-            // 40 bytes per shadow ray: its range is always (kRayTMin, kBackgroundDepth), so the .w of the two ray records carry the
-            // red and green contribution; blue and the path id follow in an 8-byte record
-            reinterpret_cast<float4*>(a.sh_rays)[j] = make_float4(o.x, o.y, o.z, contrib.x);
-            reinterpret_cast<float4*>(a.sh_rays)[S + j] = make_float4(wl.x, wl.y, wl.z, contrib.y);
-            reinterpret_cast<float2*>(a.sh_contrib)[j] = make_float2(contrib.z, __uint_as_float(pid));
-        }
-        if (emit_ext) {
-            const uint32_t j = slot.ext;
-            // 44 bytes per extension ray: its range is always (kRayTMin, kBackgroundDepth) (:31), so the .w of its two ray records carry
-            // the path's pdf and id; the throughput follows as three 4-byte planes (queue slots are contiguous per workgroup: coalesced)
-            reinterpret_cast<float4*>(a.out_rays)[j] = make_float4(o.x, o.y, o.z, pdf_n);
-            reinterpret_cast<float4*>(a.out_rays)[S + j] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(pid));
-            a.out_T[j] = Tn.x;
-            a.out_T[S + j] = Tn.y;
-            a.out_T[2 * S + j] = Tn.z;
-        }
-    }
-}
-
-// refrence_mode.slang:59-65 : radiance = (sum over samples, in sample order) / S, then blend with PrevLight
-__global__ void k_accumulate(GConstDev g, const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width,
-                             const float* __restrict__ depth, const float* __restrict__ lacc, size_t stride, uint32_t sb,
-                             int first_batch, int last_batch, float* __restrict__ radsum, float4* __restrict__ light,
-                             const float4* __restrict__ prev) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i];
-        size_t pi = (size_t)(xy >> 16) * width + (xy & 0xFFFFu);
-        if (depth[pi] == kBackgroundDepth) continue;
-        float r = first_batch ? 0.0f : radsum[i], gg = first_batch ? 0.0f : radsum[npix + i], bb = first_batch ? 0.0f : radsum[2 * (size_t)npix + i];
-        for (uint32_t s = 0; s < sb; s++) {
-            size_t p = (size_t)s * npix + i;
-            const float4 lv = reinterpret_cast<const float4*>(lacc)[p];
-            r += lv.x;
-            gg += lv.y;
-            bb += lv.z;
-        }
-        if (!last_batch) {
-            radsum[i] = r;
-            radsum[npix + i] = gg;
-            radsum[2 * (size_t)npix + i] = bb;
-        } else {
-            float fs = (float)g.samples;
-            r = r / fs;
-            gg = gg / fs;
-            bb = bb / fs;
-            if (g.blendfactor >= 1.0f) {
-                light[pi] = make_float4(r, gg, bb, 0.0f);
-            } else {
-                float4 pv = prev[pi];
-                float bf = g.blendfactor;
-                light[pi] = make_float4(pv.x + (r - pv.x) * bf, pv.y + (gg - pv.y) * bf, pv.z + (bb - pv.z) * bf, 0.0f);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ postprocess
-// postprocess.slang:13-25
-__device__ __forceinline__ float agx_contrast(float x) {
-    float x2 = x * x, x4 = x2 * x2;
-    return 15.5f * x4 * x2 - 40.14f * x4 * x + 31.96f * x4 - 6.868f * x2 * x + 0.4298f * x2 + 0.1191f * x - 0.00232f;
-}
-// postprocess.slang:27-88 (AGX_LOOK 2; pow base clamped at 0)
-__device__ __forceinline__ V3 agx_tonemap(V3 c) {
-    const float m[9] = {0.842479062253094f, 0.0423282422610123f, 0.0423756549057051f, 0.0784335999999992f, 0.878468636469772f,
-                        0.0784336f, 0.0792237451477643f, 0.0791661274605434f, 0.879142973793104f};
-    const float mi[9] = {1.19687900512017f, -0.0528968517574562f, -0.0529716355144438f, -0.0980208811401368f, 1.15190312990417f,
-                         -0.0980434501171241f, -0.0990297440797205f, -0.0989611768448433f, 1.15107367264116f};
-    const float min_ev = -12.47393f, max_ev = 4.026069f;
-    float v[3], w[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) v[j] = c.x * m[j] + c.y * m[3 + j] + c.z * m[6 + j];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        float l = v[j] > 0.0f ? log2f(v[j]) : min_ev;
-        l = fmin_sel(fmax_sel(l, min_ev), max_ev);
-        l = (l - min_ev) / (max_ev - min_ev);
-        v[j] = agx_contrast(l);
-    }
-    float luma = v[0] * 0.2126f + v[1] * 0.7152f + v[2] * 0.0722f;
-#pragma unroll
-    for (int j = 0; j < 3; j++) w[j] = luma + 1.1f * (powf(fmax_sel(v[j], 0.0f), 1.1f) - luma);
-    return v3(w[0] * mi[0] + w[1] * mi[3] + w[2] * mi[6], w[0] * mi[1] + w[1] * mi[4] + w[2] * mi[7], w[0] * mi[2] + w[1] * mi[5] + w[2] * mi[8]);
-}
-// postprocess.slang:90-112
-__global__ void k_postprocess(GConstDev g, SceneDev sc, const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width,
-                              const float* __restrict__ depth, const float4* __restrict__ in, float4* __restrict__ out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i], px = xy & 0xFFFFu, py = xy >> 16;
-        size_t pi = (size_t)py * width + px;
-        V3 col;
-        if (depth[pi] != kBackgroundDepth) {
-            float4 c = in[pi];
-            col = v3(c.x, c.y, c.z);
-        } else {
-            V3 o, d;
-            primary_ray(g, px, py, o, d);
-            float su, sv;
-            direction_to_equirect_uv(d, su, sv);
-            col = sky_eval(sc, su, sv);
-        }
-        V3 r = agx_tonemap(col);
-        out[pi] = make_float4(r.x, r.y, r.z, 1.0f);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ tiles
-__global__ void k_pack_tiles(const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width, const float4* __restrict__ img,
-                             float4* __restrict__ dst) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i];
-        dst[i] = img[(size_t)(xy >> 16) * width + (xy & 0xFFFFu)];
-    }
-}
-__global__ void k_unpack_tiles(const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width, const float4* __restrict__ src,
-                               float4* __restrict__ img) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        uint32_t xy = pixels[i];
-        img[(size_t)(xy >> 16) * width + (xy & 0xFFFFu)] = src[i];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ self-test
-// Evaluates one device function per element so that tests can pin the device arithmetic against known answers
-// (rt3_selftest_eval).  in / out are dense arrays of `in_w` / `out_w` 32-bit words per element.
-// Ops 25 and 26 read the context's sky through `sc` (rt3_selftest_eval refuses them without one); op 29 reads the flattened world's
-// shading tables (refused without a current acceleration structure, and for a primitive the world does not have).
-__global__ void k_selftest(int op, const SceneDev sc, const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    auto F = [](uint32_t u) { return __uint_as_float(u); };
-    auto U = [](float f) { return __float_as_uint(f); };
-    switch (op) {
-        case 0: out[i] = jenkins_hash(in[i]); break;
-        case 1: out[i] = zcurve(in[2 * i], in[2 * i + 1]); break;
-        case 2: out[i] = murmur3(in[2 * i], in[2 * i + 1]); break;
-        case 3: out[i] = U(uniform_float(in[2 * i], in[2 * i + 1])); break;
-        case 4: {
-            const uint32_t* p = in + 11 * i;
-            Surface s;
-            s.albedo = v3(F(p[0]), F(p[1]), F(p[2]));
-            s.emissive = v3(F(p[3]), F(p[4]), F(p[5]));
-            s.normal = v3(F(p[6]), F(p[7]), F(p[8]));
-            s.roughness = F(p[9]);
-            s.metalness = F(p[10]);
-            uint4 q = gbuffer_pack(s);
-            out[4 * i] = q.x; out[4 * i + 1] = q.y; out[4 * i + 2] = q.z; out[4 * i + 3] = q.w;
-            break;
-        }
-        case 5: {
-            Surface s = gbuffer_unpack(make_uint4(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]));
-            uint32_t* o = out + 11 * i;
-            o[0] = U(s.albedo.x); o[1] = U(s.albedo.y); o[2] = U(s.albedo.z);
-            o[3] = U(s.emissive.x); o[4] = U(s.emissive.y); o[5] = U(s.emissive.z);
-            o[6] = U(s.normal.x); o[7] = U(s.normal.y); o[8] = U(s.normal.z);
-            o[9] = U(s.roughness); o[10] = U(s.metalness);
-            break;
-        }
-        case 6: {
-            V3 w = diffuse_sample(F(in[2 * i]), F(in[2 * i + 1]));
-            out[3 * i] = U(w.x); out[3 * i + 1] = U(w.y); out[3 * i + 2] = U(w.z);
-            break;
-        }
-        case 7: {
-            V3 b1, b2;
-            build_orthonormal_basis(v3(F(in[3 * i]), F(in[3 * i + 1]), F(in[3 * i + 2])), b1, b2);
-            uint32_t* o = out + 6 * i;
-            o[0] = U(b1.x); o[1] = U(b1.y); o[2] = U(b1.z); o[3] = U(b2.x); o[4] = U(b2.y); o[5] = U(b2.z);
-            break;
-        }
-        case 8: {
-            V3 r = agx_tonemap(v3(F(in[3 * i]), F(in[3 * i + 1]), F(in[3 * i + 2])));
-            out[3 * i] = U(r.x); out[3 * i + 1] = U(r.y); out[3 * i + 2] = U(r.z);
-            break;
-        }
-        case 9: {
-            float sn, cs;
-            sincos_2pi(F(in[i]), sn, cs);
-            out[2 * i] = U(sn); out[2 * i + 1] = U(cs);
-            break;
-        }
-        case 10: out[i] = U(atan2_poly(F(in[2 * i]), F(in[2 * i + 1]))); break;
-        case 11: out[i] = rng_seed(in[3 * i], in[3 * i + 1], in[3 * i + 2]); break;
-        case 12: {  // the division-free n / d and wrap used by k_shade: {n / d, n % d, wrap_index((int)n, (int)d)}
-            const uint32_t nn = in[2 * i], dd = in[2 * i + 1];
-            const FastDiv f = make_fastdiv(dd);
-            const uint32_t q = fast_div(f, nn);
-            out[3 * i] = q;
-            out[3 * i + 1] = nn - q * dd;
-            out[3 * i + 2] = (uint32_t)wrap_index((int)nn, (int)(dd & 0xFFFFu) + 1);
-            break;
-        }
-        case 17: out[i] = octa_encode16(v3(F(in[3 * i]), F(in[3 * i + 1]), F(in[3 * i + 2]))); break;  // shading-record normals
-        case 18: {
-            const V3 n = octa_decode16(in[i]);
-            out[3 * i] = U(n.x);
-            out[3 * i + 1] = U(n.y);
-            out[3 * i + 2] = U(n.z);
-            break;
-        }
-        case 19:    // layered BSDF: {albedo, roughness, metalness, wo, wi} -> {value, pdf_proj}
-        case 20: {  // {albedo, roughness, metalness, wo, u0, u1, u2} -> {valid, wi, value / pdf, pdf_solid}
-            const uint32_t* p = in + 11 * i;
-            const Bsdf b = bsdf_setup(v3(F(p[0]), F(p[1]), F(p[2])), F(p[3]), F(p[4]));
-            const V3 wo = v3(F(p[5]), F(p[6]), F(p[7]));
-            if (op == 19) {
-                V3 value;
-                float pdf;
-                bsdf_eval(b, wo, v3(F(p[8]), F(p[9]), F(p[10])), value, pdf);
-                uint32_t* o = out + 4 * i;
-                o[0] = U(value.x); o[1] = U(value.y); o[2] = U(value.z); o[3] = U(pdf);
-            } else {
-                V3 wi = v3(0.0f, 0.0f, 0.0f), vop = v3(0.0f, 0.0f, 0.0f);
-                float pdf = 0.0f;
-                const bool ok = bsdf_sample(b, wo, F(p[8]), F(p[9]), F(p[10]), wi, vop, pdf);
-                if (!ok) wi = v3(0.0f, 0.0f, 0.0f);
-                uint32_t* o = out + 8 * i;
-                o[0] = ok ? 1u : 0u;
-                o[1] = U(wi.x); o[2] = U(wi.y); o[3] = U(wi.z); o[4] = U(vop.x); o[5] = U(vop.y); o[6] = U(vop.z); o[7] = U(pdf);
-            }
-            break;
-        }
-        case 21: {  // {alpha, wo, u0, u1} -> half vector
-            const uint32_t* p = in + 6 * i;
-            const V3 h = sample_vndf(F(p[0]), v3(F(p[1]), F(p[2]), F(p[3])), F(p[4]), F(p[5]));
-            out[3 * i] = U(h.x); out[3 * i + 1] = U(h.y); out[3 * i + 2] = U(h.z);
-            break;
-        }
-        case 22: {
-            float u, v;
-            direction_to_equirect_uv(v3(F(in[3 * i]), F(in[3 * i + 1]), F(in[3 * i + 2])), u, v);
-            out[2 * i] = U(u); out[2 * i + 1] = U(v);
-            break;
-        }
-        case 23: out[i] = float3_to_rgb9e5(v3(F(in[3 * i]), F(in[3 * i + 1]), F(in[3 * i + 2]))); break;  // G-buffer emissive
-        case 24: {
-            const V3 c = rgb9e5_to_float3(in[i]);
-            out[3 * i] = U(c.x); out[3 * i + 1] = U(c.y); out[3 * i + 2] = U(c.z);
-            break;
-        }
-        case 25: {  // sky light sample: {u0, u1} -> {dir, radiance, pdf, texel x, texel y}
-            V3 dir, rad;
-            float pdf;
-            const SkyPick pk = sky_sample_direction(sc, sc.cdf_marg, sc.guide_marg, F(in[2 * i]), F(in[2 * i + 1]), dir);
-            sky_sample_radiance(sc, pk, rad, pdf);
-            uint32_t* o = out + 9 * i;
-            o[0] = U(dir.x); o[1] = U(dir.y); o[2] = U(dir.z); o[3] = U(rad.x); o[4] = U(rad.y); o[5] = U(rad.z); o[6] = U(pdf);
-            o[7] = (uint32_t)pk.x; o[8] = (uint32_t)pk.y;
-            break;
-        }
-        case 26: {  // escaped path: {u, v} -> {radiance, pdf}
-            float pdf;
-            const V3 rad = sky_eval_and_pdf(sc, F(in[2 * i]), F(in[2 * i + 1]), pdf);
-            out[4 * i] = U(rad.x); out[4 * i + 1] = U(rad.y); out[4 * i + 2] = U(rad.z); out[4 * i + 3] = U(pdf);
-            break;
-        }
-        case 27:  // alpha mask: {texture index (int32), u, v} -> tex_alpha, the traversal's function
-            out[i] = U(tex_alpha(sc.tex_table, sc.tex_pixels, sc.n_tex, (int32_t)in[3 * i], F(in[3 * i + 1]), F(in[3 * i + 2])));
-            break;
-        case 29: {  // surface stage: {prim, bu, bv} -> Surface in op 5's order (rt3_selftest_eval checks prim against the flattened world)
-            const Surface s = hit_info(sc, in[3 * i], F(in[3 * i + 1]), F(in[3 * i + 2]));
-            uint32_t* o = out + 11 * i;
-            o[0] = U(s.albedo.x); o[1] = U(s.albedo.y); o[2] = U(s.albedo.z);
-            o[3] = U(s.emissive.x); o[4] = U(s.emissive.y); o[5] = U(s.emissive.z);
-            o[6] = U(s.normal.x); o[7] = U(s.normal.y); o[8] = U(s.normal.z);
-            o[9] = U(s.roughness); o[10] = U(s.metalness);
-            break;
-        }
-        default: break;
-    }
-}
-bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
-    static const uint32_t w[30][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
-                                      {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
-                                      {2, 9}, {2, 4}, {3, 1}, {1, 1}, {3, 11}};
-    if (op < 0 || op > 29) return false;
-    *in_w = w[op][0];
-    *out_w = w[op][1];
-    return true;
-}
-void launch_selftest(hipStream_t st, int op, const SceneDev& sc, const uint32_t* in, uint32_t n, uint32_t* out) {
-    if (op >= 13 && op <= 16) return launch_selftest_probes(st, op, in, n, out);
-    if (op == 28) return launch_selftest_denoise(st, in, n, out);
-    hipLaunchKernelGGL(k_selftest, dim3((n + 255) / 256), dim3(256), 0, st, op, sc, in, n, out);
-}
-
 // ------------------------------------------------------------------------------------------------ launchers
-static inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks) {
-    uint64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    return (unsigned)(b > max_blocks ? max_blocks : b);
-}
-
-void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride) {
-    hipLaunchKernelGGL(k_raygen, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, g, pixels, npix, rays, stride);
-}
 // The k_extend / k_shadow instance of (count, layout, mask): `launch` is called with std::integral_constant<bool, COUNT>,
 // std::integral_constant<int, LAYOUT> and std::integral_constant<bool, MASK>.  A layout that is none of the named ones runs as kLayoutBinary64.
 // MASK instances exist for the default layout and the two-level one only (rt3_accel_build refuses masks with the others).
@@ -1382,59 +673,6 @@ void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) 
         if (L.tmax) launch(std::true_type{});
         else launch(std::false_type{});
     });
-}
-void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
-                    size_t stride, void* gbuffer, float* depth) {
-    hipLaunchKernelGGL(k_gbuffer, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, sc, pixels, npix, width, hits, stride, (uint4*)gbuffer, depth);
-}
-__global__ void k_pixbn(const uint32_t* __restrict__ pixels, uint32_t npix, const uint8_t* __restrict__ bluenoise, uint32_t bn_w, uint32_t bn_h,
-                        uint2* __restrict__ out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        const uint32_t xy = pixels[i], px = xy & 0xFFFFu, py = xy >> 16;
-        uint32_t bn = 0;
-        if (bluenoise) bn = *reinterpret_cast<const uint32_t*>(bluenoise + 4 * ((size_t)(py % bn_h) * bn_w + (px % bn_w)));
-        out[i] = make_uint2(xy, bn);
-    }
-}
-void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out) {
-    hipLaunchKernelGGL(k_pixbn, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, st, pixels, npix, bluenoise, bn_w, bn_h, out);
-}
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a) {
-    a.npix_div = make_fastdiv(a.npix);
-    unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
-    const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
-    if (!first && a.sc.mat_tex != nullptr) {  // the built scene has material textures: the MAT instances, GLDS x EMIT
-        const bool emit = a.lights.n != 0u;
-        if (glds && emit) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        else if (glds) hipLaunchKernelGGL((k_shade<false, true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        else if (emit) hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        else hipLaunchKernelGGL((k_shade<false, false, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        return;
-    }
-    if (a.lights.n != 0u) {  // RT3_F_NEE_EMISSIVE with something to sample
-        if (first) hipLaunchKernelGGL((k_shade<true, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        else if (glds) hipLaunchKernelGGL((k_shade<false, true, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-        else hipLaunchKernelGGL((k_shade<false, false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-    } else if (first) hipLaunchKernelGGL((k_shade<true, false>), dim3(grid), dim3(kShadeBlock), 0, st, a);  // the first vertex comes from the G-buffer
-    else if (glds) hipLaunchKernelGGL((k_shade<false, true>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-    else hipLaunchKernelGGL((k_shade<false, false>), dim3(grid), dim3(kShadeBlock), 0, st, a);
-}
-void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
-                       const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,
-                       const void* prev) {
-    hipLaunchKernelGGL(k_accumulate, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, g, pixels, npix, width, depth, lacc, stride, sb,
-                       first_batch, last_batch, radsum, (float4*)light, (const float4*)prev);
-}
-void launch_postprocess(hipStream_t st, const GConstDev& g, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width,
-                        const float* depth, const void* in, void* out) {
-    hipLaunchKernelGGL(k_postprocess, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, g, sc, pixels, npix, width, depth, (const float4*)in,
-                       (float4*)out);
-}
-void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst) {
-    hipLaunchKernelGGL(k_pack_tiles, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, pixels, npix, width, (const float4*)img, (float4*)dst);
-}
-void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img) {
-    hipLaunchKernelGGL(k_unpack_tiles, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, pixels, npix, width, (const float4*)src, (float4*)img);
 }
 
 }  // namespace rt3

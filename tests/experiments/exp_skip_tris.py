@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What would the walk cost if the triangle tests were somebody else's work?  (round 3: the premise check that stopped a "decoupled triangle
 queue" redesign before it was written.)  The bounce-1 batch of the bench frame, tiled to 46 M rays, through rt3_trace_rays; run once with the
-product's librt3.so and once with a throw-away build of rt3_kernels.hip compiled with -DRT3_EXP_SKIP_TRIS (a leaf is fetched and popped, no
+product's librt3.so and once with a throw-away build of rt3_trace.hip compiled with -DRT3_EXP_SKIP_TRIS (a leaf is fetched and popped, no
 triangle is tested: 39 % fewer vector instructions in an iteration that visits a leaf lane).  Result on the box: 6.02 ps per lane-iteration
 with the tests, 5.17 without -- the iteration is a dependent fetch first and ~235 vector instructions second (elasticity 0.36), so taking the
 tests out of the loop and running them in iterations of their own (3.5 more wave-iterations per 64 rays against 19.8 / 0.9 = 22 now) cannot pay.

@@ -68,7 +68,7 @@ def object_points(mesh, flat, prim, u, v):
 
 
 def transform_point(m, p):
-    """glam's transform_point3 as rt3_device.hpp writes it: w_axis + (z_axis z + (y_axis y + x_axis x)); m (n, 4, 4) row-major, p (n, 3)"""
+    """glam's transform_point3 as rt3_surface.hpp writes it: w_axis + (z_axis z + (y_axis y + x_axis x)); m (n, 4, 4) row-major, p (n, 3)"""
     x, y, z = p[:, 0:1], p[:, 1:2], p[:, 2:3]
     return m[:, :3, 3] + (m[:, :3, 2] * z + (m[:, :3, 1] * y + m[:, :3, 0] * x))
 

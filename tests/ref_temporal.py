@@ -5,7 +5,7 @@ ray are the oracle's (ref_denoise.unpack_gbuffer, orc.primary_rays -- the latter
 surface record (P, n, c, m, e) is ref_denoise.prepare(), the one the "denoise" pass uses.
 
 Association order, chosen here and followed by the device: a matrix row times a vector is summed left to right,
-((m0 x + m4 y) + m8 z) + m12 w, like primary_ray in rt3_device.hpp; the four taps are accumulated rows outer (j), columns inner (i); a
+((m0 x + m4 y) + m8 z) + m12 w, like primary_ray in rt3_camera.hpp; the four taps are accumulated rows outer (j), columns inner (i); a
 tap's bilinear weight is w_x * w_y.  A tap that does not count is skipped by the device; here it adds +0, which leaves every bit of a sum
 that started at +0 alone.  `floor` and the float -> int conversion are exact, and are applied only after the window test in float.
 """

@@ -1,5 +1,5 @@
 """Alpha-masked cutout geometry (glTF alphaMode MASK) without a GPU: the glTF round trip of alphaMode / alphaCutoff /
-baseColorFactor[3], the C++ loader against the Python one, and the numpy fp32 restatement of the device's tex_alpha (rt3_device.hpp) that
+baseColorFactor[3], the C++ loader against the Python one, and the numpy fp32 restatement of the device's tex_alpha (rt3_surface.hpp) that
 the GPU tests pin bit for bit, checked here against float64."""
 import json
 import struct
@@ -20,7 +20,7 @@ F = np.float32
 
 # ------------------------------------------------------------------------------------------------ restatements of the device functions
 def tex_alpha_f32(tex, u, v):
-    """tex_alpha (rt3_device.hpp) in fp32: texture_sample's texel coordinates, weights and association on byte * (1 / 255); tex (h, w, 4)
+    """tex_alpha (rt3_surface.hpp) in fp32: texture_sample's texel coordinates, weights and association on byte * (1 / 255); tex (h, w, 4)
     uint8 or None (no texture: 1)"""
     u, v = np.asarray(u, F), np.asarray(v, F)
     if tex is None:

@@ -6,7 +6,7 @@ one frame (RT3_OPT_PROFILE) for five versions of the same scene:
   normal    a normal map on every geometry (tangent records, the dependent gather)
   emissive  an emissive map on every geometry (a few geometries emit; the others multiply zero)
   all       the three maps on every geometry
-The maps are 256 x 256 textures generated from a seed; uvs are the scene's own.  With --resources the tool also compiles rt3_kernels.hip
+The maps are 256 x 256 textures generated from a seed; uvs are the scene's own.  With --resources the tool also compiles rt3_shade.hip
 with -Rpass-analysis=kernel-resource-usage (the library's own flags) and reports VGPRs, scratch and occupancy of every k_shade instance.
 Prints one JSON line (medians of --frames timed frames after --warmup).
 
@@ -32,7 +32,7 @@ def shade_resources():
     """{k_shade<...>: {vgprs, scratch_bytes, waves_per_simd, lds_bytes}} from the compiler's resource remarks"""
     csrc = ROOT / "raytracer3_amd" / "csrc"
     flags = re.search(r"^FLAGS = (.*)$", (csrc / "Makefile").read_text(), re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", "rt3_kernels.hip", "-o", "/dev/null"],
+    r = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", "rt3_shade.hip", "-o", "/dev/null"],
                        cwd=csrc, capture_output=True, text=True, check=True)
     out, cur = {}, None
     for line in r.stderr.splitlines():
