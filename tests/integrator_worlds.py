@@ -1,0 +1,112 @@
+"""Scenes of the integrator tests (tests/test_integrator_cpu.py, tests/test_integrator.py, tests/golden/gen_integrator_ref.py).
+
+furnace(scale): a closed diffuse room in which every surface has the same albedo and the same emission, so the radiance of every path
+has a closed form.  open_room(): a small lit scene under a sky for the comparison with the float64 reference tracer."""
+import math
+
+import numpy as np
+
+from raytracer3_amd import scenes
+from raytracer3_amd.assets import Material, MeshBuilder
+
+WINDOW_FURNACE = (64, 48)
+WINDOW_ROOM = (48, 32)
+
+# ---------------------------------------------------------------------------------------------------------------- furnace
+FURNACE_ALBEDO = (0.5, 0.25, 0.75)
+FURNACE_EMISSION = (0.25, 0.125, 0.5)  # x 12 in hit_info: E = (3, 1.5, 6)
+FURNACE_MATERIAL = Material(FURNACE_ALBEDO, 0.0, 1.0, emission=FURNACE_EMISSION)
+BLOCK_LO, BLOCK_HI = (-0.3, -1.0, -0.2), (0.1, -0.2, 0.3)  # in units of the room's half size
+
+
+def furnace_camera(scale):
+    return dict(position=tuple(scale * c for c in (0.1, 0.2, 0.9)), direction=(0.05, -0.3, -1.0), fov_deg=70.0)
+
+
+def translate(x, y, z):
+    m = np.eye(4)
+    m[:3, 3] = (x, y, z)
+    return m
+
+
+def rot_y(deg):
+    c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+    m = np.eye(4)
+    m[0, 0], m[0, 2], m[2, 0], m[2, 2] = c, s, -s, c
+    return m
+
+
+def furnace(scale, instanced=False):
+    """(mesh, instances or None, camera): the room [-scale, scale]^3 with inward normals and one block with outward normals.  With
+    `instanced` the block is a geometry placed twice by instance matrices, once where it stands and once rotated, both inside the room
+    and apart from each other."""
+    s = float(scale)
+    mb = MeshBuilder()
+    scenes._box(mb, "room", [-s] * 3, [s] * 3, FURNACE_MATERIAL, inward=True)
+    scenes._box(mb, "block", [s * c for c in BLOCK_LO], [s * c for c in BLOCK_HI], FURNACE_MATERIAL)
+    inst = None
+    if instanced:
+        inst = [(0, 1, np.eye(4)), (1, 1, np.eye(4)), (1, 1, translate(0.7 * s, 0.3 * s, -0.5 * s) @ rot_y(30.0))]
+    return mb.build(), inst, furnace_camera(s)
+
+
+# ---------------------------------------------------------------------------------------------------------------- open room
+ROOM_CAMERA = dict(position=(2.5, 2.0, 3.5), direction=(-0.45, -0.3, -1.0), fov_deg=60.0)
+ROOM_ALBEDO = {"floor": (0.7, 0.6, 0.5), "back": (0.3, 0.6, 0.8), "left": (0.8, 0.3, 0.25), "panel": (0.5, 0.5, 0.5), "block": (0.6, 0.7, 0.3)}
+ROOM_PANEL_EMISSION = (0.5, 0.45, 0.35)
+ROOM_PANEL_CENTRE = (0.0, 0.0)  # x, z
+ROOM_CORNER = (-4.0, -4.0)  # x, z of the corner where the floor and the two walls meet
+# (roughness, metalness) of the specular material set: nothing below roughness 0.3 (the VNDF frame band of DESIGN.md section 2)
+ROOM_SPECULAR = {"floor": (0.5, 0.0), "back": (0.6, 0.5), "left": (0.3, 1.0), "panel": (1.0, 0.0), "block": (0.3, 0.5)}
+
+
+def _rotated_box(mb, name, lo, hi, deg, mat):
+    """an axis-aligned box without its bottom face, turned about the vertical axis through its centre"""
+    tmp = MeshBuilder()
+    scenes._box(tmp, name, lo, hi, mat)
+    v, tris = tmp.v[0].astype(np.float64), tmp.i[0].reshape(-1, 3)
+    tris = tris[np.abs(v[tris[:, 0], 4] + 1.0) > 0.5]  # drop the face whose normal is -y
+    r = rot_y(deg)[:3, :3]
+    c = 0.5 * (np.asarray(lo, np.float64) + np.asarray(hi, np.float64))
+    mb.add(name, (v[:, :3] - c) @ r.T + c, v[:, 3:6] @ r.T, None, tris, mat)
+
+
+def open_room(specular=False):
+    """floor 8 x 8 at y = 0, a back wall (z = -4) and a left wall (x = -4) 4 high, an emissive 3 x 3 panel at y = 3.5 facing down, a
+    block on the floor turned by 30 degrees: 18 triangles.  `specular` picks the second material set."""
+    def mat(name, emission=(0.0, 0.0, 0.0)):
+        rough, metal = ROOM_SPECULAR[name] if specular else (1.0, 0.0)
+        return Material(ROOM_ALBEDO[name], metal, rough, emission=emission)
+    mb = MeshBuilder()
+    x0, z0 = ROOM_CORNER
+    mb.add("floor", *scenes._grid([x0, 0, z0], [0, 0, 8], [8, 0, 0], 1, 1), mat("floor"))
+    mb.add("back", *scenes._grid([x0, 0, z0], [8, 0, 0], [0, 4, 0], 1, 1), mat("back"))
+    mb.add("left", *scenes._grid([x0, 0, z0 + 8], [0, 0, -8], [0, 4, 0], 1, 1), mat("left"))
+    mb.add("panel", *scenes._grid([ROOM_PANEL_CENTRE[0] - 1.5, 3.5, ROOM_PANEL_CENTRE[1] - 1.5], [3, 0, 0], [0, 0, 3], 1, 1), mat("panel", ROOM_PANEL_EMISSION))
+    _rotated_box(mb, "block", (-1.6, 0.0, -1.8), (-0.4, 1.2, -0.6), 30.0, mat("block"))
+    return mb.build()
+
+
+F_NEE_SKY, F_SPECULAR, F_FACEFORWARD = 1, 4, 8  # RT3_F_* of include/rt3.h
+FRAME_SPP = 2048  # samples per pixel of one frame of the code under test
+# The cases of tests/golden/integrator_ref.npz: name -> (flags, bounces, specular material set, reference samples per pixel, seed, frames
+# of the code under test).  The two sample counts of a case are tied by the two conditions of the comparison: the
+# fixture's relative standard error must be small enough to see 2 % in 90 % of the block-channels, and the code under test must have at
+# most half the fixture's standard error in every block-channel.  8 frames do that where the kernels' light sampling beats the reference's
+# cosine sampling everywhere.  It does not in "ff_b4" (no sky, so the kernels trace the same estimator as the reference: half the error
+# takes four times the samples) and in "sky_b1" (pure light sampling is noisier than cosine sampling on the walls, which the sun patch
+# does not reach): those two render more frames, the others the 8 frames x 2048 the checks were designed with.
+ROOM_CASES = {
+    "ff_b4": (F_FACEFORWARD, 4, False, 12288, 101, 28),
+    "sky_b1": (F_NEE_SKY | F_FACEFORWARD, 1, False, 6144, 102, 30),
+    "sky_b2": (F_NEE_SKY | F_FACEFORWARD, 2, False, 3072, 103, 8),
+    "sky_b4": (F_NEE_SKY | F_FACEFORWARD, 4, False, 3072, 104, 8),
+    "spec_b2": (F_NEE_SKY | F_FACEFORWARD | F_SPECULAR, 2, True, 3584, 105, 8),
+    "spec_b4": (F_NEE_SKY | F_FACEFORWARD | F_SPECULAR, 4, True, 3584, 106, 8),
+}
+
+
+def room_sky():
+    from test_bsdf_consistency import sky_gradient
+
+    return sky_gradient()
