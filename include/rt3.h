@@ -130,6 +130,10 @@ typedef struct rt3_stats {
     double accel_build_ms;       /* host wall clock of the last rt3_accel_build, stream synchronised on both sides */
     uint64_t accel_bulk_copies;  /* host <-> device copies of array size (> 64 KiB) made by rt3_accel_build calls since rt3_stats_reset:
                                     the build stays on the GPU, so only geometry tables over 64 KiB (many placements) count */
+    uint64_t accel_arena_serial; /* which device allocation the structure's arena (node array + triangle records, what the traversal kernels
+                                    address from one base) is: a process-wide serial number taken where an arena is allocated, 0 = no
+                                    arena (empty scene).  It changes whenever the structure moves to a new allocation (a build that makes
+                                    new trees, rt3_accel_import) and stays when it is rewritten in place (rt3_accel_refit). */
 } rt3_stats;
 
 typedef struct rt3_ctx rt3_ctx;

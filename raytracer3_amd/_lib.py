@@ -59,7 +59,8 @@ class Stats(C.Structure):
                 ("extend_launches", C.c_uint64), ("extend_ms", C.c_double), ("shadow_launches", C.c_uint64), ("shadow_ms", C.c_double),
                 ("shade_ms", C.c_double), ("other_ms", C.c_double),
                 ("trace_launches", C.c_uint64), ("trace_ms", C.c_double), ("trace_rays", C.c_uint64 * 2), ("trace_nodes", C.c_uint64 * 2),
-                ("trace_tris", C.c_uint64 * 2), ("gather_ms", C.c_double), ("nodes_visited_lds", C.c_uint64), ("shadow_nodes_visited_lds", C.c_uint64), ("accel_build_ms", C.c_double), ("accel_bulk_copies", C.c_uint64)]
+                ("trace_tris", C.c_uint64 * 2), ("gather_ms", C.c_double), ("nodes_visited_lds", C.c_uint64), ("shadow_nodes_visited_lds", C.c_uint64), ("accel_build_ms", C.c_double), ("accel_bulk_copies", C.c_uint64),
+                ("accel_arena_serial", C.c_uint64)]
 
 
 class Instance(C.Structure):

@@ -231,6 +231,11 @@ static void free_accel(rt3_ctx* c) {
     c->accel.bvh = LbvhResult{};
     tl_reset(c);
 }
+// the RT3_E_INVALID of a structure whose nodes and triangle records do not fit one arena of 32-bit byte offsets (LbvhResult::alloc_arena)
+static int fail_arena(rt3_ctx* c, const char* who, uint64_t need) {
+    return fail(c, RT3_E_INVALID, std::string(who) + ": the nodes and triangle records need " + std::to_string(need) + " bytes, the traversal kernels address " +
+                                      std::to_string(kArenaMaxBytes) + " (one base + 32-bit offsets)");
+}
 // the union of the child boxes of a quantised 64-byte node, decoded as the traversal decodes them (origin + q * step), in double
 static void quantised_node_box(const uint32_t* w, double box[6]) {
     float org[3], step[3];
@@ -291,6 +296,7 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (res->arena_need > kArenaMaxBytes) return fail_arena(c, "two-level: bottom tree", res->arena_need);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("two-level: bottom tree: ") + hipGetErrorString(e));
     m.n_nodes = res->n_nodes;
     m.depth = res->max_depth;
@@ -358,8 +364,7 @@ static int tl_records_and_top(rt3_ctx* c) {
         slot++;
     }
     if (n_ne == 0) {  // nothing placed: every ray misses (the kernels' empty-scene path)
-        c->accel.bvh.nodes.reset();
-        c->accel.bvh.tris.reset();
+        c->accel.bvh.free_arena();
         c->accel.bvh.top.reset();
         tl.valid = false;
         tl.n_meshes = 0;
@@ -526,23 +531,24 @@ static int build_two_level(rt3_ctx* c) {
         }
         if (rc == RT3_OK && (nodes_total >= (1ull << 29) || tris_total > (1ull << 28)))
             rc = fail(c, RT3_E_UNSUPPORTED, "instance mode 1: the bottom trees exceed the 28-bit references");
-        DevBuf<float4> nodes, tris;
+        LbvhResult fresh;  // (only its arena is used: the combined node array, then the combined triangle records)
         hipError_t e = hipSuccess;
         if (rc == RT3_OK) {
-            e = nodes.alloc_bytes((size_t)nodes_total * 64);
-            if (e == hipSuccess) e = tris.alloc_bytes((size_t)tris_total * 48 + 128);  // + the traversal's over-read slack
-            if (e == hipSuccess) e = hipMemsetAsync((char*)tris.get() + (size_t)tris_total * 48, 0, 128, c->stream);
+            e = fresh.alloc_arena((size_t)nodes_total * 64, (size_t)tris_total, c->stream);
+            if (fresh.arena_need > kArenaMaxBytes) rc = fail_arena(c, "two-level: bottom trees", fresh.arena_need);
+        }
+        if (rc == RT3_OK) {
             for (size_t q = 0; e == hipSuccess && q < meshes.size(); q++) {
                 const TlMesh& m = meshes[q];
                 if (from[q] >= 0) {
                     const TlMesh& om = tl.meshes[from[q]];
-                    tlas_rebase_nodes(c->stream, c->accel.bvh.nodes.get() + 4 * (size_t)om.node_off, nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, om.node_off,
+                    tlas_rebase_nodes(c->stream, c->accel.bvh.nodes.get() + 4 * (size_t)om.node_off, fresh.nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, om.node_off,
                                       m.node_off, om.tri_off, m.tri_off);
-                    e = hipMemcpyAsync(tris.get() + 3 * (size_t)m.tri_off, c->accel.bvh.tris.get() + 3 * (size_t)om.tri_off, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice,
+                    e = hipMemcpyAsync(fresh.tris.get() + 3 * (size_t)m.tri_off, c->accel.bvh.tris.get() + 3 * (size_t)om.tri_off, (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice,
                                        c->stream);
                 } else {
-                    tlas_rebase_nodes(c->stream, built[q].nodes.get(), nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, 0u, m.node_off, 0u, m.tri_off);
-                    e = hipMemcpyAsync(tris.get() + 3 * (size_t)m.tri_off, built[q].tris.get(), (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
+                    tlas_rebase_nodes(c->stream, built[q].nodes.get(), fresh.nodes.get() + 4 * (size_t)m.node_off, m.n_nodes, 0u, m.node_off, 0u, m.tri_off);
+                    e = hipMemcpyAsync(fresh.tris.get() + 3 * (size_t)m.tri_off, built[q].tris.get(), (size_t)m.n_tris * 48, hipMemcpyDeviceToDevice, c->stream);
                 }
             }
             if (e == hipSuccess) e = hipGetLastError();
@@ -553,8 +559,7 @@ static int build_two_level(rt3_ctx* c) {
             free_accel(c);
             return rc;
         }
-        c->accel.bvh.nodes = std::move(nodes);
-        c->accel.bvh.tris = std::move(tris);
+        c->accel.bvh.take_arena(fresh);  // (the old arena, which kept bottom trees were copied from, goes here)
         tl.meshes = meshes;
         tl.head = head;
         tl.gen = c->scene.content_gen;
@@ -629,7 +634,9 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
                                   c->opt.sah_top, c->accel.build_scratch, &c->accel.bvh, c->accel.masked ? c->accel.d_geom_mask.get() : nullptr);
         if (c->accel.build_scratch.capacity_bytes() > ((size_t)1 << 30)) c->accel.build_scratch.reset();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
+            const uint64_t need = c->accel.bvh.arena_need;
             free_accel(c);  // (what the failed build allocated)
+            if (need > kArenaMaxBytes) return fail_arena(c, "lbvh_build", need);
             return fail(c, RT3_E_HIP, std::string("lbvh_build: ") + hipGetErrorString(e));
         }
         const uint32_t stack_need = stack_entries(c->opt.node_width, c->accel.bvh.max_depth);
@@ -719,15 +726,14 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     if (stack_entries(4, depth) > kMaxStack) return fail(c, RT3_E_DEPTH, "accel_import: the tree is deeper than the traversal stack supports");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    DevBuf<float4> d_nodes, d_tris;
-    HIPC(c, d_nodes.alloc_bytes(nodes_bytes));
-    hipError_t e = d_tris.alloc_bytes(tris_bytes + 128);  // (the walk over-reads a leaf's last record by up to 128 bytes)
-    if (e == hipSuccess) e = hipMemset(d_tris.get(), 0, tris_bytes + 128);
-    if (e == hipSuccess) e = hipMemcpy(d_nodes.get(), nodes, nodes_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && tris_bytes) e = hipMemcpy(d_tris.get(), tris, tris_bytes, hipMemcpyHostToDevice);
+    LbvhResult fresh;  // (only its arena is used; the structure in place stays whole until the new one is complete)
+    hipError_t e = fresh.alloc_arena(nodes_bytes, nt, c->stream);  // (zeroes the over-read slack behind the last record)
+    if (fresh.arena_need > kArenaMaxBytes) return fail_arena(c, "accel_import", fresh.arena_need);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(fresh.nodes.get(), nodes, nodes_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tris_bytes) e = hipMemcpy(fresh.tris.get(), tris, tris_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("accel_import: ") + hipGetErrorString(e));
-    c->accel.bvh.nodes = std::move(d_nodes);
-    c->accel.bvh.tris = std::move(d_tris);
+    c->accel.bvh.take_arena(fresh);
     c->accel.bvh.n_nodes = nn;
     c->accel.bvh.n_tris = nt;
     c->accel.bvh.max_depth = depth;

@@ -391,6 +391,7 @@ int rt3_stats_get(rt3_ctx* c, rt3_stats* out) {
     HIPC(c, hipStreamSynchronize(c->stream));
     if (int r = harvest(c)) return r;
     *out = c->prof.stats;
+    out->accel_arena_serial = c->accel.bvh.arena_serial;  // (a property of the structure in place, not a sum since the reset)
     return RT3_OK;
 }
 

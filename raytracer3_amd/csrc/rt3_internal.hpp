@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
 
 #include "rt3_camera.hpp"
@@ -214,14 +215,70 @@ private:
     size_t end_ = 0;
 };
 
+// A piece of an allocation that somebody else owns, with DevBuf's reading interface.
+template <typename T>
+class DevView {
+public:
+    DevView() = default;
+    explicit DevView(T* p) : p_(p) {}
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    T* p_ = nullptr;
+};
+
+// The traversal kernels address a structure as ONE base plus a 32-bit byte offset per lane: the arena may not be
+// larger than this, over-read slack included.
+constexpr uint64_t kArenaMaxBytes = (4ull << 30) - 128;
+uint64_t next_arena_serial();  // 1, 2, ...: process-wide, one per arena allocated (rt3_lbvh.hip)
+constexpr size_t kArenaSlack = 128;  // a leaf fetch reads 64 B (four-wide fp32 layout: 128 B) from a 48 B record: zeroed bytes behind the last record
+
 struct LbvhResult {
-    DevBuf<float4> nodes;      // n_nodes x node_bytes: 64 B {box0, box1, ref0, ref1, pad} or 128 B 4 x {min, max, ref, pad}
+    // One allocation for what a walk fetches: the node array at byte 0, the triangle records at byte tri_off (the node bytes rounded up to
+    // 128), then kArenaSlack zero bytes.  nodes / tris are views into it.
+    DevBuf<float4> arena;
+    DevView<float4> nodes;     // n_nodes x node_bytes: 64 B {box0, box1, ref0, ref1, pad} or 128 B 4 x {min, max, ref, pad}
     uint32_t node_bytes = 128;
     int layout = kLayoutWide128;
-    DevBuf<float4> tris;       // n_tris x 3 float4 (48 B), Morton order
+    DevView<float4> tris;      // n_tris x 3 float4 (48 B), Morton order
+    uint32_t tri_off = 0;
+    uint64_t arena_need = 0;   // the size the last alloc_arena asked for: > kArenaMaxBytes when it refused (hipErrorInvalidValue)
+    uint64_t arena_serial = 0; // which allocation the arena is (next_arena_serial, taken where it is allocated); 0 = none
     DevBuf<float4> top;        // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
+
+    // a fresh arena for nodes_bytes of nodes and n_records triangle records (the old one goes first); the slack is zeroed on `st`
+    hipError_t alloc_arena(size_t nodes_bytes, size_t n_records, hipStream_t st) {
+        free_arena();
+        const size_t off = (nodes_bytes + 127) & ~(size_t)127, rec_end = off + n_records * 48;
+        arena_need = rec_end + kArenaSlack;
+        if (arena_need > kArenaMaxBytes) return hipErrorInvalidValue;
+        RT3_TRY(arena.alloc_bytes(rec_end + kArenaSlack));
+        arena_serial = next_arena_serial();
+        tri_off = (uint32_t)off;
+        nodes = DevView<float4>(arena.get());
+        tris = DevView<float4>(reinterpret_cast<float4*>(reinterpret_cast<char*>(arena.get()) + off));
+        return hipMemsetAsync(reinterpret_cast<char*>(arena.get()) + rec_end, 0, kArenaSlack, st);
+    }
+    void free_arena() {
+        arena.reset();
+        nodes = tris = DevView<float4>();
+        tri_off = 0;
+        arena_serial = 0;
+    }
+    // the arena of `from` becomes this structure's (counts, layout and top copy stay what they are)
+    void take_arena(LbvhResult& from) {
+        arena = std::move(from.arena);
+        nodes = from.nodes;
+        tris = from.tris;
+        tri_off = from.tri_off;
+        arena_serial = from.arena_serial;
+        from.nodes = from.tris = DevView<float4>();
+        from.tri_off = 0;
+        from.arena_serial = 0;
+    }
 };
 // One traversal launch over a ray queue: closest hit (launch_extend) or any hit (launch_shadow).  Each reads only its own outputs.
 struct TraceLaunch {

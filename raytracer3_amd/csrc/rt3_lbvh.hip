@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -761,6 +762,9 @@ struct LbvhScratch {
     // compact layout: Morton-ordered triangle records before they move into leaf order; child counts and their bases
     float4* tris_morton;
     uint32_t *n_int, *n_ltri, *cbase, *tbase;
+    // the triangle records in their final order, until the node count is known and the arena (nodes, then records) can be allocated
+    // (the compact layout emits its records after that, straight into the arena)
+    float4* tris_stage;
     SahTopScratch sah;
     uint32_t *fr_a, *fr_b, *fr_n;  // four-wide collapse: the frontiers and their sizes
     uint32_t* n_top;               // the top-of-tree copy's node count
@@ -775,6 +779,7 @@ hipError_t plan_scratch(hipStream_t st, uint32_t n, int quant, int collapse, boo
         plan.add(&s->dk, nn).add(&s->dc, 3 * nn).add(&s->newpos, n).add(&s->lmin2, 3 * (size_t)n).add(&s->lmax2, 3 * (size_t)n);
         plan.add(&s->tris_dp, 3 * (size_t)n);
     }
+    if (quant != 2 || n == 1) plan.add(&s->tris_stage, 3 * (size_t)n);
     if (quant == 2 && n > 1)
         plan.add(&s->tris_morton, 3 * (size_t)n).add(&s->n_int, nn).add(&s->n_ltri, nn).add(&s->cbase, nn).add(&s->tbase, nn);
     RT3_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, s->sort_bytes, s->keys_in, s->keys_out, s->vals_in, s->vals_out, (int)n, 0, 63, st));
@@ -788,6 +793,11 @@ hipError_t plan_scratch(hipStream_t st, uint32_t n, int quant, int collapse, boo
     return hipSuccess;
 }
 }  // namespace
+
+uint64_t next_arena_serial() {
+    static std::atomic<uint64_t> serial{0};
+    return ++serial;
+}
 
 hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
                       uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask) {
@@ -817,8 +827,6 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
         init_bounds[6 + k] = 0xFFFFFFFFu;
         init_bounds[9 + k] = 0u;
     }
-    RT3_TRY(out->tris.alloc_bytes((size_t)n * 48 + 128));  // + slack: the traversal fetch may over-read the last leaf by up to 128 B
-    RT3_TRY(hipMemsetAsync((char*)out->tris.get() + (size_t)n * 48, 0, 128, st));
     RT3_TRY(hipMemcpyAsync(s.bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
     RT3_TRY(hipMemsetAsync(s.arrive, 0, (size_t)nn * 4, st));
     RT3_TRY(hipMemsetAsync(s.levels, 0, 4, st));
@@ -826,10 +834,11 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
     hipLaunchKernelGGL(k_morton, dim3(grid), dim3(256), 0, st, s.bmin, s.bmax, s.bounds, n, s.keys_in, s.vals_in);
     RT3_TRY(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp, s.sort_bytes, s.keys_in, s.keys_out, s.vals_in, s.vals_out, (int)n, 0, 63, st));
     hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, s.vals_out, s.bmin, s.bmax, s.bounds, n,
-                       s.tris_dp ? s.tris_dp : (s.tris_morton ? s.tris_morton : out->tris.get()), s.lmin, s.lmax, geom_mask);
+                       s.tris_dp ? s.tris_dp : (s.tris_morton ? s.tris_morton : s.tris_stage), s.lmin, s.lmax, geom_mask);
     if (n == 1) {
-        RT3_TRY(out->nodes.alloc_bytes(out->node_bytes));
+        RT3_TRY(out->alloc_arena(out->node_bytes, 1, st));
         hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, s.lmin, s.lmax, wide, quant, out->nodes.get());
+        RT3_TRY(hipMemcpyAsync(out->tris.get(), s.tris_stage, 48, hipMemcpyDeviceToDevice, st));
         out->n_nodes = 1;
         out->max_depth = 2;
         RT3_TRY(hipGetLastError());
@@ -864,7 +873,7 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
                                s.live, s.arrive);
             const unsigned g3 = (unsigned)(((uint64_t)n + nn + 255) / 256 > 4096 ? 4096 : ((uint64_t)n + nn + 255) / 256);
             hipLaunchKernelGGL(k_tree_order, dim3(g3), dim3(256), 0, st, s.left, s.right, s.pint, s.pleaf, s.rcnt, n, nn, s.newpos, s.rlo);
-            float4* tris_to = quant == 2 ? s.tris_morton : out->tris.get();  // (the compact layout moves them once more, into leaf order, when it emits)
+            float4* tris_to = quant == 2 ? s.tris_morton : s.tris_stage;  // (the compact layout moves them once more, into leaf order, when it emits)
             hipLaunchKernelGGL(k_tree_reorder, dim3(g3), dim3(256), 0, st, s.newpos, n, nn, s.tris_dp, tris_to, s.lmin, s.lmax, s.lmin2, s.lmax2, s.left, s.right);
             s.lmin = s.lmin2;
             s.lmax = s.lmax2;
@@ -907,7 +916,9 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
         RT3_TRY(hipMemcpyAsync(&out->max_depth, s.levels, 4, hipMemcpyDeviceToHost, st));
         RT3_TRY(hipStreamSynchronize(st));
         out->n_nodes = tail[0] + tail[1];
-        RT3_TRY(out->nodes.alloc_bytes((size_t)out->n_nodes * out->node_bytes));
+        RT3_TRY(out->alloc_arena((size_t)out->n_nodes * out->node_bytes, n, st));
+        // the one copy of a build: the records were finished before the node count, and with it their place, was known
+        if (quant != 2) RT3_TRY(hipMemcpyAsync(out->tris.get(), s.tris_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         if (quant == 2) {
             hipLaunchKernelGGL(k_child_counts, dim3(grid), dim3(256), 0, st, s.left, s.right, s.rcnt, s.nbox, s.keep, nn, s.live, s.dk, collapse, s.n_int, s.n_ltri);
             RT3_TRY(hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, s.scan_bytes, s.n_int, s.cbase, (int)nn, st));

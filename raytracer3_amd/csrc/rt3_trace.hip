@@ -150,7 +150,7 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // best) is alpha-tested inline in its leaf step -- the extra gathers (table, 3 uvs, texture entry, 4 texels) stay out of every other step.
 // best is only updated, and an any-hit lane only finishes, on an intersection that counts.
 template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, typename Finish>
-__device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, const float4* __restrict__ tris,
+__device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, uint32_t tri_off,
                                              const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
                                              const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr,
@@ -292,10 +292,24 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
         const bool cached = LAYOUT == kLayoutWide64Q && !is_leaf && (r.cur & kTopFlag) != 0u;  // a top-of-tree node held in LDS
         const bool is_inst = TWO && is_leaf && !tl_bottom;  // a leaf of the top tree: the instance record at node `first`
         const bool is_tri = is_leaf && !is_inst;
-        const float4* p = is_tri ? tris + 3 * (size_t)(first + r.leaf_k)
-                                 : nodes + (WIDE ? 8 : (C48 ? kC48Stride : 4)) * (size_t)(cached ? 0u : (is_inst ? first : r.cur));
-        // one batch of loads (the triangle array carries 128 B of slack so that over-reading a leaf is in bounds)
+        // `nodes` is the base of the structure's ONE arena (node array, then the triangle records at byte tri_off: LbvhResult) and a lane's
+        // item sits at a 32-bit byte offset from it, chosen by a select: the loads take the uniform base in scalar registers and the offset
+        // in one vector register, with no 64-bit address arithmetic and no divergent region that only computes an address.  The host
+        // refuses an arena beyond 4 GiB - 128 (kArenaMaxBytes), so no offset wraps.
+        constexpr uint32_t kNodeBytes = 16u * (WIDE ? 8 : (C48 ? kC48Stride : 4));
+        uint32_t off_tri = tri_off + 48u * (first + r.leaf_k), off_node = kNodeBytes * (cached ? 0u : (is_inst ? first : r.cur));
+        // (both offsets exist before the select: left to itself the compiler turns the select back into two exec regions, one per product)
+        asm volatile("" : "+v"(off_tri), "+v"(off_node));
+        const uint32_t off = is_tri ? off_tri : off_node;
+        const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + off);
+        // one batch of loads (the arena ends in 128 B of slack so that over-reading the last leaf is in bounds)
         float4 q0, q1, q2, q3, q4, q5, q6, q7;
+        if (TWO && is_tri) {  // the instance's forward matrix (the record's second node), in the same batch as the triangle
+            const float4* pm = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + 64u * (tl_rec + 1u));
+            q4 = pm[0];
+            q5 = pm[1];
+            q6 = pm[2];
+        }
         if (LAYOUT == kLayoutWide64Q && cached) {
             const float4* t = top_lds + 4 * (r.cur & 0xFFFFu);
             q0 = t[0];
@@ -314,13 +328,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
             q6 = p[6];
             q7 = p[7];
         }
-        if (TWO && is_tri) {  // the instance's forward matrix (the record's second node), in the same batch as the triangle
-            const float4* pm = nodes + 4 * (size_t)(tl_rec + 1u);
-            q4 = pm[0];
-            q5 = pm[1];
-            q6 = pm[2];
-            pin(q4); pin(q5); pin(q6);
-        }
+        if (TWO && is_tri) { pin(q4); pin(q5); pin(q6); }
         // pin the fetched registers: without this LLVM sinks the loads only one branch needs into that branch, which
         // turns one memory round trip per step into two
         pin(q0); pin(q1); pin(q2);
@@ -459,8 +467,11 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, c
                 // (farthest child first).  Occlusion does not depend on the order, but a shadow ray starts on a surface whose
                 // neighbourhood it only grazes and is usually blocked far away (ceiling, opposite wall): far-first reaches that
                 // occluder in ~35 % fewer node visits than slot order.  Non-entered slots carry +inf and sink to the end.
-                Cand c0{h0 ? (ANY ? -t0 : t0) : kInf, h0 ? r0 : kEmptySlot}, c1{h1 ? (ANY ? -t1 : t1) : kInf, h1 ? r1 : kEmptySlot};
-                Cand c2{h2 ? (ANY ? -t2 : t2) : kInf, h2 ? r2 : kEmptySlot}, c3{h3 ? (ANY ? -t3 : t3) : kInf, h3 ? r3 : kEmptySlot};
+                // A slot that was not entered keeps its raw reference: after the sort the entered slots are the first nh candidates (every
+                // entered key is finite, so +inf is never in front of one), and nh gates every use of a reference below -- r.cur is popped
+                // over when nh == 0, the pushes ask nh > 1 / 2 / 3.  Four selects less per node.
+                Cand c0{h0 ? (ANY ? -t0 : t0) : kInf, r0}, c1{h1 ? (ANY ? -t1 : t1) : kInf, r1};
+                Cand c2{h2 ? (ANY ? -t2 : t2) : kInf, r2}, c3{h3 ? (ANY ? -t3 : t3) : kInf, r3};
                 const uint32_t nh = (uint32_t)h0 + (uint32_t)h1 + (uint32_t)h2 + (uint32_t)h3;
                 // 5-comparator sorting network on the key
                 cswap(c0, c1);
@@ -566,7 +577,7 @@ struct AlphaArg<false> {
 // closest-hit over a ray queue.  rays: two float4 streams of `stride` records, {o.xyz, tmin} then {d.xyz, tmax};
 // hits: one float4 {t, u, v, prim} per ray.  16-byte records are the widest coalesced access (1 KiB per wave instruction).
 template <bool COUNT, int LAYOUT, bool MASK = false>
-__global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
+__global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restrict__ nodes, uint32_t tri_off, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
                                                          const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
                                                          float* __restrict__ hits, uint32_t* __restrict__ cnt_nodes,
@@ -585,7 +596,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
         counts.ray(i, cn, ct, cl);
     };
     trace_stream<0, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, false, MASK>(
-        nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top, nullptr, nullptr, alpha.get());
+        nodes, tri_off, rays, stride, n, work_counter, stack + threadIdx.x, finish, false, payload != 0, s_top, use_top, nullptr, nullptr, alpha.get());
     counts.add_totals(totals, lds_total);
 }
 
@@ -593,7 +604,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_extend(const float4* __restric
 // If `occluded_out` != nullptr the kernel only reports occlusion (rt3_trace_rays).
 // RANGE: the emitter shadow queue, whose rays end short of their sampled emitter point (range (kRayTMin, tmax[i]))
 template <bool COUNT, int LAYOUT, bool RANGE = false, bool MASK = false>
-__global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float4* __restrict__ top, uint32_t n_top,
+__global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restrict__ nodes, uint32_t tri_off, const float4* __restrict__ top, uint32_t n_top,
                                                          const float* __restrict__ rays, size_t stride,
                                                          const uint32_t* __restrict__ count_ptr, uint32_t count_imm, AlphaArg<MASK> alpha,
                                                          const float* __restrict__ contrib, float* __restrict__ lacc,
@@ -607,7 +618,7 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     const uint32_t n = count_ptr ? *count_ptr : count_imm;
     TraceCounts<COUNT> counts{cnt_nodes, cnt_tris};
     trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE, MASK>(
-        nodes, tris, rays, stride, n, work_counter, stack + threadIdx.x,
+        nodes, tri_off, rays, stride, n, work_counter, stack + threadIdx.x,
         [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
             if (occluded_out) {
                 occluded_out[i] = h.prim != kMiss ? 1u : 0u;
@@ -656,7 +667,7 @@ void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) 
     unsigned long long* const lds_tot = L.totals ? L.totals + kTotExtendLds : nullptr;
     dispatch_traversal(L.count, bvh.layout, L.alpha.table != nullptr, [&](auto c, auto l, auto m) {
         hipLaunchKernelGGL((k_extend<decltype(c)::value, decltype(l)::value, decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(),
-                           bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.hits, L.cnt_nodes, L.cnt_tris, tot, L.work_counter,
+                           bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.hits, L.cnt_nodes, L.cnt_tris, tot, L.work_counter,
                            L.payload ? 1 : 0, alpha_arg<decltype(m)::value>(L), lds_tot);
     });
 }
@@ -667,7 +678,7 @@ void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) 
     dispatch_traversal(L.count, bvh.layout, L.alpha.table != nullptr, [&](auto c, auto l, auto m) {
         auto launch = [&](auto range) {
             hipLaunchKernelGGL((k_shadow<decltype(c)::value, decltype(l)::value, decltype(range)::value, decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0,
-                               st, bvh.nodes.get(), bvh.tris.get(), bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n,
+                               st, bvh.nodes.get(), bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n,
                                alpha_arg<decltype(m)::value>(L), L.contrib, L.lacc, L.occluded, L.cnt_nodes, L.cnt_tris, tot, L.work_counter, lds_tot, L.tmax);
         };
         if (L.tmax) launch(std::true_type{});
