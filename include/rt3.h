@@ -163,6 +163,9 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
 /* 13: retired (was RT3_OPT_SAH_TOP_DEVICE, the host build of the SAH top); not reused */
 #define RT3_OPT_INSTANCE_MODE 14  /* how rt3_accel_build treats instances: 0 = flatten (default), 1 = two-level (shared bottom trees under a top tree; default node
                                      layout only).  See the instances block below; next rt3_accel_build */
+#define RT3_OPT_SHADOW_EXIT_TABLE 15 /* k_shadow's exit table (single-level structures of the default node layout): 1 = a shadow ray first tries the leaf
+                                     recorded for the cell where it leaves the scene box (default), 0 = off, 2 = on with pseudo-random valid entries (a test aid:
+                                     no result depends on the table's contents).  Takes effect at once; see rt3_accel_exit_table_info */
 int rt3_set_option(rt3_ctx *ctx, int option, int64_t value);
 
 /* ---- scene upload: DynamicBuffer::push (vulkan/buffer.rs:406-420) into the world buffers of
@@ -279,6 +282,11 @@ int rt3_accel_download(rt3_ctx *ctx, void *nodes, size_t nodes_bytes, void *tris
  * records; not the shading tables).  Instance mode 0 reports 0, 0, 0 and the flattened tree's bytes.  In mode 1 rt3_accel_info gives the
  * summed node and triangle counts of both levels and the combined depth. */
 int rt3_accel_levels(rt3_ctx *ctx, uint32_t *n_meshes, uint32_t *n_meshes_built, uint32_t *n_top_nodes, uint64_t *accel_bytes);
+/* k_shadow's exit table (RT3_OPT_SHADOW_EXIT_TABLE; any pointer may be NULL): its entries (0 = none: option 0, two-level mode, another node
+ * layout, an empty scene), the shadow rays that started at an entry and those an entry occluded since the last build / import / refit /
+ * rt3_scene_set_sky, and whether the next launch starts every ray at its entry (1) or only every 32nd chunk of rays (0: fewer than a
+ * quarter of more than 2^16 tries succeeded). */
+int rt3_accel_exit_table_info(rt3_ctx *ctx, uint32_t *cells, uint64_t *tried, uint64_t *occluded, uint32_t *in_use);
 /* the way back: install a tree built elsewhere over the same (flattened) triangles -- a better offline builder, a cache of an earlier run
  * (what vkCmdCopyMemoryToAccelerationStructureKHR is to the reference's driver).  Default layout only (64-byte nodes, 48-byte triangle
  * records, rt3_accel_download's format); call rt3_accel_build first (it makes the shading records).  Every reference is validated on

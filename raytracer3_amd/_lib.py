@@ -22,6 +22,7 @@ OPT_BATCH_SPP, OPT_PROFILE, OPT_COUNT_TRAVERSAL, OPT_EXTEND_VARIANT, OPT_LEAF_SI
 OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
 OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
+OPT_SHADOW_EXIT_TABLE = 15  # k_shadow's exit table: 0 = off, 1 = on (default), 2 = on with pseudo-random valid entries (a test aid)
 DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
 TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
@@ -33,7 +34,7 @@ EXPORTS = [
     "rt3_scene_set_alpha_cutoffs",
     "rt3_scene_set_material_textures",
     "rt3_scene_set_instances",
-    "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
+    "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_exit_table_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
     "rt3_buffer_create", "rt3_image_create", "rt3_image_import", "rt3_resource_upload", "rt3_resource_download", "rt3_resource_device_ptr",
     "rt3_set_tile_partition", "rt3_tile_pixel_count", "rt3_image_pack_tiles", "rt3_image_unpack_tiles",
@@ -148,6 +149,7 @@ def load():
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),
         "rt3_accel_levels": (i32, [vp, pu32, pu32, pu32, C.POINTER(C.c_uint64)]),
+        "rt3_accel_exit_table_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), pu32]),
         "rt3_accel_download": (i32, [vp, vp, sz, vp, sz]),
         "rt3_accel_import": (i32, [vp, vp, sz, vp, sz]),
         "rt3_sky_download": (i32, [vp, vp, vp, vp, vp]),

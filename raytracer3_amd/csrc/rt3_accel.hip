@@ -597,11 +597,63 @@ static int make_alpha_tables(rt3_ctx* c) {
     HIPC(c, hipMemcpy(c->accel.d_alpha.get(), table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
     return RT3_OK;
 }
+// ---- k_shadow's exit table (DESIGN.md sections 5 and 7; rt3_exit_table.hip).  Single-level structures of the default layout have room for it
+// in their arena; it is (re)filled after a build, an import and a refit, and its counters start again.
+static uint32_t exit_R(const rt3_ctx* c) {
+    if (c->opt.instance_mode == 1 || c->opt.node_width != 4 || c->opt.node_quant != 1) return 0u;
+    return kExitDefaultR;
+}
+static int make_exit_table(rt3_ctx* c) {
+    LbvhResult& b = c->accel.bvh;
+    b.exit.on = false;
+    if (!b.exit.off || !b.exit.R || b.layout != kLayoutWide64Q || !b.n_nodes || !b.nodes || !c->accel.n_flat_prims) return RT3_OK;  // no table
+    if (!c->accel.exit_counters) HIPC(c, c->accel.exit_counters.alloc_bytes(2 * sizeof(unsigned long long)));
+    b.exit.counters = c->accel.exit_counters.get();
+    HIPC(c, hipMemsetAsync(b.exit.counters, 0, 2 * sizeof(unsigned long long), c->stream));
+    if (c->opt.exit_table == 0) return RT3_OK;
+    uint32_t root[16];
+    double box[6];
+    HIPC(c, hipMemcpyAsync(root, b.nodes.get(), 64, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    quantised_node_box(root, box);
+    for (int k = 0; k < 3; k++) {
+        if (!(box[k] <= box[3 + k])) return RT3_OK;  // a root without children: nothing to lay cells on
+        b.exit.lo[k] = round_down(box[k]);
+        b.exit.hi[k] = round_up(box[3 + k]);
+        const float ext = b.exit.hi[k] - b.exit.lo[k], s = (float)b.exit.R / ext;
+        b.exit.scale[k] = (ext > 0.0f && std::isfinite(s)) ? s : 0.0f;  // a flat box: every ray falls in cell 0 of that axis
+    }
+    ExitScratch s;
+    BufLayout plan;
+    exit_table_plan(6u * b.exit.R * b.exit.R, c->accel.n_flat_prims, plan, &s);
+    HIPC(c, c->accel.exit_scratch.grow_bytes(plan.bytes()));
+    HIPC(c, plan.carve(c->accel.exit_scratch));
+    const hipError_t e = exit_table_fill(c->stream, b, c->accel.n_flat_prims, s, c->opt.exit_table == 2);
+    if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("exit table: ") + hipGetErrorString(e));
+    b.exit.on = true;
+    return RT3_OK;
+}
+extern "C++" {
+namespace rt3 {
+int exit_table_update(rt3_ctx* c) {
+    if (!c->accel.built || c->accel.stale) return RT3_OK;  // the next build or refit fills it
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = make_exit_table(c)) return r;
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return RT3_OK;
+}
+void exit_counters_reset(rt3_ctx* c) {
+    if (c->accel.exit_counters) (void)hipMemsetAsync(c->accel.exit_counters.get(), 0, 2 * sizeof(unsigned long long), c->stream);
+}
+}  // namespace rt3
+}  // extern "C++"
 // the structure's content changed (build, refit, import): what is made for one stamp (emitter table, motion tables) is remade at its next use
 static void bump_stamp(rt3_ctx* c) { c->accel.stamp++; }
 // the end of a successful build or refit: the shading records, then the structure goes live
 static int accel_finish(rt3_ctx* c, uint32_t* out_handle) {
     if (int r = make_shade_records(c)) return r;
+    if (int r = make_exit_table(c)) return r;
     HIPC(c, hipStreamSynchronize(c->stream));
     c->prof.stats.accel_bulk_copies += c->accel.bulk_copies;
     c->accel.bulk_copies = 0;
@@ -631,7 +683,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     } else {
         free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
         hipError_t e = lbvh_build(c->stream, world_tables(c), c->accel.n_flat_prims, c->opt.leaf_size, c->opt.node_width, c->opt.node_quant, c->opt.collapse,
-                                  c->opt.sah_top, c->accel.build_scratch, &c->accel.bvh, c->accel.masked ? c->accel.d_geom_mask.get() : nullptr);
+                                  c->opt.sah_top, c->accel.build_scratch, &c->accel.bvh, c->accel.masked ? c->accel.d_geom_mask.get() : nullptr, exit_R(c));
         if (c->accel.build_scratch.capacity_bytes() > ((size_t)1 << 30)) c->accel.build_scratch.reset();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
             const uint64_t need = c->accel.bvh.arena_need;
@@ -727,7 +779,7 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
     LbvhResult fresh;  // (only its arena is used; the structure in place stays whole until the new one is complete)
-    hipError_t e = fresh.alloc_arena(nodes_bytes, nt, c->stream);  // (zeroes the over-read slack behind the last record)
+    hipError_t e = fresh.alloc_arena(nodes_bytes, nt, c->stream, exit_R(c));  // (zeroes the over-read slack behind the last record)
     if (fresh.arena_need > kArenaMaxBytes) return fail_arena(c, "accel_import", fresh.arena_need);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(fresh.nodes.get(), nodes, nodes_bytes, hipMemcpyHostToDevice);
@@ -744,6 +796,26 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
         invalidate_accel(c);
         return fail(c, RT3_E_HIP, std::string("accel_import: top-of-tree copy: ") + hipGetErrorString(e));
     }
+    if (int r = make_exit_table(c)) {
+        invalidate_accel(c);
+        return r;
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return RT3_OK;
+}
+int rt3_accel_exit_table_info(rt3_ctx* c, uint32_t* cells, uint64_t* tried, uint64_t* occluded, uint32_t* in_use) {
+    if (int r = check_accel_current(c, "no acceleration structure built")) return r;
+    const ExitTable& t = c->accel.bvh.exit;
+    unsigned long long cnt[2] = {0, 0};
+    if (t.on) {
+        HIPC(c, hipSetDevice(c->device));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, hipMemcpy(cnt, t.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    }
+    if (cells) *cells = t.on ? 6u * t.R * t.R : 0u;
+    if (tried) *tried = cnt[0];
+    if (occluded) *occluded = cnt[1];
+    if (in_use) *in_use = (t.on && (cnt[0] < kExitWarmupTries || 4ull * cnt[1] >= cnt[0])) ? 1u : 0u;  // the launches' own decision
     return RT3_OK;
 }
 

@@ -189,6 +189,10 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             c->opt.instance_mode = (int)value;
             invalidate_accel(c);
             return RT3_OK;
+        case RT3_OPT_SHADOW_EXIT_TABLE:
+            if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "shadow exit table must be 0 (off), 1 (on) or 2 (on, scrambled entries)");
+            c->opt.exit_table = (int)value;
+            return exit_table_update(c);
         default: return fail(c, RT3_E_INVALID, "unknown option");
     }
 }

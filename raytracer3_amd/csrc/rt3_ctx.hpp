@@ -189,6 +189,9 @@ struct rt3_ctx {
         std::vector<rt3::MeshTables> refit_tables;    // instance mode 1: each bottom tree's (tl_build_mesh's)
         rt3::DevBuf<char> refit_scratch;              // grow-only: refit_tree's bounds, node boxes and record boxes
         rt3::TwoLevelState tl;
+        // k_shadow's exit table: the context's two counters {tried, occluded} and the grow-only scratch of a fill
+        rt3::DevBuf<unsigned long long> exit_counters;
+        rt3::DevBuf<char> exit_scratch;
     } accel;
 
     // rt3_passes.hip: the wavefront work queues (capacity in paths) and the device counters of the launches.  rt3_create allocates the
@@ -257,6 +260,7 @@ struct rt3_ctx {
         int variant = 0;  // RT3_OPT_EXTEND_VARIANT: reserved for traversal experiments
         uint32_t leaf_size = 2, node_width = 4, node_quant = 1, collapse = 2, sah_top = 1;
         int instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
+        int exit_table = 1;     // RT3_OPT_SHADOW_EXIT_TABLE: 0 off, 1 on, 2 on with scrambled entries (a test aid)
     } opt;
     // rt3_api.hip (harvest, rt3_stats_reset), the events through ScopedTimer; stats.accel_* are rt3_accel.hip's (a build's time and copies)
     struct Prof {
@@ -332,6 +336,10 @@ GeomTables world_tables(const rt3_ctx* c);
 // must be synchronised (sync_textures) first.
 AlphaDev alpha_dev(const rt3_ctx* c);
 int ensure_lights(rt3_ctx* c);
+// RT3_OPT_SHADOW_EXIT_TABLE changed: the table of a built, current structure is refilled (or switched off) now
+int exit_table_update(rt3_ctx* c);
+// what the counters measured is no longer what the launches see (a new sky): they start again
+void exit_counters_reset(rt3_ctx* c);
 
 // ---- rt3_passes.hip
 void motion_tables_stale(rt3_ctx* c);  // the previous transforms or the deformed flags changed: motion_tables remakes its tables

@@ -234,6 +234,29 @@ constexpr uint64_t kArenaMaxBytes = (4ull << 30) - 128;
 uint64_t next_arena_serial();  // 1, 2, ...: process-wide, one per arena allocated (rt3_lbvh.hip)
 constexpr size_t kArenaSlack = 128;  // a leaf fetch reads 64 B (four-wide fp32 layout: 128 B) from a 48 B record: zeroed bytes behind the last record
 
+// Exit table of k_shadow: 6 R^2 leaf references, one per cell of an R x R grid on each face of the
+// root box -- the leaf an axis-aligned probe from the cell's centre meets first, or kEmptySlot.  A shadow ray tries the entry of the cell
+// where it leaves the box before it walks.  The table lives in the arena behind the slack; a step fetches the 16-byte group of an entry
+// with the step's 64-byte batch, so kExitTableSlack bytes follow the last entry.  In front of the entries sits ExitHeader, which the walk
+// reads when it starts a ray.
+constexpr uint32_t kExitDefaultR = 256, kExitMaxR = 1024;
+constexpr size_t kExitTableSlack = 64;
+struct ExitHeader {
+    float lo[3], hi[3], scale[3];  // ExitTable's
+    uint32_t R, last;              // cells per face edge; the last entry's index, 6 R^2 - 1
+    uint32_t pad[5];
+};
+static_assert(sizeof(ExitHeader) == 64, "the entries start 64 bytes behind the header");
+constexpr uint64_t kExitWarmupTries = 1ull << 16;  // every ray uses the table until this many have (launch-start decision)
+struct ExitTable {
+    uint32_t off = 0;                     // byte offset of the table (ExitHeader, then the entries) in the arena; 0 = none
+    uint32_t R = 0;                       // cells per face edge
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // the box the cells are laid on (the root's, decoded as the walk decodes it)
+    float scale[3] = {0, 0, 0};           // R / extent per axis; 0 where the extent is 0 (every ray falls in cell 0 of that axis)
+    unsigned long long* counters = nullptr;  // the context's {rays that tried an entry, rays an entry occluded}
+    bool on = false;                      // launches use it (RT3_OPT_SHADOW_EXIT_TABLE != 0 and the entries are written)
+};
+
 struct LbvhResult {
     // One allocation for what a walk fetches: the node array at byte 0, the triangle records at byte tri_off (the node bytes rounded up to
     // 128), then kArenaSlack zero bytes.  nodes / tris are views into it.
@@ -248,25 +271,34 @@ struct LbvhResult {
     DevBuf<float4> top;        // quantised four-wide layout: the first n_top nodes in breadth-first order (64 B each), child references to
     uint32_t n_top = 0;        // cached nodes rewritten as 0x40000000 | slot -- the traversal kernels keep this copy in LDS
     uint32_t n_nodes = 0, n_tris = 0, max_depth = 0;
+    ExitTable exit;            // k_shadow's exit table: room for it is part of the arena (exit_cells), the host fills it in after a build
 
-    // a fresh arena for nodes_bytes of nodes and n_records triangle records (the old one goes first); the slack is zeroed on `st`
-    hipError_t alloc_arena(size_t nodes_bytes, size_t n_records, hipStream_t st) {
+    // a fresh arena for nodes_bytes of nodes, n_records triangle records and an exit table of 6 exit_R^2 entries (0 = none); the old one
+    // goes first; the slack is zeroed and the table emptied on `st`
+    hipError_t alloc_arena(size_t nodes_bytes, size_t n_records, hipStream_t st, uint32_t exit_R = 0) {
+        const uint32_t exit_cells = 6u * exit_R * exit_R;
         free_arena();
         const size_t off = (nodes_bytes + 127) & ~(size_t)127, rec_end = off + n_records * 48;
-        arena_need = rec_end + kArenaSlack;
+        const size_t table = exit_cells ? sizeof(ExitHeader) + (size_t)exit_cells * 4 + kExitTableSlack : 0;
+        arena_need = rec_end + kArenaSlack + table;
         if (arena_need > kArenaMaxBytes) return hipErrorInvalidValue;
-        RT3_TRY(arena.alloc_bytes(rec_end + kArenaSlack));
+        RT3_TRY(arena.alloc_bytes(rec_end + kArenaSlack + table));
         arena_serial = next_arena_serial();
         tri_off = (uint32_t)off;
         nodes = DevView<float4>(arena.get());
         tris = DevView<float4>(reinterpret_cast<float4*>(reinterpret_cast<char*>(arena.get()) + off));
-        return hipMemsetAsync(reinterpret_cast<char*>(arena.get()) + rec_end, 0, kArenaSlack, st);
+        RT3_TRY(hipMemsetAsync(reinterpret_cast<char*>(arena.get()) + rec_end, 0, kArenaSlack, st));
+        if (!table) return hipSuccess;
+        exit.R = exit_R;
+        exit.off = (uint32_t)(rec_end + kArenaSlack);  // (a multiple of 16: the records start at a multiple of 128 and are 48 bytes each)
+        return hipMemsetAsync(reinterpret_cast<char*>(arena.get()) + exit.off, 0xFF, table, st);  // kEmptySlot everywhere (the header is written with the entries)
     }
     void free_arena() {
         arena.reset();
         nodes = tris = DevView<float4>();
         tri_off = 0;
         arena_serial = 0;
+        exit = ExitTable{};
     }
     // the arena of `from` becomes this structure's (counts, layout and top copy stay what they are)
     void take_arena(LbvhResult& from) {
@@ -275,6 +307,8 @@ struct LbvhResult {
         tris = from.tris;
         tri_off = from.tri_off;
         arena_serial = from.arena_serial;
+        exit = from.exit;
+        from.exit = ExitTable{};
         from.nodes = from.tris = DevView<float4>();
         from.tri_off = 0;
         from.arena_serial = 0;
@@ -305,7 +339,18 @@ void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);
 // to what this configuration and size need and is kept for the next build.  On failure *out may hold some of its arrays: they go with it.
 // geom_mask: the alpha-mask words of the triangle records per uploaded geometry, or null (every record {v2.z, prim, 0, 0}).
 hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n_prims, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask = nullptr);
+                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask = nullptr, uint32_t exit_R = 0);
+// exit_R: room in the arena for an exit table of 6 exit_R^2 entries (default node layout only; ignored for the others)
+
+// Exit table (rt3_exit_table.hip).  Scratch of a fill: the probe rays, their hits, the primitive -> leaf reference array, the pool cursor.
+struct ExitScratch {
+    float *rays, *hits;
+    uint32_t *prim_leaf, *cursor;
+};
+void exit_table_plan(uint32_t cells, uint32_t n_prims, BufLayout& plan, ExitScratch* s);
+// Writes the bvh.exit.R^2 x 6 entries of bvh's table from bvh.exit.{lo, hi}: probes through launch_extend, then prim -> leaf reference.
+// scramble: every entry becomes a pseudo-random valid leaf reference instead (a test aid: results may not depend on the table's contents).
+hipError_t exit_table_fill(hipStream_t st, const LbvhResult& bvh, uint32_t n_prims, const ExitScratch& s, bool scramble);
 // Scratch of the binned-SAH top (rt3_sah_top.hip), part of the builder's: sah_top_plan adds it to `plan` for a tree over n triangles (at
 // most n clusters under n - 1 top nodes).  The segment and tile records are of types private to rt3_sah_top.hip.
 struct SahTopScratch {

@@ -800,7 +800,7 @@ uint64_t next_arena_serial() {
 }
 
 hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_max, uint32_t node_width, uint32_t node_quant, uint32_t collapse_mode,
-                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask) {
+                      uint32_t sah_top, DevBuf<char>& scratch, LbvhResult* out, const uint2* geom_mask, uint32_t exit_R) {
     *out = LbvhResult{};
     out->n_tris = n;
     const int wide = node_width == 4, quant = wide ? (node_quant > 2 ? 2 : (int)node_quant) : 0, collapse = wide ? (collapse_mode > 2 ? 2 : (int)collapse_mode) : 0;
@@ -808,6 +808,7 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
     out->node_bytes = (wide && !quant) ? 128u : (quant == 2 ? 16u * kC48Stride : 64u);
     out->layout = !wide ? kLayoutBinary64 : (quant == 2 ? kLayoutWide48Q : (quant ? kLayoutWide64Q : kLayoutWide128));
     if (n == 0) return hipSuccess;
+    if (out->layout != kLayoutWide64Q) exit_R = 0;
     const uint32_t nn = n > 1 ? n - 1 : 1;
     LbvhScratch s = {};
     {
@@ -836,7 +837,7 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
     hipLaunchKernelGGL(k_leaves, dim3(grid), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, s.vals_out, s.bmin, s.bmax, s.bounds, n,
                        s.tris_dp ? s.tris_dp : (s.tris_morton ? s.tris_morton : s.tris_stage), s.lmin, s.lmax, geom_mask);
     if (n == 1) {
-        RT3_TRY(out->alloc_arena(out->node_bytes, 1, st));
+        RT3_TRY(out->alloc_arena(out->node_bytes, 1, st, exit_R));
         hipLaunchKernelGGL(k_single, dim3(1), dim3(1), 0, st, s.lmin, s.lmax, wide, quant, out->nodes.get());
         RT3_TRY(hipMemcpyAsync(out->tris.get(), s.tris_stage, 48, hipMemcpyDeviceToDevice, st));
         out->n_nodes = 1;
@@ -916,7 +917,7 @@ hipError_t lbvh_build(hipStream_t st, GeomTables t, uint32_t n, uint32_t leaf_ma
         RT3_TRY(hipMemcpyAsync(&out->max_depth, s.levels, 4, hipMemcpyDeviceToHost, st));
         RT3_TRY(hipStreamSynchronize(st));
         out->n_nodes = tail[0] + tail[1];
-        RT3_TRY(out->alloc_arena((size_t)out->n_nodes * out->node_bytes, n, st));
+        RT3_TRY(out->alloc_arena((size_t)out->n_nodes * out->node_bytes, n, st, exit_R));
         // the one copy of a build: the records were finished before the node count, and with it their place, was known
         if (quant != 2) RT3_TRY(hipMemcpyAsync(out->tris.get(), s.tris_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         if (quant == 2) {

@@ -414,6 +414,7 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
     c->scene.sky_w = w;
     c->scene.sky_h = h;
     c->scene.sky_wt = wt;
+    exit_counters_reset(c);  // the shadow rays follow the sky's importance: the exit table's success rate is measured afresh
     return RT3_OK;
 }
 int rt3_scene_set_bluenoise(rt3_ctx* c, const uint8_t* rgba, uint32_t w, uint32_t h) {

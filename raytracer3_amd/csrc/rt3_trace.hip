@@ -90,6 +90,10 @@ __device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 
 // triangle tests (both branch-free).
 __constant__ uint32_t g_pool_chunk = 256;   // rays per pool grab (RT3_OPT_POOL_CHUNK)
 __constant__ uint32_t g_refill_lanes = 12;  // tuning knob (RT3_OPT_EXTEND_VARIANT)
+// rays per pool grab of a launch over n rays by n_waves waves (trace_stream; k_shadow_exit derives its sampled count from the same number)
+__device__ __forceinline__ uint32_t pool_chunk_for(uint32_t n, uint32_t n_waves) {
+    return (n < 2u * n_waves * g_pool_chunk && g_pool_chunk >= 128u) ? ((g_pool_chunk >> 1) & ~63u) : g_pool_chunk;
+}
 void set_refill_lanes(uint32_t v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_refill_lanes), &v, 4); }
 void set_pool_chunk(uint32_t v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pool_chunk), &v, 4); }
 static unsigned g_trace_max_blocks = kExtendMaxBlocks;  // persistent traversal workgroups per launch (RT3_OPT_TRACE_BLOCKS)
@@ -128,6 +132,25 @@ __device__ __forceinline__ bool slab_test_sorted_pad(uint32_t p, uint32_t q, V3 
     return tn <= tf;
 }
 
+// Exit table (any hit, default layout, single level: EXIT; DESIGN.md sections 5 and 7).  A lane's first item is not the root but the table
+// entry of the cell where its ray leaves the root box: r.cur = kExitFlag | cell (never a leaf reference, never a node index: the arena
+// holds fewer than 2^26 nodes; bit 30, kTopFlag, stays clear so the item is fetched from memory).  The step's own batch fetches the 16-byte
+// group of the entry; the entry, a leaf reference, becomes r.cur with the root pushed, and the ordinary leaf steps test it.  Occlusion
+// does not depend on WHICH occluder is found, so the table's contents decide the speed only.
+constexpr uint32_t kExitFlag = 0x20000000u;
+struct ExitWalk {  // per wave, all wave-uniform: where the table is, the launch's decision and what the wave counted
+    uint32_t off = 0;       // byte offset of the table's header in the arena (ExitHeader, then the entries)
+    uint32_t mode = 0;      // 1: every 32nd chunk starts at the table, so that the rate stays known; 2: every chunk does
+    uint32_t occluded = 0;  // rays an entry's leaf occluded
+};
+// rays of a queue of n that start at the table when only every 32nd chunk of `chunk` rays does
+__device__ __forceinline__ unsigned long long exit_sampled_rays(uint32_t n, uint32_t chunk) {
+    if (n == 0u) return 0ull;
+    const uint32_t n_chunks = (n - 1u) / chunk + 1u, m = (n_chunks + 31u) / 32u;  // m >= 1 sampled chunks: 0, 32, ...
+    const unsigned long long last_first = 32ull * (m - 1u) * chunk, rest = n - last_first;
+    return (unsigned long long)(m - 1u) * chunk + (rest < chunk ? rest : chunk);
+}
+
 struct LaneRay {  // traversal state of the ray a lane currently owns
     V3 o, d, inv;
     float tmin, inv_dd;  // inv_dd = 1 / d.d (the triangle test makes no unit-length assumption)
@@ -149,12 +172,13 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // MASK: the structure holds alpha-masked triangles: a candidate that would be accepted (inside, t in range, better than
 // best) is alpha-tested inline in its leaf step -- the extra gathers (table, 3 uvs, texture entry, 4 texels) stay out of every other step.
 // best is only updated, and an any-hit lane only finishes, on an intersection that counts.
-template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, typename Finish>
+template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, bool EXIT = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, uint32_t tri_off,
                                              const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
                                              const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr,
-                                             const AlphaDev& alpha = AlphaDev{}) {
+                                             const AlphaDev& alpha = AlphaDev{}, ExitWalk* xw = nullptr) {
+    static_assert(!EXIT || (MODE == 1 && !COUNT && !TWO && !RANGE && LAYOUT == kLayoutWide64Q), "the exit table serves the plain any-hit walk only");
     // any_payload: the any-hit rays come from k_shade's shadow queue, where every ray has the range (kRayTMin, kBackgroundDepth):
     // the two .w slots of its record carry payload (two contribution channels) instead of tmin / tmax -- 16 bytes less per ray.
     // ext_payload: likewise for the extension rays of the path tracer's own queue (.w = the path's pdf and id, read by k_shade)
@@ -174,13 +198,14 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
     // a launch whose queue is mostly covered by the waves' static first chunks (a 1-spp frame: 2 M rays over 8192 waves) balances
     // better with chunks of half the size: 0.79 -> 0.72 ms per frame at 1080p, 1 spp, one bounce; long queues keep the full chunk
     const uint32_t kRefillLanes = g_refill_lanes,
-                   kPoolChunk = (n < 2u * n_waves * g_pool_chunk && g_pool_chunk >= 128u) ? ((g_pool_chunk >> 1) & ~63u) : g_pool_chunk;
+                   kPoolChunk = pool_chunk_for(n, n_waves);
     // the first chunk of every wave is static (chunk number = global wave number): no atomic storm at launch, when all the
     // waves of the grid would hit the cursor at once (8192 returning atomics on one word ~ 0.1 ms); the cursor counts the
     // chunks handed out after those
     // (wave-uniform, but only the hardware knows: without the readfirstlane the pool cursors live in vector registers)
     const uint32_t wave_id = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     bool first_chunk = true;
+    bool chunk_exit = false;  // EXIT: the rays of the current chunk start at their table entry
     uint32_t spill[kSpill];
     LaneRay r;
     r.o = r.d = r.inv = v3(0.0f, 0.0f, 0.0f);
@@ -230,6 +255,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
             queue_empty = base >= n;
             pool_next = base < n ? base : n;
             pool_end = (n - pool_next) > kPoolChunk ? pool_next + kPoolChunk : n;
+            if constexpr (EXIT) chunk_exit = xw->mode == 2u || (xw->mode == 1u && ((base / kPoolChunk) & 31u) == 0u);
         }
         if (m_idle != 0ull && pool_next < pool_end && ((uint32_t)__popcll(m_idle) >= kRefillLanes || m_idle == ~0ull)) {
             const uint32_t idx = pool_next + (uint32_t)__popcll(m_idle & lanes_below);
@@ -264,6 +290,33 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
                     r.sel_q1 = r.sel_q0 + 0x00000202u;
                 }
                 r.cur = (LAYOUT == kLayoutWide64Q && use_top) ? kTopFlag : 0u;  // the root: slot 0 of the LDS copy, or node 0
+                if constexpr (EXIT) {
+                    if (chunk_exit) {
+                        // where the ray leaves the box: the nearest of the three far planes; the other two coordinates of that point, in cells.
+                        // Whatever the ray is (origin outside, pointing away, zero components, overflow to inf or NaN), the index is clamped
+                        // into the table: fmax / fmin drop a NaN, the integer minimum below is the last word.
+                        // The box and the grid come from the table's header in the arena, read here with scalar loads (the offset is made
+                        // opaque so that they stay in this block: held across the walk they cost the kernel a wave of occupancy).
+                        uint32_t hoff = xw->off;
+                        asm volatile("" : "+s"(hoff));
+                        const ExitHeader e = *reinterpret_cast<const ExitHeader*>(reinterpret_cast<const char*>(nodes) + hoff);
+                        const float tx = ((r.inv.x < 0.0f ? e.lo[0] : e.hi[0]) - r.o.x) * r.inv.x, ty = ((r.inv.y < 0.0f ? e.lo[1] : e.hi[1]) - r.o.y) * r.inv.y,
+                                    tz = ((r.inv.z < 0.0f ? e.lo[2] : e.hi[2]) - r.o.z) * r.inv.z;
+                        const bool ax0 = (tx <= ty) & (tx <= tz), ax1 = !ax0 & (ty <= tz);
+                        const float te = ax0 ? tx : (ax1 ? ty : tz);
+                        const float cx = (__builtin_fmaf(te, r.d.x, r.o.x) - e.lo[0]) * e.scale[0], cy = (__builtin_fmaf(te, r.d.y, r.o.y) - e.lo[1]) * e.scale[1],
+                                    cz = (__builtin_fmaf(te, r.d.z, r.o.z) - e.lo[2]) * e.scale[2];
+                        // axis 0: (u, v) = (y, z); 1: (z, x); 2: (x, y); face = 2 axis + (leaves through the high plane)
+                        const float cu = ax0 ? cy : (ax1 ? cz : cx), cv = ax0 ? cz : (ax1 ? cx : cy);
+                        const float ia = ax0 ? r.inv.x : (ax1 ? r.inv.y : r.inv.z);
+                        const uint32_t face = (ax0 ? 0u : (ax1 ? 2u : 4u)) + (ia < 0.0f ? 0u : 1u);
+                        const float top = (float)(e.R - 1u);
+                        const uint32_t iu = (uint32_t)__builtin_fminf(__builtin_fmaxf(cu, 0.0f), top), iv = (uint32_t)__builtin_fminf(__builtin_fmaxf(cv, 0.0f), top);
+                        uint32_t cell = (face * e.R + iv) * e.R + iu;
+                        cell = cell < e.last ? cell : e.last;
+                        r.cur = kExitFlag | cell;
+                    }
+                }
                 if (TWO) tl_world();
                 r.leaf_k = 0u;
                 r.sp = 0;
@@ -286,6 +339,7 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
         if (__ballot(busy) == 0ull && pool_next >= pool_end && queue_empty) break;
         // ---- one traversal step.  (One region under `if (busy)` and a single way back to the loop header: with `continue`s in front of it
         // the compiler copied the eight registers of the walk's state aside at the top of every step and back at its end.)
+        bool by_entry = false;  // EXIT: the lane finishes in this step on a hit in its table entry's leaf
         if (busy) {
         const bool is_leaf = (r.cur & 0x80000000u) != 0u;
         const uint32_t first = r.cur & 0x0FFFFFFFu, cnt = ((r.cur >> 28) & 7u) + 1u;
@@ -300,7 +354,14 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
         uint32_t off_tri = tri_off + 48u * (first + r.leaf_k), off_node = kNodeBytes * (cached ? 0u : (is_inst ? first : r.cur));
         // (both offsets exist before the select: left to itself the compiler turns the select back into two exec regions, one per product)
         asm volatile("" : "+v"(off_tri), "+v"(off_node));
-        const uint32_t off = is_tri ? off_tri : off_node;
+        uint32_t off = is_tri ? off_tri : off_node;
+        bool is_exit = false;
+        if constexpr (EXIT) {  // a third value for the select: the 16-byte group that holds the lane's table entry
+            is_exit = !is_leaf && (r.cur & kExitFlag) != 0u;
+            uint32_t off_exit = xw->off + (uint32_t)sizeof(ExitHeader) + ((r.cur & 0x00FFFFFCu) << 2);
+            asm volatile("" : "+v"(off_exit));
+            off = is_exit ? off_exit : off;
+        }
         const float4* p = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + off);
         // one batch of loads (the arena ends in 128 B of slack so that over-reading the last leaf is in bounds)
         float4 q0, q1, q2, q3, q4, q5, q6, q7;
@@ -337,7 +398,18 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
         bool pop = false, done = false;
         const V3 o = r.o, d = r.d, inv = r.inv;
         const float tmin = r.tmin;
-        if (TWO && is_inst) {
+        if (EXIT && is_exit) {
+            // table step: the entry becomes the current item with the root left pending (the lane's stack is empty here); an empty
+            // entry means the walk starts at the root as it always did
+            const uint32_t k = r.cur & 3u;
+            const uint32_t e = __float_as_uint(k == 0u ? q0.x : (k == 1u ? q0.y : (k == 2u ? q0.z : q0.w)));
+            const uint32_t root = use_top ? kTopFlag : 0u;
+            if (e != kEmptySlot) {
+                lds[0] = root;
+                r.sp = 1;
+            }
+            r.cur = e != kEmptySlot ? e : root;
+        } else if (TWO && is_inst) {
             // hand-over: record = {inverse 3 x 4 (words 0..11, FlatGeomDev order), bottom root, prim base | identity << 31, pad_abs, pad_rel}.
             // The object-space ray (direction not normalised: t keeps its meaning) only steers the bottom tree's box tests.
             if (COUNT) r.cn++;
@@ -533,10 +605,16 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
         // kMaxSteps bounds the walk so that a corrupt tree can never hang the GPU (a valid tree visits < 2 n nodes)
         if (++r.steps >= kMaxSteps) done = true;
         if (done) {
+            if constexpr (EXIT) {
+                // the entry's leaf occluded the ray: a hit with the root still pending (the root is nobody's child, so no walk pushes it)
+                by_entry = r.best.prim != kMiss && r.sp == 1 && lds[0] == (use_top ? kTopFlag : 0u);
+            }
             finish(r.index, r.best, r.cn, r.ct, r.cl, r.pay0, r.pay1, r.pay2, r.pay3);
             busy = false;
         }
         }  // if (busy)
+        // counted here, where the whole wave passes: a sum kept inside the divergent region would be one per lane (two scalar instructions a step)
+        if constexpr (EXIT) xw->occluded += (uint32_t)__popcll(__ballot(by_entry));
     }
 }
 
@@ -636,6 +714,59 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     counts.add_totals(totals, lds_total);
 }
 
+// k_shadow<false, kLayoutWide64Q, false, MASK> with the exit table (DESIGN.md sections 5 and 7): the same queue, the same finish; every ray, or
+// every 32nd chunk of rays, first tries the leaf its exit cell names.  exit_off: the table's header in the arena; counters: the context's
+// {rays that started at an entry, rays an entry's leaf occluded}.
+template <bool MASK>
+__global__ __launch_bounds__(kExtendBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shadow_exit(const float4* __restrict__ nodes, uint32_t tri_off, const float4* __restrict__ top, uint32_t n_top,
+                                                              const float* __restrict__ rays, size_t stride,
+                                                              const uint32_t* __restrict__ count_ptr, uint32_t count_imm, AlphaArg<MASK> alpha,
+                                                              const float* __restrict__ contrib, float* __restrict__ lacc,
+                                                              uint32_t* __restrict__ occluded_out, uint32_t* __restrict__ work_counter, uint32_t exit_off,
+                                                              unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t stack[kLdsStack * kExtendBlock];
+    __shared__ float4 s_top[4 * kTopNodes];
+    const bool use_top = load_top(s_top, top, n_top);
+    const uint32_t n = count_ptr ? *count_ptr : count_imm;
+    // The switch: every ray starts at its table entry while fewer than 2^16 rays have, and while at least a quarter of those that did were
+    // occluded by the entry's leaf; below that only every 32nd chunk does.  Every workgroup reads the counters at its own start, and the
+    // workgroups of the same launch add to them at their end: on a queue so short that some finish before others start, two workgroups of
+    // one launch can decide differently, and block 0's count of started rays then follows its own decision.  That moves the rate a
+    // little and no result.  (The launcher takes this kernel only for a structure that has nodes and a table.)
+    ExitWalk xw;
+    xw.off = exit_off;
+    {
+        const unsigned long long tried = counters[0], occluded = counters[1];
+        xw.mode = (tried < kExitWarmupTries || 4ull * occluded >= tried) ? 2u : 1u;
+    }
+    trace_stream<1, false, kLayoutWide64Q, false, false, MASK, true>(
+        nodes, tri_off, rays, stride, n, work_counter, stack + threadIdx.x,
+        [&](uint32_t i, const Hit& h, uint32_t, uint32_t, uint32_t, float c_r, float c_g, float c_b, float c_pid) {
+            if (occluded_out) {
+                occluded_out[i] = h.prim != kMiss ? 1u : 0u;
+            } else if (h.prim == kMiss) {
+                float4* L = reinterpret_cast<float4*>(lacc) + __float_as_uint(c_pid);
+                float4 v = *L;
+                *L = make_float4(v.x + c_r, v.y + c_g, v.z + c_b, 0.0f);
+            }
+        },
+        occluded_out == nullptr, false, s_top, use_top, occluded_out == nullptr ? reinterpret_cast<const float2*>(contrib) : nullptr, nullptr, alpha.get(), &xw);
+    {  // the workgroup's count: its waves' scalars through the stack's LDS, which nobody walks any more
+        __syncthreads();
+        if ((threadIdx.x & 63u) == 0u) stack[threadIdx.x >> 6] = xw.occluded;
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            unsigned long long o = 0;
+            for (uint32_t w = 0; w < kExtendBlock / 64u; w++) o += stack[w];
+            if (o) atomicAdd(&counters[1], o);
+            if (blockIdx.x == 0u) {  // the rays that started at an entry follow from the queue's length: all of them, or the sampled chunks
+                const unsigned long long t = xw.mode == 2u ? n : exit_sampled_rays(n, pool_chunk_for(n, gridDim.x * (kExtendBlock / 64u)));
+                if (t) atomicAdd(&counters[0], t);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 // The k_extend / k_shadow instance of (count, layout, mask): `launch` is called with std::integral_constant<bool, COUNT>,
 // std::integral_constant<int, LAYOUT> and std::integral_constant<bool, MASK>.  A layout that is none of the named ones runs as kLayoutBinary64.
@@ -673,6 +804,15 @@ void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) 
 }
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
     const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
+    if (bvh.exit.on && bvh.exit.off && bvh.exit.counters && bvh.layout == kLayoutWide64Q && bvh.nodes && !L.count && !L.tmax) {  // the plain any-hit walk, table present
+        auto launch = [&](auto m) {
+            hipLaunchKernelGGL((k_shadow_exit<decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays,
+                               L.stride, L.count_ptr, L.n, alpha_arg<decltype(m)::value>(L), L.contrib, L.lacc, L.occluded, L.work_counter, bvh.exit.off, bvh.exit.counters);
+        };
+        if (L.alpha.table != nullptr) launch(std::true_type{});
+        else launch(std::false_type{});
+        return;
+    }
     unsigned long long* const tot = L.totals ? L.totals + kTotShadowNodes : nullptr;
     unsigned long long* const lds_tot = L.totals ? L.totals + kTotShadowLds : nullptr;
     dispatch_traversal(L.count, bvh.layout, L.alpha.table != nullptr, [&](auto c, auto l, auto m) {

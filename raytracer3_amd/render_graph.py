@@ -281,6 +281,12 @@ class Context:
         self.check(self.lib.rt3_accel_levels(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
+    def exit_table_info(self):
+        """(cells, tried, occluded, in_use) of k_shadow's exit table (rt3_accel_exit_table_info): 0 cells = no table"""
+        a, b, c, d = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self.check(self.lib.rt3_accel_exit_table_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
     def accel_download(self):
         nn, nt, _, nb = self.accel_info()
         nodes = np.empty((nn, nb // 4), np.uint32)
