@@ -64,6 +64,10 @@ extern "C" {
  * weight p_bsdf / (p_bsdf + p_solid).  No emitter NEE at the last vertex, so with B = 1 (or a scene without emission) nothing changes.  Only
  * refrence_mode reads the bit; the emitter table follows every rt3_accel_build / refit / import (rt3_light_info). */
 #define RT3_F_NEE_EMISSIVE 32u
+/* next-event estimation to the punctual lights of rt3_scene_set_lights (the block comment at rt3_scene_set_lights states
+ * the estimator).  Only refrence_mode reads the bit.  Without lights, or with B = 1, the frame is the one without the bit, bit for bit, from the
+ * same kernels: the bit is dropped from the flag word such a frame runs with, so RT3_F_NEE_PUNCTUAL alone is then flags = 0. */
+#define RT3_F_NEE_PUNCTUAL 64u
 
 /* src/renderer/mod.rs:47-63 == shaders/include/datatypes.slang:28-43.  304 bytes, 16-byte aligned, column-major
  * matrices.  Offsets 0,64,128,192,256,264,268,272,276,280,284,288,296. */
@@ -252,6 +256,52 @@ int rt3_scene_set_instances(rt3_ctx *ctx, const rt3_instance *instances, uint32_
  * it must be the instance count of the built structure (1 when no instances were set) or 0, else RT3_E_STATE.  Borrowed for the call; the
  * device table (64 B per instance) is uploaded when the matrices or the structure changed. */
 int rt3_scene_set_prev_transforms(rt3_ctx *ctx, const float *transforms /* n x 16, column-major */, uint32_t n);
+/* ---- punctual lights (glTF KHR_lights_punctual): point, spot and directional lights, sampled by next-event estimation under
+ *      RT3_F_NEE_PUNCTUAL.  DESIGN.md section 4k.
+ *      A light is 64 bytes, in world space.  `intensity` is colour x intensity in W/sr (point, spot) or W/m^2 (directional): no 683 lm/W and
+ *      no x12 is applied.  `direction` is the way the light shines and need not be of unit length (it is normalised on the device).
+ *      range <= 0 means unlimited (glTF: undefined).
+ *      rt3_scene_set_lights replaces the list; (NULL, 0) forgets it.  RT3_E_INVALID, with nothing changed, for an unknown type, a value that
+ *      is not finite, a negative intensity component, a zero direction on a spot or directional light, or cone angles outside
+ *      0 <= inner < outer <= pi/2.  Borrowed for the call.  The acceleration structure does not become stale and no build reads the lights;
+ *      only the light table is remade before the next frame that samples it.  rt3_scene_set_geometry does not reset the lights: they belong
+ *      to the world, not to a mesh.  rt3_light_info / rt3_light_download keep reporting the emitter triangles alone.
+ *      The estimator: a light is a path vertex.  With the flag, a non-empty list and B > 1, every vertex b <= B-2 picks ONE entry of the
+ *      light table with the draw of RNG dim 5 (the rule and the dim of RT3_F_NEE_EMISSIVE).  The table holds
+ *        RT3_F_NEE_PUNCTUAL alone         : the punctual lights (emission keeps weight 1 where a BSDF-sampled ray hits it)
+ *        with RT3_F_NEE_EMISSIVE          : the emitter triangles followed by the punctual lights, under one CDF
+ *        RT3_F_NEE_EMISSIVE alone         : the emitter table as without this call, bit for bit
+ *      and is remade when the combination changes.  Selection masses are in the emitters' unit, power / pi: a triangle has
+ *      area x luminance(12 emission), a point or spot light 4 luminance(I) (the cone is ignored), a directional light luminance(E) R^2 with R
+ *      half the diagonal of the box of the built world's triangles (the box every root box encloses: the same in both instance modes and
+ *      every node layout; 0 for a world without triangles).  A light of zero mass is never sampled; p_sel is the realised mass / 2^23.
+ *      At the vertex x with shading normal N (after face-forward), BSDF f (albedo / pi, or the layered BSDF under RT3_F_SPECULAR) and
+ *      throughput T:
+ *        point / spot : wv = P - x, d^2 = wv.wv, wl = wv / d, cs = N.wl; nothing unless d^2 > 0 and cs > 0.  I' = I cone window, cone = 1 for a
+ *                       point light and c^2 for a spot, c = clamp((-wl.axis) a + o, 0, 1), a = 1 / max(0.001, cos inner - cos outer),
+ *                       o = -cos outer a (glTF's recommended form); window = clamp(1 - (d / range)^4, 0, 1) when range > 0, else 1.
+ *                       contribution = T f cs I' / (d^2 p_sel) behind a shadow ray (x, wl) that ends at d (1 - 2^-10).
+ *        directional  : wl = -axis, contribution = T f cs E / p_sel behind a shadow ray to RT3_BACKGROUND_DEPTH.
+ *      There is no MIS weight (a BSDF-sampled ray never hits a delta light); a zero contribution emits no shadow ray.
+ *      rt3_light_masses: the selection masses, in CDF units, of the table that flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL) samples:
+ *      *n_emitters entries for the emitter triangles, then *n_punctual for the lights in call order (both 0 when the combination samples
+ *      nothing); `mass` may be NULL, else it holds n_emitters + n_punctual words.  RT3_E_STATE where rt3_light_info returns it. ---- */
+#define RT3_LIGHT_POINT 0u
+#define RT3_LIGHT_SPOT 1u
+#define RT3_LIGHT_DIRECTIONAL 2u
+typedef struct rt3_punctual_light {
+    uint32_t type;
+    float range;                  /* <= 0: unlimited */
+    float inner_cone, outer_cone; /* radians, spot only: 0 <= inner < outer <= pi/2 */
+    float position[3];            /* point, spot */
+    float _pad0;
+    float direction[3];           /* spot, directional */
+    float _pad1;
+    float intensity[3];           /* colour x intensity */
+    float _pad2;
+} rt3_punctual_light;
+int rt3_scene_set_lights(rt3_ctx *ctx, const rt3_punctual_light *lights, uint32_t n);
+int rt3_light_masses(rt3_ctx *ctx, uint32_t flags, uint32_t *n_emitters, uint32_t *n_punctual, uint32_t *mass);
 /* ---- previous vertex positions: what lets the "motion" pass (below) follow a mesh that rt3_scene_update_vertices deforms (skinning, cloth,
  *      morph targets).  DESIGN.md section 4i.
  *      rt3_scene_snapshot_vertices: the positions the vertex buffer holds now become "the previous frame's".  A device-side copy on the
@@ -506,6 +556,9 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      roughness, metalness), read from the shading tables of the current acceleration structure in either instance mode: RT3_E_STATE
  *      without a built, current structure; RT3_E_INVALID, before anything is launched, if a row's primitive id is not below the number
  *      of flattened primitives.
+ *      30 the punctual-light function of RT3_F_NEE_PUNCTUAL (light index as u32, P xyz, N xyz -> wl xyz, shadow-range end, cs = N.wl, I' rgb) for
+ *      the lights of the context, from their device records (unit directions made on the device); I' is I cone window for a point or spot
+ *      light (everything zero when d = 0) and E for a directional one.  RT3_E_INVALID for an index the list does not have.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

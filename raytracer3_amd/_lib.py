@@ -18,6 +18,9 @@ BACKGROUND_DEPTH = 100000.0
 FORMAT_R32_SFLOAT, FORMAT_R32G32B32A32_SFLOAT, FORMAT_R32G32B32A32_UINT, FORMAT_R8G8B8A8_UNORM, FORMAT_R16_UINT = 100, 109, 107, 37, 74
 F_NEE_SKY, F_BLUENOISE, F_SPECULAR, F_FACEFORWARD, F_PROBE_RADIANCE = 1, 2, 4, 8, 16
 F_NEE_EMISSIVE = 32  # next-event estimation + MIS to emissive triangles; off by default
+F_NEE_PUNCTUAL = 64  # next-event estimation to the punctual lights of rt3_scene_set_lights; off by default
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2
+SELFTEST_LIGHT = 30  # rt3_selftest_eval op: {light index (u32), P, N} -> {wl, range end, cs, I'} (8 words), the punctual-light function
 OPT_BATCH_SPP, OPT_PROFILE, OPT_COUNT_TRAVERSAL, OPT_EXTEND_VARIANT, OPT_LEAF_SIZE, OPT_NODE_WIDTH, OPT_NODE_QUANT = 1, 2, 3, 4, 5, 6, 7
 OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
@@ -41,6 +44,7 @@ EXPORTS = [
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
+    "rt3_scene_set_lights", "rt3_light_masses",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
@@ -180,6 +184,8 @@ def load():
         "rt3_temporal_set_prev_view": (i32, [vp, vp, sz]),
         "rt3_temporal_set_params": (i32, [vp, C.POINTER(TemporalParams)]),
         "rt3_scene_set_prev_transforms": (i32, [vp, vp, u32]),
+        "rt3_scene_set_lights": (i32, [vp, vp, u32]),
+        "rt3_light_masses": (i32, [vp, u32, pu32, pu32, vp]),
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),

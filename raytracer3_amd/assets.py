@@ -13,6 +13,7 @@ cache are raster-/bevy-specific and out of scope.
 from __future__ import annotations
 
 import json
+import math
 import struct
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -37,6 +38,39 @@ MATERIAL_TEXTURES_DTYPE = np.dtype(
     [("metallic_roughness_texture", "<i4"), ("normal_texture", "<i4"), ("emissive_texture", "<i4"), ("normal_scale", "<f4")]
 )
 assert MATERIAL_TEXTURES_DTYPE.itemsize == 16
+# rt3_punctual_light (include/rt3.h): a point, spot or directional light of KHR_lights_punctual, in world space
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2
+LIGHT_DTYPE = np.dtype(
+    [
+        ("type", "<u4"),
+        ("range", "<f4"),  # <= 0: unlimited
+        ("inner_cone", "<f4"),
+        ("outer_cone", "<f4"),
+        ("position", "<f4", (3,)),
+        ("_pad0", "<f4"),
+        ("direction", "<f4", (3,)),  # the way the light shines
+        ("_pad1", "<f4"),
+        ("intensity", "<f4", (3,)),  # colour x intensity: W/sr (point, spot), W/m^2 (directional)
+        ("_pad2", "<f4"),
+    ]
+)
+assert LIGHT_DTYPE.itemsize == 64
+
+
+def make_light(type, intensity, position=(0, 0, 0), direction=(0, 0, -1), range=0.0, inner_cone=0.0, outer_cone=math.pi / 4):
+    """one LIGHT_DTYPE record"""
+    l = np.zeros((), LIGHT_DTYPE)
+    l["type"], l["range"], l["inner_cone"], l["outer_cone"] = type, range, inner_cone, outer_cone
+    l["position"], l["direction"], l["intensity"] = position, direction, intensity
+    return l
+
+
+def lights_array(records) -> np.ndarray:
+    """(l,) LIGHT_DTYPE from a sequence of make_light records"""
+    out = np.zeros(len(records), LIGHT_DTYPE)
+    for k, r in enumerate(records):
+        out[k] = r
+    return out
 
 
 def no_material_textures(n: int) -> np.ndarray:
@@ -77,8 +111,10 @@ class Mesh:
     textures: list = field(default_factory=list)  # base-colour textures: (h, w, 4) uint8, sRGB-encoded colour
     alpha_cutoffs: np.ndarray = None  # (g,) float32 alpha cutoff per geometry (rt3_scene_set_alpha_cutoffs); None -> zeros (all opaque)
     material_textures: np.ndarray = None  # (g,) MATERIAL_TEXTURES_DTYPE (rt3_scene_set_material_textures); None -> no texture anywhere
+    lights: np.ndarray = None  # (l,) LIGHT_DTYPE punctual lights (rt3_scene_set_lights); None -> none
 
     def __post_init__(self):
+        self.lights = np.ascontiguousarray(np.zeros(0, LIGHT_DTYPE) if self.lights is None else self.lights, LIGHT_DTYPE).reshape(-1)
         if self.material_textures is None:
             self.material_textures = no_material_textures(len(self.geometries))
         self.material_textures = np.ascontiguousarray(self.material_textures, MATERIAL_TEXTURES_DTYPE).reshape(len(self.geometries))
@@ -154,7 +190,8 @@ _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
 
 
 def write_glb(path, mesh: Mesh) -> None:
-    """One glTF mesh+node per geometry, identity transforms, u32 indices, one material per geometry."""
+    """One glTF mesh+node per geometry, identity transforms, u32 indices, one material per geometry; one node per punctual light
+    (KHR_lights_punctual: translation, and the rotation that takes -z to the light's direction)."""
     bin_parts, views, accessors, meshes, nodes, materials = [], [], [], [], [], []
     off = 0
 
@@ -208,6 +245,27 @@ def write_glb(path, mesh: Mesh) -> None:
         meshes.append({"name": mesh.names[gi] if gi < len(mesh.names) else f"g{gi}",
                        "primitives": [{"attributes": {"POSITION": acc[0], "NORMAL": acc[1], "TEXCOORD_0": acc[2]}, "indices": ia, "material": gi}]})
         nodes.append({"mesh": gi})
+    gl_lights = []
+    for li, l in enumerate(mesh.lights):
+        I = np.asarray(l["intensity"], np.float64)
+        top = float(I.max())
+        kind = ("point", "spot", "directional")[int(l["type"])]
+        gl = {"type": kind, "color": [float(x / top) for x in I] if top > 0 else [0.0, 0.0, 0.0], "intensity": top}
+        if float(l["range"]) > 0.0 and kind != "directional":
+            gl["range"] = float(l["range"])
+        if kind == "spot":
+            gl["spot"] = {"innerConeAngle": float(l["inner_cone"]), "outerConeAngle": float(l["outer_cone"])}
+        node = {"name": f"light{li}", "extensions": {"KHR_lights_punctual": {"light": li}}}
+        if kind != "directional":
+            node["translation"] = [float(x) for x in l["position"]]
+        if kind != "point":  # the shortest rotation from -z to d: q = (cross(-z, d), 1 + dot(-z, d)), normalised
+            d = np.asarray(l["direction"], np.float64)
+            d = d / np.linalg.norm(d)
+            q = np.array([d[1], -d[0], 0.0, 1.0 - d[2]])
+            q = q / np.linalg.norm(q) if np.linalg.norm(q) > 1e-12 else np.array([1.0, 0.0, 0.0, 0.0])  # d = +z: half a turn about x
+            node["rotation"] = [float(x) for x in q]
+        gl_lights.append(gl)
+        nodes.append(node)
     images, textures = [], []
     for ti, tex in enumerate(mesh.textures):  # embedded PNG (lossless), one glTF texture per image
         import io
@@ -227,6 +285,9 @@ def write_glb(path, mesh: Mesh) -> None:
     }
     if images:
         doc["images"], doc["textures"] = images, textures
+    if gl_lights:
+        doc["extensionsUsed"] = ["KHR_lights_punctual"]
+        doc["extensions"] = {"KHR_lights_punctual": {"lights": gl_lights}}
     js = json.dumps(doc, separators=(",", ":")).encode()
     js += b" " * ((-len(js)) % 4)
     blob = b"".join(bin_parts)
@@ -300,10 +361,21 @@ class GltfMeshLoader:
 
         mb = MeshBuilder()
         mats = doc.get("materials", [])
+        gl_lights = doc.get("extensions", {}).get("KHR_lights_punctual", {}).get("lights", [])
+        lights = []
 
         def visit(ni, parent):
             node = doc["nodes"][ni]
             m = parent @ _node_matrix(node)
+            li = node.get("extensions", {}).get("KHR_lights_punctual", {}).get("light")
+            if li is not None:  # baked like the meshes: position M (0, 0, 0, 1), direction normalise(M3 (0, 0, -1)); scale leaves the intensity alone
+                gl = gl_lights[li]
+                kind = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL}[gl["type"]]
+                d = m[:3, :3] @ np.array([0.0, 0.0, -1.0])
+                spot = gl.get("spot", {})
+                lights.append(make_light(kind, np.array(gl.get("color", [1, 1, 1]), np.float64) * gl.get("intensity", 1.0), m[:3, 3], d / np.linalg.norm(d),
+                                         0.0 if kind == LIGHT_DIRECTIONAL else gl.get("range", 0.0), spot.get("innerConeAngle", 0.0),
+                                         spot.get("outerConeAngle", math.pi / 4)))
             if "mesh" in node:
                 gm = doc["meshes"][node["mesh"]]
                 nm = np.linalg.inv(m[:3, :3]).T
@@ -356,6 +428,7 @@ class GltfMeshLoader:
         for root in scene["nodes"]:
             visit(root, np.eye(4))
         mesh = mb.build()
+        mesh.lights = lights_array(lights)
         # textures -> images (embedded PNG / JPEG, decoded by Pillow); Material.texture_offset indexes doc["textures"]
         for tex in doc.get("textures", []):
             img = doc["images"][tex["source"]]

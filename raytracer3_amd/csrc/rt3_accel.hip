@@ -184,9 +184,18 @@ namespace rt3 {
 
 // The emitter table (RT3_F_NEE_EMISSIVE, rt3_lights.hip) of the current structure, remade when a build, refit or import has happened since.  The
 // host walks only the flattened geometries (flatten_world's list) to find the emissive ones; the table itself is made on the GPU.
-int ensure_lights(rt3_ctx* c) {
+// With RT3_F_NEE_PUNCTUAL in `combo` the punctual lights follow the emitters; without RT3_F_NEE_EMISSIVE no triangle
+// is an entry (geom_base all kMiss: emission keeps weight 1).  One table is kept, remade when the structure, the lights or the pair changes.
+// A directional light's mass takes its R from the box of the flattened world's triangles, found on the device: the same in every layout
+// and both instance modes.
+int ensure_lights(rt3_ctx* c, uint32_t combo) {
     if (int r = check_accel_current(c)) return r;
-    if (c->accel.lights.stamp == c->accel.stamp) return RT3_OK;
+    combo &= RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL;
+    const bool with_emit = (combo & RT3_F_NEE_EMISSIVE) != 0u;
+    const bool with_punct = (combo & RT3_F_NEE_PUNCTUAL) != 0u && !c->scene.lights.empty();
+    if (!with_punct) combo &= ~RT3_F_NEE_PUNCTUAL;  // no lights: the table of the other flag alone, whatever the list's stamp
+    LightTable& lt = c->accel.lights;
+    if (lt.stamp == c->accel.stamp && lt.combo == combo && (!with_punct || lt.lights_stamp == c->scene.lights_stamp)) return RT3_OK;
     std::vector<uint32_t> geom_base, eg_geom, eg_first;
     uint64_t n = 0;
     for (const Placed& p : c->accel.placed) {
@@ -194,7 +203,7 @@ int ensure_lights(rt3_ctx* c) {
         const bool masked = any_cutoff(c) && c->scene.h_cutoffs[p.geom] > 0.0f;  // left out: its points may be cut away
         // an emissive texture scales the radiance point by point: left out like a masked geometry
         const bool textured = any_mat_tex(c) && c->scene.h_mat_tex[p.geom].emissive_texture >= 0;
-        const bool emissive = (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked && !textured;
+        const bool emissive = with_emit && (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked && !textured;
         geom_base.push_back(emissive ? (uint32_t)n : kMiss);
         if (emissive) {
             eg_geom.push_back((uint32_t)(geom_base.size() - 1));
@@ -203,9 +212,14 @@ int ensure_lights(rt3_ctx* c) {
         }
     }
     HIPC(c, hipSetDevice(c->device));
-    const hipError_t e = lights_build(c->stream, world_tables(c), geom_base, eg_geom, eg_first, (uint32_t)n, &c->accel.lights);
+    if (n + c->scene.lights.size() > 0x7FFFFFFFull) return fail(c, RT3_E_INVALID, "light table: too many entries");
+    const hipError_t e = lights_build(c->stream, world_tables(c), geom_base, eg_geom, eg_first, (uint32_t)n, &lt,
+                                      with_punct ? reinterpret_cast<const float*>(c->scene.lights.data()) : nullptr,
+                                      with_punct ? (uint32_t)c->scene.lights.size() : 0u, c->accel.n_flat_prims);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("emitter table: ") + hipGetErrorString(e));
-    c->accel.lights.stamp = c->accel.stamp;
+    lt.stamp = c->accel.stamp;
+    lt.combo = combo;
+    lt.lights_stamp = c->scene.lights_stamp;
     return RT3_OK;
 }
 
@@ -913,7 +927,7 @@ int rt3_light_info(rt3_ctx* c, uint32_t* n_emitters, uint64_t* cdf_total) {
 int rt3_light_download(rt3_ctx* c, uint32_t* prim, float* area, uint32_t* mass) {
     if (!c) return RT3_E_INVALID;
     if (int r = ensure_lights(c)) return r;
-    const LightTable& t = c->accel.lights;
+    const LightTable& t = c->accel.lights;  // (the table of RT3_F_NEE_EMISSIVE alone: emitters only)
     if (!t.n) return RT3_OK;
     if (prim) HIPC(c, hipMemcpy(prim, t.prim.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
     if (area) HIPC(c, hipMemcpy(area, t.area.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
@@ -921,6 +935,20 @@ int rt3_light_download(rt3_ctx* c, uint32_t* prim, float* area, uint32_t* mass) 
         HIPC(c, hipMemcpy(mass, t.cdf.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
         for (uint32_t k = t.n - 1; k > 0; k--) mass[k] -= mass[k - 1];  // inclusive CDF -> masses
     }
+    return RT3_OK;
+}
+
+int rt3_light_masses(rt3_ctx* c, uint32_t flags, uint32_t* n_emitters, uint32_t* n_punctual, uint32_t* mass) {
+    if (!c) return RT3_E_INVALID;
+    const uint32_t combo = flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL);
+    if (int r = ensure_lights(c, combo ? combo : RT3_F_NEE_EMISSIVE)) return r;  // (no flag: nothing is sampled, but the state is still checked)
+    const LightTable& t = c->accel.lights;
+    const bool any = combo != 0u && t.n != 0u;
+    if (n_emitters) *n_emitters = any ? t.n_emit : 0u;
+    if (n_punctual) *n_punctual = any ? t.n_punct : 0u;
+    if (!any || !mass) return RT3_OK;
+    HIPC(c, hipMemcpy(mass, t.cdf.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t k = t.n - 1; k > 0; k--) mass[k] -= mass[k - 1];  // inclusive CDF -> masses
     return RT3_OK;
 }
 

@@ -19,7 +19,8 @@ using namespace rt3;
 
 static_assert(sizeof(rt3_gconst) == 304 && sizeof(GConstDev) == 304, "GConst is 304 bytes (renderer/mod.rs:47-63)");
 static_assert(sizeof(rt3_geometry_info) == 64, "geometry info is 64 bytes");
-static_assert(RT3_F_NEE_SKY == RT3_FLAG_NEE_SKY && RT3_F_BLUENOISE == RT3_FLAG_BLUENOISE && RT3_F_FACEFORWARD == RT3_FLAG_FACEFORWARD && RT3_F_SPECULAR == RT3_FLAG_SPECULAR && RT3_F_PROBE_RADIANCE == RT3_FLAG_PROBE_RADIANCE && RT3_F_NEE_EMISSIVE == RT3_FLAG_NEE_EMISSIVE, "flags");
+static_assert(RT3_F_NEE_SKY == RT3_FLAG_NEE_SKY && RT3_F_BLUENOISE == RT3_FLAG_BLUENOISE && RT3_F_FACEFORWARD == RT3_FLAG_FACEFORWARD && RT3_F_SPECULAR == RT3_FLAG_SPECULAR && RT3_F_PROBE_RADIANCE == RT3_FLAG_PROBE_RADIANCE && RT3_F_NEE_EMISSIVE == RT3_FLAG_NEE_EMISSIVE && RT3_F_NEE_PUNCTUAL == RT3_FLAG_NEE_PUNCTUAL, "flags");
+static_assert(sizeof(rt3_punctual_light) == 64, "rt3_punctual_light is four float4 to the device");
 
 static thread_local std::string g_create_error;
 
@@ -364,6 +365,12 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
             if (rows[3 * (size_t)i] >= c->accel.n_flat_prims)
                 return fail(c, RT3_E_INVALID, "selftest: hit_info row " + std::to_string(i) + " names a primitive the flattened world does not have");
     }
+    if (op == 30) {  // the light function reads the context's lights: nothing is launched for an index the list does not have
+        const uint32_t* rows = static_cast<const uint32_t*>(in);
+        for (uint32_t i = 0; i < n; i++)
+            if (rows[7 * (size_t)i] >= c->scene.lights.size())
+                return fail(c, RT3_E_INVALID, "selftest: light row " + std::to_string(i) + " names a light the context does not have");
+    }
     if (n == 0) return RT3_OK;
     HIPC(c, hipSetDevice(c->device));
     if (op == 27 || op == 29)
@@ -372,8 +379,14 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     HIPC(c, d_in.alloc_bytes((size_t)n * iw * 4));
     HIPC(c, d_out.alloc_bytes((size_t)n * ow * 4));
     hipError_t e = hipMemcpy(d_in.get(), in, (size_t)n * iw * 4, hipMemcpyHostToDevice);
+    DevBuf<float4> d_lights;
+    if (op == 30) {
+        HIPC(c, d_lights.alloc_bytes(c->scene.lights.size() * 64));
+        if (e == hipSuccess) e = hipMemcpy(d_lights.get(), c->scene.lights.data(), c->scene.lights.size() * 64, hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) {
-        launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
+        if (op == 30) launch_selftest_light(c->stream, d_lights.get(), (uint32_t)c->scene.lights.size(), d_in.get(), n, d_out.get());
+        else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), (size_t)n * ow * 4, hipMemcpyDeviceToHost);

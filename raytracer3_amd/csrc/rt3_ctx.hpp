@@ -141,6 +141,10 @@ struct rt3_ctx {
         std::vector<rt3_instance> h_instances;   // empty = one identity instance of every geometry
         // the previous frame's instance matrices, n x 16 column-major (rt3_scene_set_prev_transforms; empty = every instance unmoved)
         std::vector<float> prev_transforms;
+        // punctual lights (rt3_scene_set_lights), as validated; lights_stamp is bumped by every successful call, and is
+        // all that changes: the acceleration structure stays as it is
+        std::vector<rt3_punctual_light> lights;
+        uint64_t lights_stamp = 1;
         rt3::DevBuf<uint2> d_sky;  // 8-byte texels {RGB9E5, pdf_uv} in 4 x 4 tiles
         rt3::DevBuf<float> d_cdf_marg;
         rt3::DevBuf<uint32_t> d_sky_alias, d_guide_marg;
@@ -182,7 +186,7 @@ struct rt3_ctx {
         bool stale = false;     // vertices updated since the structure was built or refitted: nothing traces it until a refit or build
         uint64_t topo_gen = 0;  // scene.topo_gen of the last successful rt3_accel_build
         uint64_t stamp = 0;     // bumped by every successful rt3_accel_build / rt3_accel_refit / rt3_accel_import
-        rt3::LightTable lights; // RT3_F_NEE_EMISSIVE: built lazily for `stamp` (ensure_lights)
+        rt3::LightTable lights; // RT3_F_NEE_EMISSIVE / RT3_F_NEE_PUNCTUAL: built lazily for `stamp`, the light list and the flag pair (ensure_lights)
         // refit plans (rt3_refit.hip), made on the first refit after a build or import: one per tree (instance mode 1: one per bottom tree)
         bool refit_planned = false;
         std::vector<rt3::RefitTree> refit_trees;
@@ -335,7 +339,7 @@ GeomTables world_tables(const rt3_ctx* c);
 // the alpha-mask tables of a traversal launch over the current structure: empty (table null) without masked triangles.  The texture atlas
 // must be synchronised (sync_textures) first.
 AlphaDev alpha_dev(const rt3_ctx* c);
-int ensure_lights(rt3_ctx* c);
+int ensure_lights(rt3_ctx* c, uint32_t combo = RT3_F_NEE_EMISSIVE);  // combo: flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL)
 // RT3_OPT_SHADOW_EXIT_TABLE changed: the table of a built, current structure is refilled (or switched off) now
 int exit_table_update(rt3_ctx* c);
 // what the counters measured is no longer what the launches see (a new sky): they start again

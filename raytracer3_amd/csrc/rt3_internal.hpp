@@ -17,6 +17,7 @@
 #define RT3_FLAG_FACEFORWARD 8u
 #define RT3_FLAG_PROBE_RADIANCE 16u
 #define RT3_FLAG_NEE_EMISSIVE 32u
+#define RT3_FLAG_NEE_PUNCTUAL 64u
 
 namespace rt3 {
 
@@ -101,7 +102,7 @@ inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks) {
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
-void launch_shade(hipStream_t st, bool first, ShadeLaunch L);
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false);  // punct: L.lights holds punctual records
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,
@@ -405,7 +406,12 @@ struct LightTable {
     DevBuf<float> area;
     DevBuf<char> scratch;                     // grow-only: power, quantised power and its scan, the scan's temporary storage
     uint32_t n = 0, n_guide = 0, guide_shift = 0, total = 0;  // total: cdf[n - 1] (2^23, or 0 when no emitter has power)
+    // RT3_F_NEE_PUNCTUAL: of the n entries the first n_emit are emitter triangles, the last n_punct punctual lights
+    // (prim = kMiss, area = 1, so that their record's p_sel / area is p_sel)
+    uint32_t n_emit = 0, n_punct = 0;
     uint64_t stamp = 0;                       // the acceleration-structure stamp the table was built for (0 = none)
+    uint64_t lights_stamp = 0;                // the punctual-light list it was built for (rt3_ctx::Scene::lights_stamp)
+    uint32_t combo = 0;                       // flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL) it was built for
     LightsDev dev() const {
         LightsDev d;
         d.rec = rec.get(); d.cdf = cdf.get(); d.guide = guide.get(); d.geom_base = geom_base.get();
@@ -415,8 +421,13 @@ struct LightTable {
 };
 // geom_base: per flattened geometry its first emitter or kMiss (host table, n_flat_geoms entries); eg_geom / eg_first: the emissive flattened
 // geometries and their first emitter (n_eg entries); n: emitters.  Reads back nothing but the CDF's last word (into *total).
+// punct / n_punct: the punctual lights to append (host, rt3_punctual_light's 16 words each); n_world_prims: the primitives the tables `t`
+// cover, whose box gives the R of a directional light's mass (read only when there are punctual lights).
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
-                        const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out);
+                        const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out, const float* punct = nullptr, uint32_t n_punct = 0,
+                        uint32_t n_world_prims = 0);
+// self-test op 30: rows {light index, P, N} -> {wl, range end, cs, I'} from punctual records made of `lights` (n_lights x 16 words, device)
+void launch_selftest_light(hipStream_t st, const float4* lights, uint32_t n_lights, const uint32_t* in, uint32_t n, uint32_t* out);
 
 // "denoise" pass (rt3_denoise.hip).  Scratch: two guide records and two signal images of W x H float4, carved from the
 // context's grow-only denoise buffer.  Stages in stream order: prepare, variance, `iterations` x atrous (iteration 0, 1, ...), finish.

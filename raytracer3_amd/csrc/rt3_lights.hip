@@ -14,6 +14,7 @@
 #include "rt3_bvh_device.hpp"
 #include "rt3_internal.hpp"
 #include "rt3_math.hpp"
+#include "rt3_punctual.hpp"
 #include "rt3_surface.hpp"
 
 namespace rt3 {
@@ -57,6 +58,103 @@ __global__ void k_emit_prims(const float* __restrict__ verts, const uint32_t* __
     }
 }
 
+// RT3_F_NEE_PUNCTUAL: the record of one punctual light (rt3_punctual.hpp) from the 64 bytes the host validated,
+// and its selection mass in the emitters' unit, power / pi: 4 luminance(I) for a point or spot light (the cone is ignored), luminance(E) R^2
+// for a directional one.  The unit axis is made here, on the device.
+// R of a directional light is half the diagonal of the box of the world's triangles: every flattened primitive through fetch_triangle
+// (flattening's own expression, so the same box in both instance modes and whatever the node layout), min / max by ordered-uint atomics
+// (exact, so the same answer whatever the order).  bounds[0..2] min, [3..5] max; an empty world leaves min > max and R = 0.
+__global__ void k_world_bounds(const float* __restrict__ verts, const uint32_t* __restrict__ indices, const FlatGeomDev* __restrict__ geoms,
+                               const uint32_t* __restrict__ prim_geom, const uint32_t* __restrict__ first_prim, uint32_t n_prims, uint32_t* __restrict__ bounds) {
+    __shared__ uint32_t s_b[6];
+    if (threadIdx.x < 3) s_b[threadIdx.x] = 0xFFFFFFFFu;
+    else if (threadIdx.x < 6) s_b[threadIdx.x] = 0u;
+    __syncthreads();
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_prims; p += gridDim.x * blockDim.x) {
+        V3 a, b, c;
+        fetch_triangle(verts, indices, geoms, prim_geom, first_prim, p, a, b, c);
+        const float lo[3] = {fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z))};
+        const float hi[3] = {fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z))};
+        for (int k = 0; k < 3; k++) {
+            atomicMin(&s_b[k], float_to_ordered(lo[k]));
+            atomicMax(&s_b[3 + k], float_to_ordered(hi[k]));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) atomicMin(&bounds[threadIdx.x], s_b[threadIdx.x]);
+    else if (threadIdx.x < 6) atomicMax(&bounds[threadIdx.x], s_b[threadIdx.x]);
+}
+__device__ float world_radius2(const uint32_t* __restrict__ bounds) {
+    double d2 = 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double e = (double)ordered_to_float(bounds[3 + k]) - (double)ordered_to_float(bounds[k]);
+        if (!(e >= 0.0)) return 0.0f;
+        d2 += e * e;
+    }
+    const float r2 = (float)(0.25 * d2);
+    return r2 <= kFloatMax ? r2 : 0.0f;
+}
+struct PunctRecord {
+    float4 r[4];
+    float power;
+};
+__device__ PunctRecord punct_record(const float4* __restrict__ in, float radius2) {
+    const float4 h = in[0], P = in[1], D = in[2], I = in[3];  // {type, range, inner, outer} {position} {direction} {intensity}
+    const uint32_t type = __float_as_uint(h.x);
+    V3 axis = v3(D.x, D.y, D.z);
+    const float len = sqrtf(dot(axis, axis));
+    axis = (type != 0u && len > 0.0f) ? axis * (1.0f / len) : v3(0.0f, 0.0f, 0.0f);
+    float ca = 0.0f, co = 1.0f;  // a point light: c = 1
+    if (type == 1u) {
+        const float cos_in = cosf(h.z), cos_out = cosf(h.w);
+        ca = 1.0f / fmaxf(0.001f, cos_in - cos_out);
+        co = -cos_out * ca;
+    }
+    const float inv_range = (type != 2u && h.y > 0.0f) ? 1.0f / h.y : 0.0f;
+    const float lum = luminance(v3(I.x, I.y, I.z));
+    PunctRecord o;
+    o.r[0] = make_float4(P.x, P.y, P.z, 0.0f);  // .w: p_sel (k_emit_cdf)
+    o.r[1] = make_float4(axis.x, axis.y, axis.z, I.x);
+    o.r[2] = make_float4(ca, co, inv_range, I.y);
+    o.r[3] = make_float4(kPunctTag + (float)type, 0.0f, 0.0f, I.z);
+    const float p = type == 2u ? lum * radius2 : 4.0f * lum;
+    o.power = (p > 0.0f && p <= kFloatMax) ? p : 0.0f;
+    return o;
+}
+__global__ void k_punct_records(const float4* __restrict__ in, uint32_t n_punct, uint32_t first, const uint32_t* __restrict__ bounds, float4* __restrict__ rec,
+                                uint32_t* __restrict__ prim_out, float* __restrict__ area_out, float* __restrict__ power, uint32_t* __restrict__ max_power) {
+    const float radius2 = world_radius2(bounds);
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n_punct; j += gridDim.x * blockDim.x) {
+        const PunctRecord o = punct_record(in + 4 * (size_t)j, radius2);
+        const size_t e = (size_t)first + j;
+        for (int k = 0; k < 4; k++) rec[4 * e + k] = o.r[k];
+        prim_out[e] = kMiss;
+        area_out[e] = 1.0f;  // k_emit_cdf's p_sel / area is then p_sel itself
+        power[e] = o.power;
+        atomicMax(max_power, __float_as_uint(o.power));
+    }
+}
+// self-test op 30
+__global__ void k_selftest_light(const float4* __restrict__ lights, uint32_t n_lights, const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = in + 7 * (size_t)i;
+    uint32_t* o = out + 8 * (size_t)i;
+    if (p[0] >= n_lights) {
+        for (int k = 0; k < 8; k++) o[k] = 0u;
+        return;
+    }
+    const PunctRecord r = punct_record(lights + 4 * (size_t)p[0], 1.0f);
+    const PunctualSample s = punctual_sample(r.r[0], r.r[1], r.r[2], r.r[3], v3(__uint_as_float(p[1]), __uint_as_float(p[2]), __uint_as_float(p[3])),
+                                             v3(__uint_as_float(p[4]), __uint_as_float(p[5]), __uint_as_float(p[6])), kEmitShadowEnd);
+    o[0] = __float_as_uint(s.wl.x); o[1] = __float_as_uint(s.wl.y); o[2] = __float_as_uint(s.wl.z);
+    o[3] = __float_as_uint(s.tmax); o[4] = __float_as_uint(s.cs);
+    o[5] = __float_as_uint(s.Ic.x); o[6] = __float_as_uint(s.Ic.y); o[7] = __float_as_uint(s.Ic.z);
+}
+void launch_selftest_light(hipStream_t st, const float4* lights, uint32_t n_lights, const uint32_t* in, uint32_t n, uint32_t* out) {
+    hipLaunchKernelGGL(k_selftest_light, dim3((n + 255) / 256), dim3(256), 0, st, lights, n_lights, in, n, out);
+}
+
 __global__ void k_emit_quant(const float* __restrict__ power, const uint32_t* __restrict__ max_power, uint32_t n, unsigned long long* __restrict__ q) {
     const double pm = (double)__uint_as_float(*max_power);
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x)
@@ -98,9 +196,9 @@ static hipError_t alloc_n(DevBuf<T>& b, size_t n) {
 }
 
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
-                        const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out) {
+                        const std::vector<uint32_t>& eg_first, uint32_t n_emit, LightTable* out, const float* punct, uint32_t n_punct, uint32_t n_world_prims) {
     out->stamp = 0;
-    out->n = out->total = 0;
+    out->n = out->total = out->n_emit = out->n_punct = 0;
     const size_t ng = geom_base.size(), neg = eg_geom.size();
     // per flattened geometry its first emitter, then the emissive geometries' {flattened index, first emitter}: a few KiB at most
     std::vector<uint32_t> small(ng + 2 * neg);
@@ -109,7 +207,9 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     std::copy(eg_first.begin(), eg_first.end(), small.begin() + ng + neg);
     RT3_TRY(alloc_n(out->geom_base, small.size()));
     if (!small.empty()) RT3_TRY(hipMemcpyAsync(out->geom_base.get(), small.data(), small.size() * 4, hipMemcpyHostToDevice, st));
-    if (n == 0 || neg == 0) {
+    if (neg == 0) n_emit = 0;
+    const uint32_t n = n_emit + n_punct;  // emitters first, then the punctual lights: one table, one CDF
+    if (n == 0) {
         RT3_TRY(hipStreamSynchronize(st));  // (the host vector goes out of scope)
         return hipSuccess;
     }
@@ -125,20 +225,31 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     RT3_TRY(alloc_n(out->guide, (size_t)cells + 1));
     // scratch: power, max word, weights, prefix, scan storage
     float* power = nullptr;
-    uint32_t* max_power = nullptr;
+    float4* punct_in = nullptr;
+    uint32_t *max_power = nullptr, *bounds = nullptr;
     unsigned long long *q = nullptr, *prefix = nullptr;
     char* scan_tmp = nullptr;
     size_t scan_bytes = 0;
     RT3_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, q, prefix, (int)n, st));
     BufLayout plan;
-    plan.add(&power, n).add(&max_power, 1).add(&q, n).add(&prefix, n).add(&scan_tmp, scan_bytes);
+    plan.add(&power, n).add(&max_power, 1).add(&q, n).add(&prefix, n).add(&scan_tmp, scan_bytes).add(&punct_in, 4 * (size_t)n_punct).add(&bounds, 6);
     RT3_TRY(out->scratch.grow_bytes(plan.bytes()));
     RT3_TRY(plan.carve(out->scratch));
     const uint32_t* d_eg_geom = out->geom_base.get() + ng;
     const uint32_t* d_eg_first = d_eg_geom + neg;
     RT3_TRY(hipMemsetAsync(max_power, 0, 4, st));
-    hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, d_eg_geom, d_eg_first, (uint32_t)neg, n,
-                       out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
+    if (n_emit)
+        hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n_emit)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, d_eg_geom, d_eg_first, (uint32_t)neg,
+                           n_emit, out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
+    if (n_punct) {
+        RT3_TRY(hipMemcpyAsync(punct_in, punct, 64 * (size_t)n_punct, hipMemcpyHostToDevice, st));
+        RT3_TRY(hipMemsetAsync(bounds, 0xFF, 12, st));  // min: beyond every ordered float; max: 0 = below every one
+        RT3_TRY(hipMemsetAsync(bounds + 3, 0, 12, st));
+        if (n_world_prims)
+            hipLaunchKernelGGL(k_world_bounds, dim3(grid_of(n_world_prims)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n_world_prims, bounds);
+        hipLaunchKernelGGL(k_punct_records, dim3(grid_of(n_punct)), dim3(256), 0, st, punct_in, n_punct, n_emit, bounds, out->rec.get(), out->prim.get(), out->area.get(),
+                           power, max_power);
+    }
     hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, power, max_power, n, q);
     RT3_TRY(hipcub::DeviceScan::InclusiveSum(scan_tmp, scan_bytes, q, prefix, (int)n, st));
     hipLaunchKernelGGL(k_emit_cdf, dim3(grid_of(n)), dim3(256), 0, st, prefix, out->area.get(), n, out->cdf.get(), out->rec.get());
@@ -148,6 +259,8 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     RT3_TRY(hipMemcpyAsync(&total, out->cdf.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
     RT3_TRY(hipStreamSynchronize(st));
     out->n = n;
+    out->n_emit = n_emit;
+    out->n_punct = n_punct;
     out->n_guide = cells;
     out->guide_shift = shift;
     out->total = total;

@@ -233,14 +233,21 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     if ((uint64_t)sb * npix > 0xFFFFFF00ull) return fail(c, RT3_E_INVALID, "batch too large");
     if (int r = ensure_work(c, (size_t)sb * npix, npix)) return r;
     const size_t S = c->work.cap;
-    const GConstDev gd = gconst_dev(g);
+    GConstDev gd = gconst_dev(g);
+    // RT3_F_NEE_PUNCTUAL without lights, or with B = 1, is the frame without the bit, bit for bit: the kernels draw 8 RNG dimensions per
+    // vertex for any flag word but 0, so the bit itself goes where it changes nothing else
+    if (c->scene.lights.empty() || B <= 1) gd.pad[0] &= ~RT3_F_NEE_PUNCTUAL;
     const bool nee = (g->pad[0] & RT3_F_NEE_SKY) && c->scene.d_sky;
     // RT3_F_NEE_EMISSIVE: only with something to sample; otherwise the frame is the flag-less one, same kernels
     // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
+    // RT3_F_NEE_PUNCTUAL (section 4k): the same, with the punctual lights as further entries of the table
     LightsDev lights{};
-    if ((g->pad[0] & RT3_F_NEE_EMISSIVE) && B > 1) {
-        if (int r = ensure_lights(c)) return r;
+    bool punct = false;
+    const uint32_t combo = g->pad[0] & (RT3_F_NEE_EMISSIVE | (c->scene.lights.empty() ? 0u : RT3_F_NEE_PUNCTUAL));
+    if (combo && B > 1) {
+        if (int r = ensure_lights(c, combo)) return r;
         lights = c->accel.lights.dev();
+        punct = lights.n != 0u && c->accel.lights.n_punct != 0u;
         if (lights.n)
             if (int r = ensure_emit_queue(c)) return r;
     }
@@ -274,7 +281,7 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
             L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
             {
                 ScopedTimer t(c, CAT_SHADE);
-                launch_shade(c->stream, bn == 0, L);
+                launch_shade(c->stream, bn == 0, L, punct);
             }
             cur ^= 1;
             if (nee) {

@@ -488,5 +488,27 @@ int rt3_scene_set_prev_transforms(rt3_ctx* c, const float* transforms, uint32_t 
     motion_tables_stale(c);
     return RT3_OK;
 }
+// Punctual lights: no build reads them and the structure stays as it is; the light table follows lights_stamp
+int rt3_scene_set_lights(rt3_ctx* c, const rt3_punctual_light* lights, uint32_t n) {
+    if (!c || (!lights && n)) return fail(c, RT3_E_INVALID, "lights NULL");
+    auto bad = [&](uint32_t i, const char* what) { return fail(c, RT3_E_INVALID, "light " + std::to_string(i) + ": " + what); };
+    for (uint32_t i = 0; i < n; i++) {
+        const rt3_punctual_light& l = lights[i];
+        if (l.type > RT3_LIGHT_DIRECTIONAL) return bad(i, "unknown type");
+        const float vals[] = {l.range, l.inner_cone, l.outer_cone, l.position[0], l.position[1], l.position[2], l.direction[0], l.direction[1], l.direction[2],
+                              l.intensity[0], l.intensity[1], l.intensity[2]};
+        for (float v : vals)
+            if (!std::isfinite(v)) return bad(i, "a value is not finite");
+        for (int k = 0; k < 3; k++)
+            if (l.intensity[k] < 0.0f) return bad(i, "negative intensity");
+        if (l.type != RT3_LIGHT_POINT && l.direction[0] == 0.0f && l.direction[1] == 0.0f && l.direction[2] == 0.0f) return bad(i, "zero direction");
+        if (l.type == RT3_LIGHT_SPOT && !(0.0f <= l.inner_cone && l.inner_cone < l.outer_cone && l.outer_cone <= 1.57079637f))  // fp32(pi / 2)
+            return bad(i, "cone angles must satisfy 0 <= inner < outer <= pi/2");
+    }
+    c->scene.lights.assign(lights, lights + n);
+    for (rt3_punctual_light& l : c->scene.lights) l._pad0 = l._pad1 = l._pad2 = 0.0f;
+    c->scene.lights_stamp++;
+    return RT3_OK;
+}
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "rt3_camera.hpp"
 #include "rt3_internal.hpp"
 #include "rt3_math.hpp"
+#include "rt3_punctual.hpp"
 #include "rt3_rng.hpp"
 #include "rt3_sky.hpp"
 #include "rt3_surface.hpp"
@@ -99,8 +100,7 @@ __device__ __forceinline__ BlockAppend3 block_append3(bool want_ext, bool want_s
     r.sh2 = lds[2 * kW1 + kWaves] + lds[2 * kW1 + wave] + (uint32_t)__popcll(m_sh2 & below);
     return r;
 }
-// the emitter shadow ray ends this far along its way to the sampled point: the emitter never occludes itself, another one in front does
-constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
+// (kEmitShadowEnd, where an emitter's or a punctual light's shadow ray ends, is rt3_punctual.hpp's)
 
 // refrence_mode.slang:28-57 for one bounce of every live path
 // GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
@@ -113,301 +113,22 @@ constexpr float kEmitShadowEnd = 0.9990234375f;  // 1 - 2^-10
 // the compiler's own choice of 93 VGPRs (4 waves with 512-thread blocks).  MAT holds up to twelve more texels and three footprints' weights
 // across the light sample: the compiler's own allocation is 94 VGPRs (116 with EMIT), above the 80 that 6 waves leave, and a 512-thread
 // block is 2 waves per SIMD, so the next step down from 6 is 4 = 128 VGPRs, which holds both without scratch.
+// PUNCT (on the EMIT instances): the table in use also holds punctual lights (RT3_F_NEE_PUNCTUAL); a record's tag
+// says which kind the draw of dim 5 picked.  Launched only when the table holds a punctual record, so every other instance keeps its code.
 constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
+// The body is rt3_shade_body.inc, included once per kernel template: the PUNCT twins are kernels of their own name, and the instances of
+// k_shade keep both their names and, being compiled from the same text with PUNCT = false, their instructions.
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
-    static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
-    __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
-    __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
-    __shared__ MatTexDev s_mats[GLDS && MAT ? kShadeGeomsLds : 1];
-    if (GLDS) {
-        const uint32_t ng = a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds;
-        const uint32_t words = ng * (uint32_t)(sizeof(ShadeGeomDev) / 4);
-        for (uint32_t k = threadIdx.x; k < words; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_geoms)[k] = reinterpret_cast<const uint32_t*>(a.sc.shade_geoms)[k];
-        if constexpr (MAT)
-            for (uint32_t k = threadIdx.x; k < ng * 4u; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_mats)[k] = reinterpret_cast<const uint32_t*>(a.sc.mat_tex)[k];
-        __syncthreads();
-    }
-    uint32_t parity = 0;
-    // the marginal sky tables (one guide word + one CDF value per row) are the first two links of every light sample's chain of
-    // dependent lookups: staged in LDS they cost ~100 cycles each instead of an L1/L2 round trip
-    constexpr uint32_t kMargRows = 2048;
-    __shared__ uint32_t s_guide_marg[kMargRows];
-    __shared__ float s_cdf_marg[kMargRows + 4];
-    const bool marg_in_lds = (a.g.pad[0] & RT3_FLAG_NEE_SKY) && a.sc.sky != nullptr && a.sc.sky_h <= kMargRows;
-    if (marg_in_lds) {
-        for (uint32_t k = threadIdx.x; k < a.sc.sky_h; k += kShadeBlock) s_guide_marg[k] = a.sc.guide_marg[k];
-        for (uint32_t k = threadIdx.x; k < a.sc.sky_h + 4u; k += kShadeBlock) s_cdf_marg[k] = a.sc.cdf_marg[k];
-        __syncthreads();
-    }
-    const float* cdf_marg = marg_in_lds ? s_cdf_marg : a.sc.cdf_marg;
-    const uint32_t* guide_marg = marg_in_lds ? s_guide_marg : a.sc.guide_marg;
-    const GConstDev& g = a.g;
-    const uint32_t flags = g.pad[0], B = g.bounces, b = a.bounce;
-    const uint32_t dims = flags ? 8u : 2u;
-    const bool nee = (flags & RT3_FLAG_NEE_SKY) && a.sc.sky != nullptr;
-    const bool bnz = (flags & RT3_FLAG_BLUENOISE) && a.sc.bluenoise != nullptr;
-    const bool spec = (flags & RT3_FLAG_SPECULAR) != 0u;
-    const size_t S = a.stride;
-    const uint32_t n = FIRST ? a.n_first : *a.in_count;
-    const uint32_t n_round = (n + (kShadeBlock - 1)) & ~(uint32_t)(kShadeBlock - 1);  // whole workgroups iterate: barriers inside
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += gridDim.x * blockDim.x) {
-        bool active = i < n;
-        uint32_t pid = 0;
-        V3 o = v3(0, 0, 0), d = v3(0, 0, 1), T = v3(1, 1, 1);
-        float t = 0.0f, pdf_b = 0.0f;
-        Surface surf;
-        surf.albedo = surf.emissive = v3(0, 0, 0);
-        surf.normal = v3(0, 0, 1);
-        surf.roughness = 1.0f;
-        surf.metalness = 0.0f;
-        uint32_t px = 0, py = 0, sample_in_batch = 0, bn = 0;
-        HitRecord hrecord;
-        hrecord.rec = make_uint4(0u, 0u, 0u, 0u);
-        hrecord.prim = 0u;
-        float hbu = 0.0f, hbv = 0.0f;
-        uint32_t htan = 0u;
-        float4 ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-        if (!FIRST && active) {  // ray records {o, pdf} + {d, path id}
-            ro = reinterpret_cast<const float4*>(a.in_rays)[i];
-            rd = reinterpret_cast<const float4*>(a.in_rays)[S + i];
-        }
-        if (active) {
-            pid = FIRST ? i : __float_as_uint(rd.w);
-            sample_in_batch = fast_div(a.npix_div, pid);
-            const uint2 pb = a.pixbn[pid - sample_in_batch * a.npix];  // pixel and its blue-noise word in one load
-            px = pb.x & 0xFFFFu;
-            py = pb.x >> 16;
-            bn = pb.y;
-        }
-        if (FIRST) {
-            if (active) {
-                size_t pi = (size_t)py * a.width + px;
-                float d0 = a.depth[pi];
-                if (d0 == kBackgroundDepth) {  // :18-21
-                    reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                    active = false;
-                } else {
-                    surf = gbuffer_unpack(a.gbuffer[pi]);  // :23
-                    primary_ray(g, px, py, o, d);          // :30
-                    t = d0;                                // :33
-                }
-            }
-        } else if (active) {
-            o = v3(ro.x, ro.y, ro.z);
-            d = v3(rd.x, rd.y, rd.z);
-            T = v3(a.in_T[i], a.in_T[S + i], a.in_T[2 * S + i]);
-            pdf_b = ro.w;
-            const float4 hrec = reinterpret_cast<const float4*>(a.in_hits)[i];
-            uint32_t prim = __float_as_uint(hrec.w);
-            if (prim == kMiss) {  // :37-40 ; sky through MIS (north_star)
-                if (nee && pdf_b > 0.0f) {
-                    float su, sv;
-                    direction_to_equirect_uv(d, su, sv);
-                    float pl;
-                    V3 rad = sky_eval_and_pdf(a.sc, su, sv, pl);
-                    float w = pdf_b / (pdf_b + pl);
-                    float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
-                    float4 lv = *Lp;
-                    *Lp = make_float4(lv.x + T.x * (rad.x * w), lv.y + T.y * (rad.y * w), lv.z + T.z * (rad.z * w), 0.0f);
-                }
-                active = false;
-            } else {
-                t = hrec.x;
-                hbu = hrec.y;
-                hbv = hrec.z;
-                hrecord = hit_fetch(a.sc, prim);  // :55, first half: the loads are issued here, used after the light-sample gathers
-                if constexpr (MAT) htan = tan_fetch(a.sc, prim);
-            }
-        }
-        bool emit_shadow = false, emit_ext = false;
-        V3 wl = v3(0, 1, 0), contrib = v3(0, 0, 0), nd = v3(0, 0, 1), Tn = T;
-        float pdf_n = 0.0f;
-        bool emit_shadow_e = false;  // EMIT: the emitter shadow ray
-        V3 wle = v3(0, 1, 0), contrib_e = v3(0, 0, 0);
-        float tmax_e = 0.0f;
-        if (active) {
-            uint32_t seed = rng_seed(px, py, g.frame);  // :25
-            uint32_t sm = a.s0 + sample_in_batch;
-            uint32_t base = (sm * B + b) * dims;
-            float u0 = uniform_float(seed, base), u1 = uniform_float(seed, base + 1);  // :43
-            if (bnz) {  // bn = bluenoise[(py % bn_h), (px % bn_w)], gathered once per pixel list (k_pixbn)
-                u0 = bluenoise_shift(u0, bn & 0xFFu);
-                u1 = bluenoise_shift(u1, (bn >> 8) & 0xFFu);
-            }
-            // the light sample first: its chain of dependent table gathers (guide -> CDF -> guide -> CDF -> texels) is then in
-            // flight while the shading record arrives and the BSDF is set up and sampled below.  Samples below the horizon
-            // of the surface (cos <= 0) are dropped before the radiance texels are fetched: those two cache lines are the
-            // expensive part of a light sample.
-            V3 rad = v3(0.0f, 0.0f, 0.0f);
-            float pl = 0.0f, cosl = 0.0f;
-            SkyPick pick;
-            pick.u = pick.v = pick.sin_theta = 0.0f;
-            pick.x = pick.y = 0;
-            if (nee) {
-                float ul0 = uniform_float(seed, base + 3), ul1 = uniform_float(seed, base + 4);
-                if (bnz) {
-                    ul0 = bluenoise_shift(ul0, (bn >> 16) & 0xFFu);
-                    ul1 = bluenoise_shift(ul1, (bn >> 24) & 0xFFu);
-                }
-                pick = sky_sample_direction(a.sc, cdf_marg, guide_marg, ul0, ul1, wl);
-            }
-            // EMIT: an emitter and a point on it for vertices 0 .. B-2 (the emission vertex b + 1 would collect); dims 5, 6, 7, no blue-noise
-            // shift.  The chain guide -> CDF -> record is issued here, beside the sky's, and used once the surface is known.
-            const bool nee_e = EMIT && b + 1u < B;
-            float4 er0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), er1 = er0, er2 = er0, er3 = er0;
-            float eu6 = 0.0f, eu7 = 0.0f;
-            if (nee_e) {
-                const uint32_t ke = (uint32_t)(uniform_float(seed, base + 5) * 8388608.0f);  // exact: the 23-bit integer uniform_float was made of
-                eu6 = uniform_float(seed, base + 6);
-                eu7 = uniform_float(seed, base + 7);
-                const float4* R = a.lights.rec + 4 * (size_t)light_find(a.lights, ke);
-                er0 = R[0];
-                er1 = R[1];
-                er2 = R[2];
-                er3 = R[3];
-            }
-            if (!FIRST) {  // :55, second half (two calls, not a selected pointer: a select would turn the LDS reads into flat loads)
-                if constexpr (MAT) {
-                    if (GLDS) surf = hit_finish<true>(a.sc, s_geoms, hrecord, hbu, hbv, s_mats, htan);
-                    else surf = hit_finish<true>(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv, a.sc.mat_tex, htan);
-                } else if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
-                else surf = hit_finish(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv);
-            }
-            V3 N = surf.normal;
-            if ((flags & RT3_FLAG_FACEFORWARD) && dot(N, d) > 0.0f) N = neg(N);
-            if (nee) {
-                cosl = dot(N, wl);
-                if (cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
-            }
-            V3 b1, b2;
-            build_orthonormal_basis(N, b1, b2);  // :44
-            V3 wi = v3(0.0f, 0.0f, 1.0f), vop = surf.albedo, wo = v3(0.0f, 0.0f, 1.0f);
-            float pdf_s = 0.0f;
-            bool valid = true;
-            Bsdf bs;
-            const bool last = b == B - 1;  // the last vertex of a path emits no extension ray (:53): its BSDF sample is never used
-            if (spec) {  // layered diffuse + GGX (brdf.slang:141-311)
-                bs = bsdf_setup(surf.albedo, surf.roughness, surf.metalness);
-                wo = v3(-(d.x * b1.x + d.y * b1.y + d.z * b1.z), -(d.x * b2.x + d.y * b2.y + d.z * b2.z), -(d.x * N.x + d.y * N.y + d.z * N.z));
-                if (!last) {
-                    float u2 = uniform_float(seed, base + 2);
-                    valid = bsdf_sample(bs, wo, u0, u1, u2, wi, vop, pdf_s);
-                }
-            } else if (!last) {
-                wi = diffuse_sample(u0, u1);  // :45
-                pdf_s = wi.z * kInvPi;
-            }
-            o = v3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);  // :47
-            // :50 radiance += ray_color * emissive.  x + (+0) == x exactly, so non-emitters skip the read-modify-write.
-            if (FIRST) {  // L starts at 0 and T = 1: 0 + 1 * e == e
-                reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(T.x * surf.emissive.x, T.y * surf.emissive.y, T.z * surf.emissive.z, 0.0f);
-            } else if (surf.emissive.x != 0.0f || surf.emissive.y != 0.0f || surf.emissive.z != 0.0f) {
-                V3 le = surf.emissive;
-                if (EMIT) {  // a BSDF-sampled ray found an emitter the previous vertex also sampled directly: balance weight pdf_b / (pdf_b + p_solid)
-                    const uint32_t eb = a.lights.geom_base[hrecord.rec.w];
-                    if (eb != kMiss) {
-                        const float4* R = a.lights.rec + 4 * (size_t)(eb + (hrecord.prim - a.sc.first_prim[hrecord.rec.w]));
-                        const float pa = R[0].w;  // p_sel / area, the value the sampler divides by
-                        const float4 rn = R[3];
-                        const float dl = sqrtf(dot(d, d)), cle = fabsf(rn.x * d.x + rn.y * d.y + rn.z * d.z) / dl, dist = t * dl;
-                        if (pa > 0.0f && cle > 0.0f) {
-                            const float ps = pa * (dist * dist) / cle;
-                            le = le * (pdf_b / (pdf_b + ps));
-                        }
-                    }
-                }
-                float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
-                float4 lv = *Lp;
-                *Lp = make_float4(lv.x + T.x * le.x, lv.y + T.y * le.y, lv.z + T.z * le.z, 0.0f);
-            }
-            if (nee_e && er0.w > 0.0f) {  // the emitter sample: p = A + b1 E1 + b2 E2 with b0 = 1 - sqrt(u6), b1 = u7 sqrt(u6)
-                const float su = sqrtf(eu6), lb1 = eu7 * su, lb2 = su - lb1;
-                const V3 pe = v3(er0.x + er1.x * lb1 + er2.x * lb2, er0.y + er1.y * lb1 + er2.y * lb2, er0.z + er1.z * lb1 + er2.z * lb2);
-                const V3 wv = pe - o;
-                const float dist2 = dot(wv, wv), dist = sqrtf(dist2);
-                if (dist2 > 0.0f) {
-                    wle = wv * (1.0f / dist);
-                    const float cs = dot(N, wle), cle = fabsf(er3.x * wle.x + er3.y * wle.y + er3.z * wle.z);  // emission is two-sided
-                    if (cs > 0.0f && cle > 0.0f) {
-                        const float ps = er0.w * dist2 / cle;  // p_sel / area * dist^2 / |cos_l|: solid-angle density of the sample
-                        V3 fv;
-                        float scale;
-                        if (spec) {  // f cos Le / (p_solid + p_bsdf) == f cos Le w / p_solid, balance heuristic
-                            float pproj;
-                            bsdf_eval(bs, wo, v3(dot(wle, b1), dot(wle, b2), cs), fv, pproj);
-                            scale = cs / (ps + pproj * cs);
-                        } else {
-                            fv = surf.albedo;
-                            scale = (cs * kInvPi) / (ps + cs * kInvPi);
-                        }
-                        contrib_e = v3((T.x * fv.x) * (er1.w * scale), (T.y * fv.y) * (er2.w * scale), (T.z * fv.z) * (er3.w * scale));
-                        tmax_e = dist * kEmitShadowEnd;
-                        emit_shadow_e = contrib_e.x > 0.0f || contrib_e.y > 0.0f || contrib_e.z > 0.0f;
-                    }
-                }
-            }
-            if (nee) {
-                if (cosl > 0.0f && pl > 0.0f) {
-                    V3 fv;
-                    float scale;
-                    if (spec) {  // evaluate the layered BSDF towards the light; f cos / (p_light + p_bsdf)
-                        float pproj;
-                        bsdf_eval(bs, wo, v3(dot(wl, b1), dot(wl, b2), cosl), fv, pproj);
-                        float pb = pproj * cosl;
-                        scale = (b == B - 1) ? cosl / pl : cosl / (pl + pb);
-                    } else {  // diffuse: f = albedo / pi folded into the scale
-                        float pb = cosl * kInvPi;
-                        fv = surf.albedo;
-                        scale = (b == B - 1) ? (cosl * kInvPi) / pl : (cosl * kInvPi) / (pl + pb);
-                    }
-                    contrib = v3((T.x * fv.x) * (rad.x * scale), (T.y * fv.y) * (rad.y * scale), (T.z * fv.z) * (rad.z * scale));
-                    emit_shadow = true;
-                }
-            }
-            if (valid && !last) {  // an invalid specular sample (brdf.slang:227-229) ends the path
-                nd = basis_apply(b1, b2, N, wi);  // :48
-                pdf_n = pdf_s;
-                Tn = T * vop;                     // :51 value_over_pdf (= albedo for the diffuse BRDF)
-                emit_ext = true;                  // :53
-            }
-        }
-        BlockAppend slot;
-        uint32_t slot_e = 0;
-        if (EMIT) {
-            const BlockAppend3 s3 = block_append3(emit_ext, emit_shadow, emit_shadow_e, reinterpret_cast<unsigned long long*>(a.out_count), a.sh2_count, append_lds[parity]);
-            slot.ext = s3.ext;
-            slot.sh = s3.sh;
-            slot_e = s3.sh2;
-        } else {
-            slot = block_append2(emit_ext, emit_shadow, reinterpret_cast<unsigned long long*>(a.out_count), append_lds[parity]);  // out_count, sh_count: one pair
-        }
-        parity ^= 1u;
-        if (EMIT && emit_shadow_e) {  // 44 bytes: the 40-byte shadow record plus the ray's own range end
-            reinterpret_cast<float4*>(a.sh2_rays)[slot_e] = make_float4(o.x, o.y, o.z, contrib_e.x);
-            reinterpret_cast<float4*>(a.sh2_rays)[S + slot_e] = make_float4(wle.x, wle.y, wle.z, contrib_e.y);
-            reinterpret_cast<float2*>(a.sh2_contrib)[slot_e] = make_float2(contrib_e.z, __uint_as_float(pid));
-            a.sh2_tmax[slot_e] = tmax_e;
-        }
-        if (emit_shadow) {
-            const uint32_t j = slot.sh;
-            // 40 bytes per shadow ray: its range is always (kRayTMin, kBackgroundDepth), so the .w of the two ray records carry the
-            // red and green contribution; blue and the path id follow in an 8-byte record
-            reinterpret_cast<float4*>(a.sh_rays)[j] = make_float4(o.x, o.y, o.z, contrib.x);
-            reinterpret_cast<float4*>(a.sh_rays)[S + j] = make_float4(wl.x, wl.y, wl.z, contrib.y);
-            reinterpret_cast<float2*>(a.sh_contrib)[j] = make_float2(contrib.z, __uint_as_float(pid));
-        }
-        if (emit_ext) {
-            const uint32_t j = slot.ext;
-            // 44 bytes per extension ray: its range is always (kRayTMin, kBackgroundDepth) (:31), so the .w of its two ray records carry
-            // the path's pdf and id; the throughput follows as three 4-byte planes (queue slots are contiguous per workgroup: coalesced)
-            reinterpret_cast<float4*>(a.out_rays)[j] = make_float4(o.x, o.y, o.z, pdf_n);
-            reinterpret_cast<float4*>(a.out_rays)[S + j] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(pid));
-            a.out_T[j] = Tn.x;
-            a.out_T[S + j] = Tn.y;
-            a.out_T[2 * S + j] = Tn.z;
-        }
-    }
+    constexpr bool PUNCT = false;
+#include "rt3_shade_body.inc"
+}
+// Waves: at six (80 VGPRs) the light function costs the FIRST and GLDS twins more scratch than their EMIT instance has (108 against 96 bytes,
+// 124 against 120), so all five take the four-wave step that MAT took: 128 VGPRs, no scratch.
+template <bool FIRST, bool GLDS, bool MAT>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
+    constexpr bool EMIT = true, PUNCT = true;
+#include "rt3_shade_body.inc"
 }
 
 // refrence_mode.slang:59-65 : radiance = (sum over samples, in sample order) / S, then blend with PrevLight
@@ -449,13 +170,15 @@ __global__ void k_accumulate(GConstDev g, const uint32_t* __restrict__ pixels, u
 
 // ------------------------------------------------------------------------------------------------ launchers
 // The k_shade instance of (first, glds, emit, mat): `launch` is called with four std::integral_constant<bool, ..>, in that order.  The first
-// vertex comes from the G-buffer and has neither the LDS table nor material textures, so ten instances exist: FIRST x EMIT, and
-// GLDS x EMIT x MAT for the later vertices.
+// vertex comes from the G-buffer and has neither the LDS table nor material textures, so ten instances of k_shade exist: FIRST x EMIT, and
+// GLDS x EMIT x MAT for the later vertices; and five of k_shade_punct, one beside each EMIT instance.
+// With punctual lights in the table (punct, which implies emit) the five EMIT shapes have a PUNCT twin: FIRST, and GLDS x MAT.
 template <typename Launch>
-static void dispatch_shade(bool first, bool glds, bool emit, bool mat, Launch launch) {
+static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punct, Launch launch) {
     auto by_emit = [&](auto f, auto g, auto m) {
-        if (emit) launch(f, g, std::true_type{}, m);
-        else launch(f, g, std::false_type{}, m);
+        if (emit && punct) launch(f, g, std::true_type{}, m, std::true_type{});
+        else if (emit) launch(f, g, std::true_type{}, m, std::false_type{});
+        else launch(f, g, std::false_type{}, m, std::false_type{});
     };
     auto by_mat = [&](auto g) {
         if (mat) by_emit(std::false_type{}, g, std::true_type{});
@@ -465,13 +188,15 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, Launch la
     else if (glds) by_mat(std::true_type{});
     else by_mat(std::false_type{});
 }
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a) {
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
     // emit: RT3_F_NEE_EMISSIVE with something to sample; mat: the built scene has material textures
-    dispatch_shade(first, glds, a.lights.n != 0u, a.sc.mat_tex != nullptr, [&](auto f, auto g, auto e, auto m) {
-        hipLaunchKernelGGL((k_shade<decltype(f)::value, decltype(g)::value, decltype(e)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+    // punct: that table holds punctual lights (RT3_F_NEE_PUNCTUAL)
+    dispatch_shade(first, glds, a.lights.n != 0u, a.sc.mat_tex != nullptr, punct && a.lights.n != 0u, [&](auto f, auto g, auto e, auto m, auto p) {
+        if constexpr (decltype(p)::value) hipLaunchKernelGGL((k_shade_punct<decltype(f)::value, decltype(g)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        else hipLaunchKernelGGL((k_shade<decltype(f)::value, decltype(g)::value, decltype(e)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
     });
 }
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,

@@ -749,6 +749,7 @@ struct Mesh {
     std::vector<Image> textures;
     std::vector<float> alpha_cutoffs;           // one per geometry (rt3_scene_set_alpha_cutoffs), 0 = opaque
     std::vector<rt3_material_textures> material_textures;  // one per geometry (rt3_scene_set_material_textures)
+    std::vector<rt3_punctual_light> lights;     // KHR_lights_punctual, baked through their nodes (rt3_scene_set_lights)
     size_t n_vertices() const { return vertices.size() / 8; }
     size_t n_triangles() const {
         size_t t = 0;
@@ -927,9 +928,37 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
         return decode_image(raw.data(), raw.size());
     }
 
+    // a light on a node: position M (0, 0, 0, 1), direction normalise(M3 (0, 0, -1)); node scale leaves the intensity alone
+    void light(size_t li, const Mat4& m) {
+        const Json& gl = doc_.at("extensions").at("KHR_lights_punctual").at("lights").at(li);
+        const std::string& kind = gl.at("type").str;
+        rt3_punctual_light l{};
+        l.type = kind == "point" ? RT3_LIGHT_POINT : kind == "spot" ? RT3_LIGHT_SPOT : RT3_LIGHT_DIRECTIONAL;
+        if (kind != "point" && kind != "spot" && kind != "directional") throw std::runtime_error("glTF: unknown light type " + kind);
+        const double d[3] = {0.0 - m.m[0][2], 0.0 - m.m[1][2], 0.0 - m.m[2][2]};  // M3 (0, 0, -1) as a sum of products: no -0
+        const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        const double intensity = gl.has("intensity") ? gl.at("intensity").number(1.0) : 1.0;
+        for (int k = 0; k < 3; k++) {
+            l.position[k] = (float)m.m[k][3];
+            l.direction[k] = (float)(d[k] / len);
+            l.intensity[k] = (float)((gl.has("color") ? gl.at("color").at((size_t)k).number(1.0) : 1.0) * intensity);
+        }
+        l.range = l.type != RT3_LIGHT_DIRECTIONAL && gl.has("range") ? (float)gl.at("range").number(0.0) : 0.0f;
+        l.inner_cone = 0.0f;
+        l.outer_cone = (float)(3.14159265358979323846 / 4.0);
+        if (const Json* spot = gl.find("spot")) {
+            if (spot->has("innerConeAngle")) l.inner_cone = (float)spot->at("innerConeAngle").number(0.0);
+            if (spot->has("outerConeAngle")) l.outer_cone = (float)spot->at("outerConeAngle").number(0.0);
+        }
+        mesh_.lights.push_back(l);
+    }
+
     void visit(size_t ni, const Mat4& parent) {
         const Json& node = doc_.at("nodes").at(ni);
         const Mat4 m = mul(parent, node_matrix(node));
+        if (const Json* ext = node.find("extensions"))
+            if (const Json* lp = ext->find("KHR_lights_punctual"))
+                if (lp->has("light")) light((size_t)lp->at("light").integer(0), m);
         if (node.has("mesh")) {
             const Json& gm = doc_.at("meshes").at((size_t)node.at("mesh").integer(0));
             const bool identity = m.is_identity();
@@ -1506,6 +1535,8 @@ inline uint32_t upload(rt3_ctx* ctx, const Mesh& m) {
         check(ctx, rt3_scene_set_material_textures(ctx, m.material_textures.data(), (uint32_t)m.material_textures.size()), "rt3_scene_set_material_textures");
     for (size_t i = 0; i < m.textures.size(); i++)
         check(ctx, rt3_scene_set_texture(ctx, (uint32_t)i, m.textures[i].rgba.data(), m.textures[i].w, m.textures[i].h), "rt3_scene_set_texture");
+    if (!m.lights.empty())  // punctual lights; a scene without them makes no call
+        check(ctx, rt3_scene_set_lights(ctx, m.lights.data(), (uint32_t)m.lights.size()), "rt3_scene_set_lights");
     uint32_t handle = 0;
     check(ctx, rt3_accel_build(ctx, &handle), "rt3_accel_build");
     return handle;

@@ -176,6 +176,9 @@ class Context:
         mt = getattr(mesh, "material_textures", None)
         if mt is not None and len(mt) and any(np.any(mt[k] >= 0) for k in ("metallic_roughness_texture", "normal_texture", "emissive_texture")):
             self.set_material_textures(mt)  # material textures; scenes without them make no call
+        lights = getattr(mesh, "lights", None)
+        if lights is not None and len(lights):  # punctual lights; scenes without them make no call
+            self.set_lights(lights)
         for i, t in enumerate(getattr(mesh, "textures", None) or []):  # base-colour textures, RGBA8 sRGB
             t = np.ascontiguousarray(t, np.uint8)
             self.check(self.lib.rt3_scene_set_texture(self.h, i, t.ctypes.data, t.shape[1], t.shape[0]))
@@ -208,6 +211,24 @@ class Context:
         n = 0 if transforms is None else len(transforms)
         arr = np.ascontiguousarray([np.asarray(m, np.float32).T.ravel() for m in transforms], np.float32).reshape(n, 16) if n else None
         self.check(self.lib.rt3_scene_set_prev_transforms(self.h, arr.ctypes.data if n else None, n))
+
+    def set_lights(self, lights=None):
+        """the world's punctual lights (assets.LIGHT_DTYPE records; rt3_scene_set_lights), sampled under F_NEE_PUNCTUAL; None or [] forgets
+        them.  No rebuild is needed: the next frame sees them."""
+        from .assets import LIGHT_DTYPE
+
+        arr = np.ascontiguousarray(np.zeros(0, LIGHT_DTYPE) if lights is None else lights, LIGHT_DTYPE).reshape(-1)
+        self.check(self.lib.rt3_scene_set_lights(self.h, arr.ctypes.data if len(arr) else None, len(arr)))
+
+    def light_masses(self, flags):
+        """(n_emitters, n_punctual, masses uint32 in CDF units) of the light table that `flags` samples: emitter triangles first, then the
+        punctual lights in set_lights order (rt3_light_masses)"""
+        ne, npu = C.c_uint32(), C.c_uint32()
+        self.check(self.lib.rt3_light_masses(self.h, int(flags), C.byref(ne), C.byref(npu), None))
+        mass = np.zeros(ne.value + npu.value, np.uint32)
+        if len(mass):
+            self.check(self.lib.rt3_light_masses(self.h, int(flags), C.byref(ne), C.byref(npu), mass.ctypes.data))
+        return ne.value, npu.value, mass
 
     def snapshot_vertices(self):
         """the positions the vertex buffer holds now become the previous frame's (rt3_scene_snapshot_vertices): the "motion" pass follows

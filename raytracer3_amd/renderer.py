@@ -147,7 +147,9 @@ class PathTracer:
         self.ctx.close()
 
     def set_scene(self, mesh, sky=None, bluenoise=None):
-        self.ctx.upload_mesh(mesh)
+        self.ctx.upload_mesh(mesh)  # (with the mesh's punctual lights, when it has some)
+        if not len(getattr(mesh, "lights", ())):
+            self.ctx.set_lights(None)  # the lights belong to the world: a scene without them replaces the previous scene's
         self._snapshot = False  # (new vertices: the context forgot it)
         if sky is not None:
             self.ctx.set_sky(sky)
@@ -155,6 +157,11 @@ class PathTracer:
             self.ctx.set_bluenoise(bluenoise)
         self._accel = self.ctx.build_accel()
         self.reset_history()
+
+    def set_lights(self, lights=None):
+        """Replace the world's punctual lights (assets.LIGHT_DTYPE; None forgets them).  No rebuild: frames with F_NEE_PUNCTUAL in their
+        flags sample them from the next frame on.  Moved lights' shadows lag in temporal history like any moved light."""
+        self.ctx.set_lights(lights)
 
     def set_instances(self, instances):
         """Place the scene's geometries: upload the list (ctx.set_instances) and rebuild.  The next temporal frame compares it with the

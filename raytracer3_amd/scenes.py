@@ -337,6 +337,22 @@ def textured_cornell() -> Mesh:
     return mesh
 
 
+def lit_room() -> Mesh:
+    """The Cornell box with its panel switched off and three punctual lights instead (KHR_lights_punctual): a warm
+    point lamp between the blocks, a spot from the ceiling onto the tall block, a dim cool sun slanting in from the open side.  Render it
+    with F_NEE_PUNCTUAL in the flags; without the flag it is black."""
+    from .assets import LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT, lights_array, make_light
+
+    mesh = cornell()
+    mesh.geometries["emission"][mesh.names.index("panel")] = 0.0
+    mesh.lights = lights_array([
+        make_light(LIGHT_POINT, (2.4, 1.8, 1.1), position=(0.15, 0.45, 0.35), range=6.0),
+        make_light(LIGHT_SPOT, (9.0, 9.0, 8.0), position=(-0.3, 1.9, 0.1), direction=(-0.1, -1.0, -0.25), inner_cone=0.25, outer_cone=0.55),
+        make_light(LIGHT_DIRECTIONAL, (0.25, 0.3, 0.4), direction=(0.2, -0.5, -1.0)),
+    ])
+    return mesh
+
+
 def cutout_cornell() -> Mesh:
     """The Cornell box with alpha-masked cutout geometry (glTF alphaMode MASK): a tilted lattice panel (hard 0 / 255
     alpha, cutoff 0.5) and overlapping leaf quads at different depths whose alpha is a smooth gradient (cutoffs 0.3, 0.5, 0.7, uv repeated),

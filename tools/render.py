@@ -29,7 +29,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -62,6 +62,8 @@ def main():
         mesh, cam_kw = scenes.cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "cutout_cornell":  # alpha-masked cutout geometry
         mesh, cam_kw = scenes.cutout_cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "lit_room":  # point, spot and directional lights
+        mesh, cam_kw = scenes.lit_room(), scenes.CORNELL_CAMERA
     elif args.scene == "material_cornell":  # metallic-roughness, normal and emissive maps
         mesh, cam_kw = scenes.material_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "cornell_ref":
@@ -72,6 +74,8 @@ def main():
     if sky is not None:  # rt3_scene_set_sky wants finite, non-negative radiance; HDR files carry inf / NaN / tiny negatives
         sky = np.clip(np.nan_to_num(sky, nan=0.0, posinf=65504.0, neginf=0.0), 0.0, 65504.0).astype(np.float32)
     flags = args.flags if args.flags >= 0 else (DEFAULT_FLAGS if sky is not None else L.F_FACEFORWARD | L.F_SPECULAR)
+    if args.flags < 0 and len(getattr(mesh, "lights", ())):  # a scene with punctual lights is lit by them
+        flags |= L.F_NEE_PUNCTUAL
     pt = PathTracer((W, H))
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
