@@ -422,6 +422,8 @@ int rt3_gather_unpack(rt3_ctx *ctx, uint32_t image, uint32_t root, uint32_t n_ra
  *                        (no reference counterpart: the reprojected accumulation described at rt3_temporal_set_params below)
  *        "motion"        (x,y)=window   bindings {Motion RGBA32F}
  *                        (no reference counterpart: where each surface point was one frame ago, rt3_temporal_set_motion_input below)
+ *        "adaptive"      (x,y)=window   bindings {gbuffer, gbuffer_depth, Light, PrevLight, Moments RGBA32F}
+ *                        (no reference counterpart: refrence_mode to a noise threshold, rt3_adaptive_set_params below)
  *      and the probe-GI passes (restated as written, debug stores included; rules for what the text leaves open are listed in
  *      DESIGN.md section 11).  A probe owns 16x16 pixels and an 8x8-texel cell of the atlas images; bindings are ordered by
  *      (descriptor set, binding) as the shaders declare them:
@@ -523,6 +525,50 @@ int rt3_temporal_set_params(rt3_ctx *ctx, const rt3_temporal_params *params);
  *      surfaces; "deformed" is per geometry, so the still part of a deformed mesh pays for the gather (its texel is its own point);
  *      there are no previous normals: a surface that bends by more than acos(normal_cos) in one frame loses its history. ---- */
 int rt3_temporal_set_motion_input(rt3_ctx *ctx, uint32_t motion_image);
+/* ---- "adaptive": refrence_mode "to a noise threshold, up to N samples".  No reference counterpart; DESIGN.md section 4l.  The pass traces the
+ *      paths refrence_mode traces -- GConst.bounces, the flags, frame and blendfactor mean what they mean there -- but GConst.samples is the
+ *      CAP: a pixel stops when the variance of its luminance says its mean is good enough.  Moments may be none of the other four images.
+ *      Per foreground pixel of this rank's list the pass keeps n, the sample count; S1 = sum y and S2 = sum y * y in float32 and in sample
+ *      order, y = luminance(sample rgb) = r 0.299 + g 0.587 + b 0.114; and the three colour sums exactly as refrence_mode forms them (from
+ *      0.0f, in sample order).
+ *      The loop:
+ *       - round 0 gives every foreground pixel min(min_samples, cap) samples; each later round gives the still-active pixels
+ *         min(step, cap - n) more, numbered n, n + 1, ...: n is the same for every active pixel, and the RNG counter
+ *         (sample * bounces + bounce) * dims + dim does not know the cap;
+ *       - after each round a pixel PASSES when, in this operation order, in float32, without contraction and with IEEE divides,
+ *             mean = S1 / n
+ *             var  = (S2 - S1 * mean) / (n - 1), replaced by 0 if negative
+ *             rel  = threshold * (mean + dark)
+ *             var <= (rel * rel) * n
+ *         (the variance of the mean, var / n, against the square of a relative error; `dark` keeps black pixels from never passing);
+ *       - a pixel STAYS ACTIVE if it fails or, with dilate = 1, if any foreground pixel of this rank's list in its 3 x 3 neighbourhood
+ *         fails; background pixels, pixels outside the window and pixels of other ranks count as passing.  A pixel that has stopped never
+ *         restarts: its state is frozen;
+ *       - the loop ends when no pixel is active or n == cap.  An empty list launches nothing further.  A cap below min_samples runs
+ *         `samples` for every pixel.
+ *      At the end, per foreground pixel: Light = sums / (float)n, then refrence_mode's blend with PrevLight under blendfactor; Moments =
+ *      {S1, S2, n, 1 if the pixel stopped before the cap else 0}.  So a pixel that stopped at n holds the bits refrence_mode writes for it
+ *      in a frame of samples = n.  Background pixels: Light untouched (as refrence_mode leaves it), Moments = 0; they are in no traced
+ *      list, round 0 included.  samples = 0 or bounces = 0 does nothing, like refrence_mode.
+ *      The estimate is NOT unbiased: a pixel that draws a prefix of low variance stops early; min_samples and the dilation are the
+ *      mitigations.  Works under a tile partition on the rank's own pixels; with dilate = 0 the result does not depend on the partition.
+ *      The active count comes back to the host once per round (4 bytes, one stream synchronisation): the launch returns after the last
+ *      round is enqueued, not at once.  RT3_OPT_BATCH_SPP splits a round as it splits refrence_mode's frame.
+ *      rt3_adaptive_set_params: NULL restores the defaults {16, 16, 0.05, 0.01, 1, 0}.  RT3_E_INVALID (nothing changed) for min_samples < 2,
+ *      step < 1, a threshold that is not finite or negative, a dark that is not finite or not positive, dilate > 1 or any flag bit (none
+ *      is defined).
+ *      rt3_adaptive_info (any pointer may be NULL): of the last "adaptive" launch, the rounds run, the first-vertex paths traced (the sum
+ *      of n over this rank's foreground pixels) and the pixels that reached the cap. ---- */
+typedef struct rt3_adaptive_params {
+    uint32_t min_samples; /* round 0; >= 2 (the variance divides by n - 1) */
+    uint32_t step;        /* samples per later round; >= 1 */
+    float threshold;      /* relative standard error of the pixel mean to stop at; finite, >= 0 (0: only var == 0 passes) */
+    float dark;           /* added to the mean; finite, > 0 */
+    uint32_t dilate;      /* 0, or 1: the 3 x 3 rule */
+    uint32_t flags;       /* none defined: 0 */
+} rt3_adaptive_params;
+int rt3_adaptive_set_params(rt3_ctx *ctx, const rt3_adaptive_params *params);
+int rt3_adaptive_info(rt3_ctx *ctx, uint32_t *rounds, uint64_t *paths_traced, uint32_t *pixels_capped);
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);

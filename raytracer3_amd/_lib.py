@@ -44,6 +44,7 @@ EXPORTS = [
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
+    "rt3_adaptive_set_params", "rt3_adaptive_info",
     "rt3_scene_set_lights", "rt3_light_masses",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
@@ -91,6 +92,16 @@ class TemporalParams(C.Structure):
 
     def __init__(self, alpha=0.2, alpha_moments=0.2, max_history=32, normal_cos=0.9, plane_tolerance=0.01, flags=0):
         super().__init__(alpha, alpha_moments, max_history, normal_cos, plane_tolerance, flags)
+
+
+class AdaptiveParams(C.Structure):
+    """rt3_adaptive_params: the "adaptive" pass.  The defaults are the library's."""
+
+    _fields_ = [("min_samples", C.c_uint32), ("step", C.c_uint32), ("threshold", C.c_float), ("dark", C.c_float), ("dilate", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+    def __init__(self, min_samples=16, step=16, threshold=0.05, dark=0.01, dilate=1, flags=0):
+        super().__init__(min_samples, step, threshold, dark, dilate, flags)
 
 
 assert C.sizeof(GConst) == 304
@@ -187,6 +198,8 @@ def load():
         "rt3_scene_set_lights": (i32, [vp, vp, u32]),
         "rt3_light_masses": (i32, [vp, u32, pu32, pu32, vp]),
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
+        "rt3_adaptive_set_params": (i32, [vp, C.POINTER(AdaptiveParams)]),
+        "rt3_adaptive_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), pu32]),
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),
         "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),

@@ -20,6 +20,7 @@ namespace rt3 {
 
 inline const rt3_denoise_params kDenoiseDefaults = {5u, 7u, 0.05f, 4.0f, 0u};
 inline const rt3_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32u, 0.9f, 0.01f, 0u};
+inline const rt3_adaptive_params kAdaptiveDefaults = {16u, 16u, 0.05f, 0.01f, 1u, 0u};
 inline constexpr float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 // a column-major 4 x 4 whose last row is (0, 0, 0, 1) as the device tables hold it: 3 x 4, column-major (FlatGeomDev::m)
 inline void pack3x4(const float* m16, float* m12) {
@@ -245,6 +246,14 @@ struct rt3_ctx {
         rt3::DevBuf<rt3::MotionPrevDev> d_prev;
         rt3::DevBuf<uint32_t> d_slot;
     } motion;
+    // rt3_passes.hip: "adaptive" pass: parameters (rt3_adaptive_set_params), the grow-only scratch its state and lists are carved from, and
+    // what the last launch did (rt3_adaptive_info)
+    struct Adaptive {
+        rt3_adaptive_params params = rt3::kAdaptiveDefaults;
+        rt3::DevBuf<char> scratch;
+        uint32_t rounds = 0, pixels_capped = 0;
+        uint64_t paths_traced = 0;
+    } adaptive;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot

@@ -501,6 +501,34 @@ void launch_snapshot_positions(hipStream_t st, const float* verts, uint32_t firs
 constexpr uint32_t kDeformChunk = 1024;  // vertices per chunk, at most
 void launch_compare_positions(hipStream_t st, const float* verts, const float4* prev_pos, const uint4* chunks, uint32_t n_chunks, uint32_t* flags);
 
+// "adaptive" pass (rt3_adaptive.hip).  Scratch, carved from the context's grow-only adaptive buffer: the per-pixel
+// state in window space (index y * W + x, so that compacting the list moves nothing), two pixel lists that take turns (a list is the words
+// x | y << 16 and, in the same order, k_pixbn's {xy, blue-noise word} records), and the compaction's per-block counts and result.
+struct AdaptiveScratch {
+    float4* sums;           // {sum r, sum g, sum b, n as uint32 bits}
+    float2* mom;            // {S1, S2}
+    uint8_t* mask;          // 1: the pixel's last test failed; 0 for everything that is not a listed foreground pixel of this rank
+    uint32_t* xy[2];
+    uint2* bn[2];
+    uint32_t* block_count;  // one word per compaction block: its count, then its offset
+    uint32_t* count;        // the length of the list the last compaction wrote
+};
+void adaptive_plan(uint32_t W, uint32_t H, uint32_t npix, BufLayout& plan, AdaptiveScratch* s);
+// foreground pixels of the rank's list: mask = 1 (s.mask zeroed for the whole window before); background ones: Moments = 0
+void launch_adaptive_init(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth, const AdaptiveScratch& s,
+                          void* moments);
+// k_accumulate's sums plus S1, S2 over the list's `sb` samples in lacc (path id = sample * npix + index); first: the pixels' first batch
+void launch_adaptive_accumulate(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* lacc, uint32_t sb, bool first,
+                                uint32_t n_after, const AdaptiveScratch& s);
+void launch_adaptive_test(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, float threshold, float dark,
+                          const AdaptiveScratch& s);
+// the entries of the n_in >= 1 records in_bn that stay active (mask, with the 3 x 3 rule if dilate) into s.xy[out] / s.bn[out], in order;
+// their number into *s.count.  Three launches: count, scan, scatter.
+void launch_adaptive_compact(hipStream_t st, const uint2* in_bn, uint32_t n_in, uint32_t W, uint32_t H, uint32_t dilate, const AdaptiveScratch& s,
+                             int out);
+void launch_adaptive_finalise(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth, float blendfactor,
+                              uint32_t cap, const AdaptiveScratch& s, void* light, const void* prev, void* moments);
+
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 
 }  // namespace rt3

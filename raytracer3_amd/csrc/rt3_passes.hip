@@ -1,6 +1,7 @@
 // rt3_passes.hip -- host layer, the passes: the wavefront work queues and counter reservation, the primary trace, every pass function,
-// the pass table kPasses and its validator, rt3_pass_launch, and the state of the "denoise", "temporal" and "motion" passes
-// (include/rt3.h: rt3_pass_launch, rt3_denoise_*, rt3_temporal_*).  Owns rt3_ctx::work, ::denoise, ::temporal and ::motion.
+// the pass table kPasses and its validator, rt3_pass_launch, and the state of the "denoise", "temporal", "motion" and "adaptive" passes
+// (include/rt3.h: rt3_pass_launch, rt3_denoise_*, rt3_temporal_*, rt3_adaptive_*).  Owns rt3_ctx::work, ::denoise, ::temporal, ::motion
+// and ::adaptive.
 // rt3_pass_launch() is the drop-in for executing one pass node of the reference's frame graph (render_graph/mod.rs:80-107): the pass
 // name selects a HIP kernel sequence instead of a SPIR-V pipeline.
 #include <hip/hip_runtime.h>
@@ -214,6 +215,107 @@ int pass_gbuffer(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
     return RT3_OK;
 }
 
+// What every batch of a path-tracing frame shares: the constants as the kernels see them, which estimators run, the light table
+struct PathSetup {
+    GConstDev gd;
+    SceneDev sc;
+    LightsDev lights{};
+    bool nee = false, nee_e = false, punct = false;
+};
+// (B = g->bounces >= 1; the queues must exist before an emitter queue can be sized: call after ensure_work)
+int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
+    const uint32_t B = g->bounces;
+    ps->gd = gconst_dev(g);
+    // RT3_F_NEE_PUNCTUAL without lights, or with B = 1, is the frame without the bit, bit for bit: the kernels draw 8 RNG dimensions per
+    // vertex for any flag word but 0, so the bit itself goes where it changes nothing else
+    if (c->scene.lights.empty() || B <= 1) ps->gd.pad[0] &= ~RT3_F_NEE_PUNCTUAL;
+    ps->nee = (g->pad[0] & RT3_F_NEE_SKY) && c->scene.d_sky;
+    // RT3_F_NEE_EMISSIVE (DESIGN.md section 4d): only with something to sample; otherwise the frame is the flag-less one, same kernels
+    // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
+    // RT3_F_NEE_PUNCTUAL (section 4k): the same, with the punctual lights as further entries of the table
+    const uint32_t combo = g->pad[0] & (RT3_F_NEE_EMISSIVE | (c->scene.lights.empty() ? 0u : RT3_F_NEE_PUNCTUAL));
+    if (combo && B > 1) {
+        if (int r = ensure_lights(c, combo)) return r;
+        ps->lights = c->accel.lights.dev();
+        ps->punct = ps->lights.n != 0u && c->accel.lights.n_punct != 0u;
+        if (ps->lights.n)
+            if (int r = ensure_emit_queue(c)) return r;
+    }
+    ps->nee_e = ps->lights.n != 0u;
+    ps->sc = scene_dev(c);
+    return RT3_OK;
+}
+// One wavefront batch: samples s0 .. s0 + nsb - 1 of the npix listed pixels (path id = sample_in_batch * npix + index) through all B
+// bounces; each path's radiance ends up in c->work.lacc.  The loop body of "refrence_mode", and of a round of "adaptive".
+int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb, const Resource* dp, const uint32_t* pixels, const uint2* pixbn,
+                uint32_t npix, uint32_t s0, uint32_t nsb) {
+    const uint32_t B = ps.gd.bounces;
+    const size_t S = c->work.cap;
+    const bool nee = ps.nee, nee_e = ps.nee_e;
+    const uint32_t n_first = nsb * npix;
+    uint32_t first;
+    if (int r = reserve_counters(c, (nee_e ? 6 : 4) * B + 1, &first)) return r;
+    first += first & 1u;  // 8-byte aligned pairs
+    // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
+    uint32_t* pairs = c->work.d_counters.get() + first;
+    uint32_t* pool_cur = c->work.d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
+    // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
+    uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
+    c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
+    auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
+    auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
+    int cur = 0;
+    for (uint32_t bn = 0; bn < B; bn++) {
+        ShadeLaunch L;
+        L.g = ps.gd; L.sc = ps.sc; L.pixels = pixels; L.pixbn = pixbn; L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
+        L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
+        L.in_rays = c->work.rays[cur].get(); L.in_hits = c->work.hits.get(); L.in_T = c->work.T[cur].get();
+        L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
+        L.out_rays = c->work.rays[cur ^ 1].get(); L.out_T = c->work.T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
+        L.sh_rays = c->work.sh_rays.get(); L.sh_contrib = c->work.sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
+        L.lacc = c->work.lacc.get(); L.stride = S;
+        L.lights = ps.lights;
+        L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
+        {
+            ScopedTimer t(c, CAT_SHADE);
+            launch_shade(c->stream, bn == 0, L, ps.punct);
+        }
+        cur ^= 1;
+        if (nee) {
+            TraceLaunch tr = ctx_trace(c);
+            tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
+            tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
+            ScopedTimer t(c, CAT_SHADOW);
+            launch_shadow(c->stream, c->accel.bvh, tr);
+        }
+        if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
+            TraceLaunch tr = ctx_trace(c);
+            tr.rays = c->work.sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
+            tr.contrib = c->work.sh2_contrib.get(); tr.lacc = c->work.lacc.get(); tr.tmax = c->work.sh2_tmax.get();
+            ScopedTimer t(c, CAT_SHADOW);
+            launch_shadow(c->stream, c->accel.bvh, tr);
+        }
+        if (bn != B - 1) {
+            TraceLaunch tr = ctx_trace(c);
+            tr.rays = c->work.rays[cur].get(); tr.count_ptr = ext_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + bn;
+            tr.hits = c->work.hits.get(); tr.payload = true;
+            ScopedTimer t(c, CAT_EXTEND);
+            launch_extend(c->stream, c->accel.bvh, tr);
+        }
+    }
+    return RT3_OK;
+}
+// paths per wavefront batch: 160 B of queue state each, so 2^28 paths = 43 GB of the 288 GB; the C3 frame (132.7 M paths)
+// is ONE batch.  Larger launches amortise the ramp / tail of the persistent traversal kernels: 16 -> 64 spp per batch = -6.5 % frame time.
+// *sb: the samples of a batch over npix >= 1 pixels that are to get `spp` samples (RT3_OPT_BATCH_SPP, or as many as fit)
+int batch_spp(rt3_ctx* c, uint32_t npix, uint32_t spp, uint32_t* sb) {
+    uint64_t max_paths = 1ull << 28;
+    *sb = c->opt.batch_spp > 0 ? (uint32_t)c->opt.batch_spp : (uint32_t)std::max<uint64_t>(1, max_paths / npix);
+    if (*sb > spp) *sb = spp;
+    if ((uint64_t)*sb * npix > 0xFFFFFF00ull) return fail(c, RT3_E_INVALID, "batch too large");
+    return RT3_OK;
+}
+
 // refrence_mode.slang:14-66 as a wavefront loop
 int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
     const Resource *gb = res[0], *dp = res[1], *li = res[2], *pv = res[3];
@@ -225,92 +327,105 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     const uint32_t npix = pl->count;
     if (npix == 0) return RT3_OK;
     if (int r = pixlist_bluenoise(c, pl)) return r;
-    // paths per wavefront batch: 160 B of queue state each, so 2^28 paths = 43 GB of the 288 GB; the C3 frame (132.7 M paths)
-    // is ONE batch.  Larger launches amortise the ramp / tail of the persistent traversal kernels: 16 -> 64 spp per batch = -6.5 % frame time.
-    uint64_t max_paths = 1ull << 28;
-    uint32_t sb = c->opt.batch_spp > 0 ? (uint32_t)c->opt.batch_spp : (uint32_t)std::max<uint64_t>(1, max_paths / npix);
-    if (sb > Sspp) sb = Sspp;
-    if ((uint64_t)sb * npix > 0xFFFFFF00ull) return fail(c, RT3_E_INVALID, "batch too large");
+    uint32_t sb;
+    if (int r = batch_spp(c, npix, Sspp, &sb)) return r;
     if (int r = ensure_work(c, (size_t)sb * npix, npix)) return r;
-    const size_t S = c->work.cap;
-    GConstDev gd = gconst_dev(g);
-    // RT3_F_NEE_PUNCTUAL without lights, or with B = 1, is the frame without the bit, bit for bit: the kernels draw 8 RNG dimensions per
-    // vertex for any flag word but 0, so the bit itself goes where it changes nothing else
-    if (c->scene.lights.empty() || B <= 1) gd.pad[0] &= ~RT3_F_NEE_PUNCTUAL;
-    const bool nee = (g->pad[0] & RT3_F_NEE_SKY) && c->scene.d_sky;
-    // RT3_F_NEE_EMISSIVE (DESIGN.md section 4d): only with something to sample; otherwise the frame is the flag-less one, same kernels
-    // (and B >= 2: emitter shadow rays leave vertices 0 .. B-2)
-    // RT3_F_NEE_PUNCTUAL (section 4k): the same, with the punctual lights as further entries of the table
-    LightsDev lights{};
-    bool punct = false;
-    const uint32_t combo = g->pad[0] & (RT3_F_NEE_EMISSIVE | (c->scene.lights.empty() ? 0u : RT3_F_NEE_PUNCTUAL));
-    if (combo && B > 1) {
-        if (int r = ensure_lights(c, combo)) return r;
-        lights = c->accel.lights.dev();
-        punct = lights.n != 0u && c->accel.lights.n_punct != 0u;
-        if (lights.n)
-            if (int r = ensure_emit_queue(c)) return r;
-    }
-    const bool nee_e = lights.n != 0u;
-    SceneDev sc = scene_dev(c);
+    PathSetup ps;
+    if (int r = path_setup(c, g, &ps)) return r;
     for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
         const uint32_t nsb = std::min(sb, Sspp - s0);
-        const uint32_t n_first = nsb * npix;
-        uint32_t first;
-        if (int r = reserve_counters(c, (nee_e ? 6 : 4) * B + 1, &first)) return r;
-        first += first & 1u;  // 8-byte aligned pairs
-        // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
-        uint32_t* pairs = c->work.d_counters.get() + first;
-        uint32_t* pool_cur = c->work.d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
-        // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
-        uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
-        c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
-        auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
-        auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
-        int cur = 0;
-        for (uint32_t bn = 0; bn < B; bn++) {
-            ShadeLaunch L;
-            L.g = gd; L.sc = sc; L.pixels = pl->dev.get(); L.pixbn = pl->dev_bn.get(); L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
-            L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
-            L.in_rays = c->work.rays[cur].get(); L.in_hits = c->work.hits.get(); L.in_T = c->work.T[cur].get();
-            L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
-            L.out_rays = c->work.rays[cur ^ 1].get(); L.out_T = c->work.T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
-            L.sh_rays = c->work.sh_rays.get(); L.sh_contrib = c->work.sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
-            L.lacc = c->work.lacc.get(); L.stride = S;
-            L.lights = lights;
-            L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
-            {
-                ScopedTimer t(c, CAT_SHADE);
-                launch_shade(c->stream, bn == 0, L, punct);
-            }
-            cur ^= 1;
-            if (nee) {
-                TraceLaunch tr = ctx_trace(c);
-                tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
-                tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
-                ScopedTimer t(c, CAT_SHADOW);
-                launch_shadow(c->stream, c->accel.bvh, tr);
-            }
-            if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
-                TraceLaunch tr = ctx_trace(c);
-                tr.rays = c->work.sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
-                tr.contrib = c->work.sh2_contrib.get(); tr.lacc = c->work.lacc.get(); tr.tmax = c->work.sh2_tmax.get();
-                ScopedTimer t(c, CAT_SHADOW);
-                launch_shadow(c->stream, c->accel.bvh, tr);
-            }
-            if (bn != B - 1) {
-                TraceLaunch tr = ctx_trace(c);
-                tr.rays = c->work.rays[cur].get(); tr.count_ptr = ext_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + bn;
-                tr.hits = c->work.hits.get(); tr.payload = true;
-                ScopedTimer t(c, CAT_EXTEND);
-                launch_extend(c->stream, c->accel.bvh, tr);
-            }
+        if (int r = trace_batch(c, ps, W, gb, dp, pl->dev.get(), pl->dev_bn.get(), npix, s0, nsb)) return r;
+        {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_accumulate(c->stream, ps.gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->work.lacc.get(), c->work.cap, nsb, s0 == 0, s0 + nsb >= Sspp,
+                              c->work.radsum.get(), li->ptr, pv->ptr);
+        }
+    }
+    HIPC(c, hipGetLastError());
+    return RT3_OK;
+}
+
+// "adaptive": refrence_mode to a noise threshold, GConst.samples the cap (no reference counterpart).  The rounds'
+// paths are trace_batch's; the pixel list shrinks between rounds.  The length of the next list comes back to the host once per round (4
+// bytes behind one stream synchronisation): npix and its fast_div constant are launch arguments of k_shade, and sizes every grid.
+int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
+    const Resource *gb = res[0], *dp = res[1], *li = res[2], *pv = res[3], *mo = res[4];
+    const rt3_adaptive_params& p = c->adaptive.params;
+    const uint32_t cap = g->samples, B = g->bounces;
+    c->adaptive.rounds = c->adaptive.pixels_capped = 0;
+    c->adaptive.paths_traced = 0;
+    if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
+    if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
+    PixelList* pl;
+    if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
+    if (pl->count == 0) return RT3_OK;
+    if (int r = pixlist_bluenoise(c, pl)) return r;
+    AdaptiveScratch s;
+    BufLayout plan;
+    adaptive_plan(W, H, pl->count, plan, &s);
+    if (c->adaptive.scratch.capacity_bytes() < plan.bytes()) {  // the stream may still read the old allocation
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, c->adaptive.scratch.grow_bytes(plan.bytes()));
+    }
+    HIPC(c, plan.carve(c->adaptive.scratch));
+    const float* depth = (const float*)dp->ptr;
+    // the length of the list launch_adaptive_compact wrote last
+    auto list_length = [&](uint32_t* n) {
+        HIPC(c, hipMemcpyAsync(n, s.count, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        return (int)RT3_OK;
+    };
+    // round 0's list: the foreground pixels of the rank's list, in its order
+    uint32_t n_act = 0;
+    int cur = 0;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        HIPC(c, hipMemsetAsync(s.mask, 0, (size_t)W * H, c->stream));
+        launch_adaptive_init(c->stream, pl->dev.get(), pl->count, W, depth, s, mo->ptr);
+        launch_adaptive_compact(c->stream, pl->dev_bn.get(), pl->count, W, H, 0u, s, cur);
+    }
+    if (int r = list_length(&n_act)) return r;
+    const uint32_t n_fg = n_act;
+    if (n_fg) {
+        // the queues are sized once, for the largest batch of any round: round 0's list is the longest
+        const uint32_t most = std::max(std::min(p.min_samples, cap), std::min(p.step, cap));
+        uint32_t sb;
+        if (int r = batch_spp(c, n_fg, most, &sb)) return r;
+        if (int r = ensure_work(c, (size_t)sb * n_fg, 0)) return r;
+    }
+    PathSetup ps;
+    if (n_fg)
+        if (int r = path_setup(c, g, &ps)) return r;
+    uint32_t n = 0;  // the sample count of every active pixel
+    while (n_act) {
+        const uint32_t ns = n == 0 ? std::min(p.min_samples, cap) : std::min(p.step, cap - n);
+        uint32_t sb;
+        if (int r = batch_spp(c, n_act, ns, &sb)) return r;
+        sb = (uint32_t)std::min<uint64_t>(sb, c->work.cap / n_act);  // (a shorter list may not take more samples per batch than the queues hold)
+        for (uint32_t s0 = 0; s0 < ns; s0 += sb) {
+            const uint32_t nsb = std::min(sb, ns - s0);
+            if (int r = trace_batch(c, ps, W, gb, dp, s.xy[cur], s.bn[cur], n_act, n + s0, nsb)) return r;
+            ScopedTimer t(c, CAT_OTHER);
+            launch_adaptive_accumulate(c->stream, s.xy[cur], n_act, W, c->work.lacc.get(), nsb, n + s0 == 0, n + s0 + nsb, s);
+        }
+        n += ns;
+        c->adaptive.rounds++;
+        c->adaptive.paths_traced += (uint64_t)ns * n_act;
+        if (n >= cap) {
+            c->adaptive.pixels_capped = n_act;
+            break;
         }
         {
             ScopedTimer t(c, CAT_OTHER);
-            launch_accumulate(c->stream, gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->work.lacc.get(), S, nsb, s0 == 0, s0 + nsb >= Sspp, c->work.radsum.get(), li->ptr,
-                              pv->ptr);
+            launch_adaptive_test(c->stream, s.xy[cur], n_act, W, p.threshold, p.dark, s);
+            launch_adaptive_compact(c->stream, s.bn[cur], n_act, W, H, p.dilate, s, cur ^ 1);
         }
+        cur ^= 1;
+        if (int r = list_length(&n_act)) return r;
+    }
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_adaptive_finalise(c->stream, pl->dev.get(), pl->count, W, depth, g->blendfactor, cap, s, li->ptr, pv->ptr, mo->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -519,6 +634,8 @@ const PassDesc kPasses[] = {
      {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"In", kF4}, {"PrevGbuffer", kU4}, {"PrevDepth", kF1}, {"PrevHistory", kF4}, {"PrevMoments", kF4},
       {"Out", kF4, false, 0x7Fu}, {"History", kF4, false, 0xFFu}, {"Moments", kF4, false, 0x1FFu}}},
     {"motion", kWindow, true, false, pass_motion, {{"Motion", kF4}}},
+    {"adaptive", kWindow, true, false, pass_adaptive,
+     {{"gbuffer", kU4}, {"gbuffer_depth", kF1}, {"Light", kF4}, {"PrevLight", kF4}, {"Moments", kF4, false, 0xCu}}},
 };
 // a, b, ... : the names of a table's entries
 template <typename T, size_t N>
@@ -618,6 +735,28 @@ int rt3_denoise_set_params(rt3_ctx* c, const rt3_denoise_params* p) {
 int rt3_denoise_set_variance_input(rt3_ctx* c, uint32_t moments_image) {
     if (!c) return RT3_E_INVALID;
     c->denoise.variance_image = moments_image;  // checked when "denoise" is launched: the image may be created, resized or destroyed in between
+    return RT3_OK;
+}
+int rt3_adaptive_set_params(rt3_ctx* c, const rt3_adaptive_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->adaptive.params = kAdaptiveDefaults;
+        return RT3_OK;
+    }
+    if (p->min_samples < 2) return fail(c, RT3_E_INVALID, "adaptive params: min_samples must be at least 2 (the variance divides by n - 1)");
+    if (p->step < 1) return fail(c, RT3_E_INVALID, "adaptive params: step must be at least 1");
+    if (!(std::isfinite(p->threshold) && p->threshold >= 0.0f)) return fail(c, RT3_E_INVALID, "adaptive params: threshold must be finite and not negative");
+    if (!(std::isfinite(p->dark) && p->dark > 0.0f)) return fail(c, RT3_E_INVALID, "adaptive params: dark must be finite and positive");
+    if (p->dilate > 1) return fail(c, RT3_E_INVALID, "adaptive params: dilate must be 0 or 1");
+    if (p->flags) return fail(c, RT3_E_INVALID, "adaptive params: unknown flag bits");
+    c->adaptive.params = *p;
+    return RT3_OK;
+}
+int rt3_adaptive_info(rt3_ctx* c, uint32_t* rounds, uint64_t* paths_traced, uint32_t* pixels_capped) {
+    if (!c) return RT3_E_INVALID;
+    if (rounds) *rounds = c->adaptive.rounds;
+    if (paths_traced) *paths_traced = c->adaptive.paths_traced;
+    if (pixels_capped) *pixels_capped = c->adaptive.pixels_capped;
     return RT3_OK;
 }
 int rt3_temporal_set_prev_view(rt3_ctx* c, const void* prev_gconst, size_t size) {

@@ -101,6 +101,12 @@ class Context {
     // and the Motion image that "temporal" follows moved instances with (0 = none)
     void set_prev_transforms(const float* m, uint32_t n) const { check(rt3_scene_set_prev_transforms(ctx_, m, n), "rt3_scene_set_prev_transforms"); }
     void set_temporal_motion_input(uint32_t motion_image) const { check(rt3_temporal_set_motion_input(ctx_, motion_image), "rt3_temporal_set_motion_input"); }
+    // RayTracingPass "adaptive" (no reference counterpart): refrence_mode to a noise threshold with GConst.samples as the cap; bindings
+    // {gbuffer, gbuffer_depth, Light, PrevLight, Moments}.  Its parameters (nullptr = the defaults) and what the last launch did
+    void set_adaptive_params(const rt3_adaptive_params* p) const { check(rt3_adaptive_set_params(ctx_, p), "rt3_adaptive_set_params"); }
+    void adaptive_info(uint32_t* rounds, uint64_t* paths_traced, uint32_t* pixels_capped) const {
+        check(rt3_adaptive_info(ctx_, rounds, paths_traced, pixels_capped), "rt3_adaptive_info");
+    }
     // previous vertex positions: "motion" follows meshes that update_vertices deforms after a snapshot
     void snapshot_vertices() const { check(rt3_scene_snapshot_vertices(ctx_), "rt3_scene_snapshot_vertices"); }
     void forget_prev_vertices() const { check(rt3_scene_forget_prev_vertices(ctx_), "rt3_scene_forget_prev_vertices"); }

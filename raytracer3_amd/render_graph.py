@@ -370,6 +370,18 @@ class Context:
         """the "motion" pass's image that "temporal" follows moved instances with (rt3_temporal_set_motion_input); 0 = none"""
         self.check(self.lib.rt3_temporal_set_motion_input(self.h, int(motion_image)))
 
+    def adaptive_set_params(self, params=None, **kw):
+        """parameters of the "adaptive" pass (rt3_adaptive_set_params): an L.AdaptiveParams, or its fields as keywords; nothing = the defaults"""
+        if params is None and kw:
+            params = L.AdaptiveParams(**kw)
+        self.check(self.lib.rt3_adaptive_set_params(self.h, C.byref(params) if params is not None else None))
+
+    def adaptive_info(self):
+        """(rounds, paths_traced, pixels_capped) of the last "adaptive" launch (rt3_adaptive_info)"""
+        r, p, k = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        self.check(self.lib.rt3_adaptive_info(self.h, C.byref(r), C.byref(p), C.byref(k)))
+        return r.value, p.value, k.value
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

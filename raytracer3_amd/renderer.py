@@ -5,6 +5,7 @@ Per frame, three passes exactly as the old shaders were wired:
   RayTracingPass("gbuffer")        -> packed G-buffer + depth                 shaders/old/gbuffer.slang
   RayTracingPass("refrence_mode")  -> Light (RGBA32F linear radiance)          shaders/old/refrence_mode.slang
   ComputePass("postprocess")       -> display image (AgX)                      shaders/old/postprocess.slang
+(or, on request, RayTracingPass("adaptive") in its place: the same paths up to a noise threshold),
 with, on request, ComputePass("temporal") and / or ComputePass("denoise") between the last two (no reference counterpart: the reprojected
 accumulation of DESIGN.md section 4g and the a-trous filter of section 4f), and RayTracingPass("motion") in front of "temporal" in a frame
 whose instances moved (section 4h) or whose vertices were updated (section 4i),
@@ -48,11 +49,13 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
-def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False):
+def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
     `temporal`, the "temporal" node accumulates `Light` with the reprojected history into `accumulated`; with `denoise`, the "denoise"
     node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them.  With `motion`, the "motion" node is
-    in the list too (handle `motion`); "temporal" reads its image as context state, so it is a root of its own, drawn first."""
+    in the list too (handle `motion`); "temporal" reads its image as context state, so it is a root of its own, drawn first.  With
+    `adaptive`, the "adaptive" node takes the place of "refrence_mode" (GConst.samples is then the cap; parameters: ctx.adaptive_set_params)
+    and writes the image `AdaptiveMoments` as well (handle `adaptive_moments`: {S1, S2, n, stopped before the cap})."""
     gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
     depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
     light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
@@ -61,8 +64,13 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     handles = dict(gbuffer=gbuffer, depth=depth, light=light, prev=prev, color=out)
     gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
           .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
-    pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
-          .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
+    if adaptive:
+        handles["adaptive_moments"] = am = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "AdaptiveMoments")
+        pt = (RayTracingPass.new(rg, "adaptive").shader("adaptive").constants(gconst)
+              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).write(IMPORTED, am).launch(WorkSize2D.FullScreen))
+    else:
+        pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
+              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
     src, lit = pt, light
     if motion:
         handles["motion"] = motion_node(rg, gconst)[1]
@@ -240,11 +248,11 @@ class PathTracer:
         g.pad[0] = flags
         return g
 
-    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False):
+    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
         """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
         denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""
         self.rg.begin_frame()
-        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion)
+        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion, adaptive)
         return self.handles
 
     def denoise(self, gconst, wait=True, temporal=False, denoise=True):
@@ -346,18 +354,23 @@ class PathTracer:
         W, H = self.window
         self.rg.upload(self.handles["prev_atlas"], self.rg.download(self.handles["atlas"], (H // 16 * 8, W // 16 * 8, 4), np.float32))
 
-    def render(self, gconst, postprocess=False, wait=True, denoise=False, temporal=False):
+    def render(self, gconst, postprocess=False, wait=True, denoise=False, temporal=False, adaptive=None):
         """One frame.  `temporal` accumulates it with the reprojected history of the previous temporal frame (this object keeps two sets
         of history images, the previous G-buffer, depth and GConst, and starts from zeros after set_scene / reset_history); with
         `denoise` too, the filter reads the accumulated image and its temporal variance.  One rank only: see denoise().  After
         set_instances() moved something or update_vertices() deformed something, the frame has the "motion" node as well (handle `motion`)
-        and "temporal" follows the instances and the deformed geometries."""
+        and "temporal" follows the instances and the deformed geometries.
+        `adaptive`: an L.AdaptiveParams (or True for the parameters the context holds): the "adaptive" pass renders `Light` instead of
+        "refrence_mode", with gconst.samples as the cap; its Moments image is the handle `adaptive_moments` (adaptive_moments(),
+        sample_counts(), ctx.adaptive_info())."""
+        if adaptive is not None and adaptive is not True and adaptive is not False:
+            self.ctx.adaptive_set_params(adaptive)
         motion = False
         if temporal:
             motion = self._begin_temporal(gconst, denoise)
         elif denoise:
             self.ctx.set_denoise_variance_input(0)
-        h = self.commands(gconst, postprocess, denoise, temporal, motion)
+        h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive is not None and adaptive is not False)
         if motion:
             self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
@@ -387,6 +400,15 @@ class PathTracer:
         """(History, Moments) of the "temporal" pass"""
         W, H = self.window
         return self.rg.download(self.handles["history"], (H, W, 4), np.float32), self.rg.download(self.handles["moments"], (H, W, 4), np.float32)
+
+    def adaptive_moments(self):
+        """Moments of the "adaptive" pass: {S1, S2, n, 1 = stopped before the cap} per foreground pixel, 0 for background"""
+        W, H = self.window
+        return self.rg.download(self.handles["adaptive_moments"], (H, W, 4), np.float32)
+
+    def sample_counts(self):
+        """the samples each pixel got in the last adaptive frame (H, W) uint32; 0 = background"""
+        return self.adaptive_moments()[..., 2].astype(np.uint32)
 
     def motion(self):
         """the "motion" pass's image of the last frame that had one"""

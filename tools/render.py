@@ -12,6 +12,9 @@
   python tools/render.py --scene atrium --size 1920x1080 --spp 1 --temporal 16 --denoise --out atrium_1spp_temporal.png
                          (16 frames of 1 spp along a small camera move through the "temporal" pass of DESIGN.md section 4g -- reprojected
                          accumulation -- and, with --denoise, the a-trous filter fed with its variance; the last frame is written)
+  python tools/render.py --scene atrium --size 1920x1080 --spp 256 --adaptive 0.05 --spp-map atrium_spp.png --out atrium_adaptive.png
+                         (the "adaptive" pass of DESIGN.md section 4l: --spp is the cap, pixels stop at a relative standard error of
+                         0.05; --spp-map writes the sample counts as a grey PNG, white = the cap)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -42,6 +45,11 @@ def main():
     ap.add_argument("--denoise-iterations", type=int, default=5, help="a-trous iterations of --denoise (0..8)")
     ap.add_argument("--temporal", type=int, default=0, metavar="N",
                     help="render N frames of --spp along a small camera move through the 'temporal' pass and write the last one (replaces --passes)")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
+                    help="render with the 'adaptive' pass: --spp is the cap, a pixel stops at this relative standard error of its mean")
+    ap.add_argument("--min-spp", type=int, default=16, help="with --adaptive: samples every pixel gets first")
+    ap.add_argument("--step", type=int, default=16, help="with --adaptive: samples per later round")
+    ap.add_argument("--spp-map", default=None, help="with --adaptive: write the per-pixel sample counts as a grey PNG here (white = the cap)")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
@@ -80,6 +88,11 @@ def main():
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
+    adaptive = None
+    if args.adaptive is not None:
+        if args.temporal:
+            ap.error("--adaptive renders single frames: it does not combine with --temporal")
+        adaptive = L.AdaptiveParams(min_samples=args.min_spp, step=args.step, threshold=args.adaptive)
     cam = Camera(cam_kw["position"], cam_kw["direction"], math.radians(cam_kw["fov_deg"]), W / H)
     history, t0 = [], time.perf_counter()
     for k in range(args.temporal):  # the camera slides and turns by a few pixels per frame; every frame reprojects the one before
@@ -91,7 +104,7 @@ def main():
     for p in range(args.passes if not args.temporal else 0):
         g = pt.make_gconst(cam, args.spp, args.bounces, frame=p, blendfactor=1.0 / (p + 1), flags=flags)
         last = p == args.passes - 1
-        pt.render(g, postprocess=last, denoise=args.denoise and last)
+        pt.render(g, postprocess=last, denoise=args.denoise and last, adaptive=adaptive)
         if args.curve:
             history.append(pt.light()[..., :3].copy())
         if p != args.passes - 1:
@@ -105,6 +118,15 @@ def main():
     Image.fromarray(img8).save(args.out)
     rays = st.extension_rays + st.shadow_rays
     print(f"{args.out}: {W}x{H} {args.temporal or args.passes} x {args.spp} spp, {rays / 1e6:.0f} Mrays in {dt:.2f} s ({rays / dt / 1e6:.0f} Mrays/s incl. host), mean radiance {light[..., :3].mean():.4f}")
+    if adaptive is not None:  # of the last pass
+        n = pt.sample_counts()
+        rounds, paths, capped = pt.ctx.adaptive_info()
+        fgn = n[n > 0]
+        print(f"adaptive: threshold {args.adaptive}, cap {args.spp}: {rounds} rounds, {paths / 1e6:.1f} M paths, mean {fgn.mean() if fgn.size else 0:.1f} spp over "
+              f"{fgn.size} foreground pixels, {capped} at the cap")
+        if args.spp_map:
+            Path(args.spp_map).parent.mkdir(parents=True, exist_ok=True)
+            Image.fromarray((n.astype(np.float64) * (255.0 / max(1, args.spp)) + 0.5).astype(np.uint8)).save(args.spp_map)
     if args.curve:
         ref = history[-1].astype(np.float64)
         curve = [{"spp": (i + 1) * args.spp, "rmse_vs_final": float(np.sqrt(np.mean((h - ref) ** 2)))} for i, h in enumerate(history[:-1])]
