@@ -569,6 +569,34 @@ typedef struct rt3_adaptive_params {
 } rt3_adaptive_params;
 int rt3_adaptive_set_params(rt3_ctx *ctx, const rt3_adaptive_params *params);
 int rt3_adaptive_info(rt3_ctx *ctx, uint32_t *rounds, uint64_t *paths_traced, uint32_t *pixels_capped);
+/* ---- per-sample camera rays: pixel-filter antialiasing and a thin lens.  No reference counterpart; DESIGN.md section 4m.  By default every
+ *      sample of a pixel starts at the G-buffer's hit, the one through the pixel centre.  With a lens set, "refrence_mode" gives every sample
+ *      its own camera ray instead: sample s (absolute index, 0 .. samples-1) of pixel (px, py) draws four numbers at the RNG indices
+ *      0x80000000 + 4 s + k of the pixel's stream (seed as for the path's vertices, no blue-noise shift): k = 0, 1 place the film point in
+ *      the box of width pixel_jitter pixels around the pixel centre, k = 2, 3 a point on the lens disk of radius aperture_radius around the
+ *      eye, in the plane of view_inverse's columns 0 and 1 (uniform in area).  The ray leaves the lens point towards the point where the
+ *      pinhole ray through the film point meets the plane of focus, at view depth focus_distance.  It is traced like every extension ray
+ *      (from t = 0.001), and its hit is shaded as a path vertex from the shading records, not from the G-buffer: materials at vertex 0 are
+ *      not quantised, so a lens frame is not the default frame plus jitter.  A camera ray that escapes adds the sky's bilinear radiance along
+ *      its direction (nothing without a sky), once.  Every listed pixel is written: Light = (sum over samples) / samples, then the blend with
+ *      PrevLight, on pixels whose centre sees the background too.
+ *      A non-NULL call switches this on, {0, f, 0} included (a per-sample pinhole through the pixel centre); NULL switches it off, the
+ *      default.  The state lives in the context; nothing is rebuilt.  RT3_E_INVALID (nothing changed) for a value that is not finite, an
+ *      aperture_radius < 0, a pixel_jitter outside [0, 1], a focus_distance <= 0 with aperture_radius > 0, or reserved != 0.
+ *      Coupled passes while a lens is set: "postprocess" takes every pixel from In (the Depth == background branch would put the pinhole sky
+ *      over half of each antialiased silhouette); "adaptive" returns RT3_E_STATE (it selects pixels by G-buffer depth); "refrence_mode" with
+ *      samples * bounces * 8 > 2^31 returns RT3_E_INVALID (the vertices' RNG indices would reach the camera's).  "gbuffer", "denoise",
+ *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres, so guiding a
+ *      depth-of-field frame by it is not supported.
+ *      rt3_camera_get_lens (either pointer may be NULL): the parameters last set (the defaults {0, 1, 1, 0} before any) and whether on. ---- */
+typedef struct rt3_lens_params {
+    float aperture_radius;  /* world units, >= 0; 0 = pinhole */
+    float focus_distance;   /* > 0 when aperture_radius > 0: distance of the plane of focus along the view axis */
+    float pixel_jitter;     /* in [0, 1]: width of the box the film point is drawn from, in pixels; 1 = the whole pixel, 0 = its centre */
+    uint32_t reserved;      /* 0 */
+} rt3_lens_params;
+int rt3_camera_set_lens(rt3_ctx *ctx, const rt3_lens_params *p);   /* NULL: off, the default */
+int rt3_camera_get_lens(rt3_ctx *ctx, rt3_lens_params *out, int *enabled);
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);
@@ -605,6 +633,9 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      30 the punctual-light function of RT3_F_NEE_PUNCTUAL (light index as u32, P xyz, N xyz -> wl xyz, shadow-range end, cs = N.wl, I' rgb) for
  *      the lights of the context, from their device records (unit directions made on the device); I' is I cone window for a point or spot
  *      light (everything zero when d = 0) and E for a directional one.  RT3_E_INVALID for an index the list does not have.
+ *      31 the camera sample of rt3_camera_set_lens (proj_inverse[16], view_inverse[16], window_size[2], aperture_radius, focus_distance,
+ *      pixel_jitter, px, py, frame, absolute sample index as u32: 41 words -> ray origin xyz, direction xyz, film point in pixels xy, lens
+ *      point in view space xy: 10 words); reads no context state.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

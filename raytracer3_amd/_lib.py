@@ -30,6 +30,7 @@ DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not
 TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
 SELFTEST_HIT_INFO = 29  # rt3_selftest_eval op: {flattened primitive (u32), bu, bv} -> Surface (11 words), hit_info of the built world
+SELFTEST_LENS = 31  # rt3_selftest_eval op: {proj_inverse, view_inverse, window, lens, px, py, frame, sample} (41 words) -> {o, d, film, lens point} (10)
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
@@ -45,6 +46,7 @@ EXPORTS = [
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
     "rt3_adaptive_set_params", "rt3_adaptive_info",
+    "rt3_camera_set_lens", "rt3_camera_get_lens",
     "rt3_scene_set_lights", "rt3_light_masses",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
@@ -102,6 +104,15 @@ class AdaptiveParams(C.Structure):
 
     def __init__(self, min_samples=16, step=16, threshold=0.05, dark=0.01, dilate=1, flags=0):
         super().__init__(min_samples, step, threshold, dark, dilate, flags)
+
+
+class LensParams(C.Structure):
+    """rt3_lens_params: per-sample camera rays.  The defaults are antialiasing over the whole pixel, no aperture."""
+
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("pixel_jitter", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self, aperture_radius=0.0, focus_distance=1.0, pixel_jitter=1.0, reserved=0):
+        super().__init__(aperture_radius, focus_distance, pixel_jitter, reserved)
 
 
 assert C.sizeof(GConst) == 304
@@ -200,6 +211,8 @@ def load():
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
         "rt3_adaptive_set_params": (i32, [vp, C.POINTER(AdaptiveParams)]),
         "rt3_adaptive_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), pu32]),
+        "rt3_camera_set_lens": (i32, [vp, C.POINTER(LensParams)]),
+        "rt3_camera_get_lens": (i32, [vp, C.POINTER(LensParams), C.POINTER(i32)]),
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),
         "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),

@@ -254,6 +254,11 @@ struct rt3_ctx {
         uint32_t rounds = 0, pixels_capped = 0;
         uint64_t paths_traced = 0;
     } adaptive;
+    // rt3_passes.hip: per-sample camera rays (rt3_camera_set_lens): off by default
+    struct Lens {
+        rt3_lens_params params = {0.0f, 1.0f, 1.0f, 0u};
+        bool on = false;
+    } lens;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot

@@ -109,6 +109,21 @@ void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixel
                        const void* prev);
 void launch_postprocess(hipStream_t st, const GConstDev& g, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width,
                         const float* depth, const void* in, void* out);
+// per-sample camera rays (rt3_lens.hip)
+// the camera rays of samples s0 .. of the listed pixels as records 0 .. n_first-1 of the extension queue `rays` (path id = record index), with
+// throughput 1 in T and radiance 0 in lacc; *count = n_first
+void launch_lens_rays(hipStream_t st, const GConstDev& g, const LensDev& lens, const uint32_t* pixels, uint32_t npix, uint32_t s0, uint32_t n_first,
+                      float* rays, float* T, float* lacc, size_t stride, uint32_t* count);
+// the sky's radiance into lacc for the records of that queue whose hit is a miss
+void launch_lens_miss(hipStream_t st, const SceneDev& sc, const float* rays, const float* hits, float* lacc, size_t stride, uint32_t n);
+// launch_accumulate for every listed pixel, background-centred ones included
+void launch_accumulate_lens(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* lacc, uint32_t sb,
+                            int first_batch, int last_batch, float* radsum, void* light, const void* prev);
+// launch_postprocess with every pixel taken from `in`
+void launch_postprocess_lens(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* in, void* out);
+// self-test op 31: lens_ray, kSelftestLensIn words in, kSelftestLensOut words out
+constexpr uint32_t kSelftestLensIn = 41, kSelftestLensOut = 10;
+void launch_selftest_lens(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
 void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst);
 void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img);
 

@@ -4,6 +4,8 @@
 // and ::adaptive.
 // rt3_pass_launch() is the drop-in for executing one pass node of the reference's frame graph (render_graph/mod.rs:80-107): the pass
 // name selects a HIP kernel sequence instead of a SPIR-V pipeline.
+// Also owns rt3_ctx::lens: per-sample camera rays (rt3_camera_set_lens), which "refrence_mode", "postprocess" and
+// "adaptive" read.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -221,6 +223,8 @@ struct PathSetup {
     SceneDev sc;
     LightsDev lights{};
     bool nee = false, nee_e = false, punct = false;
+    bool lens_on = false;  // every sample starts from its own camera ray (rt3_camera_set_lens), not from the G-buffer ...
+    LensDev lens{};        // ... made by these parameters
 };
 // (B = g->bounces >= 1; the queues must exist before an emitter queue can be sized: call after ensure_work)
 int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
@@ -245,6 +249,10 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     ps->sc = scene_dev(c);
     return RT3_OK;
 }
+LensDev lens_dev(const rt3_ctx* c) {
+    const rt3_lens_params& p = c->lens.params;
+    return LensDev{p.aperture_radius, p.focus_distance, p.pixel_jitter};
+}
 // One wavefront batch: samples s0 .. s0 + nsb - 1 of the npix listed pixels (path id = sample_in_batch * npix + index) through all B
 // bounces; each path's radiance ends up in c->work.lacc.  The loop body of "refrence_mode", and of a round of "adaptive".
 int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb, const Resource* dp, const uint32_t* pixels, const uint2* pixbn,
@@ -253,24 +261,50 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     const size_t S = c->work.cap;
     const bool nee = ps.nee, nee_e = ps.nee_e;
     const uint32_t n_first = nsb * npix;
+    const bool lens = ps.lens_on;
+    const uint32_t n_words = (nee_e ? 6 : 4) * B;
     uint32_t first;
-    if (int r = reserve_counters(c, (nee_e ? 6 : 4) * B + 1, &first)) return r;
+    // (a lens frame: two words more, the camera queue's length and the ray-pool cursor of its k_extend launch)
+    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0), &first)) return r;
     first += first & 1u;  // 8-byte aligned pairs
     // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
     uint32_t* pairs = c->work.d_counters.get() + first;
     uint32_t* pool_cur = c->work.d_counters.get() + first + 2 * B;  // [b], [B + b]: ray-pool cursors of the k_extend / k_shadow launch of bounce b
     // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
     uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
+    uint32_t* lens_cnt = c->work.d_counters.get() + first + n_words;  // [0] the camera queue's length, [1] its ray-pool cursor
     c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
     auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
     auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
     int cur = 0;
+    if (lens) {
+        // Vertex 0 of a lens frame: the camera rays become records of the extension queue rays[0], are traced as extension rays (payload:
+        // the .w words carry pdf and id, so a camera ray starts at kRayTMin like every extension ray, not at 0 like the G-buffer's), and are
+        // shaded below by k_shade<FIRST = false> at bounce 0, which reads the queue's length from lens_cnt[0].
+        {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_lens_rays(c->stream, ps.gd, ps.lens, pixels, npix, s0, n_first, c->work.rays[0].get(), c->work.T[0].get(), c->work.lacc.get(), S,
+                             lens_cnt);
+        }
+        {
+            TraceLaunch tr = ctx_trace(c);
+            tr.rays = c->work.rays[0].get(); tr.n = n_first; tr.work_counter = lens_cnt + 1; tr.hits = c->work.hits.get(); tr.payload = true;
+            c->work.primary_rays_pending += n_first;
+            ScopedTimer t(c, CAT_EXTEND);
+            launch_extend(c->stream, c->accel.bvh, tr);
+        }
+        // an escaped camera sample collects the sky once: in k_shade's miss branch with weight 1 under sky NEE, here otherwise
+        if (!nee && ps.sc.sky != nullptr) {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_lens_miss(c->stream, ps.sc, c->work.rays[0].get(), c->work.hits.get(), c->work.lacc.get(), S, n_first);
+        }
+    }
     for (uint32_t bn = 0; bn < B; bn++) {
         ShadeLaunch L;
         L.g = ps.gd; L.sc = ps.sc; L.pixels = pixels; L.pixbn = pixbn; L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
         L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
         L.in_rays = c->work.rays[cur].get(); L.in_hits = c->work.hits.get(); L.in_T = c->work.T[cur].get();
-        L.in_count = bn ? ext_cnt_at(bn - 1) : nullptr; L.n_first = n_first;
+        L.in_count = bn ? ext_cnt_at(bn - 1) : (lens ? lens_cnt : nullptr); L.n_first = n_first;
         L.out_rays = c->work.rays[cur ^ 1].get(); L.out_T = c->work.T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
         L.sh_rays = c->work.sh_rays.get(); L.sh_contrib = c->work.sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
         L.lacc = c->work.lacc.get(); L.stride = S;
@@ -278,7 +312,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
         {
             ScopedTimer t(c, CAT_SHADE);
-            launch_shade(c->stream, bn == 0, L, ps.punct);
+            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct);
         }
         cur ^= 1;
         if (nee) {
@@ -322,6 +356,8 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     const uint32_t Sspp = g->samples, B = g->bounces;
     if (Sspp == 0 || B == 0) return RT3_OK;  // GConst::default() leaves samples = bounces = 0 (renderer/mod.rs:47-63): nothing to trace
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
+    if (c->lens.on && (uint64_t)Sspp * B * 8u > (1ull << 31))
+        return fail(c, RT3_E_INVALID, "refrence_mode with a lens: samples * bounces * 8 may not exceed 2^31 (the camera's RNG indices start there)");
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     const uint32_t npix = pl->count;
@@ -332,13 +368,19 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     if (int r = ensure_work(c, (size_t)sb * npix, npix)) return r;
     PathSetup ps;
     if (int r = path_setup(c, g, &ps)) return r;
+    ps.lens_on = c->lens.on;
+    ps.lens = lens_dev(c);
     for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
         const uint32_t nsb = std::min(sb, Sspp - s0);
         if (int r = trace_batch(c, ps, W, gb, dp, pl->dev.get(), pl->dev_bn.get(), npix, s0, nsb)) return r;
         {
             ScopedTimer t(c, CAT_OTHER);
-            launch_accumulate(c->stream, ps.gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->work.lacc.get(), c->work.cap, nsb, s0 == 0, s0 + nsb >= Sspp,
-                              c->work.radsum.get(), li->ptr, pv->ptr);
+            if (ps.lens_on)  // every listed pixel: one whose centre sees the background may be partly covered
+                launch_accumulate_lens(c->stream, ps.gd, pl->dev.get(), npix, W, c->work.lacc.get(), nsb, s0 == 0, s0 + nsb >= Sspp, c->work.radsum.get(),
+                                       li->ptr, pv->ptr);
+            else
+                launch_accumulate(c->stream, ps.gd, pl->dev.get(), npix, W, (const float*)dp->ptr, c->work.lacc.get(), c->work.cap, nsb, s0 == 0, s0 + nsb >= Sspp,
+                                  c->work.radsum.get(), li->ptr, pv->ptr);
         }
     }
     HIPC(c, hipGetLastError());
@@ -354,6 +396,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     const uint32_t cap = g->samples, B = g->bounces;
     c->adaptive.rounds = c->adaptive.pixels_capped = 0;
     c->adaptive.paths_traced = 0;
+    if (c->lens.on)
+        return fail(c, RT3_E_STATE, "adaptive: not with a lens set (rt3_camera_set_lens): the pass selects pixels by G-buffer depth, which knows nothing "
+                                    "of partly covered pixels; switch the lens off (NULL) or use refrence_mode");
     if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     PixelList* pl;
@@ -438,7 +483,10 @@ int pass_postprocess(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Re
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     if (pl->count == 0) return RT3_OK;
     ScopedTimer t(c, CAT_OTHER);
-    launch_postprocess(c->stream, gconst_dev(g), scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
+    if (c->lens.on)  // a lens frame's Light holds the sky already, antialiased (rt3_camera_set_lens)
+        launch_postprocess_lens(c->stream, pl->dev.get(), pl->count, W, in->ptr, out->ptr);
+    else
+        launch_postprocess(c->stream, gconst_dev(g), scene_dev(c), pl->dev.get(), pl->count, W, (const float*)dp->ptr, in->ptr, out->ptr);
     HIPC(c, hipGetLastError());
     return RT3_OK;
 }
@@ -757,6 +805,29 @@ int rt3_adaptive_info(rt3_ctx* c, uint32_t* rounds, uint64_t* paths_traced, uint
     if (rounds) *rounds = c->adaptive.rounds;
     if (paths_traced) *paths_traced = c->adaptive.paths_traced;
     if (pixels_capped) *pixels_capped = c->adaptive.pixels_capped;
+    return RT3_OK;
+}
+int rt3_camera_set_lens(rt3_ctx* c, const rt3_lens_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->lens.on = false;
+        return RT3_OK;
+    }
+    if (!std::isfinite(p->aperture_radius) || !std::isfinite(p->focus_distance) || !std::isfinite(p->pixel_jitter))
+        return fail(c, RT3_E_INVALID, "lens params: every value must be finite");
+    if (!(p->aperture_radius >= 0.0f)) return fail(c, RT3_E_INVALID, "lens params: aperture_radius must not be negative");
+    if (!(p->pixel_jitter >= 0.0f && p->pixel_jitter <= 1.0f)) return fail(c, RT3_E_INVALID, "lens params: pixel_jitter must lie in [0, 1]");
+    if (p->aperture_radius > 0.0f && !(p->focus_distance > 0.0f))
+        return fail(c, RT3_E_INVALID, "lens params: focus_distance must be positive when aperture_radius is");
+    if (p->reserved != 0u) return fail(c, RT3_E_INVALID, "lens params: reserved must be 0");
+    c->lens.params = *p;
+    c->lens.on = true;
+    return RT3_OK;
+}
+int rt3_camera_get_lens(rt3_ctx* c, rt3_lens_params* out, int* enabled) {
+    if (!c) return RT3_E_INVALID;
+    if (out) *out = c->lens.params;
+    if (enabled) *enabled = c->lens.on ? 1 : 0;
     return RT3_OK;
 }
 int rt3_temporal_set_prev_view(rt3_ctx* c, const void* prev_gconst, size_t size) {

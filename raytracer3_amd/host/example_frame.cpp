@@ -214,6 +214,14 @@ int main(int argc, char** argv) {
             printf("example_frame: two temporal frames %ux%u, %llu frames drawn\n", W, H, (unsigned long long)rg.frame_number);
             return 0;
         }
+        {  // the lens wrapper: set, read back, off again -- the frame below is the frame of a context that never had one
+            rt3_lens_params lp;
+            ctx.set_lens(0.125f, 2.0f);
+            if (!ctx.get_lens(&lp) || lp.aperture_radius != 0.125f || lp.focus_distance != 2.0f || lp.pixel_jitter != 1.0f)
+                throw std::runtime_error("set_lens / get_lens disagree");
+            ctx.set_lens(nullptr);
+            if (ctx.get_lens(&lp)) throw std::runtime_error("set_lens(nullptr) left the lens on");
+        }
         auto gbuffer = rg.image(rt3::ImageSize::FullScreen(), RT3_FORMAT_R32G32B32A32_UINT, "gbuffer");
         auto depth = rg.image(rt3::ImageSize::FullScreen(), RT3_FORMAT_R32_SFLOAT, "gbuffer_depth");
         auto light = rg.image(rt3::ImageSize::FullScreen(), RT3_FORMAT_R32G32B32A32_SFLOAT, "Light");

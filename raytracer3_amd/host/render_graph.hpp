@@ -107,6 +107,18 @@ class Context {
     void adaptive_info(uint32_t* rounds, uint64_t* paths_traced, uint32_t* pixels_capped) const {
         check(rt3_adaptive_info(ctx_, rounds, paths_traced, pixels_capped), "rt3_adaptive_info");
     }
+    // per-sample camera rays (no reference counterpart): antialiasing over the pixel and a thin lens for the
+    // "refrence_mode" frames that follow; nullptr = off, the default.  While set, "postprocess" shows In everywhere and "adaptive" is refused
+    void set_lens(const rt3_lens_params* p) const { check(rt3_camera_set_lens(ctx_, p), "rt3_camera_set_lens"); }
+    void set_lens(float aperture, float focus, float jitter = 1.0f) const {
+        const rt3_lens_params p = {aperture, focus, jitter, 0u};
+        set_lens(&p);
+    }
+    bool get_lens(rt3_lens_params* out) const {
+        int on = 0;
+        check(rt3_camera_get_lens(ctx_, out, &on), "rt3_camera_get_lens");
+        return on != 0;
+    }
     // previous vertex positions: "motion" follows meshes that update_vertices deforms after a snapshot
     void snapshot_vertices() const { check(rt3_scene_snapshot_vertices(ctx_), "rt3_scene_snapshot_vertices"); }
     void forget_prev_vertices() const { check(rt3_scene_forget_prev_vertices(ctx_), "rt3_scene_forget_prev_vertices"); }

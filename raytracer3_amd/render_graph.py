@@ -382,6 +382,18 @@ class Context:
         self.check(self.lib.rt3_adaptive_info(self.h, C.byref(r), C.byref(p), C.byref(k)))
         return r.value, p.value, k.value
 
+    def set_lens(self, params=None, **kw):
+        """per-sample camera rays (rt3_camera_set_lens): an L.LensParams, or its fields as keywords; nothing = off"""
+        if params is None and kw:
+            params = L.LensParams(**kw)
+        self.check(self.lib.rt3_camera_set_lens(self.h, C.byref(params) if params is not None else None))
+
+    def get_lens(self):
+        """(L.LensParams last set, whether a lens is on) (rt3_camera_get_lens)"""
+        p, on = L.LensParams(), C.c_int()
+        self.check(self.lib.rt3_camera_get_lens(self.h, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

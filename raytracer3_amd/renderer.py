@@ -248,6 +248,16 @@ class PathTracer:
         g.pad[0] = flags
         return g
 
+    def set_lens(self, aperture=0.0, focus=1.0, jitter=1.0):
+        """Per-sample camera rays for the frames that follow (ctx.set_lens): `jitter` is the width in pixels of the
+        box each sample's film point is drawn from (1 = antialiasing over the whole pixel), `aperture` the lens radius in world units
+        (0 = pinhole), `focus` the view depth of the plane of focus.  set_lens(None) switches back to one primary hit per pixel.  With a
+        lens, "postprocess" shows `Light` everywhere and adaptive frames are refused."""
+        if aperture is None:
+            self.ctx.set_lens(None)
+        else:
+            self.ctx.set_lens(L.LensParams(aperture, focus, jitter))
+
     def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
         """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
         denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""

@@ -15,6 +15,8 @@
   python tools/render.py --scene atrium --size 1920x1080 --spp 256 --adaptive 0.05 --spp-map atrium_spp.png --out atrium_adaptive.png
                          (the "adaptive" pass of DESIGN.md section 4l: --spp is the cap, pixels stop at a relative standard error of
                          0.05; --spp-map writes the sample counts as a grey PNG, white = the cap)
+  python tools/render.py --scene atrium --size 1920x1080 --spp 256 --aa --aperture 0.05 --focus 8 --out atrium_dof.png
+                         (per-sample camera rays, DESIGN.md section 4m: --aa antialiases over the pixel, --aperture / --focus add a thin lens)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -50,6 +52,9 @@ def main():
     ap.add_argument("--min-spp", type=int, default=16, help="with --adaptive: samples every pixel gets first")
     ap.add_argument("--step", type=int, default=16, help="with --adaptive: samples per later round")
     ap.add_argument("--spp-map", default=None, help="with --adaptive: write the per-pixel sample counts as a grey PNG here (white = the cap)")
+    ap.add_argument("--aa", action="store_true", help="per-sample camera rays: every sample's film point is drawn from the whole pixel (DESIGN.md section 4m)")
+    ap.add_argument("--aperture", type=float, default=0.0, metavar="R", help="thin lens of radius R (world units); implies per-sample camera rays")
+    ap.add_argument("--focus", type=float, default=1.0, metavar="F", help="with --aperture: view depth of the plane of focus")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
@@ -88,6 +93,10 @@ def main():
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
+    if args.aa or args.aperture > 0.0:
+        if args.adaptive is not None or args.temporal or args.denoise:
+            ap.error("--aa / --aperture render plain frames: the adaptive pass refuses a lens, and the temporal and denoise passes are guided by the pinhole G-buffer")
+        pt.set_lens(args.aperture, args.focus, 1.0)
     adaptive = None
     if args.adaptive is not None:
         if args.temporal:
