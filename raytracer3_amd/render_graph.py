@@ -139,7 +139,7 @@ class Context:
 
     def check(self, rc):
         if rc != 0:
-            raise L.Rt3Error(rc, self.lib.rt3_last_error(self.h).decode())
+            raise L.Rt3Error(rc, self.last_error())
 
     def close(self):
         if getattr(self, "h", None):
@@ -402,6 +402,14 @@ class Context:
         self.check(self.lib.rt3_stats_get(self.h, C.byref(s)))
         return s
 
+    def pass_launch(self, name, x, y, z, gconst, bindings, entry="main") -> int:
+        """rt3_pass_launch of pass `name` over x * y * z with the handles `bindings`; returns the code (check() raises on one)"""
+        b = (C.c_uint32 * max(1, len(bindings)))(*bindings)
+        return self.lib.rt3_pass_launch(self.h, name.encode(), entry.encode(), x, y, z, C.byref(gconst), C.sizeof(gconst), b, len(bindings))
+
+    def last_error(self) -> str:
+        return self.lib.rt3_last_error(self.h).decode()
+
     def wait(self):
         self.check(self.lib.rt3_frame_wait(self.h))
 
@@ -572,10 +580,7 @@ class RenderGraph:
         for ni in self.bake(roots[-1]):
             n = self.nodes[ni]
             x, y, z = (*n.size.size(self.window), 1) if n.kind == "raytracing" else n.size.size(self.window)
-            b = (C.c_uint32 * len(n.edges))(*[e.resource for e in n.edges])  # bake.rs:51-83
-            cst = n.constants
-            self.ctx.check(self.ctx.lib.rt3_pass_launch(self.ctx.h, n.path.encode(), n.entry.encode(), x, y, z, C.byref(cst), C.sizeof(cst),
-                                                        b, len(n.edges)))
+            self.ctx.check(self.ctx.pass_launch(n.path, x, y, z, n.constants, [e.resource for e in n.edges], n.entry))  # bake.rs:51-83
         self.frame_number += 1
         if wait:
             self.ctx.wait()

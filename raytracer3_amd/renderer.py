@@ -14,6 +14,7 @@ and, as a second frame description, the probe-GI chain of the old shaders (SURVE
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -49,33 +50,43 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
-def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
+def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False, *,
+                gbuffer_names=("gbuffer", "gbuffer_depth"), gbuffer_node=True, trace=True):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
     `temporal`, the "temporal" node accumulates `Light` with the reprojected history into `accumulated`; with `denoise`, the "denoise"
     node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them.  With `motion`, the "motion" node is
     in the list too (handle `motion`); "temporal" reads its image as context state, so it is a root of its own, drawn first.  With
     `adaptive`, the "adaptive" node takes the place of "refrence_mode" (GConst.samples is then the cap; parameters: ctx.adaptive_set_params)
-    and writes the image `AdaptiveMoments` as well (handle `adaptive_moments`: {S1, S2, n, stopped before the cap})."""
-    gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, "gbuffer")
-    depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, "gbuffer_depth")
-    light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
-    prev = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "PrevLight")
-    out = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "color")
-    handles = dict(gbuffer=gbuffer, depth=depth, light=light, prev=prev, color=out)
-    gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
-          .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
-    if adaptive:
-        handles["adaptive_moments"] = am = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "AdaptiveMoments")
-        pt = (RayTracingPass.new(rg, "adaptive").shader("adaptive").constants(gconst)
-              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).write(IMPORTED, am).launch(WorkSize2D.FullScreen))
-    else:
-        pt = (RayTracingPass.new(rg, "refrence_mode").shader("refrence_mode").constants(gconst)
-              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, prev).launch(WorkSize2D.FullScreen))
-    src, lit = pt, light
+    and writes the image `AdaptiveMoments` as well (handle `adaptive_moments`: {S1, S2, n, stopped before the cap}).
+    A frame over a `Light` that is already there (PathTracer.denoise) is the same chain with other ends: `trace=False` imports `Light`
+    (no path-trace node, hence no `prev`, and no `color` unless `postprocess`), `gbuffer_node=False` imports the G-buffer too, and
+    `gbuffer_names` are the images the G-buffer and its depth live in."""
+    full, f4 = ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT
+    gbuffer = rg.image(full, L.FORMAT_R32G32B32A32_UINT, gbuffer_names[0])
+    depth = rg.image(full, L.FORMAT_R32_SFLOAT, gbuffer_names[1])
+    light = rg.image(full, f4, "Light")
+    handles = dict(gbuffer=gbuffer, depth=depth, light=light)
+    if trace:
+        handles["prev"] = rg.image(full, f4, "PrevLight")
+    if trace or postprocess:
+        handles["color"] = rg.image(full, f4, "color")
+    gb = src = IMPORTED
+    if gbuffer_node:
+        gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
+              .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
+    if trace:
+        name = "adaptive" if adaptive else "refrence_mode"
+        pt = (RayTracingPass.new(rg, name).shader(name).constants(gconst)
+              .read(gb, gbuffer).read(gb, depth).write(IMPORTED, light).read(IMPORTED, handles["prev"]))
+        if adaptive:
+            handles["adaptive_moments"] = rg.image(full, f4, "AdaptiveMoments")
+            pt.write(IMPORTED, handles["adaptive_moments"])
+        src = pt.launch(WorkSize2D.FullScreen)
+    lit = light
     if motion:
         handles["motion"] = motion_node(rg, gconst)[1]
     if temporal:
-        src, th = temporal_node(rg, gconst, gb, gbuffer, depth, pt, light)
+        src, th = temporal_node(rg, gconst, gb, gbuffer, depth, src, light)
         handles.update(th)
         lit = th["accumulated"]
     if denoise:
@@ -83,7 +94,7 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         handles["denoised"] = lit
     if postprocess:
         (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
-         .read(gb, depth).write(IMPORTED, out).read(src, lit).dispatch(DispatchSize.FullScreen))
+         .read(gb, depth).write(IMPORTED, handles["color"]).read(src, lit).dispatch(DispatchSize.FullScreen))
     return handles
 
 
@@ -132,115 +143,153 @@ def _instance_key(instances):
             [np.ascontiguousarray(np.asarray(m, np.float32)).view(np.uint32).tolist() for _, _, m in instances])
 
 
+class _TemporalHistory:
+    """What the next temporal frame needs to know of the last one: its view, the instance list it was rendered with, and whether the
+    context holds the vertex positions as they were then."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.prev_gconst = None     # the view of the frame whose G-buffer / History / Moments the images hold; None = no history
+        self.instances = None       # the list the structure was built for; None = never set
+        self.prev_instances = None  # ... and the one the last temporal frame was rendered with
+        self.snapshot = False       # the context holds a snapshot of the vertex positions (ctx.snapshot_vertices)
+        self.verts_updated = False  # vertices updated since the last temporal frame (the snapshot was taken before the first upload)
+
+    def reset(self):
+        self.prev_gconst = None
+        self.verts_updated = False
+        if self.snapshot:
+            self.ctx.forget_prev_vertices()
+            self.snapshot = False
+
+    def scene_set(self):
+        self.snapshot = False  # (new vertices: the context forgot it)
+        self.reset()
+
+    def instances_set(self, instances):
+        """A list with other geometry runs (another count included), and the first list set, start the history over."""
+        if self.instances is None or _instance_key(instances)[0] != _instance_key(self.instances)[0]:
+            self.reset()
+        self.instances = instances
+
+    def vertices_updated(self):
+        """before the upload: between temporal frames the positions of the last one are kept, once per frame interval"""
+        if self.prev_gconst is not None and not self.verts_updated:
+            self.ctx.snapshot_vertices()
+            self.snapshot = True
+        self.verts_updated = True
+
+    def begin_frame(self):
+        """Hand the context what moved since the last temporal frame; returns whether anything did (the frame then needs "motion")."""
+        # instances that moved: hand over the last frame's matrices
+        moved = (self.prev_gconst is not None and self.instances is not None and self.prev_instances is not None
+                 and _instance_key(self.instances) != _instance_key(self.prev_instances))
+        self.ctx.set_prev_transforms([m for _, _, m in self.prev_instances] if moved else None)
+        # vertices updated: vertices_updated() took the snapshot, "motion" follows the deformed geometries.  No update since: the snapshot
+        # is brought up to the current positions (a copy of the ranges last updated), so nothing is deformed
+        deformed = self.prev_gconst is not None and self.verts_updated and self.snapshot
+        if self.snapshot and not deformed:
+            self.ctx.snapshot_vertices()
+        return moved or deformed
+
+    def end_frame(self, gconst):
+        self.prev_gconst = L.GConst()
+        C.memmove(C.byref(self.prev_gconst), C.byref(gconst), C.sizeof(gconst))
+        self.prev_instances = self.instances
+        self.verts_updated = False
+
+
 class PathTracer:
     """One GPU's share of the frame.  `rank` / `n_ranks` select the interleaved 64x64 tiles this process renders."""
 
-    def __init__(self, window, device=0, rank=0, n_ranks=1):
+    def __init__(self, window, device=0, rank=0, n_ranks=1, ctx=None):
         self.window = (int(window[0]), int(window[1]))
-        self.ctx = Context(device)
+        self.ctx = Context(device) if ctx is None else ctx
         self.rank, self.n_ranks = rank, n_ranks
         self.ctx.set_tile_partition(self.window[0], self.window[1], rank, n_ranks)
         self.rg = RenderGraph(self.ctx, self.window)
-        self._accel = None
+        self.handles = {}
         self.comm_ready = False  # True once init_comm() has joined librt3's RCCL communicator
         self._stage = None       # rehearsal path only: staging buffer of the host-moved gather
         self.host_group = None   # process group of the host-moved gather (None = the default group)
-        self._prev_gconst = None  # "temporal": the view of the frame whose G-buffer / History / Moments the images hold; None = no history
-        self._instances = None    # set_instances: the list the structure was built for; None = never called
-        self._prev_instances = None  # ... and the one the last temporal frame was rendered with
-        self._snapshot = False        # the context holds a snapshot of the vertex positions (ctx.snapshot_vertices)
-        self._verts_updated = False   # update_vertices() since the last temporal frame (it took the snapshot before its first upload)
+        self._history = _TemporalHistory(self.ctx)
 
     def close(self):
         self.ctx.close()
 
-    def set_scene(self, mesh, sky=None, bluenoise=None):
+    def set_scene(self, mesh, sky=None, bluenoise=None, *, instances=None, options=()):
+        """Upload the world and build its acceleration structure once.  `options`: (L.OPT_*, value) pairs set first; `instances`: the list
+        set_instances() would take, placed before the build."""
+        for opt, value in options:
+            self.ctx.set_option(opt, value)
         self.ctx.upload_mesh(mesh)  # (with the mesh's punctual lights, when it has some)
         if not len(getattr(mesh, "lights", ())):
             self.ctx.set_lights(None)  # the lights belong to the world: a scene without them replaces the previous scene's
-        self._snapshot = False  # (new vertices: the context forgot it)
+        if instances is not None:
+            instances = self._upload_instances(instances)
         if sky is not None:
             self.ctx.set_sky(sky)
         if bluenoise is not None:
             self.ctx.set_bluenoise(bluenoise)
-        self._accel = self.ctx.build_accel()
-        self.reset_history()
+        self.ctx.build_accel()
+        self._history.scene_set()
+        if instances is not None:
+            self._history.instances_set(instances)
 
     def set_lights(self, lights=None):
         """Replace the world's punctual lights (assets.LIGHT_DTYPE; None forgets them).  No rebuild: frames with F_NEE_PUNCTUAL in their
         flags sample them from the next frame on.  Moved lights' shadows lag in temporal history like any moved light."""
         self.ctx.set_lights(lights)
 
+    def _upload_instances(self, instances):
+        instances = [(int(f), int(n), np.array(m, np.float32)) for f, n, m in instances]
+        self.ctx.set_instances(instances)
+        return instances
+
     def set_instances(self, instances):
         """Place the scene's geometries: upload the list (ctx.set_instances) and rebuild.  The next temporal frame compares it with the
         list of the last one and, where matrices differ, runs the "motion" pass so that moved instances keep their history.  A list with
         other geometry runs (another count included), and the first list set, start the history over."""
-        instances = [(int(f), int(n), np.array(m, np.float32)) for f, n, m in instances]
-        self.ctx.set_instances(instances)
-        self._accel = self.ctx.build_accel()
-        if self._instances is None or _instance_key(instances)[0] != _instance_key(self._instances)[0]:
-            self.reset_history()
-        self._instances = instances
+        instances = self._upload_instances(instances)
+        self.ctx.build_accel()
+        self._history.instances_set(instances)
 
     def reset_history(self):
         """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
-        self._prev_gconst = None
-        self._verts_updated = False
-        if self._snapshot:
-            self.ctx.forget_prev_vertices()
-            self._snapshot = False
+        self._history.reset()
 
     def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth")):
         """Before a temporal frame's nodes are built: what the last temporal frame wrote, and the G-buffer it read (the images named
         `gbuffer_names`), become `Prev*` (the images trade names, like swap_light_prev), or, with no history, zeros are uploaded; the
         previous view and the variance input of "denoise" are set.  A frame rendered without `temporal` in between overwrites the kept
-        G-buffer: call reset_history() after one."""
-        rg = self.rg
+        G-buffer: call reset_history() after one.  Returns whether the frame needs the "motion" node."""
+        rg, prev_gconst = self.rg, self._history.prev_gconst
         temporal_images(rg)
         for name, fmt in zip(gbuffer_names, (L.FORMAT_R32G32B32A32_UINT, L.FORMAT_R32_SFLOAT)):
             rg.image(ImageSize.FullScreen, fmt, name)
-        if self._prev_gconst is not None:
+        if prev_gconst is not None:
             n = rg.named
             for a, b in TEMPORAL_SWAPS + ((gbuffer_names[0], "PrevGbuffer"), (gbuffer_names[1], "PrevDepth")):
                 n[a], n[b] = n[b], n[a]
         t = temporal_images(rg)
-        if self._prev_gconst is None:
+        if prev_gconst is None:
             W, H = self.window
             zero = np.zeros((H, W, 4), np.float32)
             rg.upload(t["prev_history"], zero)
             rg.upload(t["prev_moments"], zero)
-        self.ctx.set_prev_view(self._prev_gconst if self._prev_gconst is not None else gconst)
+        self.ctx.set_prev_view(prev_gconst if prev_gconst is not None else gconst)
         self.ctx.set_denoise_variance_input(t["moments"] if denoise else 0)
-        # instances that moved since the last temporal frame: hand over its matrices and let "temporal" read the "motion" pass's image
-        moved = (self._prev_gconst is not None and self._instances is not None and self._prev_instances is not None
-                 and _instance_key(self._instances) != _instance_key(self._prev_instances))
-        self.ctx.set_prev_transforms([m for _, _, m in self._prev_instances] if moved else None)
-        # vertices updated since the last temporal frame: update_vertices() took the snapshot, "motion" follows the deformed geometries.  No
-        # update since: the snapshot is brought up to the current positions (a copy of the ranges last updated), so nothing is deformed
-        deformed = self._prev_gconst is not None and self._verts_updated and self._snapshot
-        if self._snapshot and not deformed:
-            self.ctx.snapshot_vertices()
-        moved = moved or deformed
+        moved = self._history.begin_frame()  # "temporal" then reads the "motion" pass's image
         self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved else 0)
         return moved
-
-    def _end_temporal(self, gconst):
-        keep = L.GConst()
-        C.memmove(C.byref(keep), C.byref(gconst), C.sizeof(keep))
-        self._prev_gconst = keep
-        self._prev_instances = self._instances
-        self._verts_updated = False
 
     def update_vertices(self, vertices, first=0):
         """deformed vertices (same topology): upload them and refit the acceleration structure.  Between temporal frames the positions as
         they were at the last one are kept first (ctx.snapshot_vertices, once per frame interval, before its first upload), and the next
         temporal frame runs the "motion" pass so that the deformed geometries keep their history."""
-        if self._prev_gconst is not None and not self._verts_updated:
-            self.ctx.snapshot_vertices()
-            self._snapshot = True
-        self._verts_updated = True
+        self._history.vertices_updated()
         self.ctx.update_vertices(vertices, first)
-        self._accel = self.ctx.refit_accel()
+        self.ctx.refit_accel()
 
     def make_gconst(self, camera: Camera, samples, bounces=4, frame=0, blendfactor=1.0, flags=DEFAULT_FLAGS) -> L.GConst:
         g = camera.gconst(self.window)
@@ -265,6 +314,19 @@ class PathTracer:
         self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion, adaptive)
         return self.handles
 
+    @contextlib.contextmanager
+    def _whole_window(self):
+        """The tile partition switched off for the launches enqueued inside: a chain that reads other tiles' pixels runs for the whole
+        window on this rank.  Launches read the partition when they are enqueued: safe to restore behind them."""
+        W, H = self.window
+        if self.n_ranks > 1:
+            self.ctx.set_tile_partition(W, H, 0, 1)
+        try:
+            yield
+        finally:
+            if self.n_ranks > 1:
+                self.ctx.set_tile_partition(W, H, self.rank, self.n_ranks)
+
     def denoise(self, gconst, wait=True, temporal=False, denoise=True):
         """Filter the `Light` of the last render() into `denoised` with the "denoise" pass (parameters: ctx.set_denoise_params).  A tap
         reads pixels of other tiles, so with several ranks this runs on the rank that holds the assembled frame -- after
@@ -279,38 +341,14 @@ class PathTracer:
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
         rg.begin_frame()
-        gbuffer = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_UINT, names[0])
-        depth = rg.image(ImageSize.FullScreen, L.FORMAT_R32_SFLOAT, names[1])
-        light = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Light")
-        gb = IMPORTED
-        if self.n_ranks > 1 or temporal:
-            gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
-                  .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
-        src, lit, extra = IMPORTED, light, {}
+        h = frame_nodes(rg, gconst, False, denoise, temporal, moved, gbuffer_names=names, gbuffer_node=self.n_ranks > 1 or temporal, trace=False)
+        self.handles = {k: v for k, v in self.handles.items() if k != "motion"} | h  # earlier frames' handles stay, but for a stale `motion`
+        with self._whole_window():
+            if moved:  # on the whole window, like the G-buffer
+                rg.draw_frame(h["motion"])
+            rg.draw_frame(h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"]), wait=wait)
         if temporal:
-            src, extra = temporal_node(rg, gconst, gb, gbuffer, depth, IMPORTED, light)
-            lit = extra["accumulated"]
-        if moved:
-            extra = dict(extra, motion=motion_node(rg, gconst)[1])
-        denoised = lit
-        if denoise:
-            _, denoised = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit)
-            extra = dict(extra, denoised=denoised)
-        self.handles = dict(getattr(self, "handles", {}), gbuffer=gbuffer, depth=depth, light=light, **extra)
-        if not moved:
-            self.handles.pop("motion", None)
-        W, H = self.window
-        if self.n_ranks > 1:
-            self.ctx.set_tile_partition(W, H, 0, 1)
-        try:
-            if moved:  # on the whole window, like the G-buffer above
-                rg.draw_frame(extra["motion"])
-            rg.draw_frame(denoised, wait=wait)
-        finally:
-            if self.n_ranks > 1:  # launches read the partition when they are enqueued: safe to restore behind them
-                self.ctx.set_tile_partition(W, H, self.rank, self.n_ranks)
-        if temporal:
-            self._end_temporal(gconst)
+            self._history.end_frame(gconst)
         return self.handles
 
     def probe_commands(self, gconst: L.GConst):
@@ -349,14 +387,8 @@ class PathTracer:
 
     def render_probes(self, gconst, wait=True):
         h = self.probe_commands(gconst)
-        W, H = self.window
-        if self.n_ranks > 1:  # replicas: the whole window on every rank (see probe_commands)
-            self.ctx.set_tile_partition(W, H, 0, 1)
-        try:
+        with self._whole_window():  # replicas: the whole window on every rank (see probe_commands)
             self.rg.draw_frame(h["light"], wait=wait)
-        finally:
-            if self.n_ranks > 1:  # launches read the partition when they are enqueued: safe to restore behind them
-                self.ctx.set_tile_partition(W, H, self.rank, self.n_ranks)
         return h
 
     def copy_atlas_to_prev(self):
@@ -375,46 +407,42 @@ class PathTracer:
         sample_counts(), ctx.adaptive_info())."""
         if adaptive is not None and adaptive is not True and adaptive is not False:
             self.ctx.adaptive_set_params(adaptive)
-        motion = False
-        if temporal:
-            motion = self._begin_temporal(gconst, denoise)
-        elif denoise:
+        motion = temporal and self._begin_temporal(gconst, denoise)
+        if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
         h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive is not None and adaptive is not False)
         if motion:
             self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
         if temporal:
-            self._end_temporal(gconst)
+            self._history.end_frame(gconst)
         return h
 
     # ---- results
-    def light(self):
+    def _download(self, key, dtype=np.float32, channels=(4,)):
         W, H = self.window
-        return self.rg.download(self.handles["light"], (H, W, 4), np.float32)
+        return self.rg.download(self.handles[key], (H, W, *channels), dtype)
+
+    def light(self):
+        return self._download("light")
 
     def color(self):
-        W, H = self.window
-        return self.rg.download(self.handles["color"], (H, W, 4), np.float32)
+        return self._download("color")
 
     def denoised(self):
-        W, H = self.window
-        return self.rg.download(self.handles["denoised"], (H, W, 4), np.float32)
+        return self._download("denoised")
 
     def accumulated(self):
         """Out of the "temporal" pass"""
-        W, H = self.window
-        return self.rg.download(self.handles["accumulated"], (H, W, 4), np.float32)
+        return self._download("accumulated")
 
     def history(self):
         """(History, Moments) of the "temporal" pass"""
-        W, H = self.window
-        return self.rg.download(self.handles["history"], (H, W, 4), np.float32), self.rg.download(self.handles["moments"], (H, W, 4), np.float32)
+        return self._download("history"), self._download("moments")
 
     def adaptive_moments(self):
         """Moments of the "adaptive" pass: {S1, S2, n, 1 = stopped before the cap} per foreground pixel, 0 for background"""
-        W, H = self.window
-        return self.rg.download(self.handles["adaptive_moments"], (H, W, 4), np.float32)
+        return self._download("adaptive_moments")
 
     def sample_counts(self):
         """the samples each pixel got in the last adaptive frame (H, W) uint32; 0 = background"""
@@ -422,12 +450,10 @@ class PathTracer:
 
     def motion(self):
         """the "motion" pass's image of the last frame that had one"""
-        W, H = self.window
-        return self.rg.download(self.handles["motion"], (H, W, 4), np.float32)
+        return self._download("motion")
 
     def gbuffer(self):
-        W, H = self.window
-        return self.rg.download(self.handles["gbuffer"], (H, W, 4), np.uint32), self.rg.download(self.handles["depth"], (H, W), np.float32)
+        return self._download("gbuffer", np.uint32), self._download("depth", channels=())
 
     def copy_light_to_prev(self):
         """Progressive accumulation: PrevLight <- Light (refrence_mode.slang:11,61-65), through the host (tests)."""

@@ -5,7 +5,6 @@ block or of 64, two tiles of the partition): the window holds the wall in the mi
 normals lights the wall smoothly, so per-pixel variances spread and the counts take every value 4, 8, ..., 24.  min_samples = step = 4,
 cap 24, three bounces.  THRESHOLD[dilate] is picked so that a good share of the foreground pixels stops before the cap and a good share
 reaches it: test_adaptive_cpu.py asserts both shares (MIN_SHARE) on oracle frames, test_adaptive.py on the GPU frames."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -69,14 +68,6 @@ def instanced_world():
         m[0, 3], m[2, 3] = dx, dz
         inst.append((t, 1, m))
     return room, inst
-
-
-def as_orc(g):
-    import orc
-
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
 
 
 def fov(cam):

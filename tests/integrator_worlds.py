@@ -8,6 +8,7 @@ import numpy as np
 
 from raytracer3_amd import scenes
 from raytracer3_amd.assets import Material, MeshBuilder
+from support import translate
 
 WINDOW_FURNACE = (64, 48)
 WINDOW_ROOM = (48, 32)
@@ -21,12 +22,6 @@ BLOCK_LO, BLOCK_HI = (-0.3, -1.0, -0.2), (0.1, -0.2, 0.3)  # in units of the roo
 
 def furnace_camera(scale):
     return dict(position=tuple(scale * c for c in (0.1, 0.2, 0.9)), direction=(0.05, -0.3, -1.0), fov_deg=70.0)
-
-
-def translate(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
 
 
 def rot_y(deg):

@@ -5,6 +5,7 @@ import numpy as np
 
 from raytracer3_amd import scenes
 from raytracer3_amd.assets import Material, MeshBuilder
+from support import translate
 
 F = np.float32
 EYE = np.eye(4, dtype=F)
@@ -18,12 +19,6 @@ def rot_y(deg):
 def rot_z(deg):
     c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
     return np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float64)
-
-
-def translate(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
 
 
 def scale(x, y, z):

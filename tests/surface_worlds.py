@@ -7,19 +7,12 @@ import numpy as np
 import ref_surface
 from raytracer3_amd import scenes
 from raytracer3_amd.assets import GEOMETRY_DTYPE, Material, Mesh, MeshBuilder
+from support import rotation
 
 F = np.float32
 EYE = np.eye(4, dtype=F)
 TEXTURE_SIZES = [(1, 1), (1, 7), (3, 5), (64, 64), (257, 2)]  # W x H
 SOUP_TRIANGLES = [37, 400, 113, 64, 150, 1, 18]  # per geometry: all different, so a wrong first_prim or 3 * prim offset lands in a neighbour
-
-
-def rotation(rng):
-    q = rng.normal(size=4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
 def affine(m3, t=(0.0, 0.0, 0.0)):

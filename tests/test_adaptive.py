@@ -15,16 +15,13 @@ import ref_adaptive as ra
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.renderer import Camera, PathTracer
+from support import bits
 
 pytestmark = pytest.mark.gpu
 
 W, H, CAP = aw.W, aw.H, aw.CAP
 CAPS = list(range(aw.MIN_SAMPLES, CAP + 1, aw.STEP))  # 4, 8, ..., 24
 U = 2.0 ** -24  # unit roundoff of float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def camera(cam=aw.CAMERA):
@@ -283,7 +280,7 @@ def test_params_validation_leaves_them_unchanged(world):
         fields.update(b)
         pr = L.AdaptiveParams(**fields)
         assert ctx.lib.rt3_adaptive_set_params(ctx.h, C.byref(pr)) == L.E_INVALID, b
-        assert "adaptive params" in ctx.lib.rt3_last_error(ctx.h).decode()
+        assert "adaptive params" in ctx.last_error()
     world.pt.render(world.gconst(CAP, aw.FLAGS, aw.BOUNCES, 1.0, aw.FRAME), adaptive=True)  # with the parameters the context holds
     assert np.array_equal(bits(world.pt.adaptive_moments()), bits(before))
     ctx.adaptive_set_params()  # the defaults: 16 samples first
@@ -301,10 +298,9 @@ def test_bindings_are_checked(world):
     good = [h["gbuffer"], h["depth"], h["light"], h["prev"], h["adaptive_moments"]]
 
     def launch(b, x=W, y=H):
-        arr = (C.c_uint32 * len(b))(*b)
-        return ctx.lib.rt3_pass_launch(ctx.h, b"adaptive", b"main", x, y, 1, C.byref(g), C.sizeof(g), arr, len(b))
+        return ctx.pass_launch("adaptive", x, y, 1, g, b)
 
-    err = lambda: ctx.lib.rt3_last_error(ctx.h).decode()
+    err = ctx.last_error
     assert launch(good) == 0, err()
     assert launch(good[:4]) == L.E_INVALID and "5 bindings" in err()
     assert launch(good + [h["color"]]) == L.E_INVALID and "5 bindings" in err()

@@ -14,17 +14,14 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.assets import Material, MeshBuilder
 from raytracer3_amd.render_graph import Context
-from raytracer3_amd.renderer import Camera, PathTracer
+import support
+from support import bits
 from test_alpha_mask_cpu import alpha_f32, tex_alpha_f32, tri_uvs
 
 pytestmark = pytest.mark.gpu
 
 FULL = L.F_NEE_SKY | L.F_BLUENOISE | L.F_SPECULAR | L.F_FACEFORWARD | L.F_NEE_EMISSIVE
 WIN = (64, 48)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def merged(a, b, textures=None):
@@ -53,20 +50,11 @@ def texture(alpha_byte):
 
 
 def make_pt(mesh, mode, instances=None):
-    pt = PathTracer(WIN)
-    pt.ctx.set_option(L.OPT_INSTANCE_MODE, mode)
-    pt.ctx.upload_mesh(mesh)
-    if instances:
-        pt.ctx.set_instances(instances)
-    pt.ctx.set_sky(scenes.sky(64, 32))
-    pt.ctx.set_bluenoise(assets.load_bluenoise())
-    pt._accel = pt.ctx.build_accel()
-    return pt
+    return support.tracer(mesh, WIN, sky=scenes.sky(64, 32), bluenoise=assets.load_bluenoise(), instances=instances, mode=mode)
 
 
 def camera():
-    c = scenes.CORNELL_CAMERA
-    return Camera(c["position"], c["direction"], math.radians(c["fov_deg"]), WIN[0] / WIN[1])
+    return support.camera(scenes.CORNELL_CAMERA, WIN)
 
 
 def rays_for(mesh, n, seed):

@@ -29,12 +29,12 @@ import ref_pathtrace as RP
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.assets import LIGHT_POINT, Material, MeshBuilder, make_light
-from raytracer3_amd.renderer import PathTracer
+from support import bits, camera
 from test_combined_cpu import fixture
 from test_integrator_cpu import check_against_fixture
 from test_lens import check_binomial, lens_frame
 from test_materials import mapped_room
-from test_nee_emissive import FULL, bits, camera, frame, make_pt, owned_mask
+from test_nee_emissive import FULL, frame, make_pt, owned_mask
 from test_punctual_lights import EPS, check_closed_form, device_rays
 
 pytestmark = pytest.mark.gpu
@@ -47,16 +47,8 @@ LDS_GEOMS = 256  # kShadeGeomsLds (rt3_surface.hpp)
 # ---------------------------------------------------------------------------------------------------------------- helpers
 def build_pt(mesh, window=CW.WINDOW, instances=None, lens=None, options=(), sky=True, **kw):
     """make_pt with options that must precede the build (RT3_OPT_* name -> value)"""
-    pt = PathTracer(window, rank=kw.get("rank", 0), n_ranks=kw.get("n_ranks", 1))
-    for opt, value in dict(options).items():
-        pt.ctx.set_option(opt, value)
-    pt.ctx.upload_mesh(mesh)
-    if instances:
-        pt.ctx.set_instances(instances)
-    if sky:
-        pt.ctx.set_sky(CW.sky())
-    pt.ctx.set_bluenoise(assets.load_bluenoise())
-    pt._accel = pt.ctx.build_accel()
+    pt = make_pt(mesh, window, sky=CW.sky() if sky else None, instances=instances, options=dict(options).items(),
+                 rank=kw.get("rank", 0), n_ranks=kw.get("n_ranks", 1))
     if lens is not None:
         pt.set_lens(*lens)
     return pt

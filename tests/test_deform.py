@@ -17,7 +17,8 @@ import ref_motion as rm
 import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd.assets import Material, MeshBuilder
-from test_motion import SENTINEL, as_orc, bits, err, gconst, launch, motion_image, run_motion, same, tracer
+from support import as_orc, bits, err, launch, same, tracer
+from test_motion import SENTINEL, gconst, motion_image, run_motion
 
 pytestmark = pytest.mark.gpu
 BG = np.float32(orc.BACKGROUND_DEPTH)
@@ -140,7 +141,7 @@ def test_compare_kernel_follows_the_span_rule():
     assert lib.rt3_scene_deformed_geometries(ctx.h, flags.ctypes.data, ng + 1) == L.E_INVALID
     assert lib.rt3_scene_deformed_geometries(ctx.h, None, ng) == L.E_INVALID
     ctx.forget_prev_vertices()
-    assert lib.rt3_scene_deformed_geometries(ctx.h, flags.ctypes.data, ng) == L.E_STATE and "snapshot" in lib.rt3_last_error(ctx.h).decode()
+    assert lib.rt3_scene_deformed_geometries(ctx.h, flags.ctypes.data, ng) == L.E_STATE and "snapshot" in ctx.last_error()
     snapshot()
     check([], "a first snapshot again: every vertex copied")
     ctx.close()
@@ -152,7 +153,7 @@ def deformed_tracer(W, H, mode, snapshot=True):
     mesh, prev_v, inst, prev = dw.parity_world()
     before = copy.copy(mesh)
     before.vertices = prev_v
-    pt = tracer(before, W, H, inst, mode)
+    pt = tracer(before, (W, H), instances=inst, mode=mode)
     if snapshot:
         pt.ctx.snapshot_vertices()
     pt.ctx.update_vertices(mesh.vertices)
@@ -242,7 +243,7 @@ def run_sequence(mode, K=4, W=160, H=120, feature=True, check=True):
     frame is compared with the reference chain on the frame's own Light and the previous frame's (GPU) History and Moments.  Without
     `feature` the vertices go up past PathTracer (no snapshot).  Returns the frames' images and the last frame's cloth mask."""
     mesh, inst = dw.world(0)
-    pt = tracer(mesh, W, H, inst, mode)
+    pt = tracer(mesh, (W, H), instances=inst, mode=mode)
     prev = prev_inst = prev_mesh = None
     frames = []
     for k in range(K):
@@ -342,7 +343,7 @@ def test_errors_and_forgetting():
     from raytracer3_amd.render_graph import Context
 
     fresh = Context()
-    assert fresh.lib.rt3_scene_snapshot_vertices(fresh.h) == L.E_STATE and "rt3_scene_set_vertices" in fresh.lib.rt3_last_error(fresh.h).decode()
+    assert fresh.lib.rt3_scene_snapshot_vertices(fresh.h) == L.E_STATE and "rt3_scene_set_vertices" in fresh.last_error()
     assert fresh.lib.rt3_scene_forget_prev_vertices(fresh.h) == 0
     fresh.close()
 
@@ -362,7 +363,7 @@ def test_two_launches_give_identical_bits():
 def test_pathtracer_snapshots_inserts_skips_and_resets():
     W, H = 128, 96
     mesh0, inst = dw.world(0)
-    pt = tracer(mesh0, W, H, inst)
+    pt = tracer(mesh0, (W, H), instances=inst)
     gs = [gconst(pt, dw.CAMERA, 1, k + 1, k) for k in range(6)]
     ng = len(mesh0.geometries)
     flags = np.zeros(ng, np.uint8)

@@ -17,7 +17,8 @@ import ref_motion as rm
 import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd.assets import Material, MeshBuilder
-from test_motion_cpu import QUALITY_MOVE, bits, erode, frame, gconst, rmse, zeros
+from support import bits, zeros
+from test_motion_cpu import QUALITY_MOVE, erode, frame, gconst, rmse
 
 BG = np.float32(orc.BACKGROUND_DEPTH)
 F = np.float32

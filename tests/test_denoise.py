@@ -12,33 +12,10 @@ import orc
 import ref_denoise as rd
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
+from support import as_orc, bits, camera, launch, tracer
 
 pytestmark = pytest.mark.gpu
 BG = np.float32(orc.BACKGROUND_DEPTH)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def as_orc(g):
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
-
-
-def tracer(mesh, W, H, sky=None, bn=None):
-    from raytracer3_amd.renderer import PathTracer
-
-    pt = PathTracer((W, H))
-    pt.set_scene(mesh, sky, bn)
-    return pt
-
-
-def camera(kw, W, H):
-    from raytracer3_amd.renderer import Camera
-
-    return Camera(kw["position"], kw["direction"], math.radians(kw["fov_deg"]), W / H)
 
 
 def check_parity(pt, g, what, **params):
@@ -58,8 +35,8 @@ def check_parity(pt, g, what, **params):
 
 def test_parity_cornell_iterations_and_parameters():
     W = H = 128
-    pt = tracer(scenes.cornell(), W, H)
-    cam = camera(scenes.CORNELL_CAMERA, W, H)
+    pt = tracer(scenes.cornell(), (W, H))
+    cam = camera(scenes.CORNELL_CAMERA, (W, H))
     for spp in (1, 16):
         g = pt.make_gconst(cam, spp, 4, frame=7, flags=L.F_FACEFORWARD)
         check_parity(pt, g, f"cornell {spp} spp")
@@ -80,8 +57,8 @@ def test_parity_atrium_sky_columns_and_odd_window():
 
     sky, bn = scenes.sky(512, 256), assets.load_bluenoise()
     for W, H in ((192, 108), (250, 187)):  # 250 x 187: no multiple of 8 nor of the kernels' tile
-        pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
-        g = pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H), 1, 4, frame=5, flags=DEFAULT_FLAGS)
+        pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
+        g = pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H)), 1, 4, frame=5, flags=DEFAULT_FLAGS)
         light, out, gb, depth = check_parity(pt, g, "atrium 1 spp")
         fg = depth != BG
         assert (~fg).any() and np.array_equal(bits(out)[~fg], bits(light)[~fg])  # sky pixels pass through
@@ -96,8 +73,8 @@ def test_parity_atrium_sky_columns_and_odd_window():
 
 def test_parity_textured_cornell():
     W, H = 160, 120
-    pt = tracer(scenes.textured_cornell(), W, H)
-    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H), 4, 3, frame=2, flags=L.F_FACEFORWARD | L.F_SPECULAR)
+    pt = tracer(scenes.textured_cornell(), (W, H))
+    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H)), 4, 3, frame=2, flags=L.F_FACEFORWARD | L.F_SPECULAR)
     check_parity(pt, g, "textured cornell 4 spp")
     check_parity(pt, g, "textured cornell 4 spp, 3 iterations", iterations=3)
     pt.close()
@@ -121,21 +98,16 @@ def test_expn_selftest_bit_exact():
     assert bad.size == 0, f"{bad.size} of {x.size} differ, e.g. x = {x[bad[:4]].tolist()}"
 
 
-def launch(pt, name, x, y, z, g, bindings):
-    b = (C.c_uint32 * max(1, len(bindings)))(*bindings)
-    return pt.ctx.lib.rt3_pass_launch(pt.ctx.h, name.encode(), b"main", x, y, z, C.byref(g), C.sizeof(g), b, len(bindings))
-
-
 def test_errors_leave_the_context_usable():
     from raytracer3_amd.render_graph import ImageSize
 
     W, H = 100, 60
-    pt = tracer(scenes.cornell(), W, H)
-    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H), 2, 3, frame=1, flags=L.F_FACEFORWARD)
+    pt = tracer(scenes.cornell(), (W, H))
+    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H)), 2, 3, frame=1, flags=L.F_FACEFORWARD)
     h = pt.commands(g, denoise=True)
     pt.rg.draw_frame(h["denoised"], wait=True)
     first = pt.denoised()
-    lib, err = pt.ctx.lib, lambda: pt.ctx.lib.rt3_last_error(pt.ctx.h).decode()
+    lib, err = pt.ctx.lib, pt.ctx.last_error
     X, Y = math.ceil(W / 8), math.ceil(H / 8)
     good = [h["gbuffer"], h["depth"], h["light"], h["denoised"]]
     assert launch(pt, "denoise", X, Y, 1, g, good) == 0
@@ -173,8 +145,8 @@ def test_deterministic_and_scratch_reuse():
     """two runs give the same bits; a second, larger window on the same context grows the scratch and still matches the reference; a
     pre-existing garbage Out does not leak into the result"""
     W, H = 128, 96
-    pt = tracer(scenes.cornell(), W, H)
-    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H), 1, 4, frame=9, flags=L.F_FACEFORWARD)
+    pt = tracer(scenes.cornell(), (W, H))
+    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H)), 1, 4, frame=9, flags=L.F_FACEFORWARD)
     _, a, _, _ = check_parity(pt, g, "run 1")
     pt.rg.upload(pt.handles["denoised"], np.full((H, W, 4), np.nan, np.float32))
     _, b, _, _ = check_parity(pt, g, "run 2")
@@ -182,7 +154,7 @@ def test_deterministic_and_scratch_reuse():
     # the same context, other window sizes through the raw ABI (scratch grows, then is reused for the smaller one)
     from raytracer3_amd.render_graph import ImageSize
     for k, (w, h) in enumerate(((200, 150), (64, 40))):
-        gg = camera(scenes.CORNELL_CAMERA, w, h).gconst((w, h))
+        gg = camera(scenes.CORNELL_CAMERA, (w, h)).gconst((w, h))
         gg.samples, gg.bounces, gg.frame, gg.blendfactor = 1, 3, 4, 1.0
         gg.pad[0] = L.F_FACEFORWARD
         pt.ctx.set_tile_partition(w, h, 0, 1)
@@ -205,8 +177,8 @@ def test_windows_around_the_tile_size():
 
     sky, bn = scenes.sky(128, 64), assets.load_bluenoise()
     for W, H in ((97, 41), (20, 6), (33, 3), (3, 9)):
-        pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
-        cam = camera(scenes.ATRIUM_CAMERA, W, H)
+        pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
+        cam = camera(scenes.ATRIUM_CAMERA, (W, H))
         g = pt.make_gconst(cam, 1, 3, frame=8, flags=DEFAULT_FLAGS)
         check_parity(pt, g, "odd window", iterations=8)
         check_parity(pt, g, "odd window")
@@ -221,8 +193,8 @@ def test_multi_rank_denoise_on_the_gather_root():
 
     mesh, sky, bn = scenes.atrium(0.25), scenes.sky(128, 64), assets.load_bluenoise()
     W, H, n, root = 200, 136, 3, 0
-    cam = camera(scenes.ATRIUM_CAMERA, W, H)
-    solo = tracer(mesh, W, H, sky, bn)
+    cam = camera(scenes.ATRIUM_CAMERA, (W, H))
+    solo = tracer(mesh, (W, H), sky=sky, bluenoise=bn)
     g = solo.make_gconst(cam, 2, 3, frame=6, flags=DEFAULT_FLAGS)
     zero = np.zeros((H, W, 4), np.float32)
     solo.rg.upload(solo.commands(g)["light"], zero)  # k_accumulate leaves background pixels of Light unwritten: give them known bits
@@ -273,7 +245,7 @@ def test_cpp_host_names_the_pass(tmp_path):
         subprocess.check_call(["make", "-C", str(exe.parent)])
     mesh, sky, bn = scenes.atrium(0.2), scenes.sky(256, 128), assets.load_bluenoise()
     W, H, spp, bounces, frame, flags = 96, 54, 2, 3, 9, 15
-    cam = camera(scenes.ATRIUM_CAMERA, W, H)
+    cam = camera(scenes.ATRIUM_CAMERA, (W, H))
     scene = tmp_path / "scene.bin"
     with open(scene, "wb") as f:
         f.write(struct.pack("<8I", len(mesh.vertices), len(mesh.indices), len(mesh.geometries), sky.shape[1], sky.shape[0], bn.shape[1], bn.shape[0], 0))

@@ -15,17 +15,12 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.renderer import Camera, PathTracer
 from raytracer3_amd.render_graph import Context
+from support import as_orc
 
 pytestmark = pytest.mark.gpu
 
 FULL = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD
 SPEC = FULL | L.F_SPECULAR  # + layered GGX BSDF (brdf.slang:141-311)
-
-
-def as_orc(g: L.GConst) -> orc.GConst:
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
 
 
 @pytest.fixture(scope="module")
@@ -724,14 +719,14 @@ def test_error_behaviour(small):
     g.window_size[0], g.window_size[1] = 64, 64
     b = (C.c_uint32 * 2)(0, 0)
     # pass before accel build
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 304, b, 2) == L.E_STATE
+    assert ctx.pass_launch("gbuffer", 64, 64, 1, g, b) == L.E_STATE
     ctx.upload_mesh(mesh)
     ctx.build_accel()
-    assert lib.rt3_pass_launch(ctx.h, b"nope", b"main", 64, 64, 1, C.byref(g), 304, b, 2) == L.E_INVALID
-    assert b"unknown pass" in lib.rt3_last_error(ctx.h)
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"other_entry", 64, 64, 1, C.byref(g), 304, b, 2) == L.E_INVALID
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 300, b, 2) == L.E_INVALID
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 304, b, 2) == L.E_INVALID  # handles are not images
+    assert ctx.pass_launch("nope", 64, 64, 1, g, b) == L.E_INVALID
+    assert "unknown pass" in ctx.last_error()
+    assert ctx.pass_launch("gbuffer", 64, 64, 1, g, b, entry="other_entry") == L.E_INVALID
+    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 300, b, 2) == L.E_INVALID  # (the raw call: a wrong constants size)
+    assert ctx.pass_launch("gbuffer", 64, 64, 1, g, b) == L.E_INVALID  # handles are not images
     img = C.c_uint32()
     assert lib.rt3_image_create(ctx.h, 64, 64, 12345, C.byref(img)) == L.E_INVALID
     assert lib.rt3_image_create(ctx.h, 64, 64, L.FORMAT_R32_SFLOAT, C.byref(img)) == 0
@@ -743,7 +738,7 @@ def test_error_behaviour(small):
     for bad_value in (np.nan, np.inf, -1.0):
         bad_sky = np.ones((4, 8, 3), np.float32)
         bad_sky[2, 3, 1] = bad_value
-        assert lib.rt3_scene_set_sky(ctx.h, bad_sky.ctypes.data, 8, 4) == L.E_INVALID and b"sky texel 19" in lib.rt3_last_error(ctx.h)
+        assert lib.rt3_scene_set_sky(ctx.h, bad_sky.ctypes.data, 8, 4) == L.E_INVALID and "sky texel 19" in ctx.last_error()
         assert orc.lib().orc_scene_set_sky(osc.h, orc.ptr(bad_sky), 8, 4) == -1
     # a geometry that references a texture nobody uploaded is refused at launch time, not dereferenced on the GPU
     gi = mesh.geometries.copy()
@@ -755,12 +750,12 @@ def test_error_behaviour(small):
     i0, i1 = C.c_uint32(), C.c_uint32()
     assert lib.rt3_image_create(ctx.h, 64, 64, L.FORMAT_R32G32B32A32_UINT, C.byref(i0)) == 0 and lib.rt3_image_create(ctx.h, 64, 64, L.FORMAT_R32_SFLOAT, C.byref(i1)) == 0
     bb = (C.c_uint32 * 2)(i0.value, i1.value)
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 304, bb, 2) == L.E_STATE
-    assert b"texture" in lib.rt3_last_error(ctx.h)
+    assert ctx.pass_launch("gbuffer", 64, 64, 1, g, bb) == L.E_STATE
+    assert "texture" in ctx.last_error()
     # non-finite positions are rejected at upload
     bad = np.zeros((3, 8), np.float32)
     bad[1, 2] = np.nan
-    assert lib.rt3_scene_set_vertices(ctx.h, bad.ctypes.data, 3) == L.E_INVALID and b"not finite" in lib.rt3_last_error(ctx.h)
+    assert lib.rt3_scene_set_vertices(ctx.h, bad.ctypes.data, 3) == L.E_INVALID and "not finite" in ctx.last_error()
     bad[1, 2] = np.inf
     assert lib.rt3_scene_set_vertices(ctx.h, bad.ctypes.data, 3) == L.E_INVALID
     # out-of-range geometry is rejected on the host instead of faulting on the GPU
@@ -772,12 +767,12 @@ def test_error_behaviour(small):
     assert lib.rt3_accel_build(ctx.h, C.byref(out)) == 0
     fewer = np.ascontiguousarray(mesh.vertices[: len(mesh.vertices) // 2], np.float32)
     assert lib.rt3_scene_set_vertices(ctx.h, fewer.ctypes.data, len(fewer)) == 0
-    assert lib.rt3_accel_build(ctx.h, C.byref(out)) == L.E_INVALID and b"vertex range" in lib.rt3_last_error(ctx.h)
-    assert lib.rt3_pass_launch(ctx.h, b"gbuffer", b"main", 64, 64, 1, C.byref(g), 304, bb, 2) == L.E_STATE  # no stale BVH is used
+    assert lib.rt3_accel_build(ctx.h, C.byref(out)) == L.E_INVALID and "vertex range" in ctx.last_error()
+    assert ctx.pass_launch("gbuffer", 64, 64, 1, g, bb) == L.E_STATE  # no stale BVH is used
     ctx.upload_mesh(mesh)
     short_idx = np.ascontiguousarray(mesh.indices[: len(mesh.indices) // 2], np.uint32)
     assert lib.rt3_scene_set_indices(ctx.h, short_idx.ctypes.data, len(short_idx)) == 0
-    assert lib.rt3_accel_build(ctx.h, C.byref(out)) == L.E_INVALID and b"index range" in lib.rt3_last_error(ctx.h)
+    assert lib.rt3_accel_build(ctx.h, C.byref(out)) == L.E_INVALID and "index range" in ctx.last_error()
     ctx.close()
 
 
@@ -1129,7 +1124,7 @@ def test_rccl_communicator_single_rank(small):
     pt.render(pt.make_gconst(cam, 1, 2, flags=FULL))
     ref = pt.light()
     lib, h, img = pt.ctx.lib, pt.ctx.h, pt.handles["light"]
-    assert lib.rt3_gather_tiles(h, img, 0) == L.E_STATE and b"rt3_comm_init" in lib.rt3_last_error(h)
+    assert lib.rt3_gather_tiles(h, img, 0) == L.E_STATE and "rt3_comm_init" in pt.ctx.last_error()
     uid = pt.ctx.comm_unique_id()
     assert len(uid) == L.COMM_ID_BYTES and any(uid)
     assert lib.rt3_comm_init(h, uid, 1, 1) == L.E_INVALID  # rank must be < n_ranks
@@ -1139,7 +1134,7 @@ def test_rccl_communicator_single_rank(small):
     pt.ctx.gather_tiles(img, 0)  # one rank: the frame is already whole
     assert np.array_equal(pt.light().view(np.uint32), ref.view(np.uint32))
     pt.ctx.set_tile_partition(W, H, 1, 2)  # the partition and the communicator must agree
-    assert lib.rt3_gather_tiles(h, img, 0) == L.E_STATE and b"disagree" in lib.rt3_last_error(h)
+    assert lib.rt3_gather_tiles(h, img, 0) == L.E_STATE and "disagree" in pt.ctx.last_error()
     pt.ctx.comm_destroy()
     pt.ctx.comm_destroy()  # idempotent
     assert lib.rt3_gather_tiles(h, img, 0) == L.E_STATE
@@ -1170,7 +1165,7 @@ def test_rccl_rendezvous_of_two_processes(tmp_path):
         "    while not os.path.exists(path) and time.time() - t0 < 60: time.sleep(0.05)\n"
         "    uid = open(path, 'rb').read()\n"
         "rc = ctx.lib.rt3_comm_init(ctx.h, C.c_char_p(uid), r, 2)\n"
-        "print('RESULT', r, rc, ctx.lib.rt3_last_error(ctx.h).decode())\n"
+        "print('RESULT', r, rc, ctx.last_error())\n"
     )
     uid_file = str(tmp_path / "uid.bin")
     env = dict(os.environ, NCCL_DEBUG="WARN")
@@ -1217,8 +1212,7 @@ def test_config_c1_primary_visibility_256():
     cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), 1.0)
     g = pt.make_gconst(cam, 1, 1, flags=0)
     h = pt.commands(g, postprocess=False)
-    b = (C.c_uint32 * 2)(h["gbuffer"], h["depth"])  # the gbuffer node alone
-    pt.ctx.check(pt.ctx.lib.rt3_pass_launch(pt.ctx.h, b"gbuffer", b"main", 256, 256, 1, C.byref(g), C.sizeof(g), b, 2))
+    pt.ctx.check(pt.ctx.pass_launch("gbuffer", 256, 256, 1, g, [h["gbuffer"], h["depth"]]))  # the gbuffer node alone
     pt.ctx.wait()
     gb, depth = pt.gbuffer()
     st = pt.ctx.stats()

@@ -55,7 +55,7 @@ def test_camera_matches_oracle_and_reference_defaults():
 
 
 class FakeCtx:
-    """Records rt3_pass_launch calls instead of running them (no GPU in the build container)."""
+    """Records pass launches instead of running them (no GPU in the build container)."""
 
     def __init__(self):
         self.calls, self.n = [], 0
@@ -69,8 +69,8 @@ class FakeCtx:
         out._obj.value = (1 << 30) | self.n
         return 0
 
-    def rt3_pass_launch(self, h, path, entry, x, y, z, cst, size, b, nb):
-        self.calls.append((path.decode(), entry.decode(), x, y, z, size, [b[i] for i in range(nb)]))
+    def pass_launch(self, name, x, y, z, gconst, bindings, entry="main"):
+        self.calls.append((name, entry, x, y, z, C.sizeof(gconst), list(bindings)))
         return 0
 
     def wait(self):

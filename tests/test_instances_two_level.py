@@ -1,7 +1,6 @@
 """Instance mode 1 (RT3_OPT_INSTANCE_MODE): shared object-space bottom trees under a GPU-built top tree.  The
 oracle flattens the instances with the product's fp32 expression, and the two-level walk tests the same world-space triangles, so every
 hit, G-buffer texel and radiance value must equal the oracle's (and mode 0's) bit for bit: the structure changes the walk, never the answer."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -12,29 +11,12 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.renderer import Camera, PathTracer
 from raytracer3_amd.render_graph import Context
+from support import as_orc, bits, rotation
 
 pytestmark = pytest.mark.gpu
 
 SPEC = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD | L.F_SPECULAR
 EYE = np.eye(4, dtype=np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def as_orc(g):
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
-
-
-def rotation(rng):
-    q = rng.normal(size=4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
 def placement(rng, center, lo, hi, scale=(0.25, 0.6)):
@@ -129,7 +111,7 @@ def test_instance_mode_interface():
     for opt, val in ((L.OPT_NODE_QUANT, 0), (L.OPT_NODE_QUANT, 2), (L.OPT_NODE_WIDTH, 2)):
         ctx.set_option(opt, val)
         assert lib.rt3_accel_build(h, None) == L.E_UNSUPPORTED
-        assert b"default node layout" in lib.rt3_last_error(h)
+        assert "default node layout" in ctx.last_error()
         ctx.set_option(L.OPT_NODE_QUANT, 1)
         ctx.set_option(L.OPT_NODE_WIDTH, 4)
     ctx.build_accel()

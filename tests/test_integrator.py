@@ -7,7 +7,8 @@ import pytest
 import integrator_worlds as IW
 from raytracer3_amd import _lib as L
 from test_integrator_cpu import FURNACE_BS, LOW_CAP, check_against_fixture, check_furnace, fixture, furnace_radiance
-from test_nee_emissive import camera, frame, make_pt
+from support import camera
+from test_nee_emissive import frame, make_pt
 
 pytestmark = pytest.mark.gpu
 

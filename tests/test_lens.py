@@ -11,9 +11,10 @@ import integrator_worlds as IW
 import lens_worlds as LW
 import ref_lens as RL
 from raytracer3_amd import _lib as L
+from support import bits, camera
 from test_integrator_cpu import FURNACE_BS, LOW_CAP, check_against_fixture, furnace_tolerance
 from test_lens_cpu import band, fixture
-from test_nee_emissive import bits, camera, make_pt, owned_mask
+from test_nee_emissive import make_pt, owned_mask
 
 pytestmark = pytest.mark.gpu
 

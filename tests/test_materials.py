@@ -18,6 +18,7 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets
 from raytracer3_amd.render_graph import Context
 from raytracer3_amd.renderer import Camera, PathTracer
+from support import bits, constant
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,6 @@ F = np.float32
 W, H, SPP, BOUNCES = 64, 48, 2, 4
 FLAGS = L.F_NEE_SKY | L.F_BLUENOISE | L.F_SPECULAR
 world = M.world  # the module-scoped fixture: the same world, hits and float64 reference
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def context(mesh, instances, mode=0):
@@ -161,10 +158,6 @@ def frame_of(mesh, camera, env, flags=FLAGS, instances=None):
 
 def same(a, b):
     return all(np.array_equal(bits(x), bits(y)) for x, y in zip(a, b))
-
-
-def constant(rgba, w, h):
-    return np.ascontiguousarray(np.tile(np.array(rgba, np.uint8), (h, w, 1)))
 
 
 def mapped_room(rng, emissive):

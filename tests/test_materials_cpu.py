@@ -13,6 +13,7 @@ import ref_materials as RM
 import ref_surface as R
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.assets import Material, MeshBuilder
+from support import constant
 
 F = np.float32
 HOST = Path(__file__).resolve().parent.parent / "raytracer3_amd" / "host"
@@ -33,10 +34,6 @@ def one_triangle(uv, normal=(0.0, 0.0, 1.0), textures=(), **material):
     mesh = mb.build()
     mesh.textures = [np.ascontiguousarray(t, np.uint8) for t in textures]
     return mesh
-
-
-def constant(rgba, w=3, h=2):
-    return np.tile(np.array(rgba, np.uint8), (h, w, 1))
 
 
 HITS = (np.zeros(5, np.uint32), np.array([0.0, 1.0, 0.0, 0.25, 0.3], F), np.array([0.0, 0.0, 1.0, 0.25, 0.6], F))

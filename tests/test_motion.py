@@ -3,7 +3,6 @@ tests/ref_motion.py in both instance modes, at two windows and under a tile part
 "temporal" without one; sequences of moving instances under a moving camera, fed back into each other and chained into "denoise", equal
 the reference and each other across the instance modes; the documented errors; determinism; and the PathTracer path.  The hits come from
 the GPU's own primary trace, which test_gpu_parity.py and test_instances_two_level.py pin to the oracle's."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -15,6 +14,7 @@ import ref_motion as rm
 import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd import scenes
+from support import as_orc, bits, camera, err, launch, same, tracer
 
 pytestmark = pytest.mark.gpu
 BG = np.float32(orc.BACKGROUND_DEPTH)
@@ -23,48 +23,8 @@ FLAGS = L.F_FACEFORWARD
 CAMERA_MOVE = ((0.004, 0.0, 0.0), (0.004, 0.0, 0.0))
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def as_orc(g):
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
-
-
-def same(got, want, what):
-    diff = (bits(got) != bits(want)).reshape(got.shape[0], got.shape[1], -1).any(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} pixels differ, first at {np.argwhere(diff)[:3].tolist()}"
-
-
-def tracer(mesh, W, H, instances=None, mode=0, **kw):
-    from raytracer3_amd.renderer import PathTracer
-
-    pt = PathTracer((W, H), **kw)
-    pt.ctx.set_option(L.OPT_INSTANCE_MODE, mode)
-    pt.set_scene(mesh)
-    if instances is not None:
-        pt.set_instances(instances)
-    return pt
-
-
 def gconst(pt, cam, spp=1, frame=1, step=0, move=CAMERA_MOVE):
-    from raytracer3_amd.renderer import Camera
-
-    W, H = pt.window
-    pos = np.asarray(cam["position"], np.float64) + step * np.asarray(move[0])
-    dirn = np.asarray(cam["direction"], np.float64) + step * np.asarray(move[1])
-    return pt.make_gconst(Camera(pos, dirn, math.radians(cam["fov_deg"]), W / H), spp, 4, frame=frame, flags=FLAGS)
-
-
-def launch(pt, name, x, y, z, g, bindings):
-    b = (C.c_uint32 * max(1, len(bindings)))(*bindings)
-    return pt.ctx.lib.rt3_pass_launch(pt.ctx.h, name.encode(), b"main", x, y, z, C.byref(g), C.sizeof(g), b, len(bindings))
-
-
-def err(pt):
-    return pt.ctx.lib.rt3_last_error(pt.ctx.h).decode()
+    return pt.make_gconst(camera(cam, pt.window, step, move), spp, 4, frame=frame, flags=FLAGS)
 
 
 def motion_image(pt):
@@ -93,7 +53,7 @@ def test_motion_parity_windows_and_partition(mode):
     mesh, cur, prev = mw.parity_world()
     osc = orc.Scene(mesh, instances=cur)
     for W, H in ((192, 108), (250, 187)):
-        pt = tracer(mesh, W, H, cur, mode)
+        pt = tracer(mesh, (W, H), instances=cur, mode=mode)
         pt.ctx.set_prev_transforms(prev)
         g = gconst(pt, mw.PARITY_CAMERA)
         want = rm.motion(mesh, cur, prev, as_orc(g), rm.primary_hits(osc, as_orc(g)))
@@ -119,7 +79,7 @@ def test_motion_parity_windows_and_partition(mode):
 def test_temporal_with_all_unmoved_motion_equals_temporal_without():
     mesh, cur, _ = mw.parity_world()
     W, H = 192, 108
-    pt = tracer(mesh, W, H, cur)
+    pt = tracer(mesh, (W, H), instances=cur)
     gs = [gconst(pt, mw.PARITY_CAMERA, 1, k + 1, k) for k in range(3)]
     for g in gs:
         h = pt.render(g, temporal=True)
@@ -145,7 +105,7 @@ def run_sequence(mode, K=5, W=160, H=120, denoise=True):
     """K frames of the moving world through PathTracer.set_instances + render(temporal=True); every frame is compared with the reference
     chain on the frame's own Light and the previous frame's (GPU) History and Moments.  Returns the frames' images."""
     mesh, inst = mw.moving_world(0)
-    pt = tracer(mesh, W, H, inst, mode)
+    pt = tracer(mesh, (W, H), instances=inst, mode=mode)
     prev, prev_inst, frames = None, None, []
     for k in range(K):
         mesh, inst = mw.moving_world(k)
@@ -213,7 +173,7 @@ def test_errors_and_state():
     assert launch(fresh, "motion", W, H, 1, g, [motion_image(fresh)]) == L.E_STATE
     fresh.close()
 
-    pt = tracer(mesh, W, H, cur)
+    pt = tracer(mesh, (W, H), instances=cur)
     osc = orc.Scene(mesh, instances=cur)
     og = as_orc(g)
     hits = rm.primary_hits(osc, og)
@@ -298,7 +258,7 @@ def test_world_without_an_instance_list():
     """no rt3_scene_set_instances call: one identity instance of everything, so one previous transform moves the whole scene"""
     mesh = scenes.cornell()
     W, H = 96, 96
-    pt = tracer(mesh, W, H)
+    pt = tracer(mesh, (W, H))
     g = gconst(pt, scenes.CORNELL_CAMERA)
     og = as_orc(g)
     hits = rm.primary_hits(orc.Scene(mesh), og)
@@ -316,7 +276,7 @@ def test_world_without_an_instance_list():
 # ------------------------------------------------------------------------------------------------ 5. determinism
 def test_two_launches_give_identical_bits():
     mesh, cur, prev = mw.parity_world()
-    pt = tracer(mesh, 250, 187, cur, 1)
+    pt = tracer(mesh, (250, 187), instances=cur, mode=1)
     pt.ctx.set_prev_transforms(prev)
     g = gconst(pt, mw.PARITY_CAMERA)
     a = run_motion(pt, g)
@@ -329,8 +289,8 @@ def test_two_launches_give_identical_bits():
 def test_pathtracer_inserts_skips_and_resets():
     W, H = 128, 96
     mesh, inst0 = mw.moving_world(0)
-    pt = tracer(mesh, W, H, inst0)
-    other = tracer(mesh, W, H, inst0)  # the same frames through render() + denoise(temporal=True), the multi-rank root's path
+    pt = tracer(mesh, (W, H), instances=inst0)
+    other = tracer(mesh, (W, H), instances=inst0)  # the same frames through render() + denoise(temporal=True), the multi-rank root's path
     gs = [gconst(pt, scenes.CORNELL_CAMERA, 1, k + 1, k) for k in range(4)]
 
     def both(g, inst=None):

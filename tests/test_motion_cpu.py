@@ -18,17 +18,10 @@ import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.render_graph import RenderGraph
+from support import bits, zeros
 
 BG = np.float32(orc.BACKGROUND_DEPTH)
 F = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def zeros(H, W):
-    return np.zeros((H, W, 4), F)
 
 
 def gconst(cam, W, H, spp=1, frame=1, flags=L.F_FACEFORWARD, move=((0, 0, 0), (0, 0, 0)), step=0):
@@ -254,7 +247,7 @@ def test_moved_instances_converge():
 # ------------------------------------------------------------------------------------------------ 5. the Python surface
 def test_frame_graph_places_the_motion_node():
     from raytracer3_amd.renderer import frame_nodes, motion_node
-    from test_temporal_cpu import RecordingCtx
+    from support import RecordingCtx
 
     W, H = 250, 187
     ctx = RecordingCtx()

@@ -13,7 +13,8 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.assets import Material, MeshBuilder
 from raytracer3_amd.render_graph import Context
-from raytracer3_amd.renderer import Camera, PathTracer
+from raytracer3_amd.renderer import Camera
+from support import bits, camera, tracer, translate, with_vertices
 from test_nee_emissive_cpu import CDF_TOTAL, emitter_table, rect_form_factor
 
 pytestmark = pytest.mark.gpu
@@ -23,25 +24,8 @@ FULL = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD | L.F_SPECULAR
 SPEC_FF = L.F_SPECULAR | L.F_FACEFORWARD
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def make_pt(mesh, window, sky=None, instances=None, mode=0, rank=0, n_ranks=1):
-    pt = PathTracer(window, rank=rank, n_ranks=n_ranks)
-    pt.ctx.set_option(L.OPT_INSTANCE_MODE, mode)
-    pt.ctx.upload_mesh(mesh)
-    if instances:
-        pt.ctx.set_instances(instances)
-    if sky is not None:
-        pt.ctx.set_sky(sky)
-    pt.ctx.set_bluenoise(assets.load_bluenoise())
-    pt._accel = pt.ctx.build_accel()
-    return pt
-
-
-def camera(cam, window):
-    return Camera(cam["position"], cam["direction"], math.radians(cam["fov_deg"]), window[0] / window[1])
+def make_pt(mesh, window, **kw):
+    return tracer(mesh, window, bluenoise=assets.load_bluenoise(), **kw)
 
 
 def frame(pt, cam, flags, spp, bounces, index=0):
@@ -49,12 +33,6 @@ def frame(pt, cam, flags, spp, bounces, index=0):
     light = pt.light()[..., :3].copy()
     light[pt.gbuffer()[1] == L.BACKGROUND_DEPTH] = 0.0  # (the pass leaves background pixels untouched)
     return light
-
-
-def translate(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
 
 
 def rot(axis, deg):
@@ -69,10 +47,6 @@ def without_emission(mesh):
     g = mesh.geometries.copy()
     g["emission"] = 0.0
     return assets.Mesh(mesh.vertices, mesh.indices, g, mesh.prim_counts, list(mesh.names), list(mesh.textures))
-
-
-def with_vertices(mesh, v):
-    return assets.Mesh(np.ascontiguousarray(v, np.float32), mesh.indices, mesh.geometries, mesh.prim_counts, list(mesh.names), list(mesh.textures))
 
 
 def moved_light(mesh):

@@ -4,7 +4,6 @@ binding's kind, size and format, the images that may not alias (and the ones tha
 
 Cornell at 64 x 48: the probe grid (4 x 3) is more than one probe each way, the group dispatch (8 x 6) differs from the window, and the
 probe atlas (32 x 24) differs from both."""
-import ctypes as C
 import math
 
 import pytest
@@ -70,12 +69,10 @@ class World:
 
     def launch(self, name, xyz, bindings, ctx=None):
         ctx = ctx or self.pt.ctx
-        b = (C.c_uint32 * max(1, len(bindings)))(*bindings)
-        return ctx.lib.rt3_pass_launch(ctx.h, name.encode(), b"main", *xyz, C.byref(self.g), C.sizeof(self.g), b, len(bindings))
+        return ctx.pass_launch(name, *xyz, self.g, bindings)
 
     def err(self, ctx=None):
-        ctx = ctx or self.pt.ctx
-        return ctx.lib.rt3_last_error(ctx.h).decode()
+        return (ctx or self.pt.ctx).last_error()
 
     def good(self, name):
         _, xyz, keys, _ = PASSES[NAMES.index(name)]

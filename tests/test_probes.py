@@ -11,13 +11,10 @@ import pytest
 import orc
 from raytracer3_amd import _lib as L
 from raytracer3_amd import scenes
+from support import bits, err, launch
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 FW, FH, PX, PY = 96, 64, 6, 4  # the probes.npz fixture: window and probe grid
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def octa(fx, fy):
@@ -159,11 +156,6 @@ def test_constant_radiance_gives_albedo_plus_emissive():
 
 # ------------------------------------------------------------------------------------------------ GPU: bit-exact vs the oracle
 gpu = pytest.mark.gpu
-
-
-def launch(pt, name, x, y, z, g, bindings):
-    b = (C.c_uint32 * len(bindings))(*bindings)
-    return pt.ctx.lib.rt3_pass_launch(pt.ctx.h, name.encode(), b"main", x, y, z, C.byref(g), C.sizeof(g), b, len(bindings))
 
 
 def as_lib(g: orc.GConst) -> L.GConst:
@@ -350,7 +342,7 @@ def test_gpu_probe_pass_error_behaviour():
     assert launch(pt, "spherical_harmonic_conversion", 4, 3, 1, cam_g, [h["atlas"], h["atlas"]]) == E  # `out` must be a buffer
     small = pt.rg.buffer(48, "too_small")
     assert launch(pt, "spherical_harmonic_conversion", 4, 3, 1, cam_g, [small, h["atlas"]]) == E
-    assert b"at least" in pt.ctx.lib.rt3_last_error(pt.ctx.h)
+    assert "at least" in err(pt)
     assert launch(pt, "interpolate_probes", 8, 6, 1, cam_g, [h["gbuffer"], h["depth"], small, h["light"]]) == E
     assert launch(pt, "interpolate_probes", 7, 6, 1, cam_g, [h["gbuffer"], h["depth"], h["sh"], h["light"]]) == E
     assert launch(pt, "probe_magic", 1, 1, 1, cam_g, []) == E

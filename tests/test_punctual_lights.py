@@ -18,9 +18,10 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import scenes
 from raytracer3_amd.assets import LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT, make_light
 from raytracer3_amd.render_graph import Context
+from support import bits, camera
 from test_alpha_mask_cpu import tex_alpha_f64
 from test_integrator_cpu import check_against_fixture
-from test_nee_emissive import FULL, SPEC_FF, bits, block_z, camera, frame, make_pt, owned_mask
+from test_nee_emissive import FULL, SPEC_FF, block_z, frame, make_pt, owned_mask
 from test_nee_emissive_cpu import CDF_TOTAL
 from test_punctual_lights_cpu import fixture
 

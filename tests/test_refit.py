@@ -18,7 +18,8 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.render_graph import Context
 from raytracer3_amd.renderer import Camera, PathTracer
-from test_instances_two_level import as_orc, check_hits, cornell_world, make_rays
+from support import as_orc, bits, with_vertices
+from test_instances_two_level import check_hits, cornell_world, make_rays
 from test_traversal_exactness_cpu import DISPUTED_MAX, brute, check_against_brute, interval_rays, placed, ray_families
 
 pytestmark = pytest.mark.gpu
@@ -29,16 +30,8 @@ MOVED = {"cornell": "tall", "atrium": "col0_3"}
 FLAGS = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD | L.F_SPECULAR
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def scene(name, offset):
     return placed(scenes.cornell() if name == "cornell" else scenes.atrium(0.2), 1.0, offset)
-
-
-def with_vertices(mesh, v):
-    return assets.Mesh(np.ascontiguousarray(v, np.float32), mesh.indices, mesh.geometries, mesh.prim_counts, list(mesh.names), list(mesh.textures))
 
 
 def geometry_vertices(mesh, gname):

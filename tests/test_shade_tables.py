@@ -22,16 +22,13 @@ import surface_worlds as SW
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.renderer import Camera, PathTracer
+from support import bits
 
 pytestmark = pytest.mark.gpu
 
 W, H, SPP, BOUNCES = 64, 48, 4, 3
 FULL = L.F_NEE_SKY | L.F_BLUENOISE | L.F_FACEFORWARD | L.F_SPECULAR
 FLAG_SETS = (0, FULL, FULL | L.F_NEE_EMISSIVE)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -17,7 +17,7 @@ from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.render_graph import Context
 from raytracer3_amd.renderer import Camera, PathTracer
-from test_gpu_parity import as_orc
+from support import as_orc, bits, soup_mesh
 from test_traversal_exactness_cpu import SOUP_KINDS, _pack, _unit, base_mesh, interval_rays, placed, ray_families
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +26,6 @@ FULL = L.F_NEE_SKY | L.F_BLUENOISE | L.F_SPECULAR | L.F_FACEFORWARD  # the flags
 EMIT = FULL | L.F_NEE_EMISSIVE  # and with the emitter queue beside the sky's: compared between the settings only
 OPTIONS = (0, 1, 2)
 WARMUP = 1 << 16  # tries below which every ray uses the table (kExitWarmupTries)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def built(mesh, **opts):
@@ -127,11 +123,6 @@ def test_any_hit_flags(name, offset):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. edges of the cell computation
-def soup_mesh(tri):
-    mb = assets.MeshBuilder()
-    v = np.ascontiguousarray(tri, np.float32).reshape(-1, 3)
-    mb.add("soup", v, np.tile([0, 0, 1], (len(v), 1)), None, np.arange(len(v), dtype=np.uint32).reshape(-1, 3), assets.Material())
-    return mb.build()
 
 
 def root_box(osc):

@@ -90,7 +90,7 @@ def test_hit_info_refuses_what_it_cannot_index(world):
         out[:] = 0xDEADBEEF
         ctx.update_vertices(mesh.vertices[:3])  # the structure is stale until a refit or a rebuild
         assert call(ctx, rows) == L.E_STATE and (out == 0xDEADBEEF).all()
-        assert b"vertices were updated" in ctx.lib.rt3_last_error(ctx.h)
+        assert "vertices were updated" in ctx.last_error()
         ctx.refit_accel()
         assert call(ctx, rows) == L.RT3_OK
     finally:

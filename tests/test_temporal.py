@@ -14,45 +14,15 @@ import ref_denoise as rd
 import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
+from support import as_orc, bits, camera, launch, same, tracer
 
 pytestmark = pytest.mark.gpu
 BG = np.float32(orc.BACKGROUND_DEPTH)
 F = np.float32
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def as_orc(g):
-    o = orc.GConst()
-    C.memmove(C.byref(o), C.byref(g), 304)
-    return o
-
-
-def tracer(mesh, W, H, sky=None, bn=None):
-    from raytracer3_amd.renderer import PathTracer
-
-    pt = PathTracer((W, H))
-    pt.set_scene(mesh, sky, bn)
-    return pt
-
-
-def camera(kw, W, H, step=0, move=((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))):
-    from raytracer3_amd.renderer import Camera
-
-    pos = np.asarray(kw["position"], np.float64) + step * np.asarray(move[0])
-    dirn = np.asarray(kw["direction"], np.float64) + step * np.asarray(move[1])
-    return Camera(pos, dirn, math.radians(kw["fov_deg"]), W / H)
-
-
 CORNELL_MOVE = ((0.01, 0.0, 0.0), (0.0105, 0.0, 0.0))
 ATRIUM_MOVE = ((0.02, 0.0, 0.01), (0.0, 0.0, 0.012))
-
-
-def same(got, want, what):
-    diff = (bits(got) != bits(want)).any(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} pixels differ, first at {np.argwhere(diff)[:3].tolist()}"
 
 
 def check_sequence(pt, gconsts, what, denoise=False, **params):
@@ -83,10 +53,10 @@ def check_sequence(pt, gconsts, what, denoise=False, **params):
 
 def test_parity_cornell_static_moving_and_parameters():
     W = H = 128
-    pt = tracer(scenes.cornell(), W, H)
+    pt = tracer(scenes.cornell(), (W, H))
 
     def seq(steps, first_frame=1):
-        return [pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H, s, CORNELL_MOVE), 1, 4, frame=first_frame + k, flags=L.F_FACEFORWARD)
+        return [pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H), s, CORNELL_MOVE), 1, 4, frame=first_frame + k, flags=L.F_FACEFORWARD)
                 for k, s in enumerate(steps)]
 
     r = check_sequence(pt, seq([0, 0, 0, 0]), "cornell static")
@@ -106,16 +76,16 @@ def test_parity_atrium_sky_columns_and_odd_window():
 
     sky, bn = scenes.sky(512, 256), assets.load_bluenoise()
     for W, H in ((192, 108), (250, 187)):  # 250 x 187: no multiple of 8 nor of the kernel's tile
-        pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
-        gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, s, ATRIUM_MOVE), 1, 4, frame=5 + s, flags=DEFAULT_FLAGS) for s in range(4)]
+        pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
+        gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), s, ATRIUM_MOVE), 1, 4, frame=5 + s, flags=DEFAULT_FLAGS) for s in range(4)]
         r = check_sequence(pt, gs, "atrium moving")
         fg = r["depth"] != BG
         assert (~fg).any() and np.array_equal(bits(r["out"])[~fg], bits(r["light"])[~fg])  # sky pixels pass through
         assert not r["hist"][~fg].any() and not r["mom"][~fg].any()
         assert np.array_equal(bits(r["out"][..., 3]), bits(r["light"][..., 3]))
         # through the tone map: postprocess reads the accumulated image
-        pt.render(pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, 4, ATRIUM_MOVE), 1, 4, frame=9, flags=DEFAULT_FLAGS), postprocess=True, temporal=True)
-        g = pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, 4, ATRIUM_MOVE), 1, 4, frame=9, flags=DEFAULT_FLAGS)
+        pt.render(pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), 4, ATRIUM_MOVE), 1, 4, frame=9, flags=DEFAULT_FLAGS), postprocess=True, temporal=True)
+        g = pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), 4, ATRIUM_MOVE), 1, 4, frame=9, flags=DEFAULT_FLAGS)
         want = orc.Scene(scenes.atrium(0.25), sky, bn).postprocess(as_orc(g), pt.gbuffer()[1], pt.accumulated())
         assert np.allclose(pt.color(), want, atol=2e-5, rtol=1e-4)
         pt.close()
@@ -126,8 +96,8 @@ def test_windows_around_the_tile_size():
 
     sky, bn = scenes.sky(128, 64), assets.load_bluenoise()
     for W, H in ((97, 41), (20, 6), (3, 9)):
-        pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
-        gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, s, ATRIUM_MOVE), 1, 3, frame=8 + s, flags=DEFAULT_FLAGS) for s in (0, 1, 3)]
+        pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
+        gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), s, ATRIUM_MOVE), 1, 3, frame=8 + s, flags=DEFAULT_FLAGS) for s in (0, 1, 3)]
         check_sequence(pt, gs, "odd window")
         check_sequence(pt, gs[:1] * 3, "odd window, static")
         pt.close()
@@ -135,8 +105,8 @@ def test_windows_around_the_tile_size():
 
 def test_parity_textured_cornell():
     W, H = 160, 120
-    pt = tracer(scenes.textured_cornell(), W, H)
-    gs = [pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H, s, CORNELL_MOVE), 2, 3, frame=2 + s, flags=L.F_FACEFORWARD | L.F_SPECULAR) for s in range(3)]
+    pt = tracer(scenes.textured_cornell(), (W, H))
+    gs = [pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H), s, CORNELL_MOVE), 2, 3, frame=2 + s, flags=L.F_FACEFORWARD | L.F_SPECULAR) for s in range(3)]
     check_sequence(pt, gs, "textured cornell")
     pt.close()
 
@@ -148,7 +118,7 @@ def test_camera_turned_away():
 
     W, H = 192, 108
     sky, bn = scenes.sky(128, 64), assets.load_bluenoise()
-    pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
+    pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
     kw = scenes.ATRIUM_CAMERA
     for what, dirs in (("turned 50 degrees", ((1.0, 0.1, 0.0), (0.64, 0.1, 0.77))), ("turned round", ((1.0, 0.1, 0.0), (-1.0, 0.1, 0.3), (1.0, 0.1, 0.0)))):
         gs = [pt.make_gconst(Camera(kw["position"], d, math.radians(kw["fov_deg"]), W / H), 1, 3, frame=4 + k, flags=DEFAULT_FLAGS) for k, d in enumerate(dirs)]
@@ -167,8 +137,8 @@ def test_temporal_then_denoise_with_the_variance_input():
 
     W, H = 192, 108
     sky, bn = scenes.sky(512, 256), assets.load_bluenoise()
-    pt = tracer(scenes.atrium(0.25), W, H, sky, bn)
-    gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, s, ATRIUM_MOVE), 1, 4, frame=1 + s, flags=DEFAULT_FLAGS) for s in range(6)]
+    pt = tracer(scenes.atrium(0.25), (W, H), sky=sky, bluenoise=bn)
+    gs = [pt.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), s, ATRIUM_MOVE), 1, 4, frame=1 + s, flags=DEFAULT_FLAGS) for s in range(6)]
     r = check_sequence(pt, gs, "atrium temporal + denoise", denoise=True)
     fg = r["depth"] != BG
     old = fg & (r["mom"][..., 3] >= 4)
@@ -179,8 +149,7 @@ def test_temporal_then_denoise_with_the_variance_input():
     assert not np.array_equal(bits(den), bits(plain))
     h = pt.handles
     pt.ctx.set_denoise_variance_input(0)
-    b = (C.c_uint32 * 4)(h["gbuffer"], h["depth"], h["accumulated"], h["denoised"])
-    pt.ctx.check(pt.ctx.lib.rt3_pass_launch(pt.ctx.h, b"denoise", b"main", math.ceil(W / 8), math.ceil(H / 8), 1, C.byref(gs[-1]), 304, b, 4))
+    pt.ctx.check(launch(pt, "denoise", math.ceil(W / 8), math.ceil(H / 8), 1, gs[-1], [h["gbuffer"], h["depth"], h["accumulated"], h["denoised"]]))
     pt.ctx.wait()
     same(pt.denoised(), plain, "denoise, variance input unset")
     # render(denoise=True) without temporal clears the input too
@@ -192,8 +161,8 @@ def test_temporal_then_denoise_with_the_variance_input():
 
 def test_deterministic_and_outputs_prefilled_with_nan():
     W, H = 128, 96
-    pt = tracer(scenes.cornell(), W, H)
-    gs = [pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H, s, CORNELL_MOVE), 1, 4, frame=9 + s, flags=L.F_FACEFORWARD) for s in range(3)]
+    pt = tracer(scenes.cornell(), (W, H))
+    gs = [pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H), s, CORNELL_MOVE), 1, 4, frame=9 + s, flags=L.F_FACEFORWARD) for s in range(3)]
     a = check_sequence(pt, gs, "run 1")
     nan = np.full((H, W, 4), np.nan, F)
     for name in ("accumulated", "History", "Moments", "PrevHistory", "PrevMoments"):  # reset_history() must not depend on what they hold
@@ -204,22 +173,17 @@ def test_deterministic_and_outputs_prefilled_with_nan():
     pt.close()
 
 
-def launch(pt, name, x, y, z, g, bindings):
-    b = (C.c_uint32 * max(1, len(bindings)))(*bindings)
-    return pt.ctx.lib.rt3_pass_launch(pt.ctx.h, name.encode(), b"main", x, y, z, C.byref(g), C.sizeof(g), b, len(bindings))
-
-
 def test_errors_leave_the_context_usable():
     from raytracer3_amd.render_graph import ImageSize
 
     W, H = 100, 60
-    pt = tracer(scenes.cornell(), W, H)
-    g0 = pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H, 0, CORNELL_MOVE), 2, 3, frame=1, flags=L.F_FACEFORWARD)
-    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, W, H, 1, CORNELL_MOVE), 2, 3, frame=2, flags=L.F_FACEFORWARD)
+    pt = tracer(scenes.cornell(), (W, H))
+    g0 = pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H), 0, CORNELL_MOVE), 2, 3, frame=1, flags=L.F_FACEFORWARD)
+    g = pt.make_gconst(camera(scenes.CORNELL_CAMERA, (W, H), 1, CORNELL_MOVE), 2, 3, frame=2, flags=L.F_FACEFORWARD)
     pt.render(g0, temporal=True)
     h = pt.render(g, temporal=True, denoise=True)
     first = (pt.accumulated(), *pt.history())
-    lib, err = pt.ctx.lib, lambda: pt.ctx.lib.rt3_last_error(pt.ctx.h).decode()
+    lib, err = pt.ctx.lib, pt.ctx.last_error
     X, Y = math.ceil(W / 8), math.ceil(H / 8)
     names = ["gbuffer", "depth", "light", "prev_gbuffer", "prev_depth", "prev_history", "prev_moments", "accumulated", "history", "moments"]
     shown = ["gbuffer", "gbuffer_depth", "In", "PrevGbuffer", "PrevDepth", "PrevHistory", "PrevMoments", "Out", "History", "Moments"]
@@ -254,7 +218,7 @@ def test_errors_leave_the_context_usable():
     assert launch(pt, "temporal", X, Y, 1, g, good) == 0  # ... refused calls left the view in place
     pt.ctx.set_prev_view(None)
     assert launch(pt, "temporal", X, Y, 1, g, good) == L.E_STATE and "previous view" in err()
-    other = camera(scenes.CORNELL_CAMERA, W, H).gconst((W + 1, H))
+    other = camera(scenes.CORNELL_CAMERA, (W, H)).gconst((W + 1, H))
     pt.ctx.set_prev_view(other)
     assert launch(pt, "temporal", X, Y, 1, g, good) == L.E_INVALID and "window_size" in err()
     pt.ctx.set_prev_view(g0)
@@ -302,14 +266,14 @@ def test_multi_rank_temporal_on_the_gather_root():
 
     mesh, sky, bn = scenes.atrium(0.25), scenes.sky(128, 64), assets.load_bluenoise()
     W, H, n, root = 200, 136, 3, 0
-    solo = tracer(mesh, W, H, sky, bn)
+    solo = tracer(mesh, (W, H), sky=sky, bluenoise=bn)
     pts = [PathTracer((W, H), rank=r, n_ranks=n) for r in range(n)]
     for pt in pts:
         pt.set_scene(mesh, sky, bn)
     rootpt = pts[root]
     zero = np.zeros((H, W, 4), F)
     for k in range(2):
-        g = solo.make_gconst(camera(scenes.ATRIUM_CAMERA, W, H, k, ATRIUM_MOVE), 2, 3, frame=6 + k, flags=DEFAULT_FLAGS)
+        g = solo.make_gconst(camera(scenes.ATRIUM_CAMERA, (W, H), k, ATRIUM_MOVE), 2, 3, frame=6 + k, flags=DEFAULT_FLAGS)
         solo.rg.upload(solo.commands(g)["light"], zero)  # k_accumulate leaves background pixels of Light unwritten: give them known bits
         solo.render(g, temporal=True, denoise=True)
         want = (solo.light(), solo.accumulated(), *solo.history(), solo.denoised())
@@ -352,7 +316,7 @@ def test_cpp_host_renders_two_temporal_frames(tmp_path):
         subprocess.check_call(["make", "-C", str(exe.parent)])
     mesh, sky, bn = scenes.atrium(0.2), scenes.sky(256, 128), assets.load_bluenoise()
     W, H, spp, bounces, frame, flags = 96, 54, 2, 3, 9, 15
-    cam = camera(scenes.ATRIUM_CAMERA, W, H)
+    cam = camera(scenes.ATRIUM_CAMERA, (W, H))
     scene = tmp_path / "scene.bin"
     with open(scene, "wb") as f:
         f.write(struct.pack("<8I", len(mesh.vertices), len(mesh.indices), len(mesh.geometries), sky.shape[1], sky.shape[0], bn.shape[1], bn.shape[0], 0))

@@ -16,29 +16,13 @@ import ref_denoise as rd
 import ref_temporal as rt
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
-from raytracer3_amd.assets import Material, MeshBuilder
+from raytracer3_amd.assets import MeshBuilder
 from raytracer3_amd.render_graph import RenderGraph
+from support import RecordingCtx, bits, gamma, quad, rmse_fg, zeros
 
 U = 2.0 ** -24  # unit roundoff of float32
 BG = np.float32(orc.BACKGROUND_DEPTH)
 F = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def gamma(n):
-    """Higham's gamma_n = n u / (1 - n u): the relative error bound of n chained float32 roundings"""
-    return n * U / (1 - n * U)
-
-
-def rmse_fg(a, ref, fg):
-    return float(np.sqrt((((a[..., :3].astype(np.float64) - ref[..., :3].astype(np.float64))[fg]) ** 2).mean()))
-
-
-def zeros(H, W):
-    return np.zeros((H, W, 4), F)
 
 
 # ------------------------------------------------------------------------------------------------ the two oracle cases
@@ -160,12 +144,6 @@ def test_moving_camera_beats_one_sample_and_the_prevlight_blend(name):
 
 
 # ------------------------------------------------------------------------------------------------ 4. no bleeding, from geometry alone
-def quad(mb, name, origin, du, dv, color):
-    o, du, dv = (np.asarray(a, np.float64) for a in (origin, du, dv))
-    pos = np.array([o, o + du, o + du + dv, o + dv])
-    n = np.cross(du, dv)
-    mb.add(name, pos, np.tile(n / np.linalg.norm(n), (4, 1)), np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float64), [[0, 1, 2], [0, 2, 3]],
-           Material(color))
 
 
 def synthetic(kind, step, W=96, H=80):
@@ -302,27 +280,6 @@ def test_denoise_starts_from_the_temporal_variance():
 
 
 # ------------------------------------------------------------------------------------------------ 6. the Python surface
-class RecordingCtx:
-    """stands in for render_graph.Context: records rt3_pass_launch instead of running it"""
-
-    def __init__(self):
-        self.calls, self.n = [], 0
-        self.lib, self.h = self, None
-
-    def check(self, rc):
-        assert rc == 0
-
-    def rt3_image_create(self, h, w, hh, fmt, out):
-        self.n += 1
-        out._obj.value = (L.TAG_IMAGE << 30) | self.n
-        return 0
-
-    def rt3_pass_launch(self, h, path, entry, x, y, z, cst, size, b, nb):
-        self.calls.append((path.decode(), (x, y, z), [b[i] for i in range(nb)]))
-        return 0
-
-    def wait(self):
-        pass
 
 
 def test_frame_graph_places_the_temporal_node():

@@ -14,21 +14,11 @@ import orc
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.render_graph import Context
+from support import bits, soup_mesh
 
 pytestmark = pytest.mark.gpu
 
 N_RAYS = 4096
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def soup_mesh(tri):
-    mb = assets.MeshBuilder()
-    v = np.ascontiguousarray(tri, np.float32).reshape(-1, 3)
-    mb.add("soup", v, np.tile([0, 0, 1], (len(v), 1)), None, np.arange(len(v), dtype=np.uint32).reshape(-1, 3), assets.Material())
-    return mb.build()
 
 
 def rays_at(tri, n=N_RAYS, seed=1):

@@ -12,16 +12,12 @@ import orc
 from raytracer3_amd import _lib as L
 from raytracer3_amd import assets, scenes
 from raytracer3_amd.render_graph import Context
-from test_gpu_parity import as_orc, render_both
-from test_instances_two_level import rotation
+from support import as_orc, bits, rotation, soup_mesh
+from test_gpu_parity import render_both
 from test_traversal_exactness_cpu import (DISPUTED_MAX, LAYOUTS, PLACEMENTS, SCENES, base_mesh, brute, check_against_brute,
                                           interval_rays, placed, ray_families)
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def all_rays(mesh, osc, seed):
@@ -71,14 +67,6 @@ def test_trace_rays_equal_brute_force(name, scale, offset):
                 check_gpu(f"{name} x{scale} +{offset} layout {lay} {fam}", ctx, osc, rays, ref, dp, DISPUTED_MAX[fam])
         finally:
             ctx.close()
-
-
-def soup_mesh(tri):
-    """a mesh of world-space triangles (n, 3, 3), for generating rays against a flattened instance scene"""
-    mb = assets.MeshBuilder()
-    v = np.ascontiguousarray(tri, np.float32).reshape(-1, 3)
-    mb.add("soup", v, np.tile([0, 0, 1], (len(v), 1)), None, np.arange(len(v), dtype=np.uint32).reshape(-1, 3), assets.Material())
-    return mb.build()
 
 
 def far_instances(seed=9, n=12, at=(1e4, 1.2e4, -1e4)):

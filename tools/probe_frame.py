@@ -8,7 +8,6 @@ Frames accumulate through trace_probes' temporal blend (prev_probe_atlas, blendf
 trace_probes.slang:74 keeps in a comment (RT3_F_PROBE_RADIANCE) unless --as-written is given, which shows the debug state.
 """
 import argparse
-import math
 import sys
 import time
 from pathlib import Path
@@ -33,14 +32,14 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import scenes
-    from raytracer3_amd.renderer import Camera, PathTracer
+    from raytracer3_amd.renderer import PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     mesh, cam_kw = (scenes.cornell(), scenes.CORNELL_CAMERA) if args.scene == "cornell" else (scenes.atrium(1.0), scenes.ATRIUM_CAMERA)
     pt = PathTracer((W, H))
     pt.set_scene(mesh, scenes.sky(512, 256) if args.scene == "atrium" else None)
     pt.ctx.set_option(L.OPT_PROFILE, 1)
-    cam = Camera(cam_kw["position"], cam_kw["direction"], math.radians(cam_kw["fov_deg"]), W / H)
+    cam = default_camera((W, H), cam_kw["position"], cam_kw["direction"], cam_kw["fov_deg"])
     flags = 0 if args.as_written else L.F_PROBE_RADIANCE
     wall = []
     for f in range(args.frames):

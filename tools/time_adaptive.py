@@ -53,12 +53,12 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
     pt.set_scene(scenes.atrium(args.detail), scenes.sky(2048, 1024), assets.load_bluenoise())
-    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], scenes.ATRIUM_CAMERA["fov_deg"])
 
     def timed(samples, adaptive=None, frames=args.frames, warmup=args.warmup):
         """median ms of `frames` waited frames (frame numbers 0, 1, ...; the last one's images stay)"""

@@ -10,7 +10,6 @@ Prints one JSON line (medians of --frames timed frames after --warmup).
 """
 import argparse
 import json
-import math
 import statistics
 import sys
 import time
@@ -34,7 +33,7 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     mesh = scenes.cutout_cornell()
@@ -46,7 +45,7 @@ def main():
         "mask_opaque": assets.Mesh(mesh.vertices, mesh.indices, g1, mesh.prim_counts, list(mesh.names), solid, mesh.alpha_cutoffs),
         "masked": mesh,
     }
-    cam = Camera(scenes.CORNELL_CAMERA["position"], scenes.CORNELL_CAMERA["direction"], math.radians(scenes.CORNELL_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.CORNELL_CAMERA["position"], scenes.CORNELL_CAMERA["direction"], scenes.CORNELL_CAMERA["fov_deg"])
     result = {"scene": "cutout_cornell", "size": [W, H], "spp": args.spp, "bounces": args.bounces, "flags": DEFAULT_FLAGS}
     for name, m in variants.items():
         pt = PathTracer((W, H))

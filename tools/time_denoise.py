@@ -14,7 +14,6 @@
   python tools/time_denoise.py --size 1920x1080 --out time_denoise.json
 """
 import argparse
-import ctypes as C
 import json
 import math
 import statistics
@@ -47,12 +46,12 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
     pt.set_scene(scenes.atrium(args.detail), scenes.sky(2048, 1024), assets.load_bluenoise())
-    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], scenes.ATRIUM_CAMERA["fov_deg"])
     ctx = pt.ctx
 
     def gconst(spp, frame):
@@ -61,11 +60,11 @@ def main():
     # ---- the pass alone, HIP events
     g = gconst(1, 1)
     h = pt.render(g, denoise=True)
-    b = (C.c_uint32 * 4)(h["gbuffer"], h["depth"], h["light"], h["denoised"])
+    b = [h["gbuffer"], h["depth"], h["light"], h["denoised"]]
     X, Y = -(-W // 8), -(-H // 8)
 
     def launch():
-        ctx.check(ctx.lib.rt3_pass_launch(ctx.h, b"denoise", b"main", X, Y, 1, C.byref(g), C.sizeof(g), b, 4))
+        ctx.check(ctx.pass_launch("denoise", X, Y, 1, g, b))
 
     ctx.set_option(L.OPT_PROFILE, 1)
     pass_ms, rows = {}, []

@@ -10,7 +10,6 @@ over all its timed frames, the median of each round, the extension rays per fram
 """
 import argparse
 import json
-import math
 import statistics
 import sys
 import time
@@ -35,12 +34,12 @@ def main():
     args = ap.parse_args()
 
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
     pt.set_scene(scenes.atrium(args.detail), scenes.sky(2048, 1024), assets.load_bluenoise())
-    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], scenes.ATRIUM_CAMERA["fov_deg"])
     result = {"scene": "atrium", "detail": args.detail, "size": [W, H], "spp": args.spp, "bounces": args.bounces, "rounds": args.rounds, "runs": []}
     configs = {"off": None, "antialiasing": (0.0, 1.0, 1.0), "aperture": (args.aperture, args.focus, 1.0)}
     runs = {name: {"lens": name, "params": list(p) if p else None, "ms_rounds": [], "ms_all": []} for name, p in configs.items()}

@@ -9,7 +9,6 @@ its timed frames, the median of each round, and the shadow rays per frame (rt3_s
 """
 import argparse
 import json
-import math
 import statistics
 import sys
 import time
@@ -51,12 +50,12 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
     pt.set_scene(scenes.atrium(args.detail), scenes.sky(2048, 1024), assets.load_bluenoise())
-    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], scenes.ATRIUM_CAMERA["fov_deg"])
     result = {"scene": "atrium", "detail": args.detail, "size": [W, H], "spp": args.spp, "bounces": args.bounces, "rounds": args.rounds, "runs": []}
     configs = [(n, emissive) for n in (0, 1, 16) for emissive in (False, True)]
     runs = {cfg: {"lights": cfg[0], "nee_emissive": cfg[1], "ms_rounds": [], "ms_all": []} for cfg in configs}

@@ -14,7 +14,6 @@ Prints one JSON line (medians of --frames timed frames after --warmup).
 """
 import argparse
 import json
-import math
 import re
 import statistics
 import subprocess
@@ -62,7 +61,7 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     rng = np.random.default_rng(args.seed)
@@ -80,7 +79,7 @@ def main():
 
     variants = {"none": variant(()), "mr": variant((0,)), "normal": variant((1,)), "emissive": variant((2,)), "all": variant((0, 1, 2))}
     c = scenes.ATRIUM_CAMERA
-    cam = Camera(c["position"], c["direction"], math.radians(c["fov_deg"]), W / H)
+    cam = default_camera((W, H), c["position"], c["direction"], c["fov_deg"])
     result = {"scene": "atrium", "detail": args.detail, "size": [W, H], "spp": args.spp, "bounces": args.bounces, "flags": DEFAULT_FLAGS}
     sky, bn = scenes.sky(2048, 1024), assets.load_bluenoise()
     for name, m in variants.items():

@@ -18,9 +18,7 @@ compare kernel over that range, and "motion" with the deformed mesh in view (bot
   python tools/time_motion.py --size 1920x1080 --out time_motion.json
 """
 import argparse
-import ctypes as C
 import json
-import math
 import statistics
 import sys
 from pathlib import Path
@@ -86,7 +84,7 @@ def main():
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
     from raytracer3_amd.render_graph import ImageSize
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     mesh = scenes.atrium(args.detail)
@@ -112,7 +110,7 @@ def main():
         pt.set_instances(world(k))
         pos = np.asarray(kw["position"], np.float32) + np.float32(k) * np.array([0.02, 0.0, 0.01], np.float32)
         dirn = np.asarray(kw["direction"], np.float32) + np.float32(k) * np.array([0.0, 0.0, 0.012], np.float32)
-        gs.append(pt.make_gconst(Camera(pos, dirn, math.radians(kw["fov_deg"]), W / H), 1, args.bounces, frame=k + 1, flags=DEFAULT_FLAGS))
+        gs.append(pt.make_gconst(default_camera((W, H), pos, dirn, kw["fov_deg"]), 1, args.bounces, frame=k + 1, flags=DEFAULT_FLAGS))
         h = pt.render(gs[-1], temporal=True)
     g = gs[1]
     M = pt.motion()  # the second frame had the node
@@ -121,10 +119,8 @@ def main():
     n_moved = float(n_hist[M[..., 3] == 2].mean()) if moved else 0.0
 
     def passes(name, x, y, z, bindings):
-        b = (C.c_uint32 * len(bindings))(*bindings)
-
         def launch():
-            ctx.check(ctx.lib.rt3_pass_launch(ctx.h, name.encode(), b"main", x, y, z, C.byref(g), C.sizeof(g), b, len(bindings)))
+            ctx.check(ctx.pass_launch(name, x, y, z, g, bindings))
 
         for _ in range(args.warmup):
             launch()
@@ -145,7 +141,7 @@ def main():
     ctx.set_prev_transforms(None)
     out["motion_nothing_moved"] = passes("motion", W, H, 1, [h["motion"]])
     ctx.set_prev_transforms([m for _, _, m in world(0)])
-    ctx.check(ctx.lib.rt3_pass_launch(ctx.h, b"motion", b"main", W, H, 1, C.byref(g), C.sizeof(g), (C.c_uint32 * 1)(h["motion"]), 1))
+    ctx.check(ctx.pass_launch("motion", W, H, 1, g, [h["motion"]]))
     tb = [h[n] for n in ("gbuffer", "depth", "light", "prev_gbuffer", "prev_depth", "prev_history", "prev_moments", "accumulated", "history", "moments")]
     X, Y = -(-W // 8), -(-H // 8)
     out["temporal_with_motion_input"] = passes("temporal", X, Y, 1, tb)

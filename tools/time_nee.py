@@ -7,7 +7,6 @@ one frame against a flag-less reference of --ref-frames x --spp samples per pixe
 """
 import argparse
 import json
-import math
 import statistics
 import sys
 import time
@@ -33,12 +32,12 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
     pt.set_scene(scenes.atrium(args.detail), scenes.sky(2048, 1024), assets.load_bluenoise())
-    cam = Camera(scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], math.radians(scenes.ATRIUM_CAMERA["fov_deg"]), W / H)
+    cam = default_camera((W, H), scenes.ATRIUM_CAMERA["position"], scenes.ATRIUM_CAMERA["direction"], scenes.ATRIUM_CAMERA["fov_deg"])
 
     def render(flags, index):
         pt.render(pt.make_gconst(cam, args.spp, args.bounces, frame=index, flags=flags))

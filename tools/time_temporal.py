@@ -12,9 +12,7 @@ reaches on this GPU, the fraction of that floor the pass reaches, and the rate a
   python tools/time_temporal.py --size 1920x1080 --out time_temporal.json
 """
 import argparse
-import ctypes as C
 import json
-import math
 import statistics
 import sys
 from pathlib import Path
@@ -40,7 +38,7 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, PathTracer, default_camera
 
     W, H = (int(x) for x in args.size.split("x"))
     pt = PathTracer((W, H))
@@ -51,17 +49,17 @@ def main():
     for k in range(2):
         pos = np.asarray(kw["position"], np.float32) + np.float32(k) * np.array([0.02, 0.0, 0.01], np.float32)
         dirn = np.asarray(kw["direction"], np.float32) + np.float32(k) * np.array([0.0, 0.0, 0.012], np.float32)
-        gs.append(pt.make_gconst(Camera(pos, dirn, math.radians(kw["fov_deg"]), W / H), 1, args.bounces, frame=k + 1, flags=DEFAULT_FLAGS))
+        gs.append(pt.make_gconst(default_camera((W, H), pos, dirn, kw["fov_deg"]), 1, args.bounces, frame=k + 1, flags=DEFAULT_FLAGS))
         h = pt.render(gs[-1], temporal=True)
     g = gs[1]
     fg = int((pt.gbuffer()[1] != np.float32(L.BACKGROUND_DEPTH)).sum())
     n_hist = pt.history()[0][..., 3]
-    b = (C.c_uint32 * 10)(h["gbuffer"], h["depth"], h["light"], h["prev_gbuffer"], h["prev_depth"], h["prev_history"], h["prev_moments"],
-                          h["accumulated"], h["history"], h["moments"])
+    b = [h["gbuffer"], h["depth"], h["light"], h["prev_gbuffer"], h["prev_depth"], h["prev_history"], h["prev_moments"],
+         h["accumulated"], h["history"], h["moments"]]
     X, Y = -(-W // 8), -(-H // 8)
 
     def launch():
-        ctx.check(ctx.lib.rt3_pass_launch(ctx.h, b"temporal", b"main", X, Y, 1, C.byref(g), C.sizeof(g), b, 10))
+        ctx.check(ctx.pass_launch("temporal", X, Y, 1, g, b))
 
     def timed():
         for _ in range(args.warmup):
