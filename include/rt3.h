@@ -230,6 +230,41 @@ typedef struct rt3_material_textures {
     float   normal_scale;               /* glTF normalTexture.scale */
 } rt3_material_textures;                /* 16 bytes */
 int rt3_scene_set_material_textures(rt3_ctx *ctx, const rt3_material_textures *m, uint32_t n);
+/* ---- glass: transmissive dielectric surfaces, solid and thin-walled (glTF KHR_materials_transmission, _ior, _volume).  No reference
+ *      counterpart.  DESIGN.md section 4n.  One entry per geometry of the last rt3_scene_set_geometry (n = that count), or n = 0: no glass,
+ *      which is also what rt3_scene_set_geometry resets every geometry to.
+ *       - Lobe selection: a path vertex on a geometry with transmission t > 0 is a glass vertex with probability t, decided by the draw at
+ *         RNG index 0x40000000 + 2 (s B + b) of the pixel's stream (s the absolute sample index, b the bounce, B = GConst.bounces; no draw
+ *         at t = 1, no blue-noise shift): glass when u < t.  Otherwise the vertex is shaded as without this call, from the same draws.
+ *       - The glass vertex is a smooth, delta dielectric.  n: the shading normal, not face-forwarded (RT3_F_FACEFORWARD and RT3_F_SPECULAR
+ *         do not affect it); d: the ray direction, normalised.  The ray enters when dot(n, d) < 0: eta = ior, else 1 / ior (every
+ *         interface is air <-> ior; nested media are not modelled).  cos_i = |n.d|, cos_t^2 = 1 - (1 - cos_i^2) / eta^2; cos_t^2 <= 0:
+ *         total internal reflection, F = 1; else F = (r_s^2 + r_p^2) / 2, r_s = (cos_i - eta cos_t) / (cos_i + eta cos_t),
+ *         r_p = (eta cos_i - cos_t) / (eta cos_i + cos_t) (exact Fresnel).  thin_walled: eta = ior on both sides and
+ *         F' = 2 F / (1 + F), the sum of a slab's inter-reflections; the transmitted direction is d.  The draw at index + 1 picks the
+ *         event: u < F mirrors d about n, throughput unchanged; else transmission along d / eta + (cos_i / eta - cos_t) n' (n' the normal
+ *         on the incoming side), throughput x albedo (base colour x base-colour texture).  Emission is collected as at any vertex.
+ *       - A glass vertex takes no light sample (no sky, emitter or punctual shadow ray); what its extension ray finds counts with weight
+ *         1 (an emitter under RT3_F_NEE_EMISSIVE, the sky under RT3_F_NEE_SKY).  At the last vertex (b = B - 1) under RT3_F_NEE_SKY the
+ *         chosen direction goes out as the sky shadow ray, carrying throughput x the sky's bilinear radiance along it.
+ *       - Without RT3_F_NEE_SKY a ray that escapes after nothing but glass vertices since the camera adds throughput x the sky's bilinear
+ *         radiance, as an escaped camera ray of a lens frame does; after any other vertex it adds nothing, as without glass.
+ *       - Shadow rays are unchanged: glass occludes them.  Light through glass arrives by BSDF-sampled paths only (unbiased for emitters
+ *         and the sky); punctual lights do not shine through glass.  Alpha cutoffs work independently on the same geometry.
+ *       - The packed G-buffer has no room for a material class: in a built scene with glass "refrence_mode" needs per-sample camera rays
+ *         (rt3_camera_set_lens; {0, f, 0} is the per-sample pinhole) and returns RT3_E_STATE without, as does "adaptive" always; with
+ *         samples * bounces * 8 > 2^30 it returns RT3_E_INVALID (the vertices' RNG indices would reach the glass draws').  "gbuffer",
+ *         "denoise", "temporal", "motion", the probe passes and rt3_trace_rays see glass as the opaque surface its material describes.
+ *      Works in both instance modes, after rt3_accel_import and across rt3_accel_refit.  A value that is not finite, a transmission outside
+ *      [0, 1], ior < 1, thin_walled > 1, reserved != 0 or a wrong n is RT3_E_INVALID and changes nothing.  Takes effect at the next
+ *      rt3_accel_build; until then an existing structure is unusable, as after rt3_scene_set_alpha_cutoffs.  Borrowed for the call. ---- */
+typedef struct rt3_transmission {
+    float    transmission; /* [0, 1]: the probability that a vertex on the geometry is a glass vertex */
+    float    ior;          /* >= 1 */
+    uint32_t thin_walled;  /* 0 = solid (refracts), 1 = thin-walled (a pane: passes straight through) */
+    uint32_t reserved;     /* 0 */
+} rt3_transmission;        /* 16 bytes */
+int rt3_scene_set_transmission(rt3_ctx *ctx, const rt3_transmission *t, uint32_t n);
 
 /* ---- instances: the reference's world is a list of placed meshes (add_instance / loaded_assets, world/mod.rs:50-101) under a
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info
@@ -636,6 +671,8 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      31 the camera sample of rt3_camera_set_lens (proj_inverse[16], view_inverse[16], window_size[2], aperture_radius, focus_distance,
  *      pixel_jitter, px, py, frame, absolute sample index as u32: 41 words -> ray origin xyz, direction xyz, film point in pixels xy, lens
  *      point in view space xy: 10 words); reads no context state.
+ *      32 the glass function of rt3_scene_set_transmission (ior, thin_walled as u32, d xyz, n xyz, u: 9 words -> event as u32 (0 reflect /
+ *      1 transmit), direction xyz, reflection probability F: 5 words); reads no context state.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

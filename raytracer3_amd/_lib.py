@@ -31,12 +31,14 @@ TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "tem
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
 SELFTEST_HIT_INFO = 29  # rt3_selftest_eval op: {flattened primitive (u32), bu, bv} -> Surface (11 words), hit_info of the built world
 SELFTEST_LENS = 31  # rt3_selftest_eval op: {proj_inverse, view_inverse, window, lens, px, py, frame, sample} (41 words) -> {o, d, film, lens point} (10)
+SELFTEST_GLASS = 32  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, u} (9 words) -> {event (u32), direction, F} (5), the glass function
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_alpha_cutoffs",
     "rt3_scene_set_material_textures",
+    "rt3_scene_set_transmission",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_exit_table_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
@@ -171,6 +173,7 @@ def load():
         "rt3_scene_set_texture": (i32, [vp, u32, vp, u32, u32]),
         "rt3_scene_set_alpha_cutoffs": (i32, [vp, vp, u32]),
         "rt3_scene_set_material_textures": (i32, [vp, vp, u32]),
+        "rt3_scene_set_transmission": (i32, [vp, vp, u32]),
         "rt3_scene_set_instances": (i32, [vp, vp, u32]),
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),

@@ -38,6 +38,9 @@ MATERIAL_TEXTURES_DTYPE = np.dtype(
     [("metallic_roughness_texture", "<i4"), ("normal_texture", "<i4"), ("emissive_texture", "<i4"), ("normal_scale", "<f4")]
 )
 assert MATERIAL_TEXTURES_DTYPE.itemsize == 16
+# rt3_transmission (include/rt3.h): glass per geometry
+TRANSMISSION_DTYPE = np.dtype([("transmission", "<f4"), ("ior", "<f4"), ("thin_walled", "<u4"), ("reserved", "<u4")])
+assert TRANSMISSION_DTYPE.itemsize == 16
 # rt3_punctual_light (include/rt3.h): a point, spot or directional light of KHR_lights_punctual, in world space
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2
 LIGHT_DTYPE = np.dtype(
@@ -81,6 +84,14 @@ def no_material_textures(n: int) -> np.ndarray:
     return t
 
 
+def no_transmission(n: int) -> np.ndarray:
+    """n entries of TRANSMISSION_DTYPE without glass: what a glTF material without the transmission, ior and volume extensions is
+    (transmission 0, ior 1.5, thin-walled)"""
+    t = np.zeros(n, TRANSMISSION_DTYPE)
+    t["ior"], t["thin_walled"] = 1.5, 1
+    return t
+
+
 @dataclass
 class Material:
     """assets/mod.rs:52-59 (f16 fields there; plain floats here) + emission (datatypes.slang:17)."""
@@ -97,6 +108,10 @@ class Material:
     normal_texture: int = -1  # tangent-space normal map, linear
     emissive_texture: int = -1  # sRGB-encoded colour
     normal_scale: float = 1.0  # glTF normalTexture.scale
+    # glass: KHR_materials_transmission, _ior, _volume
+    transmission: float = 0.0  # transmissionFactor
+    ior: float = 1.5
+    thin_walled: int = 1  # 0 = solid: the material has a volume (thicknessFactor > 0)
 
 
 @dataclass
@@ -112,12 +127,16 @@ class Mesh:
     alpha_cutoffs: np.ndarray = None  # (g,) float32 alpha cutoff per geometry (rt3_scene_set_alpha_cutoffs); None -> zeros (all opaque)
     material_textures: np.ndarray = None  # (g,) MATERIAL_TEXTURES_DTYPE (rt3_scene_set_material_textures); None -> no texture anywhere
     lights: np.ndarray = None  # (l,) LIGHT_DTYPE punctual lights (rt3_scene_set_lights); None -> none
+    transmission: np.ndarray = None  # (g,) TRANSMISSION_DTYPE glass (rt3_scene_set_transmission); None -> no glass anywhere
 
     def __post_init__(self):
         self.lights = np.ascontiguousarray(np.zeros(0, LIGHT_DTYPE) if self.lights is None else self.lights, LIGHT_DTYPE).reshape(-1)
         if self.material_textures is None:
             self.material_textures = no_material_textures(len(self.geometries))
         self.material_textures = np.ascontiguousarray(self.material_textures, MATERIAL_TEXTURES_DTYPE).reshape(len(self.geometries))
+        if self.transmission is None:
+            self.transmission = no_transmission(len(self.geometries))
+        self.transmission = np.ascontiguousarray(self.transmission, TRANSMISSION_DTYPE).reshape(len(self.geometries))
         if self.alpha_cutoffs is None:
             self.alpha_cutoffs = np.zeros(len(self.geometries), np.float32)
         self.alpha_cutoffs = np.ascontiguousarray(self.alpha_cutoffs, np.float32).reshape(len(self.geometries))
@@ -140,7 +159,7 @@ class MeshBuilder:
     """Accumulates (positions, normals, uvs, triangles, material) parts into a `Mesh`."""
 
     def __init__(self):
-        self.v, self.i, self.g, self.c, self.names, self.cut, self.mt = [], [], [], [], [], [], []
+        self.v, self.i, self.g, self.c, self.names, self.cut, self.mt, self.tr = [], [], [], [], [], [], [], []
         self.nv = 0
         self.ni = 0
 
@@ -168,6 +187,7 @@ class MeshBuilder:
         self.c.append(len(tris))
         self.cut.append(mat.alpha_cutoff)
         self.mt.append((mat.metallic_roughness_texture, mat.normal_texture, mat.emissive_texture, mat.normal_scale))
+        self.tr.append((mat.transmission, mat.ior, mat.thin_walled, 0))
         self.names.append(name)
         self.nv += len(pos)
         self.ni += tris.size
@@ -181,6 +201,7 @@ class MeshBuilder:
             list(self.names),
             alpha_cutoffs=np.array(self.cut, np.float32),
             material_textures=np.array(self.mt, MATERIAL_TEXTURES_DTYPE),
+            transmission=np.array(self.tr, TRANSMISSION_DTYPE),
         )
 
 
@@ -193,6 +214,7 @@ def write_glb(path, mesh: Mesh) -> None:
     """One glTF mesh+node per geometry, identity transforms, u32 indices, one material per geometry; one node per punctual light
     (KHR_lights_punctual: translation, and the rotation that takes -z to the light's direction)."""
     bin_parts, views, accessors, meshes, nodes, materials = [], [], [], [], [], []
+    used = []  # extensionsUsed, in order of first use
     off = 0
 
     def push(arr, target=None):
@@ -241,6 +263,17 @@ def write_glb(path, mesh: Mesh) -> None:
             mtl["emissiveTexture"] = {"index": int(mt["emissive_texture"])}
         if float(mesh.alpha_cutoffs[gi]) > 0.0:  # masked; opaque is glTF's default and stays implicit
             mtl["alphaMode"], mtl["alphaCutoff"] = "MASK", float(mesh.alpha_cutoffs[gi])
+        # glass: the three extensions' defaults -- no transmission, ior 1.5, no volume = thin-walled -- stay implicit
+        tr, ext = mesh.transmission[gi], {}
+        if float(tr["transmission"]) > 0.0:
+            ext["KHR_materials_transmission"] = {"transmissionFactor": float(tr["transmission"])}
+        if float(tr["transmission"]) > 0.0 or float(tr["ior"]) != 1.5:
+            ext["KHR_materials_ior"] = {"ior": float(tr["ior"])}
+        if int(tr["thin_walled"]) == 0:
+            ext["KHR_materials_volume"] = {"thicknessFactor": 1.0}
+        if ext:
+            mtl["extensions"] = ext
+            used += [k for k in ext if k not in used]
         materials.append(mtl)
         meshes.append({"name": mesh.names[gi] if gi < len(mesh.names) else f"g{gi}",
                        "primitives": [{"attributes": {"POSITION": acc[0], "NORMAL": acc[1], "TEXCOORD_0": acc[2]}, "indices": ia, "material": gi}]})
@@ -286,8 +319,10 @@ def write_glb(path, mesh: Mesh) -> None:
     if images:
         doc["images"], doc["textures"] = images, textures
     if gl_lights:
-        doc["extensionsUsed"] = ["KHR_lights_punctual"]
+        used.append("KHR_lights_punctual")
         doc["extensions"] = {"KHR_lights_punctual": {"lights": gl_lights}}
+    if used:
+        doc["extensionsUsed"] = used
     js = json.dumps(doc, separators=(",", ":")).encode()
     js += b" " * ((-len(js)) % 4)
     blob = b"".join(bin_parts)
@@ -416,10 +451,15 @@ class GltfMeshLoader:
                         def tex_index(info):  # a texture reference; one through another uv set than TEXCOORD_0 counts as absent
                             return int(info.get("index", -1)) if info and info.get("texCoord", 0) == 0 else -1
 
+                        # glass: a transmission texture is ignored; no volume extension, or thicknessFactor 0, is thin-walled
+                        gext = gmtl.get("extensions", {})
+                        tau = float(gext.get("KHR_materials_transmission", {}).get("transmissionFactor", 0.0))
+                        ior = float(gext.get("KHR_materials_ior", {}).get("ior", 1.5))
+                        thin = 0 if float(gext.get("KHR_materials_volume", {}).get("thicknessFactor", 0.0)) > 0.0 else 1
                         nt = gmtl.get("normalTexture")
                         mat = Material(tuple(bc[:3]), pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), tuple(em), tex, cut,
                                        float(bc[3]) if len(bc) > 3 else 1.0, tex_index(pbr.get("metallicRoughnessTexture")), tex_index(nt),
-                                       tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0)
+                                       tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0, tau, ior, thin)
                     mb.add(f"{gm.get('name', 'mesh')}.{pi}", pos, nrm, uv, tris, mat, normalize=not keep)
             for c in node.get("children", []):
                 visit(c, m)

@@ -87,6 +87,7 @@ static int flatten_world(rt3_ctx* c) {
     std::vector<FlatGeomDev> flat;
     std::vector<ShadeGeomDev> shade;
     std::vector<MatTexDev> mats;
+    std::vector<GlassDev> glass;
     std::vector<uint32_t> first;
     std::vector<Placed> placed;
     uint64_t total = 0;
@@ -121,6 +122,12 @@ static int flatten_world(rt3_ctx* c) {
                 memcpy(&mt, &c->scene.h_mat_tex[g], sizeof(mt));
                 mats.push_back(mt);
             }
+            if (any_glass(c)) {
+                static_assert(sizeof(rt3_transmission) == sizeof(GlassDev), "transmission layouts");
+                GlassDev gd;
+                memcpy(&gd, &c->scene.h_transmission[g], sizeof(gd));
+                glass.push_back(gd);
+            }
             first.push_back((uint32_t)total);
             placed.push_back({(uint32_t)i, g, (uint32_t)total, c->scene.h_prim_counts[g], identity});
             total += c->scene.h_prim_counts[g];
@@ -146,6 +153,12 @@ static int flatten_world(rt3_ctx* c) {
         HIPC(c, hipMemcpy(c->accel.d_mat_tex.get(), mats.data(), nf * sizeof(MatTexDev), hipMemcpyHostToDevice));
         c->accel.has_mat_tex = true;
         for (const MatTexDev& mt : mats) c->accel.has_normal_tex = c->accel.has_normal_tex || mt.normal_tex >= 0;
+    }
+    c->accel.has_glass = false;
+    if (!glass.empty()) {
+        if (int r = dev_alloc(c, c->accel.d_glass, nf)) return r;
+        HIPC(c, hipMemcpy(c->accel.d_glass.get(), glass.data(), nf * sizeof(GlassDev), hipMemcpyHostToDevice));
+        c->accel.has_glass = true;
     }
     c->accel.n_flat_geoms = (uint32_t)nf;
     c->accel.n_flat_prims = (uint32_t)total;

@@ -387,6 +387,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     if (e == hipSuccess) {
         if (op == 30) launch_selftest_light(c->stream, d_lights.get(), (uint32_t)c->scene.lights.size(), d_in.get(), n, d_out.get());
         else if (op == 31) launch_selftest_lens(c->stream, d_in.get(), n, d_out.get());
+        else if (op == 32) launch_selftest_glass(c->stream, d_in.get(), n, d_out.get());
         else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }

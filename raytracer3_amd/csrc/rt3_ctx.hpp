@@ -139,6 +139,8 @@ struct rt3_ctx {
         std::vector<float> h_cutoffs;
         // material textures per uploaded geometry (empty = none anywhere)
         std::vector<rt3_material_textures> h_mat_tex;
+        // transmission per uploaded geometry (empty = no glass anywhere)
+        std::vector<rt3_transmission> h_transmission;
         std::vector<rt3_instance> h_instances;   // empty = one identity instance of every geometry
         // the previous frame's instance matrices, n x 16 column-major (rt3_scene_set_prev_transforms; empty = every instance unmoved)
         std::vector<float> prev_transforms;
@@ -172,6 +174,8 @@ struct rt3_ctx {
         rt3::DevBuf<rt3::ShadeGeomDev> d_shade_geoms;      // the same table as hit_info reads it
         rt3::DevBuf<rt3::MatTexDev> d_mat_tex;             // per flattened geometry; has_mat_tex: the built scene names a material texture
         bool has_mat_tex = false, has_normal_tex = false;
+        rt3::DevBuf<rt3::GlassDev> d_glass;                // per flattened geometry; has_glass: the built scene has a transmission > 0
+        bool has_glass = false;
         rt3::DevBuf<uint32_t> d_prim_geom, d_first_prim;
         uint32_t n_flat_geoms = 0, n_flat_prims = 0;  // after flattening: what the acceleration structure and the shading records cover
         std::vector<rt3::Placed> placed;              // the same, on the host: n_flat_geoms entries
@@ -339,6 +343,7 @@ int revalidate_geometry(rt3_ctx* c);
 int deform_flags(rt3_ctx* c);
 inline bool any_cutoff(const rt3_ctx* c) { return !c->scene.h_cutoffs.empty(); }
 inline bool any_mat_tex(const rt3_ctx* c) { return !c->scene.h_mat_tex.empty(); }
+inline bool any_glass(const rt3_ctx* c) { return !c->scene.h_transmission.empty(); }
 
 // ---- rt3_accel.hip
 void invalidate_accel(rt3_ctx* c);  // the structure is not for the current scene any more: accel.built goes

@@ -1,0 +1,71 @@
+// rt3_glass.hpp -- transmissive dielectric surfaces (rt3_scene_set_transmission): the side table of k_shade_glass and
+// the one function a glass vertex evaluates.  No reference counterpart (every surface of the reference is DiffuseBrdf under GGX).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt3_math.hpp"
+
+namespace rt3 {
+
+// == rt3_transmission, per flattened geometry; the table exists only when some transmission is > 0
+struct GlassDev {
+    float transmission, ior;
+    uint32_t thin_walled, pad;
+};
+static_assert(sizeof(GlassDev) == 16, "Glass layout");
+
+// The pdf slot of a glass vertex's extension ray.  Both values are delta markers in the sense of rt3_lens.hip's header comment: k_shade's MIS
+// weights pdf_b / (pdf_b + p_light) are exactly 1 while p_light stays below half an ulp of the marker (2^103), under the same assumption
+// for an emitter seen edge-on.  kFloatMax is the camera's own marker and is handed on by a glass vertex that received it: "nothing but
+// glass since the camera", which lets an escaped ray show the sky without RT3_F_NEE_SKY, as k_lens_miss does for a camera ray.  A glass
+// vertex reached from an opaque one hands on kGlassDeltaPdf, the next float below.
+constexpr float kGlassDeltaPdf = 3.4028232635611926e38f;  // 0x7F7FFFFE
+// the first RNG index of the glass draws: 0x40000000 + 2 (s B + b) selects the lobe, + 1 the event
+constexpr uint32_t kGlassRngBase = 0x40000000u;
+
+struct GlassEvent {
+    uint32_t transmit;  // 0: mirror reflection about n, 1: transmission
+    V3 dir;             // unit up to rounding
+    float F;            // the reflection probability: exact Fresnel, or F' = 2 F / (1 + F) of a thin slab
+};
+// A smooth dielectric interface air <-> ior with shading normal n (not face-forwarded), met by a ray of direction d (any length); u picks
+// the event.  The ray enters when dot(n, d) < 0: eta = ior, else 1 / ior; thin-walled: eta = ior on both sides, the transmitted direction
+// is d's.  cos_t^2 <= 0 is total internal reflection.
+RT3_DEV GlassEvent glass_sample(float ior, bool thin, V3 d, V3 n, float u) {
+    const float dl = sqrtf(dot(d, d));
+    const V3 ud = v3(d.x / dl, d.y / dl, d.z / dl);
+    const float c = dot(n, ud);
+    const bool enter = c < 0.0f;
+    const float cos_i = fabsf(c);
+    const float eta = (thin || enter) ? ior : 1.0f / ior;
+    // cos_t^2 = 1 - (1 - cos_i^2) / eta^2, written without the cancellation of 1 - (1 - x): at eta = 1 it is cos_i^2 exactly, so an
+    // index-matched surface has cos_t = cos_i, F = 0 and hands the unit direction on unchanged
+    const float eta2 = eta * eta;
+    const float cos_t2 = (cos_i * cos_i + (eta2 - 1.0f)) / eta2;
+    float F = 1.0f, cos_t = 0.0f;
+    if (cos_t2 > 0.0f) {
+        cos_t = sqrtf(cos_t2);
+        const float rs = (cos_i - eta * cos_t) / (cos_i + eta * cos_t);
+        const float rp = (eta * cos_i - cos_t) / (eta * cos_i + cos_t);
+        F = 0.5f * (rs * rs + rp * rp);
+    }
+    if (thin) F = (2.0f * F) / (1.0f + F);
+    GlassEvent e;
+    e.F = F;
+    if (u < F) {
+        const float k = 2.0f * c;
+        e.transmit = 0u;
+        e.dir = v3(ud.x - k * n.x, ud.y - k * n.y, ud.z - k * n.z);
+    } else if (thin) {
+        e.transmit = 1u;
+        e.dir = ud;
+    } else {
+        const float k = cos_i / eta - cos_t, sg = enter ? k : -k;  // along n', the normal on the incoming side
+        e.transmit = 1u;
+        e.dir = v3(ud.x / eta + sg * n.x, ud.y / eta + sg * n.y, ud.z / eta + sg * n.z);
+    }
+    return e;
+}
+
+}  // namespace rt3

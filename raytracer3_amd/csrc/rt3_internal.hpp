@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rt3_camera.hpp"
+#include "rt3_glass.hpp"
 #include "rt3_math.hpp"
 #include "rt3_surface.hpp"
 
@@ -56,8 +57,13 @@ struct ShadeLaunch {
     FastDiv npix_div;        // path id = sample_in_batch * npix + pixel_index
     uint32_t s0;             // first sample index of this batch
     uint32_t bounce;         // b
-    // FIRST: gbuffer images
-    const uint4* gbuffer;
+    // FIRST: gbuffer images.  GLASS (k_shade_glass, rt3_scene_set_transmission): the side table per flattened geometry
+    // in the G-buffer's slot -- a glass frame never shades from the G-buffer (FIRST = false), and a member of its own would move the
+    // arguments behind it, the hidden ones included, in every kernel that takes this struct.  launch_shade fills it in.
+    union {
+        const uint4* gbuffer;
+        const GlassDev* glass;
+    };
     const float* depth;
     // !FIRST: input queue
     const float* in_rays;
@@ -102,7 +108,8 @@ inline unsigned grid_for(uint64_t n, unsigned block, unsigned max_blocks) {
 void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, float* rays, size_t stride);
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
-void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false);  // punct: L.lights holds punctual records
+// punct: L.lights holds punctual records; glass: the built scene's transmission table (null: none), never with `first`
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,
@@ -124,6 +131,9 @@ void launch_postprocess_lens(hipStream_t st, const uint32_t* pixels, uint32_t np
 // self-test op 31: lens_ray, kSelftestLensIn words in, kSelftestLensOut words out
 constexpr uint32_t kSelftestLensIn = 41, kSelftestLensOut = 10;
 void launch_selftest_lens(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 32: glass_sample, {ior, thin_walled, d xyz, n xyz, u} -> {event, direction xyz, F} (rt3_shade.hip)
+constexpr uint32_t kSelftestGlassIn = 9, kSelftestGlassOut = 5;
+void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
 void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst);
 void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img);
 

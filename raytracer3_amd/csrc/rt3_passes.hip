@@ -312,7 +312,8 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         L.sh2_rays = c->work.sh2_rays.get(); L.sh2_contrib = c->work.sh2_contrib.get(); L.sh2_tmax = c->work.sh2_tmax.get(); L.sh2_count = emit_cnt + bn;
         {
             ScopedTimer t(c, CAT_SHADE);
-            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct);
+            // (glass only with a lens: pass_reference_mode and pass_adaptive see to it)
+            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr);
         }
         cur ^= 1;
         if (nee) {
@@ -358,6 +359,13 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     if (c->lens.on && (uint64_t)Sspp * B * 8u > (1ull << 31))
         return fail(c, RT3_E_INVALID, "refrence_mode with a lens: samples * bounces * 8 may not exceed 2^31 (the camera's RNG indices start there)");
+    if (c->accel.has_glass) {
+        if (!c->lens.on)
+            return fail(c, RT3_E_STATE, "refrence_mode: the scene has glass (rt3_scene_set_transmission) and the packed G-buffer has no room for a material "
+                                        "class: start every sample from its own camera ray with rt3_camera_set_lens ({0, f, 0} is the per-sample pinhole)");
+        if ((uint64_t)Sspp * B * 8u > (1ull << 30))
+            return fail(c, RT3_E_INVALID, "refrence_mode with glass: samples * bounces * 8 may not exceed 2^30 (the glass draws' RNG indices start there)");
+    }
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     const uint32_t npix = pl->count;
@@ -399,6 +407,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     if (c->lens.on)
         return fail(c, RT3_E_STATE, "adaptive: not with a lens set (rt3_camera_set_lens): the pass selects pixels by G-buffer depth, which knows nothing "
                                     "of partly covered pixels; switch the lens off (NULL) or use refrence_mode");
+    if (c->accel.has_glass)
+        return fail(c, RT3_E_STATE, "adaptive: not for a scene with glass (rt3_scene_set_transmission): glass needs per-sample camera rays "
+                                    "(rt3_camera_set_lens), which this pass does not take; use refrence_mode");
     if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     PixelList* pl;

@@ -247,6 +247,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->scene.h_prim_counts.assign(prim_counts, prim_counts + n);
     c->scene.h_cutoffs.clear();  // every geometry opaque again
     c->scene.h_mat_tex.clear();  // and without material textures
+    c->scene.h_transmission.clear();  // and without glass
     c->scene.n_geoms = n;
     c->scene.max_tex_index = max_tex;
     c->scene.n_prims = (uint32_t)total;
@@ -280,6 +281,22 @@ int rt3_scene_set_material_textures(rt3_ctx* c, const rt3_material_textures* m, 
     if (std::any_of(m, m + n, [](const rt3_material_textures& e) { return e.metallic_roughness_texture >= 0 || e.normal_texture >= 0 || e.emissive_texture >= 0; }))
         c->scene.h_mat_tex.assign(m, m + n);  // (kept only when some geometry names a texture)
     invalidate_topology(c);  // the side table and the tangent records are made by a build
+    return RT3_OK;
+}
+// transmission of the geometries of the last rt3_scene_set_geometry; n = 0: no glass
+int rt3_scene_set_transmission(rt3_ctx* c, const rt3_transmission* t, uint32_t n) {
+    if (!c || (!t && n)) return fail(c, RT3_E_INVALID, "transmission NULL");
+    if (n != 0 && n != c->scene.n_geoms)
+        return fail(c, RT3_E_INVALID, "transmission: n must be 0 or the geometry count of rt3_scene_set_geometry (" + std::to_string(c->scene.n_geoms) + ")");
+    for (uint32_t i = 0; i < n; i++) {
+        if (!(t[i].transmission >= 0.0f && t[i].transmission <= 1.0f)) return fail(c, RT3_E_INVALID, "transmission " + std::to_string(i) + " is not in [0, 1]");
+        if (!(t[i].ior >= 1.0f && t[i].ior <= kFloatMax)) return fail(c, RT3_E_INVALID, "transmission: ior " + std::to_string(i) + " is not a finite value >= 1");
+        if (t[i].thin_walled > 1u) return fail(c, RT3_E_INVALID, "transmission: thin_walled " + std::to_string(i) + " is neither 0 nor 1");
+        if (t[i].reserved != 0u) return fail(c, RT3_E_INVALID, "transmission: reserved " + std::to_string(i) + " must be 0");
+    }
+    c->scene.h_transmission.clear();
+    if (std::any_of(t, t + n, [](const rt3_transmission& e) { return e.transmission > 0.0f; })) c->scene.h_transmission.assign(t, t + n);  // (kept only when some geometry is glass)
+    invalidate_topology(c);  // the side table is made by a build
     return RT3_OK;
 }
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same

@@ -6,6 +6,7 @@
 
 #include "rt3_bsdf.hpp"
 #include "rt3_camera.hpp"
+#include "rt3_glass.hpp"
 #include "rt3_internal.hpp"
 #include "rt3_math.hpp"
 #include "rt3_punctual.hpp"
@@ -120,15 +121,37 @@ constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
 // k_shade keep both their names and, being compiled from the same text with PUNCT = false, their instructions.
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
-    constexpr bool PUNCT = false;
+    constexpr bool PUNCT = false, GLASS = false;
 #include "rt3_shade_body.inc"
 }
 // Waves: at six (80 VGPRs) the light function costs the FIRST and GLDS twins more scratch than their EMIT instance has (108 against 96 bytes,
 // 124 against 120), so all five take the four-wave step that MAT took: 128 VGPRs, no scratch.
 template <bool FIRST, bool GLDS, bool MAT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
-    constexpr bool EMIT = true, PUNCT = true;
+    constexpr bool EMIT = true, PUNCT = true, GLASS = false;
 #include "rt3_shade_body.inc"
+}
+// GLASS: the built scene has the transmission side table (a.glass); a vertex on a geometry with transmission > 0 is,
+// with that probability, a smooth dielectric (rt3_glass.hpp) instead of the opaque surface.  Launched only for such scenes, which always
+// start from per-sample camera rays (FIRST = false).  Kernels of their own name, like the PUNCT twins, so that every other instance keeps
+// its name and its instructions.  Waves: the four-wave step of MAT and PUNCT (128 VGPRs); the table of registers and scratch per instance
+// is in DESIGN.md section 4n.
+template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_glass(ShadeLaunch a) {
+    constexpr bool FIRST = false, GLASS = true;
+#include "rt3_shade_body.inc"
+}
+// self-test op 32: {ior, thin_walled, d xyz, n xyz, u} -> {event (0 reflect / 1 transmit), direction xyz, F}
+__global__ void k_selftest_glass(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = in + kSelftestGlassIn * (size_t)i;
+    auto F = [](uint32_t u) { return __uint_as_float(u); };
+    const GlassEvent e = glass_sample(F(p[0]), p[1] != 0u, v3(F(p[2]), F(p[3]), F(p[4])), v3(F(p[5]), F(p[6]), F(p[7])), F(p[8]));
+    uint32_t* o = out + kSelftestGlassOut * (size_t)i;
+    o[0] = e.transmit;
+    o[1] = __float_as_uint(e.dir.x); o[2] = __float_as_uint(e.dir.y); o[3] = __float_as_uint(e.dir.z);
+    o[4] = __float_as_uint(e.F);
 }
 
 // refrence_mode.slang:59-65 : radiance = (sum over samples, in sample order) / S, then blend with PrevLight
@@ -188,16 +211,27 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punc
     else if (glds) by_mat(std::true_type{});
     else by_mat(std::false_type{});
 }
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct) {
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
     // emit: RT3_F_NEE_EMISSIVE with something to sample; mat: the built scene has material textures
     // punct: that table holds punctual lights (RT3_F_NEE_PUNCTUAL)
+    // glass: the built scene has the transmission table; twelve instances of k_shade_glass, GLDS x MAT x {no table, EMIT, EMIT + PUNCT}
     dispatch_shade(first, glds, a.lights.n != 0u, a.sc.mat_tex != nullptr, punct && a.lights.n != 0u, [&](auto f, auto g, auto e, auto m, auto p) {
+        if constexpr (!decltype(f)::value) {
+            if (glass != nullptr) {
+                a.glass = glass;  // (in the slot of the G-buffer, which these kernels do not read)
+                hipLaunchKernelGGL((k_shade_glass<decltype(g)::value, decltype(e)::value, decltype(m)::value, decltype(p)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+                return;
+            }
+        }
         if constexpr (decltype(p)::value) hipLaunchKernelGGL((k_shade_punct<decltype(f)::value, decltype(g)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
         else hipLaunchKernelGGL((k_shade<decltype(f)::value, decltype(g)::value, decltype(e)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
     });
+}
+void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out) {
+    hipLaunchKernelGGL(k_selftest_glass, dim3((n + 255) / 256), dim3(256), 0, st, in, n, out);
 }
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,

@@ -1,16 +1,20 @@
-// rt3_shade_body.inc -- the body of k_shade and k_shade_punct (rt3_shade.hip), which include it with FIRST, GLDS, EMIT, MAT and PUNCT in scope
-// and the launch argument `a`.
+// rt3_shade_body.inc -- the body of k_shade, k_shade_punct and k_shade_glass (rt3_shade.hip), which include it with FIRST, GLDS, EMIT, MAT, PUNCT
+// and GLASS in scope and the launch argument `a`.
     static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
     static_assert(EMIT || !PUNCT, "punctual lights are records of the emitter table");
+    static_assert(!(FIRST && GLASS), "the G-buffer has no room for a material class: glass frames start from camera rays");
     __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
     __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
     __shared__ MatTexDev s_mats[GLDS && MAT ? kShadeGeomsLds : 1];
+    __shared__ GlassDev s_glass[GLDS && GLASS ? kShadeGeomsLds : 1];  // (referenced by the GLASS kernels only)
     if (GLDS) {
         const uint32_t ng = a.sc.n_geoms < kShadeGeomsLds ? a.sc.n_geoms : kShadeGeomsLds;
         const uint32_t words = ng * (uint32_t)(sizeof(ShadeGeomDev) / 4);
         for (uint32_t k = threadIdx.x; k < words; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_geoms)[k] = reinterpret_cast<const uint32_t*>(a.sc.shade_geoms)[k];
         if constexpr (MAT)
             for (uint32_t k = threadIdx.x; k < ng * 4u; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_mats)[k] = reinterpret_cast<const uint32_t*>(a.sc.mat_tex)[k];
+        if constexpr (GLASS)
+            for (uint32_t k = threadIdx.x; k < ng * 4u; k += kShadeBlock) reinterpret_cast<uint32_t*>(s_glass)[k] = reinterpret_cast<const uint32_t*>(a.glass)[k];
         __syncthreads();
     }
     uint32_t parity = 0;
@@ -96,6 +100,18 @@
                     float4 lv = *Lp;
                     *Lp = make_float4(lv.x + T.x * (rad.x * w), lv.y + T.y * (rad.y * w), lv.z + T.z * (rad.z * w), 0.0f);
                 }
+                if constexpr (GLASS) {
+                    // without sky NEE an escaped ray adds nothing -- unless nothing but glass lies between it and the camera (the pdf slot
+                    // still holds the camera's marker): then the sky shows as it does beside the glass.  Bounce 0 is k_lens_miss's.
+                    if (!nee && b != 0u && pdf_b == kFloatMax && a.sc.sky != nullptr) {
+                        float su, sv;
+                        direction_to_equirect_uv(d, su, sv);
+                        const V3 rad = sky_eval(a.sc, su, sv);
+                        float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
+                        float4 lv = *Lp;
+                        *Lp = make_float4(lv.x + T.x * rad.x, lv.y + T.y * rad.y, lv.z + T.z * rad.z, 0.0f);
+                    }
+                }
                 active = false;
             } else {
                 t = hrec.x;
@@ -159,9 +175,20 @@
                 } else if (GLDS) surf = hit_finish(a.sc, s_geoms, hrecord, hbu, hbv);
                 else surf = hit_finish(a.sc, a.sc.shade_geoms, hrecord, hbu, hbv);
             }
+            // GLASS: is this a glass vertex?  The side-table entry is read here, ahead of the branch, beside hit_finish's own table reads; the
+            // draw at RNG index 0x40000000 + 2 (s B + b) selects the lobe with probability transmission (no draw at 1, no blue-noise shift).
+            // A glass vertex takes no light sample and no BSDF sample: everything below that is the opaque vertex's is skipped for it.
+            bool glass_v = false;
+            GlassDev gl = {0.0f, 1.0f, 0u, 0u};
+            if constexpr (GLASS) {
+                if (GLDS) gl = s_glass[hrecord.rec.w];
+                else gl = a.glass[hrecord.rec.w];
+                if (gl.transmission > 0.0f) glass_v = gl.transmission >= 1.0f || uniform_float(seed, kGlassRngBase + 2u * (sm * B + b)) < gl.transmission;
+            }
+            // (`GLASS && glass_v` is a constant in the kernels without glass, which so keep their instructions)
             V3 N = surf.normal;
             if ((flags & RT3_FLAG_FACEFORWARD) && dot(N, d) > 0.0f) N = neg(N);
-            if (nee) {
+            if (!(GLASS && glass_v) && nee) {
                 cosl = dot(N, wl);
                 if (cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
             }
@@ -172,7 +199,8 @@
             bool valid = true;
             Bsdf bs;
             const bool last = b == B - 1;  // the last vertex of a path emits no extension ray (:53): its BSDF sample is never used
-            if (spec) {  // layered diffuse + GGX (brdf.slang:141-311)
+            if (GLASS && glass_v) {  // (a smooth dielectric: glass_sample below)
+            } else if (spec) {  // layered diffuse + GGX (brdf.slang:141-311)
                 bs = bsdf_setup(surf.albedo, surf.roughness, surf.metalness);
                 wo = v3(-(d.x * b1.x + d.y * b1.y + d.z * b1.z), -(d.x * b2.x + d.y * b2.y + d.z * b2.z), -(d.x * N.x + d.y * N.y + d.z * N.z));
                 if (!last) {
@@ -207,7 +235,7 @@
                 *Lp = make_float4(lv.x + T.x * le.x, lv.y + T.y * le.y, lv.z + T.z * le.z, 0.0f);
             }
             if constexpr (PUNCT) {
-                if (nee_e && er0.w > 0.0f && is_punctual_record(er3)) {  // a delta light: no MIS weight, the BSDF never samples it; er0.w = p_sel
+                if (!(GLASS && glass_v) && nee_e && er0.w > 0.0f && is_punctual_record(er3)) {  // a delta light: no MIS weight, the BSDF never samples it; er0.w = p_sel
                     const PunctualSample ls = punctual_sample(er0, er1, er2, er3, o, N, kEmitShadowEnd);
                     if (ls.cs > 0.0f && ls.geo > 0.0f) {
                         V3 fv;
@@ -227,7 +255,7 @@
                     er0.w = 0.0f;  // not a triangle: the emitter sample below is skipped
                 }
             }
-            if (nee_e && er0.w > 0.0f) {  // the emitter sample: p = A + b1 E1 + b2 E2 with b0 = 1 - sqrt(u6), b1 = u7 sqrt(u6)
+            if (!(GLASS && glass_v) && nee_e && er0.w > 0.0f) {  // the emitter sample: p = A + b1 E1 + b2 E2 with b0 = 1 - sqrt(u6), b1 = u7 sqrt(u6)
                 const float su = sqrtf(eu6), lb1 = eu7 * su, lb2 = su - lb1;
                 const V3 pe = v3(er0.x + er1.x * lb1 + er2.x * lb2, er0.y + er1.y * lb1 + er2.y * lb2, er0.z + er1.z * lb1 + er2.z * lb2);
                 const V3 wv = pe - o;
@@ -271,7 +299,27 @@
                     emit_shadow = true;
                 }
             }
-            if (valid && !last) {  // an invalid specular sample (brdf.slang:227-229) ends the path
+            if (GLASS && glass_v) {
+                if constexpr (GLASS) {
+                    // the event draw at index + 1; the normal is hit_finish's, not face-forwarded.  The extension ray carries a delta marker
+                    // in its pdf slot (rt3_glass.hpp): whatever it finds counts with weight 1.  The last vertex sends the chosen direction
+                    // out as its sky shadow ray instead: the weight-1 light sample every other last vertex has.
+                    const GlassEvent ev = glass_sample(gl.ior, gl.thin_walled != 0u, d, surf.normal, uniform_float(seed, kGlassRngBase + 2u * (sm * B + b) + 1u));
+                    nd = ev.dir;
+                    if (ev.transmit) Tn = T * surf.albedo;  // the tint: base colour x base-colour texture
+                    if (!last) {
+                        pdf_n = pdf_b == kFloatMax ? kFloatMax : kGlassDeltaPdf;
+                        emit_ext = true;
+                    } else if (nee) {
+                        float su, sv;
+                        direction_to_equirect_uv(nd, su, sv);
+                        const V3 srad = sky_eval(a.sc, su, sv);
+                        wl = nd;
+                        contrib = v3(Tn.x * srad.x, Tn.y * srad.y, Tn.z * srad.z);
+                        emit_shadow = contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f;
+                    }
+                }
+            } else if (valid && !last) {  // an invalid specular sample (brdf.slang:227-229) ends the path
                 nd = basis_apply(b1, b2, N, wi);  // :48
                 pdf_n = pdf_s;
                 Tn = T * vop;                     // :51 value_over_pdf (= albedo for the diffuse BRDF)

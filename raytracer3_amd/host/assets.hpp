@@ -739,6 +739,8 @@ struct Material {  // assets/mod.rs:52-59 (+ emission, datatypes.slang:17)
     float alpha = 1.0f;         // baseColorFactor[3] -> rt3_geometry_info::base_color[3]
     // material textures: indices into Mesh::textures, -1 = none; glTF normalTexture.scale
     rt3_material_textures textures = {-1, -1, -1, 1.0f};
+    // glass: KHR_materials_transmission, _ior, _volume; without a volume (or with thicknessFactor 0) thin-walled
+    rt3_transmission transmission = {0.0f, 1.5f, 1u, 0u};
 };
 struct Mesh {
     std::vector<float> vertices;                // n x 8: position, normal, uv (Vertex, assets/mod.rs:127-133)
@@ -749,6 +751,7 @@ struct Mesh {
     std::vector<Image> textures;
     std::vector<float> alpha_cutoffs;           // one per geometry (rt3_scene_set_alpha_cutoffs), 0 = opaque
     std::vector<rt3_material_textures> material_textures;  // one per geometry (rt3_scene_set_material_textures)
+    std::vector<rt3_transmission> transmission;  // one per geometry (rt3_scene_set_transmission)
     std::vector<rt3_punctual_light> lights;     // KHR_lights_punctual, baked through their nodes (rt3_scene_set_lights)
     size_t n_vertices() const { return vertices.size() / 8; }
     size_t n_triangles() const {
@@ -1054,6 +1057,15 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                     mat.textures.emissive_texture = tex_index(gmtl.find("emissiveTexture"));
                     if (const Json* nt = gmtl.find("normalTexture"))
                         if (const Json* sc = nt->find("scale")) mat.textures.normal_scale = (float)sc->number(1.0);
+                    // glass: a transmission texture is ignored; no volume extension, or thicknessFactor 0, is thin-walled
+                    if (const Json* ext = gmtl.find("extensions")) {
+                        if (const Json* tr = ext->find("KHR_materials_transmission"))
+                            if (const Json* f = tr->find("transmissionFactor")) mat.transmission.transmission = (float)f->number(0.0);
+                        if (const Json* io = ext->find("KHR_materials_ior"))
+                            if (const Json* f = io->find("ior")) mat.transmission.ior = (float)f->number(1.5);
+                        if (const Json* vo = ext->find("KHR_materials_volume"))
+                            if (const Json* f = vo->find("thicknessFactor")) mat.transmission.thin_walled = f->number(0.0) > 0.0 ? 0u : 1u;
+                    }
                 }
                 rt3_geometry_info g{};
                 for (int k = 0; k < 3; k++) {
@@ -1076,6 +1088,7 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                 mesh_.prim_counts.push_back((uint32_t)(idx.size() / 3));
                 mesh_.alpha_cutoffs.push_back(mat.alpha_cutoff);
                 mesh_.material_textures.push_back(mat.textures);
+                mesh_.transmission.push_back(mat.transmission);
                 mesh_.names.push_back((gm.has("name") ? gm.at("name").str : std::string("mesh")) + "." + std::to_string(this_pi));
             }
         }
@@ -1533,6 +1546,10 @@ inline uint32_t upload(rt3_ctx* ctx, const Mesh& m) {
     for (const rt3_material_textures& t : m.material_textures) mapped = mapped || t.metallic_roughness_texture >= 0 || t.normal_texture >= 0 || t.emissive_texture >= 0;
     if (mapped)  // material textures; a scene without them makes no call
         check(ctx, rt3_scene_set_material_textures(ctx, m.material_textures.data(), (uint32_t)m.material_textures.size()), "rt3_scene_set_material_textures");
+    bool glass = false;
+    for (const rt3_transmission& t : m.transmission) glass = glass || t.transmission > 0.0f;
+    if (glass)  // glass; a scene without it makes no call
+        check(ctx, rt3_scene_set_transmission(ctx, m.transmission.data(), (uint32_t)m.transmission.size()), "rt3_scene_set_transmission");
     for (size_t i = 0; i < m.textures.size(); i++)
         check(ctx, rt3_scene_set_texture(ctx, (uint32_t)i, m.textures[i].rgba.data(), m.textures[i].w, m.textures[i].h), "rt3_scene_set_texture");
     if (!m.lights.empty())  // punctual lights; a scene without them makes no call

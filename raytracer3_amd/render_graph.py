@@ -176,6 +176,9 @@ class Context:
         mt = getattr(mesh, "material_textures", None)
         if mt is not None and len(mt) and any(np.any(mt[k] >= 0) for k in ("metallic_roughness_texture", "normal_texture", "emissive_texture")):
             self.set_material_textures(mt)  # material textures; scenes without them make no call
+        tr = getattr(mesh, "transmission", None)
+        if tr is not None and len(tr) and np.any(tr["transmission"] > 0):
+            self.set_transmission(tr)  # glass; scenes without it make no call
         lights = getattr(mesh, "lights", None)
         if lights is not None and len(lights):  # punctual lights; scenes without them make no call
             self.set_lights(lights)
@@ -195,6 +198,14 @@ class Context:
 
         t = np.ascontiguousarray(table, MATERIAL_TEXTURES_DTYPE).reshape(-1)
         self.check(self.lib.rt3_scene_set_material_textures(self.h, t.ctypes.data if len(t) else None, len(t)))
+
+    def set_transmission(self, table):
+        """per-geometry glass: transmission, index of refraction, thin-walled (assets.TRANSMISSION_DTYPE; [] = none);
+        rt3_scene_set_transmission, next build_accel().  A built scene with glass needs a lens for "refrence_mode" (set_lens)."""
+        from .assets import TRANSMISSION_DTYPE
+
+        t = np.ascontiguousarray(table, TRANSMISSION_DTYPE).reshape(-1)
+        self.check(self.lib.rt3_scene_set_transmission(self.h, t.ctypes.data if len(t) else None, len(t)))
 
     def set_instances(self, instances):
         """instances: [(geometry_first, geometry_count, 4x4 matrix as numpy, object -> world)] -- Instance + Transform of

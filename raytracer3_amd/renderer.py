@@ -213,13 +213,16 @@ class PathTracer:
         self._stage = None       # rehearsal path only: staging buffer of the host-moved gather
         self.host_group = None   # process group of the host-moved gather (None = the default group)
         self._history = _TemporalHistory(self.ctx)
+        self._glass_lens = False  # the lens in force is the pinhole set_scene switched on for a scene with glass
 
     def close(self):
         self.ctx.close()
 
     def set_scene(self, mesh, sky=None, bluenoise=None, *, instances=None, options=()):
         """Upload the world and build its acceleration structure once.  `options`: (L.OPT_*, value) pairs set first; `instances`: the list
-        set_instances() would take, placed before the build."""
+        set_instances() would take, placed before the build.  A mesh with glass (Mesh.transmission) needs per-sample camera rays: with no
+        lens on, set_lens(0, 1, 0) -- the per-sample pinhole -- is switched on, and off again by the next set_scene without glass.  A lens
+        the caller set stays."""
         for opt, value in options:
             self.ctx.set_option(opt, value)
         self.ctx.upload_mesh(mesh)  # (with the mesh's punctual lights, when it has some)
@@ -232,6 +235,14 @@ class PathTracer:
         if bluenoise is not None:
             self.ctx.set_bluenoise(bluenoise)
         self.ctx.build_accel()
+        tr = getattr(mesh, "transmission", None)
+        glass = tr is not None and len(tr) and bool(np.any(tr["transmission"] > 0))
+        if glass and not self.ctx.get_lens()[1]:
+            self.ctx.set_lens(L.LensParams(0.0, 1.0, 0.0))
+            self._glass_lens = True
+        elif not glass and self._glass_lens:
+            self.ctx.set_lens(None)
+            self._glass_lens = False
         self._history.scene_set()
         if instances is not None:
             self._history.instances_set(instances)
@@ -302,6 +313,7 @@ class PathTracer:
         box each sample's film point is drawn from (1 = antialiasing over the whole pixel), `aperture` the lens radius in world units
         (0 = pinhole), `focus` the view depth of the plane of focus.  set_lens(None) switches back to one primary hit per pixel.  With a
         lens, "postprocess" shows `Light` everywhere and adaptive frames are refused."""
+        self._glass_lens = False  # the caller's choice from here on
         if aperture is None:
             self.ctx.set_lens(None)
         else:

@@ -8,6 +8,7 @@
                     unit cubes and eight materials of the reference's processed asset `imported_assets/Default/box.glb`, placed
                     (the asset lost its node transforms and its emission) so that a render from CORNELL_REF_CAMERA lines up with
                     that image.  Informational: Cycles is not this estimator and the display transforms differ.
+* `glass_cornell()` the Cornell box with a solid glass sphere and a thin-walled tinted pane.
 * `sky(w, h)`       equirect RGB32F gradient sky + 0.5 degree sun disc (peak radiance 5e4).
 All surfaces carry normals facing the side they are meant to be seen from.
 """
@@ -382,6 +383,25 @@ def cutout_cornell() -> Mesh:
                 np.concatenate([mesh.prim_counts, cut.prim_counts]).astype(np.uint32), mesh.names + cut.names,
                 [np.ascontiguousarray(lattice), np.ascontiguousarray(leaf)],
                 np.concatenate([mesh.alpha_cutoffs, cut.alpha_cutoffs]).astype(np.float32))
+
+
+def glass_cornell() -> Mesh:
+    """The Cornell box with glass: a solid glass sphere (ior 1.5, a UV sphere with smooth normals) resting on the
+    short block and a thin-walled, green-tinted pane standing in front of the tall one.  Render it with a lens (PathTracer.set_scene
+    switches the per-sample pinhole on)."""
+    mesh = cornell()
+    mb = MeshBuilder()
+    _sphere(mb, "glass_sphere", [0.4, 0.9, 0.3], 0.3, 48, 24, Material((1.0, 1.0, 1.0), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=0))
+    mb.add("glass_pane", *_grid([-0.9, 0.0, 0.45], [0.75, 0.0, 0.3], [0.0, 1.4, 0.0], 1, 1),
+           Material((0.7, 0.95, 0.8), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=1))
+    add = mb.build()
+    g = add.geometries.copy()
+    g["index_offset"] += len(mesh.indices)
+    g["vertex_offset"] += len(mesh.vertices)
+    return Mesh(np.ascontiguousarray(np.concatenate([mesh.vertices, add.vertices]), np.float32),
+                np.ascontiguousarray(np.concatenate([mesh.indices, add.indices]), np.uint32), np.concatenate([mesh.geometries, g]),
+                np.concatenate([mesh.prim_counts, add.prim_counts]).astype(np.uint32), mesh.names + add.names,
+                transmission=np.concatenate([mesh.transmission, add.transmission]))
 
 
 MATERIAL_SEED = 20240607

@@ -34,7 +34,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -79,6 +79,8 @@ def main():
         mesh, cam_kw = scenes.lit_room(), scenes.CORNELL_CAMERA
     elif args.scene == "material_cornell":  # metallic-roughness, normal and emissive maps
         mesh, cam_kw = scenes.material_cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "glass_cornell":  # a solid glass sphere and a thin-walled pane; set_scene switches the pinhole lens on
+        mesh, cam_kw = scenes.glass_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "cornell_ref":
         mesh, cam_kw = scenes.cornell_ref(), scenes.CORNELL_REF_CAMERA
     else:
