@@ -632,6 +632,34 @@ typedef struct rt3_lens_params {
 } rt3_lens_params;
 int rt3_camera_set_lens(rt3_ctx *ctx, const rt3_lens_params *p);   /* NULL: off, the default */
 int rt3_camera_get_lens(rt3_ctx *ctx, rt3_lens_params *out, int *enabled);
+/* ---- Russian roulette on extension rays.  No reference counterpart; DESIGN.md section 4o.  By default every path that still has an extension
+ *      ray is traced and shaded for all GConst.bounces vertices.  With roulette set, "refrence_mode" and "adaptive" test the extension ray that
+ *      a path emitted at vertex b, for start_bounce <= b < bounces - 1, between the shading of vertex b and the trace that follows, in a
+ *      kernel of its own (k_roulette), which compacts the survivors into the free half of the queue pair:
+ *        m = max(T.r, T.g, T.b) of the ray's throughput (a NaN in any component makes m a NaN); !(m > 0) ends the path, no number is drawn;
+ *        q = min(1, max(m, min_survival)); q >= 1: the ray goes on unchanged, no number is drawn;
+ *        q_g = ceil(q 2^23) 2^-23 (the random numbers are multiples of 2^-23, so u < q <=> u < q_g and P(u < q_g) = q_g exactly);
+ *        u = the number at RNG index 0x60000000 + s * bounces + b of the pixel's stream (s: absolute sample index; seed as for the path's
+ *        vertices, no blue-noise shift); the ray goes on iff u < q_g, with throughput T / q_g (three IEEE divisions); its origin, direction,
+ *        pdf slot (the delta markers of lens and glass included) and path id keep their bits.
+ *      The estimator stays unbiased; its variance rises.  The decision depends on (pixel, frame, sample, vertex, T) alone, so a frame's bits
+ *      do not depend on RT3_OPT_BATCH_SPP, the tile partition or RT3_OPT_INSTANCE_MODE.  With start_bounce >= bounces - 1 nothing is tested
+ *      and the frame is the one without roulette, bit for bit.  Shadow rays and the probe passes are not tested.
+ *      A non-NULL call switches this on; NULL switches it off, the default.  The state lives in the context; nothing is rebuilt.
+ *      RT3_E_INVALID (nothing changed) for a min_survival that is not finite or outside [2^-7, 1], or reserved != 0.
+ *      While roulette is on, "refrence_mode" and "adaptive" with samples * bounces * 8 > 2^30 return RT3_E_INVALID (the vertices' RNG indices
+ *      would reach the roulette draws').  rt3_stats.extension_rays counts the rays traced: the survivors.
+ *      rt3_path_get_roulette (either pointer may be NULL): the parameters last set (the defaults {2, 0.0625, {0, 0}} before any) and whether on.
+ *      rt3_path_roulette_info (either pointer may be NULL; synchronises the stream): of the last "refrence_mode" or "adaptive" launch, the
+ *      extension rays tested and how many of them were ended; 0 and 0 after a launch without roulette. ---- */
+typedef struct rt3_roulette_params {
+    uint32_t start_bounce;  /* first vertex whose extension ray is tested; vertices 0 .. start_bounce-1 always continue */
+    float min_survival;     /* in [2^-7, 1]: floor of the survival probability, so a survivor's weight grows by at most 128 */
+    uint32_t reserved[2];   /* 0 */
+} rt3_roulette_params;
+int rt3_path_set_roulette(rt3_ctx *ctx, const rt3_roulette_params *p);  /* NULL: off, the default */
+int rt3_path_get_roulette(rt3_ctx *ctx, rt3_roulette_params *out, int *enabled);  /* defaults {2, 0.0625} before any call */
+int rt3_path_roulette_info(rt3_ctx *ctx, uint64_t *tested, uint64_t *ended);  /* of the last refrence_mode / adaptive launch; synchronises */
 
 /* timeline-semaphore wait of begin_frame (render_graph/mod.rs:656-665) -> hipStreamSynchronize */
 int rt3_frame_wait(rt3_ctx *ctx);
@@ -673,6 +701,13 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      point in view space xy: 10 words); reads no context state.
  *      32 the glass function of rt3_scene_set_transmission (ior, thin_walled as u32, d xyz, n xyz, u: 9 words -> event as u32 (0 reflect /
  *      1 transmit), direction xyz, reflection probability F: 5 words); reads no context state.
+ *      33 the roulette rule of rt3_path_set_roulette (T rgb, min_survival, u: 5 words -> survived as u32, T' rgb, q_g: 5 words; an ended row
+ *      has T' = 0, a row with !(m > 0) also q_g = 0; q_g = 1: T' = T and u is not read); reads no context state.
+ *      34 k_roulette itself on a caller-made queue of n records; reads no context state.  in: the header {frame, bounces, b, s0 (first sample
+ *      index), min_survival, npix >= 1, workgroups to launch (1 .. 65535)}, then npix pixel words x | y << 16, then n records of 11 words
+ *      {o xyz, pdf, d xyz, path id, T rgb}; path id = sample_in_batch * npix + pixel index.  out: {new count, tested, ended}, then n records:
+ *      the words the caller put there are the destination queue's contents before the launch, so on return the first `count` records are
+ *      the survivors and the words behind them are the caller's unless the kernel wrote out of place.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

@@ -32,6 +32,8 @@ SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of th
 SELFTEST_HIT_INFO = 29  # rt3_selftest_eval op: {flattened primitive (u32), bu, bv} -> Surface (11 words), hit_info of the built world
 SELFTEST_LENS = 31  # rt3_selftest_eval op: {proj_inverse, view_inverse, window, lens, px, py, frame, sample} (41 words) -> {o, d, film, lens point} (10)
 SELFTEST_GLASS = 32  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, u} (9 words) -> {event (u32), direction, F} (5), the glass function
+SELFTEST_ROULETTE = 33  # rt3_selftest_eval op: {T rgb, min_survival, u} (5 words) -> {survived (u32), T' rgb, q_g} (5), the roulette rule
+SELFTEST_ROULETTE_QUEUE = 34  # rt3_selftest_eval op: k_roulette on a caller-made queue (Context.selftest_roulette_queue)
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
@@ -49,6 +51,7 @@ EXPORTS = [
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
     "rt3_adaptive_set_params", "rt3_adaptive_info",
     "rt3_camera_set_lens", "rt3_camera_get_lens",
+    "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
@@ -115,6 +118,15 @@ class LensParams(C.Structure):
 
     def __init__(self, aperture_radius=0.0, focus_distance=1.0, pixel_jitter=1.0, reserved=0):
         super().__init__(aperture_radius, focus_distance, pixel_jitter, reserved)
+
+
+class RouletteParams(C.Structure):
+    """rt3_roulette_params: Russian roulette on extension rays.  The defaults are the library's."""
+
+    _fields_ = [("start_bounce", C.c_uint32), ("min_survival", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, start_bounce=2, min_survival=0.0625, reserved=(0, 0)):
+        super().__init__(start_bounce, min_survival, (C.c_uint32 * 2)(*reserved))
 
 
 assert C.sizeof(GConst) == 304
@@ -216,6 +228,9 @@ def load():
         "rt3_adaptive_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), pu32]),
         "rt3_camera_set_lens": (i32, [vp, C.POINTER(LensParams)]),
         "rt3_camera_get_lens": (i32, [vp, C.POINTER(LensParams), C.POINTER(i32)]),
+        "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),
+        "rt3_path_get_roulette": (i32, [vp, C.POINTER(RouletteParams), C.POINTER(i32)]),
+        "rt3_path_roulette_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),
         "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),

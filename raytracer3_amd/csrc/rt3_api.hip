@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rt3_ctx.hpp"
+#include "rt3_roulette.hpp"
 
 using namespace rt3;
 
@@ -55,7 +56,16 @@ int harvest(rt3_ctx* c) {  // stream must be idle
         HIPC(c, hipMemcpy(h.data(), c->work.d_counters.get(), (size_t)c->work.counters_next * 4, hipMemcpyDeviceToHost));
         for (auto& b : c->work.pending_counters) {
             for (uint32_t k = 0; k < b.n_pairs; k++) {
-                c->prof.stats.extension_rays += h[b.first + 2 * k];
+                uint32_t traced = h[b.first + 2 * k];
+                if (b.rr_first && k >= b.rr_lo && k + 1 < b.n_pairs) {  // k_extend traced k_roulette's survivors
+                    const uint32_t emitted = traced;
+                    traced = h[b.rr_first + k];
+                    if (b.launch == c->work.launch_serial) {
+                        c->work.roulette_tested += emitted;
+                        c->work.roulette_ended += emitted - traced;
+                    }
+                }
+                c->prof.stats.extension_rays += traced;
                 c->prof.stats.shadow_rays += h[b.first + 2 * k + 1];
             }
             for (uint32_t k = 0; k < b.n_emit; k++) c->prof.stats.shadow_rays += h[b.emit_first + k];
@@ -354,8 +364,69 @@ int rt3_trace_rays(rt3_ctx* c, const float* rays, uint32_t n, int any_hit, float
     return RT3_OK;
 }
 
+// Self-test op 34: k_roulette on a caller-made queue of n records.  in: {frame, B, b, s0, min_survival, npix, workgroups}, npix pixel words,
+// n records {o xyz, pdf, d xyz, path id, T rgb}.  out: {count, tested, ended}, then n records: the caller's words go into the destination
+// queue before the launch and come back after it, so the words behind the survivors show what the kernel left alone.
+static int selftest_roulette_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const uint32_t npix = in[5], groups = in[6];
+    if (in[1] == 0 || in[1] > 64 || npix == 0 || groups == 0 || groups > 65535 || n > (1u << 24))
+        return fail(c, RT3_E_INVALID, "selftest: roulette queue header: bounces 1..64, at least one pixel, 1..65535 workgroups, at most 2^24 records");
+    HIPC(c, hipSetDevice(c->device));
+    const size_t S = n ? n : 1;
+    // host SoA images of the two queues: rays {o, pdf} x S, {d, id} x S; T three planes of S
+    std::vector<uint32_t> rays[2], T[2];
+    const uint32_t* rec[2] = {in + kSelftestQueueHeader + npix, out + 3};
+    for (int q = 0; q < 2; q++) {
+        rays[q].assign(8 * S, 0u);
+        T[q].assign(3 * S, 0u);
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t* r = rec[q] + kSelftestQueueRecord * i;
+            memcpy(&rays[q][4 * i], r, 16);
+            memcpy(&rays[q][4 * (S + i)], r + 4, 16);
+            for (int k = 0; k < 3; k++) T[q][k * S + i] = r[8 + k];
+        }
+    }
+    DevBuf<float> d_rays[2], d_T[2];
+    DevBuf<uint32_t> d_pix, d_cnt;
+    for (int q = 0; q < 2; q++) {
+        HIPC(c, d_rays[q].alloc_bytes(8 * S * 4));
+        HIPC(c, d_T[q].alloc_bytes(3 * S * 4));
+        HIPC(c, hipMemcpy(d_rays[q].get(), rays[q].data(), 8 * S * 4, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(d_T[q].get(), T[q].data(), 3 * S * 4, hipMemcpyHostToDevice));
+    }
+    HIPC(c, d_pix.alloc_bytes((size_t)npix * 4));
+    HIPC(c, d_cnt.alloc_bytes(8));
+    HIPC(c, hipMemcpy(d_pix.get(), in + kSelftestQueueHeader, (size_t)npix * 4, hipMemcpyHostToDevice));
+    const uint32_t cnt[2] = {n, 0u};
+    HIPC(c, hipMemcpy(d_cnt.get(), cnt, 8, hipMemcpyHostToDevice));
+    RouletteLaunch a{};
+    a.in_rays = d_rays[0].get(); a.in_T = d_T[0].get(); a.in_count = d_cnt.get();
+    a.out_rays = d_rays[1].get(); a.out_T = d_T[1].get(); a.out_count = d_cnt.get() + 1;
+    a.stride = S; a.pixels = d_pix.get(); a.npix = npix;
+    a.frame = in[0]; a.bounces = in[1]; a.bounce = in[2]; a.s0 = in[3];
+    memcpy(&a.min_survival, &in[4], 4);
+    launch_roulette(c->stream, a, n, groups);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    uint32_t got[2];
+    HIPC(c, hipMemcpy(got, d_cnt.get(), 8, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(rays[1].data(), d_rays[1].get(), 8 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(T[1].data(), d_T[1].get(), 3 * S * 4, hipMemcpyDeviceToHost));
+    out[0] = got[1];
+    out[1] = n;
+    out[2] = n - got[1];
+    for (size_t i = 0; i < n; i++) {
+        uint32_t* r = out + 3 + kSelftestQueueRecord * i;
+        memcpy(r, &rays[1][4 * i], 16);
+        memcpy(r + 4, &rays[1][4 * (S + i)], 16);
+        for (int k = 0; k < 3; k++) r[8 + k] = T[1][k * S + i];
+    }
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 34 && c && in && out) return selftest_roulette_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));  // no rows of one width
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
     if ((op == 25 || op == 26) && !c->scene.d_sky) return fail(c, RT3_E_STATE, "selftest: the sky ops need a sky (rt3_scene_set_sky)");
     if (op == 29) {  // hit_info indexes the flattened world's tables: nothing is launched that would read outside them
@@ -388,6 +459,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
         if (op == 30) launch_selftest_light(c->stream, d_lights.get(), (uint32_t)c->scene.lights.size(), d_in.get(), n, d_out.get());
         else if (op == 31) launch_selftest_lens(c->stream, d_in.get(), n, d_out.get());
         else if (op == 32) launch_selftest_glass(c->stream, d_in.get(), n, d_out.get());
+        else if (op == 33) launch_selftest_roulette(c->stream, d_in.get(), n, d_out.get());
         else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }

@@ -58,6 +58,10 @@ struct Timed {
 struct CounterBlock {  // device counters of one refrence_mode launch, harvested lazily
     uint32_t first, n_pairs;  // n_pairs x {extension-queue size, shadow-queue size}: one 8-byte pair per bounce (k_shade bumps both with ONE 64-bit atomic)
     uint32_t emit_first = 0, n_emit = 0;  // RT3_F_NEE_EMISSIVE: n_emit emitter-shadow-queue sizes from emit_first (one per bounce)
+    // roulette: for bounces rr_lo .. n_pairs-2 the rays k_extend traced are k_roulette's survivors, whose count is word
+    // rr_first + bounce; rr_first = 0: no roulette in this batch.  `launch`: the pass launch the batch belongs to (Work::launch_serial)
+    uint32_t rr_first = 0, rr_lo = 0;
+    uint64_t launch = 0;
 };
 
 // RT3_OPT_INSTANCE_MODE 1: what a build keeps for the next one.  The bottom trees live in the combined arrays
@@ -216,6 +220,8 @@ struct rt3_ctx {
         rt3::DevBuf<unsigned long long> d_totals;  // counting mode: kTotWords words (TotalsWord)
         std::vector<rt3::CounterBlock> pending_counters;
         uint64_t primary_rays_pending = 0;
+        // roulette: records k_roulette read / ended in the pass launch numbered launch_serial (rt3_path_roulette_info)
+        uint64_t launch_serial = 0, roulette_tested = 0, roulette_ended = 0;
     } work;
 
     // rt3_tiles.hip: the tile partition and the frame-end gather
@@ -263,6 +269,11 @@ struct rt3_ctx {
         rt3_lens_params params = {0.0f, 1.0f, 1.0f, 0u};
         bool on = false;
     } lens;
+    // rt3_passes.hip: Russian roulette on extension rays (rt3_path_set_roulette): off by default
+    struct Roulette {
+        rt3_roulette_params params = {2u, 0.0625f, {0u, 0u}};
+        bool on = false;
+    } roulette;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot

@@ -134,6 +134,15 @@ void launch_selftest_lens(hipStream_t st, const uint32_t* in, uint32_t n, uint32
 // self-test op 32: glass_sample, {ior, thin_walled, d xyz, n xyz, u} -> {event, direction xyz, F} (rt3_shade.hip)
 constexpr uint32_t kSelftestGlassIn = 9, kSelftestGlassOut = 5;
 void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// Russian roulette on the extension queue (rt3_roulette.hip); rt3_roulette.hpp has the argument.  The grid is sized
+// for n_max records (an upper bound of *in_count), or is `groups` workgroups when that is not 0 (self-test op 34)
+struct RouletteLaunch;
+void launch_roulette(hipStream_t st, const RouletteLaunch& a, uint32_t n_max, uint32_t groups = 0);
+// self-test op 33: roulette_rule, {T rgb, min_survival, u} -> {survived, T' rgb, q_g}
+constexpr uint32_t kSelftestRouletteIn = 5, kSelftestRouletteOut = 5;
+void launch_selftest_roulette(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 34: k_roulette on a caller-made queue; header words, then the pixel words, then records of kSelftestQueueRecord words
+constexpr uint32_t kSelftestQueueHeader = 7, kSelftestQueueRecord = 11;
 void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst);
 void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img);
 

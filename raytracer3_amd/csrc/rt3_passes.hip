@@ -6,6 +6,8 @@
 // name selects a HIP kernel sequence instead of a SPIR-V pipeline.
 // Also owns rt3_ctx::lens: per-sample camera rays (rt3_camera_set_lens), which "refrence_mode", "postprocess" and
 // "adaptive" read.
+// Also owns rt3_ctx::roulette: Russian roulette on extension rays (rt3_path_set_roulette), which trace_batch applies
+// for "refrence_mode" and "adaptive".
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "rt3_ctx.hpp"
+#include "rt3_roulette.hpp"
 
 using namespace rt3;
 
@@ -225,6 +228,10 @@ struct PathSetup {
     bool nee = false, nee_e = false, punct = false;
     bool lens_on = false;  // every sample starts from its own camera ray (rt3_camera_set_lens), not from the G-buffer ...
     LensDev lens{};        // ... made by these parameters
+    // Russian roulette (rt3_path_set_roulette) on the extension rays of vertices rr_start .. B-2; off when no vertex is in that range
+    bool rr = false;
+    uint32_t rr_start = 0;
+    float rr_min = 1.0f;
 };
 // (B = g->bounces >= 1; the queues must exist before an emitter queue can be sized: call after ensure_work)
 int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
@@ -247,11 +254,23 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     }
     ps->nee_e = ps->lights.n != 0u;
     ps->sc = scene_dev(c);
+    ps->rr = c->roulette.on && c->roulette.params.start_bounce < B - 1u;
+    ps->rr_start = c->roulette.params.start_bounce;
+    ps->rr_min = c->roulette.params.min_survival;
     return RT3_OK;
 }
 LensDev lens_dev(const rt3_ctx* c) {
     const rt3_lens_params& p = c->lens.params;
     return LensDev{p.aperture_radius, p.focus_distance, p.pixel_jitter};
+}
+// A path-tracing launch begins: the roulette counts of rt3_path_roulette_info start again, and with roulette on the vertices' RNG indices may
+// not reach the roulette draws' (kRouletteRngBase)
+int roulette_begin(rt3_ctx* c, const char* pass, uint32_t samples, uint32_t bounces) {
+    if (c->roulette.on && (uint64_t)samples * bounces * 8u > (1ull << 30))
+        return fail(c, RT3_E_INVALID, std::string(pass) + " with roulette: samples * bounces * 8 may not exceed 2^30 (the roulette draws' RNG indices start behind it)");
+    c->work.launch_serial++;
+    c->work.roulette_tested = c->work.roulette_ended = 0;
+    return RT3_OK;
 }
 // One wavefront batch: samples s0 .. s0 + nsb - 1 of the npix listed pixels (path id = sample_in_batch * npix + index) through all B
 // bounces; each path's radiance ends up in c->work.lacc.  The loop body of "refrence_mode", and of a round of "adaptive".
@@ -265,7 +284,9 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     const uint32_t n_words = (nee_e ? 6 : 4) * B;
     uint32_t first;
     // (a lens frame: two words more, the camera queue's length and the ray-pool cursor of its k_extend launch)
-    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0), &first)) return r;
+    // (roulette: B words more, [b] the extension queue's length after k_roulette of bounce b)
+    const bool rr = ps.rr;
+    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0) + (rr ? B : 0), &first)) return r;
     first += first & 1u;  // 8-byte aligned pairs
     // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
     uint32_t* pairs = c->work.d_counters.get() + first;
@@ -273,10 +294,13 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     // with emitter NEE: [4B + b] emitter shadow rays emitted at bounce b, [5B + b] the ray-pool cursor of their k_shadow launch
     uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
     uint32_t* lens_cnt = c->work.d_counters.get() + first + n_words;  // [0] the camera queue's length, [1] its ray-pool cursor
-    c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u});
+    uint32_t* rr_cnt = lens_cnt + (lens ? 2 : 0);
+    c->work.pending_counters.push_back(
+        CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u, rr ? first + n_words + (lens ? 2u : 0u) : 0u, ps.rr_start, c->work.launch_serial});
     auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
     auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
     int cur = 0;
+    const uint32_t* live_cnt = lens ? lens_cnt : nullptr;  // the length of the queue the next k_shade reads
     if (lens) {
         // Vertex 0 of a lens frame: the camera rays become records of the extension queue rays[0], are traced as extension rays (payload:
         // the .w words carry pdf and id, so a camera ray starts at kRayTMin like every extension ray, not at 0 like the G-buffer's), and are
@@ -304,7 +328,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         L.g = ps.gd; L.sc = ps.sc; L.pixels = pixels; L.pixbn = pixbn; L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
         L.gbuffer = (const uint4*)gb->ptr; L.depth = (const float*)dp->ptr;
         L.in_rays = c->work.rays[cur].get(); L.in_hits = c->work.hits.get(); L.in_T = c->work.T[cur].get();
-        L.in_count = bn ? ext_cnt_at(bn - 1) : (lens ? lens_cnt : nullptr); L.n_first = n_first;
+        L.in_count = live_cnt; L.n_first = n_first;
         L.out_rays = c->work.rays[cur ^ 1].get(); L.out_T = c->work.T[cur ^ 1].get(); L.out_count = ext_cnt_at(bn);
         L.sh_rays = c->work.sh_rays.get(); L.sh_contrib = c->work.sh_contrib.get(); L.sh_count = sh_cnt_at(bn);
         L.lacc = c->work.lacc.get(); L.stride = S;
@@ -330,9 +354,22 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             ScopedTimer t(c, CAT_SHADOW);
             launch_shadow(c->stream, c->accel.bvh, tr);
         }
+        live_cnt = ext_cnt_at(bn);
+        if (rr && bn >= ps.rr_start && bn != B - 1) {
+            // k_shade has read the other half of the ping-pong pair: the survivors go there, and k_extend and the next k_shade read them
+            RouletteLaunch R{};
+            R.in_rays = c->work.rays[cur].get(); R.in_T = c->work.T[cur].get(); R.in_count = live_cnt;
+            R.out_rays = c->work.rays[cur ^ 1].get(); R.out_T = c->work.T[cur ^ 1].get(); R.out_count = rr_cnt + bn;
+            R.stride = S; R.pixels = pixels; R.npix = npix; R.s0 = s0; R.bounces = B; R.bounce = bn; R.frame = ps.gd.frame;
+            R.min_survival = ps.rr_min;
+            ScopedTimer t(c, CAT_OTHER);
+            launch_roulette(c->stream, R, n_first);
+            cur ^= 1;
+            live_cnt = rr_cnt + bn;
+        }
         if (bn != B - 1) {
             TraceLaunch tr = ctx_trace(c);
-            tr.rays = c->work.rays[cur].get(); tr.count_ptr = ext_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + bn;
+            tr.rays = c->work.rays[cur].get(); tr.count_ptr = live_cnt; tr.n = n_first; tr.work_counter = pool_cur + bn;
             tr.hits = c->work.hits.get(); tr.payload = true;
             ScopedTimer t(c, CAT_EXTEND);
             launch_extend(c->stream, c->accel.bvh, tr);
@@ -366,6 +403,7 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
         if ((uint64_t)Sspp * B * 8u > (1ull << 30))
             return fail(c, RT3_E_INVALID, "refrence_mode with glass: samples * bounces * 8 may not exceed 2^30 (the glass draws' RNG indices start there)");
     }
+    if (int r = roulette_begin(c, "refrence_mode", Sspp, B)) return r;
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     const uint32_t npix = pl->count;
@@ -412,6 +450,7 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
                                     "(rt3_camera_set_lens), which this pass does not take; use refrence_mode");
     if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
+    if (int r = roulette_begin(c, "adaptive", cap, B)) return r;
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     if (pl->count == 0) return RT3_OK;
@@ -833,6 +872,34 @@ int rt3_camera_set_lens(rt3_ctx* c, const rt3_lens_params* p) {
     if (p->reserved != 0u) return fail(c, RT3_E_INVALID, "lens params: reserved must be 0");
     c->lens.params = *p;
     c->lens.on = true;
+    return RT3_OK;
+}
+int rt3_path_set_roulette(rt3_ctx* c, const rt3_roulette_params* p) {
+    if (!c) return RT3_E_INVALID;
+    if (!p) {
+        c->roulette.on = false;
+        return RT3_OK;
+    }
+    if (!std::isfinite(p->min_survival)) return fail(c, RT3_E_INVALID, "roulette params: min_survival must be finite");
+    if (!(p->min_survival >= 0.0078125f && p->min_survival <= 1.0f)) return fail(c, RT3_E_INVALID, "roulette params: min_survival must lie in [2^-7, 1]");
+    if (p->reserved[0] != 0u || p->reserved[1] != 0u) return fail(c, RT3_E_INVALID, "roulette params: reserved must be 0");
+    c->roulette.params = *p;
+    c->roulette.on = true;
+    return RT3_OK;
+}
+int rt3_path_get_roulette(rt3_ctx* c, rt3_roulette_params* out, int* enabled) {
+    if (!c) return RT3_E_INVALID;
+    if (out) *out = c->roulette.params;
+    if (enabled) *enabled = c->roulette.on ? 1 : 0;
+    return RT3_OK;
+}
+int rt3_path_roulette_info(rt3_ctx* c, uint64_t* tested, uint64_t* ended) {
+    if (!c) return RT3_E_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = harvest(c)) return r;
+    if (tested) *tested = c->work.roulette_tested;
+    if (ended) *ended = c->work.roulette_ended;
     return RT3_OK;
 }
 int rt3_camera_get_lens(rt3_ctx* c, rt3_lens_params* out, int* enabled) {

@@ -405,6 +405,40 @@ class Context:
         self.check(self.lib.rt3_camera_get_lens(self.h, C.byref(p), C.byref(on)))
         return p, bool(on.value)
 
+    def set_roulette(self, params=None, **kw):
+        """Russian roulette on extension rays (rt3_path_set_roulette, DESIGN.md section 4o): an L.RouletteParams, or its fields as keywords;
+        nothing = off"""
+        if params is None and kw:
+            params = L.RouletteParams(**kw)
+        self.check(self.lib.rt3_path_set_roulette(self.h, C.byref(params) if params is not None else None))
+
+    def get_roulette(self):
+        """(L.RouletteParams last set, whether roulette is on) (rt3_path_get_roulette)"""
+        p, on = L.RouletteParams(), C.c_int()
+        self.check(self.lib.rt3_path_get_roulette(self.h, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def roulette_info(self):
+        """(extension rays tested, of them ended) of the last "refrence_mode" / "adaptive" launch (rt3_path_roulette_info); synchronises"""
+        t, e = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.rt3_path_roulette_info(self.h, C.byref(t), C.byref(e)))
+        return t.value, e.value
+
+    def selftest_roulette_queue(self, frame, bounces, bounce, s0, min_survival, pixels, records, groups, prefill=None):
+        """Self-test op 34: k_roulette on the queue `records` (n, 11) of 32-bit words {o xyz, pdf, d xyz, path id, T rgb}, launched with `groups`
+        workgroups over the pixel words `pixels`; `prefill` (n, 11): the destination queue's words before the launch (zeros without).
+        Returns (count, tested, ended, the destination queue (n, 11) uint32 afterwards)."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 11)
+        n = len(records)
+        head = np.array([frame, bounces, bounce, s0, np.float32(min_survival).view(np.uint32), len(pixels), groups], np.uint32)
+        inp = np.concatenate([head, pixels, records.reshape(-1)])
+        out = np.zeros(3 + 11 * n, np.uint32)
+        if prefill is not None:
+            out[3:] = np.ascontiguousarray(prefill).view(np.uint32).reshape(-1)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ROULETTE_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return int(out[0]), int(out[1]), int(out[2]), out[3:].reshape(n, 11)
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

@@ -319,6 +319,20 @@ class PathTracer:
         else:
             self.ctx.set_lens(L.LensParams(aperture, focus, jitter))
 
+    def set_roulette(self, start_bounce=2, min_survival=0.0625):
+        """Russian roulette for the frames that follow (ctx.set_roulette): the extension rays of vertices
+        `start_bounce` .. bounces - 2 survive with probability min(1, max(largest throughput component, `min_survival`)) and carry their
+        throughput divided by it.  Unbiased; noisier per sample, cheaper per sample at many bounces.  set_roulette(None) switches it off,
+        the default."""
+        if start_bounce is None:
+            self.ctx.set_roulette(None)
+        else:
+            self.ctx.set_roulette(L.RouletteParams(start_bounce, min_survival))
+
+    def roulette_info(self):
+        """(extension rays tested, of them ended) of the last frame's path-tracing launch"""
+        return self.ctx.roulette_info()
+
     def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
         """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
         denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""

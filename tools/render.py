@@ -57,6 +57,8 @@ def main():
     ap.add_argument("--focus", type=float, default=1.0, metavar="F", help="with --aperture: view depth of the plane of focus")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
+    ap.add_argument("--roulette", nargs="?", type=int, const=2, default=None, metavar="START",
+                    help="Russian roulette on the extension rays from vertex START on (default 2), survival floor 1/16 (DESIGN.md section 4o)")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
     ap.add_argument("--side-by-side", default=None, help="with --compare: write [render | reference] at the reference's size here")
     ap.add_argument("--report", default=None, help="with --compare: write the numbers and the scene parameters as JSON here")
@@ -99,6 +101,8 @@ def main():
         if args.adaptive is not None or args.temporal or args.denoise:
             ap.error("--aa / --aperture render plain frames: the adaptive pass refuses a lens, and the temporal and denoise passes are guided by the pinhole G-buffer")
         pt.set_lens(args.aperture, args.focus, 1.0)
+    if args.roulette is not None:
+        pt.set_roulette(args.roulette)
     adaptive = None
     if args.adaptive is not None:
         if args.temporal:
@@ -129,6 +133,9 @@ def main():
     Image.fromarray(img8).save(args.out)
     rays = st.extension_rays + st.shadow_rays
     print(f"{args.out}: {W}x{H} {args.temporal or args.passes} x {args.spp} spp, {rays / 1e6:.0f} Mrays in {dt:.2f} s ({rays / dt / 1e6:.0f} Mrays/s incl. host), mean radiance {light[..., :3].mean():.4f}")
+    if args.roulette is not None:  # of the last pass
+        tested, ended = pt.roulette_info()
+        print(f"roulette from vertex {args.roulette}: {ended / 1e6:.2f} M of {tested / 1e6:.2f} M tested extension rays ended")
     if adaptive is not None:  # of the last pass
         n = pt.sample_counts()
         rounds, paths, capped = pt.ctx.adaptive_info()
