@@ -170,6 +170,10 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
 #define RT3_OPT_SHADOW_EXIT_TABLE 15 /* k_shadow's exit table (single-level structures of the default node layout): 1 = a shadow ray first tries the leaf
                                      recorded for the cell where it leaves the scene box (default), 0 = off, 2 = on with pseudo-random valid entries (a test aid:
                                      no result depends on the table's contents).  Takes effect at once; see rt3_accel_exit_table_info */
+#define RT3_OPT_DEFER_SKY_LIGHT 16 /* sky next-event estimation of refrence_mode and adaptive: 1 = a light sample is evaluated (radiance texels, BSDF, weight)
+                                     only once its shadow ray came through unoccluded, in a kernel of its own (default); 0 = before the ray is
+                                     traced.  Same frame bit for bit.  Scenes with glass, punctual lights or material textures, and skies whose
+                                     smallest texel density is below 2^-100, take the path of 0 whatever the option says.  Takes effect at once */
 int rt3_set_option(rt3_ctx *ctx, int option, int64_t value);
 
 /* ---- scene upload: DynamicBuffer::push (vulkan/buffer.rs:406-420) into the world buffers of

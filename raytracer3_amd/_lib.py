@@ -26,6 +26,7 @@ OPT_WIDE_COLLAPSE, OPT_POOL_CHUNK, OPT_SAH_TOP, OPT_TRACE_BLOCKS = 8, 9, 11, 12
 OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the name stays for callers that still pass it)
 OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
 OPT_SHADOW_EXIT_TABLE = 15  # k_shadow's exit table: 0 = off, 1 = on (default), 2 = on with pseudo-random valid entries (a test aid)
+OPT_DEFER_SKY_LIGHT = 16  # sky NEE: 1 = light samples are evaluated after their shadow rays, for the unoccluded ones only (default), 0 = before
 DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
 TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass
@@ -138,7 +139,7 @@ def kernel_source_hash() -> str:
     import hashlib
 
     h = hashlib.sha256()
-    files = sorted((PKG / "csrc").glob("*.hip")) + sorted((PKG / "csrc").glob("*.hpp")) + [PKG / "csrc" / "Makefile", PKG.parent / "include" / "rt3.h"]
+    files = sorted((PKG / "csrc").glob("*.hip")) + sorted((PKG / "csrc").glob("*.hpp")) + sorted((PKG / "csrc").glob("*.inc")) + [PKG / "csrc" / "Makefile", PKG.parent / "include" / "rt3.h"]
     for f in files:
         h.update(f.name.encode())
         h.update(f.read_bytes())

@@ -204,6 +204,10 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
             if (value < 0 || value > 2) return fail(c, RT3_E_INVALID, "shadow exit table must be 0 (off), 1 (on) or 2 (on, scrambled entries)");
             c->opt.exit_table = (int)value;
             return exit_table_update(c);
+        case RT3_OPT_DEFER_SKY_LIGHT:
+            if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "defer sky light must be 0 (off) or 1 (on)");
+            c->opt.defer_sky_light = value != 0;
+            return RT3_OK;
         default: return fail(c, RT3_E_INVALID, "unknown option");
     }
 }

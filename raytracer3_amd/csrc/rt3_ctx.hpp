@@ -156,6 +156,7 @@ struct rt3_ctx {
         rt3::DevBuf<float> d_cdf_marg;
         rt3::DevBuf<uint32_t> d_sky_alias, d_guide_marg;
         uint32_t sky_w = 0, sky_h = 0, sky_wt = 0;
+        float sky_min_pdf = 0.0f;  // the smallest texel density rt3_scene_set_sky stored (what RT3_OPT_DEFER_SKY_LIGHT's cover asks of it)
         rt3::DevBuf<uint8_t> d_bn;
         uint32_t bn_w = 0, bn_h = 0;
         uint64_t bn_stamp = 0;  // bumped by every rt3_scene_set_bluenoise
@@ -294,6 +295,7 @@ struct rt3_ctx {
         uint32_t leaf_size = 2, node_width = 4, node_quant = 1, collapse = 2, sah_top = 1;
         int instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
         int exit_table = 1;     // RT3_OPT_SHADOW_EXIT_TABLE: 0 off, 1 on, 2 on with scrambled entries (a test aid)
+        bool defer_sky_light = true;  // RT3_OPT_DEFER_SKY_LIGHT
     } opt;
     // rt3_api.hip (harvest, rt3_stats_reset), the events through ScopedTimer; stats.accel_* are rt3_accel.hip's (a build's time and copies)
     struct Prof {

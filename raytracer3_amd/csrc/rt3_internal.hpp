@@ -109,7 +109,11 @@ void launch_raygen(hipStream_t st, const GConstDev& g, const uint32_t* pixels, u
 void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* hits,
                     size_t stride, void* gbuffer, float* depth);
 // punct: L.lights holds punctual records; glass: the built scene's transmission table (null: none), never with `first`
-void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr);
+// defer: k_shade_defer -- the sky shadow queue then holds plain ray records in sh_rays and, in sh_contrib, one plane
+// of `stride` words with each ray's vertex (its index in the input queue) and a second plane for k_shadow's occlusion words; launch_light
+// finishes the unoccluded light samples from them.  Only without material textures, punctual lights and glass.
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false);
+void launch_light(hipStream_t st, bool first, ShadeLaunch L);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,

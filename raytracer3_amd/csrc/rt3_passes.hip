@@ -226,6 +226,9 @@ struct PathSetup {
     SceneDev sc;
     LightsDev lights{};
     bool nee = false, nee_e = false, punct = false;
+    // RT3_OPT_DEFER_SKY_LIGHT: k_shade_defer, k_shadow in its reporting mode, k_light.  Only inside their cover: sky NEE
+    // on; no glass, punctual record or material table; every sky texel's density large enough that a sample's pdf cannot round to 0
+    bool defer = false;
     bool lens_on = false;  // every sample starts from its own camera ray (rt3_camera_set_lens), not from the G-buffer ...
     LensDev lens{};        // ... made by these parameters
     // Russian roulette (rt3_path_set_roulette) on the extension rays of vertices rr_start .. B-2; off when no vertex is in that range
@@ -233,6 +236,8 @@ struct PathSetup {
     uint32_t rr_start = 0;
     float rr_min = 1.0f;
 };
+// pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
+constexpr float kSkyDeferMinPdf = 0x1p-100f;
 // (B = g->bounces >= 1; the queues must exist before an emitter queue can be sized: call after ensure_work)
 int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     const uint32_t B = g->bounces;
@@ -254,6 +259,7 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     }
     ps->nee_e = ps->lights.n != 0u;
     ps->sc = scene_dev(c);
+    ps->defer = c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
     ps->rr = c->roulette.on && c->roulette.params.start_bounce < B - 1u;
     ps->rr_start = c->roulette.params.start_bounce;
     ps->rr_min = c->roulette.params.min_survival;
@@ -337,15 +343,25 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         {
             ScopedTimer t(c, CAT_SHADE);
             // (glass only with a lens: pass_reference_mode and pass_adaptive see to it)
-            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr);
+            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr, ps.defer);
         }
         cur ^= 1;
         if (nee) {
             TraceLaunch tr = ctx_trace(c);
             tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
-            tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
+            if (ps.defer) {  // report only, into the second plane of sh_contrib; the first holds the rays' vertices
+                tr.occluded = reinterpret_cast<uint32_t*>(c->work.sh_contrib.get()) + S;
+            } else {
+                tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
+            }
             ScopedTimer t(c, CAT_SHADOW);
             launch_shadow(c->stream, c->accel.bvh, tr);
+        }
+        if (ps.defer) {
+            // before the emitter launch (which adds into the same radiance slots after the sky's), before k_roulette (which overwrites the
+            // half of the ray pair k_shade_defer read) and before k_extend (which overwrites the hit queue)
+            ScopedTimer t(c, CAT_SHADE);
+            launch_light(c->stream, bn == 0 && !lens, L);
         }
         if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
             TraceLaunch tr = ctx_trace(c);

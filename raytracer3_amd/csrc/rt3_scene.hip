@@ -389,6 +389,11 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
         for (uint32_t x = 0; x < w; x++) pdf[(size_t)y * w + x] = (float)((double)pdf[(size_t)y * w + x] * rowp);
     }
     marg[h - 1] = 1.0f;
+    // Every density is positive: f = (lum + 1e-6) sin(theta_row) > 0 for every texel, so every row weight is above 0, and a realised column
+    // weight is at least 1/65536 (Q >= 1/65536 for the column itself).  RT3_OPT_DEFER_SKY_LIGHT rests on it -- a light sample's pdf is positive
+    // exactly when its sin(theta) is -- so the smallest stored value is kept, and path_setup checks it instead of assuming.
+    float min_pdf = pdf[0];
+    for (size_t i = 1; i < n; i++) min_pdf = std::min(min_pdf, pdf[i]);
     // guide table of the marginal CDF: guide[k] = first index with cdf > k / n, so a lookup of u (cell k = floor(u n)) starts inside
     // [guide[k-1], guide[k+1]].  Stored per cell as one word lo | hi << 16 (hi clamped to n-1): one load instead of two.
     std::vector<uint32_t> gmarg(h);
@@ -431,6 +436,7 @@ int rt3_scene_set_sky(rt3_ctx* c, const float* rgb, uint32_t w, uint32_t h) {
     c->scene.sky_w = w;
     c->scene.sky_h = h;
     c->scene.sky_wt = wt;
+    c->scene.sky_min_pdf = min_pdf;
     exit_counters_reset(c);  // the shadow rays follow the sky's importance: the exit table's success rate is measured afresh
     return RT3_OK;
 }

@@ -103,6 +103,48 @@ __device__ __forceinline__ BlockAppend3 block_append3(bool want_ext, bool want_s
 }
 // (kEmitShadowEnd, where an emitter's or a punctual light's shadow ray ends, is rt3_punctual.hpp's)
 
+// One trip of k_light's loop.  The workgroup looks at slots it .. of the deferred shadow queue, one per thread: slot j
+// holds, in the two planes of sh_contrib, the queue index of the vertex that sent ray j (k_shade_defer) and whether the ray was occluded
+// (k_shadow's reporting mode).  The indices of the unoccluded ones are packed into LDS behind the `held` ones earlier trips left there, in
+// slot order.  Once a workgroup's worth is packed -- or on the last trip, it >= n_round, which finds no slot and takes what is left -- every
+// thread gets one: `i`, with `active` saying whether there was one for it; the rest moves to the front.  Returns false when the workgroup
+// shades nothing this trip.  No atomics: the packing never leaves the workgroup.  Must be reached by all threads of the block, with `it`
+// of one trip either below n_round for all of them or not (n_round and the loop's stride are multiples of the block).
+__device__ __forceinline__ bool light_next(const ShadeLaunch& a, uint32_t it, uint32_t n, uint32_t n_round, uint32_t& held, uint32_t& i, bool& active) {
+    constexpr int kWaves = kShadeBlock / 64;
+    __shared__ uint32_t packed[2 * kShadeBlock];  // held < kShadeBlock before a trip adds at most kShadeBlock
+    __shared__ uint32_t wave_count[kWaves];
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.sh_contrib);
+    const uint32_t* occluded = src + a.stride;
+    bool keep = false;
+    uint32_t s = 0;
+    if (it < n) {
+        keep = occluded[it] == 0u;
+        s = src[it];
+    }
+    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_count[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; w++) {
+        const uint32_t c = wave_count[w];
+        before += (uint32_t)w < wave ? c : 0u;
+        total += c;
+    }
+    if (keep) packed[held + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = s;
+    held += total;
+    __syncthreads();  // (the next trip writes wave_count behind this barrier, and packed behind its own first one)
+    if (held < (uint32_t)kShadeBlock && !(it >= n_round && held != 0u)) return false;
+    const uint32_t take = held < (uint32_t)kShadeBlock ? held : (uint32_t)kShadeBlock;
+    active = threadIdx.x < take;
+    i = active ? packed[threadIdx.x] : 0u;
+    held -= take;
+    if (threadIdx.x < held) packed[threadIdx.x] = packed[kShadeBlock + threadIdx.x];  // thread t alone reads and writes packed[t] here
+    return true;
+}
+
 // refrence_mode.slang:28-57 for one bounce of every live path
 // GLDS: the flattened-geometry table (80-byte entries, at most kShadeGeomsLds of them) is staged in LDS, so that a hit's material and
 // normal matrix cost an LDS read behind the shading record instead of a second dependent global gather
@@ -121,14 +163,14 @@ constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
 // k_shade keep both their names and, being compiled from the same text with PUNCT = false, their instructions.
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
-    constexpr bool PUNCT = false, GLASS = false;
+    constexpr bool PUNCT = false, GLASS = false, DEFER = false, LIGHT = false;
 #include "rt3_shade_body.inc"
 }
 // Waves: at six (80 VGPRs) the light function costs the FIRST and GLDS twins more scratch than their EMIT instance has (108 against 96 bytes,
 // 124 against 120), so all five take the four-wave step that MAT took: 128 VGPRs, no scratch.
 template <bool FIRST, bool GLDS, bool MAT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
-    constexpr bool EMIT = true, PUNCT = true, GLASS = false;
+    constexpr bool EMIT = true, PUNCT = true, GLASS = false, DEFER = false, LIGHT = false;
 #include "rt3_shade_body.inc"
 }
 // GLASS: the built scene has the transmission side table (a.glass); a vertex on a geometry with transmission > 0 is,
@@ -138,7 +180,24 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 // is in DESIGN.md section 4n.
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_glass(ShadeLaunch a) {
-    constexpr bool FIRST = false, GLASS = true;
+    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false;
+#include "rt3_shade_body.inc"
+}
+// DEFER: k_shade<FIRST, GLDS, EMIT> with the sky light sample cut off behind its direction.  Four of five sky shadow
+// rays are occluded, and for those the radiance texels, the BSDF towards the light and the weight were thrown away; this kernel sends the
+// ray with the vertex's queue index instead, and k_light finishes the samples whose ray came through.  A kernel of its own name, so that
+// k_shade's instances keep their names and instructions.  Launched only for scenes without material textures, punctual lights and glass.
+template <bool FIRST, bool GLDS, bool EMIT>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer(ShadeLaunch a) {
+    constexpr bool MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
+#include "rt3_shade_body.inc"
+}
+// The second half of k_shade_defer's light samples, for the rays k_shadow reported as unoccluded: a.sh_count slots in a.sh_contrib (light_next),
+// the vertices behind them in the queues the k_shade_defer launch read, which nothing has overwritten yet.  The emitter table plays no part
+// (the emitter sample is k_shade_defer's), so one instance serves both of its EMIT twins.
+template <bool FIRST, bool GLDS>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_light(ShadeLaunch a) {
+    constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = false, LIGHT = true;
 #include "rt3_shade_body.inc"
 }
 // self-test op 32: {ior, thin_walled, d xyz, n xyz, u} -> {event (0 reflect / 1 transmit), direction xyz, F}
@@ -211,10 +270,17 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punc
     else if (glds) by_mat(std::true_type{});
     else by_mat(std::false_type{});
 }
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass) {
+// defer: the k_shade_defer instance (the caller has checked that the scene is inside its cover: shade_defer_covers)
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
+    if (defer) {
+        dispatch_shade(first, glds, a.lights.n != 0u, false, false, [&](auto f, auto g, auto e, auto, auto) {
+            hipLaunchKernelGGL((k_shade_defer<decltype(f)::value, decltype(g)::value, decltype(e)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+        });
+        return;
+    }
     // emit: RT3_F_NEE_EMISSIVE with something to sample; mat: the built scene has material textures
     // punct: that table holds punctual lights (RT3_F_NEE_PUNCTUAL)
     // glass: the built scene has the transmission table; twelve instances of k_shade_glass, GLDS x MAT x {no table, EMIT, EMIT + PUNCT}
@@ -228,6 +294,16 @@ void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const G
         }
         if constexpr (decltype(p)::value) hipLaunchKernelGGL((k_shade_punct<decltype(f)::value, decltype(g)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
         else hipLaunchKernelGGL((k_shade<decltype(f)::value, decltype(g)::value, decltype(e)::value, decltype(m)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
+    });
+}
+// k_light over the shadow queue of the k_shade_defer launch of the same arguments.  A workgroup takes several trips, so that the few
+// unoccluded slots of each add up to whole workgroups of vertices.
+void launch_light(hipStream_t st, bool first, ShadeLaunch a) {
+    a.npix_div = make_fastdiv(a.npix);
+    const unsigned grid = grid_for(a.n_first, kShadeBlock * 8, 8192);
+    const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
+    dispatch_shade(first, glds, false, false, false, [&](auto f, auto g, auto, auto, auto) {
+        hipLaunchKernelGGL((k_light<decltype(f)::value, decltype(g)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
     });
 }
 void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out) {

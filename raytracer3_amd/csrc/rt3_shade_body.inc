@@ -1,5 +1,10 @@
-// rt3_shade_body.inc -- the body of k_shade, k_shade_punct and k_shade_glass (rt3_shade.hip), which include it with FIRST, GLDS, EMIT, MAT, PUNCT
-// and GLASS in scope and the launch argument `a`.
+// rt3_shade_body.inc -- the body of k_shade, k_shade_punct, k_shade_glass, k_shade_defer and k_light (rt3_shade.hip), which include it with
+// FIRST, GLDS, EMIT, MAT, PUNCT, GLASS, DEFER and LIGHT in scope and the launch argument `a`.
+// DEFER (k_shade_defer, DESIGN.md section 4p): the sky light sample stops at its direction.  The shadow ray is a plain ray record plus the
+// index of the vertex in the queue it was read from; radiance, BSDF and weight wait for k_light, which evaluates them for the unoccluded
+// rays only.  LIGHT (k_light): the same text as that second half -- the loop visits the unoccluded slots of the shadow queue (light_next),
+// rebuilds each one's vertex from the inputs k_shade_defer read, and adds the contribution where k_shadow would have.
+    static_assert(!(DEFER && LIGHT) && !((DEFER || LIGHT) && (MAT || PUNCT || GLASS)), "deferral covers the plain opaque instances");
     static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
     static_assert(EMIT || !PUNCT, "punctual lights are records of the emitter table");
     static_assert(!(FIRST && GLASS), "the G-buffer has no room for a material class: glass frames start from camera rays");
@@ -38,10 +43,16 @@
     const bool bnz = (flags & RT3_FLAG_BLUENOISE) && a.sc.bluenoise != nullptr;
     const bool spec = (flags & RT3_FLAG_SPECULAR) != 0u;
     const size_t S = a.stride;
-    const uint32_t n = FIRST ? a.n_first : *a.in_count;
+    const uint32_t n = LIGHT ? *a.sh_count : FIRST ? a.n_first : *a.in_count;  // LIGHT: the slots of the shadow queue
     const uint32_t n_round = (n + (kShadeBlock - 1)) & ~(uint32_t)(kShadeBlock - 1);  // whole workgroups iterate: barriers inside
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += gridDim.x * blockDim.x) {
+    // (LIGHT: one more trip per workgroup, which shades what its earlier trips left packed in LDS)
+    uint32_t light_held = 0;  // LIGHT: the packed vertices waiting in LDS
+    for (uint32_t it = blockIdx.x * blockDim.x + threadIdx.x; it < n_round + (LIGHT ? gridDim.x * blockDim.x : 0u); it += gridDim.x * blockDim.x) {
+        uint32_t i = it;
         bool active = i < n;
+        if constexpr (LIGHT) {  // slot `it` of the shadow queue -> the queue index of a vertex whose ray was not occluded, or no vertex yet
+            if (!light_next(a, it, n, n_round, light_held, i, active)) continue;
+        }
         uint32_t pid = 0;
         V3 o = v3(0, 0, 0), d = v3(0, 0, 1), T = v3(1, 1, 1);
         float t = 0.0f, pdf_b = 0.0f;
@@ -73,7 +84,7 @@
             if (active) {
                 size_t pi = (size_t)py * a.width + px;
                 float d0 = a.depth[pi];
-                if (d0 == kBackgroundDepth) {  // :18-21
+                if (!LIGHT && d0 == kBackgroundDepth) {  // :18-21
                     reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                     active = false;
                 } else {
@@ -89,7 +100,7 @@
             pdf_b = ro.w;
             const float4 hrec = reinterpret_cast<const float4*>(a.in_hits)[i];
             uint32_t prim = __float_as_uint(hrec.w);
-            if (prim == kMiss) {  // :37-40 ; sky through MIS (north_star)
+            if (!LIGHT && prim == kMiss) {  // :37-40 ; sky through MIS (north_star)
                 if (nee && pdf_b > 0.0f) {
                     float su, sv;
                     direction_to_equirect_uv(d, su, sv);
@@ -155,7 +166,7 @@
             }
             // EMIT: an emitter and a point on it for vertices 0 .. B-2 (the emission vertex b + 1 would collect); dims 5, 6, 7, no blue-noise
             // shift.  The chain guide -> CDF -> record is issued here, beside the sky's, and used once the surface is known.
-            const bool nee_e = EMIT && b + 1u < B;
+            const bool nee_e = !LIGHT && EMIT && b + 1u < B;
             float4 er0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), er1 = er0, er2 = er0, er3 = er0;
             float eu6 = 0.0f, eu7 = 0.0f;
             if (nee_e) {
@@ -190,7 +201,7 @@
             if ((flags & RT3_FLAG_FACEFORWARD) && dot(N, d) > 0.0f) N = neg(N);
             if (!(GLASS && glass_v) && nee) {
                 cosl = dot(N, wl);
-                if (cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
+                if (!DEFER && cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
             }
             V3 b1, b2;
             build_orthonormal_basis(N, b1, b2);  // :44
@@ -198,7 +209,7 @@
             float pdf_s = 0.0f;
             bool valid = true;
             Bsdf bs;
-            const bool last = b == B - 1;  // the last vertex of a path emits no extension ray (:53): its BSDF sample is never used
+            const bool last = LIGHT || b == B - 1;  // the last vertex of a path emits no extension ray (:53): its BSDF sample is never used
             if (GLASS && glass_v) {  // (a smooth dielectric: glass_sample below)
             } else if (spec) {  // layered diffuse + GGX (brdf.slang:141-311)
                 bs = bsdf_setup(surf.albedo, surf.roughness, surf.metalness);
@@ -213,7 +224,8 @@
             }
             o = v3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);  // :47
             // :50 radiance += ray_color * emissive.  x + (+0) == x exactly, so non-emitters skip the read-modify-write.
-            if (FIRST) {  // L starts at 0 and T = 1: 0 + 1 * e == e
+            if (LIGHT) {  // (k_shade_defer added the emission)
+            } else if (FIRST) {  // L starts at 0 and T = 1: 0 + 1 * e == e
                 reinterpret_cast<float4*>(a.lacc)[pid] = make_float4(T.x * surf.emissive.x, T.y * surf.emissive.y, T.z * surf.emissive.z, 0.0f);
             } else if (surf.emissive.x != 0.0f || surf.emissive.y != 0.0f || surf.emissive.z != 0.0f) {
                 V3 le = surf.emissive;
@@ -282,7 +294,9 @@
                 }
             }
             if (nee) {
-                if (cosl > 0.0f && pl > 0.0f) {
+                // DEFER: pl > 0 exactly when sin_theta > 0, because every texel's density is positive (rt3_scene_set_sky checks it)
+                if (DEFER) emit_shadow = cosl > 0.0f && pick.sin_theta > 0.0f;
+                else if (cosl > 0.0f && pl > 0.0f) {
                     V3 fv;
                     float scale;
                     if (spec) {  // evaluate the layered BSDF towards the light; f cos / (p_light + p_bsdf)
@@ -326,6 +340,14 @@
                 emit_ext = true;                  // :53
             }
         }
+        if constexpr (LIGHT) {  // k_shadow's expression; one shadow ray per path and launch, so nobody else adds to this slot
+            if (emit_shadow) {
+                float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
+                float4 v = *Lp;
+                *Lp = make_float4(v.x + contrib.x, v.y + contrib.y, v.z + contrib.z, 0.0f);
+            }
+            continue;
+        }
         BlockAppend slot;
         uint32_t slot_e = 0;
         if (EMIT) {
@@ -343,7 +365,12 @@
             reinterpret_cast<float2*>(a.sh2_contrib)[slot_e] = make_float2(contrib_e.z, __uint_as_float(pid));
             a.sh2_tmax[slot_e] = tmax_e;
         }
-        if (emit_shadow) {
+        if (DEFER && emit_shadow) {  // 36 bytes: the plain ray record k_shadow's reporting mode reads, and the vertex's place in the input queue
+            const uint32_t j = slot.sh;
+            reinterpret_cast<float4*>(a.sh_rays)[j] = make_float4(o.x, o.y, o.z, kRayTMin);
+            reinterpret_cast<float4*>(a.sh_rays)[S + j] = make_float4(wl.x, wl.y, wl.z, kBackgroundDepth);
+            reinterpret_cast<uint32_t*>(a.sh_contrib)[j] = i;
+        } else if (emit_shadow) {
             const uint32_t j = slot.sh;
             // 40 bytes per shadow ray: its range is always (kRayTMin, kBackgroundDepth), so the .w of the two ray records carry the
             // red and green contribution; blue and the path id follow in an 8-byte record
