@@ -254,7 +254,8 @@ int rt3_scene_set_material_textures(rt3_ctx *ctx, const rt3_material_textures *m
  *       - Without RT3_F_NEE_SKY a ray that escapes after nothing but glass vertices since the camera adds throughput x the sky's bilinear
  *         radiance, as an escaped camera ray of a lens frame does; after any other vertex it adds nothing, as without glass.
  *       - Shadow rays are unchanged: glass occludes them.  Light through glass arrives by BSDF-sampled paths only (unbiased for emitters
- *         and the sky); punctual lights do not shine through glass.  Alpha cutoffs work independently on the same geometry.
+ *         and the sky); punctual lights do not shine through glass.  (rt3_scene_set_pane_shadows, below, changes this for thin-walled
+ *         panes.)  Alpha cutoffs work independently on the same geometry.
  *       - The packed G-buffer has no room for a material class: in a built scene with glass "refrence_mode" needs per-sample camera rays
  *         (rt3_camera_set_lens; {0, f, 0} is the per-sample pinhole) and returns RT3_E_STATE without, as does "adaptive" always; with
  *         samples * bounces * 8 > 2^30 it returns RT3_E_INVALID (the vertices' RNG indices would reach the glass draws').  "gbuffer",
@@ -269,6 +270,26 @@ typedef struct rt3_transmission {
     uint32_t reserved;     /* 0 */
 } rt3_transmission;        /* 16 bytes */
 int rt3_scene_set_transmission(rt3_ctx *ctx, const rt3_transmission *t, uint32_t n);
+/* ---- pane shadows: light sampling through thin-walled glass.  No reference counterpart.  DESIGN.md section 4q.  A mode of the context, off
+ *      by default, that survives rt3_scene_set_geometry.  A pane is a geometry with transmission > 0 that is thin_walled and names no
+ *      normal texture; rt3_accel_build classifies.  With the mode on, in a built scene with at least one pane:
+ *       - the shadow rays of "refrence_mode" (sky, last-vertex sky, emitter and punctual) are not occluded by a pane triangle they meet inside
+ *         their range (after its alpha cutout test, if it has one); their contribution is multiplied by
+ *         A = transmission (1 - F'(cos_i)) tint per crossing, cos_i = |n.d| / |d| with the interpolated shading normal n, F' = 2 F / (1 + F)
+ *         at eta = ior, tint = base colour x base-colour texture: the expectation of what a glass vertex there does to a straight path;
+ *       - a glass vertex on a pane that transmits hands the incoming pdf slot on unchanged (no delta marker), so that what the ray finds
+ *         is weighted against the light samples of the vertex that chose the direction, with the emitter density taken over the whole
+ *         distance back to that vertex; at the last vertex its sky ray carries that weight.  Reflection keeps the delta marker.
+ *      Solid glass, and a thin-walled geometry with a normal texture, occlude as before.  "gbuffer", the probe passes and rt3_trace_rays
+ *      see glass as opaque, as before.  A ray within the 2^-20 barycentric band of an edge shared by two pane triangles is attenuated twice.
+ *      on other than 0 or 1 is RT3_E_INVALID and changes nothing.  A change takes effect at the next rt3_accel_build; until then an existing
+ *      structure is unusable, as after rt3_scene_set_alpha_cutoffs; rt3_accel_refit keeps it.  With the mode on and a pane, rt3_accel_build
+ *      needs the default node layout (either instance mode) and rt3_accel_import is refused: RT3_E_UNSUPPORTED.  With the mode on and no
+ *      pane nothing differs from off.  rt3_pane_shadow_info: the flattened geometries with triangles that the built structure holds as
+ *      panes, 0 while the mode is off; RT3_E_STATE before a build. ---- */
+int rt3_scene_set_pane_shadows(rt3_ctx *ctx, int on);
+int rt3_scene_get_pane_shadows(rt3_ctx *ctx, int *on);
+int rt3_pane_shadow_info(rt3_ctx *ctx, uint32_t *n_panes);
 
 /* ---- instances: the reference's world is a list of placed meshes (add_instance / loaded_assets, world/mod.rs:50-101) under a
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info

@@ -42,6 +42,7 @@ EXPORTS = [
     "rt3_scene_set_alpha_cutoffs",
     "rt3_scene_set_material_textures",
     "rt3_scene_set_transmission",
+    "rt3_scene_set_pane_shadows", "rt3_scene_get_pane_shadows", "rt3_pane_shadow_info",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_exit_table_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
@@ -187,6 +188,9 @@ def load():
         "rt3_scene_set_alpha_cutoffs": (i32, [vp, vp, u32]),
         "rt3_scene_set_material_textures": (i32, [vp, vp, u32]),
         "rt3_scene_set_transmission": (i32, [vp, vp, u32]),
+        "rt3_scene_set_pane_shadows": (i32, [vp, i32]),
+        "rt3_scene_get_pane_shadows": (i32, [vp, C.POINTER(i32)]),
+        "rt3_pane_shadow_info": (i32, [vp, C.POINTER(u32)]),
         "rt3_scene_set_instances": (i32, [vp, vp, u32]),
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),

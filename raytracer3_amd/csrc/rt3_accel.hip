@@ -75,6 +75,8 @@ AlphaDev alpha_dev(const rt3_ctx* c) {
     return a;
 }
 
+PaneDev pane_dev(const rt3_ctx* c) { return PaneDev{scene_dev(c), c->accel.d_glass.get(), c->accel.pane_first_slot}; }
+
 }  // namespace rt3
 
 // the geometry tables of a bottom tree: the world's vertices and indices, read through the tree's own tables
@@ -126,6 +128,7 @@ static int flatten_world(rt3_ctx* c) {
                 static_assert(sizeof(rt3_transmission) == sizeof(GlassDev), "transmission layouts");
                 GlassDev gd;
                 memcpy(&gd, &c->scene.h_transmission[g], sizeof(gd));
+                if (pane_geometry(c, g)) gd.pad = kGlassPaneBit;  // (the reserved word is 0 as uploaded)
                 glass.push_back(gd);
             }
             first.push_back((uint32_t)total);
@@ -319,7 +322,7 @@ static int tl_build_mesh(rt3_ctx* c, TlMesh& m, LbvhResult* res) {
     hipError_t e = make_mesh_tables(c, m, &t);
     if (e == hipSuccess)
         e = lbvh_build(c->stream, mesh_tables(c, t), m.n_tris, c->opt.leaf_size, 4, 1, c->opt.collapse, c->opt.sah_top, c->accel.build_scratch, res,
-                       c->accel.masked ? c->accel.d_geom_mask.get() : nullptr);
+                       c->accel.marked ? c->accel.d_geom_mask.get() : nullptr);
     uint32_t root[16];
     if (e == hipSuccess) e = hipMemcpyAsync(root, res->nodes.get(), 64, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -603,12 +606,23 @@ static int build_two_level(rt3_ctx* c) {
 // The alpha-mask tables of a build: per uploaded geometry the triangle records' last two words {cutoff bits, slot} and
 // per masked geometry (slot) {texture index, base_color[3] bits}.  c->accel.masked: some placed geometry with triangles is masked.
 static int make_alpha_tables(rt3_ctx* c) {
-    c->accel.masked = false;
-    if (!any_cutoff(c)) return RT3_OK;
-    if (c->opt.node_width != 4 || c->opt.node_quant != 1)
-        return fail(c, RT3_E_UNSUPPORTED, "alpha-masked geometry needs the default node layout (RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1)");
+    c->accel.masked = c->accel.marked = false;
+    c->accel.n_panes = c->accel.pane_first_slot = 0;
+    // pane shadows: with the mode off, or without a placed pane, everything below is what it is without the mode
+    std::vector<uint8_t> pane(c->scene.n_geoms, 0);
+    for (const Placed& p : c->accel.placed)
+        if (p.n_prims > 0 && pane_geometry(c, p.geom)) {
+            pane[p.geom] = 1;
+            c->accel.n_panes++;
+        }
+    if (!any_cutoff(c) && c->accel.n_panes == 0) return RT3_OK;
+    if (c->opt.node_width != 4 || c->opt.node_quant != 1) {
+        c->accel.n_panes = 0;
+        return fail(c, RT3_E_UNSUPPORTED, any_cutoff(c) ? "alpha-masked geometry needs the default node layout (RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1)"
+                                                         : "pane shadows (rt3_scene_set_pane_shadows) need the default node layout (RT3_OPT_NODE_WIDTH 4, RT3_OPT_NODE_QUANT 1)");
+    }
     std::vector<uint2> mask(c->scene.n_geoms, make_uint2(0u, 0u)), table;
-    for (uint32_t g = 0; g < c->scene.n_geoms; g++) {
+    for (uint32_t g = 0; any_cutoff(c) && g < c->scene.n_geoms; g++) {
         if (!(c->scene.h_cutoffs[g] > 0.0f)) continue;
         uint32_t cb, ab;
         memcpy(&cb, &c->scene.h_cutoffs[g], 4);
@@ -618,10 +632,23 @@ static int make_alpha_tables(rt3_ctx* c) {
     }
     for (const Placed& p : c->accel.placed)
         if (mask[p.geom].x != 0u && p.n_prims > 0) c->accel.masked = true;
+    // a pane's records: {0, 1} without a mask; with one {cutoff, a slot at or behind pane_first_slot that holds a copy of the geometry's entry},
+    // which the MASK kernels read like any slot.  The words of every other record keep their bits.
+    c->accel.pane_first_slot = (uint32_t)table.size();
+    for (uint32_t g = 0; g < c->scene.n_geoms; g++) {
+        if (!pane[g]) continue;
+        if (mask[g].x != 0u) {
+            table.push_back(table[mask[g].y]);
+            mask[g].y = (uint32_t)table.size() - 1u;
+        } else {
+            mask[g] = make_uint2(0u, 1u);
+        }
+    }
+    c->accel.marked = c->accel.masked || c->accel.n_panes != 0;
     if (int r = dev_alloc(c, c->accel.d_geom_mask, mask.size())) return r;
     if (int r = dev_alloc(c, c->accel.d_alpha, table.size())) return r;
     HIPC(c, hipMemcpy(c->accel.d_geom_mask.get(), mask.data(), mask.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->accel.d_alpha.get(), table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    if (!table.empty()) HIPC(c, hipMemcpy(c->accel.d_alpha.get(), table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice));
     return RT3_OK;
 }
 // ---- k_shadow's exit table (DESIGN.md sections 5 and 7; rt3_exit_table.hip).  Single-level structures of the default layout have room for it
@@ -710,7 +737,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     } else {
         free_accel(c);  // the old tree (two-level or not) goes before the new one is allocated
         hipError_t e = lbvh_build(c->stream, world_tables(c), c->accel.n_flat_prims, c->opt.leaf_size, c->opt.node_width, c->opt.node_quant, c->opt.collapse,
-                                  c->opt.sah_top, c->accel.build_scratch, &c->accel.bvh, c->accel.masked ? c->accel.d_geom_mask.get() : nullptr, exit_R(c));
+                                  c->opt.sah_top, c->accel.build_scratch, &c->accel.bvh, c->accel.marked ? c->accel.d_geom_mask.get() : nullptr, exit_R(c));
         if (c->accel.build_scratch.capacity_bytes() > ((size_t)1 << 30)) c->accel.build_scratch.reset();  // a big scene's scratch is not worth keeping resident
         if (e != hipSuccess) {
             const uint64_t need = c->accel.bvh.arena_need;
@@ -728,6 +755,11 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     }
     if (int r = accel_finish(c, out_handle)) return r;
     c->prof.stats.accel_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+    return RT3_OK;
+}
+int rt3_pane_shadow_info(rt3_ctx* c, uint32_t* n_panes) {
+    if (!c || !c->accel.built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    if (n_panes) *n_panes = c->accel.n_panes;
     return RT3_OK;
 }
 int rt3_accel_info(rt3_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* max_depth, uint32_t* node_bytes) {
@@ -773,6 +805,7 @@ int rt3_accel_import(rt3_ctx* c, const void* nodes, size_t nodes_bytes, const vo
     if (c->accel.bvh.layout == kLayoutTwoLevel) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for the two-level structure (RT3_OPT_INSTANCE_MODE 1)");
     if (c->accel.bvh.layout != kLayoutWide64Q) return fail(c, RT3_E_UNSUPPORTED, "accel_import: default node layout only");
     if (any_cutoff(c)) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for a scene with alpha-masked geometry (rt3_scene_set_alpha_cutoffs)");
+    if (c->accel.n_panes) return fail(c, RT3_E_UNSUPPORTED, "accel_import: not for a structure with panes (rt3_scene_set_pane_shadows): imported records carry no pane marks");
     if (nodes_bytes == 0 || nodes_bytes % 64 || tris_bytes % 48 || nodes_bytes / 64 > 0x3FFFFFFFull) return fail(c, RT3_E_INVALID, "accel_import: sizes must be multiples of 64 / 48 bytes");
     const uint32_t nn = (uint32_t)(nodes_bytes / 64), nt = (uint32_t)(tris_bytes / 48);
     const uint32_t* w = static_cast<const uint32_t*>(nodes);

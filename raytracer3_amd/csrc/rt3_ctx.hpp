@@ -189,6 +189,10 @@ struct rt3_ctx {
         // geometry {texture index, base_color[3] bits}
         rt3::DevBuf<uint2> d_geom_mask, d_alpha;
         bool masked = false;  // the structure holds masked triangles: traversal launches run the MASK kernels
+        // pane shadows: flattened geometries with triangles that the last rt3_accel_build classified as panes (0 while
+        // the mode is off) and the first alpha slot of the masked ones' marked records.  marked: the records carry mask or pane words
+        uint32_t n_panes = 0, pane_first_slot = 0;
+        bool marked = false;
         rt3::LbvhResult bvh;
         rt3::ShadeRecords shade;
         rt3::DevBuf<char> build_scratch;  // grow-only: lbvh_build's scratch, kept from build to build
@@ -216,6 +220,8 @@ struct rt3_ctx {
         rt3::DevBuf<float> sh_rays, sh_contrib, lacc, radsum;
         rt3::DevBuf<float> sh2_rays, sh2_contrib, sh2_tmax;  // RT3_F_NEE_EMISSIVE: the emitter shadow queue, allocated when the flag is first used
         size_t cap_emit = 0;
+        rt3::DevBuf<float> pane_dist;  // pane shadows: one float per path of the batch (k_shade_pane), allocated when a frame first needs it
+        size_t cap_pane = 0;
         rt3::DevBuf<uint32_t> d_counters;
         uint32_t counters_cap = 1 << 16, counters_next = 0;
         rt3::DevBuf<unsigned long long> d_totals;  // counting mode: kTotWords words (TotalsWord)
@@ -275,6 +281,9 @@ struct rt3_ctx {
         rt3_roulette_params params = {2u, 0.0625f, {0u, 0u}};
         bool on = false;
     } roulette;
+    // rt3_scene.hip: pane shadows (rt3_scene_set_pane_shadows): the mode, read by the next rt3_accel_build; off by default.
+    // It lives here, not in `scene`: rt3_scene_set_geometry leaves it as it is
+    bool pane_shadows = false;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot
@@ -357,6 +366,13 @@ int deform_flags(rt3_ctx* c);
 inline bool any_cutoff(const rt3_ctx* c) { return !c->scene.h_cutoffs.empty(); }
 inline bool any_mat_tex(const rt3_ctx* c) { return !c->scene.h_mat_tex.empty(); }
 inline bool any_glass(const rt3_ctx* c) { return !c->scene.h_transmission.empty(); }
+// is uploaded geometry g a pane (rt3_scene_set_pane_shadows)?  Mode on, transmission > 0, thin-walled, no normal texture
+inline bool pane_geometry(const rt3_ctx* c, uint32_t g) {
+    if (!c->pane_shadows || !any_glass(c)) return false;
+    const rt3_transmission& t = c->scene.h_transmission[g];
+    if (!(t.transmission > 0.0f) || t.thin_walled != 1u) return false;
+    return !any_mat_tex(c) || c->scene.h_mat_tex[g].normal_texture < 0;
+}
 
 // ---- rt3_accel.hip
 void invalidate_accel(rt3_ctx* c);  // the structure is not for the current scene any more: accel.built goes
@@ -371,6 +387,8 @@ GeomTables world_tables(const rt3_ctx* c);
 // the alpha-mask tables of a traversal launch over the current structure: empty (table null) without masked triangles.  The texture atlas
 // must be synchronised (sync_textures) first.
 AlphaDev alpha_dev(const rt3_ctx* c);
+// what k_shadow_pane reads of a structure with panes (accel.n_panes != 0)
+PaneDev pane_dev(const rt3_ctx* c);
 int ensure_lights(rt3_ctx* c, uint32_t combo = RT3_F_NEE_EMISSIVE);  // combo: flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL)
 // RT3_OPT_SHADOW_EXIT_TABLE changed: the table of a built, current structure is refilled (or switched off) now
 int exit_table_update(rt3_ctx* c);

@@ -68,4 +68,22 @@ RT3_DEV GlassEvent glass_sample(float ior, bool thin, V3 d, V3 n, float u) {
     return e;
 }
 
+// Pane shadows (rt3_scene_set_pane_shadows).  GlassDev::pad of a geometry the build classified as a pane:
+constexpr uint32_t kGlassPaneBit = 1u;
+// 1 - F' of a thin-walled pane of index ior met at cos_i = |n.d| / |d|: glass_sample's Fresnel expression at eta = ior (a pane has the
+// same eta on both sides), so that an index-matched pane gives exactly 1.  With the transmission and the tint it is the expectation of
+// what a glass vertex there does to the throughput of a path that goes straight on.
+RT3_DEV float pane_pass_fraction(float ior, float cos_i) {
+    const float eta2 = ior * ior;
+    const float cos_t2 = (cos_i * cos_i + (eta2 - 1.0f)) / eta2;
+    float F = 1.0f;
+    if (cos_t2 > 0.0f) {
+        const float cos_t = sqrtf(cos_t2);
+        const float rs = (cos_i - ior * cos_t) / (cos_i + ior * cos_t);
+        const float rp = (ior * cos_i - cos_t) / (ior * cos_i + cos_t);
+        F = 0.5f * (rs * rs + rp * rp);
+    }
+    return 1.0f - (2.0f * F) / (1.0f + F);
+}
+
 }  // namespace rt3

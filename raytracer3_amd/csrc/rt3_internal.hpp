@@ -112,7 +112,8 @@ void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, 
 // defer: k_shade_defer -- the sky shadow queue then holds plain ray records in sh_rays and, in sh_contrib, one plane
 // of `stride` words with each ray's vertex (its index in the input queue) and a second plane for k_shadow's occlusion words; launch_light
 // finishes the unoccluded light samples from them.  Only without material textures, punctual lights and glass.
-void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false);
+// pane_dist (with glass): k_shade_pane and its per-path distance array, one float per path of the batch, zero at its start
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false, float* pane_dist = nullptr);
 void launch_light(hipStream_t st, bool first, ShadeLaunch L);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
@@ -353,6 +354,14 @@ struct LbvhResult {
         from.arena_serial = 0;
     }
 };
+// What k_shadow_pane reads besides the tree and the alpha tables (pane shadows): the scene tables hit_finish needs for
+// a pane's shading normal and tint, the glass table for its transmission and index, and the first alpha slot that marks a masked pane
+// record (an unmasked pane record is {0, 1}; a masked one {cutoff, slot >= first_slot}, its slot a copy of the geometry's alpha entry).
+struct PaneDev {
+    SceneDev sc;
+    const GlassDev* glass;
+    uint32_t first_slot;
+};
 // One traversal launch over a ray queue: closest hit (launch_extend) or any hit (launch_shadow).  Each reads only its own outputs.
 struct TraceLaunch {
     const float* rays = nullptr;          // two float4 streams of `stride` records, {o.xyz, tmin} then {d.xyz, tmax}
@@ -370,6 +379,7 @@ struct TraceLaunch {
     uint32_t *cnt_nodes = nullptr, *cnt_tris = nullptr;
     unsigned long long* totals = nullptr;
     AlphaDev alpha = {};                  // alpha.table set: the structure holds masked triangles, the launch runs the MASK instance
+    const PaneDev* pane = nullptr;        // any hit over the path tracer's own queue in a structure with panes: k_shadow_pane
 };
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
 void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);

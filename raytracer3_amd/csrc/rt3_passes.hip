@@ -45,6 +45,8 @@ void free_work(rt3_ctx* c) {
     c->work.hits.reset(); c->work.sh_rays.reset(); c->work.sh_contrib.reset(); c->work.lacc.reset(); c->work.radsum.reset();
     c->work.sh2_rays.reset(); c->work.sh2_contrib.reset(); c->work.sh2_tmax.reset();
     c->work.cap_emit = 0;
+    c->work.pane_dist.reset();
+    c->work.cap_pane = 0;
     c->work.cap = 0;
     c->work.cap_pix = 0;
 }
@@ -79,6 +81,16 @@ int ensure_emit_queue(rt3_ctx* c) {
     if (!r) r = dev_alloc(c, c->work.sh2_contrib, 2 * c->work.cap);
     if (!r) r = dev_alloc(c, c->work.sh2_tmax, c->work.cap);
     if (!r) c->work.cap_emit = c->work.cap;
+    else free_work(c);
+    return r;
+}
+
+// k_shade_pane's distance per path, as many as the queues hold (after ensure_work)
+int ensure_pane_dist(rt3_ctx* c) {
+    if (c->work.cap_pane >= c->work.cap) return RT3_OK;
+    c->work.cap_pane = 0;
+    int r = dev_alloc(c, c->work.pane_dist, c->work.cap);
+    if (!r) c->work.cap_pane = c->work.cap;
     else free_work(c);
     return r;
 }
@@ -235,6 +247,9 @@ struct PathSetup {
     bool rr = false;
     uint32_t rr_start = 0;
     float rr_min = 1.0f;
+    // pane shadows (rt3_scene_set_pane_shadows): the built structure has panes -- k_shade_pane and k_shadow_pane
+    bool panes = false;
+    PaneDev pane{};
 };
 // pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
 constexpr float kSkyDeferMinPdf = 0x1p-100f;
@@ -260,6 +275,11 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     ps->nee_e = ps->lights.n != 0u;
     ps->sc = scene_dev(c);
     ps->defer = c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
+    ps->panes = c->accel.n_panes != 0u && c->accel.has_glass;
+    if (ps->panes) {
+        if (int r = ensure_pane_dist(c)) return r;
+        ps->pane = pane_dev(c);
+    }
     ps->rr = c->roulette.on && c->roulette.params.start_bounce < B - 1u;
     ps->rr_start = c->roulette.params.start_bounce;
     ps->rr_min = c->roulette.params.min_survival;
@@ -329,6 +349,8 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             launch_lens_miss(c->stream, ps.sc, c->work.rays[0].get(), c->work.hits.get(), c->work.lacc.get(), S, n_first);
         }
     }
+    // every path starts at distance 0 from the vertex that chose its direction (the camera)
+    if (ps.panes) HIPC(c, hipMemsetAsync(c->work.pane_dist.get(), 0, (size_t)n_first * sizeof(float), c->stream));
     for (uint32_t bn = 0; bn < B; bn++) {
         ShadeLaunch L;
         L.g = ps.gd; L.sc = ps.sc; L.pixels = pixels; L.pixbn = pixbn; L.npix = npix; L.width = W; L.s0 = s0; L.bounce = bn;
@@ -343,7 +365,8 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         {
             ScopedTimer t(c, CAT_SHADE);
             // (glass only with a lens: pass_reference_mode and pass_adaptive see to it)
-            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr, ps.defer);
+            launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr, ps.defer,
+                         ps.panes ? c->work.pane_dist.get() : nullptr);
         }
         cur ^= 1;
         if (nee) {
@@ -353,6 +376,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
                 tr.occluded = reinterpret_cast<uint32_t*>(c->work.sh_contrib.get()) + S;
             } else {
                 tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
+                if (ps.panes) tr.pane = &ps.pane;
             }
             ScopedTimer t(c, CAT_SHADOW);
             launch_shadow(c->stream, c->accel.bvh, tr);
@@ -367,6 +391,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             TraceLaunch tr = ctx_trace(c);
             tr.rays = c->work.sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
             tr.contrib = c->work.sh2_contrib.get(); tr.lacc = c->work.lacc.get(); tr.tmax = c->work.sh2_tmax.get();
+            if (ps.panes) tr.pane = &ps.pane;
             ScopedTimer t(c, CAT_SHADOW);
             launch_shadow(c->stream, c->accel.bvh, tr);
         }

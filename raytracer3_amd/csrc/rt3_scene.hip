@@ -299,6 +299,20 @@ int rt3_scene_set_transmission(rt3_ctx* c, const rt3_transmission* t, uint32_t n
     invalidate_topology(c);  // the side table is made by a build
     return RT3_OK;
 }
+// pane shadows: the mode is the context's, the classification is made by the next build
+int rt3_scene_set_pane_shadows(rt3_ctx* c, int on) {
+    if (!c) return RT3_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, RT3_E_INVALID, "pane shadows: the mode is 0 or 1");
+    if ((on != 0) == c->pane_shadows) return RT3_OK;
+    c->pane_shadows = on != 0;
+    invalidate_topology(c);  // the triangle records carry the pane marks: a new build, not a refit
+    return RT3_OK;
+}
+int rt3_scene_get_pane_shadows(rt3_ctx* c, int* on) {
+    if (!c || !on) return fail(c, RT3_E_INVALID, "pane shadows: NULL");
+    *on = c->pane_shadows ? 1 : 0;
+    return RT3_OK;
+}
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
 // arithmetic, in double, in the same order): radiance stored as RGB9E5 (packing.slang:99-162), marginal CDF over rows, one alias
 // table per row with 16-bit keep-thresholds, pdf_uv = the density the quantised tables really realise.

@@ -164,6 +164,8 @@ constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
     constexpr bool PUNCT = false, GLASS = false, DEFER = false, LIGHT = false;
+    constexpr bool PANE = false;
+    float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
 // Waves: at six (80 VGPRs) the light function costs the FIRST and GLDS twins more scratch than their EMIT instance has (108 against 96 bytes,
@@ -171,6 +173,8 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool MAT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
     constexpr bool EMIT = true, PUNCT = true, GLASS = false, DEFER = false, LIGHT = false;
+    constexpr bool PANE = false;
+    float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
 // GLASS: the built scene has the transmission side table (a.glass); a vertex on a geometry with transmission > 0 is,
@@ -181,6 +185,18 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_glass(ShadeLaunch a) {
     constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false;
+    constexpr bool PANE = false;
+    float* const pane_dist = nullptr;
+#include "rt3_shade_body.inc"
+}
+// PANE: k_shade_glass for a built scene with panes under rt3_scene_set_pane_shadows.  A glass vertex on a pane that
+// transmits hands the incoming pdf slot on instead of a delta marker, because the light samples of the vertex before it now cross the pane
+// (k_shadow_pane) and the two must share one pair of MIS weights; pane_dist[path] carries the distance walked along the direction since the
+// vertex that sampled it, which an emitter hit needs for that vertex's solid-angle density.  A kernel of its own name and argument list,
+// so that every other instance keeps its name and its instructions.  Registers and scratch per instance: DESIGN.md section 4q.
+template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_pane(ShadeLaunch a, float* pane_dist) {
+    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false, PANE = true;
 #include "rt3_shade_body.inc"
 }
 // DEFER: k_shade<FIRST, GLDS, EMIT> with the sky light sample cut off behind its direction.  Four of five sky shadow
@@ -190,6 +206,8 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool EMIT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer(ShadeLaunch a) {
     constexpr bool MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
+    constexpr bool PANE = false;
+    float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
 // The second half of k_shade_defer's light samples, for the rays k_shadow reported as unoccluded: a.sh_count slots in a.sh_contrib (light_next),
@@ -198,6 +216,8 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_light(ShadeLaunch a) {
     constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = false, LIGHT = true;
+    constexpr bool PANE = false;
+    float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
 // self-test op 32: {ior, thin_walled, d xyz, n xyz, u} -> {event (0 reflect / 1 transmit), direction xyz, F}
@@ -271,7 +291,8 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punc
     else by_mat(std::false_type{});
 }
 // defer: the k_shade_defer instance (the caller has checked that the scene is inside its cover: shade_defer_covers)
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer) {
+// pane_dist: the built scene has panes and pane shadows are on (with `glass`): k_shade_pane, twelve instances shaped like k_shade_glass's
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer, float* pane_dist) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
@@ -288,6 +309,10 @@ void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const G
         if constexpr (!decltype(f)::value) {
             if (glass != nullptr) {
                 a.glass = glass;  // (in the slot of the G-buffer, which these kernels do not read)
+                if (pane_dist != nullptr) {
+                    hipLaunchKernelGGL((k_shade_pane<decltype(g)::value, decltype(e)::value, decltype(m)::value, decltype(p)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a, pane_dist);
+                    return;
+                }
                 hipLaunchKernelGGL((k_shade_glass<decltype(g)::value, decltype(e)::value, decltype(m)::value, decltype(p)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);
                 return;
             }

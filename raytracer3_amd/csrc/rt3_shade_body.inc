@@ -4,6 +4,9 @@
 // index of the vertex in the queue it was read from; radiance, BSDF and weight wait for k_light, which evaluates them for the unoccluded
 // rays only.  LIGHT (k_light): the same text as that second half -- the loop visits the unoccluded slots of the shadow queue (light_next),
 // rebuilds each one's vertex from the inputs k_shade_defer read, and adds the contribution where k_shadow would have.
+// PANE (k_shade_pane, DESIGN.md section 4q): GLASS in a built scene with panes and pane shadows on; `pane_dist` (one float per path of the batch)
+// is in scope beside `a`.  Every use of either is `PANE && ...`, a constant in the other kernels, which so keep their instructions.
+    static_assert(GLASS || !PANE, "a pane is a glass geometry");
     static_assert(!(DEFER && LIGHT) && !((DEFER || LIGHT) && (MAT || PUNCT || GLASS)), "deferral covers the plain opaque instances");
     static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
     static_assert(EMIT || !PUNCT, "punctual lights are records of the emitter table");
@@ -135,6 +138,7 @@
         bool emit_shadow = false, emit_ext = false;
         V3 wl = v3(0, 1, 0), contrib = v3(0, 0, 0), nd = v3(0, 0, 1), Tn = T;
         float pdf_n = 0.0f;
+        float dist_n = 0.0f;  // PANE: the distance the extension ray's direction has been followed since the vertex that sampled it
         bool emit_shadow_e = false;  // EMIT: the emitter shadow ray
         V3 wle = v3(0, 1, 0), contrib_e = v3(0, 0, 0);
         float tmax_e = 0.0f;
@@ -235,7 +239,10 @@
                         const float4* R = a.lights.rec + 4 * (size_t)(eb + (hrecord.prim - a.sc.first_prim[hrecord.rec.w]));
                         const float pa = R[0].w;  // p_sel / area, the value the sampler divides by
                         const float4 rn = R[3];
-                        const float dl = sqrtf(dot(d, d)), cle = fabsf(rn.x * d.x + rn.y * d.y + rn.z * d.z) / dl, dist = t * dl;
+                        const float dl = sqrtf(dot(d, d)), cle = fabsf(rn.x * d.x + rn.y * d.y + rn.z * d.z) / dl;
+                        float dist = t * dl;
+                        // PANE: the density is the one seen from the vertex that sampled the direction, the panes crossed since lie on the way
+                        if (PANE) dist = pane_dist[pid] + dist;
                         if (pa > 0.0f && cle > 0.0f) {
                             const float ps = pa * (dist * dist) / cle;
                             le = le * (pdf_b / (pdf_b + ps));
@@ -321,7 +328,22 @@
                     const GlassEvent ev = glass_sample(gl.ior, gl.thin_walled != 0u, d, surf.normal, uniform_float(seed, kGlassRngBase + 2u * (sm * B + b) + 1u));
                     nd = ev.dir;
                     if (ev.transmit) Tn = T * surf.albedo;  // the tint: base colour x base-colour texture
-                    if (!last) {
+                    // PANE (DESIGN.md section 4q): a path that goes straight on through a pane is still the sample of the vertex that chose its
+                    // direction, whose light samples now cross the pane too: the pdf slot is handed on as it came, with the distance walked
+                    const bool pane_on = PANE && (gl.pad & kGlassPaneBit) != 0u && ev.transmit != 0u;
+                    if (PANE && pane_on && !last) {
+                        pdf_n = pdf_b;
+                        dist_n = pane_dist[pid] + t * sqrtf(dot(d, d));
+                        emit_ext = true;
+                    } else if (PANE && pane_on && nee) {  // the last vertex: the miss branch's weight, one vertex early
+                        float su, sv, pl_s;
+                        direction_to_equirect_uv(nd, su, sv);
+                        const V3 srad = sky_eval_and_pdf(a.sc, su, sv, pl_s);
+                        const float w = pdf_b > 0.0f ? pdf_b / (pdf_b + pl_s) : 0.0f;
+                        wl = nd;
+                        contrib = v3(Tn.x * (srad.x * w), Tn.y * (srad.y * w), Tn.z * (srad.z * w));
+                        emit_shadow = contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f;
+                    } else if (!last) {
                         pdf_n = pdf_b == kFloatMax ? kFloatMax : kGlassDeltaPdf;
                         emit_ext = true;
                     } else if (nee) {
@@ -387,5 +409,6 @@
             a.out_T[j] = Tn.x;
             a.out_T[S + j] = Tn.y;
             a.out_T[2 * S + j] = Tn.z;
+            if (PANE) pane_dist[pid] = dist_n;  // per path, not per queue slot: k_roulette moves records, not paths
         }
     }

@@ -54,8 +54,21 @@ __device__ __forceinline__ void pin(float4& q) { asm volatile("" : "+v"(q.x), "+
 __device__ __forceinline__ V3 cross_exact(V3 a, V3 b) { return V3{(a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)}; }
 // MASK: a candidate that would be accepted is, if its record is masked (q2.z = cutoff > 0, q2.w = slot), kept only when its alpha passes
 // (alpha_counts): a masked triangle that fails is not there for this ray.
-template <bool MASK = false>
-__device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 o, V3 d, float inv_dd, float tmin, Hit& best, const AlphaDev& alpha = AlphaDev{}) {
+// PANE (any hit, the path tracer's own shadow queues): a candidate that would be accepted -- the cutout test included -- on
+// a pane record does not occlude: the ray's contribution pay[0..2] is multiplied by the pane's expected straight-through transmittance
+// (pane_attenuation) and best stays what it is.  A contribution that has become 0 in all three channels ends the ray as occluded.
+__device__ __forceinline__ bool pane_record(float cutoff, uint32_t slot, uint32_t first_slot) { return cutoff != 0.0f ? slot >= first_slot : slot != 0u; }
+// A = transmission (1 - F'(cos_i)) tint at barycentrics (u, v) of primitive prim: hit_finish's shading normal (not face-forwarded) and albedo
+__device__ __forceinline__ V3 pane_attenuation(const PaneDev& p, uint32_t prim, float u, float v, V3 d) {
+    const HitRecord h = hit_fetch(p.sc, prim);
+    const Surface s = hit_finish(p.sc, p.sc.shade_geoms, h, u, v);
+    const GlassDev gl = p.glass[h.rec.w];
+    const float cos_i = fabsf(dot(s.normal, d)) / sqrtf(dot(d, d));
+    return s.albedo * (gl.transmission * pane_pass_fraction(gl.ior, cos_i));
+}
+template <bool MASK = false, bool PANE = false>
+__device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 o, V3 d, float inv_dd, float tmin, Hit& best, const AlphaDev& alpha = AlphaDev{},
+                                            const PaneDev* pane = nullptr, float* pay0 = nullptr, float* pay1 = nullptr, float* pay2 = nullptr) {
     const V3 A = v3(q0.x, q0.y, q0.z) - o, B = v3(q0.w, q1.x, q1.y) - o, C = v3(q1.z, q1.w, q2.x) - o;
     const float U = dot_fma(d, cross_exact(B, C)), V = dot_fma(d, cross_exact(C, A)), W = dot_fma(d, cross_exact(A, B));
     const float det = U + (V + W);  // the association of T below: equal vertex distances give t exactly
@@ -70,6 +83,15 @@ __device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 
     const bool inside = (w >= -kEdgeEps) & (u >= -kEdgeEps) & (v >= -kEdgeEps);
     bool ok = (det != 0.0f) & inside & (t > tmin) & ((t < best.t) | ((t == best.t) & (prim < best.prim)));
     if (MASK && ok && q2.z != 0.0f) ok = alpha_counts(alpha, __float_as_uint(q2.w), q2.z, prim, u, v);
+    if constexpr (PANE) {
+        if (ok && pane_record(q2.z, __float_as_uint(q2.w), pane->first_slot)) {
+            const V3 att = pane_attenuation(*pane, prim, u, v, d);
+            *pay0 *= att.x;
+            *pay1 *= att.y;
+            *pay2 *= att.z;
+            ok = *pay0 == 0.0f && *pay1 == 0.0f && *pay2 == 0.0f;
+        }
+    }
     best.t = ok ? t : best.t;
     best.u = ok ? u : best.u;
     best.v = ok ? v : best.v;
@@ -172,12 +194,15 @@ struct LaneRay {  // traversal state of the ray a lane currently owns
 // MASK: the structure holds alpha-masked triangles: a candidate that would be accepted (inside, t in range, better than
 // best) is alpha-tested inline in its leaf step -- the extra gathers (table, 3 uvs, texture entry, 4 texels) stay out of every other step.
 // best is only updated, and an any-hit lane only finishes, on an intersection that counts.
-template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, bool EXIT = false, typename Finish>
+// PANE (any hit, MASK instances): pane triangles attenuate the lane's payload instead of occluding it (tri_test_nb).  Like
+// the alpha test, the gathers of an attenuation (shading record, geometry and glass entries, texels) stay inside the leaf step that meets one.
+template <int MODE, bool COUNT, int LAYOUT, bool TWO = false, bool RANGE = false, bool MASK = false, bool EXIT = false, bool PANE = false, typename Finish>
 __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, uint32_t tri_off,
                                              const float* __restrict__ rays, size_t stride, uint32_t n, uint32_t* __restrict__ work_counter,
                                              uint32_t* __restrict__ lds, Finish finish, bool any_payload = false, bool ext_payload = false, const float4* top_lds = nullptr, bool use_top = false,
                                              const float2* __restrict__ any_contrib = nullptr, const float* __restrict__ any_tmax = nullptr,
-                                             const AlphaDev& alpha = AlphaDev{}, ExitWalk* xw = nullptr) {
+                                             const AlphaDev& alpha = AlphaDev{}, ExitWalk* xw = nullptr, const PaneDev* pane = nullptr) {
+    static_assert(!PANE || (MODE == 1 && MASK && !EXIT && LAYOUT == kLayoutWide64Q), "panes: the any-hit walk of the default node layout, never from the exit table");
     static_assert(!EXIT || (MODE == 1 && !COUNT && !TWO && !RANGE && LAYOUT == kLayoutWide64Q), "the exit table serves the plain any-hit walk only");
     // any_payload: the any-hit rays come from k_shade's shadow queue, where every ray has the range (kRayTMin, kBackgroundDepth):
     // the two .w slots of its record carry payload (two contribution channels) instead of tmin / tmax -- 16 bytes less per ray.
@@ -440,10 +465,11 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
                     c = transform_point(fm, c);
                 }
                 const uint32_t gp = __float_as_uint(q2.y) + (tl_base & 0x7FFFFFFFu);
-                tri_test_nb<MASK>(make_float4(a.x, a.y, a.z, b.x), make_float4(b.y, b.z, c.x, c.y),
-                                  make_float4(c.z, __uint_as_float(gp), MASK ? q2.z : 0.0f, MASK ? q2.w : 0.0f), o, d, r.inv_dd, tmin, r.best, alpha);
+                tri_test_nb<MASK, PANE>(make_float4(a.x, a.y, a.z, b.x), make_float4(b.y, b.z, c.x, c.y),
+                                        make_float4(c.z, __uint_as_float(gp), MASK ? q2.z : 0.0f, MASK ? q2.w : 0.0f), o, d, r.inv_dd, tmin, r.best, alpha, pane,
+                                        &r.pay0, &r.pay1, &r.pay2);
             } else {
-                tri_test_nb<MASK>(q0, q1, q2, o, d, r.inv_dd, tmin, r.best, alpha);
+                tri_test_nb<MASK, PANE>(q0, q1, q2, o, d, r.inv_dd, tmin, r.best, alpha, pane, &r.pay0, &r.pay1, &r.pay2);
             }
             r.leaf_k++;
             if (WIDE) {  // the 128 B fetch holds a second triangle
@@ -714,6 +740,37 @@ __global__ __launch_bounds__(kExtendBlock) void k_shadow(const float4* __restric
     counts.add_totals(totals, lds_total);
 }
 
+// k_shadow<COUNT, LAYOUT, RANGE, MASK = true> for a structure with panes (rt3_scene_set_pane_shadows): the path tracer's own
+// shadow queues only (no reporting mode), and an unoccluded ray adds its contribution as the panes it crossed left it.  A kernel of its own
+// name, so that every instance of k_shadow keeps its name and its instructions.  Always carries the alpha test: a scene without masks has no
+// record with a cutoff, and its alpha table is never read.
+template <bool COUNT, int LAYOUT, bool RANGE>
+__global__ __launch_bounds__(kExtendBlock) void k_shadow_pane(const float4* __restrict__ nodes, uint32_t tri_off, const float4* __restrict__ top, uint32_t n_top,
+                                                              const float* __restrict__ rays, size_t stride,
+                                                              const uint32_t* __restrict__ count_ptr, uint32_t count_imm, AlphaDev alpha, PaneDev pane,
+                                                              const float* __restrict__ contrib, float* __restrict__ lacc,
+                                                              uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_tris,
+                                                              unsigned long long* __restrict__ totals, uint32_t* __restrict__ work_counter,
+                                                              unsigned long long* __restrict__ lds_total, const float* __restrict__ tmax) {
+    __shared__ uint32_t stack[kLdsStack * kExtendBlock];
+    __shared__ float4 s_top[4 * kTopNodes];
+    const bool use_top = load_top(s_top, top, n_top);
+    const uint32_t n = count_ptr ? *count_ptr : count_imm;
+    TraceCounts<COUNT> counts{cnt_nodes, cnt_tris};
+    trace_stream<1, COUNT, LAYOUT == kLayoutTwoLevel ? kLayoutWide64Q : LAYOUT, LAYOUT == kLayoutTwoLevel, RANGE, true, false, true>(
+        nodes, tri_off, rays, stride, n, work_counter, stack + threadIdx.x,
+        [&](uint32_t i, const Hit& h, uint32_t cn, uint32_t ct, uint32_t cl, float c_r, float c_g, float c_b, float c_pid) {
+            if (h.prim == kMiss) {
+                float4* L = reinterpret_cast<float4*>(lacc) + __float_as_uint(c_pid);
+                float4 v = *L;
+                *L = make_float4(v.x + c_r, v.y + c_g, v.z + c_b, 0.0f);
+            }
+            counts.ray(i, cn, ct, cl);
+        },
+        true, false, s_top, use_top, reinterpret_cast<const float2*>(contrib), tmax, alpha, nullptr, &pane);
+    counts.add_totals(totals, lds_total);
+}
+
 // k_shadow<false, kLayoutWide64Q, false, MASK> with the exit table (DESIGN.md sections 5 and 7): the same queue, the same finish; every ray, or
 // every 32nd chunk of rays, first tries the leaf its exit cell names.  exit_off: the table's header in the arena; counters: the context's
 // {rays that started at an entry, rays an entry's leaf occluded}.
@@ -802,8 +859,30 @@ void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) 
                            L.payload ? 1 : 0, alpha_arg<decltype(m)::value>(L), lds_tot);
     });
 }
+// the k_shadow_pane instance of (count, layout, range): L.pane set, the path tracer's own queue (contrib and lacc set, no reporting).  Never
+// from the exit table: a leaf tried there is walked again from the root and would attenuate twice.
+static void launch_shadow_pane(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L, unsigned grid) {
+    unsigned long long* const tot = L.totals ? L.totals + kTotShadowNodes : nullptr;
+    unsigned long long* const lds_tot = L.totals ? L.totals + kTotShadowLds : nullptr;
+    auto launch = [&](auto c, auto l, auto range) {
+        hipLaunchKernelGGL((k_shadow_pane<decltype(c)::value, decltype(l)::value, decltype(range)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(),
+                           bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays, L.stride, L.count_ptr, L.n, L.alpha, *L.pane, L.contrib, L.lacc, L.cnt_nodes, L.cnt_tris, tot,
+                           L.work_counter, lds_tot, L.tmax);
+    };
+    auto by_range = [&](auto c, auto l) {
+        if (L.tmax) launch(c, l, std::true_type{});
+        else launch(c, l, std::false_type{});
+    };
+    auto by_layout = [&](auto c) {
+        if (bvh.layout == kLayoutTwoLevel) by_range(c, std::integral_constant<int, kLayoutTwoLevel>{});
+        else by_range(c, std::integral_constant<int, kLayoutWide64Q>{});
+    };
+    if (L.count) by_layout(std::true_type{});
+    else by_layout(std::false_type{});
+}
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
     const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
+    if (L.pane != nullptr && L.occluded == nullptr && (bvh.layout == kLayoutWide64Q || bvh.layout == kLayoutTwoLevel)) return launch_shadow_pane(st, bvh, L, grid);
     if (bvh.exit.on && bvh.exit.off && bvh.exit.counters && bvh.layout == kLayoutWide64Q && bvh.nodes && !L.count && !L.tmax) {  // the plain any-hit walk, table present
         auto launch = [&](auto m) {
             hipLaunchKernelGGL((k_shadow_exit<decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays,

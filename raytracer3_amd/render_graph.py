@@ -207,6 +207,22 @@ class Context:
         t = np.ascontiguousarray(table, TRANSMISSION_DTYPE).reshape(-1)
         self.check(self.lib.rt3_scene_set_transmission(self.h, t.ctypes.data if len(t) else None, len(t)))
 
+    def set_pane_shadows(self, on):
+        """pane shadows (rt3_scene_set_pane_shadows): shadow rays cross thin-walled glass attenuated.  A mode of the
+        context (set_geometry keeps it); a change takes effect at the next build_accel()."""
+        self.check(self.lib.rt3_scene_set_pane_shadows(self.h, int(on)))
+
+    def get_pane_shadows(self):
+        on = C.c_int32(0)
+        self.check(self.lib.rt3_scene_get_pane_shadows(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def pane_shadow_info(self):
+        """flattened geometries the built structure holds as panes (rt3_pane_shadow_info): 0 while the mode is off"""
+        n = C.c_uint32(0)
+        self.check(self.lib.rt3_pane_shadow_info(self.h, C.byref(n)))
+        return int(n.value)
+
     def set_instances(self, instances):
         """instances: [(geometry_first, geometry_count, 4x4 matrix as numpy, object -> world)] -- Instance + Transform of
         src/renderer/world/mod.rs:46-60; [] = every geometry once under the identity.  Takes effect at the next build_accel()."""

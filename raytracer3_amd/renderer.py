@@ -214,6 +214,7 @@ class PathTracer:
         self.host_group = None   # process group of the host-moved gather (None = the default group)
         self._history = _TemporalHistory(self.ctx)
         self._glass_lens = False  # the lens in force is the pinhole set_scene switched on for a scene with glass
+        self._scene_set = False   # set_scene has built a structure (set_pane_shadows rebuilds it)
 
     def close(self):
         self.ctx.close()
@@ -235,6 +236,7 @@ class PathTracer:
         if bluenoise is not None:
             self.ctx.set_bluenoise(bluenoise)
         self.ctx.build_accel()
+        self._scene_set = True
         tr = getattr(mesh, "transmission", None)
         glass = tr is not None and len(tr) and bool(np.any(tr["transmission"] > 0))
         if glass and not self.ctx.get_lens()[1]:
@@ -246,6 +248,17 @@ class PathTracer:
         self._history.scene_set()
         if instances is not None:
             self._history.instances_set(instances)
+
+    def set_pane_shadows(self, on=True):
+        """Pane shadows (ctx.set_pane_shadows): light is sampled through thin-walled glass -- sky, emitter and punctual
+        shadow rays cross a pane attenuated by its expected transmittance instead of stopping at it.  Rebuilds, as set_scene does, when
+        the mode changes and a scene is set.  Unbiased; the same image in expectation for sky and emitters, and the only way a punctual
+        light shines through a window."""
+        if bool(on) == self.ctx.get_pane_shadows():
+            return
+        self.ctx.set_pane_shadows(bool(on))
+        if self._scene_set:
+            self.ctx.build_accel()
 
     def set_lights(self, lights=None):
         """Replace the world's punctual lights (assets.LIGHT_DTYPE; None forgets them).  No rebuild: frames with F_NEE_PUNCTUAL in their

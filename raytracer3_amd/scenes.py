@@ -404,6 +404,37 @@ def glass_cornell() -> Mesh:
                 transmission=np.concatenate([mesh.transmission, add.transmission]))
 
 
+SUNLIT_ROOM_CAMERA = dict(position=(0.0, 1.3, 2.6), direction=(-0.25, -0.12, -1.0), fov_deg=60.0)
+
+
+def sunlit_room() -> Mesh:
+    """A closed room, 4 x 2.6 x 6, whose only light comes through one window: an opening in the +x wall closed by a thin-walled, faintly
+    green pane, with the sky and a directional "sun" outside.  Render it under sky(), with F_NEE_SKY | F_NEE_PUNCTUAL
+    and PathTracer.set_pane_shadows(True): without pane shadows the sun never enters and the sky arrives only by paths that happen to
+    cross the pane.  A diffuse block stands in the patch of sunlight."""
+    from .assets import LIGHT_DIRECTIONAL, lights_array, make_light
+
+    mb = MeshBuilder()
+    wall, floor = Material((0.74, 0.72, 0.68), 0.0, 1.0), Material((0.55, 0.42, 0.3), 0.0, 0.8)
+    x0, x1, y0, y1, z0, z1 = -2.0, 2.0, 0.0, 2.6, -3.0, 3.0
+    wy0, wy1, wz0, wz1 = 0.7, 2.1, -1.6, 0.4  # the window in the wall x = x1
+    mb.add("floor", *_grid([x0, y0, z1], [x1 - x0, 0, 0], [0, 0, z0 - z1], 1, 1), floor)
+    mb.add("ceiling", *_grid([x0, y1, z0], [x1 - x0, 0, 0], [0, 0, z1 - z0], 1, 1), wall)
+    mb.add("back", *_grid([x0, y0, z0], [x1 - x0, 0, 0], [0, y1 - y0, 0], 1, 1), wall)
+    mb.add("front", *_grid([x1, y0, z1], [x0 - x1, 0, 0], [0, y1 - y0, 0], 1, 1), wall)
+    mb.add("left", *_grid([x0, y0, z1], [0, 0, z0 - z1], [0, y1 - y0, 0], 1, 1), Material((0.6, 0.3, 0.25), 0.0, 1.0))
+    # the +x wall around the window: below, above, and the two sides (normals -x: du along +z, dv along +y)
+    for name, (a0, a1, b0, b1) in (("right_below", (z0, z1, y0, wy0)), ("right_above", (z0, z1, wy1, y1)),
+                                   ("right_far", (z0, wz0, wy0, wy1)), ("right_near", (wz1, z1, wy0, wy1))):
+        mb.add(name, *_grid([x1, b0, a0], [0, 0, a1 - a0], [0, b1 - b0, 0], 1, 1), wall)
+    mb.add("window", *_grid([x1, wy0, wz0], [0, 0, wz1 - wz0], [0, wy1 - wy0, 0], 1, 1),
+           Material((0.85, 0.95, 0.88), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=1))
+    _box(mb, "block", [-0.6, 0.0, -1.3], [0.2, 0.7, -0.5], Material((0.3, 0.45, 0.7), 0.0, 0.9))
+    mesh = mb.build()
+    mesh.lights = lights_array([make_light(LIGHT_DIRECTIONAL, (6.0, 5.4, 4.6), direction=(-1.0, -0.55, -0.2))])
+    return mesh
+
+
 MATERIAL_SEED = 20240607
 
 

@@ -34,7 +34,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -59,6 +59,7 @@ def main():
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--roulette", nargs="?", type=int, const=2, default=None, metavar="START",
                     help="Russian roulette on the extension rays from vertex START on (default 2), survival floor 1/16 (DESIGN.md section 4o)")
+    ap.add_argument("--pane-shadows", action="store_true", help="sample lights through thin-walled glass (PathTracer.set_pane_shadows, DESIGN.md section 4q)")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
     ap.add_argument("--side-by-side", default=None, help="with --compare: write [render | reference] at the reference's size here")
     ap.add_argument("--report", default=None, help="with --compare: write the numbers and the scene parameters as JSON here")
@@ -83,17 +84,20 @@ def main():
         mesh, cam_kw = scenes.material_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "glass_cornell":  # a solid glass sphere and a thin-walled pane; set_scene switches the pinhole lens on
         mesh, cam_kw = scenes.glass_cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "sunlit_room":  # a closed room lit through one window by the sky and a sun; try --pane-shadows
+        mesh, cam_kw = scenes.sunlit_room(), scenes.SUNLIT_ROOM_CAMERA
     elif args.scene == "cornell_ref":
         mesh, cam_kw = scenes.cornell_ref(), scenes.CORNELL_REF_CAMERA
     else:
         mesh, cam_kw = scenes.atrium(args.detail), scenes.ATRIUM_CAMERA
-    sky = assets.read_exr(args.exr) if args.exr else (scenes.sky(2048, 1024) if args.scene == "atrium" or args.glb else None)
+    sky = assets.read_exr(args.exr) if args.exr else (scenes.sky(2048, 1024) if args.scene in ("atrium", "sunlit_room") or args.glb else None)
     if sky is not None:  # rt3_scene_set_sky wants finite, non-negative radiance; HDR files carry inf / NaN / tiny negatives
         sky = np.clip(np.nan_to_num(sky, nan=0.0, posinf=65504.0, neginf=0.0), 0.0, 65504.0).astype(np.float32)
     flags = args.flags if args.flags >= 0 else (DEFAULT_FLAGS if sky is not None else L.F_FACEFORWARD | L.F_SPECULAR)
     if args.flags < 0 and len(getattr(mesh, "lights", ())):  # a scene with punctual lights is lit by them
         flags |= L.F_NEE_PUNCTUAL
     pt = PathTracer((W, H))
+    pt.set_pane_shadows(args.pane_shadows)
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
