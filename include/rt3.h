@@ -174,6 +174,11 @@ int rt3_device_name(rt3_ctx *ctx, char *buf, size_t buf_size);
                                      only once its shadow ray came through unoccluded, in a kernel of its own (default); 0 = before the ray is
                                      traced.  Same frame bit for bit.  Scenes with glass, punctual lights or material textures, and skies whose
                                      smallest texel density is below 2^-100, take the path of 0 whatever the option says.  Takes effect at once */
+#define RT3_OPT_SHADE_EXIT_TEST 17 /* deferred sky light samples in a structure with an exit table: 1 = the shade kernel tries a sky shadow ray against the
+                                     leaf of its exit-table entry itself and queues only the rays that leaf does not occlude (default); 0 = every
+                                     ray is queued and k_shadow tries the entry.  Same frame and the same rt3_stats ray counts, bit for bit.
+                                     Frames with emitter or punctual sampling, alpha masks, panes, a two-level structure, RT3_OPT_COUNT_TRAVERSAL
+                                     or without deferral take the path of 0 whatever the option says.  Takes effect at once */
 int rt3_set_option(rt3_ctx *ctx, int option, int64_t value);
 
 /* ---- scene upload: DynamicBuffer::push (vulkan/buffer.rs:406-420) into the world buffers of

@@ -27,6 +27,7 @@ OPT_FUSED_TRACE = 10  # retired: rt3_set_option refuses it with E_INVALID (the n
 OPT_INSTANCE_MODE = 14  # 0 = flatten the instances (default), 1 = two-level: shared bottom trees under a top tree
 OPT_SHADOW_EXIT_TABLE = 15  # k_shadow's exit table: 0 = off, 1 = on (default), 2 = on with pseudo-random valid entries (a test aid)
 OPT_DEFER_SKY_LIGHT = 16  # sky NEE: 1 = light samples are evaluated after their shadow rays, for the unoccluded ones only (default), 0 = before
+OPT_SHADE_EXIT_TEST = 17  # deferred sky shadow rays: 1 = the shade kernel tries a ray's exit-table leaf and queues only undecided rays (default), 0 = k_shadow does
 DENOISE_NO_DEMODULATION = 1  # rt3_denoise_params.flags: filter In as it is (not refrence_mode's Light)
 TEMPORAL_NO_DEMODULATION = 1  # rt3_temporal_params.flags: the same for the "temporal" pass
 SELFTEST_EXPN = 28  # rt3_selftest_eval op: x >= 0 -> e^-x, the polynomial of the denoise pass

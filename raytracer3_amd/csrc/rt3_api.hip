@@ -67,6 +67,7 @@ int harvest(rt3_ctx* c) {  // stream must be idle
                 }
                 c->prof.stats.extension_rays += traced;
                 c->prof.stats.shadow_rays += h[b.first + 2 * k + 1];
+                if (b.dec_first) c->prof.stats.shadow_rays += h[b.dec_first + k];  // generated, and decided in the shade kernel
             }
             for (uint32_t k = 0; k < b.n_emit; k++) c->prof.stats.shadow_rays += h[b.emit_first + k];
         }
@@ -207,6 +208,10 @@ int rt3_set_option(rt3_ctx* c, int option, int64_t value) {
         case RT3_OPT_DEFER_SKY_LIGHT:
             if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "defer sky light must be 0 (off) or 1 (on)");
             c->opt.defer_sky_light = value != 0;
+            return RT3_OK;
+        case RT3_OPT_SHADE_EXIT_TEST:
+            if (value != 0 && value != 1) return fail(c, RT3_E_INVALID, "shade exit test must be 0 (off) or 1 (on)");
+            c->opt.shade_exit_test = value != 0;
             return RT3_OK;
         default: return fail(c, RT3_E_INVALID, "unknown option");
     }

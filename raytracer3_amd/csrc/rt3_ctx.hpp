@@ -62,6 +62,9 @@ struct CounterBlock {  // device counters of one refrence_mode launch, harvested
     // rr_first + bounce; rr_first = 0: no roulette in this batch.  `launch`: the pass launch the batch belongs to (Work::launch_serial)
     uint32_t rr_first = 0, rr_lo = 0;
     uint64_t launch = 0;
+    // RT3_OPT_SHADE_EXIT_TEST: word dec_first + bounce counts the sky shadow rays k_shade_defer_exit generated and decided
+    // itself, which the shadow-queue size no longer holds; dec_first = 0: none in this batch
+    uint32_t dec_first = 0;
 };
 
 // RT3_OPT_INSTANCE_MODE 1: what a build keeps for the next one.  The bottom trees live in the combined arrays
@@ -305,6 +308,7 @@ struct rt3_ctx {
         int instance_mode = 0;  // RT3_OPT_INSTANCE_MODE: 0 flatten, 1 two-level
         int exit_table = 1;     // RT3_OPT_SHADOW_EXIT_TABLE: 0 off, 1 on, 2 on with scrambled entries (a test aid)
         bool defer_sky_light = true;  // RT3_OPT_DEFER_SKY_LIGHT
+        bool shade_exit_test = true;  // RT3_OPT_SHADE_EXIT_TEST
     } opt;
     // rt3_api.hip (harvest, rt3_stats_reset), the events through ScopedTimer; stats.accel_* are rt3_accel.hip's (a build's time and copies)
     struct Prof {

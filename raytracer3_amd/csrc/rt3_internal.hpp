@@ -113,7 +113,16 @@ void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, 
 // of `stride` words with each ray's vertex (its index in the input queue) and a second plane for k_shadow's occlusion words; launch_light
 // finishes the unoccluded light samples from them.  Only without material textures, punctual lights and glass.
 // pane_dist (with glass): k_shade_pane and its per-path distance array, one float per path of the batch, zero at its start
-void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false, float* pane_dist = nullptr);
+// exit (with defer, no emitter table): k_shade_defer_exit, which tries a sky shadow ray against the leaf of its
+// exit-table entry and queues it only when that leaf does not occlude it
+struct ShadeExit {
+    const float4* arena = nullptr;            // the structure's arena (LbvhResult::nodes): triangle records at tri_off, the table at exit_off
+    uint32_t tri_off = 0, exit_off = 0;
+    unsigned long long* counters = nullptr;   // the context's {rays that tried an entry, rays an entry occluded} (ExitTable::counters)
+    uint32_t* decided = nullptr;              // the bounce's word for the shadow rays that were generated and decided here, never queued
+};
+void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false, float* pane_dist = nullptr,
+                  const ShadeExit* exit = nullptr);
 void launch_light(hipStream_t st, bool first, ShadeLaunch L);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
@@ -380,6 +389,8 @@ struct TraceLaunch {
     unsigned long long* totals = nullptr;
     AlphaDev alpha = {};                  // alpha.table set: the structure holds masked triangles, the launch runs the MASK instance
     const PaneDev* pane = nullptr;        // any hit over the path tracer's own queue in a structure with panes: k_shadow_pane
+    bool from_root = false;               // any hit: every ray starts at the root even when the structure has an exit table -- the queue holds
+                                          // what k_shade_defer_exit has tried against it already
 };
 // traversal of `bvh` (its layout, nodes, triangle records and LDS top copy)
 void launch_extend(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L);

@@ -241,6 +241,10 @@ struct PathSetup {
     // RT3_OPT_DEFER_SKY_LIGHT: k_shade_defer, k_shadow in its reporting mode, k_light.  Only inside their cover: sky NEE
     // on; no glass, punctual record or material table; every sky texel's density large enough that a sample's pdf cannot round to 0
     bool defer = false;
+    // RT3_OPT_SHADE_EXIT_TEST: k_shade_defer_exit, the plain k_shadow from the root, k_light.  Only with deferral, an
+    // exit table in use, no emitter queue, no alpha masks, no panes and no counting; `exit` is what the kernel needs of the structure
+    bool shade_exit = false;
+    ShadeExit exit{};
     bool lens_on = false;  // every sample starts from its own camera ray (rt3_camera_set_lens), not from the G-buffer ...
     LensDev lens{};        // ... made by these parameters
     // Russian roulette (rt3_path_set_roulette) on the extension rays of vertices rr_start .. B-2; off when no vertex is in that range
@@ -275,6 +279,17 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     ps->nee_e = ps->lights.n != 0u;
     ps->sc = scene_dev(c);
     ps->defer = c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
+    {
+        const LbvhResult& bvh = c->accel.bvh;
+        ps->shade_exit = c->opt.shade_exit_test && ps->defer && !ps->nee_e && !c->opt.count && alpha_dev(c).table == nullptr && c->accel.n_panes == 0u &&
+                         bvh.exit.on && bvh.exit.off && bvh.exit.counters && bvh.layout == kLayoutWide64Q && bvh.nodes;
+        if (ps->shade_exit) {
+            ps->exit.arena = bvh.nodes.get();
+            ps->exit.tri_off = bvh.tri_off;
+            ps->exit.exit_off = bvh.exit.off;
+            ps->exit.counters = bvh.exit.counters;
+        }
+    }
     ps->panes = c->accel.n_panes != 0u && c->accel.has_glass;
     if (ps->panes) {
         if (int r = ensure_pane_dist(c)) return r;
@@ -312,7 +327,9 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     // (a lens frame: two words more, the camera queue's length and the ray-pool cursor of its k_extend launch)
     // (roulette: B words more, [b] the extension queue's length after k_roulette of bounce b)
     const bool rr = ps.rr;
-    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0) + (rr ? B : 0), &first)) return r;
+    // (the exit test in the shade kernel: B words more, [b] the sky shadow rays of bounce b that were decided there and never queued)
+    const bool shade_exit = ps.shade_exit;
+    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0) + (rr ? B : 0) + (shade_exit ? B : 0), &first)) return r;
     first += first & 1u;  // 8-byte aligned pairs
     // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
     uint32_t* pairs = c->work.d_counters.get() + first;
@@ -321,8 +338,9 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     uint32_t* emit_cnt = c->work.d_counters.get() + first + 4 * B;
     uint32_t* lens_cnt = c->work.d_counters.get() + first + n_words;  // [0] the camera queue's length, [1] its ray-pool cursor
     uint32_t* rr_cnt = lens_cnt + (lens ? 2 : 0);
-    c->work.pending_counters.push_back(
-        CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u, rr ? first + n_words + (lens ? 2u : 0u) : 0u, ps.rr_start, c->work.launch_serial});
+    uint32_t* dec_cnt = rr_cnt + (rr ? B : 0);
+    c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u, rr ? first + n_words + (lens ? 2u : 0u) : 0u, ps.rr_start,
+                                                    c->work.launch_serial, shade_exit ? (uint32_t)(dec_cnt - c->work.d_counters.get()) : 0u});
     auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
     auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
     int cur = 0;
@@ -365,8 +383,10 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
         {
             ScopedTimer t(c, CAT_SHADE);
             // (glass only with a lens: pass_reference_mode and pass_adaptive see to it)
+            ShadeExit sx = ps.exit;
+            sx.decided = dec_cnt + bn;
             launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr, ps.defer,
-                         ps.panes ? c->work.pane_dist.get() : nullptr);
+                         ps.panes ? c->work.pane_dist.get() : nullptr, shade_exit ? &sx : nullptr);
         }
         cur ^= 1;
         if (nee) {
@@ -374,6 +394,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
             if (ps.defer) {  // report only, into the second plane of sh_contrib; the first holds the rays' vertices
                 tr.occluded = reinterpret_cast<uint32_t*>(c->work.sh_contrib.get()) + S;
+                tr.from_root = shade_exit;  // the queue holds what the entries' leaves did not occlude
             } else {
                 tr.contrib = c->work.sh_contrib.get(); tr.lacc = c->work.lacc.get();
                 if (ps.panes) tr.pane = &ps.pane;

@@ -8,6 +8,7 @@
 #include "rt3_camera.hpp"
 #include "rt3_glass.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_leaf_test.hpp"
 #include "rt3_math.hpp"
 #include "rt3_punctual.hpp"
 #include "rt3_rng.hpp"
@@ -164,8 +165,9 @@ constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
     constexpr bool PUNCT = false, GLASS = false, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false;
+    constexpr bool PANE = false, EXIT = false;
     float* const pane_dist = nullptr;
+    const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
 // Waves: at six (80 VGPRs) the light function costs the FIRST and GLDS twins more scratch than their EMIT instance has (108 against 96 bytes,
@@ -173,8 +175,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool MAT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
     constexpr bool EMIT = true, PUNCT = true, GLASS = false, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false;
+    constexpr bool PANE = false, EXIT = false;
     float* const pane_dist = nullptr;
+    const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
 // GLASS: the built scene has the transmission side table (a.glass); a vertex on a geometry with transmission > 0 is,
@@ -185,8 +188,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_glass(ShadeLaunch a) {
     constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false;
+    constexpr bool PANE = false, EXIT = false;
     float* const pane_dist = nullptr;
+    const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
 // PANE: k_shade_glass for a built scene with panes under rt3_scene_set_pane_shadows.  A glass vertex on a pane that
@@ -196,7 +200,8 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 // so that every other instance keeps its name and its instructions.  Registers and scratch per instance: DESIGN.md section 4q.
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_pane(ShadeLaunch a, float* pane_dist) {
-    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false, PANE = true;
+    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false, PANE = true, EXIT = false;
+    const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
 // DEFER: k_shade<FIRST, GLDS, EMIT> with the sky light sample cut off behind its direction.  Four of five sky shadow
@@ -206,7 +211,21 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool EMIT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer(ShadeLaunch a) {
     constexpr bool MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
-    constexpr bool PANE = false;
+    constexpr bool PANE = false, EXIT = false;
+    float* const pane_dist = nullptr;
+    const ShadeExit x = {};
+#include "rt3_shade_body.inc"
+}
+// EXIT: k_shade_defer<FIRST, GLDS, false> for a structure with an exit table.  Three of four sky shadow rays are
+// occluded by the leaf their exit cell names, which k_shadow_exit found out in the ray's first two steps -- after the ray had been written,
+// read back, prepared at a refill and its occlusion word written and scanned.  Origin and direction are in this kernel's registers: it
+// makes that test itself and queues only the rays the table cannot decide, which the plain k_shadow then walks from the root.  A kernel of
+// its own name, so that every other instance keeps its name and its instructions.  Launched only without an emitter queue, alpha masks,
+// panes and counting (trace_batch).
+template <bool FIRST, bool GLDS>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer_exit(ShadeLaunch a, ShadeExit x) {
+    constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
+    constexpr bool PANE = false, EXIT = true;
     float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
@@ -216,8 +235,9 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_light(ShadeLaunch a) {
     constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = false, LIGHT = true;
-    constexpr bool PANE = false;
+    constexpr bool PANE = false, EXIT = false;
     float* const pane_dist = nullptr;
+    const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
 // self-test op 32: {ior, thin_walled, d xyz, n xyz, u} -> {event (0 reflect / 1 transmit), direction xyz, F}
@@ -292,10 +312,17 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punc
 }
 // defer: the k_shade_defer instance (the caller has checked that the scene is inside its cover: shade_defer_covers)
 // pane_dist: the built scene has panes and pane shadows are on (with `glass`): k_shade_pane, twelve instances shaped like k_shade_glass's
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer, float* pane_dist) {
+// exit (with defer and an empty emitter table): k_shade_defer_exit
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer, float* pane_dist, const ShadeExit* exit) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
+    if (defer && exit != nullptr && a.lights.n == 0u) {
+        dispatch_shade(first, glds, false, false, false, [&](auto f, auto g, auto, auto, auto) {
+            hipLaunchKernelGGL((k_shade_defer_exit<decltype(f)::value, decltype(g)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a, *exit);
+        });
+        return;
+    }
     if (defer) {
         dispatch_shade(first, glds, a.lights.n != 0u, false, false, [&](auto f, auto g, auto e, auto, auto) {
             hipLaunchKernelGGL((k_shade_defer<decltype(f)::value, decltype(g)::value, decltype(e)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a);

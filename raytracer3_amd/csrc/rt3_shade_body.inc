@@ -6,11 +6,15 @@
 // rebuilds each one's vertex from the inputs k_shade_defer read, and adds the contribution where k_shadow would have.
 // PANE (k_shade_pane, DESIGN.md section 4q): GLASS in a built scene with panes and pane shadows on; `pane_dist` (one float per path of the batch)
 // is in scope beside `a`.  Every use of either is `PANE && ...`, a constant in the other kernels, which so keep their instructions.
+// EXIT (k_shade_defer_exit, DESIGN.md section 4r): DEFER with the structure's exit table in scope (`x`, ShadeExit).  A lane that would send a sky
+// shadow ray first tries the leaf its exit cell names -- k_shadow_exit's first step, with its cell rule and its triangle test
+// (rt3_leaf_test.hpp) -- and sends the ray only when that leaf does not occlude it.  Every use is `EXIT && ...` or `if constexpr (EXIT)`.
     static_assert(GLASS || !PANE, "a pane is a glass geometry");
     static_assert(!(DEFER && LIGHT) && !((DEFER || LIGHT) && (MAT || PUNCT || GLASS)), "deferral covers the plain opaque instances");
     static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
     static_assert(EMIT || !PUNCT, "punctual lights are records of the emitter table");
     static_assert(!(FIRST && GLASS), "the G-buffer has no room for a material class: glass frames start from camera rays");
+    static_assert(!EXIT || (DEFER && !EMIT), "the exit test decides deferred sky shadow rays, in frames without an emitter queue");
     __shared__ uint32_t append_lds[2][(EMIT ? 3 : 2) * (kShadeBlock / 64 + 1)];  // double-buffered: see block_append2
     __shared__ ShadeGeomDev s_geoms[GLDS ? kShadeGeomsLds : 1];
     __shared__ MatTexDev s_mats[GLDS && MAT ? kShadeGeomsLds : 1];
@@ -26,6 +30,18 @@
         __syncthreads();
     }
     uint32_t parity = 0;
+    // EXIT: k_shadow_exit's switch, decided where the workgroup starts: every vertex tries its entry while fewer than 2^16 rays have, and
+    // while at least a quarter of those that did were occluded by the entry's leaf; below that every 32nd workgroup's worth of the input
+    // queue does (the trips of the loop below, numbered across the grid), so that the rate stays known at every queue length.
+    // exit_tested / exit_decided: what this wave tried and what its entries occluded (wave-uniform).
+    bool exit_every = false;
+    uint32_t exit_tested = 0u, exit_decided = 0u;
+    ExitHeader xh = {};
+    if constexpr (EXIT) {
+        const unsigned long long tried = x.counters[0], occluded = x.counters[1];
+        exit_every = tried < kExitWarmupTries || 4ull * occluded >= tried;
+        xh = *reinterpret_cast<const ExitHeader*>(reinterpret_cast<const char*>(x.arena) + x.exit_off);
+    }
     // the marginal sky tables (one guide word + one CDF value per row) are the first two links of every light sample's chain of
     // dependent lookups: staged in LDS they cost ~100 cycles each instead of an L1/L2 round trip
     constexpr uint32_t kMargRows = 2048;
@@ -53,6 +69,9 @@
     for (uint32_t it = blockIdx.x * blockDim.x + threadIdx.x; it < n_round + (LIGHT ? gridDim.x * blockDim.x : 0u); it += gridDim.x * blockDim.x) {
         uint32_t i = it;
         bool active = i < n;
+        const bool exit_trip = EXIT && (exit_every || ((it / kShadeBlock) & 31u) == 0u);  // (a workgroup's `it` / kShadeBlock is one number)
+        bool x_tested = false, x_decided = false;  // EXIT: the lane's shadow ray tried its entry; the entry's leaf occluded it
+        uint32_t x_entry = kEmptySlot;
         if constexpr (LIGHT) {  // slot `it` of the shadow queue -> the queue index of a vertex whose ray was not occluded, or no vertex yet
             if (!light_next(a, it, n, n_round, light_held, i, active)) continue;
         }
@@ -206,6 +225,21 @@
             if (!(GLASS && glass_v) && nee) {
                 cosl = dot(N, wl);
                 if (!DEFER && cosl > 0.0f) sky_sample_radiance(a.sc, pick, rad, pl);
+                if constexpr (EXIT) {
+                    // the ray exists (emit_shadow below): its entry is fetched here, as soon as the horizon test has passed, and used behind
+                    // the BSDF sample.  A ray with a non-finite origin or direction tries nothing: k_shadow calls it a miss, and it must
+                    // get there.
+                    if (exit_trip && cosl > 0.0f && pick.sin_theta > 0.0f) {
+                        x_tested = true;
+                        const V3 xo = v3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);  // (the vertex, as below)
+                        const bool finite_ray = fabsf(xo.x) <= kFloatMax && fabsf(xo.y) <= kFloatMax && fabsf(xo.z) <= kFloatMax && fabsf(wl.x) <= kFloatMax &&
+                                                fabsf(wl.y) <= kFloatMax && fabsf(wl.z) <= kFloatMax;
+                        if (finite_ray) {
+                            const uint32_t cell = exit_cell(xh, xo, wl, v3(guarded_inverse(wl.x), guarded_inverse(wl.y), guarded_inverse(wl.z)));
+                            x_entry = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(x.arena) + x.exit_off + sizeof(ExitHeader))[cell];
+                        }
+                    }
+                }
             }
             V3 b1, b2;
             build_orthonormal_basis(N, b1, b2);  // :44
@@ -303,6 +337,18 @@
             if (nee) {
                 // DEFER: pl > 0 exactly when sin_theta > 0, because every texel's density is positive (rt3_scene_set_sky checks it)
                 if (DEFER) emit_shadow = cosl > 0.0f && pick.sin_theta > 0.0f;
+                if constexpr (EXIT) {
+                    // the entry's leaf: 1 .. 8 consecutive records, tested in order until one occludes (the walk's leaf steps)
+                    if (emit_shadow && x_entry != kEmptySlot && (x_entry & 0x80000000u) != 0u) {
+                        const uint32_t cnt = ((x_entry >> 28) & 7u) + 1u;
+                        const float4* rec = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(x.arena) + x.tri_off) + 3 * (size_t)(x_entry & 0x0FFFFFFFu);
+                        const float inv_dd = 1.0f / dot_fma(wl, wl);
+                        Hit best = Hit{kBackgroundDepth, 0.0f, 0.0f, kMiss};
+                        for (uint32_t k = 0; k < cnt && best.prim == kMiss; k++) tri_test_nb(rec[3 * k], rec[3 * k + 1], rec[3 * k + 2], o, wl, inv_dd, kRayTMin, best);
+                        x_decided = best.prim != kMiss;
+                        emit_shadow = !x_decided;
+                    }
+                }
                 else if (cosl > 0.0f && pl > 0.0f) {
                     V3 fv;
                     float scale;
@@ -362,6 +408,10 @@
                 emit_ext = true;                  // :53
             }
         }
+        if constexpr (EXIT) {  // counted here, where the whole wave passes
+            exit_tested += (uint32_t)__popcll(__ballot(x_tested));
+            exit_decided += (uint32_t)__popcll(__ballot(x_decided));
+        }
         if constexpr (LIGHT) {  // k_shadow's expression; one shadow ray per path and launch, so nobody else adds to this slot
             if (emit_shadow) {
                 float4* Lp = reinterpret_cast<float4*>(a.lacc) + pid;
@@ -410,5 +460,25 @@
             a.out_T[S + j] = Tn.y;
             a.out_T[2 * S + j] = Tn.z;
             if (PANE) pane_dist[pid] = dist_n;  // per path, not per queue slot: k_roulette moves records, not paths
+        }
+    }
+    if constexpr (EXIT) {  // the workgroup's counts: its waves' through LDS, then one atomic per counter
+        __shared__ uint32_t s_exit[2 * (kShadeBlock / 64)];
+        if (__lane_id() == 0u) {
+            s_exit[threadIdx.x >> 6] = exit_tested;
+            s_exit[kShadeBlock / 64 + (threadIdx.x >> 6)] = exit_decided;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            unsigned long long nt = 0ull, nd = 0ull;
+            for (int w = 0; w < kShadeBlock / 64; w++) {
+                nt += s_exit[w];
+                nd += s_exit[kShadeBlock / 64 + w];
+            }
+            if (nt) atomicAdd(&x.counters[0], nt);
+            if (nd) {
+                atomicAdd(&x.counters[1], nd);
+                atomicAdd(x.decided, (uint32_t)nd);
+            }
         }
     }

@@ -6,6 +6,7 @@
 
 #include "rt3_hit.hpp"
 #include "rt3_internal.hpp"
+#include "rt3_leaf_test.hpp"
 #include "rt3_math.hpp"
 #include "rt3_surface.hpp"
 
@@ -25,7 +26,6 @@ constexpr uint32_t kTopFlag = 0x40000000u;
 constexpr int kSpill = 64 - kLdsStack;  // kLdsStack + kSpill >= kMaxBvhDepth (checked on the host after the build)
 constexpr uint32_t kMaxSteps = 1u << 20;  // safety bound on traversal steps per ray (a corrupt tree must not hang the GPU)
 
-constexpr uint32_t kEmptySlot = 0xFFFFFFFFu;
 // two-level walk: the boxes of the top tree are widened by kTopPadRel max|o| (the rounding of the slab test itself, which grows with the
 // distance of the origin; the instance boxes carry the rest of the bound)
 constexpr float kTopPadRel = 2.44140625e-4f;  // 2^-12
@@ -46,57 +46,7 @@ __device__ __forceinline__ void cswap(Cand& a, Cand& b) {
     b.ref = sw ? ra : b.ref;
 }
 __device__ __forceinline__ void pin(float4& q) { asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w)); }
-// Watertight ray / triangle test, branch-free (the oracle's tri_test_dd has the argument): edge functions as signed volumes
-// U = d.(B x C), V = d.(C x A), W = d.(A x B) of the vertices relative to the ray origin, every cross-product component two rounded
-// products and a subtraction (NO fma: the file is compiled with -ffp-contract=off), so the two triangles of a shared edge compute
-// the same number for it up to sign and no ray passes between them.  No early-outs: the three loads of a triangle are issued
-// together instead of being sunk behind branches.  Record: {v0.xyz, v1.x} {v1.yz, v2.xy} {v2.z, prim, -, -}.
-__device__ __forceinline__ V3 cross_exact(V3 a, V3 b) { return V3{(a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)}; }
-// MASK: a candidate that would be accepted is, if its record is masked (q2.z = cutoff > 0, q2.w = slot), kept only when its alpha passes
-// (alpha_counts): a masked triangle that fails is not there for this ray.
-// PANE (any hit, the path tracer's own shadow queues): a candidate that would be accepted -- the cutout test included -- on
-// a pane record does not occlude: the ray's contribution pay[0..2] is multiplied by the pane's expected straight-through transmittance
-// (pane_attenuation) and best stays what it is.  A contribution that has become 0 in all three channels ends the ray as occluded.
-__device__ __forceinline__ bool pane_record(float cutoff, uint32_t slot, uint32_t first_slot) { return cutoff != 0.0f ? slot >= first_slot : slot != 0u; }
-// A = transmission (1 - F'(cos_i)) tint at barycentrics (u, v) of primitive prim: hit_finish's shading normal (not face-forwarded) and albedo
-__device__ __forceinline__ V3 pane_attenuation(const PaneDev& p, uint32_t prim, float u, float v, V3 d) {
-    const HitRecord h = hit_fetch(p.sc, prim);
-    const Surface s = hit_finish(p.sc, p.sc.shade_geoms, h, u, v);
-    const GlassDev gl = p.glass[h.rec.w];
-    const float cos_i = fabsf(dot(s.normal, d)) / sqrtf(dot(d, d));
-    return s.albedo * (gl.transmission * pane_pass_fraction(gl.ior, cos_i));
-}
-template <bool MASK = false, bool PANE = false>
-__device__ __forceinline__ void tri_test_nb(float4 q0, float4 q1, float4 q2, V3 o, V3 d, float inv_dd, float tmin, Hit& best, const AlphaDev& alpha = AlphaDev{},
-                                            const PaneDev* pane = nullptr, float* pay0 = nullptr, float* pay1 = nullptr, float* pay2 = nullptr) {
-    const V3 A = v3(q0.x, q0.y, q0.z) - o, B = v3(q0.w, q1.x, q1.y) - o, C = v3(q1.z, q1.w, q2.x) - o;
-    const float U = dot_fma(d, cross_exact(B, C)), V = dot_fma(d, cross_exact(C, A)), W = dot_fma(d, cross_exact(A, B));
-    const float det = U + (V + W);  // the association of T below: equal vertex distances give t exactly
-    const float inv = 1.0f / det;
-    const float w = U * inv, u = V * inv, v = W * inv;
-    const float T = __builtin_fmaf(U, dot_fma(A, d), __builtin_fmaf(V, dot_fma(B, d), W * dot_fma(C, d)));
-    const float t = (T * inv) * inv_dd;
-    const uint32_t prim = __float_as_uint(q2.y);
-    // barycentrics >= -2^-20: a superset of "U, V, W share a sign" (the shared-edge guarantee stands) that also closes T-junctions
-    // and edges of separate meshes that merely coincide, which no watertight test covers
-    constexpr float kEdgeEps = 9.5367431640625e-07f;
-    const bool inside = (w >= -kEdgeEps) & (u >= -kEdgeEps) & (v >= -kEdgeEps);
-    bool ok = (det != 0.0f) & inside & (t > tmin) & ((t < best.t) | ((t == best.t) & (prim < best.prim)));
-    if (MASK && ok && q2.z != 0.0f) ok = alpha_counts(alpha, __float_as_uint(q2.w), q2.z, prim, u, v);
-    if constexpr (PANE) {
-        if (ok && pane_record(q2.z, __float_as_uint(q2.w), pane->first_slot)) {
-            const V3 att = pane_attenuation(*pane, prim, u, v, d);
-            *pay0 *= att.x;
-            *pay1 *= att.y;
-            *pay2 *= att.z;
-            ok = *pay0 == 0.0f && *pay1 == 0.0f && *pay2 == 0.0f;
-        }
-    }
-    best.t = ok ? t : best.t;
-    best.u = ok ? u : best.u;
-    best.v = ok ? v : best.v;
-    best.prim = ok ? prim : best.prim;
-}
+// (the watertight triangle test tri_test_nb and its pane helpers: rt3_leaf_test.hpp)
 
 // Persistent-wave traversal.  The waves of a launch share one pool of rays (chunks of g_pool_chunk, handed out by an atomic
 // cursor).  One ray per lane; a lane that finishes its ray takes the next one from the wave's current chunk (refill once
@@ -317,29 +267,13 @@ __device__ __forceinline__ void trace_stream(const float4* __restrict__ nodes, u
                 r.cur = (LAYOUT == kLayoutWide64Q && use_top) ? kTopFlag : 0u;  // the root: slot 0 of the LDS copy, or node 0
                 if constexpr (EXIT) {
                     if (chunk_exit) {
-                        // where the ray leaves the box: the nearest of the three far planes; the other two coordinates of that point, in cells.
-                        // Whatever the ray is (origin outside, pointing away, zero components, overflow to inf or NaN), the index is clamped
-                        // into the table: fmax / fmin drop a NaN, the integer minimum below is the last word.
+                        // the cell where the ray leaves the box (exit_cell, rt3_leaf_test.hpp).
                         // The box and the grid come from the table's header in the arena, read here with scalar loads (the offset is made
                         // opaque so that they stay in this block: held across the walk they cost the kernel a wave of occupancy).
                         uint32_t hoff = xw->off;
                         asm volatile("" : "+s"(hoff));
                         const ExitHeader e = *reinterpret_cast<const ExitHeader*>(reinterpret_cast<const char*>(nodes) + hoff);
-                        const float tx = ((r.inv.x < 0.0f ? e.lo[0] : e.hi[0]) - r.o.x) * r.inv.x, ty = ((r.inv.y < 0.0f ? e.lo[1] : e.hi[1]) - r.o.y) * r.inv.y,
-                                    tz = ((r.inv.z < 0.0f ? e.lo[2] : e.hi[2]) - r.o.z) * r.inv.z;
-                        const bool ax0 = (tx <= ty) & (tx <= tz), ax1 = !ax0 & (ty <= tz);
-                        const float te = ax0 ? tx : (ax1 ? ty : tz);
-                        const float cx = (__builtin_fmaf(te, r.d.x, r.o.x) - e.lo[0]) * e.scale[0], cy = (__builtin_fmaf(te, r.d.y, r.o.y) - e.lo[1]) * e.scale[1],
-                                    cz = (__builtin_fmaf(te, r.d.z, r.o.z) - e.lo[2]) * e.scale[2];
-                        // axis 0: (u, v) = (y, z); 1: (z, x); 2: (x, y); face = 2 axis + (leaves through the high plane)
-                        const float cu = ax0 ? cy : (ax1 ? cz : cx), cv = ax0 ? cz : (ax1 ? cx : cy);
-                        const float ia = ax0 ? r.inv.x : (ax1 ? r.inv.y : r.inv.z);
-                        const uint32_t face = (ax0 ? 0u : (ax1 ? 2u : 4u)) + (ia < 0.0f ? 0u : 1u);
-                        const float top = (float)(e.R - 1u);
-                        const uint32_t iu = (uint32_t)__builtin_fminf(__builtin_fmaxf(cu, 0.0f), top), iv = (uint32_t)__builtin_fminf(__builtin_fmaxf(cv, 0.0f), top);
-                        uint32_t cell = (face * e.R + iv) * e.R + iu;
-                        cell = cell < e.last ? cell : e.last;
-                        r.cur = kExitFlag | cell;
+                        r.cur = kExitFlag | exit_cell(e, r.o, r.d, r.inv);
                     }
                 }
                 if (TWO) tl_world();
@@ -883,7 +817,7 @@ static void launch_shadow_pane(hipStream_t st, const LbvhResult& bvh, const Trac
 void launch_shadow(hipStream_t st, const LbvhResult& bvh, const TraceLaunch& L) {
     const unsigned grid = grid_for(L.n, kExtendBlock, g_trace_max_blocks);
     if (L.pane != nullptr && L.occluded == nullptr && (bvh.layout == kLayoutWide64Q || bvh.layout == kLayoutTwoLevel)) return launch_shadow_pane(st, bvh, L, grid);
-    if (bvh.exit.on && bvh.exit.off && bvh.exit.counters && bvh.layout == kLayoutWide64Q && bvh.nodes && !L.count && !L.tmax) {  // the plain any-hit walk, table present
+    if (!L.from_root && bvh.exit.on && bvh.exit.off && bvh.exit.counters && bvh.layout == kLayoutWide64Q && bvh.nodes && !L.count && !L.tmax) {  // the plain any-hit walk, table present
         auto launch = [&](auto m) {
             hipLaunchKernelGGL((k_shadow_exit<decltype(m)::value>), dim3(grid), dim3(kExtendBlock), 0, st, bvh.nodes.get(), bvh.tri_off, bvh.top.get(), bvh.n_top, L.rays,
                                L.stride, L.count_ptr, L.n, alpha_arg<decltype(m)::value>(L), L.contrib, L.lacc, L.occluded, L.work_counter, bvh.exit.off, bvh.exit.counters);
