@@ -262,8 +262,8 @@ int rt3_scene_set_material_textures(rt3_ctx *ctx, const rt3_material_textures *m
  *         and the sky); punctual lights do not shine through glass.  (rt3_scene_set_pane_shadows, below, changes this for thin-walled
  *         panes.)  Alpha cutoffs work independently on the same geometry.
  *       - The packed G-buffer has no room for a material class: in a built scene with glass "refrence_mode" needs per-sample camera rays
- *         (rt3_camera_set_lens; {0, f, 0} is the per-sample pinhole) and returns RT3_E_STATE without, as does "adaptive" always; with
- *         samples * bounces * 8 > 2^30 it returns RT3_E_INVALID (the vertices' RNG indices would reach the glass draws').  "gbuffer",
+ *         (rt3_camera_set_lens; {0, f, 0} is the per-sample pinhole) and returns RT3_E_STATE without, as does "adaptive" ("adaptive" takes
+ *         a lens only under rt3_adaptive_set_coverage); with samples * bounces * 8 > 2^30 either returns RT3_E_INVALID (the vertices' RNG indices would reach the glass draws').  "gbuffer",
  *         "denoise", "temporal", "motion", the probe passes and rt3_trace_rays see glass as the opaque surface its material describes.
  *      Works in both instance modes, after rt3_accel_import and across rt3_accel_refit.  A value that is not finite, a transmission outside
  *      [0, 1], ior < 1, thin_walled > 1, reserved != 0 or a wrong n is RT3_E_INVALID and changes nothing.  Takes effect at the next
@@ -623,7 +623,17 @@ int rt3_temporal_set_motion_input(rt3_ctx *ctx, uint32_t motion_image);
  *      step < 1, a threshold that is not finite or negative, a dark that is not finite or not positive, dilate > 1 or any flag bit (none
  *      is defined).
  *      rt3_adaptive_info (any pointer may be NULL): of the last "adaptive" launch, the rounds run, the first-vertex paths traced (the sum
- *      of n over this rank's foreground pixels) and the pixels that reached the cap. ---- */
+ *      of n over this rank's foreground pixels; in coverage mode over all of this rank's pixels) and the pixels that reached the cap.
+ *      Coverage mode (rt3_adaptive_set_coverage; 0, the default: "adaptive" refuses a lens).  A mode of the context that survives scene
+ *      changes; on other than 0 or 1 is RT3_E_INVALID and changes nothing.  It matters only while a lens is set (rt3_camera_set_lens): then
+ *      the pass starts every sample from its own camera ray, as "refrence_mode" does, and "foreground pixel" above reads "pixel of this
+ *      rank's list": round 0 lists them all, in the list's order, without a depth test (and without a device-to-host read); pixels outside
+ *      the window and pixels of other ranks still count as passing; every listed pixel gets Light and Moments at the end, one whose centre
+ *      sees the background included, so n is never 0 on an owned pixel.  gbuffer and gbuffer_depth stay bound and validated and are not
+ *      read.  A pixel that stopped at n holds the bits "refrence_mode" with the same lens writes for it at samples = n.  Glass, pane
+ *      shadows and roulette work as there.  "refrence_mode"'s range rules hold with the cap as `samples`: RT3_E_INVALID for
+ *      cap * bounces * 8 > 2^31, and > 2^30 in a built scene with glass.  Without a lens the mode is inert: the pass above, and
+ *      RT3_E_STATE for a scene with glass.  With a lens and the mode off: RT3_E_STATE. ---- */
 typedef struct rt3_adaptive_params {
     uint32_t min_samples; /* round 0; >= 2 (the variance divides by n - 1) */
     uint32_t step;        /* samples per later round; >= 1 */
@@ -634,6 +644,8 @@ typedef struct rt3_adaptive_params {
 } rt3_adaptive_params;
 int rt3_adaptive_set_params(rt3_ctx *ctx, const rt3_adaptive_params *params);
 int rt3_adaptive_info(rt3_ctx *ctx, uint32_t *rounds, uint64_t *paths_traced, uint32_t *pixels_capped);
+int rt3_adaptive_set_coverage(rt3_ctx *ctx, int on);
+int rt3_adaptive_get_coverage(rt3_ctx *ctx, int *on);
 /* ---- per-sample camera rays: pixel-filter antialiasing and a thin lens.  No reference counterpart; DESIGN.md section 4m.  By default every
  *      sample of a pixel starts at the G-buffer's hit, the one through the pixel centre.  With a lens set, "refrence_mode" gives every sample
  *      its own camera ray instead: sample s (absolute index, 0 .. samples-1) of pixel (px, py) draws four numbers at the RNG indices
@@ -649,8 +661,8 @@ int rt3_adaptive_info(rt3_ctx *ctx, uint32_t *rounds, uint64_t *paths_traced, ui
  *      default.  The state lives in the context; nothing is rebuilt.  RT3_E_INVALID (nothing changed) for a value that is not finite, an
  *      aperture_radius < 0, a pixel_jitter outside [0, 1], a focus_distance <= 0 with aperture_radius > 0, or reserved != 0.
  *      Coupled passes while a lens is set: "postprocess" takes every pixel from In (the Depth == background branch would put the pinhole sky
- *      over half of each antialiased silhouette); "adaptive" returns RT3_E_STATE (it selects pixels by G-buffer depth); "refrence_mode" with
- *      samples * bounces * 8 > 2^31 returns RT3_E_INVALID (the vertices' RNG indices would reach the camera's).  "gbuffer", "denoise",
+ *      over half of each antialiased silhouette); "adaptive" returns RT3_E_STATE (it selects pixels by G-buffer depth) unless
+ *      rt3_adaptive_set_coverage lets it take every pixel; "refrence_mode", and "adaptive" then, with samples * bounces * 8 > 2^31 return RT3_E_INVALID (the vertices' RNG indices would reach the camera's).  "gbuffer", "denoise",
  *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres, so guiding a
  *      depth-of-field frame by it is not supported.
  *      rt3_camera_get_lens (either pointer may be NULL): the parameters last set (the defaults {0, 1, 1, 0} before any) and whether on. ---- */

@@ -52,7 +52,7 @@ EXPORTS = [
     "rt3_comm_version", "rt3_comm_unique_id", "rt3_comm_init", "rt3_comm_destroy", "rt3_gather_tiles", "rt3_gather_layout", "rt3_gather_unpack",
     "rt3_pass_launch", "rt3_denoise_set_params", "rt3_denoise_set_variance_input", "rt3_temporal_set_prev_view", "rt3_temporal_set_params",
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
-    "rt3_adaptive_set_params", "rt3_adaptive_info",
+    "rt3_adaptive_set_params", "rt3_adaptive_info", "rt3_adaptive_set_coverage", "rt3_adaptive_get_coverage",
     "rt3_camera_set_lens", "rt3_camera_get_lens",
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses",
@@ -232,6 +232,8 @@ def load():
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
         "rt3_adaptive_set_params": (i32, [vp, C.POINTER(AdaptiveParams)]),
         "rt3_adaptive_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), pu32]),
+        "rt3_adaptive_set_coverage": (i32, [vp, i32]),
+        "rt3_adaptive_get_coverage": (i32, [vp, C.POINTER(i32)]),
         "rt3_camera_set_lens": (i32, [vp, C.POINTER(LensParams)]),
         "rt3_camera_get_lens": (i32, [vp, C.POINTER(LensParams), C.POINTER(i32)]),
         "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),

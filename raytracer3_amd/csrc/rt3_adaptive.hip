@@ -187,6 +187,31 @@ __global__ void k_ad_finalise(const uint32_t* __restrict__ pixels, uint32_t npix
     }
 }
 
+// Coverage mode (rt3_adaptive_set_coverage): k_ad_finalise for every listed pixel.  A pixel whose centre sees the background may be partly
+// covered and was sampled like any other, so there is no depth test; the blend is k_accumulate_lens's.  Streaming: 4 + 16 + 8 (+ 16) bytes
+// read and 32 written per pixel, sums and mom in window order under a list of row-major tiles; no LDS.
+__global__ __launch_bounds__(256) void k_ad_finalise_all(const uint32_t* __restrict__ pixels, uint32_t npix, uint32_t width, float blendfactor,
+                                                         uint32_t cap, const float4* __restrict__ sums, const float2* __restrict__ mom,
+                                                         float4* __restrict__ light, const float4* __restrict__ prev, float4* __restrict__ moments) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        const uint32_t xy = pixels[i];
+        const size_t pi = (size_t)(xy >> 16) * width + (xy & 0xFFFFu);
+        const float4 sv = sums[pi];
+        const float2 mv = mom[pi];
+        const uint32_t n = __float_as_uint(sv.w);
+        const float fs = (float)n;
+        const float r = sv.x / fs, gg = sv.y / fs, bb = sv.z / fs;
+        if (blendfactor >= 1.0f) {
+            light[pi] = make_float4(r, gg, bb, 0.0f);
+        } else {
+            const float4 pv = prev[pi];
+            const float bf = blendfactor;
+            light[pi] = make_float4(pv.x + (r - pv.x) * bf, pv.y + (gg - pv.y) * bf, pv.z + (bb - pv.z) * bf, 0.0f);
+        }
+        moments[pi] = make_float4(mv.x, mv.y, fs, n < cap ? 1.0f : 0.0f);
+    }
+}
+
 }  // namespace
 
 void adaptive_plan(uint32_t W, uint32_t H, uint32_t npix, BufLayout& plan, AdaptiveScratch* s) {
@@ -218,6 +243,11 @@ void launch_adaptive_compact(hipStream_t st, const uint2* in_bn, uint32_t n_in, 
 void launch_adaptive_finalise(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth, float blendfactor,
                               uint32_t cap, const AdaptiveScratch& s, void* light, const void* prev, void* moments) {
     hipLaunchKernelGGL(k_ad_finalise, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, pixels, npix, width, depth, blendfactor, cap, s.sums, s.mom,
+                       (float4*)light, (const float4*)prev, (float4*)moments);
+}
+void launch_adaptive_finalise_all(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, float blendfactor, uint32_t cap,
+                                  const AdaptiveScratch& s, void* light, const void* prev, void* moments) {
+    hipLaunchKernelGGL(k_ad_finalise_all, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, st, pixels, npix, width, blendfactor, cap, s.sums, s.mom,
                        (float4*)light, (const float4*)prev, (float4*)moments);
 }
 

@@ -267,9 +267,11 @@ struct rt3_ctx {
         rt3::DevBuf<uint32_t> d_slot;
     } motion;
     // rt3_passes.hip: "adaptive" pass: parameters (rt3_adaptive_set_params), the grow-only scratch its state and lists are carved from, and
-    // what the last launch did (rt3_adaptive_info)
+    // what the last launch did (rt3_adaptive_info); `coverage` (rt3_adaptive_set_coverage): with a lens set the pass lists every pixel of the
+    // rank instead of refusing; off by default, untouched by scene changes
     struct Adaptive {
         rt3_adaptive_params params = rt3::kAdaptiveDefaults;
+        bool coverage = false;
         rt3::DevBuf<char> scratch;
         uint32_t rounds = 0, pixels_capped = 0;
         uint64_t paths_traced = 0;

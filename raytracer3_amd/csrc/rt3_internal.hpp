@@ -587,6 +587,9 @@ void launch_adaptive_compact(hipStream_t st, const uint2* in_bn, uint32_t n_in, 
                              int out);
 void launch_adaptive_finalise(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth, float blendfactor,
                               uint32_t cap, const AdaptiveScratch& s, void* light, const void* prev, void* moments);
+// coverage mode (rt3_adaptive_set_coverage): the same for every listed pixel, whatever the G-buffer's depth says
+void launch_adaptive_finalise_all(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, float blendfactor, uint32_t cap,
+                                  const AdaptiveScratch& s, void* light, const void* prev, void* moments);
 
 hipError_t lbvh_make_top(hipStream_t st, const float4* nodes, uint32_t n_nodes, DevBuf<float4>& top, uint32_t* n_top);
 

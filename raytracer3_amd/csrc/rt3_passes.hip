@@ -504,14 +504,23 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     const uint32_t cap = g->samples, B = g->bounces;
     c->adaptive.rounds = c->adaptive.pixels_capped = 0;
     c->adaptive.paths_traced = 0;
-    if (c->lens.on)
+    // coverage mode (rt3_adaptive_set_coverage): with a lens every pixel of the rank's list is a pixel of round 0
+    const bool cover = c->lens.on && c->adaptive.coverage;
+    if (c->lens.on && !cover)
         return fail(c, RT3_E_STATE, "adaptive: not with a lens set (rt3_camera_set_lens): the pass selects pixels by G-buffer depth, which knows nothing "
-                                    "of partly covered pixels; switch the lens off (NULL) or use refrence_mode");
-    if (c->accel.has_glass)
+                                    "of partly covered pixels; switch the lens off (NULL), use refrence_mode, or let the pass take every pixel with "
+                                    "rt3_adaptive_set_coverage");
+    if (c->accel.has_glass && !cover)
         return fail(c, RT3_E_STATE, "adaptive: not for a scene with glass (rt3_scene_set_transmission): glass needs per-sample camera rays "
                                     "(rt3_camera_set_lens), which this pass does not take; use refrence_mode");
     if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
+    if (cover) {  // refrence_mode's range rules, the cap as `samples`
+        if ((uint64_t)cap * B * 8u > (1ull << 31))
+            return fail(c, RT3_E_INVALID, "adaptive with a lens: samples * bounces * 8 may not exceed 2^31 (the camera's RNG indices start there)");
+        if (c->accel.has_glass && (uint64_t)cap * B * 8u > (1ull << 30))
+            return fail(c, RT3_E_INVALID, "adaptive with glass: samples * bounces * 8 may not exceed 2^30 (the glass draws' RNG indices start there)");
+    }
     if (int r = roulette_begin(c, "adaptive", cap, B)) return r;
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
@@ -532,16 +541,27 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
         HIPC(c, hipStreamSynchronize(c->stream));
         return (int)RT3_OK;
     };
-    // round 0's list: the foreground pixels of the rank's list, in its order
+    // round 0's list: the foreground pixels of the rank's list, in its order; in coverage mode the rank's list itself, whose length the
+    // host knows
     uint32_t n_act = 0;
     int cur = 0;
+    const uint32_t* list_xy = s.xy[cur];
+    const uint2* list_bn = s.bn[cur];
     {
         ScopedTimer t(c, CAT_OTHER);
         HIPC(c, hipMemsetAsync(s.mask, 0, (size_t)W * H, c->stream));
-        launch_adaptive_init(c->stream, pl->dev.get(), pl->count, W, depth, s, mo->ptr);
-        launch_adaptive_compact(c->stream, pl->dev_bn.get(), pl->count, W, H, 0u, s, cur);
+        if (!cover) {
+            launch_adaptive_init(c->stream, pl->dev.get(), pl->count, W, depth, s, mo->ptr);
+            launch_adaptive_compact(c->stream, pl->dev_bn.get(), pl->count, W, H, 0u, s, cur);
+        }
     }
-    if (int r = list_length(&n_act)) return r;
+    if (cover) {
+        n_act = pl->count;
+        list_xy = pl->dev.get();
+        list_bn = pl->dev_bn.get();
+    } else if (int r = list_length(&n_act)) {
+        return r;
+    }
     const uint32_t n_fg = n_act;
     if (n_fg) {
         // the queues are sized once, for the largest batch of any round: round 0's list is the longest
@@ -553,6 +573,8 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     PathSetup ps;
     if (n_fg)
         if (int r = path_setup(c, g, &ps)) return r;
+    ps.lens_on = cover;
+    ps.lens = lens_dev(c);
     uint32_t n = 0;  // the sample count of every active pixel
     while (n_act) {
         const uint32_t ns = n == 0 ? std::min(p.min_samples, cap) : std::min(p.step, cap - n);
@@ -561,9 +583,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
         sb = (uint32_t)std::min<uint64_t>(sb, c->work.cap / n_act);  // (a shorter list may not take more samples per batch than the queues hold)
         for (uint32_t s0 = 0; s0 < ns; s0 += sb) {
             const uint32_t nsb = std::min(sb, ns - s0);
-            if (int r = trace_batch(c, ps, W, gb, dp, s.xy[cur], s.bn[cur], n_act, n + s0, nsb)) return r;
+            if (int r = trace_batch(c, ps, W, gb, dp, list_xy, list_bn, n_act, n + s0, nsb)) return r;
             ScopedTimer t(c, CAT_OTHER);
-            launch_adaptive_accumulate(c->stream, s.xy[cur], n_act, W, c->work.lacc.get(), nsb, n + s0 == 0, n + s0 + nsb, s);
+            launch_adaptive_accumulate(c->stream, list_xy, n_act, W, c->work.lacc.get(), nsb, n + s0 == 0, n + s0 + nsb, s);
         }
         n += ns;
         c->adaptive.rounds++;
@@ -574,15 +596,20 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
         }
         {
             ScopedTimer t(c, CAT_OTHER);
-            launch_adaptive_test(c->stream, s.xy[cur], n_act, W, p.threshold, p.dark, s);
-            launch_adaptive_compact(c->stream, s.bn[cur], n_act, W, H, p.dilate, s, cur ^ 1);
+            launch_adaptive_test(c->stream, list_xy, n_act, W, p.threshold, p.dark, s);
+            launch_adaptive_compact(c->stream, list_bn, n_act, W, H, p.dilate, s, cur ^ 1);
         }
         cur ^= 1;
+        list_xy = s.xy[cur];
+        list_bn = s.bn[cur];
         if (int r = list_length(&n_act)) return r;
     }
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_adaptive_finalise(c->stream, pl->dev.get(), pl->count, W, depth, g->blendfactor, cap, s, li->ptr, pv->ptr, mo->ptr);
+        if (cover)
+            launch_adaptive_finalise_all(c->stream, pl->dev.get(), pl->count, W, g->blendfactor, cap, s, li->ptr, pv->ptr, mo->ptr);
+        else
+            launch_adaptive_finalise(c->stream, pl->dev.get(), pl->count, W, depth, g->blendfactor, cap, s, li->ptr, pv->ptr, mo->ptr);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -910,6 +937,18 @@ int rt3_adaptive_set_params(rt3_ctx* c, const rt3_adaptive_params* p) {
     if (p->dilate > 1) return fail(c, RT3_E_INVALID, "adaptive params: dilate must be 0 or 1");
     if (p->flags) return fail(c, RT3_E_INVALID, "adaptive params: unknown flag bits");
     c->adaptive.params = *p;
+    return RT3_OK;
+}
+// coverage mode: the context's, read by the next "adaptive" launch; scene changes leave it
+int rt3_adaptive_set_coverage(rt3_ctx* c, int on) {
+    if (!c) return RT3_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, RT3_E_INVALID, "adaptive coverage: the mode is 0 or 1");
+    c->adaptive.coverage = on != 0;
+    return RT3_OK;
+}
+int rt3_adaptive_get_coverage(rt3_ctx* c, int* on) {
+    if (!c || !on) return fail(c, RT3_E_INVALID, "adaptive coverage: NULL");
+    *on = c->adaptive.coverage ? 1 : 0;
     return RT3_OK;
 }
 int rt3_adaptive_info(rt3_ctx* c, uint32_t* rounds, uint64_t* paths_traced, uint32_t* pixels_capped) {

@@ -107,8 +107,16 @@ class Context {
     void adaptive_info(uint32_t* rounds, uint64_t* paths_traced, uint32_t* pixels_capped) const {
         check(rt3_adaptive_info(ctx_, rounds, paths_traced, pixels_capped), "rt3_adaptive_info");
     }
+    // coverage mode: with a lens set "adaptive" lists every pixel of the rank instead of refusing; off by default
+    void set_adaptive_coverage(bool on) const { check(rt3_adaptive_set_coverage(ctx_, on ? 1 : 0), "rt3_adaptive_set_coverage"); }
+    bool adaptive_coverage() const {
+        int on = 0;
+        check(rt3_adaptive_get_coverage(ctx_, &on), "rt3_adaptive_get_coverage");
+        return on != 0;
+    }
     // per-sample camera rays (no reference counterpart): antialiasing over the pixel and a thin lens for the
     // "refrence_mode" frames that follow; nullptr = off, the default.  While set, "postprocess" shows In everywhere and "adaptive" is refused
+    // unless set_adaptive_coverage(true)
     void set_lens(const rt3_lens_params* p) const { check(rt3_camera_set_lens(ctx_, p), "rt3_camera_set_lens"); }
     void set_lens(float aperture, float focus, float jitter = 1.0f) const {
         const rt3_lens_params p = {aperture, focus, jitter, 0u};

@@ -409,6 +409,16 @@ class Context:
         self.check(self.lib.rt3_adaptive_info(self.h, C.byref(r), C.byref(p), C.byref(k)))
         return r.value, p.value, k.value
 
+    def adaptive_set_coverage(self, on):
+        """coverage mode of the "adaptive" pass (rt3_adaptive_set_coverage): with a lens set the pass lists every pixel
+        of the rank and starts each sample from its own camera ray, instead of refusing.  A mode of the context: it outlives scene changes."""
+        self.check(self.lib.rt3_adaptive_set_coverage(self.h, int(on)))
+
+    def adaptive_coverage(self):
+        on = C.c_int()
+        self.check(self.lib.rt3_adaptive_get_coverage(self.h, C.byref(on)))
+        return bool(on.value)
+
     def set_lens(self, params=None, **kw):
         """per-sample camera rays (rt3_camera_set_lens): an L.LensParams, or its fields as keywords; nothing = off"""
         if params is None and kw:

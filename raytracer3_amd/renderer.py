@@ -325,12 +325,18 @@ class PathTracer:
         """Per-sample camera rays for the frames that follow (ctx.set_lens): `jitter` is the width in pixels of the
         box each sample's film point is drawn from (1 = antialiasing over the whole pixel), `aperture` the lens radius in world units
         (0 = pinhole), `focus` the view depth of the plane of focus.  set_lens(None) switches back to one primary hit per pixel.  With a
-        lens, "postprocess" shows `Light` everywhere and adaptive frames are refused."""
+        lens, "postprocess" shows `Light` everywhere, and adaptive frames are refused unless set_adaptive_coverage(True)."""
         self._glass_lens = False  # the caller's choice from here on
         if aperture is None:
             self.ctx.set_lens(None)
         else:
             self.ctx.set_lens(L.LensParams(aperture, focus, jitter))
+
+    def set_adaptive_coverage(self, on=True):
+        """Coverage mode of adaptive frames (ctx.adaptive_set_coverage): with a lens set -- by set_lens, or by set_scene
+        for a scene with glass -- render(g, adaptive=...) samples every pixel of the rank to the threshold, each sample from its own camera
+        ray, instead of being refused.  Off by default; render() never switches it on.  Without a lens it changes nothing."""
+        self.ctx.adaptive_set_coverage(bool(on))
 
     def set_roulette(self, start_bounce=2, min_survival=0.0625):
         """Russian roulette for the frames that follow (ctx.set_roulette): the extension rays of vertices
@@ -480,11 +486,13 @@ class PathTracer:
         return self._download("history"), self._download("moments")
 
     def adaptive_moments(self):
-        """Moments of the "adaptive" pass: {S1, S2, n, 1 = stopped before the cap} per foreground pixel, 0 for background"""
+        """Moments of the "adaptive" pass: {S1, S2, n, 1 = stopped before the cap} per foreground pixel, 0 for background; in coverage mode
+        (set_adaptive_coverage with a lens) per pixel of this rank, background included"""
         return self._download("adaptive_moments")
 
     def sample_counts(self):
-        """the samples each pixel got in the last adaptive frame (H, W) uint32; 0 = background"""
+        """the samples each pixel got in the last adaptive frame (H, W) uint32; 0 = background, or, in coverage mode (set_adaptive_coverage with a
+        lens), only a pixel of another rank"""
         return self.adaptive_moments()[..., 2].astype(np.uint32)
 
     def motion(self):

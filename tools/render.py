@@ -17,6 +17,8 @@
                          0.05; --spp-map writes the sample counts as a grey PNG, white = the cap)
   python tools/render.py --scene atrium --size 1920x1080 --spp 256 --aa --aperture 0.05 --focus 8 --out atrium_dof.png
                          (per-sample camera rays, DESIGN.md section 4m: --aa antialiases over the pixel, --aperture / --focus add a thin lens)
+  python tools/render.py --scene glass_cornell --size 1920x1080 --spp 256 --bounces 8 --adaptive 0.3 --spp-map glass_spp.png --out glass_adaptive.png
+                         (--adaptive with --aa, --aperture or a scene with glass: the pass's coverage mode, every pixel sampled to the threshold)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -102,8 +104,8 @@ def main():
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
     if args.aa or args.aperture > 0.0:
-        if args.adaptive is not None or args.temporal or args.denoise:
-            ap.error("--aa / --aperture render plain frames: the adaptive pass refuses a lens, and the temporal and denoise passes are guided by the pinhole G-buffer")
+        if args.temporal or args.denoise:
+            ap.error("--aa / --aperture do not combine with --temporal or --denoise: those passes are guided by the pinhole G-buffer")
         pt.set_lens(args.aperture, args.focus, 1.0)
     if args.roulette is not None:
         pt.set_roulette(args.roulette)
@@ -112,6 +114,8 @@ def main():
         if args.temporal:
             ap.error("--adaptive renders single frames: it does not combine with --temporal")
         adaptive = L.AdaptiveParams(min_samples=args.min_spp, step=args.step, threshold=args.adaptive)
+        if pt.ctx.get_lens()[1]:  # --aa, --aperture or a scene with glass: every pixel is sampled to the threshold
+            pt.set_adaptive_coverage(True)
     cam = Camera(cam_kw["position"], cam_kw["direction"], math.radians(cam_kw["fov_deg"]), W / H)
     history, t0 = [], time.perf_counter()
     for k in range(args.temporal):  # the camera slides and turns by a few pixels per frame; every frame reprojects the one before
@@ -143,9 +147,9 @@ def main():
     if adaptive is not None:  # of the last pass
         n = pt.sample_counts()
         rounds, paths, capped = pt.ctx.adaptive_info()
-        fgn = n[n > 0]
+        fgn = n[n > 0]  # (with a lens: every pixel)
         print(f"adaptive: threshold {args.adaptive}, cap {args.spp}: {rounds} rounds, {paths / 1e6:.1f} M paths, mean {fgn.mean() if fgn.size else 0:.1f} spp over "
-              f"{fgn.size} foreground pixels, {capped} at the cap")
+              f"{fgn.size} {'pixels' if pt.ctx.get_lens()[1] else 'foreground pixels'}, {capped} at the cap")
         if args.spp_map:
             Path(args.spp_map).parent.mkdir(parents=True, exist_ok=True)
             Image.fromarray((n.astype(np.float64) * (255.0 / max(1, args.spp)) + 0.5).astype(np.uint8)).save(args.spp_map)
