@@ -750,6 +750,16 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      {o xyz, pdf, d xyz, path id, T rgb}; path id = sample_in_batch * npix + pixel index.  out: {new count, tested, ended}, then n records:
  *      the words the caller put there are the destination queue's contents before the launch, so on return the first `count` records are
  *      the survivors and the words behind them are the caller's unless the kernel wrote out of place.
+ *      35 the list compaction of the "adaptive" pass (rt3_adaptive_set_params: count, scan, scatter) on a caller-made list of n records and a
+ *      caller-made mask, with the pass's own scratch layout and launch shapes; reads no context state.  in: the header {W, H, dilate (0 / 1),
+ *      n}, then the window-space mask, W H bytes, row-major (byte y W + x; non-zero: the pixel's test failed), padded with zero bytes to a
+ *      whole word, then n records of 2 words {x | y << 16, blue-noise word}.  out: {count, n_blocks = ceil(n / 2048)}, then the n_blocks
+ *      exclusive offsets the scan left (offset b: what the list's entries before 2048 b keep), then n words and behind them n records of 2
+ *      words: the destination's xy list and {xy, blue-noise} list.  As with op 34 the caller's words in both are the destination's contents
+ *      before the launch: on return the first `count` entries of each are the kept ones, in the list's order, and the rest is the caller's
+ *      unless a kernel wrote out of place.  An entry is kept when its pixel's mask byte is non-zero or, with dilate, any byte of the 3 x 3
+ *      neighbourhood inside the window is.  RT3_E_INVALID, before anything is launched, for W or H outside 1 .. 65535, dilate > 1, n = 0,
+ *      n > 2^24, a header n that is not the call's n, or a record with x >= W or y >= H.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

@@ -36,6 +36,8 @@ SELFTEST_LENS = 31  # rt3_selftest_eval op: {proj_inverse, view_inverse, window,
 SELFTEST_GLASS = 32  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, u} (9 words) -> {event (u32), direction, F} (5), the glass function
 SELFTEST_ROULETTE = 33  # rt3_selftest_eval op: {T rgb, min_survival, u} (5 words) -> {survived (u32), T' rgb, q_g} (5), the roulette rule
 SELFTEST_ROULETTE_QUEUE = 34  # rt3_selftest_eval op: k_roulette on a caller-made queue (Context.selftest_roulette_queue)
+SELFTEST_ADAPTIVE_COMPACT = 35  # rt3_selftest_eval op: the "adaptive" pass's list compaction on a caller-made list and mask (Context.selftest_adaptive_compact)
+ADAPTIVE_TILE = 2048  # list entries per compaction block (op 35 returns one offset per tile)
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",

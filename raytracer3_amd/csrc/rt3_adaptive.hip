@@ -16,6 +16,7 @@ namespace {
 constexpr int kAdBlock = 256, kAdWaves = kAdBlock / 64;
 constexpr int kAdItems = 8;                       // list entries per thread of a compaction block
 constexpr uint32_t kAdTile = kAdBlock * kAdItems;  // ... and per block
+static_assert(kAdTile == kAdaptiveTile, "rt3_internal.hpp states the tile for whoever reads block_count");
 
 // Round 0's input: foreground pixels of the rank's list count as "failed" (so the first compaction keeps exactly them); a background pixel
 // gets Moments = 0 and is never listed.  `mask` was zeroed for the whole window before: pixels of other ranks stay 0.

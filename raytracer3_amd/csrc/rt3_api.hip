@@ -433,8 +433,49 @@ static int selftest_roulette_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, u
     return RT3_OK;
 }
 
+// Self-test op 35: the "adaptive" pass's list compaction (count, scan, scatter) on a caller-made list of n records and a caller-made mask,
+// through adaptive_plan and launch_adaptive_compact: the scratch layout and the launch shapes are the pass's.  in: {W, H, dilate, n}, the
+// W H mask bytes (row-major, padded to whole words), n records {x | y << 16, blue-noise word}.  out: {count, n_blocks}, the n_blocks
+// exclusive block offsets, n xy words, n bn records: the caller's words go into the destination lists before the launch (op 34's rule).
+static int selftest_adaptive_compact(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const uint32_t W = in[0], H = in[1], dilate = in[2];
+    if (W == 0 || W > 65535 || H == 0 || H > 65535 || dilate > 1 || n == 0 || n > (1u << 24) || in[3] != n)
+        return fail(c, RT3_E_INVALID, "selftest: adaptive compaction header: W and H 1..65535, dilate 0 or 1, 1..2^24 records, as many as the call's n");
+    const size_t win = (size_t)W * H;
+    const uint32_t* rec = in + kSelftestCompactHeader + (win + 3) / 4;
+    for (uint32_t i = 0; i < n; i++)  // ad_keep indexes the mask with the entry's pixel: nothing is launched that would read outside it
+        if ((rec[2 * (size_t)i] & 0xFFFFu) >= W || (rec[2 * (size_t)i] >> 16) >= H)
+            return fail(c, RT3_E_INVALID, "selftest: adaptive compaction record " + std::to_string(i) + " names a pixel outside the window");
+    HIPC(c, hipSetDevice(c->device));
+    AdaptiveScratch s;
+    BufLayout plan;
+    adaptive_plan(W, H, n, plan, &s);
+    DevBuf<char> scratch;  // the op's own: the context's may be in use
+    HIPC(c, scratch.alloc_bytes(plan.bytes()));
+    HIPC(c, plan.carve(scratch));
+    const uint32_t n_blocks = (n + kAdaptiveTile - 1) / kAdaptiveTile;
+    uint32_t* o_off = out + 2;
+    uint32_t* o_xy = o_off + n_blocks;
+    uint32_t* o_bn = o_xy + n;
+    HIPC(c, hipMemset(scratch.get(), 0xA5, plan.bytes()));  // a count or an offset the kernels do not write is not a small number
+    HIPC(c, hipMemcpy(s.mask, in + kSelftestCompactHeader, win, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(s.bn[0], rec, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(s.xy[1], o_xy, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(s.bn[1], o_bn, (size_t)n * 8, hipMemcpyHostToDevice));
+    launch_adaptive_compact(c->stream, s.bn[0], n, W, H, dilate, s, 1);  // a later round's: from list 0 into list 1
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpy(out, s.count, 4, hipMemcpyDeviceToHost));
+    out[1] = n_blocks;
+    HIPC(c, hipMemcpy(o_off, s.block_count, (size_t)n_blocks * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(o_xy, s.xy[1], (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(o_bn, s.bn[1], (size_t)n * 8, hipMemcpyDeviceToHost));
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 35 && c && in && out) return selftest_adaptive_compact(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 34 && c && in && out) return selftest_roulette_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));  // no rows of one width
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
     if ((op == 25 || op == 26) && !c->scene.d_sky) return fail(c, RT3_E_STATE, "selftest: the sky ops need a sky (rt3_scene_set_sky)");

@@ -573,6 +573,9 @@ struct AdaptiveScratch {
     uint32_t* count;        // the length of the list the last compaction wrote
 };
 void adaptive_plan(uint32_t W, uint32_t H, uint32_t npix, BufLayout& plan, AdaptiveScratch* s);
+constexpr uint32_t kAdaptiveTile = 2048;  // list entries per compaction block: s.block_count has one word per tile of the list
+// self-test op 35: the compaction on a caller-made list; header words, then the mask bytes padded to whole words, then the records
+constexpr uint32_t kSelftestCompactHeader = 4;
 // foreground pixels of the rank's list: mask = 1 (s.mask zeroed for the whole window before); background ones: Moments = 0
 void launch_adaptive_init(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth, const AdaptiveScratch& s,
                           void* moments);

@@ -465,6 +465,28 @@ class Context:
         self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ROULETTE_QUEUE, inp.ctypes.data, n, out.ctypes.data))
         return int(out[0]), int(out[1]), int(out[2]), out[3:].reshape(n, 11)
 
+    def selftest_adaptive_compact(self, W, H, dilate, mask, records, prefill_xy=None, prefill_bn=None):
+        """Self-test op 35: the "adaptive" pass's list compaction on the list `records` (n, 2) of 32-bit words {x | y << 16, blue-noise word}
+        under the window-space `mask` (H, W) of bytes; `prefill_xy` (n,) and `prefill_bn` (n, 2): the destination lists' words before the
+        launch (zeros without).  Returns (count, the exclusive block offsets (n_blocks,), the destination xy list (n,), the destination
+        {xy, blue-noise} list (n, 2)), all uint32."""
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        records = np.ascontiguousarray(records, np.uint32).reshape(-1, 2)
+        n = len(records)
+        n_blocks = -(-n // L.ADAPTIVE_TILE)
+        inp = np.zeros(4 + -(-len(mask) // 4) + 2 * n, np.uint32)
+        inp[:4] = W, H, dilate, n
+        inp[4:].view(np.uint8)[:len(mask)] = mask
+        inp[len(inp) - 2 * n:] = records.reshape(-1)
+        out = np.zeros(2 + n_blocks + 3 * n, np.uint32)
+        if prefill_xy is not None:
+            out[2 + n_blocks:2 + n_blocks + n] = np.ascontiguousarray(prefill_xy, np.uint32).reshape(-1)
+        if prefill_bn is not None:
+            out[2 + n_blocks + n:] = np.ascontiguousarray(prefill_bn, np.uint32).reshape(-1)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ADAPTIVE_COMPACT, inp.ctypes.data, n, out.ctypes.data))
+        assert int(out[1]) == n_blocks
+        return int(out[0]), out[2:2 + n_blocks], out[2 + n_blocks:2 + n_blocks + n], out[2 + n_blocks + n:].reshape(n, 2)
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

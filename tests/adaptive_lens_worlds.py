@@ -2,7 +2,8 @@
 tests/test_adaptive_lens_cpu.py, tests/test_adaptive_lens.py).
 
 World A: the fixture of tests/adaptive_worlds.py (scenes.cornell() seen from outside, 67 x 45: no multiple of 64 or 256, two tiles of the
-partition, 3015 list entries across one 2048-entry compaction block boundary) through a thin lens focused on the wall the camera faces.
+partition; its 3015 list entries make two 2048-entry compaction blocks, which is all of the compaction these frames exercise: the scan's
+wave and chunk boundaries are tests/test_adaptive_compaction.py's) through a thin lens focused on the wall the camera faces.
 With a lens every pixel is listed: the background around the wall is the small sky, antialiased along the wall's outline.
 World B: glass_worlds.glass_room() (a solid glass block and a thin-walled pane in integrator_worlds' open room) at glass_worlds' 64 x 48
 window under the antialiasing pinhole, four bounces.

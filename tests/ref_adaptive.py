@@ -48,6 +48,32 @@ def next_active(S1, S2, n, active, fg, threshold, dark, dilate):
     return stay, dict(active=int(active.sum()), failed=int(fail.sum()), staying=int(stay.sum()))
 
 
+TILE = 2048  # list entries per block of the compaction (rt3_adaptive.hip: kAdTile)
+
+
+def keeps(records, mask, W, H, dilate):
+    """per record of a list ((n, 2) words {x | y << 16, blue-noise word}): does it stay -- its pixel's byte of the window-space mask (H, W)
+    is non-zero or, with dilate, any byte of the 3 x 3 neighbourhood inside the window is"""
+    m = np.asarray(mask).reshape(H, W) != 0
+    if dilate:
+        m = dilate3(m)
+    xy = np.asarray(records, np.uint32).reshape(-1, 2)[:, 0]
+    return m[(xy >> 16).astype(np.int64), (xy & 0xFFFF).astype(np.int64)]
+
+
+def block_offsets(records, mask, W, H, dilate):
+    """what the scan leaves: per TILE-entry tile of the list, the number of kept entries in front of it"""
+    k = keeps(records, mask, W, H, dilate)
+    per_tile = np.add.reduceat(k.astype(np.int64), np.arange(0, len(k), TILE)) if len(k) else np.zeros(0, np.int64)
+    return np.cumsum(per_tile) - per_tile
+
+
+def compact(records, mask, W, H, dilate):
+    """The list after a compaction: (the kept records in the list's order, block_offsets(...)).  Integer work: exact."""
+    records = np.asarray(records, np.uint32).reshape(-1, 2)
+    return records[keeps(records, mask, W, H, dilate)], block_offsets(records, mask, W, H, dilate)
+
+
 def round_samples(n, min_samples, step, cap):
     """the samples the round that starts at count n hands out"""
     return min(min_samples, cap) if n == 0 else min(step, cap - n)

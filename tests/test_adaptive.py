@@ -24,21 +24,22 @@ CAPS = list(range(aw.MIN_SAMPLES, CAP + 1, aw.STEP))  # 4, 8, ..., 24
 U = 2.0 ** -24  # unit roundoff of float32
 
 
-def camera(cam=aw.CAMERA):
-    return Camera(cam["position"], cam["direction"], aw.fov(cam), W / H)
+def camera(cam=aw.CAMERA, window=(W, H)):
+    return Camera(cam["position"], cam["direction"], aw.fov(cam), window[0] / window[1])
 
 
 class World:
-    """one context with the fixture's scene; frames are rendered once per distinct request"""
+    """one context with the fixture's scene in a window (the fixture's 67 x 45 unless told otherwise); frames are rendered once per
+    distinct request"""
 
-    def __init__(self, mesh=None, cam=aw.CAMERA, rank=0, n_ranks=1, instances=None, instance_mode=0):
-        self.pt = pt = PathTracer((W, H), rank=rank, n_ranks=n_ranks)
+    def __init__(self, mesh=None, cam=aw.CAMERA, rank=0, n_ranks=1, instances=None, instance_mode=0, window=(W, H)):
+        self.pt = pt = PathTracer(tuple(window), rank=rank, n_ranks=n_ranks)
         if instance_mode:
             pt.ctx.set_option(L.OPT_INSTANCE_MODE, instance_mode)
         pt.set_scene(mesh if mesh is not None else scenes.cornell(), aw.sky(), assets.load_bluenoise())
         if instances is not None:
             pt.set_instances(instances)
-        self.cam = camera(cam)
+        self.cam = camera(cam, window)
         self.cache = {}
 
     def close(self):
@@ -78,16 +79,16 @@ def counts_of(moments, fg):
     return n.astype(np.int64)
 
 
-def check_against_fixed(w, light, moments, fg, **frame):
-    """every foreground pixel holds the bits of the fixed frame of its own count; at most six such frames"""
+def check_against_fixed(w, light, moments, fg, cap=CAP, **frame):
+    """every foreground pixel holds the bits of the fixed frame of its own count; at most cap / step such frames"""
     n = counts_of(moments, fg)
     distinct = sorted(set(n[fg].tolist()))
-    assert set(distinct) <= set(CAPS), distinct
+    assert set(distinct) <= set(range(aw.MIN_SAMPLES, cap + 1, aw.STEP)), distinct
     for k in distinct:
         sel = fg & (n == k)
         fixed = w.fixed(k, **frame)
         assert np.array_equal(bits(light)[sel], bits(fixed)[sel]), f"{(bits(light)[sel] != bits(fixed)[sel]).any(-1).sum()} of {sel.sum()} pixels with n = {k} differ"
-    assert np.array_equal(moments[..., 3][fg], (n[fg] < CAP).astype(np.float32))
+    assert np.array_equal(moments[..., 3][fg], (n[fg] < cap).astype(np.float32))
     assert (bits(moments)[~fg] == 0).all()
     return n
 
@@ -115,12 +116,11 @@ def test_bit_exact_with_blendfactor(world):
 
 
 # ---- 2. the decisions
-@pytest.mark.parametrize("dilate", [0, 1])
-def test_decisions_follow_the_reference(world, dilate):
-    runs = [world.adaptive(cap=c, dilate=dilate) for c in CAPS]
-    fg = runs[0][3] != aw.BACKGROUND_DEPTH
-    p = aw.params(dilate=dilate)
-    for c, (_, m, info, _), (_, m_next, _, _) in zip(CAPS, runs, runs[1:]):
+def check_decisions(runs, caps, fg, p):
+    """runs[k]: World.adaptive at cap caps[k] under the parameters p.  The Moments of the run at one cap, fed to the reference, say which
+    pixels go on in the run at the next; a stopped pixel's state is frozen.  Returns the last run's counts."""
+    dilate = p["dilate"]
+    for c, (_, m, info, _), (_, m_next, _, _) in zip(caps, runs, runs[1:]):
         n, n_next = counts_of(m, fg), counts_of(m_next, fg)
         stay, cnt = ra.next_active(m[..., 0], m[..., 1], n, fg & (n == c), fg, p["threshold"], p["dark"], dilate)
         grows = n_next > n
@@ -129,7 +129,14 @@ def test_decisions_follow_the_reference(world, dilate):
         assert info[0] == c // aw.STEP and info[2] == cnt["active"]
         frozen = fg & ~grows  # a stopped pixel's state is frozen
         assert np.array_equal(bits(m[..., :3])[frozen], bits(m_next[..., :3])[frozen])
-    early, full = aw.shares(counts_of(runs[-1][1], fg), fg)
+    return counts_of(runs[-1][1], fg)
+
+
+@pytest.mark.parametrize("dilate", [0, 1])
+def test_decisions_follow_the_reference(world, dilate):
+    runs = [world.adaptive(cap=c, dilate=dilate) for c in CAPS]
+    fg = runs[0][3] != aw.BACKGROUND_DEPTH
+    early, full = aw.shares(check_decisions(runs, CAPS, fg, aw.params(dilate=dilate)), fg)
     print(f"dilate={dilate}: {early:.3f} of the foreground stops early, {full:.3f} reaches the cap")
     assert early >= aw.MIN_SHARE and full >= aw.MIN_SHARE
 
