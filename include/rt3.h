@@ -295,6 +295,36 @@ int rt3_scene_set_transmission(rt3_ctx *ctx, const rt3_transmission *t, uint32_t
 int rt3_scene_set_pane_shadows(rt3_ctx *ctx, int on);
 int rt3_scene_get_pane_shadows(rt3_ctx *ctx, int *on);
 int rt3_pane_shadow_info(rt3_ctx *ctx, uint32_t *n_panes);
+/* ---- absorbing glass: Beer-Lambert attenuation inside solid dielectrics.  No reference counterpart.  DESIGN.md section 4s.  One entry per
+ *      geometry of the last rt3_scene_set_geometry; n = 0: none, and rt3_scene_set_geometry resets every geometry to that.  sigma: the
+ *      absorption coefficient per colour channel, per world-space unit of length (glTF KHR_materials_volume:
+ *      sigma = -ln(attenuationColor) / attenuationDistance).  rt3_accel_build classifies a geometry as absorbing when its transmission is > 0,
+ *      it is solid (thin_walled = 0) and some sigma is > 0, and keeps a table per flattened geometry only when some geometry is absorbing;
+ *      a sigma on any other geometry is ignored.  With the table, "refrence_mode" and "adaptive" run a kernel of its own name (k_absorb)
+ *      between the k_extend and the k_shade of every vertex b >= 1, which applies one rule to the closest hit {t, u, v, prim} of each
+ *      extension ray {o, d}: a path segment is inside an absorbing solid when it ARRIVES AT A BACK FACE of it.
+ *        n = the interpolated vertex normal of the hit as a geometry without a normal map gets it (through the geometry's matrix unless it
+ *        is the identity; not face-forwarded; a normal map is deliberately ignored);
+ *        if prim's geometry is absorbing and dot(n, d) > 0:  x = t sqrtf(dot(d, d));  T.c = T.c expf(-(sigma.c x)) per channel, in fp32, in
+ *        this order.  A channel with sigma 0 keeps its bits (expf(-0) = 1).  The pdf slot, the ray and the hit are not touched; a miss, a
+ *        front-face hit and a hit on any other geometry leave T bit for bit.
+ *      So every internal segment counts, those between total internal reflections included; emission and light samples at the arrival
+ *      vertex see the attenuated T; the per-crossing albedo tint of rt3_scene_set_transmission stays (glTF multiplies both).  Limits: media
+ *      do not nest -- a segment belongs to the geometry whose back face ends it, so an opaque object embedded in glass ends the segment on
+ *      its own front face and that segment is not attenuated; camera rays (vertex 0) are not attenuated: a camera inside a solid sees its
+ *      first segment clear.  Shadow rays are unchanged: solid glass still occludes them.  Without an absorbing geometry in the built scene
+ *      nothing is launched and every frame keeps its bits.
+ *      Works in both instance modes, after rt3_accel_import and across rt3_accel_refit.  A sigma that is not finite or is negative,
+ *      reserved != 0 or a wrong n is RT3_E_INVALID and changes nothing.  Takes effect at the next rt3_accel_build; until then an existing
+ *      structure is unusable, as after rt3_scene_set_transmission.  Borrowed for the call.
+ *      rt3_attenuation_info: the flattened geometries the built structure holds as absorbing (0: no table, no k_absorb); RT3_E_STATE
+ *      before a build. ---- */
+typedef struct rt3_attenuation {
+    float    sigma[3];  /* >= 0, per world-space unit of length */
+    uint32_t reserved;  /* 0 */
+} rt3_attenuation;      /* 16 bytes */
+int rt3_scene_set_attenuation(rt3_ctx *ctx, const rt3_attenuation *a, uint32_t n);
+int rt3_attenuation_info(rt3_ctx *ctx, uint32_t *n_absorbing);
 
 /* ---- instances: the reference's world is a list of placed meshes (add_instance / loaded_assets, world/mod.rs:50-101) under a
  *      top-level acceleration structure (create_acceleration_structure(.., level, ..), vulkan/raytracing.rs:88-148), and hit_info
@@ -760,6 +790,13 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      unless a kernel wrote out of place.  An entry is kept when its pixel's mask byte is non-zero or, with dilate, any byte of the 3 x 3
  *      neighbourhood inside the window is.  RT3_E_INVALID, before anything is launched, for W or H outside 1 .. 65535, dilate > 1, n = 0,
  *      n > 2^24, a header n that is not the call's n, or a record with x >= W or y >= H.
+ *      36 the absorption rule of rt3_scene_set_attenuation (T rgb, sigma rgb, t, d xyz, n xyz: 13 words -> T' rgb, applied as u32: 4 words;
+ *      applied = 0: dot(n, d) <= 0 or every sigma 0, and T' = T bit for bit); reads no context state.
+ *      37 k_absorb itself on a caller-made queue of n records over the built scene's tables; RT3_E_STATE without an absorption table.
+ *      in: the header {workgroups to launch (1 .. 65535)}, then n records of 10 words {d xyz, t, u, v, prim (0xFFFFFFFF: a miss), T rgb}.
+ *      out: T' rgb per record.  RT3_E_INVALID, before anything is launched, for a primitive the flattened world does not have.  The
+ *      queue's planes are made one record longer than n and filled with a pattern: RT3_E_STATE when the kernel changed a ray or hit
+ *      record or wrote behind the queue's end.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

@@ -38,13 +38,15 @@ SELFTEST_ROULETTE = 33  # rt3_selftest_eval op: {T rgb, min_survival, u} (5 word
 SELFTEST_ROULETTE_QUEUE = 34  # rt3_selftest_eval op: k_roulette on a caller-made queue (Context.selftest_roulette_queue)
 SELFTEST_ADAPTIVE_COMPACT = 35  # rt3_selftest_eval op: the "adaptive" pass's list compaction on a caller-made list and mask (Context.selftest_adaptive_compact)
 ADAPTIVE_TILE = 2048  # list entries per compaction block (op 35 returns one offset per tile)
+SELFTEST_ABSORB = 36  # rt3_selftest_eval op: {T rgb, sigma rgb, t, d xyz, n xyz} (13 words) -> {T' rgb, applied (u32)} (4), the absorption rule
+SELFTEST_ABSORB_QUEUE = 37  # rt3_selftest_eval op: k_absorb on a caller-made queue over the built scene (Context.selftest_absorb_queue)
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
     "rt3_scene_set_vertices", "rt3_scene_set_indices", "rt3_scene_set_geometry", "rt3_scene_set_sky", "rt3_scene_set_bluenoise", "rt3_scene_set_texture",
     "rt3_scene_set_alpha_cutoffs",
     "rt3_scene_set_material_textures",
-    "rt3_scene_set_transmission",
+    "rt3_scene_set_transmission", "rt3_scene_set_attenuation", "rt3_attenuation_info",
     "rt3_scene_set_pane_shadows", "rt3_scene_get_pane_shadows", "rt3_pane_shadow_info",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_exit_table_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
@@ -191,6 +193,8 @@ def load():
         "rt3_scene_set_alpha_cutoffs": (i32, [vp, vp, u32]),
         "rt3_scene_set_material_textures": (i32, [vp, vp, u32]),
         "rt3_scene_set_transmission": (i32, [vp, vp, u32]),
+        "rt3_scene_set_attenuation": (i32, [vp, vp, u32]),
+        "rt3_attenuation_info": (i32, [vp, pu32]),
         "rt3_scene_set_pane_shadows": (i32, [vp, i32]),
         "rt3_scene_get_pane_shadows": (i32, [vp, C.POINTER(i32)]),
         "rt3_pane_shadow_info": (i32, [vp, C.POINTER(u32)]),

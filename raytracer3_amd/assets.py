@@ -41,6 +41,10 @@ assert MATERIAL_TEXTURES_DTYPE.itemsize == 16
 # rt3_transmission (include/rt3.h): glass per geometry
 TRANSMISSION_DTYPE = np.dtype([("transmission", "<f4"), ("ior", "<f4"), ("thin_walled", "<u4"), ("reserved", "<u4")])
 assert TRANSMISSION_DTYPE.itemsize == 16
+# rt3_attenuation (include/rt3.h): absorption coefficients of solid glass per geometry
+ATTENUATION_DTYPE = np.dtype([("sigma", "<f4", (3,)), ("reserved", "<u4")])
+assert ATTENUATION_DTYPE.itemsize == 16
+FLT_MIN = 1.1754943508222875e-38  # the smallest normal float32: the floor of an attenuation colour's component
 # rt3_punctual_light (include/rt3.h): a point, spot or directional light of KHR_lights_punctual, in world space
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2
 LIGHT_DTYPE = np.dtype(
@@ -92,6 +96,25 @@ def no_transmission(n: int) -> np.ndarray:
     return t
 
 
+def attenuation_sigma(color, distance) -> np.ndarray:
+    """(3,) float32 absorption coefficients of KHR_materials_volume's attenuationColor / attenuationDistance:
+    sigma = -ln(max(c, FLT_MIN)) / distance, in float64, rounded once to float32; an infinite distance gives 0.  (A component above 1 would
+    amplify: it counts as 1.)"""
+    c = np.minimum(np.maximum(np.asarray(color, np.float64).reshape(3), FLT_MIN), 1.0)
+    d = float(distance)
+    if not d > 0.0:
+        raise ValueError("attenuationDistance must be > 0")
+    if math.isinf(d):
+        return np.zeros(3, np.float32)
+    # (math.log: the C library's, as host/assets.hpp calls it; + 0.0: no negative zero)
+    return np.array([-math.log(float(x)) / d + 0.0 for x in c], np.float64).astype(np.float32)
+
+
+def no_attenuation(n: int) -> np.ndarray:
+    """n entries of ATTENUATION_DTYPE that absorb nothing: what a glTF material without attenuationColor / attenuationDistance is"""
+    return np.zeros(n, ATTENUATION_DTYPE)
+
+
 @dataclass
 class Material:
     """assets/mod.rs:52-59 (f16 fields there; plain floats here) + emission (datatypes.slang:17)."""
@@ -112,6 +135,9 @@ class Material:
     transmission: float = 0.0  # transmissionFactor
     ior: float = 1.5
     thin_walled: int = 1  # 0 = solid: the material has a volume (thicknessFactor > 0)
+    # absorbing glass: KHR_materials_volume's attenuationColor / attenuationDistance (attenuation_sigma)
+    attenuation_color: tuple = (1.0, 1.0, 1.0)
+    attenuation_distance: float = math.inf
 
 
 @dataclass
@@ -128,6 +154,11 @@ class Mesh:
     material_textures: np.ndarray = None  # (g,) MATERIAL_TEXTURES_DTYPE (rt3_scene_set_material_textures); None -> no texture anywhere
     lights: np.ndarray = None  # (l,) LIGHT_DTYPE punctual lights (rt3_scene_set_lights); None -> none
     transmission: np.ndarray = None  # (g,) TRANSMISSION_DTYPE glass (rt3_scene_set_transmission); None -> no glass anywhere
+    # (g,) ATTENUATION_DTYPE sigma per geometry (rt3_scene_set_attenuation); None -> zeros.  A thin-walled or opaque
+    # geometry keeps what its material said; only solid glass absorbs (absorbing()).
+    attenuation: np.ndarray = None
+    # (g, 4) float64 {attenuationColor rgb, attenuationDistance} the sigmas were made from, for write_glb; None -> derived from the sigmas
+    attenuation_source: np.ndarray = None
 
     def __post_init__(self):
         self.lights = np.ascontiguousarray(np.zeros(0, LIGHT_DTYPE) if self.lights is None else self.lights, LIGHT_DTYPE).reshape(-1)
@@ -137,9 +168,17 @@ class Mesh:
         if self.transmission is None:
             self.transmission = no_transmission(len(self.geometries))
         self.transmission = np.ascontiguousarray(self.transmission, TRANSMISSION_DTYPE).reshape(len(self.geometries))
+        if self.attenuation is None:
+            self.attenuation = no_attenuation(len(self.geometries))
+        self.attenuation = np.ascontiguousarray(self.attenuation, ATTENUATION_DTYPE).reshape(len(self.geometries))
         if self.alpha_cutoffs is None:
             self.alpha_cutoffs = np.zeros(len(self.geometries), np.float32)
         self.alpha_cutoffs = np.ascontiguousarray(self.alpha_cutoffs, np.float32).reshape(len(self.geometries))
+
+    def absorbing(self) -> np.ndarray:
+        """(g,) bool: the geometries rt3_accel_build classifies as absorbing -- transmission > 0, solid, some sigma > 0"""
+        tr = self.transmission
+        return (tr["transmission"] > 0) & (tr["thin_walled"] == 0) & np.any(self.attenuation["sigma"] > 0, axis=1)
 
     @property
     def n_triangles(self) -> int:
@@ -160,6 +199,7 @@ class MeshBuilder:
 
     def __init__(self):
         self.v, self.i, self.g, self.c, self.names, self.cut, self.mt, self.tr = [], [], [], [], [], [], [], []
+        self.at, self.at_src = [], []
         self.nv = 0
         self.ni = 0
 
@@ -188,6 +228,8 @@ class MeshBuilder:
         self.cut.append(mat.alpha_cutoff)
         self.mt.append((mat.metallic_roughness_texture, mat.normal_texture, mat.emissive_texture, mat.normal_scale))
         self.tr.append((mat.transmission, mat.ior, mat.thin_walled, 0))
+        self.at.append((tuple(attenuation_sigma(mat.attenuation_color, mat.attenuation_distance)), 0))
+        self.at_src.append((*[float(x) for x in mat.attenuation_color], float(mat.attenuation_distance)))
         self.names.append(name)
         self.nv += len(pos)
         self.ni += tris.size
@@ -202,12 +244,29 @@ class MeshBuilder:
             alpha_cutoffs=np.array(self.cut, np.float32),
             material_textures=np.array(self.mt, MATERIAL_TEXTURES_DTYPE),
             transmission=np.array(self.tr, TRANSMISSION_DTYPE),
+            attenuation=np.array(self.at, ATTENUATION_DTYPE),
+            attenuation_source=np.array(self.at_src, np.float64).reshape(-1, 4),
         )
 
 
 # ----------------------------------------------------------------------------------------------- glTF (.glb)
 _COMP = {5120: ("i1", 1), 5121: ("u1", 1), 5122: ("<i2", 2), 5123: ("<u2", 2), 5125: ("<u4", 4), 5126: ("<f4", 4)}
 _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
+
+
+def _attenuation_gltf(mesh: Mesh, gi: int):
+    """(attenuationColor, attenuationDistance) that attenuation_sigma takes back to mesh.attenuation[gi], bit for bit: the pair the sigmas
+    were made from where the mesh still has it, otherwise distance 2^k with the largest sigma x distance in [0.5, 1) and colour
+    exp(-sigma x distance)"""
+    sigma = mesh.attenuation["sigma"][gi]
+    src = mesh.attenuation_source
+    if src is not None and len(src) == len(mesh.geometries) and np.array_equal(attenuation_sigma(src[gi, :3], src[gi, 3]), sigma):
+        return [float(x) for x in src[gi, :3]], float(src[gi, 3])
+    dist = 2.0 ** -math.ceil(math.log2(float(sigma.max())) + 1e-9)
+    col = np.exp(-sigma.astype(np.float64) * dist)
+    if not np.array_equal(attenuation_sigma(col, dist), sigma):
+        raise ValueError(f"geometry {gi}: its absorption coefficients {sigma} have no attenuationColor / attenuationDistance that reads back exactly")
+    return [float(x) for x in col], dist
 
 
 def write_glb(path, mesh: Mesh) -> None:
@@ -271,6 +330,10 @@ def write_glb(path, mesh: Mesh) -> None:
             ext["KHR_materials_ior"] = {"ior": float(tr["ior"])}
         if int(tr["thin_walled"]) == 0:
             ext["KHR_materials_volume"] = {"thicknessFactor": 1.0}
+        # absorbing glass: the defaults -- colour 1, infinite distance -- stay implicit
+        if np.any(mesh.attenuation["sigma"][gi] > 0):
+            col, dist = _attenuation_gltf(mesh, gi)
+            ext.setdefault("KHR_materials_volume", {}).update({"attenuationColor": col, "attenuationDistance": dist})
         if ext:
             mtl["extensions"] = ext
             used += [k for k in ext if k not in used]
@@ -455,11 +518,14 @@ class GltfMeshLoader:
                         gext = gmtl.get("extensions", {})
                         tau = float(gext.get("KHR_materials_transmission", {}).get("transmissionFactor", 0.0))
                         ior = float(gext.get("KHR_materials_ior", {}).get("ior", 1.5))
-                        thin = 0 if float(gext.get("KHR_materials_volume", {}).get("thicknessFactor", 0.0)) > 0.0 else 1
+                        gvol = gext.get("KHR_materials_volume", {})
+                        thin = 0 if float(gvol.get("thicknessFactor", 0.0)) > 0.0 else 1
+                        att_c = tuple(float(x) for x in gvol.get("attenuationColor", (1.0, 1.0, 1.0)))
+                        att_d = float(gvol.get("attenuationDistance", math.inf))
                         nt = gmtl.get("normalTexture")
                         mat = Material(tuple(bc[:3]), pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0), tuple(em), tex, cut,
                                        float(bc[3]) if len(bc) > 3 else 1.0, tex_index(pbr.get("metallicRoughnessTexture")), tex_index(nt),
-                                       tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0, tau, ior, thin)
+                                       tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0, tau, ior, thin, att_c, att_d)
                     mb.add(f"{gm.get('name', 'mesh')}.{pi}", pos, nrm, uv, tris, mat, normalize=not keep)
             for c in node.get("children", []):
                 visit(c, m)

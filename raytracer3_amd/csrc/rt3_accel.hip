@@ -90,6 +90,8 @@ static int flatten_world(rt3_ctx* c) {
     std::vector<ShadeGeomDev> shade;
     std::vector<MatTexDev> mats;
     std::vector<GlassDev> glass;
+    std::vector<AbsorbDev> absorb;
+    uint32_t n_absorbing = 0;
     std::vector<uint32_t> first;
     std::vector<Placed> placed;
     uint64_t total = 0;
@@ -131,6 +133,15 @@ static int flatten_world(rt3_ctx* c) {
                 if (pane_geometry(c, g)) gd.pad = kGlassPaneBit;  // (the reserved word is 0 as uploaded)
                 glass.push_back(gd);
             }
+            {  // absorption: a geometry that does not absorb holds zeros, whatever was uploaded for it
+                AbsorbDev ad = {{0.0f, 0.0f, 0.0f}, 0u};
+                if (absorbing_geometry(c, g)) {
+                    for (int q = 0; q < 3; q++) ad.sigma[q] = c->scene.h_attenuation[g].sigma[q];
+                    ad.absorbing = 1u;
+                    n_absorbing++;
+                }
+                absorb.push_back(ad);
+            }
             first.push_back((uint32_t)total);
             placed.push_back({(uint32_t)i, g, (uint32_t)total, c->scene.h_prim_counts[g], identity});
             total += c->scene.h_prim_counts[g];
@@ -162,6 +173,14 @@ static int flatten_world(rt3_ctx* c) {
         if (int r = dev_alloc(c, c->accel.d_glass, nf)) return r;
         HIPC(c, hipMemcpy(c->accel.d_glass.get(), glass.data(), nf * sizeof(GlassDev), hipMemcpyHostToDevice));
         c->accel.has_glass = true;
+    }
+    c->accel.n_absorbing = 0;
+    if (n_absorbing) {  // (kept only when some flattened geometry absorbs)
+        if (int r = dev_alloc(c, c->accel.d_absorb, nf)) return r;
+        HIPC(c, hipMemcpy(c->accel.d_absorb.get(), absorb.data(), nf * sizeof(AbsorbDev), hipMemcpyHostToDevice));
+        c->accel.n_absorbing = n_absorbing;
+    } else {
+        c->accel.d_absorb.reset();
     }
     c->accel.n_flat_geoms = (uint32_t)nf;
     c->accel.n_flat_prims = (uint32_t)total;
@@ -760,6 +779,11 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
 int rt3_pane_shadow_info(rt3_ctx* c, uint32_t* n_panes) {
     if (!c || !c->accel.built) return fail(c, RT3_E_STATE, "no acceleration structure built");
     if (n_panes) *n_panes = c->accel.n_panes;
+    return RT3_OK;
+}
+int rt3_attenuation_info(rt3_ctx* c, uint32_t* n_absorbing) {
+    if (!c || !c->accel.built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    if (n_absorbing) *n_absorbing = c->accel.n_absorbing;
     return RT3_OK;
 }
 int rt3_accel_info(rt3_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* max_depth, uint32_t* node_bytes) {

@@ -15,6 +15,7 @@
 
 #include "rt3_ctx.hpp"
 #include "rt3_roulette.hpp"
+#include "rt3_volume.hpp"
 
 using namespace rt3;
 
@@ -473,8 +474,63 @@ static int selftest_adaptive_compact(rt3_ctx* c, const uint32_t* in, uint32_t n,
     return RT3_OK;
 }
 
+// Self-test op 37: k_absorb on a caller-made queue of n records over the built scene's tables.  in: {workgroups}, then n records
+// {d xyz, t, u, v, prim, T rgb}.  out: T' rgb per record.  The queue's planes are one record longer than n and the extra words carry a
+// pattern: a kernel that wrote behind the queue's end fails the call.
+static int selftest_absorb_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    if (int r = check_accel_current(c)) return r;
+    if (c->accel.n_absorbing == 0u) return fail(c, RT3_E_STATE, "selftest: the built scene has no absorption table (rt3_scene_set_attenuation)");
+    const uint32_t groups = in[0];
+    if (groups == 0 || groups > 65535 || n > (1u << 24)) return fail(c, RT3_E_INVALID, "selftest: absorb queue header: 1..65535 workgroups, at most 2^24 records");
+    const uint32_t* rec = in + kSelftestAbsorbHeader;
+    for (uint32_t i = 0; i < n; i++) {  // k_absorb indexes the shading records with the hit's primitive: nothing is launched that would read outside them
+        const uint32_t prim = rec[kSelftestAbsorbRecord * (size_t)i + 6];
+        if (prim != kMiss && prim >= c->accel.n_flat_prims)
+            return fail(c, RT3_E_INVALID, "selftest: absorb queue record " + std::to_string(i) + " names a primitive the flattened world does not have");
+    }
+    HIPC(c, hipSetDevice(c->device));
+    constexpr uint32_t kGuard = 0xA5A5A5A5u;
+    const size_t S = (size_t)n + 1;  // one guard record per plane
+    std::vector<uint32_t> rays(8 * S, kGuard), hits(4 * S, kGuard), T(3 * S, kGuard);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t* r = rec + kSelftestAbsorbRecord * i;
+        memcpy(&rays[4 * (S + i)], r, 12);
+        rays[4 * (S + i) + 3] = (uint32_t)i;  // path id
+        memcpy(&hits[4 * i], r + 3, 16);
+        for (int k = 0; k < 3; k++) T[k * S + i] = r[7 + k];
+    }
+    DevBuf<float> d_rays, d_hits, d_T;
+    DevBuf<uint32_t> d_cnt;
+    HIPC(c, d_rays.alloc_bytes(8 * S * 4));
+    HIPC(c, d_hits.alloc_bytes(4 * S * 4));
+    HIPC(c, d_T.alloc_bytes(3 * S * 4));
+    HIPC(c, d_cnt.alloc_bytes(4));
+    HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_hits.get(), hits.data(), 4 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_T.get(), T.data(), 3 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_cnt.get(), &n, 4, hipMemcpyHostToDevice));
+    const SceneDev sc = scene_dev(c);
+    AbsorbLaunch a{};
+    a.rays = d_rays.get(); a.hits = d_hits.get(); a.T = d_T.get(); a.count = d_cnt.get(); a.stride = S;
+    a.tri_shade = sc.tri_shade; a.shade_geoms = sc.shade_geoms; a.table = c->accel.d_absorb.get();
+    launch_absorb(c->stream, a, n, groups);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> rays2(8 * S), hits2(4 * S);
+    HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(hits2.data(), d_hits.get(), 4 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(T.data(), d_T.get(), 3 * S * 4, hipMemcpyDeviceToHost));
+    if (rays2 != rays || hits2 != hits) return fail(c, RT3_E_STATE, "selftest: k_absorb wrote a ray or hit record");
+    for (int k = 0; k < 3; k++)
+        if (T[k * S + n] != kGuard) return fail(c, RT3_E_STATE, "selftest: k_absorb wrote behind the queue's end");
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) out[3 * i + k] = T[k * S + i];
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 37 && c && in && out) return selftest_absorb_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 35 && c && in && out) return selftest_adaptive_compact(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 34 && c && in && out) return selftest_roulette_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));  // no rows of one width
     if (!c || !in || !out || !selftest_widths(op, &iw, &ow)) return fail(c, RT3_E_INVALID, "selftest: bad op / NULL");
@@ -510,6 +566,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
         else if (op == 31) launch_selftest_lens(c->stream, d_in.get(), n, d_out.get());
         else if (op == 32) launch_selftest_glass(c->stream, d_in.get(), n, d_out.get());
         else if (op == 33) launch_selftest_roulette(c->stream, d_in.get(), n, d_out.get());
+        else if (op == 36) launch_selftest_absorb(c->stream, d_in.get(), n, d_out.get());
         else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }

@@ -13,6 +13,7 @@
 
 #include "../../include/rt3.h"
 #include "rt3_internal.hpp"
+#include "rt3_volume.hpp"
 
 struct ncclComm;  // <rccl/rccl.h> (ncclComm_t), which only rt3_tiles.hip includes
 
@@ -148,6 +149,8 @@ struct rt3_ctx {
         std::vector<rt3_material_textures> h_mat_tex;
         // transmission per uploaded geometry (empty = no glass anywhere)
         std::vector<rt3_transmission> h_transmission;
+        // absorption inside solid glass per uploaded geometry (empty = every sigma 0)
+        std::vector<rt3_attenuation> h_attenuation;
         std::vector<rt3_instance> h_instances;   // empty = one identity instance of every geometry
         // the previous frame's instance matrices, n x 16 column-major (rt3_scene_set_prev_transforms; empty = every instance unmoved)
         std::vector<float> prev_transforms;
@@ -184,6 +187,10 @@ struct rt3_ctx {
         bool has_mat_tex = false, has_normal_tex = false;
         rt3::DevBuf<rt3::GlassDev> d_glass;                // per flattened geometry; has_glass: the built scene has a transmission > 0
         bool has_glass = false;
+        // absorption: per flattened geometry, kept only while the last rt3_accel_build classified some geometry as
+        // absorbing (n_absorbing of them; 0: no table, no k_absorb)
+        rt3::DevBuf<rt3::AbsorbDev> d_absorb;
+        uint32_t n_absorbing = 0;
         rt3::DevBuf<uint32_t> d_prim_geom, d_first_prim;
         uint32_t n_flat_geoms = 0, n_flat_prims = 0;  // after flattening: what the acceleration structure and the shading records cover
         std::vector<rt3::Placed> placed;              // the same, on the host: n_flat_geoms entries
@@ -372,6 +379,14 @@ int deform_flags(rt3_ctx* c);
 inline bool any_cutoff(const rt3_ctx* c) { return !c->scene.h_cutoffs.empty(); }
 inline bool any_mat_tex(const rt3_ctx* c) { return !c->scene.h_mat_tex.empty(); }
 inline bool any_glass(const rt3_ctx* c) { return !c->scene.h_transmission.empty(); }
+// does uploaded geometry g absorb (rt3_scene_set_attenuation)?  Transmission > 0, solid, some sigma > 0
+inline bool absorbing_geometry(const rt3_ctx* c, uint32_t g) {
+    if (c->scene.h_attenuation.empty() || !any_glass(c)) return false;
+    const rt3_transmission& t = c->scene.h_transmission[g];
+    if (!(t.transmission > 0.0f) || t.thin_walled != 0u) return false;
+    const float* s = c->scene.h_attenuation[g].sigma;
+    return s[0] > 0.0f || s[1] > 0.0f || s[2] > 0.0f;
+}
 // is uploaded geometry g a pane (rt3_scene_set_pane_shadows)?  Mode on, transmission > 0, thin-walled, no normal texture
 inline bool pane_geometry(const rt3_ctx* c, uint32_t g) {
     if (!c->pane_shadows || !any_glass(c)) return false;

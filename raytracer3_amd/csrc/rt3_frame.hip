@@ -3,7 +3,7 @@
 // The wavefront path-tracing kernels (hand-written HIP, wave64) are split by stage: traversal in rt3_trace.hip, shading in rt3_shade.hip.
 // Pipeline (replaces shaders/old/{gbuffer,refrence_mode,postprocess}.slang + the driver's ray traversal):
 //   k_raygen -> k_extend -> k_gbuffer                                   ("gbuffer" pass)
-//   k_shade<first> -> [k_shadow] -> [k_roulette] -> k_extend -> k_shade -> ... -> k_accumulate   ("refrence_mode" pass)
+//   k_shade<first> -> [k_shadow] -> [k_roulette] -> k_extend -> [k_absorb] -> k_shade -> ... -> k_accumulate   ("refrence_mode" pass)
 //   k_postprocess                                                        ("postprocess" pass)
 // All queues are structure-of-arrays of 16-byte records (ray = {o, tmin} + {d, tmax}, state = {T, pdf}, hit = {t, u, v, prim};
 // shadow ray = {o, contribution.r} + {d, contribution.g} + 8 bytes {contribution.b, path id}): lane i touches record i of each

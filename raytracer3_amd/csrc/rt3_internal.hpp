@@ -157,6 +157,15 @@ constexpr uint32_t kSelftestRouletteIn = 5, kSelftestRouletteOut = 5;
 void launch_selftest_roulette(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
 // self-test op 34: k_roulette on a caller-made queue; header words, then the pixel words, then records of kSelftestQueueRecord words
 constexpr uint32_t kSelftestQueueHeader = 7, kSelftestQueueRecord = 11;
+// Beer-Lambert absorption on the extension queue (rt3_volume.hip); rt3_volume.hpp has the argument.  The grid is sized
+// for n_max records (an upper bound of *count), or is `groups` workgroups when that is not 0 (self-test op 37)
+struct AbsorbLaunch;
+void launch_absorb(hipStream_t st, const AbsorbLaunch& a, uint32_t n_max, uint32_t groups = 0);
+// self-test op 36: absorb_rule, {T rgb, sigma rgb, t, d xyz, n xyz} -> {T' rgb, applied}
+constexpr uint32_t kSelftestAbsorbIn = 13, kSelftestAbsorbOut = 4;
+void launch_selftest_absorb(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 37: k_absorb on a caller-made queue; one header word, then records of kSelftestAbsorbRecord words, three words out per record
+constexpr uint32_t kSelftestAbsorbHeader = 1, kSelftestAbsorbRecord = 10;
 void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst);
 void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img);
 

@@ -8,6 +8,7 @@
 // "adaptive" read.
 // Also owns rt3_ctx::roulette: Russian roulette on extension rays (rt3_path_set_roulette), which trace_batch applies
 // for "refrence_mode" and "adaptive".
+// trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +19,7 @@
 
 #include "rt3_ctx.hpp"
 #include "rt3_roulette.hpp"
+#include "rt3_volume.hpp"
 
 using namespace rt3;
 
@@ -254,6 +256,8 @@ struct PathSetup {
     // pane shadows (rt3_scene_set_pane_shadows): the built structure has panes -- k_shade_pane and k_shadow_pane
     bool panes = false;
     PaneDev pane{};
+    // absorption (rt3_scene_set_attenuation): the built scene's table, null without an absorbing geometry -- k_absorb
+    const AbsorbDev* absorb = nullptr;
 };
 // pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
 constexpr float kSkyDeferMinPdf = 0x1p-100f;
@@ -295,6 +299,7 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
         if (int r = ensure_pane_dist(c)) return r;
         ps->pane = pane_dev(c);
     }
+    ps->absorb = c->accel.n_absorbing != 0u ? c->accel.d_absorb.get() : nullptr;
     ps->rr = c->roulette.on && c->roulette.params.start_bounce < B - 1u;
     ps->rr_start = c->roulette.params.start_bounce;
     ps->rr_min = c->roulette.params.min_survival;
@@ -435,6 +440,15 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             tr.hits = c->work.hits.get(); tr.payload = true;
             ScopedTimer t(c, CAT_EXTEND);
             launch_extend(c->stream, c->accel.bvh, tr);
+        }
+        if (ps.absorb != nullptr && bn != B - 1) {
+            // the segments k_extend has just closed (vertex bn -> vertex bn + 1 >= 1) that ran inside an absorbing solid, before the k_shade of
+            // vertex bn + 1 reads their throughput
+            AbsorbLaunch A{};
+            A.rays = c->work.rays[cur].get(); A.hits = c->work.hits.get(); A.T = c->work.T[cur].get(); A.count = live_cnt; A.stride = S;
+            A.tri_shade = ps.sc.tri_shade; A.shade_geoms = ps.sc.shade_geoms; A.table = ps.absorb;
+            ScopedTimer t(c, CAT_OTHER);
+            launch_absorb(c->stream, A, n_first);
         }
     }
     return RT3_OK;

@@ -248,6 +248,7 @@ int rt3_scene_set_geometry(rt3_ctx* c, const rt3_geometry_info* g, const uint32_
     c->scene.h_cutoffs.clear();  // every geometry opaque again
     c->scene.h_mat_tex.clear();  // and without material textures
     c->scene.h_transmission.clear();  // and without glass
+    c->scene.h_attenuation.clear();   // and without absorption
     c->scene.n_geoms = n;
     c->scene.max_tex_index = max_tex;
     c->scene.n_prims = (uint32_t)total;
@@ -296,6 +297,23 @@ int rt3_scene_set_transmission(rt3_ctx* c, const rt3_transmission* t, uint32_t n
     }
     c->scene.h_transmission.clear();
     if (std::any_of(t, t + n, [](const rt3_transmission& e) { return e.transmission > 0.0f; })) c->scene.h_transmission.assign(t, t + n);  // (kept only when some geometry is glass)
+    invalidate_topology(c);  // the side table is made by a build
+    return RT3_OK;
+}
+// absorption of the geometries of the last rt3_scene_set_geometry; n = 0: none
+int rt3_scene_set_attenuation(rt3_ctx* c, const rt3_attenuation* a, uint32_t n) {
+    if (!c || (!a && n)) return fail(c, RT3_E_INVALID, "attenuation NULL");
+    if (n != 0 && n != c->scene.n_geoms)
+        return fail(c, RT3_E_INVALID, "attenuation: n must be 0 or the geometry count of rt3_scene_set_geometry (" + std::to_string(c->scene.n_geoms) + ")");
+    for (uint32_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++)
+            if (!(a[i].sigma[k] >= 0.0f && a[i].sigma[k] <= kFloatMax))
+                return fail(c, RT3_E_INVALID, "attenuation: sigma " + std::to_string(i) + " is not a finite value >= 0");
+        if (a[i].reserved != 0u) return fail(c, RT3_E_INVALID, "attenuation: reserved " + std::to_string(i) + " must be 0");
+    }
+    c->scene.h_attenuation.clear();
+    if (std::any_of(a, a + n, [](const rt3_attenuation& e) { return e.sigma[0] > 0.0f || e.sigma[1] > 0.0f || e.sigma[2] > 0.0f; }))
+        c->scene.h_attenuation.assign(a, a + n);  // (kept only when some sigma is > 0)
     invalidate_topology(c);  // the side table is made by a build
     return RT3_OK;
 }

@@ -182,7 +182,12 @@ bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
         *out_w = kSelftestRouletteOut;
         return true;
     }
-    static const uint32_t w[30][2] = {{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
+    if (op == 36) {  // the absorption rule (k_selftest_absorb, rt3_volume.hip); op 37 has no rows of one width (rt3_selftest_eval)
+        *in_w = kSelftestAbsorbIn;
+        *out_w = kSelftestAbsorbOut;
+        return true;
+    }
+    static const uint32_t w[30][2] ={{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
                                       {2, 9}, {2, 4}, {3, 1}, {1, 1}, {3, 11}};
     if (op < 0 || op > 29) return false;

@@ -4,7 +4,8 @@
 //                                                     its alpha cutoffs (alpha_cutoffs.bin, one float per geometry) and its
 //                                                     material textures (material_textures.bin, one rt3_material_textures each),
 //                                                     its punctual lights (lights.bin, one rt3_punctual_light each) and its glass
-//                                                     (transmission.bin, one rt3_transmission per geometry)
+//                                                     (transmission.bin, one rt3_transmission per geometry) with its absorption
+//                                                     coefficients (attenuation.bin, one rt3_attenuation per geometry)
 //   asset_tool exr <sky.exr> <outdir>                 dump the decoded equirect image
 //   asset_tool png <image.png|.jpg> <outdir>          dump the decoded RGBA8 image (PNG or baseline JPEG)
 //   asset_tool bincode <file> <current|old> <outdir>  dump a processed-asset cache file (assets/mod.rs:118-137)
@@ -43,6 +44,7 @@ int main(int argc, char** argv) {
             dump(out + "/material_textures.bin", m.material_textures);
             dump(out + "/lights.bin", m.lights);
             dump(out + "/transmission.bin", m.transmission);
+            dump(out + "/attenuation.bin", m.attenuation);
             FILE* f = fopen((out + "/manifest.txt").c_str(), "w");
             fprintf(f, "vertices %zu\nindices %zu\ngeometries %zu\ntextures %zu\n", m.n_vertices(), m.indices.size(), m.geometries.size(), m.textures.size());
             for (size_t i = 0; i < m.textures.size(); i++) {

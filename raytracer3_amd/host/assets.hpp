@@ -741,7 +741,16 @@ struct Material {  // assets/mod.rs:52-59 (+ emission, datatypes.slang:17)
     rt3_material_textures textures = {-1, -1, -1, 1.0f};
     // glass: KHR_materials_transmission, _ior, _volume; without a volume (or with thicknessFactor 0) thin-walled
     rt3_transmission transmission = {0.0f, 1.5f, 1u, 0u};
+    // absorbing glass: KHR_materials_volume's attenuationColor / attenuationDistance as absorption coefficients
+    rt3_attenuation attenuation = {{0.0f, 0.0f, 0.0f}, 0u};
 };
+// sigma = -ln(max(c, FLT_MIN)) / distance in double, rounded once to float; an infinite distance gives 0; a component above 1 counts as 1
+inline float attenuation_sigma(double c, double distance) {
+    if (!(distance > 0.0)) throw std::runtime_error("attenuationDistance must be > 0");
+    if (std::isinf(distance)) return 0.0f;
+    c = std::min(std::max(c, 1.1754943508222875e-38), 1.0);
+    return (float)(-std::log(c) / distance + 0.0);
+}
 struct Mesh {
     std::vector<float> vertices;                // n x 8: position, normal, uv (Vertex, assets/mod.rs:127-133)
     std::vector<uint32_t> indices;              // relative to each geometry's vertex_offset
@@ -752,6 +761,7 @@ struct Mesh {
     std::vector<float> alpha_cutoffs;           // one per geometry (rt3_scene_set_alpha_cutoffs), 0 = opaque
     std::vector<rt3_material_textures> material_textures;  // one per geometry (rt3_scene_set_material_textures)
     std::vector<rt3_transmission> transmission;  // one per geometry (rt3_scene_set_transmission)
+    std::vector<rt3_attenuation> attenuation;    // one per geometry (rt3_scene_set_attenuation)
     std::vector<rt3_punctual_light> lights;     // KHR_lights_punctual, baked through their nodes (rt3_scene_set_lights)
     size_t n_vertices() const { return vertices.size() / 8; }
     size_t n_triangles() const {
@@ -1065,6 +1075,13 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                             if (const Json* f = io->find("ior")) mat.transmission.ior = (float)f->number(1.5);
                         if (const Json* vo = ext->find("KHR_materials_volume"))
                             if (const Json* f = vo->find("thicknessFactor")) mat.transmission.thin_walled = f->number(0.0) > 0.0 ? 0u : 1u;
+                        if (const Json* vo = ext->find("KHR_materials_volume")) {
+                            double col[3] = {1.0, 1.0, 1.0}, dist = INFINITY;
+                            if (const Json* ac = vo->find("attenuationColor"))
+                                for (int k = 0; k < 3; k++) col[k] = ac->at((size_t)k).number(1.0);
+                            if (const Json* f = vo->find("attenuationDistance")) dist = f->number(INFINITY);
+                            for (int k = 0; k < 3; k++) mat.attenuation.sigma[k] = attenuation_sigma(col[k], dist);
+                        }
                     }
                 }
                 rt3_geometry_info g{};
@@ -1089,6 +1106,7 @@ class GltfMeshLoader {  // assets/mod.rs:179-200 (`impl AssetLoader`), extension
                 mesh_.alpha_cutoffs.push_back(mat.alpha_cutoff);
                 mesh_.material_textures.push_back(mat.textures);
                 mesh_.transmission.push_back(mat.transmission);
+                mesh_.attenuation.push_back(mat.attenuation);
                 mesh_.names.push_back((gm.has("name") ? gm.at("name").str : std::string("mesh")) + "." + std::to_string(this_pi));
             }
         }
@@ -1550,6 +1568,10 @@ inline uint32_t upload(rt3_ctx* ctx, const Mesh& m) {
     for (const rt3_transmission& t : m.transmission) glass = glass || t.transmission > 0.0f;
     if (glass)  // glass; a scene without it makes no call
         check(ctx, rt3_scene_set_transmission(ctx, m.transmission.data(), (uint32_t)m.transmission.size()), "rt3_scene_set_transmission");
+    bool absorbs = false;
+    for (const rt3_attenuation& a : m.attenuation) absorbs = absorbs || a.sigma[0] > 0.0f || a.sigma[1] > 0.0f || a.sigma[2] > 0.0f;
+    if (absorbs)  // absorbing glass; a scene without it makes no call
+        check(ctx, rt3_scene_set_attenuation(ctx, m.attenuation.data(), (uint32_t)m.attenuation.size()), "rt3_scene_set_attenuation");
     for (size_t i = 0; i < m.textures.size(); i++)
         check(ctx, rt3_scene_set_texture(ctx, (uint32_t)i, m.textures[i].rgba.data(), m.textures[i].w, m.textures[i].h), "rt3_scene_set_texture");
     if (!m.lights.empty())  // punctual lights; a scene without them makes no call

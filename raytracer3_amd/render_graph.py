@@ -179,6 +179,9 @@ class Context:
         tr = getattr(mesh, "transmission", None)
         if tr is not None and len(tr) and np.any(tr["transmission"] > 0):
             self.set_transmission(tr)  # glass; scenes without it make no call
+        at = getattr(mesh, "attenuation", None)
+        if at is not None and len(at) and np.any(at["sigma"] > 0):
+            self.set_attenuation(at)  # absorbing glass; scenes without it make no call
         lights = getattr(mesh, "lights", None)
         if lights is not None and len(lights):  # punctual lights; scenes without them make no call
             self.set_lights(lights)
@@ -206,6 +209,25 @@ class Context:
 
         t = np.ascontiguousarray(table, TRANSMISSION_DTYPE).reshape(-1)
         self.check(self.lib.rt3_scene_set_transmission(self.h, t.ctypes.data if len(t) else None, len(t)))
+
+    def set_attenuation(self, table):
+        """per-geometry absorption coefficients sigma rgb, per world-space unit of length (assets.ATTENUATION_DTYPE, or an (n, 3) array;
+        [] = none); rt3_scene_set_attenuation, next build_accel().  Only solid glass absorbs."""
+        from .assets import ATTENUATION_DTYPE
+
+        a = np.asarray(table)
+        if a.dtype != ATTENUATION_DTYPE:
+            sig = np.asarray(table, np.float32).reshape(-1, 3)
+            a = np.zeros(len(sig), ATTENUATION_DTYPE)
+            a["sigma"] = sig
+        a = np.ascontiguousarray(a, ATTENUATION_DTYPE).reshape(-1)
+        self.check(self.lib.rt3_scene_set_attenuation(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    def attenuation_info(self):
+        """flattened geometries the built structure holds as absorbing (rt3_attenuation_info): 0 = no table, k_absorb is not launched"""
+        n = C.c_uint32(0)
+        self.check(self.lib.rt3_attenuation_info(self.h, C.byref(n)))
+        return int(n.value)
 
     def set_pane_shadows(self, on):
         """pane shadows (rt3_scene_set_pane_shadows): shadow rays cross thin-walled glass attenuated.  A mode of the
@@ -486,6 +508,25 @@ class Context:
         self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ADAPTIVE_COMPACT, inp.ctypes.data, n, out.ctypes.data))
         assert int(out[1]) == n_blocks
         return int(out[0]), out[2:2 + n_blocks], out[2 + n_blocks:2 + n_blocks + n], out[2 + n_blocks + n:].reshape(n, 2)
+
+    def selftest_absorb(self, rows):
+        """Self-test op 36: the absorption rule on rows (n, 13) float32 {T rgb, sigma rgb, t, d xyz, n xyz}.  Returns (T' (n, 3) float32,
+        applied (n,) bool)."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 13)
+        out = np.zeros((len(rows), 4), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ABSORB, rows.ctypes.data, len(rows), out.ctypes.data))
+        return out[:, :3].copy().view(np.float32), out[:, 3] != 0
+
+    def selftest_absorb_queue(self, records, groups):
+        """Self-test op 37: k_absorb on the queue `records` (n, 10) of 32-bit words {d xyz, t, u, v, prim, T rgb} over the built scene,
+        launched with `groups` workgroups.  Returns T' (n, 3) uint32.  The library fails the call when the kernel wrote anything but the
+        throughput words of the n records."""
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 10)
+        n = len(records)
+        inp = np.concatenate([np.array([groups], np.uint32), records.reshape(-1)])
+        out = np.zeros(3 * max(n, 1), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ABSORB_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return out[: 3 * n].reshape(n, 3)
 
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))

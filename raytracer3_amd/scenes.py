@@ -9,6 +9,7 @@
                     (the asset lost its node transforms and its emission) so that a render from CORNELL_REF_CAMERA lines up with
                     that image.  Informational: Cycles is not this estimator and the display transforms differ.
 * `glass_cornell()` the Cornell box with a solid glass sphere and a thin-walled tinted pane.
+* `amber_cornell()` the Cornell box with absorbing glass: an amber block and two green spheres of two sizes.
 * `sky(w, h)`       equirect RGB32F gradient sky + 0.5 degree sun disc (peak radiance 5e4).
 All surfaces carry normals facing the side they are meant to be seen from.
 """
@@ -402,6 +403,34 @@ def glass_cornell() -> Mesh:
                 np.ascontiguousarray(np.concatenate([mesh.indices, add.indices]), np.uint32), np.concatenate([mesh.geometries, g]),
                 np.concatenate([mesh.prim_counts, add.prim_counts]).astype(np.uint32), mesh.names + add.names,
                 transmission=np.concatenate([mesh.transmission, add.transmission]))
+
+
+def _append(mesh: Mesh, add: Mesh) -> Mesh:
+    """`mesh` followed by the geometries of `add`, with the glass and absorption tables of both"""
+    g = add.geometries.copy()
+    g["index_offset"] += len(mesh.indices)
+    g["vertex_offset"] += len(mesh.vertices)
+    return Mesh(np.ascontiguousarray(np.concatenate([mesh.vertices, add.vertices]), np.float32),
+                np.ascontiguousarray(np.concatenate([mesh.indices, add.indices]), np.uint32), np.concatenate([mesh.geometries, g]),
+                np.concatenate([mesh.prim_counts, add.prim_counts]).astype(np.uint32), mesh.names + add.names,
+                transmission=np.concatenate([mesh.transmission, add.transmission]),
+                attenuation=np.concatenate([mesh.attenuation, add.attenuation]),
+                attenuation_source=np.concatenate([mesh.attenuation_source if mesh.attenuation_source is not None
+                                                   else np.tile([1.0, 1.0, 1.0, np.inf], (len(mesh.geometries), 1)), add.attenuation_source]))
+
+
+def amber_cornell(absorb=True) -> Mesh:
+    """The glass Cornell box with absorbing glass: an amber block of solid glass leaning against the short block, and two
+    green spheres of the same glass, one of twice the other's radius -- the large one is the darker and the more saturated.  `absorb` False:
+    the same geometry with every attenuation at its default, which launches nothing new."""
+    inf = float("inf")
+    amber = dict(attenuation_color=(0.95, 0.55, 0.12), attenuation_distance=0.25 if absorb else inf)
+    green = dict(attenuation_color=(0.35, 0.9, 0.45), attenuation_distance=0.3 if absorb else inf)
+    mb = MeshBuilder()
+    _sphere(mb, "green_sphere_large", [0.4, 0.9, 0.3], 0.3, 48, 24, Material((1.0, 1.0, 1.0), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=0, **green))
+    _sphere(mb, "green_sphere_small", [0.0, 0.152, 0.85], 0.15, 32, 16, Material((1.0, 1.0, 1.0), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=0, **green))
+    _box(mb, "amber_block", [-0.8, 0.002, 0.25], [-0.35, 0.8, 0.5], Material((1.0, 1.0, 1.0), 0.0, 0.0, transmission=1.0, ior=1.5, thin_walled=0, **amber))
+    return _append(cornell(), mb.build())
 
 
 SUNLIT_ROOM_CAMERA = dict(position=(0.0, 1.3, 2.6), direction=(-0.25, -0.12, -1.0), fov_deg=60.0)

@@ -36,7 +36,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -86,6 +86,8 @@ def main():
         mesh, cam_kw = scenes.material_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "glass_cornell":  # a solid glass sphere and a thin-walled pane; set_scene switches the pinhole lens on
         mesh, cam_kw = scenes.glass_cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "amber_cornell":  # absorbing glass: an amber block and two green spheres of two sizes
+        mesh, cam_kw = scenes.amber_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "sunlit_room":  # a closed room lit through one window by the sky and a sun; try --pane-shadows
         mesh, cam_kw = scenes.sunlit_room(), scenes.SUNLIT_ROOM_CAMERA
     elif args.scene == "cornell_ref":
