@@ -295,6 +295,31 @@ int rt3_scene_set_transmission(rt3_ctx *ctx, const rt3_transmission *t, uint32_t
 int rt3_scene_set_pane_shadows(rt3_ctx *ctx, int on);
 int rt3_scene_get_pane_shadows(rt3_ctx *ctx, int *on);
 int rt3_pane_shadow_info(rt3_ctx *ctx, uint32_t *n_panes);
+/* ---- rough transmission: frosted glass, transmission through GGX microfacets.  No reference counterpart.  DESIGN.md section 4t.  A mode of
+ *      the context, off by default, that survives rt3_scene_set_geometry.  A geometry is frosted when its transmission is > 0 and its material
+ *      roughness factor is > 0 or it names a metallic-roughness texture, solid or thin-walled; rt3_accel_build classifies.  A frosted geometry is
+ *      never a pane (rt3_scene_set_pane_shadows): shadow rays are occluded by it.  With the mode on, in a built scene with a frosted geometry,
+ *      a glass vertex (selected as always) on such a geometry whose roughness alpha at the hit (factor x texture, as the opaque BSDF takes it:
+ *      not squared, no floor) is > 0 follows this rule instead of the smooth one; alpha = 0 is the smooth vertex, bit for bit:
+ *       - ud = d / |d|; enter = dot(n, ud) < 0 (n the shading normal, not face-forwarded); n_in = enter ? n : -n; wo = -ud in the tangent frame
+ *         about n_in; wo.z <= 1e-5 ends the path.
+ *       - m = the opaque BSDF's sample_vndf(alpha, wo, u2, u3): a GGX micro-normal visible from wo; u2, u3 are the draws at RNG indices
+ *         0x50000000 + 2 (s B + b) + {0, 1} (no blue-noise shift).
+ *       - cos_i = dot(wo, m); eta, cos_t^2, F and the thin-walled F' are the smooth vertex's expressions at this cos_i; the smooth vertex's
+ *         event draw picks reflection when u < F.
+ *       - reflection r = 2 cos_i m - wo, valid when r.z > 1e-5; solid transmission t = -wo / eta + (cos_i / eta - cos_t) m, valid when
+ *         t.z < -1e-5; thin-walled transmission (r.x, r.y, -r.z), valid when r.z > 1e-5 (a thin rough slab as one lobe: an approximation).  An
+ *         invalid sample ends the path: no extension ray, no last-vertex sky ray (single scattering: that energy is lost).
+ *       - throughput x (tint when transmitted) x G1(|wi.z|, alpha^2), the separable Smith term left of f cos / pdf.
+ *      Everything else is the glass vertex's: no light sample, the delta markers in the pdf slot, the last-vertex sky ray, emission.  So a
+ *      frosted surface is lit by BSDF-sampled paths only and punctual lights never light it.
+ *      on other than 0 or 1 is RT3_E_INVALID and changes nothing.  A change takes effect at the next rt3_accel_build; until then an existing
+ *      structure is unusable; rt3_accel_refit and rt3_accel_import keep the classification (it lives in the glass side table).  Both instance
+ *      modes.  With the mode on and no frosted geometry nothing differs from off.  rt3_rough_transmission_info: the flattened geometries with
+ *      triangles that the built structure holds as frosted, 0 while the mode is off; RT3_E_STATE before a build. ---- */
+int rt3_scene_set_rough_transmission(rt3_ctx *ctx, int on);
+int rt3_scene_get_rough_transmission(rt3_ctx *ctx, int *on);
+int rt3_rough_transmission_info(rt3_ctx *ctx, uint32_t *n_frosted);
 /* ---- absorbing glass: Beer-Lambert attenuation inside solid dielectrics.  No reference counterpart.  DESIGN.md section 4s.  One entry per
  *      geometry of the last rt3_scene_set_geometry; n = 0: none, and rt3_scene_set_geometry resets every geometry to that.  sigma: the
  *      absorption coefficient per colour channel, per world-space unit of length (glTF KHR_materials_volume:

@@ -40,6 +40,7 @@ SELFTEST_ADAPTIVE_COMPACT = 35  # rt3_selftest_eval op: the "adaptive" pass's li
 ADAPTIVE_TILE = 2048  # list entries per compaction block (op 35 returns one offset per tile)
 SELFTEST_ABSORB = 36  # rt3_selftest_eval op: {T rgb, sigma rgb, t, d xyz, n xyz} (13 words) -> {T' rgb, applied (u32)} (4), the absorption rule
 SELFTEST_ABSORB_QUEUE = 37  # rt3_selftest_eval op: k_absorb on a caller-made queue over the built scene (Context.selftest_absorb_queue)
+SELFTEST_FROST = 38  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, alpha, u_event, u2, u3} (12 words) -> {event (u32: 0 reflect, 1 transmit, 2 invalid), direction, F, weight} (6), the frosted vertex rule
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
@@ -48,6 +49,7 @@ EXPORTS = [
     "rt3_scene_set_material_textures",
     "rt3_scene_set_transmission", "rt3_scene_set_attenuation", "rt3_attenuation_info",
     "rt3_scene_set_pane_shadows", "rt3_scene_get_pane_shadows", "rt3_pane_shadow_info",
+    "rt3_scene_set_rough_transmission", "rt3_scene_get_rough_transmission", "rt3_rough_transmission_info",
     "rt3_scene_set_instances",
     "rt3_accel_build", "rt3_accel_info", "rt3_accel_levels", "rt3_accel_exit_table_info", "rt3_accel_download", "rt3_accel_import", "rt3_sky_download",
     "rt3_scene_update_vertices", "rt3_accel_refit", "rt3_light_info", "rt3_light_download",
@@ -198,6 +200,9 @@ def load():
         "rt3_scene_set_pane_shadows": (i32, [vp, i32]),
         "rt3_scene_get_pane_shadows": (i32, [vp, C.POINTER(i32)]),
         "rt3_pane_shadow_info": (i32, [vp, C.POINTER(u32)]),
+        "rt3_scene_set_rough_transmission": (i32, [vp, i32]),
+        "rt3_scene_get_rough_transmission": (i32, [vp, C.POINTER(i32)]),
+        "rt3_rough_transmission_info": (i32, [vp, C.POINTER(u32)]),
         "rt3_scene_set_instances": (i32, [vp, vp, u32]),
         "rt3_accel_build": (i32, [vp, pu32]),
         "rt3_accel_info": (i32, [vp, pu32, pu32, pu32, pu32]),

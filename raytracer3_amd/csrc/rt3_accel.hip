@@ -91,7 +91,7 @@ static int flatten_world(rt3_ctx* c) {
     std::vector<MatTexDev> mats;
     std::vector<GlassDev> glass;
     std::vector<AbsorbDev> absorb;
-    uint32_t n_absorbing = 0;
+    uint32_t n_absorbing = 0, n_frosted = 0;
     std::vector<uint32_t> first;
     std::vector<Placed> placed;
     uint64_t total = 0;
@@ -131,6 +131,10 @@ static int flatten_world(rt3_ctx* c) {
                 GlassDev gd;
                 memcpy(&gd, &c->scene.h_transmission[g], sizeof(gd));
                 if (pane_geometry(c, g)) gd.pad = kGlassPaneBit;  // (the reserved word is 0 as uploaded)
+                if (frosted_geometry(c, g)) {  // (never a pane)
+                    gd.pad = kGlassFrostBit;
+                    if (c->scene.h_prim_counts[g] > 0) n_frosted++;
+                }
                 glass.push_back(gd);
             }
             {  // absorption: a geometry that does not absorb holds zeros, whatever was uploaded for it
@@ -174,6 +178,7 @@ static int flatten_world(rt3_ctx* c) {
         HIPC(c, hipMemcpy(c->accel.d_glass.get(), glass.data(), nf * sizeof(GlassDev), hipMemcpyHostToDevice));
         c->accel.has_glass = true;
     }
+    c->accel.n_frosted = n_frosted;
     c->accel.n_absorbing = 0;
     if (n_absorbing) {  // (kept only when some flattened geometry absorbs)
         if (int r = dev_alloc(c, c->accel.d_absorb, nf)) return r;
@@ -779,6 +784,11 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
 int rt3_pane_shadow_info(rt3_ctx* c, uint32_t* n_panes) {
     if (!c || !c->accel.built) return fail(c, RT3_E_STATE, "no acceleration structure built");
     if (n_panes) *n_panes = c->accel.n_panes;
+    return RT3_OK;
+}
+int rt3_rough_transmission_info(rt3_ctx* c, uint32_t* n_frosted) {
+    if (!c || !c->accel.built) return fail(c, RT3_E_STATE, "no acceleration structure built");
+    if (n_frosted) *n_frosted = c->accel.n_frosted;
     return RT3_OK;
 }
 int rt3_attenuation_info(rt3_ctx* c, uint32_t* n_absorbing) {

@@ -567,6 +567,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
         else if (op == 32) launch_selftest_glass(c->stream, d_in.get(), n, d_out.get());
         else if (op == 33) launch_selftest_roulette(c->stream, d_in.get(), n, d_out.get());
         else if (op == 36) launch_selftest_absorb(c->stream, d_in.get(), n, d_out.get());
+        else if (op == 38) launch_selftest_frost(c->stream, d_in.get(), n, d_out.get());
         else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);
     }

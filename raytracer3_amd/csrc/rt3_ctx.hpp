@@ -202,6 +202,9 @@ struct rt3_ctx {
         // pane shadows: flattened geometries with triangles that the last rt3_accel_build classified as panes (0 while
         // the mode is off) and the first alpha slot of the masked ones' marked records.  marked: the records carry mask or pane words
         uint32_t n_panes = 0, pane_first_slot = 0;
+        // rough transmission: flattened geometries with triangles that the last rt3_accel_build classified as frosted (0
+        // while the mode is off); their d_glass entries carry kGlassFrostBit
+        uint32_t n_frosted = 0;
         bool marked = false;
         rt3::LbvhResult bvh;
         rt3::ShadeRecords shade;
@@ -296,6 +299,9 @@ struct rt3_ctx {
     // rt3_scene.hip: pane shadows (rt3_scene_set_pane_shadows): the mode, read by the next rt3_accel_build; off by default.
     // It lives here, not in `scene`: rt3_scene_set_geometry leaves it as it is
     bool pane_shadows = false;
+    // rt3_scene.hip: rough transmission (rt3_scene_set_rough_transmission): the mode, read by the next rt3_accel_build; off
+    // by default; like pane_shadows it is not part of `scene`
+    bool rough_transmission = false;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot
@@ -387,9 +393,17 @@ inline bool absorbing_geometry(const rt3_ctx* c, uint32_t g) {
     const float* s = c->scene.h_attenuation[g].sigma;
     return s[0] > 0.0f || s[1] > 0.0f || s[2] > 0.0f;
 }
-// is uploaded geometry g a pane (rt3_scene_set_pane_shadows)?  Mode on, transmission > 0, thin-walled, no normal texture
+// is uploaded geometry g frosted (rt3_scene_set_rough_transmission)?  Mode on, transmission > 0, and a roughness that can
+// be > 0 somewhere: the factor is, or a metallic-roughness texture scales it
+inline bool frosted_geometry(const rt3_ctx* c, uint32_t g) {
+    if (!c->rough_transmission || !any_glass(c)) return false;
+    if (!(c->scene.h_transmission[g].transmission > 0.0f)) return false;
+    return c->scene.h_geoms[g].roughness > 0.0f || (any_mat_tex(c) && c->scene.h_mat_tex[g].metallic_roughness_texture >= 0);
+}
+// is uploaded geometry g a pane (rt3_scene_set_pane_shadows)?  Mode on, transmission > 0, thin-walled, no normal texture,
+// not frosted (a path through a frosted pane does not go straight on)
 inline bool pane_geometry(const rt3_ctx* c, uint32_t g) {
-    if (!c->pane_shadows || !any_glass(c)) return false;
+    if (!c->pane_shadows || !any_glass(c) || frosted_geometry(c, g)) return false;
     const rt3_transmission& t = c->scene.h_transmission[g];
     if (!(t.transmission > 0.0f) || t.thin_walled != 1u) return false;
     return !any_mat_tex(c) || c->scene.h_mat_tex[g].normal_texture < 0;

@@ -113,6 +113,7 @@ void launch_gbuffer(hipStream_t st, const SceneDev& sc, const uint32_t* pixels, 
 // of `stride` words with each ray's vertex (its index in the input queue) and a second plane for k_shadow's occlusion words; launch_light
 // finishes the unoccluded light samples from them.  Only without material textures, punctual lights and glass.
 // pane_dist (with glass): k_shade_pane and its per-path distance array, one float per path of the batch, zero at its start
+// frost (with glass): k_shade_frost -- the built scene has a frosted geometry (pane_dist as above, or null)
 // exit (with defer, no emitter table): k_shade_defer_exit, which tries a sky shadow ray against the leaf of its
 // exit-table entry and queues it only when that leaf does not occlude it
 struct ShadeExit {
@@ -122,7 +123,7 @@ struct ShadeExit {
     uint32_t* decided = nullptr;              // the bounce's word for the shadow rays that were generated and decided here, never queued
 };
 void launch_shade(hipStream_t st, bool first, ShadeLaunch L, bool punct = false, const GlassDev* glass = nullptr, bool defer = false, float* pane_dist = nullptr,
-                  const ShadeExit* exit = nullptr);
+                  const ShadeExit* exit = nullptr, bool frost = false);
 void launch_light(hipStream_t st, bool first, ShadeLaunch L);
 void launch_pixbn(hipStream_t st, const uint32_t* pixels, uint32_t npix, const uint8_t* bluenoise, uint32_t bn_w, uint32_t bn_h, uint2* out);
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
@@ -148,6 +149,9 @@ void launch_selftest_lens(hipStream_t st, const uint32_t* in, uint32_t n, uint32
 // self-test op 32: glass_sample, {ior, thin_walled, d xyz, n xyz, u} -> {event, direction xyz, F} (rt3_shade.hip)
 constexpr uint32_t kSelftestGlassIn = 9, kSelftestGlassOut = 5;
 void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 38: the frosted vertex rule, {ior, thin_walled, d xyz, n xyz, alpha, u_event, u2, u3} -> {event, direction xyz, F, weight} (rt3_shade.hip)
+constexpr uint32_t kSelftestFrostIn = 12, kSelftestFrostOut = 6;
+void launch_selftest_frost(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
 // Russian roulette on the extension queue (rt3_roulette.hip); rt3_roulette.hpp has the argument.  The grid is sized
 // for n_max records (an upper bound of *in_count), or is `groups` workgroups when that is not 0 (self-test op 34)
 struct RouletteLaunch;

@@ -391,7 +391,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             ShadeExit sx = ps.exit;
             sx.decided = dec_cnt + bn;
             launch_shade(c->stream, bn == 0 && !lens, L, ps.punct, c->accel.has_glass ? c->accel.d_glass.get() : nullptr, ps.defer,
-                         ps.panes ? c->work.pane_dist.get() : nullptr, shade_exit ? &sx : nullptr);
+                         ps.panes ? c->work.pane_dist.get() : nullptr, shade_exit ? &sx : nullptr, c->accel.has_glass && c->accel.n_frosted != 0u);
         }
         cur ^= 1;
         if (nee) {

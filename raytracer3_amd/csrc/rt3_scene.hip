@@ -331,6 +331,20 @@ int rt3_scene_get_pane_shadows(rt3_ctx* c, int* on) {
     *on = c->pane_shadows ? 1 : 0;
     return RT3_OK;
 }
+// rough transmission: the mode is the context's, the classification is made by the next build
+int rt3_scene_set_rough_transmission(rt3_ctx* c, int on) {
+    if (!c) return RT3_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, RT3_E_INVALID, "rough transmission: the mode is 0 or 1");
+    if ((on != 0) == c->rough_transmission) return RT3_OK;
+    c->rough_transmission = on != 0;
+    invalidate_topology(c);  // the glass side table carries the frost marks, and a frosted pane stops being a pane: a new build, not a refit
+    return RT3_OK;
+}
+int rt3_scene_get_rough_transmission(rt3_ctx* c, int* on) {
+    if (!c || !on) return fail(c, RT3_E_INVALID, "rough transmission: NULL");
+    *on = c->rough_transmission ? 1 : 0;
+    return RT3_OK;
+}
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
 // arithmetic, in double, in the same order): radiance stored as RGB9E5 (packing.slang:99-162), marginal CDF over rows, one alias
 // table per row with 16-bit keep-thresholds, pdf_uv = the density the quantised tables really realise.

@@ -187,6 +187,11 @@ bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
         *out_w = kSelftestAbsorbOut;
         return true;
     }
+    if (op == 38) {  // the frosted vertex rule (k_selftest_frost, rt3_shade.hip)
+        *in_w = kSelftestFrostIn;
+        *out_w = kSelftestFrostOut;
+        return true;
+    }
     static const uint32_t w[30][2] ={{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
                                       {2, 9}, {2, 4}, {3, 1}, {1, 1}, {3, 11}};

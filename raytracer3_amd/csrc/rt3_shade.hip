@@ -165,7 +165,7 @@ constexpr int shade_waves(bool mat) { return mat ? 4 : 6; }
 template <bool FIRST, bool GLDS, bool EMIT = false, bool MAT = false>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(MAT), shade_waves(MAT)))) void k_shade(ShadeLaunch a) {
     constexpr bool PUNCT = false, GLASS = false, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false, EXIT = false;
+    constexpr bool PANE = false, EXIT = false, FROST = false;
     float* const pane_dist = nullptr;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool MAT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_punct(ShadeLaunch a) {
     constexpr bool EMIT = true, PUNCT = true, GLASS = false, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false, EXIT = false;
+    constexpr bool PANE = false, EXIT = false, FROST = false;
     float* const pane_dist = nullptr;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_glass(ShadeLaunch a) {
     constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false;
-    constexpr bool PANE = false, EXIT = false;
+    constexpr bool PANE = false, EXIT = false, FROST = false;
     float* const pane_dist = nullptr;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
@@ -200,7 +200,19 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 // so that every other instance keeps its name and its instructions.  Registers and scratch per instance: DESIGN.md section 4q.
 template <bool GLDS, bool EMIT, bool MAT, bool PUNCT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_pane(ShadeLaunch a, float* pane_dist) {
-    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false, PANE = true, EXIT = false;
+    constexpr bool FIRST = false, GLASS = true, DEFER = false, LIGHT = false, PANE = true, EXIT = false, FROST = false;
+    const ShadeExit x = {};
+#include "rt3_shade_body.inc"
+}
+// FROST: k_shade_glass / k_shade_pane for a built scene with a frosted geometry under rt3_scene_set_rough_transmission.  A
+// glass vertex on such a geometry whose roughness is > 0 takes its event at a GGX micro-normal (frost_sample); every other vertex does what
+// it does in the PANE twin.  A kernel of its own name, so that every other instance keeps its name and its instructions.  Twelve
+// instances: {no light table, EMIT, EMIT + PUNCT} x MAT x PANE; the geometry tables are read from global memory (no GLDS twin: staging is an
+// optimisation for small scenes, and doubling the build's largest kernels for it waits for a measurement).  pane_dist is null without PANE.
+// Registers and scratch per instance: DESIGN.md section 4t.
+template <bool EMIT, bool MAT, bool PUNCT, bool PANE>
+__global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(true), shade_waves(true)))) void k_shade_frost(ShadeLaunch a, float* pane_dist) {
+    constexpr bool FIRST = false, GLDS = false, GLASS = true, DEFER = false, LIGHT = false, EXIT = false, FROST = true;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
 }
@@ -211,7 +223,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS, bool EMIT>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer(ShadeLaunch a) {
     constexpr bool MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
-    constexpr bool PANE = false, EXIT = false;
+    constexpr bool PANE = false, EXIT = false, FROST = false;
     float* const pane_dist = nullptr;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_shade_defer_exit(ShadeLaunch a, ShadeExit x) {
     constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = true, LIGHT = false;
-    constexpr bool PANE = false, EXIT = true;
+    constexpr bool PANE = false, EXIT = true, FROST = false;
     float* const pane_dist = nullptr;
 #include "rt3_shade_body.inc"
 }
@@ -235,7 +247,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
 template <bool FIRST, bool GLDS>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(false), shade_waves(false)))) void k_light(ShadeLaunch a) {
     constexpr bool EMIT = false, MAT = false, PUNCT = false, GLASS = false, DEFER = false, LIGHT = true;
-    constexpr bool PANE = false, EXIT = false;
+    constexpr bool PANE = false, EXIT = false, FROST = false;
     float* const pane_dist = nullptr;
     const ShadeExit x = {};
 #include "rt3_shade_body.inc"
@@ -251,6 +263,30 @@ __global__ void k_selftest_glass(const uint32_t* __restrict__ in, uint32_t n, ui
     o[0] = e.transmit;
     o[1] = __float_as_uint(e.dir.x); o[2] = __float_as_uint(e.dir.y); o[3] = __float_as_uint(e.dir.z);
     o[4] = __float_as_uint(e.F);
+}
+// self-test op 38: {ior, thin_walled, d xyz, n xyz, alpha, u_event, u2, u3} -> {event (0 reflect / 1 transmit / 2 invalid), direction xyz, F,
+// weight}: the vertex rule of a frosted geometry as the kernels apply it -- frost_sample at alpha > 0, glass_sample (weight 1) at alpha = 0
+__global__ void k_selftest_frost(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = in + kSelftestFrostIn * (size_t)i;
+    auto F = [](uint32_t u) { return __uint_as_float(u); };
+    const V3 d = v3(F(p[2]), F(p[3]), F(p[4])), nn = v3(F(p[5]), F(p[6]), F(p[7]));
+    FrostEvent e;
+    if (F(p[8]) > 0.0f) {
+        e = frost_sample(F(p[0]), p[1] != 0u, d, nn, F(p[8]), F(p[9]), F(p[10]), F(p[11]));
+    } else {
+        const GlassEvent g = glass_sample(F(p[0]), p[1] != 0u, d, nn, F(p[9]));
+        e.event = g.transmit;
+        e.dir = g.dir;
+        e.F = g.F;
+        e.weight = 1.0f;
+    }
+    uint32_t* o = out + kSelftestFrostOut * (size_t)i;
+    o[0] = e.event;
+    o[1] = __float_as_uint(e.dir.x); o[2] = __float_as_uint(e.dir.y); o[3] = __float_as_uint(e.dir.z);
+    o[4] = __float_as_uint(e.F);
+    o[5] = __float_as_uint(e.weight);
 }
 
 // refrence_mode.slang:59-65 : radiance = (sum over samples, in sample order) / S, then blend with PrevLight
@@ -313,7 +349,8 @@ static void dispatch_shade(bool first, bool glds, bool emit, bool mat, bool punc
 // defer: the k_shade_defer instance (the caller has checked that the scene is inside its cover: shade_defer_covers)
 // pane_dist: the built scene has panes and pane shadows are on (with `glass`): k_shade_pane, twelve instances shaped like k_shade_glass's
 // exit (with defer and an empty emitter table): k_shade_defer_exit
-void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer, float* pane_dist, const ShadeExit* exit) {
+// frost (with glass): the built scene has a frosted geometry: k_shade_frost, twelve instances {no table, EMIT, EMIT + PUNCT} x MAT x PANE
+void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const GlassDev* glass, bool defer, float* pane_dist, const ShadeExit* exit, bool frost) {
     a.npix_div = make_fastdiv(a.npix);
     const unsigned grid = grid_for(a.n_first, kShadeBlock, 8192);
     const bool glds = a.sc.shade_geoms != nullptr && a.sc.n_geoms <= kShadeGeomsLds;
@@ -336,6 +373,11 @@ void launch_shade(hipStream_t st, bool first, ShadeLaunch a, bool punct, const G
         if constexpr (!decltype(f)::value) {
             if (glass != nullptr) {
                 a.glass = glass;  // (in the slot of the G-buffer, which these kernels do not read)
+                if (frost) {
+                    if (pane_dist != nullptr) hipLaunchKernelGGL((k_shade_frost<decltype(e)::value, decltype(m)::value, decltype(p)::value, true>), dim3(grid), dim3(kShadeBlock), 0, st, a, pane_dist);
+                    else hipLaunchKernelGGL((k_shade_frost<decltype(e)::value, decltype(m)::value, decltype(p)::value, false>), dim3(grid), dim3(kShadeBlock), 0, st, a, pane_dist);
+                    return;
+                }
                 if (pane_dist != nullptr) {
                     hipLaunchKernelGGL((k_shade_pane<decltype(g)::value, decltype(e)::value, decltype(m)::value, decltype(p)::value>), dim3(grid), dim3(kShadeBlock), 0, st, a, pane_dist);
                     return;
@@ -360,6 +402,9 @@ void launch_light(hipStream_t st, bool first, ShadeLaunch a) {
 }
 void launch_selftest_glass(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out) {
     hipLaunchKernelGGL(k_selftest_glass, dim3((n + 255) / 256), dim3(256), 0, st, in, n, out);
+}
+void launch_selftest_frost(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out) {
+    hipLaunchKernelGGL(k_selftest_frost, dim3((n + 255) / 256), dim3(256), 0, st, in, n, out);
 }
 void launch_accumulate(hipStream_t st, const GConstDev& g, const uint32_t* pixels, uint32_t npix, uint32_t width, const float* depth,
                        const float* lacc, size_t stride, uint32_t sb, int first_batch, int last_batch, float* radsum, void* light,

@@ -9,6 +9,9 @@
 // EXIT (k_shade_defer_exit, DESIGN.md section 4r): DEFER with the structure's exit table in scope (`x`, ShadeExit).  A lane that would send a sky
 // shadow ray first tries the leaf its exit cell names -- k_shadow_exit's first step, with its cell rule and its triangle test
 // (rt3_leaf_test.hpp) -- and sends the ray only when that leaf does not occlude it.  Every use is `EXIT && ...` or `if constexpr (EXIT)`.
+// FROST (k_shade_frost, DESIGN.md section 4t): GLASS in a built scene with a frosted geometry under rt3_scene_set_rough_transmission.  Every use is
+// `FROST && ...`.
+    static_assert(GLASS || !FROST, "a frosted geometry is a glass geometry");
     static_assert(GLASS || !PANE, "a pane is a glass geometry");
     static_assert(!(DEFER && LIGHT) && !((DEFER || LIGHT) && (MAT || PUNCT || GLASS)), "deferral covers the plain opaque instances");
     static_assert(!(FIRST && MAT), "the first vertex is read from the G-buffer");
@@ -371,13 +374,33 @@
                     // the event draw at index + 1; the normal is hit_finish's, not face-forwarded.  The extension ray carries a delta marker
                     // in its pdf slot (rt3_glass.hpp): whatever it finds counts with weight 1.  The last vertex sends the chosen direction
                     // out as its sky shadow ray instead: the weight-1 light sample every other last vertex has.
-                    const GlassEvent ev = glass_sample(gl.ior, gl.thin_walled != 0u, d, surf.normal, uniform_float(seed, kGlassRngBase + 2u * (sm * B + b) + 1u));
+                    // FROST (DESIGN.md section 4t): on a frosted geometry with roughness > 0 the event happens at a GGX micro-normal (frost_sample,
+                    // two more draws at kFrostRngBase, no blue-noise shift) and the throughput takes the sample's weight G1; an invalid
+                    // sample ends the path.  Roughness 0 is the smooth vertex, by glass_sample's own arithmetic.
+                    const bool frost_v = FROST && (gl.pad & kGlassFrostBit) != 0u && surf.roughness > 0.0f;
+                    bool frost_end = false;
+                    float frost_w = 1.0f;
+                    GlassEvent ev;
+                    if (FROST && frost_v) {
+                        const uint32_t fi = kFrostRngBase + 2u * (sm * B + b);
+                        const FrostEvent fe = frost_sample(gl.ior, gl.thin_walled != 0u, d, surf.normal, surf.roughness,
+                                                           uniform_float(seed, kGlassRngBase + 2u * (sm * B + b) + 1u), uniform_float(seed, fi), uniform_float(seed, fi + 1u));
+                        ev.transmit = fe.event == 1u ? 1u : 0u;
+                        ev.dir = fe.dir;
+                        ev.F = fe.F;
+                        frost_end = fe.event == 2u;
+                        frost_w = fe.weight;
+                    } else {
+                        ev = glass_sample(gl.ior, gl.thin_walled != 0u, d, surf.normal, uniform_float(seed, kGlassRngBase + 2u * (sm * B + b) + 1u));
+                    }
                     nd = ev.dir;
                     if (ev.transmit) Tn = T * surf.albedo;  // the tint: base colour x base-colour texture
+                    if (FROST && frost_v) Tn = Tn * frost_w;
                     // PANE (DESIGN.md section 4q): a path that goes straight on through a pane is still the sample of the vertex that chose its
                     // direction, whose light samples now cross the pane too: the pdf slot is handed on as it came, with the distance walked
                     const bool pane_on = PANE && (gl.pad & kGlassPaneBit) != 0u && ev.transmit != 0u;
-                    if (PANE && pane_on && !last) {
+                    if (FROST && frost_end) {  // no extension ray and no last-vertex sky ray
+                    } else if (PANE && pane_on && !last) {
                         pdf_n = pdf_b;
                         dist_n = pane_dist[pid] + t * sqrtf(dot(d, d));
                         emit_ext = true;

@@ -9,9 +9,10 @@
 //   asset_tool exr <sky.exr> <outdir>                 dump the decoded equirect image
 //   asset_tool png <image.png|.jpg> <outdir>          dump the decoded RGBA8 image (PNG or baseline JPEG)
 //   asset_tool bincode <file> <current|old> <outdir>  dump a processed-asset cache file (assets/mod.rs:118-137)
-//   asset_tool render <scene.glb> <sky.exr|-> <bluenoise.png|-> W H spp bounces flags px py pz dx dy dz fov_deg <out.bin>
+//   asset_tool render <scene.glb> <sky.exr|-> <bluenoise.png|-> W H spp bounces flags px py pz dx dy dz fov_deg <out.bin> [--rough-glass]
 //                                                     load -> upload -> gbuffer / refrence_mode / postprocess on the GPU;
-//                                                     out.bin = Light RGBA32F then colour RGBA32F
+//                                                     out.bin = Light RGBA32F then colour RGBA32F; --rough-glass: glass with
+//                                                     roughness > 0 is frosted (rt3_scene_set_rough_transmission)
 // Dumps are raw little-endian arrays + manifest.txt; tests/test_host_assets.py compares them with the Python loaders.
 // Only `render` needs librt3.so to find a GPU.
 #include <cstdio>
@@ -82,11 +83,12 @@ int main(int argc, char** argv) {
             fprintf(f, "meshlets %zu\nmaterials %zu\nvertices %zu\nindices %zu\nuploaded %d\n", pm.meshlets.size(), pm.materials.size(), pm.vertices.size() / 8,
                     pm.indices.size(), pm.uploaded ? 1 : 0);
             fclose(f);
-        } else if (cmd == "render" && argc == 18) {
+        } else if (cmd == "render" && (argc == 18 || (argc == 19 && std::string(argv[18]) == "--rough-glass"))) {
             A::Mesh mesh = A::load_glb(argv[2]);
             const uint32_t W = (uint32_t)atoi(argv[5]), H = (uint32_t)atoi(argv[6]);
             rt3::Context ctx(0);
             ctx.check(rt3_set_tile_partition(ctx.raw(), W, H, 0, 1), "partition");
+            if (argc == 19) ctx.check(rt3_scene_set_rough_transmission(ctx.raw(), 1), "rough transmission");  // before the build: it classifies
             A::upload(ctx.raw(), mesh);
             if (std::string(argv[3]) != "-") A::upload_sky(ctx.raw(), A::read_exr(argv[3]));
             if (std::string(argv[4]) != "-") {

@@ -245,6 +245,22 @@ class Context:
         self.check(self.lib.rt3_pane_shadow_info(self.h, C.byref(n)))
         return int(n.value)
 
+    def set_rough_transmission(self, on):
+        """rough transmission (rt3_scene_set_rough_transmission): glass with roughness > 0 scatters through GGX
+        microfacets.  A mode of the context (set_geometry keeps it); a change takes effect at the next build_accel()."""
+        self.check(self.lib.rt3_scene_set_rough_transmission(self.h, int(on)))
+
+    def get_rough_transmission(self):
+        on = C.c_int32(0)
+        self.check(self.lib.rt3_scene_get_rough_transmission(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def rough_transmission_info(self):
+        """flattened geometries the built structure holds as frosted (rt3_rough_transmission_info): 0 while the mode is off"""
+        n = C.c_uint32(0)
+        self.check(self.lib.rt3_rough_transmission_info(self.h, C.byref(n)))
+        return int(n.value)
+
     def set_instances(self, instances):
         """instances: [(geometry_first, geometry_count, 4x4 matrix as numpy, object -> world)] -- Instance + Transform of
         src/renderer/world/mod.rs:46-60; [] = every geometry once under the identity.  Takes effect at the next build_accel()."""

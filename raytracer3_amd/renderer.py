@@ -260,6 +260,16 @@ class PathTracer:
         if self._scene_set:
             self.ctx.build_accel()
 
+    def set_rough_transmission(self, on=True):
+        """Rough transmission (ctx.set_rough_transmission): glass whose material roughness is > 0 is frosted -- its
+        glass vertices reflect and refract at GGX micro-normals.  Rebuilds, as set_scene does, when the mode changes and a scene is set.
+        Frosted glass is lit by BSDF-sampled paths only; a frosted pane is no pane of set_pane_shadows."""
+        if bool(on) == self.ctx.get_rough_transmission():
+            return
+        self.ctx.set_rough_transmission(bool(on))
+        if self._scene_set:
+            self.ctx.build_accel()
+
     def set_lights(self, lights=None):
         """Replace the world's punctual lights (assets.LIGHT_DTYPE; None forgets them).  No rebuild: frames with F_NEE_PUNCTUAL in their
         flags sample them from the next frame on.  Moved lights' shadows lag in temporal history like any moved light."""

@@ -405,6 +405,16 @@ def glass_cornell() -> Mesh:
                 transmission=np.concatenate([mesh.transmission, add.transmission]))
 
 
+def frosted_cornell() -> Mesh:
+    """glass_cornell() with roughness on its glass: the sphere at 0.3, the pane at 0.15.  Under
+    PathTracer.set_rough_transmission(True) the sphere is matte-translucent and the room behind the pane is blurred; without the mode it is
+    glass_cornell()'s picture."""
+    mesh = glass_cornell()
+    mesh.geometries["roughness"][mesh.names.index("glass_sphere")] = 0.3
+    mesh.geometries["roughness"][mesh.names.index("glass_pane")] = 0.15
+    return mesh
+
+
 def _append(mesh: Mesh, add: Mesh) -> Mesh:
     """`mesh` followed by the geometries of `add`, with the glass and absorption tables of both"""
     g = add.geometries.copy()

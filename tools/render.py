@@ -36,7 +36,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell", "frosted_cornell"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -62,6 +62,7 @@ def main():
     ap.add_argument("--roulette", nargs="?", type=int, const=2, default=None, metavar="START",
                     help="Russian roulette on the extension rays from vertex START on (default 2), survival floor 1/16 (DESIGN.md section 4o)")
     ap.add_argument("--pane-shadows", action="store_true", help="sample lights through thin-walled glass (PathTracer.set_pane_shadows, DESIGN.md section 4q)")
+    ap.add_argument("--rough-glass", action="store_true", help="frosted glass: rough transmission on glass with roughness > 0 (PathTracer.set_rough_transmission, DESIGN.md section 4t)")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
     ap.add_argument("--side-by-side", default=None, help="with --compare: write [render | reference] at the reference's size here")
     ap.add_argument("--report", default=None, help="with --compare: write the numbers and the scene parameters as JSON here")
@@ -86,6 +87,8 @@ def main():
         mesh, cam_kw = scenes.material_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "glass_cornell":  # a solid glass sphere and a thin-walled pane; set_scene switches the pinhole lens on
         mesh, cam_kw = scenes.glass_cornell(), scenes.CORNELL_CAMERA
+    elif args.scene == "frosted_cornell":  # glass_cornell with roughness 0.3 on the sphere and 0.15 on the pane; try --rough-glass
+        mesh, cam_kw = scenes.frosted_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "amber_cornell":  # absorbing glass: an amber block and two green spheres of two sizes
         mesh, cam_kw = scenes.amber_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "sunlit_room":  # a closed room lit through one window by the sky and a sun; try --pane-shadows
@@ -102,6 +105,7 @@ def main():
         flags |= L.F_NEE_PUNCTUAL
     pt = PathTracer((W, H))
     pt.set_pane_shadows(args.pane_shadows)
+    pt.set_rough_transmission(args.rough_glass)
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
