@@ -718,8 +718,9 @@ int rt3_adaptive_get_coverage(rt3_ctx *ctx, int *on);
  *      Coupled passes while a lens is set: "postprocess" takes every pixel from In (the Depth == background branch would put the pinhole sky
  *      over half of each antialiased silhouette); "adaptive" returns RT3_E_STATE (it selects pixels by G-buffer depth) unless
  *      rt3_adaptive_set_coverage lets it take every pixel; "refrence_mode", and "adaptive" then, with samples * bounces * 8 > 2^31 return RT3_E_INVALID (the vertices' RNG indices would reach the camera's).  "gbuffer", "denoise",
- *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres, so guiding a
- *      depth-of-field frame by it is not supported.
+ *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres.  "denoise" is guided
+ *      by that G-buffer too unless it is given the lens frame's own guide images (rt3_camera_set_guide_output and
+ *      rt3_denoise_set_guide_input, below); guiding a depth-of-field frame by the pinhole G-buffer is not supported.
  *      rt3_camera_get_lens (either pointer may be NULL): the parameters last set (the defaults {0, 1, 1, 0} before any) and whether on. ---- */
 typedef struct rt3_lens_params {
     float aperture_radius;  /* world units, >= 0; 0 = pinhole */
@@ -729,6 +730,40 @@ typedef struct rt3_lens_params {
 } rt3_lens_params;
 int rt3_camera_set_lens(rt3_ctx *ctx, const rt3_lens_params *p);   /* NULL: off, the default */
 int rt3_camera_get_lens(rt3_ctx *ctx, rt3_lens_params *out, int *enabled);
+/* ---- guide images: "denoise" for lens and glass frames.  No reference counterpart; DESIGN.md section 4u.
+ *      rt3_camera_set_guide_output names four RGBA32F images of the window's size that "refrence_mode" writes while a lens is set, beside
+ *      Light; the pass's bindings and GConst are untouched.  Per listed pixel, over all S = GConst.samples camera samples in ascending order,
+ *      in fp32 with one rounding per operation and no contraction: a sample whose camera ray hit primitive prim at (t, bu, bv) adds
+ *      P = o + d t (the camera ray's origin and direction) to sum_P, and of surf = the unquantised surface the path tracer shades at vertex
+ *      0 (self-test op 29, with material textures where the scene has them) surf.normal to sum_n, surf.albedo to sum_a, surf.emissive to
+ *      sum_e, and 1 to n_hit; a sample that escaped adds (1, 1, 1) to sum_a (the sky is not albedo-modulated) and nothing else.  Written:
+ *        position = {sum_P / n_hit, n_hit / S}   (all zero when n_hit = 0: position.w is the pixel's coverage)
+ *        normal   = {sum_n / n_hit, 0}           (zero when n_hit = 0; not normalised)
+ *        albedo   = {sum_a / S, 0}
+ *        emission = {sum_e / S, 0}
+ *      The sums run in sample order whatever RT3_OPT_BATCH_SPP is (between batches the images hold them), so the bits do not depend on
+ *      it, on RT3_OPT_INSTANCE_MODE or on the tile partition: a rank writes its own pixels only.  Light has the bits it has without the
+ *      guide output.  Glass at vertex 0 contributes the glass surface's own features, not those of what is seen through it.
+ *      NULL switches the output off, the default.  RT3_E_INVALID at set time (nothing changed) for a handle that is not a live RGBA32F
+ *      image or for two equal handles.  At a "refrence_mode" launch: RT3_E_STATE when no lens is on; RT3_E_INVALID when an image has not the
+ *      window's size or is Light or PrevLight, or when samples > 2^24 (the hit count is a float); nothing is enqueued.  "adaptive" returns
+ *      RT3_E_STATE while a guide output is set: it writes no guide, and a stale one must not be filtered.
+ *      rt3_camera_get_guide_output (either pointer may be NULL): the handles last set (zeros before any) and whether on.
+ *      rt3_denoise_set_guide_input gives "denoise" such a set as its guide in the G-buffer's place; NULL (the default) = the G-buffer, and
+ *      every bit the pass writes is what it was.  The bindings stay {gbuffer, gbuffer_depth, In, Out}; the first two are then validated and
+ *      not read.  A pixel is foreground iff position.w == 1 (every sample hit) and l2 = normal . normal is finite and positive; then
+ *      P = position.xyz, n = normal.xyz * (1 / sqrt(l2)), c = (In - emission) / max(albedo, 1/256), and at the end Out = emission +
+ *      c * max(albedo, 1/256) (RT3_DENOISE_NO_DEMODULATION keeps its meaning).  Every other pixel is treated as a background pixel is:
+ *      copied from In bit for bit, weight 0 as a tap.  So partly covered pixels -- a silhouette over the sky -- stay unfiltered, and nothing
+ *      bleeds across them.  The variance and a-trous stages, the parameters, the variance input and the multi-rank refusal are those above.
+ *      The four images are checked at each launch like the variance input: live RGBA32F images of the window's size, none of them Out,
+ *      else RT3_E_INVALID.  fp32, equal to tests/ref_guide.py bit for bit. ---- */
+typedef struct rt3_guide_images {
+    uint32_t position, normal, albedo, emission; /* image handles */
+} rt3_guide_images;
+int rt3_camera_set_guide_output(rt3_ctx *ctx, const rt3_guide_images *images);  /* NULL: off, the default */
+int rt3_camera_get_guide_output(rt3_ctx *ctx, rt3_guide_images *out, int *enabled);
+int rt3_denoise_set_guide_input(rt3_ctx *ctx, const rt3_guide_images *images);  /* NULL: the G-buffer, the default */
 /* ---- Russian roulette on extension rays.  No reference counterpart; DESIGN.md section 4o.  By default every path that still has an extension
  *      ray is traced and shaded for all GConst.bounces vertices.  With roulette set, "refrence_mode" and "adaptive" test the extension ray that
  *      a path emitted at vertex b, for start_bounce <= b < bounces - 1, between the shading of vertex b and the trace that follows, in a
@@ -822,6 +857,14 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      out: T' rgb per record.  RT3_E_INVALID, before anything is launched, for a primitive the flattened world does not have.  The
  *      queue's planes are made one record longer than n and filled with a pattern: RT3_E_STATE when the kernel changed a ray or hit
  *      record or wrote behind the queue's end.
+ *      39 k_lens_guide itself (rt3_camera_set_guide_output) on a caller-made camera queue, hit queue and pixel list over the built scene's
+ *      tables; n = nsb * npix records.  in: the header {npix, nsb (samples in this batch), S (the frame's samples, 1 .. 2^24), first (0 / 1),
+ *      last (0 / 1), workgroups to launch (1 .. 65535)}, then npix pixel words x | y << 16 (all different), then n records of 10 words
+ *      {o xyz, d xyz, t, bu, bv, prim (0xFFFFFFFF: a miss)}, record sample_in_batch * npix + pixel index.  out: 16 words per listed pixel
+ *      {position, normal, albedo, emission}; the words the caller put there are the images' contents before the launch (the running sums
+ *      when first = 0).  The images span the list's bounding box from (0, 0).  RT3_E_INVALID, before anything is launched, for a bad
+ *      header, a repeated pixel or a primitive the flattened world does not have.  Queues and images are made one record longer and
+ *      filled with a pattern: RT3_E_STATE when the kernel changed a ray or hit record, a pixel that is not listed, or a word behind an end.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

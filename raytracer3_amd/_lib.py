@@ -41,6 +41,7 @@ ADAPTIVE_TILE = 2048  # list entries per compaction block (op 35 returns one off
 SELFTEST_ABSORB = 36  # rt3_selftest_eval op: {T rgb, sigma rgb, t, d xyz, n xyz} (13 words) -> {T' rgb, applied (u32)} (4), the absorption rule
 SELFTEST_ABSORB_QUEUE = 37  # rt3_selftest_eval op: k_absorb on a caller-made queue over the built scene (Context.selftest_absorb_queue)
 SELFTEST_FROST = 38  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, alpha, u_event, u2, u3} (12 words) -> {event (u32: 0 reflect, 1 transmit, 2 invalid), direction, F, weight} (6), the frosted vertex rule
+SELFTEST_GUIDE_QUEUE = 39  # rt3_selftest_eval op: k_lens_guide on caller-made camera and hit queues over the built scene (Context.selftest_guide_queue)
 
 EXPORTS = [
     "rt3_create", "rt3_destroy", "rt3_last_error", "rt3_device_name", "rt3_set_option",
@@ -60,6 +61,7 @@ EXPORTS = [
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
     "rt3_adaptive_set_params", "rt3_adaptive_info", "rt3_adaptive_set_coverage", "rt3_adaptive_get_coverage",
     "rt3_camera_set_lens", "rt3_camera_get_lens",
+    "rt3_camera_set_guide_output", "rt3_camera_get_guide_output", "rt3_denoise_set_guide_input",
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
@@ -127,6 +129,18 @@ class LensParams(C.Structure):
 
     def __init__(self, aperture_radius=0.0, focus_distance=1.0, pixel_jitter=1.0, reserved=0):
         super().__init__(aperture_radius, focus_distance, pixel_jitter, reserved)
+
+
+class GuideImages(C.Structure):
+    """rt3_guide_images: the handles of the four RGBA32F guide images of a lens frame."""
+
+    _fields_ = [("position", C.c_uint32), ("normal", C.c_uint32), ("albedo", C.c_uint32), ("emission", C.c_uint32)]
+
+    def __init__(self, position=0, normal=0, albedo=0, emission=0):
+        super().__init__(position, normal, albedo, emission)
+
+    def handles(self):
+        return (self.position, self.normal, self.albedo, self.emission)
 
 
 class RouletteParams(C.Structure):
@@ -247,6 +261,9 @@ def load():
         "rt3_adaptive_get_coverage": (i32, [vp, C.POINTER(i32)]),
         "rt3_camera_set_lens": (i32, [vp, C.POINTER(LensParams)]),
         "rt3_camera_get_lens": (i32, [vp, C.POINTER(LensParams), C.POINTER(i32)]),
+        "rt3_camera_set_guide_output": (i32, [vp, C.POINTER(GuideImages)]),
+        "rt3_camera_get_guide_output": (i32, [vp, C.POINTER(GuideImages), C.POINTER(i32)]),
+        "rt3_denoise_set_guide_input": (i32, [vp, C.POINTER(GuideImages)]),
         "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),
         "rt3_path_get_roulette": (i32, [vp, C.POINTER(RouletteParams), C.POINTER(i32)]),
         "rt3_path_roulette_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -528,8 +528,96 @@ static int selftest_absorb_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uin
     return RT3_OK;
 }
 
+// Self-test op 39: k_lens_guide on a caller-made camera queue, hit queue and pixel list over the built scene's tables.  in: {npix, nsb, S,
+// first, last, workgroups}, npix pixel words, then n = nsb npix records {o xyz, d xyz, t, bu, bv, prim}.  out: per listed pixel the 16 words
+// {position, normal, albedo, emission}; the caller's words are the images' contents before the launch.  Queues and images are one record
+// longer than needed and carry a pattern wherever the kernel has nothing to write: a kernel that wrote out of place fails the call.
+static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    if (int r = check_accel_current(c)) return r;
+    const uint32_t npix = in[0], nsb = in[1], S_total = in[2], first = in[3], last = in[4], groups = in[5];
+    if (npix == 0 || npix > (1u << 24) || nsb == 0 || (uint64_t)nsb * npix != n || n > (1u << 24) || S_total == 0 || S_total > (1u << 24) || first > 1 ||
+        last > 1 || groups == 0 || groups > 65535)
+        return fail(c, RT3_E_INVALID, "selftest: guide queue header: 1..2^24 pixels, nsb * npix = n <= 2^24 records, S 1..2^24, first and last 0 or 1, 1..65535 workgroups");
+    const uint32_t* pix = in + kSelftestGuideHeader;
+    const uint32_t* rec = pix + npix;
+    uint32_t W = 0, H = 0;
+    for (uint32_t i = 0; i < npix; i++) {
+        W = std::max(W, (pix[i] & 0xFFFFu) + 1u);
+        H = std::max(H, (pix[i] >> 16) + 1u);
+    }
+    if ((uint64_t)W * H > (1u << 24)) return fail(c, RT3_E_INVALID, "selftest: guide queue: the pixel list's bounding box holds more than 2^24 pixels");
+    const size_t win = (size_t)W * H;
+    std::vector<uint8_t> listed(win, 0);
+    for (uint32_t i = 0; i < npix; i++) {  // every thread writes its own pixel: a repeated one would be written twice
+        uint8_t& m = listed[(size_t)(pix[i] >> 16) * W + (pix[i] & 0xFFFFu)];
+        if (m) return fail(c, RT3_E_INVALID, "selftest: guide queue pixel " + std::to_string(i) + " is listed twice");
+        m = 1;
+    }
+    for (uint32_t i = 0; i < n; i++) {  // hit_info indexes the flattened world's tables: nothing is launched that would read outside them
+        const uint32_t prim = rec[kSelftestGuideRecord * (size_t)i + 9];
+        if (prim != kMiss && prim >= c->accel.n_flat_prims)
+            return fail(c, RT3_E_INVALID, "selftest: guide queue record " + std::to_string(i) + " names a primitive the flattened world does not have");
+    }
+    HIPC(c, hipSetDevice(c->device));
+    if (int r = sync_textures(c)) return r;
+    constexpr uint32_t kGuard = 0xA5A5A5A5u;
+    const size_t S = (size_t)n + 1;  // one guard record per plane
+    std::vector<uint32_t> rays(8 * S, kGuard), hits(4 * S, kGuard);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t* r = rec + kSelftestGuideRecord * i;
+        memcpy(&rays[4 * i], r, 12);
+        rays[4 * i + 3] = 0x7F7FFFFFu;  // the camera queue's pdf slot
+        memcpy(&rays[4 * (S + i)], r + 3, 12);
+        rays[4 * (S + i) + 3] = (uint32_t)i;  // path id
+        memcpy(&hits[4 * i], r + 6, 16);
+    }
+    std::vector<uint32_t> img[4];
+    for (int k = 0; k < 4; k++) img[k].assign(4 * (win + 1), kGuard);
+    for (uint32_t i = 0; i < npix; i++) {
+        const size_t pi = (size_t)(pix[i] >> 16) * W + (pix[i] & 0xFFFFu);
+        for (int k = 0; k < 4; k++) memcpy(&img[k][4 * pi], out + kSelftestGuideOut * (size_t)i + 4 * k, 16);
+    }
+    DevBuf<float> d_rays, d_hits;
+    DevBuf<uint32_t> d_pix;
+    DevBuf<float4> d_img[4];
+    HIPC(c, d_rays.alloc_bytes(8 * S * 4));
+    HIPC(c, d_hits.alloc_bytes(4 * S * 4));
+    HIPC(c, d_pix.alloc_bytes((size_t)npix * 4));
+    HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_hits.get(), hits.data(), 4 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_pix.get(), pix, (size_t)npix * 4, hipMemcpyHostToDevice));
+    for (int k = 0; k < 4; k++) {
+        HIPC(c, d_img[k].alloc_bytes((win + 1) * 16));
+        HIPC(c, hipMemcpy(d_img[k].get(), img[k].data(), (win + 1) * 16, hipMemcpyHostToDevice));
+    }
+    GuideLaunch G{};
+    G.sc = scene_dev(c); G.pixels = d_pix.get(); G.npix = npix; G.width = W; G.rays = d_rays.get(); G.hits = d_hits.get(); G.stride = S;
+    G.nsb = nsb; G.samples = S_total; G.first_batch = first != 0; G.last_batch = last != 0;
+    for (int k = 0; k < 4; k++) G.img[k] = d_img[k].get();
+    launch_lens_guide(c->stream, G, groups);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> rays2(8 * S), hits2(4 * S);
+    HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(hits2.data(), d_hits.get(), 4 * S * 4, hipMemcpyDeviceToHost));
+    if (rays2 != rays || hits2 != hits) return fail(c, RT3_E_STATE, "selftest: k_lens_guide wrote a ray or hit record");
+    for (int k = 0; k < 4; k++) {
+        HIPC(c, hipMemcpy(img[k].data(), d_img[k].get(), (win + 1) * 16, hipMemcpyDeviceToHost));
+        for (size_t pi = 0; pi <= win; pi++)
+            if (pi == win || !listed[pi])
+                for (int w = 0; w < 4; w++)
+                    if (img[k][4 * pi + w] != kGuard) return fail(c, RT3_E_STATE, "selftest: k_lens_guide wrote a pixel that is not listed, or behind an image's end");
+    }
+    for (uint32_t i = 0; i < npix; i++) {
+        const size_t pi = (size_t)(pix[i] >> 16) * W + (pix[i] & 0xFFFFu);
+        for (int k = 0; k < 4; k++) memcpy(out + kSelftestGuideOut * (size_t)i + 4 * k, &img[k][4 * pi], 16);
+    }
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 39 && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 37 && c && in && out) return selftest_absorb_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 35 && c && in && out) return selftest_adaptive_compact(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 34 && c && in && out) return selftest_roulette_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));  // no rows of one width

@@ -291,6 +291,12 @@ struct rt3_ctx {
         rt3_lens_params params = {0.0f, 1.0f, 1.0f, 0u};
         bool on = false;
     } lens;
+    // rt3_passes.hip: guide images: the four images a lens frame's "refrence_mode" writes (rt3_camera_set_guide_output)
+    // and the four "denoise" is guided by (rt3_denoise_set_guide_input); both off by default, both checked again at every launch
+    struct Guide {
+        rt3_guide_images out = {0u, 0u, 0u, 0u}, in = {0u, 0u, 0u, 0u};
+        bool out_on = false, in_on = false;
+    } guide;
     // rt3_passes.hip: Russian roulette on extension rays (rt3_path_set_roulette): off by default
     struct Roulette {
         rt3_roulette_params params = {2u, 0.0625f, {0u, 0u}};

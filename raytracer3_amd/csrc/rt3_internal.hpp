@@ -143,6 +143,25 @@ void launch_accumulate_lens(hipStream_t st, const GConstDev& g, const uint32_t* 
                             int first_batch, int last_batch, float* radsum, void* light, const void* prev);
 // launch_postprocess with every pixel taken from `in`
 void launch_postprocess_lens(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* in, void* out);
+// guide images of a lens frame (rt3_guide.hip): k_lens_guide over the camera queue `rays` and its hit queue `hits`
+// (record = sample_in_batch * npix + pixel index, `stride` records per plane), both read-only, for samples of one batch; img = {position,
+// normal, albedo, emission}, window-space float4 images of row length `width`.  first_batch: the sums start at 0; last_batch: the sums
+// become means over `samples`, the frame's sample count.  The grid covers npix, or is `groups` workgroups when that is not 0 (self-test
+// op 39)
+struct GuideLaunch {
+    SceneDev sc;
+    const uint32_t* pixels;
+    uint32_t npix, width;
+    const float *rays, *hits;
+    size_t stride;
+    uint32_t nsb, samples;
+    bool first_batch, last_batch;
+    float4* img[4];
+};
+void launch_lens_guide(hipStream_t st, const GuideLaunch& a, uint32_t groups = 0);
+// self-test op 39: k_lens_guide on caller-made queues; header words, then the pixel words, then records of kSelftestGuideRecord words;
+// kSelftestGuideOut words out per listed pixel
+constexpr uint32_t kSelftestGuideHeader = 6, kSelftestGuideRecord = 10, kSelftestGuideOut = 16;
 // self-test op 31: lens_ray, kSelftestLensIn words in, kSelftestLensOut words out
 constexpr uint32_t kSelftestLensIn = 41, kSelftestLensOut = 10;
 void launch_selftest_lens(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
@@ -516,6 +535,8 @@ struct DenoiseLaunch {
     const void* in;
     void* out;
     const void* moments = nullptr;  // rt3_denoise_set_variance_input: the "temporal" pass's Moments image, or none
+    // rt3_denoise_set_guide_input: {position, normal, albedo, emission} of a lens frame (all set, or all null: the G-buffer guides)
+    const float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
     DenoiseScratch s;
 };
 void denoise_plan(uint32_t W, uint32_t H, BufLayout& plan, DenoiseScratch* s);
@@ -523,6 +544,9 @@ void launch_denoise_prepare(hipStream_t st, const DenoiseLaunch& L);
 void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L);
 void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iteration);
 void launch_denoise_finish(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
+// the two end stages with L.guide in the G-buffer's place; the stages between them are the ones above
+void launch_denoise_prepare_guide(hipStream_t st, const DenoiseLaunch& L);
+void launch_denoise_finish_guide(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
 void launch_selftest_denoise(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);  // selftest op 28: expn
 
 // "temporal" pass (rt3_temporal.hip): one kernel, one thread per pixel, no scratch.  `prev` is the previous frame's

@@ -9,6 +9,8 @@
 // Also owns rt3_ctx::roulette: Russian roulette on extension rays (rt3_path_set_roulette), which trace_batch applies
 // for "refrence_mode" and "adaptive".
 // trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
+// Also owns rt3_ctx::guide: the guide images of a lens frame (rt3_camera_set_guide_output, rt3_denoise_set_guide_input, DESIGN.md section
+// 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through its two guided end kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -258,6 +260,8 @@ struct PathSetup {
     PaneDev pane{};
     // absorption (rt3_scene_set_attenuation): the built scene's table, null without an absorbing geometry -- k_absorb
     const AbsorbDev* absorb = nullptr;
+    // guide images (rt3_camera_set_guide_output): the frame's four images, null unless "refrence_mode" resolved them -- k_lens_guide
+    float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 // pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
 constexpr float kSkyDeferMinPdf = 0x1p-100f;
@@ -371,6 +375,16 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             ScopedTimer t(c, CAT_OTHER);
             launch_lens_miss(c->stream, ps.sc, c->work.rays[0].get(), c->work.hits.get(), c->work.lacc.get(), S, n_first);
         }
+        // the first-vertex features of this batch's samples, while the camera queue and its hits are whole: the first k_shade overwrites
+        // neither, but the k_extend behind it overwrites the hits
+        if (ps.guide[0] != nullptr) {
+            GuideLaunch G{};
+            G.sc = ps.sc; G.pixels = pixels; G.npix = npix; G.width = W; G.rays = c->work.rays[0].get(); G.hits = c->work.hits.get(); G.stride = S;
+            G.nsb = nsb; G.samples = ps.gd.samples; G.first_batch = s0 == 0; G.last_batch = s0 + nsb >= ps.gd.samples;
+            for (int k = 0; k < 4; k++) G.img[k] = ps.guide[k];
+            ScopedTimer t(c, CAT_OTHER);
+            launch_lens_guide(c->stream, G);
+        }
     }
     // every path starts at distance 0 from the vertex that chose its direction (the camera)
     if (ps.panes) HIPC(c, hipMemsetAsync(c->work.pane_dist.get(), 0, (size_t)n_first * sizeof(float), c->stream));
@@ -464,10 +478,36 @@ int batch_spp(rt3_ctx* c, uint32_t npix, uint32_t spp, uint32_t* sb) {
     return RT3_OK;
 }
 
+// The four images of a guide set as the launch sees them: live RGBA32F images of the window's size, none of them
+// one of the `n_not` images `not_these` (named `not_names` in the error); their device pointers into `out`.  RT3_E_INVALID otherwise.
+int guide_resolve(rt3_ctx* c, const rt3_guide_images& gi, uint32_t W, uint32_t H, const std::string& what, const Resource* const* not_these,
+                  uint32_t n_not, const char* not_names, float4** out) {
+    const uint32_t handles[4] = {gi.position, gi.normal, gi.albedo, gi.emission};
+    const char* names[4] = {"position", "normal", "albedo", "emission"};
+    for (int k = 0; k < 4; k++) {
+        const Resource* r = image_checked(c, handles[k], W, H, RT3_FORMAT_R32G32B32A32_SFLOAT,(what + " image '" + names[k] + "'").c_str());
+        if (!r) return RT3_E_INVALID;
+        for (uint32_t j = 0; j < n_not; j++)
+            if (r->ptr == not_these[j]->ptr) return fail(c, RT3_E_INVALID, what + " image '" + names[k] + "' must not be " + not_names);
+        out[k] = static_cast<float4*>(r->ptr);
+    }
+    return RT3_OK;
+}
+
 // refrence_mode.slang:14-66 as a wavefront loop
 int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
     const Resource *gb = res[0], *dp = res[1], *li = res[2], *pv = res[3];
     const uint32_t Sspp = g->samples, B = g->bounces;
+    float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (c->guide.out_on) {  // DESIGN.md section 4u; before anything is enqueued: a refused launch changes nothing
+        if (!c->lens.on)
+            return fail(c, RT3_E_STATE, "refrence_mode: a guide output is set (rt3_camera_set_guide_output) and no lens is on (rt3_camera_set_lens): the guide "
+                                        "images are means over per-sample camera rays");
+        if (Sspp > (1u << 24))
+            return fail(c, RT3_E_INVALID, "refrence_mode with a guide output: samples may not exceed 2^24 (the hit count is kept in a float)");
+        const Resource* const written[2] = {li, pv};
+        if (int r = guide_resolve(c, c->guide.out, W, H, "refrence_mode: guide output", written, 2, "'Light' or 'PrevLight'", guide)) return r;
+    }
     if (Sspp == 0 || B == 0) return RT3_OK;  // GConst::default() leaves samples = bounces = 0 (renderer/mod.rs:47-63): nothing to trace
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     if (c->lens.on && (uint64_t)Sspp * B * 8u > (1ull << 31))
@@ -492,6 +532,7 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     if (int r = path_setup(c, g, &ps)) return r;
     ps.lens_on = c->lens.on;
     ps.lens = lens_dev(c);
+    for (int k = 0; k < 4; k++) ps.guide[k] = guide[k];
     for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
         const uint32_t nsb = std::min(sb, Sspp - s0);
         if (int r = trace_batch(c, ps, W, gb, dp, pl->dev.get(), pl->dev_bn.get(), npix, s0, nsb)) return r;
@@ -520,6 +561,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     c->adaptive.paths_traced = 0;
     // coverage mode (rt3_adaptive_set_coverage): with a lens every pixel of the rank's list is a pixel of round 0
     const bool cover = c->lens.on && c->adaptive.coverage;
+    if (c->guide.out_on)
+        return fail(c, RT3_E_STATE, "adaptive: not while a guide output is set (rt3_camera_set_guide_output): the pass writes no guide images, and a "
+                                    "stale guide would be filtered; switch it off (NULL) or use refrence_mode");
     if (c->lens.on && !cover)
         return fail(c, RT3_E_STATE, "adaptive: not with a lens set (rt3_camera_set_lens): the pass selects pixels by G-buffer depth, which knows nothing "
                                     "of partly covered pixels; switch the lens off (NULL), use refrence_mode, or let the pass take every pixel with "
@@ -703,6 +747,10 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
         if (!mo) return RT3_E_INVALID;
         if (mo->ptr == out->ptr) return fail(c, RT3_E_INVALID, "denoise: the variance input (rt3_denoise_set_variance_input) must not be 'Out'");
     }
+    // rt3_denoise_set_guide_input: a lens frame's sample means guide the filter; gbuffer and gbuffer_depth are not read
+    float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (c->guide.in_on)
+        if (int r = guide_resolve(c, c->guide.in, W, H, "denoise: guide input", &out, 1, "'Out'", guide)) return r;
     const rt3_denoise_params& p = c->denoise.params;
     if (p.iterations == 0) {
         ScopedTimer t(c, CAT_OTHER);
@@ -721,9 +769,11 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
         HIPC(c, c->denoise.scratch.grow_bytes(plan.bytes()));
     }
     HIPC(c, plan.carve(c->denoise.scratch));
+    for (int k = 0; k < 4; k++) L.guide[k] = guide[k];
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_denoise_prepare(c->stream, L);
+        if (guide[0]) launch_denoise_prepare_guide(c->stream, L);
+        else launch_denoise_prepare(c->stream, L);
     }
     {
         ScopedTimer t(c, CAT_OTHER);
@@ -735,7 +785,8 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
     }
     {
         ScopedTimer t(c, CAT_OTHER);
-        launch_denoise_finish(c->stream, L, p.iterations);
+        if (guide[0]) launch_denoise_finish_guide(c->stream, L, p.iterations);
+        else launch_denoise_finish(c->stream, L, p.iterations);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;
@@ -987,6 +1038,37 @@ int rt3_camera_set_lens(rt3_ctx* c, const rt3_lens_params* p) {
     if (p->reserved != 0u) return fail(c, RT3_E_INVALID, "lens params: reserved must be 0");
     c->lens.params = *p;
     c->lens.on = true;
+    return RT3_OK;
+}
+// guide images.  The output is checked here (live RGBA32F images, all different) and again at every launch (size,
+// not Light / PrevLight); the input at every "denoise" launch, like the variance input
+int rt3_camera_set_guide_output(rt3_ctx* c, const rt3_guide_images* gi) {
+    if (!c) return RT3_E_INVALID;
+    if (!gi) {
+        c->guide.out_on = false;
+        return RT3_OK;
+    }
+    const uint32_t h[4] = {gi->position, gi->normal, gi->albedo, gi->emission};
+    for (int k = 0; k < 4; k++) {
+        const Resource* r = get_res(c, h[k], RT3_TAG_IMAGE);
+        if (!r || r->format != RT3_FORMAT_R32G32B32A32_SFLOAT) return fail(c, RT3_E_INVALID, "guide output: every handle must be a live RGBA32F image");
+        for (int j = 0; j < k; j++)
+            if (h[j] == h[k]) return fail(c, RT3_E_INVALID, "guide output: the four images must be different images");
+    }
+    c->guide.out = *gi;
+    c->guide.out_on = true;
+    return RT3_OK;
+}
+int rt3_camera_get_guide_output(rt3_ctx* c, rt3_guide_images* out, int* enabled) {
+    if (!c) return RT3_E_INVALID;
+    if (out) *out = c->guide.out;
+    if (enabled) *enabled = c->guide.out_on ? 1 : 0;
+    return RT3_OK;
+}
+int rt3_denoise_set_guide_input(rt3_ctx* c, const rt3_guide_images* gi) {
+    if (!c) return RT3_E_INVALID;
+    c->guide.in_on = gi != nullptr;
+    if (gi) c->guide.in = *gi;  // checked when "denoise" is launched, like the variance input
     return RT3_OK;
 }
 int rt3_path_set_roulette(rt3_ctx* c, const rt3_roulette_params* p) {

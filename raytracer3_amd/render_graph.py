@@ -469,6 +469,48 @@ class Context:
         self.check(self.lib.rt3_camera_get_lens(self.h, C.byref(p), C.byref(on)))
         return p, bool(on.value)
 
+    @staticmethod
+    def _guide_images(images):
+        """an L.GuideImages from one, from a dict with its four names, or from four handles in the order position, normal, albedo, emission"""
+        if images is None or isinstance(images, L.GuideImages):
+            return images
+        if isinstance(images, dict):
+            return L.GuideImages(**{k: int(images[k]) for k in ("position", "normal", "albedo", "emission")})
+        return L.GuideImages(*[int(h) for h in images])
+
+    def set_guide_output(self, images=None):
+        """the four RGBA32F images a lens frame's "refrence_mode" writes its guide into (rt3_camera_set_guide_output):
+        an L.GuideImages, a dict {position, normal, albedo, emission} or four handles in that order; None = off, the default"""
+        g = self._guide_images(images)
+        self.check(self.lib.rt3_camera_set_guide_output(self.h, C.byref(g) if g is not None else None))
+
+    def get_guide_output(self):
+        """(L.GuideImages last set, whether the output is on) (rt3_camera_get_guide_output)"""
+        g, on = L.GuideImages(), C.c_int()
+        self.check(self.lib.rt3_camera_get_guide_output(self.h, C.byref(g), C.byref(on)))
+        return g, bool(on.value)
+
+    def set_denoise_guide_input(self, images=None):
+        """the guide images "denoise" reads in the G-buffer's place (rt3_denoise_set_guide_input); None = the G-buffer, the default"""
+        g = self._guide_images(images)
+        self.check(self.lib.rt3_denoise_set_guide_input(self.h, C.byref(g) if g is not None else None))
+
+    def selftest_guide_queue(self, pixels, records, nsb, samples, first, last, groups, prefill=None):
+        """Self-test op 39: k_lens_guide on the camera and hit queues `records` (nsb * npix, 10) of 32-bit words {o xyz, d xyz, t, bu, bv, prim}
+        (record sample_in_batch * npix + pixel index) over the pixel words `pixels` and the built scene, launched with `groups`
+        workgroups; `prefill` (npix, 16): the four images' words at the listed pixels before the launch (zeros without).  Returns them
+        afterwards, (npix, 16) uint32: {position, normal, albedo, emission}.  The library fails the call when the kernel wrote anything else."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 10)
+        npix, n = len(pixels), len(records)
+        head = np.array([npix, nsb, samples, int(first), int(last), groups], np.uint32)
+        inp = np.concatenate([head, pixels, records.reshape(-1)])
+        out = np.zeros(16 * max(npix, 1), np.uint32)
+        if prefill is not None:
+            out[: 16 * npix] = np.ascontiguousarray(prefill).view(np.uint32).reshape(-1)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_GUIDE_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return out[: 16 * npix].reshape(npix, 16)
+
     def set_roulette(self, params=None, **kw):
         """Russian roulette on extension rays (rt3_path_set_roulette, DESIGN.md section 4o): an L.RouletteParams, or its fields as keywords;
         nothing = off"""
@@ -638,6 +680,17 @@ class NodeBuilder:
     def read_write(self, origin, handle):
         return self._edge(origin, handle, "ShaderReadWrite")
 
+    # Context-state edges (no reference counterpart): an image the pass reaches through a context setter (ctx.set_guide_output,
+    # ctx.set_denoise_guide_input), not through its bindings.  They order the nodes like any edge and are left out of the binding list.
+    def state_write(self, handle):
+        return self._edge(IMPORTED, handle, "StateWrite")
+
+    def state_read(self, origin, handle):
+        if origin != IMPORTED and not any(e.resource == handle and e.edge_type != "StateRead" for e in self.rg.nodes[origin].edges):
+            raise ValueError("Origin doesnt write to handle")
+        self.node.edges.append(NodeEdge(None if origin == IMPORTED else origin, "StateRead", handle))
+        return self
+
     def _build(self):
         seen = set()
         for e in self.node.edges:  # build.rs:195-198
@@ -730,7 +783,8 @@ class RenderGraph:
         for ni in self.bake(roots[-1]):
             n = self.nodes[ni]
             x, y, z = (*n.size.size(self.window), 1) if n.kind == "raytracing" else n.size.size(self.window)
-            self.ctx.check(self.ctx.pass_launch(n.path, x, y, z, n.constants, [e.resource for e in n.edges], n.entry))  # bake.rs:51-83
+            bindings = [e.resource for e in n.edges if not e.edge_type.startswith("State")]  # bake.rs:51-83
+            self.ctx.check(self.ctx.pass_launch(n.path, x, y, z, n.constants, bindings, n.entry))
         self.frame_number += 1
         if wait:
             self.ctx.wait()

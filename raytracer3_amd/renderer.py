@@ -50,8 +50,17 @@ class Camera:
         return np.array(self.gconst(window).proj[:], np.float32).reshape(4, 4).T
 
 
+GUIDE_IMAGES = (("position", "GuidePosition"), ("normal", "GuideNormal"), ("albedo", "GuideAlbedo"), ("emission", "GuideEmission"))
+
+
+def guide_images(rg):
+    """the four guide images of a lens frame as a dict {position, normal, albedo, emission} of handles: what
+    ctx.set_guide_output and ctx.set_denoise_guide_input take"""
+    return {key: rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, name) for key, name in GUIDE_IMAGES}
+
+
 def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False, *,
-                gbuffer_names=("gbuffer", "gbuffer_depth"), gbuffer_node=True, trace=True):
+                gbuffer_names=("gbuffer", "gbuffer_depth"), gbuffer_node=True, trace=True, guide=False):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
     `temporal`, the "temporal" node accumulates `Light` with the reprojected history into `accumulated`; with `denoise`, the "denoise"
     node filters `Light` (or `accumulated`) into `denoised`; postprocess reads the last of them.  With `motion`, the "motion" node is
@@ -60,7 +69,10 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     and writes the image `AdaptiveMoments` as well (handle `adaptive_moments`: {S1, S2, n, stopped before the cap}).
     A frame over a `Light` that is already there (PathTracer.denoise) is the same chain with other ends: `trace=False` imports `Light`
     (no path-trace node, hence no `prev`, and no `color` unless `postprocess`), `gbuffer_node=False` imports the G-buffer too, and
-    `gbuffer_names` are the images the G-buffer and its depth live in."""
+    `gbuffer_names` are the images the G-buffer and its depth live in.
+    With `guide` (a lens frame whose context has the guide output set, ctx.set_guide_output) the four images of guide_images() are
+    declared as context-state writes of the path-trace node and, with `denoise`, as context-state reads of the "denoise" node (handle
+    `guide`: the dict of guide_images); they are no bindings."""
     full, f4 = ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT
     gbuffer = rg.image(full, L.FORMAT_R32G32B32A32_UINT, gbuffer_names[0])
     depth = rg.image(full, L.FORMAT_R32_SFLOAT, gbuffer_names[1])
@@ -81,7 +93,12 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         if adaptive:
             handles["adaptive_moments"] = rg.image(full, f4, "AdaptiveMoments")
             pt.write(IMPORTED, handles["adaptive_moments"])
+        if guide:
+            for h in guide_images(rg).values():
+                pt.state_write(h)
         src = pt.launch(WorkSize2D.FullScreen)
+    if guide:
+        handles["guide"] = guide_images(rg)
     lit = light
     if motion:
         handles["motion"] = motion_node(rg, gconst)[1]
@@ -90,7 +107,7 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         handles.update(th)
         lit = th["accumulated"]
     if denoise:
-        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit)
+        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit, guide=handles.get("guide"), guide_origin=src if trace and not temporal else IMPORTED)
         handles["denoised"] = lit
     if postprocess:
         (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
@@ -98,12 +115,15 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     return handles
 
 
-def denoise_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
-    """ComputePass("denoise"): {gbuffer, gbuffer_depth, In = `light`, Out = the image `denoised`}.  Returns (node, denoised)."""
+def denoise_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light, guide=None, guide_origin=IMPORTED):
+    """ComputePass("denoise"): {gbuffer, gbuffer_depth, In = `light`, Out = the image `denoised`}.  Returns (node, denoised).  `guide`: the
+    dict of guide_images() the pass reads as context state (ctx.set_denoise_guide_input), written by node `guide_origin`."""
     denoised = rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "denoised")
     dn = (ComputePass.new(rg, "denoise").shader("denoise").constants(gconst)
-          .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light).write(IMPORTED, denoised).dispatch(DispatchSize.FullScreen))
-    return dn, denoised
+          .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light).write(IMPORTED, denoised))
+    for h in (guide or {}).values():
+        dn.state_read(guide_origin, h)
+    return dn.dispatch(DispatchSize.FullScreen), denoised
 
 
 TEMPORAL_SWAPS = (("History", "PrevHistory"), ("Moments", "PrevMoments"))
@@ -215,6 +235,7 @@ class PathTracer:
         self._history = _TemporalHistory(self.ctx)
         self._glass_lens = False  # the lens in force is the pinhole set_scene switched on for a scene with glass
         self._scene_set = False   # set_scene has built a structure (set_pane_shadows rebuilds it)
+        self._guide = False       # set_guide: lens frames write guide images, and "denoise" is guided by them
 
     def close(self):
         self.ctx.close()
@@ -342,6 +363,28 @@ class PathTracer:
         else:
             self.ctx.set_lens(L.LensParams(aperture, focus, jitter))
 
+    def set_guide(self, on=True):
+        """Sample-guided denoising of lens frames, off by default.  While on and a lens is in force -- set_lens, or the
+        pinhole set_scene switches on for a scene with glass -- render() has "refrence_mode" write the four guide images (handle `guide`,
+        guide()) from the frame's own camera samples, and render(g, denoise=True) and denoise() filter by them instead of by the pinhole
+        G-buffer.  Without a lens, and for temporal or adaptive frames, everything is as with the guide off.  With several ranks
+        denoise() raises: the guide images are not gathered."""
+        self._guide = bool(on)
+        if not self._guide:
+            self.ctx.set_guide_output(None)
+            self.ctx.set_denoise_guide_input(None)
+
+    def _guide_in_force(self, denoise, temporal=False, adaptive=False):
+        """Set the context's guide output and input for the frame that follows; returns whether the frame has guide images.  A tracer whose
+        guide was never switched on makes no call."""
+        if not self._guide:
+            return False
+        on = self.ctx.get_lens()[1] and not temporal and not adaptive
+        images = guide_images(self.rg) if on else None
+        self.ctx.set_guide_output(images)
+        self.ctx.set_denoise_guide_input(images if denoise else None)
+        return on
+
     def set_adaptive_coverage(self, on=True):
         """Coverage mode of adaptive frames (ctx.adaptive_set_coverage): with a lens set -- by set_lens, or by set_scene
         for a scene with glass -- render(g, adaptive=...) samples every pixel of the rank to the threshold, each sample from its own camera
@@ -362,11 +405,12 @@ class PathTracer:
         """(extension rays tested, of them ended) of the last frame's path-tracing launch"""
         return self.ctx.roulette_info()
 
-    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False):
+    def commands(self, gconst: L.GConst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False, guide=False):
         """Build this frame's nodes (frame_nodes).  `denoise` and `temporal` need the whole window on this rank: with several ranks use
-        denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images)."""
+        denoise().  `temporal` also needs the state that render(temporal=True) keeps (previous view, history images); `guide` the
+        context state that render() sets under set_guide()."""
         self.rg.begin_frame()
-        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion, adaptive)
+        self.handles = frame_nodes(self.rg, gconst, postprocess, denoise, temporal, motion, adaptive, guide=guide)
         return self.handles
 
     @contextlib.contextmanager
@@ -391,12 +435,19 @@ class PathTracer:
         frame; the whole-window G-buffer is rendered into images of its own, which render() does not touch, on one rank too) and
         "denoise" -- unless `denoise` is False -- filters its `accumulated` image with the temporal variance."""
         rg = self.rg
+        guide = self._guide and denoise and not temporal and self.ctx.get_lens()[1]  # the last render()'s guide images (set_guide)
+        if guide and self.n_ranks > 1:
+            raise ValueError("denoise() with the sample guide on (set_guide) needs the whole frame's guide images on this rank, and they are not "
+                             "gathered: render on one rank, or switch the guide off")
         names = ("TemporalGbuffer", "TemporalDepth") if temporal else ("gbuffer", "gbuffer_depth")  # render() must not overwrite the kept one
         moved = temporal and self._begin_temporal(gconst, denoise, names)
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
+        if self._guide:
+            self.ctx.set_denoise_guide_input(guide_images(rg) if guide else None)
         rg.begin_frame()
-        h = frame_nodes(rg, gconst, False, denoise, temporal, moved, gbuffer_names=names, gbuffer_node=self.n_ranks > 1 or temporal, trace=False)
+        h = frame_nodes(rg, gconst, False, denoise, temporal, moved, gbuffer_names=names, gbuffer_node=self.n_ranks > 1 or temporal, trace=False,
+                        guide=guide)
         self.handles = {k: v for k, v in self.handles.items() if k != "motion"} | h  # earlier frames' handles stay, but for a stale `motion`
         with self._whole_window():
             if moved:  # on the whole window, like the G-buffer
@@ -465,7 +516,9 @@ class PathTracer:
         motion = temporal and self._begin_temporal(gconst, denoise)
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
-        h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive is not None and adaptive is not False)
+        adaptive_on = adaptive is not None and adaptive is not False
+        guide = self._guide_in_force(denoise, temporal, adaptive_on)
+        h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive_on, guide=guide)
         if motion:
             self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
@@ -494,6 +547,11 @@ class PathTracer:
     def history(self):
         """(History, Moments) of the "temporal" pass"""
         return self._download("history"), self._download("moments")
+
+    def guide(self):
+        """the guide images of the last lens frame rendered under set_guide(): {position, normal, albedo, emission} -> (H, W, 4) float32"""
+        W, H = self.window
+        return {k: self.rg.download(h, (H, W, 4), np.float32) for k, h in self.handles["guide"].items()}
 
     def adaptive_moments(self):
         """Moments of the "adaptive" pass: {S1, S2, n, 1 = stopped before the cap} per foreground pixel, 0 for background; in coverage mode
