@@ -485,6 +485,18 @@ int rt3_accel_refit(rt3_ctx *ctx, uint32_t *out_handle);
  * while vertices are stale. */
 int rt3_light_info(rt3_ctx *ctx, uint32_t *n_emitters, uint64_t *cdf_total);
 int rt3_light_download(rt3_ctx *ctx, uint32_t *prim, float *area, uint32_t *mass /* CDF units */);
+/* the light table as the shading kernel reads it, for tests that pin it bit for bit (any pointer may be NULL): the table that
+ * flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL) samples, entries in rt3_light_masses' order, n = n_emitters + n_punctual of them.
+ * rec: 16 floats per entry, {A xyz, p_sel / area} {E1 xyz, Le.r} {E2 xyz, Le.g} {unit normal, Le.b} for an emitter triangle A, A + E1, A + E2
+ * with Le = 12 emission and p_sel = mass / 2^23 (0 for an entry of no mass or no area); a punctual light's record is {position, p_sel}
+ * {unit axis, I.r} {cone scale, cone offset, 1 / range, I.g} {tag, 0, 0, I.b}.  cdf: n words, the inclusive integer CDF (cdf[n - 1] = 2^23, or
+ * every word 0 when no entry has power).  guide: *cells + 1 words; *cells is the smallest power of two >= n, at most 2^20, *shift =
+ * 23 - log2(*cells); guide[c] = the first entry with cdf > c << shift (n in a table without power: there is none), guide[*cells] = n - 1.  The entry that owns k in [0, 2^23) is the first
+ * with cdf > k, searched between guide[k >> shift] and guide[(k >> shift) + 1].  prim, area: n words each, the flattened primitive and the
+ * world-space area the selection divided by (0xFFFFFFFF and 1 for a punctual light).  A combination that samples nothing: *cells = *shift = 0 and no
+ * array is written.  RT3_E_STATE where rt3_light_info returns it. */
+int rt3_light_table(rt3_ctx *ctx, uint32_t flags, float *rec /* 16 per entry */, uint32_t *cdf, uint32_t *guide, uint32_t *prim, float *area,
+                    uint32_t *cells, uint32_t *shift);
 /* sky tables for parity tests (any pointer may be NULL): per-row alias words q16 | alias << 16 (w*h), RGB9E5 texels (w*h),
  * marginal CDF (h), realised (u,v) density (w*h) */
 int rt3_sky_download(rt3_ctx *ctx, uint32_t *alias, uint32_t *texels_rgb9e5, float *cdf_marg, float *pdf_uv);
@@ -865,6 +877,17 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      when first = 0).  The images span the list's bounding box from (0, 0).  RT3_E_INVALID, before anything is launched, for a bad
  *      header, a repeated pixel or a primitive the flattened world does not have.  Queues and images are made one record longer and
  *      filled with a pattern: RT3_E_STATE when the kernel changed a ray or hit record, a pixel that is not listed, or a word behind an end.
+ *      40 the selection part of the light table on the caller-made powers of n lights, through the function, the
+ *      scratch layout and the launch shapes of the context's own table; reads no context state.  The steps: pm = the largest power;
+ *      q = floor(double(power) / pm * 2^24 + 0.5) (all 0 when pm = 0); prefix = the inclusive sums of q, Q the last; cdf = floor(double(prefix) /
+ *      double(Q) * 2^23) (all 0 when Q = 0); mass = cdf[e] - cdf[e - 1]; w = float(mass * 2^-23) / area in fp32 where mass > 0 and area > 0,
+ *      else 0; cells = the smallest power of two >= n, at most 2^20, shift = 23 - log2(cells); guide[c] = the first e with cdf[e] > c << shift
+ *      (n when there is none: every power 0), guide[cells] = n - 1; the entry found for k = the first e with cdf[e] > k.  in: the header {n, n_k}, then n power words, n area
+ *      words (fp32), then n_k words k.  out: {cells, shift, total = cdf[n - 1]}, then cdf[n], w[n] (the .w a record would get),
+ *      guide[cells + 1] and the n_k entries light_find returns.  RT3_E_INVALID, before anything is launched, for n = 0, n > 2^24, a header n
+ *      that is not the call's n, a power that is negative or not finite, a k >= 2^23, or n_k > 0 when every power is 0 (total = 0: nothing
+ *      may be looked up).  Every output array is made one element longer and filled with a pattern: RT3_E_STATE when a word behind an
+ *      end, or a record word other than w, changed.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

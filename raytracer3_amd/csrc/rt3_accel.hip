@@ -1032,4 +1032,21 @@ int rt3_light_masses(rt3_ctx* c, uint32_t flags, uint32_t* n_emitters, uint32_t*
     return RT3_OK;
 }
 
+int rt3_light_table(rt3_ctx* c, uint32_t flags, float* rec, uint32_t* cdf, uint32_t* guide, uint32_t* prim, float* area, uint32_t* cells, uint32_t* shift) {
+    if (!c) return RT3_E_INVALID;
+    const uint32_t combo = flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL);
+    if (int r = ensure_lights(c, combo ? combo : RT3_F_NEE_EMISSIVE)) return r;  // (rt3_light_masses' rule)
+    const LightTable& t = c->accel.lights;
+    const bool any = combo != 0u && t.n != 0u;
+    if (cells) *cells = any ? t.n_guide : 0u;
+    if (shift) *shift = any ? t.guide_shift : 0u;
+    if (!any) return RT3_OK;
+    if (rec) HIPC(c, hipMemcpy(rec, t.rec.get(), (size_t)t.n * 64, hipMemcpyDeviceToHost));
+    if (cdf) HIPC(c, hipMemcpy(cdf, t.cdf.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    if (guide) HIPC(c, hipMemcpy(guide, t.guide.get(), ((size_t)t.n_guide + 1) * 4, hipMemcpyDeviceToHost));
+    if (prim) HIPC(c, hipMemcpy(prim, t.prim.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    if (area) HIPC(c, hipMemcpy(area, t.area.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    return RT3_OK;
+}
+
 }  // extern "C"

@@ -615,8 +615,35 @@ static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint
     return RT3_OK;
 }
 
+// Self-test op 40: the light table's selection part (lights_selftest_table: lights_build's own function) on n caller-made powers and areas,
+// and light_find on n_k caller-made values of k.  in: {n, n_k}, n power words, n area words, n_k words k.  out: {cells, shift, total},
+// cdf[n], p_sel / area [n], guide[cells + 1], n_k entries found.  The largest power is taken here, on the host: it is not under test.
+static int selftest_light_table(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const uint32_t n_k = in[1];
+    if (n == 0 || n > (1u << 24) || in[0] != n || n_k > (1u << 24))
+        return fail(c, RT3_E_INVALID, "selftest: light table header: 1..2^24 lights, as many as the call's n, at most 2^24 values of k");
+    const float* power = reinterpret_cast<const float*>(in + kSelftestTableHeaderIn);
+    const float* area = power + n;
+    const uint32_t* k = in + kSelftestTableHeaderIn + 2 * (size_t)n;
+    float pm = 0.0f;
+    for (uint32_t e = 0; e < n; e++) {
+        if (!(power[e] >= 0.0f && power[e] <= kFloatMax))
+            return fail(c, RT3_E_INVALID, "selftest: light table power " + std::to_string(e) + " is negative or not finite");
+        pm = power[e] > pm ? power[e] : pm;
+    }
+    for (uint32_t i = 0; i < n_k; i++)  // light_find indexes the guide cells with k >> shift: nothing is launched that would read outside them
+        if (k[i] >= (1u << 23)) return fail(c, RT3_E_INVALID, "selftest: light table k " + std::to_string(i) + " is not below 2^23");
+    if (n_k && pm == 0.0f) return fail(c, RT3_E_INVALID, "selftest: light table: every power is 0, so nothing can be looked up (n_k must be 0)");
+    HIPC(c, hipSetDevice(c->device));
+    bool overrun = false;
+    HIPC(c, lights_selftest_table(c->stream, n, power, pm, area, n_k, k, out, &overrun));
+    if (overrun) return fail(c, RT3_E_STATE, "selftest: a light table kernel wrote behind an array's end, or a record word that is not p_sel / area");
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 40 && c && in && out) return selftest_light_table(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 39 && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 37 && c && in && out) return selftest_absorb_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 35 && c && in && out) return selftest_adaptive_compact(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));

@@ -517,6 +517,13 @@ struct LightTable {
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
                         const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out, const float* punct = nullptr, uint32_t n_punct = 0,
                         uint32_t n_world_prims = 0);
+// self-test op 40: the selection part of lights_build (weights, scan, CDF and p_sel / area, guide cells; the same function, scratch layout
+// and launch shapes) on n caller-made powers and areas, then light_find on n_k values of k.  Host arrays; max_power is the largest power.
+// out: {cells, shift, total}, cdf[n], the records' p_sel / area words [n], guide[cells + 1], n_k entries found.  Every device array is one
+// element longer and pattern-filled: *overrun when a word behind an end, or a record word that is not p_sel / area, changed.
+constexpr uint32_t kSelftestTableHeaderIn = 2, kSelftestTableHeader = 3;
+hipError_t lights_selftest_table(hipStream_t st, uint32_t n, const float* power, float max_power, const float* area, uint32_t n_k, const uint32_t* k,
+                                 uint32_t* out, bool* overrun);
 // self-test op 30: rows {light index, P, N} -> {wl, range end, cs, I'} from punctual records made of `lights` (n_lights x 16 words, device)
 void launch_selftest_light(hipStream_t st, const float4* lights, uint32_t n_lights, const uint32_t* in, uint32_t n, uint32_t* out);
 

@@ -7,7 +7,8 @@
 //   k_emit_cdf   : cdf[e] = floor(prefix[e] / total * 2^23), exact in fp64 (prefix < 2^53); p_sel / area into the record
 //   k_emit_guide : guide cells for a constant-time start of the lookup
 // Selection then happens on the 2^-23 grid uniform_float produces: emitter e is picked for exactly (cdf[e] - cdf[e-1]) of its 2^23 values,
-// so the probability the estimator divides by is the one realised.
+// so the probability the estimator divides by is the one realised.  Everything from k_emit_quant on is select_build, which self-test op 40
+// runs on caller-made powers (tests/test_light_table.py pins it bit for bit).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -180,7 +181,7 @@ __global__ void k_emit_guide(const uint32_t* __restrict__ cdf, uint32_t n, uint3
             continue;
         }
         const uint32_t k = c << shift;
-        uint32_t lo = 0, hi = n - 1;
+        uint32_t lo = 0, hi = n;  // n: no entry has cdf > k, which only a table without power has (cdf[n - 1] = 2^23 otherwise); it is never looked up
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
             if (cdf[mid] > k) hi = mid;
@@ -193,6 +194,41 @@ __global__ void k_emit_guide(const uint32_t* __restrict__ cdf, uint32_t n, uint3
 template <typename T>
 static hipError_t alloc_n(DevBuf<T>& b, size_t n) {
     return b.alloc_bytes((n ? n : 1) * sizeof(T));
+}
+
+// The selection part of the table: powers -> weights -> scan -> CDF and p_sel / area -> guide cells.  lights_build and self-test op 40 both
+// come through here: one scratch layout, one set of launch shapes.
+struct SelectScratch {
+    float* power = nullptr;
+    uint32_t* max_power = nullptr;
+    unsigned long long *q = nullptr, *prefix = nullptr;
+    char* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+};
+// power, max word, weights, prefix, scan storage, in this order at the head of `plan`
+static hipError_t select_plan(hipStream_t st, uint32_t n, BufLayout& plan, SelectScratch* s) {
+    RT3_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, s->scan_bytes, s->q, s->prefix, (int)n, st));
+    plan.add(&s->power, n).add(&s->max_power, 1).add(&s->q, n).add(&s->prefix, n).add(&s->scan_tmp, s->scan_bytes);
+    return hipSuccess;
+}
+// the smallest power of two >= n, at most kMaxGuideCells, and the shift that takes a k in [0, 2^23) to its cell
+static void guide_shape(uint32_t n, uint32_t* cells, uint32_t* shift) {
+    *cells = 1;
+    *shift = 23;
+    while (*cells < n && *cells < kMaxGuideCells) {
+        *cells <<= 1;
+        (*shift)--;
+    }
+}
+// s.power[n] and *s.max_power are in place; area[n] -> cdf[n], rec[4 e].w, guide[cells + 1]
+static hipError_t select_build(hipStream_t st, const SelectScratch& s, const float* area, uint32_t n, uint32_t cells, uint32_t shift, uint32_t* cdf,
+                               float4* rec, uint32_t* guide) {
+    size_t scan_bytes = s.scan_bytes;
+    hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, s.power, s.max_power, n, s.q);
+    RT3_TRY(hipcub::DeviceScan::InclusiveSum(s.scan_tmp, scan_bytes, s.q, s.prefix, (int)n, st));
+    hipLaunchKernelGGL(k_emit_cdf, dim3(grid_of(n)), dim3(256), 0, st, s.prefix, area, n, cdf, rec);
+    hipLaunchKernelGGL(k_emit_guide, dim3(grid_of((uint64_t)cells + 1)), dim3(256), 0, st, cdf, n, cells, shift, guide);
+    return hipGetLastError();
 }
 
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
@@ -213,34 +249,28 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
         RT3_TRY(hipStreamSynchronize(st));  // (the host vector goes out of scope)
         return hipSuccess;
     }
-    uint32_t cells = 1, shift = 23;
-    while (cells < n && cells < kMaxGuideCells) {
-        cells <<= 1;
-        shift--;
-    }
+    uint32_t cells, shift;
+    guide_shape(n, &cells, &shift);
     RT3_TRY(alloc_n(out->rec, 4 * (size_t)n));
     RT3_TRY(alloc_n(out->cdf, n));
     RT3_TRY(alloc_n(out->prim, n));
     RT3_TRY(alloc_n(out->area, n));
     RT3_TRY(alloc_n(out->guide, (size_t)cells + 1));
-    // scratch: power, max word, weights, prefix, scan storage
-    float* power = nullptr;
+    // scratch: the selection's, then the punctual lights' input and the world box
+    SelectScratch sel;
     float4* punct_in = nullptr;
-    uint32_t *max_power = nullptr, *bounds = nullptr;
-    unsigned long long *q = nullptr, *prefix = nullptr;
-    char* scan_tmp = nullptr;
-    size_t scan_bytes = 0;
-    RT3_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, q, prefix, (int)n, st));
+    uint32_t* bounds = nullptr;
     BufLayout plan;
-    plan.add(&power, n).add(&max_power, 1).add(&q, n).add(&prefix, n).add(&scan_tmp, scan_bytes).add(&punct_in, 4 * (size_t)n_punct).add(&bounds, 6);
+    RT3_TRY(select_plan(st, n, plan, &sel));
+    plan.add(&punct_in, 4 * (size_t)n_punct).add(&bounds, 6);
     RT3_TRY(out->scratch.grow_bytes(plan.bytes()));
     RT3_TRY(plan.carve(out->scratch));
     const uint32_t* d_eg_geom = out->geom_base.get() + ng;
     const uint32_t* d_eg_first = d_eg_geom + neg;
-    RT3_TRY(hipMemsetAsync(max_power, 0, 4, st));
+    RT3_TRY(hipMemsetAsync(sel.max_power, 0, 4, st));
     if (n_emit)
         hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n_emit)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, d_eg_geom, d_eg_first, (uint32_t)neg,
-                           n_emit, out->rec.get(), out->prim.get(), out->area.get(), power, max_power);
+                           n_emit, out->rec.get(), out->prim.get(), out->area.get(), sel.power, sel.max_power);
     if (n_punct) {
         RT3_TRY(hipMemcpyAsync(punct_in, punct, 64 * (size_t)n_punct, hipMemcpyHostToDevice, st));
         RT3_TRY(hipMemsetAsync(bounds, 0xFF, 12, st));  // min: beyond every ordered float; max: 0 = below every one
@@ -248,13 +278,9 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
         if (n_world_prims)
             hipLaunchKernelGGL(k_world_bounds, dim3(grid_of(n_world_prims)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, n_world_prims, bounds);
         hipLaunchKernelGGL(k_punct_records, dim3(grid_of(n_punct)), dim3(256), 0, st, punct_in, n_punct, n_emit, bounds, out->rec.get(), out->prim.get(), out->area.get(),
-                           power, max_power);
+                           sel.power, sel.max_power);
     }
-    hipLaunchKernelGGL(k_emit_quant, dim3(grid_of(n)), dim3(256), 0, st, power, max_power, n, q);
-    RT3_TRY(hipcub::DeviceScan::InclusiveSum(scan_tmp, scan_bytes, q, prefix, (int)n, st));
-    hipLaunchKernelGGL(k_emit_cdf, dim3(grid_of(n)), dim3(256), 0, st, prefix, out->area.get(), n, out->cdf.get(), out->rec.get());
-    hipLaunchKernelGGL(k_emit_guide, dim3(grid_of((uint64_t)cells + 1)), dim3(256), 0, st, out->cdf.get(), n, cells, shift, out->guide.get());
-    RT3_TRY(hipGetLastError());
+    RT3_TRY(select_build(st, sel, out->area.get(), n, cells, shift, out->cdf.get(), out->rec.get(), out->guide.get()));
     uint32_t total = 0;
     RT3_TRY(hipMemcpyAsync(&total, out->cdf.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
     RT3_TRY(hipStreamSynchronize(st));
@@ -264,6 +290,74 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     out->n_guide = cells;
     out->guide_shift = shift;
     out->total = total;
+    return hipSuccess;
+}
+
+// self-test op 40
+__global__ void k_selftest_light_find(LightsDev lt, const uint32_t* __restrict__ k, uint32_t n_k, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_k) out[i] = light_find(lt, k[i]);
+}
+hipError_t lights_selftest_table(hipStream_t st, uint32_t n, const float* power, float max_power, const float* area, uint32_t n_k, const uint32_t* k,
+                                 uint32_t* out, bool* overrun) {
+    constexpr uint32_t kGuard = 0xA5A5A5A5u;
+    *overrun = false;
+    uint32_t cells, shift;
+    guide_shape(n, &cells, &shift);
+    // the table's arrays, each one element longer than the kernels may write
+    DevBuf<float4> rec;
+    DevBuf<uint32_t> cdf, guide, d_k, found;
+    DevBuf<float> d_area;
+    DevBuf<char> scratch;  // the op's own: the context's may be in use
+    RT3_TRY(rec.alloc_bytes(64 * ((size_t)n + 1)));
+    RT3_TRY(cdf.alloc_bytes(4 * ((size_t)n + 1)));
+    RT3_TRY(guide.alloc_bytes(4 * ((size_t)cells + 2)));
+    RT3_TRY(d_k.alloc_bytes(4 * ((size_t)n_k + 1)));
+    RT3_TRY(found.alloc_bytes(4 * ((size_t)n_k + 1)));
+    RT3_TRY(d_area.alloc_bytes(4 * (size_t)n));
+    SelectScratch sel;
+    BufLayout plan;
+    RT3_TRY(select_plan(st, n, plan, &sel));
+    RT3_TRY(scratch.alloc_bytes(plan.bytes()));
+    RT3_TRY(plan.carve(scratch));
+    RT3_TRY(hipMemsetAsync(scratch.get(), 0xA5, plan.bytes(), st));  // a weight or a prefix the kernels do not write is not a small number
+    RT3_TRY(hipMemsetAsync(rec.get(), 0xA5, 64 * ((size_t)n + 1), st));
+    RT3_TRY(hipMemsetAsync(cdf.get(), 0xA5, 4 * ((size_t)n + 1), st));
+    RT3_TRY(hipMemsetAsync(guide.get(), 0xA5, 4 * ((size_t)cells + 2), st));
+    RT3_TRY(hipMemsetAsync(found.get(), 0xA5, 4 * ((size_t)n_k + 1), st));
+    RT3_TRY(hipMemcpyAsync(sel.power, power, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    RT3_TRY(hipMemcpyAsync(sel.max_power, &max_power, 4, hipMemcpyHostToDevice, st));
+    RT3_TRY(hipMemcpyAsync(d_area.get(), area, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    if (n_k) RT3_TRY(hipMemcpyAsync(d_k.get(), k, 4 * (size_t)n_k, hipMemcpyHostToDevice, st));
+    RT3_TRY(select_build(st, sel, d_area.get(), n, cells, shift, cdf.get(), rec.get(), guide.get()));
+    if (n_k) {
+        LightsDev lt{};
+        lt.rec = rec.get(); lt.cdf = cdf.get(); lt.guide = guide.get();
+        lt.n = n; lt.guide_shift = shift;
+        hipLaunchKernelGGL(k_selftest_light_find, dim3((n_k + 255) / 256), dim3(256), 0, st, lt, d_k.get(), n_k, found.get());
+        RT3_TRY(hipGetLastError());
+    }
+    RT3_TRY(hipStreamSynchronize(st));
+    uint32_t* o_cdf = out + kSelftestTableHeader;
+    uint32_t* o_w = o_cdf + n;
+    uint32_t* o_guide = o_w + n;
+    uint32_t* o_find = o_guide + cells + 1;
+    std::vector<uint32_t> h_rec(16 * ((size_t)n + 1));
+    uint32_t tail[3];
+    RT3_TRY(hipMemcpy(o_cdf, cdf.get(), 4 * (size_t)n, hipMemcpyDeviceToHost));
+    RT3_TRY(hipMemcpy(&tail[0], cdf.get() + n, 4, hipMemcpyDeviceToHost));
+    RT3_TRY(hipMemcpy(h_rec.data(), rec.get(), 64 * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    RT3_TRY(hipMemcpy(o_guide, guide.get(), 4 * ((size_t)cells + 1), hipMemcpyDeviceToHost));
+    RT3_TRY(hipMemcpy(&tail[1], guide.get() + cells + 1, 4, hipMemcpyDeviceToHost));
+    if (n_k) RT3_TRY(hipMemcpy(o_find, found.get(), 4 * (size_t)n_k, hipMemcpyDeviceToHost));
+    RT3_TRY(hipMemcpy(&tail[2], found.get() + n_k, 4, hipMemcpyDeviceToHost));
+    for (int j = 0; j < 3; j++) *overrun |= tail[j] != kGuard;
+    for (size_t w = 0; w < h_rec.size(); w++)  // of a record only word 3, p_sel / area, is the selection's to write
+        if (w / 16 < n && w % 16 == 3) o_w[w / 16] = h_rec[w];
+        else *overrun |= h_rec[w] != kGuard;
+    out[0] = cells;
+    out[1] = shift;
+    out[2] = o_cdf[n - 1];
     return hipSuccess;
 }
 

@@ -320,7 +320,8 @@ RT3_DEV Surface hit_info(const SceneDev& sc, uint32_t prim, float bu, float bv) 
 // The emitter table (rt3_lights.hip).  Record e, 64 bytes = 4 float4:
 //   {A.xyz, p_sel / area}  {E1.xyz, Le.r}  {E2.xyz, Le.g}  {unit geometric normal, Le.b}
 // A, A + E1, A + E2: the world-space triangle as flattening makes it; Le = 12 emission (hit_finish's value); p_sel = mass / 2^23, exact.
-// cdf: inclusive integer CDF (cdf[n - 1] = 2^23); guide: 2^23 >> guide_shift cells + 1, cell c holds the first e with cdf[e] > c << shift.
+// cdf: inclusive integer CDF (cdf[n - 1] = 2^23); guide: 2^23 >> guide_shift cells + 1, cell c holds the first e with cdf[e] > c << shift (n in a
+// table without power, which is never looked up: LightTable::dev gives it n = 0); the last word is n - 1.
 struct LightsDev {
     const float4* rec;
     const uint32_t* cdf;

@@ -295,6 +295,44 @@ class Context:
             self.check(self.lib.rt3_light_masses(self.h, int(flags), C.byref(ne), C.byref(npu), mass.ctypes.data))
         return ne.value, npu.value, mass
 
+    def light_table(self, flags):
+        """(records (n, 16) float32, cdf (n,) uint32, guide (cells + 1,) uint32, primitive ids (n,) uint32, areas (n,) float32, cells, shift) of
+        the light table that `flags` samples, as the shading kernel reads it (rt3_light_table): record words {A, p_sel / area} {E1, Le.r}
+        {E2, Le.g} {normal, Le.b}; entries in light_masses' order.  Empty arrays and cells = 0 when the combination samples nothing."""
+        ne, npu, _ = self.light_masses(flags)
+        cells, shift = C.c_uint32(), C.c_uint32()
+        self.check(self.lib.rt3_light_table(self.h, int(flags), None, None, None, None, None, C.byref(cells), C.byref(shift)))
+        n = ne + npu
+        rec, cdf = np.zeros((n, 16), np.float32), np.zeros(n, np.uint32)
+        guide = np.zeros(cells.value + 1 if n else 0, np.uint32)
+        prim, area = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        if n:
+            self.check(self.lib.rt3_light_table(self.h, int(flags), rec.ctypes.data, cdf.ctypes.data, guide.ctypes.data, prim.ctypes.data, area.ctypes.data,
+                                                C.byref(cells), C.byref(shift)))
+        return rec, cdf, guide, prim, area, cells.value, shift.value
+
+    def selftest_light_table(self, power, area, k=()):
+        """Self-test op 40: the light table's quantise, scan, CDF and guide kernels on the float32 powers and areas of n lights (the launch
+        shapes and scratch layout of the context's own table), then light_find on the values `k` (< 2^23).  Returns (cells, shift, total,
+        cdf (n,) uint32, p_sel / area (n,) float32, guide (cells + 1,) uint32, found (len(k),) uint32).  The library fails the call when a
+        kernel wrote anything else."""
+        power = np.ascontiguousarray(power, np.float32).reshape(-1)
+        area = np.ascontiguousarray(area, np.float32).reshape(-1)
+        k = np.ascontiguousarray(k, np.uint32).reshape(-1)
+        n, n_k = len(power), len(k)
+        assert len(area) == n
+        cells = 1
+        while cells < n and cells < (1 << 20):
+            cells <<= 1
+        inp = np.concatenate([np.array([n, n_k], np.uint32), power.view(np.uint32), area.view(np.uint32), k])
+        out = np.zeros(3 + 2 * n + cells + 1 + n_k, np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_LIGHT_TABLE, inp.ctypes.data, n, out.ctypes.data))
+        assert int(out[0]) == cells
+        o = 3
+        cdf, w = out[o:o + n], out[o + n:o + 2 * n].view(np.float32)
+        guide = out[o + 2 * n:o + 2 * n + cells + 1]
+        return int(out[0]), int(out[1]), int(out[2]), cdf, w, guide, out[o + 2 * n + cells + 1:]
+
     def snapshot_vertices(self):
         """the positions the vertex buffer holds now become the previous frame's (rt3_scene_snapshot_vertices): the "motion" pass follows
         geometries that update_vertices() deforms afterwards.  A device-side copy of the ranges updated since the last snapshot."""
