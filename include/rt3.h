@@ -730,9 +730,9 @@ int rt3_adaptive_get_coverage(rt3_ctx *ctx, int *on);
  *      Coupled passes while a lens is set: "postprocess" takes every pixel from In (the Depth == background branch would put the pinhole sky
  *      over half of each antialiased silhouette); "adaptive" returns RT3_E_STATE (it selects pixels by G-buffer depth) unless
  *      rt3_adaptive_set_coverage lets it take every pixel; "refrence_mode", and "adaptive" then, with samples * bounces * 8 > 2^31 return RT3_E_INVALID (the vertices' RNG indices would reach the camera's).  "gbuffer", "denoise",
- *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres.  "denoise" is guided
- *      by that G-buffer too unless it is given the lens frame's own guide images (rt3_camera_set_guide_output and
- *      rt3_denoise_set_guide_input, below); guiding a depth-of-field frame by the pinhole G-buffer is not supported.
+ *      "temporal", "motion" and the probe passes do not know the lens: they see the pinhole G-buffer at pixel centres.  "denoise" and
+ *      "temporal" are guided by that G-buffer too unless they are given the lens frame's own guide images (rt3_camera_set_guide_output,
+ *      rt3_denoise_set_guide_input and rt3_temporal_set_guide_input, below); guiding a depth-of-field frame by the pinhole G-buffer is not supported.
  *      rt3_camera_get_lens (either pointer may be NULL): the parameters last set (the defaults {0, 1, 1, 0} before any) and whether on. ---- */
 typedef struct rt3_lens_params {
     float aperture_radius;  /* world units, >= 0; 0 = pinhole */
@@ -776,6 +776,26 @@ typedef struct rt3_guide_images {
 int rt3_camera_set_guide_output(rt3_ctx *ctx, const rt3_guide_images *images);  /* NULL: off, the default */
 int rt3_camera_get_guide_output(rt3_ctx *ctx, rt3_guide_images *out, int *enabled);
 int rt3_denoise_set_guide_input(rt3_ctx *ctx, const rt3_guide_images *images);  /* NULL: the G-buffer, the default */
+/* ---- temporal accumulation for lens and glass frames.  No reference counterpart; DESIGN.md section 4v.
+ *      rt3_temporal_set_guide_input gives "temporal" two guide sets -- the one this frame's "refrence_mode" wrote and the one the previous
+ *      frame's wrote -- as its surface records in the G-buffer's place.  Both NULL (the default) = the G-buffer, and every bit the pass
+ *      writes is what it was; exactly one NULL returns RT3_E_INVALID and changes nothing.  The pass keeps its ten bindings and its
+ *      parameters; gbuffer, gbuffer_depth, PrevGbuffer and PrevDepth are then validated and not read.  rt3_temporal_set_prev_view is still
+ *      required: its view, proj and window_size are read.  Per pixel, in fp32, one rounding per operation, no contraction:
+ *        foreground iff current.position.w == 1 and l2 = (n.x n.x + n.y n.y) + n.z n.z of current.normal is finite and positive; every
+ *          other pixel is treated as a background pixel is: Out = In bit for bit, History = Moments = 0;
+ *        P = position.xyz, n = normal.xyz * (1 / sqrt(l2)), m = max(albedo, 1/256), e = emission, c = (In - e) / m
+ *          (RT3_TEMPORAL_NO_DEMODULATION: m = 1, e = 0);
+ *        P is projected into the previous view as above; a tap counts when it lies inside the window, the previous set is foreground
+ *          there by the same rule, PrevHistory.w > 0, dot(n, n_q) >= normal_cos and |dot(n, P_q - P)| <= plane_tolerance |P - eye|,
+ *          with n_q and P_q from previous.normal and previous.position (read, not reconstructed through the previous camera);
+ *        the blend and the three images written are those above.  previous.albedo and previous.emission are not read.
+ *      The eight images are checked at each "temporal" launch, before anything is enqueued: live RGBA32F images of the window's size,
+ *      pairwise different, none of them Out, History or Moments, else RT3_E_INVALID.  A guide input together with a motion input
+ *      (rt3_temporal_set_motion_input != 0) returns RT3_E_STATE: the "motion" image is made from pinhole primary hits and does not describe
+ *      the samples, so moved instances and deformed meshes are caught only as far as the plane test catches them.  The refusal under a
+ *      tile partition of several ranks stays.  Equal to tests/ref_temporal_guide.py bit for bit. ---- */
+int rt3_temporal_set_guide_input(rt3_ctx *ctx, const rt3_guide_images *current, const rt3_guide_images *previous);  /* NULL, NULL: the G-buffer */
 /* ---- Russian roulette on extension rays.  No reference counterpart; DESIGN.md section 4o.  By default every path that still has an extension
  *      ray is traced and shaded for all GConst.bounces vertices.  With roulette set, "refrence_mode" and "adaptive" test the extension ray that
  *      a path emitted at vertex b, for start_bounce <= b < bounces - 1, between the shading of vertex b and the trace that follows, in a

@@ -62,7 +62,7 @@ EXPORTS = [
     "rt3_scene_set_prev_transforms", "rt3_temporal_set_motion_input",
     "rt3_adaptive_set_params", "rt3_adaptive_info", "rt3_adaptive_set_coverage", "rt3_adaptive_get_coverage",
     "rt3_camera_set_lens", "rt3_camera_get_lens",
-    "rt3_camera_set_guide_output", "rt3_camera_get_guide_output", "rt3_denoise_set_guide_input",
+    "rt3_camera_set_guide_output", "rt3_camera_get_guide_output", "rt3_denoise_set_guide_input", "rt3_temporal_set_guide_input",
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses", "rt3_light_table",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
@@ -266,6 +266,7 @@ def load():
         "rt3_camera_set_guide_output": (i32, [vp, C.POINTER(GuideImages)]),
         "rt3_camera_get_guide_output": (i32, [vp, C.POINTER(GuideImages), C.POINTER(i32)]),
         "rt3_denoise_set_guide_input": (i32, [vp, C.POINTER(GuideImages)]),
+        "rt3_temporal_set_guide_input": (i32, [vp, C.POINTER(GuideImages), C.POINTER(GuideImages)]),
         "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),
         "rt3_path_get_roulette": (i32, [vp, C.POINTER(RouletteParams), C.POINTER(i32)]),
         "rt3_path_roulette_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

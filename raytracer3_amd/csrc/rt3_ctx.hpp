@@ -296,6 +296,10 @@ struct rt3_ctx {
     struct Guide {
         rt3_guide_images out = {0u, 0u, 0u, 0u}, in = {0u, 0u, 0u, 0u};
         bool out_on = false, in_on = false;
+        // rt3_temporal_set_guide_input: the sets of this frame and of the previous one that "temporal" takes its
+        // records from; off by default, checked at every launch
+        rt3_guide_images temporal_cur = {0u, 0u, 0u, 0u}, temporal_prev = {0u, 0u, 0u, 0u};
+        bool temporal_on = false;
     } guide;
     // rt3_passes.hip: Russian roulette on extension rays (rt3_path_set_roulette): off by default
     struct Roulette {

@@ -566,6 +566,11 @@ struct TemporalLaunch {
     const float *depth, *prev_depth;
     void *out, *history, *moments;
     const void* motion = nullptr;  // rt3_temporal_set_motion_input: the "motion" pass's image, or none
+    // rt3_temporal_set_guide_input: {position, normal, albedo, emission} of this lens frame and of the previous
+    // one (all set, or all null: the G-buffer).  With them k_temporal_guide runs: gbuffer, depth, prev_gbuffer, prev_depth and motion are
+    // not read, nor are prev_guide[2] and [3]
+    const float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
+    const float4* prev_guide[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 void launch_temporal(hipStream_t st, const TemporalLaunch& L);
 

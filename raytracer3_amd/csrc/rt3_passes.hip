@@ -10,7 +10,8 @@
 // for "refrence_mode" and "adaptive".
 // trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
 // Also owns rt3_ctx::guide: the guide images of a lens frame (rt3_camera_set_guide_output, rt3_denoise_set_guide_input, DESIGN.md section
-// 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through its two guided end kernels.
+// 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through its two guided end kernels, and the two
+// sets "temporal" reads through k_temporal_guide (rt3_temporal_set_guide_input).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -814,6 +815,24 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
             return fail(c, RT3_E_INVALID, "temporal: the motion input (rt3_temporal_set_motion_input) must not be 'Out', 'History' or 'Moments'");
         L.motion = mv->ptr;
     }
+    // rt3_temporal_set_guide_input: a lens frame's sample means, this frame's and the previous one's, are the
+    // surface records; gbuffer, gbuffer_depth, PrevGbuffer and PrevDepth are not read.  Before anything is enqueued
+    if (c->guide.temporal_on) {
+        if (c->temporal.motion_image)
+            return fail(c, RT3_E_STATE, "temporal: a guide input (rt3_temporal_set_guide_input) and a motion input (rt3_temporal_set_motion_input) are both "
+                                        "set: the \"motion\" image is made from pinhole primary hits and does not describe the camera samples; unset one (0 / NULL)");
+        const Resource* const written[3] = {r[7], r[8], r[9]};
+        float4* gi[8];
+        if (int e = guide_resolve(c, c->guide.temporal_cur, W, H, "temporal: guide input, current", written, 3, "'Out', 'History' or 'Moments'", gi)) return e;
+        if (int e = guide_resolve(c, c->guide.temporal_prev, W, H, "temporal: guide input, previous", written, 3, "'Out', 'History' or 'Moments'", gi + 4)) return e;
+        for (int k = 1; k < 8; k++)
+            for (int j = 0; j < k; j++)
+                if (gi[j] == gi[k]) return fail(c, RT3_E_INVALID, "temporal: guide input: the eight images (current and previous) must be different images");
+        for (int k = 0; k < 4; k++) {
+            L.guide[k] = gi[k];
+            L.prev_guide[k] = gi[4 + k];
+        }
+    }
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_temporal(c->stream, L);
@@ -1069,6 +1088,18 @@ int rt3_denoise_set_guide_input(rt3_ctx* c, const rt3_guide_images* gi) {
     if (!c) return RT3_E_INVALID;
     c->guide.in_on = gi != nullptr;
     if (gi) c->guide.in = *gi;  // checked when "denoise" is launched, like the variance input
+    return RT3_OK;
+}
+// both NULL: the G-buffer, the default; one NULL: refused, nothing changed.  The images are checked when "temporal" is launched
+int rt3_temporal_set_guide_input(rt3_ctx* c, const rt3_guide_images* current, const rt3_guide_images* previous) {
+    if (!c) return RT3_E_INVALID;
+    if ((current == nullptr) != (previous == nullptr))
+        return fail(c, RT3_E_INVALID, "temporal guide input: give the current and the previous guide images, or NULL for both (the G-buffer)");
+    c->guide.temporal_on = current != nullptr;
+    if (current) {
+        c->guide.temporal_cur = *current;
+        c->guide.temporal_prev = *previous;
+    }
     return RT3_OK;
 }
 int rt3_path_set_roulette(rt3_ctx* c, const rt3_roulette_params* p) {

@@ -7,6 +7,8 @@
 //                 History = {c_acc.rgb, N}, Moments = {mu1, mu2, variance, N}, Out = {emission + c_acc * albedo, In.a}
 //                 <true>: with the "motion" pass's image (rt3_motion.hip) the projected point is where the surface
 //                 point was one frame ago; <false> (no input set) projects P itself
+//   k_temporal_guide -> the same pass for lens and glass frames: the record of this pixel and of each tap comes from the guide images of
+//                 this and of the previous frame (rt3_temporal_set_guide_input) instead of the pinhole G-buffer
 //
 // Arithmetic contract: tests/ref_temporal.py restates every operation below in numpy float32, in this order (matrix rows summed left to
 // right like primary_ray, taps rows outer, columns inner); the pass equals it bit for bit.  A tap that does not count is skipped: the
@@ -147,9 +149,136 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
     a.out[pi] = make_float4(r.x, r.y, r.z, L.w);
 }
 
+struct TemporalGuideArgs {  // k_temporal_guide: everything but the two cameras
+    uint32_t W, H, flags;
+    float alpha, alpha_moments, max_history, normal_cos, plane_tolerance;
+    const float4 *position, *normal, *albedo, *emission;  // this frame's guide images
+    const float4 *prev_position, *prev_normal;            // the previous frame's; its albedo and emission are not read
+    const float4* in;
+    const float4 *prev_history, *prev_moments;
+    float4 *out, *history, *moments;
+};
+
+// A guide texel is foreground iff every camera sample hit (position.w == 1) and the summed normal has a finite, positive squared length:
+// k_dn_prepare_guide's rule
+RT3_DEV bool guide_foreground(float cover, float l2) { return cover == 1.0f && l2 > 0.0f && l2 <= kFloatMax; }
+
+// "temporal" for lens and glass frames (rt3_temporal_set_guide_input): the surface record comes from the frame's own
+// guide images -- P = position.xyz, n = normal.xyz * (1 / sqrtf(l2)), m = max(albedo, 1/256), e = emission, unquantised, what the lens
+// frame shaded -- and a tap's from the previous frame's guide images: its position is read, not reconstructed through the previous
+// camera.  Reprojection, the four taps, the blend and the three writes are k_temporal<false>'s, operation for operation;
+// tests/ref_temporal_guide.py restates the kernel, and the pass equals it bit for bit.  Per tap the loads are ordered so that a rejected
+// tap costs the fewest bytes: coverage and normal (32 B), then history (16 B), then moments (16 B).  A foreground pixel reads 80 B of this
+// frame, gathers up to 4 x 64 B of the previous one and writes 48 B; every record is an aligned float4.
+__global__ __launch_bounds__(256) void k_temporal_guide(GConstDev g, GConstDev prev, TemporalGuideArgs a) {
+    const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
+    const uint32_t W = a.W, H = a.H;
+    if (px >= W || py >= H) return;
+    const size_t pi = (size_t)py * W + px;
+    const float4 GP = a.position[pi], GN = a.normal[pi];
+    const float4 L = a.in[pi];
+    const float l2 = dot(v3(GN.x, GN.y, GN.z), v3(GN.x, GN.y, GN.z));
+    if (!guide_foreground(GP.w, l2)) {
+        a.out[pi] = L;
+        a.history[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        a.moments[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float inv_len = 1.0f / sqrtf(l2);
+    const V3 n = v3(GN.x * inv_len, GN.y * inv_len, GN.z * inv_len);
+    const V3 P = v3(GP.x, GP.y, GP.z);
+    V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
+    if (!(a.flags & 1u)) {
+        const float4 al = a.albedo[pi], em = a.emission[pi];
+        m = v3(al.x > kDnAlbedoFloor ? al.x : kDnAlbedoFloor, al.y > kDnAlbedoFloor ? al.y : kDnAlbedoFloor, al.z > kDnAlbedoFloor ? al.z : kDnAlbedoFloor);
+        e = v3(em.x, em.y, em.z);
+    }
+    const V3 c = dn_demodulate(L, e, m);
+    const float l = dn_lum(c.x, c.y, c.z);
+
+    // reproject P into the previous view
+    const float vx = mat_row(prev.view, 0, P.x, P.y, P.z, 1.0f), vy = mat_row(prev.view, 1, P.x, P.y, P.z, 1.0f);
+    const float vz = mat_row(prev.view, 2, P.x, P.y, P.z, 1.0f), vw = mat_row(prev.view, 3, P.x, P.y, P.z, 1.0f);
+    const float qx = mat_row(prev.proj, 0, vx, vy, vz, vw), qy = mat_row(prev.proj, 1, vx, vy, vz, vw), qw = mat_row(prev.proj, 3, vx, vy, vz, vw);
+    float ws = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, k1 = 0.0f, k2 = 0.0f;
+    if (qw > 0.0f) {
+        const float Wf = g.window_size[0], Hf = g.window_size[1];
+        const float ndx = qx / qw, ndy = qy / qw;
+        const float sx = (ndx * 0.5f + 0.5f) * Wf - 0.5f, sy = (-ndy * 0.5f + 0.5f) * Hf - 0.5f;
+        if (sx > -1.0f && sx < Wf && sy > -1.0f && sy < Hf) {
+            const float x0f = floorf(sx), y0f = floorf(sy);
+            const float fx = sx - x0f, fy = sy - y0f;
+            const int x0 = (int)x0f, y0 = (int)y0f;  // -1 .. W - 1, -1 .. H - 1
+            const V3 dE = P - v3(g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]);
+            const float tol = a.plane_tolerance * sqrtf(dot(dE, dE));
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int ty = y0 + j;
+                if (ty < 0 || ty >= (int)H) continue;
+                const float wy = j ? fy : 1.0f - fy;
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const int tx = x0 + i;
+                    if (tx < 0 || tx >= (int)W) continue;
+                    const size_t qi = (size_t)ty * W + tx;
+                    const float4 QP = a.prev_position[qi], QN = a.prev_normal[qi];
+                    const float q2 = dot(v3(QN.x, QN.y, QN.z), v3(QN.x, QN.y, QN.z));
+                    if (!guide_foreground(QP.w, q2)) continue;
+                    const float4 ph = a.prev_history[qi];
+                    if (!(ph.w > 0.0f)) continue;
+                    const float inv_q = 1.0f / sqrtf(q2);
+                    const V3 nq = v3(QN.x * inv_q, QN.y * inv_q, QN.z * inv_q);
+                    if (!(dot(n, nq) >= a.normal_cos)) continue;
+                    const V3 dP = v3(QP.x, QP.y, QP.z) - P;
+                    if (!(fabsf(dot(n, dP)) <= tol)) continue;
+                    const float4 pm = a.prev_moments[qi];
+                    const float wt = (i ? fx : 1.0f - fx) * wy;
+                    ws = ws + wt;
+                    hr = hr + wt * ph.x;
+                    hg = hg + wt * ph.y;
+                    hb = hb + wt * ph.z;
+                    hn = hn + wt * ph.w;
+                    k1 = k1 + wt * pm.x;
+                    k2 = k2 + wt * pm.y;
+                }
+            }
+        }
+    }
+    float N = 1.0f, cr = c.x, cg = c.y, cb = c.z, mu1 = l, mu2 = l * l;
+    if (ws > 0.0f) {
+        hr = hr / ws;
+        hg = hg / ws;
+        hb = hb / ws;
+        hn = hn / ws;
+        k1 = k1 / ws;
+        k2 = k2 / ws;
+        const float n1 = hn + 1.0f;
+        N = n1 < a.max_history ? n1 : a.max_history;
+        const float inv = 1.0f / N;
+        const float ac = a.alpha > inv ? a.alpha : inv, am = a.alpha_moments > inv ? a.alpha_moments : inv;
+        cr = hr + ac * (c.x - hr);
+        cg = hg + ac * (c.y - hg);
+        cb = hb + ac * (c.z - hb);
+        mu1 = k1 + am * (l - k1);
+        mu2 = k2 + am * (mu2 - k2);
+    }
+    const float d = mu2 - mu1 * mu1;
+    const V3 r = dn_modulate(v3(cr, cg, cb), e, m);
+    a.history[pi] = make_float4(cr, cg, cb, N);
+    a.moments[pi] = make_float4(mu1, mu2, d > 0.0f ? d : 0.0f, N);
+    a.out[pi] = make_float4(r.x, r.y, r.z, L.w);
+}
+
 }  // namespace
 
 void launch_temporal(hipStream_t st, const TemporalLaunch& L) {
+    if (L.guide[0]) {  // rt3_temporal_set_guide_input: the G-buffer bindings and the motion image are not read
+        const TemporalGuideArgs ga = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance,
+                                      L.guide[0], L.guide[1], L.guide[2], L.guide[3], L.prev_guide[0], L.prev_guide[1], (const float4*)L.in,
+                                      (const float4*)L.prev_history, (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments};
+        hipLaunchKernelGGL(k_temporal_guide, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, ga);
+        return;
+    }
     const TemporalArgs a = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance, (const uint4*)L.gbuffer,
                             L.depth, (const float4*)L.in, (const uint32_t*)L.prev_gbuffer, L.prev_depth, (const float4*)L.prev_history,
                             (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments, (const float4*)L.motion};

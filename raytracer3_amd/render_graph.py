@@ -533,6 +533,12 @@ class Context:
         g = self._guide_images(images)
         self.check(self.lib.rt3_denoise_set_guide_input(self.h, C.byref(g) if g is not None else None))
 
+    def set_temporal_guide_input(self, current=None, previous=None):
+        """the guide images of this frame and of the previous one that "temporal" takes its surface records from in the G-buffer's place
+        (rt3_temporal_set_guide_input); both None = the G-buffer, the default; one None is refused"""
+        cur, prev = self._guide_images(current), self._guide_images(previous)
+        self.check(self.lib.rt3_temporal_set_guide_input(self.h, C.byref(cur) if cur is not None else None, C.byref(prev) if prev is not None else None))
+
     def selftest_guide_queue(self, pixels, records, nsb, samples, first, last, groups, prefill=None):
         """Self-test op 39: k_lens_guide on the camera and hit queues `records` (nsb * npix, 10) of 32-bit words {o xyz, d xyz, t, bu, bv, prim}
         (record sample_in_batch * npix + pixel index) over the pixel words `pixels` and the built scene, launched with `groups`

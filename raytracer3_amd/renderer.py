@@ -53,10 +53,21 @@ class Camera:
 GUIDE_IMAGES = (("position", "GuidePosition"), ("normal", "GuideNormal"), ("albedo", "GuideAlbedo"), ("emission", "GuideEmission"))
 
 
+# the second set: the guide images of the previous temporal frame.  The two sets trade names once per guided temporal
+# frame, as History / PrevHistory do (TEMPORAL_SWAPS)
+PREV_GUIDE_IMAGES = tuple((key, "Prev" + name) for key, name in GUIDE_IMAGES)
+GUIDE_SWAPS = tuple((name, "Prev" + name) for _, name in GUIDE_IMAGES)
+
+
 def guide_images(rg):
     """the four guide images of a lens frame as a dict {position, normal, albedo, emission} of handles: what
     ctx.set_guide_output and ctx.set_denoise_guide_input take"""
     return {key: rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, name) for key, name in GUIDE_IMAGES}
+
+
+def prev_guide_images(rg):
+    """the guide images of the previous temporal frame, like guide_images(): the second argument of ctx.set_temporal_guide_input"""
+    return {key: rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, name) for key, name in PREV_GUIDE_IMAGES}
 
 
 def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False, *,
@@ -72,7 +83,8 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     `gbuffer_names` are the images the G-buffer and its depth live in.
     With `guide` (a lens frame whose context has the guide output set, ctx.set_guide_output) the four images of guide_images() are
     declared as context-state writes of the path-trace node and, with `denoise`, as context-state reads of the "denoise" node (handle
-    `guide`: the dict of guide_images); they are no bindings."""
+    `guide`: the dict of guide_images); they are no bindings.  With `temporal` too (ctx.set_temporal_guide_input)
+    the "temporal" node reads them as context state as well, and the previous frame's set (handle `prev_guide`: prev_guide_images)."""
     full, f4 = ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT
     gbuffer = rg.image(full, L.FORMAT_R32G32B32A32_UINT, gbuffer_names[0])
     depth = rg.image(full, L.FORMAT_R32_SFLOAT, gbuffer_names[1])
@@ -82,7 +94,7 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         handles["prev"] = rg.image(full, f4, "PrevLight")
     if trace or postprocess:
         handles["color"] = rg.image(full, f4, "color")
-    gb = src = IMPORTED
+    gb = src = guide_origin = IMPORTED
     if gbuffer_node:
         gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
               .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
@@ -97,17 +109,21 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
             for h in guide_images(rg).values():
                 pt.state_write(h)
         src = pt.launch(WorkSize2D.FullScreen)
+        guide_origin = src
     if guide:
         handles["guide"] = guide_images(rg)
+        if temporal:
+            handles["prev_guide"] = prev_guide_images(rg)
     lit = light
     if motion:
         handles["motion"] = motion_node(rg, gconst)[1]
     if temporal:
-        src, th = temporal_node(rg, gconst, gb, gbuffer, depth, src, light)
+        src, th = temporal_node(rg, gconst, gb, gbuffer, depth, src, light, guide=handles.get("guide"), guide_origin=guide_origin,
+                                prev_guide=handles.get("prev_guide"))
         handles.update(th)
         lit = th["accumulated"]
     if denoise:
-        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit, guide=handles.get("guide"), guide_origin=src if trace and not temporal else IMPORTED)
+        src, lit = denoise_node(rg, gconst, gb, gbuffer, depth, src, lit, guide=handles.get("guide"), guide_origin=guide_origin)
         handles["denoised"] = lit
     if postprocess:
         (ComputePass.new(rg, "postprocess").shader("postprocess").constants(gconst)
@@ -137,15 +153,21 @@ def temporal_images(rg):
                 accumulated=rg.image(full, f4, "accumulated"), history=rg.image(full, f4, "History"), moments=rg.image(full, f4, "Moments"))
 
 
-def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light):
+def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light, guide=None, guide_origin=IMPORTED, prev_guide=None):
     """ComputePass("temporal"): {gbuffer, gbuffer_depth, In = `light`, PrevGbuffer, PrevDepth, PrevHistory, PrevMoments, Out = `accumulated`,
-    History, Moments}.  The previous view is context state (ctx.set_prev_view).  Returns (node, the handles of temporal_images)."""
+    History, Moments}.  The previous view is context state (ctx.set_prev_view).  Returns (node, the handles of temporal_images).  `guide`
+    and `prev_guide`: the dicts of guide_images() and prev_guide_images() the pass reads as context state (ctx.set_temporal_guide_input),
+    the first written by node `guide_origin`."""
     t = temporal_images(rg)
     tn = (ComputePass.new(rg, "temporal").shader("temporal").constants(gconst)
           .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light)
           .read(IMPORTED, t["prev_gbuffer"]).read(IMPORTED, t["prev_depth"]).read(IMPORTED, t["prev_history"]).read(IMPORTED, t["prev_moments"])
-          .write(IMPORTED, t["accumulated"]).write(IMPORTED, t["history"]).write(IMPORTED, t["moments"]).dispatch(DispatchSize.FullScreen))
-    return tn, t
+          .write(IMPORTED, t["accumulated"]).write(IMPORTED, t["history"]).write(IMPORTED, t["moments"]))
+    for h in (guide or {}).values():
+        tn.state_read(guide_origin, h)
+    for h in (prev_guide or {}).values():
+        tn.state_read(IMPORTED, h)
+    return tn.dispatch(DispatchSize.FullScreen), t
 
 
 def motion_node(rg, gconst):
@@ -236,6 +258,8 @@ class PathTracer:
         self._glass_lens = False  # the lens in force is the pinhole set_scene switched on for a scene with glass
         self._scene_set = False   # set_scene has built a structure (set_pane_shadows rebuilds it)
         self._guide = False       # set_guide: lens frames write guide images, and "denoise" is guided by them
+        self._guide_temporal = False    # set_guide(temporal=True): temporal lens frames write them too, and "temporal" reads two sets
+        self._temporal_guided = False   # the history images were written by a guided "temporal" (the other kind of frame starts over)
 
     def close(self):
         self.ctx.close()
@@ -313,11 +337,17 @@ class PathTracer:
         """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
         self._history.reset()
 
-    def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth")):
+    def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth"), guide=False):
         """Before a temporal frame's nodes are built: what the last temporal frame wrote, and the G-buffer it read (the images named
         `gbuffer_names`), become `Prev*` (the images trade names, like swap_light_prev), or, with no history, zeros are uploaded; the
         previous view and the variance input of "denoise" are set.  A frame rendered without `temporal` in between overwrites the kept
-        G-buffer: call reset_history() after one.  Returns whether the frame needs the "motion" node."""
+        G-buffer: call reset_history() after one.  Returns whether the frame needs the "motion" node.
+        `guide` (set_guide(temporal=True) with a lens in force): "temporal" takes its records from this frame's guide
+        images and from the previous guided temporal frame's (the two sets trade names behind each such frame, _end_temporal); the motion
+        input stays 0 whatever moved.  A guided frame after an unguided one, and the reverse, start the history over."""
+        if guide != self._temporal_guided:
+            self._history.reset()
+            self._temporal_guided = guide
         rg, prev_gconst = self.rg, self._history.prev_gconst
         temporal_images(rg)
         for name, fmt in zip(gbuffer_names, (L.FORMAT_R32G32B32A32_UINT, L.FORMAT_R32_SFLOAT)):
@@ -335,8 +365,22 @@ class PathTracer:
         self.ctx.set_prev_view(prev_gconst if prev_gconst is not None else gconst)
         self.ctx.set_denoise_variance_input(t["moments"] if denoise else 0)
         moved = self._history.begin_frame()  # "temporal" then reads the "motion" pass's image
+        if guide:
+            moved = False  # the "motion" image is made from pinhole primary hits: it does not describe the camera samples
+            self.ctx.set_temporal_guide_input(guide_images(rg), prev_guide_images(rg))
+        elif self._guide:
+            self.ctx.set_temporal_guide_input(None, None)
         self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved else 0)
         return moved
+
+    def _end_temporal(self, gconst, guide):
+        """Behind a temporal frame: its view is the next one's previous view; behind a guided one the two guide sets trade names, so that
+        the next "refrence_mode" writes the other set and this frame's is `Prev*`."""
+        self._history.end_frame(gconst)
+        if guide:
+            n = self.rg.named
+            for a, b in GUIDE_SWAPS:
+                n[a], n[b] = n[b], n[a]
 
     def update_vertices(self, vertices, first=0):
         """deformed vertices (same topology): upload them and refit the acceleration structure.  Between temporal frames the positions as
@@ -363,23 +407,32 @@ class PathTracer:
         else:
             self.ctx.set_lens(L.LensParams(aperture, focus, jitter))
 
-    def set_guide(self, on=True):
+    def set_guide(self, on=True, temporal=False):
         """Sample-guided denoising of lens frames, off by default.  While on and a lens is in force -- set_lens, or the
         pinhole set_scene switches on for a scene with glass -- render() has "refrence_mode" write the four guide images (handle `guide`,
         guide()) from the frame's own camera samples, and render(g, denoise=True) and denoise() filter by them instead of by the pinhole
-        G-buffer.  Without a lens, and for temporal or adaptive frames, everything is as with the guide off.  With several ranks
-        denoise() raises: the guide images are not gathered."""
+        G-buffer.  Without a lens, and for adaptive frames, everything is as with the guide off; so it is for temporal frames unless
+        `temporal`: then render(g, temporal=True[, denoise=True]) writes the guide too, "temporal" takes its surface
+        records from this frame's and the previous temporal frame's guide images instead of the pinhole G-buffer, and "denoise" is guided
+        by this frame's with the temporal variance.  Such frames never run "motion": moved instances and updated vertices are caught only
+        as far as the plane test catches them.  With several ranks denoise() raises: the guide images are not gathered."""
         self._guide = bool(on)
+        self._guide_temporal = self._guide and bool(temporal)
         if not self._guide:
             self.ctx.set_guide_output(None)
             self.ctx.set_denoise_guide_input(None)
+            self.ctx.set_temporal_guide_input(None, None)
+
+    def _temporal_guide_in_force(self, adaptive=False):
+        """whether a temporal frame rendered now is a guided one (set_guide(temporal=True), a lens in force, not adaptive)"""
+        return bool(self._guide_temporal and not adaptive and self.ctx.get_lens()[1])
 
     def _guide_in_force(self, denoise, temporal=False, adaptive=False):
         """Set the context's guide output and input for the frame that follows; returns whether the frame has guide images.  A tracer whose
         guide was never switched on makes no call."""
         if not self._guide:
             return False
-        on = self.ctx.get_lens()[1] and not temporal and not adaptive
+        on = self.ctx.get_lens()[1] and (not temporal or self._guide_temporal) and not adaptive
         images = guide_images(self.rg) if on else None
         self.ctx.set_guide_output(images)
         self.ctx.set_denoise_guide_input(images if denoise else None)
@@ -435,16 +488,18 @@ class PathTracer:
         frame; the whole-window G-buffer is rendered into images of its own, which render() does not touch, on one rank too) and
         "denoise" -- unless `denoise` is False -- filters its `accumulated` image with the temporal variance."""
         rg = self.rg
-        guide = self._guide and denoise and not temporal and self.ctx.get_lens()[1]  # the last render()'s guide images (set_guide)
+        tguide = temporal and self._temporal_guide_in_force()
+        # the last render()'s guide images (set_guide)
+        guide = tguide or bool(self._guide and denoise and not temporal and self.ctx.get_lens()[1])
         if guide and self.n_ranks > 1:
             raise ValueError("denoise() with the sample guide on (set_guide) needs the whole frame's guide images on this rank, and they are not "
                              "gathered: render on one rank, or switch the guide off")
         names = ("TemporalGbuffer", "TemporalDepth") if temporal else ("gbuffer", "gbuffer_depth")  # render() must not overwrite the kept one
-        moved = temporal and self._begin_temporal(gconst, denoise, names)
+        moved = temporal and self._begin_temporal(gconst, denoise, names, guide=tguide)
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
         if self._guide:
-            self.ctx.set_denoise_guide_input(guide_images(rg) if guide else None)
+            self.ctx.set_denoise_guide_input(guide_images(rg) if guide and denoise else None)
         rg.begin_frame()
         h = frame_nodes(rg, gconst, False, denoise, temporal, moved, gbuffer_names=names, gbuffer_node=self.n_ranks > 1 or temporal, trace=False,
                         guide=guide)
@@ -454,7 +509,7 @@ class PathTracer:
                 rg.draw_frame(h["motion"])
             rg.draw_frame(h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"]), wait=wait)
         if temporal:
-            self._history.end_frame(gconst)
+            self._end_temporal(gconst, tguide)
         return self.handles
 
     def probe_commands(self, gconst: L.GConst):
@@ -510,20 +565,23 @@ class PathTracer:
         and "temporal" follows the instances and the deformed geometries.
         `adaptive`: an L.AdaptiveParams (or True for the parameters the context holds): the "adaptive" pass renders `Light` instead of
         "refrence_mode", with gconst.samples as the cap; its Moments image is the handle `adaptive_moments` (adaptive_moments(),
-        sample_counts(), ctx.adaptive_info())."""
+        sample_counts(), ctx.adaptive_info()).
+        Under set_guide(True, temporal=True) with a lens in force a temporal frame is guided by the camera samples:
+        handles `guide` and `prev_guide`, and no "motion" node whatever moved."""
         if adaptive is not None and adaptive is not True and adaptive is not False:
             self.ctx.adaptive_set_params(adaptive)
-        motion = temporal and self._begin_temporal(gconst, denoise)
+        adaptive_on = adaptive is not None and adaptive is not False
+        tguide = temporal and self._temporal_guide_in_force(adaptive_on)
+        motion = temporal and self._begin_temporal(gconst, denoise, guide=tguide)
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
-        adaptive_on = adaptive is not None and adaptive is not False
         guide = self._guide_in_force(denoise, temporal, adaptive_on)
         h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive_on, guide=guide)
         if motion:
             self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
         if temporal:
-            self._history.end_frame(gconst)
+            self._end_temporal(gconst, tguide)
         return h
 
     # ---- results

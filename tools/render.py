@@ -21,6 +21,8 @@
                          (--adaptive with --aa, --aperture or a scene with glass: the pass's coverage mode, every pixel sampled to the threshold)
   python tools/render.py --scene glass_cornell --size 1920x1080 --spp 4 --bounces 8 --denoise --guide --out glass_4spp_denoised.png
                          (--guide: the a-trous filter guided by the lens frame's own camera samples)
+  python tools/render.py --scene glass_cornell --size 1920x1080 --spp 1 --bounces 8 --temporal 16 --denoise --guide --out glass_1spp_temporal.png
+                         (--temporal with --guide: the "temporal" pass takes its surface records from the guide images too, section 4v)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -59,8 +61,8 @@ def main():
     ap.add_argument("--aa", action="store_true", help="per-sample camera rays: every sample's film point is drawn from the whole pixel (DESIGN.md section 4m)")
     ap.add_argument("--aperture", type=float, default=0.0, metavar="R", help="thin lens of radius R (world units); implies per-sample camera rays")
     ap.add_argument("--focus", type=float, default=1.0, metavar="F", help="with --aperture: view depth of the plane of focus")
-    ap.add_argument("--guide", action="store_true", help="with --denoise and a lens (--aa, --aperture, a scene with glass): guide the filter by the frame's own "
-                                                         "camera samples instead of the pinhole G-buffer (PathTracer.set_guide, DESIGN.md section 4u)")
+    ap.add_argument("--guide", action="store_true", help="with --denoise or --temporal and a lens (--aa, --aperture, a scene with glass): guide the filters by the "
+                                                         "frame's own camera samples instead of the pinhole G-buffer (PathTracer.set_guide, DESIGN.md sections 4u, 4v)")
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--curve", default=None, help="write the RMSE-vs-spp convergence curve (JSON) here")
     ap.add_argument("--roulette", nargs="?", type=int, const=2, default=None, metavar="START",
@@ -114,15 +116,15 @@ def main():
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
     if args.aa or args.aperture > 0.0:
-        if args.temporal or (args.denoise and not args.guide):
-            ap.error("--aa / --aperture do not combine with --temporal, nor with --denoise unless --guide: those passes are guided by the pinhole G-buffer")
+        if (args.temporal or args.denoise) and not args.guide:
+            ap.error("--aa / --aperture do not combine with --temporal or --denoise unless --guide: those passes are guided by the pinhole G-buffer")
         pt.set_lens(args.aperture, args.focus, 1.0)
     if args.guide:
-        if args.temporal or args.adaptive is not None:
-            ap.error("--guide guides single refrence_mode frames: it does not combine with --temporal or --adaptive")
+        if args.adaptive is not None:
+            ap.error("--guide guides refrence_mode frames: it does not combine with --adaptive")
         if not pt.ctx.get_lens()[1]:
             ap.error("--guide needs per-sample camera rays: --aa, --aperture or a scene with glass")
-        pt.set_guide(True)
+        pt.set_guide(True, temporal=bool(args.temporal))
     if args.roulette is not None:
         pt.set_roulette(args.roulette)
     adaptive = None
