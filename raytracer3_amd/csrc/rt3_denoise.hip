@@ -6,8 +6,9 @@
 //                    "temporal" pass where its history is at least 4 frames long: rt3_denoise_set_variance_input)
 //   k_dn_atrous   -> one iteration at step 2^i: 5 x 5 B3-spline taps weighted by h * w_n * expn(x_z + x_l); ping-pong between two signal images
 //   k_dn_finish   -> Out = emission + c * albedo (alpha and background pixels: In, bit for bit)
-// With a guide input (rt3_denoise_set_guide_input) the first and the last are k_dn_prepare_guide and k_dn_finish_guide,
-// which take the records from a lens frame's guide images instead of the G-buffer; the two in between are the same launches.
+// The first and the last are templates over the source of the records (rt3_filter_device.hpp): k_dn_prepare<DnGbuffer> and
+// k_dn_finish<DnGbuffer>, or with a guide input (rt3_denoise_set_guide_input) the <DnGuide> instances, which take
+// the records from a lens frame's guide images instead of the G-buffer; the two in between are the same launches.
 //
 // Arithmetic contract: tests/ref_denoise.py restates every operation below in numpy float32, in this order (taps rows outer, columns
 // inner); the pass equals it bit for bit.  A background record is all zero: its normal makes w_n, hence the tap's weight, exactly 0, so
@@ -45,28 +46,26 @@ RT3_DEV void dn_geo(const DnCentre& p, float4 gP, float4 gN, uint32_t squarings,
     xz = (d / (r + kDnTinyR)) * inv_sigma_z;
 }
 
-__global__ __launch_bounds__(256) void k_dn_prepare(GConstDev g, uint32_t W, uint32_t H, uint32_t flags, const uint4* __restrict__ gbuffer,
-                                                    const float* __restrict__ depth, const float4* __restrict__ in, float4* __restrict__ gP,
-                                                    float4* __restrict__ gN, float4* __restrict__ sig) {
+// Src: DnGbuffer (36 bytes read per foreground pixel) or, with a guide input, DnGuide (80: rt3_denoise_set_guide_input, DESIGN.md section
+// 4u; tests/ref_guide.py prepare_guide() restates that one).  Every pixel the source does not call foreground gets the all-zero record.
+template <class Src>
+__global__ __launch_bounds__(256) void k_dn_prepare(GConstDev g, uint32_t W, uint32_t H, uint32_t flags, Src src, const float4* __restrict__ in,
+                                                    float4* __restrict__ gP, float4* __restrict__ gN, float4* __restrict__ sig) {
     const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
     if (px >= W || py >= H) return;
     const size_t pi = (size_t)py * W + px;
-    const float t = depth[pi];
-    if (t == kBackgroundDepth) {
+    const typename Src::Texel x = src.fetch(pi);
+    if (!src.foreground(x)) {
         gP[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         gN[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         sig[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-    const uint4 w = gbuffer[pi];
     const float4 L = in[pi];
-    V3 m, e;
-    dn_modulation(flags, w, m, e);
-    const V3 n = unpack_normal_11_10_11(w.y);
-    const V3 P = dn_position(g, px, py, t);
-    const V3 s = dn_demodulate(L, e, m);
-    gP[pi] = make_float4(P.x, P.y, P.z, 1.0f);
-    gN[pi] = make_float4(n.x, n.y, n.z, 0.0f);
+    const DnSurface r = src.surface(g, flags, px, py, pi, x);
+    const V3 s = dn_demodulate(L, r.k);
+    gP[pi] = make_float4(r.P.x, r.P.y, r.P.z, 1.0f);
+    gN[pi] = make_float4(r.n.x, r.n.y, r.n.z, 0.0f);
     sig[pi] = make_float4(s.x, s.y, s.z, 0.0f);
 }
 
@@ -211,76 +210,18 @@ __global__ __launch_bounds__(256) void k_dn_atrous(uint32_t W, uint32_t H, int s
     sout[pi] = make_float4(ar / ws, ag / ws, ab / ws, vs / (ws * ws));
 }
 
-__global__ __launch_bounds__(256) void k_dn_finish(uint32_t W, uint32_t H, uint32_t flags, const uint4* __restrict__ gbuffer,
-                                                   const float* __restrict__ depth, const float4* __restrict__ in, const float4* __restrict__ sig,
-                                                   float4* __restrict__ out) {
+// Out = e + c * m where k_dn_prepare<Src> made a foreground record (Src::prepared: the depth again for the G-buffer, 4 bytes; gP.w, which
+// no stage in between writes, for the guide); alpha and every other pixel: In, bit for bit
+template <class Src>
+__global__ __launch_bounds__(256) void k_dn_finish(uint32_t W, uint32_t H, uint32_t flags, Src src, const float4* __restrict__ gP,
+                                                   const float4* __restrict__ in, const float4* __restrict__ sig, float4* __restrict__ out) {
     const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
     if (px >= W || py >= H) return;
     const size_t pi = (size_t)py * W + px;
     float4 L = in[pi];
-    if (depth[pi] != kBackgroundDepth) {
+    if (src.prepared(gP, pi)) {
         const float4 c = sig[pi];
-        V3 m, e;
-        dn_modulation(flags, gbuffer[pi], m, e);
-        const V3 r = dn_modulate(v3(c.x, c.y, c.z), e, m);
-        L.x = r.x;
-        L.y = r.y;
-        L.z = r.z;
-    }
-    out[pi] = L;
-}
-
-// The two end stages guided by a lens frame's sample means (rt3_denoise_set_guide_input) instead of the pinhole
-// G-buffer.  A pixel is foreground iff every camera sample hit (position.w == 1) and the summed normal has a finite, positive squared
-// length l2; then P = position.xyz, n = normal.xyz * (1 / sqrtf(l2)) (the header's normalize), m = max(albedo, 1/256), e = emission --
-// unquantised, what the lens frame shaded.  Every other pixel gets the all-zero background record.  tests/ref_guide.py prepare_guide()
-// restates it.  80 bytes read per pixel against k_dn_prepare's 36.
-__global__ __launch_bounds__(256) void k_dn_prepare_guide(uint32_t W, uint32_t H, uint32_t flags, const float4* __restrict__ position,
-                                                          const float4* __restrict__ normal, const float4* __restrict__ albedo,
-                                                          const float4* __restrict__ emission, const float4* __restrict__ in,
-                                                          float4* __restrict__ gP, float4* __restrict__ gN, float4* __restrict__ sig) {
-    const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const size_t pi = (size_t)py * W + px;
-    const float4 P = position[pi], N = normal[pi];
-    const float l2 = dot(v3(N.x, N.y, N.z), v3(N.x, N.y, N.z));
-    if (!(P.w == 1.0f) || !(l2 > 0.0f) || !(l2 <= kFloatMax)) {
-        gP[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        gN[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        sig[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
-    }
-    const float inv = 1.0f / sqrtf(l2);
-    V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
-    if (!(flags & 1u)) {
-        const float4 a = albedo[pi], em = emission[pi];
-        m = v3(a.x > kDnAlbedoFloor ? a.x : kDnAlbedoFloor, a.y > kDnAlbedoFloor ? a.y : kDnAlbedoFloor, a.z > kDnAlbedoFloor ? a.z : kDnAlbedoFloor);
-        e = v3(em.x, em.y, em.z);
-    }
-    const V3 s = dn_demodulate(in[pi], e, m);
-    gP[pi] = make_float4(P.x, P.y, P.z, 1.0f);
-    gN[pi] = make_float4(N.x * inv, N.y * inv, N.z * inv, 0.0f);
-    sig[pi] = make_float4(s.x, s.y, s.z, 0.0f);
-}
-
-// Out = emission + c * max(albedo, 1/256) where k_dn_prepare_guide made a foreground record (gP.w, which no stage in between writes);
-// alpha and every other pixel: In, bit for bit
-__global__ __launch_bounds__(256) void k_dn_finish_guide(uint32_t W, uint32_t H, uint32_t flags, const float4* __restrict__ gP,
-                                                         const float4* __restrict__ albedo, const float4* __restrict__ emission,
-                                                         const float4* __restrict__ in, const float4* __restrict__ sig, float4* __restrict__ out) {
-    const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const size_t pi = (size_t)py * W + px;
-    float4 L = in[pi];
-    if (gP[pi].w != 0.0f) {
-        const float4 c = sig[pi];
-        V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
-        if (!(flags & 1u)) {
-            const float4 a = albedo[pi], em = emission[pi];
-            m = v3(a.x > kDnAlbedoFloor ? a.x : kDnAlbedoFloor, a.y > kDnAlbedoFloor ? a.y : kDnAlbedoFloor, a.z > kDnAlbedoFloor ? a.z : kDnAlbedoFloor);
-            e = v3(em.x, em.y, em.z);
-        }
-        const V3 r = dn_modulate(v3(c.x, c.y, c.z), e, m);
+        const V3 r = dn_modulate(v3(c.x, c.y, c.z), src.modulation(flags, pi));
         L.x = r.x;
         L.y = r.y;
         L.z = r.z;
@@ -299,10 +240,18 @@ void denoise_plan(uint32_t W, uint32_t H, BufLayout& plan, DenoiseScratch* s) {
     const size_t n = (size_t)W * H;
     plan.add(&s->gP, n).add(&s->gN, n).add(&s->sig[0], n).add(&s->sig[1], n);
 }
+// the two end stages take their records from the guide input where one is set (rt3_denoise_set_guide_input), else from the G-buffer
+template <class Launch>
+static void with_source(const DenoiseLaunch& L, Launch launch) {
+    if (L.guide[0]) launch(DnGuide{L.guide[0], L.guide[1], L.guide[2], L.guide[3]});
+    else launch(DnGbuffer{(const uint4*)L.gbuffer, L.depth});
+}
 // prepare writes sig[0]; the variance stage sig[0] -> sig[1]; iteration i reads sig[(i + 1) & 1] and writes sig[i & 1]
 void launch_denoise_prepare(hipStream_t st, const DenoiseLaunch& L) {
-    hipLaunchKernelGGL(k_dn_prepare, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.W, L.H, L.flags, (const uint4*)L.gbuffer, L.depth,
-                       (const float4*)L.in, L.s.gP, L.s.gN, L.s.sig[0]);
+    with_source(L, [&](auto src) {
+        hipLaunchKernelGGL(k_dn_prepare<decltype(src)>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.W, L.H, L.flags, src,
+                           (const float4*)L.in, L.s.gP, L.s.gN, L.s.sig[0]);
+    });
 }
 void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L) {
     auto k = L.moments ? k_dn_variance<true> : k_dn_variance<false>;
@@ -316,16 +265,10 @@ void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iter
                        L.s.gN, L.s.sig[(iteration + 1u) & 1u], L.s.sig[iteration & 1u]);
 }
 void launch_denoise_finish(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations) {
-    hipLaunchKernelGGL(k_dn_finish, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.flags, (const uint4*)L.gbuffer, L.depth,
-                       (const float4*)L.in, L.s.sig[(iterations - 1u) & 1u], (float4*)L.out);
-}
-void launch_denoise_prepare_guide(hipStream_t st, const DenoiseLaunch& L) {
-    hipLaunchKernelGGL(k_dn_prepare_guide, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.flags, L.guide[0], L.guide[1], L.guide[2],
-                       L.guide[3], (const float4*)L.in, L.s.gP, L.s.gN, L.s.sig[0]);
-}
-void launch_denoise_finish_guide(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations) {
-    hipLaunchKernelGGL(k_dn_finish_guide, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.flags, (const float4*)L.s.gP, L.guide[2],
-                       L.guide[3], (const float4*)L.in, L.s.sig[(iterations - 1u) & 1u], (float4*)L.out);
+    with_source(L, [&](auto src) {
+        hipLaunchKernelGGL(k_dn_finish<decltype(src)>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.W, L.H, L.flags, src,
+                           (const float4*)L.s.gP, (const float4*)L.in, (const float4*)L.s.sig[(iterations - 1u) & 1u], (float4*)L.out);
+    });
 }
 void launch_selftest_denoise(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out) {
     hipLaunchKernelGGL(k_selftest_expn, dim3((n + 255) / 256), dim3(256), 0, st, in, n, out);

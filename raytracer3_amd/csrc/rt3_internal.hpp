@@ -547,13 +547,11 @@ struct DenoiseLaunch {
     DenoiseScratch s;
 };
 void denoise_plan(uint32_t W, uint32_t H, BufLayout& plan, DenoiseScratch* s);
+// prepare and finish read L.guide where it is set, in the G-buffer's place; the stages between them do not differ
 void launch_denoise_prepare(hipStream_t st, const DenoiseLaunch& L);
 void launch_denoise_variance(hipStream_t st, const DenoiseLaunch& L);
 void launch_denoise_atrous(hipStream_t st, const DenoiseLaunch& L, uint32_t iteration);
 void launch_denoise_finish(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
-// the two end stages with L.guide in the G-buffer's place; the stages between them are the ones above
-void launch_denoise_prepare_guide(hipStream_t st, const DenoiseLaunch& L);
-void launch_denoise_finish_guide(hipStream_t st, const DenoiseLaunch& L, uint32_t iterations);
 void launch_selftest_denoise(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);  // selftest op 28: expn
 
 // "temporal" pass (rt3_temporal.hip): one kernel, one thread per pixel, no scratch.  `prev` is the previous frame's
@@ -567,8 +565,8 @@ struct TemporalLaunch {
     void *out, *history, *moments;
     const void* motion = nullptr;  // rt3_temporal_set_motion_input: the "motion" pass's image, or none
     // rt3_temporal_set_guide_input: {position, normal, albedo, emission} of this lens frame and of the previous
-    // one (all set, or all null: the G-buffer).  With them k_temporal_guide runs: gbuffer, depth, prev_gbuffer, prev_depth and motion are
-    // not read, nor are prev_guide[2] and [3]
+    // one (all set, or all null: the G-buffer).  With them k_temporal<TemporalGuide> runs: gbuffer, depth, prev_gbuffer, prev_depth and
+    // motion are not read, nor are prev_guide[2] and [3]
     const float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
     const float4* prev_guide[4] = {nullptr, nullptr, nullptr, nullptr};
 };

@@ -10,8 +10,8 @@
 // for "refrence_mode" and "adaptive".
 // trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
 // Also owns rt3_ctx::guide: the guide images of a lens frame (rt3_camera_set_guide_output, rt3_denoise_set_guide_input, DESIGN.md section
-// 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through its two guided end kernels, and the two
-// sets "temporal" reads through k_temporal_guide (rt3_temporal_set_guide_input).
+// 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through the <DnGuide> instances of its two end
+// kernels, and the two sets "temporal" reads through k_temporal<TemporalGuide> (rt3_temporal_set_guide_input).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -773,8 +773,7 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
     for (int k = 0; k < 4; k++) L.guide[k] = guide[k];
     {
         ScopedTimer t(c, CAT_OTHER);
-        if (guide[0]) launch_denoise_prepare_guide(c->stream, L);
-        else launch_denoise_prepare(c->stream, L);
+        launch_denoise_prepare(c->stream, L);
     }
     {
         ScopedTimer t(c, CAT_OTHER);
@@ -786,8 +785,7 @@ int pass_denoise(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resour
     }
     {
         ScopedTimer t(c, CAT_OTHER);
-        if (guide[0]) launch_denoise_finish_guide(c->stream, L, p.iterations);
-        else launch_denoise_finish(c->stream, L, p.iterations);
+        launch_denoise_finish(c->stream, L, p.iterations);
     }
     HIPC(c, hipGetLastError());
     return RT3_OK;

@@ -2,24 +2,28 @@
 // half of SVGF).  No reference counterpart (the reference blends pixel (x, y) with pixel (x, y): refrence_mode's PrevLight); DESIGN.md
 // section 4g.
 //
-//   k_temporal -> per pixel: the surface record of the denoise pass (rt3_filter_device.hpp), its world position projected into the previous
-//                 view, four bilinear taps of the previous History / Moments that pass a normal and a plane test, and the blend
+//   k_temporal<Src> -> per pixel: the surface record of the denoise pass (rt3_filter_device.hpp), its world position projected into the
+//                 previous view, four bilinear taps of the previous History / Moments that pass a normal and a plane test, and the blend
 //                 History = {c_acc.rgb, N}, Moments = {mu1, mu2, variance, N}, Out = {emission + c_acc * albedo, In.a}
-//                 <true>: with the "motion" pass's image (rt3_motion.hip) the projected point is where the surface
-//                 point was one frame ago; <false> (no input set) projects P itself
-//   k_temporal_guide -> the same pass for lens and glass frames: the record of this pixel and of each tap comes from the guide images of
-//                 this and of the previous frame (rt3_temporal_set_guide_input) instead of the pinhole G-buffer
+//   Src says where the record of this pixel and of each tap comes from:
+//     TemporalGbuffer<false> the pinhole G-buffer of this frame and of the previous one
+//     TemporalGbuffer<true>  the same, and with the "motion" pass's image (rt3_motion.hip) the projected point is
+//                            where the surface point was one frame ago instead of P itself
+//     TemporalGuide          lens and glass frames: the guide images of this and of the previous frame (rt3_temporal_set_guide_input,
+//                            DESIGN.md section 4v)
 //
 // Arithmetic contract: tests/ref_temporal.py restates every operation below in numpy float32, in this order (matrix rows summed left to
-// right like primary_ray, taps rows outer, columns inner); the pass equals it bit for bit.  A tap that does not count is skipped: the
-// reference adds +0 in its place, which leaves every bit of a sum that started at +0 alone.  The window test on the reprojected position is
-// made in float before anything becomes an integer, so NaN and huge values never reach the conversion, and every tap index is tested against
-// the window before it is used.  A thread writes only its own pixel and reads only this frame's and the previous frame's images, which the
-// host checks to be different from the three it writes: the result does not depend on the launch shape.
+// right like primary_ray, taps rows outer, columns inner), tests/ref_motion.py and tests/ref_temporal_guide.py the records of the other
+// two sources; the pass equals them bit for bit.  A tap that does not count is skipped: the reference adds +0 in its place, which leaves
+// every bit of a sum that started at +0 alone.  The window test on the reprojected position is made in float before anything becomes an
+// integer, so NaN and huge values never reach the conversion, and every tap index is tested against the window before it is used.  A
+// thread writes only its own pixel and reads only this frame's and the previous frame's images, which the host checks to be different
+// from the three it writes: the result does not depend on the launch shape.
 //
-// A foreground pixel reads 36 B of this frame, gathers up to 4 x 52 B of the previous one and writes 48 B.  Under small motion the taps of
-// neighbouring pixels are the same cache lines, so the gathers are plain cached loads (no LDS tile: the footprint is not tile-aligned, the
-// case that lost in DESIGN.md section 7's denoise measurements).
+// From the G-buffer a foreground pixel reads 36 B of this frame, gathers up to 4 x 52 B of the previous one and writes 48 B; from the guide
+// it reads 80 B and gathers up to 4 x 64 B, every record an aligned float4.  Under small motion the taps of neighbouring pixels are the
+// same cache lines, so the gathers are plain cached loads (no LDS tile: the footprint is not tile-aligned, the case that lost in
+// DESIGN.md section 7's denoise measurements).
 #include <hip/hip_runtime.h>
 
 #include "rt3_camera.hpp"
@@ -31,53 +35,61 @@ namespace rt3 {
 
 namespace {
 
-struct TemporalArgs {  // everything but the two cameras
+struct TemporalArgs {  // everything but the two cameras and the source
     uint32_t W, H, flags;
     float alpha, alpha_moments, max_history, normal_cos, plane_tolerance;
-    const uint4* gbuffer;
-    const float* depth;
     const float4* in;
-    const uint32_t* prev_gbuffer;  // 4 words per pixel; only word 1, the normal, is read
-    const float* prev_depth;
     const float4 *prev_history, *prev_moments;
     float4 *out, *history, *moments;
+};
+
+// A source: `cur` gives this pixel's record and `prev` a tap's (rt3_filter_device.hpp; the kernel asks a tap for its texel, then the
+// history, then its normal and position, so a rejected tap costs the fewest bytes: from the G-buffer the depth, the history, the packed
+// normal, the position reconstructed through the previous camera; from the guide position and normal (32 B), read, not reconstructed,
+// then the history).  lookup() may replace the point R that is looked up in the previous frame, or say that it is not known.
+template <bool MOTION>
+struct TemporalGbuffer {
+    DnGbuffer cur, prev;   // of prev's words only word 1, the normal, is read
     const float4* motion;  // MOTION only: the "motion" pass's image {P', kind}
+    // MOTION: R is the Motion texel's point (where this surface point was one frame ago) instead of P, and a texel of kind < 1 on a
+    // foreground pixel means "no history".  Everything else stays on the current frame.
+    RT3_DEV void lookup(size_t pi, V3& R, bool& known) const {
+        if (MOTION) {
+            const float4 M = motion[pi];
+            R = v3(M.x, M.y, M.z);
+            known = !(M.w < 1.0f);
+        }
+    }
+};
+struct TemporalGuide {
+    DnGuide cur, prev;  // prev's albedo and emission are not read
+    RT3_DEV void lookup(size_t, V3&, bool&) const {}
 };
 
 // row r of (column-major m) * (v, w), summed left to right like primary_ray
 RT3_DEV float mat_row(const float* m, int r, float x, float y, float z, float w) { return m[r] * x + m[4 + r] * y + m[8 + r] * z + m[12 + r] * w; }
 
-// MOTION: the point that is looked up in the previous frame is the Motion texel's (where this surface point was one frame ago) instead of
-// P, and a texel of kind < 1 on a foreground pixel means "no history".  Everything else stays on the current frame.
-template <bool MOTION>
-__global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, TemporalArgs a) {
+template <class Src>
+__global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, TemporalArgs a, Src s) {
     const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
     const uint32_t W = a.W, H = a.H;
     if (px >= W || py >= H) return;
     const size_t pi = (size_t)py * W + px;
-    const float t = a.depth[pi];
+    const auto x = s.cur.fetch(pi);
     const float4 L = a.in[pi];
-    if (t == kBackgroundDepth) {
+    if (!s.cur.foreground(x)) {
         a.out[pi] = L;
         a.history[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         a.moments[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-    const uint4 w = a.gbuffer[pi];
-    V3 m, e;
-    dn_modulation(a.flags, w, m, e);
-    const V3 n = unpack_normal_11_10_11(w.y);
-    const V3 P = dn_position(g, px, py, t);
-    const V3 c = dn_demodulate(L, e, m);
+    const DnSurface p = s.cur.surface(g, a.flags, px, py, pi, x);
+    const V3 c = dn_demodulate(L, p.k);
     const float l = dn_lum(c.x, c.y, c.z);
 
-    V3 R = P;  // the point whose place in the previous frame is looked up
+    V3 R = p.P;  // the point whose place in the previous frame is looked up
     bool known = true;
-    if (MOTION) {
-        const float4 M = a.motion[pi];
-        R = v3(M.x, M.y, M.z);
-        known = !(M.w < 1.0f);
-    }
+    s.lookup(pi, R, known);
     // reproject R into the previous view
     const float vx = mat_row(prev.view, 0, R.x, R.y, R.z, 1.0f), vy = mat_row(prev.view, 1, R.x, R.y, R.z, 1.0f);
     const float vz = mat_row(prev.view, 2, R.x, R.y, R.z, 1.0f), vw = mat_row(prev.view, 3, R.x, R.y, R.z, 1.0f);
@@ -91,7 +103,7 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
             const float x0f = floorf(sx), y0f = floorf(sy);
             const float fx = sx - x0f, fy = sy - y0f;
             const int x0 = (int)x0f, y0 = (int)y0f;  // -1 .. W - 1, -1 .. H - 1
-            const V3 dE = P - v3(g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]);
+            const V3 dE = p.P - v3(g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]);
             const float tol = a.plane_tolerance * sqrtf(dot(dE, dE));
 #pragma unroll
             for (int j = 0; j < 2; j++) {
@@ -103,14 +115,14 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
                     const int tx = x0 + i;
                     if (tx < 0 || tx >= (int)W) continue;
                     const size_t qi = (size_t)ty * W + tx;
-                    const float td = a.prev_depth[qi];
-                    if (td == kBackgroundDepth) continue;
+                    const auto q = s.prev.fetch(qi);
+                    if (!s.prev.foreground(q)) continue;
                     const float4 ph = a.prev_history[qi];
                     if (!(ph.w > 0.0f)) continue;
-                    const V3 nq = unpack_normal_11_10_11(a.prev_gbuffer[qi * 4 + 1]);
-                    if (!(dot(n, nq) >= a.normal_cos)) continue;
-                    const V3 dP = dn_position(prev, (uint32_t)tx, (uint32_t)ty, td) - R;
-                    if (!(fabsf(dot(n, dP)) <= tol)) continue;
+                    const V3 nq = s.prev.unit_normal(qi, q);
+                    if (!(dot(p.n, nq) >= a.normal_cos)) continue;
+                    const V3 dP = s.prev.world_position(prev, (uint32_t)tx, (uint32_t)ty, q) - R;
+                    if (!(fabsf(dot(p.n, dP)) <= tol)) continue;
                     const float4 pm = a.prev_moments[qi];
                     const float wt = (i ? fx : 1.0f - fx) * wy;
                     ws = ws + wt;
@@ -143,127 +155,7 @@ __global__ __launch_bounds__(256) void k_temporal(GConstDev g, GConstDev prev, T
         mu2 = k2 + am * (mu2 - k2);
     }
     const float d = mu2 - mu1 * mu1;
-    const V3 r = dn_modulate(v3(cr, cg, cb), e, m);
-    a.history[pi] = make_float4(cr, cg, cb, N);
-    a.moments[pi] = make_float4(mu1, mu2, d > 0.0f ? d : 0.0f, N);
-    a.out[pi] = make_float4(r.x, r.y, r.z, L.w);
-}
-
-struct TemporalGuideArgs {  // k_temporal_guide: everything but the two cameras
-    uint32_t W, H, flags;
-    float alpha, alpha_moments, max_history, normal_cos, plane_tolerance;
-    const float4 *position, *normal, *albedo, *emission;  // this frame's guide images
-    const float4 *prev_position, *prev_normal;            // the previous frame's; its albedo and emission are not read
-    const float4* in;
-    const float4 *prev_history, *prev_moments;
-    float4 *out, *history, *moments;
-};
-
-// A guide texel is foreground iff every camera sample hit (position.w == 1) and the summed normal has a finite, positive squared length:
-// k_dn_prepare_guide's rule
-RT3_DEV bool guide_foreground(float cover, float l2) { return cover == 1.0f && l2 > 0.0f && l2 <= kFloatMax; }
-
-// "temporal" for lens and glass frames (rt3_temporal_set_guide_input): the surface record comes from the frame's own
-// guide images -- P = position.xyz, n = normal.xyz * (1 / sqrtf(l2)), m = max(albedo, 1/256), e = emission, unquantised, what the lens
-// frame shaded -- and a tap's from the previous frame's guide images: its position is read, not reconstructed through the previous
-// camera.  Reprojection, the four taps, the blend and the three writes are k_temporal<false>'s, operation for operation;
-// tests/ref_temporal_guide.py restates the kernel, and the pass equals it bit for bit.  Per tap the loads are ordered so that a rejected
-// tap costs the fewest bytes: coverage and normal (32 B), then history (16 B), then moments (16 B).  A foreground pixel reads 80 B of this
-// frame, gathers up to 4 x 64 B of the previous one and writes 48 B; every record is an aligned float4.
-__global__ __launch_bounds__(256) void k_temporal_guide(GConstDev g, GConstDev prev, TemporalGuideArgs a) {
-    const uint32_t px = blockIdx.x * kDnTileX + threadIdx.x, py = blockIdx.y * kDnTileY + threadIdx.y;
-    const uint32_t W = a.W, H = a.H;
-    if (px >= W || py >= H) return;
-    const size_t pi = (size_t)py * W + px;
-    const float4 GP = a.position[pi], GN = a.normal[pi];
-    const float4 L = a.in[pi];
-    const float l2 = dot(v3(GN.x, GN.y, GN.z), v3(GN.x, GN.y, GN.z));
-    if (!guide_foreground(GP.w, l2)) {
-        a.out[pi] = L;
-        a.history[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        a.moments[pi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        return;
-    }
-    const float inv_len = 1.0f / sqrtf(l2);
-    const V3 n = v3(GN.x * inv_len, GN.y * inv_len, GN.z * inv_len);
-    const V3 P = v3(GP.x, GP.y, GP.z);
-    V3 m = v3(1.0f, 1.0f, 1.0f), e = v3(0.0f, 0.0f, 0.0f);
-    if (!(a.flags & 1u)) {
-        const float4 al = a.albedo[pi], em = a.emission[pi];
-        m = v3(al.x > kDnAlbedoFloor ? al.x : kDnAlbedoFloor, al.y > kDnAlbedoFloor ? al.y : kDnAlbedoFloor, al.z > kDnAlbedoFloor ? al.z : kDnAlbedoFloor);
-        e = v3(em.x, em.y, em.z);
-    }
-    const V3 c = dn_demodulate(L, e, m);
-    const float l = dn_lum(c.x, c.y, c.z);
-
-    // reproject P into the previous view
-    const float vx = mat_row(prev.view, 0, P.x, P.y, P.z, 1.0f), vy = mat_row(prev.view, 1, P.x, P.y, P.z, 1.0f);
-    const float vz = mat_row(prev.view, 2, P.x, P.y, P.z, 1.0f), vw = mat_row(prev.view, 3, P.x, P.y, P.z, 1.0f);
-    const float qx = mat_row(prev.proj, 0, vx, vy, vz, vw), qy = mat_row(prev.proj, 1, vx, vy, vz, vw), qw = mat_row(prev.proj, 3, vx, vy, vz, vw);
-    float ws = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f, k1 = 0.0f, k2 = 0.0f;
-    if (qw > 0.0f) {
-        const float Wf = g.window_size[0], Hf = g.window_size[1];
-        const float ndx = qx / qw, ndy = qy / qw;
-        const float sx = (ndx * 0.5f + 0.5f) * Wf - 0.5f, sy = (-ndy * 0.5f + 0.5f) * Hf - 0.5f;
-        if (sx > -1.0f && sx < Wf && sy > -1.0f && sy < Hf) {
-            const float x0f = floorf(sx), y0f = floorf(sy);
-            const float fx = sx - x0f, fy = sy - y0f;
-            const int x0 = (int)x0f, y0 = (int)y0f;  // -1 .. W - 1, -1 .. H - 1
-            const V3 dE = P - v3(g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]);
-            const float tol = a.plane_tolerance * sqrtf(dot(dE, dE));
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int ty = y0 + j;
-                if (ty < 0 || ty >= (int)H) continue;
-                const float wy = j ? fy : 1.0f - fy;
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const int tx = x0 + i;
-                    if (tx < 0 || tx >= (int)W) continue;
-                    const size_t qi = (size_t)ty * W + tx;
-                    const float4 QP = a.prev_position[qi], QN = a.prev_normal[qi];
-                    const float q2 = dot(v3(QN.x, QN.y, QN.z), v3(QN.x, QN.y, QN.z));
-                    if (!guide_foreground(QP.w, q2)) continue;
-                    const float4 ph = a.prev_history[qi];
-                    if (!(ph.w > 0.0f)) continue;
-                    const float inv_q = 1.0f / sqrtf(q2);
-                    const V3 nq = v3(QN.x * inv_q, QN.y * inv_q, QN.z * inv_q);
-                    if (!(dot(n, nq) >= a.normal_cos)) continue;
-                    const V3 dP = v3(QP.x, QP.y, QP.z) - P;
-                    if (!(fabsf(dot(n, dP)) <= tol)) continue;
-                    const float4 pm = a.prev_moments[qi];
-                    const float wt = (i ? fx : 1.0f - fx) * wy;
-                    ws = ws + wt;
-                    hr = hr + wt * ph.x;
-                    hg = hg + wt * ph.y;
-                    hb = hb + wt * ph.z;
-                    hn = hn + wt * ph.w;
-                    k1 = k1 + wt * pm.x;
-                    k2 = k2 + wt * pm.y;
-                }
-            }
-        }
-    }
-    float N = 1.0f, cr = c.x, cg = c.y, cb = c.z, mu1 = l, mu2 = l * l;
-    if (ws > 0.0f) {
-        hr = hr / ws;
-        hg = hg / ws;
-        hb = hb / ws;
-        hn = hn / ws;
-        k1 = k1 / ws;
-        k2 = k2 / ws;
-        const float n1 = hn + 1.0f;
-        N = n1 < a.max_history ? n1 : a.max_history;
-        const float inv = 1.0f / N;
-        const float ac = a.alpha > inv ? a.alpha : inv, am = a.alpha_moments > inv ? a.alpha_moments : inv;
-        cr = hr + ac * (c.x - hr);
-        cg = hg + ac * (c.y - hg);
-        cb = hb + ac * (c.z - hb);
-        mu1 = k1 + am * (l - k1);
-        mu2 = k2 + am * (mu2 - k2);
-    }
-    const float d = mu2 - mu1 * mu1;
-    const V3 r = dn_modulate(v3(cr, cg, cb), e, m);
+    const V3 r = dn_modulate(v3(cr, cg, cb), p.k);
     a.history[pi] = make_float4(cr, cg, cb, N);
     a.moments[pi] = make_float4(mu1, mu2, d > 0.0f ? d : 0.0f, N);
     a.out[pi] = make_float4(r.x, r.y, r.z, L.w);
@@ -272,18 +164,16 @@ __global__ __launch_bounds__(256) void k_temporal_guide(GConstDev g, GConstDev p
 }  // namespace
 
 void launch_temporal(hipStream_t st, const TemporalLaunch& L) {
-    if (L.guide[0]) {  // rt3_temporal_set_guide_input: the G-buffer bindings and the motion image are not read
-        const TemporalGuideArgs ga = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance,
-                                      L.guide[0], L.guide[1], L.guide[2], L.guide[3], L.prev_guide[0], L.prev_guide[1], (const float4*)L.in,
-                                      (const float4*)L.prev_history, (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments};
-        hipLaunchKernelGGL(k_temporal_guide, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, ga);
-        return;
-    }
-    const TemporalArgs a = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance, (const uint4*)L.gbuffer,
-                            L.depth, (const float4*)L.in, (const uint32_t*)L.prev_gbuffer, L.prev_depth, (const float4*)L.prev_history,
-                            (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments, (const float4*)L.motion};
-    if (L.motion) hipLaunchKernelGGL(k_temporal<true>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a);
-    else hipLaunchKernelGGL(k_temporal<false>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a);
+    const TemporalArgs a = {L.W, L.H, L.flags, L.alpha, L.alpha_moments, L.max_history, L.normal_cos, L.plane_tolerance, (const float4*)L.in,
+                            (const float4*)L.prev_history, (const float4*)L.prev_moments, (float4*)L.out, (float4*)L.history, (float4*)L.moments};
+    const auto launch = [&](auto src) {
+        hipLaunchKernelGGL(k_temporal<decltype(src)>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a, src);
+    };
+    const DnGbuffer cur = {(const uint4*)L.gbuffer, L.depth}, prev = {(const uint4*)L.prev_gbuffer, L.prev_depth};
+    if (L.guide[0])  // rt3_temporal_set_guide_input: the G-buffer bindings and the motion image are not read
+        launch(TemporalGuide{{L.guide[0], L.guide[1], L.guide[2], L.guide[3]}, {L.prev_guide[0], L.prev_guide[1], L.prev_guide[2], L.prev_guide[3]}});
+    else if (L.motion) launch(TemporalGbuffer<true>{cur, prev, (const float4*)L.motion});
+    else launch(TemporalGbuffer<false>{cur, prev, nullptr});
 }
 
 }  // namespace rt3

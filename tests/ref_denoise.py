@@ -129,17 +129,24 @@ class _Taps:
 
 def denoise(g, gb, depth, light, iterations=5, normal_squarings=7, sigma_z=0.05, sigma_l=4.0, flags=0, stages=None):
     """Out (H, W, 4) float32 of the "denoise" pass.  `stages` (a dict) receives the intermediate images for debugging."""
+    return denoise_records(lambda light, demodulate: prepare(g, gb, depth, light, demodulate), light, None, iterations, normal_squarings, sigma_z,
+                           sigma_l, flags, stages)
+
+
+def denoise_records(prepare_fn, light, moments=None, iterations=5, normal_squarings=7, sigma_z=0.05, sigma_l=4.0, flags=0, stages=None):
+    """The pass over the records of `prepare_fn(light, demodulate)` (prepare()'s dict, from whichever source: the G-buffer here, the guide
+    images in ref_guide) and, with `moments`, the variance input (rt3_denoise_set_variance_input): the Moments image {mu1, mu2, variance,
+    N} of ref_temporal.temporal(), whose z replaces the result of the 7 x 7 stage per foreground pixel where w >= 4."""
     light = np.ascontiguousarray(light, F)
-    H, W = depth.shape
     if iterations == 0:
         return light.copy()
     with np.errstate(all="ignore"):
-        return _denoise(g, gb, depth, light, iterations, normal_squarings, F(sigma_z), F(sigma_l), flags, stages)
+        pr = prepare_fn(light, not (flags & NO_DEMODULATION))
+        return _denoise(pr, light, moments, iterations, normal_squarings, F(sigma_z), F(sigma_l), stages)
 
 
-def _denoise(g, gb, depth, light, iterations, squarings, sigma_z, sigma_l, flags, stages):
-    H, W = depth.shape
-    pr = prepare(g, gb, depth, light, demodulate=not (flags & NO_DEMODULATION))
+def _denoise(pr, light, moments, iterations, squarings, sigma_z, sigma_l, stages):
+    H, W = light.shape[:2]
     fg, c = pr["fg"], pr["c"]
     reach = max(3, 2 << (iterations - 1))
     T = _Taps(pr["P"], pr["n"], reach, squarings, F(1.0) / sigma_z)
@@ -158,6 +165,10 @@ def _denoise(g, gb, depth, light, iterations, squarings, sigma_z, sigma_l, flags
     mu1 = s1 / s0
     d = s2 / s0 - mu1 * mu1
     var = np.where(fg, np.where(d > F(0), d, F(0)), zero)
+    if stages is not None:
+        stages["var_spatial"] = var.copy()
+    if moments is not None:  # the temporal variance where the history is at least four frames long (SVGF's rule)
+        var = np.where(fg & (moments[..., 3] >= F(4)), moments[..., 2].astype(F), var)
     if stages is not None:
         stages["var0"] = var.copy()
     ones = T.pad(np.ones((H, W), F))

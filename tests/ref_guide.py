@@ -2,18 +2,15 @@
 
 accumulate() is k_lens_guide: per pixel the first-vertex features of the camera samples, summed in sample order, one rounding per written
 operation, no fused multiply-add; between batches the images hold the running sums with the hit count in position.w, so the result does
-not depend on how the samples are split.  prepare_guide() is k_dn_prepare_guide; denoise() runs stages 2 to 4 of tests/ref_denoise.py (in
-the form of tests/ref_temporal.py, which adds the variance input) with that prepare in the place of the G-buffer's for the duration of
-the call -- the variance stage, the a-trous iterations and the modulation are not restated here.  The GPU equals both bit for bit.
+not depend on how the samples are split.  prepare_guide() is k_dn_prepare<DnGuide>; denoise() hands it to
+ref_denoise.denoise_records, which runs stages 2 to 4 over whichever records it is given -- the variance stage (with the variance
+input), the a-trous iterations and the modulation are not restated here.  The GPU equals both bit for bit.
 """
 from __future__ import annotations
-
-import contextlib
 
 import numpy as np
 
 import ref_denoise as rd
-import ref_temporal as rt
 
 F = np.float32
 U = 2.0 ** -24
@@ -80,14 +77,19 @@ def foreground(guide):
     return fg, l2
 
 
+def unit_normal(guide, l2):
+    """normal.xyz * (1 / sqrt(l2)), the device header's normalize"""
+    with np.errstate(all="ignore"):
+        inv = F(1.0) / np.sqrt(l2)
+        return guide["normal"][..., :3] * inv[..., None]
+
+
 def prepare_guide(guide, light, demodulate=True):
-    """k_dn_prepare_guide: the records of ref_denoise.prepare from the guide images (H, W, 4).  n = normal.xyz * (1 / sqrt(l2)), the
-    device header's normalize."""
+    """k_dn_prepare<DnGuide>: the records of ref_denoise.prepare from the guide images (H, W, 4)"""
     H, W = light.shape[:2]
     fg, l2 = foreground(guide)
     with np.errstate(all="ignore"):
-        inv = F(1.0) / np.sqrt(l2)
-        n = guide["normal"][..., :3] * inv[..., None]
+        n = unit_normal(guide, l2)
         if demodulate:
             alb = guide["albedo"][..., :3]
             m = np.where(alb > rd.ALBEDO_FLOOR, alb, rd.ALBEDO_FLOOR)
@@ -101,25 +103,11 @@ def prepare_guide(guide, light, demodulate=True):
     return dict(P=np.where(f3, guide["position"][..., :3], z), n=np.where(f3, n, z).astype(F), c=np.where(f3, c, z).astype(F), m=m, e=e, fg=fg)
 
 
-@contextlib.contextmanager
-def _guided(guide):
-    """ref_denoise.prepare replaced by prepare_guide over `guide` (ref_temporal.denoise reaches it as rd.prepare)"""
-    kept = rd.prepare
-    rd.prepare = lambda g, gb, depth, light, demodulate=True: prepare_guide(guide, light, demodulate)
-    try:
-        yield
-    finally:
-        rd.prepare = kept
-
-
 def denoise(guide, light, moments=None, stages=None, **params):
     """Out (H, W, 4) float32 of "denoise" with the guide input set to `guide` ({position, normal, albedo, emission} -> (H, W, 4)) and,
     with `moments`, the variance input; `params` as ref_denoise.denoise's"""
-    light = np.ascontiguousarray(light, F)
     guide = {k: np.ascontiguousarray(guide[k], F) for k in KEYS}
-    H, W = light.shape[:2]
-    with _guided(guide):
-        return rt.denoise(None, None, np.zeros((H, W), F), light, moments=moments, stages=stages, **params)
+    return rd.denoise_records(lambda light, demodulate: prepare_guide(guide, light, demodulate), light, moments, stages=stages, **params)
 
 
 TAP_ROUNDINGS = 52  # a 5 x 5 weighted mean: 25 products and 24 sums above, 24 sums below, one division -- 74 operations, but a sum's error

@@ -3,7 +3,7 @@
 fused multiply-add.  The primary ray is the oracle's (orc.primary_rays); the hits {t, u, v, prim} come from the oracle's closest-hit
 traversal of the same instanced world (orc.Scene(mesh, instances=...).trace_closest), which tests/test_gpu_parity.py and
 tests/test_instances_two_level.py pin the GPU's hits to.  The surface record, the reprojection and the tap loop are those of
-ref_temporal / ref_denoise, which this module imports and does not edit.
+ref_temporal / ref_denoise (ref_temporal.accumulate, which takes the looked-up points R and the `known` mask from here).
 
 Texel kinds (Motion.w): 0 miss, 1 the hit instance did not move, 2 it moved.  "Moved" = the 12 stored floats of the instance's current
 matrix (its 3 x 4 part) differ from the previous ones in some 32-bit word.  An exact-identity previous matrix (all 16 words) leaves the
@@ -14,7 +14,6 @@ from __future__ import annotations
 import numpy as np
 
 import orc
-import ref_denoise as rd
 import ref_temporal as rt
 
 F = np.float32
@@ -110,77 +109,7 @@ def temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, pre
     kw = dict(alpha=alpha, alpha_moments=alpha_moments, max_history=max_history, normal_cos=normal_cos, plane_tolerance=plane_tolerance, flags=flags)
     if motion is None:
         return rt.temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, stages=stages, **kw)
-    light = np.ascontiguousarray(light, F)
-    with np.errstate(all="ignore"):
-        return _temporal(g, gb, depth, light, prev_g, prev_gb, np.asarray(prev_depth, F), np.asarray(prev_history, F), np.asarray(prev_moments, F),
-                         np.asarray(motion, F), F(alpha), F(alpha_moments), F(max_history), F(normal_cos), F(plane_tolerance), flags, stages)
-
-
-def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, motion, alpha, alpha_m, max_history, normal_cos,
-              plane_tol, flags, stages):
-    H, W = depth.shape
-    assert (prev_g.window_size[0], prev_g.window_size[1]) == (g.window_size[0], g.window_size[1]) == (W, H)
-    BG = F(orc.BACKGROUND_DEPTH)
-    pr = rd.prepare(g, gb, depth, light, demodulate=not (flags & rt.NO_DEMODULATION))
-    fg, P, n, c, m, e = pr["fg"], pr["P"], pr["n"], pr["c"], pr["m"], pr["e"]
-    l = rd._lum(c)
-    zero = np.zeros((H, W), F)
+    motion = np.asarray(motion, F)
     R = np.ascontiguousarray(motion[..., :3])  # where this surface point was one frame ago
     known = ~(motion[..., 3] < F(1.0))
-    valid, sx, sy = rt.reproject(g, prev_g, R)
-    valid = valid & fg & known
-    x0f, y0f = np.floor(sx), np.floor(sy)
-    fx, fy = sx - x0f, sy - y0f
-    x0 = np.where(valid, x0f, F(0)).astype(np.int32)
-    y0 = np.where(valid, y0f, F(0)).astype(np.int32)
-    eye = np.array([g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]], F)
-    dE = P - eye
-    tol = plane_tol * np.sqrt(rd._dot(dE, dE))
-    _, _, prev_n = rd.unpack_gbuffer(prev_gb)
-    prev_P = rt.positions(prev_g, prev_depth)
-    ws = zero.copy()
-    hs = np.zeros((H, W, 4), F)
-    ks = np.zeros((H, W, 2), F)
-    for j in (0, 1):
-        ty = y0 + j
-        wy = fy if j else F(1.0) - fy
-        for i in (0, 1):
-            tx = x0 + i
-            wx = fx if i else F(1.0) - fx
-            inside = valid & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-            cy, cx = np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)
-            ph, pm = prev_history[cy, cx], prev_moments[cy, cx]
-            dP = prev_P[cy, cx] - R
-            counts = (inside & (prev_depth[cy, cx] != BG) & (ph[..., 3] > F(0)) & (rd._dot(n, prev_n[cy, cx]) >= normal_cos)
-                      & (np.abs(rd._dot(n, dP)) <= tol))
-            wt = wx * wy
-            ws = ws + np.where(counts, wt, F(0))
-            hs = hs + np.where(counts[..., None], wt[..., None] * ph, F(0))
-            ks = ks + np.where(counts[..., None], wt[..., None] * pm[..., :2], F(0))
-    has = ws > F(0)
-    h = hs / ws[..., None]
-    k = ks / ws[..., None]
-    n1 = h[..., 3] + F(1.0)
-    N = np.where(n1 < max_history, n1, max_history)
-    inv = F(1.0) / N
-    ac = np.where(alpha > inv, alpha, inv)
-    am = np.where(alpha_m > inv, alpha_m, inv)
-    ll = l * l
-    c_hist = h[..., :3] + ac[..., None] * (c - h[..., :3])
-    mu1_hist = k[..., 0] + am * (l - k[..., 0])
-    mu2_hist = k[..., 1] + am * (ll - k[..., 1])
-    N = np.where(has, N, F(1.0)).astype(F)
-    c_acc = np.where(has[..., None], c_hist, c).astype(F)
-    mu1 = np.where(has, mu1_hist, l).astype(F)
-    mu2 = np.where(has, mu2_hist, ll).astype(F)
-    d = mu2 - mu1 * mu1
-    var = np.where(d > F(0), d, F(0))
-    rgb = e + c_acc * m
-    f3 = fg[..., None]
-    history = np.where(f3, np.concatenate([c_acc, N[..., None]], -1), F(0)).astype(F)
-    moments = np.where(f3, np.stack([mu1, mu2, var, N], -1), F(0)).astype(F)
-    out = light.copy()
-    out[..., :3] = np.where(f3, rgb, light[..., :3])
-    if stages is not None:
-        stages.update(valid=valid, sx=sx, sy=sy, ws=ws, has=has & fg, c=c, l=l, fg=fg)
-    return out, history, moments
+    return rt._temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, R, known, stages=stages, **kw)

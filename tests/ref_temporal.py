@@ -49,27 +49,51 @@ def reproject(g, prev_g, P):
     return valid, sx, sy
 
 
+def gbuffer_records(g, gb, depth):
+    """{fg, P, n} of a frame's G-buffer, as a tap reads them: foreground by the depth, the position through the frame's own camera"""
+    _, _, n = rd.unpack_gbuffer(gb)
+    return dict(fg=depth != F(orc.BACKGROUND_DEPTH), P=positions(g, depth), n=n)
+
+
 def temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, alpha=0.2, alpha_moments=0.2, max_history=32,
              normal_cos=0.9, plane_tolerance=0.01, flags=0, stages=None):
     """(Out, History, Moments), each (H, W, 4) float32, of the "temporal" pass.  `stages` (a dict) receives intermediates."""
+    return _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, None, None, alpha, alpha_moments, max_history,
+                     normal_cos, plane_tolerance, flags, stages)
+
+
+def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, R, known, alpha, alpha_moments, max_history, normal_cos,
+              plane_tolerance, flags, stages):
+    """the pass over the G-buffers of this frame and of the previous one; R, known: accumulate()'s (ref_motion.temporal sets them)"""
     light = np.ascontiguousarray(light, F)
     with np.errstate(all="ignore"):
-        return _temporal(g, gb, depth, light, prev_g, prev_gb, np.asarray(prev_depth, F), np.asarray(prev_history, F), np.asarray(prev_moments, F),
-                         F(alpha), F(alpha_moments), F(max_history), F(normal_cos), F(plane_tolerance), flags, stages)
+        cur = rd.prepare(g, gb, depth, light, demodulate=not (flags & NO_DEMODULATION))
+        prev = gbuffer_records(prev_g, prev_gb, np.asarray(prev_depth, F))
+        return accumulate(g, prev_g, light, cur, prev, prev_history, prev_moments, alpha, alpha_moments, max_history, normal_cos, plane_tolerance,
+                          stages, R, known)
 
 
-def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, prev_moments, alpha, alpha_m, max_history, normal_cos, plane_tol, flags,
-              stages):
-    H, W = depth.shape
+def accumulate(g, prev_g, light, cur, prev, prev_history, prev_moments, alpha, alpha_moments, max_history, normal_cos, plane_tolerance, stages=None,
+               R=None, known=None):
+    """Steps 3 to 5 of the pass -- reprojection, the four taps, the blend -- for whichever source the records come from.  `cur`: this
+    frame's record {fg, P, n, c, m, e} (ref_denoise.prepare's dict); `prev`: the previous frame's {fg, P, n}, which a tap reads.  `R` (H,
+    W, 3): the points that are looked up in the previous frame instead of P, and `known` (H, W) bool: whether a pixel has one (the motion
+    input); the tolerance, the normal and the record stay this frame's."""
+    prev_history, prev_moments = np.asarray(prev_history, F), np.asarray(prev_moments, F)
+    alpha, alpha_m, max_history, normal_cos, plane_tol = F(alpha), F(alpha_moments), F(max_history), F(normal_cos), F(plane_tolerance)
+    H, W = light.shape[:2]
     assert (prev_g.window_size[0], prev_g.window_size[1]) == (g.window_size[0], g.window_size[1]) == (W, H)
-    BG = F(orc.BACKGROUND_DEPTH)
-    pr = rd.prepare(g, gb, depth, light, demodulate=not (flags & NO_DEMODULATION))
-    fg, P, n, c, m, e = pr["fg"], pr["P"], pr["n"], pr["c"], pr["m"], pr["e"]
+    fg, P, n, c, m, e = cur["fg"], cur["P"], cur["n"], cur["c"], cur["m"], cur["e"]
+    prev_fg, prev_P, prev_n = prev["fg"], prev["P"], prev["n"]
     l = rd._lum(c)
     zero = np.zeros((H, W), F)
-    # reprojection
-    valid, sx, sy = reproject(g, prev_g, P)
+    # step 3: reprojection
+    if R is None:
+        R = P
+    valid, sx, sy = reproject(g, prev_g, R)
     valid = valid & fg
+    if known is not None:
+        valid = valid & known
     x0f, y0f = np.floor(sx), np.floor(sy)
     fx, fy = sx - x0f, sy - y0f
     x0 = np.where(valid, x0f, F(0)).astype(np.int32)
@@ -77,9 +101,7 @@ def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, pr
     eye = np.array([g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]], F)
     dE = P - eye
     tol = plane_tol * np.sqrt(rd._dot(dE, dE))
-    # the previous frame's records
-    _, _, prev_n = rd.unpack_gbuffer(prev_gb)
-    prev_P = positions(prev_g, prev_depth)
+    # step 4: the four taps, rows outer
     ws = zero.copy()
     hs = np.zeros((H, W, 4), F)
     ks = np.zeros((H, W, 2), F)
@@ -92,13 +114,14 @@ def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, pr
             inside = valid & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
             cy, cx = np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)
             ph, pm = prev_history[cy, cx], prev_moments[cy, cx]
-            dP = prev_P[cy, cx] - P
-            counts = (inside & (prev_depth[cy, cx] != BG) & (ph[..., 3] > F(0)) & (rd._dot(n, prev_n[cy, cx]) >= normal_cos)
+            dP = prev_P[cy, cx] - R
+            counts = (inside & prev_fg[cy, cx] & (ph[..., 3] > F(0)) & (rd._dot(n, prev_n[cy, cx]) >= normal_cos)
                       & (np.abs(rd._dot(n, dP)) <= tol))
             wt = wx * wy
             ws = ws + np.where(counts, wt, F(0))
             hs = hs + np.where(counts[..., None], wt[..., None] * ph, F(0))
             ks = ks + np.where(counts[..., None], wt[..., None] * pm[..., :2], F(0))
+    # step 5: the blend
     has = ws > F(0)
     h = hs / ws[..., None]
     k = ks / ws[..., None]
@@ -130,74 +153,7 @@ def _temporal(g, gb, depth, light, prev_g, prev_gb, prev_depth, prev_history, pr
 
 def denoise(g, gb, depth, light, moments=None, iterations=5, normal_squarings=7, sigma_z=0.05, sigma_l=4.0, flags=0, stages=None):
     """Out (H, W, 4) float32 of the "denoise" pass with the variance input (rt3_denoise_set_variance_input) set to `moments`, the Moments
-    image {mu1, mu2, variance, N} of temporal(): the result of the 7 x 7 stage is replaced per foreground pixel by Moments.z where
-    Moments.w >= 4.  The stages are those of ref_denoise.denoise, restated from its parts (prepare, the tap geometry, expn) line for line;
-    with `moments` None this is that function, bit for bit (tests/test_temporal_cpu.py holds the two together)."""
-    light = np.ascontiguousarray(light, F)
-    if iterations == 0:
-        return light.copy()
-    with np.errstate(all="ignore"):
-        return _denoise(g, gb, depth, light, moments, iterations, normal_squarings, F(sigma_z), F(sigma_l), flags, stages)
-
-
-def _denoise(g, gb, depth, light, moments, iterations, squarings, sigma_z, sigma_l, flags, stages):
-    H, W = depth.shape
-    pr = rd.prepare(g, gb, depth, light, demodulate=not (flags & rd.NO_DEMODULATION))
-    fg, c = pr["fg"], pr["c"]
-    reach = max(3, 2 << (iterations - 1))
-    T = rd._Taps(pr["P"], pr["n"], reach, squarings, F(1.0) / sigma_z)
-    zero = np.zeros((H, W), F)
-    # stage 2: spatial variance of the luminance over 7 x 7, weighted by w_n * w_z
-    lp = T.pad(rd._lum(c))
-    s0, s1, s2 = zero.copy(), zero.copy(), zero.copy()
-    for dy in range(-3, 4):
-        for dx in range(-3, 4):
-            wn, xz = T.geo(dy, dx)
-            w = wn * rd.expn(xz)
-            lq = T.at(lp, dy, dx)
-            s0 = s0 + w
-            s1 = s1 + w * lq
-            s2 = s2 + w * (lq * lq)
-    mu1 = s1 / s0
-    d = s2 / s0 - mu1 * mu1
-    var = np.where(fg, np.where(d > F(0), d, F(0)), zero)
-    if stages is not None:
-        stages["var_spatial"] = var.copy()
-    if moments is not None:  # the temporal variance where the history is at least four frames long (SVGF's rule)
-        var = np.where(fg & (moments[..., 3] >= F(4)), moments[..., 2].astype(F), var)
-    if stages is not None:
-        stages["var0"] = var.copy()
-    ones = T.pad(np.ones((H, W), F))
-    # stage 3: a-trous iterations
-    for it in range(iterations):
-        st = 1 << it
-        vp, cp = T.pad(var), T.pad(c)
-        gs, ks = zero.copy(), zero.copy()
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                k = rd.K3[dy + 1] * rd.K3[dx + 1]
-                gs = gs + k * T.at(vp, dy, dx)
-                ks = ks + k * T.at(ones, dy, dx)
-        gv = gs / ks
-        inv_l = F(1.0) / (sigma_l * np.sqrt(gv) + rd.TINY_L)
-        l = rd._lum(c)
-        lp = T.pad(l)
-        acc = np.zeros((H, W, 3), F)
-        ws, vs = zero.copy(), zero.copy()
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                h = rd.H5[dy + 2] * rd.H5[dx + 2]
-                wn, xz = T.geo(dy * st, dx * st)
-                xl = np.abs(T.at(lp, dy * st, dx * st) - l) * inv_l
-                w = (h * wn) * rd.expn(xz + xl)
-                cq = T.at(cp, dy * st, dx * st)
-                acc = acc + w[..., None] * cq
-                ws = ws + w
-                vs = vs + (w * w) * T.at(vp, dy * st, dx * st)
-        c = np.where(fg[..., None], acc / ws[..., None], np.zeros((H, W, 3), F))
-        var = np.where(fg, vs / (ws * ws), zero)
-    # stage 4
-    out = light.copy()
-    rgb = pr["e"] + c * pr["m"]
-    out[..., :3] = np.where(fg[..., None], rgb, light[..., :3])
-    return out
+    image {mu1, mu2, variance, N} of temporal(): ref_denoise.denoise_records over the G-buffer's records.  With `moments` None this is
+    ref_denoise.denoise, bit for bit (tests/test_temporal_cpu.py holds the two together)."""
+    return rd.denoise_records(lambda light, demodulate: rd.prepare(g, gb, depth, light, demodulate), light, moments, iterations, normal_squarings,
+                              sigma_z, sigma_l, flags, stages)

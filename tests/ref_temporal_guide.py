@@ -1,13 +1,13 @@
-"""numpy float32 restatement of the "temporal" pass guided by the camera samples (k_temporal_guide): reprojected
+"""numpy float32 restatement of the "temporal" pass guided by the camera samples (k_temporal<TemporalGuide>): reprojected
 accumulation whose surface records come from the guide images of this frame and of the previous one instead of the pinhole G-buffer.
 The GPU pass must equal `temporal()` bit for bit, so every line below is ONE rounded device operation on float32 arrays, in the device's
 order: `+ - * /` and `sqrt` only, min / max as selects, no fused multiply-add.
 
-What is shared is imported, not restated: the foreground rule and the normalisation are ref_guide's (foreground, prepare_guide -- the
-records of k_dn_prepare_guide), the matrix rows and the reprojection are ref_temporal's (_mat_row, reproject).  Steps 4 and 5 -- the four
-taps, rows outer, and the blend -- follow ref_temporal._temporal line for line; what differs is where a tap's record comes from: the
-previous guide is foreground at the tap by the same rule, its normal is normalised the same way, and its position is read, not
-reconstructed through the previous camera.  A tap that does not count adds +0.  previous.albedo and previous.emission are not read.
+What is shared is imported, not restated: the foreground rule, the normalisation and this frame's record are ref_guide's (foreground,
+unit_normal, prepare_guide -- the records of k_dn_prepare<DnGuide>); the reprojection, the four taps and the blend are
+ref_temporal.accumulate, the same lines that serve the G-buffer.  What differs is where a tap's record comes from: the previous guide is
+foreground at the tap by the same rule, its normal is normalised the same way, and its position is read, not reconstructed through the
+previous camera.  previous.albedo and previous.emission are not read.
 
 denoise() is the guided "denoise" of ref_guide with the variance input: what follows a guided "temporal" in a frame.
 """
@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import numpy as np
 
-import ref_denoise as rd
 import ref_guide as rgd
 import ref_temporal as rt
 
@@ -35,82 +34,17 @@ def temporal(g, guide, light, prev_g, prev_guide, prev_history, prev_moments, al
     {position, normal, albedo, emission} -> (H, W, 4) (`prev_guide` needs position and normal only).  `g`, `prev_g`: the GConst of this
     frame and of the previous one (view, proj, view_inverse, window_size are read).  `stages` (a dict) receives intermediates."""
     light = np.ascontiguousarray(light, F)
+    guide, prev_guide = _images(guide), _images(prev_guide, ("position", "normal"))
     with np.errstate(all="ignore"):
-        return _temporal(g, _images(guide), light, prev_g, _images(prev_guide, ("position", "normal")), np.asarray(prev_history, F),
-                         np.asarray(prev_moments, F), F(alpha), F(alpha_moments), F(max_history), F(normal_cos), F(plane_tolerance), flags, stages)
-
-
-def _temporal(g, guide, light, prev_g, prev_guide, prev_history, prev_moments, alpha, alpha_m, max_history, normal_cos, plane_tol, flags, stages):
-    H, W = light.shape[:2]
-    assert (prev_g.window_size[0], prev_g.window_size[1]) == (g.window_size[0], g.window_size[1]) == (W, H)
-    # steps 1 and 2: the record of k_dn_prepare_guide (P, n, c are zero off the foreground)
-    pr = rgd.prepare_guide(guide, light, demodulate=not (flags & NO_DEMODULATION))
-    fg, P, n, c, m, e = pr["fg"], pr["P"], pr["n"], pr["c"], pr["m"], pr["e"]
-    l = rd._lum(c)
-    zero = np.zeros((H, W), F)
-    # step 3: reprojection
-    valid, sx, sy = rt.reproject(g, prev_g, P)
-    valid = valid & fg
-    x0f, y0f = np.floor(sx), np.floor(sy)
-    fx, fy = sx - x0f, sy - y0f
-    x0 = np.where(valid, x0f, F(0)).astype(np.int32)
-    y0 = np.where(valid, y0f, F(0)).astype(np.int32)
-    eye = np.array([g.view_inverse[12], g.view_inverse[13], g.view_inverse[14]], F)
-    dE = P - eye
-    tol = plane_tol * np.sqrt(rd._dot(dE, dE))
-    # the previous frame's records
-    prev_fg, prev_l2 = rgd.foreground(prev_guide)
-    prev_inv = F(1.0) / np.sqrt(prev_l2)
-    prev_n = prev_guide["normal"][..., :3] * prev_inv[..., None]
-    prev_P = prev_guide["position"][..., :3]
-    # step 4
-    ws = zero.copy()
-    hs = np.zeros((H, W, 4), F)
-    ks = np.zeros((H, W, 2), F)
-    for j in (0, 1):
-        ty = y0 + j
-        wy = fy if j else F(1.0) - fy
-        for i in (0, 1):
-            tx = x0 + i
-            wx = fx if i else F(1.0) - fx
-            inside = valid & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-            cy, cx = np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)
-            ph, pm = prev_history[cy, cx], prev_moments[cy, cx]
-            dP = prev_P[cy, cx] - P
-            counts = (inside & prev_fg[cy, cx] & (ph[..., 3] > F(0)) & (rd._dot(n, prev_n[cy, cx]) >= normal_cos)
-                      & (np.abs(rd._dot(n, dP)) <= tol))
-            wt = wx * wy
-            ws = ws + np.where(counts, wt, F(0))
-            hs = hs + np.where(counts[..., None], wt[..., None] * ph, F(0))
-            ks = ks + np.where(counts[..., None], wt[..., None] * pm[..., :2], F(0))
-    # step 5
-    has = ws > F(0)
-    h = hs / ws[..., None]
-    k = ks / ws[..., None]
-    n1 = h[..., 3] + F(1.0)
-    N = np.where(n1 < max_history, n1, max_history)
-    inv = F(1.0) / N
-    ac = np.where(alpha > inv, alpha, inv)
-    am = np.where(alpha_m > inv, alpha_m, inv)
-    ll = l * l
-    c_hist = h[..., :3] + ac[..., None] * (c - h[..., :3])
-    mu1_hist = k[..., 0] + am * (l - k[..., 0])
-    mu2_hist = k[..., 1] + am * (ll - k[..., 1])
-    N = np.where(has, N, F(1.0)).astype(F)
-    c_acc = np.where(has[..., None], c_hist, c).astype(F)
-    mu1 = np.where(has, mu1_hist, l).astype(F)
-    mu2 = np.where(has, mu2_hist, ll).astype(F)
-    d = mu2 - mu1 * mu1
-    var = np.where(d > F(0), d, F(0))
-    rgb = e + c_acc * m
-    f3 = fg[..., None]
-    history = np.where(f3, np.concatenate([c_acc, N[..., None]], -1), F(0)).astype(F)
-    moments = np.where(f3, np.stack([mu1, mu2, var, N], -1), F(0)).astype(F)
-    out = light.copy()
-    out[..., :3] = np.where(f3, rgb, light[..., :3])
+        # steps 1 and 2: this frame's record is prepare_guide's (P, n, c are zero off the foreground); a tap's comes from the previous guide
+        cur = rgd.prepare_guide(guide, light, demodulate=not (flags & NO_DEMODULATION))
+        prev_fg, prev_l2 = rgd.foreground(prev_guide)
+        prev = dict(fg=prev_fg, P=prev_guide["position"][..., :3], n=rgd.unit_normal(prev_guide, prev_l2))
+        out = rt.accumulate(g, prev_g, light, cur, prev, prev_history, prev_moments, alpha, alpha_moments, max_history, normal_cos, plane_tolerance,
+                            stages)
     if stages is not None:
-        stages.update(valid=valid, sx=sx, sy=sy, ws=ws, has=has & fg, c=c, l=l, fg=fg, prev_fg=prev_fg)
-    return out, history, moments
+        stages["prev_fg"] = prev_fg
+    return out
 
 
 def denoise(guide, light, moments=None, **params):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Instruction statistics of the traversal kernels from `hipcc -S --cuda-device-only` output (usage: isa_stats.py file.s), or of the kernels
-whose mangled names contain one of the given words (usage: isa_stats.py file.s k_motion k_temporal)."""
+whose mangled names contain one of the given words (usage: isa_stats.py file.s k_motion k_temporal).  A template's instances share the
+kernel's name: k_temporal lists all three sources, TemporalGuide or k_dn_prepareINS_7DnGuide one of them."""
 import re
 import sys
 

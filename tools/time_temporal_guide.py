@@ -4,8 +4,8 @@ through the per-sample pinhole a scene with glass switches on, default flags + R
 of tests/test_temporal_cpu.py's moving Cornell row (about 2 pixels a frame).
 
 1. HIP-event time of the pass alone (RT3_OPT_PROFILE brackets its launch) at --size: median of --repeats launches after --warmup, of the
-   guided launch (k_temporal_guide: rt3_temporal_set_guide_input) and of the G-buffer launch (k_temporal<false>, the kernel every earlier
-   tree has: tools/isa_diff.py shows it unchanged) on the same frame, the same bindings and the same history; once reprojecting the
+   guided launch (k_temporal<TemporalGuide>: rt3_temporal_set_guide_input) and of the G-buffer launch (k_temporal<TemporalGbuffer<false>>,
+   the same kernel body over the other source of records) on the same frame, the same bindings and the same history; once reprojecting the
    previous frame under the camera move and once with zeroed history (no tap counts: the gathers stop at PrevHistory.w).  Per foreground
    pixel the guided launch reads 80 B of this frame and gathers up to 4 x 64 B where the G-buffer launch reads 36 B and gathers 4 x 52 B;
    both write 48 B.
