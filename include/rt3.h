@@ -793,9 +793,38 @@ int rt3_denoise_set_guide_input(rt3_ctx *ctx, const rt3_guide_images *images);  
  *      The eight images are checked at each "temporal" launch, before anything is enqueued: live RGBA32F images of the window's size,
  *      pairwise different, none of them Out, History or Moments, else RT3_E_INVALID.  A guide input together with a motion input
  *      (rt3_temporal_set_motion_input != 0) returns RT3_E_STATE: the "motion" image is made from pinhole primary hits and does not describe
- *      the samples, so moved instances and deformed meshes are caught only as far as the plane test catches them.  The refusal under a
+ *      the samples; moved instances and deformed meshes take rt3_temporal_set_guide_motion_input, below.  The refusal under a
  *      tile partition of several ranks stays.  Equal to tests/ref_temporal_guide.py bit for bit. ---- */
 int rt3_temporal_set_guide_input(rt3_ctx *ctx, const rt3_guide_images *current, const rt3_guide_images *previous);  /* NULL, NULL: the G-buffer */
+/* ---- motion under a lens: the samples' mean previous position.  No reference counterpart; DESIGN.md section 4w.
+ *      rt3_camera_set_guide_motion_output names a fifth guide image, one RGBA32F image of the window's size; rt3_guide_images keeps its
+ *      layout.  While it, a lens and the four-image guide output are all set, "refrence_mode" also writes it: per listed pixel, over the
+ *      S camera samples in ascending order, in fp32 with one rounding per operation and no contraction, a sample that escaped adds
+ *      nothing, and a sample that hit prim at (t, bu, bv) adds 1 to n_hit and R to sum_R, R chosen by the hit geometry like the "motion"
+ *      pass's texel (above):
+ *        the instance did not move and the geometry is not deformed:  R = o + d t, the addend of the guide's sum_P, bit for bit
+ *        the instance moved:      R = prev_i * ((a w + b u) + c v), w = (1 - u) - v, over the triangle's object-space corners (the point
+ *                                 itself when prev_i is exactly the identity); rt3_scene_set_prev_transforms gives prev_i
+ *        the geometry is deformed: the same expression over the three records of the snapshot (rt3_scene_snapshot_vertices); prev_i = the
+ *                                 current matrix when there are no previous transforms
+ *      Written: {sum_R / n_hit, n_hit / S}, all zero when n_hit = 0; between batches the image holds {sum_R, n_hit}, so the bits do not
+ *      depend on RT3_OPT_BATCH_SPP, RT3_OPT_INSTANCE_MODE or the tile partition.  With nothing moved and nothing deformed the image is
+ *      the guide's position image bit for bit.  Light and the four guide images keep their bits.  0 switches it off, the default.
+ *      RT3_E_INVALID at set time (nothing changed) for a handle that is not a live RGBA32F image.  At a "refrence_mode" launch, before
+ *      anything is enqueued: RT3_E_STATE when no four-image guide output is set, or when the number of previous transforms is neither 0 nor
+ *      the built structure's instance count; RT3_E_INVALID when the image has not the window's size or is one of the four guide images,
+ *      Light or PrevLight.  rt3_camera_get_guide_motion_output: the handle last set (0 before any).
+ *      rt3_temporal_set_guide_motion_input gives "temporal" that image, beside the two guide sets: the point projected into the previous
+ *      view, and P in the plane test's P_q - P, is image.xyz instead of position.xyz; the tolerance |P - eye|, the normal and the record
+ *      stay this frame's.  A foreground pixel has n_hit = S, so the point always exists.  0 (the default) = none, and an image made with
+ *      nothing moved gives the bits of no input.  At a "temporal" launch: RT3_E_STATE without a guide input; RT3_E_INVALID when the image is
+ *      not a live RGBA32F image of the window's size, or is one of the eight guide images, Out, History or Moments.  The refusal of a guide
+ *      input together with the pinhole rt3_temporal_set_motion_input stays.  Out of scope: previous normals (a surface that turns more than
+ *      acos(normal_cos) per frame loses its history), partly covered pixels, and what is seen through glass.  Equal to
+ *      tests/ref_guide_motion.py bit for bit. ---- */
+int rt3_camera_set_guide_motion_output(rt3_ctx *ctx, uint32_t image);   /* 0: off, the default */
+int rt3_camera_get_guide_motion_output(rt3_ctx *ctx, uint32_t *image);
+int rt3_temporal_set_guide_motion_input(rt3_ctx *ctx, uint32_t image);  /* 0: none, the default */
 /* ---- Russian roulette on extension rays.  No reference counterpart; DESIGN.md section 4o.  By default every path that still has an extension
  *      ray is traced and shaded for all GConst.bounces vertices.  With roulette set, "refrence_mode" and "adaptive" test the extension ray that
  *      a path emitted at vertex b, for start_bounce <= b < bounces - 1, between the shading of vertex b and the trace that follows, in a
@@ -908,6 +937,10 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      that is not the call's n, a power that is negative or not finite, a k >= 2^23, or n_k > 0 when every power is 0 (total = 0: nothing
  *      may be looked up).  Every output array is made one element longer and filled with a pattern: RT3_E_STATE when a word behind an
  *      end, or a record word other than w, changed.
+ *      41 k_lens_guide_prev itself (rt3_camera_set_guide_motion_output) on caller-made queues over the built scene and the context's current
+ *      motion tables (rt3_scene_set_prev_transforms, rt3_scene_snapshot_vertices; RT3_E_STATE for a wrong transform count).  The header,
+ *      pixel words, records, checks and guards are op 39's.  out: 4 words per listed pixel; the words the caller put there are the image's
+ *      contents before the launch.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

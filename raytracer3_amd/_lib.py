@@ -42,6 +42,7 @@ SELFTEST_ABSORB = 36  # rt3_selftest_eval op: {T rgb, sigma rgb, t, d xyz, n xyz
 SELFTEST_ABSORB_QUEUE = 37  # rt3_selftest_eval op: k_absorb on a caller-made queue over the built scene (Context.selftest_absorb_queue)
 SELFTEST_FROST = 38  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, alpha, u_event, u2, u3} (12 words) -> {event (u32: 0 reflect, 1 transmit, 2 invalid), direction, F, weight} (6), the frosted vertex rule
 SELFTEST_GUIDE_QUEUE = 39  # rt3_selftest_eval op: k_lens_guide on caller-made camera and hit queues over the built scene (Context.selftest_guide_queue)
+SELFTEST_GUIDE_PREV_QUEUE = 41  # rt3_selftest_eval op: k_lens_guide_prev on caller-made camera and hit queues over the built scene and the current motion tables (Context.selftest_guide_prev_queue)
 SELFTEST_LIGHT_TABLE = 40  # rt3_selftest_eval op: the light table's quantise / scan / CDF / guide kernels and light_find on caller-made powers (Context.selftest_light_table)
 
 EXPORTS = [
@@ -63,6 +64,7 @@ EXPORTS = [
     "rt3_adaptive_set_params", "rt3_adaptive_info", "rt3_adaptive_set_coverage", "rt3_adaptive_get_coverage",
     "rt3_camera_set_lens", "rt3_camera_get_lens",
     "rt3_camera_set_guide_output", "rt3_camera_get_guide_output", "rt3_denoise_set_guide_input", "rt3_temporal_set_guide_input",
+    "rt3_camera_set_guide_motion_output", "rt3_camera_get_guide_motion_output", "rt3_temporal_set_guide_motion_input",
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses", "rt3_light_table",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
@@ -267,6 +269,9 @@ def load():
         "rt3_camera_get_guide_output": (i32, [vp, C.POINTER(GuideImages), C.POINTER(i32)]),
         "rt3_denoise_set_guide_input": (i32, [vp, C.POINTER(GuideImages)]),
         "rt3_temporal_set_guide_input": (i32, [vp, C.POINTER(GuideImages), C.POINTER(GuideImages)]),
+        "rt3_camera_set_guide_motion_output": (i32, [vp, u32]),
+        "rt3_camera_get_guide_motion_output": (i32, [vp, C.POINTER(u32)]),
+        "rt3_temporal_set_guide_motion_input": (i32, [vp, u32]),
         "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),
         "rt3_path_get_roulette": (i32, [vp, C.POINTER(RouletteParams), C.POINTER(i32)]),
         "rt3_path_roulette_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -532,8 +532,13 @@ static int selftest_absorb_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uin
 // first, last, workgroups}, npix pixel words, then n = nsb npix records {o xyz, d xyz, t, bu, bv, prim}.  out: per listed pixel the 16 words
 // {position, normal, albedo, emission}; the caller's words are the images' contents before the launch.  Queues and images are one record
 // longer than needed and carry a pattern wherever the kernel has nothing to write: a kernel that wrote out of place fails the call.
-static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+// Self-test op 41 (`prev`): k_lens_guide_prev on the same header, records and guards, over the context's current motion tables
+// (motion_tables: its refusals); out: per listed pixel the 4 words of its one image.
+static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out, bool prev) {
     if (int r = check_accel_current(c)) return r;
+    const int n_img = prev ? 1 : 4;
+    const uint32_t out_words = prev ? kSelftestGuidePrevOut : kSelftestGuideOut;
+    const char* kernel = prev ? "k_lens_guide_prev" : "k_lens_guide";
     const uint32_t npix = in[0], nsb = in[1], S_total = in[2], first = in[3], last = in[4], groups = in[5];
     if (npix == 0 || npix > (1u << 24) || nsb == 0 || (uint64_t)nsb * npix != n || n > (1u << 24) || S_total == 0 || S_total > (1u << 24) || first > 1 ||
         last > 1 || groups == 0 || groups > 65535)
@@ -572,10 +577,10 @@ static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint
         memcpy(&hits[4 * i], r + 6, 16);
     }
     std::vector<uint32_t> img[4];
-    for (int k = 0; k < 4; k++) img[k].assign(4 * (win + 1), kGuard);
+    for (int k = 0; k < n_img; k++) img[k].assign(4 * (win + 1), kGuard);
     for (uint32_t i = 0; i < npix; i++) {
         const size_t pi = (size_t)(pix[i] >> 16) * W + (pix[i] & 0xFFFFu);
-        for (int k = 0; k < 4; k++) memcpy(&img[k][4 * pi], out + kSelftestGuideOut * (size_t)i + 4 * k, 16);
+        for (int k = 0; k < n_img; k++) memcpy(&img[k][4 * pi], out + out_words * (size_t)i + 4 * k, 16);
     }
     DevBuf<float> d_rays, d_hits;
     DevBuf<uint32_t> d_pix;
@@ -586,31 +591,39 @@ static int selftest_guide_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint
     HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(d_hits.get(), hits.data(), 4 * S * 4, hipMemcpyHostToDevice));
     HIPC(c, hipMemcpy(d_pix.get(), pix, (size_t)npix * 4, hipMemcpyHostToDevice));
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < n_img; k++) {
         HIPC(c, d_img[k].alloc_bytes((win + 1) * 16));
         HIPC(c, hipMemcpy(d_img[k].get(), img[k].data(), (win + 1) * 16, hipMemcpyHostToDevice));
     }
     GuideLaunch G{};
     G.sc = scene_dev(c); G.pixels = d_pix.get(); G.npix = npix; G.width = W; G.rays = d_rays.get(); G.hits = d_hits.get(); G.stride = S;
     G.nsb = nsb; G.samples = S_total; G.first_batch = first != 0; G.last_batch = last != 0;
-    for (int k = 0; k < 4; k++) G.img[k] = d_img[k].get();
-    launch_lens_guide(c->stream, G, groups);
+    for (int k = 0; k < n_img; k++) G.img[k] = d_img[k].get();
+    if (prev) {
+        GuidePrevLaunch P{};
+        if (int r = motion_launch_tables(c, &P.m, &P.prev_pos)) return r;
+        P.pixels = G.pixels; P.npix = npix; P.width = W; P.rays = G.rays; P.hits = G.hits; P.stride = S;
+        P.nsb = nsb; P.samples = S_total; P.first_batch = G.first_batch; P.last_batch = G.last_batch; P.out = d_img[0].get();
+        launch_lens_guide_prev(c->stream, P, groups);
+    } else {
+        launch_lens_guide(c->stream, G, groups);
+    }
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(c->stream));
     std::vector<uint32_t> rays2(8 * S), hits2(4 * S);
     HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
     HIPC(c, hipMemcpy(hits2.data(), d_hits.get(), 4 * S * 4, hipMemcpyDeviceToHost));
-    if (rays2 != rays || hits2 != hits) return fail(c, RT3_E_STATE, "selftest: k_lens_guide wrote a ray or hit record");
-    for (int k = 0; k < 4; k++) {
+    if (rays2 != rays || hits2 != hits) return fail(c, RT3_E_STATE, std::string("selftest: ") + kernel + " wrote a ray or hit record");
+    for (int k = 0; k < n_img; k++) {
         HIPC(c, hipMemcpy(img[k].data(), d_img[k].get(), (win + 1) * 16, hipMemcpyDeviceToHost));
         for (size_t pi = 0; pi <= win; pi++)
             if (pi == win || !listed[pi])
                 for (int w = 0; w < 4; w++)
-                    if (img[k][4 * pi + w] != kGuard) return fail(c, RT3_E_STATE, "selftest: k_lens_guide wrote a pixel that is not listed, or behind an image's end");
+                    if (img[k][4 * pi + w] != kGuard) return fail(c, RT3_E_STATE, std::string("selftest: ") + kernel + " wrote a pixel that is not listed, or behind an image's end");
     }
     for (uint32_t i = 0; i < npix; i++) {
         const size_t pi = (size_t)(pix[i] >> 16) * W + (pix[i] & 0xFFFFu);
-        for (int k = 0; k < 4; k++) memcpy(out + kSelftestGuideOut * (size_t)i + 4 * k, &img[k][4 * pi], 16);
+        for (int k = 0; k < n_img; k++) memcpy(out + out_words * (size_t)i + 4 * k, &img[k][4 * pi], 16);
     }
     return RT3_OK;
 }
@@ -644,7 +657,7 @@ static int selftest_light_table(rt3_ctx* c, const uint32_t* in, uint32_t n, uint
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
     if (op == 40 && c && in && out) return selftest_light_table(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
-    if (op == 39 && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
+    if ((op == 39 || op == 41) && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out), op == 41);
     if (op == 37 && c && in && out) return selftest_absorb_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 35 && c && in && out) return selftest_adaptive_compact(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 34 && c && in && out) return selftest_roulette_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));  // no rows of one width

@@ -42,6 +42,20 @@ __device__ __forceinline__ void fetch_triangle_object(const float* verts, const 
     b = v3(v1[0], v1[1], v1[2]);
     c = v3(v2[0], v2[1], v2[2]);
 }
+// fetch_triangle_object's index arithmetic over the snapshot's 16-byte records (rt3_scene_snapshot_vertices): the triangle one frame ago
+// (rt3_motion.hip, rt3_guide.hip)
+__device__ __forceinline__ void fetch_triangle_snapshot(const float4* prev_pos, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
+                                                        const uint32_t* first_prim, uint32_t prim, V3& a, V3& b, V3& c) {
+    uint32_t g = prim_geom[prim];
+    const FlatGeomDev& fg = geoms[g];
+    uint32_t io = fg.g.index_offset + 3u * (prim - first_prim[g]);
+    const float4 v0 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io])];
+    const float4 v1 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io + 1])];
+    const float4 v2 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io + 2])];
+    a = v3(v0.x, v0.y, v0.z);
+    b = v3(v1.x, v1.y, v1.z);
+    c = v3(v2.x, v2.y, v2.z);
+}
 // conservative leaf padding from the scene bounds (ordered-uint encoded min.xyz, max.xyz): a share of the extent, and at least 2^-20
 // of the largest coordinate magnitude ("Leaf padding")
 __device__ __forceinline__ float leaf_pad(const uint32_t* bounds) {

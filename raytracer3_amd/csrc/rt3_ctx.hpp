@@ -300,6 +300,9 @@ struct rt3_ctx {
         // records from; off by default, checked at every launch
         rt3_guide_images temporal_cur = {0u, 0u, 0u, 0u}, temporal_prev = {0u, 0u, 0u, 0u};
         bool temporal_on = false;
+        // the fifth image "refrence_mode" writes beside the four (rt3_camera_set_guide_motion_output), the samples'
+        // mean previous position, and the one "temporal" looks up (rt3_temporal_set_guide_motion_input); 0 = off, checked at every launch
+        uint32_t motion_out = 0, temporal_motion = 0;
     } guide;
     // rt3_passes.hip: Russian roulette on extension rays (rt3_path_set_roulette): off by default
     struct Roulette {
@@ -442,6 +445,9 @@ void exit_counters_reset(rt3_ctx* c);
 
 // ---- rt3_passes.hip
 void motion_tables_stale(rt3_ctx* c);  // the previous transforms or the deformed flags changed: motion_tables remakes its tables
+// motion_tables for the built structure (its refusals; it may synchronise the stream), then the tables as a kernel follows them: geom_slot
+// null when nothing moved, *prev_pos null when nothing is deformed
+int motion_launch_tables(rt3_ctx* c, MotionDev* m, const float4** prev_pos);
 
 // ---- rt3_tiles.hip
 int get_pixlist(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks, PixelList** out);

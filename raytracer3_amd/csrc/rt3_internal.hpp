@@ -147,7 +147,7 @@ void launch_postprocess_lens(hipStream_t st, const uint32_t* pixels, uint32_t np
 // (record = sample_in_batch * npix + pixel index, `stride` records per plane), both read-only, for samples of one batch; img = {position,
 // normal, albedo, emission}, window-space float4 images of row length `width`.  first_batch: the sums start at 0; last_batch: the sums
 // become means over `samples`, the frame's sample count.  The grid covers npix, or is `groups` workgroups when that is not 0 (self-test
-// op 39)
+// op 39).  GuidePrevLaunch, below the "motion" pass's tables, describes k_lens_guide_prev's launch over the same queues
 struct GuideLaunch {
     SceneDev sc;
     const uint32_t* pixels;
@@ -569,6 +569,9 @@ struct TemporalLaunch {
     // motion are not read, nor are prev_guide[2] and [3]
     const float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
     const float4* prev_guide[4] = {nullptr, nullptr, nullptr, nullptr};
+    // rt3_temporal_set_guide_motion_input, only with the guide: the samples' mean previous position, the point
+    // k_temporal<TemporalGuideMotion> looks up in the previous frame; null: none
+    const float4* guide_motion = nullptr;
 };
 void launch_temporal(hipStream_t st, const TemporalLaunch& L);
 
@@ -600,6 +603,25 @@ struct MotionLaunch {
     const float4* prev_pos = nullptr;  // some geometry is deformed: the snapshot, one {x, y, z, 0} per vertex; selects k_motion<true>
 };
 void launch_motion(hipStream_t st, const MotionLaunch& L);
+// GuideLaunch's companion (rt3_guide.hip): k_lens_guide_prev over the same camera queue and hit queue, following the
+// "motion" pass's tables `m` (geom_slot = nullptr: nothing moved, only the queues are read) and the snapshot `prev_pos` (null: nothing is
+// deformed).  out: one window-space float4 image of row length `width`, {sum R, n_hit} between batches, {sum R / n_hit, n_hit / samples}
+// after the last.  The grid covers npix, or is `groups` workgroups when that is not 0 (self-test op 41)
+struct GuidePrevLaunch {
+    MotionDev m;
+    const float4* prev_pos;
+    const uint32_t* pixels;
+    uint32_t npix, width;
+    const float *rays, *hits;
+    size_t stride;
+    uint32_t nsb, samples;
+    bool first_batch, last_batch;
+    float4* out;
+};
+void launch_lens_guide_prev(hipStream_t st, const GuidePrevLaunch& a, uint32_t groups = 0);
+// self-test op 41: k_lens_guide_prev on caller-made queues; op 39's header, pixel words and records; kSelftestGuidePrevOut words out per
+// listed pixel
+constexpr uint32_t kSelftestGuidePrevOut = 4;
 // The snapshot of rt3_scene_snapshot_vertices: prev_pos[v] = {verts[8 v], verts[8 v + 1], verts[8 v + 2], 0} for v in [first, first + n)
 void launch_snapshot_positions(hipStream_t st, const float* verts, uint32_t first, uint32_t n, float4* prev_pos);
 // Which geometries are deformed: chunk {geometry, lo, hi, -} sets flags[geometry] = 1 when a vertex v in [lo, hi) has a position word that

@@ -35,20 +35,6 @@ namespace rt3 {
 
 namespace {
 
-// fetch_triangle_object's index arithmetic over the snapshot's 16-byte records
-__device__ __forceinline__ void fetch_triangle_snapshot(const float4* prev_pos, const uint32_t* indices, const FlatGeomDev* geoms, const uint32_t* prim_geom,
-                                                        const uint32_t* first_prim, uint32_t prim, V3& a, V3& b, V3& c) {
-    uint32_t g = prim_geom[prim];
-    const FlatGeomDev& fg = geoms[g];
-    uint32_t io = fg.g.index_offset + 3u * (prim - first_prim[g]);
-    const float4 v0 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io])];
-    const float4 v1 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io + 1])];
-    const float4 v2 = prev_pos[(size_t)(fg.g.vertex_offset + indices[io + 2])];
-    a = v3(v0.x, v0.y, v0.z);
-    b = v3(v1.x, v1.y, v1.z);
-    c = v3(v2.x, v2.y, v2.z);
-}
-
 __device__ __forceinline__ const float4* snapshot_of() { return nullptr; }
 __device__ __forceinline__ const float4* snapshot_of(const float4* prev_pos) { return prev_pos; }
 

@@ -11,7 +11,9 @@
 // trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
 // Also owns rt3_ctx::guide: the guide images of a lens frame (rt3_camera_set_guide_output, rt3_denoise_set_guide_input, DESIGN.md section
 // 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through the <DnGuide> instances of its two end
-// kernels, and the two sets "temporal" reads through k_temporal<TemporalGuide> (rt3_temporal_set_guide_input).
+// kernels, and the two sets "temporal" reads through k_temporal<TemporalGuide> (rt3_temporal_set_guide_input); and
+// the fifth image, the samples' mean previous position (rt3_camera_set_guide_motion_output, rt3_temporal_set_guide_motion_input, DESIGN.md
+// section 4w), which trace_batch writes with k_lens_guide_prev and "temporal" reads through k_temporal<TemporalGuideMotion>.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -181,6 +183,24 @@ int motion_tables(rt3_ctx* c) {
     return RT3_OK;
 }
 
+}  // namespace
+
+namespace rt3 {
+
+int motion_launch_tables(rt3_ctx* c, MotionDev* m, const float4** prev_pos) {
+    if (int r = motion_tables(c)) return r;
+    const GeomTables t = world_tables(c);
+    m->verts = t.verts; m->indices = t.indices; m->geoms = t.geoms; m->prim_geom = t.prim_geom; m->first_prim = t.first_prim;
+    m->geom_slot = c->motion.any_moved ? c->motion.d_slot.get() : nullptr;
+    m->prev = c->motion.d_prev.get();
+    *prev_pos = c->motion.any_deformed ? c->deform.d_prev_pos.get() : nullptr;
+    return RT3_OK;
+}
+
+}  // namespace rt3
+
+namespace {
+
 // ---------------------------------------------------------------------------------------------- passes
 // A pass is one entry of kPasses (below): launch_pass checks the launch against the entry and hands the pass function (pass_*) the window
 // and the resolved bindings, in the entry's order.  What a pass function still checks is its own: context state, the least size of a
@@ -263,6 +283,11 @@ struct PathSetup {
     const AbsorbDev* absorb = nullptr;
     // guide images (rt3_camera_set_guide_output): the frame's four images, null unless "refrence_mode" resolved them -- k_lens_guide
     float4* guide[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the fifth (rt3_camera_set_guide_motion_output), null unless "refrence_mode" resolved it, and the "motion" pass's
+    // tables and snapshot it follows -- k_lens_guide_prev
+    float4* guide_prev = nullptr;
+    MotionDev motion{};
+    const float4* prev_pos = nullptr;
 };
 // pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
 constexpr float kSkyDeferMinPdf = 0x1p-100f;
@@ -385,6 +410,12 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             for (int k = 0; k < 4; k++) G.img[k] = ps.guide[k];
             ScopedTimer t(c, CAT_OTHER);
             launch_lens_guide(c->stream, G);
+            if (ps.guide_prev != nullptr) {  // where the same samples' points were one frame ago, from the same two queues
+                GuidePrevLaunch P{};
+                P.m = ps.motion; P.prev_pos = ps.prev_pos; P.pixels = pixels; P.npix = npix; P.width = W; P.rays = G.rays; P.hits = G.hits; P.stride = S;
+                P.nsb = nsb; P.samples = G.samples; P.first_batch = G.first_batch; P.last_batch = G.last_batch; P.out = ps.guide_prev;
+                launch_lens_guide_prev(c->stream, P);
+            }
         }
     }
     // every path starts at distance 0 from the vertex that chose its direction (the camera)
@@ -509,6 +540,22 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
         const Resource* const written[2] = {li, pv};
         if (int r = guide_resolve(c, c->guide.out, W, H, "refrence_mode: guide output", written, 2, "'Light' or 'PrevLight'", guide)) return r;
     }
+    float4* guide_prev = nullptr;
+    MotionDev motion{};
+    const float4* prev_pos = nullptr;
+    if (c->guide.motion_out) {  // DESIGN.md section 4w; before anything is enqueued too
+        if (!c->guide.out_on)
+            return fail(c, RT3_E_STATE, "refrence_mode: a guide motion output is set (rt3_camera_set_guide_motion_output) and no guide output "
+                                        "(rt3_camera_set_guide_output): the image is written beside the four, from the same samples");
+        const Resource* r = image_checked(c, c->guide.motion_out, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "refrence_mode: guide motion output");
+        if (!r) return RT3_E_INVALID;
+        if (r->ptr == li->ptr || r->ptr == pv->ptr)
+            return fail(c, RT3_E_INVALID, "refrence_mode: the guide motion output must not be 'Light' or 'PrevLight'");
+        for (int k = 0; k < 4; k++)
+            if (r->ptr == guide[k]) return fail(c, RT3_E_INVALID, "refrence_mode: the guide motion output must not be one of the four guide images");
+        if (int e = motion_launch_tables(c, &motion, &prev_pos)) return e;
+        guide_prev = static_cast<float4*>(r->ptr);
+    }
     if (Sspp == 0 || B == 0) return RT3_OK;  // GConst::default() leaves samples = bounces = 0 (renderer/mod.rs:47-63): nothing to trace
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     if (c->lens.on && (uint64_t)Sspp * B * 8u > (1ull << 31))
@@ -534,6 +581,9 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
     ps.lens_on = c->lens.on;
     ps.lens = lens_dev(c);
     for (int k = 0; k < 4; k++) ps.guide[k] = guide[k];
+    ps.guide_prev = guide_prev;
+    ps.motion = motion;
+    ps.prev_pos = prev_pos;
     for (uint32_t s0 = 0; s0 < Sspp; s0 += sb) {
         const uint32_t nsb = std::min(sb, Sspp - s0);
         if (int r = trace_batch(c, ps, W, gb, dp, pl->dev.get(), pl->dev_bn.get(), npix, s0, nsb)) return r;
@@ -831,6 +881,20 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
             L.prev_guide[k] = gi[4 + k];
         }
     }
+    // rt3_temporal_set_guide_motion_input: the samples' mean previous position is the point looked up
+    if (c->guide.temporal_motion) {
+        if (!c->guide.temporal_on)
+            return fail(c, RT3_E_STATE, "temporal: a guide motion input is set (rt3_temporal_set_guide_motion_input) and no guide input "
+                                        "(rt3_temporal_set_guide_input): the image describes a lens frame's samples; unset it (0), or give the guide sets");
+        const Resource* gm = image_checked(c, c->guide.temporal_motion, W, H, RT3_FORMAT_R32G32B32A32_SFLOAT, "temporal: guide motion input");
+        if (!gm) return RT3_E_INVALID;
+        if (gm->ptr == r[7]->ptr || gm->ptr == r[8]->ptr || gm->ptr == r[9]->ptr)
+            return fail(c, RT3_E_INVALID, "temporal: the guide motion input must not be 'Out', 'History' or 'Moments'");
+        for (int k = 0; k < 4; k++)
+            if (gm->ptr == L.guide[k] || gm->ptr == L.prev_guide[k])
+                return fail(c, RT3_E_INVALID, "temporal: the guide motion input must not be one of the eight guide images");
+        L.guide_motion = static_cast<const float4*>(gm->ptr);
+    }
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_temporal(c->stream, L);
@@ -842,18 +906,13 @@ int pass_temporal(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
 // "motion": where each pixel's surface point was one frame ago (no reference counterpart).  The primary trace is
 // pass_gbuffer's (primary_hits), so the hits are the G-buffer's.
 int pass_motion(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resource* const* res) {
-    if (int r = motion_tables(c)) return r;
     MotionLaunch L;
+    if (int r = motion_launch_tables(c, &L.m, &L.prev_pos)) return r;
     L.g = gconst_dev(g);
     PixelList* pl;
     if (int r = primary_hits(c, L.g, W, H, &pl)) return r;
     if (pl->count == 0) return RT3_OK;
-    const GeomTables t = world_tables(c);
-    L.m.verts = t.verts; L.m.indices = t.indices; L.m.geoms = t.geoms; L.m.prim_geom = t.prim_geom; L.m.first_prim = t.first_prim;
-    L.m.geom_slot = c->motion.any_moved ? c->motion.d_slot.get() : nullptr;
-    L.m.prev = c->motion.d_prev.get();
     L.pixels = pl->dev.get(); L.npix = pl->count; L.width = W; L.hits = c->work.hits.get(); L.out = res[0]->ptr;
-    L.prev_pos = c->motion.any_deformed ? c->deform.d_prev_pos.get() : nullptr;
     {
         ScopedTimer t(c, CAT_OTHER);
         launch_motion(c->stream, L);
@@ -1098,6 +1157,27 @@ int rt3_temporal_set_guide_input(rt3_ctx* c, const rt3_guide_images* current, co
         c->guide.temporal_cur = *current;
         c->guide.temporal_prev = *previous;
     }
+    return RT3_OK;
+}
+// the fifth guide image.  The output is checked here (a live RGBA32F image) and again at every "refrence_mode" launch
+// (size, not one of the images written there); the input at every "temporal" launch
+int rt3_camera_set_guide_motion_output(rt3_ctx* c, uint32_t image) {
+    if (!c) return RT3_E_INVALID;
+    if (image != 0) {
+        const Resource* r = get_res(c, image, RT3_TAG_IMAGE);
+        if (!r || r->format != RT3_FORMAT_R32G32B32A32_SFLOAT) return fail(c, RT3_E_INVALID, "guide motion output: the handle must be a live RGBA32F image");
+    }
+    c->guide.motion_out = image;
+    return RT3_OK;
+}
+int rt3_camera_get_guide_motion_output(rt3_ctx* c, uint32_t* image) {
+    if (!c || !image) return fail(c, RT3_E_INVALID, "guide motion output: NULL");
+    *image = c->guide.motion_out;
+    return RT3_OK;
+}
+int rt3_temporal_set_guide_motion_input(rt3_ctx* c, uint32_t image) {
+    if (!c) return RT3_E_INVALID;
+    c->guide.temporal_motion = image;  // checked when "temporal" is launched, like the motion input
     return RT3_OK;
 }
 int rt3_path_set_roulette(rt3_ctx* c, const rt3_roulette_params* p) {

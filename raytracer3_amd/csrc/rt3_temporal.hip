@@ -11,6 +11,8 @@
 //                            where the surface point was one frame ago instead of P itself
 //     TemporalGuide          lens and glass frames: the guide images of this and of the previous frame (rt3_temporal_set_guide_input,
 //                            DESIGN.md section 4v)
+//     TemporalGuideMotion    the same, and with k_lens_guide_prev's image (rt3_temporal_set_guide_motion_input) the
+//                            projected point is the mean of where the samples' surface points were one frame ago
 //
 // Arithmetic contract: tests/ref_temporal.py restates every operation below in numpy float32, in this order (matrix rows summed left to
 // right like primary_ray, taps rows outer, columns inner), tests/ref_motion.py and tests/ref_temporal_guide.py the records of the other
@@ -64,6 +66,16 @@ struct TemporalGbuffer {
 struct TemporalGuide {
     DnGuide cur, prev;  // prev's albedo and emission are not read
     RT3_DEV void lookup(size_t, V3&, bool&) const {}
+};
+struct TemporalGuideMotion {
+    DnGuide cur, prev;     // like TemporalGuide's
+    const float4* motion;  // k_lens_guide_prev's image {mean previous position, coverage} (rt3_guide.hip)
+    // R is the mean of where the samples' surface points were one frame ago.  A foreground pixel has coverage 1, every sample hit, so the
+    // point always exists: `known` stays true.  The tolerance, the normal and the record stay this frame's.
+    RT3_DEV void lookup(size_t pi, V3& R, bool&) const {
+        const float4 M = motion[pi];
+        R = v3(M.x, M.y, M.z);
+    }
 };
 
 // row r of (column-major m) * (v, w), summed left to right like primary_ray
@@ -170,8 +182,9 @@ void launch_temporal(hipStream_t st, const TemporalLaunch& L) {
         hipLaunchKernelGGL(k_temporal<decltype(src)>, dn_grid(L.W, L.H), dim3(kDnTileX, kDnTileY), 0, st, L.g, L.prev, a, src);
     };
     const DnGbuffer cur = {(const uint4*)L.gbuffer, L.depth}, prev = {(const uint4*)L.prev_gbuffer, L.prev_depth};
-    if (L.guide[0])  // rt3_temporal_set_guide_input: the G-buffer bindings and the motion image are not read
-        launch(TemporalGuide{{L.guide[0], L.guide[1], L.guide[2], L.guide[3]}, {L.prev_guide[0], L.prev_guide[1], L.prev_guide[2], L.prev_guide[3]}});
+    const DnGuide gcur = {L.guide[0], L.guide[1], L.guide[2], L.guide[3]}, gprev = {L.prev_guide[0], L.prev_guide[1], L.prev_guide[2], L.prev_guide[3]};
+    if (L.guide[0] && L.guide_motion) launch(TemporalGuideMotion{gcur, gprev, L.guide_motion});
+    else if (L.guide[0]) launch(TemporalGuide{gcur, gprev});  // rt3_temporal_set_guide_input: the G-buffer bindings and the motion image are not read
     else if (L.motion) launch(TemporalGbuffer<true>{cur, prev, (const float4*)L.motion});
     else launch(TemporalGbuffer<false>{cur, prev, nullptr});
 }

@@ -555,6 +555,37 @@ class Context:
         self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_GUIDE_QUEUE, inp.ctypes.data, n, out.ctypes.data))
         return out[: 16 * npix].reshape(npix, 16)
 
+    def set_guide_motion_output(self, image=0):
+        """the fifth guide image a lens frame's "refrence_mode" writes beside the four: the samples' mean previous position
+        (rt3_camera_set_guide_motion_output); an RGBA32F image handle, 0 = off, the default"""
+        self.check(self.lib.rt3_camera_set_guide_motion_output(self.h, int(image)))
+
+    def get_guide_motion_output(self):
+        """the handle last set (rt3_camera_get_guide_motion_output); 0: off"""
+        image = C.c_uint32()
+        self.check(self.lib.rt3_camera_get_guide_motion_output(self.h, C.byref(image)))
+        return int(image.value)
+
+    def set_temporal_guide_motion_input(self, image=0):
+        """the image of set_guide_motion_output as the point a guided "temporal" looks up in the previous frame
+        (rt3_temporal_set_guide_motion_input); 0 = none, the default"""
+        self.check(self.lib.rt3_temporal_set_guide_motion_input(self.h, int(image)))
+
+    def selftest_guide_prev_queue(self, pixels, records, nsb, samples, first, last, groups, prefill=None):
+        """Self-test op 41: k_lens_guide_prev on the queues of selftest_guide_queue, over the built scene and the context's current motion
+        tables (set_prev_transforms, snapshot_vertices); `prefill` (npix, 4): the image's words at the listed pixels before the launch
+        (zeros without).  Returns them afterwards, (npix, 4) uint32.  The library fails the call when the kernel wrote anything else."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 10)
+        npix, n = len(pixels), len(records)
+        head = np.array([npix, nsb, samples, int(first), int(last), groups], np.uint32)
+        inp = np.concatenate([head, pixels, records.reshape(-1)])
+        out = np.zeros(4 * max(npix, 1), np.uint32)
+        if prefill is not None:
+            out[: 4 * npix] = np.ascontiguousarray(prefill).view(np.uint32).reshape(-1)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_GUIDE_PREV_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return out[: 4 * npix].reshape(npix, 4)
+
     def set_roulette(self, params=None, **kw):
         """Russian roulette on extension rays (rt3_path_set_roulette, DESIGN.md section 4o): an L.RouletteParams, or its fields as keywords;
         nothing = off"""

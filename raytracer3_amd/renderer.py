@@ -70,6 +70,12 @@ def prev_guide_images(rg):
     return {key: rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, name) for key, name in PREV_GUIDE_IMAGES}
 
 
+def guide_prev_position_image(rg):
+    """the fifth guide image of a lens frame, the samples' mean previous position: what
+    ctx.set_guide_motion_output and ctx.set_temporal_guide_motion_input take"""
+    return rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "GuidePrevPosition")
+
+
 def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, motion=False, adaptive=False, *,
                 gbuffer_names=("gbuffer", "gbuffer_depth"), gbuffer_node=True, trace=True, guide=False):
     """This frame's nodes in `rg` (the analogue of renderer::commands, renderer/mod.rs:65-106); returns the resource handles.  With
@@ -84,7 +90,10 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     With `guide` (a lens frame whose context has the guide output set, ctx.set_guide_output) the four images of guide_images() are
     declared as context-state writes of the path-trace node and, with `denoise`, as context-state reads of the "denoise" node (handle
     `guide`: the dict of guide_images); they are no bindings.  With `temporal` too (ctx.set_temporal_guide_input)
-    the "temporal" node reads them as context state as well, and the previous frame's set (handle `prev_guide`: prev_guide_images)."""
+    the "temporal" node reads them as context state as well, and the previous frame's set (handle `prev_guide`: prev_guide_images).
+    With `guide`, `temporal` and `motion` together no "motion" node is added: the image of
+    guide_prev_position_image() (handle `guide_motion`) is a context-state write of the path-trace node
+    (ctx.set_guide_motion_output) and a context-state read of "temporal" (ctx.set_temporal_guide_motion_input)."""
     full, f4 = ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT
     gbuffer = rg.image(full, L.FORMAT_R32G32B32A32_UINT, gbuffer_names[0])
     depth = rg.image(full, L.FORMAT_R32_SFLOAT, gbuffer_names[1])
@@ -95,6 +104,7 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
     if trace or postprocess:
         handles["color"] = rg.image(full, f4, "color")
     gb = src = guide_origin = IMPORTED
+    guide_motion = guide_prev_position_image(rg) if guide and temporal and motion else None
     if gbuffer_node:
         gb = (RayTracingPass.new(rg, "gbuffer").shader("gbuffer").constants(gconst)
               .write(IMPORTED, gbuffer).write(IMPORTED, depth).launch(WorkSize2D.FullScreen))
@@ -108,6 +118,8 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         if guide:
             for h in guide_images(rg).values():
                 pt.state_write(h)
+            if guide_motion is not None:
+                pt.state_write(guide_motion)
         src = pt.launch(WorkSize2D.FullScreen)
         guide_origin = src
     if guide:
@@ -115,11 +127,13 @@ def frame_nodes(rg, gconst, postprocess=True, denoise=False, temporal=False, mot
         if temporal:
             handles["prev_guide"] = prev_guide_images(rg)
     lit = light
-    if motion:
+    if guide_motion is not None:
+        handles["guide_motion"] = guide_motion
+    elif motion:
         handles["motion"] = motion_node(rg, gconst)[1]
     if temporal:
         src, th = temporal_node(rg, gconst, gb, gbuffer, depth, src, light, guide=handles.get("guide"), guide_origin=guide_origin,
-                                prev_guide=handles.get("prev_guide"))
+                                prev_guide=handles.get("prev_guide"), guide_motion=guide_motion)
         handles.update(th)
         lit = th["accumulated"]
     if denoise:
@@ -153,11 +167,13 @@ def temporal_images(rg):
                 accumulated=rg.image(full, f4, "accumulated"), history=rg.image(full, f4, "History"), moments=rg.image(full, f4, "Moments"))
 
 
-def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light, guide=None, guide_origin=IMPORTED, prev_guide=None):
+def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light, guide=None, guide_origin=IMPORTED, prev_guide=None,
+                  guide_motion=None):
     """ComputePass("temporal"): {gbuffer, gbuffer_depth, In = `light`, PrevGbuffer, PrevDepth, PrevHistory, PrevMoments, Out = `accumulated`,
     History, Moments}.  The previous view is context state (ctx.set_prev_view).  Returns (node, the handles of temporal_images).  `guide`
     and `prev_guide`: the dicts of guide_images() and prev_guide_images() the pass reads as context state (ctx.set_temporal_guide_input),
-    the first written by node `guide_origin`."""
+    the first written by node `guide_origin`; `guide_motion`: the image of guide_prev_position_image(), written by that node too and read
+    as context state (ctx.set_temporal_guide_motion_input)."""
     t = temporal_images(rg)
     tn = (ComputePass.new(rg, "temporal").shader("temporal").constants(gconst)
           .read(gb_origin, gbuffer).read(gb_origin, depth).read(light_origin, light)
@@ -167,6 +183,8 @@ def temporal_node(rg, gconst, gb_origin, gbuffer, depth, light_origin, light, gu
         tn.state_read(guide_origin, h)
     for h in (prev_guide or {}).values():
         tn.state_read(IMPORTED, h)
+    if guide_motion is not None:
+        tn.state_read(guide_origin, guide_motion)
     return tn.dispatch(DispatchSize.FullScreen), t
 
 
@@ -337,14 +355,19 @@ class PathTracer:
         """the next temporal frame starts over (zeroed PrevHistory / PrevMoments: the reset rule of the "temporal" pass)"""
         self._history.reset()
 
-    def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth"), guide=False):
+    def _begin_temporal(self, gconst, denoise, gbuffer_names=("gbuffer", "gbuffer_depth"), guide=False, trace=True):
         """Before a temporal frame's nodes are built: what the last temporal frame wrote, and the G-buffer it read (the images named
         `gbuffer_names`), become `Prev*` (the images trade names, like swap_light_prev), or, with no history, zeros are uploaded; the
         previous view and the variance input of "denoise" are set.  A frame rendered without `temporal` in between overwrites the kept
-        G-buffer: call reset_history() after one.  Returns whether the frame needs the "motion" node.
+        G-buffer: call reset_history() after one.  Returns whether the frame follows what moved: with the "motion" node, or, guided, with
+        the guide's fifth image.
         `guide` (set_guide(temporal=True) with a lens in force): "temporal" takes its records from this frame's guide
-        images and from the previous guided temporal frame's (the two sets trade names behind each such frame, _end_temporal); the motion
-        input stays 0 whatever moved.  A guided frame after an unguided one, and the reverse, start the history over."""
+        images and from the previous guided temporal frame's (the two sets trade names behind each such frame, _end_temporal).  The
+        pinhole motion input stays 0 whatever moved; when something moved or deformed, "refrence_mode" is given the image of
+        guide_prev_position_image() to write (ctx.set_guide_motion_output) and "temporal" the same image to look up
+        (ctx.set_temporal_guide_motion_input), else both are set to 0.  Not with `trace` False (denoise(): the frame's
+        "refrence_mode" has run already): the input is 0 and False is returned.  A guided frame after an unguided one, and the reverse,
+        start the history over."""
         if guide != self._temporal_guided:
             self._history.reset()
             self._temporal_guided = guide
@@ -366,11 +389,17 @@ class PathTracer:
         self.ctx.set_denoise_variance_input(t["moments"] if denoise else 0)
         moved = self._history.begin_frame()  # "temporal" then reads the "motion" pass's image
         if guide:
-            moved = False  # the "motion" image is made from pinhole primary hits: it does not describe the camera samples
+            # the "motion" image is made from pinhole primary hits and does not describe the camera samples: their own mean previous position
+            moved = moved and trace
+            image = guide_prev_position_image(rg) if moved else 0
             self.ctx.set_temporal_guide_input(guide_images(rg), prev_guide_images(rg))
+            self.ctx.set_temporal_guide_motion_input(image)
+            if trace:
+                self.ctx.set_guide_motion_output(image)
         elif self._guide:
             self.ctx.set_temporal_guide_input(None, None)
-        self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved else 0)
+            self.ctx.set_temporal_guide_motion_input(0)
+        self.ctx.set_temporal_motion_input(rg.image(ImageSize.FullScreen, L.FORMAT_R32G32B32A32_SFLOAT, "Motion") if moved and not guide else 0)
         return moved
 
     def _end_temporal(self, gconst, guide):
@@ -385,7 +414,8 @@ class PathTracer:
     def update_vertices(self, vertices, first=0):
         """deformed vertices (same topology): upload them and refit the acceleration structure.  Between temporal frames the positions as
         they were at the last one are kept first (ctx.snapshot_vertices, once per frame interval, before its first upload), and the next
-        temporal frame runs the "motion" pass so that the deformed geometries keep their history."""
+        temporal frame runs the "motion" pass so that the deformed geometries keep their history -- or, guided by the
+        camera samples (set_guide(temporal=True)), writes their mean previous position from the same snapshot (section 4w)."""
         self._history.vertices_updated()
         self.ctx.update_vertices(vertices, first)
         self.ctx.refit_accel()
@@ -414,14 +444,19 @@ class PathTracer:
         G-buffer.  Without a lens, and for adaptive frames, everything is as with the guide off; so it is for temporal frames unless
         `temporal`: then render(g, temporal=True[, denoise=True]) writes the guide too, "temporal" takes its surface
         records from this frame's and the previous temporal frame's guide images instead of the pinhole G-buffer, and "denoise" is guided
-        by this frame's with the temporal variance.  Such frames never run "motion": moved instances and updated vertices are caught only
-        as far as the plane test catches them.  With several ranks denoise() raises: the guide images are not gathered."""
+        by this frame's with the temporal variance.  Such frames never run "motion": after set_instances() moved something or
+        update_vertices() deformed something, render() has "refrence_mode" write a fifth image, the samples' mean previous position, and
+        "temporal" looks that point up in the previous frame, so moved instances and deformed meshes keep their
+        history under a lens as they do without one.  denoise(temporal=True) runs behind the frame's "refrence_mode" and does not follow them.
+        With several ranks denoise() raises: the guide images are not gathered."""
         self._guide = bool(on)
         self._guide_temporal = self._guide and bool(temporal)
         if not self._guide:
             self.ctx.set_guide_output(None)
+            self.ctx.set_guide_motion_output(0)
             self.ctx.set_denoise_guide_input(None)
             self.ctx.set_temporal_guide_input(None, None)
+            self.ctx.set_temporal_guide_motion_input(0)
 
     def _temporal_guide_in_force(self, adaptive=False):
         """whether a temporal frame rendered now is a guided one (set_guide(temporal=True), a lens in force, not adaptive)"""
@@ -435,6 +470,8 @@ class PathTracer:
         on = self.ctx.get_lens()[1] and (not temporal or self._guide_temporal) and not adaptive
         images = guide_images(self.rg) if on else None
         self.ctx.set_guide_output(images)
+        if not (on and temporal):  # a guided temporal frame's fifth image is _begin_temporal's; every other frame writes none
+            self.ctx.set_guide_motion_output(0)
         self.ctx.set_denoise_guide_input(images if denoise else None)
         return on
 
@@ -495,7 +532,7 @@ class PathTracer:
             raise ValueError("denoise() with the sample guide on (set_guide) needs the whole frame's guide images on this rank, and they are not "
                              "gathered: render on one rank, or switch the guide off")
         names = ("TemporalGbuffer", "TemporalDepth") if temporal else ("gbuffer", "gbuffer_depth")  # render() must not overwrite the kept one
-        moved = temporal and self._begin_temporal(gconst, denoise, names, guide=tguide)
+        moved = temporal and self._begin_temporal(gconst, denoise, names, guide=tguide, trace=False)
         if denoise and not temporal:
             self.ctx.set_denoise_variance_input(0)
         if self._guide:
@@ -567,7 +604,9 @@ class PathTracer:
         "refrence_mode", with gconst.samples as the cap; its Moments image is the handle `adaptive_moments` (adaptive_moments(),
         sample_counts(), ctx.adaptive_info()).
         Under set_guide(True, temporal=True) with a lens in force a temporal frame is guided by the camera samples:
-        handles `guide` and `prev_guide`, and no "motion" node whatever moved."""
+        handles `guide` and `prev_guide`, and no "motion" node whatever moved.  After set_instances() moved something or update_vertices()
+        deformed something such a frame has "refrence_mode" write the samples' mean previous position as a fifth guide image (handle
+        `guide_motion`), which "temporal" looks up in the previous frame."""
         if adaptive is not None and adaptive is not True and adaptive is not False:
             self.ctx.adaptive_set_params(adaptive)
         adaptive_on = adaptive is not None and adaptive is not False
@@ -577,7 +616,7 @@ class PathTracer:
             self.ctx.set_denoise_variance_input(0)
         guide = self._guide_in_force(denoise, temporal, adaptive_on)
         h = self.commands(gconst, postprocess, denoise, temporal, motion, adaptive=adaptive_on, guide=guide)
-        if motion:
+        if motion and not tguide:
             self.rg.draw_frame(h["motion"])
         self.rg.draw_frame(h["color"] if postprocess else (h["denoised"] if denoise else (h["accumulated"] if temporal else h["light"])), wait=wait)
         if temporal:
