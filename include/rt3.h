@@ -138,6 +138,8 @@ typedef struct rt3_stats {
                                     address from one base) is: a process-wide serial number taken where an arena is allocated, 0 = no
                                     arena (empty scene).  It changes whenever the structure moves to a new allocation (a build that makes
                                     new trees, rt3_accel_import) and stays when it is rewritten in place (rt3_accel_refit). */
+    uint64_t emit_tex_launches;  /* k_emit_tex launches (rt3_scene_set_textured_emitters) since rt3_stats_reset: 0 for every frame whose light
+                                    table holds no textured emitter */
 } rt3_stats;
 
 typedef struct rt3_ctx rt3_ctx;
@@ -497,6 +499,40 @@ int rt3_light_download(rt3_ctx *ctx, uint32_t *prim, float *area, uint32_t *mass
  * array is written.  RT3_E_STATE where rt3_light_info returns it. */
 int rt3_light_table(rt3_ctx *ctx, uint32_t flags, float *rec /* 16 per entry */, uint32_t *cdf, uint32_t *guide, uint32_t *prim, float *area,
                     uint32_t *cells, uint32_t *shift);
+
+/* ---- textured emitters (no reference equivalent).  Off by default: RT3_F_NEE_EMISSIVE leaves out every geometry whose
+ * rt3_material_textures entry names an emissive texture, and such a geometry is found by BSDF-sampled rays alone, with weight 1.
+ * rt3_scene_set_textured_emitters(ctx, 1) makes those geometries entries of the light table too.  The mode moves only the light table's
+ * key (as rt3_scene_set_lights does): the acceleration structure stays current, and the next frame or readback remakes the table.  The
+ * key also holds the texture pool: a later rt3_scene_set_texture remakes the table of a context whose mode is on.
+ *   Which tables change: only those of a built scene with at least one textured emitter -- a geometry with non-zero emission, triangles,
+ * no alpha cutoff (masked geometries stay out, section 4e) and an emissive texture index below the number of uploaded textures.  Without
+ * one (no material textures, or every emissive index not uploaded) table and frames are the mode-off ones bit for bit and nothing more is
+ * launched.  With one, every emissive unmasked geometry is listed; an emitter whose emissive index is not uploaded is listed without
+ * texture, as the hit side reads it.
+ *   Records: unchanged, Le = 12 emission (the factor, as if the texture were 1).  A side array of 32 bytes per table entry holds
+ * {uv0, uv1, uv2, emissive texture index or -1, 0}: the vertex uvs in the order the record's A, E1, E2 were made, so the point
+ * A + b1 E1 + b2 E2 has uv = uv0 (1 - b1 - b2) + uv1 b1 + uv2 b2 -- the hit side's expression.  rt3_light_emit_tex reads it back
+ * (*n_entries = 0 and nothing written for a table without textured emitter).
+ *   Selection mass of a textured emitter: area x luminance(Le (*) mean_rgb), where mean_rgb is a fixed quadrature of the emissive lookup
+ * (bilinear, repeat addressing, sRGB decode per texel: the hit side's) over the triangle:
+ *     L = clamp(ceil(longest uv edge in texels), 1, 64); the edge (du, dv) of a W x H texture measures max(|du| W, |dv| H), all in fp32;
+ *         a non-finite edge gives L = 1;
+ *     the triangle is cut into L^2 congruent triangles by the lines b1 = i / L, b2 = j / L, b1 + b2 = k / L; the lookup is taken at their
+ *         centroids: (b1, b2) = ((3 i + 1) / 3L, (3 j + 1) / 3L) for i + j < L and ((3 i + 2) / 3L, (3 j + 2) / 3L) for i + j < L - 1, each one fp32
+ *         division of two exact integers;
+ *     mean_rgb = the sum of the L^2 lookups / L^2 per channel.  Centroid number k = a L + c (a, c < L) is the first kind's (i, j) = (a, c) when
+ *         a + c < L and the second kind's (L - 1 - a, L - 1 - c) otherwise; lane l of 64 adds centroids l, l + 64, ... in rising order and the
+ *         lane sums meet in a butterfly (xor 32, 16, .. 1): the same bits on every run, in both instance modes and after a refit.
+ * The mean steers variance only: a triangle whose quadrature finds nothing gets mass 0 and is never sampled (its hits keep weight 1), a
+ * sampled point whose texel is black contributes 0, and all points of one triangle share one density (uniform on the triangle, not
+ * proportional to the texel).
+ *   The light sample: k_shade queues the emitter shadow ray with the factor as radiance; k_emit_tex, between it and the k_shadow launch,
+ * redraws the path's RNG dims 5, 6, 7, finds the emitter and the point again and multiplies the ray's contribution by the texture there.
+ * rt3_stats.emit_tex_launches counts its launches.  RT3_E_INVALID for a mode other than 0 or 1. */
+int rt3_scene_set_textured_emitters(rt3_ctx *ctx, int on);
+int rt3_scene_get_textured_emitters(rt3_ctx *ctx, int *on);
+int rt3_light_emit_tex(rt3_ctx *ctx, uint32_t flags, uint32_t *n_entries, void *out /* 8 words per entry, may be NULL */);
 /* sky tables for parity tests (any pointer may be NULL): per-row alias words q16 | alias << 16 (w*h), RGB9E5 texels (w*h),
  * marginal CDF (h), realised (u,v) density (w*h) */
 int rt3_sky_download(rt3_ctx *ctx, uint32_t *alias, uint32_t *texels_rgb9e5, float *cdf_marg, float *pdf_uv);
@@ -941,6 +977,17 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      motion tables (rt3_scene_set_prev_transforms, rt3_scene_snapshot_vertices; RT3_E_STATE for a wrong transform count).  The header,
  *      pixel words, records, checks and guards are op 39's.  out: 4 words per listed pixel; the words the caller put there are the image's
  *      contents before the launch.
+ *      42 the emitter-side radiance of a textured-emitter table (rt3_scene_set_textured_emitters).  in: {flags}, then n rows {table entry, b1,
+ *      b2}.  out: 3 words per row, Le (*) the emissive texture at barycentrics (1 - b1 - b2, b1, b2) (Le itself for an entry without texture).
+ *      Ops 42 - 44 run over the light table `flags` samples (RT3_F_NEE_EMISSIVE must be in it): RT3_E_STATE when it holds no textured emitter,
+ *      RT3_E_INVALID for an entry the table does not have.
+ *      43 k_emit_tex itself on a caller-made emitter shadow queue of n slots.  in: the header {frame, bounces, b, s0, dims (RNG dimensions per
+ *      vertex, 1 .. 8), npix, workgroups to launch (1 .. 65535), count (<= n: the queue's length word), flags}, then npix pixel words
+ *      x | y << 16, then n records of 4 words {contribution r, g, b, path id}.  out: 3 words per slot, the contributions after the launch.
+ *      The queue's planes are one record longer than n and filled with a pattern: RT3_E_STATE when the kernel changed an origin, a
+ *      direction, a path id or a word behind the end.  Slots at and behind `count` must come back as they went in.
+ *      44 the mean texel k_emit_tex_power found for every entry of the table (1 1 1 for an entry without texture).  in: {flags}; n = the table's
+ *      entries.  out: 3 words per entry.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

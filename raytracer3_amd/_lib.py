@@ -43,6 +43,9 @@ SELFTEST_ABSORB_QUEUE = 37  # rt3_selftest_eval op: k_absorb on a caller-made qu
 SELFTEST_FROST = 38  # rt3_selftest_eval op: {ior, thin_walled (u32), d, n, alpha, u_event, u2, u3} (12 words) -> {event (u32: 0 reflect, 1 transmit, 2 invalid), direction, F, weight} (6), the frosted vertex rule
 SELFTEST_GUIDE_QUEUE = 39  # rt3_selftest_eval op: k_lens_guide on caller-made camera and hit queues over the built scene (Context.selftest_guide_queue)
 SELFTEST_GUIDE_PREV_QUEUE = 41  # rt3_selftest_eval op: k_lens_guide_prev on caller-made camera and hit queues over the built scene and the current motion tables (Context.selftest_guide_prev_queue)
+SELFTEST_EMIT_RADIANCE = 42  # rt3_selftest_eval op: {flags}, rows {table entry, b1, b2} -> the emitter-side radiance Le (*) texture (3 words) (Context.selftest_emit_radiance)
+SELFTEST_EMIT_TEX_QUEUE = 43  # rt3_selftest_eval op: k_emit_tex on a caller-made emitter shadow queue over the built scene's light table (Context.selftest_emit_tex_queue)
+SELFTEST_EMIT_MEAN = 44  # rt3_selftest_eval op: the mean texel of every light-table entry, as k_emit_tex_power found it (Context.selftest_emit_mean)
 SELFTEST_LIGHT_TABLE = 40  # rt3_selftest_eval op: the light table's quantise / scan / CDF / guide kernels and light_find on caller-made powers (Context.selftest_light_table)
 
 EXPORTS = [
@@ -67,6 +70,7 @@ EXPORTS = [
     "rt3_camera_set_guide_motion_output", "rt3_camera_get_guide_motion_output", "rt3_temporal_set_guide_motion_input",
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses", "rt3_light_table",
+    "rt3_scene_set_textured_emitters", "rt3_scene_get_textured_emitters", "rt3_light_emit_tex",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
@@ -87,7 +91,7 @@ class Stats(C.Structure):
                 ("shade_ms", C.c_double), ("other_ms", C.c_double),
                 ("trace_launches", C.c_uint64), ("trace_ms", C.c_double), ("trace_rays", C.c_uint64 * 2), ("trace_nodes", C.c_uint64 * 2),
                 ("trace_tris", C.c_uint64 * 2), ("gather_ms", C.c_double), ("nodes_visited_lds", C.c_uint64), ("shadow_nodes_visited_lds", C.c_uint64), ("accel_build_ms", C.c_double), ("accel_bulk_copies", C.c_uint64),
-                ("accel_arena_serial", C.c_uint64)]
+                ("accel_arena_serial", C.c_uint64), ("emit_tex_launches", C.c_uint64)]
 
 
 class Instance(C.Structure):
@@ -258,6 +262,9 @@ def load():
         "rt3_scene_set_lights": (i32, [vp, vp, u32]),
         "rt3_light_masses": (i32, [vp, u32, pu32, pu32, vp]),
         "rt3_light_table": (i32, [vp, u32, vp, vp, vp, vp, vp, pu32, pu32]),
+        "rt3_scene_set_textured_emitters": (i32, [vp, i32]),
+        "rt3_scene_get_textured_emitters": (i32, [vp, C.POINTER(i32)]),
+        "rt3_light_emit_tex": (i32, [vp, u32, pu32, vp]),
         "rt3_temporal_set_motion_input": (i32, [vp, u32]),
         "rt3_adaptive_set_params": (i32, [vp, C.POINTER(AdaptiveParams)]),
         "rt3_adaptive_info": (i32, [vp, pu32, C.POINTER(C.c_uint64), pu32]),

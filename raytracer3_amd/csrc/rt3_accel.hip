@@ -235,14 +235,33 @@ int ensure_lights(rt3_ctx* c, uint32_t combo) {
     const bool with_punct = (combo & RT3_F_NEE_PUNCTUAL) != 0u && !c->scene.lights.empty();
     if (!with_punct) combo &= ~RT3_F_NEE_PUNCTUAL;  // no lights: the table of the other flag alone, whatever the list's stamp
     LightTable& lt = c->accel.lights;
-    if (lt.stamp == c->accel.stamp && lt.combo == combo && (!with_punct || lt.lights_stamp == c->scene.lights_stamp)) return RT3_OK;
+    // textured emitters: the mode is part of the key, and with it the texture pool: the masses depend on texels
+    const bool tex_mode = c->scene.textured_emitters;
+    if (lt.stamp == c->accel.stamp && lt.combo == combo && (!with_punct || lt.lights_stamp == c->scene.lights_stamp) && lt.tex_mode == tex_mode &&
+        (!tex_mode || lt.tex_stamp == c->scene.tex_stamp))
+        return RT3_OK;
+    HIPC(c, hipSetDevice(c->device));
+    // is any geometry a textured emitter?  Only then does the mode change anything: non-zero emission, triangles, no mask, and an emissive
+    // texture that is uploaded (hit_finish<true>'s has_e).  Without one the table is the mode-off table, bit for bit.
+    bool tex_on = false;
+    if (tex_mode && with_emit && any_mat_tex(c)) {
+        if (int r = sync_textures(c)) return r;
+        const int64_t n_tex = c->scene.d_tex_pixels ? (int64_t)c->scene.h_tex.size() : 0;
+        for (const Placed& p : c->accel.placed) {
+            const float* em = c->scene.h_geoms[p.geom].emission;
+            const bool masked = any_cutoff(c) && c->scene.h_cutoffs[p.geom] > 0.0f;
+            const int64_t et = c->scene.h_mat_tex[p.geom].emissive_texture;
+            tex_on = tex_on || ((em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked && et >= 0 && et < n_tex);
+        }
+    }
     std::vector<uint32_t> geom_base, eg_geom, eg_first;
     uint64_t n = 0;
     for (const Placed& p : c->accel.placed) {
         const float* em = c->scene.h_geoms[p.geom].emission;
         const bool masked = any_cutoff(c) && c->scene.h_cutoffs[p.geom] > 0.0f;  // left out: its points may be cut away
-        // an emissive texture scales the radiance point by point: left out like a masked geometry
-        const bool textured = any_mat_tex(c) && c->scene.h_mat_tex[p.geom].emissive_texture >= 0;
+        // an emissive texture scales the radiance point by point: left out like a masked geometry, unless the
+        // textured-emitter mode samples it (section 4x)
+        const bool textured = !tex_on && any_mat_tex(c) && c->scene.h_mat_tex[p.geom].emissive_texture >= 0;
         const bool emissive = with_emit && (em[0] != 0.0f || em[1] != 0.0f || em[2] != 0.0f) && p.n_prims > 0 && !masked && !textured;
         geom_base.push_back(emissive ? (uint32_t)n : kMiss);
         if (emissive) {
@@ -251,15 +270,17 @@ int ensure_lights(rt3_ctx* c, uint32_t combo) {
             n += p.n_prims;
         }
     }
-    HIPC(c, hipSetDevice(c->device));
     if (n + c->scene.lights.size() > 0x7FFFFFFFull) return fail(c, RT3_E_INVALID, "light table: too many entries");
+    const SceneDev sc = scene_dev(c);
     const hipError_t e = lights_build(c->stream, world_tables(c), geom_base, eg_geom, eg_first, (uint32_t)n, &lt,
                                       with_punct ? reinterpret_cast<const float*>(c->scene.lights.data()) : nullptr,
-                                      with_punct ? (uint32_t)c->scene.lights.size() : 0u, c->accel.n_flat_prims);
+                                      with_punct ? (uint32_t)c->scene.lights.size() : 0u, c->accel.n_flat_prims, tex_on ? &sc : nullptr);
     if (e != hipSuccess) return fail(c, RT3_E_HIP, std::string("emitter table: ") + hipGetErrorString(e));
     lt.stamp = c->accel.stamp;
     lt.combo = combo;
     lt.lights_stamp = c->scene.lights_stamp;
+    lt.tex_mode = tex_mode;
+    lt.tex_stamp = c->scene.tex_stamp;
     return RT3_OK;
 }
 
@@ -1046,6 +1067,18 @@ int rt3_light_table(rt3_ctx* c, uint32_t flags, float* rec, uint32_t* cdf, uint3
     if (guide) HIPC(c, hipMemcpy(guide, t.guide.get(), ((size_t)t.n_guide + 1) * 4, hipMemcpyDeviceToHost));
     if (prim) HIPC(c, hipMemcpy(prim, t.prim.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
     if (area) HIPC(c, hipMemcpy(area, t.area.get(), (size_t)t.n * 4, hipMemcpyDeviceToHost));
+    return RT3_OK;
+}
+
+// the side array of a table with textured emitters: 8 words per entry {uv0, uv1, uv2, texture index or -1, pad}
+int rt3_light_emit_tex(rt3_ctx* c, uint32_t flags, uint32_t* n_entries, void* out) {
+    if (!c) return RT3_E_INVALID;
+    const uint32_t combo = flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL);
+    if (int r = ensure_lights(c, combo ? combo : RT3_F_NEE_EMISSIVE)) return r;  // (rt3_light_masses' rule)
+    const LightTable& t = c->accel.lights;
+    const bool any = combo != 0u && t.n != 0u && t.textured;
+    if (n_entries) *n_entries = any ? t.n : 0u;
+    if (any && out) HIPC(c, hipMemcpy(out, t.emit_tex.get(), (size_t)t.n * sizeof(EmitTexDev), hipMemcpyDeviceToHost));
     return RT3_OK;
 }
 

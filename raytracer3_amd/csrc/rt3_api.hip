@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rt3_ctx.hpp"
+#include "rt3_emit_tex.hpp"
 #include "rt3_roulette.hpp"
 #include "rt3_volume.hpp"
 
@@ -654,8 +655,105 @@ static int selftest_light_table(rt3_ctx* c, const uint32_t* in, uint32_t n, uint
     return RT3_OK;
 }
 
+// The light table the textured-emitter self-test ops (42, 43, 44) run over: the one `flags` samples, which must hold a textured emitter
+static int selftest_textured_table(rt3_ctx* c, uint32_t flags, const LightTable** out) {
+    const uint32_t combo = flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL);
+    if (!(combo & RT3_F_NEE_EMISSIVE)) return fail(c, RT3_E_INVALID, "selftest: the textured-emitter ops need RT3_F_NEE_EMISSIVE in their flags word");
+    if (int r = ensure_lights(c, combo)) return r;
+    if (!c->accel.lights.textured || c->accel.lights.n == 0u)
+        return fail(c, RT3_E_STATE, "selftest: the light table holds no textured emitter (rt3_scene_set_textured_emitters, an emissive geometry with an uploaded emissive texture)");
+    *out = &c->accel.lights;
+    return RT3_OK;
+}
+// Self-test op 42: the emitter-side radiance.  in: {flags}, then n rows {entry, b1, b2}.  out: 3 words per row.
+static int selftest_emit_radiance(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const LightTable* t;
+    if (int r = selftest_textured_table(c, in[0], &t)) return r;
+    const uint32_t* rows = in + 1;
+    for (uint32_t i = 0; i < n; i++)  // the kernel indexes the table with the entry: nothing is launched that would read outside it
+        if (rows[3 * (size_t)i] >= t->n) return fail(c, RT3_E_INVALID, "selftest: emitter radiance row " + std::to_string(i) + " names an entry the light table does not have");
+    if (n == 0) return RT3_OK;
+    DevBuf<uint32_t> d_in, d_out;
+    HIPC(c, d_in.alloc_bytes((size_t)n * 12));
+    HIPC(c, d_out.alloc_bytes((size_t)n * 12));
+    HIPC(c, hipMemcpy(d_in.get(), rows, (size_t)n * 12, hipMemcpyHostToDevice));
+    launch_selftest_emit_radiance(c->stream, scene_dev(c), t->rec.get(), t->emit_tex.get(), d_in.get(), n, d_out.get());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpy(out, d_out.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
+    return RT3_OK;
+}
+// Self-test op 43: k_emit_tex on a caller-made emitter shadow queue of n slots over the built scene's light table.  in: the header {frame, B,
+// b, s0, dims, npix, workgroups, count, flags}, npix pixel words, n records {contribution rgb, path id}.  out: the n contributions after the
+// launch.  The queue's planes are one record longer than n and everything the kernel has no business writing carries a pattern.
+static int selftest_emit_tex_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const uint32_t npix = in[5], groups = in[6], count = in[7];
+    if (in[1] == 0 || in[1] > 64 || in[2] >= in[1] || npix == 0 || npix > (1u << 24) || groups == 0 || groups > 65535 || n > (1u << 24) || count > n ||
+        in[4] == 0 || in[4] > 8)
+        return fail(c, RT3_E_INVALID, "selftest: emitter queue header: bounces 1..64, bounce below them, dims 1..8, 1..2^24 pixels, 1..65535 workgroups, count <= n <= 2^24 records");
+    const LightTable* t;
+    if (int r = selftest_textured_table(c, in[8], &t)) return r;
+    if (t->total == 0u) return fail(c, RT3_E_STATE, "selftest: the light table has no power: nothing can be looked up");
+    const uint32_t* pix = in + kSelftestEmitTexHeader;
+    const uint32_t* rec = pix + npix;
+    constexpr uint32_t kGuard = 0xA5A5A5A5u;
+    const size_t S = (size_t)n + 1;  // one guard record per plane
+    std::vector<uint32_t> rays(8 * S, kGuard), contrib(2 * S, kGuard);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t* r = rec + kSelftestEmitTexRecord * i;
+        rays[4 * i + 3] = r[0];
+        rays[4 * (S + i) + 3] = r[1];
+        contrib[2 * i] = r[2];
+        contrib[2 * i + 1] = r[3];
+    }
+    DevBuf<float> d_rays, d_contrib;
+    DevBuf<uint32_t> d_pix, d_cnt;
+    HIPC(c, d_rays.alloc_bytes(8 * S * 4));
+    HIPC(c, d_contrib.alloc_bytes(2 * S * 4));
+    HIPC(c, d_pix.alloc_bytes((size_t)npix * 4));
+    HIPC(c, d_cnt.alloc_bytes(4));
+    HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_contrib.get(), contrib.data(), 2 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_pix.get(), pix, (size_t)npix * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_cnt.get(), &count, 4, hipMemcpyHostToDevice));
+    EmitTexLaunch a{};
+    a.sc = scene_dev(c); a.lights = t->dev(); a.emit_tex = t->emit_tex.get();
+    a.rays = d_rays.get(); a.contrib = d_contrib.get(); a.count = d_cnt.get(); a.stride = S;
+    a.pixels = d_pix.get(); a.npix = npix;
+    a.frame = in[0]; a.bounces = in[1]; a.bounce = in[2]; a.s0 = in[3]; a.dims = in[4];
+    launch_emit_tex(c->stream, a, count, groups);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> rays2(8 * S), contrib2(2 * S);
+    HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(contrib2.data(), d_contrib.get(), 2 * S * 4, hipMemcpyDeviceToHost));
+    for (size_t w = 0; w < 8 * S; w++) {  // of a ray record only the .w words of the n slots are the kernel's to write
+        const size_t slot = (w / 4) % S;
+        if (!(w % 4 == 3 && slot < n) && rays2[w] != rays[w]) return fail(c, RT3_E_STATE, "selftest: k_emit_tex wrote a ray's origin or direction, or behind the queue's end");
+    }
+    for (size_t w = 0; w < 2 * S; w++)
+        if (!(w % 2 == 0 && w / 2 < n) && contrib2[w] != contrib[w]) return fail(c, RT3_E_STATE, "selftest: k_emit_tex wrote a path id, or behind the queue's end");
+    for (size_t i = 0; i < n; i++) {
+        out[3 * i] = rays2[4 * i + 3];
+        out[3 * i + 1] = rays2[4 * (S + i) + 3];
+        out[3 * i + 2] = contrib2[2 * i];
+    }
+    return RT3_OK;
+}
+// Self-test op 44: k_emit_tex_power's mean texel of every entry of the table.  in: {flags}; n: the table's entries.  out: 3 words per entry.
+static int selftest_emit_mean(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const LightTable* t;
+    if (int r = selftest_textured_table(c, in[0], &t)) return r;
+    if (n != t->n) return fail(c, RT3_E_INVALID, "selftest: emitter mean: n must be the light table's entry count (" + std::to_string(t->n) + ")");
+    HIPC(c, hipMemcpy(out, t->emit_mean.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
+    return RT3_OK;
+}
+
 int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out) {
     uint32_t iw, ow;
+    if (op == 42 && c && in && out) return selftest_emit_radiance(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
+    if (op == 43 && c && in && out) return selftest_emit_tex_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
+    if (op == 44 && c && in && out) return selftest_emit_mean(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 40 && c && in && out) return selftest_light_table(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if ((op == 39 || op == 41) && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out), op == 41);
     if (op == 37 && c && in && out) return selftest_absorb_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));

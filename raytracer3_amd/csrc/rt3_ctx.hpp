@@ -158,6 +158,8 @@ struct rt3_ctx {
         // all that changes: the acceleration structure stays as it is
         std::vector<rt3_punctual_light> lights;
         uint64_t lights_stamp = 1;
+        // textured emitters (rt3_scene_set_textured_emitters): a mode of the light table alone, like the light list
+        bool textured_emitters = false;
         rt3::DevBuf<uint2> d_sky;  // 8-byte texels {RGB9E5, pdf_uv} in 4 x 4 tiles
         rt3::DevBuf<float> d_cdf_marg;
         rt3::DevBuf<uint32_t> d_sky_alias, d_guide_marg;
@@ -173,6 +175,7 @@ struct rt3_ctx {
         rt3::DevBuf<uint4> d_tex_table;
         rt3::DevBuf<float> d_srgb_lut;
         bool tex_dirty = false;
+        uint64_t tex_stamp = 1;  // bumped by every rt3_scene_set_texture: a textured emitter's mass depends on texels
         // generations: topo_gen is bumped by everything a tree's shape depends on (vertex count, indices, geometry, leaf size, layout,
         // collapse, SAH top); content_gen by all of that and by rt3_scene_update_vertices too.  A refit needs the topology of the build it
         // updates; the two-level structure keeps its bottom trees while the content is what they were built (or refitted) for

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rt3_camera.hpp"
+#include "rt3_emit_tex.hpp"
 #include "rt3_glass.hpp"
 #include "rt3_math.hpp"
 #include "rt3_surface.hpp"
@@ -503,6 +504,13 @@ struct LightTable {
     uint64_t stamp = 0;                       // the acceleration-structure stamp the table was built for (0 = none)
     uint64_t lights_stamp = 0;                // the punctual-light list it was built for (rt3_ctx::Scene::lights_stamp)
     uint32_t combo = 0;                       // flags & (RT3_F_NEE_EMISSIVE | RT3_F_NEE_PUNCTUAL) it was built for
+    // textured emitters (rt3_scene_set_textured_emitters): the mode and the texture pool (rt3_ctx::Scene::tex_stamp) the
+    // table was built for; textured: it holds an emitter with an emissive texture, and only then the side array (one entry per table entry)
+    // and k_emit_tex_power's mean texels (3 floats per entry) exist
+    bool tex_mode = false, textured = false;
+    uint64_t tex_stamp = 0;
+    DevBuf<EmitTexDev> emit_tex;
+    DevBuf<float> emit_mean;
     LightsDev dev() const {
         LightsDev d;
         d.rec = rec.get(); d.cdf = cdf.get(); d.guide = guide.get(); d.geom_base = geom_base.get();
@@ -516,7 +524,15 @@ struct LightTable {
 // cover, whose box gives the R of a directional light's mass (read only when there are punctual lights).
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
                         const std::vector<uint32_t>& eg_first, uint32_t n, LightTable* out, const float* punct = nullptr, uint32_t n_punct = 0,
-                        uint32_t n_world_prims = 0);
+                        uint32_t n_world_prims = 0, const SceneDev* textured = nullptr);
+// `textured` (above): the scene's tables when some listed emitter names an uploaded emissive texture (the atlas synchronised), else null.
+// k_emit_tex (rt3_emit_tex.hip) over the emitter shadow queue; rt3_emit_tex.hpp has the argument.  The grid is sized for
+// n_max records (an upper bound of *count), or is `groups` workgroups when that is not 0 (self-test op 43)
+void launch_emit_tex(hipStream_t st, const EmitTexLaunch& a, uint32_t n_max, uint32_t groups = 0);
+// self-test op 42: rows {table entry, b1, b2} -> the emitter-side radiance there, 3 words
+void launch_selftest_emit_radiance(hipStream_t st, const SceneDev& sc, const float4* rec, const EmitTexDev* emit_tex, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 43: k_emit_tex on a caller-made queue; header words, then the pixel words, then records of kSelftestEmitTexRecord words
+constexpr uint32_t kSelftestEmitTexHeader = 9, kSelftestEmitTexRecord = 4;
 // self-test op 40: the selection part of lights_build (weights, scan, CDF and p_sel / area, guide cells; the same function, scratch layout
 // and launch shapes) on n caller-made powers and areas, then light_find on n_k values of k.  Host arrays; max_power is the largest power.
 // out: {cells, shift, total}, cdf[n], the records' p_sel / area words [n], guide[cells + 1], n_k entries found.  Every device array is one

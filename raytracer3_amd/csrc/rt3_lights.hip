@@ -1,6 +1,8 @@
 // rt3_lights.hip -- the emitter table of RT3_F_NEE_EMISSIVE, built on the GPU from the flattened geometry tables.
 //
 //   k_emit_prims : emitter e -> its primitive, world triangle (fetch_triangle: flattening's own expression), area, normal, radiance, power
+//   k_emit_tex_power : only for a table with textured emitters: the side array, a textured emitter's power from the
+//                  quadrature of its texture, and the largest power over the emitters (k_emit_prims' then goes to a spare word)
 //   k_emit_max   : the largest power (ordered-uint atomicMax: the same answer whatever the order)
 //   k_emit_quant : power -> 64-bit integer weight on a 2^24 grid relative to the largest
 //   hipcub inclusive scan of the weights (integer: associative, so the same bits on every run, in both instance modes)
@@ -13,6 +15,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rt3_bvh_device.hpp"
+#include "rt3_emit_tex.hpp"
 #include "rt3_internal.hpp"
 #include "rt3_math.hpp"
 #include "rt3_punctual.hpp"
@@ -56,6 +59,60 @@ __global__ void k_emit_prims(const float* __restrict__ verts, const uint32_t* __
         area_out[e] = area;
         power[e] = p;
         atomicMax(max_power, __float_as_uint(p));  // non-negative floats order like their bits
+    }
+}
+
+// Textured emitters (rt3_scene_set_textured_emitters), behind k_emit_prims: entry e's side record, and for a textured
+// emitter the power area x luminance(Le (*) mean_rgb) in place of k_emit_prims' area x luminance(Le).  mean_rgb is the quadrature rt3.h
+// states.  One wave per entry: lane l takes centroids l, l + 64, ... in rising order and adds their texels up in that order; the 64 lane
+// sums meet in a butterfly (xor 32, 16, .. 1), whose additions commute pairwise, so every lane ends with the same bits on every run.  The
+// largest power of the emitters is taken here (k_emit_prims saw the untextured values).  mean: 3 floats per entry, 1 1 1 without texture.
+__global__ __launch_bounds__(256) void k_emit_tex_power(SceneDev sc, const uint32_t* __restrict__ prim_in, const float* __restrict__ area,
+                                                        const float4* __restrict__ rec, uint32_t n_emit, uint32_t n, EmitTexDev* __restrict__ emit_tex,
+                                                        float* __restrict__ mean, float* __restrict__ power, uint32_t* __restrict__ max_power) {
+    const uint32_t lane = threadIdx.x & 63u, waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; e < n; e += waves) {  // (uniform per wave)
+        EmitTexDev t;
+        t.uv[0] = t.uv[1] = t.uv[2] = make_float2(0.0f, 0.0f);
+        t.tex = -1;
+        t.pad = 0u;
+        if (e < n_emit) {
+            const uint32_t prim = prim_in[e];
+            const int32_t et = sc.mat_tex[sc.prim_geom[prim]].emissive_tex;
+            if (et > -1 && (uint32_t)et < sc.n_tex) {  // hit_finish<true>'s has_e
+                t.tex = et;
+                for (int k = 0; k < 3; k++) t.uv[k] = sc.tri_uv[3 * (size_t)prim + k];
+            }
+        }
+        V3 m = v3(1.0f, 1.0f, 1.0f);
+        if (t.tex >= 0) {
+            const uint4 tt = sc.tex_table[t.tex];
+            const uint32_t L = emit_tex_subdiv(t, tt.y, tt.z), L2 = L * L;
+            V3 s = v3(0.0f, 0.0f, 0.0f);
+            for (uint32_t k = lane; k < L2; k += 64u) {
+                float b1, b2;
+                emit_tex_centroid(L, k, b1, b2);
+                const V3 c = emit_tex_rgb(sc, t, b1, b2);
+                s = v3(s.x + c.x, s.y + c.y, s.z + c.z);
+            }
+            for (int w = 32; w >= 1; w >>= 1) s = v3(s.x + __shfl_xor(s.x, w), s.y + __shfl_xor(s.y, w), s.z + __shfl_xor(s.z, w));
+            const float d = (float)L2;
+            m = v3(s.x / d, s.y / d, s.z / d);
+        }
+        if (lane == 0u) {
+            emit_tex[e] = t;
+            mean[3 * (size_t)e] = m.x; mean[3 * (size_t)e + 1] = m.y; mean[3 * (size_t)e + 2] = m.z;
+            if (e < n_emit) {
+                float p = power[e];
+                if (t.tex >= 0) {
+                    const V3 le = v3(rec[4 * (size_t)e + 1].w * m.x, rec[4 * (size_t)e + 2].w * m.y, rec[4 * (size_t)e + 3].w * m.z);
+                    p = area[e] * luminance(le);
+                    p = (p > 0.0f && p <= kFloatMax) ? p : 0.0f;  // the quadrature found nothing: never sampled
+                    power[e] = p;
+                }
+                atomicMax(max_power, __float_as_uint(p));
+            }
+        }
     }
 }
 
@@ -232,9 +289,12 @@ static hipError_t select_build(hipStream_t st, const SelectScratch& s, const flo
 }
 
 hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t>& geom_base, const std::vector<uint32_t>& eg_geom,
-                        const std::vector<uint32_t>& eg_first, uint32_t n_emit, LightTable* out, const float* punct, uint32_t n_punct, uint32_t n_world_prims) {
+                        const std::vector<uint32_t>& eg_first, uint32_t n_emit, LightTable* out, const float* punct, uint32_t n_punct, uint32_t n_world_prims, const SceneDev* textured) {
     out->stamp = 0;
     out->n = out->total = out->n_emit = out->n_punct = 0;
+    out->textured = false;
+    out->emit_tex.reset();
+    out->emit_mean.reset();
     const size_t ng = geom_base.size(), neg = eg_geom.size();
     // per flattened geometry its first emitter, then the emissive geometries' {flattened index, first emitter}: a few KiB at most
     std::vector<uint32_t> small(ng + 2 * neg);
@@ -263,6 +323,14 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     BufLayout plan;
     RT3_TRY(select_plan(st, n, plan, &sel));
     plan.add(&punct_in, 4 * (size_t)n_punct).add(&bounds, 6);
+    // textured emitters: k_emit_prims' largest power goes to a spare word, k_emit_tex_power takes the emitters' largest
+    uint32_t* spare_max = nullptr;
+    const bool tex = textured != nullptr && n_emit != 0u;
+    if (tex) {
+        plan.add(&spare_max, 1);
+        RT3_TRY(alloc_n(out->emit_tex, n));
+        RT3_TRY(alloc_n(out->emit_mean, 3 * (size_t)n));
+    }
     RT3_TRY(out->scratch.grow_bytes(plan.bytes()));
     RT3_TRY(plan.carve(out->scratch));
     const uint32_t* d_eg_geom = out->geom_base.get() + ng;
@@ -270,7 +338,12 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     RT3_TRY(hipMemsetAsync(sel.max_power, 0, 4, st));
     if (n_emit)
         hipLaunchKernelGGL(k_emit_prims, dim3(grid_of(n_emit)), dim3(256), 0, st, t.verts, t.indices, t.geoms, t.prim_geom, t.first_prim, d_eg_geom, d_eg_first, (uint32_t)neg,
-                           n_emit, out->rec.get(), out->prim.get(), out->area.get(), sel.power, sel.max_power);
+                           n_emit, out->rec.get(), out->prim.get(), out->area.get(), sel.power, tex ? spare_max : sel.max_power);
+    if (tex) {  // one wave per entry, the punctual lights' (no texture) included
+        const uint64_t blocks = ((uint64_t)n + 3) / 4;  // four waves each
+        hipLaunchKernelGGL(k_emit_tex_power, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, *textured, out->prim.get(), out->area.get(), out->rec.get(),
+                           n_emit, n, out->emit_tex.get(), out->emit_mean.get(), sel.power, sel.max_power);
+    }
     if (n_punct) {
         RT3_TRY(hipMemcpyAsync(punct_in, punct, 64 * (size_t)n_punct, hipMemcpyHostToDevice, st));
         RT3_TRY(hipMemsetAsync(bounds, 0xFF, 12, st));  // min: beyond every ordered float; max: 0 = below every one
@@ -290,6 +363,7 @@ hipError_t lights_build(hipStream_t st, GeomTables t, const std::vector<uint32_t
     out->n_guide = cells;
     out->guide_shift = shift;
     out->total = total;
+    out->textured = tex;
     return hipSuccess;
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "rt3_ctx.hpp"
+#include "rt3_emit_tex.hpp"
 #include "rt3_roulette.hpp"
 #include "rt3_volume.hpp"
 
@@ -263,6 +264,9 @@ struct PathSetup {
     SceneDev sc;
     LightsDev lights{};
     bool nee = false, nee_e = false, punct = false;
+    // textured emitters (rt3_scene_set_textured_emitters): the table's side array, null unless it holds a textured
+    // emitter -- k_emit_tex
+    const EmitTexDev* emit_tex = nullptr;
     // RT3_OPT_DEFER_SKY_LIGHT: k_shade_defer, k_shadow in its reporting mode, k_light.  Only inside their cover: sky NEE
     // on; no glass, punctual record or material table; every sky texel's density large enough that a sample's pdf cannot round to 0
     bool defer = false;
@@ -311,6 +315,7 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
             if (int r = ensure_emit_queue(c)) return r;
     }
     ps->nee_e = ps->lights.n != 0u;
+    ps->emit_tex = ps->nee_e && c->accel.lights.textured ? c->accel.lights.emit_tex.get() : nullptr;
     ps->sc = scene_dev(c);
     ps->defer = c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
     {
@@ -458,6 +463,17 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             // half of the ray pair k_shade_defer read) and before k_extend (which overwrites the hit queue)
             ScopedTimer t(c, CAT_SHADE);
             launch_light(c->stream, bn == 0 && !lens, L);
+        }
+        if (nee_e && bn + 1 < B && ps.emit_tex != nullptr) {
+            // the queued emitter samples' contributions carry Le = the factor: those on a textured emitter take their texel here, before
+            // the walk adds them in
+            EmitTexLaunch E{};
+            E.sc = ps.sc; E.lights = ps.lights; E.emit_tex = ps.emit_tex;
+            E.rays = c->work.sh2_rays.get(); E.contrib = c->work.sh2_contrib.get(); E.count = emit_cnt + bn; E.stride = S;
+            E.pixels = pixels; E.npix = npix; E.s0 = s0; E.bounces = B; E.bounce = bn; E.frame = ps.gd.frame; E.dims = ps.gd.pad[0] ? 8u : 2u;
+            ScopedTimer t(c, CAT_OTHER);
+            launch_emit_tex(c->stream, E, n_first);
+            c->prof.stats.emit_tex_launches++;
         }
         if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
             TraceLaunch tr = ctx_trace(c);

@@ -508,6 +508,7 @@ int rt3_scene_set_texture(rt3_ctx* c, uint32_t index, const uint8_t* rgba, uint3
     c->scene.tex_w[index] = w;
     c->scene.tex_h[index] = h;
     c->scene.tex_dirty = true;
+    c->scene.tex_stamp++;
     return RT3_OK;
 }
 int rt3_sky_download(rt3_ctx* c, uint32_t* alias, uint32_t* texels, float* marg, float* pdf) {
@@ -577,6 +578,18 @@ int rt3_scene_set_lights(rt3_ctx* c, const rt3_punctual_light* lights, uint32_t 
     c->scene.lights.assign(lights, lights + n);
     for (rt3_punctual_light& l : c->scene.lights) l._pad0 = l._pad1 = l._pad2 = 0.0f;
     c->scene.lights_stamp++;
+    return RT3_OK;
+}
+// Textured emitters: no build reads the mode and the structure stays as it is; the light table's key holds it
+int rt3_scene_set_textured_emitters(rt3_ctx* c, int on) {
+    if (!c) return RT3_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, RT3_E_INVALID, "textured emitters: the mode is 0 or 1");
+    c->scene.textured_emitters = on != 0;
+    return RT3_OK;
+}
+int rt3_scene_get_textured_emitters(rt3_ctx* c, int* on) {
+    if (!c || !on) return fail(c, RT3_E_INVALID, "textured emitters: NULL");
+    *on = c->scene.textured_emitters ? 1 : 0;
     return RT3_OK;
 }
 

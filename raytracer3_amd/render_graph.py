@@ -311,6 +311,63 @@ class Context:
                                                 C.byref(cells), C.byref(shift)))
         return rec, cdf, guide, prim, area, cells.value, shift.value
 
+    def set_textured_emitters(self, on=True):
+        """textured emitters (rt3_scene_set_textured_emitters): F_NEE_EMISSIVE also samples the geometries whose
+        emission carries an emissive texture.  A mode of the light table alone: no rebuild is needed, the next frame sees it."""
+        self.check(self.lib.rt3_scene_set_textured_emitters(self.h, int(on)))
+
+    def get_textured_emitters(self):
+        on = C.c_int32(0)
+        self.check(self.lib.rt3_scene_get_textured_emitters(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def light_emit_tex(self, flags):
+        """the side array of the light table that `flags` samples (rt3_light_emit_tex): (uv (n, 3, 2) float32, emissive texture index (n,)
+        int32, -1 = none), entries in light_masses' order; empty arrays when the table holds no textured emitter"""
+        n = C.c_uint32()
+        self.check(self.lib.rt3_light_emit_tex(self.h, int(flags), C.byref(n), None))
+        out = np.zeros((n.value, 8), np.uint32)
+        if n.value:
+            self.check(self.lib.rt3_light_emit_tex(self.h, int(flags), C.byref(n), out.ctypes.data))
+        return out[:, :6].copy().view(np.float32).reshape(-1, 3, 2), out[:, 6].copy().view(np.int32)
+
+    def selftest_emit_radiance(self, flags, entries, b1, b2):
+        """Self-test op 42: the emitter-side radiance Le (*) emissive texture of the table entries `entries` at barycentrics
+        (1 - b1 - b2, b1, b2), over the light table `flags` samples.  Returns (n, 3) float32."""
+        entries = np.ascontiguousarray(entries, np.uint32).reshape(-1)
+        n = len(entries)
+        rows = np.zeros((n, 3), np.uint32)
+        rows[:, 0] = entries
+        rows[:, 1] = np.ascontiguousarray(b1, np.float32).reshape(-1).view(np.uint32)
+        rows[:, 2] = np.ascontiguousarray(b2, np.float32).reshape(-1).view(np.uint32)
+        inp = np.concatenate([np.array([flags], np.uint32), rows.reshape(-1)])
+        out = np.zeros((max(n, 1), 3), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_EMIT_RADIANCE, inp.ctypes.data, n, out.ctypes.data))
+        return out[:n].view(np.float32)
+
+    def selftest_emit_tex_queue(self, flags, frame, bounces, bounce, s0, dims, pixels, records, groups, count=None):
+        """Self-test op 43: k_emit_tex on the emitter shadow queue `records` (n, 4) of 32-bit words {contribution r, g, b, path id}, whose
+        length word says `count` (n without), launched with `groups` workgroups over the pixel words `pixels` and the light table `flags`
+        samples.  Returns the contributions (n, 3) uint32 afterwards.  The library fails the call when the kernel wrote anything else."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 4)
+        n = len(records)
+        head = np.array([frame, bounces, bounce, s0, dims, len(pixels), groups, n if count is None else count, flags], np.uint32)
+        inp = np.concatenate([head, pixels, records.reshape(-1)])
+        out = np.zeros(3 * max(n, 1), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_EMIT_TEX_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return out[: 3 * n].reshape(n, 3)
+
+    def selftest_emit_mean(self, flags):
+        """Self-test op 44: the mean texel (n, 3) float32 k_emit_tex_power found for every entry of the light table `flags` samples
+        (1 1 1 for an entry without texture)"""
+        ne, npu, _ = self.light_masses(flags)
+        n = ne + npu
+        out = np.zeros((max(n, 1), 3), np.float32)
+        inp = np.array([flags], np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_EMIT_MEAN, inp.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
     def selftest_light_table(self, power, area, k=()):
         """Self-test op 40: the light table's quantise, scan, CDF and guide kernels on the float32 powers and areas of n lights (the launch
         shapes and scratch layout of the context's own table), then light_find on the values `k` (< 2^23).  Returns (cells, shift, total,

@@ -491,6 +491,13 @@ class PathTracer:
         else:
             self.ctx.set_roulette(L.RouletteParams(start_bounce, min_survival))
 
+    def set_textured_emitters(self, on=True):
+        """Textured emitters for the frames that follow (ctx.set_textured_emitters): under F_NEE_EMISSIVE the light
+        sampler also picks the triangles whose emission is a factor times an emissive texture (lamps, screens, signs of a glTF asset),
+        which are otherwise found by BSDF-sampled rays alone.  Same expectation, less noise where such emitters are small.  Off by
+        default; no rebuild is needed."""
+        self.ctx.set_textured_emitters(bool(on))
+
     def roulette_info(self):
         """(extension rays tested, of them ended) of the last frame's path-tracing launch"""
         return self.ctx.roulette_info()

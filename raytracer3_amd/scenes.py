@@ -519,6 +519,43 @@ def material_cornell(seed: int = MATERIAL_SEED) -> Mesh:
     return mesh
 
 
+NEON_ROOM_CAMERA = dict(position=(0.6, 1.3, 1.7), direction=(-0.25, -0.05, -1.0), fov_deg=65.0)
+
+
+def neon_sign_texture() -> np.ndarray:
+    """64 x 16 RGBA8: black, with a few bright strokes (two bars, a rule and a dot).  Columns 0 .. 16 stay black."""
+    t = np.zeros((16, 64, 4), np.uint8)
+    t[..., 3] = 255
+    t[2:14, 20:23, :3] = (255, 255, 255)
+    t[2:14, 25:28, :3] = (255, 200, 255)
+    t[7:9, 36:60, :3] = (255, 255, 230)
+    t[11:13, 44:46, :3] = (200, 255, 255)
+    return np.ascontiguousarray(t)
+
+
+def neon_room() -> Mesh:
+    """A closed 4 x 3 x 4 m room lit only by a thin sign on its back wall: the sign's emission is a factor times an
+    emissive texture that is mostly black (neon_sign_texture), and its uvs run from -0.5 to 1.5, so the texture repeats twice along it.  Two
+    boxes stand on the floor.  Without rt3_scene_set_textured_emitters only BSDF-sampled rays find the strokes."""
+    mb = MeshBuilder()
+    grey = Material((0.7, 0.7, 0.7))
+    mb.add("floor", *_grid([-2, 0, 2], [4, 0, 0], [0, 0, -4], 4, 4), Material((0.6, 0.55, 0.5)))
+    mb.add("ceiling", *_grid([-2, 3, -2], [4, 0, 0], [0, 0, 4], 2, 2), grey)
+    mb.add("back", *_grid([-2, 0, -2], [4, 0, 0], [0, 3, 0], 2, 2), grey)
+    mb.add("front", *_grid([2, 0, 2], [-4, 0, 0], [0, 3, 0], 2, 2), grey)
+    mb.add("left", *_grid([-2, 0, 2], [0, 0, -4], [0, 3, 0], 2, 2), Material((0.65, 0.3, 0.3)))
+    mb.add("right", *_grid([2, 0, -2], [0, 0, 4], [0, 3, 0], 2, 2), Material((0.3, 0.4, 0.65)))
+    _box(mb, "box0", [-1.3, 0.0, -1.1], [-0.5, 1.0, -0.3], Material((0.8, 0.8, 0.75)))
+    _box(mb, "box1", [0.4, 0.0, -0.3], [1.2, 0.5, 0.6], Material((0.75, 0.8, 0.8)))
+    pos, nrm, uv, tris = _grid([-1.0, 1.9, -1.98], [2.0, 0, 0], [0, 0.3, 0], 8, 1)
+    uv = uv.copy()
+    uv[:, 0] = uv[:, 0] * 2.0 - 0.5
+    mb.add("sign", pos, nrm, uv, tris, Material((0.1, 0.1, 0.1), emission=(8.0, 2.0, 6.0), emissive_texture=0))
+    mesh = mb.build()
+    mesh.textures = [neon_sign_texture()]
+    return mesh
+
+
 def sky(width: int = 2048, height: int = 1024, seed: int = SKY_SEED) -> np.ndarray:
     """Equirect RGB32F sky: horizon-to-zenith gradient, ground bounce, soft cloud noise, 0.5 degree sun (5e4)."""
     rng = np.random.default_rng(seed)

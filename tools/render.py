@@ -23,6 +23,8 @@
                          (--guide: the a-trous filter guided by the lens frame's own camera samples)
   python tools/render.py --scene glass_cornell --size 1920x1080 --spp 1 --bounces 8 --temporal 16 --denoise --guide --out glass_1spp_temporal.png
                          (--temporal with --guide: the "temporal" pass takes its surface records from the guide images too, section 4v)
+  python tools/render.py --scene material_cornell --size 960x540 --spp 64 --flags 47 --textured-emitters --out material_cornell_nee.png
+                         (flags 47 = the full estimator + RT3_F_NEE_EMISSIVE: the panel's lamps are sampled directly)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -40,7 +42,7 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell", "frosted_cornell"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell", "frosted_cornell", "neon_room"])
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -68,6 +70,8 @@ def main():
     ap.add_argument("--roulette", nargs="?", type=int, const=2, default=None, metavar="START",
                     help="Russian roulette on the extension rays from vertex START on (default 2), survival floor 1/16 (DESIGN.md section 4o)")
     ap.add_argument("--pane-shadows", action="store_true", help="sample lights through thin-walled glass (PathTracer.set_pane_shadows, DESIGN.md section 4q)")
+    ap.add_argument("--textured-emitters", action="store_true",
+                    help="sample emitters whose emission carries an emissive texture (PathTracer.set_textured_emitters, DESIGN.md section 4x); needs RT3_F_NEE_EMISSIVE (32) in --flags")
     ap.add_argument("--rough-glass", action="store_true", help="frosted glass: rough transmission on glass with roughness > 0 (PathTracer.set_rough_transmission, DESIGN.md section 4t)")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
     ap.add_argument("--side-by-side", default=None, help="with --compare: write [render | reference] at the reference's size here")
@@ -99,6 +103,8 @@ def main():
         mesh, cam_kw = scenes.amber_cornell(), scenes.CORNELL_CAMERA
     elif args.scene == "sunlit_room":  # a closed room lit through one window by the sky and a sun; try --pane-shadows
         mesh, cam_kw = scenes.sunlit_room(), scenes.SUNLIT_ROOM_CAMERA
+    elif args.scene == "neon_room":  # a room lit only by a sign whose emissive texture is mostly black; try --textured-emitters
+        mesh, cam_kw = scenes.neon_room(), scenes.NEON_ROOM_CAMERA
     elif args.scene == "cornell_ref":
         mesh, cam_kw = scenes.cornell_ref(), scenes.CORNELL_REF_CAMERA
     else:
@@ -112,6 +118,7 @@ def main():
     pt = PathTracer((W, H))
     pt.set_pane_shadows(args.pane_shadows)
     pt.set_rough_transmission(args.rough_glass)
+    pt.set_textured_emitters(args.textured_emitters)
     pt.set_scene(mesh, sky, assets.load_bluenoise())
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
