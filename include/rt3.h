@@ -533,6 +533,38 @@ int rt3_light_table(rt3_ctx *ctx, uint32_t flags, float *rec /* 16 per entry */,
 int rt3_scene_set_textured_emitters(rt3_ctx *ctx, int on);
 int rt3_scene_get_textured_emitters(rt3_ctx *ctx, int *on);
 int rt3_light_emit_tex(rt3_ctx *ctx, uint32_t flags, uint32_t *n_entries, void *out /* 8 words per entry, may be NULL */);
+
+/* ---- fog (no reference equivalent): one axis-aligned box of homogeneous medium with single scattering.  Off by
+ * default; with it off every frame keeps its bits and nothing more is launched.  "refrence_mode" and "adaptive" read it.
+ *   rt3_scene_set_medium(ctx, m): sigma_a and sigma_s are the absorption and scattering coefficients per colour channel (per world unit),
+ * g the Henyey-Greenstein asymmetry, box_min / box_max the box.  NULL switches the medium off.  RT3_E_INVALID, and nothing changes, for a
+ * sigma that is negative or not finite, |g| >= 1 or a g that is not finite, a box coordinate that is not finite, or box_min.k >= box_max.k
+ * on some axis.  A medium whose sigma_a + sigma_s is 0 in every channel is stored and counts as off.  The call leaves the acceleration
+ * structure and the light table as they are; rt3_scene_set_geometry leaves the medium as it is.
+ *   The rule (csrc/rt3_fog.hpp states it once): every traced path segment o + s d, s in [0, t] (t = +inf on a miss) is cut by the box's
+ * slabs to [t0, t1]; the throughput takes exp(-sigma_t (t1 - t0) |d|) per channel, sigma_t = sigma_a + sigma_s.  When some sigma_s > 0 and the
+ * frame samples lights, one point of the segment is drawn (density proportional to exp(-mean(sigma_t) s)) and lit by one sky sample
+ * (RT3_F_NEE_SKY with a sky) and one sample of the light table (RT3_F_NEE_EMISSIVE / RT3_F_NEE_PUNCTUAL, bounces >= 2), each a shadow ray
+ * with the phase function and the transmittance towards the light in its contribution; and the shadow rays of surface vertices have their
+ * contribution multiplied by the transmittance along them.  Light scattered out of a ray is lost (no multiple scattering): dense fog with
+ * a high albedo renders too dark.
+ *   Launches: a medium needs per-sample camera rays (rt3_camera_set_lens; {0, f, 0} is the per-sample pinhole): "refrence_mode" without a
+ * lens is RT3_E_STATE, "adaptive" takes it in coverage mode (rt3_adaptive_set_coverage) and is RT3_E_STATE otherwise; a launch with
+ * samples * bounces * 8 > 2^28 is RT3_E_INVALID (the fog draws' RNG indices start at 0x70000000 and end where the camera's start).
+ * RT3_OPT_DEFER_SKY_LIGHT and RT3_OPT_SHADE_EXIT_TEST do not apply to a frame with a medium.  "gbuffer", "denoise", "temporal", "motion",
+ * the guide images and the probe passes do not see the medium.
+ *   rt3_medium_info (either pointer may be NULL; synchronises the stream): of the last "refrence_mode" or "adaptive" launch, the traced
+ * segments that ran through the medium and the in-scatter shadow rays queued for them. */
+typedef struct rt3_medium {
+    float sigma_a[3];
+    float sigma_s[3];
+    float g;
+    float box_min[3];
+    float box_max[3];
+} rt3_medium;           /* 52 bytes */
+int rt3_scene_set_medium(rt3_ctx *ctx, const rt3_medium *m);   /* NULL: off, the default */
+int rt3_scene_get_medium(rt3_ctx *ctx, rt3_medium *out, int *enabled);
+int rt3_medium_info(rt3_ctx *ctx, uint64_t *segments, uint64_t *inscatter_rays);  /* of the last launch; synchronises */
 /* sky tables for parity tests (any pointer may be NULL): per-row alias words q16 | alias << 16 (w*h), RGB9E5 texels (w*h),
  * marginal CDF (h), realised (u,v) density (w*h) */
 int rt3_sky_download(rt3_ctx *ctx, uint32_t *alias, uint32_t *texels_rgb9e5, float *cdf_marg, float *pdf_uv);
@@ -988,6 +1020,19 @@ int rt3_trace_rays(rt3_ctx *ctx, const float *rays, uint32_t n, int any_hit, flo
  *      direction, a path id or a word behind the end.  Slots at and behind `count` must come back as they went in.
  *      44 the mean texel k_emit_tex_power found for every entry of the table (1 1 1 for an entry without texture).  in: {flags}; n = the table's
  *      entries.  out: 3 words per entry.
+ *      45 the fog rule (rt3_scene_set_medium; reads no context state): rows {o xyz, d xyz, t, box_min xyz, box_max xyz, sigma_a rgb, sigma_s
+ *      rgb, u} -> {1 when the segment runs through the box, t0, t1, s of the drawn point, its density per unit length, the segment's
+ *      transmittance rgb} (zeros behind a 0).
+ *      46 k_fog_segment or k_fog_shadow themselves on caller-made queues of n records, with the context's medium (RT3_E_STATE without one)
+ *      over the built scene.  in: the header {kind, workgroups to launch (1 .. 65535), flags, frame, bounces, segment, s0, npix, attenuate
+ *      the radiance of missed records (0 / 1)}, then npix pixel words x | y << 16, then the records.  kind 0, k_fog_segment: records
+ *      {o xyz, d xyz, t, prim (0xFFFFFFFF: a miss), T rgb, path id < max(n, 1), each once}; the sky sample is on with RT3_F_NEE_SKY in `flags`
+ *      and a sky, the light table is the one `flags` and `bounces` give a frame.  out: {length of queue 0, of queue 1, segments in the
+ *      medium, rays queued}, 3 n words T', 4 n words of radiance slots (path id p starts as {1, 1, 1, 0}), then for each queue n slots of 12
+ *      words {x, c.r, w_l, c.g, c.b, path id, tmax, 0} (a slot behind the length holds the pattern).  kind 1 / 2, k_fog_shadow on a queue
+ *      without / with range ends: records {o xyz, c.r, d xyz, c.g, c.b, path id, tmax}; out: 3 words per record, the contributions after
+ *      the launch.  Queues are one record longer than n and filled with a pattern: RT3_E_STATE when a kernel wrote behind an end or changed
+ *      a word that is not its to change.
  *      in/out: host arrays of 32-bit words. ---- */
 int rt3_selftest_eval(rt3_ctx *ctx, int op, const void *in, uint32_t n, void *out);
 

@@ -46,6 +46,8 @@ SELFTEST_GUIDE_PREV_QUEUE = 41  # rt3_selftest_eval op: k_lens_guide_prev on cal
 SELFTEST_EMIT_RADIANCE = 42  # rt3_selftest_eval op: {flags}, rows {table entry, b1, b2} -> the emitter-side radiance Le (*) texture (3 words) (Context.selftest_emit_radiance)
 SELFTEST_EMIT_TEX_QUEUE = 43  # rt3_selftest_eval op: k_emit_tex on a caller-made emitter shadow queue over the built scene's light table (Context.selftest_emit_tex_queue)
 SELFTEST_EMIT_MEAN = 44  # rt3_selftest_eval op: the mean texel of every light-table entry, as k_emit_tex_power found it (Context.selftest_emit_mean)
+SELFTEST_FOG = 45  # rt3_selftest_eval op: {o, d, t, box_min, box_max, sigma_a, sigma_s, u} (20 words) -> {in medium (u32), t0, t1, s, pdf, Tr rgb} (8), the fog rule
+SELFTEST_FOG_QUEUE = 46  # rt3_selftest_eval op: k_fog_segment / k_fog_shadow on caller-made queues with the context's medium (Context.selftest_fog_segment, selftest_fog_shadow)
 SELFTEST_LIGHT_TABLE = 40  # rt3_selftest_eval op: the light table's quantise / scan / CDF / guide kernels and light_find on caller-made powers (Context.selftest_light_table)
 
 EXPORTS = [
@@ -71,6 +73,7 @@ EXPORTS = [
     "rt3_path_set_roulette", "rt3_path_get_roulette", "rt3_path_roulette_info",
     "rt3_scene_set_lights", "rt3_light_masses", "rt3_light_table",
     "rt3_scene_set_textured_emitters", "rt3_scene_get_textured_emitters", "rt3_light_emit_tex",
+    "rt3_scene_set_medium", "rt3_scene_get_medium", "rt3_medium_info",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
@@ -159,6 +162,20 @@ class RouletteParams(C.Structure):
         super().__init__(start_bounce, min_survival, (C.c_uint32 * 2)(*reserved))
 
 
+class Medium(C.Structure):
+    """rt3_medium: one axis-aligned box of homogeneous medium with single scattering: absorption and scattering
+    coefficients per colour channel and world unit, the Henyey-Greenstein asymmetry g in (-1, 1), and the box."""
+
+    _fields_ = [("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3), ("g", C.c_float), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3)]
+
+    def __init__(self, sigma_a=(0.0, 0.0, 0.0), sigma_s=(0.0, 0.0, 0.0), g=0.0, box_min=(-1.0, -1.0, -1.0), box_max=(1.0, 1.0, 1.0)):
+        def three(v):
+            v = (v, v, v) if isinstance(v, (int, float)) else tuple(v)
+            return (C.c_float * 3)(*[float(x) for x in v])
+        super().__init__(three(sigma_a), three(sigma_s), float(g), three(box_min), three(box_max))
+
+
+assert C.sizeof(Medium) == 52
 assert C.sizeof(GConst) == 304
 
 
@@ -282,6 +299,9 @@ def load():
         "rt3_path_set_roulette": (i32, [vp, C.POINTER(RouletteParams)]),
         "rt3_path_get_roulette": (i32, [vp, C.POINTER(RouletteParams), C.POINTER(i32)]),
         "rt3_path_roulette_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "rt3_scene_set_medium": (i32, [vp, vp]),
+        "rt3_scene_get_medium": (i32, [vp, vp, C.POINTER(C.c_int)]),
+        "rt3_medium_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),
         "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),

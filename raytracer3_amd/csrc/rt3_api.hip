@@ -753,6 +753,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
     uint32_t iw, ow;
     if (op == 42 && c && in && out) return selftest_emit_radiance(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 43 && c && in && out) return selftest_emit_tex_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
+    if (op == 46 && c && in && out) return selftest_fog_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 44 && c && in && out) return selftest_emit_mean(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if (op == 40 && c && in && out) return selftest_light_table(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out));
     if ((op == 39 || op == 41) && c && in && out) return selftest_guide_queue(c, static_cast<const uint32_t*>(in), n, static_cast<uint32_t*>(out), op == 41);
@@ -793,6 +794,7 @@ int rt3_selftest_eval(rt3_ctx* c, int op, const void* in, uint32_t n, void* out)
         else if (op == 32) launch_selftest_glass(c->stream, d_in.get(), n, d_out.get());
         else if (op == 33) launch_selftest_roulette(c->stream, d_in.get(), n, d_out.get());
         else if (op == 36) launch_selftest_absorb(c->stream, d_in.get(), n, d_out.get());
+        else if (op == 45) launch_selftest_fog(c->stream, d_in.get(), n, d_out.get());
         else if (op == 38) launch_selftest_frost(c->stream, d_in.get(), n, d_out.get());
         else launch_selftest(c->stream, op, scene_dev(c), d_in.get(), n, d_out.get());
         e = hipStreamSynchronize(c->stream);

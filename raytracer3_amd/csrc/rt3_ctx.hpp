@@ -318,6 +318,16 @@ struct rt3_ctx {
     // rt3_scene.hip: rough transmission (rt3_scene_set_rough_transmission): the mode, read by the next rt3_accel_build; off
     // by default; like pane_shadows it is not part of `scene`
     bool rough_transmission = false;
+    // rt3_scene.hip: fog (rt3_scene_set_medium): the medium as validated; `on`: set, and some sigma_a + sigma_s > 0.  Not
+    // part of `scene`: rt3_scene_set_geometry leaves it as it is.  rt3_passes.hip owns the rest: the two in-scatter shadow queues (as large
+    // as the other queues, allocated while a medium is on, freed by the first launch without one) and the device words of rt3_medium_info
+    struct Medium {
+        rt3_medium params = {};
+        bool set = false, on = false;
+        rt3::DevBuf<float> q_rays[2], q_contrib[2], q_tmax[2];
+        size_t cap = 0;
+        rt3::DevBuf<unsigned long long> d_info;  // {segments, in-scatter rays} of the last launch
+    } medium;
     // rt3_scene.hip: deformation: the snapshot of rt3_scene_snapshot_vertices, one {x, y, z, 0} per vertex; the vertex
     // ranges rt3_scene_update_vertices touched since it, sorted and merged; and, once deform_flags has run, per uploaded geometry whether
     // some position word inside its span differs from the snapshot
@@ -451,6 +461,8 @@ void motion_tables_stale(rt3_ctx* c);  // the previous transforms or the deforme
 // motion_tables for the built structure (its refusals; it may synchronise the stream), then the tables as a kernel follows them: geom_slot
 // null when nothing moved, *prev_pos null when nothing is deformed
 int motion_launch_tables(rt3_ctx* c, MotionDev* m, const float4** prev_pos);
+// self-test op 46 (include/rt3.h): k_fog_segment / k_fog_shadow on caller-made queues, with the light setup of a frame
+int selftest_fog_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out);
 
 // ---- rt3_tiles.hip
 int get_pixlist(rt3_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks, PixelList** out);

@@ -190,6 +190,17 @@ constexpr uint32_t kSelftestAbsorbIn = 13, kSelftestAbsorbOut = 4;
 void launch_selftest_absorb(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
 // self-test op 37: k_absorb on a caller-made queue; one header word, then records of kSelftestAbsorbRecord words, three words out per record
 constexpr uint32_t kSelftestAbsorbHeader = 1, kSelftestAbsorbRecord = 10;
+// Fog (rt3_fog.hip); rt3_fog.hpp has the rule and the arguments.  The grids are sized for n_max records (an upper bound
+// of *count), or are `groups` workgroups when that is not 0 (self-test op 46)
+struct FogSegmentLaunch;
+struct FogShadowLaunch;
+void launch_fog_segment(hipStream_t st, const FogSegmentLaunch& a, uint32_t n_max, uint32_t groups = 0);
+void launch_fog_shadow(hipStream_t st, const FogShadowLaunch& a, uint32_t n_max, uint32_t groups = 0);
+// self-test op 45: the fog rule, {o xyz, d xyz, t, lo xyz, hi xyz, sigma_a rgb, sigma_s rgb, u} -> {in medium, t0, t1, s, pdf, Tr rgb}
+constexpr uint32_t kSelftestFogIn = 20, kSelftestFogOut = 8;
+void launch_selftest_fog(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out);
+// self-test op 46: k_fog_segment or k_fog_shadow on caller-made queues (rt3_passes.hip: selftest_fog_queue has the layout)
+constexpr uint32_t kSelftestFogQueueHeader = 9, kSelftestFogSegmentRecord = 12, kSelftestFogShadowRecord = 11, kSelftestFogRayOut = 12;
 void launch_pack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* img, void* dst);
 void launch_unpack_tiles(hipStream_t st, const uint32_t* pixels, uint32_t npix, uint32_t width, const void* src, void* img);
 

@@ -9,6 +9,8 @@
 // Also owns rt3_ctx::roulette: Russian roulette on extension rays (rt3_path_set_roulette), which trace_batch applies
 // for "refrence_mode" and "adaptive".
 // trace_batch also launches k_absorb (rt3_scene_set_attenuation) when the built scene has an absorption table.
+// Also owns the launch side of rt3_ctx::medium (rt3_scene_set_medium): the in-scatter shadow queues, the words of
+// rt3_medium_info, and the k_fog_segment / k_fog_shadow launches of trace_batch.
 // Also owns rt3_ctx::guide: the guide images of a lens frame (rt3_camera_set_guide_output, rt3_denoise_set_guide_input, DESIGN.md section
 // 4u), which trace_batch writes with k_lens_guide for "refrence_mode" and "denoise" reads through the <DnGuide> instances of its two end
 // kernels, and the two sets "temporal" reads through k_temporal<TemporalGuide> (rt3_temporal_set_guide_input); and
@@ -24,6 +26,7 @@
 
 #include "rt3_ctx.hpp"
 #include "rt3_emit_tex.hpp"
+#include "rt3_fog.hpp"
 #include "rt3_roulette.hpp"
 #include "rt3_volume.hpp"
 
@@ -91,6 +94,42 @@ int ensure_emit_queue(rt3_ctx* c) {
     if (!r) c->work.cap_emit = c->work.cap;
     else free_work(c);
     return r;
+}
+
+// the two in-scatter shadow queues of a medium, as large as the other queues (after ensure_work), and the info words
+int ensure_fog_queues(rt3_ctx* c) {
+    if (!c->medium.d_info) {
+        HIPC(c, c->medium.d_info.alloc_bytes(16));
+        HIPC(c, hipMemsetAsync(c->medium.d_info.get(), 0, 16, c->stream));
+    }
+    if (c->medium.cap >= c->work.cap && c->medium.q_rays[0]) return RT3_OK;
+    c->medium.cap = 0;
+    int r = RT3_OK;
+    for (int k = 0; k < 2 && !r; k++) {
+        r = dev_alloc(c, c->medium.q_rays[k], 8 * c->work.cap);
+        if (!r) r = dev_alloc(c, c->medium.q_contrib[k], 2 * c->work.cap);
+        if (!r) r = dev_alloc(c, c->medium.q_tmax[k], c->work.cap);
+    }
+    if (!r) c->medium.cap = c->work.cap;
+    return r;
+}
+// a launch without a medium: the queues go (hipFree waits for the device)
+void release_fog_queues(rt3_ctx* c) {
+    if (!c->medium.q_rays[0] && !c->medium.q_rays[1]) return;
+    for (int k = 0; k < 2; k++) { c->medium.q_rays[k].reset(); c->medium.q_contrib[k].reset(); c->medium.q_tmax[k].reset(); }
+    c->medium.cap = 0;
+}
+FogDev fog_dev(const rt3_ctx* c) {
+    const rt3_medium& m = c->medium.params;
+    FogDev f;
+    for (int k = 0; k < 3; k++) {
+        f.sigma_t[k] = m.sigma_a[k] + m.sigma_s[k];
+        f.sigma_s[k] = m.sigma_s[k];
+        f.lo[k] = m.box_min[k];
+        f.hi[k] = m.box_max[k];
+    }
+    f.g = m.g;
+    return f;
 }
 
 // k_shade_pane's distance per path, as many as the queues hold (after ensure_work)
@@ -292,6 +331,10 @@ struct PathSetup {
     float4* guide_prev = nullptr;
     MotionDev motion{};
     const float4* prev_pos = nullptr;
+    // fog (rt3_scene_set_medium): a medium is on -- k_fog_segment behind every k_extend, k_fog_shadow ahead of the
+    // surface vertices' k_shadow launches; fog_scatter: some sigma_s > 0 and the frame samples a light -- the in-scatter queues and their walks
+    bool fog = false, fog_scatter = false;
+    FogDev fogdev{};
 };
 // pl = pt / (2 pi^2 sin_theta) of a light sample is positive for every sin_theta in (0, 1] when the texel density pt is at least this
 constexpr float kSkyDeferMinPdf = 0x1p-100f;
@@ -317,7 +360,17 @@ int path_setup(rt3_ctx* c, const rt3_gconst* g, PathSetup* ps) {
     ps->nee_e = ps->lights.n != 0u;
     ps->emit_tex = ps->nee_e && c->accel.lights.textured ? c->accel.lights.emit_tex.get() : nullptr;
     ps->sc = scene_dev(c);
-    ps->defer = c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
+    ps->fog = c->medium.on;
+    if (ps->fog) {
+        ps->fogdev = fog_dev(c);
+        const float* ss = ps->fogdev.sigma_s;
+        ps->fog_scatter = (ss[0] > 0.0f || ss[1] > 0.0f || ss[2] > 0.0f) && (ps->nee || ps->nee_e);
+        if (int r = ensure_fog_queues(c)) return r;
+    } else {
+        release_fog_queues(c);
+    }
+    // (a medium: in a deferred frame sh_contrib holds vertices, not the contributions k_fog_shadow multiplies)
+    ps->defer = !ps->fog && c->opt.defer_sky_light && ps->nee && !c->accel.has_glass && !ps->punct && ps->sc.mat_tex == nullptr && c->scene.sky_min_pdf >= kSkyDeferMinPdf;
     {
         const LbvhResult& bvh = c->accel.bvh;
         ps->shade_exit = c->opt.shade_exit_test && ps->defer && !ps->nee_e && !c->opt.count && alpha_dev(c).table == nullptr && c->accel.n_panes == 0u &&
@@ -353,6 +406,18 @@ int roulette_begin(rt3_ctx* c, const char* pass, uint32_t samples, uint32_t boun
     c->work.roulette_tested = c->work.roulette_ended = 0;
     return RT3_OK;
 }
+// Ahead of roulette_begin, so that a refused launch leaves its counts alone: with a medium on the fog draws' RNG indices, 8 per (sample,
+// segment) from kFogRngBase, may not run into the camera's (kLensRngBase)
+int fog_range_check(rt3_ctx* c, const char* pass, uint32_t samples, uint32_t bounces) {
+    if (c->medium.on && (uint64_t)samples * bounces * kFogRngDims > (uint64_t)(kLensRngBase - kFogRngBase))
+        return fail(c, RT3_E_INVALID, std::string(pass) + " with a medium: samples * bounces * 8 may not exceed 2^28 (the fog draws' RNG indices end where the camera's start)");
+    return RT3_OK;
+}
+// A path-tracing launch begins (behind roulette_begin): the counts of rt3_medium_info start again
+int fog_begin(rt3_ctx* c) {
+    if (c->medium.d_info) HIPC(c, hipMemsetAsync(c->medium.d_info.get(), 0, 16, c->stream));
+    return RT3_OK;
+}
 // One wavefront batch: samples s0 .. s0 + nsb - 1 of the npix listed pixels (path id = sample_in_batch * npix + index) through all B
 // bounces; each path's radiance ends up in c->work.lacc.  The loop body of "refrence_mode", and of a round of "adaptive".
 int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb, const Resource* dp, const uint32_t* pixels, const uint2* pixbn,
@@ -369,7 +434,9 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     const bool rr = ps.rr;
     // (the exit test in the shade kernel: B words more, [b] the sky shadow rays of bounce b that were decided there and never queued)
     const bool shade_exit = ps.shade_exit;
-    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0) + (rr ? B : 0) + (shade_exit ? B : 0), &first)) return r;
+    // (a medium that scatters: 4 B words more, per segment the two in-scatter queues' lengths, then the ray-pool cursors of their k_shadow launches)
+    const bool fog = ps.fog, fog_sc = ps.fog && ps.fog_scatter;
+    if (int r = reserve_counters(c, n_words + 1 + (lens ? 2 : 0) + (rr ? B : 0) + (shade_exit ? B : 0) + (fog_sc ? 4 * B : 0), &first)) return r;
     first += first & 1u;  // 8-byte aligned pairs
     // pair b = {extension rays emitted at bounce b (b < B-1), shadow rays emitted at bounce b}; then the ray-pool cursors
     uint32_t* pairs = c->work.d_counters.get() + first;
@@ -379,12 +446,51 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
     uint32_t* lens_cnt = c->work.d_counters.get() + first + n_words;  // [0] the camera queue's length, [1] its ray-pool cursor
     uint32_t* rr_cnt = lens_cnt + (lens ? 2 : 0);
     uint32_t* dec_cnt = rr_cnt + (rr ? B : 0);
+    uint32_t* fog_cnt = dec_cnt + (shade_exit ? B : 0);  // [2 seg + q]: queue q's length for segment seg; [2 B + 2 seg + q]: its ray-pool cursor
     c->work.pending_counters.push_back(CounterBlock{first, B, first + 4 * B, nee_e ? B : 0u, rr ? first + n_words + (lens ? 2u : 0u) : 0u, ps.rr_start,
                                                     c->work.launch_serial, shade_exit ? (uint32_t)(dec_cnt - c->work.d_counters.get()) : 0u});
     auto ext_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b; };
     auto sh_cnt_at = [pairs](uint32_t b) { return pairs + 2 * b + 1; };
     int cur = 0;
     const uint32_t* live_cnt = lens ? lens_cnt : nullptr;  // the length of the queue the next k_shade reads
+    // Fog on segment `seg` (0: the camera's; b + 1: the one the k_extend of bounce b has just closed), the records of queue `q`: the
+    // throughputs are attenuated; with scattering one point per segment is lit, and its shadow rays are walked at once, the sky sample's
+    // queue first, then the light table's, so that a path's radiance slot sees a fixed sequence of adds
+    auto fog_segment = [&](uint32_t seg, int q, const uint32_t* count, float* lacc_miss) {
+        FogSegmentLaunch F{};
+        F.fog = ps.fogdev; F.sc = ps.sc; F.lights = ps.lights; F.emit_tex = ps.emit_tex;
+        F.rays = c->work.rays[q].get(); F.hits = c->work.hits.get(); F.T = c->work.T[q].get(); F.count = count; F.stride = S;
+        F.lacc_miss = lacc_miss;
+        F.scatter = fog_sc ? 1u : 0u; F.sky = fog_sc && nee ? 1u : 0u;
+        if (!fog_sc) F.lights.n = 0u;
+        for (int k = 0; k < 2; k++) {
+            F.q_rays[k] = c->medium.q_rays[k].get(); F.q_contrib[k] = c->medium.q_contrib[k].get(); F.q_tmax[k] = c->medium.q_tmax[k].get();
+            F.q_count[k] = fog_sc ? fog_cnt + 2 * seg + k : nullptr;
+        }
+        F.q_stride = S;
+        F.pixels = pixels; F.npix = npix; F.s0 = s0; F.bounces = B; F.segment = seg; F.frame = ps.gd.frame;
+        F.info = c->medium.d_info.get();
+        {
+            ScopedTimer t(c, CAT_OTHER);
+            launch_fog_segment(c->stream, F, n_first);
+        }
+        for (int k = 0; k < 2 && fog_sc; k++) {
+            if (k == 0 ? !nee : !nee_e) continue;
+            TraceLaunch tr = ctx_trace(c);
+            tr.rays = c->medium.q_rays[k].get(); tr.count_ptr = fog_cnt + 2 * seg + k; tr.n = n_first; tr.work_counter = fog_cnt + 2 * B + 2 * seg + k;
+            tr.contrib = c->medium.q_contrib[k].get(); tr.lacc = c->work.lacc.get(); tr.tmax = c->medium.q_tmax[k].get();
+            if (ps.panes) tr.pane = &ps.pane;
+            ScopedTimer t(c, CAT_SHADOW);
+            launch_shadow(c->stream, c->accel.bvh, tr);
+        }
+    };
+    // the light samples k_shade has just queued, before their walk adds them in
+    auto fog_shadow = [&](float* rays, float* contrib, const float* tmax, const uint32_t* count) {
+        FogShadowLaunch F{};
+        F.fog = ps.fogdev; F.rays = rays; F.contrib = contrib; F.tmax = tmax; F.count = count; F.stride = S;
+        ScopedTimer t(c, CAT_OTHER);
+        launch_fog_shadow(c->stream, F, n_first);
+    };
     if (lens) {
         // Vertex 0 of a lens frame: the camera rays become records of the extension queue rays[0], are traced as extension rays (payload:
         // the .w words carry pdf and id, so a camera ray starts at kRayTMin like every extension ray, not at 0 like the G-buffer's), and are
@@ -406,6 +512,9 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             ScopedTimer t(c, CAT_OTHER);
             launch_lens_miss(c->stream, ps.sc, c->work.rays[0].get(), c->work.hits.get(), c->work.lacc.get(), S, n_first);
         }
+        // the camera segment in the medium, behind k_lens_miss: the sky an escaped sample took there with throughput 1 is attenuated in
+        // this launch (under sky NEE the first k_shade's miss branch takes it, with the throughput this launch leaves)
+        if (fog) fog_segment(0u, 0, lens_cnt, !nee && ps.sc.sky != nullptr ? c->work.lacc.get() : nullptr);
         // the first-vertex features of this batch's samples, while the camera queue and its hits are whole: the first k_shade overwrites
         // neither, but the k_extend behind it overwrites the hits
         if (ps.guide[0] != nullptr) {
@@ -445,6 +554,7 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
                          ps.panes ? c->work.pane_dist.get() : nullptr, shade_exit ? &sx : nullptr, c->accel.has_glass && c->accel.n_frosted != 0u);
         }
         cur ^= 1;
+        if (nee && fog) fog_shadow(c->work.sh_rays.get(), c->work.sh_contrib.get(), nullptr, sh_cnt_at(bn));
         if (nee) {
             TraceLaunch tr = ctx_trace(c);
             tr.rays = c->work.sh_rays.get(); tr.count_ptr = sh_cnt_at(bn); tr.n = n_first; tr.work_counter = pool_cur + B + bn;
@@ -475,6 +585,8 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             launch_emit_tex(c->stream, E, n_first);
             c->prof.stats.emit_tex_launches++;
         }
+        // (behind k_emit_tex: the two products commute only up to rounding)
+        if (nee_e && bn + 1 < B && fog) fog_shadow(c->work.sh2_rays.get(), c->work.sh2_contrib.get(), c->work.sh2_tmax.get(), emit_cnt + bn);
         if (nee_e && bn + 1 < B) {  // after the sky's: the two add into the same radiance slots, one launch after the other
             TraceLaunch tr = ctx_trace(c);
             tr.rays = c->work.sh2_rays.get(); tr.count_ptr = emit_cnt + bn; tr.n = n_first; tr.work_counter = emit_cnt + B + bn;
@@ -512,6 +624,8 @@ int trace_batch(rt3_ctx* c, const PathSetup& ps, uint32_t W, const Resource* gb,
             ScopedTimer t(c, CAT_OTHER);
             launch_absorb(c->stream, A, n_first);
         }
+        // behind k_absorb (the two products commute only up to rounding): the same segments, where they run through the medium
+        if (fog && bn != B - 1) fog_segment(bn + 1u, cur, live_cnt, nullptr);
     }
     return RT3_OK;
 }
@@ -583,7 +697,14 @@ int pass_reference_mode(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H,
         if ((uint64_t)Sspp * B * 8u > (1ull << 30))
             return fail(c, RT3_E_INVALID, "refrence_mode with glass: samples * bounces * 8 may not exceed 2^30 (the glass draws' RNG indices start there)");
     }
+    if (c->medium.on) {
+        if (!c->lens.on)
+            return fail(c, RT3_E_STATE, "refrence_mode: a medium is set (rt3_scene_set_medium) and the camera segment of a G-buffer frame is no record of the "
+                                        "extension queue: start every sample from its own camera ray with rt3_camera_set_lens ({0, f, 0} is the per-sample pinhole)");
+    }
+    if (int r = fog_range_check(c, "refrence_mode", Sspp, B)) return r;
     if (int r = roulette_begin(c, "refrence_mode", Sspp, B)) return r;
+    if (int r = fog_begin(c)) return r;
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     const uint32_t npix = pl->count;
@@ -638,6 +759,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
     if (c->accel.has_glass && !cover)
         return fail(c, RT3_E_STATE, "adaptive: not for a scene with glass (rt3_scene_set_transmission): glass needs per-sample camera rays "
                                     "(rt3_camera_set_lens), which this pass does not take; use refrence_mode");
+    if (c->medium.on && !cover)
+        return fail(c, RT3_E_STATE, "adaptive: not with a medium set (rt3_scene_set_medium) outside coverage mode: fog needs per-sample camera rays "
+                                    "(rt3_camera_set_lens with rt3_adaptive_set_coverage); or use refrence_mode");
     if (cap == 0 || B == 0) return RT3_OK;  // like refrence_mode
     if (B > 64) return fail(c, RT3_E_INVALID, "bounces > 64");
     if (cover) {  // refrence_mode's range rules, the cap as `samples`
@@ -646,7 +770,9 @@ int pass_adaptive(rt3_ctx* c, const rt3_gconst* g, uint32_t W, uint32_t H, Resou
         if (c->accel.has_glass && (uint64_t)cap * B * 8u > (1ull << 30))
             return fail(c, RT3_E_INVALID, "adaptive with glass: samples * bounces * 8 may not exceed 2^30 (the glass draws' RNG indices start there)");
     }
+    if (int r = fog_range_check(c, "adaptive", cap, B)) return r;
     if (int r = roulette_begin(c, "adaptive", cap, B)) return r;
+    if (int r = fog_begin(c)) return r;
     PixelList* pl;
     if (int r = get_pixlist(c, W, H, c->tiles.rank, c->tiles.n_ranks, &pl)) return r;
     if (pl->count == 0) return RT3_OK;
@@ -1041,6 +1167,192 @@ int launch_pass(rt3_ctx* c, const PassDesc& p, const rt3_gconst* g, uint32_t x, 
 
 }  // namespace
 
+namespace rt3 {
+
+// Self-test op 46 (include/rt3.h has the layout).  Every plane is one record longer than n and carries a pattern where the kernels have
+// nothing to write.
+int selftest_fog_queue(rt3_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out) {
+    const uint32_t kind = in[0], groups = in[1], flags = in[2], frame = in[3], B = in[4], seg = in[5], s0 = in[6], npix = in[7], miss_lacc = in[8];
+    if (kind > 2 || groups == 0 || groups > 65535 || B == 0 || B > 64 || seg >= B || npix == 0 || npix > (1u << 24) || n > (1u << 24) || miss_lacc > 1)
+        return fail(c, RT3_E_INVALID, "selftest: fog queue header: kind 0..2, 1..65535 workgroups, bounces 1..64, segment < bounces, 1..2^24 pixels, at most 2^24 records");
+    if (((uint64_t)s0 + (n ? n : 1u)) * B * kFogRngDims > (uint64_t)(kLensRngBase - kFogRngBase)) return fail(c, RT3_E_INVALID, "selftest: fog queue: s0 too large");
+    if (!c->medium.on) return fail(c, RT3_E_STATE, "selftest: no medium is on (rt3_scene_set_medium)");
+    if (int r = check_accel_current(c)) return r;
+    HIPC(c, hipSetDevice(c->device));
+    constexpr uint32_t kGuard = 0xA5A5A5A5u;
+    const size_t S = (size_t)n + 1;
+    const uint32_t* rec = in + kSelftestFogQueueHeader + npix;
+    DevBuf<uint32_t> d_cnt;
+    HIPC(c, d_cnt.alloc_bytes(16));
+    const uint32_t cnt0[4] = {n, 0u, 0u, 0u};
+    HIPC(c, hipMemcpy(d_cnt.get(), cnt0, 16, hipMemcpyHostToDevice));
+    if (kind != 0) {  // k_fog_shadow
+        std::vector<uint32_t> rays(8 * S, kGuard), contrib(2 * S, kGuard), tmax(S, kGuard);
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t* r = rec + kSelftestFogShadowRecord * i;
+            memcpy(&rays[4 * i], r, 16);
+            memcpy(&rays[4 * (S + i)], r + 4, 16);
+            contrib[2 * i] = r[8];
+            contrib[2 * i + 1] = r[9];
+            tmax[i] = r[10];
+        }
+        DevBuf<float> d_rays, d_contrib, d_tmax;
+        HIPC(c, d_rays.alloc_bytes(8 * S * 4));
+        HIPC(c, d_contrib.alloc_bytes(2 * S * 4));
+        HIPC(c, d_tmax.alloc_bytes(S * 4));
+        HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(d_contrib.get(), contrib.data(), 2 * S * 4, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(d_tmax.get(), tmax.data(), S * 4, hipMemcpyHostToDevice));
+        FogShadowLaunch F{};
+        F.fog = fog_dev(c); F.rays = d_rays.get(); F.contrib = d_contrib.get(); F.tmax = kind == 2 ? d_tmax.get() : nullptr; F.count = d_cnt.get(); F.stride = S;
+        launch_fog_shadow(c->stream, F, n, groups);
+        HIPC(c, hipGetLastError());
+        HIPC(c, hipStreamSynchronize(c->stream));
+        std::vector<uint32_t> rays2(8 * S), contrib2(2 * S), tmax2(S);
+        HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(contrib2.data(), d_contrib.get(), 2 * S * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(tmax2.data(), d_tmax.get(), S * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < S; i++) {
+            const bool guard = i == n;
+            for (int k = 0; k < 4; k++)
+                if ((guard || k < 3) && (rays2[4 * i + k] != rays[4 * i + k] || rays2[4 * (S + i) + k] != rays[4 * (S + i) + k]))
+                    return fail(c, RT3_E_STATE, "selftest: k_fog_shadow changed an origin, a direction or a word behind the queue's end");
+            if (contrib2[2 * i + 1] != contrib[2 * i + 1] || (guard && contrib2[2 * i] != kGuard) || tmax2[i] != tmax[i])
+                return fail(c, RT3_E_STATE, "selftest: k_fog_shadow changed a path id, a range end or a word behind the queue's end");
+        }
+        for (size_t i = 0; i < n; i++) {
+            out[3 * i] = rays2[4 * i + 3];
+            out[3 * i + 1] = rays2[4 * (S + i) + 3];
+            out[3 * i + 2] = contrib2[2 * i];
+        }
+        return RT3_OK;
+    }
+    {  // every path id once, below max(n, 1): the radiance slots and the queues have n slots
+        std::vector<uint8_t> seen(n ? n : 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t pid = rec[kSelftestFogSegmentRecord * i + 11];
+            if (pid >= n || seen[pid]) return fail(c, RT3_E_INVALID, "selftest: fog queue record " + std::to_string(i) + ": path ids are 0 .. n-1, each once");
+            seen[pid] = 1;
+        }
+    }
+    rt3_gconst g;
+    memset(&g, 0, sizeof(g));
+    g.bounces = B;
+    g.samples = 1;
+    g.frame = frame;
+    g.pad[0] = flags;
+    // (path_setup as a frame calls it, so that the light table, the sky and the emitter side array are the frame's.  No ensure_work runs
+    // ahead of it here: as a side effect it sizes the context's own in-scatter queues for whatever work.cap is, possibly one element; the
+    // next frame's path_setup grows them again.  This op launches over queues of its own, below.)
+    PathSetup ps;
+    if (int r = path_setup(c, &g, &ps)) return r;
+    std::vector<uint32_t> rays(8 * S, kGuard), hits(4 * S, kGuard), T(3 * S, kGuard), lacc(4 * S, kGuard);
+    const float one = 1.0f;
+    uint32_t one_bits;
+    memcpy(&one_bits, &one, 4);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t* r = rec + kSelftestFogSegmentRecord * i;
+        memcpy(&rays[4 * i], r, 12);
+        rays[4 * i + 3] = one_bits;  // the pdf slot
+        memcpy(&rays[4 * (S + i)], r + 3, 12);
+        rays[4 * (S + i) + 3] = r[11];
+        hits[4 * i] = r[6];
+        hits[4 * i + 1] = hits[4 * i + 2] = 0u;
+        hits[4 * i + 3] = r[7];
+        for (int k = 0; k < 3; k++) T[k * S + i] = r[8 + k];
+        lacc[4 * i] = lacc[4 * i + 1] = lacc[4 * i + 2] = one_bits;
+        lacc[4 * i + 3] = 0u;
+    }
+    DevBuf<float> d_rays, d_hits, d_T, d_lacc, q_rays[2], q_contrib[2], q_tmax[2];
+    DevBuf<uint32_t> d_pix;
+    DevBuf<unsigned long long> d_info;
+    HIPC(c, d_rays.alloc_bytes(8 * S * 4));
+    HIPC(c, d_hits.alloc_bytes(4 * S * 4));
+    HIPC(c, d_T.alloc_bytes(3 * S * 4));
+    HIPC(c, d_lacc.alloc_bytes(4 * S * 4));
+    HIPC(c, d_pix.alloc_bytes((size_t)npix * 4));
+    HIPC(c, d_info.alloc_bytes(16));
+    HIPC(c, hipMemset(d_info.get(), 0, 16));
+    HIPC(c, hipMemcpy(d_rays.get(), rays.data(), 8 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_hits.get(), hits.data(), 4 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_T.get(), T.data(), 3 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_lacc.get(), lacc.data(), 4 * S * 4, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(d_pix.get(), in + kSelftestFogQueueHeader, (size_t)npix * 4, hipMemcpyHostToDevice));
+    for (int k = 0; k < 2; k++) {
+        HIPC(c, q_rays[k].alloc_bytes(8 * S * 4));
+        HIPC(c, q_contrib[k].alloc_bytes(2 * S * 4));
+        HIPC(c, q_tmax[k].alloc_bytes(S * 4));
+        HIPC(c, hipMemset(q_rays[k].get(), 0xA5, 8 * S * 4));
+        HIPC(c, hipMemset(q_contrib[k].get(), 0xA5, 2 * S * 4));
+        HIPC(c, hipMemset(q_tmax[k].get(), 0xA5, S * 4));
+    }
+    FogSegmentLaunch F{};
+    F.fog = ps.fogdev; F.sc = ps.sc; F.lights = ps.lights; F.emit_tex = ps.emit_tex;
+    F.rays = d_rays.get(); F.hits = d_hits.get(); F.T = d_T.get(); F.count = d_cnt.get(); F.stride = S;
+    F.lacc_miss = miss_lacc ? d_lacc.get() : nullptr;
+    F.scatter = ps.fog_scatter ? 1u : 0u; F.sky = ps.fog_scatter && ps.nee ? 1u : 0u;
+    if (!ps.fog_scatter) F.lights.n = 0u;
+    for (int k = 0; k < 2; k++) {
+        F.q_rays[k] = q_rays[k].get(); F.q_contrib[k] = q_contrib[k].get(); F.q_tmax[k] = q_tmax[k].get();
+        F.q_count[k] = d_cnt.get() + 1 + k;
+    }
+    F.q_stride = S;
+    F.pixels = d_pix.get(); F.npix = npix; F.s0 = s0; F.bounces = B; F.segment = seg; F.frame = frame;
+    F.info = d_info.get();
+    launch_fog_segment(c->stream, F, n, groups);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> rays2(8 * S), hits2(4 * S);
+    uint32_t cnt[4];
+    unsigned long long info[2];
+    HIPC(c, hipMemcpy(rays2.data(), d_rays.get(), 8 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(hits2.data(), d_hits.get(), 4 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(T.data(), d_T.get(), 3 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(lacc.data(), d_lacc.get(), 4 * S * 4, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(cnt, d_cnt.get(), 16, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(info, d_info.get(), 16, hipMemcpyDeviceToHost));
+    if (rays2 != rays || hits2 != hits) return fail(c, RT3_E_STATE, "selftest: k_fog_segment wrote a ray or hit record");
+    for (int k = 0; k < 3; k++)
+        if (T[k * S + n] != kGuard) return fail(c, RT3_E_STATE, "selftest: k_fog_segment wrote behind the queue's end");
+    for (int k = 0; k < 4; k++)
+        if (lacc[4 * (size_t)n + k] != kGuard) return fail(c, RT3_E_STATE, "selftest: k_fog_segment wrote behind the radiance slots' end");
+    if (cnt[0] != n || cnt[1] > n || cnt[2] > n) return fail(c, RT3_E_STATE, "selftest: k_fog_segment left an impossible queue length");
+    out[0] = cnt[1];
+    out[1] = cnt[2];
+    out[2] = (uint32_t)info[0];
+    out[3] = (uint32_t)info[1];
+    uint32_t* o = out + 4;
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) o[3 * i + k] = T[k * S + i];
+    o += 3 * (size_t)n;
+    memcpy(o, lacc.data(), 16 * (size_t)n);
+    o += 4 * (size_t)n;
+    for (int k = 0; k < 2; k++) {
+        std::vector<uint32_t> qr(8 * S), qc(2 * S), qt(S);
+        HIPC(c, hipMemcpy(qr.data(), q_rays[k].get(), 8 * S * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(qc.data(), q_contrib[k].get(), 2 * S * 4, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(qt.data(), q_tmax[k].get(), S * 4, hipMemcpyDeviceToHost));
+        for (size_t i = cnt[1 + k]; i < S; i++) {  // behind the length nothing is written
+            bool clean = qc[2 * i] == kGuard && qc[2 * i + 1] == kGuard && qt[i] == kGuard;
+            for (int w = 0; w < 4; w++) clean = clean && qr[4 * i + w] == kGuard && qr[4 * (S + i) + w] == kGuard;
+            if (!clean) return fail(c, RT3_E_STATE, "selftest: k_fog_segment wrote behind an in-scatter queue's length");
+        }
+        for (size_t i = 0; i < n; i++) {
+            uint32_t* r = o + kSelftestFogRayOut * i;
+            memcpy(r, &qr[4 * i], 16);
+            memcpy(r + 4, &qr[4 * (S + i)], 16);
+            r[8] = qc[2 * i];
+            r[9] = qc[2 * i + 1];
+            r[10] = qt[i];
+            r[11] = 0u;
+        }
+        o += kSelftestFogRayOut * (size_t)n;
+    }
+    return RT3_OK;
+}
+
+}  // namespace rt3
+
 extern "C" {
 
 // ---- pass launch
@@ -1213,6 +1525,16 @@ int rt3_path_get_roulette(rt3_ctx* c, rt3_roulette_params* out, int* enabled) {
     if (!c) return RT3_E_INVALID;
     if (out) *out = c->roulette.params;
     if (enabled) *enabled = c->roulette.on ? 1 : 0;
+    return RT3_OK;
+}
+int rt3_medium_info(rt3_ctx* c, uint64_t* segments, uint64_t* inscatter_rays) {
+    if (!c) return RT3_E_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    unsigned long long h[2] = {0ull, 0ull};
+    if (c->medium.d_info) HIPC(c, hipMemcpy(h, c->medium.d_info.get(), 16, hipMemcpyDeviceToHost));
+    if (segments) *segments = h[0];
+    if (inscatter_rays) *inscatter_rays = h[1];
     return RT3_OK;
 }
 int rt3_path_roulette_info(rt3_ctx* c, uint64_t* tested, uint64_t* ended) {

@@ -345,6 +345,37 @@ int rt3_scene_get_rough_transmission(rt3_ctx* c, int* on) {
     *on = c->rough_transmission ? 1 : 0;
     return RT3_OK;
 }
+// fog: the medium is the context's; the launches read it by value, so no structure or table depends on it
+int rt3_scene_set_medium(rt3_ctx* c, const rt3_medium* m) {
+    if (!c) return RT3_E_INVALID;
+    if (!m) {
+        c->medium.params = rt3_medium{};
+        c->medium.set = c->medium.on = false;
+        return RT3_OK;
+    }
+    bool any = false;
+    for (int k = 0; k < 3; k++) {
+        if (!(m->sigma_a[k] >= 0.0f && m->sigma_a[k] <= kFloatMax) || !(m->sigma_s[k] >= 0.0f && m->sigma_s[k] <= kFloatMax))
+            return fail(c, RT3_E_INVALID, "medium: sigma_a and sigma_s must be finite values >= 0");
+        if (!(m->sigma_a[k] + m->sigma_s[k] <= kFloatMax)) return fail(c, RT3_E_INVALID, "medium: sigma_a + sigma_s must be finite");
+        any = any || m->sigma_a[k] + m->sigma_s[k] > 0.0f;
+    }
+    if (!(m->g > -1.0f && m->g < 1.0f)) return fail(c, RT3_E_INVALID, "medium: g must lie in (-1, 1)");
+    for (int k = 0; k < 3; k++) {
+        if (!(std::fabs(m->box_min[k]) <= kFloatMax && std::fabs(m->box_max[k]) <= kFloatMax)) return fail(c, RT3_E_INVALID, "medium: the box must be finite");
+        if (!(m->box_min[k] < m->box_max[k])) return fail(c, RT3_E_INVALID, "medium: the box is empty (box_min must be below box_max on every axis)");
+    }
+    c->medium.params = *m;
+    c->medium.set = true;
+    c->medium.on = any;
+    return RT3_OK;
+}
+int rt3_scene_get_medium(rt3_ctx* c, rt3_medium* out, int* enabled) {
+    if (!c || (!out && !enabled)) return fail(c, RT3_E_INVALID, "medium: NULL");
+    if (out) *out = c->medium.params;
+    if (enabled) *enabled = c->medium.on ? 1 : 0;
+    return RT3_OK;
+}
 // Sky storage and importance tables (north_star; the oracle's orc_scene_set_sky has the definitions and is built by the same
 // arithmetic, in double, in the same order): radiance stored as RGB9E5 (packing.slang:99-162), marginal CDF over rows, one alias
 // table per row with 16-bit keep-thresholds, pdf_uv = the density the quantised tables really realise.

@@ -192,6 +192,11 @@ bool selftest_widths(int op, uint32_t* in_w, uint32_t* out_w) {
         *out_w = kSelftestFrostOut;
         return true;
     }
+    if (op == 45) {  // the fog rule (k_selftest_fog, rt3_fog.hip); op 46 has no rows of one width (rt3_selftest_eval)
+        *in_w = kSelftestFogIn;
+        *out_w = kSelftestFogOut;
+        return true;
+    }
     static const uint32_t w[30][2] ={{1, 1}, {2, 1}, {2, 1}, {2, 1}, {11, 4}, {4, 11}, {2, 3}, {3, 6}, {3, 3}, {1, 2}, {2, 1}, {3, 1}, {2, 3},
                                       {2, 3}, {3, 9}, {64, 128}, {64, 1}, {3, 1}, {1, 3}, {11, 4}, {11, 8}, {6, 3}, {3, 2}, {3, 1}, {1, 3},
                                       {2, 9}, {2, 4}, {3, 1}, {1, 1}, {3, 11}};

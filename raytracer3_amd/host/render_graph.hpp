@@ -122,6 +122,15 @@ class Context {
         const rt3_lens_params p = {aperture, focus, jitter, 0u};
         set_lens(&p);
     }
+    // fog: one box of homogeneous medium with single scattering; nullptr switches it off.  Needs a lens (set_lens)
+    void set_medium(const rt3_medium* m) const { check(rt3_scene_set_medium(ctx_, m), "rt3_scene_set_medium"); }
+    bool get_medium(rt3_medium* out) const {
+        int on = 0;
+        check(rt3_scene_get_medium(ctx_, out, &on), "rt3_scene_get_medium");
+        return on != 0;
+    }
+    // (traced segments in the medium, in-scatter shadow rays) of the last refrence_mode / adaptive launch; synchronises
+    void medium_info(uint64_t* segments, uint64_t* inscatter_rays) const { check(rt3_medium_info(ctx_, segments, inscatter_rays), "rt3_medium_info"); }
     bool get_lens(rt3_lens_params* out) const {
         int on = 0;
         check(rt3_camera_get_lens(ctx_, out, &on), "rt3_camera_get_lens");

@@ -718,6 +718,61 @@ class Context:
         self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_ABSORB_QUEUE, inp.ctypes.data, n, out.ctypes.data))
         return out[: 3 * n].reshape(n, 3)
 
+    def set_medium(self, medium=None, **kw):
+        """fog (rt3_scene_set_medium): an L.Medium, or its fields as keywords; nothing = off.  Needs per-sample camera
+        rays (set_lens); the acceleration structure stays as it is."""
+        if medium is None and kw:
+            medium = L.Medium(**kw)
+        self.check(self.lib.rt3_scene_set_medium(self.h, C.byref(medium) if medium is not None else None))
+
+    def get_medium(self):
+        """(L.Medium last set, whether a medium is on) (rt3_scene_get_medium)"""
+        m, on = L.Medium(), C.c_int()
+        self.check(self.lib.rt3_scene_get_medium(self.h, C.byref(m), C.byref(on)))
+        return m, bool(on.value)
+
+    def medium_info(self):
+        """(traced segments that ran through the medium, in-scatter shadow rays queued) of the last "refrence_mode" / "adaptive" launch
+        (rt3_medium_info); synchronises"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.rt3_medium_info(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def selftest_fog(self, rows):
+        """Self-test op 45: the fog rule on rows (n, 20) float32 {o, d, t, box_min, box_max, sigma_a, sigma_s, u}.  Returns (in medium (n,)
+        bool, {t0, t1, s, pdf, Tr rgb} (n, 7) float32)."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 20)
+        out = np.zeros((len(rows), 8), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_FOG, rows.ctypes.data, len(rows), out.ctypes.data))
+        return out[:, 0] != 0, out[:, 1:].copy().view(np.float32)
+
+    def selftest_fog_segment(self, records, pixels, groups, flags, frame, bounces, segment, s0=0, miss_radiance=False):
+        """Self-test op 46, kind 0: k_fog_segment with the context's medium on the queue `records` (n, 12) of 32-bit words {o xyz, d xyz, t,
+        prim, T rgb, path id}, launched with `groups` workgroups over the pixel words `pixels`.  Returns a dict: counts (2,), segments, rays,
+        T (n, 3) uint32, radiance (n, 4) uint32, queues: two (n, 12) uint32 arrays {x, c.r, w_l, c.g, c.b, path id, tmax, 0}."""
+        pixels = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 12)
+        n = len(records)
+        head = np.array([0, groups, flags, frame, bounces, segment, s0, len(pixels), int(miss_radiance)], np.uint32)
+        inp = np.concatenate([head, pixels, records.reshape(-1)])
+        out = np.zeros(4 + 31 * n, np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_FOG_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        body = out[4:]
+        return dict(counts=out[0:2].copy(), segments=int(out[2]), rays=int(out[3]), T=body[: 3 * n].reshape(n, 3), radiance=body[3 * n : 7 * n].reshape(n, 4),
+                    queues=[body[7 * n + 12 * n * k : 7 * n + 12 * n * (k + 1)].reshape(n, 12) for k in range(2)])
+
+    def selftest_fog_shadow(self, records, groups, with_tmax):
+        """Self-test op 46, kinds 1 and 2: k_fog_shadow with the context's medium on the shadow queue `records` (n, 11) of 32-bit words
+        {o xyz, c.r, d xyz, c.g, c.b, path id, tmax}; without `with_tmax` the rays run to the box's exit.  Returns the contributions (n, 3)
+        uint32 after the launch."""
+        records = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 11)
+        n = len(records)
+        head = np.array([2 if with_tmax else 1, groups, 0, 0, 1, 0, 0, 1, 0], np.uint32)
+        inp = np.concatenate([head, np.zeros(1, np.uint32), records.reshape(-1)])
+        out = np.zeros(3 * max(n, 1), np.uint32)
+        self.check(self.lib.rt3_selftest_eval(self.h, L.SELFTEST_FOG_QUEUE, inp.ctypes.data, n, out.ctypes.data))
+        return out[: 3 * n].reshape(n, 3)
+
     def stats_reset(self):
         self.check(self.lib.rt3_stats_reset(self.h))
 

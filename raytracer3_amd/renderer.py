@@ -59,6 +59,18 @@ PREV_GUIDE_IMAGES = tuple((key, "Prev" + name) for key, name in GUIDE_IMAGES)
 GUIDE_SWAPS = tuple((name, "Prev" + name) for _, name in GUIDE_IMAGES)
 
 
+def scene_medium(mesh, sigma_s, sigma_a=0.0, g=0.0, margin=0.0, box=None):
+    """An L.Medium for PathTracer.set_medium: scattering and absorption coefficients (a number, or one per colour channel) in a box that
+    defaults to the bounds of the mesh's vertices (as uploaded: instance transforms are not followed), grown by `margin` world units."""
+    if box is None:
+        p = np.asarray(mesh.vertices, np.float64)[:, :3]
+        lo, hi = p.min(0) - margin, p.max(0) + margin
+        hi = np.maximum(hi, lo + 1e-3)  # a flat world still gets a box
+    else:
+        lo, hi = np.asarray(box[0], np.float64), np.asarray(box[1], np.float64)
+    return L.Medium(sigma_a, sigma_s, g, tuple(lo), tuple(hi))
+
+
 def guide_images(rg):
     """the four guide images of a lens frame as a dict {position, normal, albedo, emission} of handles: what
     ctx.set_guide_output and ctx.set_denoise_guide_input take"""
@@ -274,6 +286,8 @@ class PathTracer:
         self.host_group = None   # process group of the host-moved gather (None = the default group)
         self._history = _TemporalHistory(self.ctx)
         self._glass_lens = False  # the lens in force is the pinhole set_scene switched on for a scene with glass
+        self._fog_lens = False  # ... or the one set_medium switched on for a medium
+        self._medium_on = False  # set_medium's medium is on (some coefficient > 0)
         self._scene_set = False   # set_scene has built a structure (set_pane_shadows rebuilds it)
         self._guide = False       # set_guide: lens frames write guide images, and "denoise" is guided by them
         self._guide_temporal = False    # set_guide(temporal=True): temporal lens frames write them too, and "temporal" reads two sets
@@ -308,9 +322,34 @@ class PathTracer:
         elif not glass and self._glass_lens:
             self.ctx.set_lens(None)
             self._glass_lens = False
+        if glass and self._fog_lens:  # the pinhole set_medium switched on is the glass's from here on: the next scene without glass ends it
+            self._fog_lens = False
+            self._glass_lens = True
+        if self._medium_on and not self.ctx.get_lens()[1]:  # the medium outlives the scene, and needs the pinhole too
+            self.ctx.set_lens(L.LensParams(0.0, 1.0, 0.0))
+            self._fog_lens = True
         self._history.scene_set()
         if instances is not None:
             self._history.instances_set(instances)
+
+    def set_medium(self, medium=None):
+        """Fog for the frames that follow (ctx.set_medium): an L.Medium -- one axis-aligned box of homogeneous medium
+        with single scattering; scene_medium() makes one over a mesh's bounds -- or None for none, the default.  No rebuild.  A medium
+        needs per-sample camera rays: with no lens on, set_lens(0, 1, 0) -- the per-sample pinhole -- is switched on, and off again by
+        set_medium(None); a lens the caller set stays.  Denoise, temporal and motion frames do not see the medium."""
+        self.ctx.set_medium(medium)
+        on = self._medium_on = self.ctx.get_medium()[1]
+        if on and not self.ctx.get_lens()[1]:
+            self.ctx.set_lens(L.LensParams(0.0, 1.0, 0.0))
+            self._fog_lens = True
+        elif not on and self._fog_lens:
+            if not self._glass_lens:
+                self.ctx.set_lens(None)
+            self._fog_lens = False
+
+    def medium_info(self):
+        """(traced segments that ran through the medium, in-scatter shadow rays queued) of the last frame's path-tracing launch"""
+        return self.ctx.medium_info()
 
     def set_pane_shadows(self, on=True):
         """Pane shadows (ctx.set_pane_shadows): light is sampled through thin-walled glass -- sky, emitter and punctual
@@ -431,7 +470,7 @@ class PathTracer:
         box each sample's film point is drawn from (1 = antialiasing over the whole pixel), `aperture` the lens radius in world units
         (0 = pinhole), `focus` the view depth of the plane of focus.  set_lens(None) switches back to one primary hit per pixel.  With a
         lens, "postprocess" shows `Light` everywhere, and adaptive frames are refused unless set_adaptive_coverage(True)."""
-        self._glass_lens = False  # the caller's choice from here on
+        self._glass_lens = self._fog_lens = False  # the caller's choice from here on
         if aperture is None:
             self.ctx.set_lens(None)
         else:

@@ -72,6 +72,11 @@ def main():
     ap.add_argument("--pane-shadows", action="store_true", help="sample lights through thin-walled glass (PathTracer.set_pane_shadows, DESIGN.md section 4q)")
     ap.add_argument("--textured-emitters", action="store_true",
                     help="sample emitters whose emission carries an emissive texture (PathTracer.set_textured_emitters, DESIGN.md section 4x); needs RT3_F_NEE_EMISSIVE (32) in --flags")
+    ap.add_argument("--fog", type=float, default=None, metavar="SIGMA_S",
+                    help="fog over the scene's bounds: scattering coefficient per world unit, single scattering (PathTracer.set_medium, DESIGN.md section 4y); "
+                         "switches per-sample camera rays on; try --scene sunlit_room --pane-shadows --fog 0.15")
+    ap.add_argument("--fog-absorb", type=float, default=0.0, metavar="A", help="with --fog: absorption coefficient per world unit")
+    ap.add_argument("--fog-g", type=float, default=0.0, metavar="G", help="with --fog: Henyey-Greenstein asymmetry in (-1, 1); > 0 scatters forward")
     ap.add_argument("--rough-glass", action="store_true", help="frosted glass: rough transmission on glass with roughness > 0 (PathTracer.set_rough_transmission, DESIGN.md section 4t)")
     ap.add_argument("--compare", default=None, help="PNG to compare the tone-mapped result with (RMSE of 8-bit values / 255)")
     ap.add_argument("--side-by-side", default=None, help="with --compare: write [render | reference] at the reference's size here")
@@ -82,7 +87,7 @@ def main():
 
     from raytracer3_amd import _lib as L
     from raytracer3_amd import assets, scenes
-    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer
+    from raytracer3_amd.renderer import DEFAULT_FLAGS, Camera, PathTracer, scene_medium
 
     W, H = (int(x) for x in args.size.split("x"))
     if args.glb:
@@ -126,6 +131,10 @@ def main():
         if (args.temporal or args.denoise) and not args.guide:
             ap.error("--aa / --aperture do not combine with --temporal or --denoise unless --guide: those passes are guided by the pinhole G-buffer")
         pt.set_lens(args.aperture, args.focus, 1.0)
+    if args.fog is not None:
+        if args.temporal or args.denoise:
+            ap.error("--fog does not combine with --temporal or --denoise: those passes do not see the medium")
+        pt.set_medium(scene_medium(mesh, args.fog, args.fog_absorb, args.fog_g))
     if args.guide:
         if args.adaptive is not None:
             ap.error("--guide guides refrence_mode frames: it does not combine with --adaptive")
@@ -169,6 +178,9 @@ def main():
     if args.roulette is not None:  # of the last pass
         tested, ended = pt.roulette_info()
         print(f"roulette from vertex {args.roulette}: {ended / 1e6:.2f} M of {tested / 1e6:.2f} M tested extension rays ended")
+    if args.fog is not None:  # of the last pass
+        segments, fog_rays = pt.medium_info()
+        print(f"fog sigma_s {args.fog} sigma_a {args.fog_absorb} g {args.fog_g}: {segments / 1e6:.2f} M segments in the medium, {fog_rays / 1e6:.2f} M in-scatter shadow rays")
     if adaptive is not None:  # of the last pass
         n = pt.sample_counts()
         rounds, paths, capped = pt.ctx.adaptive_info()
