@@ -480,6 +480,51 @@ int rt3_scene_update_vertices(rt3_ctx *ctx, const float *interleaved_p_n_t, uint
  * modes (mode 1: every bottom tree, then the instance records and the top tree; rt3_accel_levels then reports 0 meshes built).  Does not
  * change rt3_stats.accel_build_ms. */
 int rt3_accel_refit(rt3_ctx *ctx, uint32_t *out_handle);
+/* ---- skins: skinned and morphed meshes posed on the device (glTF skins and morph targets).  No reference counterpart; DESIGN.md section 4z.
+ *      A skin owns a range of the vertex buffer and keeps what a pose needs resident on the device: the rest records, four joint indices
+ *      and weights per vertex, and up to RT3_SKIN_MAX_TARGETS morph targets (position deltas, optionally normal deltas).  A pose sends the
+ *      joint palette and the target weights only; k_skin_pose writes the range's records:
+ *        morph  for t = 0 .. n_targets-1 with a_t != 0: p.k = p.k + a_t * dP[t][v].k, and n with dN when the skin has normal deltas
+ *        blend  M = the sum of w_k * J[j_k] over the weights w_k != 0, in the order k = 0, 1, 2, 3, entry by entry (a product, then a sum);
+ *               a vertex whose four weights are 0 keeps its morphed p and n as they are
+ *        place  p' = ((M.x_axis p.x + M.y_axis p.y) + M.z_axis p.z) + M.w_axis;  n' = normalize(M's upper 3 x 3 applied to n), no inverse
+ *               transpose, as for an instance;  uv is the rest record's
+ *      fp32, singly rounded, equal to tests/ref_skin.py bit for bit.
+ *      rt3_scene_add_skin: RT3_E_INVALID, with nothing changed, for an empty range, one past the vertex buffer or one that overlaps another
+ *      skin's; n_joints outside 1 .. 65536; n_targets above RT3_SKIN_MAX_TARGETS; joints or weights NULL; target_dpos NULL with targets or
+ *      set without; a joint index >= n_joints (whatever its weight); a weight that is negative or not finite; a rest position that is not
+ *      finite or beyond 1e18; a delta that is not finite.  RT3_E_STATE before rt3_scene_set_vertices.  It touches neither the vertex buffer
+ *      nor the acceleration structure.  The arrays are tight and borrowed for the call.  *out_skin: the skin's index, counted from 0.
+ *      rt3_scene_clear_skins forgets every skin, and so does rt3_scene_set_vertices (the buffer they index is gone); rt3_scene_set_indices and
+ *      rt3_scene_set_geometry keep them.  rt3_scene_update_vertices on a skinned range is allowed: the next pose overwrites it.
+ *      rt3_scene_pose_skin: n_joints matrices, column-major 4 x 4, validated like an instance's (finite, last row (0, 0, 0, 1)), and n_targets
+ *      finite weights (NULL when the skin has none); otherwise RT3_E_INVALID and nothing changes.  The palette is uploaded and the kernel
+ *      launched on the context's stream, behind the frames already in it, without waiting for them.  Like rt3_scene_update_vertices it marks
+ *      the acceleration structure stale (rt3_accel_refit next) and, after a rt3_scene_snapshot_vertices, counts the range as updated.  A
+ *      second pose overwrites the first.  Borrowed for the call.
+ *      A posed position that is not finite or beyond 1e18 is still written, and sets the skin's flag on the device: the next rt3_accel_refit
+ *      or rt3_accel_build returns RT3_E_INVALID ("skin s: a posed position ...") and the structure stays stale, until that skin is posed
+ *      again, which clears the flag.
+ *      rt3_skin_info: the number of skins and the device bytes they hold.  rt3_scene_download_vertices: introspection for tests, records
+ *      [first, first + n) of the vertex buffer as they are on the device; it waits for the stream.  RT3_E_STATE before
+ *      rt3_scene_set_vertices, RT3_E_INVALID for a range past the buffer. ---- */
+#define RT3_SKIN_MAX_TARGETS 8u
+typedef struct rt3_skin_desc {
+    uint32_t first_vertex, n_vertices; /* the range of the vertex buffer this skin writes */
+    uint32_t n_joints;                 /* 1 .. 65536 */
+    uint32_t n_targets;                /* 0 .. RT3_SKIN_MAX_TARGETS */
+    const float *rest;                 /* n_vertices x 8 (Vertex layout); NULL: the range's current contents, copied on the device */
+    const uint16_t *joints;            /* n_vertices x 4 */
+    const float *weights;              /* n_vertices x 4 */
+    const float *target_dpos;          /* n_targets x n_vertices x 3; NULL iff n_targets == 0 */
+    const float *target_dnrm;          /* same shape, or NULL: normals are not morphed */
+} rt3_skin_desc;
+int rt3_scene_add_skin(rt3_ctx *ctx, const rt3_skin_desc *desc, uint32_t *out_skin);
+int rt3_scene_clear_skins(rt3_ctx *ctx);
+int rt3_scene_pose_skin(rt3_ctx *ctx, uint32_t skin, const float *joint_matrices /* n_joints x 16, column-major */,
+                        const float *target_weights /* n_targets, may be NULL when 0 */);
+int rt3_skin_info(rt3_ctx *ctx, uint32_t *n_skins, uint64_t *device_bytes);
+int rt3_scene_download_vertices(rt3_ctx *ctx, float *out /* n x 8 */, uint32_t first, uint32_t n);
 /* the emitter table of RT3_F_NEE_EMISSIVE for the current structure, built on the GPU on first use after rt3_accel_build / refit / import:
  * every flattened primitive of a geometry with non-zero emission, in primitive order.  *cdf_total = 2^23 (the selection grid), or 0 when no
  * emitter has power (the flag then changes nothing).  rt3_light_download (any pointer may be NULL; n_emitters entries each): primitive ids,

@@ -75,6 +75,7 @@ EXPORTS = [
     "rt3_scene_set_textured_emitters", "rt3_scene_get_textured_emitters", "rt3_light_emit_tex",
     "rt3_scene_set_medium", "rt3_scene_get_medium", "rt3_medium_info",
     "rt3_scene_snapshot_vertices", "rt3_scene_forget_prev_vertices", "rt3_scene_deformed_geometries",
+    "rt3_scene_add_skin", "rt3_scene_clear_skins", "rt3_scene_pose_skin", "rt3_skin_info", "rt3_scene_download_vertices",
     "rt3_frame_wait", "rt3_trace_rays", "rt3_selftest_eval", "rt3_stats_reset", "rt3_stats_get", "rt3_camera_gconst",
 ]
 
@@ -175,6 +176,18 @@ class Medium(C.Structure):
         super().__init__(three(sigma_a), three(sigma_s), float(g), three(box_min), three(box_max))
 
 
+SKIN_MAX_TARGETS = 8  # RT3_SKIN_MAX_TARGETS
+
+
+class SkinDesc(C.Structure):
+    """rt3_skin_desc: one skin of rt3_scene_add_skin: the vertex range it writes, and tight host arrays borrowed for
+    the call."""
+
+    _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("n_joints", C.c_uint32), ("n_targets", C.c_uint32),
+                ("rest", C.c_void_p), ("joints", C.c_void_p), ("weights", C.c_void_p), ("target_dpos", C.c_void_p), ("target_dnrm", C.c_void_p)]
+
+
+assert C.sizeof(SkinDesc) == 56
 assert C.sizeof(Medium) == 52
 assert C.sizeof(GConst) == 304
 
@@ -305,6 +318,11 @@ def load():
         "rt3_scene_snapshot_vertices": (i32, [vp]),
         "rt3_scene_forget_prev_vertices": (i32, [vp]),
         "rt3_scene_deformed_geometries": (i32, [vp, vp, u32]),
+        "rt3_scene_add_skin": (i32, [vp, C.POINTER(SkinDesc), pu32]),
+        "rt3_scene_clear_skins": (i32, [vp]),
+        "rt3_scene_pose_skin": (i32, [vp, u32, vp, vp]),
+        "rt3_skin_info": (i32, [vp, pu32, C.POINTER(C.c_uint64)]),
+        "rt3_scene_download_vertices": (i32, [vp, vp, u32, u32]),
         "rt3_frame_wait": (i32, [vp]),
         "rt3_trace_rays": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_double)]),
         "rt3_selftest_eval": (i32, [vp, i32, vp, u32, vp]),

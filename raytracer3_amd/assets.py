@@ -140,6 +140,80 @@ class Material:
     attenuation_distance: float = math.inf
 
 
+SKIN_MAX_TARGETS, SKIN_MAX_JOINTS = 8, 65536  # RT3_SKIN_MAX_TARGETS; joint indices are uint16
+
+
+@dataclass
+class Skin:
+    """One skinned and / or morphed primitive (rt3_skin_desc): the vertex range it owns and what a pose needs.  The rest
+    records are in bind space: the accessors' own values, without the mesh node's matrix, as glTF prescribes for a skinned mesh.  A morphed
+    primitive without a glTF skin is bound with weight 1 to one joint, its own node, under an identity inverse bind matrix."""
+
+    first_vertex: int
+    rest: np.ndarray  # (n, 8) float32  p n t
+    joints: np.ndarray  # (n, 4) uint16, indices into joint_nodes
+    weights: np.ndarray  # (n, 4) float32
+    joint_nodes: list  # indices into Rig.nodes
+    inverse_bind: np.ndarray  # (n_joints, 4, 4) float32, acting on column vectors
+    target_dpos: np.ndarray = None  # (n_targets, n, 3) float32; None -> no targets
+    target_dnrm: np.ndarray = None  # same shape, or None: normals are not morphed
+    default_weights: np.ndarray = None  # (n_targets,) float32: the mesh's (or its node's) `weights`
+    geometry: int = -1  # the geometry of Mesh.geometries it deforms
+
+    def __post_init__(self):
+        self.rest = np.ascontiguousarray(self.rest, np.float32).reshape(-1, 8)
+        n = len(self.rest)
+        self.joints = np.ascontiguousarray(self.joints, np.uint16).reshape(n, 4)
+        self.weights = np.ascontiguousarray(self.weights, np.float32).reshape(n, 4)
+        self.inverse_bind = np.ascontiguousarray(self.inverse_bind, np.float32).reshape(len(self.joint_nodes), 4, 4)
+        self.target_dpos = np.zeros((0, n, 3), np.float32) if self.target_dpos is None else np.ascontiguousarray(self.target_dpos, np.float32).reshape(-1, n, 3)
+        if self.target_dnrm is not None:
+            self.target_dnrm = np.ascontiguousarray(self.target_dnrm, np.float32).reshape(len(self.target_dpos), n, 3)
+        nt = len(self.target_dpos)
+        self.default_weights = np.zeros(nt, np.float32) if self.default_weights is None else np.ascontiguousarray(self.default_weights, np.float32).reshape(nt)
+
+
+@dataclass
+class Rig:
+    """The node hierarchy and the animations the skins are posed from.  nodes: dicts with glTF's own keys (`translation`, `rotation` xyzw,
+    `scale`, or `matrix` as 16 column-major floats; `name`) plus `parent` (-1: a root).  animations: dicts {name, channels}, a channel being
+    {path: translation | rotation | scale | weights, node (or, for weights, skin: the index into Mesh.skins), interpolation: LINEAR | STEP,
+    times (k,) float32, values (k, components) float32}."""
+
+    nodes: list = field(default_factory=list)
+    animations: list = field(default_factory=list)
+
+
+def _sample_channel(ch, t):
+    """the channel's value at time t (clamped to its key range), float64"""
+    times = np.asarray(ch["times"], np.float64)
+    vals = np.asarray(ch["values"], np.float64).reshape(len(times), -1)
+    rot = ch["path"] == "rotation"
+
+    def unit(q):
+        return q / np.linalg.norm(q) if rot else q
+
+    if t <= times[0]:
+        return unit(vals[0])
+    if t >= times[-1]:
+        return unit(vals[-1])
+    i = int(np.searchsorted(times, t, side="right")) - 1
+    if ch.get("interpolation", "LINEAR") == "STEP" or times[i + 1] == times[i]:
+        return unit(vals[i])
+    u = (t - times[i]) / (times[i + 1] - times[i])
+    a, b = vals[i], vals[i + 1]
+    if not rot:
+        return a + (b - a) * u
+    d = float(np.dot(a, b))
+    if d < 0.0:  # the shorter arc
+        b, d = -b, -d
+    d = min(d / (np.linalg.norm(a) * np.linalg.norm(b)), 1.0)
+    theta = math.acos(d)
+    if theta < 1e-6:
+        return unit(a + (b - a) * u)
+    return unit((math.sin((1.0 - u) * theta) * a + math.sin(u * theta) * b) / math.sin(theta))
+
+
 @dataclass
 class Mesh:
     """Flattened scene: global vertex / index buffers + one GeometryInfo per primitive (world/mod.rs:103-125)."""
@@ -159,6 +233,49 @@ class Mesh:
     attenuation: np.ndarray = None
     # (g, 4) float64 {attenuationColor rgb, attenuationDistance} the sigmas were made from, for write_glb; None -> derived from the sigmas
     attenuation_source: np.ndarray = None
+    # skinned and / or morphed primitives: one Skin each, in vertex order; `rig` holds the nodes and animations they
+    # are posed from.  `vertices` stays the static load whatever these say.
+    skins: list = field(default_factory=list)
+    rig: "Rig" = None
+
+    def pose(self, t, animation=0):
+        """per skin (palette (n_joints, 4, 4) float32, target weights (n_targets,) float32) at time `t` of animation `animation`: palette
+        entry k = G(joint_k, t) . IBM_k, with G the joint's global matrix through the node hierarchy, evaluated in float64 and rounded once.
+        Translation and scale are interpolated linearly, rotations along the shorter arc (slerp) and normalised, STEP holds the earlier key;
+        `t` is clamped to each sampler's key range.  Without animations (animation 0 only) the nodes' own transforms pose the skins."""
+        if not self.skins:
+            return []
+        rig = self.rig if self.rig is not None else Rig()
+        if animation != 0 or rig.animations:
+            channels = rig.animations[animation]["channels"]  # (IndexError: no such animation)
+        else:
+            channels = []
+        over, skin_weights = {}, {}
+        for ch in channels:
+            v = _sample_channel(ch, float(t))
+            if ch["path"] == "weights":
+                skin_weights[ch["skin"]] = v
+            else:
+                over.setdefault(ch["node"], {})[ch["path"]] = v
+        memo = {}
+
+        def world(ni):
+            if ni not in memo:
+                node = rig.nodes[ni]
+                if ni in over:  # (an animated node has no `matrix`: glTF)
+                    node = {k: v for k, v in node.items() if k != "matrix"}
+                    node.update(over[ni])
+                m = _node_matrix(node)
+                parent = rig.nodes[ni].get("parent", -1)
+                memo[ni] = m if parent < 0 else world(parent) @ m
+            return memo[ni]
+
+        out = []
+        for k, s in enumerate(self.skins):
+            pal = np.stack([world(j) @ s.inverse_bind[q].astype(np.float64) for q, j in enumerate(s.joint_nodes)])
+            w = np.asarray(skin_weights.get(k, s.default_weights), np.float64).reshape(-1)
+            out.append((np.ascontiguousarray(pal, np.float32), np.ascontiguousarray(w, np.float32)))
+        return out
 
     def __post_init__(self):
         self.lights = np.ascontiguousarray(np.zeros(0, LIGHT_DTYPE) if self.lights is None else self.lights, LIGHT_DTYPE).reshape(-1)
@@ -288,12 +405,28 @@ def write_glb(path, mesh: Mesh) -> None:
         off += len(b) + pad
         return len(views) - 1
 
+    # skins: the rig's nodes come first, under their own indices, so that joint lists and animation channels read
+    # back as they are; a skinned geometry's node follows them and is written in bind space (Skin.rest), with its joints, weights and targets
+    rig = (mesh.rig or Rig()) if mesh.skins else None
+    n_rig = len(rig.nodes) if rig else 0
+    gl_skins, skin_at = [], {s.geometry: k for k, s in enumerate(mesh.skins)}
+    for i in range(n_rig):
+        rn = {k: ([float(x) for x in v] if k != "name" else v) for k, v in rig.nodes[i].items() if k != "parent"}
+        kids = [c for c in range(n_rig) if rig.nodes[c].get("parent", -1) == i]
+        if kids:
+            rn["children"] = kids
+        nodes.append(rn)
     for gi, (g, cnt) in enumerate(zip(mesh.geometries, mesh.prim_counts)):
         io, vo, cnt = int(g["index_offset"]), int(g["vertex_offset"]), int(cnt)
         idx = mesh.indices[io : io + 3 * cnt]
         later = [int(x) for x in mesh.geometries["vertex_offset"] if int(x) > vo]
         nv = (min(later) if later else len(mesh.vertices)) - vo  # keep unreferenced vertices: the round trip is exact
         v = mesh.vertices[vo : vo + nv]
+        skin = mesh.skins[skin_at[gi]] if gi in skin_at else None
+        if skin is not None:
+            if skin.first_vertex != vo or len(skin.rest) != nv:
+                raise ValueError(f"geometry {gi}: its skin does not cover the geometry's own vertex range")
+            v = skin.rest
         acc = []
         for col, typ in ((slice(0, 3), "VEC3"), (slice(3, 6), "VEC3"), (slice(6, 8), "VEC2")):
             data = np.ascontiguousarray(v[:, col], "<f4")
@@ -341,6 +474,27 @@ def write_glb(path, mesh: Mesh) -> None:
         meshes.append({"name": mesh.names[gi] if gi < len(mesh.names) else f"g{gi}",
                        "primitives": [{"attributes": {"POSITION": acc[0], "NORMAL": acc[1], "TEXCOORD_0": acc[2]}, "indices": ia, "material": gi}]})
         nodes.append({"mesh": gi})
+        if skin is not None:
+            prim = meshes[-1]["primitives"][0]
+            accessors.append({"bufferView": push(skin.joints.astype("<u2"), 34962), "componentType": 5123, "count": nv, "type": "VEC4"})
+            prim["attributes"]["JOINTS_0"] = len(accessors) - 1
+            accessors.append({"bufferView": push(skin.weights.astype("<f4"), 34962), "componentType": 5126, "count": nv, "type": "VEC4"})
+            prim["attributes"]["WEIGHTS_0"] = len(accessors) - 1
+            for t in range(len(skin.target_dpos)):
+                tg = {}
+                for key, arr in (("POSITION", skin.target_dpos), ("NORMAL", skin.target_dnrm)):
+                    if arr is not None:
+                        data = np.ascontiguousarray(arr[t], "<f4")
+                        accessors.append({"bufferView": push(data, 34962), "componentType": 5126, "count": nv, "type": "VEC3",
+                                          "min": [float(x) for x in data.min(axis=0)], "max": [float(x) for x in data.max(axis=0)]})
+                        tg[key] = len(accessors) - 1
+                prim.setdefault("targets", []).append(tg)
+            if len(skin.target_dpos):
+                meshes[-1]["weights"] = [float(x) for x in skin.default_weights]
+            ibm = np.ascontiguousarray(skin.inverse_bind.transpose(0, 2, 1), "<f4")  # column-major
+            accessors.append({"bufferView": push(ibm), "componentType": 5126, "count": len(ibm), "type": "MAT4"})
+            gl_skins.append({"joints": [int(j) for j in skin.joint_nodes], "inverseBindMatrices": len(accessors) - 1})
+            nodes[-1]["skin"] = len(gl_skins) - 1
     gl_lights = []
     for li, l in enumerate(mesh.lights):
         I = np.asarray(l["intensity"], np.float64)
@@ -375,10 +529,29 @@ def write_glb(path, mesh: Mesh) -> None:
     doc = {
         "asset": {"version": "2.0", "generator": "raytracer3_amd.assets"},
         "scene": 0,
-        "scenes": [{"nodes": list(range(len(nodes)))}],
+        "scenes": [{"nodes": [i for i in range(len(nodes)) if i >= n_rig or rig.nodes[i].get("parent", -1) < 0]}],
         "nodes": nodes, "meshes": meshes, "materials": materials, "accessors": accessors, "bufferViews": views,
         "buffers": [{"byteLength": off}],
     }
+    if gl_skins:
+        doc["skins"] = gl_skins
+    gl_anims = []
+    for an in (rig.animations if rig else []):
+        samplers, channels = [], []
+        for ch in an["channels"]:
+            times = np.ascontiguousarray(ch["times"], "<f4").reshape(-1)
+            vals = np.ascontiguousarray(ch["values"], "<f4").reshape(len(times), -1)
+            accessors.append({"bufferView": push(times), "componentType": 5126, "count": len(times), "type": "SCALAR",
+                              "min": [float(times.min())], "max": [float(times.max())]})
+            typ = {"translation": "VEC3", "scale": "VEC3", "rotation": "VEC4", "weights": "SCALAR"}[ch["path"]]
+            accessors.append({"bufferView": push(vals), "componentType": 5126, "count": vals.size if typ == "SCALAR" else len(vals), "type": typ})
+            samplers.append({"input": len(accessors) - 2, "output": len(accessors) - 1, "interpolation": ch.get("interpolation", "LINEAR")})
+            node = n_rig + mesh.skins[ch["skin"]].geometry if ch["path"] == "weights" else int(ch["node"])
+            channels.append({"sampler": len(samplers) - 1, "target": {"node": node, "path": ch["path"]}})
+        gl_anims.append({"name": an.get("name", ""), "samplers": samplers, "channels": channels})
+    if gl_anims:
+        doc["animations"] = gl_anims
+        doc["buffers"][0]["byteLength"] = off
     if images:
         doc["images"], doc["textures"] = images, textures
     if gl_lights:
@@ -459,6 +632,83 @@ class GltfMeshLoader:
 
         mb = MeshBuilder()
         mats = doc.get("materials", [])
+        # skins, morph targets and animations.  What cannot be represented -- JOINTS_1, sparse accessors, CUBICSPLINE
+        # samplers, more than SKIN_MAX_TARGETS targets or SKIN_MAX_JOINTS joints -- leaves the primitive a static one, with a warning.
+        gl_nodes = doc.get("nodes", [])
+        parents = [-1] * len(gl_nodes)
+        for i, nd in enumerate(gl_nodes):
+            for c in nd.get("children", []):
+                parents[c] = i
+        cubic = set()  # (node, path) pairs a CUBICSPLINE sampler drives
+        for an in doc.get("animations", []):
+            for ch in an.get("channels", []):
+                if an["samplers"][ch["sampler"]].get("interpolation", "LINEAR") == "CUBICSPLINE" and "node" in ch.get("target", {}):
+                    cubic.add((ch["target"]["node"], "weights" if ch["target"]["path"] == "weights" else "trs"))
+        skins, skin_nodes = [], []
+
+        def skin_of(ni, node, gm, pi, prim, tris):
+            """the Skin of one primitive (first_vertex and geometry are filled in by the caller), or None: neither skinned nor morphed, or
+            not representable"""
+            at, targets = prim["attributes"], prim.get("targets") or []
+            skinned = "skin" in node and "JOINTS_0" in at and "WEIGHTS_0" in at
+            if not skinned and not targets:
+                return None
+            gs = doc["skins"][node["skin"]] if skinned else None
+            jn = list(gs["joints"]) if skinned else [ni]
+            used = [at[k] for k in ("POSITION", "NORMAL", "TEXCOORD_0", "JOINTS_0", "WEIGHTS_0") if k in at]
+            used += [tg[k] for tg in targets for k in ("POSITION", "NORMAL") if k in tg]
+            if skinned and "inverseBindMatrices" in gs:
+                used.append(gs["inverseBindMatrices"])
+            chain = set()
+            for j in jn:
+                while j >= 0 and j not in chain:
+                    chain.add(j)
+                    j = parents[j]
+            why = None
+            if "JOINTS_1" in at or "WEIGHTS_1" in at:
+                why = "more than four influences per vertex (JOINTS_1)"
+            elif any("sparse" in doc["accessors"][a] for a in used):
+                why = "a sparse accessor"
+            elif len(targets) > SKIN_MAX_TARGETS:
+                why = f"{len(targets)} morph targets (at most {SKIN_MAX_TARGETS})"
+            elif len(jn) > SKIN_MAX_JOINTS:
+                why = f"{len(jn)} joints (at most {SKIN_MAX_JOINTS})"
+            elif any((j, "trs") in cubic for j in chain) or (targets and (ni, "weights") in cubic):
+                why = "a CUBICSPLINE animation sampler"
+            elif any("POSITION" not in tg for tg in targets):
+                why = "a morph target without POSITION"
+            if why:
+                import warnings
+
+                warnings.warn(f"{path}: primitive {pi} of mesh {gm.get('name', 'mesh')!r} has {why}: it is loaded statically")
+                return None
+            pos = accessor(at["POSITION"]).astype(np.float32)
+            if "NORMAL" in at:
+                nrm = accessor(at["NORMAL"]).astype(np.float32)
+            else:  # flat normals from the bind-space geometry, like the static load's
+                fn = np.cross(pos[tris[:, 1]].astype(np.float64) - pos[tris[:, 0]], pos[tris[:, 2]].astype(np.float64) - pos[tris[:, 0]])
+                acc = np.zeros((len(pos), 3), np.float64)
+                for k in range(3):
+                    np.add.at(acc, tris[:, k], fn)
+                nrm = (acc / np.maximum(np.linalg.norm(acc, axis=1, keepdims=True), 1e-20)).astype(np.float32)
+            uv = accessor(at["TEXCOORD_0"]).astype(np.float32) if "TEXCOORD_0" in at else np.zeros((len(pos), 2), np.float32)
+            if skinned:
+                joints = accessor(at["JOINTS_0"]).astype(np.uint16)
+                w = accessor(at["WEIGHTS_0"])
+                weights = w.astype(np.float32) if w.dtype.kind == "f" else w.astype(np.float32) / np.float32(np.iinfo(w.dtype).max)
+                if "inverseBindMatrices" in gs:
+                    ibm = accessor(gs["inverseBindMatrices"]).astype(np.float32).reshape(-1, 4, 4).transpose(0, 2, 1)  # glTF is column-major
+                else:
+                    ibm = np.tile(np.eye(4, dtype=np.float32), (len(jn), 1, 1))
+            else:
+                joints = np.zeros((len(pos), 4), np.uint16)
+                weights = np.tile(np.array([1, 0, 0, 0], np.float32), (len(pos), 1))
+                ibm = np.eye(4, dtype=np.float32)[None]
+            dpos = np.stack([accessor(tg["POSITION"]).astype(np.float32) for tg in targets]) if targets else None
+            dnrm = np.stack([accessor(tg["NORMAL"]).astype(np.float32) for tg in targets]) if targets and all("NORMAL" in tg for tg in targets) else None
+            dw = node.get("weights", gm.get("weights"))
+            return Skin(0, np.concatenate([pos, nrm, uv], 1), joints, weights, jn, ibm, dpos, dnrm, None if dw is None else np.asarray(dw, np.float32))
+
         gl_lights = doc.get("extensions", {}).get("KHR_lights_punctual", {}).get("lights", [])
         lights = []
 
@@ -527,6 +777,11 @@ class GltfMeshLoader:
                                        float(bc[3]) if len(bc) > 3 else 1.0, tex_index(pbr.get("metallicRoughnessTexture")), tex_index(nt),
                                        tex_index(gmtl.get("emissiveTexture")), float(nt.get("scale", 1.0)) if nt else 1.0, tau, ior, thin, att_c, att_d)
                     mb.add(f"{gm.get('name', 'mesh')}.{pi}", pos, nrm, uv, tris, mat, normalize=not keep)
+                    sk = skin_of(ni, node, gm, pi, prim, tris)
+                    if sk is not None:
+                        sk.first_vertex, sk.geometry = mb.nv - len(pos), len(mb.g) - 1
+                        skins.append(sk)
+                        skin_nodes.append(ni)
             for c in node.get("children", []):
                 visit(c, m)
 
@@ -535,6 +790,28 @@ class GltfMeshLoader:
             visit(root, np.eye(4))
         mesh = mb.build()
         mesh.lights = lights_array(lights)
+        if skins:
+            rig = Rig()
+            for i, nd in enumerate(gl_nodes):
+                rn = {k: nd[k] for k in ("name", "translation", "rotation", "scale", "matrix") if k in nd}
+                rn["parent"] = parents[i]
+                rig.nodes.append(rn)
+            for an in doc.get("animations", []):
+                chans = []
+                for ch in an.get("channels", []):
+                    smp, tgt = an["samplers"][ch["sampler"]], ch.get("target", {})
+                    interp = smp.get("interpolation", "LINEAR")
+                    if "node" not in tgt or interp == "CUBICSPLINE":
+                        continue
+                    times = accessor(smp["input"]).astype(np.float32).reshape(-1)
+                    vals = np.asarray(accessor(smp["output"]), np.float32).reshape(len(times), -1)
+                    if tgt["path"] == "weights":
+                        chans += [dict(path="weights", skin=k, interpolation=interp, times=times, values=vals)
+                                  for k, sn in enumerate(skin_nodes) if sn == tgt["node"] and vals.shape[1] == len(skins[k].target_dpos)]
+                    else:
+                        chans.append(dict(path=tgt["path"], node=tgt["node"], interpolation=interp, times=times, values=vals))
+                rig.animations.append(dict(name=an.get("name", ""), channels=chans))
+            mesh.skins, mesh.rig = skins, rig
         # textures -> images (embedded PNG / JPEG, decoded by Pillow); Material.texture_offset indexes doc["textures"]
         for tex in doc.get("textures", []):
             img = doc["images"][tex["source"]]

@@ -770,6 +770,7 @@ int rt3_accel_build(rt3_ctx* c, uint32_t* out_handle) {
     // the vertex / index buffers may have been replaced since rt3_scene_set_geometry checked its ranges against them
     if (int r = revalidate_geometry(c)) return r;
     HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = check_skin_flags(c)) return r;  // a posed position out of range: nothing is built over it
     const auto t_build0 = std::chrono::steady_clock::now();
     // until the rebuild has succeeded: a failed one (the geometry tables reallocated by flatten_world included) must leave
     // RT3_E_STATE behind, not an empty tree or one that points at freed tables
@@ -1012,6 +1013,7 @@ int rt3_accel_refit(rt3_ctx* c, uint32_t* out_handle) {
     if (!two && c->accel.bvh.layout != kLayoutWide64Q) return fail(c, RT3_E_UNSUPPORTED, "accel_refit: default node layout only");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
+    if (int r = check_skin_flags(c)) return r;  // (the structure stays stale: the skin's next valid pose and a refit recover)
     invalidate_accel(c);  // until the refit has succeeded: a failed one leaves boxes of neither the old nor the new vertices
     if (int r = two ? refit_two_level(c) : refit_flat(c)) return r;
     return accel_finish(c, out_handle);

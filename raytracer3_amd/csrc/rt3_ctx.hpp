@@ -120,6 +120,31 @@ struct Placed {
     bool identity;                 // the instance's matrix is exactly the identity
 };
 
+// One skin (rt3_scene_add_skin): the vertex range it writes and k_skin_pose's inputs.  flag_pending: posed since its
+// flag word was last read clear
+struct Skin {
+    uint32_t first = 0, n = 0, n_joints = 0, n_targets = 0;
+    DevBuf<float4> rest, weights, palette;
+    DevBuf<uint2> joints;
+    DevBuf<float> dpos, dnrm;
+    uint64_t bytes = 0;
+    bool flag_pending = false;
+};
+// A pinned host buffer and the event behind the last copy out of it
+struct PaletteSlot {
+    float* host = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool in_flight = false;
+    PaletteSlot() = default;
+    PaletteSlot(const PaletteSlot&) = delete;
+    PaletteSlot& operator=(const PaletteSlot&) = delete;
+    ~PaletteSlot() {
+        if (host) (void)hipHostFree(host);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
 }  // namespace rt3
 
 struct rt3_ctx {
@@ -339,6 +364,16 @@ struct rt3_ctx {
         rt3::DevBuf<uint32_t> d_deformed;
         rt3::DevBuf<uint4> d_chunks;
     } deform;
+    // rt3_scene.hip: skins (rt3_scene_add_skin): what k_skin_pose reads of each, resident on the device; one range flag
+    // word per skin in d_flags (grown in steps, behind a stream synchronise); and the pinned ring a pose's palette is packed into, so that
+    // rt3_scene_pose_skin uploads it stream-ordered from memory the caller cannot change (a slot is reused once its copy has completed)
+    struct Skins {
+        std::vector<rt3::Skin> list;
+        rt3::DevBuf<uint32_t> d_flags;
+        uint32_t flags_cap = 0;
+        rt3::PaletteSlot ring[4];
+        uint32_t ring_next = 0;
+    } skin;
 
     // rt3_api.hip (rt3_set_option)
     struct Opt {
@@ -408,6 +443,9 @@ int sync_textures(rt3_ctx* c);
 // rt3_scene_set_geometry's range checks again, against the vertex and index buffers as they are now; remakes scene.h_geom_span
 int revalidate_geometry(rt3_ctx* c);
 int deform_flags(rt3_ctx* c);
+// the range flags of the skins posed since they were last read clear; the stream must be idle.  RT3_E_INVALID when one
+// is set: rt3_accel_build and rt3_accel_refit refuse, before they change anything, to put boxes around such positions
+int check_skin_flags(rt3_ctx* c);
 inline bool any_cutoff(const rt3_ctx* c) { return !c->scene.h_cutoffs.empty(); }
 inline bool any_mat_tex(const rt3_ctx* c) { return !c->scene.h_mat_tex.empty(); }
 inline bool any_glass(const rt3_ctx* c) { return !c->scene.h_transmission.empty(); }

@@ -656,6 +656,24 @@ void launch_snapshot_positions(hipStream_t st, const float* verts, uint32_t firs
 constexpr uint32_t kDeformChunk = 1024;  // vertices per chunk, at most
 void launch_compare_positions(hipStream_t st, const float* verts, const float4* prev_pos, const uint4* chunks, uint32_t n_chunks, uint32_t* flags);
 
+// Skinning (rt3_skin.hip): one launch of k_skin_pose poses one skin.  Every array is the skin's own, indexed by the
+// vertex within the skin: rest 2 x float4 per vertex (the Vertex layout), joints 4 x uint16, weights float4, dpos / dnrm n_targets x n x 3
+// floats (tight; dnrm null: normals are not morphed), palette 3 x float4 per joint (pack3x4).  out: the skin's first record in the vertex
+// buffer.  flag: the skin's range word.  The caller has checked every joint index against the palette and the range against the buffer.
+constexpr uint32_t kSkinMaxTargets = 8;  // == RT3_SKIN_MAX_TARGETS
+struct SkinLaunch {
+    const float4* rest;
+    const uint2* joints;
+    const float4* weights;
+    const float4* palette;
+    const float *dpos, *dnrm;
+    float4* out;
+    uint32_t* flag;
+    uint32_t n, n_targets;
+    float a[kSkinMaxTargets];  // the target weights
+};
+void launch_skin_pose(hipStream_t st, const SkinLaunch& L);
+
 // "adaptive" pass (rt3_adaptive.hip).  Scratch, carved from the context's grow-only adaptive buffer: the per-pixel
 // state in window space (index y * W + x, so that compacting the list moves nothing), two pixel lists that take turns (a list is the words
 // x | y << 16 and, in the same order, k_pixbn's {xy, blue-noise word} records), and the compaction's per-block counts and result.

@@ -115,6 +115,20 @@ int deform_flags(rt3_ctx* c) {
     motion_tables_stale(c);
     return RT3_OK;
 }
+int check_skin_flags(rt3_ctx* c) {
+    auto& list = c->skin.list;
+    if (std::none_of(list.begin(), list.end(), [](const Skin& s) { return s.flag_pending; })) return RT3_OK;
+    std::vector<uint32_t> words(list.size());
+    HIPC(c, hipMemcpy(words.data(), c->skin.d_flags.get(), words.size() * 4, hipMemcpyDeviceToHost));
+    size_t bad = list.size();
+    for (size_t s = 0; s < list.size(); s++) {
+        if (!list[s].flag_pending) continue;
+        if (words[s] == 0u) list[s].flag_pending = false;  // (a set flag stays pending: only the skin's next pose clears the word)
+        else if (bad == list.size()) bad = s;
+    }
+    if (bad != list.size()) return fail(c, RT3_E_INVALID, "skin " + std::to_string(bad) + ": a posed position is not finite (or beyond 1e18)");
+    return RT3_OK;
+}
 
 }  // namespace rt3
 
@@ -155,10 +169,20 @@ static int check_positions(rt3_ctx* c, const float* v, uint32_t first, uint32_t 
             if (!(std::fabs(v[8 * i + k]) <= 1.0e18f)) return fail(c, RT3_E_INVALID, "vertex " + std::to_string(first + i) + ": position is not finite (or beyond 1e18)");
     return RT3_OK;
 }
+// every skin goes; a launch in flight may still read them, so the stream is drained first -- only when there are any
+static int forget_skins(rt3_ctx* c) {
+    if (c->skin.list.empty()) return RT3_OK;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    c->skin.list.clear();
+    for (PaletteSlot& s : c->skin.ring) s.in_flight = false;
+    return RT3_OK;
+}
 int rt3_scene_set_vertices(rt3_ctx* c, const float* v, uint32_t n) {
     if (!c || (!v && n)) return fail(c, RT3_E_INVALID, "vertices NULL");
     if (int r = check_positions(c, v, 0u, n)) return r;
     HIPC(c, hipSetDevice(c->device));
+    if (int r = forget_skins(c)) return r;  // the buffer they index is replaced
     if (int r = dev_alloc(c, c->scene.d_verts, (size_t)n * 8)) return r;
     if (n) HIPC(c, hipMemcpy(c->scene.d_verts.get(), v, (size_t)n * 32, hipMemcpyHostToDevice));
     c->scene.n_verts = n;
@@ -621,6 +645,152 @@ int rt3_scene_set_textured_emitters(rt3_ctx* c, int on) {
 int rt3_scene_get_textured_emitters(rt3_ctx* c, int* on) {
     if (!c || !on) return fail(c, RT3_E_INVALID, "textured emitters: NULL");
     *on = c->scene.textured_emitters ? 1 : 0;
+    return RT3_OK;
+}
+
+// ---- skins: the rest pose lives on the device; a pose sends the joint palette and the target weights
+int rt3_scene_add_skin(rt3_ctx* c, const rt3_skin_desc* d, uint32_t* out_skin) {
+    if (!c || !d) return fail(c, RT3_E_INVALID, "add_skin: NULL");
+    if (!c->scene.d_verts) return fail(c, RT3_E_STATE, "add_skin: no vertices (rt3_scene_set_vertices)");
+    auto bad = [&](const std::string& what) { return fail(c, RT3_E_INVALID, "add_skin: " + what); };
+    const uint32_t first = d->first_vertex, n = d->n_vertices, nt = d->n_targets;
+    if (n == 0 || (uint64_t)first + n > c->scene.n_verts) return bad("[first_vertex, first_vertex + n_vertices) is empty or exceeds the vertex buffer");
+    for (size_t s = 0; s < c->skin.list.size(); s++)
+        if (first < c->skin.list[s].first + c->skin.list[s].n && c->skin.list[s].first < first + n) return bad("the range overlaps skin " + std::to_string(s) + "'s");
+    if (d->n_joints < 1u || d->n_joints > 65536u) return bad("n_joints must lie in 1 .. 65536");
+    if (nt > RT3_SKIN_MAX_TARGETS) return bad("n_targets exceeds RT3_SKIN_MAX_TARGETS");
+    if (!d->joints || !d->weights) return bad("joints or weights NULL");
+    if ((d->target_dpos == nullptr) != (nt == 0u)) return bad("target_dpos must be NULL exactly when n_targets is 0");
+    if (d->target_dnrm && nt == 0u) return bad("target_dnrm without targets");
+    for (size_t i = 0; i < 4 * (size_t)n; i++) {
+        if (d->joints[i] >= d->n_joints) return bad("vertex " + std::to_string(i / 4) + ": joint index " + std::to_string(d->joints[i]) + " is not below n_joints");
+        if (!(d->weights[i] >= 0.0f && d->weights[i] <= kFloatMax)) return bad("vertex " + std::to_string(i / 4) + ": a weight is negative or not finite");
+    }
+    if (d->rest)
+        if (int r = check_positions(c, d->rest, 0u, n)) return r;  // (the message counts from the skin's first vertex)
+    for (const float* delta : {d->target_dpos, d->target_dnrm})
+        for (size_t i = 0; delta && i < 3 * (size_t)nt * n; i++)
+            if (!(std::fabs(delta[i]) <= kFloatMax)) return bad("target " + std::to_string(i / (3 * (size_t)n)) + ": a delta is not finite");
+    HIPC(c, hipSetDevice(c->device));
+    Skin s;
+    s.first = first;
+    s.n = n;
+    s.n_joints = d->n_joints;
+    s.n_targets = nt;
+    const size_t delta_bytes = 12 * (size_t)nt * n;
+    HIPC(c, s.rest.alloc_bytes(32 * (size_t)n));
+    HIPC(c, s.joints.alloc_bytes(8 * (size_t)n));
+    HIPC(c, s.weights.alloc_bytes(16 * (size_t)n));
+    HIPC(c, s.palette.alloc_bytes(48 * (size_t)s.n_joints));
+    if (nt) HIPC(c, s.dpos.alloc_bytes(delta_bytes));
+    if (d->target_dnrm) HIPC(c, s.dnrm.alloc_bytes(delta_bytes));
+    s.bytes = 32ull * n + 8ull * n + 16ull * n + 48ull * s.n_joints + (nt ? delta_bytes : 0) + (d->target_dnrm ? delta_bytes : 0) + 4ull;
+    const size_t index = c->skin.list.size();
+    if (index + 1 > c->skin.flags_cap) {  // more flag words: a launch in flight may hold the old ones
+        const uint32_t cap = c->skin.flags_cap + 64u;
+        DevBuf<uint32_t> grown;
+        HIPC(c, hipStreamSynchronize(c->stream));
+        HIPC(c, grown.alloc_bytes((size_t)cap * 4));
+        HIPC(c, hipMemset(grown.get(), 0, (size_t)cap * 4));
+        if (c->skin.flags_cap) HIPC(c, hipMemcpy(grown.get(), c->skin.d_flags.get(), (size_t)c->skin.flags_cap * 4, hipMemcpyDeviceToDevice));
+        c->skin.d_flags = std::move(grown);
+        c->skin.flags_cap = cap;
+    }
+    // the arrays go into allocations nothing reads yet; the buffer's own contents (rest NULL) are copied behind the work ahead in the stream
+    if (d->rest) HIPC(c, hipMemcpy(s.rest.get(), d->rest, 32 * (size_t)n, hipMemcpyHostToDevice));
+    else HIPC(c, hipMemcpyAsync(s.rest.get(), c->scene.d_verts.get() + 8 * (size_t)first, 32 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    HIPC(c, hipMemcpy(s.joints.get(), d->joints, 8 * (size_t)n, hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(s.weights.get(), d->weights, 16 * (size_t)n, hipMemcpyHostToDevice));
+    if (nt) HIPC(c, hipMemcpy(s.dpos.get(), d->target_dpos, delta_bytes, hipMemcpyHostToDevice));
+    if (d->target_dnrm) HIPC(c, hipMemcpy(s.dnrm.get(), d->target_dnrm, delta_bytes, hipMemcpyHostToDevice));
+    HIPC(c, hipMemsetAsync(c->skin.d_flags.get() + index, 0, 4, c->stream));  // (a cleared skin may have left its word set)
+    c->skin.list.push_back(std::move(s));
+    if (out_skin) *out_skin = (uint32_t)index;
+    return RT3_OK;
+}
+int rt3_scene_clear_skins(rt3_ctx* c) {
+    if (!c) return fail(c, RT3_E_INVALID, "context NULL");
+    return forget_skins(c);
+}
+int rt3_scene_pose_skin(rt3_ctx* c, uint32_t skin, const float* joint_matrices, const float* target_weights) {
+    if (!c) return fail(c, RT3_E_INVALID, "context NULL");
+    if (skin >= c->skin.list.size()) return fail(c, RT3_E_INVALID, "pose_skin: no skin " + std::to_string(skin) + " (rt3_scene_add_skin)");
+    Skin& s = c->skin.list[skin];
+    if (!joint_matrices || (!target_weights && s.n_targets)) return fail(c, RT3_E_INVALID, "pose_skin: joint matrices or target weights NULL");
+    // an instance's checks without the magnitude bound: what a large matrix makes of the positions is the range flag's to catch, on the device
+    for (uint32_t i = 0; i < s.n_joints; i++) {
+        const float* m = joint_matrices + 16 * (size_t)i;
+        for (int k = 0; k < 16; k++)
+            if (!(std::fabs(m[k]) <= kFloatMax)) return fail(c, RT3_E_INVALID, "pose_skin: joint matrix " + std::to_string(i) + " is not finite");
+        if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f)
+            return fail(c, RT3_E_INVALID, "pose_skin: joint matrix " + std::to_string(i) + ": the last row must be (0, 0, 0, 1), as for an instance's matrix");
+    }
+    SkinLaunch L = {};
+    for (uint32_t t = 0; t < s.n_targets; t++) {
+        if (!(std::fabs(target_weights[t]) <= kFloatMax)) return fail(c, RT3_E_INVALID, "pose_skin: target weight " + std::to_string(t) + " is not finite");
+        L.a[t] = target_weights[t];
+    }
+    HIPC(c, hipSetDevice(c->device));
+    // the palette, packed 3 x 4, into the ring's next pinned slot: the caller's array is free when this call returns, and the copy is
+    // ordered behind the frames ahead of it in the stream.  No hipStreamSynchronize: only a slot whose copy of four poses ago still runs waits
+    PaletteSlot& slot = c->skin.ring[c->skin.ring_next];
+    c->skin.ring_next = (c->skin.ring_next + 1u) % 4u;
+    if (slot.in_flight) HIPC(c, hipEventSynchronize(slot.done));
+    slot.in_flight = false;
+    const size_t bytes = 48 * (size_t)s.n_joints;
+    if (slot.cap < bytes) {
+        if (slot.host) (void)hipHostFree(slot.host);
+        slot.host = nullptr;
+        slot.cap = 0;
+        HIPC(c, hipHostMalloc((void**)&slot.host, bytes, hipHostMallocDefault));
+        slot.cap = bytes;
+    }
+    if (!slot.done) HIPC(c, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    for (uint32_t i = 0; i < s.n_joints; i++) pack3x4(joint_matrices + 16 * (size_t)i, slot.host + 12 * (size_t)i);
+    HIPC(c, hipMemcpyAsync(s.palette.get(), slot.host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipEventRecord(slot.done, c->stream));
+    slot.in_flight = true;
+    if (s.flag_pending) HIPC(c, hipMemsetAsync(c->skin.d_flags.get() + skin, 0, 4, c->stream));  // (not pending: the word is known to be 0)
+    L.rest = s.rest.get();
+    L.joints = s.joints.get();
+    L.weights = s.weights.get();
+    L.palette = s.palette.get();
+    L.dpos = s.dpos.get();
+    L.dnrm = s.dnrm.get();
+    L.out = reinterpret_cast<float4*>(c->scene.d_verts.get() + 8 * (size_t)s.first);
+    L.flag = c->skin.d_flags.get() + skin;
+    L.n = s.n;
+    L.n_targets = s.n_targets;
+    {
+        ScopedTimer t(c, CAT_OTHER);
+        launch_skin_pose(c->stream, L);
+    }
+    HIPC(c, hipGetLastError());
+    s.flag_pending = true;
+    c->scene.content_gen++;  // what rt3_scene_update_vertices does to the state
+    mark_accel_stale(c);
+    if (c->deform.snapshot) {
+        add_dirty_range(c->deform.ranges, s.first, s.first + s.n);
+        c->deform.dirty = true;
+    }
+    return RT3_OK;
+}
+int rt3_skin_info(rt3_ctx* c, uint32_t* n_skins, uint64_t* device_bytes) {
+    if (!c) return fail(c, RT3_E_INVALID, "context NULL");
+    uint64_t total = 0;
+    for (const Skin& s : c->skin.list) total += s.bytes;
+    if (n_skins) *n_skins = (uint32_t)c->skin.list.size();
+    if (device_bytes) *device_bytes = total;
+    return RT3_OK;
+}
+int rt3_scene_download_vertices(rt3_ctx* c, float* out, uint32_t first, uint32_t n) {
+    if (!c || (!out && n)) return fail(c, RT3_E_INVALID, "download_vertices: NULL");
+    if (!c->scene.d_verts) return fail(c, RT3_E_STATE, "download_vertices: no vertices (rt3_scene_set_vertices)");
+    if ((uint64_t)first + n > c->scene.n_verts) return fail(c, RT3_E_INVALID, "download_vertices: [first, first + n) exceeds the vertex buffer");
+    if (n == 0) return RT3_OK;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));  // a pose may still be writing
+    HIPC(c, hipMemcpy(out, c->scene.d_verts.get() + 8 * (size_t)first, (size_t)n * 32, hipMemcpyDeviceToHost));
     return RT3_OK;
 }
 

@@ -141,6 +141,19 @@ class Context {
     void forget_prev_vertices() const { check(rt3_scene_forget_prev_vertices(ctx_), "rt3_scene_forget_prev_vertices"); }
     void deformed_geometries(uint8_t* flags, uint32_t n) const { check(rt3_scene_deformed_geometries(ctx_, flags, n), "rt3_scene_deformed_geometries"); }
     void set_denoise_variance_input(uint32_t moments_image) const { check(rt3_denoise_set_variance_input(ctx_, moments_image), "rt3_denoise_set_variance_input"); }
+    // skins: the rest pose stays on the device, a pose sends the joint palette (n_joints x 16, column-major) and the
+    // target weights, stream-ordered; rt3_accel_refit follows, as after rt3_scene_update_vertices
+    uint32_t add_skin(const rt3_skin_desc& desc) const {
+        uint32_t skin = 0;
+        check(rt3_scene_add_skin(ctx_, &desc, &skin), "rt3_scene_add_skin");
+        return skin;
+    }
+    void clear_skins() const { check(rt3_scene_clear_skins(ctx_), "rt3_scene_clear_skins"); }
+    void pose_skin(uint32_t skin, const float* joint_matrices, const float* target_weights = nullptr) const {
+        check(rt3_scene_pose_skin(ctx_, skin, joint_matrices, target_weights), "rt3_scene_pose_skin");
+    }
+    void skin_info(uint32_t* n_skins, uint64_t* device_bytes) const { check(rt3_skin_info(ctx_, n_skins, device_bytes), "rt3_skin_info"); }
+    void download_vertices(float* out, uint32_t first, uint32_t n) const { check(rt3_scene_download_vertices(ctx_, out, first, n), "rt3_scene_download_vertices"); }
 
    private:
     rt3_ctx* ctx_ = nullptr;

@@ -168,6 +168,7 @@ class Context:
         g = np.ascontiguousarray(mesh.geometries)
         pc = np.ascontiguousarray(mesh.prim_counts, np.uint32)
         self.check(self.lib.rt3_scene_set_vertices(self.h, v.ctypes.data, len(v)))
+        self.__dict__.pop("_skin_shapes", None)  # (rt3_scene_set_vertices forgets the skins)
         self.check(self.lib.rt3_scene_set_indices(self.h, i.ctypes.data, len(i)))
         self.check(self.lib.rt3_scene_set_geometry(self.h, g.ctypes.data, pc.ctypes.data, len(g)))
         cut = getattr(mesh, "alpha_cutoffs", None)
@@ -405,6 +406,52 @@ class Context:
         flags = np.zeros(int(n), np.uint8)
         self.check(self.lib.rt3_scene_deformed_geometries(self.h, flags.ctypes.data, len(flags)))
         return flags.astype(bool)
+
+    # ---- skins
+    def add_skin(self, first_vertex, joints, weights, n_joints, rest=None, target_dpos=None, target_dnrm=None):
+        """a skin over vertices [first_vertex, first_vertex + len(joints)) (rt3_scene_add_skin): joints (n, 4) uint16, weights (n, 4), rest
+        (n, 8) Vertex rows or None = the range's current contents, target_dpos / target_dnrm (n_targets, n, 3) or None.  Returns its index."""
+        j = np.ascontiguousarray(joints, np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+        n = len(j)
+        r = None if rest is None else np.ascontiguousarray(rest, np.float32).reshape(-1, 8)
+        dp = None if target_dpos is None or len(target_dpos) == 0 else np.ascontiguousarray(target_dpos, np.float32).reshape(-1, n, 3)
+        dn = None if target_dnrm is None or len(target_dnrm) == 0 else np.ascontiguousarray(target_dnrm, np.float32).reshape(-1, n, 3)
+        if len(w) != n or (r is not None and len(r) != n) or (dn is not None and (dp is None or len(dn) != len(dp))):
+            raise ValueError("add_skin: the arrays disagree about the vertex or target count")
+        d = L.SkinDesc(int(first_vertex), n, int(n_joints), 0 if dp is None else len(dp), None if r is None else r.ctypes.data, j.ctypes.data, w.ctypes.data,
+                       None if dp is None else dp.ctypes.data, None if dn is None else dn.ctypes.data)
+        out = C.c_uint32()
+        self.check(self.lib.rt3_scene_add_skin(self.h, C.byref(d), C.byref(out)))
+        self.__dict__.setdefault("_skin_shapes", {})[out.value] = (int(n_joints), d.n_targets)  # what pose_skin's arrays must hold
+        return out.value
+
+    def clear_skins(self):
+        """forget every skin (rt3_scene_clear_skins); the vertex buffer keeps what the last pose wrote"""
+        self.check(self.lib.rt3_scene_clear_skins(self.h))
+        self.__dict__.pop("_skin_shapes", None)
+
+    def pose_skin(self, skin, palette, target_weights=None):
+        """pose skin `skin` (rt3_scene_pose_skin): palette (n_joints, 4, 4), matrices that act on column vectors like set_instances', and the
+        target weights.  Stream-ordered, no wait; a built structure is stale until refit_accel()."""
+        m = np.ascontiguousarray(np.asarray(palette, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))  # column-major, like glam's Mat4
+        a = None if target_weights is None or len(target_weights) == 0 else np.ascontiguousarray(target_weights, np.float32).reshape(-1)
+        shape = self.__dict__.get("_skin_shapes", {}).get(int(skin))
+        if shape is not None and (len(m), 0 if a is None else len(a)) != shape:  # (the library reads as many as the skin has)
+            raise ValueError(f"pose_skin: skin {skin} has {shape[0]} joints and {shape[1]} targets")
+        self.check(self.lib.rt3_scene_pose_skin(self.h, int(skin), m.ctypes.data, None if a is None else a.ctypes.data))
+
+    def skin_info(self):
+        """(number of skins, device bytes they hold) (rt3_skin_info)"""
+        n, b = C.c_uint32(), C.c_uint64()
+        self.check(self.lib.rt3_skin_info(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def download_vertices(self, first, n):
+        """rows [first, first + n) of the vertex buffer as the device holds them, (n, 8) float32 (rt3_scene_download_vertices); synchronises"""
+        out = np.zeros((int(n), 8), np.float32)
+        self.check(self.lib.rt3_scene_download_vertices(self.h, out.ctypes.data if n else None, int(first), int(n)))
+        return out
 
     def set_sky(self, rgb):
         s = np.ascontiguousarray(rgb, np.float32)

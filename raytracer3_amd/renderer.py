@@ -314,6 +314,10 @@ class PathTracer:
             self.ctx.set_bluenoise(bluenoise)
         self.ctx.build_accel()
         self._scene_set = True
+        # skins: the mesh's, in its order; the vertex buffer holds the static load until pose()
+        self._posed_mesh = mesh if getattr(mesh, "skins", None) else None
+        for s in getattr(mesh, "skins", None) or []:
+            self.ctx.add_skin(s.first_vertex, s.joints, s.weights, len(s.joint_nodes), s.rest, s.target_dpos, s.target_dnrm)
         tr = getattr(mesh, "transmission", None)
         glass = tr is not None and len(tr) and bool(np.any(tr["transmission"] > 0))
         if glass and not self.ctx.get_lens()[1]:
@@ -457,6 +461,19 @@ class PathTracer:
         camera samples (set_guide(temporal=True)), writes their mean previous position from the same snapshot (section 4w)."""
         self._history.vertices_updated()
         self.ctx.update_vertices(vertices, first)
+        self.ctx.refit_accel()
+
+    def pose(self, t, animation=0):
+        """the scene's skins at time `t` of animation `animation` (Mesh.pose): every skin is posed on the device (ctx.pose_skin, DESIGN.md
+        section 4z) and the acceleration structure refitted once.  For the temporal history this is update_vertices(): the snapshot is taken
+        first, and the next temporal frame follows the skinned geometries."""
+        mesh = getattr(self, "_posed_mesh", None)
+        if mesh is None:
+            raise ValueError("pose: the scene has no skins (Mesh.skins)")
+        poses = mesh.pose(t, animation)
+        self._history.vertices_updated()
+        for k, (palette, weights) in enumerate(poses):
+            self.ctx.pose_skin(k, palette, weights)
         self.ctx.refit_accel()
 
     def make_gconst(self, camera: Camera, samples, bounces=4, frame=0, blendfactor=1.0, flags=DEFAULT_FLAGS) -> L.GConst:

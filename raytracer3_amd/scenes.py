@@ -10,6 +10,7 @@
                     that image.  Informational: Cycles is not this estimator and the display transforms differ.
 * `glass_cornell()` the Cornell box with a solid glass sphere and a thin-walled tinted pane.
 * `amber_cornell()` the Cornell box with absorbing glass: an amber block and two green spheres of two sizes.
+* `skinned_arm()`   the open Cornell room with a three-joint skinned tube, one morph target and a bend animation.
 * `sky(w, h)`       equirect RGB32F gradient sky + 0.5 degree sun disc (peak radiance 5e4).
 All surfaces carry normals facing the side they are meant to be seen from.
 """
@@ -553,6 +554,70 @@ def neon_room() -> Mesh:
     mb.add("sign", pos, nrm, uv, tris, Material((0.1, 0.1, 0.1), emission=(8.0, 2.0, 6.0), emissive_texture=0))
     mesh = mb.build()
     mesh.textures = [neon_sign_texture()]
+    return mesh
+
+
+SKINNED_ARM_CAMERA = dict(position=(0.0137, 1.0071, 3.4), direction=(-0.08, -0.0033, -1.0), fov_deg=48.0)
+# (the foot's coordinates and the segment length are binary fractions: the bind pose's palette is then the exact identity)
+SKINNED_ARM_BASE, SKINNED_ARM_SEGMENT, SKINNED_ARM_RADIUS = (0.0625, 0.0, 0.625), 0.5, 0.17
+
+
+def skinned_arm() -> Mesh:
+    """The Cornell room without its left and front walls and, in it, an arm: a tube of three segments of 0.5 m standing
+    on the floor, skinned to a chain of three joints (the root at its foot, one at each later segment's start) with weights that pass
+    smoothly from a segment to the next, and one morph target, a bulge around the first joint above the root.  One animation of two seconds:
+    the two upper joints bend about z and straighten again while the bulge swells and goes.  Mesh.vertices is the rest pose."""
+    from .assets import Rig, Skin
+
+    white, green = Material((0.73, 0.73, 0.73)), Material((0.12, 0.45, 0.15))
+    light = Material((0.78, 0.78, 0.78), emission=(1.4, 1.2, 0.9))
+    mb = MeshBuilder()
+    n = 4
+    mb.add("floor", *_grid([-1, 0, -1], [0, 0, 5], [2, 0, 0], n, n), white)
+    mb.add("ceiling", *_grid([-1, 2, -1], [2, 0, 0], [0, 0, 5], n, n), white)
+    mb.add("back", *_grid([-1, 0, -1], [2, 0, 0], [0, 2, 0], n, n), white)
+    mb.add("right", *_grid([1, 0, -1], [0, 0, 5], [0, 2, 0], n, n), green)
+    mb.add("panel", *_grid([-0.35, 1.995, -0.35], [0.7, 0, 0], [0, 0, 0.7], 2, 2), light)
+    base, seg, radius = np.array(SKINNED_ARM_BASE), SKINNED_ARM_SEGMENT, SKINNED_ARM_RADIUS
+    nseg, nring = 16, 24
+    th, y = np.linspace(0, 2 * np.pi, nseg + 1), np.linspace(0, 1, nring + 1)
+    T, Y = np.meshgrid(th, y, indexing="xy")
+    H = 3.0 * seg * Y
+    radial = np.stack([np.cos(T), np.zeros_like(T), np.sin(T)], -1)
+    pos = (base + radius * radial + np.stack([np.zeros_like(H), H, np.zeros_like(H)], -1)).reshape(-1, 3)
+    i = np.arange(nseg)[None, :] + (nseg + 1) * np.arange(nring)[:, None]
+    a, b, c, d = i, i + 1, i + nseg + 2, i + nseg + 1
+    tris = np.stack([np.stack([a, c, b], -1), np.stack([a, d, c], -1)], -2).reshape(-1, 3)  # outward
+    first = mb.nv
+    mb.add("arm", pos, radial.reshape(-1, 3), np.stack([T / (2 * np.pi), Y], -1).reshape(-1, 2), tris, Material((0.8, 0.55, 0.4)))
+    mesh = mb.build()
+    h = H.reshape(-1)
+
+    def smooth(x):
+        x = np.clip(x, 0.0, 1.0)
+        return x * x * (3.0 - 2.0 * x)
+
+    t1, t2 = smooth((h - 0.7 * seg) / (0.6 * seg)), smooth((h - 1.7 * seg) / (0.6 * seg))
+    weights = np.stack([1.0 - t1, t1 - t2, t2, np.zeros_like(h)], 1).astype(np.float32)
+    joints = np.tile(np.array([0, 1, 2, 0], np.uint16), (len(h), 1))
+    bulge = (0.09 * np.exp(-(((h - seg) / (0.45 * seg)) ** 2)))[:, None] * radial.reshape(-1, 3)
+    ibm = np.tile(np.eye(4), (3, 1, 1))
+    for k in range(3):
+        ibm[k, :3, 3] = -(base + [0.0, k * seg, 0.0])
+    mesh.skins = [Skin(first, mesh.vertices[first:].copy(), joints, weights, [0, 1, 2], ibm, bulge[None], None, np.zeros(1, np.float32), len(mesh.geometries) - 1)]
+
+    def about_z(deg):
+        r = np.radians(deg) / 2.0
+        return [0.0, 0.0, float(np.sin(r)), float(np.cos(r))]
+
+    times = np.array([0.0, 1.0, 2.0], np.float32)
+    nodes = [dict(name="shoulder", translation=[float(x) for x in base], parent=-1),
+             dict(name="elbow", translation=[0.0, seg, 0.0], rotation=about_z(0.0), parent=0),
+             dict(name="wrist", translation=[0.0, seg, 0.0], rotation=about_z(0.0), parent=1)]
+    channels = [dict(path="rotation", node=1, interpolation="LINEAR", times=times, values=np.array([about_z(0), about_z(50), about_z(0)], np.float32)),
+                dict(path="rotation", node=2, interpolation="LINEAR", times=times, values=np.array([about_z(0), about_z(-70), about_z(0)], np.float32)),
+                dict(path="weights", skin=0, interpolation="LINEAR", times=times, values=np.array([[0.0], [1.0], [0.0]], np.float32))]
+    mesh.rig = Rig(nodes, [dict(name="bend", channels=channels)])
     return mesh
 
 

@@ -25,6 +25,8 @@
                          (--temporal with --guide: the "temporal" pass takes its surface records from the guide images too, section 4v)
   python tools/render.py --scene material_cornell --size 960x540 --spp 64 --flags 47 --textured-emitters --out material_cornell_nee.png
                          (flags 47 = the full estimator + RT3_F_NEE_EMISSIVE: the panel's lamps are sampled directly)
+  python tools/render.py --scene skinned_arm --size 960x540 --spp 64 --time 1.0 --out arm_bent.png
+                         (--time T [--animation N]: the scene's skins posed on the device at T seconds; a rigged --glb works too)
   python tools/render.py --glb resources/sponza_scene.glb --exr resources/skybox2.exr ...               (if the real assets are dropped in)
 """
 import argparse
@@ -42,7 +44,10 @@ sys.path.insert(0, str(ROOT))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell", "frosted_cornell", "neon_room"])
+    ap.add_argument("--scene", default="atrium", choices=["atrium", "cornell", "cornell_ref", "cutout_cornell", "material_cornell", "lit_room", "glass_cornell", "sunlit_room", "amber_cornell", "frosted_cornell", "neon_room", "skinned_arm"])
+    ap.add_argument("--time", type=float, default=None, metavar="T",
+                    help="pose the scene's skins at T seconds of --animation before rendering (PathTracer.pose, DESIGN.md section 4z); try --scene skinned_arm --time 1")
+    ap.add_argument("--animation", type=int, default=0, metavar="N", help="with --time: which of the file's animations")
     ap.add_argument("--glb", default=None)
     ap.add_argument("--exr", default=None)
     ap.add_argument("--detail", type=float, default=1.0)
@@ -110,6 +115,8 @@ def main():
         mesh, cam_kw = scenes.sunlit_room(), scenes.SUNLIT_ROOM_CAMERA
     elif args.scene == "neon_room":  # a room lit only by a sign whose emissive texture is mostly black; try --textured-emitters
         mesh, cam_kw = scenes.neon_room(), scenes.NEON_ROOM_CAMERA
+    elif args.scene == "skinned_arm":  # a three-joint skinned tube with a morph target and a bend animation; try --time 1
+        mesh, cam_kw = scenes.skinned_arm(), scenes.SKINNED_ARM_CAMERA
     elif args.scene == "cornell_ref":
         mesh, cam_kw = scenes.cornell_ref(), scenes.CORNELL_REF_CAMERA
     else:
@@ -125,6 +132,10 @@ def main():
     pt.set_rough_transmission(args.rough_glass)
     pt.set_textured_emitters(args.textured_emitters)
     pt.set_scene(mesh, sky, assets.load_bluenoise())
+    if args.time is not None:
+        if not mesh.skins:
+            ap.error("--time poses skins: this scene has none (Mesh.skins)")
+        pt.pose(args.time, args.animation)
     if args.denoise:
         pt.ctx.set_denoise_params(iterations=args.denoise_iterations)
     if args.aa or args.aperture > 0.0:
